@@ -12,6 +12,11 @@ already resident in HBM.
           int32 H + int32 P do not fit two GPUs, so every N > 1 point uses int32 H + int8 P (5 B/cell, 344 GB in total:
           172 GB per GPU at N = 2); `config.workload` says so.  (--mode replicas keeps the old one-pair-per-rank run.)
 
+A plain run sets up, warms up, times --steps steps and prints the line.  --full adds what takes runs of its own: the fills into a
+plain first allocation and into a foreign pair, the contiguous-fill bandwidth, the in-kernel chain stamps, the clocks and the CPU
+baselines.  --dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy (float64; a fixed, seeded sample of
+the matrices).
+
 Prints ONE JSON line on rank 0.
 """
 import argparse
@@ -184,6 +189,43 @@ def batch_valu_per_step(label):
         return None, None
 
 
+DUMP_SAMPLES = 1 << 20          # cells of each matrix written by --dump-outputs (8 MiB each as float64)
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def _sample_index(n, seed=20240601):
+    """A fixed, seeded, sorted sample of DUMP_SAMPLES flat indices into n cells (all of them when n is small)."""
+    import numpy as np
+    if n <= DUMP_SAMPLES:
+        return np.arange(n, dtype=np.int64)
+    return np.unique(np.random.default_rng(seed).integers(0, n, DUMP_SAMPLES, dtype=np.int64))
+
+
+def _gather(torch, X, idx):
+    """X.flatten()[idx] gathered on the device, as float64 on the host (exact for int8/int32/int64 scores below 2^53)."""
+    i = torch.from_numpy(idx).to(X.device)
+    return X.reshape(-1).index_select(0, i).cpu().numpy().astype("float64")
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: every array as <path>/<name>.npy in float64, at most DUMP_LIMIT_BYTES in all."""
+    import numpy as np
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float64) for k, v in arrays.items()}
+    total = sum(v.nbytes for v in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise ValueError(f"--dump-outputs: {total} bytes exceed the limit of {DUMP_LIMIT_BYTES}")
+    os.makedirs(path, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), v)
+
+
+def _matrix_outputs(torch, prefix, X, idx):
+    """A (rows+1, cols+1) matrix as its sampled cells, its bottom row and its right-hand column."""
+    return {f"{prefix}_sample": _gather(torch, X, idx),
+            f"{prefix}_last_row": X[-1, :].cpu().numpy().astype("float64"),
+            f"{prefix}_last_col": X[:, -1].cpu().numpy().astype("float64")}
+
+
 def run_pair(args, sw, eng, torch, dist, rank, world, local):
     cols, rows = args.cols, args.rows
     a, b = sw.generate(cols, rows, 1 + rank)          # reference generator; rank r uses seed 1+r (replicas mode)
@@ -212,7 +254,7 @@ def run_pair(args, sw, eng, torch, dist, rank, world, local):
         dt = time.perf_counter() - t0
         return dt, [e0.elapsed_time(e1) for e0, e1 in evs]
 
-    clocks0 = _clocks()
+    clocks0 = _clocks() if args.full else None
     t_alloc = 0.0
     if args.placement_trials == 1:
         # a plain first allocation: what a caller of sw_device_malloc gets
@@ -238,35 +280,41 @@ def run_pair(args, sw, eng, torch, dist, rank, world, local):
             eng.fill_into(out, d_a, d_b)
         torch.cuda.synchronize()
         nheat += 20
-    f0, f1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    out.H.fill_(0); torch.cuda.synchronize()
-    f0.record()
-    for _ in range(5):
-        out.H.fill_(0)
-    f1.record(); torch.cuda.synchronize()
-    fill_gbs = 5 * out.H.numel() * out.H.element_size() / (f0.elapsed_time(f1) * 1e-3) / 1e9
-    # the same fill into plain pairs (a handful of launches each): `value_first_allocation` -- two back-to-back allocations through the C-ABI
-    # (sw_alloc_outputs with trials = 1: no search, but the library probes the pair once and picks the strip geometry by the class it
-    # finds) -- and `value_foreign_pair` -- two torch allocations the library knows nothing about
-    if args.placement_trials == 1:
-        first = out
-    else:
-        first, _ = eng.alloc_outputs(d_a, d_b, cols, rows, h_dtype, p_dtype, trials=1)
-    first_ratio = eng.get_option("last_placement_ratio_x1000") / 1000 if first is not out else None
-    dt_first, ms_first = timed(first, max(3, args.steps // 4), 4)
-    value_first = world * len(ms_first) * cols * rows / dt_first / 1e9
-    first_strips = int(eng.get_option("last_strips2")) or eng.get_option("last_strips")
-    if first is not out:
-        first.free()
-    foreign = eng.alloc(cols, rows, h_dtype, p_dtype)
-    dt_foreign, ms_foreign = timed(foreign, max(3, args.steps // 4), 4)
-    value_foreign = world * len(ms_foreign) * cols * rows / dt_foreign / 1e9
-    del foreign
-    torch.cuda.empty_cache()
+    if args.full:
+        f0, f1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        out.H.fill_(0); torch.cuda.synchronize()
+        f0.record()
+        for _ in range(5):
+            out.H.fill_(0)
+        f1.record(); torch.cuda.synchronize()
+        fill_gbs = 5 * out.H.numel() * out.H.element_size() / (f0.elapsed_time(f1) * 1e-3) / 1e9
+        # the same fill into plain pairs (a handful of launches each): `value_first_allocation` -- two back-to-back allocations through the C-ABI
+        # (sw_alloc_outputs with trials = 1: no search, but the library probes the pair once and picks the strip geometry by the class it
+        # finds) -- and `value_foreign_pair` -- two torch allocations the library knows nothing about
+        if args.placement_trials == 1:
+            first = out
+        else:
+            first, _ = eng.alloc_outputs(d_a, d_b, cols, rows, h_dtype, p_dtype, trials=1)
+        first_ratio = eng.get_option("last_placement_ratio_x1000") / 1000 if first is not out else None
+        dt_first, ms_first = timed(first, max(3, args.steps // 4), 4)
+        value_first = world * len(ms_first) * cols * rows / dt_first / 1e9
+        first_strips = int(eng.get_option("last_strips2")) or eng.get_option("last_strips")
+        if first is not out:
+            first.free()
+        foreign = eng.alloc(cols, rows, h_dtype, p_dtype)
+        dt_foreign, ms_foreign = timed(foreign, max(3, args.steps // 4), 4)
+        value_foreign = world * len(ms_foreign) * cols * rows / dt_foreign / 1e9
+        del foreign
+        torch.cuda.empty_cache()
     dt, kern_ms = timed(out, args.steps, args.warmup)
     res = out.result()
-    tau_ns, lag_ns, shader_ghz, chain_extra = chain_stamps(sw, eng, torch, d_a, d_b, out, cols, rows) if args.engine == 0 else (0.0, 0.0, None, {})
-    clocks1 = _clocks()
+    if args.dump_outputs and rank == 0:
+        idx = _sample_index(out.H.numel())
+        dump_outputs(args.dump_outputs, {"result_max_score_max_pos": [res["max_score"], res["max_pos"]], "sample_index": idx,
+                                         **_matrix_outputs(torch, "H", out.H, idx), **_matrix_outputs(torch, "P", out.P, idx)})
+    if args.full:
+        tau_ns, lag_ns, shader_ghz, chain_extra = chain_stamps(sw, eng, torch, d_a, d_b, out, cols, rows) if args.engine == 0 else (0.0, 0.0, None, {})
+        clocks1 = _clocks()
     if world > 1:
         tmax = torch.tensor([dt], device=f"cuda:{local}")
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
@@ -294,22 +342,26 @@ def run_pair(args, sw, eng, torch, dist, rank, world, local):
                    "placement_probe_ms" if args.placement_trials <= 0 else "placement_trials_ms": placement_ms, "sw_alloc_outputs_ms": t_alloc * 1e3,
                    "placement_held_gib": out_held,
                    "placement_ratio": out_ratio if placement_ms is not None else None,
-                   "value_first_allocation": value_first, "value_first_allocation_is": "the same fill into a plain pair from the C-ABI (sw_alloc_outputs, trials = 1: two back-to-back hipMallocs, usually one class of the HBM; the library probes the pair once and fills a one-class pair with overlapping strips)",
-                   "first_allocation_probe_ratio": first_ratio, "first_allocation_strips": first_strips,
-                   "value_foreign_pair": value_foreign, "value_foreign_pair_is": "the same fill into two torch allocations (not probed: 126-column strips whatever their class)",
-                   "preheat_fills": nheat,
-                   "clocks_before": clocks0, "clocks_after": clocks1, "shader_clock_ghz_in_kernel": shader_ghz,
-                   "ms_first_allocation": sum(ms_first) / len(ms_first)},
+                   "preheat_fills": nheat},
         "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                      "frac": achieved / HBM_PEAK_GBS,
                      "traffic": traffic, "traffic_source": traffic_src,
                      "kernel": ("sw_systolic2" if int(eng.get_option("last_strips2")) > 0 else "sw_systolic") if args.engine == 0 else "sw_strip_scan", "avg_launch_ms": avg_ms, "min_launch_ms": min(kern_ms),
-                     "algorithmic_bytes_per_cell": bytes_per_cell, "measured_contiguous_fill_GBs": fill_gbs,
-                     "tau_step_ns": tau_ns, "strip_handoff_lag_ns": lag_ns, **chain_extra,
-                     # the chain of sequential steps with free hand-offs: rows + columns / (columns per lane) steps of tau each
-                     "dependency_bound_gcups": (cells / ((rows + cols / (2 if int(eng.get_option("last_strips2")) > 0 else 1) - 1) * tau_ns)) if tau_ns > 0 else None},
+                     "algorithmic_bytes_per_cell": bytes_per_cell},
     }
-    if not args.no_cpu and world == 1:
+    if args.full:
+        line["config"].update({
+            "value_first_allocation": value_first, "value_first_allocation_is": "the same fill into a plain pair from the C-ABI (sw_alloc_outputs, trials = 1: two back-to-back hipMallocs, usually one class of the HBM; the library probes the pair once and fills a one-class pair with overlapping strips)",
+            "first_allocation_probe_ratio": first_ratio, "first_allocation_strips": first_strips,
+            "value_foreign_pair": value_foreign, "value_foreign_pair_is": "the same fill into two torch allocations (not probed: 126-column strips whatever their class)",
+            "clocks_before": clocks0, "clocks_after": clocks1, "shader_clock_ghz_in_kernel": shader_ghz,
+            "ms_first_allocation": sum(ms_first) / len(ms_first)})
+        line["roofline"].update({
+            "measured_contiguous_fill_GBs": fill_gbs,
+            "tau_step_ns": tau_ns, "strip_handoff_lag_ns": lag_ns, **chain_extra,
+            # the chain of sequential steps with free hand-offs: rows + columns / (columns per lane) steps of tau each
+            "dependency_bound_gcups": (cells / ((rows + cols / (2 if int(eng.get_option("last_strips2")) > 0 else 1) - 1) * tau_ns)) if tau_ns > 0 else None})
+    if args.full and not args.no_cpu and world == 1:
         cb = cpu_baseline(cols, rows)
         for k in ("omp", "omp_all_cores", "omp_critical"):
             v = cb.pop(k, None)
@@ -343,6 +395,8 @@ def run_bands(args, sw, eng, torch, dist, rank, world, local):
         score, pos = pipe.fill()
     barrier()
     dt = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"result_max_score_max_pos": [score, pos]})
     if world > 1:
         tmax = torch.tensor([dt], device=f"cuda:{local}")
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
@@ -399,6 +453,14 @@ def run_batch(args, sw, eng, torch, dist, rank, world, local):
     dt = time.perf_counter() - t0
     if rank != 0:
         return
+    if args.dump_outputs:
+        res, H, P = out
+        arrays = {"result_max_pos_max_score_path_len": res.cpu().numpy()}
+        if H is not None or P is not None:
+            idx = _sample_index((H if H is not None else P).numel())
+            arrays["sample_index"] = idx
+            arrays.update({f"{k}_sample": _gather(torch, X, idx) for k, X in (("H", H), ("P", P)) if X is not None})
+        dump_outputs(args.dump_outputs, arrays)
     cells = npairs * cols * rows
     bpc = ((0 if args.no_h else 4) + (1 if args.p8 else 4)) if args.store else 0
     bk = eng.get_option("last_batch_kernel")
@@ -434,7 +496,7 @@ def run_batch(args, sw, eng, torch, dist, rank, world, local):
         ach = bpc * cells / (dt / args.steps) / 1e9
         line["roofline"] = {"bound": "hbm", "achieved": ach, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": ach / HBM_PEAK_GBS, "traffic": None,
                             "kernel": "sw_systolic", "algorithmic_bytes_per_cell": bpc}
-    if not args.no_cpu:
+    if args.full and not args.no_cpu:
         ref = os.path.join(ROOT, "oracle", "_ref", "serial_smithW")
         if os.path.exists(ref):   # the reference handles one pair per process: serial_smithW <cols> <rows>, best of 5 (fill loop only)
             sec = _best_of([ref, str(cols), str(rows)], 5)
@@ -451,7 +513,12 @@ def main():
     ap.add_argument("--cols", type=int, default=0)
     ap.add_argument("--rows", type=int, default=0)
     ap.add_argument("--h64", action="store_true", help="int64 H (BASELINE config 3 element type)")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline leg")
+    ap.add_argument("--no-cpu", action="store_true", help="--full: skip the CPU baseline leg")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: fills into a plain first allocation and a foreign pair, contiguous-fill bandwidth, in-kernel "
+                         "chain stamps, clocks and the CPU baselines")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float64; a fixed, seeded sample of the matrices)")
     ap.add_argument("--mode", default="auto", choices=["auto", "pair", "bands", "batch", "replicas"],
                     help="auto: pair on one GPU, bands (one matrix sharded over the ranks) on several; replicas: one independent pair "
                          "per GPU; batch: --pairs independent pairs in one call (BASELINE config 5)")

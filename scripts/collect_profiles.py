@@ -61,17 +61,17 @@ for d in ("prof", "prof_batch"):
             if i < 5:
                 print(f"{d:11s} {row['Name'][:70]:70s} calls {row['Calls']:>5s} avg {float(row['AverageNs']) / 1e3:10.1f} us  {row['Percentage']}%")
 
-# the timed launches of the default bench: the last launch is the stamped one (chain_stamps), the `steps` before it are timed
+# the timed launches of the default bench (a run without --full): the last `steps` launches are the timed ones
 timed = None
 for f in newest(os.path.join(src, "prof", "**", "*kernel_trace.csv")):
     rows = list(csv.DictReader(open(f)))
     d = [int(r["End_Timestamp"]) - int(r["Start_Timestamp"]) for r in rows if "sw_systolic2" in r["Kernel_Name"]]
-    if len(d) >= 21:
-        t = d[-21:-1]
+    if len(d) >= 20:
+        t = d[-20:]
         timed = {"kernel": "sw_systolic2", "launches_in_trace": len(d), "timed_steps": 20, "avg_ms": sum(t) / 20 / 1e6, "min_ms": min(t) / 1e6, "max_ms": max(t) / 1e6,
                  "all_launches_avg_ms": sum(d) / len(d) / 1e6}
         # everything a fill enqueues between two big launches: the helper kernels and the gaps
-        big = [r for r in rows if "sw_systolic2" in r["Kernel_Name"]][-21:-1]
+        big = [r for r in rows if "sw_systolic2" in r["Kernel_Name"]][-20:]
         per = [(int(big[i + 1]["Start_Timestamp"]) - int(big[i]["Start_Timestamp"])) for i in range(len(big) - 1)]
         timed["start_to_start_avg_ms"] = sum(per) / len(per) / 1e6
         print("== timed launches of the default bench:", json.dumps(timed))
