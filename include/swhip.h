@@ -320,9 +320,8 @@ int sw_synchronize(sw_ctx* ctx, void* stream);   /* waits for `stream`; reports 
  *                       while the pair lives (sw_get_option "last_placement_held_gib").  Default 0; pairs of many GiB take up to 32 by themselves
  *   "placement_budget_ms"  sw_alloc_outputs: how long the search for an H / P pair in different classes of the HBM may take at worst (default 1500; 2-5 ms on memory that needs no wiping)
  *   "max_blocks"        cap of the resident grid (0 = all CUs); concurrent band launches partition the CUs with it
- *   "waves_per_block", "debug_flags", "debug_buf", "batch_lds"   development aids (debug_flags 131072: no scout workgroups,
- *                       8388608: scouts without the per-XCD dealing of the roles, 134217728: no pacing, 65536: batches on the
- *                       single-pair machinery, 16384: one column per lane)
+ *   "waves_per_block", "debug_flags", "debug_buf", "batch_lds"   development aids (debug_flags: the bits of swk::DebugFlag in
+ *                       smith-waterman_amd/csrc/sw_debug.h)
  * sw_get_option also answers "last_grid", "last_strips", "last_strips2" (strips of the two-column kernel), "last_scouts"
  * (scout workgroups of the last fill), "last_xcd_mode" (1: that fill dealt its roles per XCD), "xcd_round_robin" (1: sw_create saw
  * workgroup i of a launch on XCD i % 8) and "last_batch_kernel" (1: the last batch ran one pair per wave). */

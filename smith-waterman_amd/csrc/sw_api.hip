@@ -11,8 +11,10 @@
 #include <thread>
 #include <vector>
 #include "sw_kernels.h"
+#include "sw_plan.h"
 
 namespace swh { void set_err(const char* fmt, ...); }
+extern "C" int sw_place_pair_ratio(void* d_X, size_t xbytes, void* d_Y, size_t ybytes, float* ratio, float* ms_together);   // sw_place.hip
 using swh::set_err;
 
 #define HIP_TRY(expr)                                                                 \
@@ -55,9 +57,6 @@ struct sw_ctx {
     unsigned int* d_part = nullptr;     // sw_prep_scan: one 256-bit presence map of byte values per block (up to 2048 blocks)
     unsigned int* d_sync = nullptr;     // one-launch fills (sw_systolic2's prologue / epilogue): barrier and exit counters, presence map; zero between launches
     unsigned char* d_priv = nullptr; size_t priv_cap = 0;   // ... and every workgroup's own padded copy of b + letter codes
-    int64_t opt_s2w = 0;                // two-column kernel: strips every 126 or 110 columns (overlapping strips, whole-line stores); 0: the library chooses
-    int64_t opt_split_blk = 0, opt_split_from = 0;   // split strips: forced split block / first strip (0: chosen by the library; tests)
-    int64_t opt_probe_foreign = 0;      // fills: probe an output pair the library did not allocate once, at its first fill (the probe writes and synchronises)
     int64_t opt_place_hold_gib = 0;     // sw_alloc_outputs: GiB a pair of small matrices may hold beside itself where no plain candidate is good (0: none)
     int64_t opt_place_budget_ms = 1500; // sw_alloc_outputs: time the search for a P in another class of the HBM may take
     int place_spacer_gib = 0;           // ... the spacer that led to one last time
@@ -65,30 +64,18 @@ struct sw_ctx {
     float last_place_ratio = 0.f;       // ... two-stream / one-stream time of the pair handed out last (~1.3-1.45: different classes, ~2: one class)
     bool key_dirty = false;             // d_key was left non-zero by a launch that does not re-arm it (everything but the one-launch fill)
     bool last_fused = false;            // the last launch_fill reports by itself (no sw_finalize behind it)
-    int64_t opt_debug = 0;
-    int64_t opt_xcd_chain = 0;          // two-column kernel without scouts: strips dealt per XCD (0 auto, 1 on, 2 off)
-    int64_t opt_filler_hop_ps = 2400000, opt_filler_tau_ps = 25000, opt_filler_bw_gbs = 4200;   // pacing of the fillers behind scouts (sw_systolic2.inc)
-    int64_t opt_store_policy = 0;       // systolic H/P stores: 0 auto (by size), 1 write-back, 2 streaming (nt)
+    swp::PlanOptions opt;               // the options the fill planner reads (sw_set_option; include/swhip.h)
+    swp::FillPlan last_plan;            // the plan of the last fill (sw_get_option "last_*")
+    int64_t last_grid = 0;              // ... and the grid of its one-column kernel after the occupancy cap
+    int s2_per_cu = 0;                  // occupancy of sw_systolic2 at 768 threads (queried at the first fill)
     int64_t opt_xcd_order = 0;          // systolic: 1 = neighbouring strip groups on one XCD
-    int64_t opt_importers = 0;          // systolic, one strip per workgroup: importer waves (as far as 12 waves allow); 0 = by problem size
     int64_t opt_pace_ps = 0;            // systolic: pacing of strip 0 (ps per row; 0 = off)
     int64_t opt_dbg_ptr = 0;
     int64_t opt_band_wait_ms = 20000;   // band-resident launch: patience of the top-halo poll
-    int64_t opt_engine = 0;             // 0 = systolic producer/consumer pipeline, 1 = strip_scan (row scan)
-    int64_t opt_strips_per_group = 0;   // systolic: producer waves (strips) per workgroup; 0 = by problem shape
-    int64_t opt_consumers = 0;          // systolic: consumer waves per strip; 0 = by problem shape
-    int64_t opt_waves_per_block = 4;
-    int64_t opt_max_blocks = 0;         // 0 -> 2 * CUs
     unsigned char* d_bcodes = nullptr; size_t bcodes_cap = 0;   // batch kernel: padded letter codes of every pair's b
     int* d_bnd = nullptr; size_t bnd_cap = 0;                   // batch kernel: boundary columns between strips (ints)
     int64_t opt_batch_lds = 0;          // batch kernel: dynamic LDS bytes per workgroup (caps the waves per CU; experiments)
     int64_t last_batch_kernel = 0;      // 1: the last sw_batch_device call ran on sw_batch_wave (one pair per wave)
-    int64_t last_grid = 0, last_strips = 0;
-    int64_t last_strips2 = 0;           // strips of the two-column kernel in the last launch (0: not launched)
-    int64_t last_scouts = 0;            // scout workgroups of that launch
-    int64_t last_xcd_mode = 0;          // that launch dealt its roles per XCD
-    int64_t last_tiles = 1;             // column tiles (launches of the two-column kernel) of the last fill
-    int64_t last_split_from = 0;        // first strip whose scout also fills (split strips), 0: none
     bool xcd_round_robin = false;       // sw_xcc_probe saw workgroup i on XCD i % 8 (8 XCDs of 32 CUs)
     std::map<void*, void*> out_base;    // sw_alloc_outputs: pointer handed out -> allocation to free
     std::map<void*, float> pair_ratio;  // ... P handed out -> the store probe's ratio of its pair (~1.4: two classes of the HBM, ~2: one)
@@ -151,34 +138,34 @@ int sw_set_option(sw_ctx* c, const char* name, int64_t v) {
     if (!c || !name) { set_err("sw_set_option: bad argument"); return SW_EINVAL; }
     if (!strcmp(name, "waves_per_block")) {
         if (v != 0 && v != 1 && v != 2 && v != 4 && v != 8) { set_err("waves_per_block must be 1,2,4,8"); return SW_EINVAL; }
-        c->opt_waves_per_block = v ? v : 4;
+        c->opt.waves_per_block = v ? v : 4;
         return SW_OK;
     }
-    if (!strcmp(name, "max_blocks")) { c->opt_max_blocks = v < 0 ? 0 : v; return SW_OK; }
-    if (!strcmp(name, "strips_per_group")) { c->opt_strips_per_group = v; return SW_OK; }
-    if (!strcmp(name, "consumers")) { c->opt_consumers = v; return SW_OK; }
-    if (!strcmp(name, "debug_flags")) { c->opt_debug = v; return SW_OK; }
-    if (!strcmp(name, "xcd_chain")) { c->opt_xcd_chain = v; return SW_OK; }
-    if (!strcmp(name, "filler_hop_ps")) { c->opt_filler_hop_ps = v < 0 ? 0 : v; return SW_OK; }
-    if (!strcmp(name, "filler_tau_ps")) { c->opt_filler_tau_ps = v < 1000 ? 1000 : v; return SW_OK; }
-    if (!strcmp(name, "filler_bw_gbs")) { c->opt_filler_bw_gbs = v < 100 ? 100 : v; return SW_OK; }
+    if (!strcmp(name, "max_blocks")) { c->opt.max_blocks = v < 0 ? 0 : v; return SW_OK; }
+    if (!strcmp(name, "strips_per_group")) { c->opt.strips_per_group = v; return SW_OK; }
+    if (!strcmp(name, "consumers")) { c->opt.consumers = v; return SW_OK; }
+    if (!strcmp(name, "debug_flags")) { c->opt.debug_flags = v; return SW_OK; }
+    if (!strcmp(name, "xcd_chain")) { c->opt.xcd_chain = v; return SW_OK; }
+    if (!strcmp(name, "filler_hop_ps")) { c->opt.filler_hop_ps = v < 0 ? 0 : v; return SW_OK; }
+    if (!strcmp(name, "filler_tau_ps")) { c->opt.filler_tau_ps = v < 1000 ? 1000 : v; return SW_OK; }
+    if (!strcmp(name, "filler_bw_gbs")) { c->opt.filler_bw_gbs = v < 100 ? 100 : v; return SW_OK; }
     if (!strcmp(name, "pace_ps")) { c->opt_pace_ps = v; return SW_OK; }
-    if (!strcmp(name, "store_policy")) { if (v < 0 || v > 2) return SW_EINVAL; c->opt_store_policy = v; return SW_OK; }
+    if (!strcmp(name, "store_policy")) { if (v < 0 || v > 2) return SW_EINVAL; c->opt.store_policy = v; return SW_OK; }
     if (!strcmp(name, "xcd_order")) { c->opt_xcd_order = v ? 1 : 0; return SW_OK; }
-    if (!strcmp(name, "importers")) { if (v < 0 || v > 8) return SW_EINVAL; c->opt_importers = v; return SW_OK; }
+    if (!strcmp(name, "importers")) { if (v < 0 || v > 8) return SW_EINVAL; c->opt.importers = v; return SW_OK; }
     if (!strcmp(name, "debug_buf")) { c->opt_dbg_ptr = v; return SW_OK; }
     if (!strcmp(name, "batch_lds")) { c->opt_batch_lds = v < 0 ? 0 : v; return SW_OK; }
     if (!strcmp(name, "band_wait_ms")) { c->opt_band_wait_ms = v > 0 ? v : 20000; return SW_OK; }
     if (!strcmp(name, "placement_budget_ms")) { c->opt_place_budget_ms = v > 0 ? v : 1500; return SW_OK; }
     if (!strcmp(name, "placement_hold_gib")) { c->opt_place_hold_gib = v < 0 ? 0 : (v > 128 ? 128 : v); return SW_OK; }
-    if (!strcmp(name, "probe_foreign_pairs")) { c->opt_probe_foreign = v ? 1 : 0; return SW_OK; }
-    if (!strcmp(name, "s2w")) { if (v != 0 && v != 126 && v != 110) return SW_EINVAL; c->opt_s2w = v; return SW_OK; }
-    if (!strcmp(name, "split_blk")) { c->opt_split_blk = v > 0 ? v : 0; return SW_OK; }
-    if (!strcmp(name, "split_from")) { c->opt_split_from = v > 0 ? v : 0; return SW_OK; }
+    if (!strcmp(name, "probe_foreign_pairs")) { c->opt.probe_foreign_pairs = v ? 1 : 0; return SW_OK; }
+    if (!strcmp(name, "s2w")) { if (v != 0 && v != 126 && v != 110) return SW_EINVAL; c->opt.s2w = v; return SW_OK; }
+    if (!strcmp(name, "split_blk")) { c->opt.split_blk = v > 0 ? v : 0; return SW_OK; }
+    if (!strcmp(name, "split_from")) { c->opt.split_from = v > 0 ? v : 0; return SW_OK; }
     if (!strcmp(name, "debug_epoch8")) { c->epoch8 = (unsigned)(v & 255); return SW_OK; }   // development aid: next launch tag = v + 1
     if (!strcmp(name, "engine")) {
         if (v != 0 && v != 1) { set_err("engine must be 0 (systolic) or 1 (strip_scan)"); return SW_EINVAL; }
-        c->opt_engine = v;
+        c->opt.engine = v;
         return SW_OK;
     }
     set_err("sw_set_option: unknown option '%s'", name);
@@ -187,31 +174,32 @@ int sw_set_option(sw_ctx* c, const char* name, int64_t v) {
 
 int64_t sw_get_option(sw_ctx* c, const char* name) {
     if (!c || !name) return -1;
-    if (!strcmp(name, "waves_per_block")) return c->opt_waves_per_block;
-    if (!strcmp(name, "max_blocks")) return c->opt_max_blocks;
-    if (!strcmp(name, "engine")) return c->opt_engine;
-    if (!strcmp(name, "strips_per_group")) return c->opt_strips_per_group;
-    if (!strcmp(name, "consumers")) return c->opt_consumers;
-    if (!strcmp(name, "store_policy")) return c->opt_store_policy;
+    if (!strcmp(name, "waves_per_block")) return c->opt.waves_per_block;
+    if (!strcmp(name, "max_blocks")) return c->opt.max_blocks;
+    if (!strcmp(name, "engine")) return c->opt.engine;
+    if (!strcmp(name, "strips_per_group")) return c->opt.strips_per_group;
+    if (!strcmp(name, "consumers")) return c->opt.consumers;
+    if (!strcmp(name, "store_policy")) return c->opt.store_policy;
     if (!strcmp(name, "xcd_order")) return c->opt_xcd_order;
-    if (!strcmp(name, "importers")) return c->opt_importers;
+    if (!strcmp(name, "importers")) return c->opt.importers;
     if (!strcmp(name, "pace_ps")) return c->opt_pace_ps;
     if (!strcmp(name, "band_wait_ms")) return c->opt_band_wait_ms;
     if (!strcmp(name, "num_cus")) return c->num_cus;
     if (!strcmp(name, "debug_edge4_ptr")) return (int64_t)(uintptr_t)c->d_edge4;
     if (!strcmp(name, "debug_edge4_cap")) return (int64_t)c->edge4_cap;
     if (!strcmp(name, "last_grid")) return c->last_grid;
-    if (!strcmp(name, "last_strips")) return c->last_strips;
-    if (!strcmp(name, "last_strips2")) return c->last_strips2;
-    if (!strcmp(name, "last_scouts")) return c->last_scouts;
-    if (!strcmp(name, "last_xcd_mode")) return c->last_xcd_mode;
-    if (!strcmp(name, "last_tiles")) return c->last_tiles;
-    if (!strcmp(name, "last_split_from")) return c->last_split_from;
+    const swp::TilePlan& last_tile = c->last_plan.tile[c->last_plan.ntile - 1];   // (all zero where the two-column kernel did not run)
+    if (!strcmp(name, "last_strips")) return c->last_plan.S;
+    if (!strcmp(name, "last_strips2")) return last_tile.strips;
+    if (!strcmp(name, "last_scouts")) return last_tile.nscout;
+    if (!strcmp(name, "last_xcd_mode")) return last_tile.xcd_mode;
+    if (!strcmp(name, "last_tiles")) return c->last_plan.ntile;
+    if (!strcmp(name, "last_split_from")) return last_tile.split_blk ? last_tile.split_from : 0;
     if (!strcmp(name, "xcd_round_robin")) return c->xcd_round_robin ? 1 : 0;
     if (!strcmp(name, "last_batch_kernel")) return c->last_batch_kernel;
     if (!strcmp(name, "placement_budget_ms")) return c->opt_place_budget_ms;
     if (!strcmp(name, "placement_hold_gib")) return c->opt_place_hold_gib;
-    if (!strcmp(name, "probe_foreign_pairs")) return c->opt_probe_foreign;
+    if (!strcmp(name, "probe_foreign_pairs")) return c->opt.probe_foreign_pairs;
     if (!strcmp(name, "last_placement_held_gib")) return c->last_place_held_gib;
     if (!strcmp(name, "last_placement_ratio_x1000")) return (int64_t)(c->last_place_ratio * 1000.f);
     return -1;
@@ -256,7 +244,6 @@ struct FillJob {
     int reserve_cus = 0;          // CUs left free for other kernels (halo transfers)
     bool concurrent = false;      // do not order this launch behind fills on other streams (the caller partitions the CUs)
     int64_t total_rows = 0;       // band: rows of the whole matrix (bounds the scores a halo can carry)
-    bool reserve_only = false;    // size the per-context workspaces for this job and return: nothing is launched
     bool zero_key = false;        // the preparation kernel also zeroes d_keys[0..1] (fill_one leaves that to it)
     sw_result* d_result = nullptr;   // fill_one: where the result goes (a one-launch fill writes it by itself)
 };
@@ -284,29 +271,110 @@ struct DevOrder {   // RAII: device lock + stream ordering for one fill call
     }
 };
 
+// Grows a workspace of the context to `need` elements of `elem` bytes (+ `slack` bytes): waits for the stream (launches in flight may
+// still read the old one), frees it and allocates afresh.  `fresh` says whether it did: the caller wipes what must start zeroed.
+static int grow_workspace(void** buf, size_t& cap, size_t need, size_t elem, size_t slack, hipStream_t stream, bool& fresh) {
+    fresh = false;
+    if (need <= cap) return SW_OK;
+    HIP_TRY(hipStreamSynchronize(stream));
+    if (*buf) HIP_TRY(hipFree(*buf));
+    *buf = nullptr; cap = 0;
+    const size_t bytes = need * elem + slack;
+    if (hipMalloc(buf, bytes) != hipSuccess) { set_err("workspace allocation of %zu bytes failed", bytes); return SW_ENOMEM; }
+    cap = need; fresh = true;
+    return SW_OK;
+}
+
+static int ensure_workspaces(sw_ctx* c, const swp::FillPlan& f, hipStream_t stream) {
+    bool fresh = false;
+    if (int rc = grow_workspace((void**)&c->d_edge, c->edge_cap, f.edge_need, 8, 0, stream, fresh)) return rc;
+    if (fresh) { HIP_TRY(hipMemsetAsync(c->d_edge, 0, c->edge_cap * 8, stream)); c->epoch = 0; }
+    if (int rc = grow_workspace((void**)&c->d_cb, c->cb_cap, f.cb_need, 4, 64, stream, fresh)) return rc;
+    if (int rc = grow_workspace((void**)&c->d_edge4, c->edge4_cap, f.edge4_need, 4, 0, stream, fresh)) return rc;
+    if (fresh) c->epoch8 = 255;   // fresh memory: the next tag wraps and wipes it
+    return grow_workspace((void**)&c->d_priv, c->priv_cap, f.priv_need, 1, 0, stream, fresh);
+}
+
+// Advances the 8-bit launch tag of the perm producer's self-tagged edge values and returns the G bias that carries it.  A wrapped tag
+// could match stale values: they are wiped.
+static unsigned next_gbias(sw_ctx* c, hipStream_t stream) {
+    if (++c->epoch8 >= (unsigned)((c->opt.debug_flags & swk::DBG_EPOCH8_WRAP_EARLY) ? 4 : 256)) {
+        const unsigned nb = (unsigned)std::max<size_t>(1, std::min<size_t>((c->edge4_cap + 255) / 256, 2048));
+        hipLaunchKernelGGL(swk::sw_wipe_u32, dim3(nb), dim3(256), 0, stream, c->d_edge4, c->edge4_cap);
+        c->epoch8 = 1;
+    }
+    return (c->epoch8 << 24) | 0x10000u;
+}
+
+static int plan_for(sw_ctx* c, const swp::PlanJob& pj, swp::FillPlan& plan) {
+    if (c->opt.engine == 0 && c->s2_per_cu < 1)
+        HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&c->s2_per_cu, swk::sw_systolic2<6, false>, 768, 0));
+    swp::DeviceFacts dev;
+    dev.num_cus = c->num_cus; dev.xcd_round_robin = c->xcd_round_robin; dev.s2_per_cu = c->s2_per_cu;
+    plan = swp::plan_fill(pj, dev, c->opt);
+    return SW_OK;
+}
+
+// the instantiations of the two kernels (sw_systolic.hip, sw_systolic2.inc)
+using SystolicKernel = void (*)(const unsigned char*, const unsigned char*, const unsigned char*, swk::FillParams);
+static const struct { int ns, nc; SystolicKernel h32, h64; } kSystolic[] = {
+    {2, 2, swk::sw_systolic<int32_t, 2, 2>, swk::sw_systolic<int64_t, 2, 2>}, {2, 3, swk::sw_systolic<int32_t, 2, 3>, swk::sw_systolic<int64_t, 2, 3>},
+    {2, 4, swk::sw_systolic<int32_t, 2, 4>, swk::sw_systolic<int64_t, 2, 4>}, {1, 2, swk::sw_systolic<int32_t, 1, 2>, swk::sw_systolic<int64_t, 1, 2>},
+    {1, 3, swk::sw_systolic<int32_t, 1, 3>, swk::sw_systolic<int64_t, 1, 3>}, {1, 4, swk::sw_systolic<int32_t, 1, 4>, swk::sw_systolic<int64_t, 1, 4>},
+    {1, 6, swk::sw_systolic<int32_t, 1, 6>, swk::sw_systolic<int64_t, 1, 6>}, {1, 7, swk::sw_systolic<int32_t, 1, 7>, swk::sw_systolic<int64_t, 1, 7>},
+};
+using Systolic2Kernel = void (*)(const unsigned char*, const unsigned char*, swk::FillParams);
+static const Systolic2Kernel kSystolic2[4][2] = {   // [consumers - 4][overlapping strips]
+    {swk::sw_systolic2<4, false>, swk::sw_systolic2<4, true>}, {swk::sw_systolic2<5, false>, swk::sw_systolic2<5, true>},
+    {swk::sw_systolic2<6, false>, swk::sw_systolic2<6, true>}, {swk::sw_systolic2<7, false>, swk::sw_systolic2<7, true>},
+};
+
+static swp::PlanJob plan_job(const FillJob& j, const sw_scores* sc) {
+    swp::PlanJob pj;
+    pj.cols = j.cols; pj.rows = j.rows; pj.npairs = j.npairs; pj.full_stride = j.stride == j.cols + 1;
+    pj.h_elem_bytes = j.h_elem_bytes; pj.p_elem_bytes = j.p_elem_bytes; pj.has_H = j.d_H; pj.has_P = j.d_P;
+    pj.has_top = j.d_top; pj.has_left = j.d_left; pj.has_right = j.d_right; pj.has_top_gran = j.d_top_gran; pj.has_bot_gran = j.d_bot_gran;
+    pj.has_result = j.d_result; pj.total_rows = j.total_rows; pj.reserve_cus = j.reserve_cus;
+    pj.h_aligned = ((uintptr_t)j.d_H & (j.h_elem_bytes == 8 ? 15u : 7u)) == 0; pj.p_aligned = ((uintptr_t)j.d_P & 7u) == 0;
+    pj.match = sc->match; pj.mismatch = sc->mismatch; pj.gap = sc->gap;
+    return pj;
+}
+
+// Carries out the plan of one fill (sw_plan.cpp): workspaces, launch tags, parameters, launches.
 static int launch_fill(sw_ctx* c, const sw_scores* sc, const FillJob& j, hipStream_t stream) {
     const int64_t cols = j.cols, rows = j.rows;
-    const bool systolic = (c->opt_engine == 0);
+    const bool systolic = (c->opt.engine == 0);
     c->last_fused = false;
     const bool tile_features = j.d_left || j.d_right || j.stride != cols + 1 || j.npairs != 1 || !j.d_H || !j.d_P || j.d_top_gran || j.d_bot_gran;
     if (!systolic && tile_features) { set_err("tiles / batches / bands / matrix-less fills need the systolic engine (engine 0)"); return SW_EINVAL; }
-    // (the caller holds the device lock and has ordered `stream` behind earlier fills: DevOrder)
-    const int64_t S = systolic ? (cols + 62) / 63 : (cols + 63) / 64;
+    if (j.p_elem_bytes == 1 && !systolic) { set_err("compact (int8) P needs the systolic engine"); return SW_EINVAL; }
     if (((uintptr_t)j.d_b & 15) != 0 || (j.b_pstride & 15) != 0) { set_err("d_b (and the batch stride of b) must be 16-byte aligned"); return SW_EINVAL; }
-    const size_t need = (size_t)S * (size_t)(rows + 1) * (size_t)j.npairs;
-    if (need > c->edge_cap) {
-        HIP_TRY(hipStreamSynchronize(stream));
-        if (c->d_edge) HIP_TRY(hipFree(c->d_edge));
-        c->d_edge = nullptr; c->edge_cap = 0;
-        if (hipMalloc((void**)&c->d_edge, need * 8) != hipSuccess) { set_err("workspace allocation of %zu bytes failed", need * 8); return SW_ENOMEM; }
-        c->edge_cap = need;
-        HIP_TRY(hipMemsetAsync(c->d_edge, 0, need * 8, stream));
-        c->epoch = 0;
+    // (the caller holds the device lock and has ordered `stream` behind earlier fills: DevOrder)
+    swp::PlanJob pj = plan_job(j, sc);
+    auto known = j.d_P ? c->pair_ratio.find(j.d_P) : c->pair_ratio.end();
+    if (known != c->pair_ratio.end()) pj.pair_ratio = known->second;
+    swp::FillPlan plan;
+    if (int rc = plan_for(c, pj, plan)) return rc;
+    if (plan.probe_pair_class) {
+        // option "probe_foreign_pairs": a pair the library did not allocate is probed once, at its first fill -- the probe WRITES both
+        // buffers (this fill overwrites them anyway) and synchronises the stream (~0.3 ms); remembered by the address of P (at most 64)
+        float r = 0.f, ms = 0.f;
+        if (c->pair_ratio.size() >= 64) c->pair_ratio.clear();
+        if (hipStreamSynchronize(stream) == hipSuccess && sw_place_pair_ratio(j.d_H, plan.h_bytes, j.d_P, plan.p_bytes, &r, &ms) == SW_OK) {
+            c->pair_ratio[j.d_P] = pj.pair_ratio = r;
+            if (int rc = plan_for(c, pj, plan)) return rc;
+        }
     }
+    const auto* one_col = systolic ? std::find_if(std::begin(kSystolic), std::end(kSystolic), [&](const auto& k) { return k.ns == plan.NS && k.nc == plan.NC; })
+                                   : std::end(kSystolic);
+    if (systolic && one_col == std::end(kSystolic)) { set_err("unsupported strips_per_group/consumers combination %d/%d", plan.NS, plan.NC); return SW_EINVAL; }
+    if (int rc = ensure_workspaces(c, plan, stream)) return rc;
     if (++c->epoch >= 4096) {  // 12-bit tag wrapped: stale tags could match again, wipe them
         HIP_TRY(hipMemsetAsync(c->d_edge, 0, c->edge_cap * 8, stream));
         c->epoch = 1;
     }
+    c->last_plan = plan;
+    const int64_t S = plan.S;
     swk::FillParams p;
     memset(&p, 0, sizeof p);
     p.cols = cols; p.rows = rows; p.M = j.stride;
@@ -317,377 +385,89 @@ static int launch_fill(sw_ctx* c, const sw_scores* sc, const FillJob& j, hipStre
     p.edge = c->d_edge; p.tag_base = c->epoch << 20;
     p.result_key = j.d_keys; p.abort_flag = (unsigned int*)(c->d_key + 1);
     p.nstrips = (int)S;
-    p.debug_flags = (int)c->opt_debug;
+    p.debug_flags = (int)c->opt.debug_flags;
     p.pace_ps = (int)c->opt_pace_ps;
-    // streaming stores pay off while the matrices are small next to what is in flight; measured cross-over between
-    // 16384^2 (nt 15-18 % faster) and 32768^2 (write-back 2-20 % faster)
-    p.store_nt = c->opt_store_policy == 2 || (c->opt_store_policy == 0 && (double)cols * (double)rows * (double)j.npairs <= 6.0e8);
+    p.store_nt = plan.store_nt;
     p.xcd_order = (int)c->opt_xcd_order;
     p.dbg = (unsigned long long*)(uintptr_t)c->opt_dbg_ptr;
     p.npairs = (int)j.npairs; p.store_hp = (j.d_H || j.d_P) ? 1 : 0;
     p.p_bytes = j.p_elem_bytes;
-    if (j.p_elem_bytes == 1 && !systolic) { set_err("compact (int8) P needs the systolic engine"); return SW_EINVAL; }
     p.a_pstride = j.a_pstride; p.b_pstride = j.b_pstride; p.hp_pstride = j.hp_pstride;
     p.edge_pstride = S * (rows + 1);
     const unsigned char* ua = (const unsigned char*)j.d_a;
     const unsigned char* ub = (const unsigned char*)j.d_b;
-    if (systolic) {
-        // Workgroup shape.  One strip + 8 consumers per workgroup gives every producer a SIMD of its own (measured on
-        // single pairs from 4096^2 to 32768^2: equal to 5 % faster than 2 + 2x4, equal at 65536^2); batches that
-        // do not fit the CUs at once run two strips per workgroup, twice the work per CU (1024^2 pairs: 415 vs 194 GCUPS
-        // for 20000 pairs, 203 vs 143 for 64).
-        int NS = (int)c->opt_strips_per_group, NC = (int)c->opt_consumers;
-        if (NS == 0) NS = (j.npairs == 1 ? (double)S <= 4.5 * c->num_cus : (double)S * (double)j.npairs <= (double)c->num_cus) ? 1 : 2;
-        // NS == 1: nine waves on the three SIMDs the producer leaves.  A chain-bound fill (one pair, up to ~3.5e8 cells: 16384^2)
-        // wants the hand-off found early -- 4 consumers + 5 importer waves: 240 vs 232 GCUPS at 16384^2, +7 % at 8192^2; bigger
-        // fills are bound by the stores and want 6 consumers + 3 importer waves (65536^2: 389 vs 340 GCUPS).
-        const bool chain_bound = NS == 1 && j.npairs == 1 && (double)cols * (double)rows <= 3.5e8;
-        if (NC == 0) NC = (NS == 1) ? (chain_bound ? 4 : 6) : 4;
-        const int importers = c->opt_importers > 0 ? (int)c->opt_importers : (chain_bound && NC <= 4 ? 4 : 2);
-        if (NS == 1 && NC > 7) NC = 7;         // nine waves off the producer's SIMD: at most 7 consumers + exporter + importer
-        if (NS == 1 && NC == 5) NC = 4;        // (the one-column kernel has no five-consumer form: option "consumers" = 5 is for the two-column kernel)
-        // padded copies of b per problem: [front | b | tail]; front covers the fast producers' phi (< strips) + 63 lanes
-        // (+ one 16-step block: the perm producer's first score window ends at step 0)
-        const int64_t bfront = ((S + 64 + 32 + 127) / 128) * 128;
-        const int64_t per = ((rows + bfront + 512 + 15) / 16) * 16;
-        const size_t ncb = (size_t)per * (size_t)j.npairs;
-        if (ncb > c->cb_cap) {
-            HIP_TRY(hipStreamSynchronize(stream));
-            if (c->d_cb) HIP_TRY(hipFree(c->d_cb));
-            c->d_cb = nullptr; c->cb_cap = 0;
-            if (hipMalloc((void**)&c->d_cb, ncb * 4 + 64) != hipSuccess) { set_err("workspace allocation failed"); return SW_ENOMEM; }
-            c->cb_cap = ncb;
-        }
-        const size_t cb16 = ((c->cb_cap + 15) / 16) * 16;
-        unsigned short* d_cb16 = (unsigned short*)(c->d_cb + cb16);
-        unsigned char* d_cbc = c->d_cb + cb16 + ((2 * c->cb_cap + 15) / 16) * 16;
-        // perm producer (alphabets of up to 7 letters): eligible when the scores fit a signed byte and every G value,
-        // with the 2^16 bias, stays below 2^24 (the top byte carries the launch tag)
-        const int64_t lo = std::min(cols, rows);
-        const int64_t gmax = (int64_t)sc->match * std::max<int64_t>(lo, std::min(cols, j.total_rows)) + (int64_t)(-sc->gap) * (rows + cols + 2);
-        const bool halo_unbounded = (j.d_top || j.d_left) && j.total_rows == 0;   // a tile whose halo magnitudes are unknown here
-        const bool perm_ok = !halo_unbounded && p.mm <= 127 && p.mm >= -127 && p.xm <= 127 && p.xm >= -127 && gmax + 0x10000 + 1024 < (1ll << 24) &&
-                             !(c->opt_debug & 16);
-        if (perm_ok) {
-            const int64_t e4stride = ((rows + S + 160 + 31) / 32) * 32;   // (whole 128-byte lines: strips written on different XCDs share none)
-            const size_t need4 = (size_t)S * (size_t)e4stride * (size_t)j.npairs;
-            if (need4 > c->edge4_cap) {
-                HIP_TRY(hipStreamSynchronize(stream));
-                if (c->d_edge4) HIP_TRY(hipFree(c->d_edge4));
-                c->d_edge4 = nullptr; c->edge4_cap = 0;
-                if (hipMalloc((void**)&c->d_edge4, need4 * 4) != hipSuccess) { set_err("workspace allocation of %zu bytes failed", need4 * 4); return SW_ENOMEM; }
-                c->edge4_cap = need4;
-                c->epoch8 = 255;   // fresh memory: wipe it below
-            }
-            if (++c->epoch8 >= (unsigned)((c->opt_debug & 1024) ? 4 : 256)) {   // 8-bit tag wrapped: wipe stale values (debug bit 10: wrap early)
-                const unsigned nb = (unsigned)std::max<size_t>(1, std::min<size_t>((c->edge4_cap + 255) / 256, 2048));
-                hipLaunchKernelGGL(swk::sw_wipe_u32, dim3(nb), dim3(256), 0, stream, c->d_edge4, c->edge4_cap);
-                c->epoch8 = 1;
-            }
-            p.edge4 = c->d_edge4; p.e4stride = e4stride; p.edge4_pstride = (int64_t)S * e4stride;
-            p.gbias = (c->epoch8 << 24) | 0x10000u;
-        }
-        // Two matrix columns per lane (sw_systolic2.inc): half as many strips -- and row segments of 504 bytes per store -- for the
-        // same work: 16384^2 +4 %, 8192^2 +11 %, 24576^2 +29 %, 32768^2 +32 %, 65536^2 +9 % over one column per lane.  Whole
-        // matrix of one pair, int32 H and P both stored, rows a multiple of 16; the alphabet (found on the device) must allow the
-        // perm path -- so both kernels are enqueued and each checks for itself which of them has to work.  (debug bit 14: off)
-        // Also: int8 P, either matrix left out, and band-resident launches (halo row in, last row out as granules).
-        const bool base_mode = j.d_H && j.d_P && j.h_elem_bytes == 4 && j.p_elem_bytes == 4 && !j.d_top && !j.d_top_gran && !j.d_bot_gran;   // int32 H + P, whole matrix
-        // Where it pays: always for int32 H + P (8-byte stores of both matrices); in the other output formats while the strip chain
-        // (~3.1 us per 63-column strip) rather than the output volume (~3.2 TB/s) bounds the fill -- measured: 262144 x 32768 with
-        // int8 P +18 %, 131072^2 with int8 P -3 %, 262144^2 P-only -21 % (two byte stores per row and the in-block arg-max).
-        const double est_chain = (double)S * 3.1e-6;
-        const double est_hbm = (double)(cols + 1) * (double)(rows + 1) * ((j.d_H ? (double)j.h_elem_bytes : 0.0) + (j.d_P ? (double)j.p_elem_bytes : 0.0)) / 3.2e12;
-        // (... and int32 H + int8 P beyond the reach of the scouts: the H of overlapping strips goes out in streamed whole lines -- 65536^2 597 GCUPS
-        //  against 429 on the one-column kernel and 494 with 126-column strips)
-        const bool pays = (j.d_H && j.d_P && j.p_elem_bytes == 4) || (j.d_H && j.h_elem_bytes == 8) || est_chain >= (j.d_H ? 0.5 : 2.0) * est_hbm || (c->opt_debug & 32768) ||
-                          (j.d_H && j.h_elem_bytes == 4 && (!j.d_P || j.p_elem_bytes == 1) && cols % 2 == 0 && cols > 126 * 170);
-        int per_cu2 = 0;
-        bool two_cols = pays && perm_ok && c->opt_strips_per_group == 0 && (c->opt_consumers == 0 || c->opt_consumers >= 4) && j.npairs == 1 &&
-                              !j.d_left && !j.d_right && j.stride == cols + 1 && (rows % 16 == 0 || !j.d_bot_gran) && rows >= 1 && cols >= 1 &&   // (a band's last row leaves from a full block)
-                             
-                              (base_mode || (cols % 2 == 0)) &&   // (an odd column count leaves one lane with a single column: only the base mode handles it)
-                              !(c->opt_debug & (2 | 8 | 64 | 128 | 512 | 16384));
-        // The two-column kernel is ONE launch per fill: its prologue does what sw_prep_scan / sw_prep_code do for the other kernels (every
-        // workgroup keeps its own padded copy of b and of its letter codes) and its last workgroup out writes the result (sw_systolic2.inc).
-        // The strict one-launch path needs a result to write (a batch keeps its own keys and never comes here).
-        const int64_t priv_stride = ((2 * per + 255) / 256) * 256;
-        if (two_cols) {
-            HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu2, swk::sw_systolic2<6, false>, 768, 0));
-            if (per_cu2 < 1 || !j.d_result) two_cols = false;
-        }
-        if (two_cols) {
-            const size_t needp = (size_t)priv_stride * (size_t)per_cu2 * (size_t)c->num_cus;
-            if (needp > c->priv_cap) {
-                HIP_TRY(hipStreamSynchronize(stream));
-                if (c->d_priv) HIP_TRY(hipFree(c->d_priv));
-                c->d_priv = nullptr; c->priv_cap = 0;
-                if (hipMalloc((void**)&c->d_priv, needp) != hipSuccess) { set_err("workspace allocation of %zu bytes failed", needp); return SW_ENOMEM; }
-                c->priv_cap = needp;
-            }
-        }
-        if (j.reserve_only) {   // every workspace of this job exists now (and is wiped where fresh): wait for that, launch nothing
-            HIP_TRY(hipStreamSynchronize(stream));
-            return SW_OK;
-        }
-        // input preparation, two dispatches (sw_systolic.hip): presence maps of the letters, then codes / padded copies of b -- and, for
-        // the two-column kernel, row 0 and column 0 of the matrices and the arg-max key
-        auto prepare = [&](void* zH, void* zP, bool skip_row0) {
-            const int64_t total = (cols + rows) * j.npairs;
-            const unsigned nscan = (unsigned)std::max<int64_t>(1, std::min<int64_t>((total + 1023) / 1024, 2048));
-            hipLaunchKernelGGL(swk::sw_prep_scan, dim3(nscan), dim3(256), 0, stream, ua, cols, j.a_pstride, ub, rows, j.b_pstride, j.npairs, c->d_part);
-            const unsigned npad = (unsigned)((per + 255) / 256);
-            const unsigned nzero = (zH || zP) ? (unsigned)((cols + 1 + rows + 255) / 256) : 0u;
-            hipLaunchKernelGGL(swk::sw_prep_code, dim3(npad + nzero, (unsigned)j.npairs), dim3(256), 0, stream, ub, rows, bfront, j.b_pstride, c->d_cb, d_cb16,
-                               d_cbc, (const unsigned int*)c->d_part, (int)nscan, c->d_alpha + 64, per, (int)npad, zH, j.h_elem_bytes, zP, j.p_elem_bytes,
-                               cols + 1, rows + 1, skip_row0 ? 1 : 0, j.zero_key ? j.d_keys : nullptr);
-        };
-        p.bcode = d_cbc;
-        p.atab = c->d_alpha + 64;
-        const bool fast = (j.d_top == nullptr) && (j.d_top_gran == nullptr) && (sc->mismatch <= 0) && !(c->opt_debug & 4);
-        p.phi_base = fast ? (int)S - 1 : -1;
-        p.bfront = (int)bfront;
-        p.bpad16 = d_cb16;
-        p.bpad8 = c->d_cb;
-        p.bpad_pstride = per;
-        const int64_t ngroups = ((S + NS - 1) / NS) * j.npairs;
-        const int64_t maxb = c->opt_max_blocks > 0 ? c->opt_max_blocks : std::max<int64_t>(8, (int64_t)c->num_cus - j.reserve_cus);
-        int grid = (int)std::max<int64_t>(1, std::min<int64_t>(ngroups, maxb));
-        int threads;
-        if (NS == 1) {
-            // wave 0 (the producer) owns SIMD 0: waves 4, 8, 12 idle; consumers, the exporter and the importers are the
-            // K waves off SIMD 0 (wave id of ordinal k: k + 1 + k/3)
-            const int K = std::min<int>(9, NC + 1 + std::max(1, importers));   // 12 waves: 3 per SIMD
-            threads = 64 * (K + (K - 1) / 3 + 1);
-        } else {
-            threads = 64 * (NS * (1 + NC) + 2);
-        }
-        const unsigned char* cbp = c->d_cb;
-        bool launched = false;
-        c->last_strips2 = 0; c->last_scouts = 0; c->last_xcd_mode = 0; c->last_tiles = 1;
-        if (two_cols) {
-            // strip geometry: every 126 columns (the strips tile the matrix), or every 110 with 16 columns of overlap -- whole-line stores
-            // (sw_systolic2.inc); option "s2w" forces one of the two (tests, A/B runs)
-            const bool band_io = j.d_top || j.d_top_gran || j.d_bot_gran;
-            int64_t W2 = 126;
-            // Overlapping strips store whole 64-byte lines, and whole lines can be STREAMED (nt): together that is worth 1.2 - 1.5x wherever the strips
-            // do not leave room for scouts (GCUPS, strips every 126 write-back / every 110 streaming, same buffers: int32 H 21760^2 278 (tiles) / 363,
-            // 24576^2 314 (tiles) / 409, 32768^2 382 (tiles) / 481, 40000^2 385 / 540, 49152^2 403 / 595, 65536^2 436 / 624, 81920^2 474 / 559; int64 H
-            // 20480^2 264 (scouts) / 330, 24576^2 238 / 369, 32768^2 265 / 409, 49152^2 282 / 403, 65536^2 382 / 451).  Streaming PARTIAL lines is what
-            // round 2 measured as harmful; write-back whole lines are what the first version of the overlap did (+14 % for int64 H only).  Behind
-            // scouts (up to 170 strips) the 126-column geometry stays: there the chain bounds the fill and 14 % more strips cost more than the
-            // stores gain (int32 16384^2: 335 / 322) -- except for an int64 H whose 110-column strips no longer fit beside scouts (18 700 - 21 400
-            // columns), which is faster as a plain chain of overlapping strips than behind scouts.
-            const bool wl_fmt = !band_io && j.d_H && (!j.d_P || j.p_elem_bytes == 4 || (j.h_elem_bytes == 4 && cols % 2 == 0)) && (j.d_P || cols % 2 == 0) && j.stride == cols + 1 &&
-                                ((uintptr_t)j.d_H & (j.h_elem_bytes == 8 ? 15u : 7u)) == 0 && ((uintptr_t)j.d_P & 7u) == 0;
-            const int64_t S126 = cols <= 126 ? 1 : (cols - 126 + 125) / 126 + 1, S110 = cols <= 126 ? 1 : (cols - 126 + 109) / 110 + 1;
-            // A pair that lies in ONE class of the HBM (the allocator's probe said so: its search ran out of budget, or the caller asked for a
-            // plain pair) is slowed much less when its lines are streamed whole: 16384^2 307 against 232 GCUPS with 126-column strips -- 7 % behind a
-            // pair in two classes instead of 30 %.  (Pairs the library did not allocate are not probed -- the probe writes -- and keep 126.)
-            bool one_class = false;
-            if (j.d_P && (double)cols * (double)rows >= 2.0e8) {
-                auto it = c->pair_ratio.find(j.d_P);
-                if (it == c->pair_ratio.end() && c->opt_probe_foreign && c->opt_s2w == 0 && wl_fmt && S126 <= 170 && !j.reserve_only) {
-                    // option "probe_foreign_pairs": a pair the library did not allocate is probed once, at its first fill -- the probe WRITES both
-                    // buffers (this fill overwrites them anyway) and synchronises the stream (~0.3 ms); remembered by the address of P (at most 64)
-                    float r = 0.f, ms = 0.f;
-                    if (c->pair_ratio.size() >= 64) c->pair_ratio.clear();
-                    if (hipStreamSynchronize(stream) == hipSuccess &&
-                        sw_place_pair_ratio(j.d_H, (size_t)(cols + 1) * (size_t)(rows + 1) * (size_t)j.h_elem_bytes, j.d_P, (size_t)(cols + 1) * (size_t)(rows + 1) * 4, &r, &ms) == SW_OK)
-                        it = c->pair_ratio.emplace(j.d_P, r).first;
-                }
-                one_class = it != c->pair_ratio.end() && it->second >= 1.7f;
-            }
-            if (c->opt_s2w == 110 ? (!band_io && (cols % 2 == 0 || wl_fmt)) : (c->opt_s2w == 0 && wl_fmt && (S126 > 170 || (j.h_elem_bytes == 8 && S110 > 170) || one_class))) W2 = 110;
-            const bool ov_auto = W2 == 110 && c->opt_s2w == 0;   // (the library's own choice: one launch, streaming stores)
-            auto strips_of = [&](int64_t ncols) { return ncols <= 126 ? (int64_t)1 : (ncols - 126 + W2 - 1) / W2 + 1; };
-            const int64_t S2all = strips_of(cols);
-            // Column tiles.  Scout workgroups beside one filler per strip (sw_systolic2.inc) need 1.5 .. 2 workgroups per strip: up to ~170
-            // strips (21 000 columns) on 256 CUs.  A wider matrix used to run the classic chain, fillers handing over to fillers at 7 us per
-            // strip (32768^2: 349 GCUPS).  Now it is cut into column tiles of at most 160 strips, ONE LAUNCH EACH, every one with scouts,
-            // roles per XCD and paced fillers; a tile's left halo is the previous tile's last column, read from H itself (kernel boundary:
-            // no flags), the arg-max accumulates in the key across the launches and the last one reports.  Taken where the estimate says
-            // it pays: not where the stores bound the fill anyway (int64 H at 65536^2), not for bands (their halo row arrives while they
-            // run).  (debug bit 19: off)
-            int64_t ntile = 1, tstrips = S2all;
-            if (S2all > 170 && base_mode && j.stride == cols + 1 && j.d_result && !ov_auto && !(c->opt_debug & 524288)) {
-                const int64_t nt = (S2all + 159) / 160, st = (S2all + nt - 1) / nt;
-                // measured (one box, GCUPS tiled / untiled): 24576^2 314 / 277, 32768^2 376 / 330, 40000^2 328 / 394, 49152^2 308 / 406 -- a tile
-                // ramps up and drains its chain with the stores idle (3.0 TB/s on average where the untiled fill of a big matrix keeps 3.3),
-                // so tiles pay while the untiled fill is bound by its 7 us hand-offs, up to ~36 000 columns
-                const double bytes = (double)(cols + 1) * (double)(rows + 1) * 8.0;
-                const double t_tiles = (double)nt * std::max((double)st * 2.4e-6 + (double)(rows + 200) * 26e-9, bytes / (double)nt / 3.0e12);
-                const double t_classic = std::max((double)S2all * 7.6e-6 + (double)rows * 35e-9, bytes / 3.3e12);
-                if (t_tiles < 0.98 * t_classic) { ntile = nt; tstrips = st; }
-            }
-            c->last_tiles = ntile;
-            for (int64_t tile = 0; tile < ntile; ++tile) {
-            const int64_t c0 = tile * tstrips * W2, tcols = tile + 1 == ntile ? cols - c0 : tstrips * W2;   // (a tile owns tstrips * W2 columns; the last one the rest)
-            const int64_t S2 = strips_of(tcols);
-            swk::FillParams p2 = p;
-            p2.nstrips = (int)S2;
-            p2.h_bytes = j.h_elem_bytes;
-            p2.cols = tcols;
-            p2.s2w = (int)W2;
-            if (ntile > 1) p2.store_nt = c->opt_store_policy == 2 || (c->opt_store_policy == 0 && (double)tcols * (double)rows <= 6.0e8);   // (per launch, as for a matrix of the tile's size)
-            if (W2 == 110 && wl_fmt && c->opt_store_policy == 0) p2.store_nt = 1;   // (whole lines: streamed)
-            p2.alpha_a = ua; p2.alpha_cols = cols;
-            p2.idx_off = c0; p2.final_launch = tile + 1 == ntile ? 1 : 0;
-            if (ntile > 1) {
-                p2.H = (char*)j.d_H + c0 * 4; p2.P = (int32_t*)((char*)j.d_P + c0 * 4);
-                p2.tile_left = tile ? (const int32_t*)j.d_H + c0 : nullptr;
-                if (tile) {   // the edge values of this context are self-tagged with the launch tag: every tile launch has its own
-                    if (++c->epoch8 >= (unsigned)((c->opt_debug & 1024) ? 4 : 256)) {
-                        const unsigned nb = (unsigned)std::max<size_t>(1, std::min<size_t>((c->edge4_cap + 255) / 256, 2048));
-                        hipLaunchKernelGGL(swk::sw_wipe_u32, dim3(nb), dim3(256), 0, stream, c->d_edge4, c->edge4_cap);
-                        c->epoch8 = 1;
-                    }
-                    p2.gbias = (c->epoch8 << 24) | 0x10000u;
-                }
-            }
-            const unsigned char* ua_t = ua + c0;
-            const int per_cu = per_cu2;
-            {
-                int grid2 = (int)std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(S2, maxb), (int64_t)per_cu * c->num_cus));
-                // Scouts (sw_systolic2.inc): while every strip has a workgroup of its own and half as many more fit the device, the chain
-                // of strips runs in extra workgroups that keep nothing but the edge columns, and the workgroups that write the matrices
-                // follow them instead of each other.  (debug bit 17: off)
-                // One scout strip per workgroup where the device has the workgroups for it (S2 fillers + S2 scouts), two in as many
-                // scout workgroups as it takes to fit; at least 1.5 S2 workgroups in all.
-                const int64_t avail = std::min<int64_t>(maxb, (int64_t)per_cu * c->num_cus);
-                const int64_t ndouble = std::max<int64_t>(0, 2 * S2 - 1 - avail);   // (the last strip needs no scout: nobody reads its edge)
-                const int64_t nsc = S2 - 1 - ndouble;
-                const bool scouts = S2 >= 4 && 2 * ndouble <= S2 - 1 && nsc >= 1 && !(c->opt_debug & 131072);
-                p2.nscout = scouts ? (int)nsc : 0;
-                p2.scout_double = scouts ? (int)ndouble : 0;
-                if (scouts) grid2 = (int)(S2 + nsc);
-                // Roles dealt per XCD (sw_systolic2.inc): an eighth of the fillers and the scouts that feed them on every XCD, so that
-                // an edge column is read on the XCD that wrote it -- out of its L2, without the trip through the memory fabric.  Needs the
-                // whole device (256 workgroups, one per CU, workgroup i on XCD i % 8).  (debug bit 23: off)
-                p2.xcd_mode = 0;
-                // measured (same buffers, classic against dealt per XCD): 24576^2 -1 %, 32768^2 -0.4 %, 65536^2 int32 +0.3 %, int64 H +2.3 %,
-                // 262144 x 32768 with int8 P +4.4 %: the classic hand-off is not the trip through memory (the polls of a filler queue behind
-                // its own H / P stores in the CU), so the gain is small and only where a workgroup runs several strips
-                // (with overlapping strips and streaming stores the dealing per XCD costs instead: 65536^2 int64 H 9.52 against 8.59 ms, int32 7.00 / 6.89, 24576^2 1.60 / 1.48)
-                const bool xcd_chain_pays = S2 >= 384 && W2 != 110;
-                if (scouts && c->xcd_round_robin && avail >= 256 && S2 >= 16 && !(c->opt_debug & 8388608)) {
-                    bool fits = true;
-                    int wg = 0, dbl = 0;
-                    for (int x = 0; x < 8 && fits; ++x) {
-                        const int nf = (int)(S2 / 8) + (x < (int)(S2 % 8) ? 1 : 0), ns = x ? nf : nf - 1;
-                        const int ndx = std::max(0, ns - (32 - nf));
-                        fits = nf <= 31 && 2 * ndx <= ns;
-                        wg += ns - ndx; dbl += ndx;
-                    }
-                    if (fits) { p2.xcd_mode = 1; p2.nscout = wg; p2.scout_double = dbl; grid2 = 256; }
-                }
-                // Split strips (sw_systolic2.inc): from strip split_from on -- those that would end after everybody else -- the strip's scout
-                // (a workgroup with rings and consumers then) writes the blocks from split_blk on and the filler only those before; the
-                // last strip gets a scout for it (one more workgroup on XCD 7).  The split point equalises the two ends: the filler needs
-                // tau_f per row, the scout ~21.5 ns before its consumers start and tau_f after.  Needs the per-XCD dealing and pacing (the
-                // common end every filler is paced to moves with it).  (debug bit 20: off)
-                p2.split_blk = 0; p2.split_from = 0; p2.split_extra = 0; p2.filler_end_steps = 0; p2.filler_full_steps = 0;
-                if (p2.xcd_mode == 1 && (rows >= 4096 || c->opt_split_blk > 0) && !j.d_top && !j.d_top_gran && !j.d_bot_gran && c->opt_filler_hop_ps > 0 &&
-                    !(c->opt_debug & (134217728 | 1048576))) {
-                    bool fits = true;
-                    int wg = 0, dbl = 0;
-                    for (int x = 0; x < 8 && fits; ++x) {
-                        const int nf = (int)(S2 / 8) + (x < (int)(S2 % 8) ? 1 : 0), ns = (x ? nf : nf - 1) + (x == 7 ? 1 : 0);
-                        const int ndx = std::max(0, ns - (32 - nf));
-                        fits = nf <= 31 && 2 * ndx <= ns;
-                        wg += ns - ndx; dbl += ndx;
-                    }
-                    const double hop = (double)c->opt_filler_hop_ps * 1e-12, tf = (double)c->opt_filler_tau_ps * 1e-12, ts = 21.5e-9;
-                    const int64_t nblk = (rows + 15) / 16;
-                    const int64_t sblk = (int64_t)((double)nblk * tf / (2.0 * tf - std::min(ts, tf)));
-                    const bool forced = c->opt_split_blk > 0;   // (tests: any split point, any first strip)
-                    if (fits && forced && c->opt_split_blk < nblk) {
-                        p2.split_blk = (int)c->opt_split_blk; p2.split_from = (int)std::max<int64_t>(1, c->opt_split_from); p2.split_extra = 1;
-                        p2.filler_end_steps = (int)((c->opt_split_blk * 16 + 126) / 64 * 64 + 64); p2.filler_full_steps = (int)((nblk * 16 + 126) / 64 * 64 + 64);
-                        p2.nscout = wg; p2.scout_double = dbl;
-                    } else if (fits && sblk >= 16 && sblk < nblk && rows >= 4096) {
-                        const int64_t full_steps = (nblk * 16 + 126) / 64 * 64 + 64, end_steps = (sblk * 16 + 126) / 64 * 64 + 64;
-                        // strip s, unsplit, would end s hand-offs + a whole strip after the start; the split ones end (S2 - 1) hand-offs + end_steps
-                        const double lead = ((double)full_steps - (double)end_steps) * tf / hop;
-                        const int64_t from = std::max<int64_t>(1, (int64_t)((double)(S2 - 1) - lead) + 1);
-                        if (from < S2) {
-                            p2.split_blk = (int)sblk; p2.split_from = (int)from; p2.split_extra = 1;
-                            p2.filler_end_steps = (int)end_steps; p2.filler_full_steps = (int)full_steps;
-                            p2.nscout = wg; p2.scout_double = dbl;
-                        }
-                    }
-                }
-                c->last_split_from = p2.split_blk ? p2.split_from : 0;
-                // The classic chain (no room for scouts), dealt per XCD the same way: neighbouring strips on one XCD, edge columns through
-                // its L2.  (option "xcd_chain": 0 auto, 1 on, 2 off)
-                if (!scouts && c->xcd_round_robin && grid2 >= 64 && !(c->opt_debug & 8388608) &&
-                    (c->opt_xcd_chain == 1 || (c->opt_xcd_chain == 0 && xcd_chain_pays)))
-                    p2.xcd_mode = 2;
-                // pacing of the fillers behind scouts (sw_systolic2.inc): estimates on the low side, so that nobody is held back more
-                // than the last filler's best case allows.  (options "filler_hop_ps" / "filler_tau_ps"; debug bit 27: off)
-                p2.filler_hop_ps = (scouts && !(c->opt_debug & 134217728)) ? (int)c->opt_filler_hop_ps : 0;
-                p2.filler_tau_ps = (int)c->opt_filler_tau_ps;
-                p2.filler_bw_gbs = (int)c->opt_filler_bw_gbs;
-                c->last_xcd_mode = p2.xcd_mode;
-                c->last_scouts = p2.nscout;
-                // one launch per fill: the kernel's prologue prepares (letter codes, every workgroup's padded copy of b, zeros in row 0 /
-                // column 0 -- except a band's halo row: its H comes from the row above, written by the kernel; its P belongs to the band
-                // above), its last workgroup out reports and re-arms key / abort flag / sync words -- which therefore are zero here, unless
-                // another kind of launch has used the key since
-                if (c->key_dirty) { HIP_TRY(hipMemsetAsync(c->d_key, 0, 16, stream)); c->key_dirty = false; }
-                p2.sync = c->d_sync; p2.priv = c->d_priv; p2.priv_stride = priv_stride;
-                p2.bpad16_w = d_cb16; p2.bpad8_w = c->d_cb; p2.bcode_w = d_cbc; p2.atab_w = c->d_alpha + 64;
-                p2.result = j.d_result; p2.skip_row0 = (j.d_top || j.d_top_gran) ? 1 : 0;
-                // consumer waves (+ 9 - nc2 importers).  Behind scouts a filler is never the one a hand-off waits for: two importers do, and seven
-                // consumers keep more stores in flight (16384^2 -1.5 %, 12288^2 -2.5 %, 20480^2 +-0 against five)
-                // (overlapping strips, whose consumers are dearer: seven as well -- 32768^2 485 against 453-466 GCUPS, 65536^2 633 / 607, int64 H 502 / 495)
-                const int nc2 = c->opt_consumers == 0 ? ((scouts || W2 == 110) ? 7 : (chain_bound ? 5 : 6)) : (int)std::min<int64_t>(7, c->opt_consumers);
-                auto launch2 = [&](auto nc, auto ov) { hipLaunchKernelGGL((swk::sw_systolic2<decltype(nc)::value, decltype(ov)::value>), dim3(grid2), dim3(768), 0, stream, ua_t, ub, p2); };
-                auto launch_nc = [&](auto ov) {
-                    if (nc2 == 7) launch2(std::integral_constant<int, 7>{}, ov);
-                    else if (nc2 == 6) launch2(std::integral_constant<int, 6>{}, ov);
-                    else if (nc2 == 5) launch2(std::integral_constant<int, 5>{}, ov);
-                    else launch2(std::integral_constant<int, 4>{}, ov);
-                };
-                if (W2 == 110) launch_nc(std::true_type{}); else launch_nc(std::false_type{});   // (the strip geometry is compiled in)
-                c->last_strips2 = S2;
-            }
-            }   // (tiles)
-            // the fall-back (an alphabet of more than 7 letters, known on the device only): enqueued behind, leaves at once otherwise;
-            // it fills the whole matrix by itself, whatever the tiling
-            p.skip_if_perm = 1;
-            p.sync = c->d_sync; p.atab_w = c->d_alpha + 64; p.result = j.d_result; p.final_launch = 1;
-            c->last_fused = true;
-        }
-        if (!two_cols) { prepare(nullptr, nullptr, false); c->key_dirty = true; }
-#define SW_LAUNCH(ns, nc)                                                                                                        \
-    if (!launched && NS == ns && NC == nc) {                                                                                      \
-        launched = true;                                                                                                          \
-        int per_cu = 0;                                                                                                           \
-        if (j.h_elem_bytes == 4) HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, swk::sw_systolic<int32_t, ns, nc>, threads, 0)); \
-        else HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, swk::sw_systolic<int64_t, ns, nc>, threads, 0));     \
-        if (per_cu < 1) { set_err("the fill kernel does not fit a CU on this device"); return SW_EDEVICE; }                      \
-        grid = (int)std::min<int64_t>(grid, (int64_t)per_cu * c->num_cus);                                                        \
-        c->last_grid = grid; c->last_strips = S;                                                                                  \
-        if (j.h_elem_bytes == 4)                                                                                                  \
-            hipLaunchKernelGGL((swk::sw_systolic<int32_t, ns, nc>), dim3(grid), dim3(threads), 0, stream, ua, ub, cbp, p);       \
-        else                                                                                                                      \
-            hipLaunchKernelGGL((swk::sw_systolic<int64_t, ns, nc>), dim3(grid), dim3(threads), 0, stream, ua, ub, cbp, p);       \
-    }
-        SW_LAUNCH(2, 2) SW_LAUNCH(2, 3) SW_LAUNCH(2, 4) SW_LAUNCH(1, 2) SW_LAUNCH(1, 3) SW_LAUNCH(1, 4) SW_LAUNCH(1, 6) SW_LAUNCH(1, 7)
-#undef SW_LAUNCH
-        if (!launched) { set_err("unsupported strips_per_group/consumers combination %d/%d", NS, NC); return SW_EINVAL; }
-    } else {
+    if (!systolic) {
         c->key_dirty = true;
-        const int wpb = (int)c->opt_waves_per_block;
-        const int64_t maxb = c->opt_max_blocks > 0 ? c->opt_max_blocks : 2ll * c->num_cus;
-        const int grid = (int)std::max<int64_t>(1, std::min<int64_t>((S + wpb - 1) / wpb, maxb));
-        c->last_grid = grid; c->last_strips = S;
+        c->last_grid = plan.grid;
         if (j.h_elem_bytes == 4)
-            hipLaunchKernelGGL((swk::sw_strip_scan<int32_t, 16>), dim3(grid), dim3(64 * wpb), 0, stream, ua, ub, p);
+            hipLaunchKernelGGL((swk::sw_strip_scan<int32_t, 16>), dim3(plan.grid), dim3(plan.threads), 0, stream, ua, ub, p);
         else
-            hipLaunchKernelGGL((swk::sw_strip_scan<int64_t, 16>), dim3(grid), dim3(64 * wpb), 0, stream, ua, ub, p);
+            hipLaunchKernelGGL((swk::sw_strip_scan<int64_t, 16>), dim3(plan.grid), dim3(plan.threads), 0, stream, ua, ub, p);
+        HIP_TRY(hipGetLastError());
+        return SW_OK;
     }
+    const size_t cb16 = ((c->cb_cap + 15) / 16) * 16;
+    unsigned short* d_cb16 = (unsigned short*)(c->d_cb + cb16);
+    unsigned char* d_cbc = c->d_cb + cb16 + ((2 * c->cb_cap + 15) / 16) * 16;
+    if (plan.perm) {
+        p.edge4 = c->d_edge4; p.e4stride = plan.e4stride; p.edge4_pstride = S * plan.e4stride;
+        p.gbias = next_gbias(c, stream);
+    }
+    p.bcode = d_cbc;
+    p.atab = c->d_alpha + 64;
+    p.phi_base = plan.fast ? (int)S - 1 : -1;
+    p.bfront = (int)plan.bfront;
+    p.bpad16 = d_cb16;
+    p.bpad8 = c->d_cb;
+    p.bpad_pstride = plan.per;
+    if (plan.two_cols) {
+        // one launch per tile: the kernel's prologue prepares (letter codes, every workgroup's padded copy of b, zeros in row 0 /
+        // column 0 -- except a band's halo row: its H comes from the row above, written by the kernel; its P belongs to the band
+        // above), its last workgroup out reports and re-arms key / abort flag / sync words -- which therefore are zero here, unless
+        // another kind of launch has used the key since
+        if (c->key_dirty) { HIP_TRY(hipMemsetAsync(c->d_key, 0, 16, stream)); c->key_dirty = false; }
+        for (int64_t tile = 0; tile < plan.ntile; ++tile) {
+            const swp::TilePlan& t = plan.tile[tile];
+            swk::FillParams p2 = p;
+            p2.nstrips = (int)t.strips; p2.cols = t.cols; p2.h_bytes = j.h_elem_bytes; p2.s2w = plan.W2; p2.store_nt = t.store_nt;
+            p2.alpha_a = ua; p2.alpha_cols = cols;
+            p2.idx_off = t.c0; p2.final_launch = tile + 1 == plan.ntile ? 1 : 0;
+            if (plan.ntile > 1) {   // a tile's left halo is the previous tile's last column, read from H itself
+                p2.H = (char*)j.d_H + t.c0 * 4; p2.P = (int32_t*)((char*)j.d_P + t.c0 * 4);
+                p2.tile_left = tile ? (const int32_t*)j.d_H + t.c0 : nullptr;
+                if (tile) p2.gbias = next_gbias(c, stream);   // (the edge values are self-tagged: every tile launch has its own tag)
+            }
+            p2.nscout = t.nscout; p2.scout_double = t.scout_double; p2.xcd_mode = t.xcd_mode;
+            p2.split_blk = t.split_blk; p2.split_from = t.split_from; p2.split_extra = t.split_extra;
+            p2.filler_end_steps = t.filler_end_steps; p2.filler_full_steps = t.filler_full_steps;
+            p2.filler_hop_ps = t.filler_hop_ps; p2.filler_tau_ps = t.filler_tau_ps; p2.filler_bw_gbs = t.filler_bw_gbs;
+            p2.sync = c->d_sync; p2.priv = c->d_priv; p2.priv_stride = plan.priv_stride;
+            p2.bpad16_w = d_cb16; p2.bpad8_w = c->d_cb; p2.bcode_w = d_cbc; p2.atab_w = c->d_alpha + 64;
+            p2.result = j.d_result; p2.skip_row0 = (j.d_top || j.d_top_gran) ? 1 : 0;
+            hipLaunchKernelGGL(kSystolic2[t.consumers - 4][plan.W2 == 110], dim3(t.grid), dim3(768), 0, stream, ua + t.c0, ub, p2);
+        }
+        // the fall-back (an alphabet of more than 7 letters, known on the device only): enqueued behind, leaves at once otherwise;
+        // it fills the whole matrix by itself, whatever the tiling
+        p.skip_if_perm = 1;
+        p.sync = c->d_sync; p.atab_w = c->d_alpha + 64; p.result = j.d_result; p.final_launch = 1;
+        c->last_fused = true;
+    } else {
+        // input preparation, two dispatches (sw_systolic.hip): presence maps of the letters, then codes / padded copies of b
+        const int64_t total = (cols + rows) * j.npairs;
+        const unsigned nscan = (unsigned)std::max<int64_t>(1, std::min<int64_t>((total + 1023) / 1024, 2048));
+        hipLaunchKernelGGL(swk::sw_prep_scan, dim3(nscan), dim3(256), 0, stream, ua, cols, j.a_pstride, ub, rows, j.b_pstride, j.npairs, c->d_part);
+        const unsigned npad = (unsigned)((plan.per + 255) / 256);
+        hipLaunchKernelGGL(swk::sw_prep_code, dim3(npad, (unsigned)j.npairs), dim3(256), 0, stream, ub, rows, plan.bfront, j.b_pstride, c->d_cb, d_cb16,
+                           d_cbc, (const unsigned int*)c->d_part, (int)nscan, c->d_alpha + 64, plan.per, (int)npad, (void*)nullptr, j.h_elem_bytes,
+                           (void*)nullptr, j.p_elem_bytes, cols + 1, rows + 1, 0, j.zero_key ? j.d_keys : nullptr);
+        c->key_dirty = true;
+    }
+    const SystolicKernel kern = j.h_elem_bytes == 4 ? one_col->h32 : one_col->h64;
+    int per_cu = 0;
+    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, plan.threads, 0));
+    if (per_cu < 1) { set_err("the fill kernel does not fit a CU on this device"); return SW_EDEVICE; }
+    c->last_grid = std::min<int64_t>(plan.grid, (int64_t)per_cu * c->num_cus);
+    hipLaunchKernelGGL(kern, dim3((unsigned)c->last_grid), dim3(plan.threads), 0, stream, ua, ub, (const unsigned char*)c->d_cb, p);
     HIP_TRY(hipGetLastError());
     return SW_OK;
 }
@@ -712,7 +492,7 @@ static int fill_one(sw_ctx* c, const sw_scores* scores, FillJob j, int64_t gcols
     if (order.rc) return order.rc;
     j.d_keys = c->d_key;
     j.d_result = d_result;
-    j.zero_key = c->opt_engine == 0 && cols > 0 && rows > 0;   // (the systolic engine's preparation zeroes the key and the abort flag -- or finds them zero)
+    j.zero_key = c->opt.engine == 0 && cols > 0 && rows > 0;   // (the systolic engine's preparation zeroes the key and the abort flag -- or finds them zero)
     if (!j.zero_key) { HIP_TRY(hipMemsetAsync(c->d_key, 0, 16, stream)); c->key_dirty = true; }
     c->last_fused = false;
     if (cols == 0 || rows == 0) {
@@ -773,7 +553,7 @@ int sw_fill_band_device(sw_ctx* c, const char* d_a, int64_t cols, const char* d_
         set_err("sw_fill_band_device: bad argument");
         return SW_EINVAL;
     }
-    if (c && c->opt_engine != 0) { set_err("sw_fill_band_device needs the systolic engine"); return SW_EINVAL; }
+    if (c && c->opt.engine != 0) { set_err("sw_fill_band_device needs the systolic engine"); return SW_EINVAL; }
     FillJob j = make_job(d_a, cols, d_b, rows, d_H, h_elem_bytes, d_P, p_elem_bytes, cols + 1, nullptr, nullptr, nullptr);
     j.d_top_gran = (const unsigned long long*)d_top_gran; j.d_bot_gran = (unsigned long long*)d_bot_gran; j.d_bot_done = d_bot_done;
     j.top_tag = top_tag; j.bot_tag = bot_tag; j.reserve_cus = reserve_cus; j.concurrent = concurrent != 0; j.total_rows = total_rows;
@@ -824,10 +604,10 @@ static int batch_one_pair_per_wave(sw_ctx* c, const char* d_a, int64_t a_stride,
     unsigned int nletters = 0;
     // Score-only batches whose scores fit 15 bits run two pairs per wave on packed 16-bit lanes (sw_batch_wave16: 5 VALU per two cells
     // instead of 8).  (debug bit 18: off, A/B runs)
-    const bool fits16 = npairs >= 2 && C == 16 && (int64_t)sc->match * std::min(cols, rows) < 32000 && -sc->gap < 32000 && rows < 65000 && !(c->opt_debug & 262144);
+    const bool fits16 = npairs >= 2 && C == 16 && (int64_t)sc->match * std::min(cols, rows) < 32000 && -sc->gap < 32000 && rows < 65000 && !(c->opt.debug_flags & swk::DBG_BATCH_NO_WAVE16);
     const bool k12 = (int64_t)sc->match * std::min(cols, rows) < 4096;   // (scores of 12 bits: the arg-max runs on score * 16 + column keys)
     // ... and with an int8 P as the only matrix, P codes from packed arithmetic (debug bit 21: off)
-    const bool packed16 = fits16 && !d_H && (!d_P || (p_elem_bytes == 1 && !(c->opt_debug & 2097152)));
+    const bool packed16 = fits16 && !d_H && (!d_P || (p_elem_bytes == 1 && !(c->opt.debug_flags & swk::DBG_BATCH_NO_PACKED_P)));
     for (int64_t k0 = 0; k0 < npairs; k0 += chunk) {
         const int64_t n = std::min(chunk, npairs - k0);
         hipLaunchKernelGGL(swk::sw_batch_codes, dim3((unsigned)std::min<int64_t>((per + 255) / 256, 64), (unsigned)std::min<int64_t>(n, 65535)), dim3(256), 0, stream,
@@ -849,7 +629,7 @@ static int batch_one_pair_per_wave(sw_ctx* c, const char* d_a, int64_t a_stride,
         bp.match = sc->match; bp.mismatch = sc->mismatch; bp.ngap = -sc->gap;
         bp.bnd = c->d_bnd; bp.bnd_pstride = bnd_per;
         bp.results = d_results + k0;
-        bp.debug = (int)(c->opt_debug & 7);   // bit 0: no matrix stores, bit 1: nt stores, bit 2: sc1 stores (experiments)
+        bp.debug = (int)(c->opt.debug_flags & swk::DBG_BATCH_MASK);
         const int pb = d_P ? p_elem_bytes : 0;
         if (packed16 && n >= 2) {
             const dim3 grid16((unsigned)(((n + 1) / 2 + 3) / 4)), block16(256);   // 4 waves = 8 pairs per workgroup
@@ -869,7 +649,7 @@ static int batch_one_pair_per_wave(sw_ctx* c, const char* d_a, int64_t a_stride,
         HIP_TRY(hipGetLastError());
     }
     if (c->last_batch_kernel != 2) c->last_batch_kernel = 1;
-    c->last_grid = (chunk + 3) / 4; c->last_strips = nstrips;
+    c->last_grid = (chunk + 3) / 4; c->last_plan.S = nstrips;   // (sw_get_option "last_grid", "last_strips")
     return SW_OK;
 }
 
@@ -881,15 +661,19 @@ int sw_fill_band_reserve(sw_ctx* c, int64_t cols, int64_t rows, int64_t total_ro
                          void* stream_) {
     const sw_scores* sc = scores ? scores : &kDefaultScores;
     if (!c || cols <= 0 || rows <= 0) { set_err("sw_fill_band_reserve: bad argument"); return SW_EINVAL; }
-    if (c->opt_engine != 0) { set_err("sw_fill_band_reserve needs the systolic engine"); return SW_EINVAL; }   // (no placeholder pointer may reach a launch)
+    if (c->opt.engine != 0) { set_err("sw_fill_band_reserve needs the systolic engine"); return SW_EINVAL; }
     if (int rc = check_dims(cols, rows, sc, cols, total_rows)) return rc;
     HIP_TRY(hipSetDevice(c->device));
-    FillJob j = make_job((const char*)16, cols, (const char*)16, rows, want_h ? (void*)16 : nullptr, h_elem_bytes, (void*)16, p_elem_bytes, cols + 1, nullptr, nullptr, nullptr);
-    j.d_top_gran = (const unsigned long long*)16; j.d_bot_gran = (unsigned long long*)16;   // (placeholders: only their presence matters)
-    j.top_tag = j.bot_tag = 1; j.total_rows = total_rows; j.concurrent = true; j.reserve_only = true;
-    j.d_keys = c->d_key; j.d_result = (sw_result*)16;
+    swp::PlanJob pj;   // (a band: halo row in and last row out as granules, a result of its own)
+    pj.cols = cols; pj.rows = rows; pj.total_rows = total_rows; pj.h_elem_bytes = h_elem_bytes; pj.p_elem_bytes = p_elem_bytes; pj.has_H = want_h != 0;
+    pj.has_top_gran = pj.has_bot_gran = true;
+    pj.match = sc->match; pj.mismatch = sc->mismatch; pj.gap = sc->gap;
+    swp::FillPlan plan;
+    if (int rc = plan_for(c, pj, plan)) return rc;
     std::unique_lock<std::mutex> lk(g_dev[c->device & 63].mu);
-    return launch_fill(c, sc, j, (hipStream_t)stream_);
+    if (int rc = ensure_workspaces(c, plan, (hipStream_t)stream_)) return rc;
+    HIP_TRY(hipStreamSynchronize((hipStream_t)stream_));   // (every workspace exists now, and is wiped where fresh)
+    return SW_OK;
 }
 
 // BASELINE config 5: npairs independent cols x rows problems; pair k reads a at d_a + k*a_stride, b at d_b + k*b_stride.
@@ -903,14 +687,14 @@ int sw_batch_device_ex(sw_ctx* c, const char* d_a, int64_t a_stride, int64_t col
         set_err("sw_batch_device: bad argument");
         return SW_EINVAL;
     }
-    if (c->opt_engine != 0) { set_err("sw_batch_device needs the systolic engine"); return SW_EINVAL; }
+    if (c->opt.engine != 0) { set_err("sw_batch_device needs the systolic engine"); return SW_EINVAL; }
     if (int rc = check_dims(cols, rows, sc)) return rc;
     hipStream_t stream = (hipStream_t)stream_;
     HIP_TRY(hipSetDevice(c->device));
     DevOrder order(c, stream, false);
     if (order.rc) return order.rc;
     c->last_batch_kernel = 0;
-    if (!(c->opt_debug & 65536)) {   // (debug bit 16: keep the batch on the single-pair machinery, A/B runs)
+    if (!(c->opt.debug_flags & swk::DBG_BATCH_SINGLE_PAIR)) {
         int rc = batch_one_pair_per_wave(c, d_a, a_stride, cols, d_b, b_stride, rows, npairs, sc, d_H, d_P, p_elem_bytes, d_results, stream);
         if (rc != 1) return rc;      // 1: not eligible (alphabet of more than 8 letters, scores beyond a byte, huge pairs)
     }
@@ -1093,7 +877,6 @@ int sw_traceback_device(sw_ctx* c, int32_t* d_P, int64_t cols, int64_t rows, int
 // spacer allocation, so that they come from elsewhere in the HBM -- are CLASSIFIED against H with the two-stream store probe of
 // csrc/sw_place.hip (~0.3 ms per candidate, no fill of the caller's problem), the first one in another class is kept.  trials == 1: a plain
 // pair.  trials > 1: round 3's search with trial fills of the caller's problem (kept for A/B runs).
-int sw_place_pair_ratio(void* d_X, size_t xbytes, void* d_Y, size_t ybytes, float* ratio, float* ms_together);   // sw_place.hip
 
 static int alloc_outputs_probed(sw_ctx* c, size_t hbytes, size_t pbytes, void** d_H, void** d_P, float* trial_ms, int ntrial_ms) {
     const size_t phase = 4u << 20;

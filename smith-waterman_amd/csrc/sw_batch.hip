@@ -171,7 +171,7 @@ __global__ void __launch_bounds__(256) sw_batch_wave(BatchParams p) {
         int diag0 = 0, lbest = 0, lk = 0, lstep = 0;
         // output offsets of my row segment at step u = 0 (row -lane): wraps to a huge unsigned offset above the matrix, runs past
         // the descriptor below it -- stores outside rows 0..rows are dropped by the bounds check.  (Row 0 is stored too: H = P = 0.)
-        const bool full = nval == C && !(p.debug & 1);   // (debug bit 0: drop the matrix stores, timing experiments)
+        const bool full = nval == C && !(p.debug & DBG_NO_STORES);   // (debug bit 0: drop the matrix stores, timing experiments)
         u32 voffH = (full && wh) ? (u32)((-lane * M + c0) * 4) : SB_OOB;
         u32 voffP = (full && wp) ? (u32)((-lane * M + c0) * PB) : SB_OOB;
         // int8 P: delayed stores through the LDS ring (see the store below): this lane's piece leaves 1 + dly steps late
@@ -488,7 +488,7 @@ __global__ void __launch_bounds__(256, PB1 ? 2 : (LE4 ? 4 : 3)) sw_batch_wave16(
         // P stores (PB1): as in sw_batch_wave -- my piece of row u - lane leaves 1 + dly steps late, so that the 16 lanes of a group store
         // 256 contiguous bytes of ONE row per instruction
         const int nval = min(C, max(0, cols - c0 + 1));
-        const bool full = PB1 && nval == C && !(p.debug & 1);
+        const bool full = PB1 && nval == C && !(p.debug & DBG_NO_STORES);
         int foff = 0;
         u32 voffP = full ? (u32)(-lane * M + c0) - (u32)((1 + dly) * M) : SB_OOB;
         const bool col0 = PB1 && st == 0 && lane == 0;
@@ -563,7 +563,7 @@ __global__ void __launch_bounds__(256, PB1 ? 2 : (LE4 ? 4 : 3)) sw_batch_wave16(
                     if (ragged) {   // the lane that holds the matrix's last columns: byte by byte, undelayed
 #pragma unroll
                         for (int k = 0; k < C - 1; ++k)
-                            if (!full && k < nval && !(p.debug & 1)) {
+                            if (!full && k < nval && !(p.debug & DBG_NO_STORES)) {
                                 const u32 off = (u32)((u - lane) * M + c0 + k);
                                 __builtin_amdgcn_raw_buffer_store_b8((unsigned char)(pc[k] & 0xffu), rPA, (int)off, 0, 0);
                                 __builtin_amdgcn_raw_buffer_store_b8((unsigned char)((pc[k] >> 16) & 0xffu), rPB, (int)off, 0, 0);

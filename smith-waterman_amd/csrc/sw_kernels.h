@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/swhip.h"
+#include "sw_debug.h"
 
 namespace swk {
 
@@ -35,7 +36,7 @@ struct FillParams {
     int store_nt;              // systolic: streaming (nt) H/P stores
     int xcd_order;             // systolic: neighbouring strip groups on one XCD
     int pace_ps;               // systolic: strip 0 releases one row per pace_ps picoseconds (0 = unpaced)
-    int debug_flags;           // bit0: drop the H/P stores (timing experiments only)
+    int debug_flags;           // development aids: swk::DebugFlag (sw_debug.h)
     int nstrips;               // strip_scan: ceil(cols/64); systolic: ceil(cols/63)
     // band-resident launch (systolic; multi-GPU row bands): the halo row arrives / leaves as 8-byte
     // {tag, H value} granules, one per column, while the kernel runs

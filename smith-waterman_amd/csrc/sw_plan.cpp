@@ -1,0 +1,267 @@
+// sw_plan.cpp -- the fill planner (sw_plan.h).  No side effects, no allocation, no runtime calls.
+#include "sw_plan.h"
+#include <algorithm>
+
+namespace swp {
+
+// ---- measured constants (MI355X, 256 CUs).  Changing one is a change of policy: tests/test_fill_plan.py has each threshold from both sides.
+//
+// Workgroup shape of the one-column kernel.  One strip + 8 consumers per workgroup gives every producer a SIMD of its own (measured on
+// single pairs from 4096^2 to 32768^2: equal to 5 % faster than 2 + 2x4, equal at 65536^2) -- while the strips fit the CUs 4.5 times;
+// batches that do not fit the CUs at once run two strips per workgroup, twice the work per CU (1024^2 pairs: 415 vs 194 GCUPS for
+// 20000 pairs, 203 vs 143 for 64).
+constexpr double kOneStripPerCu = 4.5;
+// A chain-bound fill (one pair, up to ~3.5e8 cells: 16384^2) wants the hand-off found early -- 4 consumers + 5 importer waves: 240 vs
+// 232 GCUPS at 16384^2, +7 % at 8192^2; bigger fills are bound by the stores and want 6 consumers + 3 importer waves (65536^2: 389 vs
+// 340 GCUPS).
+constexpr double kChainBoundCells = 3.5e8;
+// Streaming stores pay off while the matrices are small next to what is in flight; measured cross-over between 16384^2 (nt 15-18 %
+// faster) and 32768^2 (write-back 2-20 % faster).
+constexpr double kStreamCells = 6.0e8;
+// Where the two-column kernel pays: always for int32 H + P (8-byte stores of both matrices); in the other output formats while the
+// strip chain (~3.1 us per 63-column strip) rather than the output volume (~3.2 TB/s) bounds the fill -- measured: 262144 x 32768
+// with int8 P +18 %, 131072^2 with int8 P -3 %, 262144^2 P-only -21 % (two byte stores per row and the in-block arg-max).
+constexpr double kChainSecPerStrip = 3.1e-6, kHbmBytesPerSec = 3.2e12;
+// Scouts beside one filler per strip need 1.5 .. 2 workgroups per strip: up to ~170 strips (21 000 columns) on 256 CUs.
+constexpr int64_t kScoutStrips = 170;
+// A pair that lies in ONE class of the HBM (store probe ratio >= 1.7) and has at least 2e8 cells is slowed much less when its lines are
+// streamed whole: 16384^2 307 against 232 GCUPS with 126-column strips -- 7 % behind a pair in two classes instead of 30 %.
+constexpr double kOneClassCells = 2.0e8;
+constexpr float kOneClassRatio = 1.7f;
+// Column tiles of at most 160 strips.  Measured (one box, GCUPS tiled / untiled): 24576^2 314 / 277, 32768^2 376 / 330, 40000^2 328 /
+// 394, 49152^2 308 / 406 -- a tile ramps up and drains its chain with the stores idle (3.0 TB/s on average where the untiled fill of a
+// big matrix keeps 3.3), so tiles pay while the untiled fill is bound by its 7 us hand-offs, up to ~36 000 columns.  Estimates: a tile
+// hands over every 2.4 us and takes 26 ns per row (+200 rows of ramp), the classic chain 7.6 us per hand-off and 35 ns per row;
+// tiles are taken when they are estimated at least 2 % faster.
+constexpr int64_t kTileStrips = 160;
+constexpr double kTileHopSec = 2.4e-6, kTileRowSec = 26e-9, kTileBytesPerSec = 3.0e12;
+constexpr double kClassicHopSec = 7.6e-6, kClassicRowSec = 35e-9, kClassicBytesPerSec = 3.3e12;
+constexpr double kTileGain = 0.98;
+// Roles dealt per XCD in the classic chain pay only where a workgroup runs several strips (same buffers, classic against dealt per XCD:
+// 24576^2 -1 %, 32768^2 -0.4 %, 65536^2 int32 +0.3 %, int64 H +2.3 %, 262144 x 32768 with int8 P +4.4 %: the classic hand-off is not
+// the trip through memory -- the polls of a filler queue behind its own H / P stores in the CU); with overlapping strips and streaming
+// stores the dealing costs instead: 65536^2 int64 H 9.52 against 8.59 ms, int32 7.00 / 6.89, 24576^2 1.60 / 1.48.
+constexpr int64_t kXcdChainStrips = 384;
+// Split strips: a scout runs ~21.5 ns ahead of its consumers; fills of fewer rows are not split.
+constexpr double kScoutLeadSec = 21.5e-9;
+constexpr int64_t kSplitRows = 4096;
+
+namespace {
+
+// Roles dealt per XCD (workgroup i on XCD i % 8, 32 CUs each): an eighth of the fillers on every XCD and the scouts that feed them,
+// two strips to a scout where the XCD has no room for one each.  The last strip needs no scout (one fewer on XCD 0); split strips
+// give it one (one more on XCD 7).
+struct Deal { bool fits = true; int scouts = 0, doubles = 0; };
+Deal deal_per_xcd(int64_t S2, bool last_strip_scout) {
+    Deal r;
+    for (int x = 0; x < 8 && r.fits; ++x) {
+        const int nf = (int)(S2 / 8) + (x < (int)(S2 % 8) ? 1 : 0), ns = (x ? nf : nf - 1) + (last_strip_scout && x == 7 ? 1 : 0);
+        const int ndx = std::max(0, ns - (32 - nf));
+        r.fits = nf <= 31 && 2 * ndx <= ns;
+        r.scouts += ns - ndx; r.doubles += ndx;
+    }
+    return r;
+}
+
+}  // namespace
+
+FillPlan plan_fill(const PlanJob& j, const DeviceFacts& dev, const PlanOptions& o) {
+    using namespace swk;
+    FillPlan f;
+    const int64_t cols = j.cols, rows = j.rows;
+    const bool systolic = o.engine == 0;
+    f.engine = systolic ? 0 : 1;
+    const int64_t S = f.S = systolic ? (cols + 62) / 63 : (cols + 63) / 64;
+    f.edge_need = (size_t)S * (size_t)(rows + 1) * (size_t)j.npairs;
+    f.h_bytes = (size_t)(cols + 1) * (size_t)(rows + 1) * (size_t)j.h_elem_bytes;
+    f.p_bytes = (size_t)(cols + 1) * (size_t)(rows + 1) * (size_t)j.p_elem_bytes;
+    f.store_nt = o.store_policy == 2 || (o.store_policy == 0 && (double)cols * (double)rows * (double)j.npairs <= kStreamCells);
+    if (!systolic) {
+        const int wpb = (int)o.waves_per_block;
+        const int64_t maxb = o.max_blocks > 0 ? o.max_blocks : 2ll * dev.num_cus;
+        f.grid = (int)std::max<int64_t>(1, std::min<int64_t>((S + wpb - 1) / wpb, maxb));
+        f.threads = 64 * wpb;
+        return f;
+    }
+    int NS = (int)o.strips_per_group, NC = (int)o.consumers;
+    if (NS == 0) NS = (j.npairs == 1 ? (double)S <= kOneStripPerCu * dev.num_cus : (double)S * (double)j.npairs <= (double)dev.num_cus) ? 1 : 2;
+    // NS == 1: nine waves on the three SIMDs the producer leaves
+    const bool chain_bound = NS == 1 && j.npairs == 1 && (double)cols * (double)rows <= kChainBoundCells;
+    if (NC == 0) NC = (NS == 1) ? (chain_bound ? 4 : 6) : 4;
+    f.importers = o.importers > 0 ? (int)o.importers : (chain_bound && NC <= 4 ? 4 : 2);
+    if (NS == 1 && NC > 7) NC = 7;         // nine waves off the producer's SIMD: at most 7 consumers + exporter + importer
+    if (NS == 1 && NC == 5) NC = 4;        // (the one-column kernel has no five-consumer form: option "consumers" = 5 is for the two-column kernel)
+    f.NS = NS; f.NC = NC;
+    // padded copies of b per problem: [front | b | tail]; front covers the fast producers' phi (< strips) + 63 lanes
+    // (+ one 16-step block: the perm producer's first score window ends at step 0)
+    f.bfront = ((S + 64 + 32 + 127) / 128) * 128;
+    f.per = ((rows + f.bfront + 512 + 15) / 16) * 16;
+    f.cb_need = (size_t)f.per * (size_t)j.npairs;
+    // perm producer (alphabets of up to 7 letters): eligible when the scores fit a signed byte and every G value,
+    // with the 2^16 bias, stays below 2^24 (the top byte carries the launch tag)
+    const int64_t mm = j.match - 2 * j.gap, xm = j.mismatch - 2 * j.gap;
+    const int64_t lo = std::min(cols, rows);
+    const int64_t gmax = (int64_t)j.match * std::max<int64_t>(lo, std::min(cols, j.total_rows)) + (int64_t)(-j.gap) * (rows + cols + 2);
+    const bool halo_unbounded = (j.has_top || j.has_left) && j.total_rows == 0;   // a tile whose halo magnitudes are unknown here
+    f.perm = !halo_unbounded && mm <= 127 && mm >= -127 && xm <= 127 && xm >= -127 && gmax + 0x10000 + 1024 < (1ll << 24) &&
+             !(o.debug_flags & DBG_NO_PERM);
+    if (f.perm) {
+        f.e4stride = ((rows + S + 160 + 31) / 32) * 32;   // (whole 128-byte lines: strips written on different XCDs share none)
+        f.edge4_need = (size_t)S * (size_t)f.e4stride * (size_t)j.npairs;
+    }
+    f.fast = !j.has_top && !j.has_top_gran && j.mismatch <= 0 && !(o.debug_flags & DBG_GENERIC_PRODUCER);
+    const int64_t ngroups = ((S + NS - 1) / NS) * j.npairs;
+    const int64_t maxb = o.max_blocks > 0 ? o.max_blocks : std::max<int64_t>(8, (int64_t)dev.num_cus - j.reserve_cus);
+    f.grid = (int)std::max<int64_t>(1, std::min<int64_t>(ngroups, maxb));
+    if (NS == 1) {
+        // wave 0 (the producer) owns SIMD 0: waves 4, 8, 12 idle; consumers, the exporter and the importers are the
+        // K waves off SIMD 0 (wave id of ordinal k: k + 1 + k/3)
+        const int K = std::min<int>(9, NC + 1 + std::max(1, f.importers));   // 12 waves: 3 per SIMD
+        f.threads = 64 * (K + (K - 1) / 3 + 1);
+    } else {
+        f.threads = 64 * (NS * (1 + NC) + 2);
+    }
+
+    // Two matrix columns per lane (sw_systolic2.inc): half as many strips -- and row segments of 504 bytes per store -- for the
+    // same work: 16384^2 +4 %, 8192^2 +11 %, 24576^2 +29 %, 32768^2 +32 %, 65536^2 +9 % over one column per lane.  Whole
+    // matrix of one pair, int32 H and P both stored, rows a multiple of 16; the alphabet (found on the device) must allow the
+    // perm path -- so both kernels are enqueued and each checks for itself which of them has to work.
+    // Also: int8 P, either matrix left out, and band-resident launches (halo row in, last row out as granules).
+    const bool base_mode = j.has_H && j.has_P && j.h_elem_bytes == 4 && j.p_elem_bytes == 4 && !j.has_top && !j.has_top_gran && !j.has_bot_gran;   // int32 H + P, whole matrix
+    const double est_chain = (double)S * kChainSecPerStrip;
+    const double est_hbm = (double)(cols + 1) * (double)(rows + 1) * ((j.has_H ? (double)j.h_elem_bytes : 0.0) + (j.has_P ? (double)j.p_elem_bytes : 0.0)) / kHbmBytesPerSec;
+    // (... and int32 H + int8 P or H alone beyond the reach of the scouts: the H of overlapping strips goes out in streamed whole lines --
+    //  65536^2 597 GCUPS against 429 on the one-column kernel and 494 with 126-column strips)
+    const bool pays = (j.has_H && j.has_P && j.p_elem_bytes == 4) || (j.has_H && j.h_elem_bytes == 8) || est_chain >= (j.has_H ? 0.5 : 2.0) * est_hbm ||
+                      (o.debug_flags & DBG_FORCE_TWO_COLUMNS) ||
+                      (j.has_H && j.h_elem_bytes == 4 && (!j.has_P || j.p_elem_bytes == 1) && cols % 2 == 0 && cols > 126 * kScoutStrips);
+    // The two-column kernel is ONE launch per fill: its prologue does what sw_prep_scan / sw_prep_code do for the other kernels (every
+    // workgroup keeps its own padded copy of b and of its letter codes) and its last workgroup out writes the result (sw_systolic2.inc).
+    // The strict one-launch path needs a result to write (a batch keeps its own keys and never comes here).
+    f.two_cols = pays && f.perm && o.strips_per_group == 0 && (o.consumers == 0 || o.consumers >= 4) && j.npairs == 1 &&
+                 !j.has_left && !j.has_right && j.full_stride && (rows % 16 == 0 || !j.has_bot_gran) && rows >= 1 && cols >= 1 &&   // (a band's last row leaves from a full block)
+                 (base_mode || (cols % 2 == 0)) &&   // (an odd column count leaves one lane with a single column: only the base mode handles it)
+                 !(o.debug_flags & (DBG_PRODUCER_ONLY | DBG_SKIP_STRIP1 | DBG_WAVE_PLACEMENT | DBG_BLOCK_STAMPS | DBG_EDGE_DUMP | DBG_NO_TWO_COLUMNS)) &&
+                 dev.s2_per_cu >= 1 && j.has_result;
+    f.priv_stride = ((2 * f.per + 255) / 256) * 256;
+    if (!f.two_cols) return f;
+    f.priv_need = (size_t)f.priv_stride * (size_t)dev.s2_per_cu * (size_t)dev.num_cus;
+
+    // Strip geometry: every 126 columns (the strips tile the matrix), or every 110 with 16 columns of overlap -- whole-line stores
+    // (sw_systolic2.inc); option "s2w" forces one of the two (tests, A/B runs).
+    // Overlapping strips store whole 64-byte lines, and whole lines can be STREAMED (nt): together that is worth 1.2 - 1.5x wherever the strips
+    // do not leave room for scouts (GCUPS, strips every 126 write-back / every 110 streaming, same buffers: int32 H 21760^2 278 (tiles) / 363,
+    // 24576^2 314 (tiles) / 409, 32768^2 382 (tiles) / 481, 40000^2 385 / 540, 49152^2 403 / 595, 65536^2 436 / 624, 81920^2 474 / 559; int64 H
+    // 20480^2 264 (scouts) / 330, 24576^2 238 / 369, 32768^2 265 / 409, 49152^2 282 / 403, 65536^2 382 / 451).  Streaming PARTIAL lines is what
+    // round 2 measured as harmful; write-back whole lines are what the first version of the overlap did (+14 % for int64 H only).  Behind
+    // scouts (up to 170 strips) the 126-column geometry stays: there the chain bounds the fill and 14 % more strips cost more than the
+    // stores gain (int32 16384^2: 335 / 322) -- except for an int64 H whose 110-column strips no longer fit beside scouts (18 700 - 21 400
+    // columns), which is faster as a plain chain of overlapping strips than behind scouts.
+    const bool band_io = j.has_top || j.has_top_gran || j.has_bot_gran;
+    const bool wl_fmt = !band_io && j.has_H && (!j.has_P || j.p_elem_bytes == 4 || (j.h_elem_bytes == 4 && cols % 2 == 0)) && (j.has_P || cols % 2 == 0) &&
+                        j.full_stride && j.h_aligned && j.p_aligned;
+    const int64_t S126 = cols <= 126 ? 1 : (cols - 126 + 125) / 126 + 1, S110 = cols <= 126 ? 1 : (cols - 126 + 109) / 110 + 1;
+    // A pair in one class of the HBM: the allocator's probe knows (its search ran out of budget, or the caller asked for a plain pair).  Pairs
+    // the library did not allocate are probed only with option "probe_foreign_pairs" -- the probe writes -- and keep 126 otherwise.
+    bool one_class = false;
+    if (j.has_P && (double)cols * (double)rows >= kOneClassCells) {
+        f.probe_pair_class = j.pair_ratio == 0.f && o.probe_foreign_pairs && o.s2w == 0 && wl_fmt && S126 <= kScoutStrips;
+        one_class = j.pair_ratio >= kOneClassRatio;
+    }
+    int64_t W2 = 126;
+    if (o.s2w == 110 ? (!band_io && (cols % 2 == 0 || wl_fmt))
+                     : (o.s2w == 0 && wl_fmt && (S126 > kScoutStrips || (j.h_elem_bytes == 8 && S110 > kScoutStrips) || one_class)))
+        W2 = 110;
+    f.W2 = (int)W2;
+    const bool ov_auto = W2 == 110 && o.s2w == 0;   // (the library's own choice: one launch, streaming stores)
+    auto strips_of = [&](int64_t ncols) { return ncols <= 126 ? (int64_t)1 : (ncols - 126 + W2 - 1) / W2 + 1; };
+    const int64_t S2all = strips_of(cols);
+    // Column tiles.  A matrix wider than the scouts reach used to run the classic chain, fillers handing over to fillers at 7 us per
+    // strip (32768^2: 349 GCUPS).  Now it is cut into column tiles, ONE LAUNCH EACH, every one with scouts, roles per XCD and paced
+    // fillers; a tile's left halo is the previous tile's last column, read from H itself (kernel boundary: no flags), the arg-max
+    // accumulates in the key across the launches and the last one reports.  Taken where the estimate says it pays: not where the
+    // stores bound the fill anyway (int64 H at 65536^2), not for bands (their halo row arrives while they run).
+    f.tstrips = S2all;
+    if (S2all > kScoutStrips && base_mode && j.full_stride && j.has_result && !ov_auto && !(o.debug_flags & DBG_NO_TILES)) {
+        const int64_t nt = (S2all + kTileStrips - 1) / kTileStrips, st = (S2all + nt - 1) / nt;
+        const double bytes = (double)(cols + 1) * (double)(rows + 1) * 8.0;
+        const double t_tiles = (double)nt * std::max((double)st * kTileHopSec + (double)(rows + 200) * kTileRowSec, bytes / (double)nt / kTileBytesPerSec);
+        const double t_classic = std::max((double)S2all * kClassicHopSec + (double)rows * kClassicRowSec, bytes / kClassicBytesPerSec);
+        if (t_tiles < kTileGain * t_classic) { f.ntile = nt; f.tstrips = st; }
+    }
+    const int64_t per_cu = dev.s2_per_cu;
+    for (int64_t tile = 0; tile < f.ntile; ++tile) {
+        TilePlan& t = f.tile[tile];
+        t.c0 = tile * f.tstrips * W2;
+        t.cols = tile + 1 == f.ntile ? cols - t.c0 : f.tstrips * W2;   // (a tile owns tstrips * W2 columns; the last one the rest)
+        const int64_t S2 = t.strips = strips_of(t.cols);
+        t.store_nt = f.store_nt;
+        if (f.ntile > 1) t.store_nt = o.store_policy == 2 || (o.store_policy == 0 && (double)t.cols * (double)rows <= kStreamCells);   // (per launch, as for a matrix of the tile's size)
+        if (W2 == 110 && wl_fmt && o.store_policy == 0) t.store_nt = 1;   // (whole lines: streamed)
+        t.grid = (int)std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(S2, maxb), per_cu * dev.num_cus));
+        // Scouts (sw_systolic2.inc): while every strip has a workgroup of its own and half as many more fit the device, the chain
+        // of strips runs in extra workgroups that keep nothing but the edge columns, and the workgroups that write the matrices
+        // follow them instead of each other.  One scout strip per workgroup where the device has the workgroups for it (S2 fillers
+        // + S2 scouts), two in as many scout workgroups as it takes to fit; at least 1.5 S2 workgroups in all.
+        const int64_t avail = std::min<int64_t>(maxb, per_cu * dev.num_cus);
+        const int64_t ndouble = std::max<int64_t>(0, 2 * S2 - 1 - avail);   // (the last strip needs no scout: nobody reads its edge)
+        const int64_t nsc = S2 - 1 - ndouble;
+        const bool scouts = S2 >= 4 && 2 * ndouble <= S2 - 1 && nsc >= 1 && !(o.debug_flags & DBG_NO_SCOUTS);
+        t.nscout = scouts ? (int)nsc : 0;
+        t.scout_double = scouts ? (int)ndouble : 0;
+        if (scouts) t.grid = (int)(S2 + nsc);
+        // Roles dealt per XCD (sw_systolic2.inc): an eighth of the fillers and the scouts that feed them on every XCD, so that an edge
+        // column is read on the XCD that wrote it -- out of its L2, without the trip through the memory fabric.  Needs the whole device
+        // (256 workgroups, one per CU, workgroup i on XCD i % 8).
+        if (scouts && dev.xcd_round_robin && avail >= 256 && S2 >= 16 && !(o.debug_flags & DBG_NO_XCD_DEALING)) {
+            const Deal d = deal_per_xcd(S2, false);
+            if (d.fits) { t.xcd_mode = 1; t.nscout = d.scouts; t.scout_double = d.doubles; t.grid = 256; }
+        }
+        // Split strips (sw_systolic2.inc): from strip split_from on -- those that would end after everybody else -- the strip's scout
+        // (a workgroup with rings and consumers then) writes the blocks from split_blk on and the filler only those before; the
+        // last strip gets a scout for it (one more workgroup on XCD 7).  The split point equalises the two ends: the filler needs
+        // tau_f per row, the scout kScoutLeadSec before its consumers start and tau_f after.  Needs the per-XCD dealing and pacing
+        // (the common end every filler is paced to moves with it).
+        if (t.xcd_mode == 1 && (rows >= kSplitRows || o.split_blk > 0) && !j.has_top && !j.has_top_gran && !j.has_bot_gran && o.filler_hop_ps > 0 &&
+            !(o.debug_flags & (DBG_NO_PACING | DBG_NO_SPLIT))) {
+            const Deal d = deal_per_xcd(S2, true);
+            const double hop = (double)o.filler_hop_ps * 1e-12, tf = (double)o.filler_tau_ps * 1e-12, ts = kScoutLeadSec;
+            const int64_t nblk = (rows + 15) / 16;
+            const int64_t sblk = (int64_t)((double)nblk * tf / (2.0 * tf - std::min(ts, tf)));
+            const bool forced = o.split_blk > 0;   // (tests: any split point, any first strip)
+            if (d.fits && forced && o.split_blk < nblk) {
+                t.split_blk = (int)o.split_blk; t.split_from = (int)std::max<int64_t>(1, o.split_from); t.split_extra = 1;
+                t.filler_end_steps = (int)((o.split_blk * 16 + 126) / 64 * 64 + 64); t.filler_full_steps = (int)((nblk * 16 + 126) / 64 * 64 + 64);
+                t.nscout = d.scouts; t.scout_double = d.doubles;
+            } else if (d.fits && sblk >= 16 && sblk < nblk && rows >= kSplitRows) {
+                const int64_t full_steps = (nblk * 16 + 126) / 64 * 64 + 64, end_steps = (sblk * 16 + 126) / 64 * 64 + 64;
+                // strip s, unsplit, would end s hand-offs + a whole strip after the start; the split ones end (S2 - 1) hand-offs + end_steps
+                const double lead = ((double)full_steps - (double)end_steps) * tf / hop;
+                const int64_t from = std::max<int64_t>(1, (int64_t)((double)(S2 - 1) - lead) + 1);
+                if (from < S2) {
+                    t.split_blk = (int)sblk; t.split_from = (int)from; t.split_extra = 1;
+                    t.filler_end_steps = (int)end_steps; t.filler_full_steps = (int)full_steps;
+                    t.nscout = d.scouts; t.scout_double = d.doubles;
+                }
+            }
+        }
+        // The classic chain (no room for scouts), dealt per XCD the same way: neighbouring strips on one XCD, edge columns through
+        // its L2.  (option "xcd_chain": 0 auto, 1 on, 2 off)
+        const bool xcd_chain_pays = S2 >= kXcdChainStrips && W2 != 110;
+        if (!scouts && dev.xcd_round_robin && t.grid >= 64 && !(o.debug_flags & DBG_NO_XCD_DEALING) &&
+            (o.xcd_chain == 1 || (o.xcd_chain == 0 && xcd_chain_pays)))
+            t.xcd_mode = 2;
+        // pacing of the fillers behind scouts (sw_systolic2.inc): estimates on the low side, so that nobody is held back more
+        // than the last filler's best case allows.  (options "filler_hop_ps" / "filler_tau_ps")
+        t.filler_hop_ps = (scouts && !(o.debug_flags & DBG_NO_PACING)) ? (int)o.filler_hop_ps : 0;
+        t.filler_tau_ps = (int)o.filler_tau_ps;
+        t.filler_bw_gbs = (int)o.filler_bw_gbs;
+        // consumer waves (+ 9 - consumers importers).  Behind scouts a filler is never the one a hand-off waits for: two importers do, and
+        // seven consumers keep more stores in flight (16384^2 -1.5 %, 12288^2 -2.5 %, 20480^2 +-0 against five)
+        // (overlapping strips, whose consumers are dearer: seven as well -- 32768^2 485 against 453-466 GCUPS, 65536^2 633 / 607, int64 H 502 / 495)
+        t.consumers = o.consumers == 0 ? ((scouts || W2 == 110) ? 7 : (chain_bound ? 5 : 6)) : (int)std::min<int64_t>(7, o.consumers);
+    }
+    return f;
+}
+
+}  // namespace swp

@@ -1,0 +1,80 @@
+// sw_plan.h -- the fill planner: every policy decision of one fill (kernel, workgroup shape, perm producer, strip geometry, column
+// tiles, scouts, roles per XCD, split strips, filler pacing, store kind) and the workspace sizes it needs, as a pure function of the
+// job, the device and the options.  Plain C++ (no HIP include): sw_api.hip carries a plan out, tests/test_fill_plan.py checks the
+// policy on a CPU.
+#pragma once
+#include <cstddef>
+#include <cstdint>
+#include "sw_debug.h"
+
+namespace swp {
+
+struct PlanJob {
+    int64_t cols = 0, rows = 0, npairs = 1;
+    bool full_stride = true;                 // row stride == cols + 1
+    int h_elem_bytes = 4, p_elem_bytes = 4;  // 4 / 8; 4 / 1
+    bool has_H = true, has_P = true;         // which matrices are written
+    bool has_top = false;                    // halo row in (a tile or a band)
+    bool has_left = false, has_right = false;            // halo column in / out (a tile of a wider matrix)
+    bool has_top_gran = false, has_bot_gran = false;     // band-resident launch: halo row in / last row out as granules
+    bool has_result = true;                  // a result pointer the one-launch fill can write (batches keep their own keys)
+    int64_t total_rows = 0;                  // band: rows of the whole matrix (bounds the scores a halo can carry)
+    int reserve_cus = 0;                     // CUs left free for other kernels
+    bool h_aligned = true, p_aligned = true; // d_H 16-byte (int64 H) / 8-byte aligned, d_P 8-byte aligned: whole-line stores possible
+    int match = 3, mismatch = -3, gap = -2;
+    float pair_ratio = 0.f;                  // store probe's two-stream / one-stream time of the H / P pair (~1.4: two classes of the HBM, ~2: one); 0: unknown
+};
+
+struct DeviceFacts {
+    int num_cus = 256;
+    bool xcd_round_robin = false;            // workgroup i of a launch runs on XCD i % 8 (8 XCDs of 32 CUs)
+    int s2_per_cu = 0;                       // occupancy of sw_systolic2 at 768 threads (workgroups per CU)
+};
+
+struct PlanOptions {   // the sw_set_option values the policy reads (include/swhip.h)
+    int64_t engine = 0, strips_per_group = 0, consumers = 0, importers = 0, max_blocks = 0, waves_per_block = 4, store_policy = 0;
+    int64_t s2w = 0, xcd_chain = 0, split_blk = 0, split_from = 0;
+    int64_t filler_hop_ps = 2400000, filler_tau_ps = 25000, filler_bw_gbs = 4200;
+    int64_t probe_foreign_pairs = 0, debug_flags = 0;
+};
+
+// one launch of the two-column kernel (a column tile, or the whole matrix)
+struct TilePlan {
+    int64_t c0 = 0, cols = 0, strips = 0;    // first column, columns, strips
+    int grid = 0, nscout = 0, scout_double = 0, xcd_mode = 0;
+    int split_blk = 0, split_from = 0, split_extra = 0, filler_end_steps = 0, filler_full_steps = 0;
+    int filler_hop_ps = 0, filler_tau_ps = 0, filler_bw_gbs = 0;
+    int store_nt = 0;
+    int consumers = 0;                       // consumer waves: the kernel's instantiation
+};
+
+// tiles of at most 160 strips of at least 110 columns: cols <= SW_MAX_DIM gives at most 60
+constexpr int kMaxTiles = 64;
+
+struct FillPlan {
+    int engine = 0;                          // 0: systolic (sw_systolic / sw_systolic2), 1: sw_strip_scan
+    int64_t S = 0;                           // strips of the one-column kernel (sw_strip_scan: of 64 columns)
+    int store_nt = 0;                        // streaming H / P stores
+    // sw_systolic (also enqueued behind the two-column kernel: the fall-back for alphabets it cannot take)
+    int NS = 0, NC = 0, importers = 0, threads = 0;
+    int grid = 0;                            // before the occupancy cap
+    bool fast = false;                       // fast producers (phi_base = S - 1)
+    int64_t bfront = 0, per = 0;             // padded copies of b: index of b[0], elements per pair
+    bool perm = false;                       // perm producer eligible on the host side
+    int64_t e4stride = 0;
+    // sw_systolic2: one launch per tile, each writes the result when it is the last (a fused fill: no sw_finalize behind it)
+    bool two_cols = false;
+    int W2 = 126;                            // strip width: 126 (strips tile the matrix) or 110 (overlapping strips, compiled in)
+    int64_t ntile = 1, tstrips = 0;
+    TilePlan tile[kMaxTiles];
+    int64_t priv_stride = 0;
+    // workspaces: edge granules, padded b (bytes), perm edge values, per-workgroup copies of b (bytes)
+    size_t edge_need = 0, cb_need = 0, edge4_need = 0, priv_need = 0;
+    // the output matrices, in bytes, and whether the pair's class of the HBM decides the strip geometry and is to be probed
+    size_t h_bytes = 0, p_bytes = 0;
+    bool probe_pair_class = false;
+};
+
+FillPlan plan_fill(const PlanJob& job, const DeviceFacts& dev, const PlanOptions& opt);
+
+}  // namespace swp

@@ -1062,7 +1062,7 @@ __device__ __forceinline__ void sw_systolic_body(const unsigned char* seq_a, con
     const int64_t estride = p.rows + 1;
     // perm producer: eligible on the host side (score range -> gbias != 0) AND an alphabet of at most 7 letters (found on
     // the device by sw_pad_b); it always uses the fast step numbering
-    const bool perm = (p.gbias != 0) && (*(const unsigned int*)(p.atab + 256) <= 7u) && !(p.debug_flags & 16);
+    const bool perm = (p.gbias != 0) && (*(const unsigned int*)(p.atab + 256) <= 7u) && !(p.debug_flags & DBG_NO_PERM);
     const int phib = perm ? p.nstrips - 1 : p.phi_base;
     const int gb = perm ? (int)p.gbias : 0;       // carried by every G value
     const int ugran = perm ? 64 : SY_U;   // the perm producer tests for the end once per 64-step chunk
@@ -1103,7 +1103,7 @@ __device__ __forceinline__ void sw_systolic_body(const unsigned char* seq_a, con
         if (threadIdx.x == 0) { lds.halo_ready = 1; lds.exp_done = 0; lds.never = 0x7fffffff; }
         // the halo ring starts empty: the perm producer takes a 0 for "not imported yet" (every G carries the launch bias)
         for (int i = threadIdx.x; i < SY_RH; i += blockDim.x) lds.halo[i] = 0u;
-        if ((p.debug_flags & 2048) && p.gbias == 0)   // round-1 producers: poison the halo ring, so that any slot consumed before an
+        if ((p.debug_flags & DBG_POISON_HALO) && p.gbias == 0)   // round-1 producers: poison the halo ring, so that any slot consumed before an
             for (int i = threadIdx.x; i < SY_RH; i += blockDim.x) lds.halo[i] = 0x700000u + (u32)i;   // importer wrote it shows up in the output
         const int s0 = grp * NS;
         const int nact = min(NS, p.nstrips - s0);  // active strips of this group
@@ -1158,7 +1158,7 @@ __device__ __forceinline__ void sw_systolic_body(const unsigned char* seq_a, con
             role = (wave < NS) ? R_PROD : (wave == h_imp || wave >= NWAVES) ? R_IMP : (wave == h_exp) ? R_EXP : R_CONS;
             cw = wave - NS - (wave > h_imp ? 1 : 0) - (wave > h_exp ? 1 : 0);  // consumer ordinal 0..NS*NC-1
         }
-        if (p.dbg && (p.debug_flags & 64) && blockIdx.x == 0 && lane == 0) {   // where did the hardware put my waves?
+        if (p.dbg && (p.debug_flags & DBG_WAVE_PLACEMENT) && blockIdx.x == 0 && lane == 0) {   // where did the hardware put my waves?
             u32 hwid;
             asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hwid));
             p.dbg[6 * p.nstrips + 32 + wave] = ((u64)role << 32) | hwid;
@@ -1167,7 +1167,7 @@ __device__ __forceinline__ void sw_systolic_body(const unsigned char* seq_a, con
             // ================================ producer ================================
             const int ls = wave, s = s0 + ls;
             asm volatile("; SW_PRODUCER_PATH_BEGIN ");
-            if (ls < nact && !((p.debug_flags & 8) && s == 1)) {   // debug bit 3: strip 1 never runs (tests the abort path)
+            if (ls < nact && !((p.debug_flags & DBG_SKIP_STRIP1) && s == 1)) {   // debug bit 3: strip 1 never runs (tests the abort path)
                 const int phi = phi_of(s, phib);
                 const int UT = u_total(s);
                 const u32 j = (u32)s * SY_W + (u32)lane;
@@ -1227,13 +1227,13 @@ __device__ __forceinline__ void sw_systolic_body(const unsigned char* seq_a, con
                     int polls[2];
                     // halo from the importer's ring: validated on use (unfilled slots read 0); from the left producer's ring in
                     // this workgroup: by its progress counter
-                    const int st = (lefthalo && !(p.debug_flags & 8192))   // (debug bit 13: the progress form everywhere, for A/B runs)
+                    const int st = (lefthalo && !(p.debug_flags & DBG_PROGRESS_FORM))   // (debug bit 13: the progress form everywhere, for A/B runs)
                         ? producer_perm_valid(prof_lo, prof_hi, ngap_v, wbase, voff, z1, G0v, G0v + (u32)SW_PERM_PAD, expoff, cb, hbase, hoff * 4, cnt_addr,
                                               (u32)(size_t)&lds.cons_blk[ls][0], (u32)(size_t)(has_right ? right_cnt : &lds.never),
-                                              (u32)(size_t)&lds.prod_u[ls], UT, k1, k2, kc, kr, hmask * 4 + 3, erc, (p.debug_flags & 32) ? 0 : 64, polls)
+                                              (u32)(size_t)&lds.prod_u[ls], UT, k1, k2, kc, kr, hmask * 4 + 3, erc, (p.debug_flags & DBG_NO_POLL_BACKOFF) ? 0 : 64, polls)
                         : producer_perm_progress(prof_lo, prof_hi, ngap_v, wbase, voff, z1, G0v, G0v + (u32)SW_PERM_PAD, expoff, cb, hbase, hoff * 4, cnt_addr,
                                                  (u32)(size_t)&lds.cons_blk[ls][0], (u32)(size_t)(has_right ? right_cnt : &lds.never),
-                                                 (u32)(size_t)&lds.prod_u[ls], UT, k1, k2, kc, kr, hmask * 4 + 3, erc, (p.debug_flags & 32) ? 0 : 64, polls);
+                                                 (u32)(size_t)&lds.prod_u[ls], UT, k1, k2, kc, kr, hmask * 4 + 3, erc, (p.debug_flags & DBG_NO_POLL_BACKOFF) ? 0 : 64, polls);
                     if (p.dbg && lane == 0) {
                         p.dbg[2 * s + 1] = __builtin_amdgcn_s_memrealtime();
                         if (s == 0) p.dbg[6 * p.nstrips + 49] = __builtin_amdgcn_s_memtime();
@@ -1341,7 +1341,7 @@ __device__ __forceinline__ void sw_systolic_body(const unsigned char* seq_a, con
         } else if (role == R_CONS) {
             // ================================ consumer ================================
             const int ls = cw % NS, ci = cw / NS, s = s0 + ls;
-            if (ls < nact && (p.debug_flags & 2)) {
+            if (ls < nact && (p.debug_flags & DBG_PRODUCER_ONLY)) {
                 lds_store(&lds.cons_blk[ls][ci], 1 << 24);  // timing experiment: producer alone
             } else if (ls < nact) {
                 const int phi = phi_of(s, phib);
@@ -1349,8 +1349,8 @@ __device__ __forceinline__ void sw_systolic_body(const unsigned char* seq_a, con
                 const bool jvalid = (int64_t)j <= p.cols;
                 // lane 0 of strip 0 is the tile's own column 0 only for a whole matrix (left == NULL)
                 const bool cell_ok = jvalid && (lane >= 1 || (s == 0 && p.left == nullptr));
-                const bool store_h = cell_ok && p.H != nullptr && !(p.debug_flags & 1);
-                const bool store_p = cell_ok && p.P != nullptr && !(p.debug_flags & 1);
+                const bool store_h = cell_ok && p.H != nullptr && !(p.debug_flags & DBG_NO_STORES);
+                const bool store_p = cell_ok && p.P != nullptr && !(p.debug_flags & DBG_NO_STORES);
                 const bool last_strip = (s + 1 == p.nstrips);
                 const int lc = (int)p.cols - s * SY_W;          // lane of the tile's last column (in the last strip)
                 const bool right_strip = last_strip && p.right != nullptr;   // this strip also returns the tile's right edge column
@@ -1389,7 +1389,7 @@ __device__ __forceinline__ void sw_systolic_body(const unsigned char* seq_a, con
                 bool looped = false;
                 for (int q = ci; q < nblk; q += NC) {
                     if constexpr (sizeof(HT) == 4) {
-                        if (!looped && q > 0 && q < nblk - 1 && !right_strip && !(p.debug_flags & (128 | 256))) {
+                        if (!looped && q > 0 && q < nblk - 1 && !right_strip && !(p.debug_flags & (DBG_BLOCK_STAMPS | DBG_NO_CONSUMER_LOOP))) {
                             looped = true;
                             const int qs = __builtin_amdgcn_readfirstlane(q);   // (wave-uniform by construction; say so)
                             const int nmine = (nblk - 1 - qs + NC - 1) / NC;    // my blocks below the last one
@@ -1521,7 +1521,7 @@ __device__ __forceinline__ void sw_systolic_body(const unsigned char* seq_a, con
                             wbest = __builtin_amdgcn_readfirstlane(v);
                         }
                     }
-                    if (p.dbg && (p.debug_flags & 128) && lane == 0)   // per-block completion stamps (after the strip stamps and counters)
+                    if (p.dbg && (p.debug_flags & DBG_BLOCK_STAMPS) && lane == 0)   // per-block completion stamps (after the strip stamps and counters)
                         p.dbg[6 * p.nstrips + 64 + (int64_t)s * nblk + qu] = __builtin_amdgcn_s_memrealtime();
                     if (p.bot_gran && qu == nblk - 1) {
                         // band-resident launch: the band's last row leaves as {tag, H} granules (the next band's halo row)
@@ -1539,7 +1539,7 @@ __device__ __forceinline__ void sw_systolic_body(const unsigned char* seq_a, con
                     lds_store(&lds.cons_blk[ls][slot], qu);
                 }
                 // arg-max: the lowest row of block `bestblk` holding bestv in my column (re-read what this wave stored)
-                if (cell_ok && !(p.debug_flags & 1) && bestv > 0) {
+                if (cell_ok && !(p.debug_flags & DBG_NO_STORES) && bestv > 0) {
                     if (reread) {
                         bestrow = bestblk * SY_U + 1;
                         __builtin_amdgcn_s_waitcnt(0);  // my own stores have reached L2
@@ -1564,7 +1564,7 @@ __device__ __forceinline__ void sw_systolic_body(const unsigned char* seq_a, con
                 // carry the launch tag, indexed by ITS local step; my strip's local step u needs its step u + 64.
                 // There is no exporter.  Steps above the matrix (rows <= 0) hold the row-0 value of the halo column.
                 // (debug bit 12: a single importer wave)
-                const bool importer_w = (p.debug_flags & 4096) ? (role == R_EXP) : (role == R_IMP || role == R_EXP);   // nothing to export here: one more importer
+                const bool importer_w = (p.debug_flags & DBG_ONE_IMPORTER) ? (role == R_EXP) : (role == R_IMP || role == R_EXP);   // nothing to export here: one more importer
                 if (importer_w) {
                     const int phi0 = phi_of(s0, phib);
                     const u32 row0v = (u32)(gb + top_at(0, 0, (int64_t)s0 * SY_W) + ngap * s0 * SY_W);
@@ -1617,7 +1617,7 @@ __device__ __forceinline__ void sw_systolic_body(const unsigned char* seq_a, con
                                     if (lane < npre && (front2 <= 1 || u >= front2)) {
                                         __hip_atomic_store(&lds.halo[(u - 1) & (SY_RH - 1)], vals[b4], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
                                         __hip_atomic_store(&lds.halo[(u - 1 + SY_RH / 2) & (SY_RH - 1)], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                                        if (p.dbg && (p.debug_flags & 512) && u < 256) p.dbg[1024 + (int64_t)s0 * 1024 + u] = ((u64)(u32)wave << 32) | vals[b4];
+                                        if (p.dbg && (p.debug_flags & DBG_EDGE_DUMP) && u < 256) p.dbg[1024 + (int64_t)s0 * 1024 + u] = ((u64)(u32)wave << 32) | vals[b4];
                                     }
                                     base += npre;
                                 }
@@ -1759,7 +1759,7 @@ __device__ __forceinline__ void sw_systolic_body(const unsigned char* seq_a, con
             }
         }
         __syncthreads();
-        if (p.dbg && (p.debug_flags & 512) && threadIdx.x < 256) {
+        if (p.dbg && (p.debug_flags & DBG_EDGE_DUMP) && threadIdx.x < 256) {
             const u32* r0 = (const u32*)&lds.ring[0][0];
             p.dbg[1024 + (int64_t)s0 * 1024 + 256 + threadIdx.x] = r0[threadIdx.x];          // lane 0, steps 1..256 (ring slot = step-1)
             p.dbg[1024 + (int64_t)s0 * 1024 + 512 + threadIdx.x] = lds.halo[threadIdx.x];    // the halo ring itself
@@ -1901,7 +1901,7 @@ __global__ void __launch_bounds__(NS == 1 ? 768 : 64 * (NS * (1 + NC) + 2))   //
 sw_systolic(const unsigned char* seq_a, const unsigned char* seq_b, const unsigned char* bpad, FillParams p) {
     // enqueued behind sw_systolic2 (skip_if_perm): that kernel has done the fill unless the alphabet (found on the device, by its prologue)
     // has more than 7 letters -- then this one fills, from the shared padded copies workgroup 0 of that launch left, and reports like it
-    if (p.skip_if_perm && p.gbias != 0 && *(const unsigned int*)(p.atab + 256) <= 7u && !(p.debug_flags & 16)) return;
+    if (p.skip_if_perm && p.gbias != 0 && *(const unsigned int*)(p.atab + 256) <= 7u && !(p.debug_flags & DBG_NO_PERM)) return;
     sw_systolic_body<HT, NS, NC>(seq_a, seq_b, bpad, p);
     if (p.skip_if_perm && p.sync) s2_epilogue(p, true);
 }

@@ -856,7 +856,7 @@ __device__ __forceinline__ void s2_body(Sys2Lds& lds, const unsigned char* ltab,
         // the per-XCD dealing (polls that hit the L2) the chain of 16384^2 ends after 640 us with six and 630 with nine against 655-660
         // with three (12288^2: 0.587 ms per fill against 0.602); with one or two it is as with three.  (debug bits 24-25: that many
         // importer waves on SIMD 2 only)
-        const int nimp_dbg = (p.debug_flags >> 24) & 3;
+        const int nimp_dbg = (p.debug_flags >> DBG_S2_IMPORTERS_SHIFT) & 3;
         const bool producer = wave < cnt;
         const bool importer = !producer && (cnt == 2 ? (cls >= 2 && (wave >> 2) < (nimp_dbg ? nimp_dbg : 1))
                                                      : (nimp_dbg ? (cls == 2 && (wave >> 2) < nimp_dbg) : cls != 0));
@@ -878,8 +878,8 @@ __device__ __forceinline__ void s2_body(Sys2Lds& lds, const unsigned char* ltab,
                     Spin spin; spin.code = 16;
                     if (!xcd_local_readers(p, S, s, my_xcc, sc_far_block, spin, local)) return;
                 }
-                const int st = local ? s2_produce<true, true, OV>(sides[half], nullptr, p, seq_a, ltab, my_bcode, s, S, phi, UT, lane, gb, ngap, mm, xm, !(p.debug_flags & 2097152))
-                                     : s2_produce<true, false, OV>(sides[half], nullptr, p, seq_a, ltab, my_bcode, s, S, phi, UT, lane, gb, ngap, mm, xm, !(p.debug_flags & 2097152));
+                const int st = local ? s2_produce<true, true, OV>(sides[half], nullptr, p, seq_a, ltab, my_bcode, s, S, phi, UT, lane, gb, ngap, mm, xm, !(p.debug_flags & DBG_S2_SCOUTS_NO_EXPORT))
+                                     : s2_produce<true, false, OV>(sides[half], nullptr, p, seq_a, ltab, my_bcode, s, S, phi, UT, lane, gb, ngap, mm, xm, !(p.debug_flags & DBG_S2_SCOUTS_NO_EXPORT));
                 if (st) __hip_atomic_store((gu32*)p.abort_flag, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 // The XCD's last scout: the chain has passed, every edge column of this XCD's scouts sits dirty in its L2.  None of that may
                 // outlive the launch there -- a later launch deals the strips differently, and a stale line written back after the new
@@ -887,7 +887,7 @@ __device__ __forceinline__ void s2_body(Sys2Lds& lds, const unsigned char* ltab,
                 // XCD's dirty lines back; once per XCD and launch (after every scout: 4 % of a 16384^2 fill).
                 if (p.xcd_mode == 1 && s == sc_far) __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
             } else {
-                (void)s2_importer<OV>(sides[half], p, s, phi, UT, rows, gb, ngap, lane, (p.debug_flags & 4194304) != 0);
+                (void)s2_importer<OV>(sides[half], p, s, phi, UT, rows, gb, ngap, lane, (p.debug_flags & DBG_S2_SYNTH_HALO) != 0);
             }
         }
         return;
@@ -986,7 +986,7 @@ __device__ __forceinline__ void s2_body(Sys2Lds& lds, const unsigned char* ltab,
                 const u32 mm_v = (u32)mm, xm_v = (u32)xm, ngap_v = (u32)ngap;
                 const u32 slot_addr = (u32)(size_t)&lds.cons_blk[k9];
                 const u32 g0a = (u32)(gb + topA + ngap * (int)jA), g0b = (u32)(gb + topB + ngap * (int)jB);
-                const bool nostore = (p.debug_flags & 1) != 0;   // timing experiments: drop the H / P stores
+                const bool nostore = (p.debug_flags & DBG_NO_STORES) != 0;   // timing experiments: drop the H / P stores
                 const bool nt = p.store_nt != 0, store_h = H != nullptr && !nostore, store_p = P != nullptr && !nostore, trk = H == nullptr;
                 const u32 voffH = (okB && store_h) ? (u32)jA * (h64 ? 8u : 4u) : SY_OOB, voffP = (okB && store_p) ? (u32)jA * (p8 ? 1u : 4u) : SY_OOB;
                 const u32 rowbH = (u32)(M * (h64 ? 8 : 4)), rowbP = (u32)(M * (p8 ? 1 : 4));
