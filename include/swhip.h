@@ -173,6 +173,31 @@ int sw_batch_device_ex(sw_ctx* ctx, const char* d_a, int64_t a_stride, int64_t c
 int sw_batch_traceback_device(sw_ctx* ctx, void* d_P, int p_elem_bytes, int64_t cols, int64_t rows, int64_t npairs,
                               int64_t* d_paths, int64_t path_cap, sw_result* d_results, void* stream);
 
+/* Database search: one query against ntargets sequences of different lengths.  For every target k the reference fill
+ * (serial_smithW.c:141-145 for the set-up, 187-256 for the cells: similarityScore + matchMissmatchScore, maxPos by the serial
+ * scan's rule) of a = query (cols = qlen), b = target k (rows = its length), score and arg-max only -- what the reference computes
+ * per pair, without H and P.
+ *   d_query      : device, qlen >= 1 bytes
+ *   d_db         : device, the targets back to back; target k = d_db[offsets[k] .. offsets[k+1]), no alignment asked
+ *   offsets      : HOST, ntargets + 1 non-decreasing int64 (offsets[0] may be > 0; empty targets allowed); the library
+ *                  copies what it needs before returning, so the array may be reused at once
+ *   d_results    : device, ntargets sw_result in INPUT order: max_score, max_pos = r*(qlen+1)+c in target k's own
+ *                  (len_k+1) x (qlen+1) matrix, lowest index among ties, 0 if no cell is positive; path_len = 0
+ * Any byte value is a letter (bytes compared as in matchMissmatchScore, serial_smithW.c:251-256).  Asynchronous on
+ * `stream`.  Results identical to sw_fill_device(query, target k) for every k.  SW_EINVAL for decreasing offsets, qlen < 1,
+ * qlen or a target length above 2^20 - 1, scores the fill would reject for (qlen, longest target), NULL pointers.
+ * Runs on csrc/sw_search.hip (targets scheduled longest first over persistent waves; a re-fill of a chosen hit with
+ * sw_fill_device + sw_traceback_device gives its path). */
+int sw_search_device(sw_ctx* ctx, const char* d_query, int64_t qlen, const char* d_db, const int64_t* offsets,
+                     int64_t ntargets, const sw_scores* scores, sw_result* d_results, void* stream);
+
+/* Every record of a FASTA file in one pass, under the parsing rules of sw_read_fasta.  Two-call pattern:
+ * with seq == NULL it reports the counts only (*nrecords, *total_len).  Otherwise seq receives total_len bytes (seq_cap
+ * at least that) and offsets nrecords + 1 entries (offsets_cap at least that): record k = seq[offsets[k] .. offsets[k+1]),
+ * so the output goes straight into sw_search_device.  A file without any record reports 0 records. */
+int sw_read_fasta_db(const char* path, char* seq, int64_t seq_cap, int64_t* offsets, int64_t offsets_cap,
+                     int64_t* nrecords, int64_t* total_len);
+
 /* Host-buffer convenience wrapper around sw_fill_device (alloc, H2D, fill, D2H, sync).
  * H, P: caller-owned int32 (rows+1)*(cols+1); either may be NULL to skip its copy-out. */
 int sw_fill_host(sw_ctx* ctx, const char* a, int64_t cols, const char* b, int64_t rows,

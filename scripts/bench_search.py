@@ -1,0 +1,107 @@
+#!/usr/bin/env python3
+"""Database search throughput (sw_search_device) on one GPU; prints ONE JSON line.
+  (a) query 512, protein alphabet, 200 000 targets, lengths log-normal (median 300, cut at 35 000)
+  (b) the same total cells as equal-length targets
+  (c) 4-letter equal-length 1024^2 database, search against sw_batch_device (score-only) on the same data
+  (d) the (b) data through sw_batch_device, which takes the single-pair path for more than 8 letters
+GCUPS = query letters x target letters / time of the call (torch events, median of --reps after --warmup)."""
+import argparse
+import importlib
+import json
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+swamd = importlib.import_module("smith-waterman_amd")
+import torch  # noqa: E402
+
+PROTEIN = np.frombuffer(b"ACDEFGHIKLMNPQRSTVWY", np.uint8)
+DNA = np.frombuffer(b"ACGT", np.uint8)
+
+
+def timed(fn, warmup, reps):
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    ms = []
+    for _ in range(reps):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        fn()
+        e1.record()
+        torch.cuda.synchronize()
+        ms.append(e0.elapsed_time(e1))
+    return float(np.median(ms))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--targets", type=int, default=200_000)
+    ap.add_argument("--qlen", type=int, default=512)
+    ap.add_argument("--pairs-c", type=int, default=20_000)
+    ap.add_argument("--pairs-d", type=int, default=4096, help="pairs of the (b) data sent through sw_batch_device (its slow path)")
+    ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--reps", type=int, default=5)
+    args = ap.parse_args()
+    rng = np.random.default_rng(2026)
+    eng = swamd.Engine(0)
+    dev = "cuda:0"
+    out = {"workload": "database search", "device": torch.cuda.get_device_name(0)}
+
+    def search_gcups(query, packed, offs, tag):
+        d_q = torch.from_numpy(query.copy()).to(dev)
+        d_db = torch.from_numpy(packed.copy()).to(dev)
+        res = torch.zeros((len(offs) - 1, 3), dtype=torch.int64, device=dev)
+        ms = timed(lambda: eng.search_device(d_q, len(query), d_db, offs, out=res), args.warmup, args.reps)
+        cells = float(len(query)) * float(offs[-1] - offs[0])
+        out[f"{tag}_ms"] = round(ms, 3)
+        out[f"{tag}_gcups"] = round(cells / ms / 1e6, 1)
+        out[f"{tag}_grid"] = eng.get_option("last_search_grid")
+        return res
+
+    def batch_gcups(query, b_all, tag, reps):
+        npairs, n = b_all.shape
+        d_a, d_b, cols, rows = eng.batch_to_device(np.broadcast_to(query, (npairs, len(query))), b_all)
+        res = torch.zeros((npairs, 3), dtype=torch.int64, device=dev)
+        ms = timed(lambda: eng.batch_device(d_a, d_b, cols, rows, out=(res, None, None)), min(args.warmup, 1), reps)
+        out[f"{tag}_ms"] = round(ms, 3)
+        out[f"{tag}_gcups"] = round(float(cols) * rows * npairs / ms / 1e6, 1)
+        return res
+
+    # (a) protein database, log-normal lengths
+    q = rng.choice(PROTEIN, args.qlen).astype(np.uint8)
+    lens = np.clip(np.round(rng.lognormal(np.log(300), 0.6, args.targets)), 1, 35_000).astype(np.int64)
+    offs = np.zeros(args.targets + 1, np.int64)
+    offs[1:] = np.cumsum(lens)
+    packed = rng.choice(PROTEIN, int(offs[-1])).astype(np.uint8)
+    out["a_letters"] = int(offs[-1])
+    out["a_len_median"] = int(np.median(lens))
+    out["a_len_max"] = int(lens.max())
+    search_gcups(q, packed, offs, "a")
+    # (b) the same cells, equal lengths
+    L = int(round(offs[-1] / args.targets))
+    offs_b = np.arange(args.targets + 1, dtype=np.int64) * L
+    packed_b = rng.choice(PROTEIN, int(offs_b[-1])).astype(np.uint8)
+    out["b_len"] = L
+    search_gcups(q, packed_b, offs_b, "b")
+    # (c) 4-letter 1024^2: search against the batch kernel on the same data
+    qc = rng.choice(DNA, 1024).astype(np.uint8)
+    bc = rng.choice(DNA, (args.pairs_c, 1024)).astype(np.uint8)
+    rs = search_gcups(qc, bc.reshape(-1), np.arange(args.pairs_c + 1, dtype=np.int64) * 1024, "c_search")
+    rb = batch_gcups(qc, bc, "c_batch", args.reps)
+    out["c_identical"] = bool(torch.equal(rs, rb))
+    # (d) protein equal-length data through sw_batch_device (more than 8 letters: the single-pair path)
+    bd = packed_b[: args.pairs_d * L].reshape(args.pairs_d, L)
+    batch_gcups(q, bd, "d_batch", 1)
+    out["a_over_b"] = round(out["a_gcups"] / out["b_gcups"], 3)
+    out["c_search_over_batch"] = round(out["c_search_gcups"] / out["c_batch_gcups"], 3)
+    out["a_over_d"] = round(out["a_gcups"] / out["d_batch_gcups"], 2)
+    eng.close()
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()

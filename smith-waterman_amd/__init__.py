@@ -48,6 +48,7 @@ ABI = {
     "sw_version": (ctypes.c_char_p, []),
     "sw_generate": (_i32, [_i64, _i64, _u32, _vp, _vp]),
     "sw_read_fasta": (_i32, [ctypes.c_char_p, _i64, _vp, _i64, ctypes.POINTER(_i64)]),
+    "sw_read_fasta_db": (_i32, [ctypes.c_char_p, _vp, _i64, _vp, _i64, ctypes.POINTER(_i64), ctypes.POINTER(_i64)]),
     "sw_nelement": (_i64, [_i64, _i64, _i64]),
     "sw_first_diag_element": (None, [_i64, _i64, _i64, ctypes.POINTER(_i64), ctypes.POINTER(_i64)]),
     "sw_create": (_i32, [_i32, ctypes.POINTER(_vp)]),
@@ -56,6 +57,7 @@ ABI = {
     "sw_fill_tile_device": (_i32, [_vp, _vp, _i64, _vp, _i64, ctypes.POINTER(_Scores), _vp, _i32, _vp, _i64, _vp, _vp, _vp, _vp, _vp]),
     "sw_batch_device": (_i32, [_vp, _vp, _i64, _i64, _vp, _i64, _i64, _i64, ctypes.POINTER(_Scores), _vp, _vp, _vp, _vp]),
     "sw_batch_device_ex": (_i32, [_vp, _vp, _i64, _i64, _vp, _i64, _i64, _i64, ctypes.POINTER(_Scores), _vp, _vp, _i32, _vp, _vp]),
+    "sw_search_device": (_i32, [_vp, _vp, _i64, _vp, _vp, _i64, ctypes.POINTER(_Scores), _vp, _vp]),
     "sw_batch_traceback_device": (_i32, [_vp, _vp, _i32, _i64, _i64, _i64, _vp, _i64, _vp, _vp]),
     "sw_fill_band_device": (_i32, [_vp, _vp, _i64, _vp, _i64, _i64, ctypes.POINTER(_Scores), _vp, _i32, _vp, _i32, _vp, _u32, _vp, _u32, _vp,
                                    _i32, _i32, _vp, _vp]),
@@ -137,6 +139,39 @@ def read_fasta(path: str, record: int = 0):
     seq = np.zeros(max(1, n.value), np.uint8)
     _check(lib().sw_read_fasta(os.fsencode(path), record, seq.ctypes.data, n.value, ctypes.byref(n)))
     return seq[:n.value].copy()
+
+
+def read_fasta_db(path: str):
+    """Every record of a FASTA file in one pass (sw_read_fasta_db): (packed uint8 sequence bytes, int64 offsets of nrecords + 1
+    entries); record k = packed[offsets[k]:offsets[k+1]], the layout Engine.search takes."""
+    nrec, total = _i64(), _i64()
+    _check(lib().sw_read_fasta_db(os.fsencode(path), None, 0, None, 0, ctypes.byref(nrec), ctypes.byref(total)))
+    seq = np.zeros(max(1, total.value), np.uint8)
+    offs = np.zeros(nrec.value + 1, np.int64)
+    _check(lib().sw_read_fasta_db(os.fsencode(path), seq.ctypes.data, len(seq), offs.ctypes.data, len(offs), ctypes.byref(nrec),
+                                  ctypes.byref(total)))
+    return seq[:total.value].copy(), offs
+
+
+def _pack_targets(targets):
+    """A list of sequences, or a (packed, offsets) pair -> (packed uint8, int64 offsets)."""
+    if isinstance(targets, tuple) and len(targets) == 2 and not isinstance(targets[0], (str, bytes, bytearray)):
+        packed = np.ascontiguousarray(targets[0], np.uint8).reshape(-1)
+        offs = np.ascontiguousarray(targets[1], np.int64).reshape(-1)
+        return packed, offs
+    seqs = [_as_seq(t) for t in targets]
+    offs = np.zeros(len(seqs) + 1, np.int64)
+    if seqs:
+        offs[1:] = np.cumsum([len(x) for x in seqs])
+    packed = np.concatenate(seqs) if seqs and offs[-1] > 0 else np.zeros(0, np.uint8)
+    return np.ascontiguousarray(packed, np.uint8), offs
+
+
+def top_hits(results, k: int):
+    """Indices of the k best targets of search results: score descending, then index ascending."""
+    scores = np.asarray(results)[:, 1]
+    order = np.lexsort((np.arange(len(scores)), -scores))
+    return order[: max(0, min(int(k), len(scores)))]
 
 
 def n_element(i: int, m: int, n: int) -> int:
@@ -410,6 +445,37 @@ class Engine:
         if bool((res[:, 2] < 0).any().item()):
             raise SwError(-62, "in-kernel hand-off wait timed out")
         return (res, H, P, paths) if want_paths else (res, H, P)
+
+    def search(self, query, targets, scores=DEFAULT_SCORES, top=None):
+        """Database search (sw_search_device): one query against many targets of any length and alphabet.  targets: a list of
+        sequences or a (packed uint8, int64 offsets) pair (read_fasta_db).  Returns the (ntargets, 3) int64 numpy array
+        (max_pos, max_score, path_len = 0) in input order -- and, with top=K, also the K best target indices (score descending,
+        then index ascending)."""
+        t = self.torch
+        q = _as_seq(query)
+        packed, offs = _pack_targets(targets)
+        ntargets = len(offs) - 1
+        dev = f"cuda:{self.device}"
+        d_q = t.from_numpy(q.copy()).to(dev)
+        d_db = t.from_numpy(packed.copy() if len(packed) else np.zeros(1, np.uint8)).to(dev)
+        res = self.search_device(d_q, len(q), d_db, offs, scores)
+        self.synchronize()
+        out = res.cpu().numpy()
+        return (out, top_hits(out, top)) if top is not None else out
+
+    def search_device(self, d_query, qlen: int, d_db, offsets, scores=DEFAULT_SCORES, out=None):
+        """sw_search_device on device-resident query / packed targets (torch uint8 tensors), host int64 offsets; asynchronous on
+        torch's current stream.  Returns the (ntargets, 3) int64 result tensor (`out` if given)."""
+        t = self.torch
+        offs = np.ascontiguousarray(offsets, np.int64).reshape(-1)
+        if len(offs) == 0:
+            offs = np.zeros(1, np.int64)
+        ntargets = len(offs) - 1
+        res = out if out is not None else t.zeros((max(1, ntargets), 3), dtype=t.int64, device=f"cuda:{self.device}")
+        sc = _Scores(*scores)
+        _check(lib().sw_search_device(self._h, d_query.data_ptr(), qlen, d_db.data_ptr(), offs.ctypes.data, ntargets, ctypes.byref(sc),
+                                      res.data_ptr(), self._stream()))
+        return res[:ntargets]
 
     def traceback(self, out: Fill, max_pos: int | None = None, want_path: bool = True):
         """backtrack() on the device P (negates the path in place). Returns the path indices."""

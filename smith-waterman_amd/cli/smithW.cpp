@@ -2,10 +2,13 @@
 //   smithW                  built-in 8x9 example (serial_smithW.c:105-125) + its known-answer checks
 //   smithW <cols> <rows>    random DNA pair from the reference generator (seed 1 == serial_smithW.c)
 //   smithW --fasta A.fa B.fa   real sequences: a = first record of A.fa (columns), b = first record of B.fa (rows)
+//   smithW --search Q.fa DB.fa [--top K]   database search: a = record --record-a of Q.fa against every record of DB.fa (sw_search_device);
+//                              prints the K best hits (default 10): rank, record, score, target_end, query_end (max_pos = target_end*(qlen+1)+query_end)
 // Extra flags: --seed N  --dump | --dump-labels (the header-row printers of omp_smithW.c)  --h64  --no-backtrack  --scores M X G  --record-a I  --record-b J
 //   --gpus N | --devices 0,1,..   ONE matrix over several GPUs (row bands, sw_multi_*; an id may repeat)  --p8  int8 P
 // The DP fill runs on the GPU through the C-ABI (include/swhip.h); stdout keeps the two
 // "Elapsed time ..." lines the reference's run scripts grep for (readme.liao:12).
+#include <algorithm>
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -73,6 +76,47 @@ static void print_pred_labelled(const std::vector<int32_t>& P, long long n, long
     }
 }
 
+// --search: one query record against every record of a FASTA database on the GPU, the best `top` hits by score (ties: lower record first)
+static int search_main(const char* qpath, long long rec, const char* dbpath, long long top, const sw_scores& sc) {
+    int64_t qlen = 0, nrec = 0, total = 0;
+    CHECK(sw_read_fasta(qpath, rec, nullptr, 0, &qlen));
+    std::vector<char> q((size_t)qlen + 1);
+    CHECK(sw_read_fasta(qpath, rec, q.data(), qlen, &qlen));
+    CHECK(sw_read_fasta_db(dbpath, nullptr, 0, nullptr, 0, &nrec, &total));
+    std::vector<char> db((size_t)total + 1);
+    std::vector<int64_t> offs((size_t)nrec + 1, 0);
+    CHECK(sw_read_fasta_db(dbpath, db.data(), total, offs.data(), nrec + 1, &nrec, &total));
+    sw_ctx* ctx = nullptr;
+    CHECK(sw_create(0, &ctx));
+    void *d_q = nullptr, *d_db = nullptr, *d_res = nullptr;
+    CHECK(sw_device_malloc(ctx, (size_t)qlen + 16, &d_q));
+    CHECK(sw_device_malloc(ctx, (size_t)total + 16, &d_db));
+    CHECK(sw_device_malloc(ctx, (size_t)(nrec > 0 ? nrec : 1) * sizeof(sw_result), &d_res));
+    CHECK(sw_memcpy_h2d(ctx, d_q, q.data(), (size_t)qlen));
+    if (total) CHECK(sw_memcpy_h2d(ctx, d_db, db.data(), (size_t)total));
+    const double t0 = now_s();
+    CHECK(sw_search_device(ctx, (const char*)d_q, qlen, (const char*)d_db, offs.data(), nrec, &sc, (sw_result*)d_res, nullptr));
+    CHECK(sw_synchronize(ctx, nullptr));
+    const double t1 = now_s();
+    std::vector<sw_result> res((size_t)nrec);
+    if (nrec) CHECK(sw_memcpy_d2h(ctx, res.data(), d_res, (size_t)nrec * sizeof(sw_result)));
+    std::vector<int64_t> order((size_t)nrec);
+    for (int64_t k = 0; k < nrec; ++k) order[(size_t)k] = k;
+    std::stable_sort(order.begin(), order.end(), [&](int64_t x, int64_t y) { return res[(size_t)x].max_score > res[(size_t)y].max_score; });
+    const long long K = std::max(0ll, std::min(top, (long long)nrec));
+    printf("# query %lld letters, %lld targets, %lld letters; rank\trecord\tscore\ttarget_end\tquery_end\n", (long long)qlen, (long long)nrec, (long long)total);
+    for (long long i = 0; i < K; ++i) {
+        const sw_result& r = res[(size_t)order[(size_t)i]];
+        const long long te = r.max_pos / (qlen + 1), qe = r.max_pos % (qlen + 1);
+        printf("%lld\t%lld\t%lld\t%lld\t%lld\n", i + 1, (long long)order[(size_t)i], (long long)r.max_score, te, qe);
+    }
+    const double cells = (double)qlen * (double)total;
+    printf("\nElapsed time for database search: %f (%.1f GCUPS)\n\n", t1 - t0, t1 > t0 ? cells / (t1 - t0) / 1e9 : 0.0);
+    (void)sw_device_free(ctx, d_q); (void)sw_device_free(ctx, d_db); (void)sw_device_free(ctx, d_res);
+    sw_destroy(ctx);
+    return 0;
+}
+
 int main(int argc, char** argv) {
     long long cols = 8, rows = 9;
     bool builtin = true, dump = false, labels = false, h64 = false, backtrack = true, p8 = false;
@@ -80,6 +124,8 @@ int main(int argc, char** argv) {
     unsigned seed = 1;
     const char *fasta_a = nullptr, *fasta_b = nullptr;
     long long rec_a = 0, rec_b = 0;
+    const char *search_q = nullptr, *search_db = nullptr;
+    long long top = 10;
     sw_scores sc = {3, -3, -2};
     int npos = 0;
     for (int ai = 1; ai < argc; ++ai) {
@@ -97,13 +143,16 @@ int main(int argc, char** argv) {
         else if (f == "--gpus" && ai + 1 < argc) { const int n = atoi(argv[++ai]); for (int g = 0; g < n; ++g) devices.push_back(g); }
         else if (f == "--devices" && ai + 1 < argc) { for (char* t = strtok(argv[++ai], ","); t; t = strtok(nullptr, ",")) devices.push_back(atoi(t)); }
         else if (f == "--fasta" && ai + 2 < argc) { fasta_a = argv[++ai]; fasta_b = argv[++ai]; builtin = false; }
+        else if (f == "--search" && ai + 2 < argc) { search_q = argv[++ai]; search_db = argv[++ai]; builtin = false; }
+        else if (f == "--top" && ai + 1 < argc) top = strtoll(argv[++ai], nullptr, 10);
         else if (f == "--record-a" && ai + 1 < argc) rec_a = strtoll(argv[++ai], nullptr, 10);
         else if (f == "--record-b" && ai + 1 < argc) rec_b = strtoll(argv[++ai], nullptr, 10);
         else if (f == "--seed" && ai + 1 < argc) seed = (unsigned)strtoul(argv[++ai], nullptr, 10);
         else if (f == "--scores" && ai + 3 < argc) { sc.match = atoi(argv[++ai]); sc.mismatch = atoi(argv[++ai]); sc.gap = atoi(argv[++ai]); }
-        else { fprintf(stderr, "usage: smithW [<cols> <rows> | --fasta A.fa B.fa [--record-a I] [--record-b J]] [--seed N] [--dump | --dump-labels] [--h64] [--no-backtrack] [--scores M X G] [--gpus N | --devices 0,1,..] [--p8]\n"); return 2; }
+        else { fprintf(stderr, "usage: smithW [<cols> <rows> | --fasta A.fa B.fa [--record-a I] [--record-b J] | --search QUERY.fa DB.fa [--record-a I] [--top K]] [--seed N] [--dump | --dump-labels] [--h64] [--no-backtrack] [--scores M X G] [--gpus N | --devices 0,1,..] [--p8]\n"); return 2; }
     }
     if (npos == 1) { fprintf(stderr, "smithW: <cols> needs <rows>\n"); return 2; }
+    if (search_q) return search_main(search_q, rec_a, search_db, top, sc);
     if (fasta_a) {
         int64_t la = 0, lb = 0;
         CHECK(sw_read_fasta(fasta_a, rec_a, nullptr, 0, &la));

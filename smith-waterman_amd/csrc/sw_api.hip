@@ -76,6 +76,14 @@ struct sw_ctx {
     int* d_bnd = nullptr; size_t bnd_cap = 0;                   // batch kernel: boundary columns between strips (ints)
     int64_t opt_batch_lds = 0;          // batch kernel: dynamic LDS bytes per workgroup (caps the waves per CU; experiments)
     int64_t last_batch_kernel = 0;      // 1: the last sw_batch_device call ran on sw_batch_wave (one pair per wave)
+    // database search (sw_search_device): profile of the query, per-wave boundary columns, the schedule (device + a pinned host copy
+    // whose upload the next call waits for before it overwrites it), the work counter
+    signed char* d_sprof = nullptr; size_t sprof_cap = 0;
+    int* d_sbnd = nullptr; size_t sbnd_cap = 0;
+    swk::SearchItem* d_sitems = nullptr; swk::SearchItem* h_sitems = nullptr; size_t sitems_cap = 0;
+    hipEvent_t sitems_ev = nullptr;
+    unsigned int* d_sctr = nullptr;
+    int64_t last_search_grid = 0;       // workgroups of the last search launch
     bool xcd_round_robin = false;       // sw_xcc_probe saw workgroup i on XCD i % 8 (8 XCDs of 32 CUs)
     std::map<void*, void*> out_base;    // sw_alloc_outputs: pointer handed out -> allocation to free
     std::map<void*, float> pair_ratio;  // ... P handed out -> the store probe's ratio of its pair (~1.4: two classes of the HBM, ~2: one)
@@ -131,6 +139,12 @@ void sw_destroy(sw_ctx* c) {
     if (c->d_keys) (void)hipFree(c->d_keys);
     if (c->d_bcodes) (void)hipFree(c->d_bcodes);
     if (c->d_bnd) (void)hipFree(c->d_bnd);
+    if (c->sitems_ev) { (void)hipEventSynchronize(c->sitems_ev); (void)hipEventDestroy(c->sitems_ev); }
+    if (c->d_sprof) (void)hipFree(c->d_sprof);
+    if (c->d_sbnd) (void)hipFree(c->d_sbnd);
+    if (c->d_sitems) (void)hipFree(c->d_sitems);
+    if (c->h_sitems) (void)hipHostFree(c->h_sitems);
+    if (c->d_sctr) (void)hipFree(c->d_sctr);
     delete c;
 }
 
@@ -197,6 +211,7 @@ int64_t sw_get_option(sw_ctx* c, const char* name) {
     if (!strcmp(name, "last_split_from")) return last_tile.split_blk ? last_tile.split_from : 0;
     if (!strcmp(name, "xcd_round_robin")) return c->xcd_round_robin ? 1 : 0;
     if (!strcmp(name, "last_batch_kernel")) return c->last_batch_kernel;
+    if (!strcmp(name, "last_search_grid")) return c->last_search_grid;
     if (!strcmp(name, "placement_budget_ms")) return c->opt_place_budget_ms;
     if (!strcmp(name, "placement_hold_gib")) return c->opt_place_hold_gib;
     if (!strcmp(name, "probe_foreign_pairs")) return c->opt.probe_foreign_pairs;
@@ -725,6 +740,104 @@ int sw_batch_device_ex(sw_ctx* c, const char* d_a, int64_t a_stride, int64_t col
 int sw_batch_device(sw_ctx* c, const char* d_a, int64_t a_stride, int64_t cols, const char* d_b, int64_t b_stride, int64_t rows,
                     int64_t npairs, const sw_scores* scores, int32_t* d_H, int32_t* d_P, sw_result* d_results, void* stream_) {
     return sw_batch_device_ex(c, d_a, a_stride, cols, d_b, b_stride, rows, npairs, scores, d_H, d_P, 4, d_results, stream_);
+}
+
+// Database search (csrc/sw_search.hip): for every target k the reference fill of query x target k, score and arg-max only.  No host
+// round trip: the lengths come from the host offsets, the profile is built on the device from the query.
+int sw_search_device(sw_ctx* c, const char* d_query, int64_t qlen, const char* d_db, const int64_t* offsets, int64_t ntargets,
+                     const sw_scores* scores, sw_result* d_results, void* stream_) {
+    const sw_scores* sc = scores ? scores : &kDefaultScores;
+    if (!c || !d_query || !d_db || !offsets || !d_results || ntargets < 0) { set_err("sw_search_device: NULL pointer or negative target count"); return SW_EINVAL; }
+    if (qlen < 1 || qlen > swk::SW_MAX_DIM) { set_err("sw_search_device: query length %lld out of range 1..%lld", (long long)qlen, (long long)swk::SW_MAX_DIM); return SW_EINVAL; }
+    if (offsets[0] < 0) { set_err("sw_search_device: offsets[0] = %lld is negative", (long long)offsets[0]); return SW_EINVAL; }
+    int64_t maxlen = 0, nonempty = 0;
+    for (int64_t k = 0; k < ntargets; ++k) {
+        const int64_t len = offsets[k + 1] - offsets[k];
+        if (len < 0) { set_err("sw_search_device: offsets decrease at target %lld", (long long)k); return SW_EINVAL; }
+        if (len > swk::SW_MAX_DIM) { set_err("sw_search_device: target %lld has length %lld (max %lld)", (long long)k, (long long)len, (long long)swk::SW_MAX_DIM); return SW_EINVAL; }
+        maxlen = std::max(maxlen, len);
+        nonempty += len > 0;
+    }
+    if (int rc = check_dims(qlen, maxlen, sc)) return rc;
+    if (ntargets == 0) return SW_OK;
+    hipStream_t stream = (hipStream_t)stream_;
+    HIP_TRY(hipSetDevice(c->device));
+    DevOrder order(c, stream, false);
+    if (order.rc) return order.rc;
+    // empty targets keep the zeros: {0, 0, 0}
+    HIP_TRY(hipMemsetAsync(d_results, 0, (size_t)ntargets * sizeof(sw_result), stream));
+    if (nonempty == 0) return SW_OK;
+    const int C = qlen <= 256 ? 4 : qlen <= 512 ? 8 : 16;
+    const int64_t nstrips = (qlen + 64 * C - 1) / (64 * C);
+    const int64_t qpad = nstrips * 64 * C;
+    const bool wide = sc->match > 127 || sc->mismatch < -127;   // (mismatch <= match: both fit a signed byte otherwise)
+    bool fresh = false;
+    // the schedule: non-empty targets by decreasing length (stable), uploaded from a pinned copy the previous upload has left
+    if (c->sitems_ev) HIP_TRY(hipEventSynchronize(c->sitems_ev));
+    else HIP_TRY(hipEventCreateWithFlags(&c->sitems_ev, hipEventDisableTiming));
+    if ((size_t)nonempty > c->sitems_cap) {
+        HIP_TRY(hipStreamSynchronize(stream));
+        if (c->d_sitems) HIP_TRY(hipFree(c->d_sitems));
+        if (c->h_sitems) HIP_TRY(hipHostFree(c->h_sitems));
+        c->d_sitems = nullptr; c->h_sitems = nullptr; c->sitems_cap = 0;
+        if (hipMalloc((void**)&c->d_sitems, (size_t)nonempty * sizeof(swk::SearchItem)) != hipSuccess ||
+            hipHostMalloc((void**)&c->h_sitems, (size_t)nonempty * sizeof(swk::SearchItem), 0) != hipSuccess) {
+            set_err("sw_search_device: workspace allocation failed");
+            return SW_ENOMEM;
+        }
+        c->sitems_cap = (size_t)nonempty;
+    }
+    {
+        std::vector<int64_t> order_idx;
+        order_idx.reserve((size_t)nonempty);
+        for (int64_t k = 0; k < ntargets; ++k)
+            if (offsets[k + 1] > offsets[k]) order_idx.push_back(k);
+        std::stable_sort(order_idx.begin(), order_idx.end(),
+                         [&](int64_t x, int64_t y) { return offsets[x + 1] - offsets[x] > offsets[y + 1] - offsets[y]; });
+        for (int64_t i = 0; i < nonempty; ++i) {
+            const int64_t k = order_idx[(size_t)i];
+            c->h_sitems[i] = swk::SearchItem{offsets[k], k, offsets[k + 1] - offsets[k]};
+        }
+    }
+    HIP_TRY(hipMemcpyAsync(c->d_sitems, c->h_sitems, (size_t)nonempty * sizeof(swk::SearchItem), hipMemcpyHostToDevice, stream));
+    HIP_TRY(hipEventRecord(c->sitems_ev, stream));
+    // the profile: SW_SEARCH_ROWS x qpad bytes
+    if (int rc = grow_workspace((void**)&c->d_sprof, c->sprof_cap, (size_t)(swk::SW_SEARCH_ROWS * qpad), 1, 0, stream, fresh)) return rc;
+    {
+        const int64_t n = swk::SW_SEARCH_ROWS * qpad;
+        hipLaunchKernelGGL(swk::sw_search_profile, dim3((unsigned)std::min<int64_t>((n + 255) / 256, 4096)), dim3(256), 0, stream,
+                           (const unsigned char*)d_query, qlen, qpad, c->d_sprof, sc->match, sc->mismatch, wide ? 1 : 0);
+        HIP_TRY(hipGetLastError());
+    }
+    if (!c->d_sctr) HIP_TRY(hipMalloc((void**)&c->d_sctr, 64));
+    HIP_TRY(hipMemsetAsync(c->d_sctr, 0, 4, stream));
+    // persistent waves: as many workgroups (4 waves) as are resident, fewer where the targets are fewer or the boundary columns of
+    // a multi-strip query (one per wave, sized by the longest target) would pass 1 GiB
+    auto kern = C == 4 ? (wide ? swk::sw_search_wave<4, true> : swk::sw_search_wave<4, false>)
+              : C == 8 ? (wide ? swk::sw_search_wave<8, true> : swk::sw_search_wave<8, false>)
+                       : (wide ? swk::sw_search_wave<16, true> : swk::sw_search_wave<16, false>);
+    int per_cu = 0;
+    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, 256, 0));
+    if (per_cu < 1) { set_err("the search kernel does not fit a CU on this device"); return SW_EDEVICE; }
+    int64_t grid = std::min<int64_t>((int64_t)per_cu * c->num_cus, (nonempty + 3) / 4);
+    const int64_t bnd_per = nstrips > 1 ? ((maxlen + 160 + 3) / 4) * 4 : 0;
+    if (bnd_per) {
+        grid = std::max<int64_t>(1, std::min<int64_t>(grid, (1ll << 30) / (bnd_per * 4 * 4)));
+        if (int rc = grow_workspace((void**)&c->d_sbnd, c->sbnd_cap, (size_t)(grid * 4 * bnd_per), 4, 0, stream, fresh)) return rc;
+    }
+    swk::SearchParams sp;
+    memset(&sp, 0, sizeof sp);
+    sp.db = (const unsigned char*)d_db;
+    sp.items = c->d_sitems; sp.nitems = nonempty;
+    sp.prof = c->d_sprof; sp.qpad = qpad; sp.qlen = qlen;
+    sp.match = sc->match; sp.mismatch = sc->mismatch; sp.ngap = -sc->gap;
+    sp.bnd = bnd_per ? c->d_sbnd : nullptr; sp.bnd_per = bnd_per;
+    sp.counter = c->d_sctr;
+    sp.results = d_results;
+    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(256), 0, stream, sp);
+    HIP_TRY(hipGetLastError());
+    c->last_search_grid = grid;
+    return SW_OK;
 }
 
 // backtrack() of every pair of a batch (serial_smithW.c:262-277 per pair): one lane per pair walks its P from

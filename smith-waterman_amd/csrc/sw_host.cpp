@@ -167,4 +167,47 @@ int sw_read_fasta(const char* path, int64_t record, char* seq, int64_t cap, int6
     return SW_OK;
 }
 
+// All records in one pass (the state machine of sw_read_fasta, every record kept): the database side of sw_search_device.
+int sw_read_fasta_db(const char* path, char* seq, int64_t seq_cap, int64_t* offsets, int64_t offsets_cap, int64_t* nrecords, int64_t* total_len) {
+    if (!path || !nrecords || !total_len || (seq && (seq_cap < 0 || !offsets || offsets_cap < 1))) {
+        swh::set_err("sw_read_fasta_db: bad argument");
+        return SW_EINVAL;
+    }
+    FILE* f = fopen(path, "rb");
+    if (!f) { swh::set_err("sw_read_fasta_db: cannot open %s", path); return SW_EINVAL; }
+    int64_t cur = -1, n = 0;       // cur: index of the record being read (-1: before the first header)
+    bool at_line_start = true, skip_line = false, overflow = false;
+    auto start_record = [&]() {    // record cur + 1 begins at byte n
+        ++cur;
+        if (seq) { if (cur < offsets_cap) offsets[cur] = n; else overflow = true; }
+    };
+    char buf[1 << 16];
+    size_t got;
+    while ((got = fread(buf, 1, sizeof buf, f)) > 0) {
+        for (size_t i = 0; i < got; ++i) {
+            const unsigned char ch = (unsigned char)buf[i];
+            if (ch == '\n' || ch == '\r') { at_line_start = true; skip_line = false; continue; }
+            if (at_line_start) {
+                at_line_start = false;
+                if (ch == '>') { start_record(); skip_line = true; continue; }
+                if (ch == ';') { skip_line = true; continue; }
+                if (cur < 0) start_record();   // headerless file: a single record
+            }
+            if (skip_line || ch == ' ' || ch == '\t') continue;
+            if (seq) { if (n < seq_cap) seq[n] = (char)((ch >= 'a' && ch <= 'z') ? ch - 32 : ch); else overflow = true; }
+            ++n;
+        }
+    }
+    const bool err = ferror(f) != 0;
+    fclose(f);
+    if (err) { swh::set_err("sw_read_fasta_db: read error on %s", path); return SW_EINVAL; }
+    *nrecords = cur + 1;
+    *total_len = n;
+    if (seq) {
+        if (cur + 1 < offsets_cap) offsets[cur + 1] = n; else overflow = true;
+        if (overflow) { swh::set_err("sw_read_fasta_db: buffers too small (%lld bytes, %lld records)", (long long)n, (long long)(cur + 1)); return SW_EINVAL; }
+    }
+    return SW_OK;
+}
+
 }  // extern "C"

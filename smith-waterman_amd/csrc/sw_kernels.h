@@ -108,6 +108,23 @@ __global__ void sw_batch_wave(BatchParams p);
 template <bool LE4, bool K12, bool PB1>
 __global__ void sw_batch_wave16(BatchParams p);   // two pairs per wave on packed 16-bit lanes (score + exact maxPos; PB1: int8 P too)
 
+// sw_search.hip: one query against many targets of any length (database search)
+constexpr int SW_SEARCH_ROWS = 257;      // profile rows: one per byte value + PAD (the letter of every row outside a target)
+struct SearchItem { int64_t start, idx, len; };   // a target in schedule order: first byte in db, index in the caller's order, length
+struct SearchParams {
+    const unsigned char* db;             // the targets back to back
+    const SearchItem* items; int64_t nitems;
+    const signed char* prof; int64_t qpad;   // SW_SEARCH_ROWS x qpad profile (sw_search_profile), qpad = strips * 64 * C
+    int64_t qlen;
+    int match, mismatch, ngap;           // plain scores, ngap = -gap
+    int* bnd; int64_t bnd_per;           // per resident wave: boundary column between strips (ints), only when qlen > 64 * C
+    unsigned int* counter;               // next item (zero at launch)
+    sw_result* results;                  // caller's order
+};
+__global__ void sw_search_profile(const unsigned char* q, int64_t qlen, int64_t qpad, signed char* prof, int match, int mismatch, int wide);
+template <int C, bool WIDE>
+__global__ void sw_search_wave(SearchParams p);
+
 template <typename HT, int B>
 __global__ void sw_strip_scan(const unsigned char* a, const unsigned char* b, FillParams p);
 template <typename HT, int NS, int NC>

@@ -2,7 +2,7 @@
 """Post-build audit of the gfx950 ISA of sw_kernels.hip (run by `make check_isa`):
   * v126/v127 (landing registers of the hand-tracked edge prefetch) appear ONLY in the two asm
     statements that own them;
-  * no scratch (spills) in the fill kernels."""
+  * no scratch (spills) in the fill kernels, none at all in the search kernels (sw_search.hip)."""
 import re, subprocess, sys, os, tempfile
 here = os.path.dirname(os.path.abspath(__file__))
 src = os.path.join(here, "..", "smith-waterman_amd", "csrc", "sw_kernels.hip")
@@ -59,5 +59,13 @@ for txt, what, lim in ((s3, "traceback", 0), (dev_asm("sw_batch.hip"), "batch", 
     for m in re.finditer(r"\.private_segment_fixed_size:\s*(\d+)", txt):
         if int(m.group(1)) > lim:
             print(f"scratch in use ({what}):", m.group(0)); sys.exit(1)
+# sw_search.hip (database search): no scratch at all in the search kernels, and the work counter is taken with a VECTOR buffer atomic
+s4 = dev_asm("sw_search.hip")
+for m in re.finditer(r"\.private_segment_fixed_size:\s*(\d+)", s4):
+    if int(m.group(1)) > 0:
+        print("scratch in use (search):", m.group(0)); sys.exit(1)
+nsearch = len(re.findall(r"^\s*\.name:\s+\S*sw_search_wave", s4, flags=re.M))
+if nsearch < 6 or len(re.findall(r"^\s*buffer_atomic_add ", s4, flags=re.M)) < nsearch:
+    print(f"search kernels: expected a vector buffer atomic work counter in each of {nsearch} kernels"); sys.exit(1)
 n = len(re.findall(r"global_load_dwordx2 v\[126:127\]", s))
-print(f"check_isa ok: {n} prefetch sites, v126/v127 private; {nprod} producer paths keep v100..v120 private; traceback window v62..v127 private; no scratch")
+print(f"check_isa ok: {n} prefetch sites, v126/v127 private; {nprod} producer paths keep v100..v120 private; traceback window v62..v127 private; no scratch; {nsearch} search kernels without scratch")
