@@ -5,6 +5,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <iterator>
 #include <map>
 #include <mutex>
 #include <string>
@@ -84,10 +85,20 @@ struct sw_ctx {
     hipEvent_t sitems_ev = nullptr;
     unsigned int* d_sctr = nullptr;
     int64_t last_search_grid = 0;       // workgroups of the last search launch
+    int search_per_cu[swp::kSearchKernels] = {};   // occupancy of every sw_search_wave instantiation at 256 threads ...
+    bool search_per_cu_known = false;              // ... queried at the first search
     bool xcd_round_robin = false;       // sw_xcc_probe saw workgroup i on XCD i % 8 (8 XCDs of 32 CUs)
     std::map<void*, void*> out_base;    // sw_alloc_outputs: pointer handed out -> allocation to free
     std::map<void*, float> pair_ratio;  // ... P handed out -> the store probe's ratio of its pair (~1.4: two classes of the HBM, ~2: one)
 };
+
+// A launch table: every instantiation beside the index the planner gives it, checked at compile time to sit at that index.
+template <typename K> struct Indexed { int index; K k; };
+template <typename K, size_t N> constexpr bool at_their_indices(const Indexed<K> (&t)[N]) {
+    for (size_t i = 0; i < N; ++i)
+        if (t[i].index != (int)i) return false;
+    return true;
+}
 
 extern "C" {
 
@@ -321,12 +332,17 @@ static unsigned next_gbias(sw_ctx* c, hipStream_t stream) {
     return (c->epoch8 << 24) | 0x10000u;
 }
 
+static swp::DeviceFacts device_facts(const sw_ctx* c) {
+    swp::DeviceFacts dev;
+    dev.num_cus = c->num_cus; dev.xcd_round_robin = c->xcd_round_robin; dev.s2_per_cu = c->s2_per_cu;
+    std::copy(std::begin(c->search_per_cu), std::end(c->search_per_cu), dev.search_per_cu);
+    return dev;
+}
+
 static int plan_for(sw_ctx* c, const swp::PlanJob& pj, swp::FillPlan& plan) {
     if (c->opt.engine == 0 && c->s2_per_cu < 1)
         HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&c->s2_per_cu, swk::sw_systolic2<6, false>, 768, 0));
-    swp::DeviceFacts dev;
-    dev.num_cus = c->num_cus; dev.xcd_round_robin = c->xcd_round_robin; dev.s2_per_cu = c->s2_per_cu;
-    plan = swp::plan_fill(pj, dev, c->opt);
+    plan = swp::plan_fill(pj, device_facts(c), c->opt);
     return SW_OK;
 }
 
@@ -575,96 +591,77 @@ int sw_fill_band_device(sw_ctx* c, const char* d_a, int64_t cols, const char* d_
     return fill_one(c, scores, j, cols, total_rows, d_result, stream_, "sw_fill_band_device");
 }
 
-// The batch kernel proper (csrc/sw_batch.hip): one pair per wave, no inter-workgroup traffic.  Returns 1 when the batch is not
-// eligible (the caller then runs it on the single-pair machinery): more than 8 distinct letters, scores that do not fit a signed
-// byte, or a pair whose matrix does not fit a 2 GiB buffer descriptor.
-static int batch_one_pair_per_wave(sw_ctx* c, const char* d_a, int64_t a_stride, int64_t cols, const char* d_b, int64_t b_stride, int64_t rows,
-                                   int64_t npairs, const sw_scores* sc, int32_t* d_H, void* d_P, int p_elem_bytes, sw_result* d_results,
-                                   hipStream_t stream) {
-    if (sc->match > 127 || sc->match < -127 || sc->mismatch > 127 || sc->mismatch < -127) return 1;
-    if ((double)(rows + 132) * (double)(cols + 1) * 4.0 >= 2147483648.0) return 1;
+// the instantiations of the batch kernels (sw_batch.hip), picked by swp::batch_kernel
+using BatchKernel = void (*)(swk::BatchParams);
+static constexpr Indexed<BatchKernel> kBatch[] = {
+    {swp::batch_wave_index(4, 0), swk::sw_batch_wave<4, 0>}, {swp::batch_wave_index(4, 1), swk::sw_batch_wave<4, 1>},
+    {swp::batch_wave_index(4, 4), swk::sw_batch_wave<4, 4>}, {swp::batch_wave_index(8, 0), swk::sw_batch_wave<8, 0>},
+    {swp::batch_wave_index(8, 1), swk::sw_batch_wave<8, 1>}, {swp::batch_wave_index(8, 4), swk::sw_batch_wave<8, 4>},
+    {swp::batch_wave_index(16, 0), swk::sw_batch_wave<16, 0>}, {swp::batch_wave_index(16, 1), swk::sw_batch_wave<16, 1>},
+    {swp::batch_wave_index(16, 4), swk::sw_batch_wave<16, 4>},
+    {swp::batch_wave16_index(false, false, false), swk::sw_batch_wave16<false, false, false>},
+    {swp::batch_wave16_index(false, false, true), swk::sw_batch_wave16<false, false, true>},
+    {swp::batch_wave16_index(false, true, false), swk::sw_batch_wave16<false, true, false>},
+    {swp::batch_wave16_index(false, true, true), swk::sw_batch_wave16<false, true, true>},
+    {swp::batch_wave16_index(true, false, false), swk::sw_batch_wave16<true, false, false>},
+    {swp::batch_wave16_index(true, false, true), swk::sw_batch_wave16<true, false, true>},
+    {swp::batch_wave16_index(true, true, false), swk::sw_batch_wave16<true, true, false>},
+    {swp::batch_wave16_index(true, true, true), swk::sw_batch_wave16<true, true, true>},
+};
+static_assert(std::size(kBatch) == swp::kBatchKernels && at_their_indices(kBatch));
+
+// The batch kernel proper (csrc/sw_batch.hip): one pair per wave, no inter-workgroup traffic.  Carries out a plan whose `wave` is set;
+// returns 1 when the batch has more than 8 distinct letters after all (found on the device: the caller then runs it on the single-pair
+// machinery).
+static int batch_one_pair_per_wave(sw_ctx* c, const swp::BatchPlan& plan, const char* d_a, int64_t a_stride, int64_t cols, const char* d_b,
+                                   int64_t b_stride, int64_t rows, int64_t npairs, const sw_scores* sc, int32_t* d_H, void* d_P, int p_elem_bytes,
+                                   sw_result* d_results, hipStream_t stream) {
+    bool fresh = false;
+    if (int rc = grow_workspace((void**)&c->d_bcodes, c->bcodes_cap, plan.bcodes_need, 1, 64, stream, fresh)) return rc;
+    if (int rc = grow_workspace((void**)&c->d_bnd, c->bnd_cap, plan.bnd_need, 4, 0, stream, fresh)) return rc;
     const unsigned char* ua = (const unsigned char*)d_a;
     const unsigned char* ub = (const unsigned char*)d_b;
     // alphabet of the whole batch -> letter codes; the count decides whether the profile look-up applies
-    const int64_t total_letters = (cols + rows) * npairs;
-    const unsigned nscan = (unsigned)std::max<int64_t>(1, std::min<int64_t>((total_letters + 4095) / 4096, 2048));
-    hipLaunchKernelGGL(swk::sw_prep_scan, dim3(nscan), dim3(256), 0, stream, ua, cols, a_stride, ub, rows, b_stride, npairs, c->d_part);
-    // (one map for the half million blocks of sw_batch_codes: every one of them ORing 2048 maps by itself cost 29 ms per 100 000 pairs)
-    hipLaunchKernelGGL(swk::sw_prep_reduce, dim3(1), dim3(256), 0, stream, c->d_part, (int)nscan);
-    const int front = 64;
-    const int64_t per = ((rows + front + 80 + 72 + 15) / 16) * 16;   // (+40: the drain steps of the delayed int8 P stores read on)
-    const int C = cols <= 256 ? 4 : cols <= 512 ? 8 : 16;
-    const int64_t nstrips = (cols + 64 * C - 1) / (64 * C);
-    const int64_t bnd_per = nstrips > 1 ? ((rows + 160 + 3) / 4) * 4 : 0;
-    // pairs per launch: bounds the workspace (codes: ~1.2 KB per 1024-row pair)
-    const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(npairs, std::min<int64_t>((1ll << 30) / per, bnd_per ? (1ll << 30) / (bnd_per * 4) : npairs)));
-    if ((size_t)(chunk * per) > c->bcodes_cap) {
-        HIP_TRY(hipStreamSynchronize(stream));
-        if (c->d_bcodes) HIP_TRY(hipFree(c->d_bcodes));
-        c->d_bcodes = nullptr; c->bcodes_cap = 0;
-        if (hipMalloc((void**)&c->d_bcodes, (size_t)(chunk * per) + 64) != hipSuccess) { set_err("workspace allocation failed"); return SW_ENOMEM; }
-        c->bcodes_cap = (size_t)(chunk * per);
-    }
-    if (bnd_per && (size_t)(chunk * bnd_per) > c->bnd_cap) {
-        HIP_TRY(hipStreamSynchronize(stream));
-        if (c->d_bnd) HIP_TRY(hipFree(c->d_bnd));
-        c->d_bnd = nullptr; c->bnd_cap = 0;
-        if (hipMalloc((void**)&c->d_bnd, (size_t)(chunk * bnd_per) * 4) != hipSuccess) { set_err("workspace allocation failed"); return SW_ENOMEM; }
-        c->bnd_cap = (size_t)(chunk * bnd_per);
-    }
+    hipLaunchKernelGGL(swk::sw_prep_scan, dim3((unsigned)plan.scan_blocks), dim3(256), 0, stream, ua, cols, a_stride, ub, rows, b_stride, npairs, c->d_part);
+    // (one map for the half million blocks of sw_batch_codes: every one of them ORing all the maps by itself cost 29 ms per 100 000 pairs)
+    hipLaunchKernelGGL(swk::sw_prep_reduce, dim3(1), dim3(256), 0, stream, c->d_part, plan.scan_blocks);
     // lane 0 of a later strip also reads boundary entries below the matrix that no strip of THIS call writes: they must not hold
     // an earlier call's scores (a cell outside the matrix may never exceed the cells of the matrix, see the arg-max in sw_batch.hip)
-    if (bnd_per) HIP_TRY(hipMemsetAsync(c->d_bnd, 0, (size_t)(chunk * bnd_per) * 4, stream));
+    if (plan.bnd_need) HIP_TRY(hipMemsetAsync(c->d_bnd, 0, plan.bnd_need * 4, stream));
     const int64_t cells = (cols + 1) * (rows + 1);
+    const int pb = d_P ? p_elem_bytes : 0;
     unsigned int nletters = 0;
-    // Score-only batches whose scores fit 15 bits run two pairs per wave on packed 16-bit lanes (sw_batch_wave16: 5 VALU per two cells
-    // instead of 8).  (debug bit 18: off, A/B runs)
-    const bool fits16 = npairs >= 2 && C == 16 && (int64_t)sc->match * std::min(cols, rows) < 32000 && -sc->gap < 32000 && rows < 65000 && !(c->opt.debug_flags & swk::DBG_BATCH_NO_WAVE16);
-    const bool k12 = (int64_t)sc->match * std::min(cols, rows) < 4096;   // (scores of 12 bits: the arg-max runs on score * 16 + column keys)
-    // ... and with an int8 P as the only matrix, P codes from packed arithmetic (debug bit 21: off)
-    const bool packed16 = fits16 && !d_H && (!d_P || (p_elem_bytes == 1 && !(c->opt.debug_flags & swk::DBG_BATCH_NO_PACKED_P)));
-    for (int64_t k0 = 0; k0 < npairs; k0 += chunk) {
-        const int64_t n = std::min(chunk, npairs - k0);
-        hipLaunchKernelGGL(swk::sw_batch_codes, dim3((unsigned)std::min<int64_t>((per + 255) / 256, 64), (unsigned)std::min<int64_t>(n, 65535)), dim3(256), 0, stream,
-                           ub + k0 * b_stride, rows, b_stride, c->d_bcodes, per, front, (const unsigned int*)c->d_part, 1, c->d_alpha + 64, n);
+    for (int64_t k0 = 0; k0 < npairs; k0 += plan.chunk) {
+        const int64_t n = std::min(plan.chunk, npairs - k0);
+        hipLaunchKernelGGL(swk::sw_batch_codes, dim3((unsigned)plan.codes_blocks, (unsigned)std::min<int64_t>(n, 65535)), dim3(256), 0, stream,
+                           ub + k0 * b_stride, rows, b_stride, c->d_bcodes, plan.per, plan.front, (const unsigned int*)c->d_part, 1, c->d_alpha + 64, n);
         HIP_TRY(hipGetLastError());
         if (k0 == 0) {   // the letter count (4 bytes) decides the path: the one host round trip of a batch call
             HIP_TRY(hipMemcpyAsync(&nletters, c->d_alpha + 64 + 256, 4, hipMemcpyDeviceToHost, stream));
             HIP_TRY(hipStreamSynchronize(stream));
-            if (nletters > 8u) return 1;
         }
+        const int k = swp::batch_kernel(plan, nletters, n, pb);
+        if (k < 0) return 1;
         swk::BatchParams bp;
         memset(&bp, 0, sizeof bp);
         bp.a = ua + k0 * a_stride; bp.a_pstride = a_stride; bp.cols = cols;
-        bp.bcode = c->d_bcodes; bp.bcode_pstride = per; bp.bfront = front;
+        bp.bcode = c->d_bcodes; bp.bcode_pstride = plan.per; bp.bfront = plan.front;
         bp.rows = rows; bp.npairs = n; bp.atab = c->d_alpha + 64;
         bp.H = d_H ? d_H + k0 * cells : nullptr;
         bp.P = d_P ? (void*)((char*)d_P + k0 * cells * p_elem_bytes) : nullptr;
         bp.hp_pstride = cells;
         bp.match = sc->match; bp.mismatch = sc->mismatch; bp.ngap = -sc->gap;
-        bp.bnd = c->d_bnd; bp.bnd_pstride = bnd_per;
+        bp.bnd = c->d_bnd; bp.bnd_pstride = plan.bnd_per;
         bp.results = d_results + k0;
         bp.debug = (int)(c->opt.debug_flags & swk::DBG_BATCH_MASK);
-        const int pb = d_P ? p_elem_bytes : 0;
-        if (packed16 && n >= 2) {
-            const dim3 grid16((unsigned)(((n + 1) / 2 + 3) / 4)), block16(256);   // 4 waves = 8 pairs per workgroup
-            if (d_P) {
-                if (nletters <= 4u) { if (k12) hipLaunchKernelGGL((swk::sw_batch_wave16<true, true, true>), grid16, block16, 0, stream, bp); else hipLaunchKernelGGL((swk::sw_batch_wave16<true, false, true>), grid16, block16, 0, stream, bp); }
-                else { if (k12) hipLaunchKernelGGL((swk::sw_batch_wave16<false, true, true>), grid16, block16, 0, stream, bp); else hipLaunchKernelGGL((swk::sw_batch_wave16<false, false, true>), grid16, block16, 0, stream, bp); }
-            } else if (nletters <= 4u) { if (k12) hipLaunchKernelGGL((swk::sw_batch_wave16<true, true, false>), grid16, block16, 0, stream, bp); else hipLaunchKernelGGL((swk::sw_batch_wave16<true, false, false>), grid16, block16, 0, stream, bp); }
-            else { if (k12) hipLaunchKernelGGL((swk::sw_batch_wave16<false, true, false>), grid16, block16, 0, stream, bp); else hipLaunchKernelGGL((swk::sw_batch_wave16<false, false, false>), grid16, block16, 0, stream, bp); }
-            HIP_TRY(hipGetLastError());
-            c->last_batch_kernel = 2;
-            continue;
-        }
-        const dim3 grid((unsigned)((n + 3) / 4)), block(256);   // 4 pairs (waves) per workgroup
-#define SB_LAUNCH(CC, PP) if (C == CC && pb == PP) hipLaunchKernelGGL((swk::sw_batch_wave<CC, PP>), grid, block, (size_t)c->opt_batch_lds, stream, bp);
-        SB_LAUNCH(4, 0) SB_LAUNCH(4, 1) SB_LAUNCH(4, 4) SB_LAUNCH(8, 0) SB_LAUNCH(8, 1) SB_LAUNCH(8, 4) SB_LAUNCH(16, 0) SB_LAUNCH(16, 1) SB_LAUNCH(16, 4)
-#undef SB_LAUNCH
+        const bool two = k >= swp::kBatchWave16;   // two pairs per wave (sw_batch_wave16)
+        const int64_t per_block = two ? 8 : 4;     // 4 waves per workgroup
+        hipLaunchKernelGGL(kBatch[k].k, dim3((unsigned)((n + per_block - 1) / per_block)), dim3(256), two ? 0 : (size_t)c->opt_batch_lds, stream, bp);
         HIP_TRY(hipGetLastError());
+        if (two) c->last_batch_kernel = 2;
     }
     if (c->last_batch_kernel != 2) c->last_batch_kernel = 1;
-    c->last_grid = (chunk + 3) / 4; c->last_plan.S = nstrips;   // (sw_get_option "last_grid", "last_strips")
+    c->last_grid = plan.grid; c->last_plan.S = plan.nstrips;   // (sw_get_option "last_grid", "last_strips")
     return SW_OK;
 }
 
@@ -708,23 +705,23 @@ int sw_batch_device_ex(sw_ctx* c, const char* d_a, int64_t a_stride, int64_t col
     HIP_TRY(hipSetDevice(c->device));
     DevOrder order(c, stream, false);
     if (order.rc) return order.rc;
+    swp::BatchJob bj;
+    bj.cols = cols; bj.rows = rows; bj.npairs = npairs; bj.has_H = d_H; bj.has_P = d_P; bj.p_elem_bytes = p_elem_bytes;
+    bj.match = sc->match; bj.mismatch = sc->mismatch; bj.gap = sc->gap;
+    const swp::BatchPlan plan = swp::plan_batch(bj, c->opt);
     c->last_batch_kernel = 0;
-    if (!(c->opt.debug_flags & swk::DBG_BATCH_SINGLE_PAIR)) {
-        int rc = batch_one_pair_per_wave(c, d_a, a_stride, cols, d_b, b_stride, rows, npairs, sc, d_H, d_P, p_elem_bytes, d_results, stream);
-        if (rc != 1) return rc;      // 1: not eligible (alphabet of more than 8 letters, scores beyond a byte, huge pairs)
+    if (plan.wave) {
+        int rc = batch_one_pair_per_wave(c, plan, d_a, a_stride, cols, d_b, b_stride, rows, npairs, sc, d_H, d_P, p_elem_bytes, d_results, stream);
+        if (rc != 1) return rc;      // 1: not eligible after all (an alphabet of more than 8 letters)
     }
-    const int64_t chunk_max = 4096;   // pairs per launch: bounds the edge / padded-b workspace
-    if ((size_t)std::min(npairs, chunk_max) > c->keys_cap) {
-        HIP_TRY(hipStreamSynchronize(stream));
-        if (c->d_keys) HIP_TRY(hipFree(c->d_keys));
-        c->keys_cap = (size_t)std::min(npairs, chunk_max);
-        if (hipMalloc((void**)&c->d_keys, c->keys_cap * 8) != hipSuccess) { c->d_keys = nullptr; c->keys_cap = 0; set_err("workspace allocation failed"); return SW_ENOMEM; }
-    }
+    // the fall-back: the single-pair machinery, plan.single_chunk pairs per launch
+    bool fresh = false;
+    if (int rc = grow_workspace((void**)&c->d_keys, c->keys_cap, (size_t)plan.single_chunk, 8, 0, stream, fresh)) return rc;
     HIP_TRY(hipMemsetAsync(c->d_key, 0, 16, stream));
     c->key_dirty = true;
     const int64_t cells = (cols + 1) * (rows + 1);
-    for (int64_t k0 = 0; k0 < npairs; k0 += chunk_max) {
-        const int64_t n = std::min(chunk_max, npairs - k0);
+    for (int64_t k0 = 0; k0 < npairs; k0 += plan.single_chunk) {
+        const int64_t n = std::min(plan.single_chunk, npairs - k0);
         HIP_TRY(hipMemsetAsync(c->d_keys, 0, (size_t)n * 8, stream));
         FillJob j = {d_a + k0 * a_stride, cols, d_b + k0 * b_stride, rows, d_H ? (void*)(d_H + k0 * cells) : nullptr, 4,
                      d_P ? (void*)((char*)d_P + k0 * cells * p_elem_bytes) : nullptr, cols + 1, nullptr, nullptr, nullptr, n, a_stride, b_stride,
@@ -740,6 +737,32 @@ int sw_batch_device_ex(sw_ctx* c, const char* d_a, int64_t a_stride, int64_t col
 int sw_batch_device(sw_ctx* c, const char* d_a, int64_t a_stride, int64_t cols, const char* d_b, int64_t b_stride, int64_t rows,
                     int64_t npairs, const sw_scores* scores, int32_t* d_H, int32_t* d_P, sw_result* d_results, void* stream_) {
     return sw_batch_device_ex(c, d_a, a_stride, cols, d_b, b_stride, rows, npairs, scores, d_H, d_P, 4, d_results, stream_);
+}
+
+// the instantiations of the search kernel (sw_search.hip), picked by swp::plan_search
+using SearchKernel = void (*)(swk::SearchParams);
+static constexpr Indexed<SearchKernel> kSearch[] = {
+    {swp::search_kernel_index(4, false), swk::sw_search_wave<4, false>}, {swp::search_kernel_index(4, true), swk::sw_search_wave<4, true>},
+    {swp::search_kernel_index(8, false), swk::sw_search_wave<8, false>}, {swp::search_kernel_index(8, true), swk::sw_search_wave<8, true>},
+    {swp::search_kernel_index(16, false), swk::sw_search_wave<16, false>}, {swp::search_kernel_index(16, true), swk::sw_search_wave<16, true>},
+};
+static_assert(std::size(kSearch) == swp::kSearchKernels && at_their_indices(kSearch));
+
+// The search schedule's device buffer and the pinned copy it is uploaded from, grown together to `need` items (the caller has waited
+// for the last upload from the pinned copy).
+static int grow_schedule(sw_ctx* c, size_t need, hipStream_t stream) {
+    if (need <= c->sitems_cap) return SW_OK;
+    HIP_TRY(hipStreamSynchronize(stream));
+    if (c->d_sitems) HIP_TRY(hipFree(c->d_sitems));
+    if (c->h_sitems) HIP_TRY(hipHostFree(c->h_sitems));
+    c->d_sitems = nullptr; c->h_sitems = nullptr; c->sitems_cap = 0;
+    if (hipMalloc((void**)&c->d_sitems, need * sizeof(swk::SearchItem)) != hipSuccess ||
+        hipHostMalloc((void**)&c->h_sitems, need * sizeof(swk::SearchItem), 0) != hipSuccess) {
+        set_err("sw_search_device: workspace allocation failed");
+        return SW_ENOMEM;
+    }
+    c->sitems_cap = need;
+    return SW_OK;
 }
 
 // Database search (csrc/sw_search.hip): for every target k the reference fill of query x target k, score and arg-max only.  No host
@@ -767,76 +790,42 @@ int sw_search_device(sw_ctx* c, const char* d_query, int64_t qlen, const char* d
     // empty targets keep the zeros: {0, 0, 0}
     HIP_TRY(hipMemsetAsync(d_results, 0, (size_t)ntargets * sizeof(sw_result), stream));
     if (nonempty == 0) return SW_OK;
-    const int C = qlen <= 256 ? 4 : qlen <= 512 ? 8 : 16;
-    const int64_t nstrips = (qlen + 64 * C - 1) / (64 * C);
-    const int64_t qpad = nstrips * 64 * C;
-    const bool wide = sc->match > 127 || sc->mismatch < -127;   // (mismatch <= match: both fit a signed byte otherwise)
-    bool fresh = false;
-    // the schedule: non-empty targets by decreasing length (stable), uploaded from a pinned copy the previous upload has left
+    // occupancy of every instantiation, once per context: the grid depends on the one the plan picks
+    if (!c->search_per_cu_known) {
+        for (int k = 0; k < swp::kSearchKernels; ++k) HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&c->search_per_cu[k], kSearch[k].k, 256, 0));
+        c->search_per_cu_known = true;
+    }
+    swp::SearchJob sj;
+    sj.qlen = qlen; sj.maxlen = maxlen; sj.ntargets = nonempty; sj.match = sc->match; sj.mismatch = sc->mismatch; sj.gap = sc->gap;
+    const swp::SearchPlan plan = swp::plan_search(sj, device_facts(c));
+    if (c->search_per_cu[plan.kernel] < 1) { set_err("the search kernel does not fit a CU on this device"); return SW_EDEVICE; }
+    // the schedule is uploaded from a pinned copy: the previous upload has to have left it
     if (c->sitems_ev) HIP_TRY(hipEventSynchronize(c->sitems_ev));
     else HIP_TRY(hipEventCreateWithFlags(&c->sitems_ev, hipEventDisableTiming));
-    if ((size_t)nonempty > c->sitems_cap) {
-        HIP_TRY(hipStreamSynchronize(stream));
-        if (c->d_sitems) HIP_TRY(hipFree(c->d_sitems));
-        if (c->h_sitems) HIP_TRY(hipHostFree(c->h_sitems));
-        c->d_sitems = nullptr; c->h_sitems = nullptr; c->sitems_cap = 0;
-        if (hipMalloc((void**)&c->d_sitems, (size_t)nonempty * sizeof(swk::SearchItem)) != hipSuccess ||
-            hipHostMalloc((void**)&c->h_sitems, (size_t)nonempty * sizeof(swk::SearchItem), 0) != hipSuccess) {
-            set_err("sw_search_device: workspace allocation failed");
-            return SW_ENOMEM;
-        }
-        c->sitems_cap = (size_t)nonempty;
-    }
-    {
-        std::vector<int64_t> order_idx;
-        order_idx.reserve((size_t)nonempty);
-        for (int64_t k = 0; k < ntargets; ++k)
-            if (offsets[k + 1] > offsets[k]) order_idx.push_back(k);
-        std::stable_sort(order_idx.begin(), order_idx.end(),
-                         [&](int64_t x, int64_t y) { return offsets[x + 1] - offsets[x] > offsets[y + 1] - offsets[y]; });
-        for (int64_t i = 0; i < nonempty; ++i) {
-            const int64_t k = order_idx[(size_t)i];
-            c->h_sitems[i] = swk::SearchItem{offsets[k], k, offsets[k + 1] - offsets[k]};
-        }
-    }
+    bool fresh = false;
+    if (int rc = grow_schedule(c, (size_t)nonempty, stream)) return rc;
+    if (int rc = grow_workspace((void**)&c->d_sprof, c->sprof_cap, plan.prof_need, 1, 0, stream, fresh)) return rc;
+    if (int rc = grow_workspace((void**)&c->d_sbnd, c->sbnd_cap, plan.bnd_need, 4, 0, stream, fresh)) return rc;
+    if (!c->d_sctr) HIP_TRY(hipMalloc((void**)&c->d_sctr, 64));
+    swp::search_schedule(offsets, ntargets, c->h_sitems);
     HIP_TRY(hipMemcpyAsync(c->d_sitems, c->h_sitems, (size_t)nonempty * sizeof(swk::SearchItem), hipMemcpyHostToDevice, stream));
     HIP_TRY(hipEventRecord(c->sitems_ev, stream));
-    // the profile: SW_SEARCH_ROWS x qpad bytes
-    if (int rc = grow_workspace((void**)&c->d_sprof, c->sprof_cap, (size_t)(swk::SW_SEARCH_ROWS * qpad), 1, 0, stream, fresh)) return rc;
-    {
-        const int64_t n = swk::SW_SEARCH_ROWS * qpad;
-        hipLaunchKernelGGL(swk::sw_search_profile, dim3((unsigned)std::min<int64_t>((n + 255) / 256, 4096)), dim3(256), 0, stream,
-                           (const unsigned char*)d_query, qlen, qpad, c->d_sprof, sc->match, sc->mismatch, wide ? 1 : 0);
-        HIP_TRY(hipGetLastError());
-    }
-    if (!c->d_sctr) HIP_TRY(hipMalloc((void**)&c->d_sctr, 64));
+    hipLaunchKernelGGL(swk::sw_search_profile, dim3((unsigned)plan.prof_blocks), dim3(256), 0, stream, (const unsigned char*)d_query, qlen, plan.qpad,
+                       c->d_sprof, sc->match, sc->mismatch, plan.wide ? 1 : 0);
+    HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemsetAsync(c->d_sctr, 0, 4, stream));
-    // persistent waves: as many workgroups (4 waves) as are resident, fewer where the targets are fewer or the boundary columns of
-    // a multi-strip query (one per wave, sized by the longest target) would pass 1 GiB
-    auto kern = C == 4 ? (wide ? swk::sw_search_wave<4, true> : swk::sw_search_wave<4, false>)
-              : C == 8 ? (wide ? swk::sw_search_wave<8, true> : swk::sw_search_wave<8, false>)
-                       : (wide ? swk::sw_search_wave<16, true> : swk::sw_search_wave<16, false>);
-    int per_cu = 0;
-    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, 256, 0));
-    if (per_cu < 1) { set_err("the search kernel does not fit a CU on this device"); return SW_EDEVICE; }
-    int64_t grid = std::min<int64_t>((int64_t)per_cu * c->num_cus, (nonempty + 3) / 4);
-    const int64_t bnd_per = nstrips > 1 ? ((maxlen + 160 + 3) / 4) * 4 : 0;
-    if (bnd_per) {
-        grid = std::max<int64_t>(1, std::min<int64_t>(grid, (1ll << 30) / (bnd_per * 4 * 4)));
-        if (int rc = grow_workspace((void**)&c->d_sbnd, c->sbnd_cap, (size_t)(grid * 4 * bnd_per), 4, 0, stream, fresh)) return rc;
-    }
     swk::SearchParams sp;
     memset(&sp, 0, sizeof sp);
     sp.db = (const unsigned char*)d_db;
     sp.items = c->d_sitems; sp.nitems = nonempty;
-    sp.prof = c->d_sprof; sp.qpad = qpad; sp.qlen = qlen;
+    sp.prof = c->d_sprof; sp.qpad = plan.qpad; sp.qlen = qlen;
     sp.match = sc->match; sp.mismatch = sc->mismatch; sp.ngap = -sc->gap;
-    sp.bnd = bnd_per ? c->d_sbnd : nullptr; sp.bnd_per = bnd_per;
+    sp.bnd = plan.bnd_per ? c->d_sbnd : nullptr; sp.bnd_per = plan.bnd_per;
     sp.counter = c->d_sctr;
     sp.results = d_results;
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(256), 0, stream, sp);
+    hipLaunchKernelGGL(kSearch[plan.kernel].k, dim3((unsigned)plan.grid), dim3(256), 0, stream, sp);
     HIP_TRY(hipGetLastError());
-    c->last_search_grid = grid;
+    c->last_search_grid = plan.grid;
     return SW_OK;
 }
 

@@ -3,7 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/swhip.h"
-#include "sw_debug.h"
+#include "sw_plan.h"   // (SW_SEARCH_ROWS, SearchItem)
 
 namespace swk {
 
@@ -109,8 +109,6 @@ template <bool LE4, bool K12, bool PB1>
 __global__ void sw_batch_wave16(BatchParams p);   // two pairs per wave on packed 16-bit lanes (score + exact maxPos; PB1: int8 P too)
 
 // sw_search.hip: one query against many targets of any length (database search)
-constexpr int SW_SEARCH_ROWS = 257;      // profile rows: one per byte value + PAD (the letter of every row outside a target)
-struct SearchItem { int64_t start, idx, len; };   // a target in schedule order: first byte in db, index in the caller's order, length
 struct SearchParams {
     const unsigned char* db;             // the targets back to back
     const SearchItem* items; int64_t nitems;

@@ -1,10 +1,13 @@
-// sw_plan.cpp -- the fill planner (sw_plan.h).  No side effects, no allocation, no runtime calls.
+// sw_plan.cpp -- the fill, batch and search planners (sw_plan.h).  No side effects, no allocation, no runtime calls -- except search_schedule,
+// which writes the schedule to the caller's buffer and sorts through a vector of its own.
 #include "sw_plan.h"
 #include <algorithm>
+#include <vector>
 
 namespace swp {
 
-// ---- measured constants (MI355X, 256 CUs).  Changing one is a change of policy: tests/test_fill_plan.py has each threshold from both sides.
+// ---- measured constants (MI355X, 256 CUs).  Changing one is a change of policy: tests/test_fill_plan.py and tests/test_batch_plan.py have
+// each threshold from both sides.
 //
 // Workgroup shape of the one-column kernel.  One strip + 8 consumers per workgroup gives every producer a SIMD of its own (measured on
 // single pairs from 4096^2 to 32768^2: equal to 5 % faster than 2 + 2x4, equal at 65536^2) -- while the strips fit the CUs 4.5 times;
@@ -45,6 +48,36 @@ constexpr int64_t kXcdChainStrips = 384;
 // Split strips: a scout runs ~21.5 ns ahead of its consumers; fills of fewer rows are not split.
 constexpr double kScoutLeadSec = 21.5e-9;
 constexpr int64_t kSplitRows = 4096;
+
+// One pair per wave (sw_batch.hip, sw_search.hip).  Columns per lane: 4 up to 256 columns, 8 up to 512, 16 beyond; a strip is 64 C
+// columns, wider pairs (queries) go strip after strip through a boundary column of rows + 160 ints.
+constexpr int64_t kC4Cols = 256, kC8Cols = 512;
+constexpr int64_t kBndSlackRows = 160;
+// The batch kernel: a pair whose matrix does not fit a 2 GiB buffer descriptor ((rows + 132) x (cols + 1) ints) runs on the single-pair
+// machinery; so do scores beyond a signed byte and, found on the device, more than 8 distinct letters.
+constexpr int64_t kWaveSlackRows = 132;
+constexpr double kWaveMatrixBytes = 2147483648.0;
+constexpr int kWaveScore = 127;
+constexpr unsigned kWaveLetters = 8, kLE4Letters = 4;   // (up to four letters: half-size score profiles)
+// padded letter codes of every pair's b: 64 in front, 80 + 72 behind (+40: the drain steps of the delayed int8 P stores read on)
+constexpr int kCodesFront = 64;
+constexpr int64_t kCodesTail = 80 + 72;
+// pairs per launch: bounds the workspace (codes: ~1.2 KB per 1024-row pair), 1 GiB of codes and 1 GiB of boundary columns
+constexpr int64_t kBatchWorkspaceBytes = 1ll << 30;
+// alphabet of the whole batch: one sw_prep_scan block per 4096 letters, at most 2048 (sw_prep_reduce merges their maps); sw_batch_codes:
+// at most 64 blocks per pair
+constexpr int64_t kScanLetters = 4096, kScanBlocks = 2048, kCodesBlocks = 64;
+// Score-only batches whose scores fit 15 bits run two pairs per wave on packed 16-bit lanes (sw_batch_wave16: 5 VALU per two cells
+// instead of 8): match x min(cols, rows) and -gap below 32000, fewer than 65000 rows.  (debug bit 18: off, A/B runs)
+constexpr int64_t kWave16Score = 32000, kWave16Rows = 65000;
+// (scores of 12 bits: the arg-max runs on score * 16 + column keys)
+constexpr int64_t kKeyedScore = 4096;
+// the fall-back, pairs per launch: bounds the edge / padded-b workspace
+constexpr int64_t kSingleChunk = 4096;
+// Database search: persistent waves, as many workgroups (4 waves) as are resident, fewer where the targets are fewer or the boundary
+// columns of a multi-strip query (one per wave, sized by the longest target) would pass 1 GiB.  The profile: at most 4096 blocks.
+constexpr int64_t kSearchBndBytes = 1ll << 30;
+constexpr int64_t kProfileBlocks = 4096;
 
 namespace {
 
@@ -262,6 +295,74 @@ FillPlan plan_fill(const PlanJob& j, const DeviceFacts& dev, const PlanOptions& 
         t.consumers = o.consumers == 0 ? ((scouts || W2 == 110) ? 7 : (chain_bound ? 5 : 6)) : (int)std::min<int64_t>(7, o.consumers);
     }
     return f;
+}
+
+namespace {
+int lane_columns(int64_t cols) { return cols <= kC4Cols ? 4 : cols <= kC8Cols ? 8 : 16; }
+int64_t boundary_ints(int64_t nstrips, int64_t rows) { return nstrips > 1 ? ((rows + kBndSlackRows + 3) / 4) * 4 : 0; }
+}  // namespace
+
+BatchPlan plan_batch(const BatchJob& j, const PlanOptions& o) {
+    using namespace swk;
+    BatchPlan b;
+    const int64_t cols = j.cols, rows = j.rows;
+    b.wave = !(o.debug_flags & DBG_BATCH_SINGLE_PAIR) && j.match <= kWaveScore && j.match >= -kWaveScore && j.mismatch <= kWaveScore &&
+             j.mismatch >= -kWaveScore && (double)(rows + kWaveSlackRows) * (double)(cols + 1) * 4.0 < kWaveMatrixBytes;
+    b.single_chunk = std::min(j.npairs, kSingleChunk);
+    b.C = lane_columns(cols);
+    b.nstrips = (cols + 64 * b.C - 1) / (64 * b.C);
+    b.front = kCodesFront;
+    b.per = ((rows + kCodesFront + kCodesTail + 15) / 16) * 16;
+    b.bnd_per = boundary_ints(b.nstrips, rows);
+    b.chunk = std::max<int64_t>(1, std::min<int64_t>(j.npairs, std::min<int64_t>(kBatchWorkspaceBytes / b.per,
+                                                                                  b.bnd_per ? kBatchWorkspaceBytes / (b.bnd_per * 4) : j.npairs)));
+    b.grid = (b.chunk + 3) / 4;   // (4 pairs, one per wave, per workgroup)
+    b.scan_blocks = (int)std::max<int64_t>(1, std::min<int64_t>(((cols + rows) * j.npairs + kScanLetters - 1) / kScanLetters, kScanBlocks));
+    b.codes_blocks = (int)std::min<int64_t>((b.per + 255) / 256, kCodesBlocks);
+    b.bcodes_need = (size_t)(b.chunk * b.per);
+    b.bnd_need = (size_t)(b.chunk * b.bnd_per);
+    const int64_t smax = (int64_t)j.match * std::min(cols, rows);
+    b.fits16 = j.npairs >= 2 && b.C == 16 && smax < kWave16Score && -j.gap < kWave16Score && rows < kWave16Rows && !(o.debug_flags & DBG_BATCH_NO_WAVE16);
+    b.k12 = smax < kKeyedScore;
+    // ... and with an int8 P as the only matrix, P codes from packed arithmetic (debug bit 21: off)
+    b.packed16 = b.fits16 && !j.has_H && (!j.has_P || (j.p_elem_bytes == 1 && !(o.debug_flags & DBG_BATCH_NO_PACKED_P)));
+    return b;
+}
+
+int batch_kernel(const BatchPlan& b, unsigned nletters, int64_t n, int p_bytes) {
+    if (nletters > kWaveLetters) return -1;
+    if (b.packed16 && n >= 2)   // (an odd last pair runs in both halves of a wave)
+        return batch_wave16_index(nletters <= kLE4Letters, b.k12, p_bytes != 0);
+    return batch_wave_index(b.C, p_bytes);
+}
+
+SearchPlan plan_search(const SearchJob& j, const DeviceFacts& dev) {
+    using swk::SW_SEARCH_ROWS;
+    SearchPlan s;
+    s.C = lane_columns(j.qlen);
+    s.wide = j.match > kWaveScore || j.mismatch < -kWaveScore;   // (mismatch <= match: both fit a signed byte otherwise)
+    s.kernel = search_kernel_index(s.C, s.wide);
+    s.nstrips = (j.qlen + 64 * s.C - 1) / (64 * s.C);
+    s.qpad = s.nstrips * 64 * s.C;
+    s.bnd_per = boundary_ints(s.nstrips, j.maxlen);
+    s.grid = std::min<int64_t>((int64_t)dev.search_per_cu[s.kernel] * dev.num_cus, (j.ntargets + 3) / 4);
+    if (s.bnd_per) s.grid = std::max<int64_t>(1, std::min<int64_t>(s.grid, kSearchBndBytes / (s.bnd_per * 4 * 4)));
+    s.prof_need = (size_t)(SW_SEARCH_ROWS * s.qpad);
+    s.prof_blocks = (int)std::min<int64_t>((SW_SEARCH_ROWS * s.qpad + 255) / 256, kProfileBlocks);
+    s.bnd_need = s.bnd_per ? (size_t)(s.grid * 4 * s.bnd_per) : 0;
+    return s;
+}
+
+void search_schedule(const int64_t* offsets, int64_t ntargets, swk::SearchItem* items) {
+    std::vector<int64_t> order;
+    order.reserve((size_t)ntargets);
+    for (int64_t k = 0; k < ntargets; ++k)
+        if (offsets[k + 1] > offsets[k]) order.push_back(k);
+    std::stable_sort(order.begin(), order.end(), [&](int64_t x, int64_t y) { return offsets[x + 1] - offsets[x] > offsets[y + 1] - offsets[y]; });
+    for (size_t i = 0; i < order.size(); ++i) {
+        const int64_t k = order[i];
+        items[i] = swk::SearchItem{offsets[k], k, offsets[k + 1] - offsets[k]};
+    }
 }
 
 }  // namespace swp

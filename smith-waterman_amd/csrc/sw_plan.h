@@ -1,11 +1,19 @@
-// sw_plan.h -- the fill planner: every policy decision of one fill (kernel, workgroup shape, perm producer, strip geometry, column
-// tiles, scouts, roles per XCD, split strips, filler pacing, store kind) and the workspace sizes it needs, as a pure function of the
-// job, the device and the options.  Plain C++ (no HIP include): sw_api.hip carries a plan out, tests/test_fill_plan.py checks the
-// policy on a CPU.
+// sw_plan.h -- the planners: every policy decision of one fill (kernel, workgroup shape, perm producer, strip geometry, column
+// tiles, scouts, roles per XCD, split strips, filler pacing, store kind), of one batch call (one pair or two pairs per wave, columns
+// per lane, pairs per launch, the kernel of every launch) and of one database search (columns per lane, profile kind, grid, schedule),
+// and the workspace sizes they need, as pure functions of the job, the device and the options.  Plain C++ (no HIP include):
+// sw_api.hip carries a plan out, tests/test_fill_plan.py and tests/test_batch_plan.py check the policy on a CPU.
 #pragma once
 #include <cstddef>
 #include <cstdint>
 #include "sw_debug.h"
+
+namespace swk {   // shared with the search kernels (sw_kernels.h)
+
+constexpr int SW_SEARCH_ROWS = 257;      // profile rows: one per byte value + PAD (the letter of every row outside a target)
+struct SearchItem { int64_t start, idx, len; };   // a target in schedule order: first byte in db, index in the caller's order, length
+
+}  // namespace swk
 
 namespace swp {
 
@@ -25,10 +33,15 @@ struct PlanJob {
     float pair_ratio = 0.f;                  // store probe's two-stream / one-stream time of the H / P pair (~1.4: two classes of the HBM, ~2: one); 0: unknown
 };
 
+// sw_search_wave<C, WIDE> for C = 4, 8, 16: its index in kSearch (sw_api.hip, which checks its order against it at compile time)
+constexpr int kSearchKernels = 6;
+constexpr int search_kernel_index(int C, bool wide) { return 2 * (C / 8) + wide; }
+
 struct DeviceFacts {
     int num_cus = 256;
     bool xcd_round_robin = false;            // workgroup i of a launch runs on XCD i % 8 (8 XCDs of 32 CUs)
     int s2_per_cu = 0;                       // occupancy of sw_systolic2 at 768 threads (workgroups per CU)
+    int search_per_cu[kSearchKernels] = {};  // occupancy of every sw_search_wave instantiation at 256 threads
 };
 
 struct PlanOptions {   // the sw_set_option values the policy reads (include/swhip.h)
@@ -76,5 +89,63 @@ struct FillPlan {
 };
 
 FillPlan plan_fill(const PlanJob& job, const DeviceFacts& dev, const PlanOptions& opt);
+
+// ---- batches of independent pairs (sw_batch_device_ex): one pair per wave (sw_batch_wave), two on packed 16-bit lanes (sw_batch_wave16),
+// or the single-pair machinery in chunks (the fall-back)
+struct BatchJob {
+    int64_t cols = 0, rows = 0, npairs = 1;
+    bool has_H = true, has_P = true;
+    int p_elem_bytes = 4;                    // 4 / 1
+    int match = 3, mismatch = -3, gap = -2;
+};
+
+struct BatchPlan {
+    bool wave = false;                       // one pair per wave may run (scores, pair size, debug bit 16); the letter count decides on the device
+    int C = 0;                               // columns per lane
+    int64_t nstrips = 0;                     // strips of 64 C columns one wave sweeps after each other
+    int front = 0;                           // padded letter codes of b: index of b[0] ...
+    int64_t per = 0;                         // ... and bytes per pair
+    int64_t bnd_per = 0;                     // boundary column between strips, ints per pair (0: one strip)
+    int64_t chunk = 0;                       // pairs per launch
+    int64_t grid = 0;                        // workgroups of a chunk at one pair per wave (sw_get_option "last_grid")
+    int scan_blocks = 0, codes_blocks = 0;   // sw_prep_scan blocks; sw_batch_codes blocks per pair
+    bool fits16 = false, k12 = false, packed16 = false;   // two pairs per wave: scores of 15 bits; keyed arg-max: 12 bits; taken
+    size_t bcodes_need = 0, bnd_need = 0;    // workspaces: padded letter codes (bytes), boundary columns (ints)
+    int64_t single_chunk = 0;                // the fall-back: pairs per launch (= arg-max keys of the workspace)
+};
+
+BatchPlan plan_batch(const BatchJob& job, const PlanOptions& opt);
+
+// The batch kernels: their indices in kBatch (sw_api.hip, which checks its order against them at compile time).  sw_batch_wave<C, PB> for
+// C = 4, 8, 16 and PB = 0, 1, 4 first, then sw_batch_wave16<LE4, K12, PB1> (two pairs per wave) from kBatchWave16 on.
+constexpr int kBatchWave16 = 9, kBatchKernels = 17;
+constexpr int batch_wave_index(int C, int pb) { return 3 * (C / 8) + (pb == 4 ? 2 : pb); }
+constexpr int batch_wave16_index(bool le4, bool k12, bool pb1) { return kBatchWave16 + 4 * le4 + 2 * k12 + pb1; }
+// The kernel of a chunk of n pairs, given the letter count of the batch and the bytes of a P element (0: no P); -1: the batch has to
+// run on the fall-back.
+int batch_kernel(const BatchPlan& plan, unsigned nletters, int64_t n, int p_bytes);
+
+// ---- database search (sw_search_device): one query against many targets of any length
+struct SearchJob {
+    int64_t qlen = 0, maxlen = 0;            // query length, longest target
+    int64_t ntargets = 0;                    // non-empty targets
+    int match = 3, mismatch = -3, gap = -2;
+};
+
+struct SearchPlan {
+    int C = 0;                               // query columns per lane
+    bool wide = false;                       // scores beyond a signed byte: the selector profile
+    int kernel = 0;                          // index of sw_search_wave<C, wide> (kSearchKernels)
+    int64_t nstrips = 0, qpad = 0;           // strips of 64 C columns; profile row length
+    int64_t bnd_per = 0;                     // per resident wave: boundary column between strips (ints), 0: one strip
+    int64_t grid = 0;                        // persistent workgroups of 4 waves
+    int prof_blocks = 0;                     // sw_search_profile blocks
+    size_t prof_need = 0, bnd_need = 0;      // workspaces: profile (bytes), boundary columns (ints)
+};
+
+SearchPlan plan_search(const SearchJob& job, const DeviceFacts& dev);
+
+// The schedule: the non-empty targets of offsets[0 .. ntargets], by decreasing length, ties in input order, written to items.
+void search_schedule(const int64_t* offsets, int64_t ntargets, swk::SearchItem* items);
 
 }  // namespace swp
