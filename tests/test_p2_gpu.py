@@ -4,20 +4,9 @@ import numpy as np
 import pytest
 
 from oracle_lib import golden
+from traceback_cases import np_pack
 
 pytestmark = pytest.mark.gpu
-
-
-def np_pack(P):
-    """The format by definition: cell k in bits 2 (k & 3) of byte k >> 2; path bitmap bit k & 31 of word k >> 5."""
-    flat = P.reshape(-1).astype(np.int64)
-    n = flat.size
-    pad = (-n) % 32
-    codes = np.concatenate([np.abs(flat), np.zeros(pad, np.int64)]).astype(np.uint8).reshape(-1, 4)
-    p2 = (codes[:, 0] | (codes[:, 1] << 2) | (codes[:, 2] << 4) | (codes[:, 3] << 6)).astype(np.uint8)
-    neg = np.concatenate([flat < 0, np.zeros(pad, bool)]).reshape(-1, 32)
-    bits = (neg.astype(np.uint64) << np.arange(32, dtype=np.uint64)).sum(axis=1).astype(np.uint32)
-    return p2, bits
 
 
 @pytest.mark.parametrize("name", ["kat_builtin", "rand_1x1_s1", "rand_8x9_s1", "rand_256x256_s1", "rand_300x200_s1", "rand_65x130_s7", "rand_1x77_s3",
