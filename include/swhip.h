@@ -347,9 +347,11 @@ int sw_synchronize(sw_ctx* ctx, void* stream);   /* waits for `stream`; reports 
  *   "max_blocks"        cap of the resident grid (0 = all CUs); concurrent band launches partition the CUs with it
  *   "waves_per_block", "debug_flags", "debug_buf", "batch_lds"   development aids (debug_flags: the bits of swk::DebugFlag in
  *                       smith-waterman_amd/csrc/sw_debug.h)
- * sw_get_option also answers "last_grid", "last_strips", "last_strips2" (strips of the two-column kernel), "last_scouts"
+ * sw_get_option also answers "last_grid", "last_strips", "last_strips2" (strips of the two-column kernel), "last_perm" (1: the last fill's
+ * scores and size allowed the perm producer; the letter count, found on the device, still has to), "last_scouts"
  * (scout workgroups of the last fill), "last_xcd_mode" (1: that fill dealt its roles per XCD), "xcd_round_robin" (1: sw_create saw
- * workgroup i of a launch on XCD i % 8) and "last_batch_kernel" (1: the last batch ran one pair per wave). */
+ * workgroup i of a launch on XCD i % 8), "last_batch_kernel" (0: the last batch ran on the fall-back, 1: one pair per wave, 2: two pairs per
+ * wave on packed lanes) and "last_search_kernel" (the last search: 2 * (columns per lane / 8) + 1 for the wide profile). */
 int sw_set_option(sw_ctx* ctx, const char* name, int64_t value);
 int64_t sw_get_option(sw_ctx* ctx, const char* name);
 

@@ -85,6 +85,7 @@ struct sw_ctx {
     hipEvent_t sitems_ev = nullptr;
     unsigned int* d_sctr = nullptr;
     int64_t last_search_grid = 0;       // workgroups of the last search launch
+    int64_t last_search_kernel = 0;     // its kernel: index in kSearch (swp::search_kernel_index)
     int search_per_cu[swp::kSearchKernels] = {};   // occupancy of every sw_search_wave instantiation at 256 threads ...
     bool search_per_cu_known = false;              // ... queried at the first search
     bool xcd_round_robin = false;       // sw_xcc_probe saw workgroup i on XCD i % 8 (8 XCDs of 32 CUs)
@@ -216,6 +217,7 @@ int64_t sw_get_option(sw_ctx* c, const char* name) {
     const swp::TilePlan& last_tile = c->last_plan.tile[c->last_plan.ntile - 1];   // (all zero where the two-column kernel did not run)
     if (!strcmp(name, "last_strips")) return c->last_plan.S;
     if (!strcmp(name, "last_strips2")) return last_tile.strips;
+    if (!strcmp(name, "last_perm")) return c->last_plan.perm ? 1 : 0;
     if (!strcmp(name, "last_scouts")) return last_tile.nscout;
     if (!strcmp(name, "last_xcd_mode")) return last_tile.xcd_mode;
     if (!strcmp(name, "last_tiles")) return c->last_plan.ntile;
@@ -223,6 +225,7 @@ int64_t sw_get_option(sw_ctx* c, const char* name) {
     if (!strcmp(name, "xcd_round_robin")) return c->xcd_round_robin ? 1 : 0;
     if (!strcmp(name, "last_batch_kernel")) return c->last_batch_kernel;
     if (!strcmp(name, "last_search_grid")) return c->last_search_grid;
+    if (!strcmp(name, "last_search_kernel")) return c->last_search_kernel;
     if (!strcmp(name, "placement_budget_ms")) return c->opt_place_budget_ms;
     if (!strcmp(name, "placement_hold_gib")) return c->opt_place_hold_gib;
     if (!strcmp(name, "probe_foreign_pairs")) return c->opt.probe_foreign_pairs;
@@ -825,7 +828,7 @@ int sw_search_device(sw_ctx* c, const char* d_query, int64_t qlen, const char* d
     sp.results = d_results;
     hipLaunchKernelGGL(kSearch[plan.kernel].k, dim3((unsigned)plan.grid), dim3(256), 0, stream, sp);
     HIP_TRY(hipGetLastError());
-    c->last_search_grid = plan.grid;
+    c->last_search_grid = plan.grid; c->last_search_kernel = plan.kernel;
     return SW_OK;
 }
 

@@ -7,10 +7,11 @@ import pytest
 pytestmark = pytest.mark.gpu
 
 
-def _bands(engine, oracle, swamd, cols, rows, cuts, reverse=False, p8=False, want_h=True, max_blocks=0):
+def _bands(engine, oracle, swamd, cols, rows, cuts, reverse=False, p8=False, want_h=True, max_blocks=0, scores=(3, -3, -2), ab=None):
+    """scores / ab: another scoring and the pair itself (the band case of tests/score_range_cases.py); the default is the reference's scoring on a random pair"""
     import torch
-    a, b = oracle.generate(cols, rows, 41)
-    H, P, mp = oracle.fill(a, b)
+    a, b = ab if ab is not None else oracle.generate(cols, rows, 41)
+    H, P, mp = oracle.fill(a, b, scores)
     bounds = [0] + list(cuts) + [rows]
     nb = len(bounds) - 1
     S = (cols + 62) // 63
@@ -31,7 +32,7 @@ def _bands(engine, oracle, swamd, cols, rows, cuts, reverse=False, p8=False, wan
     if reverse:   # size the per-context workspaces up front (allocation inside a launch call would wait for the device)
         for g in range(nb):
             Hb, Pb, res, lo, hi, d_b = bands[g]
-            engs[g].fill_band(d_a, cols, d_b, hi - lo, rows, None, None, res)
+            engs[g].fill_band(d_a, cols, d_b, hi - lo, rows, None, None, res, scores=scores)
     torch.cuda.synchronize()
     for e in set(engs):
         e.set_option("max_blocks", max_blocks)
@@ -42,7 +43,7 @@ def _bands(engine, oracle, swamd, cols, rows, cuts, reverse=False, p8=False, wan
             with torch.cuda.stream(streams[g]):
                 engs[g].fill_band(d_a, cols, d_b, hi - lo, rows, Hb, Pb, res,
                                   top_gran=gran[g - 1] if g > 0 else None, top_tag=7 + g - 1 if g > 0 else 0,
-                                  bot_gran=gran[g], bot_tag=7 + g, bot_done=done[g], concurrent=reverse)
+                                  bot_gran=gran[g], bot_tag=7 + g, bot_done=done[g], concurrent=reverse, scores=scores)
         torch.cuda.synchronize()
     finally:
         for e in set(engs):
