@@ -349,7 +349,8 @@ int sw_synchronize(sw_ctx* ctx, void* stream);   /* waits for `stream`; reports 
  *                       smith-waterman_amd/csrc/sw_debug.h)
  * sw_get_option also answers "last_grid", "last_strips", "last_strips2" (strips of the two-column kernel), "last_perm" (1: the last fill's
  * scores and size allowed the perm producer; the letter count, found on the device, still has to), "last_scouts"
- * (scout workgroups of the last fill), "last_xcd_mode" (1: that fill dealt its roles per XCD), "xcd_round_robin" (1: sw_create saw
+ * (scout workgroups of the last fill), "last_xcd_mode" (1: that fill dealt its roles per XCD), "last_scan_all" (1: every workgroup of that fill
+ * scanned the alphabet for itself, 0: the shared scan behind a grid barrier), "xcd_round_robin" (1: sw_create saw
  * workgroup i of a launch on XCD i % 8), "last_batch_kernel" (0: the last batch ran on the fall-back, 1: one pair per wave, 2: two pairs per
  * wave on packed lanes) and "last_search_kernel" (the last search: 2 * (columns per lane / 8) + 1 for the wide profile). */
 int sw_set_option(sw_ctx* ctx, const char* name, int64_t value);

@@ -69,6 +69,7 @@ struct sw_ctx {
     swp::FillPlan last_plan;            // the plan of the last fill (sw_get_option "last_*")
     int64_t last_grid = 0;              // ... and the grid of its one-column kernel after the occupancy cap
     int s2_per_cu = 0;                  // occupancy of sw_systolic2 at 768 threads (queried at the first fill)
+    struct { int threads, per_cu; } sys_occ[8][2] = {};   // occupancy of every sw_systolic instantiation (kSystolic x int32 / int64 H) at the workgroup size last asked about
     int64_t opt_xcd_order = 0;          // systolic: 1 = neighbouring strip groups on one XCD
     int64_t opt_pace_ps = 0;            // systolic: pacing of strip 0 (ps per row; 0 = off)
     int64_t opt_dbg_ptr = 0;
@@ -222,6 +223,7 @@ int64_t sw_get_option(sw_ctx* c, const char* name) {
     if (!strcmp(name, "last_xcd_mode")) return last_tile.xcd_mode;
     if (!strcmp(name, "last_tiles")) return c->last_plan.ntile;
     if (!strcmp(name, "last_split_from")) return last_tile.split_blk ? last_tile.split_from : 0;
+    if (!strcmp(name, "last_scan_all")) return last_tile.scan_all;
     if (!strcmp(name, "xcd_round_robin")) return c->xcd_round_robin ? 1 : 0;
     if (!strcmp(name, "last_batch_kernel")) return c->last_batch_kernel;
     if (!strcmp(name, "last_search_grid")) return c->last_search_grid;
@@ -478,6 +480,7 @@ static int launch_fill(sw_ctx* c, const sw_scores* sc, const FillJob& j, hipStre
             p2.sync = c->d_sync; p2.priv = c->d_priv; p2.priv_stride = plan.priv_stride;
             p2.bpad16_w = d_cb16; p2.bpad8_w = c->d_cb; p2.bcode_w = d_cbc; p2.atab_w = c->d_alpha + 64;
             p2.result = j.d_result; p2.skip_row0 = (j.d_top || j.d_top_gran) ? 1 : 0;
+            p2.scan_all = t.scan_all;
             hipLaunchKernelGGL(kSystolic2[t.consumers - 4][plan.W2 == 110], dim3(t.grid), dim3(768), 0, stream, ua + t.c0, ub, p2);
         }
         // the fall-back (an alphabet of more than 7 letters, known on the device only): enqueued behind, leaves at once otherwise;
@@ -497,8 +500,14 @@ static int launch_fill(sw_ctx* c, const sw_scores* sc, const FillJob& j, hipStre
         c->key_dirty = true;
     }
     const SystolicKernel kern = j.h_elem_bytes == 4 ? one_col->h32 : one_col->h64;
-    int per_cu = 0;
-    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, plan.threads, 0));
+    // (asked once per context, kernel and workgroup size, not on every fill)
+    static_assert(sizeof(kSystolic) / sizeof(kSystolic[0]) == 8, "sw_ctx::sys_occ has one row per instantiation");
+    auto& occ = c->sys_occ[one_col - std::begin(kSystolic)][j.h_elem_bytes == 4 ? 0 : 1];
+    if (occ.threads != plan.threads) {
+        HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ.per_cu, kern, plan.threads, 0));
+        occ.threads = plan.threads;
+    }
+    const int per_cu = occ.per_cu;
     if (per_cu < 1) { set_err("the fill kernel does not fit a CU on this device"); return SW_EDEVICE; }
     c->last_grid = std::min<int64_t>(plan.grid, (int64_t)per_cu * c->num_cus);
     hipLaunchKernelGGL(kern, dim3((unsigned)c->last_grid), dim3(plan.threads), 0, stream, ua, ub, (const unsigned char*)c->d_cb, p);

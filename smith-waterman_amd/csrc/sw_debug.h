@@ -34,6 +34,8 @@ enum DebugFlag : int {
     DBG_NO_XCD_DEALING = 1 << 23,      // two-column kernel: roles not dealt per XCD (neither behind scouts nor in the chain)
     DBG_S2_IMPORTERS = 3 << 24,        // bits 24-25, a count: two-column kernel, that many importer waves on SIMD 2 only
     DBG_NO_PACING = 1 << 27,           // two-column kernel: fillers behind scouts unpaced (and so no split strips)
+    DBG_S2_BARRIER_SCAN = 1 << 28,     // two-column kernel: the prologue's alphabet scan is shared and ends in a grid barrier, whatever the size
+    DBG_S2_SCAN_ALL = 1 << 29,         // two-column kernel: every workgroup scans all letters itself (no grid barrier), whatever the size
 };
 constexpr int DBG_S2_IMPORTERS_SHIFT = 24;
 constexpr int DBG_BATCH_MASK = DBG_NO_STORES | DBG_PRODUCER_ONLY | DBG_GENERIC_PRODUCER;   // handed on to BatchParams::debug (its kernels read bit 0)

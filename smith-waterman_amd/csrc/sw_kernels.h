@@ -84,6 +84,7 @@ struct FillParams {
     // matrix; s2w = 110: neighbouring strips OVERLAP by 16 columns, so that every 64-byte line of a matrix row lies wholly inside some
     // strip and can be stored by ONE instruction of that strip (whole-line stores: sw_systolic2.inc).  0 is taken as 126.
     int s2w;
+    int scan_all;                        // sw_systolic2 prologue: 1 = every workgroup scans all letters itself, no grid barrier (the planner decides)
 };
 constexpr int SW_XTAB_OFF = 448;         // atab + 448: unsigned int[256], XCD + 1 of every workgroup of the running sw_systolic2 launch (0: not there yet)
 constexpr int SW_PERM_PAD = -100;        // score of any cell outside the sequences (perm producer)

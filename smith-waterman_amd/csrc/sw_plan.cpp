@@ -293,6 +293,15 @@ FillPlan plan_fill(const PlanJob& j, const DeviceFacts& dev, const PlanOptions& 
         // seven consumers keep more stores in flight (16384^2 -1.5 %, 12288^2 -2.5 %, 20480^2 +-0 against five)
         // (overlapping strips, whose consumers are dearer: seven as well -- 32768^2 485 against 453-466 GCUPS, 65536^2 633 / 607, int64 H 502 / 495)
         t.consumers = o.consumers == 0 ? ((scouts || W2 == 110) ? 7 : (chain_bound ? 5 : 6)) : (int)std::min<int64_t>(7, o.consumers);
+        // The alphabet scan of the prologue (sw_systolic2.inc).  Shared among the workgroups it costs eight agent-scope atomics and a
+        // grid barrier over up to 256 workgroups before anybody's first step, whatever the size; done by every workgroup for itself it
+        // costs cols + rows bytes read from the L2 with 16-byte loads, 12 KB per pass of a workgroup.  Decided by the WHOLE matrix'
+        // columns and the launch's rows, so that every column tile decides alike.  (debug bits 28 / 29 force either)
+        // Measured (us until every workgroup knows the alphabet, shared | private): 32 K letters 12.4 | 10.5, 48 K 12.2 | 12.0, 64 K 12.5 | 15.3,
+        // 128 K 12.8 | 23.0 -- the crossover is at ~50 K letters (profiles/r05_prologue_stamps.log).
+        t.scan_all = (cols + rows <= kScanAllLetters) ? 1 : 0;
+        if (o.debug_flags & DBG_S2_BARRIER_SCAN) t.scan_all = 0;
+        if (o.debug_flags & DBG_S2_SCAN_ALL) t.scan_all = 1;
     }
     return f;
 }

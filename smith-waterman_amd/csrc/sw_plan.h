@@ -59,6 +59,7 @@ struct TilePlan {
     int filler_hop_ps = 0, filler_tau_ps = 0, filler_bw_gbs = 0;
     int store_nt = 0;
     int consumers = 0;                       // consumer waves: the kernel's instantiation
+    int scan_all = 0;                        // prologue: every workgroup scans all letters itself (no grid barrier); the same in every tile
 };
 
 // tiles of at most 160 strips of at least 110 columns: cols <= SW_MAX_DIM gives at most 60
@@ -89,6 +90,11 @@ struct FillPlan {
 };
 
 FillPlan plan_fill(const PlanJob& job, const DeviceFacts& dev, const PlanOptions& opt);
+
+// The prologue of the two-column kernel finds the alphabet either by a scan shared among the workgroups and one grid barrier, or by
+// every workgroup scanning all cols + rows letters for itself (no atomics in memory, no barrier).  The second is cheaper while the
+// letters are few: up to this many (sw_plan.cpp says where the figure comes from).
+constexpr int64_t kScanAllLetters = 48 * 1024;
 
 // ---- batches of independent pairs (sw_batch_device_ex): one pair per wave (sw_batch_wave), two on packed 16-bit lanes (sw_batch_wave16),
 // or the single-pair machinery in chunks (the fall-back)

@@ -541,6 +541,7 @@ __device__ __forceinline__ int s2_produce(S2Side& sd, Sys2Lds* full, const FillP
     if (dbg && lane == 0) {
         dbg[2 * s] = __builtin_amdgcn_s_memrealtime();
         if (s == 0 && dbg == p.dbg) p.dbg[6 * p.nstrips + 16] = __builtin_amdgcn_s_memtime();
+        if (s == 0 && dbg == p.dbg) p.dbg[8 * p.nstrips + 32 + 3] = dbg[0];   // (S2_STAMP_FIRST_STEP, declared with the prologue below)
     }
     int st;
     if constexpr (SCOUT) {
@@ -639,32 +640,91 @@ struct S2Prep {
 };
 constexpr int S2_SYNC_BAR = 0, S2_SYNC_OUT = 1, S2_SYNC_MAP = 8;
 
+// debug stamps of the launch's own overhead (debug_buf), 100 MHz ticks, in slots of their own behind everything the strips stamp:
+// dbg[8 n + 32 + k] for n = p.nstrips --  0: workgroup 0 enters;  1: the last workgroup knows the alphabet (past the grid barrier, or done
+// with its own scan);  2: the last workgroup leaves the prologue;  6: the last workgroup enters;  3: strip 0's producer takes its first step;  4: the last wave has its
+// stores acknowledged;  5: the last workgroup out has re-armed the launch words.  (1, 2, 4, 6: maxima over the launch -- the buffer starts zeroed)
+enum { S2_STAMP_ENTRY = 0, S2_STAMP_ALPHABET = 1, S2_STAMP_PROLOGUE = 2, S2_STAMP_FIRST_STEP = 3, S2_STAMP_STORES = 4, S2_STAMP_OUT = 5, S2_STAMP_LAST_ENTRY = 6 };
+__device__ __forceinline__ void s2_stamp(const FillParams& p, int k, bool is_max) {
+    u64* const slot = p.dbg + 8 * p.nstrips + 32 + k;
+    const u64 now = __builtin_amdgcn_s_memrealtime();
+    if (is_max) (void)__hip_atomic_fetch_max(slot, now, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    else *slot = now;
+}
+
+// The letters of seq[0 .. n) into the workgroup's presence map, 16 bytes per thread and load, four loads in flight (the loads are
+// aligned: what they read beyond either end of the sequence lies in the same 16 bytes as a byte of it, and is masked out).  A thread
+// keeps the map word it looked at last in a register, with the bits it has seen there: a letter costs an LDS access only when its word
+// changes or its bit is new -- with the few letters of a real sequence, once per thread.  (Bound by VALU issue, ~15 instructions per
+// byte: 32 K letters take ~9 us, as they did with a lookup in LDS for every byte; DESIGN.md section 6.)
+__device__ __forceinline__ void s2_scan_all(S2Prep& pp, const unsigned char* __restrict__ seq, int64_t n, int tid, int nth) {
+    if (n <= 0) return;
+    const uintptr_t a0 = (uintptr_t)seq & ~(uintptr_t)15;
+    const int64_t skew = (int64_t)((uintptr_t)seq - a0), nchunk = (skew + n + 15) >> 4;
+    u32 cw = 8u, cm = 0u;   // (no word yet)
+    for (int64_t c0 = tid; c0 < nchunk; c0 += 4 * (int64_t)nth) {
+        uint4 v[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int64_t c = c0 + (int64_t)u * nth;
+            v[u] = c < nchunk ? *(const uint4*)(a0 + 16 * (uintptr_t)c) : make_uint4(0u, 0u, 0u, 0u);
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int64_t c = c0 + (int64_t)u * nth;
+            if (c >= nchunk) break;
+            const u32 w[4] = {v[u].x, v[u].y, v[u].z, v[u].w};
+            const int64_t first = skew - 16 * c, end = skew + n - 16 * c;   // bytes [first, end) of the chunk belong to the sequence
+            const bool whole = first <= 0 && end >= 16;
+#pragma unroll
+            for (int q = 0; q < 16; ++q) {
+                if (!whole && (q < first || q >= end)) continue;
+                const u32 ch = (w[q >> 2] >> (8 * (q & 3))) & 255u;
+                const u32 bit = 1u << (ch & 31u);
+                if ((ch >> 5) != cw) { cw = ch >> 5; cm = __hip_atomic_load(&pp.pres[cw], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
+                if (!(cm & bit)) { atomicOr(&pp.pres[cw], bit); cm |= bit; }
+            }
+        }
+    }
+}
+
 __device__ __forceinline__ int s2_prologue(S2Prep& pp, const FillParams& p, const unsigned char* __restrict__ seq_a, const unsigned char* __restrict__ seq_b) {
     const int tid = (int)threadIdx.x, nth = (int)blockDim.x, G = (int)gridDim.x, wg = (int)blockIdx.x;
     gu32* const sync = (gu32*)p.sync;
+    if (p.dbg && wg == 0 && tid == 0) s2_stamp(p, S2_STAMP_ENTRY, false);
+    if (p.dbg && tid == 0) s2_stamp(p, S2_STAMP_LAST_ENTRY, true);
     if (tid < 8) pp.pres[tid] = 0u;
+    if (tid == 0) pp.ok = 1;
     __syncthreads();
-    {   // (1) my 1/G of the letters
-        const int64_t acols = p.alpha_cols, total = acols + p.rows, chunk = (total + G - 1) / G;   // (a column tile scans the whole a: every tile must decide alike)
-        const int64_t lo = (int64_t)wg * chunk, hi = min(total, lo + chunk);
-        for (int64_t i = lo + tid; i < hi; i += nth) {
-            const unsigned char ch = i < acols ? p.alpha_a[i] : seq_b[i - acols];
-            atomicOr(&pp.pres[ch >> 5], 1u << (ch & 31));
+    if (p.scan_all) {
+        // (1+2) every workgroup scans all the letters for itself: nothing shared, nobody to wait for.  (a column tile scans the whole a:
+        // every tile must decide alike -- and so must every workgroup: all of them read the same bytes)
+        s2_scan_all(pp, p.alpha_a, p.alpha_cols, tid, nth);
+        s2_scan_all(pp, seq_b, p.rows, tid, nth);
+    } else {
+        {   // (1) my 1/G of the letters
+            const int64_t acols = p.alpha_cols, total = acols + p.rows, chunk = (total + G - 1) / G;   // (a column tile scans the whole a: every tile must decide alike)
+            const int64_t lo = (int64_t)wg * chunk, hi = min(total, lo + chunk);
+            for (int64_t i = lo + tid; i < hi; i += nth) {
+                const unsigned char ch = i < acols ? p.alpha_a[i] : seq_b[i - acols];
+                atomicOr(&pp.pres[ch >> 5], 1u << (ch & 31));
+            }
+        }
+        __syncthreads();
+        if (tid < 64) {   // (2) wave 0: publish, arrive, wait for everybody, fetch the launch's map
+            if (tid < 8 && pp.pres[tid]) (void)__hip_atomic_fetch_or(sync + S2_SYNC_MAP + tid, pp.pres[tid], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");   // (the wave's atomics are performed before its arrival counts)
+            if (tid == 0) (void)__hip_atomic_fetch_add(sync + S2_SYNC_BAR, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            Spin spin; spin.code = 17;
+            bool ok = true;
+            while ((u32)__builtin_amdgcn_readfirstlane((int)__hip_atomic_load(sync + S2_SYNC_BAR, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) < (u32)G)
+                if (spin.fail(p.abort_flag)) { ok = false; break; }
+            if (tid < 8) pp.pres[tid] = __hip_atomic_load(sync + S2_SYNC_MAP + tid, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (tid == 0) pp.ok = ok ? 1 : 0;
         }
     }
     __syncthreads();
-    if (tid < 64) {   // (2) wave 0: publish, arrive, wait for everybody, fetch the launch's map
-        if (tid < 8 && pp.pres[tid]) (void)__hip_atomic_fetch_or(sync + S2_SYNC_MAP + tid, pp.pres[tid], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");   // (the wave's atomics are performed before its arrival counts)
-        if (tid == 0) (void)__hip_atomic_fetch_add(sync + S2_SYNC_BAR, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        Spin spin; spin.code = 17;
-        bool ok = true;
-        while ((u32)__builtin_amdgcn_readfirstlane((int)__hip_atomic_load(sync + S2_SYNC_BAR, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) < (u32)G)
-            if (spin.fail(p.abort_flag)) { ok = false; break; }
-        if (tid < 8) pp.pres[tid] = __hip_atomic_load(sync + S2_SYNC_MAP + tid, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (tid == 0) pp.ok = ok ? 1 : 0;
-    }
-    __syncthreads();
+    if (p.dbg && tid == 0) s2_stamp(p, S2_STAMP_ALPHABET, true);
     if (!pp.ok) return -1;
     if (tid < 256) {   // (3) code of a byte value = its rank among the values present (7 = not a letter / too many letters)
         int rank = 0, nl = 0;
@@ -695,25 +755,29 @@ __device__ __forceinline__ int s2_prologue(S2Prep& pp, const FillParams& p, cons
             }
     }
     if (nl <= 7) {
-        // (4) my own [bpad8 | bcode]: 4 bytes per thread and pass (per and front are multiples of 16, seq_b is 16-byte aligned)
+        // (4) my own [bpad8 | bcode]: 16 bytes per thread and pass (per and front are multiples of 16, seq_b and the copies are 16-byte
+        // aligned): a 16384-row b is two passes of the workgroup, where 4 bytes per thread made six, one memory latency each
         unsigned char* const mine = p.priv + (int64_t)wg * p.priv_stride;
-        for (int64_t i = 4 * (int64_t)tid; i < per; i += 4 * (int64_t)nth) {
+        for (int64_t i = 16 * (int64_t)tid; i < per; i += 16 * (int64_t)nth) {
             const int64_t k = i - front;
-            u32 raw = 0u, code = 0x07070707u;
-            if (k >= 0 && k + 4 <= rows) {
-                raw = *(const u32*)(seq_b + k);
-                code = (u32)pp.tab[raw & 255u] | ((u32)pp.tab[(raw >> 8) & 255u] << 8) | ((u32)pp.tab[(raw >> 16) & 255u] << 16) | ((u32)pp.tab[raw >> 24] << 24);
-            } else if (k + 4 > 0 && k < rows) {
+            u32 raw[4] = {0u, 0u, 0u, 0u}, code[4] = {0x07070707u, 0x07070707u, 0x07070707u, 0x07070707u};
+            if (k >= 0 && k + 16 <= rows) {
+                const uint4 v = *(const uint4*)(seq_b + k);
+                raw[0] = v.x; raw[1] = v.y; raw[2] = v.z; raw[3] = v.w;
 #pragma unroll
-                for (int q = 0; q < 4; ++q)
+                for (int d = 0; d < 4; ++d)
+                    code[d] = (u32)pp.tab[raw[d] & 255u] | ((u32)pp.tab[(raw[d] >> 8) & 255u] << 8) | ((u32)pp.tab[(raw[d] >> 16) & 255u] << 16) | ((u32)pp.tab[raw[d] >> 24] << 24);
+            } else if (k + 16 > 0 && k < rows) {
+#pragma unroll
+                for (int q = 0; q < 16; ++q)
                     if (k + q >= 0 && k + q < rows) {
                         const u32 ch = seq_b[k + q];
-                        raw |= ch << (8 * q);
-                        code = (code & ~(0xffu << (8 * q))) | ((u32)pp.tab[ch] << (8 * q));
+                        raw[q >> 2] |= ch << (8 * (q & 3));
+                        code[q >> 2] = (code[q >> 2] & ~(0xffu << (8 * (q & 3)))) | ((u32)pp.tab[ch] << (8 * (q & 3)));
                     }
             }
-            *(u32*)(mine + i) = raw;
-            *(u32*)(mine + per + i) = code;
+            *(uint4*)(mine + i) = make_uint4(raw[0], raw[1], raw[2], raw[3]);
+            *(uint4*)(mine + per + i) = make_uint4(code[0], code[1], code[2], code[3]);
         }
         // (5) my 1/G of [row 0 | column 0] of the matrices (a band's row 0 is its halo row: H comes from the kernel, P belongs to the band above)
         // (a column tile behind another one: its column 0 is that tile's last column)
@@ -737,19 +801,25 @@ __device__ __forceinline__ int s2_prologue(S2Prep& pp, const FillParams& p, cons
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");   // my copies are in the L2 before any wave of this workgroup reads them
     __syncthreads();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+    if (p.dbg && tid == 0) s2_stamp(p, S2_STAMP_PROLOGUE, true);
     return nl;
 }
 
 // worked: this launch was the one to fill (or was aborted): report and re-arm; otherwise only the sync words are reset
 __device__ __forceinline__ void s2_epilogue(const FillParams& p, bool worked) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's arg-max atomics (and stores) are acknowledged
+    if (p.dbg && (threadIdx.x & 63u) == 0) s2_stamp(p, S2_STAMP_STORES, true);
     __syncthreads();
-    if (threadIdx.x != 0) return;
+    if (threadIdx.x >= 64) return;
+    // wave 0: lane 0 counts the workgroup out; the last workgroup's whole wave re-arms (the XCD table is 256 words: four stores per lane
+    // where one thread issued 256 in a row)
+    const int lane = (int)threadIdx.x;
     gu32* const sync = (gu32*)p.sync;
-    const u32 prev = __hip_atomic_fetch_add(sync + S2_SYNC_OUT, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (prev != gridDim.x - 1u) return;
+    u32 prev = 0u;
+    if (lane == 0) prev = __hip_atomic_fetch_add(sync + S2_SYNC_OUT, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if ((u32)__builtin_amdgcn_readfirstlane((int)prev) != gridDim.x - 1u) return;
     // the last workgroup out (a column tile that is not the matrix' last one leaves key and abort flag to the tiles behind it)
-    if (worked && p.final_launch) {
+    if (lane == 0 && worked && p.final_launch) {
         const u64 k = __hip_atomic_load((gu64*)p.result_key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         const u32 ab = __hip_atomic_load((gu32*)p.abort_flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         if (p.result) {
@@ -762,11 +832,15 @@ __device__ __forceinline__ void s2_epilogue(const FillParams& p, bool worked) {
     }
     if (worked) {
         gu32* const xtab = (gu32*)(p.atab_w + SW_XTAB_OFF);
-        for (int i = 0; i < 256; ++i) __hip_atomic_store(xtab + i, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+#pragma unroll
+        for (int i = 0; i < 256; i += 64) __hip_atomic_store(xtab + i + lane, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
-    for (int w = 0; w < 8; ++w) __hip_atomic_store(sync + S2_SYNC_MAP + w, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __hip_atomic_store(sync + S2_SYNC_BAR, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __hip_atomic_store(sync + S2_SYNC_OUT, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (lane < 8) __hip_atomic_store(sync + S2_SYNC_MAP + lane, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (lane == 0) {
+        __hip_atomic_store(sync + S2_SYNC_BAR, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(sync + S2_SYNC_OUT, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (p.dbg) s2_stamp(p, S2_STAMP_OUT, false);
+    }
 }
 
 template <int NC, bool OV>
