@@ -191,6 +191,40 @@ int sw_batch_traceback_device(sw_ctx* ctx, void* d_P, int p_elem_bytes, int64_t 
 int sw_search_device(sw_ctx* ctx, const char* d_query, int64_t qlen, const char* d_db, const int64_t* offsets,
                      int64_t ntargets, const sw_scores* scores, sw_result* d_results, void* stream);
 
+/* Database search with a substitution matrix and affine gaps (csrc/sw_search_affine.hip): what protein searches use.
+ * sw_submat: s[x][y] = score of query byte x against target byte y (any byte value is a letter; the table need not be symmetric).
+ * sw_affine: gap_open <= 0 and gap_extend <= 0; a gap of k letters scores gap_open + k * gap_extend.  Per target, with q the query
+ * (columns j), t the target (rows i), go = gap_open, ge = gap_extend:
+ *   H[0][j] = H[i][0] = 0, E[0][j] = F[i][0] = -inf
+ *   E[i][j] = max(E[i-1][j], H[i-1][j] + go) + ge            (a gap that consumes target letters)
+ *   F[i][j] = max(F[i][j-1], H[i][j-1] + go) + ge            (a gap that consumes query letters)
+ *   H[i][j] = max(0, H[i-1][j-1] + s[q[j-1]][t[i-1]], E[i][j], F[i][j])
+ * d_results[k] = {max_pos, max_score, 0} by the rule and layout of sw_search_device: max_score = max H, max_pos = the lowest
+ * i*(qlen+1)+j that holds it, 0 if no cell is positive; empty targets give {0,0,0}; input order.  With gap_open = 0 and the table
+ * of sw_submat_match(match, mismatch) the results are those of sw_search_device for {match, mismatch, gap_extend}, bit for bit.
+ * d_query, d_db, offsets, d_results, stream: as for sw_search_device.  The table is HOST memory, copied before the call returns.
+ * SW_EINVAL for NULL pointers, the offsets / length errors of sw_search_device, gap_open > 0 or gap_extend > 0,
+ * gap_open + gap_extend < -2^24, and max(largest table entry, 0) * min(qlen, longest target) >= 2^24 (the 24-bit score of the
+ * arg-max key).  Score and end cell only: there is no affine fill with a predecessor matrix yet, so the alignment PATH of a hit is
+ * not available under affine scoring (sw_fill_device + sw_traceback_device re-fill a hit with linear gaps only).
+ * sw_search_affine_host: the same computation in plain C++ on host memory, no GPU needed (the CPU leg). */
+typedef struct { int8_t s[256][256]; } sw_submat;
+typedef struct { const sw_submat* sub; int32_t gap_open, gap_extend; } sw_affine;
+int sw_search_affine_device(sw_ctx* ctx, const char* d_query, int64_t qlen, const char* d_db, const int64_t* offsets,
+                            int64_t ntargets, const sw_affine* scoring, sw_result* d_results, void* stream);
+int sw_search_affine_host(const char* query, int64_t qlen, const char* db, const int64_t* offsets, int64_t ntargets,
+                          const sw_affine* scoring, sw_result* results);
+/* Tables.  sw_submat_match: s[x][y] = x == y ? match : mismatch (matchMissmatchScore, serial_smithW.c:251-256; both must fit int8:
+ * the builder returns nothing, so it clamps them to -128..127 -- a caller that takes them from a user checks the range first, as
+ * smithW and the Python wrapper do, which refuse such scores).  sw_submat_from_letters: `scores` is n x n, row = query letter, over the n bytes of
+ * `letters`; every pair with a byte not in `letters` scores `other` (n 1..256, no letter twice, other within int8).
+ * sw_read_submat: the NCBI text format -- '#' comment lines and blank lines are skipped, a header line of letters, then rows of
+ * one letter followed by n integers (row = query letter); lower-case letters in the file are upper-cased, every entry must fit
+ * int8, every row must have n entries and name a header letter; `other` is the smallest entry of the file.  No table is built in. */
+void sw_submat_match(int match, int mismatch, sw_submat* out);
+int sw_submat_from_letters(const char* letters, int n, const int8_t* scores, int other, sw_submat* out);
+int sw_read_submat(const char* path, sw_submat* out);
+
 /* Every record of a FASTA file in one pass, under the parsing rules of sw_read_fasta.  Two-call pattern:
  * with seq == NULL it reports the counts only (*nrecords, *total_len).  Otherwise seq receives total_len bytes (seq_cap
  * at least that) and offsets nrecords + 1 entries (offsets_cap at least that): record k = seq[offsets[k] .. offsets[k+1]),
@@ -352,7 +386,8 @@ int sw_synchronize(sw_ctx* ctx, void* stream);   /* waits for `stream`; reports 
  * (scout workgroups of the last fill), "last_xcd_mode" (1: that fill dealt its roles per XCD), "last_scan_all" (1: every workgroup of that fill
  * scanned the alphabet for itself, 0: the shared scan behind a grid barrier), "xcd_round_robin" (1: sw_create saw
  * workgroup i of a launch on XCD i % 8), "last_batch_kernel" (0: the last batch ran on the fall-back, 1: one pair per wave, 2: two pairs per
- * wave on packed lanes) and "last_search_kernel" (the last search: 2 * (columns per lane / 8) + 1 for the wide profile). */
+ * wave on packed lanes), "last_search_kernel" (the last search: 2 * (columns per lane / 8) + 1 for the wide profile), "last_search_affine_kernel"
+ * (the last affine search: columns per lane / 8) and "last_search_affine_grid" (its workgroups). */
 int sw_set_option(sw_ctx* ctx, const char* name, int64_t value);
 int64_t sw_get_option(sw_ctx* ctx, const char* name);
 

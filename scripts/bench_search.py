@@ -4,6 +4,8 @@
   (b) the same total cells as equal-length targets
   (c) 4-letter equal-length 1024^2 database, search against sw_batch_device (score-only) on the same data
   (d) the (b) data through sw_batch_device, which takes the single-pair path for more than 8 letters
+  (a) and (b) also through sw_search_affine_device (random symmetric 24-letter matrix, gap_open -11, gap_extend -1): *_affine_* beside
+  the linear figures of the same database in the same process, and their ratio
 GCUPS = query letters x target letters / time of the call (torch events, median of --reps after --warmup)."""
 import argparse
 import importlib
@@ -62,6 +64,23 @@ def main():
         out[f"{tag}_grid"] = eng.get_option("last_search_grid")
         return res
 
+    # a random symmetric table over 24 protein letters (the 20 of the data among them), matches 4..11, mismatches -4..2
+    letters = np.frombuffer(b"ACDEFGHIKLMNPQRSTVWYBZX*", np.uint8)
+    mrng = np.random.default_rng(24)   # (its own generator: the data sets stay those of the linear runs)
+    tri = np.triu(mrng.integers(-4, 3, (24, 24)), 1)
+    sub = swamd.submat_from_letters(letters, (tri + tri.T + np.diag(mrng.integers(4, 12, 24))).astype(np.int8), -4)
+
+    def affine_gcups(query, packed, offs, tag):
+        d_q = torch.from_numpy(query.copy()).to(dev)
+        d_db = torch.from_numpy(packed.copy()).to(dev)
+        res = torch.zeros((len(offs) - 1, 3), dtype=torch.int64, device=dev)
+        ms = timed(lambda: eng.search_affine_device(d_q, len(query), d_db, offs, sub, -11, -1, out=res), args.warmup, args.reps)
+        cells = float(len(query)) * float(offs[-1] - offs[0])
+        out[f"{tag}_affine_ms"] = round(ms, 3)
+        out[f"{tag}_affine_gcups"] = round(cells / ms / 1e6, 1)
+        out[f"{tag}_affine_grid"] = eng.get_option("last_search_affine_grid")
+        out[f"{tag}_affine_over_linear"] = round(out[f"{tag}_affine_gcups"] / out[f"{tag}_gcups"], 3)
+
     def batch_gcups(query, b_all, tag, reps):
         npairs, n = b_all.shape
         d_a, d_b, cols, rows = eng.batch_to_device(np.broadcast_to(query, (npairs, len(query))), b_all)
@@ -81,12 +100,14 @@ def main():
     out["a_len_median"] = int(np.median(lens))
     out["a_len_max"] = int(lens.max())
     search_gcups(q, packed, offs, "a")
+    affine_gcups(q, packed, offs, "a")
     # (b) the same cells, equal lengths
     L = int(round(offs[-1] / args.targets))
     offs_b = np.arange(args.targets + 1, dtype=np.int64) * L
     packed_b = rng.choice(PROTEIN, int(offs_b[-1])).astype(np.uint8)
     out["b_len"] = L
     search_gcups(q, packed_b, offs_b, "b")
+    affine_gcups(q, packed_b, offs_b, "b")
     # (c) 4-letter 1024^2: search against the batch kernel on the same data
     qc = rng.choice(DNA, 1024).astype(np.uint8)
     bc = rng.choice(DNA, (args.pairs_c, 1024)).astype(np.uint8)

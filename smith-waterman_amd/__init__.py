@@ -41,6 +41,10 @@ class _Result(ctypes.Structure):
     _fields_ = [("max_pos", ctypes.c_int64), ("max_score", ctypes.c_int64), ("path_len", ctypes.c_int64)]
 
 
+class _Affine(ctypes.Structure):   # sw_affine: the table by pointer
+    _fields_ = [("sub", ctypes.c_void_p), ("gap_open", ctypes.c_int32), ("gap_extend", ctypes.c_int32)]
+
+
 # every symbol include/swhip.h declares: (restype, argtypes)
 _vp, _i64, _i32, _u32, _sz = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_uint32, ctypes.c_size_t
 ABI = {
@@ -58,6 +62,11 @@ ABI = {
     "sw_batch_device": (_i32, [_vp, _vp, _i64, _i64, _vp, _i64, _i64, _i64, ctypes.POINTER(_Scores), _vp, _vp, _vp, _vp]),
     "sw_batch_device_ex": (_i32, [_vp, _vp, _i64, _i64, _vp, _i64, _i64, _i64, ctypes.POINTER(_Scores), _vp, _vp, _i32, _vp, _vp]),
     "sw_search_device": (_i32, [_vp, _vp, _i64, _vp, _vp, _i64, ctypes.POINTER(_Scores), _vp, _vp]),
+    "sw_search_affine_device": (_i32, [_vp, _vp, _i64, _vp, _vp, _i64, ctypes.POINTER(_Affine), _vp, _vp]),
+    "sw_search_affine_host": (_i32, [_vp, _i64, _vp, _vp, _i64, ctypes.POINTER(_Affine), _vp]),
+    "sw_submat_match": (None, [_i32, _i32, _vp]),
+    "sw_submat_from_letters": (_i32, [_vp, _i32, _vp, _i32, _vp]),
+    "sw_read_submat": (_i32, [ctypes.c_char_p, _vp]),
     "sw_batch_traceback_device": (_i32, [_vp, _vp, _i32, _i64, _i64, _i64, _vp, _i64, _vp, _vp]),
     "sw_fill_band_device": (_i32, [_vp, _vp, _i64, _vp, _i64, _i64, ctypes.POINTER(_Scores), _vp, _i32, _vp, _i32, _vp, _u32, _vp, _u32, _vp,
                                    _i32, _i32, _vp, _vp]),
@@ -165,6 +174,57 @@ def _pack_targets(targets):
         offs[1:] = np.cumsum([len(x) for x in seqs])
     packed = np.concatenate(seqs) if seqs and offs[-1] > 0 else np.zeros(0, np.uint8)
     return np.ascontiguousarray(packed, np.uint8), offs
+
+
+def submat_match(match: int, mismatch: int):
+    """(256, 256) int8 table s[x][y] = match if x == y else mismatch (sw_submat_match).  Both must fit int8: the C builder would
+    clamp them, which is a different scoring from the one asked for, so that is an error here."""
+    for name, v in (("match", match), ("mismatch", mismatch)):
+        if not -128 <= int(v) <= 127:
+            raise ValueError(f"submat_match: {name} = {v} does not fit int8")
+    out = np.zeros((256, 256), np.int8)
+    lib().sw_submat_match(match, mismatch, out.ctypes.data)
+    return out
+
+
+def submat_from_letters(letters, scores, other: int):
+    """(256, 256) int8 table from an n x n score array over `letters` (row = query letter); every pair with a byte that is not listed
+    scores `other` (sw_submat_from_letters)."""
+    lt = _as_seq(letters)
+    sc = np.ascontiguousarray(scores, np.int8)
+    if sc.shape != (len(lt), len(lt)):
+        raise ValueError(f"scores must be {len(lt)} x {len(lt)}")
+    out = np.zeros((256, 256), np.int8)
+    _check(lib().sw_submat_from_letters(lt.ctypes.data, len(lt), sc.ctypes.data, int(other), out.ctypes.data))
+    return out
+
+
+def read_submat(path: str):
+    """(256, 256) int8 table from a substitution matrix in the NCBI text format (sw_read_submat)."""
+    out = np.zeros((256, 256), np.int8)
+    _check(lib().sw_read_submat(os.fsencode(path), out.ctypes.data))
+    return out
+
+
+def _affine(submat, gap_open: int, gap_extend: int):
+    """(the table kept alive, the sw_affine that points at it)"""
+    sub = np.ascontiguousarray(submat, np.int8)
+    if sub.shape != (256, 256):
+        raise ValueError("the substitution matrix must be (256, 256) int8")
+    return sub, _Affine(sub.ctypes.data, int(gap_open), int(gap_extend))
+
+
+def search_affine_host(query, targets, submat, gap_open: int, gap_extend: int, top=None):
+    """sw_search_affine_host: the affine search in plain C++ on the host (no GPU).  Arguments and results as Engine.search_affine."""
+    q = np.ascontiguousarray(_as_seq(query))
+    packed, offs = _pack_targets(targets)
+    ntargets = len(offs) - 1
+    db = packed if len(packed) else np.zeros(1, np.uint8)
+    res = np.zeros((max(1, ntargets), 3), np.int64)
+    sub, sc = _affine(submat, gap_open, gap_extend)
+    _check(lib().sw_search_affine_host(q.ctypes.data, len(q), db.ctypes.data, offs.ctypes.data, ntargets, ctypes.byref(sc), res.ctypes.data))
+    out = res[:ntargets]
+    return (out, top_hits(out, top)) if top is not None else out
 
 
 def top_hits(results, k: int):
@@ -475,6 +535,35 @@ class Engine:
         sc = _Scores(*scores)
         _check(lib().sw_search_device(self._h, d_query.data_ptr(), qlen, d_db.data_ptr(), offs.ctypes.data, ntargets, ctypes.byref(sc),
                                       res.data_ptr(), self._stream()))
+        return res[:ntargets]
+
+    def search_affine(self, query, targets, submat, gap_open: int, gap_extend: int, top=None):
+        """Database search with a substitution matrix and affine gaps (sw_search_affine_device).  submat: (256, 256) int8,
+        s[query byte][target byte] (read_submat, submat_match, submat_from_letters); a gap of k letters scores gap_open + k * gap_extend.
+        targets and the return value as for search()."""
+        t = self.torch
+        q = _as_seq(query)
+        packed, offs = _pack_targets(targets)
+        dev = f"cuda:{self.device}"
+        d_q = t.from_numpy(q.copy()).to(dev)
+        d_db = t.from_numpy(packed.copy() if len(packed) else np.zeros(1, np.uint8)).to(dev)
+        res = self.search_affine_device(d_q, len(q), d_db, offs, submat, gap_open, gap_extend)
+        self.synchronize()
+        out = res.cpu().numpy()
+        return (out, top_hits(out, top)) if top is not None else out
+
+    def search_affine_device(self, d_query, qlen: int, d_db, offsets, submat, gap_open: int, gap_extend: int, out=None):
+        """sw_search_affine_device on device-resident query / packed targets (torch uint8 tensors), host int64 offsets and a host
+        (256, 256) int8 table; asynchronous on torch's current stream.  Returns the (ntargets, 3) int64 result tensor (`out` if given)."""
+        t = self.torch
+        offs = np.ascontiguousarray(offsets, np.int64).reshape(-1)
+        if len(offs) == 0:
+            offs = np.zeros(1, np.int64)
+        ntargets = len(offs) - 1
+        res = out if out is not None else t.zeros((max(1, ntargets), 3), dtype=t.int64, device=f"cuda:{self.device}")
+        sub, sc = _affine(submat, gap_open, gap_extend)
+        _check(lib().sw_search_affine_device(self._h, d_query.data_ptr(), qlen, d_db.data_ptr(), offs.ctypes.data, ntargets, ctypes.byref(sc),
+                                             res.data_ptr(), self._stream()))
         return res[:ntargets]
 
     def traceback(self, out: Fill, max_pos: int | None = None, want_path: bool = True):

@@ -4,6 +4,9 @@
 //   smithW --fasta A.fa B.fa   real sequences: a = first record of A.fa (columns), b = first record of B.fa (rows)
 //   smithW --search Q.fa DB.fa [--top K]   database search: a = record --record-a of Q.fa against every record of DB.fa (sw_search_device);
 //                              prints the K best hits (default 10): rank, record, score, target_end, query_end (max_pos = target_end*(qlen+1)+query_end)
+//     ... --matrix FILE --gap-open O --gap-extend E   substitution matrix (NCBI text format) and affine gaps (sw_search_affine_device): a gap of k
+//                              letters scores O + k E; without --matrix the table is match / mismatch of --scores (signed bytes),
+//                              without --gap-extend E = the gap of --scores; --gap-extend alone (O = 0) is the linear search with gap E
 // Extra flags: --seed N  --dump | --dump-labels (the header-row printers of omp_smithW.c)  --h64  --no-backtrack  --scores M X G  --record-a I  --record-b J
 //   --gpus N | --devices 0,1,..   ONE matrix over several GPUs (row bands, sw_multi_*; an id may repeat)  --p8  int8 P
 // The DP fill runs on the GPU through the C-ABI (include/swhip.h); stdout keeps the two
@@ -77,7 +80,17 @@ static void print_pred_labelled(const std::vector<int32_t>& P, long long n, long
 }
 
 // --search: one query record against every record of a FASTA database on the GPU, the best `top` hits by score (ties: lower record first)
-static int search_main(const char* qpath, long long rec, const char* dbpath, long long top, const sw_scores& sc) {
+// (`on`: --matrix or --gap-open was given, the search goes through the affine kernel; --gap-extend alone is a linear gap: sw_search_device)
+struct AffineArgs { bool on = false; const char* matrix = nullptr; bool has_open = false, has_extend = false; int open = 0, extend = 0; };
+// a whole decimal integer or nothing: "-x", "" and "3k" are errors, not 0 or 3
+static bool parse_int(const char* flag, const char* text, int* out) {
+    char* end = nullptr;
+    const long v = strtol(text, &end, 10);
+    if (end == text || *end || v < -(1l << 30) || v > (1l << 30)) { fprintf(stderr, "smithW: %s needs an integer, got \"%s\"\n", flag, text); return false; }
+    *out = (int)v;
+    return true;
+}
+static int search_main(const char* qpath, long long rec, const char* dbpath, long long top, const sw_scores& sc, const AffineArgs& af) {
     int64_t qlen = 0, nrec = 0, total = 0;
     CHECK(sw_read_fasta(qpath, rec, nullptr, 0, &qlen));
     std::vector<char> q((size_t)qlen + 1);
@@ -94,8 +107,16 @@ static int search_main(const char* qpath, long long rec, const char* dbpath, lon
     CHECK(sw_device_malloc(ctx, (size_t)(nrec > 0 ? nrec : 1) * sizeof(sw_result), &d_res));
     CHECK(sw_memcpy_h2d(ctx, d_q, q.data(), (size_t)qlen));
     if (total) CHECK(sw_memcpy_h2d(ctx, d_db, db.data(), (size_t)total));
+    std::vector<sw_submat> sub(af.on ? 1 : 0);
+    sw_affine aff = {nullptr, af.has_open ? af.open : 0, af.has_extend ? af.extend : sc.gap};
+    if (af.on) {
+        if (af.matrix) CHECK(sw_read_submat(af.matrix, sub.data()));
+        else sw_submat_match(sc.match, sc.mismatch, sub.data());
+        aff.sub = sub.data();
+    }
     const double t0 = now_s();
-    CHECK(sw_search_device(ctx, (const char*)d_q, qlen, (const char*)d_db, offs.data(), nrec, &sc, (sw_result*)d_res, nullptr));
+    if (af.on) CHECK(sw_search_affine_device(ctx, (const char*)d_q, qlen, (const char*)d_db, offs.data(), nrec, &aff, (sw_result*)d_res, nullptr));
+    else CHECK(sw_search_device(ctx, (const char*)d_q, qlen, (const char*)d_db, offs.data(), nrec, &sc, (sw_result*)d_res, nullptr));
     CHECK(sw_synchronize(ctx, nullptr));
     const double t1 = now_s();
     std::vector<sw_result> res((size_t)nrec);
@@ -126,6 +147,7 @@ int main(int argc, char** argv) {
     long long rec_a = 0, rec_b = 0;
     const char *search_q = nullptr, *search_db = nullptr;
     long long top = 10;
+    AffineArgs af;
     sw_scores sc = {3, -3, -2};
     int npos = 0;
     for (int ai = 1; ai < argc; ++ai) {
@@ -145,14 +167,25 @@ int main(int argc, char** argv) {
         else if (f == "--fasta" && ai + 2 < argc) { fasta_a = argv[++ai]; fasta_b = argv[++ai]; builtin = false; }
         else if (f == "--search" && ai + 2 < argc) { search_q = argv[++ai]; search_db = argv[++ai]; builtin = false; }
         else if (f == "--top" && ai + 1 < argc) top = strtoll(argv[++ai], nullptr, 10);
+        else if (f == "--matrix" && ai + 1 < argc) { af.matrix = argv[++ai]; af.on = true; }
+        else if (f == "--gap-open" && ai + 1 < argc) { if (!parse_int("--gap-open", argv[++ai], &af.open)) return 2; af.has_open = af.on = true; }
+        else if (f == "--gap-extend" && ai + 1 < argc) { if (!parse_int("--gap-extend", argv[++ai], &af.extend)) return 2; af.has_extend = true; }
         else if (f == "--record-a" && ai + 1 < argc) rec_a = strtoll(argv[++ai], nullptr, 10);
         else if (f == "--record-b" && ai + 1 < argc) rec_b = strtoll(argv[++ai], nullptr, 10);
         else if (f == "--seed" && ai + 1 < argc) seed = (unsigned)strtoul(argv[++ai], nullptr, 10);
         else if (f == "--scores" && ai + 3 < argc) { sc.match = atoi(argv[++ai]); sc.mismatch = atoi(argv[++ai]); sc.gap = atoi(argv[++ai]); }
-        else { fprintf(stderr, "usage: smithW [<cols> <rows> | --fasta A.fa B.fa [--record-a I] [--record-b J] | --search QUERY.fa DB.fa [--record-a I] [--top K]] [--seed N] [--dump | --dump-labels] [--h64] [--no-backtrack] [--scores M X G] [--gpus N | --devices 0,1,..] [--p8]\n"); return 2; }
+        else { fprintf(stderr, "usage: smithW [<cols> <rows> | --fasta A.fa B.fa [--record-a I] [--record-b J] | --search QUERY.fa DB.fa [--record-a I] [--top K] [--matrix FILE] [--gap-open O] [--gap-extend E]] [--seed N] [--dump | --dump-labels] [--h64] [--no-backtrack] [--scores M X G] [--gpus N | --devices 0,1,..] [--p8]\n"); return 2; }
     }
     if (npos == 1) { fprintf(stderr, "smithW: <cols> needs <rows>\n"); return 2; }
-    if (search_q) return search_main(search_q, rec_a, search_db, top, sc);
+    if (search_q) {
+        if (af.on && !af.matrix && (sc.match < -128 || sc.match > 127 || sc.mismatch < -128 || sc.mismatch > 127)) {   // (sw_submat_match would clamp them)
+            fprintf(stderr, "smithW: --gap-open without --matrix needs --scores M X within -128..127 (a table of signed bytes), got %d %d\n", sc.match, sc.mismatch);
+            return 2;
+        }
+        if (af.has_extend && !af.on) sc.gap = af.extend;   // --gap-extend alone: gap_open = 0 is the linear recurrence, and its kernel is the cheaper one
+        return search_main(search_q, rec_a, search_db, top, sc, af);
+    }
+    if (af.on || af.has_extend) { fprintf(stderr, "smithW: --matrix / --gap-open / --gap-extend go with --search\n"); return 2; }
     if (fasta_a) {
         int64_t la = 0, lb = 0;
         CHECK(sw_read_fasta(fasta_a, rec_a, nullptr, 0, &la));

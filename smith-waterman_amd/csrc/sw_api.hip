@@ -14,7 +14,11 @@
 #include "sw_kernels.h"
 #include "sw_plan.h"
 
-namespace swh { void set_err(const char* fmt, ...); }
+namespace swh {
+void set_err(const char* fmt, ...);
+int check_search_affine(const char* who, int64_t qlen, const int64_t* offsets, int64_t ntargets, const sw_affine* sc, int64_t* maxlen_out,
+                        int64_t* nonempty_out);   // sw_host.cpp
+}
 extern "C" int sw_place_pair_ratio(void* d_X, size_t xbytes, void* d_Y, size_t ybytes, float* ratio, float* ms_together);   // sw_place.hip
 using swh::set_err;
 
@@ -89,6 +93,13 @@ struct sw_ctx {
     int64_t last_search_kernel = 0;     // its kernel: index in kSearch (swp::search_kernel_index)
     int search_per_cu[swp::kSearchKernels] = {};   // occupancy of every sw_search_wave instantiation at 256 threads ...
     bool search_per_cu_known = false;              // ... queried at the first search
+    // affine search (sw_search_affine_device): it shares the workspaces above; its own are the substitution matrix (device + a pinned
+    // host copy under the schedule's event: both uploads of a call are behind sitems_ev when it is recorded)
+    signed char* d_submat = nullptr; signed char* h_submat = nullptr;
+    int64_t last_search_affine_grid = 0;    // workgroups of the last affine search launch
+    int64_t last_search_affine_kernel = 0;  // its kernel: index in kSearchAffine (swp::search_affine_kernel_index)
+    int search_affine_per_cu[swp::kSearchAffineKernels] = {};   // occupancy of every sw_search_affine_wave instantiation at 256 threads ...
+    bool search_affine_per_cu_known = false;                    // ... queried at the first affine search
     bool xcd_round_robin = false;       // sw_xcc_probe saw workgroup i on XCD i % 8 (8 XCDs of 32 CUs)
     std::map<void*, void*> out_base;    // sw_alloc_outputs: pointer handed out -> allocation to free
     std::map<void*, float> pair_ratio;  // ... P handed out -> the store probe's ratio of its pair (~1.4: two classes of the HBM, ~2: one)
@@ -158,6 +169,8 @@ void sw_destroy(sw_ctx* c) {
     if (c->d_sitems) (void)hipFree(c->d_sitems);
     if (c->h_sitems) (void)hipHostFree(c->h_sitems);
     if (c->d_sctr) (void)hipFree(c->d_sctr);
+    if (c->d_submat) (void)hipFree(c->d_submat);
+    if (c->h_submat) (void)hipHostFree(c->h_submat);
     delete c;
 }
 
@@ -228,6 +241,8 @@ int64_t sw_get_option(sw_ctx* c, const char* name) {
     if (!strcmp(name, "last_batch_kernel")) return c->last_batch_kernel;
     if (!strcmp(name, "last_search_grid")) return c->last_search_grid;
     if (!strcmp(name, "last_search_kernel")) return c->last_search_kernel;
+    if (!strcmp(name, "last_search_affine_grid")) return c->last_search_affine_grid;
+    if (!strcmp(name, "last_search_affine_kernel")) return c->last_search_affine_kernel;
     if (!strcmp(name, "placement_budget_ms")) return c->opt_place_budget_ms;
     if (!strcmp(name, "placement_hold_gib")) return c->opt_place_hold_gib;
     if (!strcmp(name, "probe_foreign_pairs")) return c->opt.probe_foreign_pairs;
@@ -838,6 +853,78 @@ int sw_search_device(sw_ctx* c, const char* d_query, int64_t qlen, const char* d
     hipLaunchKernelGGL(kSearch[plan.kernel].k, dim3((unsigned)plan.grid), dim3(256), 0, stream, sp);
     HIP_TRY(hipGetLastError());
     c->last_search_grid = plan.grid; c->last_search_kernel = plan.kernel;
+    return SW_OK;
+}
+
+// the instantiations of the affine search kernel (sw_search_affine.hip), picked by swp::plan_search_affine
+using SearchAffineKernel = void (*)(swk::SearchAffineParams);
+static constexpr Indexed<SearchAffineKernel> kSearchAffine[] = {
+    {swp::search_affine_kernel_index(4), swk::sw_search_affine_wave<4>},
+    {swp::search_affine_kernel_index(8), swk::sw_search_affine_wave<8>},
+    {swp::search_affine_kernel_index(16), swk::sw_search_affine_wave<16>},
+};
+static_assert(std::size(kSearchAffine) == swp::kSearchAffineKernels && at_their_indices(kSearchAffine));
+
+// Database search with a substitution matrix and affine gaps (csrc/sw_search_affine.hip).  The shape of sw_search_device: no host
+// round trip, the schedule and the 64 KiB table are uploaded from pinned copies, the profile is built on the device.
+int sw_search_affine_device(sw_ctx* c, const char* d_query, int64_t qlen, const char* d_db, const int64_t* offsets, int64_t ntargets,
+                            const sw_affine* scoring, sw_result* d_results, void* stream_) {
+    if (!c || !d_query || !d_db || !offsets || !d_results || !scoring || ntargets < 0) {
+        set_err("sw_search_affine_device: NULL pointer or negative target count");
+        return SW_EINVAL;
+    }
+    int64_t maxlen = 0, nonempty = 0;
+    if (int rc = swh::check_search_affine("sw_search_affine_device", qlen, offsets, ntargets, scoring, &maxlen, &nonempty)) return rc;
+    if (ntargets == 0) return SW_OK;
+    hipStream_t stream = (hipStream_t)stream_;
+    HIP_TRY(hipSetDevice(c->device));
+    DevOrder order(c, stream, false);
+    if (order.rc) return order.rc;
+    // empty targets keep the zeros: {0, 0, 0}
+    HIP_TRY(hipMemsetAsync(d_results, 0, (size_t)ntargets * sizeof(sw_result), stream));
+    if (nonempty == 0) return SW_OK;
+    // occupancy of every instantiation, once per context: the columns per lane and the grid depend on it
+    if (!c->search_affine_per_cu_known) {
+        for (int k = 0; k < swp::kSearchAffineKernels; ++k)
+            HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&c->search_affine_per_cu[k], kSearchAffine[k].k, 256, 0));
+        c->search_affine_per_cu_known = true;
+    }
+    swp::SearchAffineJob sj;
+    sj.qlen = qlen; sj.maxlen = maxlen; sj.ntargets = nonempty; sj.num_cus = c->num_cus;
+    std::copy(std::begin(c->search_affine_per_cu), std::end(c->search_affine_per_cu), sj.per_cu);
+    const swp::SearchAffinePlan plan = swp::plan_search_affine(sj);
+    if (c->search_affine_per_cu[plan.kernel] < 1) { set_err("the affine search kernel does not fit a CU on this device"); return SW_EDEVICE; }
+    // the schedule and the table are uploaded from pinned copies: the previous uploads have to have left them
+    if (c->sitems_ev) HIP_TRY(hipEventSynchronize(c->sitems_ev));
+    else HIP_TRY(hipEventCreateWithFlags(&c->sitems_ev, hipEventDisableTiming));
+    bool fresh = false;
+    if (int rc = grow_schedule(c, (size_t)nonempty, stream)) return rc;
+    if (int rc = grow_workspace((void**)&c->d_sprof, c->sprof_cap, plan.prof_need, 1, 0, stream, fresh)) return rc;
+    if (int rc = grow_workspace((void**)&c->d_sbnd, c->sbnd_cap, plan.bnd_need, 4, 0, stream, fresh)) return rc;
+    if (!c->d_sctr) HIP_TRY(hipMalloc((void**)&c->d_sctr, 64));
+    if (!c->d_submat) HIP_TRY(hipMalloc((void**)&c->d_submat, sizeof(sw_submat)));
+    if (!c->h_submat) HIP_TRY(hipHostMalloc((void**)&c->h_submat, sizeof(sw_submat), 0));
+    swp::search_schedule(offsets, ntargets, c->h_sitems);
+    memcpy(c->h_submat, scoring->sub, sizeof(sw_submat));
+    HIP_TRY(hipMemcpyAsync(c->d_sitems, c->h_sitems, (size_t)nonempty * sizeof(swk::SearchItem), hipMemcpyHostToDevice, stream));
+    HIP_TRY(hipMemcpyAsync(c->d_submat, c->h_submat, sizeof(sw_submat), hipMemcpyHostToDevice, stream));
+    HIP_TRY(hipEventRecord(c->sitems_ev, stream));
+    hipLaunchKernelGGL(swk::sw_search_profile_submat, dim3((unsigned)plan.prof_blocks), dim3(256), 0, stream, (const unsigned char*)d_query, qlen,
+                       plan.qpad, c->d_sprof, (const signed char*)c->d_submat);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemsetAsync(c->d_sctr, 0, 4, stream));
+    swk::SearchAffineParams sp;
+    memset(&sp, 0, sizeof sp);
+    sp.db = (const unsigned char*)d_db;
+    sp.items = c->d_sitems; sp.nitems = nonempty;
+    sp.prof = c->d_sprof; sp.qpad = plan.qpad; sp.qlen = qlen;
+    sp.ge = scoring->gap_extend; sp.goe = scoring->gap_open + scoring->gap_extend;
+    sp.bnd = plan.bnd_per ? c->d_sbnd : nullptr; sp.bnd_per = plan.bnd_per;
+    sp.counter = c->d_sctr;
+    sp.results = d_results;
+    hipLaunchKernelGGL(kSearchAffine[plan.kernel].k, dim3((unsigned)plan.grid), dim3(256), 0, stream, sp);
+    HIP_TRY(hipGetLastError());
+    c->last_search_affine_grid = plan.grid; c->last_search_affine_kernel = plan.kernel;
     return SW_OK;
 }
 

@@ -3,7 +3,9 @@
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
+#include <algorithm>
 #include <string>
+#include <vector>
 #include "../../include/swhip.h"
 
 namespace swh {
@@ -44,6 +46,42 @@ private:
     uint32_t st_[31];
     int f_, r_;
 };
+
+// The argument rules of the affine search (include/swhip.h), shared by the device and the host entry point; reports the longest
+// target and the number of non-empty ones.  kMaxDim: the 2^20 - 1 of sw_search_device (40-bit indices).
+int check_search_affine(const char* who, int64_t qlen, const int64_t* offsets, int64_t ntargets, const sw_affine* sc, int64_t* maxlen_out,
+                        int64_t* nonempty_out) {
+    constexpr int64_t kMaxDim = (1 << 20) - 1, kScoreLimit = 1ll << 24;
+    if (!sc || !sc->sub) { set_err("%s: NULL scoring or substitution matrix", who); return SW_EINVAL; }
+    if (qlen < 1 || qlen > kMaxDim) { set_err("%s: query length %lld out of range 1..%lld", who, (long long)qlen, (long long)kMaxDim); return SW_EINVAL; }
+    if (offsets[0] < 0) { set_err("%s: offsets[0] = %lld is negative", who, (long long)offsets[0]); return SW_EINVAL; }
+    int64_t maxlen = 0, nonempty = 0;
+    for (int64_t k = 0; k < ntargets; ++k) {
+        const int64_t len = offsets[k + 1] - offsets[k];
+        if (len < 0) { set_err("%s: offsets decrease at target %lld", who, (long long)k); return SW_EINVAL; }
+        if (len > kMaxDim) { set_err("%s: target %lld has length %lld (max %lld)", who, (long long)k, (long long)len, (long long)kMaxDim); return SW_EINVAL; }
+        maxlen = std::max(maxlen, len);
+        nonempty += len > 0;
+    }
+    if (sc->gap_open > 0) { set_err("%s: gap_open must be <= 0 (got %d)", who, sc->gap_open); return SW_EINVAL; }
+    if (sc->gap_extend > 0) { set_err("%s: gap_extend must be <= 0 (got %d)", who, sc->gap_extend); return SW_EINVAL; }
+    if ((int64_t)sc->gap_open + (int64_t)sc->gap_extend < -kScoreLimit) {
+        set_err("%s: gap_open + gap_extend = %lld is below -2^24", who, (long long)sc->gap_open + (long long)sc->gap_extend);
+        return SW_EINVAL;
+    }
+    int best = 0, bx = 0, by = 0;
+    for (int x = 0; x < 256; ++x)
+        for (int y = 0; y < 256; ++y)
+            if (sc->sub->s[x][y] > best) { best = sc->sub->s[x][y]; bx = x; by = y; }
+    if ((int64_t)best * std::min(qlen, maxlen) >= kScoreLimit) {
+        set_err("%s: table entry s[%d][%d] = %d times min(query length %lld, longest target %lld) reaches 2^24 (the 24-bit score of the arg-max key)",
+                who, bx, by, best, (long long)qlen, (long long)maxlen);
+        return SW_EINVAL;
+    }
+    *maxlen_out = maxlen;
+    *nonempty_out = nonempty;
+    return SW_OK;
+}
 
 inline char letter(int v) {  // serial_smithW.c:339-346
     switch (v) { case 0: return 'A'; case 2: return 'C'; case 3: return 'G'; default: return 'T'; }
@@ -206,6 +244,139 @@ int sw_read_fasta_db(const char* path, char* seq, int64_t seq_cap, int64_t* offs
     if (seq) {
         if (cur + 1 < offsets_cap) offsets[cur + 1] = n; else overflow = true;
         if (overflow) { swh::set_err("sw_read_fasta_db: buffers too small (%lld bytes, %lld records)", (long long)n, (long long)(cur + 1)); return SW_EINVAL; }
+    }
+    return SW_OK;
+}
+
+// ---- substitution matrices
+void sw_submat_match(int match, int mismatch, sw_submat* out) {
+    if (!out) return;
+    const int8_t m = (int8_t)std::clamp(match, -128, 127), x = (int8_t)std::clamp(mismatch, -128, 127);
+    for (int a = 0; a < 256; ++a)
+        for (int b = 0; b < 256; ++b) out->s[a][b] = a == b ? m : x;
+}
+
+int sw_submat_from_letters(const char* letters, int n, const int8_t* scores, int other, sw_submat* out) {
+    if (!letters || !scores || !out || n < 1 || n > 256) { swh::set_err("sw_submat_from_letters: bad argument"); return SW_EINVAL; }
+    if (other < -128 || other > 127) { swh::set_err("sw_submat_from_letters: other = %d does not fit int8", other); return SW_EINVAL; }
+    int at[256];
+    std::fill(at, at + 256, -1);
+    for (int i = 0; i < n; ++i) {
+        const int b = (unsigned char)letters[i];
+        if (at[b] >= 0) { swh::set_err("sw_submat_from_letters: letter 0x%02x is listed twice", b); return SW_EINVAL; }
+        at[b] = i;
+    }
+    for (int a = 0; a < 256; ++a)
+        for (int b = 0; b < 256; ++b) out->s[a][b] = (at[a] >= 0 && at[b] >= 0) ? scores[at[a] * n + at[b]] : (int8_t)other;
+    return SW_OK;
+}
+
+// NCBI text format: '#' comments, a header line of letters, rows of a letter and n integers.
+int sw_read_submat(const char* path, sw_submat* out) {
+    if (!path || !out) { swh::set_err("sw_read_submat: bad argument"); return SW_EINVAL; }
+    FILE* f = fopen(path, "rb");
+    if (!f) { swh::set_err("sw_read_submat: cannot open %s", path); return SW_EINVAL; }
+    std::string text;
+    char buf[1 << 14];
+    size_t got;
+    while ((got = fread(buf, 1, sizeof buf, f)) > 0) text.append(buf, got);
+    const bool err = ferror(f) != 0;
+    fclose(f);
+    if (err) { swh::set_err("sw_read_submat: read error on %s", path); return SW_EINVAL; }
+    auto upper = [](unsigned char ch) { return (unsigned char)((ch >= 'a' && ch <= 'z') ? ch - 32 : ch); };
+    std::string letters;             // the header's letters, in order
+    std::string row_letters;         // the letter of every row read
+    std::vector<int8_t> scores;      // rows read x n
+    int lineno = 0, lo = 127;
+    for (size_t pos = 0; pos < text.size();) {
+        size_t end = text.find_first_of("\r\n", pos);
+        if (end == std::string::npos) end = text.size();
+        std::vector<std::string> tok;
+        for (size_t i = pos; i < end;) {
+            while (i < end && (text[i] == ' ' || text[i] == '\t')) ++i;
+            size_t j = i;
+            while (j < end && text[j] != ' ' && text[j] != '\t') ++j;
+            if (j > i) tok.push_back(text.substr(i, j - i));
+            i = j;
+        }
+        pos = end + 1;
+        ++lineno;
+        if (tok.empty() || tok[0][0] == '#') continue;
+        if (letters.empty()) {       // the header
+            for (const std::string& t : tok) {
+                if (t.size() != 1) { swh::set_err("sw_read_submat: %s line %d: header entry '%s' is not one letter", path, lineno, t.c_str()); return SW_EINVAL; }
+                const char ch = (char)upper((unsigned char)t[0]);
+                if (letters.find(ch) != std::string::npos) { swh::set_err("sw_read_submat: %s line %d: letter '%c' is listed twice", path, lineno, ch); return SW_EINVAL; }
+                letters.push_back(ch);
+            }
+            continue;
+        }
+        const size_t n = letters.size();
+        if (tok[0].size() != 1 || letters.find((char)upper((unsigned char)tok[0][0])) == std::string::npos) {
+            swh::set_err("sw_read_submat: %s line %d: row '%s' names no letter of the header", path, lineno, tok[0].c_str());
+            return SW_EINVAL;
+        }
+        const char rl = (char)upper((unsigned char)tok[0][0]);
+        if (row_letters.find(rl) != std::string::npos) { swh::set_err("sw_read_submat: %s line %d: row '%c' appears twice", path, lineno, rl); return SW_EINVAL; }
+        if (tok.size() != n + 1) {
+            swh::set_err("sw_read_submat: %s line %d: %zu entries in row '%c', the header has %zu letters", path, lineno, tok.size() - 1, rl, n);
+            return SW_EINVAL;
+        }
+        for (size_t i = 1; i <= n; ++i) {
+            char* endp = nullptr;
+            const long v = strtol(tok[i].c_str(), &endp, 10);
+            if (endp == tok[i].c_str() || *endp) { swh::set_err("sw_read_submat: %s line %d: '%s' is not an integer", path, lineno, tok[i].c_str()); return SW_EINVAL; }
+            if (v < -128 || v > 127) { swh::set_err("sw_read_submat: %s line %d: entry %ld does not fit int8", path, lineno, v); return SW_EINVAL; }
+            scores.push_back((int8_t)v);
+            lo = std::min(lo, (int)v);
+        }
+        row_letters.push_back(rl);
+    }
+    const size_t n = letters.size();
+    if (n == 0) { swh::set_err("sw_read_submat: %s has no header line", path); return SW_EINVAL; }
+    if (row_letters.size() != n) { swh::set_err("sw_read_submat: %s has %zu rows for %zu letters", path, row_letters.size(), n); return SW_EINVAL; }
+    // rows may come in any order: bring them into the header's
+    std::vector<int8_t> ordered(n * n);
+    for (size_t r = 0; r < n; ++r) {
+        const size_t at = letters.find(row_letters[r]);
+        std::copy(scores.begin() + (ptrdiff_t)(r * n), scores.begin() + (ptrdiff_t)((r + 1) * n), ordered.begin() + (ptrdiff_t)(at * n));
+    }
+    return sw_submat_from_letters(letters.data(), (int)n, ordered.data(), lo, out);
+}
+
+// The CPU leg of the affine search: Gotoh's recurrence row by row with one row of H and E kept (include/swhip.h states it); -inf is a
+// value no sum can reach from below (every E, F inside the matrix is at least gap_open + gap_extend >= -2^24).
+int sw_search_affine_host(const char* query, int64_t qlen, const char* db, const int64_t* offsets, int64_t ntargets, const sw_affine* scoring,
+                          sw_result* results) {
+    if (!query || !db || !offsets || !results || !scoring || ntargets < 0) { swh::set_err("sw_search_affine_host: NULL pointer or negative target count"); return SW_EINVAL; }
+    int64_t maxlen = 0, nonempty = 0;
+    if (int rc = swh::check_search_affine("sw_search_affine_host", qlen, offsets, ntargets, scoring, &maxlen, &nonempty)) return rc;
+    const int64_t go = scoring->gap_open, ge = scoring->gap_extend, M = qlen + 1;
+    constexpr int64_t NEG = -(1ll << 40);
+    std::vector<int64_t> Hrow((size_t)M), Erow((size_t)M);
+    const unsigned char* q = (const unsigned char*)query;
+    for (int64_t k = 0; k < ntargets; ++k) {
+        const unsigned char* t = (const unsigned char*)db + offsets[k];
+        const int64_t len = offsets[k + 1] - offsets[k];
+        std::fill(Hrow.begin(), Hrow.end(), 0);
+        std::fill(Erow.begin(), Erow.end(), NEG);
+        int64_t best = 0, best_pos = 0;
+        for (int64_t i = 1; i <= len; ++i) {
+            const unsigned char y = t[i - 1];
+            int64_t diag = 0, left = 0, F = NEG;       // H[i-1][j-1], H[i][j-1], F[i][j-1]
+            for (int64_t j = 1; j <= qlen; ++j) {
+                const int64_t up = Hrow[(size_t)j];
+                const int64_t E = std::max(Erow[(size_t)j], up + go) + ge;
+                F = std::max(F, left + go) + ge;
+                const int64_t h = std::max<int64_t>({0, diag + scoring->sub->s[q[j - 1]][y], E, F});
+                Erow[(size_t)j] = E;
+                Hrow[(size_t)j] = h;
+                diag = up;
+                left = h;
+                if (h > best) { best = h; best_pos = i * M + j; }   // row-major scan, strict: the lowest index among equals
+            }
+        }
+        results[k] = sw_result{best_pos, best, 0};
     }
     return SW_OK;
 }

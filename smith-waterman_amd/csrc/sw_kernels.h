@@ -124,6 +124,21 @@ __global__ void sw_search_profile(const unsigned char* q, int64_t qlen, int64_t 
 template <int C, bool WIDE>
 __global__ void sw_search_wave(SearchParams p);
 
+// sw_search_affine.hip: the same search with a substitution matrix and affine gaps
+struct SearchAffineParams {
+    const unsigned char* db;             // the targets back to back
+    const SearchItem* items; int64_t nitems;
+    const signed char* prof; int64_t qpad;   // SW_SEARCH_ROWS x qpad profile (sw_search_profile_submat), qpad = strips * 64 * C
+    int64_t qlen;
+    int ge, goe;                         // gap_extend, gap_open + gap_extend (both <= 0)
+    int* bnd; int64_t bnd_per;           // per resident wave: boundary pairs (H, F) between strips (ints), only when qlen > 64 * C
+    unsigned int* counter;               // next item (zero at launch)
+    sw_result* results;                  // caller's order
+};
+__global__ void sw_search_profile_submat(const unsigned char* q, int64_t qlen, int64_t qpad, signed char* prof, const signed char* sub);
+template <int C>
+__global__ void sw_search_affine_wave(SearchAffineParams p);
+
 template <typename HT, int B>
 __global__ void sw_strip_scan(const unsigned char* a, const unsigned char* b, FillParams p);
 template <typename HT, int NS, int NC>

@@ -362,6 +362,33 @@ SearchPlan plan_search(const SearchJob& j, const DeviceFacts& dev) {
     return s;
 }
 
+// The affine kernel keeps two values per cell (h, e) in registers where the linear one keeps one.  What the gfx950 code object reports
+// (waves per SIMD of 512 VGPRs: 6 at 4 columns per lane, 5 at 8, 3 at 16 -- 77 / 94 / 134 VGPRs) leaves 16 columns per lane at three
+// workgroups per CU: fewer waves, but each step's hand-over, arg-max and waits are spread over twice the cells and a query takes half
+// the strips, and the loads are software-pipelined a group of rows ahead, so the kernel needs waves only to cover issue bubbles.  The
+// linear thresholds are kept while 16 columns per lane still give two waves per SIMD (two workgroups per CU); below that 8 are taken.
+// Measured: 3371 GCUPS on the kernel at 16 columns per lane and a query of 2048, 3017 at 8 columns and a query of 512.
+constexpr int kAffineC16MinPerCu = 2;
+
+SearchAffinePlan plan_search_affine(const SearchAffineJob& j) {
+    using swk::SW_SEARCH_ROWS;
+    SearchAffinePlan s;
+    s.C = lane_columns(j.qlen);
+    if (s.C == 16 && j.per_cu[search_affine_kernel_index(16)] < kAffineC16MinPerCu) s.C = 8;
+    s.kernel = search_affine_kernel_index(s.C);
+    s.nstrips = (j.qlen + 64 * s.C - 1) / (64 * s.C);
+    s.qpad = s.nstrips * 64 * s.C;
+    s.bnd_row_ints = 2;
+    s.bnd_per = s.bnd_row_ints * boundary_ints(s.nstrips, j.maxlen);
+    s.grid = std::min<int64_t>((int64_t)j.per_cu[s.kernel] * j.num_cus, (j.ntargets + 3) / 4);
+    if (s.bnd_per) s.grid = std::min<int64_t>(s.grid, kSearchBndBytes / (s.bnd_per * 4 * 4));
+    s.grid = std::max<int64_t>(1, s.grid);
+    s.prof_need = (size_t)(SW_SEARCH_ROWS * s.qpad);
+    s.prof_blocks = (int)std::min<int64_t>((SW_SEARCH_ROWS * s.qpad + 255) / 256, kProfileBlocks);
+    s.bnd_need = s.bnd_per ? (size_t)(s.grid * 4 * s.bnd_per) : 0;
+    return s;
+}
+
 void search_schedule(const int64_t* offsets, int64_t ntargets, swk::SearchItem* items) {
     std::vector<int64_t> order;
     order.reserve((size_t)ntargets);

@@ -1,6 +1,7 @@
 // sw_plan.h -- the planners: every policy decision of one fill (kernel, workgroup shape, perm producer, strip geometry, column
 // tiles, scouts, roles per XCD, split strips, filler pacing, store kind), of one batch call (one pair or two pairs per wave, columns
-// per lane, pairs per launch, the kernel of every launch) and of one database search (columns per lane, profile kind, grid, schedule),
+// per lane, pairs per launch, the kernel of every launch) and of one database search (columns per lane, profile kind, grid, schedule;
+// plan_search_affine for the affine-gap search),
 // and the workspace sizes they need, as pure functions of the job, the device and the options.  Plain C++ (no HIP include):
 // sw_api.hip carries a plan out, tests/test_fill_plan.py and tests/test_batch_plan.py check the policy on a CPU.
 #pragma once
@@ -150,6 +151,31 @@ struct SearchPlan {
 };
 
 SearchPlan plan_search(const SearchJob& job, const DeviceFacts& dev);
+
+// ---- database search with a substitution matrix and affine gaps (sw_search_affine_device): sw_search_affine_wave<C> for C = 4, 8, 16,
+// its index in kSearchAffine (sw_api.hip, which checks its order against it at compile time)
+constexpr int kSearchAffineKernels = 3;
+constexpr int search_affine_kernel_index(int C) { return C / 8; }
+
+struct SearchAffineJob {
+    int64_t qlen = 0, maxlen = 0;            // query length, longest target
+    int64_t ntargets = 0;                    // non-empty targets
+    int num_cus = 256;
+    int per_cu[kSearchAffineKernels] = {};   // occupancy of every sw_search_affine_wave instantiation at 256 threads (workgroups per CU)
+};
+
+struct SearchAffinePlan {
+    int C = 0;                               // query columns per lane
+    int kernel = 0;                          // index of sw_search_affine_wave<C> (kSearchAffineKernels)
+    int64_t nstrips = 0, qpad = 0;           // strips of 64 C columns; profile row length
+    int bnd_row_ints = 0;                    // ints per row of a boundary column: H and F
+    int64_t bnd_per = 0;                     // per resident wave: boundary column between strips (ints), 0: one strip
+    int64_t grid = 0;                        // persistent workgroups of 4 waves
+    int prof_blocks = 0;                     // sw_search_profile_submat blocks
+    size_t prof_need = 0, bnd_need = 0;      // workspaces: profile (bytes), boundary columns (ints)
+};
+
+SearchAffinePlan plan_search_affine(const SearchAffineJob& job);
 
 // The schedule: the non-empty targets of offsets[0 .. ntargets], by decreasing length, ties in input order, written to items.
 void search_schedule(const int64_t* offsets, int64_t ntargets, swk::SearchItem* items);
