@@ -205,8 +205,8 @@ int sw_search_device(sw_ctx* ctx, const char* d_query, int64_t qlen, const char*
  * d_query, d_db, offsets, d_results, stream: as for sw_search_device.  The table is HOST memory, copied before the call returns.
  * SW_EINVAL for NULL pointers, the offsets / length errors of sw_search_device, gap_open > 0 or gap_extend > 0,
  * gap_open + gap_extend < -2^24, and max(largest table entry, 0) * min(qlen, longest target) >= 2^24 (the 24-bit score of the
- * arg-max key).  Score and end cell only: there is no affine fill with a predecessor matrix yet, so the alignment PATH of a hit is
- * not available under affine scoring (sw_fill_device + sw_traceback_device re-fill a hit with linear gaps only).
+ * arg-max key).  Score and end cell only; the alignment PATH of chosen hits comes from sw_align_affine_device below, which re-fills
+ * them with the same recurrence while it records directions.
  * sw_search_affine_host: the same computation in plain C++ on host memory, no GPU needed (the CPU leg). */
 typedef struct { int8_t s[256][256]; } sw_submat;
 typedef struct { const sw_submat* sub; int32_t gap_open, gap_extend; } sw_affine;
@@ -214,6 +214,43 @@ int sw_search_affine_device(sw_ctx* ctx, const char* d_query, int64_t qlen, cons
                             int64_t ntargets, const sw_affine* scoring, sw_result* d_results, void* stream);
 int sw_search_affine_host(const char* query, int64_t qlen, const char* db, const int64_t* offsets, int64_t ntargets,
                           const sw_affine* scoring, sw_result* results);
+/* The alignment of chosen hits under affine scoring (csrc/sw_align_affine.hip): Gotoh's recurrence with one direction byte per cell
+ * and a walk through its three states.  H, E, F, go, ge, s, rows i (target letters) and columns j (query letters) as above.
+ * THE CANONICAL ALIGNMENT of a target.  The walk starts at max_pos (the arg-max of sw_search_affine_device: lowest index among
+ * ties) in state H.
+ *   State H at (i, j): if H[i][j] == 0, stop -- this cell is the begin corner and not part of the alignment.  Else if
+ *     H[i][j] == H[i-1][j-1] + s[q[j-1]][t[i-1]]: emit M, go to H at (i-1, j-1).  Else if H[i][j] == E[i][j]: go to state E at the
+ *     same cell, nothing emitted.  Else go to state F at the same cell.  (Tie order diagonal, E, F: the reference's
+ *     DIAGONAL > UP > LEFT, serial_smithW.c:221-234.)
+ *   State E at (i, j), a gap that consumes target letters: emit D; if E[i][j] == H[i-1][j] + go + ge (opening wins a tie against
+ *     extending) go to H at (i-1, j), otherwise stay in E at (i-1, j).
+ *   State F at (i, j), a gap that consumes query letters: emit I; if F[i][j] == H[i][j-1] + go + ge go to H at (i, j-1), otherwise
+ *     stay in F at (i, j-1).
+ * Ops are reported in alignment order, begin to end, one byte each: 'M' (a letter pair, match or mismatch), 'I', 'D'.  With the
+ * begin corner (i0, j0) and the end cell (i1, j1) the alignment covers query [j0, j1) and target [i0, i1), 0-based, half open:
+ * sw_alignment = {max_pos, max_score, q_begin = j0, t_begin = i0, q_end = j1, t_end = i1, nops}.  A target with nothing positive
+ * gives the empty alignment: all zeros, no ops.  The rule makes the alignment unique.  With go = 0 and the table of sw_submat_match
+ * the cells visited in state H are backtrack()'s path (serial_smithW.c:262-277) for {match, mismatch, ge}, in the same order.
+ *   hits   : HOST, nhits target indices in [0, ntargets), in any order, duplicates allowed; copied before the call returns
+ *   d_aln  : device, nhits sw_alignment in the order of `hits`; max_pos / max_score of hit h are what sw_search_affine_device
+ *            reports for target hits[h] (the call re-fills every hit in full and finds the arg-max itself: it does not take the
+ *            search's results, and stays asynchronous on `stream` without a host round trip)
+ *   d_ops  : device, nhits rows of ops_cap bytes: the ops of hit h at d_ops + h * ops_cap, left-justified.  nops is always the true
+ *            length; where nops > ops_cap that hit's op bytes are unspecified, and nothing is written outside its own row.
+ *            ops_cap >= qlen + longest hit always suffices.  d_ops may be NULL with ops_cap 0: coordinates only.
+ * nhits == 0 returns SW_OK and launches nothing.  SW_EINVAL: the argument errors of sw_search_affine_device, an index out of range,
+ * NULL hits with nhits > 0, NULL d_aln, a negative ops_cap (or NULL d_ops with ops_cap > 0).  The directions take one byte per cell
+ * of a re-filled matrix (longest hit x padded query length per slot) in a per-context workspace that the option
+ * "align_workspace_mib" bounds (default 1024): a hit whose own matrix does not fit is SW_EINVAL with a message that names the
+ * option; more hits than slots fit are processed slot after slot inside the one call.
+ * sw_align_affine_host: the same in plain C++ on host memory (the CPU leg; no workspace bound). */
+typedef struct { int64_t max_pos, max_score, q_begin, t_begin, q_end, t_end, nops; } sw_alignment;
+int sw_align_affine_device(sw_ctx* ctx, const char* d_query, int64_t qlen, const char* d_db, const int64_t* offsets,
+                           int64_t ntargets, const int64_t* hits, int64_t nhits, const sw_affine* scoring,
+                           sw_alignment* d_aln, char* d_ops, int64_t ops_cap, void* stream);
+int sw_align_affine_host(const char* query, int64_t qlen, const char* db, const int64_t* offsets, int64_t ntargets,
+                         const int64_t* hits, int64_t nhits, const sw_affine* scoring,
+                         sw_alignment* aln, char* ops, int64_t ops_cap);
 /* Tables.  sw_submat_match: s[x][y] = x == y ? match : mismatch (matchMissmatchScore, serial_smithW.c:251-256; both must fit int8:
  * the builder returns nothing, so it clamps them to -128..127 -- a caller that takes them from a user checks the range first, as
  * smithW and the Python wrapper do, which refuse such scores).  sw_submat_from_letters: `scores` is n x n, row = query letter, over the n bytes of
@@ -387,7 +424,9 @@ int sw_synchronize(sw_ctx* ctx, void* stream);   /* waits for `stream`; reports 
  * scanned the alphabet for itself, 0: the shared scan behind a grid barrier), "xcd_round_robin" (1: sw_create saw
  * workgroup i of a launch on XCD i % 8), "last_batch_kernel" (0: the last batch ran on the fall-back, 1: one pair per wave, 2: two pairs per
  * wave on packed lanes), "last_search_kernel" (the last search: 2 * (columns per lane / 8) + 1 for the wide profile), "last_search_affine_kernel"
- * (the last affine search: columns per lane / 8) and "last_search_affine_grid" (its workgroups). */
+ * (the last affine search: columns per lane / 8) and "last_search_affine_grid" (its workgroups), "last_align_affine_kernel" (the
+ * last sw_align_affine_device call: columns per lane / 8) and "last_align_affine_slots" (its direction matrices, one per wave at
+ * work); "align_workspace_mib" (settable, default 1024) bounds the direction workspace of that call. */
 int sw_set_option(sw_ctx* ctx, const char* name, int64_t value);
 int64_t sw_get_option(sw_ctx* ctx, const char* name);
 

@@ -6,6 +6,9 @@
   (d) the (b) data through sw_batch_device, which takes the single-pair path for more than 8 letters
   (a) and (b) also through sw_search_affine_device (random symmetric 24-letter matrix, gap_open -11, gap_extend -1): *_affine_* beside
   the linear figures of the same database in the same process, and their ratio
+  (a) then aligns the top 100 and the top 1000 hits of the affine search (sw_align_affine_device): a_align<K>_ms per call, the
+  re-filled cells per second, the walk's share of the waves' time (the kernel's own tick stamps, option "debug_buf") beside the
+  affine search call's time; --only-a stops after (a)
 GCUPS = query letters x target letters / time of the call (torch events, median of --reps after --warmup)."""
 import argparse
 import importlib
@@ -47,6 +50,7 @@ def main():
     ap.add_argument("--pairs-d", type=int, default=4096, help="pairs of the (b) data sent through sw_batch_device (its slow path)")
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--only-a", action="store_true", help="data set (a) only: linear search, affine search, alignment of its top hits")
     args = ap.parse_args()
     rng = np.random.default_rng(2026)
     eng = swamd.Engine(0)
@@ -80,6 +84,33 @@ def main():
         out[f"{tag}_affine_gcups"] = round(cells / ms / 1e6, 1)
         out[f"{tag}_affine_grid"] = eng.get_option("last_search_affine_grid")
         out[f"{tag}_affine_over_linear"] = round(out[f"{tag}_affine_gcups"] / out[f"{tag}_gcups"], 3)
+        return res
+
+    def align_legs(query, packed, offs, res, tag):
+        d_q = torch.from_numpy(query.copy()).to(dev)
+        d_db = torch.from_numpy(packed.copy()).to(dev)
+        order = swamd.top_hits(res.cpu().numpy(), 1000)
+        lens = np.diff(offs)
+        for k in (100, 1000):
+            hits = order[:k]
+            cap = len(query) + int(lens[hits].max())
+            bufs = (torch.zeros((k, 7), dtype=torch.int64, device=dev), torch.zeros((k, cap), dtype=torch.uint8, device=dev))
+            ms = timed(lambda: eng.align_affine_device(d_q, len(query), d_db, offs, sub, -11, -1, hits, ops_cap=cap, out=bufs), args.warmup, args.reps)
+            cells = float(len(query)) * float(lens[hits].sum())
+            out[f"{tag}_align{k}_ms"] = round(ms, 3)
+            out[f"{tag}_align{k}_gcups"] = round(cells / ms / 1e6, 2)
+            out[f"{tag}_align{k}_cells"] = int(cells)
+            out[f"{tag}_align{k}_slots"] = eng.get_option("last_align_affine_slots")
+            out[f"{tag}_align{k}_ops_mean"] = round(float(bufs[0][:, 6].double().mean().item()), 1)
+            # one more call with the kernel's tick stamps on: time in fills and in walks, summed over the waves
+            stamps = torch.zeros(2, dtype=torch.int64, device=dev)
+            eng.set_option("debug_buf", stamps.data_ptr())
+            eng.align_affine_device(d_q, len(query), d_db, offs, sub, -11, -1, hits, ops_cap=cap, out=bufs)
+            torch.cuda.synchronize()
+            eng.set_option("debug_buf", 0)
+            fill_t, walk_t = (float(x) for x in stamps.cpu().numpy())
+            out[f"{tag}_align{k}_walk_share"] = round(walk_t / max(1.0, fill_t + walk_t), 4)
+        out[f"{tag}_align100_over_affine_search_ms"] = round(out[f"{tag}_align100_ms"] / out[f"{tag}_affine_ms"], 4)
 
     def batch_gcups(query, b_all, tag, reps):
         npairs, n = b_all.shape
@@ -100,7 +131,11 @@ def main():
     out["a_len_median"] = int(np.median(lens))
     out["a_len_max"] = int(lens.max())
     search_gcups(q, packed, offs, "a")
-    affine_gcups(q, packed, offs, "a")
+    align_legs(q, packed, offs, affine_gcups(q, packed, offs, "a"), "a")
+    if args.only_a:
+        eng.close()
+        print(json.dumps(out))
+        return
     # (b) the same cells, equal lengths
     L = int(round(offs[-1] / args.targets))
     offs_b = np.arange(args.targets + 1, dtype=np.int64) * L

@@ -64,6 +64,8 @@ ABI = {
     "sw_search_device": (_i32, [_vp, _vp, _i64, _vp, _vp, _i64, ctypes.POINTER(_Scores), _vp, _vp]),
     "sw_search_affine_device": (_i32, [_vp, _vp, _i64, _vp, _vp, _i64, ctypes.POINTER(_Affine), _vp, _vp]),
     "sw_search_affine_host": (_i32, [_vp, _i64, _vp, _vp, _i64, ctypes.POINTER(_Affine), _vp]),
+    "sw_align_affine_device": (_i32, [_vp, _vp, _i64, _vp, _vp, _i64, _vp, _i64, ctypes.POINTER(_Affine), _vp, _vp, _i64, _vp]),
+    "sw_align_affine_host": (_i32, [_vp, _i64, _vp, _vp, _i64, _vp, _i64, ctypes.POINTER(_Affine), _vp, _vp, _i64]),
     "sw_submat_match": (None, [_i32, _i32, _vp]),
     "sw_submat_from_letters": (_i32, [_vp, _i32, _vp, _i32, _vp]),
     "sw_read_submat": (_i32, [ctypes.c_char_p, _vp]),
@@ -225,6 +227,54 @@ def search_affine_host(query, targets, submat, gap_open: int, gap_extend: int, t
     _check(lib().sw_search_affine_host(q.ctypes.data, len(q), db.ctypes.data, offs.ctypes.data, ntargets, ctypes.byref(sc), res.ctypes.data))
     out = res[:ntargets]
     return (out, top_hits(out, top)) if top is not None else out
+
+
+def _ops_list(aln, ops, cap):
+    """The ops rows of an alignment call as a list of bytes, each cut to its nops."""
+    return [ops[h, :aln[h, 6]].tobytes() if aln[h, 6] <= cap else b"" for h in range(len(aln))]
+
+
+def _hits_and_cap(offs, hits, qlen):
+    hits = np.ascontiguousarray(hits, np.int64).reshape(-1)
+    ntargets = len(offs) - 1
+    inside = hits[(hits >= 0) & (hits < ntargets)]
+    longest = int(np.diff(offs)[inside].max()) if len(inside) else 0
+    return hits, max(1, qlen + longest)
+
+
+def align_affine_host(query, targets, submat, gap_open: int, gap_extend: int, hits):
+    """sw_align_affine_host: the alignments of the targets `hits` in plain C++ on the host (no GPU).  Arguments and results as
+    Engine.align_affine."""
+    q = np.ascontiguousarray(_as_seq(query))
+    packed, offs = _pack_targets(targets)
+    db = packed if len(packed) else np.zeros(1, np.uint8)
+    hits, cap = _hits_and_cap(offs, hits, len(q))
+    aln = np.zeros((max(1, len(hits)), 7), np.int64)
+    ops = np.zeros((max(1, len(hits)), cap), np.uint8)
+    sub, sc = _affine(submat, gap_open, gap_extend)
+    _check(lib().sw_align_affine_host(q.ctypes.data, len(q), db.ctypes.data, offs.ctypes.data, len(offs) - 1, hits.ctypes.data, len(hits),
+                                      ctypes.byref(sc), aln.ctypes.data, ops.ctypes.data, cap))
+    aln = aln[:len(hits)]
+    return aln, _ops_list(aln, ops, cap)
+
+
+def format_alignment(query, target, aln_row, ops):
+    """The three display lines of an alignment (an sw_alignment row and its ops): the query with '-' where the target has letters
+    of its own, a midline ('|' under equal letters, a space otherwise), the target with '-'."""
+    q, t = _as_seq(query), _as_seq(target)
+    j, i = int(aln_row[2]), int(aln_row[3])
+    top, mid, bot = [], [], []
+    for op in bytes(ops):
+        if op == ord("M"):
+            top.append(chr(q[j])); bot.append(chr(t[i])); mid.append("|" if q[j] == t[i] else " ")
+            j += 1; i += 1
+        elif op == ord("I"):
+            top.append(chr(q[j])); bot.append("-"); mid.append(" ")
+            j += 1
+        else:
+            top.append("-"); bot.append(chr(t[i])); mid.append(" ")
+            i += 1
+    return "".join(top), "".join(mid), "".join(bot)
 
 
 def top_hits(results, k: int):
@@ -565,6 +615,40 @@ class Engine:
         _check(lib().sw_search_affine_device(self._h, d_query.data_ptr(), qlen, d_db.data_ptr(), offs.ctypes.data, ntargets, ctypes.byref(sc),
                                              res.data_ptr(), self._stream()))
         return res[:ntargets]
+
+    def align_affine(self, query, targets, submat, gap_open: int, gap_extend: int, hits):
+        """The alignments of the targets `hits` (indices, any order, duplicates allowed) under affine scoring
+        (sw_align_affine_device): every hit is re-filled with direction bytes and walked by the canonical rule of include/swhip.h.
+        Returns (aln, ops): aln an (nhits, 7) int64 numpy array (max_pos, max_score, q_begin, t_begin, q_end, t_end, nops), ops a
+        list of bytes over b"MID" in alignment order."""
+        t = self.torch
+        q = _as_seq(query)
+        packed, offs = _pack_targets(targets)
+        dev = f"cuda:{self.device}"
+        d_q = t.from_numpy(q.copy()).to(dev)
+        d_db = t.from_numpy(packed.copy() if len(packed) else np.zeros(1, np.uint8)).to(dev)
+        hits, cap = _hits_and_cap(offs, hits, len(q))
+        aln, ops = self.align_affine_device(d_q, len(q), d_db, offs, submat, gap_open, gap_extend, hits, ops_cap=cap)
+        self.synchronize()
+        aln = aln.cpu().numpy()
+        return aln, _ops_list(aln, ops.cpu().numpy(), cap)
+
+    def align_affine_device(self, d_query, qlen: int, d_db, offsets, submat, gap_open: int, gap_extend: int, hits, ops_cap: int = 0, out=None):
+        """sw_align_affine_device on device-resident query / packed targets (torch uint8 tensors), host int64 offsets, host hits and
+        a host table; asynchronous on torch's current stream.  Returns (aln, ops): the (nhits, 7) int64 tensor and the
+        (nhits, ops_cap) uint8 tensor (None with ops_cap = 0: coordinates only); out = (aln, ops) reuses given tensors."""
+        t = self.torch
+        offs = np.ascontiguousarray(offsets, np.int64).reshape(-1)
+        if len(offs) == 0:
+            offs = np.zeros(1, np.int64)
+        hits = np.ascontiguousarray(hits, np.int64).reshape(-1)
+        nhits, dev = len(hits), f"cuda:{self.device}"
+        aln, ops = out if out is not None else (t.zeros((max(1, nhits), 7), dtype=t.int64, device=dev),
+                                                t.zeros((max(1, nhits), ops_cap), dtype=t.uint8, device=dev) if ops_cap > 0 else None)
+        sub, sc = _affine(submat, gap_open, gap_extend)
+        _check(lib().sw_align_affine_device(self._h, d_query.data_ptr(), qlen, d_db.data_ptr(), offs.ctypes.data, len(offs) - 1, hits.ctypes.data, nhits,
+                                            ctypes.byref(sc), aln.data_ptr(), ops.data_ptr() if ops is not None else None, ops_cap, self._stream()))
+        return aln[:nhits], (ops[:nhits] if ops is not None else None)
 
     def traceback(self, out: Fill, max_pos: int | None = None, want_path: bool = True):
         """backtrack() on the device P (negates the path in place). Returns the path indices."""

@@ -7,6 +7,13 @@
 //     ... --matrix FILE --gap-open O --gap-extend E   substitution matrix (NCBI text format) and affine gaps (sw_search_affine_device): a gap of k
 //                              letters scores O + k E; without --matrix the table is match / mismatch of --scores (signed bytes),
 //                              without --gap-extend E = the gap of --scores; --gap-extend alone (O = 0) is the linear search with gap E
+//     ... --align             every printed hit is followed by its alignment (sw_align_affine_device; the canonical alignment of swhip.h), four lines:
+//                                "align\t<q_begin>\t<q_end>\t<t_begin>\t<t_end>\t<nops>"   query [q_begin, q_end) against target [t_begin, t_end), 0-based, half open
+//                                "Q <query letters, '-' where the target has letters of its own>"
+//                                "  <'|' under equal letters, a space otherwise>"
+//                                "T <target letters, '-' where the query has letters of its own>"
+//                              on a linear search (no --matrix / --gap-open) the alignment is that of the table match / mismatch of --scores (signed
+//                              bytes) with gap_open 0 and the gap of --scores: the reference's backtrack() path
 // Extra flags: --seed N  --dump | --dump-labels (the header-row printers of omp_smithW.c)  --h64  --no-backtrack  --scores M X G  --record-a I  --record-b J
 //   --gpus N | --devices 0,1,..   ONE matrix over several GPUs (row bands, sw_multi_*; an id may repeat)  --p8  int8 P
 // The DP fill runs on the GPU through the C-ABI (include/swhip.h); stdout keeps the two
@@ -90,7 +97,7 @@ static bool parse_int(const char* flag, const char* text, int* out) {
     *out = (int)v;
     return true;
 }
-static int search_main(const char* qpath, long long rec, const char* dbpath, long long top, const sw_scores& sc, const AffineArgs& af) {
+static int search_main(const char* qpath, long long rec, const char* dbpath, long long top, const sw_scores& sc, const AffineArgs& af, bool align) {
     int64_t qlen = 0, nrec = 0, total = 0;
     CHECK(sw_read_fasta(qpath, rec, nullptr, 0, &qlen));
     std::vector<char> q((size_t)qlen + 1);
@@ -107,9 +114,9 @@ static int search_main(const char* qpath, long long rec, const char* dbpath, lon
     CHECK(sw_device_malloc(ctx, (size_t)(nrec > 0 ? nrec : 1) * sizeof(sw_result), &d_res));
     CHECK(sw_memcpy_h2d(ctx, d_q, q.data(), (size_t)qlen));
     if (total) CHECK(sw_memcpy_h2d(ctx, d_db, db.data(), (size_t)total));
-    std::vector<sw_submat> sub(af.on ? 1 : 0);
+    std::vector<sw_submat> sub(af.on || align ? 1 : 0);
     sw_affine aff = {nullptr, af.has_open ? af.open : 0, af.has_extend ? af.extend : sc.gap};
-    if (af.on) {
+    if (af.on || align) {
         if (af.matrix) CHECK(sw_read_submat(af.matrix, sub.data()));
         else sw_submat_match(sc.match, sc.mismatch, sub.data());
         aff.sub = sub.data();
@@ -125,11 +132,41 @@ static int search_main(const char* qpath, long long rec, const char* dbpath, lon
     for (int64_t k = 0; k < nrec; ++k) order[(size_t)k] = k;
     std::stable_sort(order.begin(), order.end(), [&](int64_t x, int64_t y) { return res[(size_t)x].max_score > res[(size_t)y].max_score; });
     const long long K = std::max(0ll, std::min(top, (long long)nrec));
+    // --align: the K hits re-filled with directions and walked on the device, ops of at most query + longest hit letters each
+    std::vector<sw_alignment> aln((size_t)(align ? K : 0));
+    std::vector<char> ops;
+    int64_t ops_cap = 0;
+    if (align && K > 0) {
+        for (long long i = 0; i < K; ++i) ops_cap = std::max(ops_cap, qlen + offs[(size_t)order[(size_t)i] + 1] - offs[(size_t)order[(size_t)i]]);
+        void *d_aln = nullptr, *d_ops = nullptr;
+        CHECK(sw_device_malloc(ctx, (size_t)K * sizeof(sw_alignment), &d_aln));
+        CHECK(sw_device_malloc(ctx, (size_t)K * (size_t)ops_cap, &d_ops));
+        CHECK(sw_align_affine_device(ctx, (const char*)d_q, qlen, (const char*)d_db, offs.data(), nrec, order.data(), K, &aff, (sw_alignment*)d_aln, (char*)d_ops,
+                                     ops_cap, nullptr));
+        CHECK(sw_synchronize(ctx, nullptr));
+        ops.resize((size_t)K * (size_t)ops_cap);
+        CHECK(sw_memcpy_d2h(ctx, aln.data(), d_aln, (size_t)K * sizeof(sw_alignment)));
+        CHECK(sw_memcpy_d2h(ctx, ops.data(), d_ops, ops.size()));
+        (void)sw_device_free(ctx, d_aln); (void)sw_device_free(ctx, d_ops);
+    }
     printf("# query %lld letters, %lld targets, %lld letters; rank\trecord\tscore\ttarget_end\tquery_end\n", (long long)qlen, (long long)nrec, (long long)total);
     for (long long i = 0; i < K; ++i) {
         const sw_result& r = res[(size_t)order[(size_t)i]];
         const long long te = r.max_pos / (qlen + 1), qe = r.max_pos % (qlen + 1);
         printf("%lld\t%lld\t%lld\t%lld\t%lld\n", i + 1, (long long)order[(size_t)i], (long long)r.max_score, te, qe);
+        if (!align) continue;
+        const sw_alignment& a = aln[(size_t)i];
+        printf("align\t%lld\t%lld\t%lld\t%lld\t%lld\n", (long long)a.q_begin, (long long)a.q_end, (long long)a.t_begin, (long long)a.t_end, (long long)a.nops);
+        const char* t = db.data() + offs[(size_t)order[(size_t)i]];
+        const char* op = ops.data() + (size_t)i * (size_t)ops_cap;
+        std::string lq, lm, lt;
+        int64_t qi = a.q_begin, ti = a.t_begin;
+        for (int64_t k = 0; k < a.nops; ++k) {
+            if (op[k] == 'M') { lq += q[(size_t)qi]; lt += t[ti]; lm += q[(size_t)qi] == t[ti] ? '|' : ' '; ++qi; ++ti; }
+            else if (op[k] == 'I') { lq += q[(size_t)qi]; lt += '-'; lm += ' '; ++qi; }
+            else { lq += '-'; lt += t[ti]; lm += ' '; ++ti; }
+        }
+        printf("Q %s\n  %s\nT %s\n", lq.c_str(), lm.c_str(), lt.c_str());
     }
     const double cells = (double)qlen * (double)total;
     printf("\nElapsed time for database search: %f (%.1f GCUPS)\n\n", t1 - t0, t1 > t0 ? cells / (t1 - t0) / 1e9 : 0.0);
@@ -148,6 +185,7 @@ int main(int argc, char** argv) {
     const char *search_q = nullptr, *search_db = nullptr;
     long long top = 10;
     AffineArgs af;
+    bool align = false;
     sw_scores sc = {3, -3, -2};
     int npos = 0;
     for (int ai = 1; ai < argc; ++ai) {
@@ -170,11 +208,12 @@ int main(int argc, char** argv) {
         else if (f == "--matrix" && ai + 1 < argc) { af.matrix = argv[++ai]; af.on = true; }
         else if (f == "--gap-open" && ai + 1 < argc) { if (!parse_int("--gap-open", argv[++ai], &af.open)) return 2; af.has_open = af.on = true; }
         else if (f == "--gap-extend" && ai + 1 < argc) { if (!parse_int("--gap-extend", argv[++ai], &af.extend)) return 2; af.has_extend = true; }
+        else if (f == "--align") align = true;
         else if (f == "--record-a" && ai + 1 < argc) rec_a = strtoll(argv[++ai], nullptr, 10);
         else if (f == "--record-b" && ai + 1 < argc) rec_b = strtoll(argv[++ai], nullptr, 10);
         else if (f == "--seed" && ai + 1 < argc) seed = (unsigned)strtoul(argv[++ai], nullptr, 10);
         else if (f == "--scores" && ai + 3 < argc) { sc.match = atoi(argv[++ai]); sc.mismatch = atoi(argv[++ai]); sc.gap = atoi(argv[++ai]); }
-        else { fprintf(stderr, "usage: smithW [<cols> <rows> | --fasta A.fa B.fa [--record-a I] [--record-b J] | --search QUERY.fa DB.fa [--record-a I] [--top K] [--matrix FILE] [--gap-open O] [--gap-extend E]] [--seed N] [--dump | --dump-labels] [--h64] [--no-backtrack] [--scores M X G] [--gpus N | --devices 0,1,..] [--p8]\n"); return 2; }
+        else { fprintf(stderr, "usage: smithW [<cols> <rows> | --fasta A.fa B.fa [--record-a I] [--record-b J] | --search QUERY.fa DB.fa [--record-a I] [--top K] [--matrix FILE] [--gap-open O] [--gap-extend E] [--align]] [--seed N] [--dump | --dump-labels] [--h64] [--no-backtrack] [--scores M X G] [--gpus N | --devices 0,1,..] [--p8]\n"); return 2; }
     }
     if (npos == 1) { fprintf(stderr, "smithW: <cols> needs <rows>\n"); return 2; }
     if (search_q) {
@@ -183,8 +222,13 @@ int main(int argc, char** argv) {
             return 2;
         }
         if (af.has_extend && !af.on) sc.gap = af.extend;   // --gap-extend alone: gap_open = 0 is the linear recurrence, and its kernel is the cheaper one
-        return search_main(search_q, rec_a, search_db, top, sc, af);
+        if (align && !af.on && (sc.match < -128 || sc.match > 127 || sc.mismatch < -128 || sc.mismatch > 127)) {
+            fprintf(stderr, "smithW: --align on a linear search needs --scores M X within -128..127 (a table of signed bytes), got %d %d\n", sc.match, sc.mismatch);
+            return 2;
+        }
+        return search_main(search_q, rec_a, search_db, top, sc, af, align);
     }
+    if (align) { fprintf(stderr, "smithW: --align goes with --search\n"); return 2; }
     if (af.on || af.has_extend) { fprintf(stderr, "smithW: --matrix / --gap-open / --gap-extend go with --search\n"); return 2; }
     if (fasta_a) {
         int64_t la = 0, lb = 0;

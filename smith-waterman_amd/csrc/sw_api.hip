@@ -18,6 +18,8 @@ namespace swh {
 void set_err(const char* fmt, ...);
 int check_search_affine(const char* who, int64_t qlen, const int64_t* offsets, int64_t ntargets, const sw_affine* sc, int64_t* maxlen_out,
                         int64_t* nonempty_out);   // sw_host.cpp
+int check_align_affine(const char* who, const int64_t* offsets, int64_t ntargets, const int64_t* hits, int64_t nhits, const void* aln, const void* ops,
+                       int64_t ops_cap, int64_t* maxhit_out);   // sw_host.cpp
 }
 extern "C" int sw_place_pair_ratio(void* d_X, size_t xbytes, void* d_Y, size_t ybytes, float* ratio, float* ms_together);   // sw_place.hip
 using swh::set_err;
@@ -100,6 +102,12 @@ struct sw_ctx {
     int64_t last_search_affine_kernel = 0;  // its kernel: index in kSearchAffine (swp::search_affine_kernel_index)
     int search_affine_per_cu[swp::kSearchAffineKernels] = {};   // occupancy of every sw_search_affine_wave instantiation at 256 threads ...
     bool search_affine_per_cu_known = false;                    // ... queried at the first affine search
+    // alignment of hits (sw_align_affine_device): the search's workspaces plus one direction matrix per wave at work
+    unsigned char* d_adir = nullptr; size_t adir_cap = 0;
+    int64_t opt_align_workspace_mib = 1024;
+    int64_t last_align_affine_kernel = 0, last_align_affine_slots = 0;
+    int align_affine_per_cu[swp::kAlignAffineKernels] = {};     // occupancy of every sw_align_affine_wave instantiation at 256 threads ...
+    bool align_affine_per_cu_known = false;                     // ... queried at the first call
     bool xcd_round_robin = false;       // sw_xcc_probe saw workgroup i on XCD i % 8 (8 XCDs of 32 CUs)
     std::map<void*, void*> out_base;    // sw_alloc_outputs: pointer handed out -> allocation to free
     std::map<void*, float> pair_ratio;  // ... P handed out -> the store probe's ratio of its pair (~1.4: two classes of the HBM, ~2: one)
@@ -171,6 +179,7 @@ void sw_destroy(sw_ctx* c) {
     if (c->d_sctr) (void)hipFree(c->d_sctr);
     if (c->d_submat) (void)hipFree(c->d_submat);
     if (c->h_submat) (void)hipHostFree(c->h_submat);
+    if (c->d_adir) (void)hipFree(c->d_adir);
     delete c;
 }
 
@@ -196,6 +205,11 @@ int sw_set_option(sw_ctx* c, const char* name, int64_t v) {
     if (!strcmp(name, "debug_buf")) { c->opt_dbg_ptr = v; return SW_OK; }
     if (!strcmp(name, "batch_lds")) { c->opt_batch_lds = v < 0 ? 0 : v; return SW_OK; }
     if (!strcmp(name, "band_wait_ms")) { c->opt_band_wait_ms = v > 0 ? v : 20000; return SW_OK; }
+    if (!strcmp(name, "align_workspace_mib")) {
+        if (v < 1 || v > (1ll << 20)) { set_err("align_workspace_mib must be 1..2^20"); return SW_EINVAL; }
+        c->opt_align_workspace_mib = v;
+        return SW_OK;
+    }
     if (!strcmp(name, "placement_budget_ms")) { c->opt_place_budget_ms = v > 0 ? v : 1500; return SW_OK; }
     if (!strcmp(name, "placement_hold_gib")) { c->opt_place_hold_gib = v < 0 ? 0 : (v > 128 ? 128 : v); return SW_OK; }
     if (!strcmp(name, "probe_foreign_pairs")) { c->opt.probe_foreign_pairs = v ? 1 : 0; return SW_OK; }
@@ -243,6 +257,9 @@ int64_t sw_get_option(sw_ctx* c, const char* name) {
     if (!strcmp(name, "last_search_kernel")) return c->last_search_kernel;
     if (!strcmp(name, "last_search_affine_grid")) return c->last_search_affine_grid;
     if (!strcmp(name, "last_search_affine_kernel")) return c->last_search_affine_kernel;
+    if (!strcmp(name, "last_align_affine_kernel")) return c->last_align_affine_kernel;
+    if (!strcmp(name, "last_align_affine_slots")) return c->last_align_affine_slots;
+    if (!strcmp(name, "align_workspace_mib")) return c->opt_align_workspace_mib;
     if (!strcmp(name, "placement_budget_ms")) return c->opt_place_budget_ms;
     if (!strcmp(name, "placement_hold_gib")) return c->opt_place_hold_gib;
     if (!strcmp(name, "probe_foreign_pairs")) return c->opt.probe_foreign_pairs;
@@ -925,6 +942,84 @@ int sw_search_affine_device(sw_ctx* c, const char* d_query, int64_t qlen, const 
     hipLaunchKernelGGL(kSearchAffine[plan.kernel].k, dim3((unsigned)plan.grid), dim3(256), 0, stream, sp);
     HIP_TRY(hipGetLastError());
     c->last_search_affine_grid = plan.grid; c->last_search_affine_kernel = plan.kernel;
+    return SW_OK;
+}
+
+// the instantiations of the alignment kernel (sw_align_affine.hip), picked by swp::plan_align_affine
+using AlignAffineKernel = void (*)(swk::AlignAffineParams);
+static constexpr Indexed<AlignAffineKernel> kAlignAffine[] = {
+    {swp::align_affine_kernel_index(4), swk::sw_align_affine_wave<4>},
+    {swp::align_affine_kernel_index(8), swk::sw_align_affine_wave<8>},
+    {swp::align_affine_kernel_index(16), swk::sw_align_affine_wave<16>},
+};
+static_assert(std::size(kAlignAffine) == swp::kAlignAffineKernels && at_their_indices(kAlignAffine));
+
+// The alignment of chosen hits under affine scoring (csrc/sw_align_affine.hip).  The shape of sw_search_affine_device: no host round
+// trip, the order of the hits and the table are uploaded from pinned copies, the profile is built on the device; the plan decides.
+int sw_align_affine_device(sw_ctx* c, const char* d_query, int64_t qlen, const char* d_db, const int64_t* offsets, int64_t ntargets,
+                           const int64_t* hits, int64_t nhits, const sw_affine* scoring, sw_alignment* d_aln, char* d_ops, int64_t ops_cap,
+                           void* stream_) {
+    if (!c || !d_query || !d_db || !offsets || !scoring || ntargets < 0) {
+        set_err("sw_align_affine_device: NULL pointer or negative target count");
+        return SW_EINVAL;
+    }
+    int64_t maxlen = 0, nonempty = 0, maxhit = 0;
+    if (int rc = swh::check_search_affine("sw_align_affine_device", qlen, offsets, ntargets, scoring, &maxlen, &nonempty)) return rc;
+    if (int rc = swh::check_align_affine("sw_align_affine_device", offsets, ntargets, hits, nhits, d_aln, d_ops, ops_cap, &maxhit)) return rc;
+    if (nhits == 0) return SW_OK;
+    hipStream_t stream = (hipStream_t)stream_;
+    HIP_TRY(hipSetDevice(c->device));
+    DevOrder order(c, stream, false);
+    if (order.rc) return order.rc;
+    if (!c->align_affine_per_cu_known) {
+        for (int k = 0; k < swp::kAlignAffineKernels; ++k)
+            HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&c->align_affine_per_cu[k], kAlignAffine[k].k, 256, 0));
+        c->align_affine_per_cu_known = true;
+    }
+    swp::AlignAffineJob aj;
+    aj.qlen = qlen; aj.maxhit = maxhit; aj.nhits = nhits; aj.num_cus = c->num_cus; aj.budget_bytes = c->opt_align_workspace_mib << 20;
+    std::copy(std::begin(c->align_affine_per_cu), std::end(c->align_affine_per_cu), aj.per_cu);
+    const swp::AlignAffinePlan plan = swp::plan_align_affine(aj);
+    if (!plan.fits) {
+        set_err("sw_align_affine_device: the direction matrix of the longest hit (%lld rows x %lld bytes = %lld bytes) does not fit align_workspace_mib = %lld "
+                "(or the 2 GiB a slot may take)", (long long)maxhit, (long long)plan.qpad, (long long)plan.slot_bytes, (long long)c->opt_align_workspace_mib);
+        return SW_EINVAL;
+    }
+    if (c->align_affine_per_cu[plan.kernel] < 1) { set_err("the alignment kernel does not fit a CU on this device"); return SW_EDEVICE; }
+    // the order of the hits and the table are uploaded from pinned copies: the previous uploads have to have left them
+    if (c->sitems_ev) HIP_TRY(hipEventSynchronize(c->sitems_ev));
+    else HIP_TRY(hipEventCreateWithFlags(&c->sitems_ev, hipEventDisableTiming));
+    bool fresh = false;
+    if (int rc = grow_schedule(c, (size_t)nhits, stream)) return rc;
+    if (int rc = grow_workspace((void**)&c->d_sprof, c->sprof_cap, plan.prof_need, 1, 0, stream, fresh)) return rc;
+    if (int rc = grow_workspace((void**)&c->d_sbnd, c->sbnd_cap, plan.bnd_need, 4, 0, stream, fresh)) return rc;
+    if (int rc = grow_workspace((void**)&c->d_adir, c->adir_cap, plan.dir_need, 1, 0, stream, fresh)) return rc;
+    if (!c->d_sctr) HIP_TRY(hipMalloc((void**)&c->d_sctr, 64));
+    if (!c->d_submat) HIP_TRY(hipMalloc((void**)&c->d_submat, sizeof(sw_submat)));
+    if (!c->h_submat) HIP_TRY(hipHostMalloc((void**)&c->h_submat, sizeof(sw_submat), 0));
+    swp::align_schedule(offsets, hits, nhits, c->h_sitems);
+    memcpy(c->h_submat, scoring->sub, sizeof(sw_submat));
+    HIP_TRY(hipMemcpyAsync(c->d_sitems, c->h_sitems, (size_t)nhits * sizeof(swk::SearchItem), hipMemcpyHostToDevice, stream));
+    HIP_TRY(hipMemcpyAsync(c->d_submat, c->h_submat, sizeof(sw_submat), hipMemcpyHostToDevice, stream));
+    HIP_TRY(hipEventRecord(c->sitems_ev, stream));
+    hipLaunchKernelGGL(swk::sw_search_profile_submat, dim3((unsigned)plan.prof_blocks), dim3(256), 0, stream, (const unsigned char*)d_query, qlen,
+                       plan.qpad, c->d_sprof, (const signed char*)c->d_submat);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemsetAsync(c->d_sctr, 0, 4, stream));
+    swk::AlignAffineParams ap;
+    memset(&ap, 0, sizeof ap);
+    ap.db = (const unsigned char*)d_db;
+    ap.items = c->d_sitems; ap.nitems = nhits;
+    ap.prof = c->d_sprof; ap.qpad = plan.qpad; ap.qlen = qlen;
+    ap.ge = scoring->gap_extend; ap.goe = scoring->gap_open + scoring->gap_extend;
+    ap.bnd = plan.bnd_per ? c->d_sbnd : nullptr; ap.bnd_per = plan.bnd_per;
+    ap.counter = c->d_sctr;
+    ap.dir = c->d_adir; ap.slot_bytes = plan.slot_bytes; ap.nslots = plan.slots;
+    ap.aln = d_aln; ap.ops = d_ops; ap.ops_cap = ops_cap;
+    ap.stamps = (unsigned long long*)(uintptr_t)c->opt_dbg_ptr;
+    hipLaunchKernelGGL(kAlignAffine[plan.kernel].k, dim3((unsigned)plan.grid), dim3(256), 0, stream, ap);
+    HIP_TRY(hipGetLastError());
+    c->last_align_affine_kernel = plan.kernel; c->last_align_affine_slots = plan.slots;
     return SW_OK;
 }
 

@@ -83,6 +83,23 @@ int check_search_affine(const char* who, int64_t qlen, const int64_t* offsets, i
     return SW_OK;
 }
 
+// What sw_align_affine_device / _host check beyond check_search_affine (include/swhip.h); reports the longest hit.
+int check_align_affine(const char* who, const int64_t* offsets, int64_t ntargets, const int64_t* hits, int64_t nhits, const void* aln, const void* ops,
+                       int64_t ops_cap, int64_t* maxhit_out) {
+    if (nhits < 0) { set_err("%s: negative hit count", who); return SW_EINVAL; }
+    if (nhits > 0 && !hits) { set_err("%s: hits is NULL with %lld hits", who, (long long)nhits); return SW_EINVAL; }
+    if (!aln) { set_err("%s: the alignment array is NULL", who); return SW_EINVAL; }
+    if (ops_cap < 0) { set_err("%s: ops_cap = %lld is negative", who, (long long)ops_cap); return SW_EINVAL; }
+    if (!ops && ops_cap > 0) { set_err("%s: the ops buffer is NULL with ops_cap = %lld", who, (long long)ops_cap); return SW_EINVAL; }
+    int64_t maxhit = 0;
+    for (int64_t h = 0; h < nhits; ++h) {
+        if (hits[h] < 0 || hits[h] >= ntargets) { set_err("%s: hits[%lld] = %lld is out of range 0..%lld", who, (long long)h, (long long)hits[h], (long long)ntargets - 1); return SW_EINVAL; }
+        maxhit = std::max(maxhit, offsets[hits[h] + 1] - offsets[hits[h]]);
+    }
+    *maxhit_out = maxhit;
+    return SW_OK;
+}
+
 inline char letter(int v) {  // serial_smithW.c:339-346
     switch (v) { case 0: return 'A'; case 2: return 'C'; case 3: return 'G'; default: return 'T'; }
 }
@@ -377,6 +394,73 @@ int sw_search_affine_host(const char* query, int64_t qlen, const char* db, const
             }
         }
         results[k] = sw_result{best_pos, best, 0};
+    }
+    return SW_OK;
+}
+
+// The CPU leg of sw_align_affine_device: the same recurrence with one direction byte per cell (bits 0-1: where H came from, 0 nothing
+// positive / 1 diagonal / 2 E / 3 F, compared in that order; bit 2: E[i][j] opened from H[i-1][j]; bit 3: F[i][j] opened from
+// H[i][j-1]; opening wins a tie), then the walk of the canonical alignment (include/swhip.h) from the arg-max.
+int sw_align_affine_host(const char* query, int64_t qlen, const char* db, const int64_t* offsets, int64_t ntargets, const int64_t* hits, int64_t nhits,
+                         const sw_affine* scoring, sw_alignment* aln, char* ops, int64_t ops_cap) {
+    if (!query || !db || !offsets || !scoring || ntargets < 0) { swh::set_err("sw_align_affine_host: NULL pointer or negative target count"); return SW_EINVAL; }
+    int64_t maxlen = 0, nonempty = 0, maxhit = 0;
+    if (int rc = swh::check_search_affine("sw_align_affine_host", qlen, offsets, ntargets, scoring, &maxlen, &nonempty)) return rc;
+    if (int rc = swh::check_align_affine("sw_align_affine_host", offsets, ntargets, hits, nhits, aln, ops, ops_cap, &maxhit)) return rc;
+    const int64_t go = scoring->gap_open, ge = scoring->gap_extend, M = qlen + 1;
+    constexpr int64_t NEG = -(1ll << 40);
+    std::vector<int64_t> Hrow((size_t)M), Erow((size_t)M);
+    std::vector<unsigned char> dir((size_t)(maxhit + 1) * (size_t)M);
+    std::string rev;
+    const unsigned char* q = (const unsigned char*)query;
+    for (int64_t hx = 0; hx < nhits; ++hx) {
+        const unsigned char* t = (const unsigned char*)db + offsets[hits[hx]];
+        const int64_t len = offsets[hits[hx] + 1] - offsets[hits[hx]];
+        std::fill(Hrow.begin(), Hrow.end(), 0);
+        std::fill(Erow.begin(), Erow.end(), NEG);
+        int64_t best = 0, best_pos = 0;
+        for (int64_t i = 1; i <= len; ++i) {
+            const unsigned char y = t[i - 1];
+            unsigned char* d = dir.data() + i * M;
+            int64_t diag = 0, left = 0, F = NEG;       // H[i-1][j-1], H[i][j-1], F[i][j-1]
+            for (int64_t j = 1; j <= qlen; ++j) {
+                const int64_t up = Hrow[(size_t)j];
+                const bool eopen = up + go >= Erow[(size_t)j], fopen = left + go >= F;
+                const int64_t E = std::max(Erow[(size_t)j], up + go) + ge;
+                F = std::max(F, left + go) + ge;
+                const int64_t dg = diag + scoring->sub->s[q[j - 1]][y];
+                const int64_t h = std::max<int64_t>({0, dg, E, F});
+                d[j] = (unsigned char)((h == 0 ? 0 : h == dg ? 1 : h == E ? 2 : 3) | (eopen ? 4 : 0) | (fopen ? 8 : 0));
+                Erow[(size_t)j] = E;
+                Hrow[(size_t)j] = h;
+                diag = up;
+                left = h;
+                if (h > best) { best = h; best_pos = i * M + j; }
+            }
+        }
+        int64_t i = best_pos / M, j = best_pos % M;
+        const int64_t i1 = i, j1 = j;
+        rev.clear();
+        int state = 0;                                 // 0: H, 2: E, 3: F
+        while (best > 0) {
+            const unsigned char c = dir[(size_t)(i * M + j)];
+            if (state == 0) {
+                if (i == 0 || j == 0 || (c & 3) == 0) break;
+                if ((c & 3) == 1) { rev.push_back('M'); --i; --j; }
+                else state = c & 3;
+            } else if (state == 2) {
+                rev.push_back('D');
+                if (c & 4) state = 0;
+                --i;
+            } else {
+                rev.push_back('I');
+                if (c & 8) state = 0;
+                --j;
+            }
+        }
+        const int64_t nops = (int64_t)rev.size();
+        aln[hx] = best > 0 ? sw_alignment{best_pos, best, j, i, j1, i1, nops} : sw_alignment{0, 0, 0, 0, 0, 0, 0};
+        if (ops && nops <= ops_cap) std::reverse_copy(rev.begin(), rev.end(), ops + hx * ops_cap);
     }
     return SW_OK;
 }

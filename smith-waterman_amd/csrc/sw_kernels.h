@@ -139,6 +139,23 @@ __global__ void sw_search_profile_submat(const unsigned char* q, int64_t qlen, i
 template <int C>
 __global__ void sw_search_affine_wave(SearchAffineParams p);
 
+// sw_align_affine.hip: the alignment of chosen hits under affine scoring (direction fill + walk, one wave per hit)
+struct AlignAffineParams {
+    const unsigned char* db;             // the targets back to back
+    const SearchItem* items; int64_t nitems;   // the hits, longest first: first byte in db, index in the caller's `hits`, length
+    const signed char* prof; int64_t qpad;   // SW_SEARCH_ROWS x qpad profile (sw_search_profile_submat), qpad = strips * 64 * C
+    int64_t qlen;
+    int ge, goe;                         // gap_extend, gap_open + gap_extend (both <= 0)
+    int* bnd; int64_t bnd_per;           // per slot: boundary pairs (H, F) between strips (ints), only when qlen > 64 * C
+    unsigned int* counter;               // next item (zero at launch)
+    unsigned char* dir; int64_t slot_bytes, nslots;   // per slot: the direction matrix, row stride qpad (longest hit x qpad bytes, below 2^31)
+    sw_alignment* aln;                   // caller's order
+    char* ops; int64_t ops_cap;          // caller's order, ops_cap bytes per hit; NULL: coordinates only
+    unsigned long long* stamps;          // optional timing aid: [0] += ticks in fills, [1] += ticks in walks (100 MHz clock)
+};
+template <int C>
+__global__ void sw_align_affine_wave(AlignAffineParams p);
+
 template <typename HT, int B>
 __global__ void sw_strip_scan(const unsigned char* a, const unsigned char* b, FillParams p);
 template <typename HT, int NS, int NC>

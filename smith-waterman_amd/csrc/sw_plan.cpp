@@ -389,6 +389,42 @@ SearchAffinePlan plan_search_affine(const SearchAffineJob& j) {
     return s;
 }
 
+// The direction fill carries the search kernel's state plus the packed bytes of a row; the thresholds of the search hold for the same
+// reasons (plan_search_affine).  A slot is a whole direction matrix of the longest hit, so that any hit runs in any slot; the waves
+// take hits from a counter, longest first, and a call with more hits than slots simply keeps its waves busy longer.
+constexpr int64_t kAlignSlotLimit = (1ll << 31) - 256;   // a slot is addressed through one buffer descriptor with 32-bit offsets
+
+AlignAffinePlan plan_align_affine(const AlignAffineJob& j) {
+    using swk::SW_SEARCH_ROWS;
+    AlignAffinePlan a;
+    a.C = lane_columns(j.qlen);
+    if (a.C == 16 && j.per_cu[align_affine_kernel_index(16)] < kAffineC16MinPerCu) a.C = 8;
+    a.kernel = align_affine_kernel_index(a.C);
+    a.nstrips = (j.qlen + 64 * a.C - 1) / (64 * a.C);
+    a.qpad = a.nstrips * 64 * a.C;
+    a.bnd_per = 2 * boundary_ints(a.nstrips, j.maxhit);
+    a.slot_bytes = std::max<int64_t>(1, j.maxhit) * a.qpad;
+    a.fits = a.slot_bytes <= j.budget_bytes && a.slot_bytes <= kAlignSlotLimit;
+    a.prof_need = (size_t)(SW_SEARCH_ROWS * a.qpad);
+    a.prof_blocks = (int)std::min<int64_t>((SW_SEARCH_ROWS * a.qpad + 255) / 256, kProfileBlocks);
+    if (!a.fits) return a;
+    a.slots = std::min<int64_t>({j.nhits, (int64_t)j.per_cu[a.kernel] * j.num_cus * 4, j.budget_bytes / a.slot_bytes});
+    if (a.bnd_per) a.slots = std::min<int64_t>(a.slots, kSearchBndBytes / (a.bnd_per * 4));
+    a.slots = std::max<int64_t>(1, a.slots);
+    a.grid = (a.slots + 3) / 4;
+    a.bnd_need = (size_t)(a.slots * a.bnd_per);
+    a.dir_need = (size_t)(a.slots * a.slot_bytes);
+    return a;
+}
+
+void align_schedule(const int64_t* offsets, const int64_t* hits, int64_t nhits, swk::SearchItem* items) {
+    std::vector<int64_t> order((size_t)nhits);
+    for (int64_t h = 0; h < nhits; ++h) order[(size_t)h] = h;
+    auto len = [&](int64_t h) { return offsets[hits[h] + 1] - offsets[hits[h]]; };
+    std::stable_sort(order.begin(), order.end(), [&](int64_t x, int64_t y) { return len(x) > len(y); });
+    for (size_t i = 0; i < order.size(); ++i) items[i] = swk::SearchItem{offsets[hits[order[i]]], order[i], len(order[i])};
+}
+
 void search_schedule(const int64_t* offsets, int64_t ntargets, swk::SearchItem* items) {
     std::vector<int64_t> order;
     order.reserve((size_t)ntargets);

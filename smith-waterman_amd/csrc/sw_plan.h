@@ -1,7 +1,7 @@
 // sw_plan.h -- the planners: every policy decision of one fill (kernel, workgroup shape, perm producer, strip geometry, column
 // tiles, scouts, roles per XCD, split strips, filler pacing, store kind), of one batch call (one pair or two pairs per wave, columns
 // per lane, pairs per launch, the kernel of every launch) and of one database search (columns per lane, profile kind, grid, schedule;
-// plan_search_affine for the affine-gap search),
+// plan_search_affine for the affine-gap search) and of one alignment call (plan_align_affine: columns per lane, slots, grid, order of the hits),
 // and the workspace sizes they need, as pure functions of the job, the device and the options.  Plain C++ (no HIP include):
 // sw_api.hip carries a plan out, tests/test_fill_plan.py and tests/test_batch_plan.py check the policy on a CPU.
 #pragma once
@@ -176,6 +176,38 @@ struct SearchAffinePlan {
 };
 
 SearchAffinePlan plan_search_affine(const SearchAffineJob& job);
+
+// ---- alignment of chosen hits under affine scoring (sw_align_affine_device): sw_align_affine_wave<C> for C = 4, 8, 16, its index in
+// kAlignAffine (sw_api.hip, which checks its order against it at compile time)
+constexpr int kAlignAffineKernels = 3;
+constexpr int align_affine_kernel_index(int C) { return C / 8; }
+
+struct AlignAffineJob {
+    int64_t qlen = 0, maxhit = 0;            // query length, longest hit
+    int64_t nhits = 0;
+    int num_cus = 256;
+    int per_cu[kAlignAffineKernels] = {};    // occupancy of every sw_align_affine_wave instantiation at 256 threads (workgroups per CU)
+    int64_t budget_bytes = 1ll << 30;        // "align_workspace_mib": the direction workspace may take this much
+};
+
+struct AlignAffinePlan {
+    bool fits = false;                       // one hit's direction matrix fits the budget (and a buffer descriptor: below 2^31 bytes)
+    int C = 0;                               // query columns per lane
+    int kernel = 0;                          // index of sw_align_affine_wave<C> (kAlignAffineKernels)
+    int64_t nstrips = 0, qpad = 0;           // strips of 64 C columns; profile row length = row stride of a direction matrix
+    int64_t bnd_per = 0;                     // per slot: boundary column between strips (ints: H and F per row), 0: one strip
+    int64_t slot_bytes = 0;                  // direction matrix of a slot: longest hit x qpad
+    int64_t slots = 0;                       // waves at work, each with its own slot: min(hits, resident waves, budget / slot_bytes)
+    int64_t grid = 0;                        // workgroups of 4 waves
+    int prof_blocks = 0;                     // sw_search_profile_submat blocks
+    size_t prof_need = 0, bnd_need = 0, dir_need = 0;   // workspaces: profile (bytes), boundary columns (ints), directions (bytes)
+};
+
+AlignAffinePlan plan_align_affine(const AlignAffineJob& job);
+
+// The order of the hits: by decreasing length, ties in the caller's order; items[k].idx is the position in `hits` (empty hits are kept:
+// they get their all-zero alignment from the kernel like any other).
+void align_schedule(const int64_t* offsets, const int64_t* hits, int64_t nhits, swk::SearchItem* items);
 
 // The schedule: the non-empty targets of offsets[0 .. ntargets], by decreasing length, ties in input order, written to items.
 void search_schedule(const int64_t* offsets, int64_t ntargets, swk::SearchItem* items);
