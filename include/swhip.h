@@ -12,7 +12,23 @@
  *   - cols = len(a) = matrix columns, rows = len(b) = matrix rows (serial_smithW.c:72-77);
  *     H and P are (rows+1) x (cols+1), row-major, row stride cols+1 (serial_smithW.c:192).
  *   - "d_" pointers are DEVICE (HBM) pointers, everything else is host memory.
- *   - `stream` is a hipStream_t passed as void* (NULL = the default stream).
+ *   - `stream` is a hipStream_t passed as void* (NULL = the default stream).  Every launch, memset and copy of a call goes to that
+ *     stream (and, for the fills, behind the previous fill of the device, see sw_ctx).
+ *   - WRITE extents.  A call writes the outputs it documents and nothing else of the caller's: exactly (rows+1) x (cols+1) elements of
+ *     d_H / d_P (a tile: its own rectangle inside the row stride), one sw_result / sw_alignment per problem, the documented number of
+ *     granules, flags, path entries and op bytes.  Outputs need no initialisation and no particular alignment beyond that of their
+ *     element type (d_H: 4 or 8 bytes, int32 d_P: 4, int8 d_P: any address, sw_result / sw_alignment / granules: 8); base addresses
+ *     that are not 8-byte aligned (16 for an int64 d_H) only cost the whole-line stores of the widest fills.
+ *   - READ extents, from the kernels' loads.  Input sequences need no alignment except d_b of the fills and batches (16 bytes, below).
+ *     sw_batch_device*, sw_search_device, sw_search_affine_device and sw_align_affine_device read no byte outside
+ *     [d_a + k*a_stride, + cols), [d_b + k*b_stride, + rows), [d_query, + qlen) and [d_db + offsets[0], d_db + offsets[ntargets]): the
+ *     gaps of padded strides and the bytes around the query and the database are never loaded.  sw_fill_device, sw_fill_device_ex and
+ *     sw_fill_band_device read a and b, and besides them at most the rest of the 16-byte ALIGNED windows that hold the first and the last
+ *     byte of a, and the last byte of b (their alphabet scan loads whole aligned windows and masks out what is not sequence): up to 15
+ *     bytes in front of d_a, up to 15 behind a and up to 15 behind b, none of which can cross a page or leave an allocation, and none of
+ *     which influences a result.  sw_fill_tile_device reads its a and b bytes only.  (The Python wrapper's to_device keeps 16 spare
+ *     bytes behind a sequence, more than that.)  tests/test_buffer_contract_gpu.py surrounds every input with letters that would raise
+ *     the scores if they were taken for sequence data: it proves that results do not depend on those bytes, not that they are never read.
  */
 #ifndef SWHIP_H
 #define SWHIP_H
@@ -79,7 +95,8 @@ void sw_destroy(sw_ctx* ctx);
  * sw_fill_device: replaces the fill loop + similarityScore/matchMissmatchScore
  * (serial_smithW.c:141-145, 187-256; omp_smithW.c:203-216) and the rotated family's
  * smithWaterman(a,b,w,h,H,P,&maxloc) (rotated-cuda/sw-rotated-omp.cc:192-209).
- * Asynchronous on `stream`.  d_H/d_P need not be initialised (row 0 / column 0 are written).
+ * Asynchronous on `stream`.  d_H/d_P need not be initialised (row 0 / column 0 are written).  d_b must be 16-byte aligned
+ * (SW_EINVAL otherwise); d_a may start anywhere.
  *   h_elem_bytes : 4 -> d_H is int32_t*, 8 -> d_H is int64_t* (same values, widened)
  *   d_top        : optional (may be NULL) int32 H values of the row above this band, cols+1
  *                  entries (multi-GPU row bands); NULL == zeros (a whole matrix)
@@ -108,7 +125,10 @@ int sw_fill_device_ex(sw_ctx* ctx, const char* d_a, int64_t cols, const char* d_
  * of the column to the left (NULL = zeros; d_left[0] is the corner), d_right (optional): receives the
  * rows+1 H values of the tile's last column = the next tile's d_left.  The tile's last row is the next
  * band's d_top.  d_result->max_pos is relative to the corner with the full row stride.
- * Row 0 / column 0 of the tile are not re-written when they belong to a neighbour (P untouched). */
+ * Row 0 of the tile belongs to the neighbour above when d_top is given, column 0 to the neighbour on the left when d_left is given:
+ * such a row / column is not written, neither in H nor in P (the caller's matrix holds the neighbour's values there already; d_top /
+ * d_left carry them to the kernel).  Without d_top row 0, without d_left column 0 is the tile's own and is written: H = 0, P = 0.
+ * Nothing outside the (rows+1) x (cols+1) rectangle at the corner is written.  A tile with d_top needs the systolic engine. */
 int sw_fill_tile_device(sw_ctx* ctx, const char* d_a, int64_t cols, const char* d_b, int64_t rows,
                         const sw_scores* scores, void* d_H, int h_elem_bytes, int32_t* d_P, int64_t row_stride,
                         const int32_t* d_top, const int32_t* d_left, int32_t* d_right, sw_result* d_result,
@@ -160,7 +180,8 @@ void sw_multi_free(sw_multi* m);
  * distinct letters and the scores fit a signed byte -- the letter count is read back once per call, the one host round trip --
  * and on the single-pair machinery otherwise; results are identical.  Pair k reads a at
  * d_a + k*a_stride and b at d_b + k*b_stride (b_stride a multiple of 16), writes d_results[k] (exact arg-max in
- * every mode) and, where given, its matrices at element offset k*(rows+1)*(cols+1).  d_H and/or d_P may be NULL. */
+ * every mode) and, where given, its matrices at element offset k*(rows+1)*(cols+1).  d_H and/or d_P may be NULL.  a_stride >= cols and
+ * b_stride >= rows may leave gaps between the pairs: the gaps are not read, whatever they hold.  d_b must be 16-byte aligned. */
 int sw_batch_device(sw_ctx* ctx, const char* d_a, int64_t a_stride, int64_t cols, const char* d_b, int64_t b_stride,
                     int64_t rows, int64_t npairs, const sw_scores* scores, int32_t* d_H, int32_t* d_P,
                     sw_result* d_results, void* stream);

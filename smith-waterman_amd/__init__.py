@@ -407,7 +407,9 @@ class Engine:
         return _vp(self.torch.cuda.current_stream(self.device).cuda_stream)
 
     def to_device(self, seq):
-        """Sequence -> padded uint8 device tensor (16 spare bytes; the kernel reads b in 16-B windows)."""
+        """Sequence -> uint8 device tensor with 16 zeroed spare bytes behind it, at an address torch aligns to 512 bytes: the fills want b
+        16-byte aligned and may load the rest of the aligned 16-byte window that holds the last byte of a sequence (include/swhip.h,
+        READ extents); results never depend on those bytes."""
         t = self.torch
         s = _as_seq(seq)
         d = t.zeros(len(s) + 16, dtype=t.uint8, device=f"cuda:{self.device}")
@@ -510,7 +512,8 @@ class Engine:
         return self.batch_device(d_a, d_b, cols, rows, scores, store, p_dtype, store_h, traceback, want_paths)
 
     def batch_to_device(self, a_all, b_all):
-        """Host sequences of a batch -> device tensors in the layout sw_batch_device wants (rows of b padded to 16 bytes)."""
+        """Host sequences of a batch -> device tensors in the layout sw_batch_device wants: b_stride a multiple of 16 (rows of b zero padded;
+        the batch kernels read none of the padding), a at its tight stride."""
         t = self.torch
         a_all = np.ascontiguousarray(a_all, np.uint8)
         b_all = np.ascontiguousarray(b_all, np.uint8)
@@ -524,9 +527,10 @@ class Engine:
         return d_a, t.from_numpy(bpad).to(dev), cols, rows
 
     def batch_device(self, d_a, d_b, cols: int, rows: int, scores=DEFAULT_SCORES, store: bool = False, p_dtype=None, store_h=None,
-                     traceback: bool = False, want_paths: bool = False, out=None):
-        """sw_batch_device_ex (+ sw_batch_traceback_device) on sequences already resident in HBM (batch_to_device).  `out`:
-        (res, H, P) tensors of an earlier call to write into again."""
+                     traceback: bool = False, want_paths: bool = False, out=None, paths=None):
+        """sw_batch_device_ex (+ sw_batch_traceback_device) on sequences already resident in HBM (batch_to_device).  d_a / d_b are
+        (npairs, a_stride) / (npairs, b_stride) uint8 tensors: the strides may exceed cols / rows (b_stride a multiple of 16).  `out`:
+        (res, H, P) tensors of an earlier call to write into again; `paths`: an (npairs, cols + rows + 2) int64 tensor for want_paths."""
         t = self.torch
         npairs = d_a.shape[0]
         dev = f"cuda:{self.device}"
@@ -543,11 +547,10 @@ class Engine:
         _check(lib().sw_batch_device_ex(self._h, d_a.data_ptr(), d_a.shape[1], cols, d_b.data_ptr(), d_b.shape[1], rows, npairs, ctypes.byref(sc),
                                         H.data_ptr() if H is not None else None, P.data_ptr() if P is not None else None,
                                         P.element_size() if P is not None else 4, res.data_ptr(), self._stream()))
-        paths = None
         if traceback:
             assert P is not None, "the traceback walks P"
             cap = cols + rows + 2
-            if want_paths:
+            if want_paths and paths is None:
                 paths = t.zeros((npairs, cap), dtype=t.int64, device=dev)
             _check(lib().sw_batch_traceback_device(self._h, P.data_ptr(), P.element_size(), cols, rows, npairs,
                                                    paths.data_ptr() if paths is not None else None, cap, res.data_ptr(), self._stream()))

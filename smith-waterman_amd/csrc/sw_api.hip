@@ -309,6 +309,7 @@ struct FillJob {
     int64_t total_rows = 0;       // band: rows of the whole matrix (bounds the scores a halo can carry)
     bool zero_key = false;        // the preparation kernel also zeroes d_keys[0..1] (fill_one leaves that to it)
     sw_result* d_result = nullptr;   // fill_one: where the result goes (a one-launch fill writes it by itself)
+    bool keep_row0 = false;       // a tile under a neighbour (sw_fill_tile_device with d_top): row 0 of H and P is the neighbour's, not written
 };
 
 // called with g_dev[device].mu held: make `stream` wait for the fill enqueued last on another stream of this device.  The
@@ -416,6 +417,7 @@ static int launch_fill(sw_ctx* c, const sw_scores* sc, const FillJob& j, hipStre
     const bool tile_features = j.d_left || j.d_right || j.stride != cols + 1 || j.npairs != 1 || !j.d_H || !j.d_P || j.d_top_gran || j.d_bot_gran;
     if (!systolic && tile_features) { set_err("tiles / batches / bands / matrix-less fills need the systolic engine (engine 0)"); return SW_EINVAL; }
     if (j.p_elem_bytes == 1 && !systolic) { set_err("compact (int8) P needs the systolic engine"); return SW_EINVAL; }
+    if (j.keep_row0 && !systolic) { set_err("a tile with a top halo needs the systolic engine (engine 0)"); return SW_EINVAL; }
     if (((uintptr_t)j.d_b & 15) != 0 || (j.b_pstride & 15) != 0) { set_err("d_b (and the batch stride of b) must be 16-byte aligned"); return SW_EINVAL; }
     // (the caller holds the device lock and has ordered `stream` behind earlier fills: DevOrder)
     swp::PlanJob pj = plan_job(j, sc);
@@ -460,6 +462,7 @@ static int launch_fill(sw_ctx* c, const sw_scores* sc, const FillJob& j, hipStre
     p.dbg = (unsigned long long*)(uintptr_t)c->opt_dbg_ptr;
     p.npairs = (int)j.npairs; p.store_hp = (j.d_H || j.d_P) ? 1 : 0;
     p.p_bytes = j.p_elem_bytes;
+    p.skip_row0 = j.keep_row0 ? 2 : 0;   // (2: not even the halo values are stored into row 0 of H)
     p.a_pstride = j.a_pstride; p.b_pstride = j.b_pstride; p.hp_pstride = j.hp_pstride;
     p.edge_pstride = S * (rows + 1);
     const unsigned char* ua = (const unsigned char*)j.d_a;
@@ -511,7 +514,7 @@ static int launch_fill(sw_ctx* c, const sw_scores* sc, const FillJob& j, hipStre
             p2.filler_hop_ps = t.filler_hop_ps; p2.filler_tau_ps = t.filler_tau_ps; p2.filler_bw_gbs = t.filler_bw_gbs;
             p2.sync = c->d_sync; p2.priv = c->d_priv; p2.priv_stride = plan.priv_stride;
             p2.bpad16_w = d_cb16; p2.bpad8_w = c->d_cb; p2.bcode_w = d_cbc; p2.atab_w = c->d_alpha + 64;
-            p2.result = j.d_result; p2.skip_row0 = (j.d_top || j.d_top_gran) ? 1 : 0;
+            p2.result = j.d_result; p2.skip_row0 = j.keep_row0 ? 2 : (j.d_top || j.d_top_gran) ? 1 : 0;
             p2.scan_all = t.scan_all;
             hipLaunchKernelGGL(kSystolic2[t.consumers - 4][plan.W2 == 110], dim3(t.grid), dim3(768), 0, stream, ua + t.c0, ub, p2);
         }
@@ -598,8 +601,9 @@ int sw_fill_tile_device(sw_ctx* c, const char* d_a, int64_t cols, const char* d_
                         void* d_H, int h_elem_bytes, int32_t* d_P, int64_t row_stride, const int32_t* d_top,
                         const int32_t* d_left, int32_t* d_right, sw_result* d_result, void* stream_) {
     if (!d_H || !d_P) { set_err("sw_fill_tile_device: bad argument"); return SW_EINVAL; }
-    return fill_one(c, scores, make_job(d_a, cols, d_b, rows, d_H, h_elem_bytes, d_P, 4, row_stride, d_top, d_left, d_right), -1, -1, d_result,
-                    stream_, "sw_fill_tile_device");
+    FillJob j = make_job(d_a, cols, d_b, rows, d_H, h_elem_bytes, d_P, 4, row_stride, d_top, d_left, d_right);
+    j.keep_row0 = d_top != nullptr;
+    return fill_one(c, scores, j, -1, -1, d_result, stream_, "sw_fill_tile_device");
 }
 
 int sw_fill_device(sw_ctx* c, const char* d_a, int64_t cols, const char* d_b, int64_t rows, const sw_scores* scores,

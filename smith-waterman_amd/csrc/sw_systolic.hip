@@ -1364,8 +1364,8 @@ __device__ __forceinline__ void sw_systolic_body(const unsigned char* seq_a, con
                 const int G0v = topj + (jvalid ? cz : 0);
                 HT* H = (HT*)p.H;
                 int32_t* P = p.P;
-                if (ci == 0) {  // row 0: the halo row itself (P of a row owned by the tile above is left alone)
-                    if (store_h) H[j] = (HT)topj;
+                if (ci == 0) {  // row 0: the halo row itself (P of a row owned by the tile above is left alone; so is H for sw_fill_tile_device)
+                    if (store_h && p.skip_row0 != 2) H[j] = (HT)topj;
                     if (store_p && !has_top) { if (p8) ((signed char*)P)[j] = 0; else P[j] = 0; }
                 }
                 if (ci == 0 && right_lane) p.right[0] = topj;

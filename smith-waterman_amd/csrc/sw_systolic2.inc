@@ -1091,7 +1091,7 @@ __device__ __forceinline__ void s2_body(Sys2Lds& lds, const unsigned char* ltab,
                         if (!((u32)(pcP - ((f0P + (u32)k * rowbP + pcP) & 63u)) < 440u)) wm |= 1u << (16 + k);
                     }
                 }
-                if (has_top && store_h && k9 == 0) {   // a band's row 0 is the halo row: H written, P left alone
+                if (has_top && store_h && k9 == 0 && p.skip_row0 != 2) {   // a band's row 0 is the halo row: H written, P left alone (a tile's: neither)
                     if (h64) {   // (scores are never negative: the high dword is zero)
                         if (okA) ((int64_t*)H)[jA] = topA;
                         if (okB) ((int64_t*)H)[jB] = topB;
