@@ -1,0 +1,218 @@
+// sw_api_search.hip -- the search family of the C-ABI (see include/swhip.h): database search, affine search, alignment of hits.  The three
+// calls share the workspaces of the context and one protocol around them; each reads validate, plan, stage, upload, launch.
+#include <cstring>
+#include "sw_ctx.h"
+
+// the instantiations of the search kernel (sw_search.hip), picked by swp::plan_search
+using SearchKernel = void (*)(swk::SearchParams);
+static constexpr Indexed<SearchKernel> kSearch[] = {
+    {swp::search_kernel_index(4, false), swk::sw_search_wave<4, false>}, {swp::search_kernel_index(4, true), swk::sw_search_wave<4, true>},
+    {swp::search_kernel_index(8, false), swk::sw_search_wave<8, false>}, {swp::search_kernel_index(8, true), swk::sw_search_wave<8, true>},
+    {swp::search_kernel_index(16, false), swk::sw_search_wave<16, false>}, {swp::search_kernel_index(16, true), swk::sw_search_wave<16, true>},
+};
+static_assert(std::size(kSearch) == swp::kSearchKernels && at_their_indices(kSearch));
+
+// the instantiations of the affine search kernel (sw_search_affine.hip), picked by swp::plan_search_affine
+using SearchAffineKernel = void (*)(swk::SearchAffineParams);
+static constexpr Indexed<SearchAffineKernel> kSearchAffine[] = {
+    {swp::search_affine_kernel_index(4), swk::sw_search_affine_wave<4>},
+    {swp::search_affine_kernel_index(8), swk::sw_search_affine_wave<8>},
+    {swp::search_affine_kernel_index(16), swk::sw_search_affine_wave<16>},
+};
+static_assert(std::size(kSearchAffine) == swp::kSearchAffineKernels && at_their_indices(kSearchAffine));
+
+// the instantiations of the alignment kernel (sw_align_affine.hip), picked by swp::plan_align_affine
+using AlignAffineKernel = void (*)(swk::AlignAffineParams);
+static constexpr Indexed<AlignAffineKernel> kAlignAffine[] = {
+    {swp::align_affine_kernel_index(4), swk::sw_align_affine_wave<4>},
+    {swp::align_affine_kernel_index(8), swk::sw_align_affine_wave<8>},
+    {swp::align_affine_kernel_index(16), swk::sw_align_affine_wave<16>},
+};
+static_assert(std::size(kAlignAffine) == swp::kAlignAffineKernels && at_their_indices(kAlignAffine));
+
+// occupancy of every instantiation of a table at 256 threads, asked once per context: the plans' columns per lane and grids depend on it
+template <typename K, size_t N>
+static int occupancy_once(const Indexed<K> (&tab)[N], int (&per_cu)[N], bool& known) {
+    if (known) return SW_OK;
+    for (size_t k = 0; k < N; ++k) HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu[k], tab[k].k, 256, 0));
+    known = true;
+    return SW_OK;
+}
+
+// The search schedule's device buffer and the pinned copy it is uploaded from, grown together to `need` items (the caller has waited
+// for the last upload from the pinned copy).
+static int grow_schedule(sw_ctx* c, size_t need, hipStream_t stream) {
+    if (need <= c->sitems_cap) return SW_OK;
+    HIP_TRY(hipStreamSynchronize(stream));
+    if (c->d_sitems) HIP_TRY(hipFree(c->d_sitems));
+    if (c->h_sitems) HIP_TRY(hipHostFree(c->h_sitems));
+    c->d_sitems = nullptr; c->h_sitems = nullptr; c->sitems_cap = 0;
+    if (hipMalloc((void**)&c->d_sitems, need * sizeof(swk::SearchItem)) != hipSuccess ||
+        hipHostMalloc((void**)&c->h_sitems, need * sizeof(swk::SearchItem), 0) != hipSuccess) {
+        set_err("sw_search_device: workspace allocation failed");
+        return SW_ENOMEM;
+    }
+    c->sitems_cap = need;
+    return SW_OK;
+}
+
+// The schedule and the table are uploaded from pinned copies, which a call overwrites: first the previous call's uploads have to have left
+// them (sitems_ev, recorded by upload_search_call).  Then the workspaces the three kernels share grow to what this call's plan needs; the
+// counter and (for a call with a `table`) the table's two copies are allocated at their first use.  On return c->h_sitems is free to write.
+static int stage_search_call(sw_ctx* c, hipStream_t stream, size_t nitems, size_t prof_need, size_t bnd_need, const sw_submat* table) {
+    if (c->sitems_ev) HIP_TRY(hipEventSynchronize(c->sitems_ev));
+    else HIP_TRY(hipEventCreateWithFlags(&c->sitems_ev, hipEventDisableTiming));
+    bool fresh = false;
+    if (int rc = grow_schedule(c, nitems, stream)) return rc;
+    if (int rc = grow_workspace((void**)&c->d_sprof, c->sprof_cap, prof_need, 1, 0, stream, fresh)) return rc;
+    if (int rc = grow_workspace((void**)&c->d_sbnd, c->sbnd_cap, bnd_need, 4, 0, stream, fresh)) return rc;
+    if (!c->d_sctr) HIP_TRY(hipMalloc((void**)&c->d_sctr, 64));
+    if (table && !c->d_submat) HIP_TRY(hipMalloc((void**)&c->d_submat, sizeof(sw_submat)));
+    if (table && !c->h_submat) HIP_TRY(hipHostMalloc((void**)&c->h_submat, sizeof(sw_submat), 0));
+    return SW_OK;
+}
+
+// Uploads the schedule the caller has written to c->h_sitems, and the table through its pinned copy.  The event is recorded once, behind
+// BOTH uploads: whoever has waited for it may overwrite either pinned copy.  The work counter starts every launch at zero.
+static int upload_search_call(sw_ctx* c, hipStream_t stream, size_t nitems, const sw_submat* table) {
+    if (table) memcpy(c->h_submat, table, sizeof(sw_submat));
+    HIP_TRY(hipMemcpyAsync(c->d_sitems, c->h_sitems, nitems * sizeof(swk::SearchItem), hipMemcpyHostToDevice, stream));
+    if (table) HIP_TRY(hipMemcpyAsync(c->d_submat, c->h_submat, sizeof(sw_submat), hipMemcpyHostToDevice, stream));
+    HIP_TRY(hipEventRecord(c->sitems_ev, stream));
+    HIP_TRY(hipMemsetAsync(c->d_sctr, 0, 4, stream));
+    return SW_OK;
+}
+
+// What the parameters of the three kernels have in common (sw_kernels.h); the rest is zero for the entry point to set.
+template <typename Params, typename Plan>
+static Params search_params(const sw_ctx* c, const char* d_db, int64_t nitems, int64_t qlen, const Plan& plan) {
+    Params p;
+    memset(&p, 0, sizeof p);
+    p.db = (const unsigned char*)d_db;
+    p.items = c->d_sitems; p.nitems = nitems;
+    p.prof = c->d_sprof; p.qpad = plan.qpad; p.qlen = qlen;
+    p.bnd = plan.bnd_per ? c->d_sbnd : nullptr; p.bnd_per = plan.bnd_per;
+    p.counter = c->d_sctr;
+    return p;
+}
+
+extern "C" {
+
+// Database search (csrc/sw_search.hip): for every target k the reference fill of query x target k, score and arg-max only.  No host
+// round trip: the lengths come from the host offsets, the profile is built on the device from the query.
+int sw_search_device(sw_ctx* c, const char* d_query, int64_t qlen, const char* d_db, const int64_t* offsets, int64_t ntargets,
+                     const sw_scores* scores, sw_result* d_results, void* stream_) {
+    const sw_scores* sc = scores ? scores : &kDefaultScores;
+    if (!c || !d_query || !d_db || !offsets || !d_results || ntargets < 0) { set_err("sw_search_device: NULL pointer or negative target count"); return SW_EINVAL; }
+    int64_t maxlen = 0, nonempty = 0;
+    if (int rc = swh::check_targets("sw_search_device", qlen, offsets, ntargets, &maxlen, &nonempty)) return rc;
+    if (int rc = check_dims(qlen, maxlen, sc)) return rc;
+    if (ntargets == 0) return SW_OK;
+    hipStream_t stream = (hipStream_t)stream_;
+    HIP_TRY(hipSetDevice(c->device));
+    DevOrder order(c, stream, false);
+    if (order.rc) return order.rc;
+    // empty targets keep the zeros: {0, 0, 0}
+    HIP_TRY(hipMemsetAsync(d_results, 0, (size_t)ntargets * sizeof(sw_result), stream));
+    if (nonempty == 0) return SW_OK;
+    if (int rc = occupancy_once(kSearch, c->search_per_cu, c->search_per_cu_known)) return rc;
+    swp::SearchJob sj;
+    sj.qlen = qlen; sj.maxlen = maxlen; sj.ntargets = nonempty; sj.match = sc->match; sj.mismatch = sc->mismatch; sj.gap = sc->gap;
+    const swp::SearchPlan plan = swp::plan_search(sj, device_facts(c));
+    if (c->search_per_cu[plan.kernel] < 1) { set_err("the search kernel does not fit a CU on this device"); return SW_EDEVICE; }
+    if (int rc = stage_search_call(c, stream, (size_t)nonempty, plan.prof_need, plan.bnd_need, nullptr)) return rc;
+    swp::search_schedule(offsets, ntargets, c->h_sitems);
+    if (int rc = upload_search_call(c, stream, (size_t)nonempty, nullptr)) return rc;
+    hipLaunchKernelGGL(swk::sw_search_profile, dim3((unsigned)plan.prof_blocks), dim3(256), 0, stream, (const unsigned char*)d_query, qlen, plan.qpad,
+                       c->d_sprof, sc->match, sc->mismatch, plan.wide ? 1 : 0);
+    HIP_TRY(hipGetLastError());
+    swk::SearchParams sp = search_params<swk::SearchParams>(c, d_db, nonempty, qlen, plan);
+    sp.match = sc->match; sp.mismatch = sc->mismatch; sp.ngap = -sc->gap;
+    sp.results = d_results;
+    hipLaunchKernelGGL(kSearch[plan.kernel].k, dim3((unsigned)plan.grid), dim3(256), 0, stream, sp);
+    HIP_TRY(hipGetLastError());
+    c->last_search_grid = plan.grid; c->last_search_kernel = plan.kernel;
+    return SW_OK;
+}
+
+// Database search with a substitution matrix and affine gaps (csrc/sw_search_affine.hip).  The shape of sw_search_device: no host
+// round trip, the schedule and the 64 KiB table are uploaded from pinned copies, the profile is built on the device.
+int sw_search_affine_device(sw_ctx* c, const char* d_query, int64_t qlen, const char* d_db, const int64_t* offsets, int64_t ntargets,
+                            const sw_affine* scoring, sw_result* d_results, void* stream_) {
+    if (!c || !d_query || !d_db || !offsets || !d_results || !scoring || ntargets < 0) { set_err("sw_search_affine_device: NULL pointer or negative target count"); return SW_EINVAL; }
+    int64_t maxlen = 0, nonempty = 0;
+    if (int rc = swh::check_search_affine("sw_search_affine_device", qlen, offsets, ntargets, scoring, &maxlen, &nonempty)) return rc;
+    if (ntargets == 0) return SW_OK;
+    hipStream_t stream = (hipStream_t)stream_;
+    HIP_TRY(hipSetDevice(c->device));
+    DevOrder order(c, stream, false);
+    if (order.rc) return order.rc;
+    // empty targets keep the zeros: {0, 0, 0}
+    HIP_TRY(hipMemsetAsync(d_results, 0, (size_t)ntargets * sizeof(sw_result), stream));
+    if (nonempty == 0) return SW_OK;
+    if (int rc = occupancy_once(kSearchAffine, c->search_affine_per_cu, c->search_affine_per_cu_known)) return rc;
+    swp::SearchAffineJob sj;
+    sj.qlen = qlen; sj.maxlen = maxlen; sj.ntargets = nonempty; sj.num_cus = c->num_cus;
+    std::copy(std::begin(c->search_affine_per_cu), std::end(c->search_affine_per_cu), sj.per_cu);
+    const swp::SearchAffinePlan plan = swp::plan_search_affine(sj);
+    if (c->search_affine_per_cu[plan.kernel] < 1) { set_err("the affine search kernel does not fit a CU on this device"); return SW_EDEVICE; }
+    if (int rc = stage_search_call(c, stream, (size_t)nonempty, plan.prof_need, plan.bnd_need, scoring->sub)) return rc;
+    swp::search_schedule(offsets, ntargets, c->h_sitems);
+    if (int rc = upload_search_call(c, stream, (size_t)nonempty, scoring->sub)) return rc;
+    hipLaunchKernelGGL(swk::sw_search_profile_submat, dim3((unsigned)plan.prof_blocks), dim3(256), 0, stream, (const unsigned char*)d_query, qlen,
+                       plan.qpad, c->d_sprof, (const signed char*)c->d_submat);
+    HIP_TRY(hipGetLastError());
+    swk::SearchAffineParams sp = search_params<swk::SearchAffineParams>(c, d_db, nonempty, qlen, plan);
+    sp.ge = scoring->gap_extend; sp.goe = scoring->gap_open + scoring->gap_extend;
+    sp.results = d_results;
+    hipLaunchKernelGGL(kSearchAffine[plan.kernel].k, dim3((unsigned)plan.grid), dim3(256), 0, stream, sp);
+    HIP_TRY(hipGetLastError());
+    c->last_search_affine_grid = plan.grid; c->last_search_affine_kernel = plan.kernel;
+    return SW_OK;
+}
+
+// The alignment of chosen hits under affine scoring (csrc/sw_align_affine.hip).  The shape of sw_search_affine_device: no host round
+// trip, the order of the hits and the table are uploaded from pinned copies, the profile is built on the device; the plan decides.
+int sw_align_affine_device(sw_ctx* c, const char* d_query, int64_t qlen, const char* d_db, const int64_t* offsets, int64_t ntargets,
+                           const int64_t* hits, int64_t nhits, const sw_affine* scoring, sw_alignment* d_aln, char* d_ops, int64_t ops_cap,
+                           void* stream_) {
+    if (!c || !d_query || !d_db || !offsets || !scoring || ntargets < 0) { set_err("sw_align_affine_device: NULL pointer or negative target count"); return SW_EINVAL; }
+    int64_t maxlen = 0, nonempty = 0, maxhit = 0;
+    if (int rc = swh::check_search_affine("sw_align_affine_device", qlen, offsets, ntargets, scoring, &maxlen, &nonempty)) return rc;
+    if (int rc = swh::check_align_affine("sw_align_affine_device", offsets, ntargets, hits, nhits, d_aln, d_ops, ops_cap, &maxhit)) return rc;
+    if (nhits == 0) return SW_OK;
+    hipStream_t stream = (hipStream_t)stream_;
+    HIP_TRY(hipSetDevice(c->device));
+    DevOrder order(c, stream, false);
+    if (order.rc) return order.rc;
+    if (int rc = occupancy_once(kAlignAffine, c->align_affine_per_cu, c->align_affine_per_cu_known)) return rc;
+    swp::AlignAffineJob aj;
+    aj.qlen = qlen; aj.maxhit = maxhit; aj.nhits = nhits; aj.num_cus = c->num_cus; aj.budget_bytes = c->opt_align_workspace_mib << 20;
+    std::copy(std::begin(c->align_affine_per_cu), std::end(c->align_affine_per_cu), aj.per_cu);
+    const swp::AlignAffinePlan plan = swp::plan_align_affine(aj);
+    if (!plan.fits) {
+        set_err("sw_align_affine_device: the direction matrix of the longest hit (%lld rows x %lld bytes = %lld bytes) does not fit align_workspace_mib = %lld "
+                "(or the 2 GiB a slot may take)", (long long)maxhit, (long long)plan.qpad, (long long)plan.slot_bytes, (long long)c->opt_align_workspace_mib);
+        return SW_EINVAL;
+    }
+    if (c->align_affine_per_cu[plan.kernel] < 1) { set_err("the alignment kernel does not fit a CU on this device"); return SW_EDEVICE; }
+    if (int rc = stage_search_call(c, stream, (size_t)nhits, plan.prof_need, plan.bnd_need, scoring->sub)) return rc;
+    bool fresh = false;   // (its own workspace: one direction matrix per slot)
+    if (int rc = grow_workspace((void**)&c->d_adir, c->adir_cap, plan.dir_need, 1, 0, stream, fresh)) return rc;
+    swp::align_schedule(offsets, hits, nhits, c->h_sitems);
+    if (int rc = upload_search_call(c, stream, (size_t)nhits, scoring->sub)) return rc;
+    hipLaunchKernelGGL(swk::sw_search_profile_submat, dim3((unsigned)plan.prof_blocks), dim3(256), 0, stream, (const unsigned char*)d_query, qlen,
+                       plan.qpad, c->d_sprof, (const signed char*)c->d_submat);
+    HIP_TRY(hipGetLastError());
+    swk::AlignAffineParams ap = search_params<swk::AlignAffineParams>(c, d_db, nhits, qlen, plan);
+    ap.ge = scoring->gap_extend; ap.goe = scoring->gap_open + scoring->gap_extend;
+    ap.dir = c->d_adir; ap.slot_bytes = plan.slot_bytes; ap.nslots = plan.slots;
+    ap.aln = d_aln; ap.ops = d_ops; ap.ops_cap = ops_cap;
+    ap.stamps = (unsigned long long*)(uintptr_t)c->opt_dbg_ptr;
+    hipLaunchKernelGGL(kAlignAffine[plan.kernel].k, dim3((unsigned)plan.grid), dim3(256), 0, stream, ap);
+    HIP_TRY(hipGetLastError());
+    c->last_align_affine_kernel = plan.kernel; c->last_align_affine_slots = plan.slots;
+    return SW_OK;
+}
+
+}  // extern "C"

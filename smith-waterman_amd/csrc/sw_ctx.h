@@ -1,0 +1,199 @@
+// sw_ctx.h -- what the files of the C-ABI driver share (library-internal): the context, the per-device launch order, the workspace
+// helpers and the prototypes of the library-internal functions.  sw_api.hip (context, options, traceback), sw_api_fill.hip (fills and
+// batches), sw_api_search.hip (the search family) and sw_place.hip (the output allocator) carry the plans of sw_plan.cpp out on it.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <algorithm>
+#include <cstdlib>
+#include <iterator>
+#include <map>
+#include <mutex>
+#include "sw_kernels.h"
+#include "sw_plan.h"
+
+#define SW_HIDDEN __attribute__((visibility("hidden")))   // shared among the driver's files without joining the library's exported symbols
+namespace swh {   // sw_host.cpp
+void set_err(const char* fmt, ...);
+int check_search_affine(const char* who, int64_t qlen, const int64_t* offsets, int64_t ntargets, const sw_affine* sc, int64_t* maxlen_out,
+                        int64_t* nonempty_out);
+int check_align_affine(const char* who, const int64_t* offsets, int64_t ntargets, const int64_t* hits, int64_t nhits, const void* aln, const void* ops,
+                       int64_t ops_cap, int64_t* maxhit_out);
+SW_HIDDEN int check_targets(const char* who, int64_t qlen, const int64_t* offsets, int64_t ntargets, int64_t* maxlen_out, int64_t* nonempty_out);
+}
+using swh::set_err;
+extern "C" {
+int sw_place_pair_ratio(void* d_X, size_t xbytes, void* d_Y, size_t ybytes, float* ratio, float* ms_together);   // sw_place.hip
+int sw_traceback_stop_device(sw_ctx* c, void* d_P, int p_elem_bytes, int64_t cols, int64_t rows, int64_t max_pos, sw_result* d_result, int64_t* d_stop,
+                             void* stream);   // sw_api.hip
+int sw_fill_band_reserve(sw_ctx* c, int64_t cols, int64_t rows, int64_t total_rows, const sw_scores* scores, int h_elem_bytes, int p_elem_bytes, int want_h,
+                         void* stream);       // sw_api_fill.hip
+}
+
+#define HIP_TRY(expr)                                                                 \
+    do {                                                                              \
+        hipError_t e_ = (expr);                                                       \
+        if (e_ != hipSuccess) {                                                       \
+            set_err("%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
+            return SW_EDEVICE;                                                        \
+        }                                                                             \
+    } while (0)
+
+// Fills of one device are serialised.  The systolic kernel's workgroups spin on hand-offs from other workgroups, so
+// every workgroup of a launch must be resident; two fills in flight on one device (two contexts, or one context on
+// two streams) could each hold part of the CUs and wait for the rest forever.  Launches therefore happen under a
+// per-device lock, and a fill enqueued on a different stream than the previous one first waits (on the device, not
+// the host) for everything enqueued on that previous stream.
+struct DevState {
+    std::mutex mu;
+    bool any = false;
+    hipStream_t last_stream = nullptr;
+    hipEvent_t ev = nullptr;
+    int concurrent_ok = 0;   // set while band launches that partition the CUs explicitly are being enqueued
+};
+extern SW_HIDDEN DevState g_dev[64];   // sw_api.hip
+
+struct SW_HIDDEN sw_ctx {
+    int device = 0;
+    int num_cus = 256;
+    bool xcd_round_robin = false;       // sw_xcc_probe saw workgroup i on XCD i % 8 (8 XCDs of 32 CUs)
+    unsigned char* d_alpha = nullptr;   // [64..323] letter code table + letter count; [512..1535] XCD of every workgroup of the running launch (sw_systolic2, xcd_mode)
+    unsigned int* d_part = nullptr;     // sw_prep_scan: one 256-bit presence map of byte values per block (up to 2048 blocks)
+    int64_t opt_dbg_ptr = 0;
+    swp::PlanOptions opt;               // the options the planners read (sw_set_option; include/swhip.h)
+    // ---- fills (sw_api_fill.hip)
+    unsigned epoch = 0;                 // 12-bit launch tag, see FillParams::tag_base
+    unsigned long long* d_edge = nullptr;
+    size_t edge_cap = 0;                // granules
+    unsigned long long* d_key = nullptr; // [0] = arg-max key, [1] low word = abort flag
+    unsigned char* d_cb = nullptr;      // systolic engine: padded copies of b (bytes, 16-bit, letter codes; sw_pad_b)
+    size_t cb_cap = 0;
+    unsigned int* d_edge4 = nullptr;    // perm producer: lane-63 columns as self-tagged 4-byte values
+    size_t edge4_cap = 0;               // elements
+    unsigned epoch8 = 0;                // 8-bit launch tag of those values
+    unsigned int* d_sync = nullptr;     // one-launch fills (sw_systolic2's prologue / epilogue): barrier and exit counters, presence map; zero between launches
+    unsigned char* d_priv = nullptr; size_t priv_cap = 0;   // ... and every workgroup's own padded copy of b + letter codes
+    bool key_dirty = false;             // d_key was left non-zero by a launch that does not re-arm it (everything but the one-launch fill)
+    bool last_fused = false;            // the last launch_fill reports by itself (no sw_finalize behind it)
+    swp::FillPlan last_plan;            // the plan of the last fill (sw_get_option "last_*")
+    int64_t last_grid = 0;              // ... and the grid of its one-column kernel after the occupancy cap
+    int s2_per_cu = 0;                  // occupancy of sw_systolic2 at 768 threads (queried at the first fill)
+    struct { int threads, per_cu; } sys_occ[8][2] = {};   // occupancy of every sw_systolic instantiation (kSystolic x int32 / int64 H) at the workgroup size last asked about
+    int64_t opt_xcd_order = 0;          // systolic: 1 = neighbouring strip groups on one XCD
+    int64_t opt_pace_ps = 0;            // systolic: pacing of strip 0 (ps per row; 0 = off)
+    int64_t opt_band_wait_ms = 20000;   // band-resident launch: patience of the top-halo poll
+    // ---- batches (sw_api_fill.hip)
+    unsigned long long* d_keys = nullptr; size_t keys_cap = 0;  // the fall-back: one key per pair
+    unsigned char* d_bcodes = nullptr; size_t bcodes_cap = 0;   // batch kernel: padded letter codes of every pair's b
+    int* d_bnd = nullptr; size_t bnd_cap = 0;                   // batch kernel: boundary columns between strips (ints)
+    int64_t opt_batch_lds = 0;          // batch kernel: dynamic LDS bytes per workgroup (caps the waves per CU; experiments)
+    int64_t last_batch_kernel = 0;      // 1: the last sw_batch_device call ran on sw_batch_wave (one pair per wave)
+    // ---- the search family (sw_api_search.hip).  Shared by its three calls: profile of the query, per-wave boundary columns, the schedule
+    // and the substitution matrix (each on the device + a pinned host copy it is uploaded from), the work counter.  sitems_ev is recorded
+    // behind the uploads of a call; the next call waits for it before it overwrites the pinned copies (stage_search_call).
+    signed char* d_sprof = nullptr; size_t sprof_cap = 0;
+    int* d_sbnd = nullptr; size_t sbnd_cap = 0;
+    swk::SearchItem* d_sitems = nullptr; swk::SearchItem* h_sitems = nullptr; size_t sitems_cap = 0;
+    signed char* d_submat = nullptr; signed char* h_submat = nullptr;
+    hipEvent_t sitems_ev = nullptr;
+    unsigned int* d_sctr = nullptr;
+    int64_t last_search_grid = 0;       // workgroups of the last search launch
+    int64_t last_search_kernel = 0;     // its kernel: index in kSearch (swp::search_kernel_index)
+    int search_per_cu[swp::kSearchKernels] = {};   // occupancy of every sw_search_wave instantiation at 256 threads ...
+    bool search_per_cu_known = false;              // ... queried at the first search
+    int64_t last_search_affine_grid = 0;    // workgroups of the last affine search launch
+    int64_t last_search_affine_kernel = 0;  // its kernel: index in kSearchAffine (swp::search_affine_kernel_index)
+    int search_affine_per_cu[swp::kSearchAffineKernels] = {};   // occupancy of every sw_search_affine_wave instantiation at 256 threads ...
+    bool search_affine_per_cu_known = false;                    // ... queried at the first affine search
+    // alignment of hits (sw_align_affine_device): one direction matrix per wave at work
+    unsigned char* d_adir = nullptr; size_t adir_cap = 0;
+    int64_t opt_align_workspace_mib = 1024;
+    int64_t last_align_affine_kernel = 0, last_align_affine_slots = 0;
+    int align_affine_per_cu[swp::kAlignAffineKernels] = {};     // occupancy of every sw_align_affine_wave instantiation at 256 threads ...
+    bool align_affine_per_cu_known = false;                     // ... queried at the first call
+    // ---- placement of the output matrices (sw_place.hip)
+    int64_t opt_place_hold_gib = 0;     // sw_alloc_outputs: GiB a pair of small matrices may hold beside itself where no plain candidate is good (0: none)
+    int64_t opt_place_budget_ms = 1500; // sw_alloc_outputs: time the search for a P in another class of the HBM may take
+    int place_spacer_gib = 0;           // ... the spacer that led to one last time
+    int64_t last_place_held_gib = 0;
+    float last_place_ratio = 0.f;       // ... two-stream / one-stream time of the pair handed out last (~1.3-1.45: different classes, ~2: one class)
+    std::map<void*, void*> out_base;    // sw_alloc_outputs: pointer handed out -> allocation to free
+    std::map<void*, float> pair_ratio;  // ... P handed out -> the store probe's ratio of its pair (~1.4: two classes of the HBM, ~2: one)
+};
+
+// A launch table: every instantiation beside the index the planner gives it, checked at compile time to sit at that index.
+template <typename K> struct Indexed { int index; K k; };
+template <typename K, size_t N> constexpr bool at_their_indices(const Indexed<K> (&t)[N]) {
+    for (size_t i = 0; i < N; ++i)
+        if (t[i].index != (int)i) return false;
+    return true;
+}
+
+constexpr sw_scores kDefaultScores = {3, -3, -2};  // serial_smithW.c:59-61
+
+// gr, gc: extent (rows, cols) of the WHOLE matrix the values may come from (== rows, cols unless this is a tile or a
+// band whose halo carries scores accumulated outside it)
+static inline int check_dims(int64_t cols, int64_t rows, const sw_scores* sc, int64_t gc = -1, int64_t gr = -1) {
+    if (gc < cols) gc = cols;
+    if (gr < rows) gr = rows;
+    if (cols < 0 || rows < 0 || cols > swk::SW_MAX_DIM || rows > swk::SW_MAX_DIM || gc > swk::SW_MAX_DIM || gr > swk::SW_MAX_DIM) {
+        set_err("dimensions out of range: cols=%lld rows=%lld (max %lld)", (long long)cols, (long long)rows,
+                (long long)swk::SW_MAX_DIM);
+        return SW_EINVAL;
+    }
+    if (sc->gap > 0) { set_err("gap score must be <= 0 (got %d)", sc->gap); return SW_EINVAL; }
+    if (sc->match < 0) { set_err("match score must be >= 0 (got %d)", sc->match); return SW_EINVAL; }
+    if (sc->mismatch > sc->match) { set_err("mismatch score must not exceed the match score"); return SW_EINVAL; }
+    const int64_t lo = std::min(gc, gr);
+    // largest G-space magnitude: H <= match*min(dims) plus -gap*(row+col); the per-step constants ride on top
+    const int64_t gmax = (int64_t)sc->match * lo + (int64_t)(-sc->gap) * (rows + cols + 2);
+    const int64_t step = std::max<int64_t>(std::llabs((int64_t)sc->mismatch), (int64_t)sc->match) + 2 * (int64_t)(-sc->gap);
+    if (gmax + step >= (1ll << 31) || step >= (1ll << 24) || (int64_t)sc->match * lo >= (1ll << 24)) {
+        set_err("scores too large for this problem size (32-bit cell / 24-bit arg-max key)");
+        return SW_EINVAL;
+    }
+    return SW_OK;
+}
+
+static inline swp::DeviceFacts device_facts(const sw_ctx* c) {
+    swp::DeviceFacts dev;
+    dev.num_cus = c->num_cus; dev.xcd_round_robin = c->xcd_round_robin; dev.s2_per_cu = c->s2_per_cu;
+    std::copy(std::begin(c->search_per_cu), std::end(c->search_per_cu), dev.search_per_cu);
+    return dev;
+}
+
+// called with g_dev[device].mu held: make `stream` wait for the fill enqueued last on another stream of this device.  The
+// event is recorded on a fill's OWN stream when the fill has been enqueued (DevOrder's destructor), never on the previous
+// stream later on: that stream may have been destroyed by then.
+static inline int order_after_previous_fill(DevState& d, hipStream_t stream, bool allow_concurrent) {
+    if (d.any && d.last_stream != stream && !allow_concurrent && d.ev) HIP_TRY(hipStreamWaitEvent(stream, d.ev, 0));
+    return SW_OK;
+}
+
+struct DevOrder {   // RAII: device lock + stream ordering for one fill call
+    std::unique_lock<std::mutex> lk;
+    DevState& d;
+    hipStream_t stream;
+    int rc;
+    DevOrder(sw_ctx* c, hipStream_t st, bool concurrent) : lk(g_dev[c->device & 63].mu), d(g_dev[c->device & 63]), stream(st) {
+        rc = order_after_previous_fill(d, stream, concurrent);
+    }
+    ~DevOrder() {
+        if (!d.ev && hipEventCreateWithFlags(&d.ev, hipEventDisableTiming) != hipSuccess) { d.ev = nullptr; (void)hipGetLastError(); }
+        if (d.ev && hipEventRecord(d.ev, stream) == hipSuccess) { d.any = true; d.last_stream = stream; }
+        else { (void)hipGetLastError(); d.any = false; }
+    }
+};
+
+// Grows a workspace of the context to `need` elements of `elem` bytes (+ `slack` bytes): waits for the stream (launches in flight may
+// still read the old one), frees it and allocates afresh.  `fresh` says whether it did: the caller wipes what must start zeroed.
+static inline int grow_workspace(void** buf, size_t& cap, size_t need, size_t elem, size_t slack, hipStream_t stream, bool& fresh) {
+    fresh = false;
+    if (need <= cap) return SW_OK;
+    HIP_TRY(hipStreamSynchronize(stream));
+    if (*buf) HIP_TRY(hipFree(*buf));
+    *buf = nullptr; cap = 0;
+    const size_t bytes = need * elem + slack;
+    if (hipMalloc(buf, bytes) != hipSuccess) { set_err("workspace allocation of %zu bytes failed", bytes); return SW_ENOMEM; }
+    cap = need; fresh = true;
+    return SW_OK;
+}

@@ -6,7 +6,7 @@
 #include <algorithm>
 #include <string>
 #include <vector>
-#include "../../include/swhip.h"
+#include "sw_ctx.h"
 
 namespace swh {
 thread_local std::string g_err;
@@ -47,12 +47,10 @@ private:
     int f_, r_;
 };
 
-// The argument rules of the affine search (include/swhip.h), shared by the device and the host entry point; reports the longest
-// target and the number of non-empty ones.  kMaxDim: the 2^20 - 1 of sw_search_device (40-bit indices).
-int check_search_affine(const char* who, int64_t qlen, const int64_t* offsets, int64_t ntargets, const sw_affine* sc, int64_t* maxlen_out,
-                        int64_t* nonempty_out) {
-    constexpr int64_t kMaxDim = (1 << 20) - 1, kScoreLimit = 1ll << 24;
-    if (!sc || !sc->sub) { set_err("%s: NULL scoring or substitution matrix", who); return SW_EINVAL; }
+// The argument rules every search call shares: query length, offsets[0], every target's length; reports the longest target and the
+// number of non-empty ones.  kMaxDim: the 2^20 - 1 of swk::SW_MAX_DIM (40-bit indices).
+int check_targets(const char* who, int64_t qlen, const int64_t* offsets, int64_t ntargets, int64_t* maxlen_out, int64_t* nonempty_out) {
+    constexpr int64_t kMaxDim = swk::SW_MAX_DIM;
     if (qlen < 1 || qlen > kMaxDim) { set_err("%s: query length %lld out of range 1..%lld", who, (long long)qlen, (long long)kMaxDim); return SW_EINVAL; }
     if (offsets[0] < 0) { set_err("%s: offsets[0] = %lld is negative", who, (long long)offsets[0]); return SW_EINVAL; }
     int64_t maxlen = 0, nonempty = 0;
@@ -63,6 +61,18 @@ int check_search_affine(const char* who, int64_t qlen, const int64_t* offsets, i
         maxlen = std::max(maxlen, len);
         nonempty += len > 0;
     }
+    *maxlen_out = maxlen;
+    *nonempty_out = nonempty;
+    return SW_OK;
+}
+
+// The argument rules of the affine search (include/swhip.h), shared by the device and the host entry point.
+int check_search_affine(const char* who, int64_t qlen, const int64_t* offsets, int64_t ntargets, const sw_affine* sc, int64_t* maxlen_out,
+                        int64_t* nonempty_out) {
+    constexpr int64_t kScoreLimit = 1ll << 24;
+    if (!sc || !sc->sub) { set_err("%s: NULL scoring or substitution matrix", who); return SW_EINVAL; }
+    int64_t maxlen = 0, nonempty = 0;
+    if (int rc = check_targets(who, qlen, offsets, ntargets, &maxlen, &nonempty)) return rc;
     if (sc->gap_open > 0) { set_err("%s: gap_open must be <= 0 (got %d)", who, sc->gap_open); return SW_EINVAL; }
     if (sc->gap_extend > 0) { set_err("%s: gap_extend must be <= 0 (got %d)", who, sc->gap_extend); return SW_EINVAL; }
     if ((int64_t)sc->gap_open + (int64_t)sc->gap_extend < -kScoreLimit) {

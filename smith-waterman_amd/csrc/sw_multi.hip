@@ -15,19 +15,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <vector>
-#include "sw_kernels.h"
-
-namespace swh { void set_err(const char* fmt, ...); }
-using swh::set_err;
-
-#define HIP_TRYM(expr)                                                                \
-    do {                                                                              \
-        hipError_t e_ = (expr);                                                       \
-        if (e_ != hipSuccess) {                                                       \
-            set_err("%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
-            return SW_EDEVICE;                                                        \
-        }                                                                             \
-    } while (0)
+#include "sw_ctx.h"
 
 struct sw_multi_band {
     int device = 0;
@@ -56,11 +44,6 @@ struct sw_multi {
 };
 
 extern "C" {
-
-int sw_traceback_stop_device(sw_ctx* c, void* d_P, int p_elem_bytes, int64_t cols, int64_t rows, int64_t max_pos, sw_result* d_result, int64_t* d_stop,
-                             void* stream);   // sw_api.hip (library-internal)
-int sw_fill_band_reserve(sw_ctx* c, int64_t cols, int64_t rows, int64_t total_rows, const sw_scores* scores, int h_elem_bytes, int p_elem_bytes, int want_h,
-                         void* stream);       // sw_api.hip (library-internal)
 
 void sw_multi_free(sw_multi* m) {
     if (!m) return;
@@ -189,7 +172,7 @@ int sw_multi_fill(sw_multi* m, const sw_scores* scores, int nchunks, sw_result* 
     // per-context workspaces, and an allocation may wait for the device) the bands before it can always finish
     for (int g = 0; g < nb; ++g) {
         sw_multi_band& bd = m->bands[g];
-        HIP_TRYM(hipSetDevice(bd.device));
+        HIP_TRY(hipSetDevice(bd.device));
         int share = 0;
         for (int k = 0; k < nb; ++k) share += (m->bands[k].device == bd.device);
         // a band with a GPU of its own leaves a few CUs free: a peer copy normally runs on the SDMA engines, but where the runtime falls
@@ -231,7 +214,7 @@ int sw_multi_fill(sw_multi* m, const sw_scores* scores, int nchunks, sw_result* 
                 // below the next chunk's first column (the last chunk ends at cols + 1)
                 const int64_t c0 = (s0 == 0) ? 0 : ((63 * s0 + 1) & ~1ll);
                 const int64_t c1 = (s1 >= S) ? cols + 1 : ((63 * s1 + 1) & ~1ll);
-                HIP_TRYM(hipSetDevice(dst.device));
+                HIP_TRY(hipSetDevice(dst.device));
                 if (src.host_gran && dst.host_gran) {
                     for (int64_t c = c0; c < c1; ++c)
                         __atomic_store_n(dst.d_top + c, __atomic_load_n(src.d_bot + c, __ATOMIC_RELAXED), __ATOMIC_RELAXED);   // both in host-pinned memory
@@ -261,10 +244,10 @@ int sw_multi_fill(sw_multi* m, const sw_scores* scores, int nchunks, sw_result* 
     uint64_t best = 0;
     for (int g = 0; g < nb; ++g) {
         sw_multi_band& bd = m->bands[g];
-        HIP_TRYM(hipSetDevice(bd.device));
-        HIP_TRYM(hipStreamSynchronize(bd.copy));
-        HIP_TRYM(hipStreamSynchronize(bd.stream));
-        HIP_TRYM(hipMemcpy(&bd.res, bd.d_res, sizeof(sw_result), hipMemcpyDeviceToHost));
+        HIP_TRY(hipSetDevice(bd.device));
+        HIP_TRY(hipStreamSynchronize(bd.copy));
+        HIP_TRY(hipStreamSynchronize(bd.stream));
+        HIP_TRY(hipMemcpy(&bd.res, bd.d_res, sizeof(sw_result), hipMemcpyDeviceToHost));
         if (bd.res.path_len < 0) { set_err("sw_multi_fill: band %d: hand-off wait timed out", g); return SW_ETIMEOUT; }
         if (bd.res.max_score > 0) {
             const int64_t row = bd.res.max_pos / (cols + 1), col = bd.res.max_pos % (cols + 1);
@@ -290,16 +273,16 @@ int sw_multi_traceback(sw_multi* m, int64_t* path_len) {
     for (int g = (int)m->bands.size() - 1; g >= 0 && walking; --g) {
         sw_multi_band& bd = m->bands[g];
         if (!(bd.lo < row && row <= bd.hi)) continue;
-        HIP_TRYM(hipSetDevice(bd.device));
+        HIP_TRY(hipSetDevice(bd.device));
         // the band's walk stops at the first cell with P <= 0: inside the band (the end of the path) or in the band's row 0,
         // which belongs to the band above (its P is kept NONE here) -- then that band takes over at its last row
         int rc = sw_traceback_stop_device(bd.ctx, bd.d_P, m->p_elem_bytes, m->cols, bd.hi - bd.lo, (row - bd.lo) * M + col, bd.d_res, bd.d_stop, bd.stream);
         if (rc != SW_OK) return rc;
         sw_result r = {0, 0, 0};
         int64_t stop = 0;
-        HIP_TRYM(hipStreamSynchronize(bd.stream));
-        HIP_TRYM(hipMemcpy(&r, bd.d_res, sizeof r, hipMemcpyDeviceToHost));
-        HIP_TRYM(hipMemcpy(&stop, bd.d_stop, 8, hipMemcpyDeviceToHost));
+        HIP_TRY(hipStreamSynchronize(bd.stream));
+        HIP_TRY(hipMemcpy(&r, bd.d_res, sizeof r, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(&stop, bd.d_stop, 8, hipMemcpyDeviceToHost));
         walking = false;
         if (r.path_len > 0) {
             total += r.path_len;

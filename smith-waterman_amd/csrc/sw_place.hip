@@ -1,17 +1,14 @@
-// sw_place.hip -- placement of the output matrices in HBM: probe kernel + helpers.
+// sw_place.hip -- placement of the output matrices in HBM: probe kernel + helpers, and the allocator on top of them.
 //
 // Where the driver maps H and P in physical memory moves a store-bound fill by 25-35 %: physical HBM falls into a few coarse
 // "classes" (regions of several GiB), and two store streams that go to the SAME class at the same time are slower than two
 // streams into different classes.  sw_two_stream_probe reproduces the fill's store pattern -- one row segment per workgroup and
 // row, the H and the P segment of a row back to back -- on two arbitrary buffers, so that a pair can be classified in tens of
 // microseconds instead of with trial fills of the caller's problem.
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-#include <algorithm>
-#include "sw_kernels.h"
-
-namespace swh { void set_err(const char* fmt, ...); }
-using swh::set_err;
+#include <chrono>
+#include <cstdio>
+#include <vector>
+#include "sw_ctx.h"
 
 namespace swk {
 
@@ -143,6 +140,245 @@ int sw_place_pair_ratio(void* d_X, size_t xbytes, void* d_Y, size_t ybytes, floa
     }
     *ratio = sum / (float)nwin;
     if (ms_together) *ms_together = tsum / (float)nwin;
+    return SW_OK;
+}
+
+// Output matrices placed for speed.  Physical HBM falls into a few coarse classes (regions of tens of GiB), and two store streams into
+// the SAME class run ~1.4x slower than into different ones; a fill stores H[r][c] and P[r][c] together, so a 16384^2 fill takes 0.79 ms
+// with H and P in different classes and 1.05 ms with both in one (profiles/r04_placement_classes_probe.log).  Two
+// back-to-back hipMallocs land in one class.  trials <= 0 (the default): candidates for P -- from the second one on behind a temporary
+// spacer allocation, so that they come from elsewhere in the HBM -- are CLASSIFIED against H with the two-stream store probe of
+// csrc/sw_place.hip (~0.3 ms per candidate, no fill of the caller's problem), the first one in another class is kept.  trials == 1: a plain
+// pair.  trials > 1: round 3's search with trial fills of the caller's problem (kept for A/B runs).
+
+static int alloc_outputs_probed(sw_ctx* c, size_t hbytes, size_t pbytes, void** d_H, void** d_P, float* trial_ms, int ntrial_ms) {
+    const size_t phase = 4u << 20;
+    void* H = nullptr;
+    const auto t0 = std::chrono::steady_clock::now();
+    auto elapsed_ms = [&]() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); };
+    if (hipMalloc(&H, hbytes ? hbytes : 1) != hipSuccess) { (void)hipGetLastError(); set_err("sw_alloc_outputs: %zu bytes do not fit", hbytes); return SW_ENOMEM; }
+    // what a spacer can cost: 0.3 ms flat on fresh memory, 30-50 ms per GiB where the driver first wipes memory that was in use before (seen:
+    // 32 GiB in 0.2 ms, the next 64 GiB in 3.3 s) -- nothing tells beforehand, so a spacer is only tried while its worst case fits the budget
+    double ms_per_gib = 40.0;
+    struct Cand { void* base; void* P; float ratio; };
+    std::vector<Cand> cands;
+    // Candidates for P: three plain ones (a class boundary may be right here), then behind temporary spacer allocations (taken only while
+    // 8 GiB of head room remain, released as soon as the candidate behind them exists: the next spacer, of another size, then lands
+    // elsewhere).  The classes are regions of 16 .. 120 GiB in the order the driver hands memory out.  What a spacer costs depends on the
+    // box: memory that was in use before (by this or an earlier process) is wiped by the driver at ~30 GiB/s when it changes hands, fresh
+    // memory costs 0.3 ms per allocation -- so the search runs against a time budget (option "placement_budget_ms", default 1500 ms; a
+    // caller that fills many times into the pair raises it) and settles for the best candidate seen when that is spent; a spacer whose
+    // allocation alone could overrun the budget (at the wipe rate) is not tried: the default admits spacers up to 37 GiB.  The spacer that worked is
+    // remembered per context and tried first next time.
+    static const int kSpacerGiB[14] = {0, 0, 0, 32, 64, 16, 96, 48, 128, 24, 80, 8, 160, 112};
+    const bool debug = getenv("SW_PLACE_DEBUG") != nullptr;
+    // (a matrix of many GiB spans several classes itself: more sample windows, and the best of a few candidates rather than the first good one)
+    const bool big = std::max(hbytes, pbytes) > (6ull << 30);
+    const float accept = big ? 1.40f : 1.5f;   // another class: ~1.3-1.45; the same class: ~2.0
+    int best = -1, rc = SW_OK;
+    for (int i = 0; i < 14; ++i) {
+        int gib = kSpacerGiB[i];
+        if (i == 3 && c->place_spacer_gib > 0) gib = c->place_spacer_gib;                 // what worked last time, first
+        else if (i > 3 && gib == c->place_spacer_gib) continue;
+        size_t sp = (size_t)gib << 30;
+        if (sp && elapsed_ms() > (double)c->opt_place_budget_ms) break;
+        if (sp && elapsed_ms() + ms_per_gib * (double)gib > (double)c->opt_place_budget_ms) continue;   // (this spacer alone would overrun the budget: a smaller one may not)
+        if (sp) {
+            size_t fr = 0, tot = 0;
+            if (hipMemGetInfo(&fr, &tot) != hipSuccess || fr < sp + pbytes + (8ull << 30)) continue;   // not enough head room for this one
+        }
+        void* spacer = nullptr;
+        const double ts = elapsed_ms();
+        if (sp && hipMalloc(&spacer, sp) != hipSuccess) { (void)hipGetLastError(); spacer = nullptr; continue; }
+        const double ts1 = elapsed_ms();
+        Cand k = {nullptr, nullptr, 0.f};
+        const hipError_t e = hipMalloc(&k.base, pbytes + phase);
+        const double ts2 = elapsed_ms();
+        if (spacer) (void)hipFree(spacer);   // (it only steered where P landed)
+        if (sp) ms_per_gib = std::max(ms_per_gib, (elapsed_ms() - ts) / (double)gib);
+        if (debug) fprintf(stderr, "sw_alloc_outputs: spacer %d GiB: malloc %.1f ms, candidate malloc %.1f ms, free %.1f ms\n", gib, ts1 - ts, ts2 - ts1, elapsed_ms() - ts2);
+        if (e != hipSuccess) { (void)hipGetLastError(); break; }
+        // P two MiB out of phase with H modulo 4 MiB (round 1: neighbouring 2 MiB pages of the two streams)
+        const uintptr_t want = ((uintptr_t)H + (2u << 20)) % phase;
+        k.P = (char*)k.base + (want + phase - ((uintptr_t)k.base % phase)) % phase;
+        float ms = 0.f;
+        rc = sw_place_pair_ratio(H, hbytes, k.P, pbytes, &k.ratio, &ms);
+        cands.push_back(k);
+        if (rc != SW_OK) break;
+        if (debug) fprintf(stderr, "sw_alloc_outputs: candidate %d (spacer %d GiB): H %p P %p ratio %.3f (%.3f ms), %.1f ms so far\n", i, gib, H, k.P, k.ratio, ms, elapsed_ms());
+        if (trial_ms && (int)cands.size() <= ntrial_ms) trial_ms[cands.size() - 1] = ms;
+        const int prev_best = best;
+        if (best < 0 || k.ratio < cands[best].ratio) best = (int)cands.size() - 1;
+        if (big) {   // candidates of tens of GiB: only the best so far stays allocated
+            const int loser = best == (int)cands.size() - 1 ? prev_best : (int)cands.size() - 1;
+            if (loser >= 0 && cands[loser].base) { (void)hipFree(cands[loser].base); cands[loser].base = nullptr; }
+        }
+        if (k.ratio < accept) { if (gib) c->place_spacer_gib = gib; break; }
+        if (big && cands.size() >= 5) break;   // (... and the best of five)
+    }
+    // The slide.  Where no candidate is good -- matrices of many GiB span classes themselves, and so does every candidate; on a box whose
+    // memory was in use before, the driver hands out the little clean memory it has, all of one class, whatever the spacers (seen: twelve
+    // candidates in a row at ratio 2.0) -- P is allocated with slack and SLID inside its own allocation in steps of 4 GiB: one allocation is
+    // backed by whatever memory there is, dirty regions of the other classes included, and the classes are regions of 8 .. 120 GiB, so the
+    // slide changes which parts of H and P meet.  The best offset is kept; the slack stays allocated while the pair lives.  Many-GiB pairs
+    // take up to 32 GiB of slack by themselves (a few per cent of a 288 GB part for fills that are ~25 % faster); smaller pairs only what
+    // option "placement_hold_gib" allows (default 0: bench.py, which fills thousands of times into the pair, allows 48).  Only while the
+    // budget covers the worst case of that allocation.
+    c->last_place_held_gib = 0;
+    const size_t hold_max = big ? (32ull << 30) : ((size_t)c->opt_place_hold_gib << 30);
+    const bool force_slide = getenv("SW_PLACE_FORCE_SLIDE") != nullptr;   // (tests: take the slide whatever the candidates were)
+    if (hold_max >= (8ull << 30) && rc == SW_OK && best >= 0 && (cands[best].ratio >= accept || force_slide)) {
+        size_t fr = 0, tot = 0;
+        size_t slack = 0;
+        if (hipMemGetInfo(&fr, &tot) == hipSuccess && fr > pbytes + (24ull << 30)) slack = std::min<size_t>(hold_max, (fr - pbytes - (16ull << 30)) & ~((4ull << 30) - 1));
+        const double worst_ms = 40.0 * (double)((pbytes + slack) >> 30);
+        if (slack >= (8ull << 30) && elapsed_ms() + worst_ms <= (double)c->opt_place_budget_ms) {
+            void* blk = nullptr;
+            if (hipMalloc(&blk, pbytes + slack + phase) == hipSuccess) {
+                float bratio = cands[best].ratio; void* bP = nullptr;
+                for (size_t off = 0; off <= slack && rc == SW_OK; off += (4ull << 30)) {
+                    char* q = (char*)blk + off;
+                    const uintptr_t want = ((uintptr_t)H + (2u << 20)) % phase;
+                    q += (want + phase - ((uintptr_t)q % phase)) % phase;
+                    float r = 0.f, ms = 0.f;
+                    rc = sw_place_pair_ratio(H, hbytes, q, pbytes, &r, &ms);
+                    if (debug) fprintf(stderr, "sw_alloc_outputs: slide %zu GiB: ratio %.3f, %.1f ms so far\n", off >> 30, r, elapsed_ms());
+                    if (rc == SW_OK && (r < bratio || (force_slide && !bP))) { bratio = r; bP = q; }
+                    if (r < accept && !force_slide) break;
+                }
+                if (rc == SW_OK && bP) {
+                    Cand k = {blk, bP, bratio};
+                    cands.push_back(k);
+                    best = (int)cands.size() - 1;
+                    c->last_place_held_gib = (int64_t)(slack >> 30);
+                } else {
+                    (void)hipFree(blk);
+                }
+            } else {
+                (void)hipGetLastError();
+            }
+        }
+    }
+    for (int i = 0; i < (int)cands.size(); ++i)
+        if ((i != best || rc != SW_OK) && cands[i].base) (void)hipFree(cands[i].base);
+    if (rc != SW_OK || best < 0) {
+        (void)hipFree(H);
+        if (rc == SW_OK) { set_err("sw_alloc_outputs: %zu + %zu bytes do not fit", hbytes, pbytes); rc = SW_ENOMEM; }
+        return rc;
+    }
+    c->last_place_ratio = cands[best].ratio;
+    c->pair_ratio[cands[best].P] = cands[best].ratio;
+    *d_H = H; *d_P = cands[best].P;
+    c->out_base[cands[best].P] = cands[best].base;
+    return SW_OK;
+}
+
+int sw_alloc_outputs(sw_ctx* c, const char* d_a, int64_t cols, const char* d_b, int64_t rows, const sw_scores* scores, int h_elem_bytes,
+                     int p_elem_bytes, int trials, void** d_H, void** d_P, float* trial_ms) {
+    if (!c || !d_H || !d_P || cols < 0 || rows < 0 || (h_elem_bytes != 4 && h_elem_bytes != 8) || (p_elem_bytes != 4 && p_elem_bytes != 1) ||
+        (trials > 1 && (!d_a || !d_b))) {
+        set_err("sw_alloc_outputs: bad argument");
+        return SW_EINVAL;
+    }
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t cells = (size_t)(cols + 1) * (size_t)(rows + 1);
+    const size_t hbytes = cells * (size_t)h_elem_bytes, pbytes = cells * (size_t)p_elem_bytes;
+    // (below half a GiB of output the strip chain bounds a fill, not the stores: a plain pair)
+    if (trials <= 0) {
+        if (hbytes + pbytes >= (512ull << 20)) {
+            for (int i = 0; i < 16 && trial_ms; ++i) trial_ms[i] = 0.f;
+            return alloc_outputs_probed(c, hbytes, pbytes, d_H, d_P, trial_ms, 16);
+        }
+        trials = 1;
+    }
+    const size_t phase = 4u << 20;
+    struct Cand { void* H; void* Pbase; void* P; void* spacer; float ms; };
+    std::vector<Cand> cands;
+    std::vector<void*> Hs;
+    sw_result* d_res = nullptr;
+    if (hipMalloc((void**)&d_res, sizeof(sw_result)) != hipSuccess) { set_err("sw_alloc_outputs: allocation failed"); return SW_ENOMEM; }
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    (void)hipEventCreate(&e0); (void)hipEventCreate(&e1);
+    int best = -1, rc = SW_OK;
+    for (int i = 0; i < trials; ++i) {
+        Cand k = {nullptr, nullptr, nullptr, nullptr, 0.f};
+        // H stays where it is and the candidates differ in where P lands; half way through a second H is tried as well
+        if (i == 0 || (i == trials / 2 && trials >= 6 && hbytes < (8ull << 30))) {
+            void* h = nullptr;
+            if (hipMalloc(&h, hbytes ? hbytes : 1) != hipSuccess) { (void)hipGetLastError(); if (i == 0) break; }
+            else Hs.push_back(h);
+        }
+        if (Hs.empty()) break;
+        k.H = Hs.back();
+        // Measured (scripts/ab_arena.py, profiles/r02_placement_arena.log): inside one 96 GiB allocation a 16384^2 fill takes
+        // 1.12 ms when H and P lie on different sides of the 64 GiB mark and 1.38-1.47 ms when they share a side, whatever
+        // their distance.  So from the second candidate on a spacer of 64 GiB (then 32, 96, 48, 80) is allocated between
+        // H and P -- and released again when the search ends: no memory stays held.
+        // (a box where five of the first six candidates were slow has been seen: the search goes on to sixteen before it settles for a slow one)
+        static const int kSpacerGiB[16] = {0, 64, 96, 32, 128, 48, 160, 80, 16, 112, 144, 24, 176, 72, 104, 56};
+        size_t sp = (i > 0 && hbytes < (8ull << 30)) ? (size_t)kSpacerGiB[i % 16] << 30 : 0;
+        if (sp) {
+            size_t fr = 0, tot = 0;
+            if (hipMemGetInfo(&fr, &tot) != hipSuccess || fr < sp + pbytes + (8ull << 30)) sp = 0;   // not enough head room: plain candidate
+        }
+        if (!sp || hipMalloc(&k.spacer, sp) != hipSuccess) { (void)hipGetLastError(); k.spacer = nullptr; }
+        if (hipMalloc(&k.Pbase, pbytes + phase) != hipSuccess) { (void)hipGetLastError(); if (k.spacer) (void)hipFree(k.spacer); break; }
+        // P two MiB out of phase with H modulo 4 MiB
+        const uintptr_t want = ((uintptr_t)k.H + (2u << 20)) % phase;
+        const uintptr_t off = (want + phase - ((uintptr_t)k.Pbase % phase)) % phase;
+        k.P = (char*)k.Pbase + off;
+        if (trials > 1) {
+            for (int f = 0; f < 4 && rc == SW_OK; ++f) {
+                if (f == 1) (void)hipEventRecord(e0, nullptr);
+                rc = sw_fill_device_ex(c, d_a, cols, d_b, rows, scores, k.H, h_elem_bytes, k.P, p_elem_bytes, nullptr, d_res, nullptr);
+            }
+            (void)hipEventRecord(e1, nullptr);
+            if (rc == SW_OK && hipEventSynchronize(e1) != hipSuccess) { set_err("sw_alloc_outputs: trial fill failed"); rc = SW_EDEVICE; }
+            if (rc == SW_OK) { (void)hipEventElapsedTime(&k.ms, e0, e1); k.ms /= 3.f; }
+        }
+        // the spacer only steers where P lands: release it before the next candidate is placed
+        if (k.spacer) { (void)hipFree(k.spacer); k.spacer = nullptr; }
+        cands.push_back(k);
+        if (rc != SW_OK) break;
+        if (trial_ms) trial_ms[i] = k.ms;
+        if (best < 0 || k.ms < cands[best].ms) best = (int)cands.size() - 1;
+        if ((int)cands.size() >= std::min(trials, 6)) {   // several placements seen (there are half-good ones) and clearly in the fast mode: stop looking
+            float worst = 0.f;   // (the first candidate also pays the one-time costs of the first launches: not a placement signal)
+            for (size_t x = 1; x < cands.size(); ++x) worst = std::max(worst, cands[x].ms);
+            if (cands[best].ms < 0.80f * worst) {   // (fast and slow mode are 20-25 % apart; the two-column kernel also has a half-good one in between)
+                for (int j = i + 1; j < trials && trial_ms; ++j) trial_ms[j] = 0.f; break; }
+        }
+    }
+    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
+    (void)hipFree(d_res);
+    for (int i = 0; i < (int)cands.size(); ++i) {
+        if (cands[i].spacer) (void)hipFree(cands[i].spacer);
+        if (i != best || rc != SW_OK) (void)hipFree(cands[i].Pbase);
+    }
+    for (void* h : Hs)
+        if (best < 0 || rc != SW_OK || h != cands[best].H) (void)hipFree(h);
+    if (rc != SW_OK) return rc;
+    if (best < 0) { set_err("sw_alloc_outputs: %zu + %zu bytes do not fit", hbytes, pbytes); return SW_ENOMEM; }
+    *d_H = cands[best].H; *d_P = cands[best].P;
+    c->out_base[cands[best].P] = cands[best].Pbase;
+    if (hbytes + pbytes >= (512ull << 20)) {   // (which kind of pair it is decides the strip geometry of fills into it: launch_fill)
+        float r = 0.f, ms = 0.f;
+        if (sw_place_pair_ratio(*d_H, hbytes, *d_P, pbytes, &r, &ms) == SW_OK) { c->pair_ratio[*d_P] = r; c->last_place_ratio = r; }
+    }
+    return SW_OK;
+}
+
+int sw_free_outputs(sw_ctx* c, void* d_H, void* d_P) {
+    if (!c) { set_err("sw_free_outputs: bad argument"); return SW_EINVAL; }
+    HIP_TRY(hipSetDevice(c->device));
+    if (d_H) HIP_TRY(hipFree(d_H));
+    if (d_P) {
+        auto it = c->out_base.find(d_P);
+        void* base = (it != c->out_base.end()) ? it->second : d_P;
+        if (it != c->out_base.end()) c->out_base.erase(it);
+        c->pair_ratio.erase(d_P);
+        HIP_TRY(hipFree(base));
+    }
     return SW_OK;
 }
 

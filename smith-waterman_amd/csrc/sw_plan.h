@@ -3,7 +3,7 @@
 // per lane, pairs per launch, the kernel of every launch) and of one database search (columns per lane, profile kind, grid, schedule;
 // plan_search_affine for the affine-gap search) and of one alignment call (plan_align_affine: columns per lane, slots, grid, order of the hits),
 // and the workspace sizes they need, as pure functions of the job, the device and the options.  Plain C++ (no HIP include):
-// sw_api.hip carries a plan out, tests/test_fill_plan.py and tests/test_batch_plan.py check the policy on a CPU.
+// sw_api_fill.hip and sw_api_search.hip carry a plan out, tests/test_fill_plan.py and tests/test_batch_plan.py check the policy on a CPU.
 #pragma once
 #include <cstddef>
 #include <cstdint>
@@ -34,7 +34,7 @@ struct PlanJob {
     float pair_ratio = 0.f;                  // store probe's two-stream / one-stream time of the H / P pair (~1.4: two classes of the HBM, ~2: one); 0: unknown
 };
 
-// sw_search_wave<C, WIDE> for C = 4, 8, 16: its index in kSearch (sw_api.hip, which checks its order against it at compile time)
+// sw_search_wave<C, WIDE> for C = 4, 8, 16: its index in kSearch (sw_api_search.hip, which checks its order against it at compile time)
 constexpr int kSearchKernels = 6;
 constexpr int search_kernel_index(int C, bool wide) { return 2 * (C / 8) + wide; }
 
@@ -123,7 +123,7 @@ struct BatchPlan {
 
 BatchPlan plan_batch(const BatchJob& job, const PlanOptions& opt);
 
-// The batch kernels: their indices in kBatch (sw_api.hip, which checks its order against them at compile time).  sw_batch_wave<C, PB> for
+// The batch kernels: their indices in kBatch (sw_api_fill.hip, which checks its order against them at compile time).  sw_batch_wave<C, PB> for
 // C = 4, 8, 16 and PB = 0, 1, 4 first, then sw_batch_wave16<LE4, K12, PB1> (two pairs per wave) from kBatchWave16 on.
 constexpr int kBatchWave16 = 9, kBatchKernels = 17;
 constexpr int batch_wave_index(int C, int pb) { return 3 * (C / 8) + (pb == 4 ? 2 : pb); }
@@ -153,7 +153,7 @@ struct SearchPlan {
 SearchPlan plan_search(const SearchJob& job, const DeviceFacts& dev);
 
 // ---- database search with a substitution matrix and affine gaps (sw_search_affine_device): sw_search_affine_wave<C> for C = 4, 8, 16,
-// its index in kSearchAffine (sw_api.hip, which checks its order against it at compile time)
+// its index in kSearchAffine (sw_api_search.hip, which checks its order against it at compile time)
 constexpr int kSearchAffineKernels = 3;
 constexpr int search_affine_kernel_index(int C) { return C / 8; }
 
@@ -178,7 +178,7 @@ struct SearchAffinePlan {
 SearchAffinePlan plan_search_affine(const SearchAffineJob& job);
 
 // ---- alignment of chosen hits under affine scoring (sw_align_affine_device): sw_align_affine_wave<C> for C = 4, 8, 16, its index in
-// kAlignAffine (sw_api.hip, which checks its order against it at compile time)
+// kAlignAffine (sw_api_search.hip, which checks its order against it at compile time)
 constexpr int kAlignAffineKernels = 3;
 constexpr int align_affine_kernel_index(int C) { return C / 8; }
 

@@ -4,7 +4,7 @@ tests/test_score_range_gpu.py runs it: every output of every case bit for bit ag
 "last_strips2", "last_batch_kernel", "last_search_kernel").
 
 The lines, with the constants quoted BY NAME from smith-waterman_amd/csrc/sw_plan.cpp (plan_fill, plan_batch, plan_search) and from
-check_dims in sw_api.hip.  The sizes of the cases are computed from these copies; test_score_range_host.py holds every case's expected
+check_dims in sw_ctx.h.  The sizes of the cases are computed from these copies; test_score_range_host.py holds every case's expected
 route against what the planners decide, so a constant that moves in sw_plan.cpp makes a route assertion fail instead of moving a
 case off its edge unnoticed."""
 import zlib
@@ -52,7 +52,7 @@ def widest_perm_cols(rows, scores, total_rows=0):
 
 
 def dims_ok(cols, rows, scores):
-    """check_dims (sw_api.hip) for a whole matrix"""
+    """check_dims (sw_ctx.h) for a whole matrix"""
     match, mismatch, gap = scores
     if gap > 0 or match < 0 or mismatch > match:
         return False

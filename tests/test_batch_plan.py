@@ -11,7 +11,7 @@ import pytest
 from test_fill_plan import driver  # noqa: F401  (the driver, built once per module)
 
 SINGLE_PAIR, NO_WAVE16, NO_PACKED_P = 1 << 16, 1 << 18, 1 << 21
-# The order of kBatch in sw_api.hip (a static_assert there holds every entry to swp::batch_wave_index / batch_wave16_index).
+# The order of kBatch in sw_api_fill.hip (a static_assert there holds every entry to swp::batch_wave_index / batch_wave16_index).
 KBATCH = [("wave", 4, 0), ("wave", 4, 1), ("wave", 4, 4), ("wave", 8, 0), ("wave", 8, 1), ("wave", 8, 4), ("wave", 16, 0), ("wave", 16, 1),
           ("wave", 16, 4)] + [("wave16", le4, k12, pb1) for le4 in (0, 1) for k12 in (0, 1) for pb1 in (0, 1)]
 

@@ -161,6 +161,75 @@ def test_repeated_calls_regrow_workspaces(checker, swamd):  # noqa: F811
         eng.close()
 
 
+def test_three_families_interleaved_on_one_fresh_context(swamd, oracle, checker):  # noqa: F811
+    """sw_search_device, sw_search_affine_device and sw_align_affine_device share the schedule, profile, boundary, counter and table
+    workspaces and the pinned copies the schedule and the table are uploaded from.  A fresh context, no host synchronisation between the
+    calls, every call with more targets or hits than the one before (3 -> 40 -> 60 hits -> 120 -> 200 on a second stream), then one with
+    fewer: the workspaces are reallocated while earlier uploads may still be in flight, the table is first allocated between two plain
+    searches, and every call brings a table of its own.  Every result bit for bit against the host references."""
+    import torch
+    rng = np.random.default_rng(41)
+    dbs = {3: [5, 0, 5],                                                       # an empty target and a length tie
+           40: [0, 90, 90] + list(rng.integers(0, 91, 37)),
+           200: [90, 0, 1, 90] + list(rng.integers(0, 91, 196))}
+    dbs = {n: swamd._pack_targets([rng.choice(PROTEIN, int(k)).astype(np.uint8) for k in lens]) for n, lens in dbs.items()}
+    q63, q300 = (rng.choice(PROTEIN, n).astype(np.uint8) for n in (63, 300))   # one strip; more columns than one strip of 4 per lane
+    subs = [random_submat(rng) for _ in range(4)]
+    hits60 = np.concatenate([[0, 1, 2, 1], rng.integers(0, 40, 56)]).astype(np.int64)
+    hits5 = np.array([2, 0, 39, 2, 1], np.int64)
+    cap = 300 + 90
+    eng = swamd.Engine(0)                                                      # a fresh context: every workspace starts empty
+    try:
+        dev = lambda x: torch.from_numpy(np.concatenate([x, np.zeros(16, np.uint8)])).to("cuda:0")  # noqa: E731
+        d63, d300 = dev(q63), dev(q300)
+        ddb = {n: dev(packed) for n, (packed, _) in dbs.items()}
+        res = lambda n: torch.full((max(1, n), 3), 7, dtype=torch.int64, device="cuda:0")  # noqa: E731
+        alns = lambda n: (torch.full((n, 7), 7, dtype=torch.int64, device="cuda:0"), torch.zeros((n, cap), dtype=torch.uint8, device="cuda:0"))  # noqa: E731
+        r0, r1, r2, r4, r5, o3, o6 = res(0), res(3), res(40), res(120), res(200), alns(60), alns(5)
+        second = torch.cuda.Stream()
+        torch.cuda.synchronize()
+        eng.search_device(d63, 63, ddb[3], dbs[3][1][:1], out=r0)                                   # no target at all: nothing happens
+        eng.search_device(d63, 63, ddb[3], dbs[3][1], out=r1)
+        eng.search_affine_device(d300, 300, ddb[40], dbs[40][1], subs[0], -10, -1, out=r2)
+        eng.align_affine_device(d300, 300, ddb[40], dbs[40][1], subs[1], -3, -2, hits60, ops_cap=cap, out=o3)
+        eng.search_device(d300, 300, ddb[200], dbs[200][1][:121], (5, -3, -4), out=r4)
+        with torch.cuda.stream(second):
+            eng.search_affine_device(d63, 63, ddb[200], dbs[200][1], subs[2], 0, -2, out=r5)
+        eng.align_affine_device(d300, 300, ddb[40], dbs[40][1], subs[3], -4, 0, hits5, ops_cap=cap, out=o6)
+        torch.cuda.synchronize()
+    finally:
+        eng.close()
+    assert (r0.cpu().numpy() == 7).all()
+
+    def linear(query, n, ntargets, scores, got):
+        packed, offs = dbs[n]
+        exp = np.zeros((ntargets, 3), np.int64)
+        for k in range(ntargets):
+            if offs[k + 1] > offs[k]:
+                o = oracle.fill_streaming(query, packed[offs[k]:offs[k + 1]], scores)
+                exp[k] = (o["max_pos"], o["max_score"], 0)
+        assert_same(got.cpu().numpy(), exp, f"linear search, {ntargets} targets")
+
+    def affine(query, n, sub, go, ge, got):
+        exp = checker.search(query, *dbs[n], sub, go, ge)
+        assert np.array_equal(swamd.search_affine_host(query, dbs[n], sub, go, ge), exp)
+        assert_same(got.cpu().numpy(), exp, f"affine search, {n} targets")
+
+    def aligned(query, n, sub, go, ge, hits, got):
+        exp_aln, exp_ops = swamd.align_affine_host(query, dbs[n], sub, go, ge, hits)
+        assert np.array_equal(exp_aln[:, :2], checker.search(query, *dbs[n], sub, go, ge)[hits, :2])
+        aln = got[0].cpu().numpy()
+        assert np.array_equal(aln, exp_aln), f"alignment of {len(hits)} hits: rows {np.nonzero((aln != exp_aln).any(axis=1))[0][:5]} differ"
+        assert swamd._ops_list(aln, got[1].cpu().numpy(), cap) == exp_ops, f"alignment of {len(hits)} hits: ops differ"
+
+    linear(q63, 3, 3, (3, -3, -2), r1)
+    affine(q300, 40, subs[0], -10, -1, r2)
+    aligned(q300, 40, subs[1], -3, -2, hits60, o3)
+    linear(q300, 200, 120, (5, -3, -4), r4)
+    affine(q63, 200, subs[2], 0, -2, r5)
+    aligned(q300, 40, subs[3], -4, 0, hits5, o6)
+
+
 def test_scores_just_below_the_limit_and_one_step_over(engine, swamd):
     L = -(-(1 << 24) // 127) - 1                               # 127 L < 2^24 <= 127 (L + 1)
     assert 127 * L < (1 << 24) <= 127 * (L + 1)
