@@ -20,7 +20,7 @@
  *     element type (d_H: 4 or 8 bytes, int32 d_P: 4, int8 d_P: any address, sw_result / sw_alignment / granules: 8); base addresses
  *     that are not 8-byte aligned (16 for an int64 d_H) only cost the whole-line stores of the widest fills.
  *   - READ extents, from the kernels' loads.  Input sequences need no alignment except d_b of the fills and batches (16 bytes, below).
- *     sw_batch_device*, sw_search_device, sw_search_affine_device and sw_align_affine_device read no byte outside
+ *     sw_batch_device*, sw_search_device, sw_search_affine_device, sw_db_search_affine and sw_align_affine_device read no byte outside
  *     [d_a + k*a_stride, + cols), [d_b + k*b_stride, + rows), [d_query, + qlen) and [d_db + offsets[0], d_db + offsets[ntargets]): the
  *     gaps of padded strides and the bytes around the query and the database are never loaded.  sw_fill_device, sw_fill_device_ex and
  *     sw_fill_band_device read a and b, and besides them at most the rest of the 16-byte ALIGNED windows that hold the first and the last
@@ -272,6 +272,40 @@ int sw_align_affine_device(sw_ctx* ctx, const char* d_query, int64_t qlen, const
 int sw_align_affine_host(const char* query, int64_t qlen, const char* db, const int64_t* offsets, int64_t ntargets,
                          const int64_t* hits, int64_t nhits, const sw_affine* scoring,
                          sw_alignment* aln, char* ops, int64_t ops_cap);
+/* A prepared database and the search of MANY queries against it (csrc/sw_search_multi.hip).  sw_search_affine_device checks the offsets,
+ * sorts the target lengths and builds its schedule anew for every query; a handle does that once, and one call then runs every
+ * (query, target) pair of a set of queries from one work counter per launch -- short queries and small databases fill the device together.
+ *   sw_db_create  d_db and offsets as for sw_search_device: device bytes back to back, a HOST array of ntargets + 1 non-decreasing
+ *                 offsets (offsets[0] may be > 0, empty targets allowed), copied as far as needed.  The handle BORROWS d_db: the caller
+ *                 keeps it alive and unchanged until sw_db_free.  The handle owns the schedule on the device (24 bytes per non-empty
+ *                 target).  Synchronous.  ntargets == 0 gives a valid, empty handle.  SW_EINVAL: NULL pointers, ntargets < 0, the
+ *                 offsets / length errors of sw_search_device.  Free the handle before the context's device is reset.
+ *   sw_db_info    every out pointer is optional: targets, non-empty targets, the longest target, offsets[ntargets] - offsets[0].
+ *   sw_db_search_affine
+ *     d_queries : device, the queries back to back: query q = d_queries[qoffsets[q] .. qoffsets[q+1]), no alignment asked
+ *     qoffsets  : HOST, nqueries + 1 non-decreasing int64, qoffsets[0] >= 0; copied before the call returns
+ *     d_results : device, QUERY-MAJOR, nqueries x ntargets sw_result: d_results[q * ntargets + k] is bit for bit what
+ *                 sw_search_affine_device writes for query q and target k -- the recurrence, the arg-max rule, max_pos in that pair's own
+ *                 (len_k + 1) x (qlen_q + 1) layout, {0, 0, 0} for empty targets.  Every entry is written.
+ *     Asynchronous on `stream`, no host round trip; the table is HOST memory, copied before the call returns.  The host work of a call
+ *     is O(nqueries): it never reads the targets' offsets again and never sorts.  Linear gaps: pass sw_submat_match's table with
+ *     gap_open = 0, which equals sw_search_device bit for bit (above).  The queries' profiles (257 x padded length bytes each) share a
+ *     per-context workspace that the option "search_profile_mib" bounds (default 256, at least 1): queries are taken in consecutive
+ *     groups that fit it, and a query whose own profile exceeds it runs as a group of its own -- the option refuses nothing.
+ *     SW_EINVAL: NULL pointers, nqueries < 0, decreasing qoffsets or qoffsets[0] < 0, a query of length 0 or above 2^20 - 1, the
+ *     scoring errors of sw_search_affine_device with the 24-bit bound taken over the LONGEST query, a handle created on another
+ *     context's device.  nqueries == 0 returns SW_OK and launches nothing; a handle without a non-empty target only zeroes the results.
+ *   sw_search_affine_multi_host  the CPU leg: sw_search_affine_host query after query, the same result layout, no GPU needed; every
+ *     argument is checked before the first query runs. */
+typedef struct sw_db sw_db;
+int  sw_db_create(sw_ctx* ctx, const char* d_db, const int64_t* offsets, int64_t ntargets, sw_db** out);
+void sw_db_free(sw_db* db);
+int  sw_db_info(const sw_db* db, int64_t* ntargets, int64_t* nonempty, int64_t* longest, int64_t* letters);
+int  sw_db_search_affine(sw_ctx* ctx, const sw_db* db, const char* d_queries, const int64_t* qoffsets, int64_t nqueries,
+                         const sw_affine* scoring, sw_result* d_results, void* stream);
+int  sw_search_affine_multi_host(const char* queries, const int64_t* qoffsets, int64_t nqueries, const char* db,
+                                 const int64_t* offsets, int64_t ntargets, const sw_affine* scoring, sw_result* results);
+
 /* Tables.  sw_submat_match: s[x][y] = x == y ? match : mismatch (matchMissmatchScore, serial_smithW.c:251-256; both must fit int8:
  * the builder returns nothing, so it clamps them to -128..127 -- a caller that takes them from a user checks the range first, as
  * smithW and the Python wrapper do, which refuse such scores).  sw_submat_from_letters: `scores` is n x n, row = query letter, over the n bytes of
@@ -447,7 +481,9 @@ int sw_synchronize(sw_ctx* ctx, void* stream);   /* waits for `stream`; reports 
  * wave on packed lanes), "last_search_kernel" (the last search: 2 * (columns per lane / 8) + 1 for the wide profile), "last_search_affine_kernel"
  * (the last affine search: columns per lane / 8) and "last_search_affine_grid" (its workgroups), "last_align_affine_kernel" (the
  * last sw_align_affine_device call: columns per lane / 8) and "last_align_affine_slots" (its direction matrices, one per wave at
- * work); "align_workspace_mib" (settable, default 1024) bounds the direction workspace of that call. */
+ * work); "align_workspace_mib" (settable, default 1024) bounds the direction workspace of that call; "search_profile_mib" (settable,
+ * default 256) bounds the profiles of a group of sw_db_search_affine, "last_search_multi_groups", "last_search_multi_launches" and
+ * "last_search_multi_grid" (workgroups of its last launch) describe the last such call. */
 int sw_set_option(sw_ctx* ctx, const char* name, int64_t value);
 int64_t sw_get_option(sw_ctx* ctx, const char* name);
 

@@ -9,6 +9,10 @@
   (a) then aligns the top 100 and the top 1000 hits of the affine search (sw_align_affine_device): a_align<K>_ms per call, the
   re-filled cells per second, the walk's share of the waves' time (the kernel's own tick stamps, option "debug_buf") beside the
   affine search call's time; --only-a stops after (a)
+  --multi: data set (a) only, through a prepared database (sw_db_create / sw_db_search_affine): 1, 8 and 64 queries of --qlen in ONE call
+  beside the same number of sw_search_affine_device calls in the same process (multi<N>_ms / single<N>_ms, and both per query), 64
+  queries of log-normal length (median 300) likewise, and 64 queries of 32 letters against the first 2000 targets -- the case where a
+  launch per query leaves most of the device idle
 GCUPS = query letters x target letters / time of the call (torch events, median of --reps after --warmup)."""
 import argparse
 import importlib
@@ -51,6 +55,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--only-a", action="store_true", help="data set (a) only: linear search, affine search, alignment of its top hits")
+    ap.add_argument("--multi", action="store_true", help="data set (a) only: many queries through a prepared database against one call per query")
     args = ap.parse_args()
     rng = np.random.default_rng(2026)
     eng = swamd.Engine(0)
@@ -121,6 +126,38 @@ def main():
         out[f"{tag}_gcups"] = round(float(cols) * rows * npairs / ms / 1e6, 1)
         return res
 
+    def multi_legs(packed, offs):
+        import time
+        d_db = torch.from_numpy(packed.copy()).to(dev)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        db = eng.prepare_db(d_db, offs)
+        out["multi_prepare_ms"] = round((time.perf_counter() - t0) * 1e3, 3)
+        small = eng.prepare_db(d_db, offs[:2001])
+        qlog = np.clip(np.round(rng.lognormal(np.log(300), 0.6, 64)), 1, 35_000).astype(np.int64)
+        for tag, qlens, handle, toffs in [("1", [args.qlen], db, offs), ("8", [args.qlen] * 8, db, offs), ("64", [args.qlen] * 64, db, offs),
+                                          ("64_lognormal", list(qlog), db, offs), ("64_short_small_db", [32] * 64, small, offs[:2001])]:
+            qoffs = np.zeros(len(qlens) + 1, np.int64)
+            qoffs[1:] = np.cumsum(qlens)
+            d_q = torch.from_numpy(rng.choice(PROTEIN, int(qoffs[-1])).astype(np.uint8)).to(dev)
+            nt = len(toffs) - 1
+            res = torch.zeros(len(qlens) * nt * 3, dtype=torch.int64, device=dev)
+            ref = torch.zeros((len(qlens), nt, 3), dtype=torch.int64, device=dev)
+            ms = timed(lambda: handle.search_affine_device(d_q, qoffs, (sub, -11, -1), out=res), args.warmup, args.reps)
+
+            def one_by_one():
+                for k in range(len(qlens)):
+                    eng.search_affine_device(d_q[int(qoffs[k]):], int(qlens[k]), d_db, toffs, sub, -11, -1, out=ref[k])
+            ms1 = timed(one_by_one, args.warmup, args.reps)
+            cells = float(qoffs[-1]) * float(toffs[-1] - toffs[0])
+            out[f"multi{tag}_ms"], out[f"single{tag}_ms"] = round(ms, 3), round(ms1, 3)
+            out[f"multi{tag}_ms_per_query"], out[f"single{tag}_ms_per_query"] = round(ms / len(qlens), 3), round(ms1 / len(qlens), 3)
+            out[f"multi{tag}_gcups"], out[f"single{tag}_gcups"] = round(cells / ms / 1e6, 1), round(cells / ms1 / 1e6, 1)
+            out[f"multi{tag}_launches"] = eng.get_option("last_search_multi_launches")
+            out[f"multi{tag}_identical"] = bool(torch.equal(res.view(len(qlens), nt, 3), ref))
+        db.close()
+        small.close()
+
     # (a) protein database, log-normal lengths
     q = rng.choice(PROTEIN, args.qlen).astype(np.uint8)
     lens = np.clip(np.round(rng.lognormal(np.log(300), 0.6, args.targets)), 1, 35_000).astype(np.int64)
@@ -130,6 +167,11 @@ def main():
     out["a_letters"] = int(offs[-1])
     out["a_len_median"] = int(np.median(lens))
     out["a_len_max"] = int(lens.max())
+    if args.multi:
+        multi_legs(packed, offs)
+        eng.close()
+        print(json.dumps(out))
+        return
     search_gcups(q, packed, offs, "a")
     align_legs(q, packed, offs, affine_gcups(q, packed, offs, "a"), "a")
     if args.only_a:

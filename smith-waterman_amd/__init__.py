@@ -64,6 +64,11 @@ ABI = {
     "sw_search_device": (_i32, [_vp, _vp, _i64, _vp, _vp, _i64, ctypes.POINTER(_Scores), _vp, _vp]),
     "sw_search_affine_device": (_i32, [_vp, _vp, _i64, _vp, _vp, _i64, ctypes.POINTER(_Affine), _vp, _vp]),
     "sw_search_affine_host": (_i32, [_vp, _i64, _vp, _vp, _i64, ctypes.POINTER(_Affine), _vp]),
+    "sw_db_create": (_i32, [_vp, _vp, _vp, _i64, ctypes.POINTER(_vp)]),
+    "sw_db_free": (None, [_vp]),
+    "sw_db_info": (_i32, [_vp, ctypes.POINTER(_i64), ctypes.POINTER(_i64), ctypes.POINTER(_i64), ctypes.POINTER(_i64)]),
+    "sw_db_search_affine": (_i32, [_vp, _vp, _vp, _vp, _i64, ctypes.POINTER(_Affine), _vp, _vp]),
+    "sw_search_affine_multi_host": (_i32, [_vp, _vp, _i64, _vp, _vp, _i64, ctypes.POINTER(_Affine), _vp]),
     "sw_align_affine_device": (_i32, [_vp, _vp, _i64, _vp, _vp, _i64, _vp, _i64, ctypes.POINTER(_Affine), _vp, _vp, _i64, _vp]),
     "sw_align_affine_host": (_i32, [_vp, _i64, _vp, _vp, _i64, _vp, _i64, ctypes.POINTER(_Affine), _vp, _vp, _i64]),
     "sw_submat_match": (None, [_i32, _i32, _vp]),
@@ -229,6 +234,22 @@ def search_affine_host(query, targets, submat, gap_open: int, gap_extend: int, t
     return (out, top_hits(out, top)) if top is not None else out
 
 
+def search_affine_multi_host(queries, targets, scoring):
+    """sw_search_affine_multi_host: every query against every target in plain C++ on the host (no GPU).  Arguments and result as
+    Database.search_affine: queries a list of sequences or a (packed, offsets) pair, scoring = (submat, gap_open, gap_extend); returns the
+    (nqueries, ntargets, 3) int64 array of (max_pos, max_score, path_len = 0)."""
+    qpacked, qoffs = _pack_targets(queries)
+    packed, offs = _pack_targets(targets)
+    nq, ntargets = len(qoffs) - 1, len(offs) - 1
+    qs = qpacked if len(qpacked) else np.zeros(1, np.uint8)
+    db = packed if len(packed) else np.zeros(1, np.uint8)
+    res = np.zeros((max(1, nq * ntargets), 3), np.int64)
+    sub, sc = _affine(*scoring)
+    _check(lib().sw_search_affine_multi_host(qs.ctypes.data, qoffs.ctypes.data, nq, db.ctypes.data, offs.ctypes.data, ntargets, ctypes.byref(sc),
+                                             res.ctypes.data))
+    return res[:nq * ntargets].reshape(nq, ntargets, 3)
+
+
 def _ops_list(aln, ops, cap):
     """The ops rows of an alignment call as a list of bytes, each cut to its nops."""
     return [ops[h, :aln[h, 6]].tobytes() if aln[h, 6] <= cap else b"" for h in range(len(aln))]
@@ -367,6 +388,73 @@ class _Outputs:
         self.dH = self.dP = None
 
     __del__ = free
+
+
+class Database:
+    """A prepared database (sw_db): Engine.prepare_db makes one.  The checks of the offsets and the schedule of the targets are done once;
+    search_affine then takes any number of queries per call.  Keeps the device bytes of the database alive; close() (or leaving the
+    `with` block) frees the handle."""
+
+    def __init__(self, engine: "Engine", d_db, offsets):
+        self.engine, self.d_db = engine, d_db
+        offs = np.ascontiguousarray(offsets, np.int64).reshape(-1)
+        if len(offs) == 0:
+            offs = np.zeros(1, np.int64)
+        self.ntargets = len(offs) - 1
+        h = _vp()
+        _check(lib().sw_db_create(engine._h, d_db.data_ptr(), offs.ctypes.data, self.ntargets, ctypes.byref(h)))
+        self._h = h
+
+    def close(self):
+        if getattr(self, "_h", None):
+            try:
+                lib().sw_db_free(self._h)
+            except Exception:  # interpreter shutdown: module globals are already gone
+                pass
+            self._h = None
+
+    __del__ = close
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def info(self):
+        """{"ntargets", "nonempty", "longest", "letters"} of the handle (sw_db_info)."""
+        v = [_i64() for _ in range(4)]
+        _check(lib().sw_db_info(self._h, *[ctypes.byref(x) for x in v]))
+        return dict(zip(("ntargets", "nonempty", "longest", "letters"), (x.value for x in v)))
+
+    def search_affine(self, queries, scoring):
+        """Every query against every target (sw_db_search_affine).  queries: a list of sequences or a (packed uint8, int64 offsets) pair;
+        scoring = (submat, gap_open, gap_extend) as for Engine.search_affine.  Returns the (nqueries, ntargets, 3) int64 numpy array of
+        (max_pos, max_score, path_len = 0), both axes in input order."""
+        eng = self.engine
+        t = eng.torch
+        qpacked, qoffs = _pack_targets(queries)
+        d_q = t.from_numpy(qpacked.copy() if len(qpacked) else np.zeros(1, np.uint8)).to(f"cuda:{eng.device}")
+        res = self.search_affine_device(d_q, qoffs, scoring)
+        eng.synchronize()
+        return res.cpu().numpy()
+
+    def search_affine_device(self, d_queries, qoffsets, scoring, out=None):
+        """sw_db_search_affine on device-resident queries (a torch uint8 tensor), host int64 offsets and a host table; asynchronous on
+        torch's current stream.  Returns the (nqueries, ntargets, 3) int64 result tensor (a view of `out`, a flat int64 tensor of at
+        least nqueries * ntargets * 3 elements, if given)."""
+        eng = self.engine
+        t = eng.torch
+        qoffs = np.ascontiguousarray(qoffsets, np.int64).reshape(-1)
+        if len(qoffs) == 0:
+            qoffs = np.zeros(1, np.int64)
+        nq, n = len(qoffs) - 1, (len(qoffs) - 1) * self.ntargets * 3
+        res = out if out is not None else t.zeros(max(3, n), dtype=t.int64, device=f"cuda:{eng.device}")
+        if res.dtype != t.int64 or not res.is_contiguous() or res.numel() < n:
+            raise ValueError(f"out must be a contiguous int64 tensor of at least {n} elements ({nq} queries x {self.ntargets} targets x 3)")
+        sub, sc = _affine(*scoring)
+        _check(lib().sw_db_search_affine(eng._h, self._h, d_queries.data_ptr(), qoffs.ctypes.data, nq, ctypes.byref(sc), res.data_ptr(), eng._stream()))
+        return res[:n].view(nq, self.ntargets, 3)
 
 
 class Engine:
@@ -618,6 +706,19 @@ class Engine:
         _check(lib().sw_search_affine_device(self._h, d_query.data_ptr(), qlen, d_db.data_ptr(), offs.ctypes.data, ntargets, ctypes.byref(sc),
                                              res.data_ptr(), self._stream()))
         return res[:ntargets]
+
+    def prepare_db(self, db, offsets=None) -> Database:
+        """A prepared database (sw_db_create) for Database.search_affine.  db: a list of sequences, a (packed, offsets) pair, or --
+        with `offsets` given -- a torch uint8 device tensor of the targets back to back, which the handle keeps alive and which must
+        not change while the handle lives.  Use as a context manager or close() it."""
+        t = self.torch
+        if offsets is None:
+            packed, offsets = _pack_targets(db)
+            db = t.from_numpy(packed.copy() if len(packed) else np.zeros(1, np.uint8)).to(f"cuda:{self.device}")
+        elif not isinstance(db, t.Tensor):
+            packed = np.ascontiguousarray(db, np.uint8).reshape(-1)
+            db = t.from_numpy(packed.copy() if len(packed) else np.zeros(1, np.uint8)).to(f"cuda:{self.device}")
+        return Database(self, db, offsets)
 
     def align_affine(self, query, targets, submat, gap_open: int, gap_extend: int, hits):
         """The alignments of the targets `hits` (indices, any order, duplicates allowed) under affine scoring

@@ -7,6 +7,9 @@
 //     ... --matrix FILE --gap-open O --gap-extend E   substitution matrix (NCBI text format) and affine gaps (sw_search_affine_device): a gap of k
 //                              letters scores O + k E; without --matrix the table is match / mismatch of --scores (signed bytes),
 //                              without --gap-extend E = the gap of --scores; --gap-extend alone (O = 0) is the linear search with gap E
+//     ... --all-queries       EVERY record of Q.fa through one prepared database handle and one call (sw_db_create / sw_db_search_affine): the
+//                              hit block of --search once per query, each under a line "## query record <i> of <Q.fa>"; --top, --matrix,
+//                              --gap-open, --gap-extend and --align (sw_align_affine_device per query) as for one query
 //     ... --align             every printed hit is followed by its alignment (sw_align_affine_device; the canonical alignment of swhip.h), four lines:
 //                                "align\t<q_begin>\t<q_end>\t<t_begin>\t<t_end>\t<nops>"   query [q_begin, q_end) against target [t_begin, t_end), 0-based, half open
 //                                "Q <query letters, '-' where the target has letters of its own>"
@@ -97,37 +100,10 @@ static bool parse_int(const char* flag, const char* text, int* out) {
     *out = (int)v;
     return true;
 }
-static int search_main(const char* qpath, long long rec, const char* dbpath, long long top, const sw_scores& sc, const AffineArgs& af, bool align) {
-    int64_t qlen = 0, nrec = 0, total = 0;
-    CHECK(sw_read_fasta(qpath, rec, nullptr, 0, &qlen));
-    std::vector<char> q((size_t)qlen + 1);
-    CHECK(sw_read_fasta(qpath, rec, q.data(), qlen, &qlen));
-    CHECK(sw_read_fasta_db(dbpath, nullptr, 0, nullptr, 0, &nrec, &total));
-    std::vector<char> db((size_t)total + 1);
-    std::vector<int64_t> offs((size_t)nrec + 1, 0);
-    CHECK(sw_read_fasta_db(dbpath, db.data(), total, offs.data(), nrec + 1, &nrec, &total));
-    sw_ctx* ctx = nullptr;
-    CHECK(sw_create(0, &ctx));
-    void *d_q = nullptr, *d_db = nullptr, *d_res = nullptr;
-    CHECK(sw_device_malloc(ctx, (size_t)qlen + 16, &d_q));
-    CHECK(sw_device_malloc(ctx, (size_t)total + 16, &d_db));
-    CHECK(sw_device_malloc(ctx, (size_t)(nrec > 0 ? nrec : 1) * sizeof(sw_result), &d_res));
-    CHECK(sw_memcpy_h2d(ctx, d_q, q.data(), (size_t)qlen));
-    if (total) CHECK(sw_memcpy_h2d(ctx, d_db, db.data(), (size_t)total));
-    std::vector<sw_submat> sub(af.on || align ? 1 : 0);
-    sw_affine aff = {nullptr, af.has_open ? af.open : 0, af.has_extend ? af.extend : sc.gap};
-    if (af.on || align) {
-        if (af.matrix) CHECK(sw_read_submat(af.matrix, sub.data()));
-        else sw_submat_match(sc.match, sc.mismatch, sub.data());
-        aff.sub = sub.data();
-    }
-    const double t0 = now_s();
-    if (af.on) CHECK(sw_search_affine_device(ctx, (const char*)d_q, qlen, (const char*)d_db, offs.data(), nrec, &aff, (sw_result*)d_res, nullptr));
-    else CHECK(sw_search_device(ctx, (const char*)d_q, qlen, (const char*)d_db, offs.data(), nrec, &sc, (sw_result*)d_res, nullptr));
-    CHECK(sw_synchronize(ctx, nullptr));
-    const double t1 = now_s();
-    std::vector<sw_result> res((size_t)nrec);
-    if (nrec) CHECK(sw_memcpy_d2h(ctx, res.data(), d_res, (size_t)nrec * sizeof(sw_result)));
+// The hit block of one query: the header line, the best `top` hits by score (ties: lower record first) and, with `align`, every hit's
+// alignment (the K hits re-filled with directions and walked on the device).
+static int print_hits(sw_ctx* ctx, const char* q, int64_t qlen, const void* d_q, const std::vector<char>& db, const void* d_db, const std::vector<int64_t>& offs,
+                      int64_t nrec, int64_t total, const sw_result* res, long long top, bool align, const sw_affine& aff) {
     std::vector<int64_t> order((size_t)nrec);
     for (int64_t k = 0; k < nrec; ++k) order[(size_t)k] = k;
     std::stable_sort(order.begin(), order.end(), [&](int64_t x, int64_t y) { return res[(size_t)x].max_score > res[(size_t)y].max_score; });
@@ -168,8 +144,92 @@ static int search_main(const char* qpath, long long rec, const char* dbpath, lon
         }
         printf("Q %s\n  %s\nT %s\n", lq.c_str(), lm.c_str(), lt.c_str());
     }
+    return 0;
+}
+
+static int search_main(const char* qpath, long long rec, const char* dbpath, long long top, const sw_scores& sc, const AffineArgs& af, bool align) {
+    int64_t qlen = 0, nrec = 0, total = 0;
+    CHECK(sw_read_fasta(qpath, rec, nullptr, 0, &qlen));
+    std::vector<char> q((size_t)qlen + 1);
+    CHECK(sw_read_fasta(qpath, rec, q.data(), qlen, &qlen));
+    CHECK(sw_read_fasta_db(dbpath, nullptr, 0, nullptr, 0, &nrec, &total));
+    std::vector<char> db((size_t)total + 1);
+    std::vector<int64_t> offs((size_t)nrec + 1, 0);
+    CHECK(sw_read_fasta_db(dbpath, db.data(), total, offs.data(), nrec + 1, &nrec, &total));
+    sw_ctx* ctx = nullptr;
+    CHECK(sw_create(0, &ctx));
+    void *d_q = nullptr, *d_db = nullptr, *d_res = nullptr;
+    CHECK(sw_device_malloc(ctx, (size_t)qlen + 16, &d_q));
+    CHECK(sw_device_malloc(ctx, (size_t)total + 16, &d_db));
+    CHECK(sw_device_malloc(ctx, (size_t)(nrec > 0 ? nrec : 1) * sizeof(sw_result), &d_res));
+    CHECK(sw_memcpy_h2d(ctx, d_q, q.data(), (size_t)qlen));
+    if (total) CHECK(sw_memcpy_h2d(ctx, d_db, db.data(), (size_t)total));
+    std::vector<sw_submat> sub(af.on || align ? 1 : 0);
+    sw_affine aff = {nullptr, af.has_open ? af.open : 0, af.has_extend ? af.extend : sc.gap};
+    if (af.on || align) {
+        if (af.matrix) CHECK(sw_read_submat(af.matrix, sub.data()));
+        else sw_submat_match(sc.match, sc.mismatch, sub.data());
+        aff.sub = sub.data();
+    }
+    const double t0 = now_s();
+    if (af.on) CHECK(sw_search_affine_device(ctx, (const char*)d_q, qlen, (const char*)d_db, offs.data(), nrec, &aff, (sw_result*)d_res, nullptr));
+    else CHECK(sw_search_device(ctx, (const char*)d_q, qlen, (const char*)d_db, offs.data(), nrec, &sc, (sw_result*)d_res, nullptr));
+    CHECK(sw_synchronize(ctx, nullptr));
+    const double t1 = now_s();
+    std::vector<sw_result> res((size_t)nrec);
+    if (nrec) CHECK(sw_memcpy_d2h(ctx, res.data(), d_res, (size_t)nrec * sizeof(sw_result)));
+    if (int rc = print_hits(ctx, q.data(), qlen, d_q, db, d_db, offs, nrec, total, res.data(), top, align, aff)) return rc;
     const double cells = (double)qlen * (double)total;
     printf("\nElapsed time for database search: %f (%.1f GCUPS)\n\n", t1 - t0, t1 > t0 ? cells / (t1 - t0) / 1e9 : 0.0);
+    (void)sw_device_free(ctx, d_q); (void)sw_device_free(ctx, d_db); (void)sw_device_free(ctx, d_res);
+    sw_destroy(ctx);
+    return 0;
+}
+
+// --search --all-queries: every record of the query file against the database through ONE prepared handle and one call
+// (sw_db_create / sw_db_search_affine); the hit block of --search once per query, each under a line that names the record.  A linear
+// search goes through the match / mismatch table of --scores with gap_open 0, which sw_search_device equals bit for bit.
+static int search_all_main(const char* qpath, const char* dbpath, long long top, const sw_scores& sc, const AffineArgs& af, bool align) {
+    int64_t nq = 0, qtotal = 0, nrec = 0, total = 0;
+    CHECK(sw_read_fasta_db(qpath, nullptr, 0, nullptr, 0, &nq, &qtotal));
+    std::vector<char> qs((size_t)qtotal + 1);
+    std::vector<int64_t> qoffs((size_t)nq + 1, 0);
+    CHECK(sw_read_fasta_db(qpath, qs.data(), qtotal, qoffs.data(), nq + 1, &nq, &qtotal));
+    CHECK(sw_read_fasta_db(dbpath, nullptr, 0, nullptr, 0, &nrec, &total));
+    std::vector<char> db((size_t)total + 1);
+    std::vector<int64_t> offs((size_t)nrec + 1, 0);
+    CHECK(sw_read_fasta_db(dbpath, db.data(), total, offs.data(), nrec + 1, &nrec, &total));
+    sw_ctx* ctx = nullptr;
+    CHECK(sw_create(0, &ctx));
+    void *d_q = nullptr, *d_db = nullptr, *d_res = nullptr;
+    const size_t nres = (size_t)std::max<int64_t>(1, nq * nrec);
+    CHECK(sw_device_malloc(ctx, (size_t)qtotal + 16, &d_q));
+    CHECK(sw_device_malloc(ctx, (size_t)total + 16, &d_db));
+    CHECK(sw_device_malloc(ctx, nres * sizeof(sw_result), &d_res));
+    if (qtotal) CHECK(sw_memcpy_h2d(ctx, d_q, qs.data(), (size_t)qtotal));
+    if (total) CHECK(sw_memcpy_h2d(ctx, d_db, db.data(), (size_t)total));
+    std::vector<sw_submat> sub(1);
+    sw_affine aff = {sub.data(), af.has_open ? af.open : 0, af.has_extend ? af.extend : sc.gap};
+    if (af.matrix) CHECK(sw_read_submat(af.matrix, sub.data()));
+    else sw_submat_match(sc.match, sc.mismatch, sub.data());
+    sw_db* handle = nullptr;
+    const double t0 = now_s();
+    CHECK(sw_db_create(ctx, (const char*)d_db, offs.data(), nrec, &handle));
+    const double t1 = now_s();
+    CHECK(sw_db_search_affine(ctx, handle, (const char*)d_q, qoffs.data(), nq, &aff, (sw_result*)d_res, nullptr));
+    CHECK(sw_synchronize(ctx, nullptr));
+    const double t2 = now_s();
+    std::vector<sw_result> res(nres);
+    if (nq > 0 && nrec > 0) CHECK(sw_memcpy_d2h(ctx, res.data(), d_res, (size_t)(nq * nrec) * sizeof(sw_result)));
+    for (int64_t i = 0; i < nq; ++i) {
+        printf("## query record %lld of %s\n", (long long)i, qpath);
+        if (int rc = print_hits(ctx, qs.data() + qoffs[(size_t)i], qoffs[(size_t)i + 1] - qoffs[(size_t)i], (const char*)d_q + qoffs[(size_t)i], db, d_db, offs, nrec,
+                                total, res.data() + i * nrec, top, align, aff)) return rc;
+    }
+    const double cells = (double)qtotal * (double)total;
+    printf("\nElapsed time for database search: %f (%.1f GCUPS; %lld queries in one call, handle prepared in %f)\n\n", t2 - t1,
+           t2 > t1 ? cells / (t2 - t1) / 1e9 : 0.0, (long long)nq, t1 - t0);
+    sw_db_free(handle);
     (void)sw_device_free(ctx, d_q); (void)sw_device_free(ctx, d_db); (void)sw_device_free(ctx, d_res);
     sw_destroy(ctx);
     return 0;
@@ -185,7 +245,7 @@ int main(int argc, char** argv) {
     const char *search_q = nullptr, *search_db = nullptr;
     long long top = 10;
     AffineArgs af;
-    bool align = false;
+    bool align = false, all_queries = false;
     sw_scores sc = {3, -3, -2};
     int npos = 0;
     for (int ai = 1; ai < argc; ++ai) {
@@ -209,11 +269,12 @@ int main(int argc, char** argv) {
         else if (f == "--gap-open" && ai + 1 < argc) { if (!parse_int("--gap-open", argv[++ai], &af.open)) return 2; af.has_open = af.on = true; }
         else if (f == "--gap-extend" && ai + 1 < argc) { if (!parse_int("--gap-extend", argv[++ai], &af.extend)) return 2; af.has_extend = true; }
         else if (f == "--align") align = true;
+        else if (f == "--all-queries") all_queries = true;
         else if (f == "--record-a" && ai + 1 < argc) rec_a = strtoll(argv[++ai], nullptr, 10);
         else if (f == "--record-b" && ai + 1 < argc) rec_b = strtoll(argv[++ai], nullptr, 10);
         else if (f == "--seed" && ai + 1 < argc) seed = (unsigned)strtoul(argv[++ai], nullptr, 10);
         else if (f == "--scores" && ai + 3 < argc) { sc.match = atoi(argv[++ai]); sc.mismatch = atoi(argv[++ai]); sc.gap = atoi(argv[++ai]); }
-        else { fprintf(stderr, "usage: smithW [<cols> <rows> | --fasta A.fa B.fa [--record-a I] [--record-b J] | --search QUERY.fa DB.fa [--record-a I] [--top K] [--matrix FILE] [--gap-open O] [--gap-extend E] [--align]] [--seed N] [--dump | --dump-labels] [--h64] [--no-backtrack] [--scores M X G] [--gpus N | --devices 0,1,..] [--p8]\n"); return 2; }
+        else { fprintf(stderr, "usage: smithW [<cols> <rows> | --fasta A.fa B.fa [--record-a I] [--record-b J] | --search QUERY.fa DB.fa [--record-a I] [--top K] [--all-queries] [--matrix FILE] [--gap-open O] [--gap-extend E] [--align]] [--seed N] [--dump | --dump-labels] [--h64] [--no-backtrack] [--scores M X G] [--gpus N | --devices 0,1,..] [--p8]\n"); return 2; }
     }
     if (npos == 1) { fprintf(stderr, "smithW: <cols> needs <rows>\n"); return 2; }
     if (search_q) {
@@ -226,8 +287,16 @@ int main(int argc, char** argv) {
             fprintf(stderr, "smithW: --align on a linear search needs --scores M X within -128..127 (a table of signed bytes), got %d %d\n", sc.match, sc.mismatch);
             return 2;
         }
+        if (all_queries) {
+            if (!af.matrix && (sc.match < -128 || sc.match > 127 || sc.mismatch < -128 || sc.mismatch > 127)) {
+                fprintf(stderr, "smithW: --all-queries without --matrix needs --scores M X within -128..127 (a table of signed bytes), got %d %d\n", sc.match, sc.mismatch);
+                return 2;
+            }
+            return search_all_main(search_q, search_db, top, sc, af, align);
+        }
         return search_main(search_q, rec_a, search_db, top, sc, af, align);
     }
+    if (all_queries) { fprintf(stderr, "smithW: --all-queries goes with --search\n"); return 2; }
     if (align) { fprintf(stderr, "smithW: --align goes with --search\n"); return 2; }
     if (af.on || af.has_extend) { fprintf(stderr, "smithW: --matrix / --gap-open / --gap-extend go with --search\n"); return 2; }
     if (fasta_a) {

@@ -64,6 +64,8 @@ void sw_destroy(sw_ctx* c) {
     if (c->d_submat) (void)hipFree(c->d_submat);
     if (c->h_submat) (void)hipHostFree(c->h_submat);
     if (c->d_adir) (void)hipFree(c->d_adir);
+    if (c->d_mq) (void)hipFree(c->d_mq);
+    if (c->h_mq) (void)hipHostFree(c->h_mq);
     delete c;
 }
 
@@ -92,6 +94,11 @@ int sw_set_option(sw_ctx* c, const char* name, int64_t v) {
     if (!strcmp(name, "align_workspace_mib")) {
         if (v < 1 || v > (1ll << 20)) { set_err("align_workspace_mib must be 1..2^20"); return SW_EINVAL; }
         c->opt_align_workspace_mib = v;
+        return SW_OK;
+    }
+    if (!strcmp(name, "search_profile_mib")) {
+        if (v < 1 || v > (1ll << 20)) { set_err("search_profile_mib must be 1..2^20"); return SW_EINVAL; }
+        c->opt_search_profile_mib = v;
         return SW_OK;
     }
     if (!strcmp(name, "placement_budget_ms")) { c->opt_place_budget_ms = v > 0 ? v : 1500; return SW_OK; }
@@ -144,6 +151,10 @@ int64_t sw_get_option(sw_ctx* c, const char* name) {
     if (!strcmp(name, "last_align_affine_kernel")) return c->last_align_affine_kernel;
     if (!strcmp(name, "last_align_affine_slots")) return c->last_align_affine_slots;
     if (!strcmp(name, "align_workspace_mib")) return c->opt_align_workspace_mib;
+    if (!strcmp(name, "search_profile_mib")) return c->opt_search_profile_mib;
+    if (!strcmp(name, "last_search_multi_groups")) return c->last_search_multi_groups;
+    if (!strcmp(name, "last_search_multi_launches")) return c->last_search_multi_launches;
+    if (!strcmp(name, "last_search_multi_grid")) return c->last_search_multi_grid;
     if (!strcmp(name, "placement_budget_ms")) return c->opt_place_budget_ms;
     if (!strcmp(name, "placement_hold_gib")) return c->opt_place_hold_gib;
     if (!strcmp(name, "probe_foreign_pairs")) return c->opt.probe_foreign_pairs;

@@ -1,6 +1,8 @@
-// sw_api_search.hip -- the search family of the C-ABI (see include/swhip.h): database search, affine search, alignment of hits.  The three
-// calls share the workspaces of the context and one protocol around them; each reads validate, plan, stage, upload, launch.
+// sw_api_search.hip -- the search family of the C-ABI (see include/swhip.h): database search, affine search, alignment of hits, and the
+// prepared database with its many-query search.  The calls share the workspaces of the context and one protocol around them; each reads
+// validate, plan, stage, upload, launch.
 #include <cstring>
+#include <vector>
 #include "sw_ctx.h"
 
 // the instantiations of the search kernel (sw_search.hip), picked by swp::plan_search
@@ -29,6 +31,15 @@ static constexpr Indexed<AlignAffineKernel> kAlignAffine[] = {
     {swp::align_affine_kernel_index(16), swk::sw_align_affine_wave<16>},
 };
 static_assert(std::size(kAlignAffine) == swp::kAlignAffineKernels && at_their_indices(kAlignAffine));
+
+// the instantiations of the many-query kernel (sw_search_multi.hip), picked by swp::plan_search_multi
+using SearchMultiKernel = void (*)(swk::SearchMultiParams);
+static constexpr Indexed<SearchMultiKernel> kSearchMulti[] = {
+    {swp::search_multi_kernel_index(4), swk::sw_search_affine_multi_wave<4>},
+    {swp::search_multi_kernel_index(8), swk::sw_search_affine_multi_wave<8>},
+    {swp::search_multi_kernel_index(16), swk::sw_search_affine_multi_wave<16>},
+};
+static_assert(std::size(kSearchMulti) == swp::kSearchMultiKernels && at_their_indices(kSearchMulti));
 
 // occupancy of every instantiation of a table at 256 threads, asked once per context: the plans' columns per lane and grids depend on it
 template <typename K, size_t N>
@@ -94,6 +105,23 @@ static Params search_params(const sw_ctx* c, const char* d_db, int64_t nitems, i
     p.bnd = plan.bnd_per ? c->d_sbnd : nullptr; p.bnd_per = plan.bnd_per;
     p.counter = c->d_sctr;
     return p;
+}
+
+// The query table of a many-query call: the device buffer and the pinned copy it is uploaded from, grown together (the caller has waited
+// for the last upload from the pinned copy: stage_search_call).
+static int grow_query_table(sw_ctx* c, size_t need, hipStream_t stream) {
+    if (need <= c->mq_cap) return SW_OK;
+    HIP_TRY(hipStreamSynchronize(stream));
+    if (c->d_mq) HIP_TRY(hipFree(c->d_mq));
+    if (c->h_mq) HIP_TRY(hipHostFree(c->h_mq));
+    c->d_mq = nullptr; c->h_mq = nullptr; c->mq_cap = 0;
+    if (hipMalloc((void**)&c->d_mq, need * sizeof(swk::MultiQuery)) != hipSuccess ||
+        hipHostMalloc((void**)&c->h_mq, need * sizeof(swk::MultiQuery), 0) != hipSuccess) {
+        set_err("sw_db_search_affine: workspace allocation failed");
+        return SW_ENOMEM;
+    }
+    c->mq_cap = need;
+    return SW_OK;
 }
 
 extern "C" {
@@ -212,6 +240,123 @@ int sw_align_affine_device(sw_ctx* c, const char* d_query, int64_t qlen, const c
     hipLaunchKernelGGL(kAlignAffine[plan.kernel].k, dim3((unsigned)plan.grid), dim3(256), 0, stream, ap);
     HIP_TRY(hipGetLastError());
     c->last_align_affine_kernel = plan.kernel; c->last_align_affine_slots = plan.slots;
+    return SW_OK;
+}
+
+// ---- a prepared database and the search of many queries against it (csrc/sw_search_multi.hip)
+
+// Everything a search needs to know about the database and no query changes: the checks of the offsets and the schedule (the stable
+// sort of the lengths), done once.  Synchronous; the pinned staging copy of the schedule is gone when it returns.
+int sw_db_create(sw_ctx* c, const char* d_db, const int64_t* offsets, int64_t ntargets, sw_db** out) {
+    if (!c || !d_db || !offsets || !out || ntargets < 0) { set_err("sw_db_create: NULL pointer or negative target count"); return SW_EINVAL; }
+    *out = nullptr;
+    int64_t maxlen = 0, nonempty = 0;
+    if (int rc = swh::check_targets("sw_db_create", 1, offsets, ntargets, &maxlen, &nonempty)) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    sw_db* db = new sw_db;
+    db->device = c->device; db->d_db = d_db;
+    db->ntargets = ntargets; db->nonempty = nonempty; db->longest = maxlen; db->letters = offsets[ntargets] - offsets[0];
+    if (nonempty > 0) {
+        swk::SearchItem* h_items = nullptr;
+        const size_t bytes = (size_t)nonempty * sizeof(swk::SearchItem);
+        hipError_t e = hipHostMalloc((void**)&h_items, bytes, 0);
+        if (e == hipSuccess) e = hipMalloc((void**)&db->d_items, bytes);
+        if (e == hipSuccess) {
+            swp::search_schedule(offsets, ntargets, h_items);
+            e = hipMemcpy(db->d_items, h_items, bytes, hipMemcpyHostToDevice);
+        }
+        if (h_items) (void)hipHostFree(h_items);
+        if (e != hipSuccess) {
+            set_err("sw_db_create: the schedule of %lld targets could not be placed on the device: %s", (long long)nonempty, hipGetErrorString(e));
+            if (db->d_items) (void)hipFree(db->d_items);
+            delete db;
+            return e == hipErrorOutOfMemory ? SW_ENOMEM : SW_EDEVICE;
+        }
+    }
+    *out = db;
+    return SW_OK;
+}
+
+void sw_db_free(sw_db* db) {
+    if (!db) return;
+    if (db->d_items) { (void)hipSetDevice(db->device); (void)hipFree(db->d_items); }
+    delete db;
+}
+
+int sw_db_info(const sw_db* db, int64_t* ntargets, int64_t* nonempty, int64_t* longest, int64_t* letters) {
+    if (!db) { set_err("sw_db_info: NULL handle"); return SW_EINVAL; }
+    if (ntargets) *ntargets = db->ntargets;
+    if (nonempty) *nonempty = db->nonempty;
+    if (longest) *longest = db->longest;
+    if (letters) *letters = db->letters;
+    return SW_OK;
+}
+
+// Every query against every target of the handle.  Per call the host checks and plans the QUERIES (O(nqueries)), uploads their table
+// and the scoring table from pinned copies, and enqueues per group one profile launch and one launch per class of queries; the targets'
+// offsets are not looked at again and nothing is sorted.
+int sw_db_search_affine(sw_ctx* c, const sw_db* db, const char* d_queries, const int64_t* qoffsets, int64_t nqueries, const sw_affine* scoring,
+                        sw_result* d_results, void* stream_) {
+    if (!c || !db || !d_queries || !qoffsets || !scoring || !d_results) { set_err("sw_db_search_affine: NULL pointer"); return SW_EINVAL; }
+    if (db->device != c->device) { set_err("sw_db_search_affine: the handle was created on device %d, the context runs on device %d", db->device, c->device); return SW_EINVAL; }
+    int64_t maxq = 0;
+    if (int rc = swh::check_search_multi("sw_db_search_affine", qoffsets, nqueries, db->longest, scoring, &maxq)) return rc;
+    if (nqueries == 0 || db->ntargets == 0) return SW_OK;
+    hipStream_t stream = (hipStream_t)stream_;
+    HIP_TRY(hipSetDevice(c->device));
+    DevOrder order(c, stream, false);
+    if (order.rc) return order.rc;
+    // empty targets keep the zeros: {0, 0, 0}
+    HIP_TRY(hipMemsetAsync(d_results, 0, (size_t)nqueries * (size_t)db->ntargets * sizeof(sw_result), stream));
+    if (db->nonempty == 0) return SW_OK;
+    if (int rc = occupancy_once(kSearchMulti, c->search_multi_per_cu, c->search_multi_per_cu_known)) return rc;
+    std::vector<int64_t> qlens((size_t)nqueries);
+    for (int64_t q = 0; q < nqueries; ++q) qlens[(size_t)q] = qoffsets[q + 1] - qoffsets[q];
+    swp::SearchMultiJob mj;
+    mj.qlens = qlens.data(); mj.nqueries = nqueries; mj.longest = db->longest; mj.nonempty = db->nonempty; mj.num_cus = c->num_cus;
+    mj.budget_bytes = c->opt_search_profile_mib << 20;
+    std::copy(std::begin(c->search_multi_per_cu), std::end(c->search_multi_per_cu), mj.per_cu);
+    const swp::SearchMultiPlan plan = swp::plan_search_multi(mj);
+    for (const swp::MultiLaunch& l : plan.launch)
+        if (c->search_multi_per_cu[l.kernel] < 1) { set_err("the many-query search kernel does not fit a CU on this device"); return SW_EDEVICE; }
+    if (int rc = stage_search_call(c, stream, 0, plan.prof_need, plan.bnd_need, scoring->sub)) return rc;
+    if (int rc = grow_query_table(c, (size_t)nqueries, stream)) return rc;
+    for (int64_t t = 0; t < nqueries; ++t) {
+        c->h_mq[t] = plan.table[(size_t)t];
+        c->h_mq[t].qstart = qoffsets[plan.table[(size_t)t].row];
+    }
+    memcpy(c->h_submat, scoring->sub, sizeof(sw_submat));
+    HIP_TRY(hipMemcpyAsync(c->d_mq, c->h_mq, (size_t)nqueries * sizeof(swk::MultiQuery), hipMemcpyHostToDevice, stream));
+    HIP_TRY(hipMemcpyAsync(c->d_submat, c->h_submat, sizeof(sw_submat), hipMemcpyHostToDevice, stream));
+    HIP_TRY(hipEventRecord(c->sitems_ev, stream));   // behind both uploads: whoever has waited for it may overwrite either pinned copy
+    size_t li = 0;
+    for (size_t g = 0; g < plan.group.size(); ++g) {
+        const swp::MultiGroup& grp = plan.group[g];
+        // every query's profile in shares of about 16 KiB, over at most 4096 workgroups
+        const int parts = (int)std::clamp<int64_t>(grp.prof_bytes / grp.nq / 16384, 1, 4096);
+        const unsigned blocks = (unsigned)std::min<int64_t>(grp.nq * parts, 4096);
+        hipLaunchKernelGGL(swk::sw_search_profile_submat_multi, dim3(blocks), dim3(256), 0, stream, (const unsigned char*)d_queries, c->d_mq + grp.q0, grp.nq,
+                           parts, c->d_sprof, (const signed char*)c->d_submat);
+        HIP_TRY(hipGetLastError());
+        for (; li < plan.launch.size() && plan.launch[li].group == (int)g; ++li) {
+            const swp::MultiLaunch& l = plan.launch[li];
+            swk::SearchMultiParams sp;
+            memset(&sp, 0, sizeof sp);
+            sp.db = (const unsigned char*)db->d_db;
+            sp.items = db->d_items; sp.rank0 = l.rank0;
+            sp.queries = c->d_mq + l.q0; sp.nq = (unsigned)l.nq; sp.nitems = l.items;
+            sp.prof = c->d_sprof; sp.ntargets = db->ntargets;
+            sp.ge = scoring->gap_extend; sp.goe = scoring->gap_open + scoring->gap_extend;
+            sp.bnd = l.bnd_per ? c->d_sbnd : nullptr; sp.bnd_per = l.bnd_per;
+            sp.counter = c->d_sctr;
+            sp.results = d_results;
+            HIP_TRY(hipMemsetAsync(c->d_sctr, 0, 4, stream));   // the work counter starts every launch at zero
+            hipLaunchKernelGGL(kSearchMulti[l.kernel].k, dim3((unsigned)l.grid), dim3(256), 0, stream, sp);
+            HIP_TRY(hipGetLastError());
+            c->last_search_multi_grid = l.grid;
+        }
+    }
+    c->last_search_multi_groups = (int64_t)plan.group.size(); c->last_search_multi_launches = (int64_t)plan.launch.size();
     return SW_OK;
 }
 

@@ -18,6 +18,7 @@ int check_search_affine(const char* who, int64_t qlen, const int64_t* offsets, i
                         int64_t* nonempty_out);
 int check_align_affine(const char* who, const int64_t* offsets, int64_t ntargets, const int64_t* hits, int64_t nhits, const void* aln, const void* ops,
                        int64_t ops_cap, int64_t* maxhit_out);
+int check_search_multi(const char* who, const int64_t* qoffsets, int64_t nqueries, int64_t longest_target, const sw_affine* sc, int64_t* maxq_out);
 SW_HIDDEN int check_targets(const char* who, int64_t qlen, const int64_t* offsets, int64_t ntargets, int64_t* maxlen_out, int64_t* nonempty_out);
 }
 using swh::set_err;
@@ -110,6 +111,13 @@ struct SW_HIDDEN sw_ctx {
     int64_t last_align_affine_kernel = 0, last_align_affine_slots = 0;
     int align_affine_per_cu[swp::kAlignAffineKernels] = {};     // occupancy of every sw_align_affine_wave instantiation at 256 threads ...
     bool align_affine_per_cu_known = false;                     // ... queried at the first call
+    // many queries against a prepared database (sw_db_search_affine): the call's query table on the device + the pinned copy it is uploaded
+    // from (the protocol of sitems_ev covers it), the budget of a group's profiles
+    swk::MultiQuery* d_mq = nullptr; swk::MultiQuery* h_mq = nullptr; size_t mq_cap = 0;
+    int64_t opt_search_profile_mib = 256;
+    int64_t last_search_multi_groups = 0, last_search_multi_launches = 0, last_search_multi_grid = 0;   // of the last call; the grid of its last launch
+    int search_multi_per_cu[swp::kSearchMultiKernels] = {};     // occupancy of every sw_search_affine_multi_wave instantiation at 256 threads ...
+    bool search_multi_per_cu_known = false;                     // ... queried at the first call
     // ---- placement of the output matrices (sw_place.hip)
     int64_t opt_place_hold_gib = 0;     // sw_alloc_outputs: GiB a pair of small matrices may hold beside itself where no plain candidate is good (0: none)
     int64_t opt_place_budget_ms = 1500; // sw_alloc_outputs: time the search for a P in another class of the HBM may take
@@ -118,6 +126,15 @@ struct SW_HIDDEN sw_ctx {
     float last_place_ratio = 0.f;       // ... two-stream / one-stream time of the pair handed out last (~1.3-1.45: different classes, ~2: one class)
     std::map<void*, void*> out_base;    // sw_alloc_outputs: pointer handed out -> allocation to free
     std::map<void*, float> pair_ratio;  // ... P handed out -> the store probe's ratio of its pair (~1.4: two classes of the HBM, ~2: one)
+};
+
+// A prepared database (sw_db_create): the caller's device bytes, borrowed, and the search schedule of its targets on the device -- what
+// every search of it needs and no query changes.
+struct SW_HIDDEN sw_db {
+    int device = 0;
+    const char* d_db = nullptr;
+    int64_t ntargets = 0, nonempty = 0, longest = 0, letters = 0;
+    swk::SearchItem* d_items = nullptr;  // the nonempty targets, longest first (swp::search_schedule)
 };
 
 // A launch table: every instantiation beside the index the planner gives it, checked at compile time to sit at that index.

@@ -66,13 +66,9 @@ int check_targets(const char* who, int64_t qlen, const int64_t* offsets, int64_t
     return SW_OK;
 }
 
-// The argument rules of the affine search (include/swhip.h), shared by the device and the host entry point.
-int check_search_affine(const char* who, int64_t qlen, const int64_t* offsets, int64_t ntargets, const sw_affine* sc, int64_t* maxlen_out,
-                        int64_t* nonempty_out) {
+// The scoring rules of the affine calls for a query of `qlen` against a longest target of `maxlen` (include/swhip.h).
+static int check_affine_scoring(const char* who, const sw_affine* sc, int64_t qlen, int64_t maxlen) {
     constexpr int64_t kScoreLimit = 1ll << 24;
-    if (!sc || !sc->sub) { set_err("%s: NULL scoring or substitution matrix", who); return SW_EINVAL; }
-    int64_t maxlen = 0, nonempty = 0;
-    if (int rc = check_targets(who, qlen, offsets, ntargets, &maxlen, &nonempty)) return rc;
     if (sc->gap_open > 0) { set_err("%s: gap_open must be <= 0 (got %d)", who, sc->gap_open); return SW_EINVAL; }
     if (sc->gap_extend > 0) { set_err("%s: gap_extend must be <= 0 (got %d)", who, sc->gap_extend); return SW_EINVAL; }
     if ((int64_t)sc->gap_open + (int64_t)sc->gap_extend < -kScoreLimit) {
@@ -88,8 +84,37 @@ int check_search_affine(const char* who, int64_t qlen, const int64_t* offsets, i
                 who, bx, by, best, (long long)qlen, (long long)maxlen);
         return SW_EINVAL;
     }
+    return SW_OK;
+}
+
+// The argument rules of the affine search (include/swhip.h), shared by the device and the host entry point.
+int check_search_affine(const char* who, int64_t qlen, const int64_t* offsets, int64_t ntargets, const sw_affine* sc, int64_t* maxlen_out,
+                        int64_t* nonempty_out) {
+    if (!sc || !sc->sub) { set_err("%s: NULL scoring or substitution matrix", who); return SW_EINVAL; }
+    int64_t maxlen = 0, nonempty = 0;
+    if (int rc = check_targets(who, qlen, offsets, ntargets, &maxlen, &nonempty)) return rc;
+    if (int rc = check_affine_scoring(who, sc, qlen, maxlen)) return rc;
     *maxlen_out = maxlen;
     *nonempty_out = nonempty;
+    return SW_OK;
+}
+
+// The argument rules of a many-query search (sw_db_search_affine, sw_search_affine_multi_host): the query offsets, every query's
+// length, and the scoring rules taken over the longest query against the database's longest target.  O(nqueries).
+int check_search_multi(const char* who, const int64_t* qoffsets, int64_t nqueries, int64_t longest_target, const sw_affine* sc, int64_t* maxq_out) {
+    constexpr int64_t kMaxDim = swk::SW_MAX_DIM;
+    if (!qoffsets || !sc || !sc->sub) { set_err("%s: NULL query offsets, scoring or substitution matrix", who); return SW_EINVAL; }
+    if (nqueries < 0) { set_err("%s: negative query count", who); return SW_EINVAL; }
+    if (qoffsets[0] < 0) { set_err("%s: qoffsets[0] = %lld is negative", who, (long long)qoffsets[0]); return SW_EINVAL; }
+    int64_t maxq = 0;
+    for (int64_t q = 0; q < nqueries; ++q) {
+        const int64_t len = qoffsets[q + 1] - qoffsets[q];
+        if (len < 0) { set_err("%s: qoffsets decrease at query %lld", who, (long long)q); return SW_EINVAL; }
+        if (len < 1 || len > kMaxDim) { set_err("%s: query %lld has length %lld, out of range 1..%lld", who, (long long)q, (long long)len, (long long)kMaxDim); return SW_EINVAL; }
+        maxq = std::max(maxq, len);
+    }
+    if (int rc = check_affine_scoring(who, sc, maxq, longest_target)) return rc;
+    *maxq_out = maxq;
     return SW_OK;
 }
 
@@ -405,6 +430,22 @@ int sw_search_affine_host(const char* query, int64_t qlen, const char* db, const
         }
         results[k] = sw_result{best_pos, best, 0};
     }
+    return SW_OK;
+}
+
+// The CPU leg of sw_db_search_affine: sw_search_affine_host query after query into the query-major results.  Everything is checked
+// before the first query runs, so an error leaves `results` untouched.
+int sw_search_affine_multi_host(const char* queries, const int64_t* qoffsets, int64_t nqueries, const char* db, const int64_t* offsets, int64_t ntargets,
+                                const sw_affine* scoring, sw_result* results) {
+    if (!queries || !qoffsets || !db || !offsets || !results || !scoring || ntargets < 0) {
+        swh::set_err("sw_search_affine_multi_host: NULL pointer or negative target count");
+        return SW_EINVAL;
+    }
+    int64_t maxlen = 0, nonempty = 0, maxq = 0;
+    if (int rc = swh::check_targets("sw_search_affine_multi_host", 1, offsets, ntargets, &maxlen, &nonempty)) return rc;
+    if (int rc = swh::check_search_multi("sw_search_affine_multi_host", qoffsets, nqueries, maxlen, scoring, &maxq)) return rc;
+    for (int64_t q = 0; q < nqueries; ++q)
+        if (int rc = sw_search_affine_host(queries + qoffsets[q], qoffsets[q + 1] - qoffsets[q], db, offsets, ntargets, scoring, results + q * ntargets)) return rc;
     return SW_OK;
 }
 

@@ -3,7 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/swhip.h"
-#include "sw_plan.h"   // (SW_SEARCH_ROWS, SearchItem)
+#include "sw_plan.h"   // (SW_SEARCH_ROWS, SearchItem, MultiQuery)
 
 namespace swk {
 
@@ -138,6 +138,25 @@ struct SearchAffineParams {
 __global__ void sw_search_profile_submat(const unsigned char* q, int64_t qlen, int64_t qpad, signed char* prof, const signed char* sub);
 template <int C>
 __global__ void sw_search_affine_wave(SearchAffineParams p);
+
+// sw_search_multi.hip: many queries against a prepared database, one launch per class of queries (columns per lane)
+struct SearchMultiParams {
+    const unsigned char* db;             // the targets back to back
+    const SearchItem* items;             // the handle's schedule: every non-empty target, longest first
+    int64_t rank0;                       // the first target rank of this launch
+    const MultiQuery* queries;           // the launch's queries (entries of the call's table)
+    unsigned int nq;                     // ... how many: item w = (rank0 + w / nq, w % nq)
+    int64_t nitems;                      // nq * target ranks of the launch, below 2^31
+    const signed char* prof;             // the group's profiles (sw_search_profile_submat_multi), query t at its prof_off
+    int64_t ntargets;                    // row stride of the results
+    int ge, goe;                         // gap_extend, gap_open + gap_extend (both <= 0)
+    int* bnd; int64_t bnd_per;           // per resident wave: boundary pairs (H, F) between strips (ints), only when a query has more than one strip
+    unsigned int* counter;               // next item (zero at launch)
+    sw_result* results;                  // query-major, nqueries x ntargets, the caller's order
+};
+__global__ void sw_search_profile_submat_multi(const unsigned char* q, const MultiQuery* tab, int64_t nq, int parts, signed char* prof, const signed char* sub);
+template <int C>
+__global__ void sw_search_affine_multi_wave(SearchMultiParams p);
 
 // sw_align_affine.hip: the alignment of chosen hits under affine scoring (direction fill + walk, one wave per hit)
 struct AlignAffineParams {

@@ -1,5 +1,5 @@
 // sw_plan.cpp -- the fill, batch and search planners (sw_plan.h).  No side effects, no allocation, no runtime calls -- except search_schedule,
-// which writes the schedule to the caller's buffer and sorts through a vector of its own.
+// which writes the schedule to the caller's buffer and sorts through a vector of its own, and plan_search_multi, whose plan grows with the queries.
 #include "sw_plan.h"
 #include <algorithm>
 #include <vector>
@@ -387,6 +387,66 @@ SearchAffinePlan plan_search_affine(const SearchAffineJob& j) {
     s.prof_blocks = (int)std::min<int64_t>((SW_SEARCH_ROWS * s.qpad + 255) / 256, kProfileBlocks);
     s.bnd_need = s.bnd_per ? (size_t)(s.grid * 4 * s.bnd_per) : 0;
     return s;
+}
+
+// Many queries against a prepared database.  Host work is O(nqueries): one pass cuts the groups, one pass per group counts its classes
+// and lays the table out; nothing here looks at a target.
+SearchMultiPlan plan_search_multi(const SearchMultiJob& j) {
+    using swk::SW_SEARCH_ROWS;
+    SearchMultiPlan m;
+    const int64_t n = j.nqueries;
+    m.table.resize((size_t)n);
+    auto columns = [&](int64_t qlen) {
+        int C = lane_columns(qlen);
+        if (C == 16 && j.per_cu[search_multi_kernel_index(16)] < kAffineC16MinPerCu) C = 8;
+        return C;
+    };
+    auto padded = [&](int64_t qlen) { const int64_t w = 64 * columns(qlen); return (qlen + w - 1) / w * w; };
+    const int64_t max_items = std::max<int64_t>(1, std::min(j.max_items, kMultiMaxItems));
+    for (int64_t g0 = 0; g0 < n;) {
+        // the group: consecutive queries while their profiles fit the budget, at least one
+        int64_t g1 = g0, bytes = 0;
+        while (g1 < n && (g1 == g0 || bytes + SW_SEARCH_ROWS * padded(j.qlens[g1]) <= j.budget_bytes)) bytes += SW_SEARCH_ROWS * padded(j.qlens[g1++]);
+        m.group.push_back(MultiGroup{g0, g1 - g0, bytes});
+        m.prof_need = std::max(m.prof_need, (size_t)bytes);
+        // the table of the group: by class, input order within a class; the profiles lie in table order
+        int64_t at[kSearchMultiKernels + 1] = {};
+        for (int64_t q = g0; q < g1; ++q) ++at[search_multi_kernel_index(columns(j.qlens[q])) + 1];
+        for (int k = 0; k < kSearchMultiKernels; ++k) at[k + 1] += at[k];
+        int64_t first[kSearchMultiKernels + 1];
+        std::copy(at, at + kSearchMultiKernels + 1, first);
+        for (int64_t q = g0; q < g1; ++q) {
+            const int C = columns(j.qlens[q]);
+            const int64_t qpad = padded(j.qlens[q]);
+            m.table[(size_t)(g0 + at[search_multi_kernel_index(C)]++)] = swk::MultiQuery{0, 0, q, (int32_t)j.qlens[q], (int32_t)qpad, (int32_t)(qpad / (64 * C)), 0};
+        }
+        int64_t off = 0;
+        for (int64_t t = g0; t < g1; ++t) { m.table[(size_t)t].prof_off = off; off += SW_SEARCH_ROWS * m.table[(size_t)t].qpad; }
+        // the launches of the group: per class, cut by target ranks (and by queries, should a class alone pass the limit)
+        for (int k = 0; k < kSearchMultiKernels && j.nonempty > 0; ++k) {
+            for (int64_t qa = first[k]; qa < first[k + 1];) {
+                const int64_t nq = std::min(first[k + 1] - qa, max_items), ranks_per = max_items / nq;
+                int64_t strips = 1;
+                for (int64_t t = qa; t < qa + nq; ++t) strips = std::max<int64_t>(strips, m.table[(size_t)(g0 + t)].nstrips);
+                for (int64_t r0 = 0; r0 < j.nonempty; r0 += ranks_per) {
+                    MultiLaunch l;
+                    l.group = (int)m.group.size() - 1; l.C = k == 0 ? 4 : 8 * k; l.kernel = k;
+                    l.q0 = g0 + qa; l.nq = nq;
+                    l.rank0 = r0; l.nranks = std::min(ranks_per, j.nonempty - r0);
+                    l.items = l.nq * l.nranks;
+                    l.bnd_per = 2 * boundary_ints(strips, j.longest);
+                    l.grid = std::min<int64_t>((int64_t)j.per_cu[k] * j.num_cus, (l.items + 3) / 4);
+                    if (l.bnd_per) l.grid = std::min<int64_t>(l.grid, kSearchBndBytes / (l.bnd_per * 4 * 4));
+                    l.grid = std::max<int64_t>(1, l.grid);
+                    m.bnd_need = std::max(m.bnd_need, (size_t)(l.grid * 4 * l.bnd_per));
+                    m.launch.push_back(l);
+                }
+                qa += nq;
+            }
+        }
+        g0 = g1;
+    }
+    return m;
 }
 
 // The direction fill carries the search kernel's state plus the packed bytes of a row; the thresholds of the search hold for the same

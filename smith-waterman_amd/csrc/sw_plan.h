@@ -7,12 +7,17 @@
 #pragma once
 #include <cstddef>
 #include <cstdint>
+#include <vector>
 #include "sw_debug.h"
 
 namespace swk {   // shared with the search kernels (sw_kernels.h)
 
 constexpr int SW_SEARCH_ROWS = 257;      // profile rows: one per byte value + PAD (the letter of every row outside a target)
 struct SearchItem { int64_t start, idx, len; };   // a target in schedule order: first byte in db, index in the caller's order, length
+// A query of a many-query search (sw_search_multi.hip), one entry of the call's device table: where its profile starts in the group's
+// profile workspace, its first byte in the caller's query buffer, its row of the query-major results, its length, its profile row
+// length (strips * 64 * C) and its strips at the C of its class.
+struct MultiQuery { int64_t prof_off, qstart, row; int32_t qlen, qpad, nstrips, pad; };
 
 }  // namespace swk
 
@@ -176,6 +181,46 @@ struct SearchAffinePlan {
 };
 
 SearchAffinePlan plan_search_affine(const SearchAffineJob& job);
+
+// ---- many queries against a prepared database (sw_db_search_affine): sw_search_affine_multi_wave<C> for C = 4, 8, 16, its index in
+// kSearchMulti (sw_api_search.hip, which checks its order against it at compile time).
+// Classes: a query gets the columns per lane plan_search_affine gives it alone; the queries of a class share a launch.
+// Groups: consecutive queries whose profiles (257 x qpad bytes each, back to back) fit the budget; one query alone may exceed it.
+// Items: work item w of a launch is the pair (target rank rank0 + w / nq, table entry q0 + w % nq): all the class's queries against the
+// longest target first, then against the next -- the long pairs start first whatever the mix of query lengths; a launch ends where
+// its items would pass kMultiMaxItems (the work counter is 32 bits wide), the next one goes on with the following target ranks.
+constexpr int kSearchMultiKernels = 3;
+constexpr int search_multi_kernel_index(int C) { return C / 8; }
+constexpr int64_t kMultiMaxItems = (1ll << 31) - 1;
+
+struct SearchMultiJob {
+    const int64_t* qlens = nullptr;          // length of every query, input order
+    int64_t nqueries = 0;
+    int64_t longest = 0, nonempty = 0;       // of the handle: longest target, non-empty targets
+    int num_cus = 256;
+    int per_cu[kSearchMultiKernels] = {};    // occupancy of every sw_search_affine_multi_wave instantiation at 256 threads (workgroups per CU)
+    int64_t budget_bytes = 256ll << 20;      // "search_profile_mib": the profiles of a group may take this much
+    int64_t max_items = kMultiMaxItems;      // (tests lower it)
+};
+
+struct MultiGroup { int64_t q0 = 0, nq = 0, prof_bytes = 0; };   // the queries q0 .. q0 + nq - 1 = the table entries q0 .. q0 + nq - 1, by class
+struct MultiLaunch {
+    int group = 0, C = 0, kernel = 0;        // kernel: index of sw_search_affine_multi_wave<C> (kSearchMultiKernels)
+    int64_t q0 = 0, nq = 0;                  // its queries: entries q0 .. q0 + nq - 1 of the table
+    int64_t rank0 = 0, nranks = 0;           // its targets: ranks rank0 .. rank0 + nranks - 1 of the handle's schedule
+    int64_t items = 0;                       // nq * nranks <= max_items
+    int64_t bnd_per = 0;                     // per resident wave: boundary pairs between strips (ints), 0: every query has one strip
+    int64_t grid = 0;                        // persistent workgroups of 4 waves: min(resident waves, items) waves
+};
+
+struct SearchMultiPlan {
+    std::vector<swk::MultiQuery> table;      // one entry per query (qstart is left 0: the caller's offsets); per group sorted by class, input order within
+    std::vector<MultiGroup> group;
+    std::vector<MultiLaunch> launch;         // in the order they are enqueued: group after group
+    size_t prof_need = 0, bnd_need = 0;      // workspaces: profiles of the largest group (bytes), boundary columns (ints)
+};
+
+SearchMultiPlan plan_search_multi(const SearchMultiJob& job);
 
 // ---- alignment of chosen hits under affine scoring (sw_align_affine_device): sw_align_affine_wave<C> for C = 4, 8, 16, its index in
 // kAlignAffine (sw_api_search.hip, which checks its order against it at compile time)

@@ -2,8 +2,8 @@
 """Post-build audit of the gfx950 ISA of sw_kernels.hip (run by `make check_isa`):
   * v126/v127 (landing registers of the hand-tracked edge prefetch) appear ONLY in the two asm
     statements that own them;
-  * no scratch (spills) in the fill kernels, none at all in the search kernels (sw_search.hip, sw_search_affine.hip) and the alignment
-    kernels (sw_align_affine.hip), whose work counter is a vector buffer atomic."""
+  * no scratch (spills) in the fill kernels, none at all in the search kernels (sw_search.hip, sw_search_affine.hip, sw_search_multi.hip)
+    and the alignment kernels (sw_align_affine.hip), whose work counter is a vector buffer atomic."""
 import re, subprocess, sys, os, tempfile
 here = os.path.dirname(os.path.abspath(__file__))
 src = os.path.join(here, "..", "smith-waterman_amd", "csrc", "sw_kernels.hip")
@@ -79,6 +79,16 @@ bodies = re.findall(r"^(\S*sw_search_affine_wave\S*):[^\n]*\n(.*?)^\.Lfunc_end\d
 without = [name for name, body in bodies if not re.search(r"^\s*buffer_atomic_add ", body, flags=re.M)]
 if naffine < 3 or len(bodies) != naffine or without:
     print(f"affine search kernels: expected a vector buffer atomic work counter in each of {naffine} kernels ({len(bodies)} bodies found, none in {without})"); sys.exit(1)
+# sw_search_multi.hip (many queries against a prepared database): the same two rules for its three kernels
+s7 = dev_asm("sw_search_multi.hip")
+for m in re.finditer(r"\.private_segment_fixed_size:\s*(\d+)", s7):
+    if int(m.group(1)) > 0:
+        print("scratch in use (many-query search):", m.group(0)); sys.exit(1)
+nmulti = len(re.findall(r"^\s*\.name:\s+\S*sw_search_affine_multi_wave", s7, flags=re.M))
+bodies7 = re.findall(r"^(\S*sw_search_affine_multi_wave\S*):[^\n]*\n(.*?)^\.Lfunc_end\d+:", s7, flags=re.M | re.S)
+without7 = [name for name, body in bodies7 if not re.search(r"^\s*buffer_atomic_add ", body, flags=re.M)]
+if nmulti != 3 or len(bodies7) != nmulti or without7:
+    print(f"many-query search kernels: expected a vector buffer atomic work counter in each of 3 kernels ({nmulti} kernels, {len(bodies7)} bodies found, none in {without7})"); sys.exit(1)
 # sw_align_affine.hip (alignment of hits): no scratch at all
 s6 = dev_asm("sw_align_affine.hip")
 for m in re.finditer(r"\.private_segment_fixed_size:\s*(\d+)", s6):
@@ -88,4 +98,4 @@ nalign = len(re.findall(r"^\s*\.name:\s+\S*sw_align_affine_wave", s6, flags=re.M
 if nalign < 3:
     print(f"affine alignment kernels: expected 3, found {nalign}"); sys.exit(1)
 n = len(re.findall(r"global_load_dwordx2 v\[126:127\]", s))
-print(f"check_isa ok: {n} prefetch sites, v126/v127 private; {nprod} producer paths keep v100..v120 private; traceback window v62..v127 private; no scratch; {nsearch} search kernels without scratch; {naffine} affine search kernels without scratch; {nalign} affine alignment kernels without scratch")
+print(f"check_isa ok: {n} prefetch sites, v126/v127 private; {nprod} producer paths keep v100..v120 private; traceback window v62..v127 private; no scratch; {nsearch} search kernels without scratch; {naffine} affine search kernels without scratch; {nmulti} many-query search kernels without scratch; {nalign} affine alignment kernels without scratch")
