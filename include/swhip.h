@@ -306,6 +306,44 @@ int  sw_db_search_affine(sw_ctx* ctx, const sw_db* db, const char* d_queries, co
 int  sw_search_affine_multi_host(const char* queries, const int64_t* qoffsets, int64_t nqueries, const char* db,
                                  const int64_t* offsets, int64_t ntargets, const sw_affine* scoring, sw_result* results);
 
+/* The best targets of every query, selected on the device (csrc/sw_search_top.hip).  A caller of sw_db_search_affine wants the best few
+ * targets per query, not nqueries x ntargets results of 24 bytes; these calls deliver nqueries x top hits.
+ *   d_hits  : device, nqueries x top sw_hit = {target, max_pos, max_score}.  Row q holds the hits of query q in RANK ORDER: max_score
+ *             descending, then target ascending.  max_pos and max_score of a hit are bit for bit what sw_db_search_affine writes for
+ *             that (query, target) pair.
+ *   min_score : only targets with max_score >= min_score qualify; with min_score <= 0 every target does, empty ones included, with their
+ *             {target, 0, 0}.
+ *   d_nhits : device, nqueries int64: d_nhits[q] = min(top, qualifying targets of query q).  The remaining entries of row q are
+ *             {-1, 0, 0}.
+ * Every entry of d_hits and d_nhits is written and nothing outside them.  The result is unique: the rank order leaves no choice, and
+ * no run differs from another although the selection counts and gathers with atomics.  Asynchronous on `stream`, no host round trip;
+ * the host work of a call is O(nqueries).
+ *   sw_top_hits_device       the selection alone, over any query-major table of nqueries x ntargets sw_result on the device: the output of
+ *             sw_db_search_affine, or of sw_search_device / sw_search_affine_device with nqueries = 1.  PRECONDITION, which the call cannot
+ *             check on device data: 0 <= max_score < 2^24 for every entry (the bound every search call enforces).  d_results is only read.
+ *             SW_EINVAL: NULL pointers, nqueries < 0, ntargets < 0 or ntargets >= 2^31, top < 1 or top > SW_TOP_MAX.
+ *   sw_db_search_affine_top  search and selection through a prepared handle, with BOUNDED result memory: the full table never exists.
+ *             Arguments as for sw_db_search_affine.  The queries are taken in consecutive chunks whose result rows (24 bytes per target)
+ *             fit a per-context workspace that the option "search_results_mib" bounds (default 1024, 1..2^20); every chunk runs through
+ *             the many-query search of sw_db_search_affine into the workspace and the selection then writes that chunk's rows of
+ *             d_hits; chunks follow each other in the stream and share the workspace.  A query whose single row exceeds the budget is a
+ *             chunk of its own -- the option refuses nothing.  Besides the workspace the selection holds 8 KiB of counters per query of
+ *             a chunk, for at most 4096 queries.  SW_EINVAL: the argument errors of sw_db_search_affine, top < 1 or top > SW_TOP_MAX,
+ *             NULL d_hits or d_nhits.  nqueries == 0 launches nothing; a handle with ntargets == 0 writes nhits = 0 and the {-1, 0, 0}
+ *             pattern.  "last_search_top_chunks" and "last_search_top_kernel" (0: every row was sorted whole, at most SW_TOP_MAX targets;
+ *             1: radix select) describe the last call.
+ *   sw_search_affine_multi_top_host  the CPU leg on host memory, no GPU needed: sw_search_affine_host per query and a sort by the same
+ *             rule; arguments as for sw_search_affine_multi_host, every one checked before the first query runs. */
+#define SW_TOP_MAX 4096
+typedef struct { int64_t target, max_pos, max_score; } sw_hit;
+int  sw_top_hits_device(sw_ctx* ctx, const sw_result* d_results, int64_t nqueries, int64_t ntargets, int64_t top, int64_t min_score,
+                        sw_hit* d_hits, int64_t* d_nhits, void* stream);
+int  sw_db_search_affine_top(sw_ctx* ctx, const sw_db* db, const char* d_queries, const int64_t* qoffsets, int64_t nqueries,
+                             const sw_affine* scoring, int64_t top, int64_t min_score, sw_hit* d_hits, int64_t* d_nhits, void* stream);
+int  sw_search_affine_multi_top_host(const char* queries, const int64_t* qoffsets, int64_t nqueries, const char* db,
+                                     const int64_t* offsets, int64_t ntargets, const sw_affine* scoring, int64_t top, int64_t min_score,
+                                     sw_hit* hits, int64_t* nhits);
+
 /* Tables.  sw_submat_match: s[x][y] = x == y ? match : mismatch (matchMissmatchScore, serial_smithW.c:251-256; both must fit int8:
  * the builder returns nothing, so it clamps them to -128..127 -- a caller that takes them from a user checks the range first, as
  * smithW and the Python wrapper do, which refuse such scores).  sw_submat_from_letters: `scores` is n x n, row = query letter, over the n bytes of
@@ -483,7 +521,9 @@ int sw_synchronize(sw_ctx* ctx, void* stream);   /* waits for `stream`; reports 
  * last sw_align_affine_device call: columns per lane / 8) and "last_align_affine_slots" (its direction matrices, one per wave at
  * work); "align_workspace_mib" (settable, default 1024) bounds the direction workspace of that call; "search_profile_mib" (settable,
  * default 256) bounds the profiles of a group of sw_db_search_affine, "last_search_multi_groups", "last_search_multi_launches" and
- * "last_search_multi_grid" (workgroups of its last launch) describe the last such call. */
+ * "last_search_multi_grid" (workgroups of its last launch) describe the last such call; "search_results_mib" (settable, default 1024,
+ * 1..2^20) bounds the result rows a chunk of sw_db_search_affine_top holds, "last_search_top_chunks" and "last_search_top_kernel"
+ * describe the last sw_db_search_affine_top / sw_top_hits_device call. */
 int sw_set_option(sw_ctx* ctx, const char* name, int64_t value);
 int64_t sw_get_option(sw_ctx* ctx, const char* name);
 

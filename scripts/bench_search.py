@@ -13,6 +13,10 @@
   beside the same number of sw_search_affine_device calls in the same process (multi<N>_ms / single<N>_ms, and both per query), 64
   queries of log-normal length (median 300) likewise, and 64 queries of 32 letters against the first 2000 targets -- the case where a
   launch per query leaves most of the device idle
+  --top: data set (a) only, 64 queries of --qlen, the best 100 targets of each onto the host by two paths in the same process, wall
+  clock, medians and ranges of --reps after --warmup: (1) sw_db_search_affine into the full table, synchronize, the table to the host,
+  top_hits of every row; (2) sw_db_search_affine_top until the hits are on the host, at the default "search_results_mib" and at 64 (five
+  chunks).  The hits are compared one by one; the device memory of the results is computed from the sizes, not measured
 GCUPS = query letters x target letters / time of the call (torch events, median of --reps after --warmup)."""
 import argparse
 import importlib
@@ -56,6 +60,7 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--only-a", action="store_true", help="data set (a) only: linear search, affine search, alignment of its top hits")
     ap.add_argument("--multi", action="store_true", help="data set (a) only: many queries through a prepared database against one call per query")
+    ap.add_argument("--top", action="store_true", help="data set (a) only: the best 100 targets of 64 queries by the full table and by the selection on the device")
     args = ap.parse_args()
     rng = np.random.default_rng(2026)
     eng = swamd.Engine(0)
@@ -158,6 +163,60 @@ def main():
         db.close()
         small.close()
 
+    def top_leg(packed, offs, nq=64, top=100):
+        import time
+        d_db = torch.from_numpy(packed.copy()).to(dev)
+        db = eng.prepare_db(d_db, offs)
+        nt = len(offs) - 1
+        qoffs = np.arange(nq + 1, dtype=np.int64) * args.qlen
+        d_q = torch.from_numpy(rng.choice(PROTEIN, int(qoffs[-1])).astype(np.uint8)).to(dev)
+        scoring = (sub, -11, -1)
+        table = torch.zeros(nq * nt * 3, dtype=torch.int64, device=dev)
+        bufs = (torch.zeros(nq * top * 3, dtype=torch.int64, device=dev), torch.zeros(nq, dtype=torch.int64, device=dev))
+
+        def full_table():
+            res = db.search_affine_device(d_q, qoffs, scoring, out=table)
+            eng.synchronize()
+            host = res.cpu().numpy()
+            hits = np.zeros((nq, top, 3), np.int64)
+            for k in range(nq):
+                order = swamd.top_hits(host[k], top)
+                hits[k, :, 0], hits[k, :, 1], hits[k, :, 2] = order, host[k, order, 0], host[k, order, 1]
+            return hits
+
+        def on_device():
+            hits, nhits = db.search_affine_top_device(d_q, qoffs, scoring, top, out=bufs)
+            eng.synchronize()
+            return hits.cpu().numpy(), nhits.cpu().numpy()
+
+        def wall(fn):
+            for _ in range(args.warmup):
+                last = fn()
+            ms = []
+            for _ in range(args.reps):
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                last = fn()
+                ms.append((time.perf_counter() - t0) * 1e3)
+            return last, round(float(np.median(ms)), 3), [round(min(ms), 3), round(max(ms), 3)]
+
+        want, out["top_full_table_ms"], out["top_full_table_range_ms"] = wall(full_table)
+        (got, nhits), out["top_on_device_ms"], out["top_on_device_range_ms"] = wall(on_device)
+        out["top_chunks"] = eng.get_option("last_search_top_chunks")
+        out["top_identical"] = bool(np.array_equal(got, want) and (nhits == top).all())
+        eng.set_option("search_results_mib", 64)
+        (got, nhits), out["top_on_device_64mib_ms"], out["top_on_device_64mib_range_ms"] = wall(on_device)
+        out["top_64mib_chunks"] = eng.get_option("last_search_top_chunks")
+        out["top_64mib_identical"] = bool(np.array_equal(got, want) and (nhits == top).all())
+        eng.set_option("search_results_mib", 1024)
+        out["top_ranges_overlap"] = bool(out["top_on_device_range_ms"][1] >= out["top_full_table_range_ms"][0])
+        row = nt * 24
+        out["top_queries"], out["top_k"], out["top_targets"] = nq, top, nt
+        out["top_full_table_result_bytes_computed"] = nq * row
+        out["top_on_device_result_bytes_computed"] = min(nq, max(1, (1024 << 20) // row)) * row + nq * (top * 24 + 8 + 8192 + 24)
+        out["top_on_device_64mib_result_bytes_computed"] = min(nq, max(1, (64 << 20) // row)) * row + nq * (top * 24 + 8 + 8192 + 24)
+        db.close()
+
     # (a) protein database, log-normal lengths
     q = rng.choice(PROTEIN, args.qlen).astype(np.uint8)
     lens = np.clip(np.round(rng.lognormal(np.log(300), 0.6, args.targets)), 1, 35_000).astype(np.int64)
@@ -167,8 +226,11 @@ def main():
     out["a_letters"] = int(offs[-1])
     out["a_len_median"] = int(np.median(lens))
     out["a_len_max"] = int(lens.max())
-    if args.multi:
-        multi_legs(packed, offs)
+    if args.multi or args.top:
+        if args.multi:
+            multi_legs(packed, offs)
+        if args.top:
+            top_leg(packed, offs)
         eng.close()
         print(json.dumps(out))
         return

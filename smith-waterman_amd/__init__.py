@@ -69,6 +69,9 @@ ABI = {
     "sw_db_info": (_i32, [_vp, ctypes.POINTER(_i64), ctypes.POINTER(_i64), ctypes.POINTER(_i64), ctypes.POINTER(_i64)]),
     "sw_db_search_affine": (_i32, [_vp, _vp, _vp, _vp, _i64, ctypes.POINTER(_Affine), _vp, _vp]),
     "sw_search_affine_multi_host": (_i32, [_vp, _vp, _i64, _vp, _vp, _i64, ctypes.POINTER(_Affine), _vp]),
+    "sw_top_hits_device": (_i32, [_vp, _vp, _i64, _i64, _i64, _i64, _vp, _vp, _vp]),
+    "sw_db_search_affine_top": (_i32, [_vp, _vp, _vp, _vp, _i64, ctypes.POINTER(_Affine), _i64, _i64, _vp, _vp, _vp]),
+    "sw_search_affine_multi_top_host": (_i32, [_vp, _vp, _i64, _vp, _vp, _i64, ctypes.POINTER(_Affine), _i64, _i64, _vp, _vp]),
     "sw_align_affine_device": (_i32, [_vp, _vp, _i64, _vp, _vp, _i64, _vp, _i64, ctypes.POINTER(_Affine), _vp, _vp, _i64, _vp]),
     "sw_align_affine_host": (_i32, [_vp, _i64, _vp, _vp, _i64, _vp, _i64, ctypes.POINTER(_Affine), _vp, _vp, _i64]),
     "sw_submat_match": (None, [_i32, _i32, _vp]),
@@ -111,6 +114,8 @@ ABI = {
     "sw_set_option": (_i32, [_vp, ctypes.c_char_p, _i64]),
     "sw_get_option": (_i64, [_vp, ctypes.c_char_p]),
 }
+
+SW_TOP_MAX = 4096   # include/swhip.h: the most hits per query a selecting call takes
 
 _lib = None
 
@@ -248,6 +253,22 @@ def search_affine_multi_host(queries, targets, scoring):
     _check(lib().sw_search_affine_multi_host(qs.ctypes.data, qoffs.ctypes.data, nq, db.ctypes.data, offs.ctypes.data, ntargets, ctypes.byref(sc),
                                              res.ctypes.data))
     return res[:nq * ntargets].reshape(nq, ntargets, 3)
+
+
+def search_affine_multi_top_host(queries, targets, scoring, top: int, min_score: int = 0):
+    """sw_search_affine_multi_top_host: the best `top` targets of every query in plain C++ on the host (no GPU).  Arguments and results
+    as Database.search_affine_top: returns (hits (nqueries, top, 3) int64 of (target, max_pos, max_score), nhits (nqueries,) int64)."""
+    qpacked, qoffs = _pack_targets(queries)
+    packed, offs = _pack_targets(targets)
+    nq, ntargets, k = len(qoffs) - 1, len(offs) - 1, max(0, int(top))
+    qs = qpacked if len(qpacked) else np.zeros(1, np.uint8)
+    db = packed if len(packed) else np.zeros(1, np.uint8)
+    hits = np.zeros((max(1, nq * k), 3), np.int64)
+    nhits = np.zeros(max(1, nq), np.int64)
+    sub, sc = _affine(*scoring)
+    _check(lib().sw_search_affine_multi_top_host(qs.ctypes.data, qoffs.ctypes.data, nq, db.ctypes.data, offs.ctypes.data, ntargets, ctypes.byref(sc),
+                                                 int(top), int(min_score), hits.ctypes.data, nhits.ctypes.data))
+    return hits[:nq * k].reshape(nq, k, 3), nhits[:nq]
 
 
 def _ops_list(aln, ops, cap):
@@ -455,6 +476,34 @@ class Database:
         sub, sc = _affine(*scoring)
         _check(lib().sw_db_search_affine(eng._h, self._h, d_queries.data_ptr(), qoffs.ctypes.data, nq, ctypes.byref(sc), res.data_ptr(), eng._stream()))
         return res[:n].view(nq, self.ntargets, 3)
+
+    def search_affine_top(self, queries, scoring, top: int, min_score: int = 0):
+        """The best `top` targets of every query, selected on the device (sw_db_search_affine_top): the full result table never exists
+        and only the hits come back.  queries and scoring as for search_affine.  Returns numpy (hits (nqueries, top, 3) int64 of
+        (target, max_pos, max_score) in rank order -- score descending, then target ascending; unused entries (-1, 0, 0) --,
+        nhits (nqueries,) int64).  Only targets with max_score >= min_score qualify."""
+        eng = self.engine
+        t = eng.torch
+        qpacked, qoffs = _pack_targets(queries)
+        d_q = t.from_numpy(qpacked.copy() if len(qpacked) else np.zeros(1, np.uint8)).to(f"cuda:{eng.device}")
+        hits, nhits = self.search_affine_top_device(d_q, qoffs, scoring, top, min_score)
+        eng.synchronize()
+        return hits.cpu().numpy(), nhits.cpu().numpy()
+
+    def search_affine_top_device(self, d_queries, qoffsets, scoring, top: int, min_score: int = 0, out=None):
+        """sw_db_search_affine_top on device-resident queries; asynchronous on torch's current stream.  Returns torch (hits (nqueries,
+        top, 3), nhits (nqueries,)), views of `out` = (flat int64 tensor of at least nqueries * top * 3 elements, int64 tensor of at
+        least nqueries elements) if given."""
+        eng = self.engine
+        qoffs = np.ascontiguousarray(qoffsets, np.int64).reshape(-1)
+        if len(qoffs) == 0:
+            qoffs = np.zeros(1, np.int64)
+        nq = len(qoffs) - 1
+        hits, nhits = eng._top_out(nq, top, out)
+        sub, sc = _affine(*scoring)
+        _check(lib().sw_db_search_affine_top(eng._h, self._h, d_queries.data_ptr(), qoffs.ctypes.data, nq, ctypes.byref(sc), int(top), int(min_score),
+                                             hits.data_ptr(), nhits.data_ptr(), eng._stream()))
+        return eng._top_views(hits, nhits, nq, top)
 
 
 class Engine:
@@ -706,6 +755,34 @@ class Engine:
         _check(lib().sw_search_affine_device(self._h, d_query.data_ptr(), qlen, d_db.data_ptr(), offs.ctypes.data, ntargets, ctypes.byref(sc),
                                              res.data_ptr(), self._stream()))
         return res[:ntargets]
+
+    def _top_out(self, nq: int, top: int, out):
+        """The (hits, nhits) buffers of a selecting call: `out` checked, or fresh ones."""
+        t = self.torch
+        n = nq * max(0, int(top)) * 3
+        if out is None:
+            dev = f"cuda:{self.device}"
+            return t.zeros(max(3, n), dtype=t.int64, device=dev), t.zeros(max(1, nq), dtype=t.int64, device=dev)
+        hits, nhits = out
+        for x, need, what in ((hits, n, "hits"), (nhits, nq, "nhits")):
+            if x.dtype != t.int64 or not x.is_contiguous() or x.numel() < need:
+                raise ValueError(f"out: {what} must be a contiguous int64 tensor of at least {need} elements")
+        return hits, nhits
+
+    @staticmethod
+    def _top_views(hits, nhits, nq: int, top: int):
+        k = max(0, int(top))
+        return hits.view(-1)[:nq * k * 3].view(nq, k, 3), nhits.view(-1)[:nq]
+
+    def top_hits_device(self, d_results, nqueries: int, ntargets: int, top: int, min_score: int = 0, out=None):
+        """sw_top_hits_device: the best `top` targets of every row of a query-major (nqueries, ntargets, 3) int64 result tensor on the
+        device (what Database.search_affine_device or search_affine_device returns); asynchronous on torch's current stream.  Every
+        max_score must lie in 0 .. 2^24 - 1.  Returns torch (hits (nqueries, top, 3) of (target, max_pos, max_score), nhits (nqueries,));
+        `out` as for Database.search_affine_top_device."""
+        hits, nhits = self._top_out(int(nqueries), top, out)
+        _check(lib().sw_top_hits_device(self._h, d_results.data_ptr(), int(nqueries), int(ntargets), int(top), int(min_score), hits.data_ptr(),
+                                        nhits.data_ptr(), self._stream()))
+        return self._top_views(hits, nhits, int(nqueries), top)
 
     def prepare_db(self, db, offsets=None) -> Database:
         """A prepared database (sw_db_create) for Database.search_affine.  db: a list of sequences, a (packed, offsets) pair, or --

@@ -9,7 +9,9 @@
 //                              without --gap-extend E = the gap of --scores; --gap-extend alone (O = 0) is the linear search with gap E
 //     ... --all-queries       EVERY record of Q.fa through one prepared database handle and one call (sw_db_create / sw_db_search_affine): the
 //                              hit block of --search once per query, each under a line "## query record <i> of <Q.fa>"; --top, --matrix,
-//                              --gap-open, --gap-extend and --align (sw_align_affine_device per query) as for one query
+//                              --gap-open, --gap-extend and --align (sw_align_affine_device per query) as for one query.  The K best hits per
+//                              query are selected on the device (sw_db_search_affine_top): only they are copied back
+//     ... --min-score S       with --all-queries: only hits with a score of at least S are printed (fewer than K where fewer qualify)
 //     ... --align             every printed hit is followed by its alignment (sw_align_affine_device; the canonical alignment of swhip.h), four lines:
 //                                "align\t<q_begin>\t<q_end>\t<t_begin>\t<t_end>\t<nops>"   query [q_begin, q_end) against target [t_begin, t_end), 0-based, half open
 //                                "Q <query letters, '-' where the target has letters of its own>"
@@ -100,14 +102,24 @@ static bool parse_int(const char* flag, const char* text, int* out) {
     *out = (int)v;
     return true;
 }
-// The hit block of one query: the header line, the best `top` hits by score (ties: lower record first) and, with `align`, every hit's
-// alignment (the K hits re-filled with directions and walked on the device).
-static int print_hits(sw_ctx* ctx, const char* q, int64_t qlen, const void* d_q, const std::vector<char>& db, const void* d_db, const std::vector<int64_t>& offs,
-                      int64_t nrec, int64_t total, const sw_result* res, long long top, bool align, const sw_affine& aff) {
-    std::vector<int64_t> order((size_t)nrec);
-    for (int64_t k = 0; k < nrec; ++k) order[(size_t)k] = k;
+// The best K targets of one row of results in rank order -- by score, ties: lower record first --, those below min_score left out.
+static std::vector<sw_hit> rank_hits(const sw_result* res, int64_t nrec, long long K, long long min_score) {
+    std::vector<int64_t> order;
+    for (int64_t k = 0; k < nrec; ++k)
+        if (res[(size_t)k].max_score >= min_score) order.push_back(k);
     std::stable_sort(order.begin(), order.end(), [&](int64_t x, int64_t y) { return res[(size_t)x].max_score > res[(size_t)y].max_score; });
-    const long long K = std::max(0ll, std::min(top, (long long)nrec));
+    order.resize((size_t)std::max(0ll, std::min(K, (long long)order.size())));
+    std::vector<sw_hit> hits;
+    for (int64_t k : order) hits.push_back(sw_hit{k, res[(size_t)k].max_pos, res[(size_t)k].max_score});
+    return hits;
+}
+
+// The hit block of one query: the header line, its K hits in rank order and, with `align`, every hit's alignment (the K hits re-filled
+// with directions and walked on the device).
+static int print_hits(sw_ctx* ctx, const char* q, int64_t qlen, const void* d_q, const std::vector<char>& db, const void* d_db, const std::vector<int64_t>& offs,
+                      int64_t nrec, int64_t total, const sw_hit* hits, long long K, bool align, const sw_affine& aff) {
+    std::vector<int64_t> order((size_t)K);
+    for (long long i = 0; i < K; ++i) order[(size_t)i] = hits[i].target;
     // --align: the K hits re-filled with directions and walked on the device, ops of at most query + longest hit letters each
     std::vector<sw_alignment> aln((size_t)(align ? K : 0));
     std::vector<char> ops;
@@ -127,7 +139,7 @@ static int print_hits(sw_ctx* ctx, const char* q, int64_t qlen, const void* d_q,
     }
     printf("# query %lld letters, %lld targets, %lld letters; rank\trecord\tscore\ttarget_end\tquery_end\n", (long long)qlen, (long long)nrec, (long long)total);
     for (long long i = 0; i < K; ++i) {
-        const sw_result& r = res[(size_t)order[(size_t)i]];
+        const sw_hit& r = hits[i];
         const long long te = r.max_pos / (qlen + 1), qe = r.max_pos % (qlen + 1);
         printf("%lld\t%lld\t%lld\t%lld\t%lld\n", i + 1, (long long)order[(size_t)i], (long long)r.max_score, te, qe);
         if (!align) continue;
@@ -178,7 +190,8 @@ static int search_main(const char* qpath, long long rec, const char* dbpath, lon
     const double t1 = now_s();
     std::vector<sw_result> res((size_t)nrec);
     if (nrec) CHECK(sw_memcpy_d2h(ctx, res.data(), d_res, (size_t)nrec * sizeof(sw_result)));
-    if (int rc = print_hits(ctx, q.data(), qlen, d_q, db, d_db, offs, nrec, total, res.data(), top, align, aff)) return rc;
+    const std::vector<sw_hit> hits = rank_hits(res.data(), nrec, top, 0);
+    if (int rc = print_hits(ctx, q.data(), qlen, d_q, db, d_db, offs, nrec, total, hits.data(), (long long)hits.size(), align, aff)) return rc;
     const double cells = (double)qlen * (double)total;
     printf("\nElapsed time for database search: %f (%.1f GCUPS)\n\n", t1 - t0, t1 > t0 ? cells / (t1 - t0) / 1e9 : 0.0);
     (void)sw_device_free(ctx, d_q); (void)sw_device_free(ctx, d_db); (void)sw_device_free(ctx, d_res);
@@ -187,9 +200,11 @@ static int search_main(const char* qpath, long long rec, const char* dbpath, lon
 }
 
 // --search --all-queries: every record of the query file against the database through ONE prepared handle and one call
-// (sw_db_create / sw_db_search_affine); the hit block of --search once per query, each under a line that names the record.  A linear
-// search goes through the match / mismatch table of --scores with gap_open 0, which sw_search_device equals bit for bit.
-static int search_all_main(const char* qpath, const char* dbpath, long long top, const sw_scores& sc, const AffineArgs& af, bool align) {
+// (sw_db_create / sw_db_search_affine_top); the hit block of --search once per query, each under a line that names the record.  The K
+// best hits of every query are selected on the device and only they come back; more than SW_TOP_MAX hits per query go the long way:
+// the whole table to the host and a sort of every row.  A linear search goes through the match / mismatch table of --scores with
+// gap_open 0, which sw_search_device equals bit for bit.
+static int search_all_main(const char* qpath, const char* dbpath, long long top, long long min_score, const sw_scores& sc, const AffineArgs& af, bool align) {
     int64_t nq = 0, qtotal = 0, nrec = 0, total = 0;
     CHECK(sw_read_fasta_db(qpath, nullptr, 0, nullptr, 0, &nq, &qtotal));
     std::vector<char> qs((size_t)qtotal + 1);
@@ -199,13 +214,17 @@ static int search_all_main(const char* qpath, const char* dbpath, long long top,
     std::vector<char> db((size_t)total + 1);
     std::vector<int64_t> offs((size_t)nrec + 1, 0);
     CHECK(sw_read_fasta_db(dbpath, db.data(), total, offs.data(), nrec + 1, &nrec, &total));
+    const long long K = std::max(0ll, std::min(top, (long long)nrec));
+    const bool on_device = K <= SW_TOP_MAX;
     sw_ctx* ctx = nullptr;
     CHECK(sw_create(0, &ctx));
-    void *d_q = nullptr, *d_db = nullptr, *d_res = nullptr;
-    const size_t nres = (size_t)std::max<int64_t>(1, nq * nrec);
+    void *d_q = nullptr, *d_db = nullptr, *d_res = nullptr, *d_hits = nullptr, *d_nhits = nullptr;
+    const size_t nres = on_device ? 1 : (size_t)std::max<int64_t>(1, nq * nrec), nhit = (size_t)std::max<int64_t>(1, nq * K);
     CHECK(sw_device_malloc(ctx, (size_t)qtotal + 16, &d_q));
     CHECK(sw_device_malloc(ctx, (size_t)total + 16, &d_db));
     CHECK(sw_device_malloc(ctx, nres * sizeof(sw_result), &d_res));
+    CHECK(sw_device_malloc(ctx, nhit * sizeof(sw_hit), &d_hits));
+    CHECK(sw_device_malloc(ctx, (size_t)std::max<int64_t>(1, nq) * sizeof(int64_t), &d_nhits));
     if (qtotal) CHECK(sw_memcpy_h2d(ctx, d_q, qs.data(), (size_t)qtotal));
     if (total) CHECK(sw_memcpy_h2d(ctx, d_db, db.data(), (size_t)total));
     std::vector<sw_submat> sub(1);
@@ -216,21 +235,32 @@ static int search_all_main(const char* qpath, const char* dbpath, long long top,
     const double t0 = now_s();
     CHECK(sw_db_create(ctx, (const char*)d_db, offs.data(), nrec, &handle));
     const double t1 = now_s();
-    CHECK(sw_db_search_affine(ctx, handle, (const char*)d_q, qoffs.data(), nq, &aff, (sw_result*)d_res, nullptr));
+    if (!on_device) CHECK(sw_db_search_affine(ctx, handle, (const char*)d_q, qoffs.data(), nq, &aff, (sw_result*)d_res, nullptr));
+    else if (K > 0) CHECK(sw_db_search_affine_top(ctx, handle, (const char*)d_q, qoffs.data(), nq, &aff, K, min_score, (sw_hit*)d_hits, (int64_t*)d_nhits, nullptr));
     CHECK(sw_synchronize(ctx, nullptr));
     const double t2 = now_s();
+    std::vector<sw_hit> hits(nhit);
+    std::vector<int64_t> nhits((size_t)nq + 1, 0);
+    if (on_device && K > 0 && nq > 0) {
+        CHECK(sw_memcpy_d2h(ctx, hits.data(), d_hits, (size_t)(nq * K) * sizeof(sw_hit)));
+        CHECK(sw_memcpy_d2h(ctx, nhits.data(), d_nhits, (size_t)nq * sizeof(int64_t)));
+    }
     std::vector<sw_result> res(nres);
-    if (nq > 0 && nrec > 0) CHECK(sw_memcpy_d2h(ctx, res.data(), d_res, (size_t)(nq * nrec) * sizeof(sw_result)));
+    if (!on_device && nq > 0) CHECK(sw_memcpy_d2h(ctx, res.data(), d_res, (size_t)(nq * nrec) * sizeof(sw_result)));
     for (int64_t i = 0; i < nq; ++i) {
         printf("## query record %lld of %s\n", (long long)i, qpath);
+        const std::vector<sw_hit> ranked = on_device ? std::vector<sw_hit>() : rank_hits(res.data() + i * nrec, nrec, K, min_score);
+        const sw_hit* row = on_device ? hits.data() + i * K : ranked.data();
+        const long long n = on_device ? (long long)nhits[(size_t)i] : (long long)ranked.size();
         if (int rc = print_hits(ctx, qs.data() + qoffs[(size_t)i], qoffs[(size_t)i + 1] - qoffs[(size_t)i], (const char*)d_q + qoffs[(size_t)i], db, d_db, offs, nrec,
-                                total, res.data() + i * nrec, top, align, aff)) return rc;
+                                total, row, n, align, aff)) return rc;
     }
     const double cells = (double)qtotal * (double)total;
     printf("\nElapsed time for database search: %f (%.1f GCUPS; %lld queries in one call, handle prepared in %f)\n\n", t2 - t1,
            t2 > t1 ? cells / (t2 - t1) / 1e9 : 0.0, (long long)nq, t1 - t0);
     sw_db_free(handle);
     (void)sw_device_free(ctx, d_q); (void)sw_device_free(ctx, d_db); (void)sw_device_free(ctx, d_res);
+    (void)sw_device_free(ctx, d_hits); (void)sw_device_free(ctx, d_nhits);
     sw_destroy(ctx);
     return 0;
 }
@@ -243,7 +273,8 @@ int main(int argc, char** argv) {
     const char *fasta_a = nullptr, *fasta_b = nullptr;
     long long rec_a = 0, rec_b = 0;
     const char *search_q = nullptr, *search_db = nullptr;
-    long long top = 10;
+    long long top = 10, min_score = 0;
+    bool has_min_score = false;
     AffineArgs af;
     bool align = false, all_queries = false;
     sw_scores sc = {3, -3, -2};
@@ -265,6 +296,7 @@ int main(int argc, char** argv) {
         else if (f == "--fasta" && ai + 2 < argc) { fasta_a = argv[++ai]; fasta_b = argv[++ai]; builtin = false; }
         else if (f == "--search" && ai + 2 < argc) { search_q = argv[++ai]; search_db = argv[++ai]; builtin = false; }
         else if (f == "--top" && ai + 1 < argc) top = strtoll(argv[++ai], nullptr, 10);
+        else if (f == "--min-score" && ai + 1 < argc) { int v = 0; if (!parse_int("--min-score", argv[++ai], &v)) return 2; min_score = v; has_min_score = true; }
         else if (f == "--matrix" && ai + 1 < argc) { af.matrix = argv[++ai]; af.on = true; }
         else if (f == "--gap-open" && ai + 1 < argc) { if (!parse_int("--gap-open", argv[++ai], &af.open)) return 2; af.has_open = af.on = true; }
         else if (f == "--gap-extend" && ai + 1 < argc) { if (!parse_int("--gap-extend", argv[++ai], &af.extend)) return 2; af.has_extend = true; }
@@ -274,7 +306,7 @@ int main(int argc, char** argv) {
         else if (f == "--record-b" && ai + 1 < argc) rec_b = strtoll(argv[++ai], nullptr, 10);
         else if (f == "--seed" && ai + 1 < argc) seed = (unsigned)strtoul(argv[++ai], nullptr, 10);
         else if (f == "--scores" && ai + 3 < argc) { sc.match = atoi(argv[++ai]); sc.mismatch = atoi(argv[++ai]); sc.gap = atoi(argv[++ai]); }
-        else { fprintf(stderr, "usage: smithW [<cols> <rows> | --fasta A.fa B.fa [--record-a I] [--record-b J] | --search QUERY.fa DB.fa [--record-a I] [--top K] [--all-queries] [--matrix FILE] [--gap-open O] [--gap-extend E] [--align]] [--seed N] [--dump | --dump-labels] [--h64] [--no-backtrack] [--scores M X G] [--gpus N | --devices 0,1,..] [--p8]\n"); return 2; }
+        else { fprintf(stderr, "usage: smithW [<cols> <rows> | --fasta A.fa B.fa [--record-a I] [--record-b J] | --search QUERY.fa DB.fa [--record-a I] [--top K] [--all-queries [--min-score S]] [--matrix FILE] [--gap-open O] [--gap-extend E] [--align]] [--seed N] [--dump | --dump-labels] [--h64] [--no-backtrack] [--scores M X G] [--gpus N | --devices 0,1,..] [--p8]\n"); return 2; }
     }
     if (npos == 1) { fprintf(stderr, "smithW: <cols> needs <rows>\n"); return 2; }
     if (search_q) {
@@ -292,11 +324,13 @@ int main(int argc, char** argv) {
                 fprintf(stderr, "smithW: --all-queries without --matrix needs --scores M X within -128..127 (a table of signed bytes), got %d %d\n", sc.match, sc.mismatch);
                 return 2;
             }
-            return search_all_main(search_q, search_db, top, sc, af, align);
+            return search_all_main(search_q, search_db, top, min_score, sc, af, align);
         }
+        if (has_min_score) { fprintf(stderr, "smithW: --min-score goes with --search --all-queries\n"); return 2; }
         return search_main(search_q, rec_a, search_db, top, sc, af, align);
     }
     if (all_queries) { fprintf(stderr, "smithW: --all-queries goes with --search\n"); return 2; }
+    if (has_min_score) { fprintf(stderr, "smithW: --min-score goes with --search --all-queries\n"); return 2; }
     if (align) { fprintf(stderr, "smithW: --align goes with --search\n"); return 2; }
     if (af.on || af.has_extend) { fprintf(stderr, "smithW: --matrix / --gap-open / --gap-extend go with --search\n"); return 2; }
     if (fasta_a) {

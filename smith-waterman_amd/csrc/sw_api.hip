@@ -66,6 +66,9 @@ void sw_destroy(sw_ctx* c) {
     if (c->d_adir) (void)hipFree(c->d_adir);
     if (c->d_mq) (void)hipFree(c->d_mq);
     if (c->h_mq) (void)hipHostFree(c->h_mq);
+    if (c->d_tres) (void)hipFree(c->d_tres);
+    if (c->d_thist) (void)hipFree(c->d_thist);
+    if (c->d_tstate) (void)hipFree(c->d_tstate);
     delete c;
 }
 
@@ -99,6 +102,11 @@ int sw_set_option(sw_ctx* c, const char* name, int64_t v) {
     if (!strcmp(name, "search_profile_mib")) {
         if (v < 1 || v > (1ll << 20)) { set_err("search_profile_mib must be 1..2^20"); return SW_EINVAL; }
         c->opt_search_profile_mib = v;
+        return SW_OK;
+    }
+    if (!strcmp(name, "search_results_mib")) {
+        if (v < 1 || v > (1ll << 20)) { set_err("search_results_mib must be 1..2^20"); return SW_EINVAL; }
+        c->opt_search_results_mib = v;
         return SW_OK;
     }
     if (!strcmp(name, "placement_budget_ms")) { c->opt_place_budget_ms = v > 0 ? v : 1500; return SW_OK; }
@@ -155,6 +163,9 @@ int64_t sw_get_option(sw_ctx* c, const char* name) {
     if (!strcmp(name, "last_search_multi_groups")) return c->last_search_multi_groups;
     if (!strcmp(name, "last_search_multi_launches")) return c->last_search_multi_launches;
     if (!strcmp(name, "last_search_multi_grid")) return c->last_search_multi_grid;
+    if (!strcmp(name, "search_results_mib")) return c->opt_search_results_mib;
+    if (!strcmp(name, "last_search_top_chunks")) return c->last_search_top_chunks;
+    if (!strcmp(name, "last_search_top_kernel")) return c->last_search_top_kernel;
     if (!strcmp(name, "placement_budget_ms")) return c->opt_place_budget_ms;
     if (!strcmp(name, "placement_hold_gib")) return c->opt_place_hold_gib;
     if (!strcmp(name, "probe_foreign_pairs")) return c->opt.probe_foreign_pairs;

@@ -1,6 +1,7 @@
 // sw_api_search.hip -- the search family of the C-ABI (see include/swhip.h): database search, affine search, alignment of hits, and the
 // prepared database with its many-query search.  The calls share the workspaces of the context and one protocol around them; each reads
 // validate, plan, stage, upload, launch.
+#include <cstdint>
 #include <cstring>
 #include <vector>
 #include "sw_ctx.h"
@@ -121,6 +122,120 @@ static int grow_query_table(sw_ctx* c, size_t need, hipStream_t stream) {
         return SW_ENOMEM;
     }
     c->mq_cap = need;
+    return SW_OK;
+}
+
+// The many-query search of checked arguments into `d_results` (nqueries x ntargets, nqueries > 0, ntargets > 0): what sw_db_search_affine
+// does for a whole call and sw_db_search_affine_top for every chunk of one.  The caller holds the device's launch order (DevOrder).
+static int run_search_multi(sw_ctx* c, const sw_db* db, const char* d_queries, const int64_t* qoffsets, int64_t nqueries, const sw_affine* scoring,
+                            sw_result* d_results, hipStream_t stream) {
+    // empty targets keep the zeros: {0, 0, 0}
+    HIP_TRY(hipMemsetAsync(d_results, 0, (size_t)nqueries * (size_t)db->ntargets * sizeof(sw_result), stream));
+    if (db->nonempty == 0) return SW_OK;
+    if (int rc = occupancy_once(kSearchMulti, c->search_multi_per_cu, c->search_multi_per_cu_known)) return rc;
+    std::vector<int64_t> qlens((size_t)nqueries);
+    for (int64_t q = 0; q < nqueries; ++q) qlens[(size_t)q] = qoffsets[q + 1] - qoffsets[q];
+    swp::SearchMultiJob mj;
+    mj.qlens = qlens.data(); mj.nqueries = nqueries; mj.longest = db->longest; mj.nonempty = db->nonempty; mj.num_cus = c->num_cus;
+    mj.budget_bytes = c->opt_search_profile_mib << 20;
+    std::copy(std::begin(c->search_multi_per_cu), std::end(c->search_multi_per_cu), mj.per_cu);
+    const swp::SearchMultiPlan plan = swp::plan_search_multi(mj);
+    for (const swp::MultiLaunch& l : plan.launch)
+        if (c->search_multi_per_cu[l.kernel] < 1) { set_err("the many-query search kernel does not fit a CU on this device"); return SW_EDEVICE; }
+    if (int rc = stage_search_call(c, stream, 0, plan.prof_need, plan.bnd_need, scoring->sub)) return rc;
+    if (int rc = grow_query_table(c, (size_t)nqueries, stream)) return rc;
+    for (int64_t t = 0; t < nqueries; ++t) {
+        c->h_mq[t] = plan.table[(size_t)t];
+        c->h_mq[t].qstart = qoffsets[plan.table[(size_t)t].row];
+    }
+    memcpy(c->h_submat, scoring->sub, sizeof(sw_submat));
+    HIP_TRY(hipMemcpyAsync(c->d_mq, c->h_mq, (size_t)nqueries * sizeof(swk::MultiQuery), hipMemcpyHostToDevice, stream));
+    HIP_TRY(hipMemcpyAsync(c->d_submat, c->h_submat, sizeof(sw_submat), hipMemcpyHostToDevice, stream));
+    HIP_TRY(hipEventRecord(c->sitems_ev, stream));   // behind both uploads: whoever has waited for it may overwrite either pinned copy
+    size_t li = 0;
+    for (size_t g = 0; g < plan.group.size(); ++g) {
+        const swp::MultiGroup& grp = plan.group[g];
+        // every query's profile in shares of about 16 KiB, over at most 4096 workgroups
+        const int parts = (int)std::clamp<int64_t>(grp.prof_bytes / grp.nq / 16384, 1, 4096);
+        const unsigned blocks = (unsigned)std::min<int64_t>(grp.nq * parts, 4096);
+        hipLaunchKernelGGL(swk::sw_search_profile_submat_multi, dim3(blocks), dim3(256), 0, stream, (const unsigned char*)d_queries, c->d_mq + grp.q0, grp.nq,
+                           parts, c->d_sprof, (const signed char*)c->d_submat);
+        HIP_TRY(hipGetLastError());
+        for (; li < plan.launch.size() && plan.launch[li].group == (int)g; ++li) {
+            const swp::MultiLaunch& l = plan.launch[li];
+            swk::SearchMultiParams sp;
+            memset(&sp, 0, sizeof sp);
+            sp.db = (const unsigned char*)db->d_db;
+            sp.items = db->d_items; sp.rank0 = l.rank0;
+            sp.queries = c->d_mq + l.q0; sp.nq = (unsigned)l.nq; sp.nitems = l.items;
+            sp.prof = c->d_sprof; sp.ntargets = db->ntargets;
+            sp.ge = scoring->gap_extend; sp.goe = scoring->gap_open + scoring->gap_extend;
+            sp.bnd = l.bnd_per ? c->d_sbnd : nullptr; sp.bnd_per = l.bnd_per;
+            sp.counter = c->d_sctr;
+            sp.results = d_results;
+            HIP_TRY(hipMemsetAsync(c->d_sctr, 0, 4, stream));   // the work counter starts every launch at zero
+            hipLaunchKernelGGL(kSearchMulti[l.kernel].k, dim3((unsigned)l.grid), dim3(256), 0, stream, sp);
+            HIP_TRY(hipGetLastError());
+            c->last_search_multi_grid = l.grid;
+        }
+    }
+    c->last_search_multi_groups = (int64_t)plan.group.size(); c->last_search_multi_launches = (int64_t)plan.launch.size();
+    return SW_OK;
+}
+
+// The selection of one chunk (sw_search_top.hip): rows [0, nq) of `d_table` into d_hits / d_nhits, by the plan's kernel.  Everything
+// follows the stream; the histograms are wiped first, and every scan leaves them wiped for the next pass.
+static int select_top(sw_ctx* c, const swp::SearchTopPlan& plan, const sw_result* d_table, int64_t nq, int64_t ntargets, int64_t top, int64_t min_score,
+                      sw_hit* d_hits, int64_t* d_nhits, hipStream_t stream) {
+    swk::TopParams tp;
+    memset(&tp, 0, sizeof tp);
+    tp.results = d_table; tp.ntargets = ntargets; tp.nq = (unsigned)nq;
+    tp.wgs_row = (unsigned)plan.wgs_row; tp.slice = plan.slice; tp.tbits = plan.tbits;
+    tp.top = top; tp.min_score = min_score;
+    tp.hist = c->d_thist; tp.state = c->d_tstate;
+    tp.hits = d_hits; tp.nhits = d_nhits;
+    if (plan.kernel == 1) {
+        const unsigned row_grid = (unsigned)(nq * plan.wgs_row);
+        HIP_TRY(hipMemsetAsync(c->d_thist, 0, ((size_t)nq << swp::kTopDigitBits) * sizeof(unsigned int), stream));
+        for (int ps = 0; ps < plan.npasses; ++ps) {
+            tp.shift = plan.pass[ps].shift; tp.bits = plan.pass[ps].bits; tp.first = ps == 0;
+            hipLaunchKernelGGL(swk::sw_top_hist, dim3(row_grid), dim3(256), 0, stream, tp);
+            HIP_TRY(hipGetLastError());
+            hipLaunchKernelGGL(swk::sw_top_scan, dim3((unsigned)nq), dim3(256), 0, stream, tp);
+            HIP_TRY(hipGetLastError());
+        }
+        hipLaunchKernelGGL(swk::sw_top_compact, dim3(row_grid), dim3(256), 0, stream, tp);
+        HIP_TRY(hipGetLastError());
+        tp.selected = 1;
+    }
+    hipLaunchKernelGGL(swk::sw_top_sort, dim3((unsigned)nq), dim3(256), 0, stream, tp);
+    HIP_TRY(hipGetLastError());
+    return SW_OK;
+}
+
+// What the two selecting calls check alike, the plan of the call and the workspaces of the radix select.
+static int plan_top_call(sw_ctx* c, const char* who, int64_t nqueries, int64_t ntargets, int64_t top, const void* d_hits, const void* d_nhits,
+                         int64_t budget_bytes, swp::SearchTopPlan& plan) {
+    static_assert(SW_TOP_MAX == swp::kTopMax);
+    if (top < 1 || top > SW_TOP_MAX) { set_err("%s: top = %lld is out of range 1..%d", who, (long long)top, SW_TOP_MAX); return SW_EINVAL; }
+    if (!d_hits || !d_nhits) { set_err("%s: NULL d_hits or d_nhits", who); return SW_EINVAL; }
+    if (ntargets >= (1ll << 31)) { set_err("%s: %lld targets, the selection takes fewer than 2^31", who, (long long)ntargets); return SW_EINVAL; }
+    if (nqueries == 0) return SW_OK;
+    HIP_TRY(hipSetDevice(c->device));
+    if (c->top_hist_per_cu == 0) HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&c->top_hist_per_cu, swk::sw_top_hist, 256, 0));
+    swp::SearchTopJob tj;
+    tj.nqueries = nqueries; tj.ntargets = ntargets; tj.top = top; tj.budget_bytes = budget_bytes; tj.num_cus = c->num_cus; tj.per_cu = c->top_hist_per_cu;
+    plan = swp::plan_search_top(tj);
+    return SW_OK;
+}
+
+// ... grown under the device's launch order; `rows`: the call keeps the result rows of a chunk in the context's workspace
+static int grow_top_workspaces(sw_ctx* c, const swp::SearchTopPlan& plan, bool rows, hipStream_t stream) {
+    bool fresh = false;
+    if (int rc = grow_workspace((void**)&c->d_thist, c->thist_cap, plan.hist_need, sizeof(unsigned int), 0, stream, fresh)) return rc;
+    if (int rc = grow_workspace((void**)&c->d_tstate, c->tstate_cap, plan.state_need, sizeof(swk::TopState), 0, stream, fresh)) return rc;
+    if (rows)
+        if (int rc = grow_workspace((void**)&c->d_tres, c->tres_cap, plan.results_need, sizeof(sw_result), 0, stream, fresh)) return rc;
     return SW_OK;
 }
 
@@ -306,57 +421,47 @@ int sw_db_search_affine(sw_ctx* c, const sw_db* db, const char* d_queries, const
     HIP_TRY(hipSetDevice(c->device));
     DevOrder order(c, stream, false);
     if (order.rc) return order.rc;
-    // empty targets keep the zeros: {0, 0, 0}
-    HIP_TRY(hipMemsetAsync(d_results, 0, (size_t)nqueries * (size_t)db->ntargets * sizeof(sw_result), stream));
-    if (db->nonempty == 0) return SW_OK;
-    if (int rc = occupancy_once(kSearchMulti, c->search_multi_per_cu, c->search_multi_per_cu_known)) return rc;
-    std::vector<int64_t> qlens((size_t)nqueries);
-    for (int64_t q = 0; q < nqueries; ++q) qlens[(size_t)q] = qoffsets[q + 1] - qoffsets[q];
-    swp::SearchMultiJob mj;
-    mj.qlens = qlens.data(); mj.nqueries = nqueries; mj.longest = db->longest; mj.nonempty = db->nonempty; mj.num_cus = c->num_cus;
-    mj.budget_bytes = c->opt_search_profile_mib << 20;
-    std::copy(std::begin(c->search_multi_per_cu), std::end(c->search_multi_per_cu), mj.per_cu);
-    const swp::SearchMultiPlan plan = swp::plan_search_multi(mj);
-    for (const swp::MultiLaunch& l : plan.launch)
-        if (c->search_multi_per_cu[l.kernel] < 1) { set_err("the many-query search kernel does not fit a CU on this device"); return SW_EDEVICE; }
-    if (int rc = stage_search_call(c, stream, 0, plan.prof_need, plan.bnd_need, scoring->sub)) return rc;
-    if (int rc = grow_query_table(c, (size_t)nqueries, stream)) return rc;
-    for (int64_t t = 0; t < nqueries; ++t) {
-        c->h_mq[t] = plan.table[(size_t)t];
-        c->h_mq[t].qstart = qoffsets[plan.table[(size_t)t].row];
+    return run_search_multi(c, db, d_queries, qoffsets, nqueries, scoring, d_results, stream);
+}
+
+// The selection alone over a table the caller holds: the plan's chunks only bound the histograms here (no budget on the rows).
+int sw_top_hits_device(sw_ctx* c, const sw_result* d_results, int64_t nqueries, int64_t ntargets, int64_t top, int64_t min_score, sw_hit* d_hits,
+                       int64_t* d_nhits, void* stream_) {
+    if (!c || !d_results || nqueries < 0 || ntargets < 0) { set_err("sw_top_hits_device: NULL pointer or negative count"); return SW_EINVAL; }
+    hipStream_t stream = (hipStream_t)stream_;
+    swp::SearchTopPlan plan;
+    if (int rc = plan_top_call(c, "sw_top_hits_device", nqueries, ntargets, top, d_hits, d_nhits, INT64_MAX, plan)) return rc;
+    if (nqueries == 0) return SW_OK;
+    DevOrder order(c, stream, false);
+    if (order.rc) return order.rc;
+    if (int rc = grow_top_workspaces(c, plan, false, stream)) return rc;
+    for (const swp::TopChunk& ch : plan.chunk)
+        if (int rc = select_top(c, plan, d_results + ch.q0 * ntargets, ch.nq, ntargets, top, min_score, d_hits + ch.q0 * top, d_nhits + ch.q0, stream)) return rc;
+    c->last_search_top_chunks = (int64_t)plan.chunk.size(); c->last_search_top_kernel = plan.kernel;
+    return SW_OK;
+}
+
+// Search and selection with bounded result memory: chunk after chunk of queries through run_search_multi into the result workspace,
+// then that chunk's rows of d_hits.  The stream orders the chunks, which share the workspace.
+int sw_db_search_affine_top(sw_ctx* c, const sw_db* db, const char* d_queries, const int64_t* qoffsets, int64_t nqueries, const sw_affine* scoring,
+                            int64_t top, int64_t min_score, sw_hit* d_hits, int64_t* d_nhits, void* stream_) {
+    if (!c || !db || !d_queries || !qoffsets || !scoring) { set_err("sw_db_search_affine_top: NULL pointer"); return SW_EINVAL; }
+    if (db->device != c->device) { set_err("sw_db_search_affine_top: the handle was created on device %d, the context runs on device %d", db->device, c->device); return SW_EINVAL; }
+    int64_t maxq = 0;
+    if (int rc = swh::check_search_multi("sw_db_search_affine_top", qoffsets, nqueries, db->longest, scoring, &maxq)) return rc;
+    hipStream_t stream = (hipStream_t)stream_;
+    swp::SearchTopPlan plan;
+    if (int rc = plan_top_call(c, "sw_db_search_affine_top", nqueries, db->ntargets, top, d_hits, d_nhits, c->opt_search_results_mib << 20, plan)) return rc;
+    if (nqueries == 0) return SW_OK;
+    DevOrder order(c, stream, false);
+    if (order.rc) return order.rc;
+    if (int rc = grow_top_workspaces(c, plan, true, stream)) return rc;
+    for (const swp::TopChunk& ch : plan.chunk) {
+        if (db->ntargets > 0)
+            if (int rc = run_search_multi(c, db, d_queries, qoffsets + ch.q0, ch.nq, scoring, c->d_tres, stream)) return rc;
+        if (int rc = select_top(c, plan, c->d_tres, ch.nq, db->ntargets, top, min_score, d_hits + ch.q0 * top, d_nhits + ch.q0, stream)) return rc;
     }
-    memcpy(c->h_submat, scoring->sub, sizeof(sw_submat));
-    HIP_TRY(hipMemcpyAsync(c->d_mq, c->h_mq, (size_t)nqueries * sizeof(swk::MultiQuery), hipMemcpyHostToDevice, stream));
-    HIP_TRY(hipMemcpyAsync(c->d_submat, c->h_submat, sizeof(sw_submat), hipMemcpyHostToDevice, stream));
-    HIP_TRY(hipEventRecord(c->sitems_ev, stream));   // behind both uploads: whoever has waited for it may overwrite either pinned copy
-    size_t li = 0;
-    for (size_t g = 0; g < plan.group.size(); ++g) {
-        const swp::MultiGroup& grp = plan.group[g];
-        // every query's profile in shares of about 16 KiB, over at most 4096 workgroups
-        const int parts = (int)std::clamp<int64_t>(grp.prof_bytes / grp.nq / 16384, 1, 4096);
-        const unsigned blocks = (unsigned)std::min<int64_t>(grp.nq * parts, 4096);
-        hipLaunchKernelGGL(swk::sw_search_profile_submat_multi, dim3(blocks), dim3(256), 0, stream, (const unsigned char*)d_queries, c->d_mq + grp.q0, grp.nq,
-                           parts, c->d_sprof, (const signed char*)c->d_submat);
-        HIP_TRY(hipGetLastError());
-        for (; li < plan.launch.size() && plan.launch[li].group == (int)g; ++li) {
-            const swp::MultiLaunch& l = plan.launch[li];
-            swk::SearchMultiParams sp;
-            memset(&sp, 0, sizeof sp);
-            sp.db = (const unsigned char*)db->d_db;
-            sp.items = db->d_items; sp.rank0 = l.rank0;
-            sp.queries = c->d_mq + l.q0; sp.nq = (unsigned)l.nq; sp.nitems = l.items;
-            sp.prof = c->d_sprof; sp.ntargets = db->ntargets;
-            sp.ge = scoring->gap_extend; sp.goe = scoring->gap_open + scoring->gap_extend;
-            sp.bnd = l.bnd_per ? c->d_sbnd : nullptr; sp.bnd_per = l.bnd_per;
-            sp.counter = c->d_sctr;
-            sp.results = d_results;
-            HIP_TRY(hipMemsetAsync(c->d_sctr, 0, 4, stream));   // the work counter starts every launch at zero
-            hipLaunchKernelGGL(kSearchMulti[l.kernel].k, dim3((unsigned)l.grid), dim3(256), 0, stream, sp);
-            HIP_TRY(hipGetLastError());
-            c->last_search_multi_grid = l.grid;
-        }
-    }
-    c->last_search_multi_groups = (int64_t)plan.group.size(); c->last_search_multi_launches = (int64_t)plan.launch.size();
+    c->last_search_top_chunks = (int64_t)plan.chunk.size(); c->last_search_top_kernel = plan.kernel;
     return SW_OK;
 }
 

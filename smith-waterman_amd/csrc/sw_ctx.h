@@ -118,6 +118,14 @@ struct SW_HIDDEN sw_ctx {
     int64_t last_search_multi_groups = 0, last_search_multi_launches = 0, last_search_multi_grid = 0;   // of the last call; the grid of its last launch
     int search_multi_per_cu[swp::kSearchMultiKernels] = {};     // occupancy of every sw_search_affine_multi_wave instantiation at 256 threads ...
     bool search_multi_per_cu_known = false;                     // ... queried at the first call
+    // the best targets per query (sw_top_hits_device, sw_db_search_affine_top): the result rows of a chunk, the histograms and the
+    // per-row states of the radix select
+    sw_result* d_tres = nullptr; size_t tres_cap = 0;
+    unsigned int* d_thist = nullptr; size_t thist_cap = 0;
+    swk::TopState* d_tstate = nullptr; size_t tstate_cap = 0;
+    int64_t opt_search_results_mib = 1024;
+    int64_t last_search_top_chunks = 0, last_search_top_kernel = 0;
+    int top_hist_per_cu = 0;                                    // occupancy of sw_top_hist at 256 threads, queried at the first call
     // ---- placement of the output matrices (sw_place.hip)
     int64_t opt_place_hold_gib = 0;     // sw_alloc_outputs: GiB a pair of small matrices may hold beside itself where no plain candidate is good (0: none)
     int64_t opt_place_budget_ms = 1500; // sw_alloc_outputs: time the search for a P in another class of the HBM may take

@@ -449,6 +449,36 @@ int sw_search_affine_multi_host(const char* queries, const int64_t* qoffsets, in
     return SW_OK;
 }
 
+// The CPU leg of sw_db_search_affine_top: sw_search_affine_host query after query into one row, a sort of the qualifying targets by the
+// rank order (max_score descending, then target ascending), the first `top` of them and the {-1, 0, 0} tail.
+int sw_search_affine_multi_top_host(const char* queries, const int64_t* qoffsets, int64_t nqueries, const char* db, const int64_t* offsets, int64_t ntargets,
+                                    const sw_affine* scoring, int64_t top, int64_t min_score, sw_hit* hits, int64_t* nhits) {
+    if (!queries || !qoffsets || !db || !offsets || !scoring || ntargets < 0) {
+        swh::set_err("sw_search_affine_multi_top_host: NULL pointer or negative target count");
+        return SW_EINVAL;
+    }
+    int64_t maxlen = 0, nonempty = 0, maxq = 0;
+    if (int rc = swh::check_targets("sw_search_affine_multi_top_host", 1, offsets, ntargets, &maxlen, &nonempty)) return rc;
+    if (int rc = swh::check_search_multi("sw_search_affine_multi_top_host", qoffsets, nqueries, maxlen, scoring, &maxq)) return rc;
+    if (top < 1 || top > SW_TOP_MAX) { swh::set_err("sw_search_affine_multi_top_host: top = %lld is out of range 1..%d", (long long)top, SW_TOP_MAX); return SW_EINVAL; }
+    if (!hits || !nhits) { swh::set_err("sw_search_affine_multi_top_host: NULL hits or nhits"); return SW_EINVAL; }
+    std::vector<sw_result> row((size_t)ntargets);
+    std::vector<int64_t> order;
+    for (int64_t q = 0; q < nqueries; ++q) {
+        if (ntargets > 0)
+            if (int rc = sw_search_affine_host(queries + qoffsets[q], qoffsets[q + 1] - qoffsets[q], db, offsets, ntargets, scoring, row.data())) return rc;
+        order.clear();
+        for (int64_t k = 0; k < ntargets; ++k)
+            if (row[(size_t)k].max_score >= min_score) order.push_back(k);
+        std::stable_sort(order.begin(), order.end(), [&](int64_t x, int64_t y) { return row[(size_t)x].max_score > row[(size_t)y].max_score; });
+        const int64_t n = std::min<int64_t>(top, (int64_t)order.size());
+        for (int64_t i = 0; i < top; ++i)
+            hits[q * top + i] = i < n ? sw_hit{order[(size_t)i], row[(size_t)order[(size_t)i]].max_pos, row[(size_t)order[(size_t)i]].max_score} : sw_hit{-1, 0, 0};
+        nhits[q] = n;
+    }
+    return SW_OK;
+}
+
 // The CPU leg of sw_align_affine_device: the same recurrence with one direction byte per cell (bits 0-1: where H came from, 0 nothing
 // positive / 1 diagonal / 2 E / 3 F, compared in that order; bit 2: E[i][j] opened from H[i-1][j]; bit 3: F[i][j] opened from
 // H[i][j-1]; opening wins a tie), then the walk of the canonical alignment (include/swhip.h) from the arg-max.

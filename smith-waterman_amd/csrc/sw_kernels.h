@@ -158,6 +158,32 @@ __global__ void sw_search_profile_submat_multi(const unsigned char* q, const Mul
 template <int C>
 __global__ void sw_search_affine_multi_wave(SearchMultiParams p);
 
+// sw_search_top.hip: the best `top` targets of every row of a query-major result table (swp::plan_search_top has the geometry)
+struct TopState {                        // of one row, between the launches of a radix select
+    unsigned long long prefix;           // the digits found so far, highest first; after the last pass: the key of rank `top`
+    unsigned int want;                   // rank still looked for among the keys that carry the prefix
+    unsigned int all;                    // 1: fewer than `top` targets qualify, every one of them is a hit
+    unsigned int count;                  // compaction: keys written so far
+    unsigned int n;                      // hits of the row: min(top, qualifying targets), known after the first pass
+};
+struct TopParams {
+    const sw_result* results;            // query-major, nq rows of ntargets
+    int64_t ntargets;
+    unsigned int nq;
+    unsigned int wgs_row; int64_t slice; // workgroup w of a row reads the targets [w * slice, min(ntargets, (w + 1) * slice))
+    int tbits;                           // key = score << tbits | (2^tbits - 1 - target)
+    int shift, bits, first;              // this pass's digit; first: the pass with the highest bits (no prefix yet)
+    int64_t top, min_score;
+    unsigned int* hist;                  // per row 2^swp::kTopDigitBits bins, zero between the passes
+    TopState* state;                     // per row
+    sw_hit* hits; int64_t* nhits;        // nq x top, nq
+    int selected;                        // sw_top_sort: 1 = the row's keys lie compacted at the start of its hits (state has their number)
+};
+__global__ void sw_top_hist(TopParams p);
+__global__ void sw_top_scan(TopParams p);
+__global__ void sw_top_compact(TopParams p);
+__global__ void sw_top_sort(TopParams p);
+
 // sw_align_affine.hip: the alignment of chosen hits under affine scoring (direction fill + walk, one wave per hit)
 struct AlignAffineParams {
     const unsigned char* db;             // the targets back to back

@@ -449,6 +449,36 @@ SearchMultiPlan plan_search_multi(const SearchMultiJob& j) {
     return m;
 }
 
+// The best `top` of every row.  Every row has the same length, so the chunks are uniform and the geometry of a row is decided once.
+// The passes take kTopDigitBits bits each from the top of the key down; the last one takes what is left.
+SearchTopPlan plan_search_top(const SearchTopJob& j) {
+    SearchTopPlan t;
+    const int64_t nt = std::max<int64_t>(0, j.ntargets);
+    while (t.tbits < 62 && (1ll << t.tbits) < nt) ++t.tbits;
+    t.nbits = 24 + t.tbits;
+    t.kernel = nt > kTopMax ? 1 : 0;
+    const int64_t row_bytes = nt * 24;
+    int64_t per = nt > 0 ? j.budget_bytes / row_bytes : kTopChunkQueries;
+    per = std::clamp<int64_t>(per, 1, kTopChunkQueries);
+    for (int64_t q = 0; q < j.nqueries; q += per) t.chunk.push_back(TopChunk{q, std::min(per, j.nqueries - q)});
+    t.chunk_queries = std::min(per, std::max<int64_t>(0, j.nqueries));
+    t.results_need = (size_t)(t.chunk_queries * nt);
+    if (t.kernel == 0 || t.chunk_queries == 0) return t;
+    for (int hi = t.nbits; hi > 0 && t.npasses < kTopMaxPasses; ++t.npasses) {
+        const int bits = std::min(hi, kTopDigitBits);
+        t.pass[t.npasses] = TopPass{hi - bits, bits};
+        hi -= bits;
+    }
+    // enough workgroups to fill the device with the largest chunk, none with less than kTopMinSlice targets; slices in whole 256s
+    const int64_t want = ((int64_t)std::max(1, j.per_cu) * j.num_cus + t.chunk_queries - 1) / t.chunk_queries;
+    const int64_t wgs = std::clamp<int64_t>(want, 1, (nt + kTopMinSlice - 1) / kTopMinSlice);
+    t.slice = ((nt + wgs - 1) / wgs + 255) / 256 * 256;
+    t.wgs_row = (nt + t.slice - 1) / t.slice;
+    t.hist_need = (size_t)t.chunk_queries << kTopDigitBits;
+    t.state_need = (size_t)t.chunk_queries;
+    return t;
+}
+
 // The direction fill carries the search kernel's state plus the packed bytes of a row; the thresholds of the search hold for the same
 // reasons (plan_search_affine).  A slot is a whole direction matrix of the longest hit, so that any hit runs in any slot; the waves
 // take hits from a counter, longest first, and a call with more hits than slots simply keeps its waves busy longer.

@@ -222,6 +222,44 @@ struct SearchMultiPlan {
 
 SearchMultiPlan plan_search_multi(const SearchMultiJob& job);
 
+// ---- the best `top` targets of every row of a query-major result table (sw_top_hits_device, sw_db_search_affine_top; sw_search_top.hip).
+// Key: a target's key is score << tbits | (2^tbits - 1 - target) with tbits = ceil(log2 ntargets): unique per target, and plain integer
+// order of the keys is the rank order (score descending, target ascending).  nbits = 24 + tbits bits of a key can differ.
+// Kernels: rows of at most kTopMax targets are sorted whole by one workgroup (kernel 0).  Longer rows (kernel 1) are radix-selected:
+// `npasses` digit passes from the top bit down, pass p over the `bits` bits from `shift` on, find the key of rank `top`; every pass is a
+// histogram launch of wgs_row workgroups per row -- workgroup w of a row reads the targets [w * slice, min(ntargets, (w + 1) * slice)) --
+// and a one-workgroup-per-row scan; a compaction launch of the same shape gathers the keys at or above it, and kernel 0's sort orders them.
+// Chunks: consecutive queries whose rows (24 bytes per target) fit the budget, at most kTopChunkQueries of them (that bounds the
+// histograms), at least one -- a row larger than the budget is a chunk of its own.
+constexpr int64_t kTopMax = 4096;            // SW_TOP_MAX (include/swhip.h): the keys one workgroup sorts in LDS
+constexpr int kTopDigitBits = 11;            // widest digit of a pass: 2048 bins of 4 bytes in LDS and per row in the workspace
+constexpr int kTopMaxPasses = 5;             // ceil((24 + 31) / kTopDigitBits)
+constexpr int64_t kTopChunkQueries = 4096;
+constexpr int64_t kTopMinSlice = 4096;       // a workgroup of 256 threads takes at least 16 targets per thread
+
+struct SearchTopJob {
+    int64_t nqueries = 0, ntargets = 0, top = 1;
+    int64_t budget_bytes = 1ll << 30;        // "search_results_mib": the rows of a chunk may take this much
+    int num_cus = 256;
+    int per_cu = 8;                          // occupancy of the histogram kernel at 256 threads (workgroups per CU)
+};
+
+struct TopChunk { int64_t q0 = 0, nq = 0; };
+struct TopPass { int shift = 0, bits = 0; };
+struct SearchTopPlan {
+    int kernel = 0;                          // 0: every row is sorted whole, 1: radix select, then the sort of the selected keys
+    std::vector<TopChunk> chunk;             // in order, every query once
+    int64_t chunk_queries = 0;               // queries of the largest chunk
+    int tbits = 0, nbits = 24;               // bits of a key's target field; bits of a key that can differ
+    int npasses = 0;                         // kernel 1: digit passes, highest bits first
+    TopPass pass[kTopMaxPasses];
+    int64_t wgs_row = 1, slice = 0;          // kernel 1: workgroups per row and the targets each one reads
+    size_t results_need = 0;                 // workspaces: result rows of the largest chunk (sw_result elements) ...
+    size_t hist_need = 0, state_need = 0;    // ... kernel 1: histogram bins (uint32) and per-row states of the largest chunk
+};
+
+SearchTopPlan plan_search_top(const SearchTopJob& job);
+
 // ---- alignment of chosen hits under affine scoring (sw_align_affine_device): sw_align_affine_wave<C> for C = 4, 8, 16, its index in
 // kAlignAffine (sw_api_search.hip, which checks its order against it at compile time)
 constexpr int kAlignAffineKernels = 3;
