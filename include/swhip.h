@@ -278,8 +278,10 @@ int sw_align_affine_host(const char* query, int64_t qlen, const char* db, const 
  *   sw_db_create  d_db and offsets as for sw_search_device: device bytes back to back, a HOST array of ntargets + 1 non-decreasing
  *                 offsets (offsets[0] may be > 0, empty targets allowed), copied as far as needed.  The handle BORROWS d_db: the caller
  *                 keeps it alive and unchanged until sw_db_free.  The handle owns the schedule on the device (24 bytes per non-empty
- *                 target).  Synchronous.  ntargets == 0 gives a valid, empty handle.  SW_EINVAL: NULL pointers, ntargets < 0, the
- *                 offsets / length errors of sw_search_device.  Free the handle before the context's device is reset.
+ *                 target) and a copy of the ntargets + 1 offsets there (8 bytes per target; the schedule is ordered by length, and
+ *                 sw_db_align_affine_hits has to get from a target index to its bytes).  Synchronous.  ntargets == 0 gives a valid,
+ *                 empty handle.  SW_EINVAL: NULL pointers, ntargets < 0, the offsets / length errors of sw_search_device.  Free the
+ *                 handle before the context's device is reset.
  *   sw_db_info    every out pointer is optional: targets, non-empty targets, the longest target, offsets[ntargets] - offsets[0].
  *   sw_db_search_affine
  *     d_queries : device, the queries back to back: query q = d_queries[qoffsets[q] .. qoffsets[q+1]), no alignment asked
@@ -343,6 +345,42 @@ int  sw_db_search_affine_top(sw_ctx* ctx, const sw_db* db, const char* d_queries
 int  sw_search_affine_multi_top_host(const char* queries, const int64_t* qoffsets, int64_t nqueries, const char* db,
                                      const int64_t* offsets, int64_t ntargets, const sw_affine* scoring, int64_t top, int64_t min_score,
                                      sw_hit* hits, int64_t* nhits);
+
+/* The alignments of the top hits of many queries, from the device hit table as it is (csrc/sw_align_hits.hip): the step behind
+ * sw_db_search_affine_top, without a host round trip.  One call aligns every (query, hit) pair of the table; the work is sorted by
+ * size on the device and runs from device-side lists.
+ *   d_queries, qoffsets, scoring : as for sw_db_search_affine.
+ *   d_hits  : device, nqueries x top sw_hit -- typically the output of sw_db_search_affine_top or sw_top_hits_device, but any table is
+ *             accepted.  Only `target` is read: as in sw_align_affine_device a hit is re-filled in full and the kernel finds the
+ *             arg-max itself.  Duplicate targets are allowed.
+ *   d_nhits : device, nqueries int64, or NULL.  Row q uses its first clamp(d_nhits[q], 0, top) entries; with NULL all `top` of them.
+ *   d_aln   : device, nqueries x top sw_alignment.  Entry (q, r) of a used hit is bit for bit what sw_align_affine_device writes for
+ *             query q and hits = {target}.  Every other entry is all zeros: the entries beyond the row's count and those whose target
+ *             lies outside [0, ntargets).  An out-of-range target is never used as an index: it is compared, unsigned, against ntargets
+ *             before any load through it.  Every entry of d_aln is written.
+ *   d_ops   : device, the ops of entry (q, r) at d_ops + (q * top + r) * ops_cap under the ops_cap / nops rules of
+ *             sw_align_affine_device; the ops row of an all-zero entry is not touched.  May be NULL with ops_cap 0: coordinates only.
+ * Nothing is written outside d_aln and the used ops rows.  Asynchronous on `stream`; the host reads neither the hits nor the targets'
+ * offsets, its work is O(nqueries).  The order in which the device takes the pairs differs between runs, the bytes it writes do not.
+ * nqueries == 0 launches nothing; a handle with ntargets == 0 only zeroes d_aln.
+ * SW_EINVAL: the argument errors of sw_db_search_affine; top < 1 or top > SW_TOP_MAX; NULL d_hits or d_aln; a negative ops_cap, or NULL
+ * d_ops with ops_cap > 0; and a worst case that does not fit: the host cannot know which targets the table names, so the handle's
+ * longest target x the padded length of the longest query (a multiple of 256, 512 or 1024 for queries of at most 256, at most 512,
+ * longer) has to fit "align_workspace_mib" and the 2 GiB a slot may take -- decided before anything is launched, whatever the table
+ * says, with a message that names the option.  The workspaces are those of sw_align_affine_device and sw_db_search_affine
+ * ("align_workspace_mib", "search_profile_mib": queries run in consecutive groups whose profiles fit) plus 24 bytes per entry of a group,
+ * at most 96 MiB.  "last_align_hits_launches" (kernel launches), "last_align_hits_tiers" (the (class, size tier) lists planned, one
+ * alignment launch each) and "last_align_hits_slots" (direction matrices, summed over those launches) describe the last call, all 0 for
+ * a call that launched no alignment; "last_align_hits_lists" is how many of those lists received items, counted on the device:
+ * reading it waits for the device.
+ *   sw_align_affine_hits_host  the CPU leg: the same result in plain C++ from host tables (sw_align_affine_host per query), no GPU
+ *             needed, no workspace bound; every argument is checked before the first alignment. */
+int  sw_db_align_affine_hits(sw_ctx* ctx, const sw_db* db, const char* d_queries, const int64_t* qoffsets, int64_t nqueries,
+                             const sw_affine* scoring, const sw_hit* d_hits, const int64_t* d_nhits, int64_t top,
+                             sw_alignment* d_aln, char* d_ops, int64_t ops_cap, void* stream);
+int  sw_align_affine_hits_host(const char* queries, const int64_t* qoffsets, int64_t nqueries, const char* db,
+                               const int64_t* offsets, int64_t ntargets, const sw_affine* scoring, const sw_hit* hits,
+                               const int64_t* nhits, int64_t top, sw_alignment* aln, char* ops, int64_t ops_cap);
 
 /* Tables.  sw_submat_match: s[x][y] = x == y ? match : mismatch (matchMissmatchScore, serial_smithW.c:251-256; both must fit int8:
  * the builder returns nothing, so it clamps them to -128..127 -- a caller that takes them from a user checks the range first, as
@@ -523,7 +561,8 @@ int sw_synchronize(sw_ctx* ctx, void* stream);   /* waits for `stream`; reports 
  * default 256) bounds the profiles of a group of sw_db_search_affine, "last_search_multi_groups", "last_search_multi_launches" and
  * "last_search_multi_grid" (workgroups of its last launch) describe the last such call; "search_results_mib" (settable, default 1024,
  * 1..2^20) bounds the result rows a chunk of sw_db_search_affine_top holds, "last_search_top_chunks" and "last_search_top_kernel"
- * describe the last sw_db_search_affine_top / sw_top_hits_device call. */
+ * describe the last sw_db_search_affine_top / sw_top_hits_device call; "last_align_hits_launches", "last_align_hits_tiers",
+ * "last_align_hits_slots" and "last_align_hits_lists" the last sw_db_align_affine_hits call. */
 int sw_set_option(sw_ctx* ctx, const char* name, int64_t value);
 int64_t sw_get_option(sw_ctx* ctx, const char* name);
 

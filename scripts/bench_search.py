@@ -17,6 +17,11 @@
   clock, medians and ranges of --reps after --warmup: (1) sw_db_search_affine into the full table, synchronize, the table to the host,
   top_hits of every row; (2) sw_db_search_affine_top until the hits are on the host, at the default "search_results_mib" and at 64 (five
   chunks).  The hits are compared one by one; the device memory of the results is computed from the sizes, not measured
+  --align-hits: data set (a) only, 64 queries of --qlen, the alignments of their best 10 and best 100 targets onto the host by two paths in the
+  same process, wall clock, medians and ranges of --reps after --warmup, from the device hit table of sw_db_search_affine_top: (1) the
+  hits to the host, then one sw_align_affine_device call per query; (2) one sw_db_align_affine_hits call on the device table.  Both
+  write one output buffer and copy the coordinates and the ops up to the longest alignment to the host in two copies; the alignments are compared entry by entry; the search call's time in
+  the same process stands beside them
 GCUPS = query letters x target letters / time of the call (torch events, median of --reps after --warmup)."""
 import argparse
 import importlib
@@ -60,6 +65,7 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--only-a", action="store_true", help="data set (a) only: linear search, affine search, alignment of its top hits")
     ap.add_argument("--multi", action="store_true", help="data set (a) only: many queries through a prepared database against one call per query")
+    ap.add_argument("--align-hits", action="store_true", help="data set (a) only: the alignments of the top 10 / 100 hits of 64 queries, per query and in one call")
     ap.add_argument("--top", action="store_true", help="data set (a) only: the best 100 targets of 64 queries by the full table and by the selection on the device")
     args = ap.parse_args()
     rng = np.random.default_rng(2026)
@@ -217,6 +223,74 @@ def main():
         out["top_on_device_64mib_result_bytes_computed"] = min(nq, max(1, (64 << 20) // row)) * row + nq * (top * 24 + 8 + 8192 + 24)
         db.close()
 
+    def align_hits_leg(packed, offs, nq=64):
+        import time
+        d_db = torch.from_numpy(packed.copy()).to(dev)
+        db = eng.prepare_db(d_db, offs)
+        lens = np.diff(offs)
+        longest = int(lens.max())
+        qoffs = np.arange(nq + 1, dtype=np.int64) * args.qlen
+        d_q = torch.from_numpy(rng.choice(PROTEIN, int(qoffs[-1])).astype(np.uint8)).to(dev)
+        scoring = (sub, -11, -1)
+
+        def wall(fn):
+            for _ in range(args.warmup):
+                last = fn()
+            ms = []
+            for _ in range(args.reps):
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                last = fn()
+                ms.append((time.perf_counter() - t0) * 1e3)
+            return last, round(float(np.median(ms)), 3), [round(min(ms), 3), round(max(ms), 3)]
+
+        def to_host(aln, ops):
+            a = aln.cpu().numpy()
+            return a, ops[..., :max(1, int(a[..., 6].max()))].cpu().numpy()
+
+        out["align_hits_queries"], out["align_hits_qlen"] = nq, args.qlen
+        for top in (10, 100):
+            tag = f"align_hits_top{top}"
+            tbufs = (torch.zeros(nq * top * 3, dtype=torch.int64, device=dev), torch.zeros(nq, dtype=torch.int64, device=dev))
+
+            def search():
+                r = db.search_affine_top_device(d_q, qoffs, scoring, top, out=tbufs)
+                eng.synchronize()
+                return r
+            (d_hits, d_nhits), out[f"{tag}_search_ms"], out[f"{tag}_search_range_ms"] = wall(search)
+            cap = args.qlen + longest
+            # both paths write one (aln, ops) buffer of their own and copy it to the host the same way: two copies per run
+            one = (torch.zeros((nq * top, 7), dtype=torch.int64, device=dev), torch.zeros((nq * top, cap), dtype=torch.uint8, device=dev))
+            per = (torch.zeros((nq * top, 7), dtype=torch.int64, device=dev), torch.zeros((nq * top, cap), dtype=torch.uint8, device=dev))
+            views = [(per[0][k * top:(k + 1) * top], per[1][k * top:(k + 1) * top]) for k in range(nq)]
+
+            def per_query():
+                hits = d_hits.cpu().numpy()                                  # (the device table to the host: path (1) needs the indices there)
+                for k in range(nq):
+                    eng.align_affine_device(d_q[int(qoffs[k]):], args.qlen, d_db, offs, sub, -11, -1, hits[k, :, 0], ops_cap=cap, out=views[k])
+                eng.synchronize()
+                return to_host(per[0].view(nq, top, 7), per[1].view(nq, top, cap))
+
+            def one_call():
+                aln, ops = db.align_affine_hits_device(d_q, qoffs, scoring, d_hits, d_nhits, ops_cap=cap, out=one)
+                eng.synchronize()
+                return to_host(aln, ops)
+
+            want, out[f"{tag}_per_query_ms"], out[f"{tag}_per_query_range_ms"] = wall(per_query)
+            (aln, ops), out[f"{tag}_one_call_ms"], out[f"{tag}_one_call_range_ms"] = wall(one_call)
+            out[f"{tag}_launches"], out[f"{tag}_tiers"] = eng.get_option("last_align_hits_launches"), eng.get_option("last_align_hits_tiers")
+            out[f"{tag}_slots"], out[f"{tag}_lists_filled"] = eng.get_option("last_align_hits_slots"), eng.get_option("last_align_hits_lists")
+            wa, wo = want
+            same = bool((d_nhits.cpu().numpy() == top).all()) and np.array_equal(wa, aln)
+            same = same and all(wo[k, r, :wa[k, r, 6]].tobytes() == ops[k, r, :wa[k, r, 6]].tobytes() for k in range(nq) for r in range(top))
+            out[f"{tag}_identical"] = same
+            out[f"{tag}_ops_mean"] = round(float(aln[..., 6].mean()), 1)
+            out[f"{tag}_hit_len_mean"] = round(float(lens[d_hits.cpu().numpy()[..., 0]].mean()), 1)
+            out[f"{tag}_ranges_overlap"] = bool(out[f"{tag}_one_call_range_ms"][1] >= out[f"{tag}_per_query_range_ms"][0])
+            out[f"{tag}_per_query_over_one_call"] = round(out[f"{tag}_per_query_ms"] / out[f"{tag}_one_call_ms"], 2)
+            out[f"{tag}_one_call_over_search"] = round(out[f"{tag}_one_call_ms"] / out[f"{tag}_search_ms"], 4)
+        db.close()
+
     # (a) protein database, log-normal lengths
     q = rng.choice(PROTEIN, args.qlen).astype(np.uint8)
     lens = np.clip(np.round(rng.lognormal(np.log(300), 0.6, args.targets)), 1, 35_000).astype(np.int64)
@@ -226,9 +300,11 @@ def main():
     out["a_letters"] = int(offs[-1])
     out["a_len_median"] = int(np.median(lens))
     out["a_len_max"] = int(lens.max())
-    if args.multi or args.top:
+    if args.multi or args.top or args.align_hits:
         if args.multi:
             multi_legs(packed, offs)
+        if args.align_hits:
+            align_hits_leg(packed, offs)
         if args.top:
             top_leg(packed, offs)
         eng.close()

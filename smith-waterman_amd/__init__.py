@@ -72,6 +72,8 @@ ABI = {
     "sw_top_hits_device": (_i32, [_vp, _vp, _i64, _i64, _i64, _i64, _vp, _vp, _vp]),
     "sw_db_search_affine_top": (_i32, [_vp, _vp, _vp, _vp, _i64, ctypes.POINTER(_Affine), _i64, _i64, _vp, _vp, _vp]),
     "sw_search_affine_multi_top_host": (_i32, [_vp, _vp, _i64, _vp, _vp, _i64, ctypes.POINTER(_Affine), _i64, _i64, _vp, _vp]),
+    "sw_db_align_affine_hits": (_i32, [_vp, _vp, _vp, _vp, _i64, ctypes.POINTER(_Affine), _vp, _vp, _i64, _vp, _vp, _i64, _vp]),
+    "sw_align_affine_hits_host": (_i32, [_vp, _vp, _i64, _vp, _vp, _i64, ctypes.POINTER(_Affine), _vp, _vp, _i64, _vp, _vp, _i64]),
     "sw_align_affine_device": (_i32, [_vp, _vp, _i64, _vp, _vp, _i64, _vp, _i64, ctypes.POINTER(_Affine), _vp, _vp, _i64, _vp]),
     "sw_align_affine_host": (_i32, [_vp, _i64, _vp, _vp, _i64, _vp, _i64, ctypes.POINTER(_Affine), _vp, _vp, _i64]),
     "sw_submat_match": (None, [_i32, _i32, _vp]),
@@ -300,6 +302,46 @@ def align_affine_host(query, targets, submat, gap_open: int, gap_extend: int, hi
     return aln, _ops_list(aln, ops, cap)
 
 
+def _hit_table(hits, nhits, nq: int):
+    """A host hit table as the C-ABI takes it: (nq, top, 3) int64 of (target, max_pos, max_score) -- or (nq, top) target indices, which
+    are widened -- and the counts (or None)."""
+    hits = np.asarray(hits, np.int64)
+    if hits.ndim == 2:
+        hits = np.stack([hits, np.zeros_like(hits), np.zeros_like(hits)], axis=-1)
+    if hits.ndim != 3 or hits.shape[0] != nq or hits.shape[2] != 3:
+        raise ValueError(f"hits must be ({nq}, top, 3) or ({nq}, top) int64")
+    if nhits is not None:
+        nhits = np.ascontiguousarray(nhits, np.int64).reshape(-1)
+        if len(nhits) != nq:
+            raise ValueError(f"nhits must hold {nq} counts")
+    return np.ascontiguousarray(hits), nhits
+
+
+def align_affine_hits_host(queries, targets, scoring, hits, nhits=None):
+    """sw_align_affine_hits_host: the alignments of a hit table in plain C++ on the host (no GPU).  Arguments and results as
+    Database.align_affine_hits."""
+    qpacked, qoffs = _pack_targets(queries)
+    packed, offs = _pack_targets(targets)
+    nq = len(qoffs) - 1
+    hits, nhits = _hit_table(hits, nhits, nq)
+    top = hits.shape[1]
+    qs = qpacked if len(qpacked) else np.zeros(1, np.uint8)
+    db = packed if len(packed) else np.zeros(1, np.uint8)
+    cap = max(1, int(np.diff(qoffs).max(initial=0)) + int(np.diff(offs).max(initial=0)))
+    aln = np.zeros((max(1, nq * top), 7), np.int64)
+    ops = np.zeros((max(1, nq * top), cap), np.uint8)
+    sub, sc = _affine(*scoring)
+    _check(lib().sw_align_affine_hits_host(qs.ctypes.data, qoffs.ctypes.data, nq, db.ctypes.data, offs.ctypes.data, len(offs) - 1, ctypes.byref(sc),
+                                           hits.ctypes.data, nhits.ctypes.data if nhits is not None else None, top, aln.ctypes.data, ops.ctypes.data, cap))
+    aln = aln[:nq * top]
+    return aln.reshape(nq, top, 7), _ops_rows(aln, ops, cap, nq, top)
+
+
+def _ops_rows(aln, ops, cap, nq: int, top: int):
+    flat = _ops_list(aln.reshape(-1, 7), ops, cap)
+    return [flat[q * top:(q + 1) * top] for q in range(nq)]
+
+
 def format_alignment(query, target, aln_row, ops):
     """The three display lines of an alignment (an sw_alignment row and its ops): the query with '-' where the target has letters
     of its own, a midline ('|' under equal letters, a space otherwise), the target with '-'."""
@@ -504,6 +546,64 @@ class Database:
         _check(lib().sw_db_search_affine_top(eng._h, self._h, d_queries.data_ptr(), qoffs.ctypes.data, nq, ctypes.byref(sc), int(top), int(min_score),
                                              hits.data_ptr(), nhits.data_ptr(), eng._stream()))
         return eng._top_views(hits, nhits, nq, top)
+
+
+    def align_affine_hits(self, queries, scoring, hits, nhits=None):
+        """The alignments of a hit table (sw_db_align_affine_hits): queries and scoring as for search_affine; hits a (nqueries, top, 3)
+        int64 array of (target, max_pos, max_score) as search_affine_top returns it -- or (nqueries, top) target indices --, nhits the
+        (nqueries,) counts or None for whole rows.  Returns (aln, ops): aln the (nqueries, top, 7) int64 numpy array of (max_pos,
+        max_score, q_begin, t_begin, q_end, t_end, nops), all zeros for unused entries and targets outside the database; ops a list per
+        query of `top` bytes objects over b"MID"."""
+        eng = self.engine
+        t = eng.torch
+        dev = f"cuda:{eng.device}"
+        qpacked, qoffs = _pack_targets(queries)
+        nq = len(qoffs) - 1
+        hits, nhits = _hit_table(hits, nhits, nq)
+        top = hits.shape[1]
+        d_q = t.from_numpy(qpacked.copy() if len(qpacked) else np.zeros(1, np.uint8)).to(dev)
+        d_hits = t.from_numpy(hits.reshape(-1).copy() if hits.size else np.zeros(3, np.int64)).to(dev)
+        d_nhits = t.from_numpy(nhits.copy()).to(dev) if nhits is not None and len(nhits) else None
+        cap = max(1, int(np.diff(qoffs).max(initial=0)) + self.info()["longest"])
+        aln, ops = self.align_affine_hits_device(d_q, qoffs, scoring, d_hits.view(nq, top, 3) if hits.size else d_hits, d_nhits, ops_cap=cap, top=top)
+        eng.synchronize()
+        aln = aln.cpu().numpy()
+        return aln, _ops_rows(aln, ops.cpu().numpy().reshape(-1, cap), cap, nq, top)
+
+    def align_affine_hits_device(self, d_queries, qoffsets, scoring, hits, nhits, ops_cap: int = 0, out=None, top=None):
+        """sw_db_align_affine_hits on device-resident queries and a device hit table -- the (nqueries, top, 3) int64 tensor and the
+        (nqueries,) counts that search_affine_top_device or Engine.top_hits_device return (nhits may be None: whole rows; `top` is needed
+        only where the table's shape does not tell it); asynchronous on torch's current stream, nothing comes to the host.  Returns
+        (aln, ops): the (nqueries, top, 7) int64 tensor and the (nqueries, top, ops_cap) uint8 tensor (None with ops_cap = 0:
+        coordinates only); out = (aln, ops) reuses given tensors."""
+        eng = self.engine
+        t = eng.torch
+        qoffs = np.ascontiguousarray(qoffsets, np.int64).reshape(-1)
+        if len(qoffs) == 0:
+            qoffs = np.zeros(1, np.int64)
+        nq = len(qoffs) - 1
+        if top is None:
+            if hits.dim() != 3:
+                raise ValueError("hits must be (nqueries, top, 3), or `top` given")
+            top = hits.shape[1]
+        top = int(top)
+        if hits.dtype != t.int64 or not hits.is_contiguous() or hits.numel() < nq * max(0, top) * 3:
+            raise ValueError(f"hits must be a contiguous int64 tensor of at least {nq} x {top} x 3 elements")
+        if nhits is not None and (nhits.dtype != t.int64 or not nhits.is_contiguous() or nhits.numel() < nq):
+            raise ValueError(f"nhits must be a contiguous int64 tensor of at least {nq} elements")
+        n, dev = nq * max(0, top), f"cuda:{eng.device}"
+        aln, ops = out if out is not None else (t.zeros((max(1, n), 7), dtype=t.int64, device=dev),
+                                                t.zeros((max(1, n), ops_cap), dtype=t.uint8, device=dev) if ops_cap > 0 else None)
+        if aln.dtype != t.int64 or not aln.is_contiguous() or aln.numel() < n * 7:
+            raise ValueError(f"out: aln must be a contiguous int64 tensor of at least {n * 7} elements")
+        if ops is not None and (ops.dtype != t.uint8 or not ops.is_contiguous() or ops.numel() < n * ops_cap):
+            raise ValueError(f"out: ops must be a contiguous uint8 tensor of at least {n * ops_cap} elements")
+        sub, sc = _affine(*scoring)
+        _check(lib().sw_db_align_affine_hits(eng._h, self._h, d_queries.data_ptr(), qoffs.ctypes.data, nq, ctypes.byref(sc), hits.data_ptr(),
+                                             nhits.data_ptr() if nhits is not None else None, top, aln.data_ptr(),
+                                             ops.data_ptr() if ops is not None else None, ops_cap, eng._stream()))
+        return (aln.view(-1)[:n * 7].view(nq, max(0, top), 7),
+                ops.view(-1)[:n * ops_cap].view(nq, max(0, top), ops_cap) if ops is not None else None)
 
 
 class Engine:

@@ -9,7 +9,7 @@
 //                              without --gap-extend E = the gap of --scores; --gap-extend alone (O = 0) is the linear search with gap E
 //     ... --all-queries       EVERY record of Q.fa through one prepared database handle and one call (sw_db_create / sw_db_search_affine): the
 //                              hit block of --search once per query, each under a line "## query record <i> of <Q.fa>"; --top, --matrix,
-//                              --gap-open, --gap-extend and --align (sw_align_affine_device per query) as for one query.  The K best hits per
+//                              --gap-open, --gap-extend and --align (one sw_db_align_affine_hits call on the device hit table) as for one query.  The K best hits per
 //                              query are selected on the device (sw_db_search_affine_top): only they are copied back
 //     ... --min-score S       with --all-queries: only hits with a score of at least S are printed (fewer than K where fewer qualify)
 //     ... --align             every printed hit is followed by its alignment (sw_align_affine_device; the canonical alignment of swhip.h), four lines:
@@ -114,17 +114,23 @@ static std::vector<sw_hit> rank_hits(const sw_result* res, int64_t nrec, long lo
     return hits;
 }
 
-// The hit block of one query: the header line, its K hits in rank order and, with `align`, every hit's alignment (the K hits re-filled
-// with directions and walked on the device).
+// The hit block of one query: the header line, its K hits in rank order and, with `align`, every hit's alignment: the K hits re-filled
+// with directions and walked on the device here, or -- `done` given -- taken from the row of a call that aligned every query's hits
+// (done_ops: that row's ops, done_cap bytes per hit).
 static int print_hits(sw_ctx* ctx, const char* q, int64_t qlen, const void* d_q, const std::vector<char>& db, const void* d_db, const std::vector<int64_t>& offs,
-                      int64_t nrec, int64_t total, const sw_hit* hits, long long K, bool align, const sw_affine& aff) {
+                      int64_t nrec, int64_t total, const sw_hit* hits, long long K, bool align, const sw_affine& aff, const sw_alignment* done = nullptr,
+                      const char* done_ops = nullptr, int64_t done_cap = 0) {
     std::vector<int64_t> order((size_t)K);
     for (long long i = 0; i < K; ++i) order[(size_t)i] = hits[i].target;
     // --align: the K hits re-filled with directions and walked on the device, ops of at most query + longest hit letters each
     std::vector<sw_alignment> aln((size_t)(align ? K : 0));
     std::vector<char> ops;
     int64_t ops_cap = 0;
-    if (align && K > 0) {
+    if (align && K > 0 && done) {
+        std::copy(done, done + K, aln.begin());
+        ops.assign(done_ops, done_ops + (size_t)K * (size_t)done_cap);
+        ops_cap = done_cap;
+    } else if (align && K > 0) {
         for (long long i = 0; i < K; ++i) ops_cap = std::max(ops_cap, qlen + offs[(size_t)order[(size_t)i] + 1] - offs[(size_t)order[(size_t)i]]);
         void *d_aln = nullptr, *d_ops = nullptr;
         CHECK(sw_device_malloc(ctx, (size_t)K * sizeof(sw_alignment), &d_aln));
@@ -247,13 +253,43 @@ static int search_all_main(const char* qpath, const char* dbpath, long long top,
     }
     std::vector<sw_result> res(nres);
     if (!on_device && nq > 0) CHECK(sw_memcpy_d2h(ctx, res.data(), d_res, (size_t)(nq * nrec) * sizeof(sw_result)));
+    // --align: the hits of every query in ONE call on the device table as the selection left it (sw_db_align_affine_hits), ops of at most
+    // longest query + longest target letters each; a table of ops beyond 1 GiB, or one the call refuses, goes query by query instead (print_hits)
+    std::vector<sw_alignment> aln;
+    std::vector<char> ops;
+    int64_t ops_cap = 0;
+    if (align && on_device && K > 0 && nq > 0) {
+        int64_t maxq = 0, longest = 0;
+        for (int64_t i = 0; i < nq; ++i) maxq = std::max(maxq, qoffs[(size_t)i + 1] - qoffs[(size_t)i]);
+        CHECK(sw_db_info(handle, nullptr, nullptr, &longest, nullptr));
+        ops_cap = maxq + longest;
+        const size_t n = (size_t)(nq * K);
+        if ((double)n * (double)ops_cap <= (double)(1ll << 30)) {
+            void *d_aln = nullptr, *d_ops = nullptr;
+            CHECK(sw_device_malloc(ctx, n * sizeof(sw_alignment), &d_aln));
+            CHECK(sw_device_malloc(ctx, n * (size_t)ops_cap, &d_ops));
+            // the call refuses by the worst pair the table COULD name (longest target x longest query against "align_workspace_mib");
+            // the hits of such a table may still fit one by one: those go query by query, as they always did (print_hits reports what is left)
+            const int rc = sw_db_align_affine_hits(ctx, handle, (const char*)d_q, qoffs.data(), nq, &aff, (const sw_hit*)d_hits, (const int64_t*)d_nhits, K,
+                                                   (sw_alignment*)d_aln, (char*)d_ops, ops_cap, nullptr);
+            if (rc != SW_OK && rc != SW_EINVAL) CHECK(rc);
+            if (rc == SW_OK) {
+                CHECK(sw_synchronize(ctx, nullptr));
+                aln.resize(n); ops.resize(n * (size_t)ops_cap);
+                CHECK(sw_memcpy_d2h(ctx, aln.data(), d_aln, n * sizeof(sw_alignment)));
+                CHECK(sw_memcpy_d2h(ctx, ops.data(), d_ops, ops.size()));
+            }
+            (void)sw_device_free(ctx, d_aln); (void)sw_device_free(ctx, d_ops);
+        }
+    }
     for (int64_t i = 0; i < nq; ++i) {
         printf("## query record %lld of %s\n", (long long)i, qpath);
         const std::vector<sw_hit> ranked = on_device ? std::vector<sw_hit>() : rank_hits(res.data() + i * nrec, nrec, K, min_score);
         const sw_hit* row = on_device ? hits.data() + i * K : ranked.data();
         const long long n = on_device ? (long long)nhits[(size_t)i] : (long long)ranked.size();
         if (int rc = print_hits(ctx, qs.data() + qoffs[(size_t)i], qoffs[(size_t)i + 1] - qoffs[(size_t)i], (const char*)d_q + qoffs[(size_t)i], db, d_db, offs, nrec,
-                                total, row, n, align, aff)) return rc;
+                                total, row, n, align, aff, aln.empty() ? nullptr : aln.data() + i * K, aln.empty() ? nullptr : ops.data() + (size_t)(i * K) * (size_t)ops_cap,
+                                ops_cap)) return rc;
     }
     const double cells = (double)qtotal * (double)total;
     printf("\nElapsed time for database search: %f (%.1f GCUPS; %lld queries in one call, handle prepared in %f)\n\n", t2 - t1,

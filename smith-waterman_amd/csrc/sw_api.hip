@@ -64,6 +64,9 @@ void sw_destroy(sw_ctx* c) {
     if (c->d_submat) (void)hipFree(c->d_submat);
     if (c->h_submat) (void)hipHostFree(c->h_submat);
     if (c->d_adir) (void)hipFree(c->d_adir);
+    if (c->d_ahitems) (void)hipFree(c->d_ahitems);
+    if (c->d_ahctl) (void)hipFree(c->d_ahctl);
+    if (c->d_ahfilled) (void)hipFree(c->d_ahfilled);
     if (c->d_mq) (void)hipFree(c->d_mq);
     if (c->h_mq) (void)hipHostFree(c->h_mq);
     if (c->d_tres) (void)hipFree(c->d_tres);
@@ -158,6 +161,16 @@ int64_t sw_get_option(sw_ctx* c, const char* name) {
     if (!strcmp(name, "last_search_affine_kernel")) return c->last_search_affine_kernel;
     if (!strcmp(name, "last_align_affine_kernel")) return c->last_align_affine_kernel;
     if (!strcmp(name, "last_align_affine_slots")) return c->last_align_affine_slots;
+    if (!strcmp(name, "last_align_hits_launches")) return c->last_align_hits_launches;
+    if (!strcmp(name, "last_align_hits_tiers")) return c->last_align_hits_tiers;
+    if (!strcmp(name, "last_align_hits_slots")) return c->last_align_hits_slots;
+    if (!strcmp(name, "last_align_hits_lists")) {   // counted on the device: waits for it, then reads the one word back
+        unsigned int n = 0;
+        if (!c->d_ahfilled || c->last_align_hits_tiers == 0) return 0;
+        if (hipSetDevice(c->device) != hipSuccess || hipDeviceSynchronize() != hipSuccess ||
+            hipMemcpy(&n, c->d_ahfilled, sizeof n, hipMemcpyDeviceToHost) != hipSuccess) return -1;
+        return n;
+    }
     if (!strcmp(name, "align_workspace_mib")) return c->opt_align_workspace_mib;
     if (!strcmp(name, "search_profile_mib")) return c->opt_search_profile_mib;
     if (!strcmp(name, "last_search_multi_groups")) return c->last_search_multi_groups;

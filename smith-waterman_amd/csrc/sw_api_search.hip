@@ -42,6 +42,15 @@ static constexpr Indexed<SearchMultiKernel> kSearchMulti[] = {
 };
 static_assert(std::size(kSearchMulti) == swp::kSearchMultiKernels && at_their_indices(kSearchMulti));
 
+// the instantiations of the hit-table alignment kernel (sw_align_hits.hip), picked by swp::plan_align_hits
+using AlignHitsKernel = void (*)(swk::AlignHitsParams);
+static constexpr Indexed<AlignHitsKernel> kAlignHits[] = {
+    {swp::align_hits_kernel_index(4), swk::sw_align_hits_wave<4>},
+    {swp::align_hits_kernel_index(8), swk::sw_align_hits_wave<8>},
+    {swp::align_hits_kernel_index(16), swk::sw_align_hits_wave<16>},
+};
+static_assert(std::size(kAlignHits) == swp::kAlignHitsKernels && at_their_indices(kAlignHits));
+
 // occupancy of every instantiation of a table at 256 threads, asked once per context: the plans' columns per lane and grids depend on it
 template <typename K, size_t N>
 static int occupancy_once(const Indexed<K> (&tab)[N], int (&per_cu)[N], bool& known) {
@@ -371,6 +380,17 @@ int sw_db_create(sw_ctx* c, const char* d_db, const int64_t* offsets, int64_t nt
     sw_db* db = new sw_db;
     db->device = c->device; db->d_db = d_db;
     db->ntargets = ntargets; db->nonempty = nonempty; db->longest = maxlen; db->letters = offsets[ntargets] - offsets[0];
+    {   // the offsets, for the calls that get from a target index to its bytes on the device (8 bytes per target)
+        const size_t bytes = (size_t)(ntargets + 1) * sizeof(int64_t);
+        hipError_t e = hipMalloc((void**)&db->d_offsets, bytes);
+        if (e == hipSuccess) e = hipMemcpy(db->d_offsets, offsets, bytes, hipMemcpyHostToDevice);
+        if (e != hipSuccess) {
+            set_err("sw_db_create: the offsets of %lld targets could not be placed on the device: %s", (long long)ntargets, hipGetErrorString(e));
+            if (db->d_offsets) (void)hipFree(db->d_offsets);
+            delete db;
+            return e == hipErrorOutOfMemory ? SW_ENOMEM : SW_EDEVICE;
+        }
+    }
     if (nonempty > 0) {
         swk::SearchItem* h_items = nullptr;
         const size_t bytes = (size_t)nonempty * sizeof(swk::SearchItem);
@@ -384,6 +404,7 @@ int sw_db_create(sw_ctx* c, const char* d_db, const int64_t* offsets, int64_t nt
         if (e != hipSuccess) {
             set_err("sw_db_create: the schedule of %lld targets could not be placed on the device: %s", (long long)nonempty, hipGetErrorString(e));
             if (db->d_items) (void)hipFree(db->d_items);
+            (void)hipFree(db->d_offsets);
             delete db;
             return e == hipErrorOutOfMemory ? SW_ENOMEM : SW_EDEVICE;
         }
@@ -394,7 +415,9 @@ int sw_db_create(sw_ctx* c, const char* d_db, const int64_t* offsets, int64_t nt
 
 void sw_db_free(sw_db* db) {
     if (!db) return;
-    if (db->d_items) { (void)hipSetDevice(db->device); (void)hipFree(db->d_items); }
+    (void)hipSetDevice(db->device);
+    if (db->d_items) (void)hipFree(db->d_items);
+    if (db->d_offsets) (void)hipFree(db->d_offsets);
     delete db;
 }
 
@@ -462,6 +485,106 @@ int sw_db_search_affine_top(sw_ctx* c, const sw_db* db, const char* d_queries, c
         if (int rc = select_top(c, plan, c->d_tres, ch.nq, db->ntargets, top, min_score, d_hits + ch.q0 * top, d_nhits + ch.q0, stream)) return rc;
     }
     c->last_search_top_chunks = (int64_t)plan.chunk.size(); c->last_search_top_kernel = plan.kernel;
+    return SW_OK;
+}
+
+// The alignments of a device hit table (csrc/sw_align_hits.hip).  Per call the host checks and plans the QUERIES (O(nqueries)) against
+// the handle's longest target; the table, the counts and the targets' offsets are read on the device only.  Per group: one profile
+// launch, two binning launches, one alignment launch per (class, tier) whose grid the plan fixed for the longest list it could get.
+int sw_db_align_affine_hits(sw_ctx* c, const sw_db* db, const char* d_queries, const int64_t* qoffsets, int64_t nqueries, const sw_affine* scoring,
+                            const sw_hit* d_hits, const int64_t* d_nhits, int64_t top, sw_alignment* d_aln, char* d_ops, int64_t ops_cap, void* stream_) {
+    if (!c || !db || !d_queries || !qoffsets || !scoring) { set_err("sw_db_align_affine_hits: NULL pointer"); return SW_EINVAL; }
+    if (db->device != c->device) { set_err("sw_db_align_affine_hits: the handle was created on device %d, the context runs on device %d", db->device, c->device); return SW_EINVAL; }
+    int64_t maxq = 0;
+    if (int rc = swh::check_search_multi("sw_db_align_affine_hits", qoffsets, nqueries, db->longest, scoring, &maxq)) return rc;
+    if (int rc = swh::check_align_hits("sw_db_align_affine_hits", top, d_hits, d_aln, d_ops, ops_cap)) return rc;
+    c->last_align_hits_launches = c->last_align_hits_tiers = c->last_align_hits_slots = 0;   // (a call that launches no alignment reports none)
+    if (nqueries == 0) return SW_OK;
+    hipStream_t stream = (hipStream_t)stream_;
+    HIP_TRY(hipSetDevice(c->device));
+    if (int rc = occupancy_once(kAlignHits, c->align_hits_per_cu, c->align_hits_per_cu_known)) return rc;
+    std::vector<int64_t> qlens((size_t)nqueries);
+    for (int64_t q = 0; q < nqueries; ++q) qlens[(size_t)q] = qoffsets[q + 1] - qoffsets[q];
+    swp::AlignHitsJob aj;
+    aj.qlens = qlens.data(); aj.nqueries = nqueries; aj.top = top; aj.longest = db->longest; aj.num_cus = c->num_cus;
+    aj.profile_budget_bytes = c->opt_search_profile_mib << 20; aj.budget_bytes = c->opt_align_workspace_mib << 20;
+    std::copy(std::begin(c->align_hits_per_cu), std::end(c->align_hits_per_cu), aj.per_cu);
+    const swp::AlignHitsPlan plan = swp::plan_align_hits(aj);
+    if (!plan.fits) {   // decided from host data alone, whatever the table names
+        set_err("sw_db_align_affine_hits: the direction matrix of the handle's longest target against the longest query (%lld rows x %lld bytes = %lld bytes) "
+                "does not fit align_workspace_mib = %lld (or the 2 GiB a slot may take)", (long long)std::max<int64_t>(1, db->longest), (long long)plan.worst_qpad,
+                (long long)plan.worst_bytes, (long long)c->opt_align_workspace_mib);
+        return SW_EINVAL;
+    }
+    DevOrder order(c, stream, false);
+    if (order.rc) return order.rc;
+    if (db->ntargets == 0) {   // no index is inside an empty database: every entry is the zero alignment
+        HIP_TRY(hipMemsetAsync(d_aln, 0, (size_t)nqueries * (size_t)top * sizeof(sw_alignment), stream));
+        return SW_OK;
+    }
+    for (const swp::AlignHitsLaunch& l : plan.launch)
+        if (c->align_hits_per_cu[l.kernel] < 1) { set_err("the hit-table alignment kernel does not fit a CU on this device"); return SW_EDEVICE; }
+    if (int rc = stage_search_call(c, stream, 0, plan.prof_need, plan.bnd_need, scoring->sub)) return rc;
+    if (int rc = grow_query_table(c, (size_t)nqueries, stream)) return rc;
+    bool fresh = false;
+    if (int rc = grow_workspace((void**)&c->d_adir, c->adir_cap, plan.dir_need, 1, 0, stream, fresh)) return rc;
+    if (int rc = grow_workspace((void**)&c->d_ahitems, c->ahitems_cap, plan.items_need, sizeof(swk::AlignHitItem), 0, stream, fresh)) return rc;
+    if (!c->d_ahctl) HIP_TRY(hipMalloc((void**)&c->d_ahctl, sizeof(swk::AlignHitsCtl)));
+    if (!c->d_ahfilled) HIP_TRY(hipMalloc((void**)&c->d_ahfilled, 64));
+    HIP_TRY(hipMemsetAsync(c->d_ahfilled, 0, 4, stream));
+    for (int64_t t = 0; t < nqueries; ++t) {
+        c->h_mq[t] = plan.table[(size_t)t];
+        c->h_mq[t].qstart = qoffsets[plan.table[(size_t)t].row];
+    }
+    memcpy(c->h_submat, scoring->sub, sizeof(sw_submat));
+    HIP_TRY(hipMemcpyAsync(c->d_mq, c->h_mq, (size_t)nqueries * sizeof(swk::MultiQuery), hipMemcpyHostToDevice, stream));
+    HIP_TRY(hipMemcpyAsync(c->d_submat, c->h_submat, sizeof(sw_submat), hipMemcpyHostToDevice, stream));
+    HIP_TRY(hipEventRecord(c->sitems_ev, stream));   // behind both uploads: whoever has waited for it may overwrite either pinned copy
+    size_t li = 0;
+    for (size_t g = 0; g < plan.group.size(); ++g) {
+        const swp::AlignHitsGroup& grp = plan.group[g];
+        const int parts = (int)std::clamp<int64_t>(grp.prof_bytes / grp.nq / 16384, 1, 4096);
+        const unsigned blocks = (unsigned)std::min<int64_t>(grp.nq * parts, 4096);
+        hipLaunchKernelGGL(swk::sw_search_profile_submat_multi, dim3(blocks), dim3(256), 0, stream, (const unsigned char*)d_queries, c->d_mq + grp.q0, grp.nq,
+                           parts, c->d_sprof, (const signed char*)c->d_submat);
+        HIP_TRY(hipGetLastError());
+        // the lists of the group: counts, cursors and work counters start at zero
+        HIP_TRY(hipMemsetAsync(c->d_ahctl, 0, sizeof(swk::AlignHitsCtl), stream));
+        swk::AlignHitsBinParams bp;
+        memset(&bp, 0, sizeof bp);
+        bp.hits = d_hits; bp.nhits = d_nhits; bp.top = top;
+        bp.offsets = db->d_offsets; bp.ntargets = db->ntargets;
+        bp.queries = c->d_mq + grp.q0; bp.nq = grp.nq;
+        for (int k = 0; k < swp::kAlignHitsKernels; ++k) {
+            bp.cls_q0[k] = grp.cls[k].q0 - grp.q0;
+            bp.ntiers[k] = grp.cls[k].ntiers;
+            std::copy(std::begin(grp.cls[k].bound), std::end(grp.cls[k].bound), bp.bound[k]);
+        }
+        bp.cls_q0[swp::kAlignHitsKernels] = grp.nq;
+        bp.ctl = c->d_ahctl; bp.items = c->d_ahitems; bp.aln = d_aln; bp.filled = c->d_ahfilled;
+        const unsigned bin_blocks = (unsigned)std::clamp<int64_t>((grp.nq * top + 255) / 256, 1, 4096);
+        hipLaunchKernelGGL(swk::sw_align_hits_bin<false>, dim3(bin_blocks), dim3(256), 0, stream, bp);
+        HIP_TRY(hipGetLastError());
+        hipLaunchKernelGGL(swk::sw_align_hits_bin<true>, dim3(bin_blocks), dim3(256), 0, stream, bp);
+        HIP_TRY(hipGetLastError());
+        for (; li < plan.launch.size() && plan.launch[li].group == (int)g; ++li) {
+            const swp::AlignHitsLaunch& l = plan.launch[li];
+            swk::AlignHitsParams ap;
+            memset(&ap, 0, sizeof ap);
+            ap.db = (const unsigned char*)db->d_db;
+            ap.items = c->d_ahitems + grp.cls[l.kernel].item0;
+            ap.counts = c->d_ahctl->count[l.kernel]; ap.tier = l.tier;
+            ap.queries = c->d_mq + grp.q0; ap.prof = c->d_sprof;
+            ap.ge = scoring->gap_extend; ap.goe = scoring->gap_open + scoring->gap_extend;
+            ap.bnd = l.bnd_per ? c->d_sbnd : nullptr; ap.bnd_per = l.bnd_per;
+            ap.counter = &c->d_ahctl->work[l.kernel][l.tier];
+            ap.dir = c->d_adir; ap.slot_bytes = l.slot_bytes; ap.nslots = l.slots;
+            ap.aln = d_aln; ap.ops = d_ops; ap.ops_cap = ops_cap;
+            hipLaunchKernelGGL(kAlignHits[l.kernel].k, dim3((unsigned)l.grid), dim3(256), 0, stream, ap);
+            HIP_TRY(hipGetLastError());
+        }
+    }
+    c->last_align_hits_launches = (int64_t)(3 * plan.group.size() + plan.launch.size()); c->last_align_hits_tiers = plan.tiers; c->last_align_hits_slots = plan.slots;
     return SW_OK;
 }
 

@@ -19,6 +19,7 @@ int check_search_affine(const char* who, int64_t qlen, const int64_t* offsets, i
 int check_align_affine(const char* who, const int64_t* offsets, int64_t ntargets, const int64_t* hits, int64_t nhits, const void* aln, const void* ops,
                        int64_t ops_cap, int64_t* maxhit_out);
 int check_search_multi(const char* who, const int64_t* qoffsets, int64_t nqueries, int64_t longest_target, const sw_affine* sc, int64_t* maxq_out);
+int check_align_hits(const char* who, int64_t top, const void* hits, const void* aln, const void* ops, int64_t ops_cap);
 SW_HIDDEN int check_targets(const char* who, int64_t qlen, const int64_t* offsets, int64_t ntargets, int64_t* maxlen_out, int64_t* nonempty_out);
 }
 using swh::set_err;
@@ -111,6 +112,14 @@ struct SW_HIDDEN sw_ctx {
     int64_t last_align_affine_kernel = 0, last_align_affine_slots = 0;
     int align_affine_per_cu[swp::kAlignAffineKernels] = {};     // occupancy of every sw_align_affine_wave instantiation at 256 threads ...
     bool align_affine_per_cu_known = false;                     // ... queried at the first call
+    // alignment of the hits of many queries (sw_db_align_affine_hits): the item list of a group and the control words of its lists; the
+    // profiles, the boundary columns, the query table and the direction workspace are those of the calls above
+    swk::AlignHitItem* d_ahitems = nullptr; size_t ahitems_cap = 0;
+    swk::AlignHitsCtl* d_ahctl = nullptr;
+    unsigned int* d_ahfilled = nullptr;  // lists of the last call that received items, counted by the binning ("last_align_hits_lists")
+    int64_t last_align_hits_launches = 0, last_align_hits_tiers = 0, last_align_hits_slots = 0;
+    int align_hits_per_cu[swp::kAlignHitsKernels] = {};         // occupancy of every sw_align_hits_wave instantiation at 256 threads ...
+    bool align_hits_per_cu_known = false;                       // ... queried at the first call
     // many queries against a prepared database (sw_db_search_affine): the call's query table on the device + the pinned copy it is uploaded
     // from (the protocol of sitems_ev covers it), the budget of a group's profiles
     swk::MultiQuery* d_mq = nullptr; swk::MultiQuery* h_mq = nullptr; size_t mq_cap = 0;
@@ -136,13 +145,15 @@ struct SW_HIDDEN sw_ctx {
     std::map<void*, float> pair_ratio;  // ... P handed out -> the store probe's ratio of its pair (~1.4: two classes of the HBM, ~2: one)
 };
 
-// A prepared database (sw_db_create): the caller's device bytes, borrowed, and the search schedule of its targets on the device -- what
-// every search of it needs and no query changes.
+// A prepared database (sw_db_create): the caller's device bytes, borrowed, the search schedule of its targets on the device -- what
+// every search of it needs and no query changes -- and the offsets themselves: the schedule is ordered by length, and the alignment of
+// a hit table (sw_db_align_affine_hits) has to get from a target INDEX to that target's bytes.
 struct SW_HIDDEN sw_db {
     int device = 0;
     const char* d_db = nullptr;
     int64_t ntargets = 0, nonempty = 0, longest = 0, letters = 0;
     swk::SearchItem* d_items = nullptr;  // the nonempty targets, longest first (swp::search_schedule)
+    int64_t* d_offsets = nullptr;        // the ntargets + 1 offsets, the caller's order
 };
 
 // A launch table: every instantiation beside the index the planner gives it, checked at compile time to sit at that index.

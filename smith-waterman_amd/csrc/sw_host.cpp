@@ -135,6 +135,16 @@ int check_align_affine(const char* who, const int64_t* offsets, int64_t ntargets
     return SW_OK;
 }
 
+// What sw_db_align_affine_hits / sw_align_affine_hits_host check beyond check_search_multi (include/swhip.h).
+int check_align_hits(const char* who, int64_t top, const void* hits, const void* aln, const void* ops, int64_t ops_cap) {
+    if (top < 1 || top > SW_TOP_MAX) { set_err("%s: top = %lld is out of range 1..%d", who, (long long)top, SW_TOP_MAX); return SW_EINVAL; }
+    if (!hits) { set_err("%s: the hit table is NULL", who); return SW_EINVAL; }
+    if (!aln) { set_err("%s: the alignment array is NULL", who); return SW_EINVAL; }
+    if (ops_cap < 0) { set_err("%s: ops_cap = %lld is negative", who, (long long)ops_cap); return SW_EINVAL; }
+    if (!ops && ops_cap > 0) { set_err("%s: the ops buffer is NULL with ops_cap = %lld", who, (long long)ops_cap); return SW_EINVAL; }
+    return SW_OK;
+}
+
 inline char letter(int v) {  // serial_smithW.c:339-346
     switch (v) { case 0: return 'A'; case 2: return 'C'; case 3: return 'G'; default: return 'T'; }
 }
@@ -542,6 +552,43 @@ int sw_align_affine_host(const char* query, int64_t qlen, const char* db, const 
         const int64_t nops = (int64_t)rev.size();
         aln[hx] = best > 0 ? sw_alignment{best_pos, best, j, i, j1, i1, nops} : sw_alignment{0, 0, 0, 0, 0, 0, 0};
         if (ops && nops <= ops_cap) std::reverse_copy(rev.begin(), rev.end(), ops + hx * ops_cap);
+    }
+    return SW_OK;
+}
+
+// The CPU leg of sw_db_align_affine_hits: per query the used entries of its row whose target lies inside the database go through
+// sw_align_affine_host in one call, into rows of their own, and are copied to their places; every other entry is all zeros and its ops
+// row is left alone.  Everything is checked before the first alignment.
+int sw_align_affine_hits_host(const char* queries, const int64_t* qoffsets, int64_t nqueries, const char* db, const int64_t* offsets, int64_t ntargets,
+                              const sw_affine* scoring, const sw_hit* hits, const int64_t* nhits, int64_t top, sw_alignment* aln, char* ops, int64_t ops_cap) {
+    if (!queries || !qoffsets || !db || !offsets || !scoring || ntargets < 0) {
+        swh::set_err("sw_align_affine_hits_host: NULL pointer or negative target count");
+        return SW_EINVAL;
+    }
+    int64_t maxlen = 0, nonempty = 0, maxq = 0;
+    if (int rc = swh::check_targets("sw_align_affine_hits_host", 1, offsets, ntargets, &maxlen, &nonempty)) return rc;
+    if (int rc = swh::check_search_multi("sw_align_affine_hits_host", qoffsets, nqueries, maxlen, scoring, &maxq)) return rc;
+    if (int rc = swh::check_align_hits("sw_align_affine_hits_host", top, hits, aln, ops, ops_cap)) return rc;
+    std::vector<int64_t> targets, where;
+    std::vector<sw_alignment> row;
+    std::vector<char> rows;
+    for (int64_t q = 0; q < nqueries; ++q) {
+        const int64_t used = nhits ? std::clamp<int64_t>(nhits[q], 0, top) : top;
+        targets.clear(); where.clear();
+        for (int64_t r = 0; r < top; ++r) {
+            const uint64_t target = (uint64_t)hits[q * top + r].target;
+            if (r < used && target < (uint64_t)ntargets) { targets.push_back((int64_t)target); where.push_back(q * top + r); }
+            else aln[q * top + r] = sw_alignment{0, 0, 0, 0, 0, 0, 0};
+        }
+        if (targets.empty()) continue;
+        row.resize(targets.size());
+        rows.resize(ops ? targets.size() * (size_t)ops_cap : 0);
+        if (int rc = sw_align_affine_host(queries + qoffsets[q], qoffsets[q + 1] - qoffsets[q], db, offsets, ntargets, targets.data(), (int64_t)targets.size(),
+                                          scoring, row.data(), ops ? rows.data() : nullptr, ops ? ops_cap : 0)) return rc;
+        for (size_t k = 0; k < targets.size(); ++k) {
+            aln[where[k]] = row[k];
+            if (ops && row[k].nops <= ops_cap) std::copy_n(rows.data() + k * (size_t)ops_cap, (size_t)row[k].nops, ops + where[k] * ops_cap);
+        }
     }
     return SW_OK;
 }

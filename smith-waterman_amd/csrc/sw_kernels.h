@@ -201,6 +201,45 @@ struct AlignAffineParams {
 template <int C>
 __global__ void sw_align_affine_wave(AlignAffineParams p);
 
+// sw_align_hits.hip: the alignments of the hits of many queries, straight from a device hit table (sw_db_align_affine_hits).  Two binning
+// launches turn the used entries of a group's rows into work items, one list per (class, tier) (swp::plan_align_hits); one launch of
+// sw_align_hits_wave<C> per list aligns them.
+struct AlignHitItem { int64_t start, out; int32_t len, entry; };   // first byte in db, index in d_aln (q * top + r), length, entry of the group's query table
+constexpr int SW_AH_CLASSES = swp::kAlignHitsKernels, SW_AH_TIERS = swp::kAlignHitsTiers;
+// the control words of a group, zero before its binning: per list the items counted, the scatter's cursor and the work counter of its launch
+struct AlignHitsCtl { unsigned int count[SW_AH_CLASSES][SW_AH_TIERS], cursor[SW_AH_CLASSES][SW_AH_TIERS], work[SW_AH_CLASSES][SW_AH_TIERS]; };
+struct AlignHitsBinParams {
+    const sw_hit* hits; const int64_t* nhits;    // the caller's table (nqueries x top) and counts (or NULL: every entry is used)
+    int64_t top;
+    const int64_t* offsets; int64_t ntargets;    // the handle's ntargets + 1 offsets on the device
+    const MultiQuery* queries;                   // the group's entries of the call's table, by class
+    int64_t nq;
+    int64_t cls_q0[SW_AH_CLASSES + 1];           // class k: entries cls_q0[k] .. cls_q0[k + 1] - 1 of `queries`, items from cls_q0[k] * top on
+    int ntiers[SW_AH_CLASSES]; int64_t bound[SW_AH_CLASSES][SW_AH_TIERS];   // ascending bounds of the class's tiers (bytes of a direction matrix)
+    AlignHitsCtl* ctl;
+    AlignHitItem* items;                         // nq * top at most
+    sw_alignment* aln;                           // entries that yield the zero alignment are written here
+    unsigned int* filled;                        // SCATTER: += the lists of this group that received items (zero before the call's first group)
+};
+template <bool SCATTER>
+__global__ void sw_align_hits_bin(AlignHitsBinParams p);
+struct AlignHitsParams {
+    const unsigned char* db;             // the targets back to back
+    const AlignHitItem* items;           // the class's part of the group's list: its tiers back to back, smallest first
+    const unsigned int* counts;          // the class's counts per tier (AlignHitsCtl::count[k]): this list starts behind the lower tiers'
+    int tier;
+    const MultiQuery* queries;           // the group's entries of the call's table (what an item's `entry` counts from)
+    const signed char* prof;             // the group's profiles, query t at its prof_off
+    int ge, goe;                         // gap_extend, gap_open + gap_extend (both <= 0)
+    int* bnd; int64_t bnd_per;           // per slot: boundary pairs (H, F) between strips (ints), only when a query of the class has more than one strip
+    unsigned int* counter;               // next item (zero at launch)
+    unsigned char* dir; int64_t slot_bytes, nslots;   // per slot: a direction matrix of the tier's size (below 2^31), row stride = the item's qpad
+    sw_alignment* aln;                   // nqueries x top
+    char* ops; int64_t ops_cap;          // nqueries x top rows of ops_cap bytes; NULL: coordinates only
+};
+template <int C>
+__global__ void sw_align_hits_wave(AlignHitsParams p);
+
 template <typename HT, int B>
 __global__ void sw_strip_scan(const unsigned char* a, const unsigned char* b, FillParams p);
 template <typename HT, int NS, int NC>

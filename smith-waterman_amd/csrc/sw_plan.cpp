@@ -507,6 +507,83 @@ AlignAffinePlan plan_align_affine(const AlignAffineJob& j) {
     return a;
 }
 
+// The hits of many queries from a device table.  Host work is O(nqueries): the loop of plan_search_multi over the queries, with the
+// entry bound as a second reason to close a group, and per group a constant number of tiers and launches.  Nothing here depends on
+// which targets the table names; the counts of items are products of int64 counts, never sums over items.
+AlignHitsPlan plan_align_hits(const AlignHitsJob& j) {
+    using swk::SW_SEARCH_ROWS;
+    AlignHitsPlan a;
+    const int64_t n = j.nqueries, top = std::max<int64_t>(1, j.top), rows = std::max<int64_t>(1, j.longest);
+    auto columns = [&](int64_t qlen) {
+        int C = lane_columns(qlen);
+        if (C == 16 && j.per_cu[align_hits_kernel_index(16)] < kAffineC16MinPerCu) C = 8;
+        return C;
+    };
+    auto padded = [&](int64_t qlen) { const int64_t w = 64 * columns(qlen); return (qlen + w - 1) / w * w; };
+    for (int64_t q = 0; q < n; ++q) a.worst_qpad = std::max(a.worst_qpad, padded(j.qlens[q]));
+    a.worst_bytes = rows * a.worst_qpad;
+    a.fits = a.worst_bytes <= j.budget_bytes && a.worst_bytes <= kAlignSlotLimit;
+    if (!a.fits) return a;
+    a.table.resize((size_t)n);
+    const int64_t group_queries = std::max<int64_t>(1, std::max<int64_t>(1, j.max_items) / top);
+    for (int64_t g0 = 0; g0 < n;) {
+        int64_t g1 = g0, bytes = 0;
+        while (g1 < n && (g1 == g0 || (g1 - g0 < group_queries && bytes + SW_SEARCH_ROWS * padded(j.qlens[g1]) <= j.profile_budget_bytes)))
+            bytes += SW_SEARCH_ROWS * padded(j.qlens[g1++]);
+        AlignHitsGroup grp;
+        grp.q0 = g0; grp.nq = g1 - g0; grp.prof_bytes = bytes;
+        a.prof_need = std::max(a.prof_need, (size_t)bytes);
+        a.items_need = std::max(a.items_need, (size_t)(grp.nq * top));
+        // the table of the group: by class, input order within a class; the profiles lie in table order
+        int64_t at[kAlignHitsKernels + 1] = {};
+        for (int64_t q = g0; q < g1; ++q) ++at[align_hits_kernel_index(columns(j.qlens[q])) + 1];
+        for (int k = 0; k < kAlignHitsKernels; ++k) at[k + 1] += at[k];
+        for (int k = 0; k < kAlignHitsKernels; ++k) {
+            grp.cls[k].q0 = g0 + at[k]; grp.cls[k].nq = at[k + 1] - at[k];
+            grp.cls[k].item0 = at[k] * top; grp.cls[k].entries = grp.cls[k].nq * top;
+        }
+        for (int64_t q = g0; q < g1; ++q) {
+            const int C = columns(j.qlens[q]), k = align_hits_kernel_index(C);
+            const int64_t qpad = padded(j.qlens[q]);
+            a.table[(size_t)(g0 + at[k]++)] = swk::MultiQuery{0, 0, q, (int32_t)j.qlens[q], (int32_t)qpad, (int32_t)(qpad / (64 * C)), 0};
+            grp.cls[k].qpad = std::max(grp.cls[k].qpad, qpad);
+            grp.cls[k].nstrips = std::max(grp.cls[k].nstrips, qpad / (64 * C));
+        }
+        int64_t off = 0;
+        for (int64_t t = g0; t < g1; ++t) { a.table[(size_t)t].prof_off = off; off += SW_SEARCH_ROWS * a.table[(size_t)t].qpad; }
+        // the tiers of every class and their launches, largest first
+        for (int k = 0; k < kAlignHitsKernels; ++k) {
+            AlignHitsClass& c = grp.cls[k];
+            if (c.nq == 0) continue;
+            const int C = k == 0 ? 4 : 8 * k;
+            int64_t down[kAlignHitsTiers];
+            down[0] = rows * c.qpad;
+            for (c.ntiers = 1; c.ntiers < kAlignHitsTiers && down[c.ntiers - 1] / kAlignHitsTierRatio >= kAlignHitsTierFloor; ++c.ntiers)
+                down[c.ntiers] = down[c.ntiers - 1] / kAlignHitsTierRatio;
+            for (int t = 0; t < c.ntiers; ++t) c.bound[t] = down[c.ntiers - 1 - t];
+            for (int t = c.ntiers - 1; t >= 0; --t) {
+                AlignHitsLaunch l;
+                l.group = (int)a.group.size(); l.C = C; l.kernel = k; l.tier = t;
+                l.slot_bytes = c.bound[t];
+                // a query of several strips is at least two strips wide: that bounds the rows of a tier's items that cross a boundary
+                l.bnd_per = 2 * boundary_ints(c.nstrips, std::min(rows, c.bound[t] / (2 * 64 * C)));
+                l.slots = std::min<int64_t>({c.entries, (int64_t)j.per_cu[k] * j.num_cus * 4, j.budget_bytes / l.slot_bytes});
+                if (l.bnd_per) l.slots = std::min<int64_t>(l.slots, kSearchBndBytes / (l.bnd_per * 4));
+                l.slots = std::max<int64_t>(1, l.slots);
+                l.grid = (l.slots + 3) / 4;
+                a.bnd_need = std::max(a.bnd_need, (size_t)(l.slots * l.bnd_per));
+                a.dir_need = std::max(a.dir_need, (size_t)(l.slots * l.slot_bytes));
+                a.slots += l.slots;
+                a.launch.push_back(l);
+            }
+        }
+        a.group.push_back(grp);
+        g0 = g1;
+    }
+    a.tiers = (int64_t)a.launch.size();
+    return a;
+}
+
 void align_schedule(const int64_t* offsets, const int64_t* hits, int64_t nhits, swk::SearchItem* items) {
     std::vector<int64_t> order((size_t)nhits);
     for (int64_t h = 0; h < nhits; ++h) order[(size_t)h] = h;

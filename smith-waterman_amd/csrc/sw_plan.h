@@ -1,9 +1,10 @@
 // sw_plan.h -- the planners: every policy decision of one fill (kernel, workgroup shape, perm producer, strip geometry, column
 // tiles, scouts, roles per XCD, split strips, filler pacing, store kind), of one batch call (one pair or two pairs per wave, columns
 // per lane, pairs per launch, the kernel of every launch) and of one database search (columns per lane, profile kind, grid, schedule;
-// plan_search_affine for the affine-gap search) and of one alignment call (plan_align_affine: columns per lane, slots, grid, order of the hits),
-// and the workspace sizes they need, as pure functions of the job, the device and the options.  Plain C++ (no HIP include):
-// sw_api_fill.hip and sw_api_search.hip carry a plan out, tests/test_fill_plan.py and tests/test_batch_plan.py check the policy on a CPU.
+// plan_search_affine for the affine-gap search) and of one alignment call (plan_align_affine: columns per lane, slots, grid, order of the
+// hits; plan_align_hits: groups, size tiers and slots for a device hit table), and the workspace sizes they need, as pure functions of
+// the job, the device and the options.  Plain C++ (no HIP include): sw_api_fill.hip and sw_api_search.hip carry a plan out,
+// tests/test_fill_plan.py and tests/test_batch_plan.py check the policy on a CPU.
 #pragma once
 #include <cstddef>
 #include <cstdint>
@@ -287,6 +288,69 @@ struct AlignAffinePlan {
 };
 
 AlignAffinePlan plan_align_affine(const AlignAffineJob& job);
+
+// ---- alignment of the hits of many queries, taken from a device table (sw_db_align_affine_hits; sw_align_hits.hip):
+// sw_align_hits_wave<C> for C = 4, 8, 16, its index in kAlignHits (sw_api_search.hip, which checks its order against it at compile time).
+// The host knows the queries and the handle's longest target, not the targets a table names; it plans for every target the table could name.
+// Groups: consecutive queries whose profiles fit the profile budget (plan_search_multi's rule; one query alone may exceed it) and whose
+// entries -- queries x top, each at most one work item -- stay within max_items: that bounds the item list of a group.  The table of a
+// group is laid out by class (columns per lane) like plan_search_multi's, the profiles in table order.
+// Tiers: per class of a group at most kAlignHitsTiers sizes of a direction matrix.  The top tier is the worst case of the class in that
+// group, longest target x the class's largest padded query length; every lower tier is kAlignHitsTierRatio times smaller, as long as it
+// stays at or above kAlignHitsTierFloor bytes.  An item of len x qpad bytes goes to the smallest tier that holds it (the binning kernels
+// decide by the same bounds, which they get from this plan).
+// Launches: one per (class, tier) of a group, largest tier first.  The launches of a call follow each other in the stream, so every
+// launch has the direction workspace to itself: slots x slot_bytes of ONE launch stay within the budget; slots are at least 1, at most
+// the resident waves of the kernel, at most the entries of the class (no list is longer), and at most what the boundary columns allow
+// (kSearchBndBytes, as in plan_align_affine; a tier's rows are bounded by its size over two strips' width).
+// Fits: the call's worst case, longest target x the padded length of the longest query, fits the budget and a buffer descriptor.
+constexpr int kAlignHitsKernels = 3;
+constexpr int align_hits_kernel_index(int C) { return C / 8; }
+constexpr int kAlignHitsTiers = 4;
+constexpr int64_t kAlignHitsTierRatio = 4;
+constexpr int64_t kAlignHitsTierFloor = 32 << 10;
+constexpr int64_t kAlignHitsMaxItems = 1 << 22;      // entries of a group: 24 bytes of list each (96 MiB)
+
+struct AlignHitsJob {
+    const int64_t* qlens = nullptr;          // length of every query, input order
+    int64_t nqueries = 0, top = 1;
+    int64_t longest = 0;                     // of the handle: longest target
+    int num_cus = 256;
+    int per_cu[kAlignHitsKernels] = {};      // occupancy of every sw_align_hits_wave instantiation at 256 threads (workgroups per CU)
+    int64_t profile_budget_bytes = 256ll << 20;   // "search_profile_mib"
+    int64_t budget_bytes = 1ll << 30;        // "align_workspace_mib": the direction workspace may take this much
+    int64_t max_items = kAlignHitsMaxItems;  // (tests lower it)
+};
+
+struct AlignHitsClass {
+    int64_t q0 = 0, nq = 0;                  // its queries: entries q0 .. q0 + nq - 1 of the table
+    int64_t item0 = 0, entries = 0;          // its part of the group's item list: first item, nq * top items at most
+    int64_t qpad = 0, nstrips = 0;           // the largest padded query length and the most strips among its queries
+    int ntiers = 0;                          // 0: no query of this class in the group
+    int64_t bound[kAlignHitsTiers] = {};     // ascending: tier t holds the items of at most bound[t] bytes (and more than bound[t - 1])
+};
+struct AlignHitsGroup {
+    int64_t q0 = 0, nq = 0, prof_bytes = 0;  // the queries q0 .. q0 + nq - 1 = the table entries q0 .. q0 + nq - 1, by class
+    AlignHitsClass cls[kAlignHitsKernels];
+};
+struct AlignHitsLaunch {
+    int group = 0, C = 0, kernel = 0, tier = 0;
+    int64_t slot_bytes = 0, slots = 0;       // the tier's bound; waves at work, each with its own slot
+    int64_t bnd_per = 0;                     // per slot: boundary pairs between strips (ints), 0: every query of the class has one strip
+    int64_t grid = 0;                        // workgroups of 4 waves
+};
+
+struct AlignHitsPlan {
+    bool fits = false;
+    int64_t worst_qpad = 0, worst_bytes = 0; // the padded length of the longest query; longest target x that
+    std::vector<swk::MultiQuery> table;      // as SearchMultiPlan::table
+    std::vector<AlignHitsGroup> group;
+    std::vector<AlignHitsLaunch> launch;     // in the order they are enqueued: group after group, per class the largest tier first
+    int64_t tiers = 0, slots = 0;            // tiers planned (= launches) and the sum of their slots
+    size_t prof_need = 0, bnd_need = 0, dir_need = 0, items_need = 0;   // workspaces: profiles (bytes), boundary columns (ints), directions (bytes), items
+};
+
+AlignHitsPlan plan_align_hits(const AlignHitsJob& job);
 
 // The order of the hits: by decreasing length, ties in the caller's order; items[k].idx is the position in `hits` (empty hits are kept:
 // they get their all-zero alignment from the kernel like any other).

@@ -3,7 +3,7 @@
   * v126/v127 (landing registers of the hand-tracked edge prefetch) appear ONLY in the two asm
     statements that own them;
   * no scratch (spills) in the fill kernels, none at all in the search kernels (sw_search.hip, sw_search_affine.hip, sw_search_multi.hip)
-    and the alignment kernels (sw_align_affine.hip), whose work counter is a vector buffer atomic."""
+    and the alignment kernels (sw_align_affine.hip, sw_align_hits.hip), whose work counter is a vector buffer atomic."""
 import re, subprocess, sys, os, tempfile
 here = os.path.dirname(os.path.abspath(__file__))
 src = os.path.join(here, "..", "smith-waterman_amd", "csrc", "sw_kernels.hip")
@@ -97,5 +97,17 @@ for m in re.finditer(r"\.private_segment_fixed_size:\s*(\d+)", s6):
 nalign = len(re.findall(r"^\s*\.name:\s+\S*sw_align_affine_wave", s6, flags=re.M))
 if nalign < 3:
     print(f"affine alignment kernels: expected 3, found {nalign}"); sys.exit(1)
+# sw_align_hits.hip (alignment of a device hit table): no scratch at all in its three alignment kernels and two binning kernels, and the
+# work counter of every alignment kernel is taken with a vector buffer atomic
+s8 = dev_asm("sw_align_hits.hip")
+for m in re.finditer(r"\.private_segment_fixed_size:\s*(\d+)", s8):
+    if int(m.group(1)) > 0:
+        print("scratch in use (hit-table alignment):", m.group(0)); sys.exit(1)
+nhits = len(re.findall(r"^\s*\.name:\s+\S*sw_align_hits_wave", s8, flags=re.M))
+nbin = len(re.findall(r"^\s*\.name:\s+\S*sw_align_hits_bin", s8, flags=re.M))
+bodies8 = re.findall(r"^(\S*sw_align_hits_wave\S*):[^\n]*\n(.*?)^\.Lfunc_end\d+:", s8, flags=re.M | re.S)
+without8 = [name for name, body in bodies8 if not re.search(r"^\s*buffer_atomic_add ", body, flags=re.M)]
+if nhits != 3 or nbin != 2 or len(bodies8) != nhits or without8:
+    print(f"hit-table alignment kernels: expected 3 alignment kernels with a vector buffer atomic work counter and 2 binning kernels ({nhits} + {nbin} kernels, {len(bodies8)} bodies found, none in {without8})"); sys.exit(1)
 n = len(re.findall(r"global_load_dwordx2 v\[126:127\]", s))
-print(f"check_isa ok: {n} prefetch sites, v126/v127 private; {nprod} producer paths keep v100..v120 private; traceback window v62..v127 private; no scratch; {nsearch} search kernels without scratch; {naffine} affine search kernels without scratch; {nmulti} many-query search kernels without scratch; {nalign} affine alignment kernels without scratch")
+print(f"check_isa ok: {n} prefetch sites, v126/v127 private; {nprod} producer paths keep v100..v120 private; traceback window v62..v127 private; no scratch; {nsearch} search kernels without scratch; {naffine} affine search kernels without scratch; {nmulti} many-query search kernels without scratch; {nalign} affine alignment kernels without scratch; {nhits} + {nbin} hit-table alignment kernels without scratch")
