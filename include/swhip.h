@@ -264,6 +264,9 @@ int sw_search_affine_host(const char* query, int64_t qlen, const char* db, const
  * of a re-filled matrix (longest hit x padded query length per slot) in a per-context workspace that the option
  * "align_workspace_mib" bounds (default 1024): a hit whose own matrix does not fit is SW_EINVAL with a message that names the
  * option; more hits than slots fit are processed slot after slot inside the one call.
+ * Under "align_checkpoint" = 1, and under 2 for exactly the calls refused above, a slot holds one band of rows and a checkpoint row
+ * per band instead (see sw_set_option): the same sw_alignment and ops byte for byte, and a hit is refused only if that slot -- a few
+ * MB for a million rows -- does not fit "align_workspace_mib".  The argument rules stay: a target has at most 2^20 - 1 letters.
  * sw_align_affine_host: the same in plain C++ on host memory (the CPU leg; no workspace bound). */
 typedef struct { int64_t max_pos, max_score, q_begin, t_begin, q_end, t_end, nops; } sw_alignment;
 int sw_align_affine_device(sw_ctx* ctx, const char* d_query, int64_t qlen, const char* d_db, const int64_t* offsets,
@@ -367,7 +370,9 @@ int  sw_search_affine_multi_top_host(const char* queries, const int64_t* qoffset
  * d_ops with ops_cap > 0; and a worst case that does not fit: the host cannot know which targets the table names, so the handle's
  * longest target x the padded length of the longest query (a multiple of 256, 512 or 1024 for queries of at most 256, at most 512,
  * longer) has to fit "align_workspace_mib" and the 2 GiB a slot may take -- decided before anything is launched, whatever the table
- * says, with a message that names the option.  The workspaces are those of sw_align_affine_device and sw_db_search_affine
+ * says, with a message that names the option.  Under "align_checkpoint" = 1, and under 2 for exactly the calls refused so, every
+ * hit is aligned from one band of direction bytes and checkpoint rows (see sw_set_option): the same bytes in d_aln and d_ops, and a
+ * call is refused only if the checkpointed slot of that worst case does not fit the option.  The workspaces are those of sw_align_affine_device and sw_db_search_affine
  * ("align_workspace_mib", "search_profile_mib": queries run in consecutive groups whose profiles fit) plus 24 bytes per entry of a group,
  * at most 96 MiB.  "last_align_hits_launches" (kernel launches), "last_align_hits_tiers" (the (class, size tier) lists planned, one
  * alignment launch each) and "last_align_hits_slots" (direction matrices, summed over those launches) describe the last call, all 0 for
@@ -557,7 +562,22 @@ int sw_synchronize(sw_ctx* ctx, void* stream);   /* waits for `stream`; reports 
  * wave on packed lanes), "last_search_kernel" (the last search: 2 * (columns per lane / 8) + 1 for the wide profile), "last_search_affine_kernel"
  * (the last affine search: columns per lane / 8) and "last_search_affine_grid" (its workgroups), "last_align_affine_kernel" (the
  * last sw_align_affine_device call: columns per lane / 8) and "last_align_affine_slots" (its direction matrices, one per wave at
- * work); "align_workspace_mib" (settable, default 1024) bounds the direction workspace of that call; "search_profile_mib" (settable,
+ * work); "align_workspace_mib" (settable, default 1024) bounds the direction workspace of that call;
+ * "align_checkpoint" (settable, default 0) chooses how sw_align_affine_device and sw_db_align_affine_hits keep the directions of a
+ * hit: 0 the whole matrix, one byte per cell, as described at the two calls; 1 checkpointed: a score-only sweep saves H and E of
+ * every B-th row (8 bytes per column), and only the bands of B rows the walk enters are re-filled with direction bytes, each resumed
+ * from the checkpoint above it, so a slot takes qpad * (min(B, len) + 8 * (ceil(len / B) - 1)) bytes instead of qpad * len and the
+ * results are the same byte for byte (the argument rules of the two calls stay as they are: no target above 2^20 - 1 letters is
+ * accepted, checkpointed or not); 2 checkpointed for exactly the calls that 0 would refuse for size, the whole matrix otherwise
+ * (decided on the host once per call, before any launch).  "align_checkpoint_rows" (settable, default 0) is B: 0 leaves it to the
+ * planner (the power of two from 256 to 2^20 that makes the slot smallest), otherwise a power of two in 64..2^20, anything else is
+ * SW_EINVAL.  "last_align_affine_checkpointed" (0 / 1), "last_align_affine_band_rows" (B, 0 for whole matrices) and
+ * "last_align_affine_slot_bytes" describe the last sw_align_affine_device call, "last_align_hits_checkpointed" and
+ * "last_align_hits_band_rows" (the largest B over its launches) the last sw_db_align_affine_hits call.  "debug_buf" and
+ * "align_checkpoint": a checkpointed sw_align_affine_device call adds THREE words of wave ticks (sweep, walk, re-fills) where the
+ * whole-matrix call adds two, and under 2 the caller does not know beforehand which runs -- whenever "align_checkpoint" is not 0 the
+ * buffer "debug_buf" names must hold at least three 8-byte words;
+ * "search_profile_mib" (settable,
  * default 256) bounds the profiles of a group of sw_db_search_affine, "last_search_multi_groups", "last_search_multi_launches" and
  * "last_search_multi_grid" (workgroups of its last launch) describe the last such call; "search_results_mib" (settable, default 1024,
  * 1..2^20) bounds the result rows a chunk of sw_db_search_affine_top holds, "last_search_top_chunks" and "last_search_top_kernel"

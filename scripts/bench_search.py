@@ -22,6 +22,11 @@
   hits to the host, then one sw_align_affine_device call per query; (2) one sw_db_align_affine_hits call on the device table.  Both
   write one output buffer and copy the coordinates and the ops up to the longest alignment to the host in two copies; the alignments are compared entry by entry; the search call's time in
   the same process stands beside them
+  --align-hits --checkpoint: data set (a) only, checkpointed alignment (option "align_checkpoint" = 1, the planner's band height) beside
+  the whole-matrix path (0) in the same process, torch events, medians and ranges of --reps after --warmup: the sw_db_align_affine_hits
+  call on the top 10 / top 100 hits of 64 queries of --qlen, and the sw_align_affine_device call on the top 100 / 1000 hits of one
+  query with the waves' tick stamps (mode 0: fill, walk; mode 1: sweep, walk, re-fill).  The outputs of the two modes are compared on
+  the device before anything is timed
 GCUPS = query letters x target letters / time of the call (torch events, median of --reps after --warmup)."""
 import argparse
 import importlib
@@ -66,6 +71,7 @@ def main():
     ap.add_argument("--only-a", action="store_true", help="data set (a) only: linear search, affine search, alignment of its top hits")
     ap.add_argument("--multi", action="store_true", help="data set (a) only: many queries through a prepared database against one call per query")
     ap.add_argument("--align-hits", action="store_true", help="data set (a) only: the alignments of the top 10 / 100 hits of 64 queries, per query and in one call")
+    ap.add_argument("--checkpoint", action="store_true", help="with --align-hits: checkpointed alignment beside the whole-matrix path, hit table and one query")
     ap.add_argument("--top", action="store_true", help="data set (a) only: the best 100 targets of 64 queries by the full table and by the selection on the device")
     args = ap.parse_args()
     rng = np.random.default_rng(2026)
@@ -291,6 +297,83 @@ def main():
             out[f"{tag}_one_call_over_search"] = round(out[f"{tag}_one_call_ms"] / out[f"{tag}_search_ms"], 4)
         db.close()
 
+    def spread(fn):
+        """Median and range of --reps calls after --warmup, torch events."""
+        for _ in range(args.warmup):
+            fn()
+        torch.cuda.synchronize()
+        ms = []
+        for _ in range(args.reps):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            fn()
+            e1.record()
+            torch.cuda.synchronize()
+            ms.append(e0.elapsed_time(e1))
+        return round(float(np.median(ms)), 3), [round(min(ms), 3), round(max(ms), 3)]
+
+    def align_ckpt_leg(q, packed, offs, nq=64):
+        d_db = torch.from_numpy(packed.copy()).to(dev)
+        db = eng.prepare_db(d_db, offs)
+        lens = np.diff(offs)
+        longest = int(lens.max())
+        scoring = (sub, -11, -1)
+        out["ckpt_queries"], out["ckpt_qlen"] = nq, args.qlen
+        # the hit table of 64 queries: one sw_db_align_affine_hits call per mode
+        qoffs = np.arange(nq + 1, dtype=np.int64) * args.qlen
+        d_qs = torch.from_numpy(rng.choice(PROTEIN, int(qoffs[-1])).astype(np.uint8)).to(dev)
+        for top in (10, 100):
+            tag = f"ckpt_hits_top{top}"
+            d_hits, d_nhits = db.search_affine_top_device(d_qs, qoffs, scoring, top)
+            cap = args.qlen + longest
+            bufs = [(torch.zeros((nq * top, 7), dtype=torch.int64, device=dev), torch.zeros((nq * top, cap), dtype=torch.uint8, device=dev)) for _ in range(2)]
+            for mode in (0, 1):
+                db.align_affine_hits_device(d_qs, qoffs, scoring, d_hits, d_nhits, ops_cap=cap, out=bufs[mode], checkpoint=mode)
+                out[f"{tag}_mode{mode}_slots"] = eng.get_option("last_align_hits_slots")
+            out[f"{tag}_band_rows"] = eng.get_option("last_align_hits_band_rows")
+            torch.cuda.synchronize()
+            out[f"{tag}_identical"] = bool(torch.equal(bufs[0][0], bufs[1][0]) and torch.equal(bufs[0][1], bufs[1][1]))
+            for mode in (0, 1):
+                out[f"{tag}_mode{mode}_ms"], out[f"{tag}_mode{mode}_range_ms"] = spread(
+                    lambda: db.align_affine_hits_device(d_qs, qoffs, scoring, d_hits, d_nhits, ops_cap=cap, out=bufs[mode], checkpoint=mode))
+            out[f"{tag}_mode1_over_mode0"] = round(out[f"{tag}_mode1_ms"] / out[f"{tag}_mode0_ms"], 3)
+            assert bool((d_nhits.cpu().numpy() == top).all()), "every row of the table was meant to be full"   # (no entry with target -1 below)
+            out[f"{tag}_hit_len_mean"] = round(float(lens[d_hits.cpu().numpy()[..., 0]].mean()), 1)
+        db.close()
+        # the top hits of one query: sw_align_affine_device per mode, with the waves' tick stamps
+        d_q = torch.from_numpy(q.copy()).to(dev)
+        res = torch.zeros((len(offs) - 1, 3), dtype=torch.int64, device=dev)
+        eng.search_affine_device(d_q, len(q), d_db, offs, sub, -11, -1, out=res)
+        order = swamd.top_hits(res.cpu().numpy(), 1000)
+        for k in (100, 1000):
+            tag = f"ckpt_one_top{k}"
+            hits = order[:k]
+            cap = len(q) + int(lens[hits].max())
+            bufs = [(torch.zeros((k, 7), dtype=torch.int64, device=dev), torch.zeros((k, cap), dtype=torch.uint8, device=dev)) for _ in range(2)]
+            for mode in (0, 1):
+                stamps = torch.zeros(3, dtype=torch.int64, device=dev)
+                eng.set_option("debug_buf", stamps.data_ptr())
+                eng.align_affine_device(d_q, len(q), d_db, offs, sub, -11, -1, hits, ops_cap=cap, out=bufs[mode], checkpoint=mode)
+                torch.cuda.synchronize()
+                eng.set_option("debug_buf", 0)
+                t = [float(x) for x in stamps.cpu().numpy()]
+                total = max(1.0, sum(t))
+                out[f"{tag}_mode{mode}_slots"] = eng.get_option("last_align_affine_slots")
+                out[f"{tag}_mode{mode}_slot_bytes"] = eng.get_option("last_align_affine_slot_bytes")
+                if mode == 0:
+                    out[f"{tag}_mode0_fill_share"], out[f"{tag}_mode0_walk_share"] = round(t[0] / total, 4), round(t[1] / total, 4)
+                else:
+                    out[f"{tag}_band_rows"] = eng.get_option("last_align_affine_band_rows")
+                    out[f"{tag}_mode1_sweep_share"], out[f"{tag}_mode1_walk_share"], out[f"{tag}_mode1_refill_share"] = (round(x / total, 4) for x in t)
+                out[f"{tag}_mode{mode}_wave_ticks"] = int(sum(t))
+            out[f"{tag}_identical"] = bool(torch.equal(bufs[0][0], bufs[1][0]) and torch.equal(bufs[0][1], bufs[1][1]))
+            for mode in (0, 1):
+                out[f"{tag}_mode{mode}_ms"], out[f"{tag}_mode{mode}_range_ms"] = spread(
+                    lambda: eng.align_affine_device(d_q, len(q), d_db, offs, sub, -11, -1, hits, ops_cap=cap, out=bufs[mode], checkpoint=mode))
+            out[f"{tag}_mode1_over_mode0"] = round(out[f"{tag}_mode1_ms"] / out[f"{tag}_mode0_ms"], 3)
+            out[f"{tag}_hit_len_mean"], out[f"{tag}_hit_len_max"] = round(float(lens[hits].mean()), 1), int(lens[hits].max())
+            out[f"{tag}_ops_mean"] = round(float(bufs[1][0][:, 6].double().mean().item()), 1)
+
     # (a) protein database, log-normal lengths
     q = rng.choice(PROTEIN, args.qlen).astype(np.uint8)
     lens = np.clip(np.round(rng.lognormal(np.log(300), 0.6, args.targets)), 1, 35_000).astype(np.int64)
@@ -303,7 +386,9 @@ def main():
     if args.multi or args.top or args.align_hits:
         if args.multi:
             multi_legs(packed, offs)
-        if args.align_hits:
+        if args.align_hits and args.checkpoint:
+            align_ckpt_leg(q, packed, offs)
+        elif args.align_hits:
             align_hits_leg(packed, offs)
         if args.top:
             top_leg(packed, offs)

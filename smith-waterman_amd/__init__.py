@@ -13,6 +13,7 @@ Names follow the reference (paths relative to the reference repository):
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes
 import os
 import weakref
@@ -548,12 +549,12 @@ class Database:
         return eng._top_views(hits, nhits, nq, top)
 
 
-    def align_affine_hits(self, queries, scoring, hits, nhits=None):
+    def align_affine_hits(self, queries, scoring, hits, nhits=None, checkpoint=None):
         """The alignments of a hit table (sw_db_align_affine_hits): queries and scoring as for search_affine; hits a (nqueries, top, 3)
         int64 array of (target, max_pos, max_score) as search_affine_top returns it -- or (nqueries, top) target indices --, nhits the
         (nqueries,) counts or None for whole rows.  Returns (aln, ops): aln the (nqueries, top, 7) int64 numpy array of (max_pos,
         max_score, q_begin, t_begin, q_end, t_end, nops), all zeros for unused entries and targets outside the database; ops a list per
-        query of `top` bytes objects over b"MID"."""
+        query of `top` bytes objects over b"MID".  checkpoint: the option "align_checkpoint" (0, 1, 2) for this call alone."""
         eng = self.engine
         t = eng.torch
         dev = f"cuda:{eng.device}"
@@ -565,17 +566,18 @@ class Database:
         d_hits = t.from_numpy(hits.reshape(-1).copy() if hits.size else np.zeros(3, np.int64)).to(dev)
         d_nhits = t.from_numpy(nhits.copy()).to(dev) if nhits is not None and len(nhits) else None
         cap = max(1, int(np.diff(qoffs).max(initial=0)) + self.info()["longest"])
-        aln, ops = self.align_affine_hits_device(d_q, qoffs, scoring, d_hits.view(nq, top, 3) if hits.size else d_hits, d_nhits, ops_cap=cap, top=top)
+        aln, ops = self.align_affine_hits_device(d_q, qoffs, scoring, d_hits.view(nq, top, 3) if hits.size else d_hits, d_nhits, ops_cap=cap, top=top,
+                                                 checkpoint=checkpoint)
         eng.synchronize()
         aln = aln.cpu().numpy()
         return aln, _ops_rows(aln, ops.cpu().numpy().reshape(-1, cap), cap, nq, top)
 
-    def align_affine_hits_device(self, d_queries, qoffsets, scoring, hits, nhits, ops_cap: int = 0, out=None, top=None):
+    def align_affine_hits_device(self, d_queries, qoffsets, scoring, hits, nhits, ops_cap: int = 0, out=None, top=None, checkpoint=None):
         """sw_db_align_affine_hits on device-resident queries and a device hit table -- the (nqueries, top, 3) int64 tensor and the
         (nqueries,) counts that search_affine_top_device or Engine.top_hits_device return (nhits may be None: whole rows; `top` is needed
         only where the table's shape does not tell it); asynchronous on torch's current stream, nothing comes to the host.  Returns
         (aln, ops): the (nqueries, top, 7) int64 tensor and the (nqueries, top, ops_cap) uint8 tensor (None with ops_cap = 0:
-        coordinates only); out = (aln, ops) reuses given tensors."""
+        coordinates only); out = (aln, ops) reuses given tensors.  checkpoint: the option "align_checkpoint" for this call alone."""
         eng = self.engine
         t = eng.torch
         qoffs = np.ascontiguousarray(qoffsets, np.int64).reshape(-1)
@@ -599,9 +601,10 @@ class Database:
         if ops is not None and (ops.dtype != t.uint8 or not ops.is_contiguous() or ops.numel() < n * ops_cap):
             raise ValueError(f"out: ops must be a contiguous uint8 tensor of at least {n * ops_cap} elements")
         sub, sc = _affine(*scoring)
-        _check(lib().sw_db_align_affine_hits(eng._h, self._h, d_queries.data_ptr(), qoffs.ctypes.data, nq, ctypes.byref(sc), hits.data_ptr(),
-                                             nhits.data_ptr() if nhits is not None else None, top, aln.data_ptr(),
-                                             ops.data_ptr() if ops is not None else None, ops_cap, eng._stream()))
+        with eng._checkpoint(checkpoint):
+            _check(lib().sw_db_align_affine_hits(eng._h, self._h, d_queries.data_ptr(), qoffs.ctypes.data, nq, ctypes.byref(sc), hits.data_ptr(),
+                                                 nhits.data_ptr() if nhits is not None else None, top, aln.data_ptr(),
+                                                 ops.data_ptr() if ops is not None else None, ops_cap, eng._stream()))
         return (aln.view(-1)[:n * 7].view(nq, max(0, top), 7),
                 ops.view(-1)[:n * ops_cap].view(nq, max(0, top), ops_cap) if ops is not None else None)
 
@@ -639,6 +642,19 @@ class Engine:
 
     def get_option(self, name: str) -> int:
         return int(lib().sw_get_option(self._h, name.encode()))
+
+    @contextlib.contextmanager
+    def _checkpoint(self, mode):
+        """The option "align_checkpoint" set to `mode` for one call and restored after it (None: left as it is)."""
+        if mode is None:
+            yield
+            return
+        before = self.get_option("align_checkpoint")
+        self.set_option("align_checkpoint", mode)
+        try:
+            yield
+        finally:
+            self.set_option("align_checkpoint", before)
 
     def _stream(self):
         return _vp(self.torch.cuda.current_stream(self.device).cuda_stream)
@@ -897,11 +913,12 @@ class Engine:
             db = t.from_numpy(packed.copy() if len(packed) else np.zeros(1, np.uint8)).to(f"cuda:{self.device}")
         return Database(self, db, offsets)
 
-    def align_affine(self, query, targets, submat, gap_open: int, gap_extend: int, hits):
+    def align_affine(self, query, targets, submat, gap_open: int, gap_extend: int, hits, checkpoint=None):
         """The alignments of the targets `hits` (indices, any order, duplicates allowed) under affine scoring
         (sw_align_affine_device): every hit is re-filled with direction bytes and walked by the canonical rule of include/swhip.h.
         Returns (aln, ops): aln an (nhits, 7) int64 numpy array (max_pos, max_score, q_begin, t_begin, q_end, t_end, nops), ops a
-        list of bytes over b"MID" in alignment order."""
+        list of bytes over b"MID" in alignment order.  checkpoint: the option "align_checkpoint" for this call alone (0 whole direction
+        matrices, 1 checkpointed, 2 checkpointed where 0 would refuse the call for size)."""
         t = self.torch
         q = _as_seq(query)
         packed, offs = _pack_targets(targets)
@@ -909,15 +926,17 @@ class Engine:
         d_q = t.from_numpy(q.copy()).to(dev)
         d_db = t.from_numpy(packed.copy() if len(packed) else np.zeros(1, np.uint8)).to(dev)
         hits, cap = _hits_and_cap(offs, hits, len(q))
-        aln, ops = self.align_affine_device(d_q, len(q), d_db, offs, submat, gap_open, gap_extend, hits, ops_cap=cap)
+        aln, ops = self.align_affine_device(d_q, len(q), d_db, offs, submat, gap_open, gap_extend, hits, ops_cap=cap, checkpoint=checkpoint)
         self.synchronize()
         aln = aln.cpu().numpy()
         return aln, _ops_list(aln, ops.cpu().numpy(), cap)
 
-    def align_affine_device(self, d_query, qlen: int, d_db, offsets, submat, gap_open: int, gap_extend: int, hits, ops_cap: int = 0, out=None):
+    def align_affine_device(self, d_query, qlen: int, d_db, offsets, submat, gap_open: int, gap_extend: int, hits, ops_cap: int = 0, out=None,
+                            checkpoint=None):
         """sw_align_affine_device on device-resident query / packed targets (torch uint8 tensors), host int64 offsets, host hits and
         a host table; asynchronous on torch's current stream.  Returns (aln, ops): the (nhits, 7) int64 tensor and the
-        (nhits, ops_cap) uint8 tensor (None with ops_cap = 0: coordinates only); out = (aln, ops) reuses given tensors."""
+        (nhits, ops_cap) uint8 tensor (None with ops_cap = 0: coordinates only); out = (aln, ops) reuses given tensors.
+        checkpoint: the option "align_checkpoint" for this call alone."""
         t = self.torch
         offs = np.ascontiguousarray(offsets, np.int64).reshape(-1)
         if len(offs) == 0:
@@ -927,8 +946,9 @@ class Engine:
         aln, ops = out if out is not None else (t.zeros((max(1, nhits), 7), dtype=t.int64, device=dev),
                                                 t.zeros((max(1, nhits), ops_cap), dtype=t.uint8, device=dev) if ops_cap > 0 else None)
         sub, sc = _affine(submat, gap_open, gap_extend)
-        _check(lib().sw_align_affine_device(self._h, d_query.data_ptr(), qlen, d_db.data_ptr(), offs.ctypes.data, len(offs) - 1, hits.ctypes.data, nhits,
-                                            ctypes.byref(sc), aln.data_ptr(), ops.data_ptr() if ops is not None else None, ops_cap, self._stream()))
+        with self._checkpoint(checkpoint):
+            _check(lib().sw_align_affine_device(self._h, d_query.data_ptr(), qlen, d_db.data_ptr(), offs.ctypes.data, len(offs) - 1, hits.ctypes.data, nhits,
+                                                ctypes.byref(sc), aln.data_ptr(), ops.data_ptr() if ops is not None else None, ops_cap, self._stream()))
         return aln[:nhits], (ops[:nhits] if ops is not None else None)
 
     def traceback(self, out: Fill, max_pos: int | None = None, want_path: bool = True):

@@ -19,6 +19,8 @@
 //                                "T <target letters, '-' where the query has letters of its own>"
 //                              on a linear search (no --matrix / --gap-open) the alignment is that of the table match / mismatch of --scores (signed
 //                              bytes) with gap_open 0 and the gap of --scores: the reference's backtrack() path
+//     ... --align-checkpoint  with --align: option "align_checkpoint" = 2 -- hits (with --all-queries: tables) whose whole direction matrices do not
+//                              fit the workspace are aligned from checkpoint rows in bounded memory, in the same one call; the output is unchanged
 // Extra flags: --seed N  --dump | --dump-labels (the header-row printers of omp_smithW.c)  --h64  --no-backtrack  --scores M X G  --record-a I  --record-b J
 //   --gpus N | --devices 0,1,..   ONE matrix over several GPUs (row bands, sw_multi_*; an id may repeat)  --p8  int8 P
 // The DP fill runs on the GPU through the C-ABI (include/swhip.h); stdout keeps the two
@@ -165,7 +167,7 @@ static int print_hits(sw_ctx* ctx, const char* q, int64_t qlen, const void* d_q,
     return 0;
 }
 
-static int search_main(const char* qpath, long long rec, const char* dbpath, long long top, const sw_scores& sc, const AffineArgs& af, bool align) {
+static int search_main(const char* qpath, long long rec, const char* dbpath, long long top, const sw_scores& sc, const AffineArgs& af, bool align, bool align_ckpt) {
     int64_t qlen = 0, nrec = 0, total = 0;
     CHECK(sw_read_fasta(qpath, rec, nullptr, 0, &qlen));
     std::vector<char> q((size_t)qlen + 1);
@@ -176,6 +178,7 @@ static int search_main(const char* qpath, long long rec, const char* dbpath, lon
     CHECK(sw_read_fasta_db(dbpath, db.data(), total, offs.data(), nrec + 1, &nrec, &total));
     sw_ctx* ctx = nullptr;
     CHECK(sw_create(0, &ctx));
+    if (align_ckpt) CHECK(sw_set_option(ctx, "align_checkpoint", 2));   // hits too large for whole direction matrices are aligned checkpointed
     void *d_q = nullptr, *d_db = nullptr, *d_res = nullptr;
     CHECK(sw_device_malloc(ctx, (size_t)qlen + 16, &d_q));
     CHECK(sw_device_malloc(ctx, (size_t)total + 16, &d_db));
@@ -210,7 +213,8 @@ static int search_main(const char* qpath, long long rec, const char* dbpath, lon
 // best hits of every query are selected on the device and only they come back; more than SW_TOP_MAX hits per query go the long way:
 // the whole table to the host and a sort of every row.  A linear search goes through the match / mismatch table of --scores with
 // gap_open 0, which sw_search_device equals bit for bit.
-static int search_all_main(const char* qpath, const char* dbpath, long long top, long long min_score, const sw_scores& sc, const AffineArgs& af, bool align) {
+static int search_all_main(const char* qpath, const char* dbpath, long long top, long long min_score, const sw_scores& sc, const AffineArgs& af, bool align,
+                           bool align_ckpt) {
     int64_t nq = 0, qtotal = 0, nrec = 0, total = 0;
     CHECK(sw_read_fasta_db(qpath, nullptr, 0, nullptr, 0, &nq, &qtotal));
     std::vector<char> qs((size_t)qtotal + 1);
@@ -224,6 +228,8 @@ static int search_all_main(const char* qpath, const char* dbpath, long long top,
     const bool on_device = K <= SW_TOP_MAX;
     sw_ctx* ctx = nullptr;
     CHECK(sw_create(0, &ctx));
+    // --align-checkpoint: a table the one call would refuse for its worst pair goes through it checkpointed instead of query by query
+    if (align_ckpt) CHECK(sw_set_option(ctx, "align_checkpoint", 2));
     void *d_q = nullptr, *d_db = nullptr, *d_res = nullptr, *d_hits = nullptr, *d_nhits = nullptr;
     const size_t nres = on_device ? 1 : (size_t)std::max<int64_t>(1, nq * nrec), nhit = (size_t)std::max<int64_t>(1, nq * K);
     CHECK(sw_device_malloc(ctx, (size_t)qtotal + 16, &d_q));
@@ -273,6 +279,7 @@ static int search_all_main(const char* qpath, const char* dbpath, long long top,
             const int rc = sw_db_align_affine_hits(ctx, handle, (const char*)d_q, qoffs.data(), nq, &aff, (const sw_hit*)d_hits, (const int64_t*)d_nhits, K,
                                                    (sw_alignment*)d_aln, (char*)d_ops, ops_cap, nullptr);
             if (rc != SW_OK && rc != SW_EINVAL) CHECK(rc);
+            if (rc == SW_EINVAL) fprintf(stderr, "smithW: the one alignment call on the hit table was refused (%s); aligning query by query\n", sw_last_error());
             if (rc == SW_OK) {
                 CHECK(sw_synchronize(ctx, nullptr));
                 aln.resize(n); ops.resize(n * (size_t)ops_cap);
@@ -312,7 +319,7 @@ int main(int argc, char** argv) {
     long long top = 10, min_score = 0;
     bool has_min_score = false;
     AffineArgs af;
-    bool align = false, all_queries = false;
+    bool align = false, all_queries = false, align_ckpt = false;
     sw_scores sc = {3, -3, -2};
     int npos = 0;
     for (int ai = 1; ai < argc; ++ai) {
@@ -337,14 +344,16 @@ int main(int argc, char** argv) {
         else if (f == "--gap-open" && ai + 1 < argc) { if (!parse_int("--gap-open", argv[++ai], &af.open)) return 2; af.has_open = af.on = true; }
         else if (f == "--gap-extend" && ai + 1 < argc) { if (!parse_int("--gap-extend", argv[++ai], &af.extend)) return 2; af.has_extend = true; }
         else if (f == "--align") align = true;
+        else if (f == "--align-checkpoint") align_ckpt = true;
         else if (f == "--all-queries") all_queries = true;
         else if (f == "--record-a" && ai + 1 < argc) rec_a = strtoll(argv[++ai], nullptr, 10);
         else if (f == "--record-b" && ai + 1 < argc) rec_b = strtoll(argv[++ai], nullptr, 10);
         else if (f == "--seed" && ai + 1 < argc) seed = (unsigned)strtoul(argv[++ai], nullptr, 10);
         else if (f == "--scores" && ai + 3 < argc) { sc.match = atoi(argv[++ai]); sc.mismatch = atoi(argv[++ai]); sc.gap = atoi(argv[++ai]); }
-        else { fprintf(stderr, "usage: smithW [<cols> <rows> | --fasta A.fa B.fa [--record-a I] [--record-b J] | --search QUERY.fa DB.fa [--record-a I] [--top K] [--all-queries [--min-score S]] [--matrix FILE] [--gap-open O] [--gap-extend E] [--align]] [--seed N] [--dump | --dump-labels] [--h64] [--no-backtrack] [--scores M X G] [--gpus N | --devices 0,1,..] [--p8]\n"); return 2; }
+        else { fprintf(stderr, "usage: smithW [<cols> <rows> | --fasta A.fa B.fa [--record-a I] [--record-b J] | --search QUERY.fa DB.fa [--record-a I] [--top K] [--all-queries [--min-score S]] [--matrix FILE] [--gap-open O] [--gap-extend E] [--align [--align-checkpoint]]] [--seed N] [--dump | --dump-labels] [--h64] [--no-backtrack] [--scores M X G] [--gpus N | --devices 0,1,..] [--p8]\n"); return 2; }
     }
     if (npos == 1) { fprintf(stderr, "smithW: <cols> needs <rows>\n"); return 2; }
+    if (align_ckpt && !(search_q && align)) { fprintf(stderr, "smithW: --align-checkpoint goes with --search --align\n"); return 2; }
     if (search_q) {
         if (af.on && !af.matrix && (sc.match < -128 || sc.match > 127 || sc.mismatch < -128 || sc.mismatch > 127)) {   // (sw_submat_match would clamp them)
             fprintf(stderr, "smithW: --gap-open without --matrix needs --scores M X within -128..127 (a table of signed bytes), got %d %d\n", sc.match, sc.mismatch);
@@ -360,10 +369,10 @@ int main(int argc, char** argv) {
                 fprintf(stderr, "smithW: --all-queries without --matrix needs --scores M X within -128..127 (a table of signed bytes), got %d %d\n", sc.match, sc.mismatch);
                 return 2;
             }
-            return search_all_main(search_q, search_db, top, min_score, sc, af, align);
+            return search_all_main(search_q, search_db, top, min_score, sc, af, align, align_ckpt);
         }
         if (has_min_score) { fprintf(stderr, "smithW: --min-score goes with --search --all-queries\n"); return 2; }
-        return search_main(search_q, rec_a, search_db, top, sc, af, align);
+        return search_main(search_q, rec_a, search_db, top, sc, af, align, align_ckpt);
     }
     if (all_queries) { fprintf(stderr, "smithW: --all-queries goes with --search\n"); return 2; }
     if (has_min_score) { fprintf(stderr, "smithW: --min-score goes with --search --all-queries\n"); return 2; }

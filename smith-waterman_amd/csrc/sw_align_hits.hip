@@ -103,7 +103,7 @@ __device__ __forceinline__ bool ah_lookup(const AlignHitsBinParams& p, int64_t e
     if (len <= 0) return false;                            // an empty target: the zero alignment
     it.start = start; it.len = (int)len;
     k = t < p.cls_q0[1] ? 0 : (t < p.cls_q0[2] ? 1 : 2);
-    const int64_t bytes = len * (int64_t)d.qpad;
+    const int64_t bytes = p.log_band[k] ? swp::align_ckpt_slot_bytes(len, d.qpad, 1ll << p.log_band[k]) : len * (int64_t)d.qpad;
     tier = 0;
     while (tier + 1 < p.ntiers[k] && bytes > p.bound[k][tier]) ++tier;   // (the top tier holds the worst case: the host has checked that)
     return true;

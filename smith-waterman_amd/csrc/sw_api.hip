@@ -102,6 +102,19 @@ int sw_set_option(sw_ctx* c, const char* name, int64_t v) {
         c->opt_align_workspace_mib = v;
         return SW_OK;
     }
+    if (!strcmp(name, "align_checkpoint")) {
+        if (v < 0 || v > 2) { set_err("align_checkpoint must be 0 (whole direction matrices), 1 (checkpointed) or 2 (checkpointed where 0 would refuse)"); return SW_EINVAL; }
+        c->opt_align_checkpoint = v;
+        return SW_OK;
+    }
+    if (!strcmp(name, "align_checkpoint_rows")) {
+        if (v != 0 && (v < swp::kAlignCkptMinRows || v > swp::kAlignCkptMaxRows || (v & (v - 1)) != 0)) {
+            set_err("align_checkpoint_rows must be 0 (the planner's choice) or a power of two in 64..2^20");
+            return SW_EINVAL;
+        }
+        c->opt_align_checkpoint_rows = v;
+        return SW_OK;
+    }
     if (!strcmp(name, "search_profile_mib")) {
         if (v < 1 || v > (1ll << 20)) { set_err("search_profile_mib must be 1..2^20"); return SW_EINVAL; }
         c->opt_search_profile_mib = v;
@@ -172,6 +185,13 @@ int64_t sw_get_option(sw_ctx* c, const char* name) {
         return n;
     }
     if (!strcmp(name, "align_workspace_mib")) return c->opt_align_workspace_mib;
+    if (!strcmp(name, "align_checkpoint")) return c->opt_align_checkpoint;
+    if (!strcmp(name, "align_checkpoint_rows")) return c->opt_align_checkpoint_rows;
+    if (!strcmp(name, "last_align_affine_checkpointed")) return c->last_align_affine_checkpointed;
+    if (!strcmp(name, "last_align_affine_band_rows")) return c->last_align_affine_band_rows;
+    if (!strcmp(name, "last_align_affine_slot_bytes")) return c->last_align_affine_slot_bytes;
+    if (!strcmp(name, "last_align_hits_checkpointed")) return c->last_align_hits_checkpointed;
+    if (!strcmp(name, "last_align_hits_band_rows")) return c->last_align_hits_band_rows;
     if (!strcmp(name, "search_profile_mib")) return c->opt_search_profile_mib;
     if (!strcmp(name, "last_search_multi_groups")) return c->last_search_multi_groups;
     if (!strcmp(name, "last_search_multi_launches")) return c->last_search_multi_launches;

@@ -51,6 +51,22 @@ static constexpr Indexed<AlignHitsKernel> kAlignHits[] = {
 };
 static_assert(std::size(kAlignHits) == swp::kAlignHitsKernels && at_their_indices(kAlignHits));
 
+// the instantiations of the checkpointed alignment kernels (sw_align_ckpt.hip), picked by swp::plan_align_ckpt / plan_align_hits_ckpt
+using AlignCkptKernel = void (*)(swk::AlignCkptParams);
+static constexpr Indexed<AlignCkptKernel> kAlignCkpt[] = {
+    {swp::align_affine_kernel_index(4), swk::sw_align_ckpt_wave<4>},
+    {swp::align_affine_kernel_index(8), swk::sw_align_ckpt_wave<8>},
+    {swp::align_affine_kernel_index(16), swk::sw_align_ckpt_wave<16>},
+};
+static_assert(std::size(kAlignCkpt) == swp::kAlignAffineKernels && at_their_indices(kAlignCkpt));
+using AlignHitsCkptKernel = void (*)(swk::AlignHitsCkptParams);
+static constexpr Indexed<AlignHitsCkptKernel> kAlignHitsCkpt[] = {
+    {swp::align_hits_kernel_index(4), swk::sw_align_hits_ckpt_wave<4>},
+    {swp::align_hits_kernel_index(8), swk::sw_align_hits_ckpt_wave<8>},
+    {swp::align_hits_kernel_index(16), swk::sw_align_hits_ckpt_wave<16>},
+};
+static_assert(std::size(kAlignHitsCkpt) == swp::kAlignHitsKernels && at_their_indices(kAlignHitsCkpt));
+
 // occupancy of every instantiation of a table at 256 threads, asked once per context: the plans' columns per lane and grids depend on it
 template <typename K, size_t N>
 static int occupancy_once(const Indexed<K> (&tab)[N], int (&per_cu)[N], bool& known) {
@@ -323,8 +339,45 @@ int sw_search_affine_device(sw_ctx* c, const char* d_query, int64_t qlen, const 
     return SW_OK;
 }
 
+// sw_align_affine_device under "align_checkpoint" (csrc/sw_align_ckpt.hip): the caller has checked the arguments and taken the stream.
+static int align_affine_ckpt(sw_ctx* c, const char* d_query, int64_t qlen, const char* d_db, const int64_t* offsets, const int64_t* hits, int64_t nhits,
+                             int64_t maxhit, const sw_affine* scoring, sw_alignment* d_aln, char* d_ops, int64_t ops_cap, hipStream_t stream) {
+    if (int rc = occupancy_once(kAlignCkpt, c->align_ckpt_per_cu, c->align_ckpt_per_cu_known)) return rc;
+    swp::AlignCkptJob aj;
+    aj.qlen = qlen; aj.maxhit = maxhit; aj.nhits = nhits; aj.num_cus = c->num_cus; aj.budget_bytes = c->opt_align_workspace_mib << 20;
+    aj.band_rows = c->opt_align_checkpoint_rows;
+    std::copy(std::begin(c->align_ckpt_per_cu), std::end(c->align_ckpt_per_cu), aj.per_cu);
+    const swp::AlignCkptPlan plan = swp::plan_align_ckpt(aj);
+    if (!plan.fits) {
+        set_err("sw_align_affine_device: the checkpointed slot of the longest hit (%lld rows against %lld padded columns in bands of %lld rows = %lld bytes) "
+                "does not fit align_workspace_mib = %lld (or the 2 GiB a slot may take)", (long long)maxhit, (long long)plan.qpad, (long long)plan.band_rows,
+                (long long)plan.slot_bytes, (long long)c->opt_align_workspace_mib);
+        return SW_EINVAL;
+    }
+    if (c->align_ckpt_per_cu[plan.kernel] < 1) { set_err("the checkpointed alignment kernel does not fit a CU on this device"); return SW_EDEVICE; }
+    if (int rc = stage_search_call(c, stream, (size_t)nhits, plan.prof_need, plan.bnd_need, scoring->sub)) return rc;
+    bool fresh = false;   // (the direction workspace: a band and its checkpoint rows per slot)
+    if (int rc = grow_workspace((void**)&c->d_adir, c->adir_cap, plan.dir_need, 1, 0, stream, fresh)) return rc;
+    swp::align_schedule(offsets, hits, nhits, c->h_sitems);
+    if (int rc = upload_search_call(c, stream, (size_t)nhits, scoring->sub)) return rc;
+    hipLaunchKernelGGL(swk::sw_search_profile_submat, dim3((unsigned)plan.prof_blocks), dim3(256), 0, stream, (const unsigned char*)d_query, qlen,
+                       plan.qpad, c->d_sprof, (const signed char*)c->d_submat);
+    HIP_TRY(hipGetLastError());
+    swk::AlignCkptParams ap = search_params<swk::AlignCkptParams>(c, d_db, nhits, qlen, plan);
+    ap.ge = scoring->gap_extend; ap.goe = scoring->gap_open + scoring->gap_extend;
+    ap.dir = c->d_adir; ap.slot_bytes = plan.slot_bytes; ap.nslots = plan.slots; ap.log_band = plan.log_band;
+    ap.aln = d_aln; ap.ops = d_ops; ap.ops_cap = ops_cap;
+    ap.stamps = (unsigned long long*)(uintptr_t)c->opt_dbg_ptr;
+    hipLaunchKernelGGL(kAlignCkpt[plan.kernel].k, dim3((unsigned)plan.grid), dim3(256), 0, stream, ap);
+    HIP_TRY(hipGetLastError());
+    c->last_align_affine_kernel = plan.kernel; c->last_align_affine_slots = plan.slots;
+    c->last_align_affine_checkpointed = 1; c->last_align_affine_band_rows = plan.band_rows; c->last_align_affine_slot_bytes = plan.slot_bytes;
+    return SW_OK;
+}
+
 // The alignment of chosen hits under affine scoring (csrc/sw_align_affine.hip).  The shape of sw_search_affine_device: no host round
 // trip, the order of the hits and the table are uploaded from pinned copies, the profile is built on the device; the plan decides.
+// "align_checkpoint" decides once, here, before any launch, whether the call runs on whole direction matrices or checkpointed.
 int sw_align_affine_device(sw_ctx* c, const char* d_query, int64_t qlen, const char* d_db, const int64_t* offsets, int64_t ntargets,
                            const int64_t* hits, int64_t nhits, const sw_affine* scoring, sw_alignment* d_aln, char* d_ops, int64_t ops_cap,
                            void* stream_) {
@@ -342,6 +395,9 @@ int sw_align_affine_device(sw_ctx* c, const char* d_query, int64_t qlen, const c
     aj.qlen = qlen; aj.maxhit = maxhit; aj.nhits = nhits; aj.num_cus = c->num_cus; aj.budget_bytes = c->opt_align_workspace_mib << 20;
     std::copy(std::begin(c->align_affine_per_cu), std::end(c->align_affine_per_cu), aj.per_cu);
     const swp::AlignAffinePlan plan = swp::plan_align_affine(aj);
+    c->last_align_affine_checkpointed = c->last_align_affine_band_rows = 0;
+    if (swp::align_use_ckpt(c->opt_align_checkpoint, plan.fits))
+        return align_affine_ckpt(c, d_query, qlen, d_db, offsets, hits, nhits, maxhit, scoring, d_aln, d_ops, ops_cap, stream);
     if (!plan.fits) {
         set_err("sw_align_affine_device: the direction matrix of the longest hit (%lld rows x %lld bytes = %lld bytes) does not fit align_workspace_mib = %lld "
                 "(or the 2 GiB a slot may take)", (long long)maxhit, (long long)plan.qpad, (long long)plan.slot_bytes, (long long)c->opt_align_workspace_mib);
@@ -363,7 +419,7 @@ int sw_align_affine_device(sw_ctx* c, const char* d_query, int64_t qlen, const c
     ap.stamps = (unsigned long long*)(uintptr_t)c->opt_dbg_ptr;
     hipLaunchKernelGGL(kAlignAffine[plan.kernel].k, dim3((unsigned)plan.grid), dim3(256), 0, stream, ap);
     HIP_TRY(hipGetLastError());
-    c->last_align_affine_kernel = plan.kernel; c->last_align_affine_slots = plan.slots;
+    c->last_align_affine_kernel = plan.kernel; c->last_align_affine_slots = plan.slots; c->last_align_affine_slot_bytes = plan.slot_bytes;
     return SW_OK;
 }
 
@@ -499,6 +555,7 @@ int sw_db_align_affine_hits(sw_ctx* c, const sw_db* db, const char* d_queries, c
     if (int rc = swh::check_search_multi("sw_db_align_affine_hits", qoffsets, nqueries, db->longest, scoring, &maxq)) return rc;
     if (int rc = swh::check_align_hits("sw_db_align_affine_hits", top, d_hits, d_aln, d_ops, ops_cap)) return rc;
     c->last_align_hits_launches = c->last_align_hits_tiers = c->last_align_hits_slots = 0;   // (a call that launches no alignment reports none)
+    c->last_align_hits_checkpointed = c->last_align_hits_band_rows = 0;
     if (nqueries == 0) return SW_OK;
     hipStream_t stream = (hipStream_t)stream_;
     HIP_TRY(hipSetDevice(c->device));
@@ -509,8 +566,23 @@ int sw_db_align_affine_hits(sw_ctx* c, const sw_db* db, const char* d_queries, c
     aj.qlens = qlens.data(); aj.nqueries = nqueries; aj.top = top; aj.longest = db->longest; aj.num_cus = c->num_cus;
     aj.profile_budget_bytes = c->opt_search_profile_mib << 20; aj.budget_bytes = c->opt_align_workspace_mib << 20;
     std::copy(std::begin(c->align_hits_per_cu), std::end(c->align_hits_per_cu), aj.per_cu);
-    const swp::AlignHitsPlan plan = swp::plan_align_hits(aj);
-    if (!plan.fits) {   // decided from host data alone, whatever the table names
+    swp::AlignHitsPlan plan = swp::plan_align_hits(aj);
+    // "align_checkpoint": decided once, from host data alone, before any launch
+    const bool ckpt = swp::align_use_ckpt(c->opt_align_checkpoint, plan.fits);
+    if (ckpt) {
+        if (int rc = occupancy_once(kAlignHitsCkpt, c->align_hits_ckpt_per_cu, c->align_hits_ckpt_per_cu_known)) return rc;
+        swp::AlignHitsCkptJob cj;
+        static_cast<swp::AlignHitsJob&>(cj) = aj;
+        std::copy(std::begin(c->align_hits_ckpt_per_cu), std::end(c->align_hits_ckpt_per_cu), cj.per_cu);
+        cj.band_rows = c->opt_align_checkpoint_rows;
+        plan = swp::plan_align_hits_ckpt(cj);
+        if (!plan.fits) {
+            set_err("sw_db_align_affine_hits: the checkpointed slot of the handle's longest target against the longest query (%lld rows against %lld padded "
+                    "columns = %lld bytes) does not fit align_workspace_mib = %lld (or the 2 GiB a slot may take)", (long long)std::max<int64_t>(1, db->longest),
+                    (long long)plan.worst_qpad, (long long)plan.worst_bytes, (long long)c->opt_align_workspace_mib);
+            return SW_EINVAL;
+        }
+    } else if (!plan.fits) {   // decided from host data alone, whatever the table names
         set_err("sw_db_align_affine_hits: the direction matrix of the handle's longest target against the longest query (%lld rows x %lld bytes = %lld bytes) "
                 "does not fit align_workspace_mib = %lld (or the 2 GiB a slot may take)", (long long)std::max<int64_t>(1, db->longest), (long long)plan.worst_qpad,
                 (long long)plan.worst_bytes, (long long)c->opt_align_workspace_mib);
@@ -523,7 +595,7 @@ int sw_db_align_affine_hits(sw_ctx* c, const sw_db* db, const char* d_queries, c
         return SW_OK;
     }
     for (const swp::AlignHitsLaunch& l : plan.launch)
-        if (c->align_hits_per_cu[l.kernel] < 1) { set_err("the hit-table alignment kernel does not fit a CU on this device"); return SW_EDEVICE; }
+        if ((ckpt ? c->align_hits_ckpt_per_cu : c->align_hits_per_cu)[l.kernel] < 1) { set_err("the hit-table alignment kernel does not fit a CU on this device"); return SW_EDEVICE; }
     if (int rc = stage_search_call(c, stream, 0, plan.prof_need, plan.bnd_need, scoring->sub)) return rc;
     if (int rc = grow_query_table(c, (size_t)nqueries, stream)) return rc;
     bool fresh = false;
@@ -558,6 +630,7 @@ int sw_db_align_affine_hits(sw_ctx* c, const sw_db* db, const char* d_queries, c
         for (int k = 0; k < swp::kAlignHitsKernels; ++k) {
             bp.cls_q0[k] = grp.cls[k].q0 - grp.q0;
             bp.ntiers[k] = grp.cls[k].ntiers;
+            bp.log_band[k] = grp.cls[k].log_band;
             std::copy(std::begin(grp.cls[k].bound), std::end(grp.cls[k].bound), bp.bound[k]);
         }
         bp.cls_q0[swp::kAlignHitsKernels] = grp.nq;
@@ -569,6 +642,23 @@ int sw_db_align_affine_hits(sw_ctx* c, const sw_db* db, const char* d_queries, c
         HIP_TRY(hipGetLastError());
         for (; li < plan.launch.size() && plan.launch[li].group == (int)g; ++li) {
             const swp::AlignHitsLaunch& l = plan.launch[li];
+            if (ckpt) {
+                swk::AlignHitsCkptParams kp;
+                memset(&kp, 0, sizeof kp);
+                kp.db = (const unsigned char*)db->d_db;
+                kp.items = c->d_ahitems + grp.cls[l.kernel].item0;
+                kp.counts = c->d_ahctl->count[l.kernel]; kp.tier = l.tier;
+                kp.queries = c->d_mq + grp.q0; kp.prof = c->d_sprof;
+                kp.ge = scoring->gap_extend; kp.goe = scoring->gap_open + scoring->gap_extend;
+                kp.bnd = l.bnd_per ? c->d_sbnd : nullptr; kp.bnd_per = l.bnd_per;
+                kp.counter = &c->d_ahctl->work[l.kernel][l.tier];
+                kp.dir = c->d_adir; kp.slot_bytes = l.slot_bytes; kp.nslots = l.slots; kp.log_band = l.log_band;
+                kp.aln = d_aln; kp.ops = d_ops; kp.ops_cap = ops_cap;
+                hipLaunchKernelGGL(kAlignHitsCkpt[l.kernel].k, dim3((unsigned)l.grid), dim3(256), 0, stream, kp);
+                HIP_TRY(hipGetLastError());
+                c->last_align_hits_band_rows = std::max<int64_t>(c->last_align_hits_band_rows, 1ll << l.log_band);
+                continue;
+            }
             swk::AlignHitsParams ap;
             memset(&ap, 0, sizeof ap);
             ap.db = (const unsigned char*)db->d_db;
@@ -585,6 +675,7 @@ int sw_db_align_affine_hits(sw_ctx* c, const sw_db* db, const char* d_queries, c
         }
     }
     c->last_align_hits_launches = (int64_t)(3 * plan.group.size() + plan.launch.size()); c->last_align_hits_tiers = plan.tiers; c->last_align_hits_slots = plan.slots;
+    c->last_align_hits_checkpointed = ckpt ? 1 : 0;
     return SW_OK;
 }
 

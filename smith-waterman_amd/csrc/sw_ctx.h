@@ -112,6 +112,14 @@ struct SW_HIDDEN sw_ctx {
     int64_t last_align_affine_kernel = 0, last_align_affine_slots = 0;
     int align_affine_per_cu[swp::kAlignAffineKernels] = {};     // occupancy of every sw_align_affine_wave instantiation at 256 threads ...
     bool align_affine_per_cu_known = false;                     // ... queried at the first call
+    // checkpointed alignment (sw_align_ckpt.hip) of both alignment calls: 0 whole matrices, 1 always, 2 where 0 would refuse for size
+    int64_t opt_align_checkpoint = 0, opt_align_checkpoint_rows = 0;
+    int64_t last_align_affine_checkpointed = 0, last_align_affine_band_rows = 0, last_align_affine_slot_bytes = 0;
+    int64_t last_align_hits_checkpointed = 0, last_align_hits_band_rows = 0;
+    int align_ckpt_per_cu[swp::kAlignAffineKernels] = {};       // occupancy of every sw_align_ckpt_wave instantiation at 256 threads ...
+    bool align_ckpt_per_cu_known = false;                       // ... queried at the first checkpointed call
+    int align_hits_ckpt_per_cu[swp::kAlignHitsKernels] = {};    // likewise sw_align_hits_ckpt_wave
+    bool align_hits_ckpt_per_cu_known = false;
     // alignment of the hits of many queries (sw_db_align_affine_hits): the item list of a group and the control words of its lists; the
     // profiles, the boundary columns, the query table and the direction workspace are those of the calls above
     swk::AlignHitItem* d_ahitems = nullptr; size_t ahitems_cap = 0;

@@ -216,6 +216,7 @@ struct AlignHitsBinParams {
     int64_t nq;
     int64_t cls_q0[SW_AH_CLASSES + 1];           // class k: entries cls_q0[k] .. cls_q0[k + 1] - 1 of `queries`, items from cls_q0[k] * top on
     int ntiers[SW_AH_CLASSES]; int64_t bound[SW_AH_CLASSES][SW_AH_TIERS];   // ascending bounds of the class's tiers (bytes of a direction matrix)
+    int log_band[SW_AH_CLASSES];                 // 0: an item takes len x qpad bytes; else swp::align_ckpt_slot_bytes at 2^log_band rows (sw_align_ckpt.hip)
     AlignHitsCtl* ctl;
     AlignHitItem* items;                         // nq * top at most
     sw_alignment* aln;                           // entries that yield the zero alignment are written here
@@ -239,6 +240,42 @@ struct AlignHitsParams {
 };
 template <int C>
 __global__ void sw_align_hits_wave(AlignHitsParams p);
+
+// sw_align_ckpt.hip: the same alignments in bounded memory ("align_checkpoint"): a slot holds one band of 2^log_band rows of direction
+// bytes and, behind it, a checkpoint row per band boundary (swp::align_ckpt_slot_bytes; swp::plan_align_ckpt, plan_align_hits_ckpt)
+struct AlignCkptParams {                 // the hits of one query, from the host-built list: AlignAffineParams and the band
+    const unsigned char* db;
+    const SearchItem* items; int64_t nitems;
+    const signed char* prof; int64_t qpad;
+    int64_t qlen;
+    int ge, goe;
+    int* bnd; int64_t bnd_per;           // per slot: boundary pairs (H, F) between the strips of ONE BAND (ints), only when qlen > 64 * C
+    unsigned int* counter;
+    unsigned char* dir; int64_t slot_bytes, nslots;   // per slot and hit: min(2^log_band, len) x qpad direction bytes, then the checkpoint rows
+    int log_band;
+    sw_alignment* aln;
+    char* ops; int64_t ops_cap;
+    unsigned long long* stamps;          // optional timing aid, three words: += ticks in the sweep, in the walk, in the walk's re-fills
+};
+template <int C>
+__global__ void sw_align_ckpt_wave(AlignCkptParams p);
+struct AlignHitsCkptParams {             // the items of a device hit table, from the lists of sw_align_hits_bin: AlignHitsParams and the band
+    const unsigned char* db;
+    const AlignHitItem* items;
+    const unsigned int* counts;
+    int tier;
+    const MultiQuery* queries;
+    const signed char* prof;
+    int ge, goe;
+    int* bnd; int64_t bnd_per;
+    unsigned int* counter;
+    unsigned char* dir; int64_t slot_bytes, nslots;   // per slot: room for a band of 2^log_band rows x the item's qpad and its checkpoint rows
+    int log_band;
+    sw_alignment* aln;
+    char* ops; int64_t ops_cap;
+};
+template <int C>
+__global__ void sw_align_hits_ckpt_wave(AlignHitsCkptParams p);
 
 template <typename HT, int B>
 __global__ void sw_strip_scan(const unsigned char* a, const unsigned char* b, FillParams p);

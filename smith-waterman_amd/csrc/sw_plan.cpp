@@ -482,7 +482,6 @@ SearchTopPlan plan_search_top(const SearchTopJob& j) {
 // The direction fill carries the search kernel's state plus the packed bytes of a row; the thresholds of the search hold for the same
 // reasons (plan_search_affine).  A slot is a whole direction matrix of the longest hit, so that any hit runs in any slot; the waves
 // take hits from a counter, longest first, and a call with more hits than slots simply keeps its waves busy longer.
-constexpr int64_t kAlignSlotLimit = (1ll << 31) - 256;   // a slot is addressed through one buffer descriptor with 32-bit offsets
 
 AlignAffinePlan plan_align_affine(const AlignAffineJob& j) {
     using swk::SW_SEARCH_ROWS;
@@ -507,10 +506,48 @@ AlignAffinePlan plan_align_affine(const AlignAffineJob& j) {
     return a;
 }
 
+AlignCkptBand align_ckpt_band(int64_t len, int64_t qpad, int64_t forced_rows, int64_t budget_bytes) {
+    AlignCkptBand best;
+    for (int64_t B = forced_rows ? forced_rows : kAlignCkptFloorRows; B <= (forced_rows ? forced_rows : kAlignCkptMaxRows); B *= 2) {
+        const int64_t bytes = align_ckpt_slot_bytes(len, qpad, B);
+        if (best.rows == 0 || bytes <= best.slot_bytes) { best.rows = B; best.slot_bytes = bytes; }
+    }
+    while ((1ll << best.log_rows) < best.rows) ++best.log_rows;
+    best.fits = best.slot_bytes <= budget_bytes && best.slot_bytes <= kAlignSlotLimit;
+    return best;
+}
+
+// plan_align_affine with the slot of align_ckpt_band and a boundary column of one band's rows.
+AlignCkptPlan plan_align_ckpt(const AlignCkptJob& j) {
+    using swk::SW_SEARCH_ROWS;
+    AlignCkptPlan a;
+    a.C = lane_columns(j.qlen);
+    if (a.C == 16 && j.per_cu[align_affine_kernel_index(16)] < kAffineC16MinPerCu) a.C = 8;
+    a.kernel = align_affine_kernel_index(a.C);
+    a.nstrips = (j.qlen + 64 * a.C - 1) / (64 * a.C);
+    a.qpad = a.nstrips * 64 * a.C;
+    const AlignCkptBand band = align_ckpt_band(j.maxhit, a.qpad, j.band_rows, j.budget_bytes);
+    a.band_rows = band.rows; a.log_band = band.log_rows;
+    a.bnd_per = 2 * boundary_ints(a.nstrips, std::min(band.rows, std::max<int64_t>(1, j.maxhit)));
+    a.slot_bytes = band.slot_bytes;
+    a.fits = band.fits;
+    a.prof_need = (size_t)(SW_SEARCH_ROWS * a.qpad);
+    a.prof_blocks = (int)std::min<int64_t>((SW_SEARCH_ROWS * a.qpad + 255) / 256, kProfileBlocks);
+    if (!a.fits) return a;
+    a.slots = std::min<int64_t>({j.nhits, (int64_t)j.per_cu[a.kernel] * j.num_cus * 4, j.budget_bytes / a.slot_bytes});
+    if (a.bnd_per) a.slots = std::min<int64_t>(a.slots, kSearchBndBytes / (a.bnd_per * 4));
+    a.slots = std::max<int64_t>(1, a.slots);
+    a.grid = (a.slots + 3) / 4;
+    a.bnd_need = (size_t)(a.slots * a.bnd_per);
+    a.dir_need = (size_t)(a.slots * a.slot_bytes);
+    return a;
+}
+
 // The hits of many queries from a device table.  Host work is O(nqueries): the loop of plan_search_multi over the queries, with the
 // entry bound as a second reason to close a group, and per group a constant number of tiers and launches.  Nothing here depends on
 // which targets the table names; the counts of items are products of int64 counts, never sums over items.
-AlignHitsPlan plan_align_hits(const AlignHitsJob& j) {
+// ckpt: the sizes are align_ckpt_slot_bytes at the class's band height instead of len x qpad (plan_align_hits_ckpt).
+static AlignHitsPlan plan_align_hits_sized(const AlignHitsJob& j, bool ckpt, int64_t band_rows) {
     using swk::SW_SEARCH_ROWS;
     AlignHitsPlan a;
     const int64_t n = j.nqueries, top = std::max<int64_t>(1, j.top), rows = std::max<int64_t>(1, j.longest);
@@ -521,8 +558,14 @@ AlignHitsPlan plan_align_hits(const AlignHitsJob& j) {
     };
     auto padded = [&](int64_t qlen) { const int64_t w = 64 * columns(qlen); return (qlen + w - 1) / w * w; };
     for (int64_t q = 0; q < n; ++q) a.worst_qpad = std::max(a.worst_qpad, padded(j.qlens[q]));
-    a.worst_bytes = rows * a.worst_qpad;
-    a.fits = a.worst_bytes <= j.budget_bytes && a.worst_bytes <= kAlignSlotLimit;
+    if (ckpt) {   // (a slot grows with qpad at every band height: the widest query's smallest slot is the call's worst)
+        const AlignCkptBand worst = align_ckpt_band(rows, a.worst_qpad, band_rows, j.budget_bytes);
+        a.worst_bytes = worst.slot_bytes;
+        a.fits = worst.fits;
+    } else {
+        a.worst_bytes = rows * a.worst_qpad;
+        a.fits = a.worst_bytes <= j.budget_bytes && a.worst_bytes <= kAlignSlotLimit;
+    }
     if (!a.fits) return a;
     a.table.resize((size_t)n);
     const int64_t group_queries = std::max<int64_t>(1, std::max<int64_t>(1, j.max_items) / top);
@@ -557,7 +600,9 @@ AlignHitsPlan plan_align_hits(const AlignHitsJob& j) {
             if (c.nq == 0) continue;
             const int C = k == 0 ? 4 : 8 * k;
             int64_t down[kAlignHitsTiers];
-            down[0] = rows * c.qpad;
+            const AlignCkptBand band = ckpt ? align_ckpt_band(rows, c.qpad, band_rows, j.budget_bytes) : AlignCkptBand{};
+            c.log_band = band.log_rows;
+            down[0] = ckpt ? band.slot_bytes : rows * c.qpad;
             for (c.ntiers = 1; c.ntiers < kAlignHitsTiers && down[c.ntiers - 1] / kAlignHitsTierRatio >= kAlignHitsTierFloor; ++c.ntiers)
                 down[c.ntiers] = down[c.ntiers - 1] / kAlignHitsTierRatio;
             for (int t = 0; t < c.ntiers; ++t) c.bound[t] = down[c.ntiers - 1 - t];
@@ -565,8 +610,10 @@ AlignHitsPlan plan_align_hits(const AlignHitsJob& j) {
                 AlignHitsLaunch l;
                 l.group = (int)a.group.size(); l.C = C; l.kernel = k; l.tier = t;
                 l.slot_bytes = c.bound[t];
+                l.log_band = c.log_band;
                 // a query of several strips is at least two strips wide: that bounds the rows of a tier's items that cross a boundary
-                l.bnd_per = 2 * boundary_ints(c.nstrips, std::min(rows, c.bound[t] / (2 * 64 * C)));
+                // (ckpt: a boundary column is one band's)
+                l.bnd_per = 2 * boundary_ints(c.nstrips, ckpt ? std::min(rows, band.rows) : std::min(rows, c.bound[t] / (2 * 64 * C)));
                 l.slots = std::min<int64_t>({c.entries, (int64_t)j.per_cu[k] * j.num_cus * 4, j.budget_bytes / l.slot_bytes});
                 if (l.bnd_per) l.slots = std::min<int64_t>(l.slots, kSearchBndBytes / (l.bnd_per * 4));
                 l.slots = std::max<int64_t>(1, l.slots);
@@ -583,6 +630,9 @@ AlignHitsPlan plan_align_hits(const AlignHitsJob& j) {
     a.tiers = (int64_t)a.launch.size();
     return a;
 }
+
+AlignHitsPlan plan_align_hits(const AlignHitsJob& j) { return plan_align_hits_sized(j, false, 0); }
+AlignHitsPlan plan_align_hits_ckpt(const AlignHitsCkptJob& j) { return plan_align_hits_sized(j, true, j.band_rows); }
 
 void align_schedule(const int64_t* offsets, const int64_t* hits, int64_t nhits, swk::SearchItem* items) {
     std::vector<int64_t> order((size_t)nhits);

@@ -327,6 +327,7 @@ struct AlignHitsClass {
     int64_t item0 = 0, entries = 0;          // its part of the group's item list: first item, nq * top items at most
     int64_t qpad = 0, nstrips = 0;           // the largest padded query length and the most strips among its queries
     int ntiers = 0;                          // 0: no query of this class in the group
+    int log_band = 0;                        // plan_align_hits_ckpt: band height 2^log_band rows, the bounds are align_ckpt_slot_bytes (0: len x qpad)
     int64_t bound[kAlignHitsTiers] = {};     // ascending: tier t holds the items of at most bound[t] bytes (and more than bound[t - 1])
 };
 struct AlignHitsGroup {
@@ -335,6 +336,7 @@ struct AlignHitsGroup {
 };
 struct AlignHitsLaunch {
     int group = 0, C = 0, kernel = 0, tier = 0;
+    int log_band = 0;                        // plan_align_hits_ckpt: the class's band height, 2^log_band rows (0: whole matrices)
     int64_t slot_bytes = 0, slots = 0;       // the tier's bound; waves at work, each with its own slot
     int64_t bnd_per = 0;                     // per slot: boundary pairs between strips (ints), 0: every query of the class has one strip
     int64_t grid = 0;                        // workgroups of 4 waves
@@ -351,6 +353,53 @@ struct AlignHitsPlan {
 };
 
 AlignHitsPlan plan_align_hits(const AlignHitsJob& job);
+
+// ---- checkpointed alignment ("align_checkpoint"; sw_align_ckpt.hip): the same alignments from a slot that holds ONE band of B rows
+// of direction bytes and a checkpoint row (H and E of every column, 8 bytes each) per band boundary, instead of len x qpad bytes.
+// B is a power of two in [kAlignCkptMinRows, kAlignCkptMaxRows]; len <= B is one band, no checkpoint: the whole-matrix layout.
+constexpr int64_t kAlignCkptMinRows = 64, kAlignCkptMaxRows = 1 << 20;
+// The planner's own choice never goes below this: a band pays the 63 steps of lane skew whatever its height -- 20 % of its steps at
+// 256 rows, 50 % at 64.  Reasoned from that ratio, not measured.  ("align_checkpoint_rows" may force less: the tests do.)
+constexpr int64_t kAlignCkptFloorRows = 256;
+constexpr int64_t kAlignSlotLimit = (1ll << 31) - 256;   // a slot is addressed through buffer descriptors with 32-bit offsets
+
+// Bytes of a slot for a hit of `len` rows (an empty hit counts as one row) against a query padded to qpad, at band height B.  The one
+// statement of the layout: the planners size by it, the binning kernels sort by it, sw_align_ckpt.hip lays a slot out by it.
+constexpr int64_t align_ckpt_slot_bytes(int64_t len, int64_t qpad, int64_t B) {
+    const int64_t rows = len < 1 ? 1 : len;
+    return qpad * ((rows < B ? rows : B) + 8 * ((rows + B - 1) / B - 1));
+}
+
+// "align_checkpoint": 0 whole matrices, 1 checkpointed, 2 checkpointed for exactly the calls that 0 would refuse for size.
+constexpr bool align_use_ckpt(int64_t mode, bool whole_fits) { return mode == 1 || (mode == 2 && !whole_fits); }
+
+// The band height for hits of at most `len` rows: forced_rows if not 0 (a power of two in range: the caller has checked); otherwise
+// the power of two at or above kAlignCkptFloorRows that makes the slot smallest -- more slots, more hits in flight --, the larger one
+// among equals.  fits: that slot is within the budget and kAlignSlotLimit (no admissible B gives a smaller one).
+struct AlignCkptBand {
+    int64_t rows = 0; int log_rows = 0;
+    int64_t slot_bytes = 0;
+    bool fits = false;
+};
+AlignCkptBand align_ckpt_band(int64_t len, int64_t qpad, int64_t forced_rows, int64_t budget_bytes);
+
+struct AlignCkptJob : AlignAffineJob {       // per_cu: of the sw_align_ckpt_wave instantiations
+    int64_t band_rows = 0;                   // "align_checkpoint_rows": 0 = the planner's choice
+};
+struct AlignCkptPlan : AlignAffinePlan {     // slot_bytes: align_ckpt_slot_bytes of the longest hit; bnd_per: of one band's rows
+    int64_t band_rows = 0; int log_band = 0;
+};
+AlignCkptPlan plan_align_ckpt(const AlignCkptJob& job);
+
+// The hit-table call, checkpointed: plan_align_hits with another size function.  Every class of a group gets one band height, chosen
+// for the handle's longest target and the class's largest padded query; its top tier is the slot of that worst case, the lower tiers
+// follow by kAlignHitsTierRatio / kAlignHitsTierFloor, and an item goes to the smallest tier that holds align_ckpt_slot_bytes(its
+// length, its query's qpad, the class's band).  A boundary column is a band's.  Fits: the worst case's smallest slot fits; worst_bytes
+// is that slot.  per_cu: of the sw_align_hits_ckpt_wave instantiations.
+struct AlignHitsCkptJob : AlignHitsJob {
+    int64_t band_rows = 0;                   // "align_checkpoint_rows": 0 = the planner's choice
+};
+AlignHitsPlan plan_align_hits_ckpt(const AlignHitsCkptJob& job);
 
 // The order of the hits: by decreasing length, ties in the caller's order; items[k].idx is the position in `hits` (empty hits are kept:
 // they get their all-zero alignment from the kernel like any other).

@@ -3,7 +3,7 @@
   * v126/v127 (landing registers of the hand-tracked edge prefetch) appear ONLY in the two asm
     statements that own them;
   * no scratch (spills) in the fill kernels, none at all in the search kernels (sw_search.hip, sw_search_affine.hip, sw_search_multi.hip)
-    and the alignment kernels (sw_align_affine.hip, sw_align_hits.hip), whose work counter is a vector buffer atomic."""
+    and the alignment kernels (sw_align_affine.hip, sw_align_hits.hip, sw_align_ckpt.hip), whose work counter is a vector buffer atomic."""
 import re, subprocess, sys, os, tempfile
 here = os.path.dirname(os.path.abspath(__file__))
 src = os.path.join(here, "..", "smith-waterman_amd", "csrc", "sw_kernels.hip")
@@ -109,5 +109,16 @@ bodies8 = re.findall(r"^(\S*sw_align_hits_wave\S*):[^\n]*\n(.*?)^\.Lfunc_end\d+:
 without8 = [name for name, body in bodies8 if not re.search(r"^\s*buffer_atomic_add ", body, flags=re.M)]
 if nhits != 3 or nbin != 2 or len(bodies8) != nhits or without8:
     print(f"hit-table alignment kernels: expected 3 alignment kernels with a vector buffer atomic work counter and 2 binning kernels ({nhits} + {nbin} kernels, {len(bodies8)} bodies found, none in {without8})"); sys.exit(1)
+# sw_align_ckpt.hip (checkpointed alignment): the alignment kernels' two rules for its three kernels per item source
+s9 = dev_asm("sw_align_ckpt.hip")
+for m in re.finditer(r"\.private_segment_fixed_size:\s*(\d+)", s9):
+    if int(m.group(1)) > 0:
+        print("scratch in use (checkpointed alignment):", m.group(0)); sys.exit(1)
+nckpt = len(re.findall(r"^\s*\.name:\s+\S*sw_align_ckpt_wave", s9, flags=re.M))
+nckpth = len(re.findall(r"^\s*\.name:\s+\S*sw_align_hits_ckpt_wave", s9, flags=re.M))
+bodies9 = re.findall(r"^(\S*sw_align_(?:hits_)?ckpt_wave\S*):[^\n]*\n(.*?)^\.Lfunc_end\d+:", s9, flags=re.M | re.S)
+without9 = [name for name, body in bodies9 if not re.search(r"^\s*buffer_atomic_add ", body, flags=re.M)]
+if nckpt != 3 or nckpth != 3 or len(bodies9) != 6 or without9:
+    print(f"checkpointed alignment kernels: expected 3 + 3 kernels with a vector buffer atomic work counter ({nckpt} + {nckpth} kernels, {len(bodies9)} bodies found, none in {without9})"); sys.exit(1)
 n = len(re.findall(r"global_load_dwordx2 v\[126:127\]", s))
-print(f"check_isa ok: {n} prefetch sites, v126/v127 private; {nprod} producer paths keep v100..v120 private; traceback window v62..v127 private; no scratch; {nsearch} search kernels without scratch; {naffine} affine search kernels without scratch; {nmulti} many-query search kernels without scratch; {nalign} affine alignment kernels without scratch; {nhits} + {nbin} hit-table alignment kernels without scratch")
+print(f"check_isa ok: {n} prefetch sites, v126/v127 private; {nprod} producer paths keep v100..v120 private; traceback window v62..v127 private; no scratch; {nsearch} search kernels without scratch; {naffine} affine search kernels without scratch; {nmulti} many-query search kernels without scratch; {nalign} affine alignment kernels without scratch; {nhits} + {nbin} hit-table alignment kernels without scratch; {nckpt} + {nckpth} checkpointed alignment kernels without scratch")
