@@ -387,6 +387,40 @@ int  sw_align_affine_hits_host(const char* queries, const int64_t* qoffsets, int
                                const int64_t* offsets, int64_t ntargets, const sw_affine* scoring, const sw_hit* hits,
                                const int64_t* nhits, int64_t top, sw_alignment* aln, char* ops, int64_t ops_cap);
 
+/* The scores of a device LIST of (query, target) pairs against a prepared database (csrc/sw_search_pairs.hip): the rescoring stage
+ * behind a pre-filter -- k-mer or seed matching, a previous search round, a clustering step, a re-score under another matrix or other
+ * gap costs --, whose list is typically a fraction of a percent of nqueries x ntargets.  sw_db_search_affine runs the whole cross
+ * product whatever the list's size; this call runs the listed pairs and nothing else, through the same handle.
+ *   d_queries, qoffsets, scoring : as for sw_db_search_affine.
+ *   d_pairs   : device, npairs sw_pair = {query, target}, only read.  Entries may come in any order; duplicates are allowed.
+ *   d_results : device, npairs sw_result, in the order of d_pairs.  Entry p is bit for bit what sw_db_search_affine writes at
+ *               [query * ntargets + target]: the same recurrence, the same arg-max rule, max_pos in that pair's own
+ *               (len + 1) x (qlen + 1) layout.  An entry whose query lies outside [0, nqueries), whose target lies outside
+ *               [0, ntargets) or whose target is empty gives {0, 0, 0}.  An index is compared against its bound, UNSIGNED, before
+ *               anything is loaded through it (the rule of sw_db_align_affine_hits).  Every entry of d_results is written, and
+ *               nothing outside it.
+ * Asynchronous on `stream`, no host round trip.  The host reads neither the pairs nor the targets' offsets; its work is O(nqueries).
+ * The order in which the device takes the pairs may differ between runs, the bytes it writes do not.  npairs == 0 returns SW_OK and
+ * launches nothing; nqueries == 0 launches no kernel either (no entry names a query: the results are zeroed); a handle without a
+ * non-empty target only zeroes the results.  Linear gaps: pass sw_submat_match's table with gap_open = 0, as everywhere in this family.
+ * SW_EINVAL: the argument and scoring errors of sw_db_search_affine, npairs < 0, NULL d_pairs or NULL d_results with npairs > 0.
+ * The list is taken in consecutive chunks of at most "search_pairs_chunk" entries (settable, default 2^22, 1..2^31 - 1): a chunk's work
+ * items take 24 bytes each in a per-context workspace (96 MiB at the default) and its counters stay inside 32 bits; the queries run in
+ * the groups of sw_db_search_affine ("search_profile_mib").  "last_search_pairs_groups", "last_search_pairs_chunks" and
+ * "last_search_pairs_launches" (kernel launches, the profile launches included) describe the last call, all 0 for one that launched
+ * no kernel.
+ * Alignments of listed pairs are not a call of their own: pack the chosen pairs into an nqueries x top sw_hit table and call
+ * sw_db_align_affine_hits.
+ *   sw_search_affine_pairs_host  the CPU leg: every entry as sw_search_affine_host computes that pair, in plain C++ on host memory, no
+ *               GPU needed; every argument is checked before the first pair (SW_EINVAL also for the offsets / length errors of
+ *               sw_search_device). */
+typedef struct { int64_t query, target; } sw_pair;
+int  sw_db_search_affine_pairs(sw_ctx* ctx, const sw_db* db, const char* d_queries, const int64_t* qoffsets, int64_t nqueries,
+                               const sw_affine* scoring, const sw_pair* d_pairs, int64_t npairs, sw_result* d_results, void* stream);
+int  sw_search_affine_pairs_host(const char* queries, const int64_t* qoffsets, int64_t nqueries, const char* db,
+                                 const int64_t* offsets, int64_t ntargets, const sw_affine* scoring, const sw_pair* pairs,
+                                 int64_t npairs, sw_result* results);
+
 /* Tables.  sw_submat_match: s[x][y] = x == y ? match : mismatch (matchMissmatchScore, serial_smithW.c:251-256; both must fit int8:
  * the builder returns nothing, so it clamps them to -128..127 -- a caller that takes them from a user checks the range first, as
  * smithW and the Python wrapper do, which refuse such scores).  sw_submat_from_letters: `scores` is n x n, row = query letter, over the n bytes of
@@ -582,7 +616,11 @@ int sw_synchronize(sw_ctx* ctx, void* stream);   /* waits for `stream`; reports 
  * "last_search_multi_grid" (workgroups of its last launch) describe the last such call; "search_results_mib" (settable, default 1024,
  * 1..2^20) bounds the result rows a chunk of sw_db_search_affine_top holds, "last_search_top_chunks" and "last_search_top_kernel"
  * describe the last sw_db_search_affine_top / sw_top_hits_device call; "last_align_hits_launches", "last_align_hits_tiers",
- * "last_align_hits_slots" and "last_align_hits_lists" the last sw_db_align_affine_hits call. */
+ * "last_align_hits_slots" and "last_align_hits_lists" the last sw_db_align_affine_hits call; "search_pairs_chunk" (settable, default
+ * 2^22, 1..2^31 - 1) is the most entries of a pair list that sw_db_search_affine_pairs bins at a time, "last_search_pairs_groups",
+ * "last_search_pairs_chunks" and "last_search_pairs_launches" describe the last such call.  "debug_search_pairs_items_ptr" (an
+ * accessor for tests) is the device address of that call's item workspace, which a call leaves as its last (chunk, group) filled it:
+ * 24-byte items {int64 start, int64 out, int32 len, int32 entry}, the classes' lists back to back. */
 int sw_set_option(sw_ctx* ctx, const char* name, int64_t value);
 int64_t sw_get_option(sw_ctx* ctx, const char* name);
 

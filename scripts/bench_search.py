@@ -27,6 +27,10 @@
   call on the top 10 / top 100 hits of 64 queries of --qlen, and the sw_align_affine_device call on the top 100 / 1000 hits of one
   query with the waves' tick stamps (mode 0: fill, walk; mode 1: sweep, walk, re-fill).  The outputs of the two modes are compared on
   the device before anything is timed
+  --pairs: data set (a) only, 64 queries of --qlen through one handle, three legs in one process, torch events around the whole call,
+  medians and ranges of --reps after --warmup: (i) sw_db_search_affine over the full cross product, the baseline; (ii)
+  sw_db_search_affine_pairs over a uniform random 1 % of the cross product (fixed seed); (iii) sw_db_search_affine_pairs over the full
+  cross product as an explicit list in random order.  The results of (ii) and (iii) are compared on the device with the table of (i)
 GCUPS = query letters x target letters / time of the call (torch events, median of --reps after --warmup)."""
 import argparse
 import importlib
@@ -72,6 +76,7 @@ def main():
     ap.add_argument("--multi", action="store_true", help="data set (a) only: many queries through a prepared database against one call per query")
     ap.add_argument("--align-hits", action="store_true", help="data set (a) only: the alignments of the top 10 / 100 hits of 64 queries, per query and in one call")
     ap.add_argument("--checkpoint", action="store_true", help="with --align-hits: checkpointed alignment beside the whole-matrix path, hit table and one query")
+    ap.add_argument("--pairs", action="store_true", help="data set (a) only: a pair list of 1 %% and of all of the cross product of 64 queries beside the full search")
     ap.add_argument("--top", action="store_true", help="data set (a) only: the best 100 targets of 64 queries by the full table and by the selection on the device")
     args = ap.parse_args()
     rng = np.random.default_rng(2026)
@@ -312,6 +317,44 @@ def main():
             ms.append(e0.elapsed_time(e1))
         return round(float(np.median(ms)), 3), [round(min(ms), 3), round(max(ms), 3)]
 
+    def pairs_leg(packed, offs, nq=64):
+        d_db = torch.from_numpy(packed.copy()).to(dev)
+        db = eng.prepare_db(d_db, offs)
+        nt = len(offs) - 1
+        lens = np.diff(offs)
+        qoffs = np.arange(nq + 1, dtype=np.int64) * args.qlen
+        d_q = torch.from_numpy(rng.choice(PROTEIN, int(qoffs[-1])).astype(np.uint8)).to(dev)
+        scoring = (sub, -11, -1)
+        prng = np.random.default_rng(7)                                      # (its own generator: the lists do not depend on the other legs)
+        flat_sparse = prng.choice(nq * nt, nq * nt // 100, replace=False).astype(np.int64)
+        flat_full = prng.permutation(nq * nt).astype(np.int64)
+        table = torch.zeros(nq * nt * 3, dtype=torch.int64, device=dev)
+        out["pairs_queries"], out["pairs_qlen"], out["pairs_targets"] = nq, args.qlen, nt
+        out["pairs_full_ms"], out["pairs_full_range_ms"] = spread(lambda: db.search_affine_device(d_q, qoffs, scoring, out=table))
+        cells_full = float(qoffs[-1]) * float(offs[-1] - offs[0])
+        out["pairs_full_cells"] = int(cells_full)
+        out["pairs_full_ps_per_cell"] = round(out["pairs_full_ms"] * 1e9 / cells_full, 4)
+        rows = table.view(nq * nt, 3)
+        for tag, flat in (("sparse", flat_sparse), ("list", flat_full)):
+            pairs = np.stack([flat // nt, flat % nt], axis=1)
+            d_pairs = torch.from_numpy(pairs).to(dev)
+            d_flat = torch.from_numpy(flat).to(dev)
+            res = torch.full((len(flat) * 3,), -1, dtype=torch.int64, device=dev)
+            ms, rng_ms = spread(lambda: db.search_affine_pairs_device(d_q, qoffs, scoring, d_pairs, out=res))
+            cells = float(args.qlen) * float(lens[pairs[:, 1]].sum())
+            out[f"pairs_{tag}_n"], out[f"pairs_{tag}_list_bytes"], out[f"pairs_{tag}_result_bytes"] = len(flat), len(flat) * 16, len(flat) * 24
+            out[f"pairs_{tag}_ms"], out[f"pairs_{tag}_range_ms"] = ms, rng_ms
+            out[f"pairs_{tag}_cells"] = int(cells)
+            out[f"pairs_{tag}_ps_per_cell"] = round(ms * 1e9 / cells, 4)
+            out[f"pairs_{tag}_gcups"] = round(cells / ms / 1e6, 1)
+            out[f"pairs_{tag}_chunks"], out[f"pairs_{tag}_launches"] = eng.get_option("last_search_pairs_chunks"), eng.get_option("last_search_pairs_launches")
+            out[f"pairs_{tag}_identical"] = bool(torch.equal(res.view(len(flat), 3), rows[d_flat]))
+            del d_pairs, d_flat, res
+        out["pairs_sparse_faster_than_full"] = bool(out["pairs_sparse_ms"] < out["pairs_full_ms"])
+        out["pairs_sparse_over_full_ms"] = round(out["pairs_sparse_ms"] / out["pairs_full_ms"], 4)
+        out["pairs_list_over_full_per_cell"] = round(out["pairs_list_ps_per_cell"] / out["pairs_full_ps_per_cell"], 4)
+        db.close()
+
     def align_ckpt_leg(q, packed, offs, nq=64):
         d_db = torch.from_numpy(packed.copy()).to(dev)
         db = eng.prepare_db(d_db, offs)
@@ -383,7 +426,9 @@ def main():
     out["a_letters"] = int(offs[-1])
     out["a_len_median"] = int(np.median(lens))
     out["a_len_max"] = int(lens.max())
-    if args.multi or args.top or args.align_hits:
+    if args.multi or args.top or args.align_hits or args.pairs:
+        if args.pairs:
+            pairs_leg(packed, offs)
         if args.multi:
             multi_legs(packed, offs)
         if args.align_hits and args.checkpoint:
@@ -394,6 +439,10 @@ def main():
             top_leg(packed, offs)
         eng.close()
         print(json.dumps(out))
+        if args.pairs:   # the required conditions of the pair-list call: a line that misses one is printed, and the run fails
+            missed = [k for k in ("pairs_sparse_identical", "pairs_list_identical", "pairs_sparse_faster_than_full") if not out[k]]
+            if missed:
+                sys.exit("bench_search.py --pairs: " + ", ".join(missed) + " is false")
         return
     search_gcups(q, packed, offs, "a")
     align_legs(q, packed, offs, affine_gcups(q, packed, offs, "a"), "a")

@@ -70,6 +70,8 @@ ABI = {
     "sw_db_info": (_i32, [_vp, ctypes.POINTER(_i64), ctypes.POINTER(_i64), ctypes.POINTER(_i64), ctypes.POINTER(_i64)]),
     "sw_db_search_affine": (_i32, [_vp, _vp, _vp, _vp, _i64, ctypes.POINTER(_Affine), _vp, _vp]),
     "sw_search_affine_multi_host": (_i32, [_vp, _vp, _i64, _vp, _vp, _i64, ctypes.POINTER(_Affine), _vp]),
+    "sw_db_search_affine_pairs": (_i32, [_vp, _vp, _vp, _vp, _i64, ctypes.POINTER(_Affine), _vp, _i64, _vp, _vp]),
+    "sw_search_affine_pairs_host": (_i32, [_vp, _vp, _i64, _vp, _vp, _i64, ctypes.POINTER(_Affine), _vp, _i64, _vp]),
     "sw_top_hits_device": (_i32, [_vp, _vp, _i64, _i64, _i64, _i64, _vp, _vp, _vp]),
     "sw_db_search_affine_top": (_i32, [_vp, _vp, _vp, _vp, _i64, ctypes.POINTER(_Affine), _i64, _i64, _vp, _vp, _vp]),
     "sw_search_affine_multi_top_host": (_i32, [_vp, _vp, _i64, _vp, _vp, _i64, ctypes.POINTER(_Affine), _i64, _i64, _vp, _vp]),
@@ -256,6 +258,31 @@ def search_affine_multi_host(queries, targets, scoring):
     _check(lib().sw_search_affine_multi_host(qs.ctypes.data, qoffs.ctypes.data, nq, db.ctypes.data, offs.ctypes.data, ntargets, ctypes.byref(sc),
                                              res.ctypes.data))
     return res[:nq * ntargets].reshape(nq, ntargets, 3)
+
+
+def _pair_list(pairs):
+    """A host pair list as the C-ABI takes it: (npairs, 2) int64 of (query, target), from an array or a list of tuples."""
+    pr = np.asarray(pairs, np.int64)
+    if pr.size == 0:
+        pr = pr.reshape(0, 2)
+    if pr.ndim != 2 or pr.shape[1] != 2:
+        raise ValueError("pairs must be (npairs, 2) int64 of (query, target)")
+    return np.ascontiguousarray(pr)
+
+
+def search_affine_pairs_host(queries, targets, scoring, pairs):
+    """sw_search_affine_pairs_host: the scores of a list of (query, target) pairs in plain C++ on the host (no GPU).  Arguments and
+    result as Database.search_affine_pairs: returns the (npairs, 3) int64 array of (max_pos, max_score, path_len = 0) in list order."""
+    qpacked, qoffs = _pack_targets(queries)
+    packed, offs = _pack_targets(targets)
+    pr = _pair_list(pairs)
+    qs = qpacked if len(qpacked) else np.zeros(1, np.uint8)
+    db = packed if len(packed) else np.zeros(1, np.uint8)
+    res = np.zeros((max(1, len(pr)), 3), np.int64)
+    sub, sc = _affine(*scoring)
+    _check(lib().sw_search_affine_pairs_host(qs.ctypes.data, qoffs.ctypes.data, len(qoffs) - 1, db.ctypes.data, offs.ctypes.data, len(offs) - 1,
+                                             ctypes.byref(sc), pr.ctypes.data if len(pr) else None, len(pr), res.ctypes.data))
+    return res[:len(pr)]
 
 
 def search_affine_multi_top_host(queries, targets, scoring, top: int, min_score: int = 0):
@@ -519,6 +546,42 @@ class Database:
         sub, sc = _affine(*scoring)
         _check(lib().sw_db_search_affine(eng._h, self._h, d_queries.data_ptr(), qoffs.ctypes.data, nq, ctypes.byref(sc), res.data_ptr(), eng._stream()))
         return res[:n].view(nq, self.ntargets, 3)
+
+    def search_affine_pairs(self, queries, scoring, pairs):
+        """The scores of a list of (query, target) pairs (sw_db_search_affine_pairs): queries and scoring as for search_affine; pairs an
+        (npairs, 2) int64 array or a list of (query, target) tuples, any order, duplicates allowed.  Returns the (npairs, 3) int64 numpy
+        array of (max_pos, max_score, path_len = 0) in list order; an entry that names no query, no target or an empty target is zero."""
+        eng = self.engine
+        t = eng.torch
+        dev = f"cuda:{eng.device}"
+        qpacked, qoffs = _pack_targets(queries)
+        pr = _pair_list(pairs)
+        d_q = t.from_numpy(qpacked.copy() if len(qpacked) else np.zeros(1, np.uint8)).to(dev)
+        d_pairs = t.from_numpy(pr.copy() if len(pr) else np.zeros((1, 2), np.int64)).to(dev)[:len(pr)]
+        res = self.search_affine_pairs_device(d_q, qoffs, scoring, d_pairs)
+        eng.synchronize()
+        return res.cpu().numpy()
+
+    def search_affine_pairs_device(self, d_queries, qoffsets, scoring, d_pairs, out=None):
+        """sw_db_search_affine_pairs on device-resident queries and a device pair list, a contiguous torch int64 tensor of shape
+        (npairs, 2); asynchronous on torch's current stream, nothing comes to the host.  Returns the (npairs, 3) int64 result tensor
+        (a view of `out`, a flat int64 tensor of at least npairs * 3 elements, if given)."""
+        eng = self.engine
+        t = eng.torch
+        qoffs = np.ascontiguousarray(qoffsets, np.int64).reshape(-1)
+        if len(qoffs) == 0:
+            qoffs = np.zeros(1, np.int64)
+        if d_pairs.dtype != t.int64 or not d_pairs.is_contiguous() or d_pairs.dim() != 2 or d_pairs.shape[1] != 2:
+            raise ValueError("d_pairs must be a contiguous int64 tensor of shape (npairs, 2)")
+        npairs = d_pairs.shape[0]
+        n = npairs * 3
+        res = out if out is not None else t.zeros(max(3, n), dtype=t.int64, device=f"cuda:{eng.device}")
+        if res.dtype != t.int64 or not res.is_contiguous() or res.numel() < n:
+            raise ValueError(f"out must be a contiguous int64 tensor of at least {n} elements ({npairs} pairs x 3)")
+        sub, sc = _affine(*scoring)
+        _check(lib().sw_db_search_affine_pairs(eng._h, self._h, d_queries.data_ptr(), qoffs.ctypes.data, len(qoffs) - 1, ctypes.byref(sc),
+                                               d_pairs.data_ptr() if npairs else None, npairs, res.data_ptr(), eng._stream()))
+        return res.view(-1)[:n].view(npairs, 3)
 
     def search_affine_top(self, queries, scoring, top: int, min_score: int = 0):
         """The best `top` targets of every query, selected on the device (sw_db_search_affine_top): the full result table never exists

@@ -12,6 +12,10 @@
 //                              --gap-open, --gap-extend and --align (one sw_db_align_affine_hits call on the device hit table) as for one query.  The K best hits per
 //                              query are selected on the device (sw_db_search_affine_top): only they are copied back
 //     ... --min-score S       with --all-queries: only hits with a score of at least S are printed (fewer than K where fewer qualify)
+//     ... --pairs FILE        a LIST of (query, target) pairs through one prepared handle and one call (sw_db_search_affine_pairs): FILE is text, one pair
+//                              per line, "<query record> <target record>", 0-based; '#' lines and blank lines are skipped.  One line per pair in input
+//                              order: query record, target record, the target's name, score, target_end, query_end (a pair outside the files: name "-",
+//                              zeros).  --matrix, --gap-open, --gap-extend or --scores as for --all-queries; not with --all-queries, --top, --min-score, --align
 //     ... --align             every printed hit is followed by its alignment (sw_align_affine_device; the canonical alignment of swhip.h), four lines:
 //                                "align\t<q_begin>\t<q_end>\t<t_begin>\t<t_end>\t<nops>"   query [q_begin, q_end) against target [t_begin, t_end), 0-based, half open
 //                                "Q <query letters, '-' where the target has letters of its own>"
@@ -308,6 +312,111 @@ static int search_all_main(const char* qpath, const char* dbpath, long long top,
     return 0;
 }
 
+// the first word of every record's header line, by the record rule of sw_read_fasta_db (a headerless record is "-")
+static std::vector<std::string> fasta_names(const char* path) {
+    std::vector<std::string> names;
+    FILE* f = fopen(path, "rb");
+    if (!f) return names;
+    char line[1 << 12];
+    bool whole = true;   // the previous fgets ended a line
+    while (fgets(line, sizeof line, f)) {
+        const bool start = whole;
+        const size_t n = strlen(line);
+        whole = n > 0 && (line[n - 1] == '\n' || line[n - 1] == '\r');
+        if (!start || line[0] == ';' || line[0] == '\n' || line[0] == '\r') continue;
+        if (line[0] == '>') { const size_t e = strcspn(line + 1, " \t\r\n"); names.push_back(e ? std::string(line + 1, e) : std::string("-")); }
+        else if (names.empty()) names.push_back("-");
+    }
+    fclose(f);
+    return names;
+}
+
+// --search --pairs FILE: the listed (query record, target record) pairs through ONE prepared handle and one call
+// (sw_db_create / sw_db_search_affine_pairs), one output line per pair in input order.  A linear search goes through the match /
+// mismatch table of --scores with gap_open 0, as --all-queries does.
+static int search_pairs_main(const char* qpath, const char* dbpath, const char* ppath, const sw_scores& sc, const AffineArgs& af) {
+    std::vector<sw_pair> pairs;
+    {
+        FILE* f = fopen(ppath, "r");
+        if (!f) { fprintf(stderr, "smithW: --pairs: cannot open %s\n", ppath); return 2; }
+        char line[512];
+        for (long long ln = 1; fgets(line, sizeof line, f); ++ln) {
+            if (!strchr(line, '\n') && !feof(f)) {   // (a line that does not fit the buffer would be counted twice)
+                fprintf(stderr, "smithW: --pairs %s line %lld: longer than %zu bytes\n", ppath, ln, sizeof line - 2);
+                fclose(f);
+                return 2;
+            }
+            const char* t = line + strspn(line, " \t\r\n");
+            if (*t == 0 || *t == '#') continue;
+            char *e1 = nullptr, *e2 = nullptr;
+            const long long q = strtoll(t, &e1, 10);
+            const long long k = e1 != t ? strtoll(e1, &e2, 10) : 0;
+            if (e1 == t || e2 == e1 || !strchr(" \t", *e1) || e2[strspn(e2, " \t\r\n")] != 0) {
+                fprintf(stderr, "smithW: --pairs %s line %lld: expected \"<query record> <target record>\"\n", ppath, ln);
+                fclose(f);
+                return 2;
+            }
+            pairs.push_back(sw_pair{q, k});
+        }
+        fclose(f);
+    }
+    int64_t nq = 0, qtotal = 0, nrec = 0, total = 0;
+    CHECK(sw_read_fasta_db(qpath, nullptr, 0, nullptr, 0, &nq, &qtotal));
+    std::vector<char> qs((size_t)qtotal + 1);
+    std::vector<int64_t> qoffs((size_t)nq + 1, 0);
+    CHECK(sw_read_fasta_db(qpath, qs.data(), qtotal, qoffs.data(), nq + 1, &nq, &qtotal));
+    CHECK(sw_read_fasta_db(dbpath, nullptr, 0, nullptr, 0, &nrec, &total));
+    std::vector<char> db((size_t)total + 1);
+    std::vector<int64_t> offs((size_t)nrec + 1, 0);
+    CHECK(sw_read_fasta_db(dbpath, db.data(), total, offs.data(), nrec + 1, &nrec, &total));
+    const std::vector<std::string> names = fasta_names(dbpath);
+    if ((int64_t)names.size() != nrec) {   // the two readers must agree on the records, or a name would label another target
+        fprintf(stderr, "smithW: --pairs: %s has %lld records but %zu header names\n", dbpath, (long long)nrec, names.size());
+        return 1;
+    }
+    const int64_t np = (int64_t)pairs.size();
+    sw_ctx* ctx = nullptr;
+    CHECK(sw_create(0, &ctx));
+    void *d_q = nullptr, *d_db = nullptr, *d_pairs = nullptr, *d_res = nullptr;
+    CHECK(sw_device_malloc(ctx, (size_t)qtotal + 16, &d_q));
+    CHECK(sw_device_malloc(ctx, (size_t)total + 16, &d_db));
+    CHECK(sw_device_malloc(ctx, (size_t)std::max<int64_t>(1, np) * sizeof(sw_pair), &d_pairs));
+    CHECK(sw_device_malloc(ctx, (size_t)std::max<int64_t>(1, np) * sizeof(sw_result), &d_res));
+    if (qtotal) CHECK(sw_memcpy_h2d(ctx, d_q, qs.data(), (size_t)qtotal));
+    if (total) CHECK(sw_memcpy_h2d(ctx, d_db, db.data(), (size_t)total));
+    if (np) CHECK(sw_memcpy_h2d(ctx, d_pairs, pairs.data(), (size_t)np * sizeof(sw_pair)));
+    std::vector<sw_submat> sub(1);
+    sw_affine aff = {sub.data(), af.has_open ? af.open : 0, af.has_extend ? af.extend : sc.gap};
+    if (af.matrix) CHECK(sw_read_submat(af.matrix, sub.data()));
+    else sw_submat_match(sc.match, sc.mismatch, sub.data());
+    sw_db* handle = nullptr;
+    const double t0 = now_s();
+    CHECK(sw_db_create(ctx, (const char*)d_db, offs.data(), nrec, &handle));
+    const double t1 = now_s();
+    CHECK(sw_db_search_affine_pairs(ctx, handle, (const char*)d_q, qoffs.data(), nq, &aff, (const sw_pair*)d_pairs, np, (sw_result*)d_res, nullptr));
+    CHECK(sw_synchronize(ctx, nullptr));
+    const double t2 = now_s();
+    std::vector<sw_result> res((size_t)np);
+    if (np) CHECK(sw_memcpy_d2h(ctx, res.data(), d_res, (size_t)np * sizeof(sw_result)));
+    printf("# %lld pairs of %lld queries and %lld targets; query\ttarget\tname\tscore\ttarget_end\tquery_end\n", (long long)np, (long long)nq, (long long)nrec);
+    double cells = 0;
+    for (int64_t p = 0; p < np; ++p) {
+        const sw_pair& pr = pairs[(size_t)p];
+        const bool qin = pr.query >= 0 && pr.query < nq, tin = pr.target >= 0 && pr.target < nrec;
+        const long long M = qin ? qoffs[(size_t)pr.query + 1] - qoffs[(size_t)pr.query] + 1 : 1;
+        const sw_result& r = res[(size_t)p];
+        if (qin && tin) cells += (double)(M - 1) * (double)(offs[(size_t)pr.target + 1] - offs[(size_t)pr.target]);
+        printf("%lld\t%lld\t%s\t%lld\t%lld\t%lld\n", (long long)pr.query, (long long)pr.target, tin && (size_t)pr.target < names.size() ? names[(size_t)pr.target].c_str() : "-",
+               (long long)r.max_score, (long long)(r.max_pos / M), (long long)(r.max_pos % M));
+    }
+    printf("\nElapsed time for database search: %f (%.1f GCUPS; %lld pairs in one call, handle prepared in %f)\n\n", t2 - t1,
+           t2 > t1 ? cells / (t2 - t1) / 1e9 : 0.0, (long long)np, t1 - t0);
+    sw_db_free(handle);
+    (void)sw_device_free(ctx, d_q); (void)sw_device_free(ctx, d_db); (void)sw_device_free(ctx, d_pairs); (void)sw_device_free(ctx, d_res);
+    sw_destroy(ctx);
+    return 0;
+}
+
 int main(int argc, char** argv) {
     long long cols = 8, rows = 9;
     bool builtin = true, dump = false, labels = false, h64 = false, backtrack = true, p8 = false;
@@ -317,7 +426,8 @@ int main(int argc, char** argv) {
     long long rec_a = 0, rec_b = 0;
     const char *search_q = nullptr, *search_db = nullptr;
     long long top = 10, min_score = 0;
-    bool has_min_score = false;
+    bool has_min_score = false, has_top = false;
+    const char* pairs_path = nullptr;
     AffineArgs af;
     bool align = false, all_queries = false, align_ckpt = false;
     sw_scores sc = {3, -3, -2};
@@ -338,7 +448,8 @@ int main(int argc, char** argv) {
         else if (f == "--devices" && ai + 1 < argc) { for (char* t = strtok(argv[++ai], ","); t; t = strtok(nullptr, ",")) devices.push_back(atoi(t)); }
         else if (f == "--fasta" && ai + 2 < argc) { fasta_a = argv[++ai]; fasta_b = argv[++ai]; builtin = false; }
         else if (f == "--search" && ai + 2 < argc) { search_q = argv[++ai]; search_db = argv[++ai]; builtin = false; }
-        else if (f == "--top" && ai + 1 < argc) top = strtoll(argv[++ai], nullptr, 10);
+        else if (f == "--top" && ai + 1 < argc) { top = strtoll(argv[++ai], nullptr, 10); has_top = true; }
+        else if (f == "--pairs" && ai + 1 < argc) pairs_path = argv[++ai];
         else if (f == "--min-score" && ai + 1 < argc) { int v = 0; if (!parse_int("--min-score", argv[++ai], &v)) return 2; min_score = v; has_min_score = true; }
         else if (f == "--matrix" && ai + 1 < argc) { af.matrix = argv[++ai]; af.on = true; }
         else if (f == "--gap-open" && ai + 1 < argc) { if (!parse_int("--gap-open", argv[++ai], &af.open)) return 2; af.has_open = af.on = true; }
@@ -350,7 +461,7 @@ int main(int argc, char** argv) {
         else if (f == "--record-b" && ai + 1 < argc) rec_b = strtoll(argv[++ai], nullptr, 10);
         else if (f == "--seed" && ai + 1 < argc) seed = (unsigned)strtoul(argv[++ai], nullptr, 10);
         else if (f == "--scores" && ai + 3 < argc) { sc.match = atoi(argv[++ai]); sc.mismatch = atoi(argv[++ai]); sc.gap = atoi(argv[++ai]); }
-        else { fprintf(stderr, "usage: smithW [<cols> <rows> | --fasta A.fa B.fa [--record-a I] [--record-b J] | --search QUERY.fa DB.fa [--record-a I] [--top K] [--all-queries [--min-score S]] [--matrix FILE] [--gap-open O] [--gap-extend E] [--align [--align-checkpoint]]] [--seed N] [--dump | --dump-labels] [--h64] [--no-backtrack] [--scores M X G] [--gpus N | --devices 0,1,..] [--p8]\n"); return 2; }
+        else { fprintf(stderr, "usage: smithW [<cols> <rows> | --fasta A.fa B.fa [--record-a I] [--record-b J] | --search QUERY.fa DB.fa [--record-a I] [--top K] [--all-queries [--min-score S]] [--pairs FILE] [--matrix FILE] [--gap-open O] [--gap-extend E] [--align [--align-checkpoint]]] [--seed N] [--dump | --dump-labels] [--h64] [--no-backtrack] [--scores M X G] [--gpus N | --devices 0,1,..] [--p8]\n"); return 2; }
     }
     if (npos == 1) { fprintf(stderr, "smithW: <cols> needs <rows>\n"); return 2; }
     if (align_ckpt && !(search_q && align)) { fprintf(stderr, "smithW: --align-checkpoint goes with --search --align\n"); return 2; }
@@ -364,6 +475,17 @@ int main(int argc, char** argv) {
             fprintf(stderr, "smithW: --align on a linear search needs --scores M X within -128..127 (a table of signed bytes), got %d %d\n", sc.match, sc.mismatch);
             return 2;
         }
+        if (pairs_path) {
+            if (all_queries) { fprintf(stderr, "smithW: --pairs does not go with --all-queries\n"); return 2; }
+            if (has_top) { fprintf(stderr, "smithW: --pairs does not go with --top\n"); return 2; }
+            if (has_min_score) { fprintf(stderr, "smithW: --pairs does not go with --min-score\n"); return 2; }
+            if (align) { fprintf(stderr, "smithW: --pairs does not go with --align\n"); return 2; }
+            if (!af.matrix && (sc.match < -128 || sc.match > 127 || sc.mismatch < -128 || sc.mismatch > 127)) {
+                fprintf(stderr, "smithW: --pairs without --matrix needs --scores M X within -128..127 (a table of signed bytes), got %d %d\n", sc.match, sc.mismatch);
+                return 2;
+            }
+            return search_pairs_main(search_q, search_db, pairs_path, sc, af);
+        }
         if (all_queries) {
             if (!af.matrix && (sc.match < -128 || sc.match > 127 || sc.mismatch < -128 || sc.mismatch > 127)) {
                 fprintf(stderr, "smithW: --all-queries without --matrix needs --scores M X within -128..127 (a table of signed bytes), got %d %d\n", sc.match, sc.mismatch);
@@ -374,6 +496,7 @@ int main(int argc, char** argv) {
         if (has_min_score) { fprintf(stderr, "smithW: --min-score goes with --search --all-queries\n"); return 2; }
         return search_main(search_q, rec_a, search_db, top, sc, af, align, align_ckpt);
     }
+    if (pairs_path) { fprintf(stderr, "smithW: --pairs goes with --search\n"); return 2; }
     if (all_queries) { fprintf(stderr, "smithW: --all-queries goes with --search\n"); return 2; }
     if (has_min_score) { fprintf(stderr, "smithW: --min-score goes with --search --all-queries\n"); return 2; }
     if (align) { fprintf(stderr, "smithW: --align goes with --search\n"); return 2; }

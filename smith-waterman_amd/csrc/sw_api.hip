@@ -67,6 +67,8 @@ void sw_destroy(sw_ctx* c) {
     if (c->d_ahitems) (void)hipFree(c->d_ahitems);
     if (c->d_ahctl) (void)hipFree(c->d_ahctl);
     if (c->d_ahfilled) (void)hipFree(c->d_ahfilled);
+    if (c->d_spitems) (void)hipFree(c->d_spitems);
+    if (c->d_spctl) (void)hipFree(c->d_spctl);
     if (c->d_mq) (void)hipFree(c->d_mq);
     if (c->h_mq) (void)hipHostFree(c->h_mq);
     if (c->d_tres) (void)hipFree(c->d_tres);
@@ -123,6 +125,11 @@ int sw_set_option(sw_ctx* c, const char* name, int64_t v) {
     if (!strcmp(name, "search_results_mib")) {
         if (v < 1 || v > (1ll << 20)) { set_err("search_results_mib must be 1..2^20"); return SW_EINVAL; }
         c->opt_search_results_mib = v;
+        return SW_OK;
+    }
+    if (!strcmp(name, "search_pairs_chunk")) {
+        if (v < 1 || v > swp::kSearchPairsChunkMax) { set_err("search_pairs_chunk must be 1..2^31 - 1"); return SW_EINVAL; }
+        c->opt_search_pairs_chunk = v;
         return SW_OK;
     }
     if (!strcmp(name, "placement_budget_ms")) { c->opt_place_budget_ms = v > 0 ? v : 1500; return SW_OK; }
@@ -199,6 +206,11 @@ int64_t sw_get_option(sw_ctx* c, const char* name) {
     if (!strcmp(name, "search_results_mib")) return c->opt_search_results_mib;
     if (!strcmp(name, "last_search_top_chunks")) return c->last_search_top_chunks;
     if (!strcmp(name, "last_search_top_kernel")) return c->last_search_top_kernel;
+    if (!strcmp(name, "search_pairs_chunk")) return c->opt_search_pairs_chunk;
+    if (!strcmp(name, "last_search_pairs_groups")) return c->last_search_pairs_groups;
+    if (!strcmp(name, "last_search_pairs_chunks")) return c->last_search_pairs_chunks;
+    if (!strcmp(name, "last_search_pairs_launches")) return c->last_search_pairs_launches;
+    if (!strcmp(name, "debug_search_pairs_items_ptr")) return (int64_t)(uintptr_t)c->d_spitems;
     if (!strcmp(name, "placement_budget_ms")) return c->opt_place_budget_ms;
     if (!strcmp(name, "placement_hold_gib")) return c->opt_place_hold_gib;
     if (!strcmp(name, "probe_foreign_pairs")) return c->opt.probe_foreign_pairs;

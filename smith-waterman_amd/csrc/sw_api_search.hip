@@ -67,6 +67,15 @@ static constexpr Indexed<AlignHitsCkptKernel> kAlignHitsCkpt[] = {
 };
 static_assert(std::size(kAlignHitsCkpt) == swp::kAlignHitsKernels && at_their_indices(kAlignHitsCkpt));
 
+// the instantiations of the pair-list kernel (sw_search_pairs.hip), picked by swp::plan_search_pairs
+using SearchPairsKernel = void (*)(swk::SearchPairsParams);
+static constexpr Indexed<SearchPairsKernel> kSearchPairs[] = {
+    {swp::search_pairs_kernel_index(4), swk::sw_search_affine_pairs_wave<4>},
+    {swp::search_pairs_kernel_index(8), swk::sw_search_affine_pairs_wave<8>},
+    {swp::search_pairs_kernel_index(16), swk::sw_search_affine_pairs_wave<16>},
+};
+static_assert(std::size(kSearchPairs) == swp::kSearchPairsKernels && at_their_indices(kSearchPairs));
+
 // occupancy of every instantiation of a table at 256 threads, asked once per context: the plans' columns per lane and grids depend on it
 template <typename K, size_t N>
 static int occupancy_once(const Indexed<K> (&tab)[N], int (&per_cu)[N], bool& known) {
@@ -676,6 +685,100 @@ int sw_db_align_affine_hits(sw_ctx* c, const sw_db* db, const char* d_queries, c
     }
     c->last_align_hits_launches = (int64_t)(3 * plan.group.size() + plan.launch.size()); c->last_align_hits_tiers = plan.tiers; c->last_align_hits_slots = plan.slots;
     c->last_align_hits_checkpointed = ckpt ? 1 : 0;
+    return SW_OK;
+}
+
+// The scores of a device pair list (csrc/sw_search_pairs.hip).  Per call the host checks and plans the QUERIES (O(nqueries)) against the
+// handle's longest target; the pairs and the targets' offsets are read on the device only.  One memset zeroes the call's results up
+// front -- the pairs that never become an item keep it, the binning writes no result --, then per group one profile launch and per
+// chunk of the list two binning launches and one score launch per class of the group, its grid planned for the most its list could hold.
+int sw_db_search_affine_pairs(sw_ctx* c, const sw_db* db, const char* d_queries, const int64_t* qoffsets, int64_t nqueries, const sw_affine* scoring,
+                              const sw_pair* d_pairs, int64_t npairs, sw_result* d_results, void* stream_) {
+    if (!c || !db || !d_queries || !qoffsets || !scoring) { set_err("sw_db_search_affine_pairs: NULL pointer"); return SW_EINVAL; }
+    if (db->device != c->device) { set_err("sw_db_search_affine_pairs: the handle was created on device %d, the context runs on device %d", db->device, c->device); return SW_EINVAL; }
+    int64_t maxq = 0;
+    if (int rc = swh::check_search_multi("sw_db_search_affine_pairs", qoffsets, nqueries, db->longest, scoring, &maxq)) return rc;
+    if (npairs < 0) { set_err("sw_db_search_affine_pairs: negative pair count"); return SW_EINVAL; }
+    if (npairs > 0 && (!d_pairs || !d_results)) { set_err("sw_db_search_affine_pairs: NULL d_pairs or d_results with %lld pairs", (long long)npairs); return SW_EINVAL; }
+    c->last_search_pairs_groups = c->last_search_pairs_chunks = c->last_search_pairs_launches = 0;   // (a call that launches no kernel reports none)
+    if (npairs == 0) return SW_OK;
+    hipStream_t stream = (hipStream_t)stream_;
+    HIP_TRY(hipSetDevice(c->device));
+    DevOrder order(c, stream, false);
+    if (order.rc) return order.rc;
+    // every entry that names no query, no target or an empty target keeps these zeros: {0, 0, 0}
+    HIP_TRY(hipMemsetAsync(d_results, 0, (size_t)npairs * sizeof(sw_result), stream));
+    if (nqueries == 0 || db->nonempty == 0) return SW_OK;
+    if (int rc = occupancy_once(kSearchPairs, c->search_pairs_per_cu, c->search_pairs_per_cu_known)) return rc;
+    std::vector<int64_t> qlens((size_t)nqueries);
+    for (int64_t q = 0; q < nqueries; ++q) qlens[(size_t)q] = qoffsets[q + 1] - qoffsets[q];
+    swp::SearchPairsJob pj;
+    pj.qlens = qlens.data(); pj.nqueries = nqueries; pj.npairs = npairs; pj.longest = db->longest; pj.num_cus = c->num_cus;
+    pj.budget_bytes = c->opt_search_profile_mib << 20; pj.chunk = c->opt_search_pairs_chunk;
+    std::copy(std::begin(c->search_pairs_per_cu), std::end(c->search_pairs_per_cu), pj.per_cu);
+    const swp::SearchPairsPlan plan = swp::plan_search_pairs(pj);
+    for (const swp::PairsLaunch& l : plan.launch)
+        if (c->search_pairs_per_cu[l.kernel] < 1) { set_err("the pair-list search kernel does not fit a CU on this device"); return SW_EDEVICE; }
+    if (int rc = stage_search_call(c, stream, 0, plan.prof_need, plan.bnd_need, scoring->sub)) return rc;
+    // the table and, behind its nqueries entries, entry_of (4 bytes per query): one pinned copy, one upload
+    const size_t entry_slots = ((size_t)nqueries * sizeof(int32_t) + sizeof(swk::MultiQuery) - 1) / sizeof(swk::MultiQuery);
+    if (int rc = grow_query_table(c, (size_t)nqueries + entry_slots, stream)) return rc;
+    bool fresh = false;
+    if (int rc = grow_workspace((void**)&c->d_spitems, c->spitems_cap, plan.items_need, 1, 0, stream, fresh)) return rc;
+    if (!c->d_spctl) HIP_TRY(hipMalloc((void**)&c->d_spctl, sizeof(swk::SearchPairsCtl)));
+    for (int64_t t = 0; t < nqueries; ++t) {
+        c->h_mq[t] = plan.table[(size_t)t];
+        c->h_mq[t].qstart = qoffsets[plan.table[(size_t)t].row];
+    }
+    memcpy(c->h_mq + nqueries, plan.entry_of.data(), (size_t)nqueries * sizeof(int32_t));
+    memcpy(c->h_submat, scoring->sub, sizeof(sw_submat));
+    HIP_TRY(hipMemcpyAsync(c->d_mq, c->h_mq, ((size_t)nqueries + entry_slots) * sizeof(swk::MultiQuery), hipMemcpyHostToDevice, stream));
+    HIP_TRY(hipMemcpyAsync(c->d_submat, c->h_submat, sizeof(sw_submat), hipMemcpyHostToDevice, stream));
+    HIP_TRY(hipEventRecord(c->sitems_ev, stream));   // behind both uploads: whoever has waited for it may overwrite either pinned copy
+    size_t l0 = 0;
+    for (size_t g = 0; g < plan.group.size(); ++g) {
+        const swp::PairsGroup& grp = plan.group[g];
+        const int parts = (int)std::clamp<int64_t>(grp.prof_bytes / grp.nq / 16384, 1, 4096);
+        const unsigned blocks = (unsigned)std::min<int64_t>(grp.nq * parts, 4096);
+        hipLaunchKernelGGL(swk::sw_search_profile_submat_multi, dim3(blocks), dim3(256), 0, stream, (const unsigned char*)d_queries, c->d_mq + grp.q0, grp.nq,
+                           parts, c->d_sprof, (const signed char*)c->d_submat);
+        HIP_TRY(hipGetLastError());
+        size_t l1 = l0;
+        while (l1 < plan.launch.size() && plan.launch[l1].group == (int)g) ++l1;
+        for (int64_t ch = 0; ch < plan.nchunks; ++ch) {
+            const int64_t np = plan.chunk_pairs(ch, npairs);
+            // the lists of the (chunk, group): counts, cursors and work counters start at zero
+            HIP_TRY(hipMemsetAsync(c->d_spctl, 0, sizeof(swk::SearchPairsCtl), stream));
+            swk::SearchPairsBinParams bp;
+            memset(&bp, 0, sizeof bp);
+            bp.pairs = d_pairs; bp.p0 = plan.chunk_p0(ch); bp.np = np;
+            bp.offsets = db->d_offsets; bp.ntargets = db->ntargets;
+            bp.queries = c->d_mq; bp.entry_of = (const int32_t*)(c->d_mq + nqueries); bp.nqueries = nqueries;
+            std::copy(std::begin(grp.cls_q0), std::end(grp.cls_q0), bp.cls_q0);
+            bp.ctl = c->d_spctl; bp.items = c->d_spitems;
+            const unsigned bin_blocks = (unsigned)std::clamp<int64_t>((np + 255) / 256, 1, 4096);
+            hipLaunchKernelGGL(swk::sw_search_pairs_bin<false>, dim3(bin_blocks), dim3(256), 0, stream, bp);
+            HIP_TRY(hipGetLastError());
+            hipLaunchKernelGGL(swk::sw_search_pairs_bin<true>, dim3(bin_blocks), dim3(256), 0, stream, bp);
+            HIP_TRY(hipGetLastError());
+            for (size_t li = l0; li < l1; ++li) {
+                const swp::PairsLaunch& l = plan.launch[li];
+                swk::SearchPairsParams sp;
+                memset(&sp, 0, sizeof sp);
+                sp.db = (const unsigned char*)db->d_db;
+                sp.items = c->d_spitems; sp.list = &c->d_spctl->list[l.kernel];
+                sp.queries = c->d_mq; sp.prof = c->d_sprof;
+                sp.ge = scoring->gap_extend; sp.goe = scoring->gap_open + scoring->gap_extend;
+                sp.bnd = l.bnd_per ? c->d_sbnd : nullptr; sp.bnd_per = l.bnd_per;
+                sp.counter = &c->d_spctl->work[l.kernel];
+                sp.results = d_results;
+                hipLaunchKernelGGL(kSearchPairs[l.kernel].k, dim3((unsigned)swp::search_pairs_grid(l, np)), dim3(256), 0, stream, sp);
+                HIP_TRY(hipGetLastError());
+            }
+        }
+        l0 = l1;
+    }
+    c->last_search_pairs_groups = (int64_t)plan.group.size(); c->last_search_pairs_chunks = plan.nchunks; c->last_search_pairs_launches = plan.launches;
     return SW_OK;
 }
 

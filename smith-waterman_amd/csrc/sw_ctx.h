@@ -135,6 +135,14 @@ struct SW_HIDDEN sw_ctx {
     int64_t last_search_multi_groups = 0, last_search_multi_launches = 0, last_search_multi_grid = 0;   // of the last call; the grid of its last launch
     int search_multi_per_cu[swp::kSearchMultiKernels] = {};     // occupancy of every sw_search_affine_multi_wave instantiation at 256 threads ...
     bool search_multi_per_cu_known = false;                     // ... queried at the first call
+    // a pair list against a prepared database (sw_db_search_affine_pairs): the items of a chunk and the control words of a (chunk, group);
+    // the profiles, the boundary columns and the query table are those of the calls above (the table carries entry_of behind its entries)
+    swk::SearchPairItem* d_spitems = nullptr; size_t spitems_cap = 0;   // (bytes)
+    swk::SearchPairsCtl* d_spctl = nullptr;
+    int64_t opt_search_pairs_chunk = swp::kSearchPairsChunk;
+    int64_t last_search_pairs_groups = 0, last_search_pairs_chunks = 0, last_search_pairs_launches = 0;
+    int search_pairs_per_cu[swp::kSearchPairsKernels] = {};     // occupancy of every sw_search_affine_pairs_wave instantiation at 256 threads ...
+    bool search_pairs_per_cu_known = false;                     // ... queried at the first call
     // the best targets per query (sw_top_hits_device, sw_db_search_affine_top): the result rows of a chunk, the histograms and the
     // per-row states of the radix select
     sw_result* d_tres = nullptr; size_t tres_cap = 0;

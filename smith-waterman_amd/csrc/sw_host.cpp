@@ -459,6 +459,28 @@ int sw_search_affine_multi_host(const char* queries, const int64_t* qoffsets, in
     return SW_OK;
 }
 
+// The CPU leg of sw_db_search_affine_pairs: sw_search_affine_host for every listed pair, the query against that one target.  Everything
+// is checked before the first pair, so an error leaves `results` untouched; an entry that names no query or no target gives {0, 0, 0}.
+int sw_search_affine_pairs_host(const char* queries, const int64_t* qoffsets, int64_t nqueries, const char* db, const int64_t* offsets, int64_t ntargets,
+                                const sw_affine* scoring, const sw_pair* pairs, int64_t npairs, sw_result* results) {
+    if (!queries || !qoffsets || !db || !offsets || !scoring || ntargets < 0) {
+        swh::set_err("sw_search_affine_pairs_host: NULL pointer or negative target count");
+        return SW_EINVAL;
+    }
+    int64_t maxlen = 0, nonempty = 0, maxq = 0;
+    if (int rc = swh::check_targets("sw_search_affine_pairs_host", 1, offsets, ntargets, &maxlen, &nonempty)) return rc;
+    if (int rc = swh::check_search_multi("sw_search_affine_pairs_host", qoffsets, nqueries, maxlen, scoring, &maxq)) return rc;
+    if (npairs < 0) { swh::set_err("sw_search_affine_pairs_host: negative pair count"); return SW_EINVAL; }
+    if (npairs > 0 && (!pairs || !results)) { swh::set_err("sw_search_affine_pairs_host: NULL pairs or results with %lld pairs", (long long)npairs); return SW_EINVAL; }
+    for (int64_t p = 0; p < npairs; ++p) {
+        const uint64_t q = (uint64_t)pairs[p].query, k = (uint64_t)pairs[p].target;
+        results[p] = sw_result{0, 0, 0};
+        if (q >= (uint64_t)nqueries || k >= (uint64_t)ntargets) continue;
+        if (int rc = sw_search_affine_host(queries + qoffsets[q], qoffsets[q + 1] - qoffsets[q], db, offsets + k, 1, scoring, results + p)) return rc;
+    }
+    return SW_OK;
+}
+
 // The CPU leg of sw_db_search_affine_top: sw_search_affine_host query after query into one row, a sort of the qualifying targets by the
 // rank order (max_score descending, then target ascending), the first `top` of them and the {-1, 0, 0} tail.
 int sw_search_affine_multi_top_host(const char* queries, const int64_t* qoffsets, int64_t nqueries, const char* db, const int64_t* offsets, int64_t ntargets,

@@ -158,6 +158,45 @@ __global__ void sw_search_profile_submat_multi(const unsigned char* q, const Mul
 template <int C>
 __global__ void sw_search_affine_multi_wave(SearchMultiParams p);
 
+// sw_search_pairs.hip: the scores of a device list of (query, target) pairs (sw_db_search_affine_pairs).  Per (chunk of the list, group
+// of queries) two binning launches turn the usable pairs into work items, one list per class, heaviest bucket first
+// (swp::plan_search_pairs); one launch of sw_search_affine_pairs_wave<C> per class scores them.
+struct SearchPairItem { int64_t start, out; int32_t len, entry; };   // first byte in db, index in d_results (= in d_pairs), length, entry of the call's query table
+constexpr int SW_SP_CLASSES = swp::kSearchPairsKernels, SW_SP_BUCKETS = swp::kSearchPairsBuckets;
+struct SearchPairsList { unsigned int n, first; };   // a class's list: its items and where it starts in the item buffer (the scatter launch writes it)
+// the control words of a (chunk, group), zero before its binning: per (class, bucket) the items counted and the scatter's cursor, per
+// class its list and the work counter of its launch
+struct SearchPairsCtl {
+    unsigned int count[SW_SP_CLASSES][SW_SP_BUCKETS], cursor[SW_SP_CLASSES][SW_SP_BUCKETS];
+    SearchPairsList list[SW_SP_CLASSES];
+    unsigned int work[SW_SP_CLASSES];
+};
+struct SearchPairsBinParams {
+    const sw_pair* pairs;                        // the caller's list
+    int64_t p0, np;                              // the chunk: pairs p0 .. p0 + np - 1
+    const int64_t* offsets; int64_t ntargets;    // the handle's ntargets + 1 offsets on the device
+    const MultiQuery* queries;                   // the call's table (what an item's `entry` counts from)
+    const int32_t* entry_of; int64_t nqueries;   // query index -> its entry of the table
+    int64_t cls_q0[SW_SP_CLASSES + 1];           // the group: class k = entries cls_q0[k] .. cls_q0[k + 1] - 1 of the table
+    SearchPairsCtl* ctl;
+    SearchPairItem* items;                       // np at most
+};
+template <bool SCATTER>
+__global__ void sw_search_pairs_bin(SearchPairsBinParams p);
+struct SearchPairsParams {
+    const unsigned char* db;             // the targets back to back
+    const SearchPairItem* items;         // the (chunk, group)'s item buffer: the classes' lists back to back
+    const SearchPairsList* list;         // this class's list (SearchPairsCtl::list[k])
+    const MultiQuery* queries;           // the call's table
+    const signed char* prof;             // the group's profiles, query t at its prof_off
+    int ge, goe;                         // gap_extend, gap_open + gap_extend (both <= 0)
+    int* bnd; int64_t bnd_per;           // per resident wave: boundary pairs (H, F) between strips (ints), only when a query of the class has more than one strip
+    unsigned int* counter;               // next item (zero at launch)
+    sw_result* results;                  // npairs, the order of the caller's list
+};
+template <int C>
+__global__ void sw_search_affine_pairs_wave(SearchPairsParams p);
+
 // sw_search_top.hip: the best `top` targets of every row of a query-major result table (swp::plan_search_top has the geometry)
 struct TopState {                        // of one row, between the launches of a radix select
     unsigned long long prefix;           // the digits found so far, highest first; after the last pass: the key of rank `top`

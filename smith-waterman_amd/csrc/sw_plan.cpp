@@ -449,6 +449,54 @@ SearchMultiPlan plan_search_multi(const SearchMultiJob& j) {
     return m;
 }
 
+// A pair list against a prepared database.  The table and the groups come from plan_search_multi itself (asked for a handle without
+// targets, it plans no launch); the rest is O(nqueries) too: nothing here looks at a pair or a target, and the chunks are arithmetic.
+SearchPairsPlan plan_search_pairs(const SearchPairsJob& j) {
+    SearchPairsPlan s;
+    SearchMultiJob mj;
+    mj.qlens = j.qlens; mj.nqueries = j.nqueries; mj.longest = j.longest; mj.nonempty = 0; mj.num_cus = j.num_cus; mj.budget_bytes = j.budget_bytes;
+    std::copy(std::begin(j.per_cu), std::end(j.per_cu), mj.per_cu);   // (decides whether 16 columns per lane are taken, as there)
+    SearchMultiPlan m = plan_search_multi(mj);
+    s.table = std::move(m.table);
+    s.prof_need = m.prof_need;
+    s.entry_of.resize((size_t)j.nqueries);
+    for (int64_t t = 0; t < j.nqueries; ++t) s.entry_of[(size_t)s.table[(size_t)t].row] = (int32_t)t;
+    s.chunk = std::clamp<int64_t>(j.chunk, 1, kSearchPairsChunkMax);
+    const int64_t npairs = std::max<int64_t>(0, j.npairs), most = std::min(npairs, s.chunk);   // pairs of the largest chunk
+    s.nchunks = (npairs + s.chunk - 1) / s.chunk;
+    s.items_need = (size_t)(24 * most);
+    for (size_t g = 0; g < m.group.size(); ++g) {
+        PairsGroup grp;
+        grp.q0 = m.group[g].q0; grp.nq = m.group[g].nq; grp.prof_bytes = m.group[g].prof_bytes;
+        // the classes of the group: its entries are sorted by columns per lane, qpad = nstrips * 64 * C
+        int64_t strips[kSearchPairsKernels] = {}, t = grp.q0;
+        for (int k = 0; k < kSearchPairsKernels; ++k) {
+            grp.cls_q0[k] = t;
+            for (; t < grp.q0 + grp.nq; ++t) {
+                const swk::MultiQuery& d = s.table[(size_t)t];
+                if (search_pairs_kernel_index(d.qpad / d.nstrips / 64) != k) break;
+                strips[k] = std::max<int64_t>(strips[k], d.nstrips);
+            }
+        }
+        grp.cls_q0[kSearchPairsKernels] = t;
+        s.group.push_back(grp);
+        for (int k = 0; k < kSearchPairsKernels; ++k) {
+            if (grp.cls_q0[k + 1] == grp.cls_q0[k]) continue;
+            PairsLaunch l;
+            l.group = (int)g; l.C = k == 0 ? 4 : 8 * k; l.kernel = k;
+            l.q0 = grp.cls_q0[k]; l.nq = grp.cls_q0[k + 1] - grp.cls_q0[k];
+            l.bnd_per = 2 * boundary_ints(strips[k], j.longest);
+            l.max_grid = (int64_t)j.per_cu[k] * j.num_cus;
+            if (l.bnd_per) l.max_grid = std::min<int64_t>(l.max_grid, kSearchBndBytes / (l.bnd_per * 4 * 4));
+            l.max_grid = std::max<int64_t>(1, l.max_grid);
+            s.bnd_need = std::max(s.bnd_need, (size_t)(search_pairs_grid(l, most) * 4 * l.bnd_per));
+            s.launch.push_back(l);
+        }
+    }
+    s.launches = (int64_t)s.group.size() + s.nchunks * (2 * (int64_t)s.group.size() + (int64_t)s.launch.size());
+    return s;
+}
+
 // The best `top` of every row.  Every row has the same length, so the chunks are uniform and the geometry of a row is decided once.
 // The passes take kTopDigitBits bits each from the top of the key down; the last one takes what is left.
 SearchTopPlan plan_search_top(const SearchTopJob& j) {

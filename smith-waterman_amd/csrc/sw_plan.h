@@ -223,6 +223,66 @@ struct SearchMultiPlan {
 
 SearchMultiPlan plan_search_multi(const SearchMultiJob& job);
 
+// ---- a device list of (query, target) pairs against a prepared database (sw_db_search_affine_pairs; sw_search_pairs.hip):
+// sw_search_affine_pairs_wave<C> for C = 4, 8, 16, its index in kSearchPairs (sw_api_search.hip, which checks its order against it at
+// compile time).  The host knows the queries and the handle's longest target, neither the pairs nor the targets they name.
+// Queries: the table and the groups are plan_search_multi's, entry for entry, so sw_search_profile_submat_multi fills a group's profiles
+// as it does there; entry_of[q] is the table entry of query q (the device gets from a pair's query to its entry through it).
+// Chunks: the list is taken in consecutive chunks of at most `chunk` pairs ("search_pairs_chunk"); chunk i holds the pairs
+// [i * chunk, min(npairs, (i + 1) * chunk)).  That bounds the item workspace (24 bytes per pair of a chunk) and keeps every count,
+// cursor and work counter inside 32 bits.
+// Launches: every (chunk, group) gets a count launch, a scatter launch and one score launch per class present in the group -- `launch`
+// holds those of one chunk, group after group; a score launch runs min(resident waves, pairs of the chunk) waves in workgroups of four
+// (search_pairs_grid), fewer where the boundary columns would pass kSearchBndBytes.  The kernel reads its list's length on the device.
+// Order inside a class's list: heaviest first.  An item's bucket is floor(log2(len x qpad)) -- at most kSearchPairsBuckets of them, since
+// len < 2^20 and qpad <= 2^20 --, the list holds bucket after bucket from the heaviest down, and the one launch of a class starts
+// with its longest pairs (the short tail of DESIGN 9c).  Order inside a bucket comes from an atomic and is free.
+constexpr int kSearchPairsKernels = 3;
+constexpr int search_pairs_kernel_index(int C) { return C / 8; }
+constexpr int kSearchPairsBuckets = 41;
+constexpr int64_t kSearchPairsChunk = 1ll << 22;     // the default chunk: 24 bytes of list each (96 MiB), the bound of kAlignHitsMaxItems
+constexpr int64_t kSearchPairsChunkMax = (1ll << 31) - 1;
+constexpr int search_pairs_bucket(int64_t len, int64_t qpad) { return 63 - __builtin_clzll((unsigned long long)(len * qpad)); }   // len, qpad >= 1
+
+struct SearchPairsJob {
+    const int64_t* qlens = nullptr;          // length of every query, input order
+    int64_t nqueries = 0, npairs = 0;
+    int64_t longest = 0;                     // of the handle: longest target
+    int num_cus = 256;
+    int per_cu[kSearchPairsKernels] = {};    // occupancy of every sw_search_affine_pairs_wave instantiation at 256 threads (workgroups per CU)
+    int64_t budget_bytes = 256ll << 20;      // "search_profile_mib": the profiles of a group may take this much
+    int64_t chunk = kSearchPairsChunk;       // "search_pairs_chunk"
+};
+
+struct PairsGroup {
+    int64_t q0 = 0, nq = 0, prof_bytes = 0;  // as MultiGroup
+    int64_t cls_q0[kSearchPairsKernels + 1] = {};   // class k: the table entries cls_q0[k] .. cls_q0[k + 1] - 1
+};
+struct PairsLaunch {                         // the score launch of a class of a group, the same in every chunk but for its grid
+    int group = 0, C = 0, kernel = 0;        // kernel: index of sw_search_affine_pairs_wave<C> (kSearchPairsKernels)
+    int64_t q0 = 0, nq = 0;                  // its queries: entries q0 .. q0 + nq - 1 of the table
+    int64_t bnd_per = 0;                     // per resident wave: boundary pairs between strips (ints), 0: every query of the class has one strip
+    int64_t max_grid = 0;                    // workgroups of 4 waves the device (and the boundary workspace) holds
+};
+constexpr int64_t search_pairs_grid(const PairsLaunch& l, int64_t chunk_pairs) {   // min(resident waves, pairs of the chunk) waves
+    const int64_t g = (chunk_pairs + 3) / 4 < l.max_grid ? (chunk_pairs + 3) / 4 : l.max_grid;
+    return g < 1 ? 1 : g;
+}
+
+struct SearchPairsPlan {
+    std::vector<swk::MultiQuery> table;      // as SearchMultiPlan::table
+    std::vector<int32_t> entry_of;           // per query: its entry of the table
+    std::vector<PairsGroup> group;
+    std::vector<PairsLaunch> launch;         // the score launches of ONE chunk in the order they are enqueued: group after group
+    int64_t chunk = 0, nchunks = 0;          // pairs of a full chunk; chunks of the call
+    int64_t launches = 0;                    // kernel launches of the call: per group a profile launch, per (chunk, group) two binning launches and its score launches
+    size_t prof_need = 0, bnd_need = 0, items_need = 0;   // workspaces: profiles of the largest group (bytes), boundary columns (ints), items (bytes)
+    int64_t chunk_p0(int64_t i) const { return i * chunk; }
+    int64_t chunk_pairs(int64_t i, int64_t npairs) const { return npairs - i * chunk < chunk ? npairs - i * chunk : chunk; }
+};
+
+SearchPairsPlan plan_search_pairs(const SearchPairsJob& job);
+
 // ---- the best `top` targets of every row of a query-major result table (sw_top_hits_device, sw_db_search_affine_top; sw_search_top.hip).
 // Key: a target's key is score << tbits | (2^tbits - 1 - target) with tbits = ceil(log2 ntargets): unique per target, and plain integer
 // order of the keys is the rank order (score descending, target ascending).  nbits = 24 + tbits bits of a key can differ.
