@@ -22,62 +22,13 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "sw_kernels.h"
+#include "sw_wave.h"
 
 namespace swk {
 
 namespace {
 
-typedef unsigned int u32;
-typedef unsigned long long u64;
-
-constexpr u32 AA_OOB = 0xFFFFFF00u;     // buffer offset beyond every descriptor: the access is dropped (loads return 0)
 constexpr int AA_SC1 = 16;              // aux bit of the buffer builtins: sc1
-
-__device__ __forceinline__ int aa_dpp_shr1(int old, int src) {   // lane l <- lane l-1; lane 0 keeps `old`
-    return __builtin_amdgcn_update_dpp(old, src, 0x138, 0xF, 0xF, false);
-}
-__device__ __forceinline__ int aa_sbyte(u32 w, int j) { return (int)(signed char)(w >> (8 * j)); }
-
-__device__ __forceinline__ int aa_wave_max(int v) {   // max over the 64 lanes, wave-uniform result (v >= 0)
-    v = max(v, __builtin_amdgcn_update_dpp(0, v, 0x111, 0xF, 0xF, true));   // row_shr:1
-    v = max(v, __builtin_amdgcn_update_dpp(0, v, 0x112, 0xF, 0xF, true));   // row_shr:2
-    v = max(v, __builtin_amdgcn_update_dpp(0, v, 0x114, 0xF, 0xF, true));   // row_shr:4
-    v = max(v, __builtin_amdgcn_update_dpp(0, v, 0x118, 0xF, 0xF, true));   // row_shr:8
-    v = max(v, __builtin_amdgcn_update_dpp(0, v, 0x142, 0xA, 0xF, true));   // row_bcast:15
-    v = max(v, __builtin_amdgcn_update_dpp(0, v, 0x143, 0xC, 0xF, true));   // row_bcast:31
-    return __builtin_amdgcn_readlane(v, 63);
-}
-
-typedef int aa_v4i __attribute__((ext_vector_type(4)));
-typedef int aa_v2i __attribute__((ext_vector_type(2)));
-
-template <int C>
-__device__ __forceinline__ void aa_load_row(__amdgpu_buffer_rsrc_t r, u32 off, u32 (&s)[C / 4]) {
-    if constexpr (C == 16) {
-        const aa_v4i v = __builtin_amdgcn_raw_buffer_load_b128(r, (int)off, 0, 0);
-        s[0] = (u32)v.x; s[1] = (u32)v.y; s[2] = (u32)v.z; s[3] = (u32)v.w;
-    } else if constexpr (C == 8) {
-        const aa_v2i v = __builtin_amdgcn_raw_buffer_load_b64(r, (int)off, 0, 0);
-        s[0] = (u32)v.x; s[1] = (u32)v.y;
-    } else {
-        s[0] = __builtin_amdgcn_raw_buffer_load_b32(r, (int)off, 0, 0);
-    }
-}
-// the C direction bytes of one lane and row
-template <int C>
-__device__ __forceinline__ void aa_store_row(__amdgpu_buffer_rsrc_t r, u32 off, const u32 (&d)[C / 4]) {
-    if constexpr (C == 16) __builtin_amdgcn_raw_buffer_store_b128(aa_v4i{(int)d[0], (int)d[1], (int)d[2], (int)d[3]}, r, (int)off, 0, 0);
-    else if constexpr (C == 8) __builtin_amdgcn_raw_buffer_store_b64(aa_v2i{(int)d[0], (int)d[1]}, r, (int)off, 0, 0);
-    else __builtin_amdgcn_raw_buffer_store_b32((int)d[0], r, (int)off, 0, 0);
-}
-
-template <int I, int N, typename F>
-__device__ __forceinline__ void aa_for(F&& f) {
-    if constexpr (I < N) {
-        f(std::integral_constant<int, I>{});
-        aa_for<I + 1, N>(f);
-    }
-}
 
 constexpr int AA_WIN = 64;              // the walk's window: AA_WIN rows of AA_WIN direction bytes per wave
 
@@ -88,7 +39,7 @@ template <int C>
 __global__ void __launch_bounds__(256) sw_align_affine_wave(AlignAffineParams p) {
     static_assert(C % 4 == 0 && C <= 16, "C is a multiple of 4");
     constexpr int NQ = C / 4;
-    __shared__ aa_v4i win_all[4][AA_WIN * AA_WIN / 16];
+    __shared__ sw_v4i win_all[4][AA_WIN * AA_WIN / 16];
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const int64_t slot = (int64_t)blockIdx.x * (blockDim.x >> 6) + wave;     // resident wave: its own boundary column and direction matrix
@@ -104,8 +55,8 @@ __global__ void __launch_bounds__(256) sw_align_affine_wave(AlignAffineParams p)
     const __amdgpu_buffer_rsrc_t rD = __builtin_amdgcn_make_buffer_rsrc((void*)(p.dir + slot * p.slot_bytes), 0, (int)p.slot_bytes, 0x00020000);
     const u32 qpad = (u32)p.qpad;
     const __amdgpu_buffer_rsrc_t rC = __builtin_amdgcn_make_buffer_rsrc((void*)p.counter, 0, 4, 0x00020000);
-    const u32 voffL0 = lane == 0 ? 0u : AA_OOB;    // lane 0 alone touches the counter and the result
-    aa_v4i* const win = win_all[wave];
+    const u32 voffL0 = lane == 0 ? 0u : SW_OOB;    // lane 0 alone touches the counter and the result
+    sw_v4i* const win = win_all[wave];
     const unsigned char* const winb = (const unsigned char*)win;
     const int ops_size = (int)(p.ops ? (p.ops_cap < 0x7FFFFF00ll ? p.ops_cap : 0x7FFFFF00ll) : 0);
 
@@ -129,8 +80,8 @@ __global__ void __launch_bounds__(256) sw_align_affine_wave(AlignAffineParams p)
             for (int k = 0; k < C; ++k) { h[k] = 0; e[k] = goe; }
             int diag0 = 0, fout = goe, lbest = 0, lk = 0, lstep = 0;
             const bool bw = multi && st + 1 < nstrips, br = multi && st > 0;
-            aa_v4i bq0 = {0, 0, 0, 0}, bq1 = {0, 0, 0, 0};
-            const u32 voffB = lane == 0 ? 64u * 8u : AA_OOB;
+            sw_v4i bq0 = {0, 0, 0, 0}, bq1 = {0, 0, 0, 0};
+            const u32 voffB = lane == 0 ? 64u * 8u : SW_OOB;
             if (br) {   // (sc1 loads: served from L2, which this wave's own earlier stores have reached once vmcnt has drained)
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
                 bq0 = __builtin_amdgcn_raw_buffer_load_b128(rB, (int)voffB, 0, AA_SC1);
@@ -138,7 +89,7 @@ __global__ void __launch_bounds__(256) sw_align_affine_wave(AlignAffineParams p)
             }
             auto raw_of = [&](int g, int j) -> u32 {
                 const u32 pos = (u32)(4 * g + j - lane - 1);
-                return (u32)__builtin_amdgcn_raw_buffer_load_b8(rT, (int)(pos < (u32)len ? pos : AA_OOB), 0, 0);
+                return (u32)__builtin_amdgcn_raw_buffer_load_b8(rT, (int)(pos < (u32)len ? pos : SW_OOB), 0, 0);
             };
             auto row_off = [&](int g, int j, u32 raw) -> u32 {
                 const u32 pos = (u32)(4 * g + j - lane - 1);
@@ -148,13 +99,13 @@ __global__ void __launch_bounds__(256) sw_align_affine_wave(AlignAffineParams p)
 #pragma unroll
             for (int j = 0; j < 4; ++j) raw[j] = raw_of(0, j);
 #pragma unroll
-            for (int j = 0; j < 4; ++j) aa_load_row<C>(rQ, row_off(0, j, raw[j]), S[j]);
+            for (int j = 0; j < 4; ++j) sw_load_row<C>(rQ, row_off(0, j, raw[j]), S[j]);
 #pragma unroll
             for (int j = 0; j < 4; ++j) raw[j] = raw_of(1, j);
 
             for (int g = 0; g < G; ++g) {
 #pragma unroll
-                for (int j = 0; j < 4; ++j) aa_load_row<C>(rQ, row_off(g + 1, j, raw[j]), Sn[j]);
+                for (int j = 0; j < 4; ++j) sw_load_row<C>(rQ, row_off(g + 1, j, raw[j]), Sn[j]);
 #pragma unroll
                 for (int j = 0; j < 4; ++j) raw[j] = raw_of(g + 2, j);
                 const int bh[4] = {bq0.x, bq0.z, bq1.x, bq1.z}, bf[4] = {bq0.y, bq0.w, bq1.y, bq1.w};
@@ -163,21 +114,21 @@ __global__ void __launch_bounds__(256) sw_align_affine_wave(AlignAffineParams p)
                     bq1 = __builtin_amdgcn_raw_buffer_load_b128(rB, (int)voffB, 32 * (g + 1) + 16, AA_SC1);
                 }
 
-                aa_for<0, 4>([&](auto J) {
+                sw_for<0, 4>([&](auto J) {
                     constexpr int j = decltype(J)::value;
                     const int u = 4 * g + j;
                     const bool bin = br && u <= len;
-                    const int left = aa_dpp_shr1(bin ? bh[j] : 0, h[C - 1]);
-                    int f = aa_dpp_shr1(bin ? bf[j] : goe, fout);
+                    const int left = sw_dpp_shr1(bin ? bh[j] : 0, h[C - 1]);
+                    int f = sw_dpp_shr1(bin ? bf[j] : goe, fout);
                     int dprev = diag0;
                     diag0 = left;
                     u32 dw[NQ];
 #pragma unroll
                     for (int q = 0; q < NQ; ++q) dw[q] = 0;
-                    aa_for<0, C>([&](auto K) {
+                    sw_for<0, C>([&](auto K) {
                         constexpr int k = decltype(K)::value;
                         const int old = h[k];
-                        const int t = dprev + aa_sbyte(S[j][k >> 2], k & 3);
+                        const int t = dprev + sw_sbyte(S[j][k >> 2], k & 3);
                         const int ek = e[k];
                         const int hn = max(max(max(t, ek), f), 0);
                         u32 d = hn == ek ? 2u : 3u;            // the compare order of the canonical alignment: diagonal, E, F
@@ -193,10 +144,10 @@ __global__ void __launch_bounds__(256) sw_align_affine_wave(AlignAffineParams p)
                         dw[k >> 2] |= d << (8 * (k & 3));
                     });
                     fout = f;
-                    if (bw) __builtin_amdgcn_raw_buffer_store_b64(aa_v2i{h[C - 1], fout}, rB, lane == 63 ? 8 : (int)AA_OOB, 8 * u, 0);   // row u - 63 at pair index row + 64
+                    if (bw) __builtin_amdgcn_raw_buffer_store_b64(sw_v2i{h[C - 1], fout}, rB, lane == 63 ? 8 : (int)SW_OOB, 8 * u, 0);   // row u - 63 at pair index row + 64
                     {   // the direction bytes of row u - lane, columns c0 .. c0 + C - 1
                         const u32 r1 = (u32)(u - lane - 1);
-                        aa_store_row<C>(rD, r1 < (u32)len ? r1 * qpad + colb : AA_OOB, dw);
+                        sw_store_row<C>(rD, r1 < (u32)len ? r1 * qpad + colb : SW_OOB, dw);
                     }
                     // ---- arg-max: the row maximum against the wave's best so far; only a step that reaches it looks for the cell
                     int m = h[0];
@@ -204,7 +155,7 @@ __global__ void __launch_bounds__(256) sw_align_affine_wave(AlignAffineParams p)
                     for (int k = 1; k + 1 < C; k += 2) m = max(max(m, h[k]), h[k + 1]);
                     m = max(m, h[C - 1]);
                     if (__builtin_amdgcn_ballot_w64(m >= sbest) != 0) {
-                        sbest = max(sbest, aa_wave_max(m));
+                        sbest = max(sbest, sw_wave_max(m));
                         int kk = 0;                                   // first column of my row that holds its maximum
 #pragma unroll
                         for (int k = C - 1; k >= 0; --k) kk = (h[k] == m) ? k : kk;
@@ -250,7 +201,7 @@ __global__ void __launch_bounds__(256) sw_align_affine_wave(AlignAffineParams p)
             bool done = score == 0;
             // `cnt` ops `ch` behind the n already taken: the walk goes backwards, op k from the end lies at nops - 1 - k
             auto emit = [&](int cnt, int ch) {
-                if (pass == 1) __builtin_amdgcn_raw_buffer_store_b8((unsigned char)ch, rO, lane < cnt ? nops - 1 - n - lane : (int)AA_OOB, 0, 0);
+                if (pass == 1) __builtin_amdgcn_raw_buffer_store_b8((unsigned char)ch, rO, lane < cnt ? nops - 1 - n - lane : (int)SW_OOB, 0, 0);
                 n += cnt;
             };
             // (every round takes at least one op or changes the state once per op: the bound is never reached, it only keeps a damaged
@@ -263,12 +214,12 @@ __global__ void __launch_bounds__(256) sw_align_affine_wave(AlignAffineParams p)
                     wr0 = ai - (AA_WIN - 1);
                     wcb = ((aj - 1) & ~15) - (AA_WIN - 16);
                     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-                    aa_v4i v[4];
+                    sw_v4i v[4];
 #pragma unroll
                     for (int q = 0; q < 4; ++q) {
                         const int row = wr0 + 16 * q + (lane >> 2), cb = wcb + 16 * (lane & 3);
                         const bool in = row >= 1 && row <= len && cb >= 0;
-                        v[q] = __builtin_amdgcn_raw_buffer_load_b128(rD, in ? (int)((u32)(row - 1) * qpad + (u32)cb) : (int)AA_OOB, 0, AA_SC1);
+                        v[q] = __builtin_amdgcn_raw_buffer_load_b128(rD, in ? (int)((u32)(row - 1) * qpad + (u32)cb) : (int)SW_OOB, 0, AA_SC1);
                     }
 #pragma unroll
                     for (int q = 0; q < 4; ++q) win[(16 * q + (lane >> 2)) * (AA_WIN / 16) + (lane & 3)] = v[q];
@@ -306,13 +257,13 @@ __global__ void __launch_bounds__(256) sw_align_affine_wave(AlignAffineParams p)
         {
             const __amdgpu_buffer_rsrc_t rA = __builtin_amdgcn_make_buffer_rsrc((void*)(p.aln + it.idx), 0, (int)sizeof(sw_alignment), 0x00020000);
             const bool any = score != 0;
-            const aa_v4i v0 = {(int)(u32)pos, (int)(u32)(pos >> 32), (int)(u32)score, 0};
-            const aa_v4i v1 = {any ? j0 : 0, 0, any ? i0 : 0, 0};
-            const aa_v4i v2 = {any ? j1 : 0, 0, any ? i1 : 0, 0};
+            const sw_v4i v0 = {(int)(u32)pos, (int)(u32)(pos >> 32), (int)(u32)score, 0};
+            const sw_v4i v1 = {any ? j0 : 0, 0, any ? i0 : 0, 0};
+            const sw_v4i v2 = {any ? j1 : 0, 0, any ? i1 : 0, 0};
             __builtin_amdgcn_raw_buffer_store_b128(v0, rA, (int)voffL0, 0, 0);                    // max_pos, max_score
             __builtin_amdgcn_raw_buffer_store_b128(v1, rA, (int)voffL0, 16, 0);                   // q_begin, t_begin
             __builtin_amdgcn_raw_buffer_store_b128(v2, rA, (int)voffL0, 32, 0);                   // q_end, t_end
-            __builtin_amdgcn_raw_buffer_store_b64(aa_v2i{nops, 0}, rA, (int)voffL0, 48, 0);       // nops
+            __builtin_amdgcn_raw_buffer_store_b64(sw_v2i{nops, 0}, rA, (int)voffL0, 48, 0);       // nops
         }
         if (p.stamps) {   // timing aid ("debug_buf"): ticks of the 100 MHz clock spent in fills and in walks, summed over the waves
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");

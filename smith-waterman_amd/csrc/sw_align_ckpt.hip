@@ -34,81 +34,28 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "sw_kernels.h"
+#include "sw_wave.h"
 
 namespace swk {
 
 namespace {
 
-typedef unsigned int u32;
-typedef unsigned long long u64;
-
-constexpr u32 AK_OOB = 0xFFFFFF00u;     // buffer offset beyond every descriptor: the access is dropped (loads return 0)
 constexpr int AK_SC1 = 16;              // aux bit of the buffer builtins: sc1
 
-__device__ __forceinline__ int ak_dpp_shr1(int old, int src) {   // lane l <- lane l-1; lane 0 keeps `old`
-    return __builtin_amdgcn_update_dpp(old, src, 0x138, 0xF, 0xF, false);
-}
-__device__ __forceinline__ int ak_sbyte(u32 w, int j) { return (int)(signed char)(w >> (8 * j)); }
-
-__device__ __forceinline__ int ak_wave_max(int v) {   // max over the 64 lanes, wave-uniform result (v >= 0)
-    v = max(v, __builtin_amdgcn_update_dpp(0, v, 0x111, 0xF, 0xF, true));   // row_shr:1
-    v = max(v, __builtin_amdgcn_update_dpp(0, v, 0x112, 0xF, 0xF, true));   // row_shr:2
-    v = max(v, __builtin_amdgcn_update_dpp(0, v, 0x114, 0xF, 0xF, true));   // row_shr:4
-    v = max(v, __builtin_amdgcn_update_dpp(0, v, 0x118, 0xF, 0xF, true));   // row_shr:8
-    v = max(v, __builtin_amdgcn_update_dpp(0, v, 0x142, 0xA, 0xF, true));   // row_bcast:15
-    v = max(v, __builtin_amdgcn_update_dpp(0, v, 0x143, 0xC, 0xF, true));   // row_bcast:31
-    return __builtin_amdgcn_readlane(v, 63);
-}
-
-typedef int ak_v4i __attribute__((ext_vector_type(4)));
-typedef int ak_v2i __attribute__((ext_vector_type(2)));
-
-template <int C>
-__device__ __forceinline__ void ak_load_row(__amdgpu_buffer_rsrc_t r, u32 off, u32 (&s)[C / 4]) {
-    if constexpr (C == 16) {
-        const ak_v4i v = __builtin_amdgcn_raw_buffer_load_b128(r, (int)off, 0, 0);
-        s[0] = (u32)v.x; s[1] = (u32)v.y; s[2] = (u32)v.z; s[3] = (u32)v.w;
-    } else if constexpr (C == 8) {
-        const ak_v2i v = __builtin_amdgcn_raw_buffer_load_b64(r, (int)off, 0, 0);
-        s[0] = (u32)v.x; s[1] = (u32)v.y;
-    } else {
-        s[0] = __builtin_amdgcn_raw_buffer_load_b32(r, (int)off, 0, 0);
-    }
-}
-// the C direction bytes of one lane and row
-template <int C>
-__device__ __forceinline__ void ak_store_row(__amdgpu_buffer_rsrc_t r, u32 off, const u32 (&d)[C / 4]) {
-    if constexpr (C == 16) __builtin_amdgcn_raw_buffer_store_b128(ak_v4i{(int)d[0], (int)d[1], (int)d[2], (int)d[3]}, r, (int)off, 0, 0);
-    else if constexpr (C == 8) __builtin_amdgcn_raw_buffer_store_b64(ak_v2i{(int)d[0], (int)d[1]}, r, (int)off, 0, 0);
-    else __builtin_amdgcn_raw_buffer_store_b32((int)d[0], r, (int)off, 0, 0);
-}
 // C ints of a lane in a checkpoint row: C / 4 vector stores / sc1 loads of 16 bytes (16 / 32 / 64 bytes per lane)
 template <int C>
 __device__ __forceinline__ void ak_store_ints(__amdgpu_buffer_rsrc_t r, u32 off, const int (&v)[C]) {
 #pragma unroll
     for (int q = 0; q < C / 4; ++q)
-        __builtin_amdgcn_raw_buffer_store_b128(ak_v4i{v[4 * q], v[4 * q + 1], v[4 * q + 2], v[4 * q + 3]}, r, (int)off, 16 * q, 0);
+        __builtin_amdgcn_raw_buffer_store_b128(sw_v4i{v[4 * q], v[4 * q + 1], v[4 * q + 2], v[4 * q + 3]}, r, (int)off, 16 * q, 0);
 }
 template <int C>
 __device__ __forceinline__ void ak_load_ints(__amdgpu_buffer_rsrc_t r, u32 off, int (&v)[C]) {
 #pragma unroll
     for (int q = 0; q < C / 4; ++q) {
-        const ak_v4i x = __builtin_amdgcn_raw_buffer_load_b128(r, (int)off, 16 * q, AK_SC1);
+        const sw_v4i x = __builtin_amdgcn_raw_buffer_load_b128(r, (int)off, 16 * q, AK_SC1);
         v[4 * q] = x.x; v[4 * q + 1] = x.y; v[4 * q + 2] = x.z; v[4 * q + 3] = x.w;
     }
-}
-
-template <int I, int N, typename F>
-__device__ __forceinline__ void ak_for(F&& f) {
-    if constexpr (I < N) {
-        f(std::integral_constant<int, I>{});
-        ak_for<I + 1, N>(f);
-    }
-}
-
-__device__ __forceinline__ int ak_uniform(int v) { return __builtin_amdgcn_readfirstlane(v); }
-__device__ __forceinline__ int64_t ak_uniform64(int64_t v) {
-    return (int64_t)(((u64)(u32)__builtin_amdgcn_readfirstlane((int)(u32)((u64)v >> 32)) << 32) | (u32)__builtin_amdgcn_readfirstlane((int)(u32)(u64)v));
 }
 
 constexpr int AK_WIN = 64;              // the walk's window: AK_WIN rows of AK_WIN direction bytes per wave
@@ -116,7 +63,7 @@ constexpr int AK_WIN = 64;              // the walk's window: AK_WIN rows of AK_
 // What a wave keeps over all its hits: its slot (band, checkpoints, boundary column), its LDS window and the scoring.
 struct AkWave {
     int lane;
-    ak_v4i* win;
+    sw_v4i* win;
     __amdgpu_buffer_rsrc_t rB;           // boundary column of a band
     unsigned char* slot; int64_t slot_bytes;   // per hit: min(B, len) x qpad direction bytes, then its checkpoint rows
     int B, logB;                         // band height
@@ -146,7 +93,7 @@ __device__ __forceinline__ void ak_align_hit(const AkWave& w, const AkHit& hit) 
     const __amdgpu_buffer_rsrc_t rD = __builtin_amdgcn_make_buffer_rsrc((void*)w.slot, 0, (int)band_bytes, 0x00020000);
     const __amdgpu_buffer_rsrc_t rK = __builtin_amdgcn_make_buffer_rsrc((void*)(w.slot + band_bytes), 0, (int)(w.slot_bytes - band_bytes), 0x00020000);
     const int nbands = len > 0 ? (int)(((int64_t)len + B - 1) >> w.logB) : 1;
-    const u32 voffL0 = lane == 0 ? 0u : AK_OOB;
+    const u32 voffL0 = lane == 0 ? 0u : SW_OOB;
     u64 kbest = 0;                         // per lane: best (score << 40 | MASK - index) over the bands and strips done
     int sbest = 1;                         // wave-uniform: highest H seen so far (at least 1: zeros never count)
 
@@ -170,20 +117,20 @@ __device__ __forceinline__ void ak_align_hit(const AkWave& w, const AkHit& hit) 
             const u32 kin = (u32)(b - 1) * 8u * qpad + colb * 4u;
             ak_load_ints<C>(rK, kin, h);
             ak_load_ints<C>(rK, kin + 4u * qpad, e);
-            diag0 = __builtin_amdgcn_raw_buffer_load_b32(rK, colb ? (int)(kin - 4u) : (int)AK_OOB, 0, AK_SC1);   // H[b B][c0 - 1]; column 0: 0
+            diag0 = __builtin_amdgcn_raw_buffer_load_b32(rK, colb ? (int)(kin - 4u) : (int)SW_OOB, 0, AK_SC1);   // H[b B][c0 - 1]; column 0: 0
         } else {
 #pragma unroll
             for (int k = 0; k < C; ++k) { h[k] = 0; e[k] = goe; }
         }
-        ak_v4i bq0 = {0, 0, 0, 0}, bq1 = {0, 0, 0, 0};
-        const u32 voffB = lane == 0 ? 64u * 8u : AK_OOB;
+        sw_v4i bq0 = {0, 0, 0, 0}, bq1 = {0, 0, 0, 0};
+        const u32 voffB = lane == 0 ? 64u * 8u : SW_OOB;
         if (br) {
             bq0 = __builtin_amdgcn_raw_buffer_load_b128(rB, (int)voffB, 0, AK_SC1);
             bq1 = __builtin_amdgcn_raw_buffer_load_b128(rB, (int)voffB, 16, AK_SC1);
         }
         auto raw_of = [&](int g, int j) -> u32 {
             const u32 pos = (u32)(4 * g + j - lane - 1);
-            return (u32)__builtin_amdgcn_raw_buffer_load_b8(rT, (int)(pos < (u32)rows ? pos : AK_OOB), 0, 0);
+            return (u32)__builtin_amdgcn_raw_buffer_load_b8(rT, (int)(pos < (u32)rows ? pos : SW_OOB), 0, 0);
         };
         auto row_off = [&](int g, int j, u32 raw) -> u32 {
             const u32 pos = (u32)(4 * g + j - lane - 1);
@@ -193,7 +140,7 @@ __device__ __forceinline__ void ak_align_hit(const AkWave& w, const AkHit& hit) 
 #pragma unroll
         for (int j = 0; j < 4; ++j) raw[j] = raw_of(0, j);
 #pragma unroll
-        for (int j = 0; j < 4; ++j) ak_load_row<C>(rQ, row_off(0, j, raw[j]), S[j]);
+        for (int j = 0; j < 4; ++j) sw_load_row<C>(rQ, row_off(0, j, raw[j]), S[j]);
 #pragma unroll
         for (int j = 0; j < 4; ++j) raw[j] = raw_of(1, j);
 
@@ -201,7 +148,7 @@ __device__ __forceinline__ void ak_align_hit(const AkWave& w, const AkHit& hit) 
         auto steps4 = [&](auto HOLD_, const int g) __attribute__((always_inline)) {
             constexpr bool HOLD = decltype(HOLD_)::value;
 #pragma unroll
-            for (int j = 0; j < 4; ++j) ak_load_row<C>(rQ, row_off(g + 1, j, raw[j]), Sn[j]);
+            for (int j = 0; j < 4; ++j) sw_load_row<C>(rQ, row_off(g + 1, j, raw[j]), Sn[j]);
 #pragma unroll
             for (int j = 0; j < 4; ++j) raw[j] = raw_of(g + 2, j);
             const int bh[4] = {bq0.x, bq0.z, bq1.x, bq1.z}, bf[4] = {bq0.y, bq0.w, bq1.y, bq1.w};
@@ -209,22 +156,22 @@ __device__ __forceinline__ void ak_align_hit(const AkWave& w, const AkHit& hit) 
                 bq0 = __builtin_amdgcn_raw_buffer_load_b128(rB, (int)voffB, 32 * (g + 1), AK_SC1);
                 bq1 = __builtin_amdgcn_raw_buffer_load_b128(rB, (int)voffB, 32 * (g + 1) + 16, AK_SC1);
             }
-            ak_for<0, 4>([&](auto J) {
+            sw_for<0, 4>([&](auto J) {
                 constexpr int j = decltype(J)::value;
                 const int u = 4 * g + j;
                 const bool held = HOLD && u <= lane;
                 const bool bin = br && u <= rows;
-                const int left = ak_dpp_shr1(bin ? bh[j] : 0, h[C - 1]);
-                int f = ak_dpp_shr1(bin ? bf[j] : goe, fout);
+                const int left = sw_dpp_shr1(bin ? bh[j] : 0, h[C - 1]);
+                int f = sw_dpp_shr1(bin ? bf[j] : goe, fout);
                 int dprev = diag0;
                 if constexpr (HOLD) diag0 = held ? diag0 : left; else diag0 = left;
                 u32 dw[NQ];
 #pragma unroll
                 for (int q = 0; q < NQ; ++q) dw[q] = 0;
-                ak_for<0, C>([&](auto K) {
+                sw_for<0, C>([&](auto K) {
                     constexpr int k = decltype(K)::value;
                     const int old = h[k];
-                    const int t = dprev + ak_sbyte(S[j][k >> 2], k & 3);
+                    const int t = dprev + sw_sbyte(S[j][k >> 2], k & 3);
                     const int ek = e[k];
                     const int hn = max(max(max(t, ek), f), 0);
                     const int x = hn + goe, eg = ek + ge, fg = f + ge;
@@ -243,15 +190,15 @@ __device__ __forceinline__ void ak_align_hit(const AkWave& w, const AkHit& hit) 
                     dprev = old;
                 });
                 fout = f;
-                if (bw) __builtin_amdgcn_raw_buffer_store_b64(ak_v2i{h[C - 1], fout}, rB, lane == 63 ? 8 : (int)AK_OOB, 8 * u, 0);   // band row u - 63 at pair index row + 64
+                if (bw) __builtin_amdgcn_raw_buffer_store_b64(sw_v2i{h[C - 1], fout}, rB, lane == 63 ? 8 : (int)SW_OOB, 8 * u, 0);   // band row u - 63 at pair index row + 64
                 if constexpr (DIR) {   // the direction bytes of band row u - lane, columns c0 .. c0 + C - 1
                     const u32 r1 = (u32)(u - lane - 1);
-                    ak_store_row<C>(rD, r1 < (u32)rows ? r1 * qpad + colb : AK_OOB, dw);
+                    sw_store_row<C>(rD, r1 < (u32)rows ? r1 * qpad + colb : SW_OOB, dw);
                 } else if constexpr (!HOLD) {   // (B >= 64: no checkpoint row within the peeled steps)
                     if (ck_out && u >= B) {     // the lane that has just finished row B of the band: h = H[row], e = E[row + 1]
-                        const u32 off = u - lane == B ? kout : AK_OOB;
+                        const u32 off = u - lane == B ? kout : SW_OOB;
                         ak_store_ints<C>(rK, off, h);
-                        ak_store_ints<C>(rK, off == AK_OOB ? AK_OOB : off + 4u * qpad, e);
+                        ak_store_ints<C>(rK, off == SW_OOB ? SW_OOB : off + 4u * qpad, e);
                     }
                 }
                 // ---- arg-max: the row maximum against the wave's best so far; only a step that reaches it looks for the cell
@@ -262,7 +209,7 @@ __device__ __forceinline__ void ak_align_hit(const AkWave& w, const AkHit& hit) 
                     m = max(m, h[C - 1]);
                     if constexpr (HOLD) m = held ? 0 : m;             // a resumed state is not a row of this band
                     if (__builtin_amdgcn_ballot_w64(m >= sbest) != 0) {
-                        sbest = max(sbest, ak_wave_max(m));
+                        sbest = max(sbest, sw_wave_max(m));
                         int kk = 0;                                   // first column of my row that holds its maximum
 #pragma unroll
                         for (int k = C - 1; k >= 0; --k) kk = (h[k] == m) ? k : kk;
@@ -311,7 +258,7 @@ __device__ __forceinline__ void ak_align_hit(const AkWave& w, const AkHit& hit) 
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     const u64 tick1 = w.stamps ? wall_clock64() : 0;
     u64 refill_ticks = 0;
-    ak_v4i* const win = w.win;
+    sw_v4i* const win = w.win;
     const unsigned char* const winb = (const unsigned char*)win;
     int cur = nbands == 1 ? 0 : -1;            // the band whose direction bytes the slot holds
     int i0 = 0, j0 = 0, nops = 0;
@@ -322,7 +269,7 @@ __device__ __forceinline__ void ak_align_hit(const AkWave& w, const AkHit& hit) 
         bool done = score == 0;
         // `cnt` ops `ch` behind the n already taken: the walk goes backwards, op k from the end lies at nops - 1 - k
         auto emit = [&](int cnt, int ch) {
-            if (pass == 1) __builtin_amdgcn_raw_buffer_store_b8((unsigned char)ch, hit.rO, lane < cnt ? nops - 1 - n - lane : (int)AK_OOB, 0, 0);
+            if (pass == 1) __builtin_amdgcn_raw_buffer_store_b8((unsigned char)ch, hit.rO, lane < cnt ? nops - 1 - n - lane : (int)SW_OOB, 0, 0);
             n += cnt;
         };
         // (every round takes at least one op or changes the state once per op: the bound is never reached, it only keeps a damaged
@@ -350,12 +297,12 @@ __device__ __forceinline__ void ak_align_hit(const AkWave& w, const AkHit& hit) 
                 wr0 = ai - (AK_WIN - 1);
                 wcb = ((aj - 1) & ~15) - (AK_WIN - 16);
                 __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-                ak_v4i v[4];
+                sw_v4i v[4];
 #pragma unroll
                 for (int q = 0; q < 4; ++q) {
                     const int row = wr0 + 16 * q + (lane >> 2), cb = wcb + 16 * (lane & 3);
                     const bool in = row >= bf && row <= bl && cb >= 0;
-                    v[q] = __builtin_amdgcn_raw_buffer_load_b128(rD, in ? (int)((u32)(row - bf) * qpad + (u32)cb) : (int)AK_OOB, 0, AK_SC1);
+                    v[q] = __builtin_amdgcn_raw_buffer_load_b128(rD, in ? (int)((u32)(row - bf) * qpad + (u32)cb) : (int)SW_OOB, 0, AK_SC1);
                 }
 #pragma unroll
                 for (int q = 0; q < 4; ++q) win[(16 * q + (lane >> 2)) * (AK_WIN / 16) + (lane & 3)] = v[q];
@@ -393,13 +340,13 @@ __device__ __forceinline__ void ak_align_hit(const AkWave& w, const AkHit& hit) 
     }
     {
         const bool any = score != 0;
-        const ak_v4i v0 = {(int)(u32)pos, (int)(u32)(pos >> 32), (int)(u32)score, 0};
-        const ak_v4i v1 = {any ? j0 : 0, 0, any ? i0 : 0, 0};
-        const ak_v4i v2 = {any ? j1 : 0, 0, any ? i1 : 0, 0};
+        const sw_v4i v0 = {(int)(u32)pos, (int)(u32)(pos >> 32), (int)(u32)score, 0};
+        const sw_v4i v1 = {any ? j0 : 0, 0, any ? i0 : 0, 0};
+        const sw_v4i v2 = {any ? j1 : 0, 0, any ? i1 : 0, 0};
         __builtin_amdgcn_raw_buffer_store_b128(v0, hit.rA, (int)voffL0, 0, 0);                    // max_pos, max_score
         __builtin_amdgcn_raw_buffer_store_b128(v1, hit.rA, (int)voffL0, 16, 0);                   // q_begin, t_begin
         __builtin_amdgcn_raw_buffer_store_b128(v2, hit.rA, (int)voffL0, 32, 0);                   // q_end, t_end
-        __builtin_amdgcn_raw_buffer_store_b64(ak_v2i{nops, 0}, hit.rA, (int)voffL0, 48, 0);       // nops
+        __builtin_amdgcn_raw_buffer_store_b64(sw_v2i{nops, 0}, hit.rA, (int)voffL0, 48, 0);       // nops
     }
     if (w.stamps) {   // timing aid ("debug_buf", three words here): ticks of the 100 MHz clock in the sweep, the walk and its re-fills
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -418,7 +365,7 @@ __device__ __forceinline__ void ak_align_hit(const AkWave& w, const AkHit& hit) 
 template <int C>
 __global__ void __launch_bounds__(256) sw_align_ckpt_wave(AlignCkptParams p) {
     static_assert(C % 4 == 0 && C <= 16, "C is a multiple of 4");
-    __shared__ ak_v4i win_all[4][AK_WIN * AK_WIN / 16];
+    __shared__ sw_v4i win_all[4][AK_WIN * AK_WIN / 16];
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const int64_t slot = (int64_t)blockIdx.x * (blockDim.x >> 6) + wave;     // resident wave: its own boundary column, band and checkpoints
@@ -431,7 +378,7 @@ __global__ void __launch_bounds__(256) sw_align_ckpt_wave(AlignCkptParams p) {
     w.B = 1 << p.log_band; w.logB = p.log_band;
     w.ge = p.ge; w.goe = p.goe; w.stamps = p.stamps;
     const __amdgpu_buffer_rsrc_t rC = __builtin_amdgcn_make_buffer_rsrc((void*)p.counter, 0, 4, 0x00020000);
-    const u32 voffL0 = lane == 0 ? 0u : AK_OOB;    // lane 0 alone touches the counter
+    const u32 voffL0 = lane == 0 ? 0u : SW_OOB;    // lane 0 alone touches the counter
     const int ops_size = (int)(p.ops ? (p.ops_cap < 0x7FFFFF00ll ? p.ops_cap : 0x7FFFFF00ll) : 0);
     for (;;) {
         // the next hit: a vector buffer atomic of lane 0, read back into a scalar (sw_search_wave says why)
@@ -453,7 +400,7 @@ __global__ void __launch_bounds__(256) sw_align_ckpt_wave(AlignCkptParams p) {
 template <int C>
 __global__ void __launch_bounds__(256) sw_align_hits_ckpt_wave(AlignHitsCkptParams p) {
     static_assert(C % 4 == 0 && C <= 16, "C is a multiple of 4");
-    __shared__ ak_v4i win_all[4][AK_WIN * AK_WIN / 16];
+    __shared__ sw_v4i win_all[4][AK_WIN * AK_WIN / 16];
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const int64_t slot = (int64_t)blockIdx.x * (blockDim.x >> 6) + wave;
@@ -471,19 +418,19 @@ __global__ void __launch_bounds__(256) sw_align_hits_ckpt_wave(AlignHitsCkptPara
     w.B = 1 << p.log_band; w.logB = p.log_band;
     w.ge = p.ge; w.goe = p.goe; w.stamps = nullptr;
     const __amdgpu_buffer_rsrc_t rC = __builtin_amdgcn_make_buffer_rsrc((void*)p.counter, 0, 4, 0x00020000);
-    const u32 voffL0 = lane == 0 ? 0u : AK_OOB;    // lane 0 alone touches the counter
+    const u32 voffL0 = lane == 0 ? 0u : SW_OOB;    // lane 0 alone touches the counter
     const int ops_size = (int)(p.ops ? (p.ops_cap < 0x7FFFFF00ll ? p.ops_cap : 0x7FFFFF00ll) : 0);
     for (;;) {
         const u32 n = (u32)__builtin_amdgcn_readlane(__builtin_amdgcn_raw_ptr_buffer_atomic_add_i32(1, rC, (int)voffL0, 0, 0), 0);
         if (n >= nitems) break;
         // the item and its query: vector loads of wave-uniform addresses; readfirstlane tells the compiler that these are scalars
         const AlignHitItem it = items[n];
-        const MultiQuery d = p.queries[ak_uniform(it.entry)];
-        const int64_t start = ak_uniform64(it.start), out = ak_uniform64(it.out);
+        const MultiQuery d = p.queries[sw_uniform(it.entry)];
+        const int64_t start = sw_uniform64(it.start), out = sw_uniform64(it.out);
         AkHit hit;
-        hit.target = p.db + start; hit.len = ak_uniform(it.len);
-        hit.qpad = (u32)ak_uniform(d.qpad); hit.qlen = ak_uniform(d.qlen); hit.nstrips = ak_uniform(d.nstrips);
-        hit.rQ = __builtin_amdgcn_make_buffer_rsrc((void*)(p.prof + ak_uniform64(d.prof_off)), 0, (int)(SW_SEARCH_ROWS * hit.qpad), 0x00020000);
+        hit.target = p.db + start; hit.len = sw_uniform(it.len);
+        hit.qpad = (u32)sw_uniform(d.qpad); hit.qlen = sw_uniform(d.qlen); hit.nstrips = sw_uniform(d.nstrips);
+        hit.rQ = __builtin_amdgcn_make_buffer_rsrc((void*)(p.prof + sw_uniform64(d.prof_off)), 0, (int)(SW_SEARCH_ROWS * hit.qpad), 0x00020000);
         hit.rO = __builtin_amdgcn_make_buffer_rsrc((void*)(p.ops ? p.ops + out * p.ops_cap : nullptr), 0, ops_size, 0x00020000);
         hit.ops_cap = p.ops_cap; hit.has_ops = p.ops != nullptr;
         hit.rA = __builtin_amdgcn_make_buffer_rsrc((void*)(p.aln + out), 0, (int)sizeof(sw_alignment), 0x00020000);

@@ -159,6 +159,45 @@ static int grow_query_table(sw_ctx* c, size_t need, hipStream_t stream) {
     return SW_OK;
 }
 
+// The lengths of a call's queries, as the planners of the many-query calls take them.
+static std::vector<int64_t> query_lengths(const int64_t* qoffsets, int64_t nqueries) {
+    std::vector<int64_t> qlens((size_t)nqueries);
+    for (int64_t q = 0; q < nqueries; ++q) qlens[(size_t)q] = qoffsets[q + 1] - qoffsets[q];
+    return qlens;
+}
+
+// The start of a many-query call, behind stage_search_call (which has waited for the last uploads from the pinned copies): the plan's
+// table, every entry's qstart taken from the caller's offsets, and behind its entries an optional tail (the pair list's entry_of) go
+// through one pinned copy to c->d_mq in one upload; the scoring table follows through its own.  The event is recorded once, behind BOTH
+// uploads: whoever has waited for it may overwrite either pinned copy.
+static int upload_query_table(sw_ctx* c, hipStream_t stream, const std::vector<swk::MultiQuery>& table, const int64_t* qoffsets, const sw_affine* scoring,
+                              const void* tail = nullptr, size_t tail_bytes = 0) {
+    const size_t nq = table.size(), slots = nq + (tail_bytes + sizeof(swk::MultiQuery) - 1) / sizeof(swk::MultiQuery);
+    if (int rc = grow_query_table(c, slots, stream)) return rc;
+    for (size_t t = 0; t < nq; ++t) {
+        c->h_mq[t] = table[t];
+        c->h_mq[t].qstart = qoffsets[table[t].row];
+    }
+    if (tail_bytes) memcpy(c->h_mq + nq, tail, tail_bytes);
+    memcpy(c->h_submat, scoring->sub, sizeof(sw_submat));
+    HIP_TRY(hipMemcpyAsync(c->d_mq, c->h_mq, slots * sizeof(swk::MultiQuery), hipMemcpyHostToDevice, stream));
+    HIP_TRY(hipMemcpyAsync(c->d_submat, c->h_submat, sizeof(sw_submat), hipMemcpyHostToDevice, stream));
+    HIP_TRY(hipEventRecord(c->sitems_ev, stream));
+    return SW_OK;
+}
+
+// The profiles of a group's queries (the table entries grp.q0 .. grp.q0 + grp.nq - 1) in one launch: every query's profile in shares of
+// about 16 KiB, over at most 4096 workgroups.
+template <typename Group>
+static int launch_group_profiles(sw_ctx* c, hipStream_t stream, const char* d_queries, const Group& grp) {
+    const int parts = (int)std::clamp<int64_t>(grp.prof_bytes / grp.nq / 16384, 1, 4096);
+    const unsigned blocks = (unsigned)std::min<int64_t>(grp.nq * parts, 4096);
+    hipLaunchKernelGGL(swk::sw_search_profile_submat_multi, dim3(blocks), dim3(256), 0, stream, (const unsigned char*)d_queries, c->d_mq + grp.q0, grp.nq,
+                       parts, c->d_sprof, (const signed char*)c->d_submat);
+    HIP_TRY(hipGetLastError());
+    return SW_OK;
+}
+
 // The many-query search of checked arguments into `d_results` (nqueries x ntargets, nqueries > 0, ntargets > 0): what sw_db_search_affine
 // does for a whole call and sw_db_search_affine_top for every chunk of one.  The caller holds the device's launch order (DevOrder).
 static int run_search_multi(sw_ctx* c, const sw_db* db, const char* d_queries, const int64_t* qoffsets, int64_t nqueries, const sw_affine* scoring,
@@ -167,8 +206,7 @@ static int run_search_multi(sw_ctx* c, const sw_db* db, const char* d_queries, c
     HIP_TRY(hipMemsetAsync(d_results, 0, (size_t)nqueries * (size_t)db->ntargets * sizeof(sw_result), stream));
     if (db->nonempty == 0) return SW_OK;
     if (int rc = occupancy_once(kSearchMulti, c->search_multi_per_cu, c->search_multi_per_cu_known)) return rc;
-    std::vector<int64_t> qlens((size_t)nqueries);
-    for (int64_t q = 0; q < nqueries; ++q) qlens[(size_t)q] = qoffsets[q + 1] - qoffsets[q];
+    const std::vector<int64_t> qlens = query_lengths(qoffsets, nqueries);
     swp::SearchMultiJob mj;
     mj.qlens = qlens.data(); mj.nqueries = nqueries; mj.longest = db->longest; mj.nonempty = db->nonempty; mj.num_cus = c->num_cus;
     mj.budget_bytes = c->opt_search_profile_mib << 20;
@@ -177,24 +215,11 @@ static int run_search_multi(sw_ctx* c, const sw_db* db, const char* d_queries, c
     for (const swp::MultiLaunch& l : plan.launch)
         if (c->search_multi_per_cu[l.kernel] < 1) { set_err("the many-query search kernel does not fit a CU on this device"); return SW_EDEVICE; }
     if (int rc = stage_search_call(c, stream, 0, plan.prof_need, plan.bnd_need, scoring->sub)) return rc;
-    if (int rc = grow_query_table(c, (size_t)nqueries, stream)) return rc;
-    for (int64_t t = 0; t < nqueries; ++t) {
-        c->h_mq[t] = plan.table[(size_t)t];
-        c->h_mq[t].qstart = qoffsets[plan.table[(size_t)t].row];
-    }
-    memcpy(c->h_submat, scoring->sub, sizeof(sw_submat));
-    HIP_TRY(hipMemcpyAsync(c->d_mq, c->h_mq, (size_t)nqueries * sizeof(swk::MultiQuery), hipMemcpyHostToDevice, stream));
-    HIP_TRY(hipMemcpyAsync(c->d_submat, c->h_submat, sizeof(sw_submat), hipMemcpyHostToDevice, stream));
-    HIP_TRY(hipEventRecord(c->sitems_ev, stream));   // behind both uploads: whoever has waited for it may overwrite either pinned copy
+    if (int rc = upload_query_table(c, stream, plan.table, qoffsets, scoring)) return rc;
     size_t li = 0;
     for (size_t g = 0; g < plan.group.size(); ++g) {
         const swp::MultiGroup& grp = plan.group[g];
-        // every query's profile in shares of about 16 KiB, over at most 4096 workgroups
-        const int parts = (int)std::clamp<int64_t>(grp.prof_bytes / grp.nq / 16384, 1, 4096);
-        const unsigned blocks = (unsigned)std::min<int64_t>(grp.nq * parts, 4096);
-        hipLaunchKernelGGL(swk::sw_search_profile_submat_multi, dim3(blocks), dim3(256), 0, stream, (const unsigned char*)d_queries, c->d_mq + grp.q0, grp.nq,
-                           parts, c->d_sprof, (const signed char*)c->d_submat);
-        HIP_TRY(hipGetLastError());
+        if (int rc = launch_group_profiles(c, stream, d_queries, grp)) return rc;
         for (; li < plan.launch.size() && plan.launch[li].group == (int)g; ++li) {
             const swp::MultiLaunch& l = plan.launch[li];
             swk::SearchMultiParams sp;
@@ -569,8 +594,7 @@ int sw_db_align_affine_hits(sw_ctx* c, const sw_db* db, const char* d_queries, c
     hipStream_t stream = (hipStream_t)stream_;
     HIP_TRY(hipSetDevice(c->device));
     if (int rc = occupancy_once(kAlignHits, c->align_hits_per_cu, c->align_hits_per_cu_known)) return rc;
-    std::vector<int64_t> qlens((size_t)nqueries);
-    for (int64_t q = 0; q < nqueries; ++q) qlens[(size_t)q] = qoffsets[q + 1] - qoffsets[q];
+    const std::vector<int64_t> qlens = query_lengths(qoffsets, nqueries);
     swp::AlignHitsJob aj;
     aj.qlens = qlens.data(); aj.nqueries = nqueries; aj.top = top; aj.longest = db->longest; aj.num_cus = c->num_cus;
     aj.profile_budget_bytes = c->opt_search_profile_mib << 20; aj.budget_bytes = c->opt_align_workspace_mib << 20;
@@ -606,29 +630,17 @@ int sw_db_align_affine_hits(sw_ctx* c, const sw_db* db, const char* d_queries, c
     for (const swp::AlignHitsLaunch& l : plan.launch)
         if ((ckpt ? c->align_hits_ckpt_per_cu : c->align_hits_per_cu)[l.kernel] < 1) { set_err("the hit-table alignment kernel does not fit a CU on this device"); return SW_EDEVICE; }
     if (int rc = stage_search_call(c, stream, 0, plan.prof_need, plan.bnd_need, scoring->sub)) return rc;
-    if (int rc = grow_query_table(c, (size_t)nqueries, stream)) return rc;
     bool fresh = false;
     if (int rc = grow_workspace((void**)&c->d_adir, c->adir_cap, plan.dir_need, 1, 0, stream, fresh)) return rc;
     if (int rc = grow_workspace((void**)&c->d_ahitems, c->ahitems_cap, plan.items_need, sizeof(swk::AlignHitItem), 0, stream, fresh)) return rc;
     if (!c->d_ahctl) HIP_TRY(hipMalloc((void**)&c->d_ahctl, sizeof(swk::AlignHitsCtl)));
     if (!c->d_ahfilled) HIP_TRY(hipMalloc((void**)&c->d_ahfilled, 64));
     HIP_TRY(hipMemsetAsync(c->d_ahfilled, 0, 4, stream));
-    for (int64_t t = 0; t < nqueries; ++t) {
-        c->h_mq[t] = plan.table[(size_t)t];
-        c->h_mq[t].qstart = qoffsets[plan.table[(size_t)t].row];
-    }
-    memcpy(c->h_submat, scoring->sub, sizeof(sw_submat));
-    HIP_TRY(hipMemcpyAsync(c->d_mq, c->h_mq, (size_t)nqueries * sizeof(swk::MultiQuery), hipMemcpyHostToDevice, stream));
-    HIP_TRY(hipMemcpyAsync(c->d_submat, c->h_submat, sizeof(sw_submat), hipMemcpyHostToDevice, stream));
-    HIP_TRY(hipEventRecord(c->sitems_ev, stream));   // behind both uploads: whoever has waited for it may overwrite either pinned copy
+    if (int rc = upload_query_table(c, stream, plan.table, qoffsets, scoring)) return rc;
     size_t li = 0;
     for (size_t g = 0; g < plan.group.size(); ++g) {
         const swp::AlignHitsGroup& grp = plan.group[g];
-        const int parts = (int)std::clamp<int64_t>(grp.prof_bytes / grp.nq / 16384, 1, 4096);
-        const unsigned blocks = (unsigned)std::min<int64_t>(grp.nq * parts, 4096);
-        hipLaunchKernelGGL(swk::sw_search_profile_submat_multi, dim3(blocks), dim3(256), 0, stream, (const unsigned char*)d_queries, c->d_mq + grp.q0, grp.nq,
-                           parts, c->d_sprof, (const signed char*)c->d_submat);
-        HIP_TRY(hipGetLastError());
+        if (int rc = launch_group_profiles(c, stream, d_queries, grp)) return rc;
         // the lists of the group: counts, cursors and work counters start at zero
         HIP_TRY(hipMemsetAsync(c->d_ahctl, 0, sizeof(swk::AlignHitsCtl), stream));
         swk::AlignHitsBinParams bp;
@@ -710,8 +722,7 @@ int sw_db_search_affine_pairs(sw_ctx* c, const sw_db* db, const char* d_queries,
     HIP_TRY(hipMemsetAsync(d_results, 0, (size_t)npairs * sizeof(sw_result), stream));
     if (nqueries == 0 || db->nonempty == 0) return SW_OK;
     if (int rc = occupancy_once(kSearchPairs, c->search_pairs_per_cu, c->search_pairs_per_cu_known)) return rc;
-    std::vector<int64_t> qlens((size_t)nqueries);
-    for (int64_t q = 0; q < nqueries; ++q) qlens[(size_t)q] = qoffsets[q + 1] - qoffsets[q];
+    const std::vector<int64_t> qlens = query_lengths(qoffsets, nqueries);
     swp::SearchPairsJob pj;
     pj.qlens = qlens.data(); pj.nqueries = nqueries; pj.npairs = npairs; pj.longest = db->longest; pj.num_cus = c->num_cus;
     pj.budget_bytes = c->opt_search_profile_mib << 20; pj.chunk = c->opt_search_pairs_chunk;
@@ -720,29 +731,15 @@ int sw_db_search_affine_pairs(sw_ctx* c, const sw_db* db, const char* d_queries,
     for (const swp::PairsLaunch& l : plan.launch)
         if (c->search_pairs_per_cu[l.kernel] < 1) { set_err("the pair-list search kernel does not fit a CU on this device"); return SW_EDEVICE; }
     if (int rc = stage_search_call(c, stream, 0, plan.prof_need, plan.bnd_need, scoring->sub)) return rc;
-    // the table and, behind its nqueries entries, entry_of (4 bytes per query): one pinned copy, one upload
-    const size_t entry_slots = ((size_t)nqueries * sizeof(int32_t) + sizeof(swk::MultiQuery) - 1) / sizeof(swk::MultiQuery);
-    if (int rc = grow_query_table(c, (size_t)nqueries + entry_slots, stream)) return rc;
     bool fresh = false;
     if (int rc = grow_workspace((void**)&c->d_spitems, c->spitems_cap, plan.items_need, 1, 0, stream, fresh)) return rc;
     if (!c->d_spctl) HIP_TRY(hipMalloc((void**)&c->d_spctl, sizeof(swk::SearchPairsCtl)));
-    for (int64_t t = 0; t < nqueries; ++t) {
-        c->h_mq[t] = plan.table[(size_t)t];
-        c->h_mq[t].qstart = qoffsets[plan.table[(size_t)t].row];
-    }
-    memcpy(c->h_mq + nqueries, plan.entry_of.data(), (size_t)nqueries * sizeof(int32_t));
-    memcpy(c->h_submat, scoring->sub, sizeof(sw_submat));
-    HIP_TRY(hipMemcpyAsync(c->d_mq, c->h_mq, ((size_t)nqueries + entry_slots) * sizeof(swk::MultiQuery), hipMemcpyHostToDevice, stream));
-    HIP_TRY(hipMemcpyAsync(c->d_submat, c->h_submat, sizeof(sw_submat), hipMemcpyHostToDevice, stream));
-    HIP_TRY(hipEventRecord(c->sitems_ev, stream));   // behind both uploads: whoever has waited for it may overwrite either pinned copy
+    // behind the table's nqueries entries: entry_of (4 bytes per query)
+    if (int rc = upload_query_table(c, stream, plan.table, qoffsets, scoring, plan.entry_of.data(), (size_t)nqueries * sizeof(int32_t))) return rc;
     size_t l0 = 0;
     for (size_t g = 0; g < plan.group.size(); ++g) {
         const swp::PairsGroup& grp = plan.group[g];
-        const int parts = (int)std::clamp<int64_t>(grp.prof_bytes / grp.nq / 16384, 1, 4096);
-        const unsigned blocks = (unsigned)std::min<int64_t>(grp.nq * parts, 4096);
-        hipLaunchKernelGGL(swk::sw_search_profile_submat_multi, dim3(blocks), dim3(256), 0, stream, (const unsigned char*)d_queries, c->d_mq + grp.q0, grp.nq,
-                           parts, c->d_sprof, (const signed char*)c->d_submat);
-        HIP_TRY(hipGetLastError());
+        if (int rc = launch_group_profiles(c, stream, d_queries, grp)) return rc;
         size_t l1 = l0;
         while (l1 < plan.launch.size() && plan.launch[l1].group == (int)g) ++l1;
         for (int64_t ch = 0; ch < plan.nchunks; ++ch) {

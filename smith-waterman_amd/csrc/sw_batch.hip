@@ -18,16 +18,13 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "sw_kernels.h"
+#include "sw_wave.h"
 
 namespace swk {
 
-typedef unsigned int u32;
-typedef unsigned long long u64;
-
-constexpr u32 SB_OOB = 0xFFFFFF00u;
 #ifndef SB_RUN
 #define SB_RUN 256                         // bytes of one row that a lane group stores with one instruction (int8 P)
-#endif      // buffer offset beyond every descriptor: the store is dropped
+#endif
 
 // Letter codes of every pair's b (rank of the byte value among the values present in the batch, 0..7) in a padded copy:
 // bcode[pair * per + front + i] = code(b[i]); 0x0D outside the sequence -- as a v_perm_b32 selector byte that yields 0xFF, the
@@ -69,21 +66,6 @@ __global__ void __launch_bounds__(256) sw_batch_codes(const unsigned char* __res
         }
 }
 
-__device__ __forceinline__ int sb_dpp_shr1(int old, int src) {   // lane l <- lane l-1; lane 0 keeps `old`
-    return __builtin_amdgcn_update_dpp(old, src, 0x138, 0xF, 0xF, false);
-}
-__device__ __forceinline__ int sb_sbyte(u32 w, int j) { return (int)(signed char)(w >> (8 * j)); }
-
-__device__ __forceinline__ int sb_wave_max(int v) {   // max over the 64 lanes, wave-uniform result (v >= 0)
-    v = max(v, __builtin_amdgcn_update_dpp(0, v, 0x111, 0xF, 0xF, true));   // row_shr:1
-    v = max(v, __builtin_amdgcn_update_dpp(0, v, 0x112, 0xF, 0xF, true));   // row_shr:2
-    v = max(v, __builtin_amdgcn_update_dpp(0, v, 0x114, 0xF, 0xF, true));   // row_shr:4
-    v = max(v, __builtin_amdgcn_update_dpp(0, v, 0x118, 0xF, 0xF, true));   // row_shr:8
-    v = max(v, __builtin_amdgcn_update_dpp(0, v, 0x142, 0xA, 0xF, true));   // row_bcast:15
-    v = max(v, __builtin_amdgcn_update_dpp(0, v, 0x143, 0xC, 0xF, true));   // row_bcast:31
-    return __builtin_amdgcn_readlane(v, 63);
-}
-
 // P code of a cell, deposited as byte BYTE of the packed register `acc` in ONE select: acc.byte = (h == 0) ? 0 : p
 template <int BYTE>
 __device__ __forceinline__ void sb_deposit(u32& acc, int p, int h, int zero) {
@@ -101,19 +83,9 @@ __device__ __forceinline__ void sb_deposit(u32& acc, int p, int h, int zero) {
             : "+v"(acc) : "v"(p), "v"(h), "v"(zero) : "vcc");
 }
 
-template <int I, int N, typename F>
-__device__ __forceinline__ void sb_for(F&& f) {
-    if constexpr (I < N) {
-        f(std::integral_constant<int, I>{});
-        sb_for<I + 1, N>(f);
-    }
-}
-
-typedef int sb_v4i __attribute__((ext_vector_type(4)));
-typedef int sb_v2i __attribute__((ext_vector_type(2)));
 template <int C> struct SbSeg { typedef int type; };            // C packed P codes of one lane and row
-template <> struct SbSeg<8> { typedef sb_v2i type; };
-template <> struct SbSeg<16> { typedef sb_v4i type; };
+template <> struct SbSeg<8> { typedef sw_v2i type; };
+template <> struct SbSeg<16> { typedef sw_v4i type; };
 
 // C: columns per lane (4, 8, 16); PB: bytes per P element written (0: P not written, 1: int8, 4: int32)
 template <int C, int PB>
@@ -172,8 +144,8 @@ __global__ void __launch_bounds__(256) sw_batch_wave(BatchParams p) {
         // output offsets of my row segment at step u = 0 (row -lane): wraps to a huge unsigned offset above the matrix, runs past
         // the descriptor below it -- stores outside rows 0..rows are dropped by the bounds check.  (Row 0 is stored too: H = P = 0.)
         const bool full = nval == C && !(p.debug & DBG_NO_STORES);   // (debug bit 0: drop the matrix stores, timing experiments)
-        u32 voffH = (full && wh) ? (u32)((-lane * M + c0) * 4) : SB_OOB;
-        u32 voffP = (full && wp) ? (u32)((-lane * M + c0) * PB) : SB_OOB;
+        u32 voffH = (full && wh) ? (u32)((-lane * M + c0) * 4) : SW_OOB;
+        u32 voffP = (full && wp) ? (u32)((-lane * M + c0) * PB) : SW_OOB;
         // int8 P: delayed stores through the LDS ring (see the store below): this lane's piece leaves 1 + dly steps late
         constexpr int GS = PB == 1 ? SB_RUN / C : 1;
         const int dly = GS - 1 - (lane & (GS - 1));
@@ -182,15 +154,15 @@ __global__ void __launch_bounds__(256) sw_batch_wave(BatchParams p) {
         typedef typename SbSeg<C>::type SegT;
         SegT dseg = {};
         const bool col0 = st == 0 && lane == 0;
-        u32 voffH0 = (wh && col0) ? 0u : SB_OOB, voffP0 = (wp && col0) ? 0u : SB_OOB;   // column 0
+        u32 voffH0 = (wh && col0) ? 0u : SW_OOB, voffP0 = (wp && col0) ? 0u : SW_OOB;   // column 0
         // (lanes that do not store keep their out-of-range offset: pitch 0)
         const u32 pitchH = full ? (u32)(M * 4) : 0u, pitchP = full ? (u32)(M * PB) : 0u;
         const u32 pitchH0 = col0 ? (u32)(M * 4) : 0u, pitchP0 = col0 ? (u32)(M * PB) : 0u;
         // boundary column: lane 63 writes its last column (row u - 63) for the next strip, lane 0 reads row u of the previous one
         const bool bw = multi && st + 1 < nstrips, br = multi && st > 0;
         // (sc1 loads: served from L2, which this wave's own earlier stores have reached once vmcnt has drained)
-        sb_v4i bq = {0, 0, 0, 0};
-        const u32 voffB = lane == 0 ? 64u * 4u : SB_OOB;
+        sw_v4i bq = {0, 0, 0, 0};
+        const u32 voffB = lane == 0 ? 64u * 4u : SW_OOB;
         if (br) {
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             bq = __builtin_amdgcn_raw_buffer_load_b128(rB, (int)voffB, 0, 16);
@@ -204,23 +176,23 @@ __global__ void __launch_bounds__(256) sw_batch_wave(BatchParams p) {
             u32 S[C];
 #pragma unroll
             for (int k = 0; k < C; ++k) S[k] = __builtin_amdgcn_perm(hi[k], lo[k], selw);
-            const sb_v4i bcur = bq;
+            const sw_v4i bcur = bq;
             if (br) bq = __builtin_amdgcn_raw_buffer_load_b128(rB, (int)voffB, 16 * (g + 1), 16);
 
-            sb_for<0, 4>([&](auto J) {
+            sw_for<0, 4>([&](auto J) {
                 constexpr int j = decltype(J)::value;
                 const int u = 4 * g + j;
-                const int left = sb_dpp_shr1(br ? bcur[j] : 0, h[C - 1]);
+                const int left = sw_dpp_shr1(br ? bcur[j] : 0, h[C - 1]);
                 int dprev = diag0, prev = left;
                 diag0 = left;
                 u32 pk[C / 4];
                 int p32[C];
 #pragma unroll
                 for (int q = 0; q < C / 4; ++q) pk[q] = 0;
-                sb_for<0, C>([&](auto K) {
+                sw_for<0, C>([&](auto K) {
                     constexpr int k = decltype(K)::value;
                     const int old = h[k];
-                    const int t = dprev + sb_sbyte(S[k], j);
+                    const int t = dprev + sw_sbyte(S[k], j);
                     const int u2 = max(old, prev);
                     const int hn = max(max(t, u2 - ngap), 0);
                     if constexpr (PB != 0) {
@@ -237,7 +209,7 @@ __global__ void __launch_bounds__(256) sw_batch_wave(BatchParams p) {
                 if (wh) {
 #pragma unroll
                     for (int q = 0; q < C / 4; ++q) {
-                        const sb_v4i v = {h[4 * q], h[4 * q + 1], h[4 * q + 2], h[4 * q + 3]};
+                        const sw_v4i v = {h[4 * q], h[4 * q + 1], h[4 * q + 2], h[4 * q + 3]};
                         __builtin_amdgcn_raw_buffer_store_b128(v, rH, (int)voffH, 16 * q, 0);
                     }
                     __builtin_amdgcn_raw_buffer_store_b32(0, rH, (int)voffH0, 0, 0);
@@ -251,7 +223,7 @@ __global__ void __launch_bounds__(256) sw_batch_wave(BatchParams p) {
                 if constexpr (PB == 4) {
 #pragma unroll
                     for (int q = 0; q < C / 4; ++q) {
-                        const sb_v4i v = {p32[4 * q], p32[4 * q + 1], p32[4 * q + 2], p32[4 * q + 3]};
+                        const sw_v4i v = {p32[4 * q], p32[4 * q + 1], p32[4 * q + 2], p32[4 * q + 3]};
                         __builtin_amdgcn_raw_buffer_store_b128(v, rP, (int)voffP, 16 * q, 0);
                     }
                     __builtin_amdgcn_raw_buffer_store_b32(0, rP, (int)voffP0, 0, 0);
@@ -286,7 +258,7 @@ __global__ void __launch_bounds__(256) sw_batch_wave(BatchParams p) {
                     }
                     voffP += pitchP; voffP0 += pitchP0;
                 }
-                if (bw) __builtin_amdgcn_raw_buffer_store_b32(h[C - 1], rB, lane == 63 ? 4 : (int)SB_OOB, 4 * u, 0);   // row u - 63 at index row + 64
+                if (bw) __builtin_amdgcn_raw_buffer_store_b32(h[C - 1], rB, lane == 63 ? 4 : (int)SW_OOB, 4 * u, 0);   // row u - 63 at index row + 64
                 // ---- arg-max: the row maximum against the wave's best so far; only a step that reaches it looks for the cell.
                 // (Cells outside the matrix need no masking here: such a cell never exceeds a cell of the matrix computed before
                 // it -- it scores -1 against everything -- so it cannot raise `sbest` and a record it leaves in a lane loses
@@ -296,7 +268,7 @@ __global__ void __launch_bounds__(256) sw_batch_wave(BatchParams p) {
                 for (int k = 1; k + 1 < C; k += 2) m = max(max(m, h[k]), h[k + 1]);
                 m = max(m, h[C - 1]);
                 if (__builtin_amdgcn_ballot_w64(m >= sbest) != 0) {
-                    sbest = max(sbest, sb_wave_max(m));
+                    sbest = max(sbest, sw_wave_max(m));
                     int kk = 0;                                   // first column of my row that holds its maximum
 #pragma unroll
                     for (int k = C - 1; k >= 0; --k) kk = (h[k] == m) ? k : kk;
@@ -490,13 +462,13 @@ __global__ void __launch_bounds__(256, PB1 ? 2 : (LE4 ? 4 : 3)) sw_batch_wave16(
         const int nval = min(C, max(0, cols - c0 + 1));
         const bool full = PB1 && nval == C && !(p.debug & DBG_NO_STORES);
         int foff = 0;
-        u32 voffP = full ? (u32)(-lane * M + c0) - (u32)((1 + dly) * M) : SB_OOB;
+        u32 voffP = full ? (u32)(-lane * M + c0) - (u32)((1 + dly) * M) : SW_OOB;
         const bool col0 = PB1 && st == 0 && lane == 0;
-        u32 voffP0 = col0 ? 0u : SB_OOB;
+        u32 voffP0 = col0 ? 0u : SW_OOB;
         const u32 pitchP = full ? (u32)M : 0u, pitchP0 = col0 ? (u32)M : 0u;
-        sb_v2i dw = {0, 0};        // the delayed row's codes, two bits each: .x pair A, .y pair B
-        sb_v4i bq = {0, 0, 0, 0};
-        const u32 voffB = lane == 0 ? 64u * 4u : SB_OOB;
+        sw_v2i dw = {0, 0};        // the delayed row's codes, two bits each: .x pair A, .y pair B
+        sw_v4i bq = {0, 0, 0, 0};
+        const u32 voffB = lane == 0 ? 64u * 4u : SW_OOB;
         if (br) {
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             bq = __builtin_amdgcn_raw_buffer_load_b128(rB, (int)voffB, 0, 16);
@@ -515,17 +487,17 @@ __global__ void __launch_bounds__(256, PB1 ? 2 : (LE4 ? 4 : 3)) sw_batch_wave16(
                 SA[k] = __builtin_amdgcn_perm(LE4 ? loA[k] : hiA[k], loA[k], selA);
                 SB[k] = __builtin_amdgcn_perm(LE4 ? loB[k] : hiB[k], loB[k], selB);
             }
-            const sb_v4i bcur = bq;
+            const sw_v4i bcur = bq;
             if (br) bq = __builtin_amdgcn_raw_buffer_load_b128(rB, (int)voffB, 16 * (g + 1), 16);
 
-            sb_for<0, 4>([&](auto J) {
+            sw_for<0, 4>([&](auto J) {
                 constexpr int j = decltype(J)::value;
                 const int u = 4 * g + j;
-                const u32 left = (u32)sb_dpp_shr1(br ? bcur[j] : 0, (int)h[C - 1]);
+                const u32 left = (u32)sw_dpp_shr1(br ? bcur[j] : 0, (int)h[C - 1]);
                 u32 dprev = diag0, prev = left;
                 diag0 = left;
                 u32 pc[PB1 ? C : 1];
-                sb_for<0, C>([&](auto K) {
+                sw_for<0, C>([&](auto K) {
                     constexpr int k = decltype(K)::value;
                     const u32 old = h[k];
                     u32 hn;
@@ -539,23 +511,23 @@ __global__ void __launch_bounds__(256, PB1 ? 2 : (LE4 ? 4 : 3)) sw_batch_wave16(
                     // byte j of a pair's word: the codes of columns j, j + 4, j + 8, j + 12 at two bits each (Horner in packed arithmetic,
                     // halves = pairs); two v_perm_b32 separate the pairs
                     u32 nib[4];
-                    sb_for<0, 4>([&](auto Jc) {
+                    sw_for<0, 4>([&](auto Jc) {
                         constexpr int jc = decltype(Jc)::value;
                         nib[jc] = pk_mad_u16_sb(pk_mad_u16_sb(pk_mad_u16_sb(pc[jc + 12], 0x00040004u, pc[jc + 8]), 0x00040004u, pc[jc + 4]), 0x00040004u, pc[jc]);
                     });
                     const u32 X = pk_mad_u16_sb(nib[1], 0x01000100u, nib[0]), Y = pk_mad_u16_sb(nib[3], 0x01000100u, nib[2]);
-                    const sb_v2i w = {(int)__builtin_amdgcn_perm(Y, X, 0x05040100u), (int)__builtin_amdgcn_perm(Y, X, 0x07060302u)};
+                    const sw_v2i w = {(int)__builtin_amdgcn_perm(Y, X, 0x05040100u), (int)__builtin_amdgcn_perm(Y, X, 0x07060302u)};
                     // the row that left the ring a step ago, expanded to bytes: output dword k = (w >> 2k) & 0x03030303
                     const u32 m3 = 0x03030303u, dA = (u32)dw.x, dB = (u32)dw.y;
-                    const sb_v4i dsegA = {(int)(dA & m3), (int)((dA >> 2) & m3), (int)((dA >> 4) & m3), (int)((dA >> 6) & m3)};
-                    const sb_v4i dsegB = {(int)(dB & m3), (int)((dB >> 2) & m3), (int)((dB >> 4) & m3), (int)((dB >> 6) & m3)};
+                    const sw_v4i dsegA = {(int)(dA & m3), (int)((dA >> 2) & m3), (int)((dA >> 4) & m3), (int)((dA >> 6) & m3)};
+                    const sw_v4i dsegB = {(int)(dB & m3), (int)((dB >> 2) & m3), (int)((dB >> 4) & m3), (int)((dB >> 6) & m3)};
                     // (streaming: 3150-3190 GCUPS against 2890 write-back -- a row is written once and read much later, by the traceback)
                     __builtin_amdgcn_raw_buffer_store_b128(dsegA, rPA, (int)voffP, 0, 2);
                     __builtin_amdgcn_raw_buffer_store_b128(dsegB, rPB, (int)voffP, 0, 2);
                     dw = w;                                                          // (lane 63 waits for nobody)
                     if (dly) {
-                        dw = *(const sb_v2i*)(fifo + foff);                          // what I produced 63 - lane steps ago ...
-                        *(sb_v2i*)(fifo + foff) = w;                                 // ... makes room for this step's
+                        dw = *(const sw_v2i*)(fifo + foff);                          // what I produced 63 - lane steps ago ...
+                        *(sw_v2i*)(fifo + foff) = w;                                 // ... makes room for this step's
                         foff = foff + 8 == flen ? 0 : foff + 8;
                     }
                     __builtin_amdgcn_raw_buffer_store_b8((unsigned char)0, rPA, (int)voffP0, 0, 0);     // column 0
@@ -571,14 +543,14 @@ __global__ void __launch_bounds__(256, PB1 ? 2 : (LE4 ? 4 : 3)) sw_batch_wave16(
                     }
                     voffP += pitchP; voffP0 += pitchP0;
                 }
-                if (bw) __builtin_amdgcn_raw_buffer_store_b32((int)h[C - 1], rB, lane == 63 ? 4 : (int)SB_OOB, 4 * u, 0);   // row u - 63 at index row + 64
+                if (bw) __builtin_amdgcn_raw_buffer_store_b32((int)h[C - 1], rB, lane == 63 ? 4 : (int)SW_OOB, 4 * u, 0);   // row u - 63 at index row + 64
                 // ---- arg-max: tree of row maxima, first column that holds the maximum, strict update of the lane's record
                 auto sel = [&](u32 b, u32 x, u32 y) { return pk_mad_u16(b, pk_sub_u16(y, x), x); };    // b ? y : x  (b = 0 / 1 per half)
                 const u32 upk = (u32)__builtin_amdgcn_readfirstlane(u * 0x00010001);
                 if constexpr (K12) {
                     // keys: score * 16 + (15 - column): the maximum key is the highest score in its lowest column; lbest holds the lane's best KEY
                     u32 n1[8], n2[4];
-                    sb_for<0, 8>([&](auto I) {
+                    sw_for<0, 8>([&](auto I) {
                         constexpr int i = decltype(I)::value;
                         n1[i] = pk_max_u16(pk_mad_u16_sc(h[2 * i], sixteen2, (u32)(15 - 2 * i) * 0x00010001u), pk_mad_u16_sc(h[2 * i + 1], sixteen2, (u32)(14 - 2 * i) * 0x00010001u));
                     });

@@ -23,13 +23,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "sw_kernels.h"
+#include "sw_wave.h"
 
 namespace swk {
-
-typedef unsigned int u32;
-typedef unsigned long long u64;
-
-constexpr u32 SS_OOB = 0xFFFFFF00u;     // buffer offset beyond every descriptor: the access is dropped (loads return 0)
 
 // prof[x * qpad + c], x = 0..256, c = 0..qpad-1: the score of query column c + 1 against byte value x (row 256 and columns >= qlen: -1).
 // WIDE: 1 (match) / 0 (mismatch) / -1 instead of the scores.
@@ -44,46 +40,6 @@ __global__ void __launch_bounds__(256) sw_search_profile(const unsigned char* __
             v = wide ? (eq ? 1 : 0) : (eq ? match : mismatch);
         }
         prof[i] = (signed char)v;
-    }
-}
-
-__device__ __forceinline__ int ss_dpp_shr1(int old, int src) {   // lane l <- lane l-1; lane 0 keeps `old`
-    return __builtin_amdgcn_update_dpp(old, src, 0x138, 0xF, 0xF, false);
-}
-__device__ __forceinline__ int ss_sbyte(u32 w, int j) { return (int)(signed char)(w >> (8 * j)); }
-
-__device__ __forceinline__ int ss_wave_max(int v) {   // max over the 64 lanes, wave-uniform result (v >= 0)
-    v = max(v, __builtin_amdgcn_update_dpp(0, v, 0x111, 0xF, 0xF, true));   // row_shr:1
-    v = max(v, __builtin_amdgcn_update_dpp(0, v, 0x112, 0xF, 0xF, true));   // row_shr:2
-    v = max(v, __builtin_amdgcn_update_dpp(0, v, 0x114, 0xF, 0xF, true));   // row_shr:4
-    v = max(v, __builtin_amdgcn_update_dpp(0, v, 0x118, 0xF, 0xF, true));   // row_shr:8
-    v = max(v, __builtin_amdgcn_update_dpp(0, v, 0x142, 0xA, 0xF, true));   // row_bcast:15
-    v = max(v, __builtin_amdgcn_update_dpp(0, v, 0x143, 0xC, 0xF, true));   // row_bcast:31
-    return __builtin_amdgcn_readlane(v, 63);
-}
-
-typedef int ss_v4i __attribute__((ext_vector_type(4)));
-typedef int ss_v2i __attribute__((ext_vector_type(2)));
-
-// the C profile bytes of one lane and row (C / 4 dwords)
-template <int C>
-__device__ __forceinline__ void ss_load_row(__amdgpu_buffer_rsrc_t r, u32 off, u32 (&s)[C / 4]) {
-    if constexpr (C == 16) {
-        const ss_v4i v = __builtin_amdgcn_raw_buffer_load_b128(r, (int)off, 0, 0);
-        s[0] = (u32)v.x; s[1] = (u32)v.y; s[2] = (u32)v.z; s[3] = (u32)v.w;
-    } else if constexpr (C == 8) {
-        const ss_v2i v = __builtin_amdgcn_raw_buffer_load_b64(r, (int)off, 0, 0);
-        s[0] = (u32)v.x; s[1] = (u32)v.y;
-    } else {
-        s[0] = __builtin_amdgcn_raw_buffer_load_b32(r, (int)off, 0, 0);
-    }
-}
-
-template <int I, int N, typename F>
-__device__ __forceinline__ void ss_for(F&& f) {
-    if constexpr (I < N) {
-        f(std::integral_constant<int, I>{});
-        ss_for<I + 1, N>(f);
     }
 }
 
@@ -105,7 +61,7 @@ __global__ void __launch_bounds__(256) sw_search_wave(SearchParams p) {
     const __amdgpu_buffer_rsrc_t rQ = __builtin_amdgcn_make_buffer_rsrc((void*)p.prof, 0, (int)(SW_SEARCH_ROWS * p.qpad), 0x00020000);
     const u32 qpad = (u32)p.qpad;
     const __amdgpu_buffer_rsrc_t rC = __builtin_amdgcn_make_buffer_rsrc((void*)p.counter, 0, 4, 0x00020000);
-    const u32 voffL0 = lane == 0 ? 0u : SS_OOB;    // lane 0 alone touches the counter and the result
+    const u32 voffL0 = lane == 0 ? 0u : SW_OOB;    // lane 0 alone touches the counter and the result
 
     for (;;) {
         // the next target: a vector buffer atomic of lane 0 (the other lanes' offsets lie beyond the descriptor: dropped), read
@@ -130,8 +86,8 @@ __global__ void __launch_bounds__(256) sw_search_wave(SearchParams p) {
             int diag0 = 0, lbest = 0, lk = 0, lstep = 0;
             // boundary column: lane 63 writes its last column (row u - 63) for the next strip, lane 0 reads row u of the previous one
             const bool bw = multi && st + 1 < nstrips, br = multi && st > 0;
-            ss_v4i bq = {0, 0, 0, 0};
-            const u32 voffB = lane == 0 ? 64u * 4u : SS_OOB;
+            sw_v4i bq = {0, 0, 0, 0};
+            const u32 voffB = lane == 0 ? 64u * 4u : SW_OOB;
             if (br) {   // (sc1 loads: served from L2, which this wave's own earlier stores have reached once vmcnt has drained)
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
                 bq = __builtin_amdgcn_raw_buffer_load_b128(rB, (int)voffB, 0, 16);
@@ -139,7 +95,7 @@ __global__ void __launch_bounds__(256) sw_search_wave(SearchParams p) {
             // row r = 4 g + j - lane of this lane reads target byte r - 1; outside 1..len it takes the PAD row
             auto raw_of = [&](int g, int j) -> u32 {
                 const u32 pos = (u32)(4 * g + j - lane - 1);
-                return (u32)__builtin_amdgcn_raw_buffer_load_b8(rT, (int)(pos < (u32)len ? pos : SS_OOB), 0, 0);
+                return (u32)__builtin_amdgcn_raw_buffer_load_b8(rT, (int)(pos < (u32)len ? pos : SW_OOB), 0, 0);
             };
             auto row_off = [&](int g, int j, u32 raw) -> u32 {
                 const u32 pos = (u32)(4 * g + j - lane - 1);
@@ -150,29 +106,29 @@ __global__ void __launch_bounds__(256) sw_search_wave(SearchParams p) {
 #pragma unroll
             for (int j = 0; j < 4; ++j) raw[j] = raw_of(0, j);
 #pragma unroll
-            for (int j = 0; j < 4; ++j) ss_load_row<C>(rQ, row_off(0, j, raw[j]), S[j]);
+            for (int j = 0; j < 4; ++j) sw_load_row<C>(rQ, row_off(0, j, raw[j]), S[j]);
 #pragma unroll
             for (int j = 0; j < 4; ++j) raw[j] = raw_of(1, j);
 
             for (int g = 0; g < G; ++g) {
 #pragma unroll
-                for (int j = 0; j < 4; ++j) ss_load_row<C>(rQ, row_off(g + 1, j, raw[j]), Sn[j]);
+                for (int j = 0; j < 4; ++j) sw_load_row<C>(rQ, row_off(g + 1, j, raw[j]), Sn[j]);
 #pragma unroll
                 for (int j = 0; j < 4; ++j) raw[j] = raw_of(g + 2, j);
-                const ss_v4i bcur = bq;
+                const sw_v4i bcur = bq;
                 if (br) bq = __builtin_amdgcn_raw_buffer_load_b128(rB, (int)voffB, 16 * (g + 1), 16);
 
-                ss_for<0, 4>([&](auto J) {
+                sw_for<0, 4>([&](auto J) {
                     constexpr int j = decltype(J)::value;
                     const int u = 4 * g + j;
                     // lane 0: H of the previous strip's last column in row u (0 beyond the target: rows no strip of this target wrote)
-                    const int left = ss_dpp_shr1((br && u <= len) ? bcur[j] : 0, h[C - 1]);
+                    const int left = sw_dpp_shr1((br && u <= len) ? bcur[j] : 0, h[C - 1]);
                     int dprev = diag0, prev = left;
                     diag0 = left;
-                    ss_for<0, C>([&](auto K) {
+                    sw_for<0, C>([&](auto K) {
                         constexpr int k = decltype(K)::value;
                         const int old = h[k];
-                        int s = ss_sbyte(S[j][k >> 2], k & 3);
+                        int s = sw_sbyte(S[j][k >> 2], k & 3);
                         if constexpr (WIDE) {
                             const int sel = s;
                             s = sel > 0 ? p.match : p.mismatch;
@@ -185,14 +141,14 @@ __global__ void __launch_bounds__(256) sw_search_wave(SearchParams p) {
                         dprev = old;
                         prev = hn;
                     });
-                    if (bw) __builtin_amdgcn_raw_buffer_store_b32(h[C - 1], rB, lane == 63 ? 4 : (int)SS_OOB, 4 * u, 0);   // row u - 63 at index row + 64
+                    if (bw) __builtin_amdgcn_raw_buffer_store_b32(h[C - 1], rB, lane == 63 ? 4 : (int)SW_OOB, 4 * u, 0);   // row u - 63 at index row + 64
                     // ---- arg-max: the row maximum against the wave's best so far; only a step that reaches it looks for the cell
                     int m = h[0];
 #pragma unroll
                     for (int k = 1; k + 1 < C; k += 2) m = max(max(m, h[k]), h[k + 1]);
                     m = max(m, h[C - 1]);
                     if (__builtin_amdgcn_ballot_w64(m >= sbest) != 0) {
-                        sbest = max(sbest, ss_wave_max(m));
+                        sbest = max(sbest, sw_wave_max(m));
                         int kk = 0;                                   // first column of my row that holds its maximum
 #pragma unroll
                         for (int k = C - 1; k >= 0; --k) kk = (h[k] == m) ? k : kk;
@@ -225,9 +181,9 @@ __global__ void __launch_bounds__(256) sw_search_wave(SearchParams p) {
         {
             const __amdgpu_buffer_rsrc_t rR = __builtin_amdgcn_make_buffer_rsrc((void*)(p.results + it.idx), 0, (int)sizeof(sw_result), 0x00020000);
             const u64 score = kbest >> 40, pos = kbest ? SW_KEY_IDX_MASK - (kbest & SW_KEY_IDX_MASK) : 0;
-            const ss_v4i v = {(int)(u32)pos, (int)(u32)(pos >> 32), (int)(u32)score, 0};
+            const sw_v4i v = {(int)(u32)pos, (int)(u32)(pos >> 32), (int)(u32)score, 0};
             __builtin_amdgcn_raw_buffer_store_b128(v, rR, (int)voffL0, 0, 0);                 // max_pos, max_score
-            __builtin_amdgcn_raw_buffer_store_b64(ss_v2i{0, 0}, rR, (int)voffL0, 16, 0);      // path_len
+            __builtin_amdgcn_raw_buffer_store_b64(sw_v2i{0, 0}, rR, (int)voffL0, 16, 0);      // path_len
         }
     }
 }
