@@ -421,6 +421,44 @@ int  sw_search_affine_pairs_host(const char* queries, const int64_t* qoffsets, i
                                  const int64_t* offsets, int64_t ntargets, const sw_affine* scoring, const sw_pair* pairs,
                                  int64_t npairs, sw_result* results);
 
+/* The ungapped pre-filter (csrc/sw_prefilter.hip): the stage that PRODUCES the pair list sw_db_search_affine_pairs rescores -- the MSV
+ * stage of HMMER, the ungapped stage of MMseqs2.  For query q (columns j) and target t (rows i), with the table s used exactly as
+ * sw_search_affine_device uses it (next to Gotoh's recurrence above):
+ *   D[0][j] = D[i][0] = 0
+ *   D[i][j] = max(0, D[i-1][j-1] + s[q[j-1]][t[i-1]])
+ *   U(q, t) = max over all cells of D                          (0 for an empty target)
+ * the best score of a gapless local alignment, over all diagonals; exact, no seeds, no index.  A gapless alignment is a local
+ * alignment, so U <= max_score of sw_search_affine_device for the same table and ANY gap_open, gap_extend <= 0.
+ *   d_queries, qoffsets, the handle, the stream : as for sw_db_search_affine; `sub` is HOST memory, copied before the call returns.
+ *   min_score : a pair PASSES when its target is not empty and U >= min_score (min_score >= 1).
+ *   d_npairs  : device, one int64: the TRUE number of passing pairs, also where it exceeds pairs_cap (the rule of sw_alignment's nops).
+ *   d_pairs   : device, pairs_cap sw_pair.  Its first min(*d_npairs, pairs_cap) entries are distinct passing pairs, in no specified
+ *               order (the slots come from an atomic cursor, and which pairs a too-small list keeps may differ between runs); every
+ *               entry behind them, up to pairs_cap, is {-1, -1}.  Nothing is written outside pairs_cap entries.  May be NULL with
+ *               pairs_cap 0: count (and scores) only.
+ *   d_scores  : device, optional: nqueries x ntargets int32, QUERY-MAJOR; where it is not NULL every entry is written,
+ *               d_scores[q * ntargets + k] = U(q, k), exact.
+ * The {-1, -1} tail makes the chain free of a host round trip: sw_db_search_affine_pairs(..., d_pairs, pairs_cap, ...) gives {0, 0, 0}
+ * for those entries by its out-of-range rule, so a caller runs it over all pairs_cap entries and never reads *d_npairs in between.
+ * Asynchronous on `stream`, no host round trip; the host work of a call is O(nqueries).  The queries run in the groups of
+ * sw_db_search_affine ("search_profile_mib").  A query whose scores provably fit 16 bits -- max(largest table entry, 0) x
+ * min(its length, the handle's longest target) <= 32767 -- runs two targets per wave on packed 16-bit lanes, any other query on 32-bit
+ * lanes; the scores are the same.  "prefilter_lanes" (settable: 0, the default, lets the planner decide; 32 never uses the packed
+ * kernel) is the A/B switch; "last_prefilter_groups", "last_prefilter_launches" (score launches) and "last_prefilter_packed_launches"
+ * describe the last call, all 0 for one that launched no kernel.
+ * SW_EINVAL: the argument errors of sw_db_search_affine (the offsets, the query lengths, the table's 24-bit bound, a handle from
+ * another device), NULL sub, min_score < 1, pairs_cap < 0, NULL d_pairs with pairs_cap > 0, NULL d_npairs unless d_pairs is NULL and
+ * d_scores is not (so also: everything NULL).  nqueries == 0 or a handle without a non-empty target: SW_OK, *d_npairs = 0, the
+ * {-1, -1} tail, zero scores.
+ *   sw_prefilter_ungapped_host  the CPU leg: the same on host memory in plain C++, the list in ascending (query, target) order; every
+ *               argument is checked before the first pair (SW_EINVAL also for the offsets / length errors of sw_search_device). */
+int  sw_db_prefilter_ungapped(sw_ctx* ctx, const sw_db* db, const char* d_queries, const int64_t* qoffsets, int64_t nqueries,
+                              const sw_submat* sub, int64_t min_score, sw_pair* d_pairs, int64_t pairs_cap, int64_t* d_npairs,
+                              int32_t* d_scores, void* stream);
+int  sw_prefilter_ungapped_host(const char* queries, const int64_t* qoffsets, int64_t nqueries, const char* db,
+                                const int64_t* offsets, int64_t ntargets, const sw_submat* sub, int64_t min_score,
+                                sw_pair* pairs, int64_t pairs_cap, int64_t* npairs, int32_t* scores);
+
 /* Tables.  sw_submat_match: s[x][y] = x == y ? match : mismatch (matchMissmatchScore, serial_smithW.c:251-256; both must fit int8:
  * the builder returns nothing, so it clamps them to -128..127 -- a caller that takes them from a user checks the range first, as
  * smithW and the Python wrapper do, which refuse such scores).  sw_submat_from_letters: `scores` is n x n, row = query letter, over the n bytes of
@@ -618,7 +656,9 @@ int sw_synchronize(sw_ctx* ctx, void* stream);   /* waits for `stream`; reports 
  * describe the last sw_db_search_affine_top / sw_top_hits_device call; "last_align_hits_launches", "last_align_hits_tiers",
  * "last_align_hits_slots" and "last_align_hits_lists" the last sw_db_align_affine_hits call; "search_pairs_chunk" (settable, default
  * 2^22, 1..2^31 - 1) is the most entries of a pair list that sw_db_search_affine_pairs bins at a time, "last_search_pairs_groups",
- * "last_search_pairs_chunks" and "last_search_pairs_launches" describe the last such call.  "debug_search_pairs_items_ptr" (an
+ * "last_search_pairs_chunks" and "last_search_pairs_launches" describe the last such call; "prefilter_lanes" (settable, 0 or 32) and
+ * "last_prefilter_groups", "last_prefilter_launches", "last_prefilter_packed_launches" belong to sw_db_prefilter_ungapped (above).
+ * "debug_search_pairs_items_ptr" (an
  * accessor for tests) is the device address of that call's item workspace, which a call leaves as its last (chunk, group) filled it:
  * 24-byte items {int64 start, int64 out, int32 len, int32 entry}, the classes' lists back to back. */
 int sw_set_option(sw_ctx* ctx, const char* name, int64_t value);

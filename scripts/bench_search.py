@@ -31,6 +31,12 @@
   medians and ranges of --reps after --warmup: (i) sw_db_search_affine over the full cross product, the baseline; (ii)
   sw_db_search_affine_pairs over a uniform random 1 % of the cross product (fixed seed); (iii) sw_db_search_affine_pairs over the full
   cross product as an explicit list in random order.  The results of (ii) and (iii) are compared on the device with the table of (i)
+  --prefilter: data set (a) only, 64 queries of --qlen through one handle, three legs in one process, torch events around whole calls,
+  medians and ranges of --reps after --warmup: (i) sw_db_search_affine over the full cross product, the baseline; (ii)
+  sw_db_prefilter_ungapped alone, on 32-bit lanes ("prefilter_lanes" = 32) and packed (0), at the ungapped score about 1 % of the pairs
+  reach (the quantile of a d_scores run, printed); (iii) the filter and sw_db_search_affine_pairs over its whole list, no count read in
+  between.  Checked on the device: every result of (iii) for a passing pair is the table entry of (i), U <= max_score for ALL pairs, the
+  two kernels give the same scores; the run fails if a check fails or if (ii) is not faster than (i)
 GCUPS = query letters x target letters / time of the call (torch events, median of --reps after --warmup)."""
 import argparse
 import importlib
@@ -77,6 +83,7 @@ def main():
     ap.add_argument("--align-hits", action="store_true", help="data set (a) only: the alignments of the top 10 / 100 hits of 64 queries, per query and in one call")
     ap.add_argument("--checkpoint", action="store_true", help="with --align-hits: checkpointed alignment beside the whole-matrix path, hit table and one query")
     ap.add_argument("--pairs", action="store_true", help="data set (a) only: a pair list of 1 %% and of all of the cross product of 64 queries beside the full search")
+    ap.add_argument("--prefilter", action="store_true", help="data set (a) only: the ungapped pre-filter of 64 queries, alone and chained into the pair-list search, beside the full search")
     ap.add_argument("--top", action="store_true", help="data set (a) only: the best 100 targets of 64 queries by the full table and by the selection on the device")
     args = ap.parse_args()
     rng = np.random.default_rng(2026)
@@ -355,6 +362,67 @@ def main():
         out["pairs_list_over_full_per_cell"] = round(out["pairs_list_ps_per_cell"] / out["pairs_full_ps_per_cell"], 4)
         db.close()
 
+    def prefilter_leg(packed, offs, nq=64):
+        d_db = torch.from_numpy(packed.copy()).to(dev)
+        db = eng.prepare_db(d_db, offs)
+        nt = len(offs) - 1
+        lens = np.diff(offs)
+        qoffs = np.arange(nq + 1, dtype=np.int64) * args.qlen
+        d_q = torch.from_numpy(rng.choice(PROTEIN, int(qoffs[-1])).astype(np.uint8)).to(dev)
+        scoring = (sub, -11, -1)
+        n_all = nq * nt
+        cells = float(qoffs[-1]) * float(offs[-1] - offs[0])
+        out["prefilter_queries"], out["prefilter_qlen"], out["prefilter_targets"], out["prefilter_cells"] = nq, args.qlen, nt, int(cells)
+        # leg i: the full search, unchanged code
+        table = torch.zeros(n_all * 3, dtype=torch.int64, device=dev)
+        out["prefilter_full_ms"], out["prefilter_full_range_ms"] = spread(lambda: db.search_affine_device(d_q, qoffs, scoring, out=table))
+        out["prefilter_full_ps_per_cell"] = round(out["prefilter_full_ms"] * 1e9 / cells, 4)
+        rows = table.view(n_all, 3)
+        # the ungapped scores of all pairs by both kernels; min_score: the score about 1 % of the pairs reach
+        u = {}
+        for lanes in (32, 0):
+            eng.set_option("prefilter_lanes", lanes)
+            _, _, u[lanes] = db.prefilter_ungapped_device(d_q, qoffs, sub, 1, 0, want_scores=True)
+            out[f"prefilter_lanes{lanes}_packed_launches"] = eng.get_option("last_prefilter_packed_launches")
+            out[f"prefilter_lanes{lanes}_launches"] = eng.get_option("last_prefilter_launches")
+        torch.cuda.synchronize()
+        flat_u = u[0].view(-1)
+        out["prefilter_kernels_identical"] = bool(torch.equal(u[0], u[32]))
+        out["prefilter_u_le_max_score_all_pairs"] = bool((flat_u.to(torch.int64) <= rows[:, 1]).all().item())
+        min_score = max(1, int(flat_u.float().kthvalue(n_all - n_all // 100).values.item()))
+        cap = int((flat_u >= min_score).sum().item())       # (every target of data set (a) has a letter)
+        out["prefilter_min_score"], out["prefilter_passing"], out["prefilter_passing_share"] = min_score, cap, round(cap / n_all, 5)
+        out["prefilter_u_max"], out["prefilter_u_median"] = int(flat_u.max().item()), int(flat_u.float().median().item())
+        del u
+        # leg ii: the filter alone, list and count, no score table
+        bufs = (torch.empty((cap, 2), dtype=torch.int64, device=dev), torch.zeros(1, dtype=torch.int64, device=dev), None)
+        for lanes, tag in ((32, "lanes32"), (0, "packed")):
+            eng.set_option("prefilter_lanes", lanes)
+            ms, rng_ms = spread(lambda: db.prefilter_ungapped_device(d_q, qoffs, sub, min_score, cap, out=bufs))
+            out[f"prefilter_{tag}_ms"], out[f"prefilter_{tag}_range_ms"] = ms, rng_ms
+            out[f"prefilter_{tag}_ps_per_cell"] = round(ms * 1e9 / cells, 4)
+            out[f"prefilter_{tag}_gcups"] = round(cells / ms / 1e6, 1)
+            out[f"prefilter_{tag}_count_ok"] = bool(int(bufs[1].item()) == cap)
+            out[f"prefilter_full_over_{tag}"] = round(out["prefilter_full_ms"] / ms, 2)
+            out[f"prefilter_{tag}_faster_than_full"] = bool(ms < out["prefilter_full_ms"])
+        out["prefilter_lanes32_over_packed"] = round(out["prefilter_lanes32_ms"] / out["prefilter_packed_ms"], 3)
+        # leg iii: the filter and the rescoring of its whole list, nothing read in between
+        res = torch.full((cap * 3,), -1, dtype=torch.int64, device=dev)
+
+        def chain():
+            d_pairs, _, _ = db.prefilter_ungapped_device(d_q, qoffs, sub, min_score, cap, out=bufs)
+            db.search_affine_pairs_device(d_q, qoffs, scoring, d_pairs, out=res)
+
+        out["prefilter_chain_ms"], out["prefilter_chain_range_ms"] = spread(chain)
+        out["prefilter_full_over_chain"] = round(out["prefilter_full_ms"] / out["prefilter_chain_ms"], 2)
+        pr = bufs[0]
+        inside = bool(((pr[:, 0] >= 0) & (pr[:, 0] < nq) & (pr[:, 1] >= 0) & (pr[:, 1] < nt)).all().item())
+        flat = pr[:, 0] * nt + pr[:, 1]
+        out["prefilter_chain_identical"] = bool(inside and int(flat.unique().numel()) == cap and torch.equal(res.view(cap, 3), rows[flat])
+                                                and bool((flat_u[flat] >= min_score).all().item()))
+        out["prefilter_chain_rescored_cells"] = int(float(args.qlen) * float(lens[pr[:, 1].cpu().numpy()].sum())) if inside else 0
+        db.close()
+
     def align_ckpt_leg(q, packed, offs, nq=64):
         d_db = torch.from_numpy(packed.copy()).to(dev)
         db = eng.prepare_db(d_db, offs)
@@ -426,9 +494,11 @@ def main():
     out["a_letters"] = int(offs[-1])
     out["a_len_median"] = int(np.median(lens))
     out["a_len_max"] = int(lens.max())
-    if args.multi or args.top or args.align_hits or args.pairs:
+    if args.multi or args.top or args.align_hits or args.pairs or args.prefilter:
         if args.pairs:
             pairs_leg(packed, offs)
+        if args.prefilter:
+            prefilter_leg(packed, offs)
         if args.multi:
             multi_legs(packed, offs)
         if args.align_hits and args.checkpoint:
@@ -443,6 +513,11 @@ def main():
             missed = [k for k in ("pairs_sparse_identical", "pairs_list_identical", "pairs_sparse_faster_than_full") if not out[k]]
             if missed:
                 sys.exit("bench_search.py --pairs: " + ", ".join(missed) + " is false")
+        if args.prefilter:   # the required conditions of the pre-filter: a line that misses one is printed, and the run fails
+            missed = [k for k in ("prefilter_chain_identical", "prefilter_u_le_max_score_all_pairs", "prefilter_kernels_identical", "prefilter_lanes32_count_ok",
+                                  "prefilter_packed_count_ok", "prefilter_lanes32_faster_than_full", "prefilter_packed_faster_than_full") if not out[k]]
+            if missed:
+                sys.exit("bench_search.py --prefilter: " + ", ".join(missed) + " is false")
         return
     search_gcups(q, packed, offs, "a")
     align_legs(q, packed, offs, affine_gcups(q, packed, offs, "a"), "a")

@@ -72,6 +72,8 @@ ABI = {
     "sw_search_affine_multi_host": (_i32, [_vp, _vp, _i64, _vp, _vp, _i64, ctypes.POINTER(_Affine), _vp]),
     "sw_db_search_affine_pairs": (_i32, [_vp, _vp, _vp, _vp, _i64, ctypes.POINTER(_Affine), _vp, _i64, _vp, _vp]),
     "sw_search_affine_pairs_host": (_i32, [_vp, _vp, _i64, _vp, _vp, _i64, ctypes.POINTER(_Affine), _vp, _i64, _vp]),
+    "sw_db_prefilter_ungapped": (_i32, [_vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _vp]),
+    "sw_prefilter_ungapped_host": (_i32, [_vp, _vp, _i64, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp]),
     "sw_top_hits_device": (_i32, [_vp, _vp, _i64, _i64, _i64, _i64, _vp, _vp, _vp]),
     "sw_db_search_affine_top": (_i32, [_vp, _vp, _vp, _vp, _i64, ctypes.POINTER(_Affine), _i64, _i64, _vp, _vp, _vp]),
     "sw_search_affine_multi_top_host": (_i32, [_vp, _vp, _i64, _vp, _vp, _i64, ctypes.POINTER(_Affine), _i64, _i64, _vp, _vp]),
@@ -283,6 +285,34 @@ def search_affine_pairs_host(queries, targets, scoring, pairs):
     _check(lib().sw_search_affine_pairs_host(qs.ctypes.data, qoffs.ctypes.data, len(qoffs) - 1, db.ctypes.data, offs.ctypes.data, len(offs) - 1,
                                              ctypes.byref(sc), pr.ctypes.data if len(pr) else None, len(pr), res.ctypes.data))
     return res[:len(pr)]
+
+
+def _submat(submat):
+    sub = np.ascontiguousarray(submat, np.int8)
+    if sub.shape != (256, 256):
+        raise ValueError("the substitution matrix must be (256, 256) int8")
+    return sub
+
+
+def prefilter_ungapped_host(queries, targets, submat, min_score: int, cap=None, want_scores: bool = True):
+    """sw_prefilter_ungapped_host: the ungapped pre-filter in plain C++ on the host (no GPU).  queries and targets as for
+    search_affine_multi_host.  Returns (pairs, npairs, scores): the first min(npairs, cap) rows of the (cap, 2) int64 list are the
+    passing (query, target) pairs in ascending order, the rest is (-1, -1); npairs is the true count; scores is the
+    (nqueries, ntargets) int32 table of U, or None.  cap defaults to nqueries x ntargets."""
+    qpacked, qoffs = _pack_targets(queries)
+    packed, offs = _pack_targets(targets)
+    nq, ntargets = len(qoffs) - 1, len(offs) - 1
+    cap = nq * ntargets if cap is None else int(cap)
+    qs = qpacked if len(qpacked) else np.zeros(1, np.uint8)
+    db = packed if len(packed) else np.zeros(1, np.uint8)
+    sub = _submat(submat)
+    pairs = np.zeros((max(1, cap), 2), np.int64)
+    scores = np.zeros(max(1, nq * ntargets), np.int32) if want_scores else None
+    n = _i64(0)
+    _check(lib().sw_prefilter_ungapped_host(qs.ctypes.data, qoffs.ctypes.data, nq, db.ctypes.data, offs.ctypes.data, ntargets, sub.ctypes.data,
+                                            int(min_score), pairs.ctypes.data if cap > 0 else None, cap, ctypes.byref(n),
+                                            scores.ctypes.data if want_scores else None))
+    return pairs[:max(0, cap)], n.value, (scores[:nq * ntargets].reshape(nq, ntargets) if want_scores else None)
 
 
 def search_affine_multi_top_host(queries, targets, scoring, top: int, min_score: int = 0):
@@ -582,6 +612,53 @@ class Database:
         _check(lib().sw_db_search_affine_pairs(eng._h, self._h, d_queries.data_ptr(), qoffs.ctypes.data, len(qoffs) - 1, ctypes.byref(sc),
                                                d_pairs.data_ptr() if npairs else None, npairs, res.data_ptr(), eng._stream()))
         return res.view(-1)[:n].view(npairs, 3)
+
+    def prefilter_ungapped(self, queries, submat, min_score: int):
+        """The ungapped pre-filter on host queries (sw_db_prefilter_ungapped) with a list that holds every pair: returns numpy
+        (pairs, scores), the passing (query, target) pairs sorted ascending as an (npairs, 2) int64 array and the (nqueries, ntargets)
+        int32 table of U."""
+        eng = self.engine
+        t = eng.torch
+        qpacked, qoffs = _pack_targets(queries)
+        nq = len(qoffs) - 1
+        d_q = t.from_numpy(qpacked.copy() if len(qpacked) else np.zeros(1, np.uint8)).to(f"cuda:{eng.device}")
+        pairs, npairs, scores = self.prefilter_ungapped_device(d_q, qoffs, submat, min_score, nq * self.ntargets, want_scores=True)
+        eng.synchronize()
+        pr = pairs.cpu().numpy()[:int(npairs.item())]
+        return pr[np.lexsort((pr[:, 1], pr[:, 0]))], scores.cpu().numpy()
+
+    def prefilter_ungapped_device(self, d_queries, qoffsets, submat, min_score: int, cap: int, want_scores: bool = False, out=None):
+        """sw_db_prefilter_ungapped on device-resident queries; asynchronous on torch's current stream, nothing comes to the host.
+        Returns (pairs, npairs, scores): a (cap, 2) int64 tensor whose first min(npairs, cap) rows are distinct passing pairs in no
+        specified order and whose other rows are (-1, -1), a 1-element int64 tensor with the true count, and the (nqueries, ntargets)
+        int32 tensor of U or None.  `out`: such a triple of an earlier call to write into again.  The list goes as it is, all cap rows,
+        to search_affine_pairs_device: the (-1, -1) rows give zeros there."""
+        eng = self.engine
+        t = eng.torch
+        dev = f"cuda:{eng.device}"
+        qoffs = np.ascontiguousarray(qoffsets, np.int64).reshape(-1)
+        if len(qoffs) == 0:
+            qoffs = np.zeros(1, np.int64)
+        nq, cap = len(qoffs) - 1, int(cap)
+        if cap < 0:
+            raise ValueError("cap must not be negative")
+        if out is not None:
+            pairs, npairs, scores = out
+        else:
+            pairs = t.empty((cap, 2), dtype=t.int64, device=dev)
+            npairs = t.zeros(1, dtype=t.int64, device=dev)
+            scores = t.empty((nq, self.ntargets), dtype=t.int32, device=dev) if want_scores else None
+        if pairs.dtype != t.int64 or not pairs.is_contiguous() or tuple(pairs.shape) != (cap, 2):
+            raise ValueError(f"the pair list must be a contiguous int64 tensor of shape ({cap}, 2)")
+        if npairs.dtype != t.int64 or npairs.numel() != 1:
+            raise ValueError("the pair count must be a 1-element int64 tensor")
+        if want_scores and (scores is None or scores.dtype != t.int32 or not scores.is_contiguous() or tuple(scores.shape) != (nq, self.ntargets)):
+            raise ValueError(f"the scores must be a contiguous int32 tensor of shape ({nq}, {self.ntargets})")
+        sub = _submat(submat)
+        _check(lib().sw_db_prefilter_ungapped(eng._h, self._h, d_queries.data_ptr(), qoffs.ctypes.data, nq, sub.ctypes.data, int(min_score),
+                                              pairs.data_ptr() if cap > 0 else None, cap, npairs.data_ptr(),
+                                              scores.data_ptr() if want_scores and scores.numel() else None, eng._stream()))
+        return pairs, npairs, (scores if want_scores else None)
 
     def search_affine_top(self, queries, scoring, top: int, min_score: int = 0):
         """The best `top` targets of every query, selected on the device (sw_db_search_affine_top): the full result table never exists

@@ -12,6 +12,10 @@
 //                              --gap-open, --gap-extend and --align (one sw_db_align_affine_hits call on the device hit table) as for one query.  The K best hits per
 //                              query are selected on the device (sw_db_search_affine_top): only they are copied back
 //     ... --min-score S       with --all-queries: only hits with a score of at least S are printed (fewer than K where fewer qualify)
+//     ... --prefilter S       with --all-queries: the ungapped pre-filter (sw_db_prefilter_ungapped) and then the affine search of the pairs whose ungapped
+//                              score reaches S (sw_db_search_affine_pairs on the filter's device list): one handle, one read-back; the passing pairs in
+//                              ascending (query, target) order in the line format of --pairs with " ungapped=<U>" appended; S >= 1; not with --top,
+//                              --min-score, --align, --pairs
 //     ... --pairs FILE        a LIST of (query, target) pairs through one prepared handle and one call (sw_db_search_affine_pairs): FILE is text, one pair
 //                              per line, "<query record> <target record>", 0-based; '#' lines and blank lines are skipped.  One line per pair in input
 //                              order: query record, target record, the target's name, score, target_end, query_end (a pair outside the files: name "-",
@@ -417,6 +421,81 @@ static int search_pairs_main(const char* qpath, const char* dbpath, const char* 
     return 0;
 }
 
+// --search --all-queries --prefilter S: the ungapped pre-filter (sw_db_prefilter_ungapped, U >= S) and the affine search of the pairs it
+// lists (sw_db_search_affine_pairs over the whole list, its {-1, -1} tail included), through ONE prepared handle, back to back on the
+// device; one read-back at the end brings the count, the list, the results and the ungapped scores.  The passing pairs are printed in
+// ascending (query, target) order in the line format of --pairs, with " ungapped=<U>" appended.
+static int search_prefilter_main(const char* qpath, const char* dbpath, long long min_u, const sw_scores& sc, const AffineArgs& af) {
+    int64_t nq = 0, qtotal = 0, nrec = 0, total = 0;
+    CHECK(sw_read_fasta_db(qpath, nullptr, 0, nullptr, 0, &nq, &qtotal));
+    std::vector<char> qs((size_t)qtotal + 1);
+    std::vector<int64_t> qoffs((size_t)nq + 1, 0);
+    CHECK(sw_read_fasta_db(qpath, qs.data(), qtotal, qoffs.data(), nq + 1, &nq, &qtotal));
+    CHECK(sw_read_fasta_db(dbpath, nullptr, 0, nullptr, 0, &nrec, &total));
+    std::vector<char> db((size_t)total + 1);
+    std::vector<int64_t> offs((size_t)nrec + 1, 0);
+    CHECK(sw_read_fasta_db(dbpath, db.data(), total, offs.data(), nrec + 1, &nrec, &total));
+    const std::vector<std::string> names = fasta_names(dbpath);
+    if ((int64_t)names.size() != nrec) {
+        fprintf(stderr, "smithW: --prefilter: %s has %lld records but %zu header names\n", dbpath, (long long)nrec, names.size());
+        return 1;
+    }
+    // one device block for everything that comes back: the count (16 bytes), the list, the results, the ungapped scores
+    const int64_t cap = nq * nrec;
+    const size_t o_pairs = 16, o_res = o_pairs + (size_t)cap * sizeof(sw_pair), o_u = o_res + (size_t)cap * sizeof(sw_result),
+                 out_bytes = o_u + (size_t)cap * sizeof(int32_t);
+    sw_ctx* ctx = nullptr;
+    CHECK(sw_create(0, &ctx));
+    void *d_q = nullptr, *d_db = nullptr, *d_out = nullptr;
+    CHECK(sw_device_malloc(ctx, (size_t)qtotal + 16, &d_q));
+    CHECK(sw_device_malloc(ctx, (size_t)total + 16, &d_db));
+    CHECK(sw_device_malloc(ctx, out_bytes, &d_out));
+    if (qtotal) CHECK(sw_memcpy_h2d(ctx, d_q, qs.data(), (size_t)qtotal));
+    if (total) CHECK(sw_memcpy_h2d(ctx, d_db, db.data(), (size_t)total));
+    std::vector<sw_submat> sub(1);
+    sw_affine aff = {sub.data(), af.has_open ? af.open : 0, af.has_extend ? af.extend : sc.gap};
+    if (af.matrix) CHECK(sw_read_submat(af.matrix, sub.data()));
+    else sw_submat_match(sc.match, sc.mismatch, sub.data());
+    sw_pair* d_pairs = cap ? (sw_pair*)((char*)d_out + o_pairs) : nullptr;
+    sw_result* d_res = cap ? (sw_result*)((char*)d_out + o_res) : nullptr;
+    int32_t* d_u = cap ? (int32_t*)((char*)d_out + o_u) : nullptr;
+    sw_db* handle = nullptr;
+    const double t0 = now_s();
+    CHECK(sw_db_create(ctx, (const char*)d_db, offs.data(), nrec, &handle));
+    const double t1 = now_s();
+    CHECK(sw_db_prefilter_ungapped(ctx, handle, (const char*)d_q, qoffs.data(), nq, sub.data(), min_u, d_pairs, cap, (int64_t*)d_out, d_u, nullptr));
+    CHECK(sw_db_search_affine_pairs(ctx, handle, (const char*)d_q, qoffs.data(), nq, &aff, d_pairs, cap, d_res, nullptr));
+    CHECK(sw_synchronize(ctx, nullptr));
+    const double t2 = now_s();
+    std::vector<char> out(out_bytes);
+    CHECK(sw_memcpy_d2h(ctx, out.data(), d_out, out_bytes));
+    int64_t np = 0;
+    memcpy(&np, out.data(), sizeof np);
+    const sw_pair* pairs = (const sw_pair*)(out.data() + o_pairs);
+    const sw_result* res = (const sw_result*)(out.data() + o_res);
+    const int32_t* u = (const int32_t*)(out.data() + o_u);
+    std::vector<int64_t> order((size_t)np);
+    for (int64_t p = 0; p < np; ++p) order[(size_t)p] = p;
+    std::sort(order.begin(), order.end(), [&](int64_t a, int64_t b) { return pairs[a].query != pairs[b].query ? pairs[a].query < pairs[b].query : pairs[a].target < pairs[b].target; });
+    printf("# %lld pairs of %lld queries and %lld targets pass the ungapped pre-filter at %lld; query\ttarget\tname\tscore\ttarget_end\tquery_end\n", (long long)np,
+           (long long)nq, (long long)nrec, min_u);
+    double cells = 0;
+    for (int64_t i = 0; i < np; ++i) {
+        const sw_pair& pr = pairs[order[(size_t)i]];
+        const sw_result& r = res[order[(size_t)i]];
+        const long long M = qoffs[(size_t)pr.query + 1] - qoffs[(size_t)pr.query] + 1;
+        cells += (double)(M - 1) * (double)(offs[(size_t)pr.target + 1] - offs[(size_t)pr.target]);
+        printf("%lld\t%lld\t%s\t%lld\t%lld\t%lld ungapped=%d\n", (long long)pr.query, (long long)pr.target, names[(size_t)pr.target].c_str(), (long long)r.max_score,
+               (long long)(r.max_pos / M), (long long)(r.max_pos % M), u[pr.query * nrec + pr.target]);
+    }
+    printf("\nElapsed time for database search: %f (%.1f GCUPS over the rescored pairs; filter and %lld pairs in two calls, handle prepared in %f)\n\n", t2 - t1,
+           t2 > t1 ? cells / (t2 - t1) / 1e9 : 0.0, (long long)np, t1 - t0);
+    sw_db_free(handle);
+    (void)sw_device_free(ctx, d_q); (void)sw_device_free(ctx, d_db); (void)sw_device_free(ctx, d_out);
+    sw_destroy(ctx);
+    return 0;
+}
+
 int main(int argc, char** argv) {
     long long cols = 8, rows = 9;
     bool builtin = true, dump = false, labels = false, h64 = false, backtrack = true, p8 = false;
@@ -425,8 +504,8 @@ int main(int argc, char** argv) {
     const char *fasta_a = nullptr, *fasta_b = nullptr;
     long long rec_a = 0, rec_b = 0;
     const char *search_q = nullptr, *search_db = nullptr;
-    long long top = 10, min_score = 0;
-    bool has_min_score = false, has_top = false;
+    long long top = 10, min_score = 0, prefilter = 0;
+    bool has_min_score = false, has_top = false, has_prefilter = false;
     const char* pairs_path = nullptr;
     AffineArgs af;
     bool align = false, all_queries = false, align_ckpt = false;
@@ -451,6 +530,7 @@ int main(int argc, char** argv) {
         else if (f == "--top" && ai + 1 < argc) { top = strtoll(argv[++ai], nullptr, 10); has_top = true; }
         else if (f == "--pairs" && ai + 1 < argc) pairs_path = argv[++ai];
         else if (f == "--min-score" && ai + 1 < argc) { int v = 0; if (!parse_int("--min-score", argv[++ai], &v)) return 2; min_score = v; has_min_score = true; }
+        else if (f == "--prefilter" && ai + 1 < argc) { int v = 0; if (!parse_int("--prefilter", argv[++ai], &v)) return 2; prefilter = v; has_prefilter = true; }
         else if (f == "--matrix" && ai + 1 < argc) { af.matrix = argv[++ai]; af.on = true; }
         else if (f == "--gap-open" && ai + 1 < argc) { if (!parse_int("--gap-open", argv[++ai], &af.open)) return 2; af.has_open = af.on = true; }
         else if (f == "--gap-extend" && ai + 1 < argc) { if (!parse_int("--gap-extend", argv[++ai], &af.extend)) return 2; af.has_extend = true; }
@@ -461,7 +541,7 @@ int main(int argc, char** argv) {
         else if (f == "--record-b" && ai + 1 < argc) rec_b = strtoll(argv[++ai], nullptr, 10);
         else if (f == "--seed" && ai + 1 < argc) seed = (unsigned)strtoul(argv[++ai], nullptr, 10);
         else if (f == "--scores" && ai + 3 < argc) { sc.match = atoi(argv[++ai]); sc.mismatch = atoi(argv[++ai]); sc.gap = atoi(argv[++ai]); }
-        else { fprintf(stderr, "usage: smithW [<cols> <rows> | --fasta A.fa B.fa [--record-a I] [--record-b J] | --search QUERY.fa DB.fa [--record-a I] [--top K] [--all-queries [--min-score S]] [--pairs FILE] [--matrix FILE] [--gap-open O] [--gap-extend E] [--align [--align-checkpoint]]] [--seed N] [--dump | --dump-labels] [--h64] [--no-backtrack] [--scores M X G] [--gpus N | --devices 0,1,..] [--p8]\n"); return 2; }
+        else { fprintf(stderr, "usage: smithW [<cols> <rows> | --fasta A.fa B.fa [--record-a I] [--record-b J] | --search QUERY.fa DB.fa [--record-a I] [--top K] [--all-queries [--min-score S | --prefilter S]] [--pairs FILE] [--matrix FILE] [--gap-open O] [--gap-extend E] [--align [--align-checkpoint]]] [--seed N] [--dump | --dump-labels] [--h64] [--no-backtrack] [--scores M X G] [--gpus N | --devices 0,1,..] [--p8]\n"); return 2; }
     }
     if (npos == 1) { fprintf(stderr, "smithW: <cols> needs <rows>\n"); return 2; }
     if (align_ckpt && !(search_q && align)) { fprintf(stderr, "smithW: --align-checkpoint goes with --search --align\n"); return 2; }
@@ -474,6 +554,19 @@ int main(int argc, char** argv) {
         if (align && !af.on && (sc.match < -128 || sc.match > 127 || sc.mismatch < -128 || sc.mismatch > 127)) {
             fprintf(stderr, "smithW: --align on a linear search needs --scores M X within -128..127 (a table of signed bytes), got %d %d\n", sc.match, sc.mismatch);
             return 2;
+        }
+        if (has_prefilter) {
+            if (!all_queries) { fprintf(stderr, "smithW: --prefilter goes with --search --all-queries\n"); return 2; }
+            if (has_top) { fprintf(stderr, "smithW: --prefilter does not go with --top\n"); return 2; }
+            if (has_min_score) { fprintf(stderr, "smithW: --prefilter does not go with --min-score\n"); return 2; }
+            if (align) { fprintf(stderr, "smithW: --prefilter does not go with --align\n"); return 2; }
+            if (pairs_path) { fprintf(stderr, "smithW: --prefilter does not go with --pairs\n"); return 2; }
+            if (prefilter < 1) { fprintf(stderr, "smithW: --prefilter S needs S >= 1, got %lld\n", prefilter); return 2; }
+            if (!af.matrix && (sc.match < -128 || sc.match > 127 || sc.mismatch < -128 || sc.mismatch > 127)) {
+                fprintf(stderr, "smithW: --prefilter without --matrix needs --scores M X within -128..127 (a table of signed bytes), got %d %d\n", sc.match, sc.mismatch);
+                return 2;
+            }
+            return search_prefilter_main(search_q, search_db, prefilter, sc, af);
         }
         if (pairs_path) {
             if (all_queries) { fprintf(stderr, "smithW: --pairs does not go with --all-queries\n"); return 2; }
@@ -496,6 +589,7 @@ int main(int argc, char** argv) {
         if (has_min_score) { fprintf(stderr, "smithW: --min-score goes with --search --all-queries\n"); return 2; }
         return search_main(search_q, rec_a, search_db, top, sc, af, align, align_ckpt);
     }
+    if (has_prefilter) { fprintf(stderr, "smithW: --prefilter goes with --search --all-queries\n"); return 2; }
     if (pairs_path) { fprintf(stderr, "smithW: --pairs goes with --search\n"); return 2; }
     if (all_queries) { fprintf(stderr, "smithW: --all-queries goes with --search\n"); return 2; }
     if (has_min_score) { fprintf(stderr, "smithW: --min-score goes with --search --all-queries\n"); return 2; }

@@ -69,6 +69,7 @@ void sw_destroy(sw_ctx* c) {
     if (c->d_ahfilled) (void)hipFree(c->d_ahfilled);
     if (c->d_spitems) (void)hipFree(c->d_spitems);
     if (c->d_spctl) (void)hipFree(c->d_spctl);
+    if (c->d_pfctl) (void)hipFree(c->d_pfctl);
     if (c->d_mq) (void)hipFree(c->d_mq);
     if (c->h_mq) (void)hipHostFree(c->h_mq);
     if (c->d_tres) (void)hipFree(c->d_tres);
@@ -130,6 +131,11 @@ int sw_set_option(sw_ctx* c, const char* name, int64_t v) {
     if (!strcmp(name, "search_pairs_chunk")) {
         if (v < 1 || v > swp::kSearchPairsChunkMax) { set_err("search_pairs_chunk must be 1..2^31 - 1"); return SW_EINVAL; }
         c->opt_search_pairs_chunk = v;
+        return SW_OK;
+    }
+    if (!strcmp(name, "prefilter_lanes")) {
+        if (v != 0 && v != 32) { set_err("prefilter_lanes must be 0 (the planner decides) or 32 (never the packed kernel)"); return SW_EINVAL; }
+        c->opt_prefilter_lanes = v;
         return SW_OK;
     }
     if (!strcmp(name, "placement_budget_ms")) { c->opt_place_budget_ms = v > 0 ? v : 1500; return SW_OK; }
@@ -210,6 +216,10 @@ int64_t sw_get_option(sw_ctx* c, const char* name) {
     if (!strcmp(name, "last_search_pairs_groups")) return c->last_search_pairs_groups;
     if (!strcmp(name, "last_search_pairs_chunks")) return c->last_search_pairs_chunks;
     if (!strcmp(name, "last_search_pairs_launches")) return c->last_search_pairs_launches;
+    if (!strcmp(name, "prefilter_lanes")) return c->opt_prefilter_lanes;
+    if (!strcmp(name, "last_prefilter_groups")) return c->last_prefilter_groups;
+    if (!strcmp(name, "last_prefilter_launches")) return c->last_prefilter_launches;
+    if (!strcmp(name, "last_prefilter_packed_launches")) return c->last_prefilter_packed_launches;
     if (!strcmp(name, "debug_search_pairs_items_ptr")) return (int64_t)(uintptr_t)c->d_spitems;
     if (!strcmp(name, "placement_budget_ms")) return c->opt_place_budget_ms;
     if (!strcmp(name, "placement_hold_gib")) return c->opt_place_hold_gib;

@@ -76,6 +76,15 @@ static constexpr Indexed<SearchPairsKernel> kSearchPairs[] = {
 };
 static_assert(std::size(kSearchPairs) == swp::kSearchPairsKernels && at_their_indices(kSearchPairs));
 
+// the instantiations of the pre-filter kernels (sw_prefilter.hip), picked by swp::plan_prefilter
+using PrefilterKernel = void (*)(swk::PrefilterParams);
+static constexpr Indexed<PrefilterKernel> kPrefilter[] = {
+    {swp::prefilter_kernel_index(4, false), swk::sw_prefilter_wave<4>}, {swp::prefilter_kernel_index(4, true), swk::sw_prefilter_wave16<4>},
+    {swp::prefilter_kernel_index(8, false), swk::sw_prefilter_wave<8>}, {swp::prefilter_kernel_index(8, true), swk::sw_prefilter_wave16<8>},
+    {swp::prefilter_kernel_index(16, false), swk::sw_prefilter_wave<16>}, {swp::prefilter_kernel_index(16, true), swk::sw_prefilter_wave16<16>},
+};
+static_assert(std::size(kPrefilter) == swp::kPrefilterKernels && at_their_indices(kPrefilter));
+
 // occupancy of every instantiation of a table at 256 threads, asked once per context: the plans' columns per lane and grids depend on it
 template <typename K, size_t N>
 static int occupancy_once(const Indexed<K> (&tab)[N], int (&per_cu)[N], bool& known) {
@@ -776,6 +785,74 @@ int sw_db_search_affine_pairs(sw_ctx* c, const sw_db* db, const char* d_queries,
         l0 = l1;
     }
     c->last_search_pairs_groups = (int64_t)plan.group.size(); c->last_search_pairs_chunks = plan.nchunks; c->last_search_pairs_launches = plan.launches;
+    return SW_OK;
+}
+
+// The ungapped pre-filter (csrc/sw_prefilter.hip).  Per call the host checks and plans the QUERIES (O(nqueries)) against the handle; one
+// memset writes the {-1, -1} of the whole list up front, then per group one profile launch and per class the launches of its packed and
+// of its other queries, a one-thread commit between them: it starts the work counter and the cursor of the next launch at zero and
+// keeps the count.  Nothing is read back.
+int sw_db_prefilter_ungapped(sw_ctx* c, const sw_db* db, const char* d_queries, const int64_t* qoffsets, int64_t nqueries, const sw_submat* sub,
+                             int64_t min_score, sw_pair* d_pairs, int64_t pairs_cap, int64_t* d_npairs, int32_t* d_scores, void* stream_) {
+    const char* who = "sw_db_prefilter_ungapped";
+    if (!c || !db || !d_queries || !qoffsets || !sub) { set_err("%s: NULL pointer", who); return SW_EINVAL; }
+    if (db->device != c->device) { set_err("%s: the handle was created on device %d, the context runs on device %d", who, db->device, c->device); return SW_EINVAL; }
+    int64_t maxq = 0;
+    const sw_affine scoring = {sub, 0, 0};
+    if (int rc = swh::check_search_multi(who, qoffsets, nqueries, db->longest, &scoring, &maxq)) return rc;
+    if (int rc = swh::check_prefilter(who, min_score, d_pairs, pairs_cap, d_npairs, d_scores)) return rc;
+    c->last_prefilter_groups = c->last_prefilter_launches = c->last_prefilter_packed_launches = 0;   // (a call that launches no kernel reports none)
+    hipStream_t stream = (hipStream_t)stream_;
+    HIP_TRY(hipSetDevice(c->device));
+    DevOrder order(c, stream, false);
+    if (order.rc) return order.rc;
+    // the entries behind the written ones keep these {-1, -1}; empty targets keep the zeros of the scores
+    if (pairs_cap > 0) HIP_TRY(hipMemsetAsync(d_pairs, 0xFF, (size_t)pairs_cap * sizeof(sw_pair), stream));
+    if (d_scores && nqueries > 0 && db->ntargets > 0) HIP_TRY(hipMemsetAsync(d_scores, 0, (size_t)nqueries * (size_t)db->ntargets * sizeof(int32_t), stream));
+    if (nqueries == 0 || db->nonempty == 0) {
+        if (d_npairs) HIP_TRY(hipMemsetAsync(d_npairs, 0, sizeof(int64_t), stream));
+        return SW_OK;
+    }
+    if (int rc = occupancy_once(kPrefilter, c->prefilter_per_cu, c->prefilter_per_cu_known)) return rc;
+    const std::vector<int64_t> qlens = query_lengths(qoffsets, nqueries);
+    swp::PrefilterJob pj;
+    pj.qlens = qlens.data(); pj.nqueries = nqueries; pj.longest = db->longest; pj.nonempty = db->nonempty; pj.num_cus = c->num_cus;
+    pj.budget_bytes = c->opt_search_profile_mib << 20; pj.lanes = (int)c->opt_prefilter_lanes;
+    for (int x = 0; x < 256; ++x)
+        for (int y = 0; y < 256; ++y) pj.max_entry = std::max<int>(pj.max_entry, sub->s[x][y]);
+    std::copy(std::begin(c->prefilter_per_cu), std::end(c->prefilter_per_cu), pj.per_cu);
+    const swp::PrefilterPlan plan = swp::plan_prefilter(pj);
+    for (const swp::PrefilterLaunch& l : plan.launch)
+        if (c->prefilter_per_cu[l.kernel] < 1) { set_err("the pre-filter kernel does not fit a CU on this device"); return SW_EDEVICE; }
+    if (int rc = stage_search_call(c, stream, 0, plan.prof_need, plan.bnd_need, sub)) return rc;
+    if (!c->d_pfctl) HIP_TRY(hipMalloc((void**)&c->d_pfctl, sizeof(swk::PrefilterCtl)));
+    if (int rc = upload_query_table(c, stream, plan.table, qoffsets, &scoring)) return rc;
+    hipLaunchKernelGGL(swk::sw_prefilter_commit, dim3(1), dim3(64), 0, stream, c->d_pfctl, d_npairs, 1);
+    HIP_TRY(hipGetLastError());
+    size_t li = 0;
+    for (size_t g = 0; g < plan.group.size(); ++g) {
+        if (int rc = launch_group_profiles(c, stream, d_queries, plan.group[g])) return rc;
+        for (; li < plan.launch.size() && plan.launch[li].group == (int)g; ++li) {
+            const swp::PrefilterLaunch& l = plan.launch[li];
+            swk::PrefilterParams pp;
+            memset(&pp, 0, sizeof pp);
+            pp.db = (const unsigned char*)db->d_db;
+            pp.items = db->d_items; pp.rank0 = l.rank0; pp.nranks = l.nranks;
+            pp.queries = c->d_mq + l.q0; pp.nq = (unsigned)l.nq; pp.nitems = l.items;
+            pp.prof = c->d_sprof; pp.ntargets = db->ntargets;
+            pp.bnd = l.bnd_per ? c->d_sbnd : nullptr; pp.bnd_per = l.bnd_per;
+            pp.ctl = c->d_pfctl;
+            pp.min_score = (int)std::min<int64_t>(min_score, INT32_MAX);
+            pp.pairs = d_pairs; pp.pairs_cap = pairs_cap;
+            pp.scores = d_scores;
+            hipLaunchKernelGGL(kPrefilter[l.kernel].k, dim3((unsigned)l.grid), dim3(256), 0, stream, pp);
+            HIP_TRY(hipGetLastError());
+            hipLaunchKernelGGL(swk::sw_prefilter_commit, dim3(1), dim3(64), 0, stream, c->d_pfctl, d_npairs, 0);
+            HIP_TRY(hipGetLastError());
+        }
+    }
+    c->last_prefilter_groups = (int64_t)plan.group.size(); c->last_prefilter_launches = (int64_t)plan.launch.size();
+    c->last_prefilter_packed_launches = plan.packed_launches;
     return SW_OK;
 }
 

@@ -19,6 +19,7 @@ int check_search_affine(const char* who, int64_t qlen, const int64_t* offsets, i
 int check_align_affine(const char* who, const int64_t* offsets, int64_t ntargets, const int64_t* hits, int64_t nhits, const void* aln, const void* ops,
                        int64_t ops_cap, int64_t* maxhit_out);
 int check_search_multi(const char* who, const int64_t* qoffsets, int64_t nqueries, int64_t longest_target, const sw_affine* sc, int64_t* maxq_out);
+int check_prefilter(const char* who, int64_t min_score, const void* pairs, int64_t pairs_cap, const void* npairs, const void* scores);
 int check_align_hits(const char* who, int64_t top, const void* hits, const void* aln, const void* ops, int64_t ops_cap);
 SW_HIDDEN int check_targets(const char* who, int64_t qlen, const int64_t* offsets, int64_t ntargets, int64_t* maxlen_out, int64_t* nonempty_out);
 }
@@ -143,6 +144,12 @@ struct SW_HIDDEN sw_ctx {
     int64_t last_search_pairs_groups = 0, last_search_pairs_chunks = 0, last_search_pairs_launches = 0;
     int search_pairs_per_cu[swp::kSearchPairsKernels] = {};     // occupancy of every sw_search_affine_pairs_wave instantiation at 256 threads ...
     bool search_pairs_per_cu_known = false;                     // ... queried at the first call
+    // the ungapped pre-filter (sw_db_prefilter_ungapped): its control words, "prefilter_lanes", what the last call did
+    swk::PrefilterCtl* d_pfctl = nullptr;
+    int64_t opt_prefilter_lanes = 0;
+    int64_t last_prefilter_groups = 0, last_prefilter_launches = 0, last_prefilter_packed_launches = 0;
+    int prefilter_per_cu[swp::kPrefilterKernels] = {};          // occupancy of every sw_prefilter_wave / _wave16 instantiation at 256 threads ...
+    bool prefilter_per_cu_known = false;                        // ... queried at the first call
     // the best targets per query (sw_top_hits_device, sw_db_search_affine_top): the result rows of a chunk, the histograms and the
     // per-row states of the radix select
     sw_result* d_tres = nullptr; size_t tres_cap = 0;

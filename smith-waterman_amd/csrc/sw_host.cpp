@@ -118,6 +118,15 @@ int check_search_multi(const char* who, const int64_t* qoffsets, int64_t nquerie
     return SW_OK;
 }
 
+// What sw_db_prefilter_ungapped / sw_prefilter_ungapped_host check beyond check_search_multi (include/swhip.h).
+int check_prefilter(const char* who, int64_t min_score, const void* pairs, int64_t pairs_cap, const void* npairs, const void* scores) {
+    if (min_score < 1) { set_err("%s: min_score = %lld is below 1", who, (long long)min_score); return SW_EINVAL; }
+    if (pairs_cap < 0) { set_err("%s: pairs_cap = %lld is negative", who, (long long)pairs_cap); return SW_EINVAL; }
+    if (!pairs && pairs_cap > 0) { set_err("%s: the pair list is NULL with pairs_cap = %lld", who, (long long)pairs_cap); return SW_EINVAL; }
+    if (!npairs && (pairs || !scores)) { set_err("%s: the pair count is NULL (allowed only for a call that asks for the scores alone)", who); return SW_EINVAL; }
+    return SW_OK;
+}
+
 // What sw_align_affine_device / _host check beyond check_search_affine (include/swhip.h); reports the longest hit.
 int check_align_affine(const char* who, const int64_t* offsets, int64_t ntargets, const int64_t* hits, int64_t nhits, const void* aln, const void* ops,
                        int64_t ops_cap, int64_t* maxhit_out) {
@@ -478,6 +487,44 @@ int sw_search_affine_pairs_host(const char* queries, const int64_t* qoffsets, in
         if (q >= (uint64_t)nqueries || k >= (uint64_t)ntargets) continue;
         if (int rc = sw_search_affine_host(queries + qoffsets[q], qoffsets[q + 1] - qoffsets[q], db, offsets + k, 1, scoring, results + p)) return rc;
     }
+    return SW_OK;
+}
+
+// The CPU leg of sw_db_prefilter_ungapped: D[i][j] = max(0, D[i-1][j-1] + s) over one rolling row per pair, the list in ascending
+// (query, target) order.  Everything is checked before the first pair, so an error leaves the outputs untouched.
+int sw_prefilter_ungapped_host(const char* queries, const int64_t* qoffsets, int64_t nqueries, const char* db, const int64_t* offsets, int64_t ntargets,
+                               const sw_submat* sub, int64_t min_score, sw_pair* pairs, int64_t pairs_cap, int64_t* npairs, int32_t* scores) {
+    const char* who = "sw_prefilter_ungapped_host";
+    if (!queries || !qoffsets || !db || !offsets || !sub || ntargets < 0) { swh::set_err("%s: NULL pointer or negative target count", who); return SW_EINVAL; }
+    int64_t maxlen = 0, nonempty = 0, maxq = 0;
+    if (int rc = swh::check_targets(who, 1, offsets, ntargets, &maxlen, &nonempty)) return rc;
+    const sw_affine sc = {sub, 0, 0};
+    if (int rc = swh::check_search_multi(who, qoffsets, nqueries, maxlen, &sc, &maxq)) return rc;
+    if (int rc = swh::check_prefilter(who, min_score, pairs, pairs_cap, npairs, scores)) return rc;
+    if (pairs) memset(pairs, 0xFF, (size_t)pairs_cap * sizeof(sw_pair));   // {-1, -1} behind the written entries
+    int64_t n = 0;
+    std::vector<int32_t> row((size_t)maxq + 1);
+    for (int64_t q = 0; q < nqueries; ++q) {
+        const unsigned char* qq = (const unsigned char*)queries + qoffsets[q];
+        const int64_t qlen = qoffsets[q + 1] - qoffsets[q];
+        for (int64_t k = 0; k < ntargets; ++k) {
+            const unsigned char* t = (const unsigned char*)db + offsets[k];
+            const int64_t len = offsets[k + 1] - offsets[k];
+            std::fill(row.begin(), row.begin() + qlen + 1, 0);
+            int32_t best = 0;
+            for (int64_t i = 1; i <= len; ++i)
+                for (int64_t c = qlen; c >= 1; --c) {   // from the highest column down: row[c - 1] still holds row i - 1
+                    row[(size_t)c] = std::max<int32_t>(0, row[(size_t)c - 1] + sub->s[qq[c - 1]][t[i - 1]]);
+                    best = std::max(best, row[(size_t)c]);
+                }
+            if (scores) scores[q * ntargets + k] = best;
+            if (len > 0 && best >= min_score) {
+                if (n < pairs_cap) pairs[n] = sw_pair{q, k};
+                ++n;
+            }
+        }
+    }
+    if (npairs) *npairs = n;
     return SW_OK;
 }
 

@@ -197,6 +197,34 @@ struct SearchPairsParams {
 template <int C>
 __global__ void sw_search_affine_pairs_wave(SearchPairsParams p);
 
+// sw_prefilter.hip: the ungapped pre-filter (sw_db_prefilter_ungapped): the best gapless local score U of every (query, target) pair and
+// the list of the pairs with U >= min_score.  The items and the launches are swp::plan_prefilter's.
+struct PrefilterCtl {                    // the control words of a call
+    unsigned int work;                   // next item of the launch in flight (zero at launch)
+    unsigned int cursor;                 // passing pairs of the launch in flight (zero at launch)
+    long long total;                     // passing pairs of the launches before it
+};
+struct PrefilterParams {
+    const unsigned char* db;             // the targets back to back
+    const SearchItem* items;             // the handle's schedule: every non-empty target, longest first
+    int64_t rank0, nranks;               // the target ranks of this launch
+    const MultiQuery* queries;           // the launch's queries (entries of the call's table)
+    unsigned int nq;                     // ... how many: item w = (w / nq, w % nq); w / nq counts ranks, or rank PAIRS in the packed kernel
+    int64_t nitems;                      // below 2^31
+    const signed char* prof;             // the group's profiles (sw_search_profile_submat_multi), query t at its prof_off
+    int64_t ntargets;                    // row stride of the scores
+    int* bnd; int64_t bnd_per;           // per resident wave: two boundary columns of one int per row, only when a query has more than one strip
+    PrefilterCtl* ctl;
+    int min_score;
+    sw_pair* pairs; int64_t pairs_cap;   // the list: slot total + cursor, stored where it lies below pairs_cap
+    int32_t* scores;                     // optional: query-major, nqueries x ntargets
+};
+__global__ void sw_prefilter_commit(PrefilterCtl* ctl, int64_t* npairs, int first);
+template <int C>
+__global__ void sw_prefilter_wave(PrefilterParams p);
+template <int C>
+__global__ void sw_prefilter_wave16(PrefilterParams p);   // two targets of a query per wave on packed 16-bit lanes
+
 // sw_search_top.hip: the best `top` targets of every row of a query-major result table (swp::plan_search_top has the geometry)
 struct TopState {                        // of one row, between the launches of a radix select
     unsigned long long prefix;           // the digits found so far, highest first; after the last pass: the key of rank `top`

@@ -497,6 +497,65 @@ SearchPairsPlan plan_search_pairs(const SearchPairsJob& j) {
     return s;
 }
 
+// The ungapped pre-filter.  The table and the groups come from plan_search_multi itself (asked for a handle without targets, it plans
+// no launch); per (group, class) the packed queries move to the front, every entry keeping its profile's place.  O(nqueries): nothing
+// here looks at a target, and the launches of a class are cut by arithmetic on the ranks.
+PrefilterPlan plan_prefilter(const PrefilterJob& j) {
+    PrefilterPlan f;
+    SearchMultiJob mj;
+    mj.qlens = j.qlens; mj.nqueries = j.nqueries; mj.longest = j.longest; mj.nonempty = 0; mj.num_cus = j.num_cus; mj.budget_bytes = j.budget_bytes;
+    // (16 columns per lane are taken as there: where both kernels of that width keep two workgroups on a CU)
+    for (int k = 0; k < kSearchMultiKernels; ++k) {
+        const int C = k == 0 ? 4 : 8 * k;
+        mj.per_cu[k] = std::min(j.per_cu[prefilter_kernel_index(C, false)], j.per_cu[prefilter_kernel_index(C, true)]);
+    }
+    SearchMultiPlan m = plan_search_multi(mj);
+    f.table = std::move(m.table);
+    f.group = std::move(m.group);
+    f.prof_need = m.prof_need;
+    const int64_t max_items = std::max<int64_t>(1, std::min(j.max_items, kMultiMaxItems));
+    auto packed = [&](const swk::MultiQuery& d) { return prefilter_packed(j.max_entry, d.qlen, j.longest, j.lanes); };
+    auto klass = [](const swk::MultiQuery& d) { return d.qpad / d.nstrips / 64 / 8; };   // columns per lane 4, 8, 16 -> 0, 1, 2
+    for (size_t g = 0; g < f.group.size(); ++g) {
+        const int64_t g0 = f.group[g].q0, g1 = g0 + f.group[g].nq;
+        for (int64_t a = g0; a < g1;) {
+            const int k = klass(f.table[(size_t)a]), C = k == 0 ? 4 : 8 * k;
+            int64_t b = a;
+            while (b < g1 && klass(f.table[(size_t)b]) == k) ++b;
+            const int64_t mid = std::stable_partition(f.table.begin() + a, f.table.begin() + b, packed) - f.table.begin();
+            for (int side = 0; side < 2 && j.nonempty > 0; ++side) {
+                const bool pk = side == 0;
+                const int64_t s0 = pk ? a : mid, s1 = pk ? mid : b;
+                const int kernel = prefilter_kernel_index(C, pk);
+                for (int64_t qa = s0; qa < s1;) {
+                    const int64_t nq = std::min(s1 - qa, max_items);
+                    // target ranks of a launch: as many as keep its items inside max_items; packed launches take them in pairs
+                    const int64_t ranks_per = pk ? 2 * (max_items / nq) : max_items / nq;
+                    int64_t strips = 1;
+                    for (int64_t t = qa; t < qa + nq; ++t) strips = std::max<int64_t>(strips, f.table[(size_t)t].nstrips);
+                    for (int64_t r0 = 0; r0 < j.nonempty; r0 += ranks_per) {
+                        PrefilterLaunch l;
+                        l.group = (int)g; l.C = C; l.kernel = kernel; l.packed = pk;
+                        l.q0 = qa; l.nq = nq;
+                        l.rank0 = r0; l.nranks = std::min(ranks_per, j.nonempty - r0);
+                        l.items = l.nq * (pk ? (l.nranks + 1) / 2 : l.nranks);
+                        l.bnd_per = 2 * boundary_ints(strips, j.longest);
+                        l.grid = std::min<int64_t>((int64_t)j.per_cu[kernel] * j.num_cus, (l.items + 3) / 4);
+                        if (l.bnd_per) l.grid = std::min<int64_t>(l.grid, kSearchBndBytes / (l.bnd_per * 4 * 4));
+                        l.grid = std::max<int64_t>(1, l.grid);
+                        f.bnd_need = std::max(f.bnd_need, (size_t)(l.grid * 4 * l.bnd_per));
+                        f.packed_launches += pk;
+                        f.launch.push_back(l);
+                    }
+                    qa += nq;
+                }
+            }
+            a = b;
+        }
+    }
+    return f;
+}
+
 // The best `top` of every row.  Every row has the same length, so the chunks are uniform and the geometry of a row is decided once.
 // The passes take kTopDigitBits bits each from the top of the key down; the last one takes what is left.
 SearchTopPlan plan_search_top(const SearchTopJob& j) {

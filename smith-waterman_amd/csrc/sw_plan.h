@@ -283,6 +283,58 @@ struct SearchPairsPlan {
 
 SearchPairsPlan plan_search_pairs(const SearchPairsJob& job);
 
+// ---- the ungapped pre-filter of a many-query search (sw_db_prefilter_ungapped; sw_prefilter.hip): sw_prefilter_wave<C> (32-bit lanes,
+// one target per wave) and sw_prefilter_wave16<C> (packed 16-bit lanes, two targets per wave) for C = 4, 8, 16, their index in
+// kPrefilter (sw_api_search.hip, which checks its order against it at compile time).
+// Queries: the groups, the classes and every table entry are plan_search_multi's (the profiles lie where they lie there, so
+// sw_search_profile_submat_multi fills them unchanged); inside a (group, class) the entries of the queries that run packed come first,
+// input order within either part.
+// Packed: a query runs on 16-bit lanes where max_entry x min(qlen, longest target) <= kPrefilterPackedMax (max_entry: the largest
+// table entry, at least 0): no score of any of its pairs leaves int16.  lanes = 32 ("prefilter_lanes") sends every query to 32-bit lanes.
+// Launches: per (group, class) the packed queries and the others get launches of their own, cut by target ranks where the items would
+// pass max_items (the work counter and the cursor of the list are 32 bits wide).  A 32-bit launch has nq x nranks items; item w is
+// (rank rank0 + w / nq, entry q0 + w % nq).  A packed launch has nq x ceil(nranks / 2) items; item w runs the ranks rank0 + 2 (w / nq)
+// and, if it lies inside the launch, the next one -- rank0 is even, and only the last launch of a class can hold an odd last rank.
+// Boundary: per resident wave two columns of one int per row, sized by the handle's longest target; 0 where every query has one strip.
+constexpr int kPrefilterKernels = 6;
+constexpr int prefilter_kernel_index(int C, bool packed) { return 2 * (C / 8) + (packed ? 1 : 0); }
+constexpr int64_t kPrefilterPackedMax = 32767;
+constexpr bool prefilter_packed(int64_t max_entry, int64_t qlen, int64_t longest, int lanes) {
+    return lanes != 32 && (max_entry < 0 ? 0 : max_entry) * (qlen < longest ? qlen : longest) <= kPrefilterPackedMax;
+}
+
+struct PrefilterJob {
+    const int64_t* qlens = nullptr;          // length of every query, input order
+    int64_t nqueries = 0;
+    int64_t longest = 0, nonempty = 0;       // of the handle: longest target, non-empty targets
+    int num_cus = 256;
+    int per_cu[kPrefilterKernels] = {};      // occupancy of every instantiation at 256 threads (workgroups per CU)
+    int64_t budget_bytes = 256ll << 20;      // "search_profile_mib"
+    int64_t max_items = kMultiMaxItems;      // (tests lower it)
+    int max_entry = 0;                       // the largest entry of the substitution table
+    int lanes = 0;                           // "prefilter_lanes": 0 the planner decides, 32 never packed
+};
+
+struct PrefilterLaunch {
+    int group = 0, C = 0, kernel = 0;        // kernel: prefilter_kernel_index(C, packed)
+    bool packed = false;
+    int64_t q0 = 0, nq = 0;                  // its queries: entries q0 .. q0 + nq - 1 of the table
+    int64_t rank0 = 0, nranks = 0;           // its targets: ranks rank0 .. rank0 + nranks - 1 of the handle's schedule
+    int64_t items = 0;                       // nq * nranks, packed: nq * ceil(nranks / 2); <= max_items
+    int64_t bnd_per = 0;                     // per resident wave: boundary ints, 0: every query of the launch has one strip
+    int64_t grid = 0;                        // persistent workgroups of 4 waves: min(resident waves, items) waves
+};
+
+struct PrefilterPlan {
+    std::vector<swk::MultiQuery> table;      // as SearchMultiPlan::table, but for the order inside a (group, class)
+    std::vector<MultiGroup> group;
+    std::vector<PrefilterLaunch> launch;     // in the order they are enqueued: group after group
+    int64_t packed_launches = 0;
+    size_t prof_need = 0, bnd_need = 0;      // workspaces: profiles of the largest group (bytes), boundary columns (ints)
+};
+
+PrefilterPlan plan_prefilter(const PrefilterJob& job);
+
 // ---- the best `top` targets of every row of a query-major result table (sw_top_hits_device, sw_db_search_affine_top; sw_search_top.hip).
 // Key: a target's key is score << tbits | (2^tbits - 1 - target) with tbits = ceil(log2 ntargets): unique per target, and plain integer
 // order of the keys is the rank order (score descending, target ascending).  nbits = 24 + tbits bits of a key can differ.
