@@ -409,8 +409,8 @@ int  sw_align_affine_hits_host(const char* queries, const int64_t* qoffsets, int
  * the groups of sw_db_search_affine ("search_profile_mib").  "last_search_pairs_groups", "last_search_pairs_chunks" and
  * "last_search_pairs_launches" (kernel launches, the profile launches included) describe the last call, all 0 for one that launched
  * no kernel.
- * Alignments of listed pairs are not a call of their own: pack the chosen pairs into an nqueries x top sw_hit table and call
- * sw_db_align_affine_hits.
+ * Alignments of listed pairs: sw_top_hits_pairs_device (below) selects the best entries of every query from the scored list into an
+ * nqueries x top sw_hit table on the device, and sw_db_align_affine_hits aligns that table.
  *   sw_search_affine_pairs_host  the CPU leg: every entry as sw_search_affine_host computes that pair, in plain C++ on host memory, no
  *               GPU needed; every argument is checked before the first pair (SW_EINVAL also for the offsets / length errors of
  *               sw_search_device). */
@@ -458,6 +458,56 @@ int  sw_db_prefilter_ungapped(sw_ctx* ctx, const sw_db* db, const char* d_querie
 int  sw_prefilter_ungapped_host(const char* queries, const int64_t* qoffsets, int64_t nqueries, const char* db,
                                 const int64_t* offsets, int64_t ntargets, const sw_submat* sub, int64_t min_score,
                                 sw_pair* pairs, int64_t pairs_cap, int64_t* npairs, int32_t* scores);
+
+/* The best entries of every query, selected on the device from a scored PAIR LIST (csrc/sw_top_pairs.hip): the step between
+ * sw_db_search_affine_pairs and sw_db_align_affine_hits.  sw_top_hits_device needs a dense nqueries x ntargets table; the list of a
+ * pre-filter lies in the order of an atomic cursor, unsorted and ungrouped, and this call turns it into the same kind of hit table.
+ *   d_pairs, d_results : device, npairs entries each, only read; entry p of the results belongs to entry p of the pairs, exactly as
+ *             sw_db_search_affine_pairs leaves them.
+ *   An entry QUALIFIES when 0 <= query < nqueries, 0 <= target < ntargets and max_score >= min_score.  Each index is compared UNSIGNED
+ *             against its bound before anything is indexed with it (the rule of sw_db_align_affine_hits), so the {-1, -1} tail of
+ *             sw_db_prefilter_ungapped drops out by itself: a caller passes all pairs_cap entries and never reads the count.  With
+ *             min_score <= 0 every in-range entry qualifies.  PRECONDITION, as for sw_top_hits_device: 0 <= max_score < 2^24 for the
+ *             in-range entries; scores are taken modulo 2^24 so that no input carries a key out of its field.
+ *   d_hits  : device, nqueries x top sw_hit.  Row q holds the first `top` qualifying entries of query q in the order max_score
+ *             descending, then target ascending, then LIST POSITION ascending; hit = {target, max_pos, max_score} copied from the
+ *             entry.  The third key makes the output unique for ANY input, duplicates of a pair included, also where a caller made
+ *             their results differ: duplicates are kept, each one takes a rank.  The rest of a row is {-1, 0, 0}.
+ *   d_nhits : device, nqueries int64: d_nhits[q] = min(top, qualifying entries of query q).
+ * Every entry of d_hits and d_nhits is written and nothing outside them.  Asynchronous on `stream`, no host round trip; the host work
+ * is O(1): it reads neither the list nor the results.  The same bytes come out on every run, although the entries are grouped with
+ * atomics.  The entries are grouped per query in a per-context workspace of 12 bytes per list entry and 8 bytes per query that grows
+ * on demand.  A query with many entries is ordered by ONE workgroup, in blocks once it has more than SW_TOP_MAX (top <= 2048) or
+ * 2 x SW_TOP_MAX entries: the call is made for lists that are small on purpose.
+ * SW_EINVAL: NULL d_hits or d_nhits; NULL d_pairs or d_results with npairs > 0; npairs < 0 or npairs >= 2^31; nqueries < 0;
+ * ntargets < 0 or ntargets >= 2^31; top < 1 or top > SW_TOP_MAX.  npairs == 0 writes nhits = 0 and the {-1, 0, 0} pattern;
+ * nqueries == 0 launches nothing.  "last_top_pairs_launches" (kernel launches) and "last_top_pairs_kernel" (0: every segment could be
+ * sorted whole because npairs <= SW_TOP_MAX; 1: the streaming form was compiled in for the call) describe the last call.
+ *   sw_top_hits_pairs_host  the CPU leg: the same table from host memory in plain C++, no GPU needed.
+ *
+ *   sw_db_search_affine_top_prefiltered  the whole chain in one call: sw_db_prefilter_ungapped (the table of `scoring`, threshold
+ *             prefilter_min_score, no d_scores), sw_db_search_affine_pairs over all pairs_cap entries, then the selection above, all on
+ *             `stream` with no host read in between.  d_queries, qoffsets, scoring and the handle as for sw_db_search_affine; top,
+ *             min_score, d_hits, d_nhits as above.
+ *             WHAT IT COMPUTES: the table of sw_db_search_affine_top restricted to the pairs with U >= prefilter_min_score (U: the
+ *             ungapped score above).  That is a FILTER, not the same hits: a pair whose gapped score is high and whose best gapless
+ *             segment is below the threshold is not found.  One case is exact: with prefilter_min_score = 1 and min_score >= 1 the two
+ *             tables are identical, because a positive local score needs a positive cell.
+ *             d_npairs (device, one int64, not NULL) receives the filter's TRUE count.  Where it exceeds pairs_cap the table is built
+ *             from the pairs the list happened to keep: every hit is then still a correct, passing pair, but the table is NEITHER
+ *             COMPLETE NOR REPRODUCIBLE.  The call cannot know without a host read: the caller checks the count after the call.
+ *             The list and its results live in a per-context workspace of 40 bytes per entry; with the selection's segments that is at
+ *             most 56 bytes x pairs_cap, which the option "search_results_mib" bounds: a larger pairs_cap is SW_EINVAL with a message
+ *             that names the option.  Every argument is checked before the first launch.  SW_EINVAL besides: the argument errors of
+ *             sw_db_search_affine, prefilter_min_score < 1, pairs_cap < 0 or >= 2^31, NULL d_npairs, NULL d_hits or d_nhits, top < 1 or
+ *             top > SW_TOP_MAX. */
+int  sw_top_hits_pairs_device(sw_ctx* ctx, const sw_pair* d_pairs, const sw_result* d_results, int64_t npairs, int64_t nqueries,
+                              int64_t ntargets, int64_t top, int64_t min_score, sw_hit* d_hits, int64_t* d_nhits, void* stream);
+int  sw_top_hits_pairs_host(const sw_pair* pairs, const sw_result* results, int64_t npairs, int64_t nqueries, int64_t ntargets,
+                            int64_t top, int64_t min_score, sw_hit* hits, int64_t* nhits);
+int  sw_db_search_affine_top_prefiltered(sw_ctx* ctx, const sw_db* db, const char* d_queries, const int64_t* qoffsets, int64_t nqueries,
+                                         const sw_affine* scoring, int64_t prefilter_min_score, int64_t pairs_cap, int64_t top,
+                                         int64_t min_score, sw_hit* d_hits, int64_t* d_nhits, int64_t* d_npairs, void* stream);
 
 /* Tables.  sw_submat_match: s[x][y] = x == y ? match : mismatch (matchMissmatchScore, serial_smithW.c:251-256; both must fit int8:
  * the builder returns nothing, so it clamps them to -128..127 -- a caller that takes them from a user checks the range first, as
@@ -657,7 +707,9 @@ int sw_synchronize(sw_ctx* ctx, void* stream);   /* waits for `stream`; reports 
  * "last_align_hits_slots" and "last_align_hits_lists" the last sw_db_align_affine_hits call; "search_pairs_chunk" (settable, default
  * 2^22, 1..2^31 - 1) is the most entries of a pair list that sw_db_search_affine_pairs bins at a time, "last_search_pairs_groups",
  * "last_search_pairs_chunks" and "last_search_pairs_launches" describe the last such call; "prefilter_lanes" (settable, 0 or 32) and
- * "last_prefilter_groups", "last_prefilter_launches", "last_prefilter_packed_launches" belong to sw_db_prefilter_ungapped (above).
+ * "last_prefilter_groups", "last_prefilter_launches", "last_prefilter_packed_launches" belong to sw_db_prefilter_ungapped (above);
+ * "last_top_pairs_launches" and "last_top_pairs_kernel" describe the last sw_top_hits_pairs_device call, and "search_results_mib" also
+ * bounds the pairs_cap of sw_db_search_affine_top_prefiltered (56 bytes per entry).
  * "debug_search_pairs_items_ptr" (an
  * accessor for tests) is the device address of that call's item workspace, which a call leaves as its last (chunk, group) filled it:
  * 24-byte items {int64 start, int64 out, int32 len, int32 entry}, the classes' lists back to back. */

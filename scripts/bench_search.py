@@ -37,6 +37,14 @@
   reach (the quantile of a d_scores run, printed); (iii) the filter and sw_db_search_affine_pairs over its whole list, no count read in
   between.  Checked on the device: every result of (iii) for a passing pair is the table entry of (i), U <= max_score for ALL pairs, the
   two kernels give the same scores; the run fails if a check fails or if (ii) is not faster than (i)
+  --prefiltered-top: the data set and the threshold rule of --prefilter, top = 10, six legs in one process on the same buffers, torch events
+  around whole calls, medians and ranges of --reps after --warmup: (i) sw_db_search_affine_top, the baseline; (ii) sw_db_prefilter_ungapped,
+  sw_db_search_affine_pairs and sw_top_hits_pairs_device chained by hand; (iii) sw_db_search_affine_top_prefiltered, the one call; (iv)
+  the selection alone over the list of (ii); (v) the dense sw_top_hits_device over the full table, for scale; (vi) (i) and (iii) each
+  followed by sw_db_align_affine_hits.  The selection alone again over the list of a threshold that 10 % of the pairs reach: segments of
+  about 20 000 entries, the streaming sort.  Checked on the device: the tables of (ii) and (iii) are equal, both equal the top 10 of
+  the full table masked by U >= S (torch, from a d_scores run), the count is at most the cap; the run fails if a check fails or if
+  (iii) is not faster than (i).  The recall -- the share of (i)'s hits that (iii) found -- is recorded, not gated
 GCUPS = query letters x target letters / time of the call (torch events, median of --reps after --warmup)."""
 import argparse
 import importlib
@@ -84,6 +92,7 @@ def main():
     ap.add_argument("--checkpoint", action="store_true", help="with --align-hits: checkpointed alignment beside the whole-matrix path, hit table and one query")
     ap.add_argument("--pairs", action="store_true", help="data set (a) only: a pair list of 1 %% and of all of the cross product of 64 queries beside the full search")
     ap.add_argument("--prefilter", action="store_true", help="data set (a) only: the ungapped pre-filter of 64 queries, alone and chained into the pair-list search, beside the full search")
+    ap.add_argument("--prefiltered-top", action="store_true", help="data set (a) only: the top 10 of 64 queries by the full search and by pre-filter, rescoring and selection from the pair list")
     ap.add_argument("--top", action="store_true", help="data set (a) only: the best 100 targets of 64 queries by the full table and by the selection on the device")
     args = ap.parse_args()
     rng = np.random.default_rng(2026)
@@ -423,6 +432,115 @@ def main():
         out["prefilter_chain_rescored_cells"] = int(float(args.qlen) * float(lens[pr[:, 1].cpu().numpy()].sum())) if inside else 0
         db.close()
 
+    def prefiltered_top_leg(packed, offs, nq=64, top=10):
+        d_db = torch.from_numpy(packed.copy()).to(dev)
+        db = eng.prepare_db(d_db, offs)
+        nt = len(offs) - 1
+        qoffs = np.arange(nq + 1, dtype=np.int64) * args.qlen
+        d_q = torch.from_numpy(rng.choice(PROTEIN, int(qoffs[-1])).astype(np.uint8)).to(dev)
+        scoring = (sub, -11, -1)
+        n_all = nq * nt
+        P = "prefiltered_top"
+        out[f"{P}_queries"], out[f"{P}_qlen"], out[f"{P}_targets"], out[f"{P}_top"] = nq, args.qlen, nt, top
+        # the full table and the ungapped scores of all pairs: the reference of the checks and the threshold about 1 % of the pairs reach
+        table = db.search_affine_device(d_q, qoffs, scoring).view(nq, nt, 3)
+        _, _, u = db.prefilter_ungapped_device(d_q, qoffs, sub, 1, 0, want_scores=True)
+        torch.cuda.synchronize()
+        flat_u = u.view(-1)
+        S = max(1, int(flat_u.float().kthvalue(n_all - n_all // 100).values.item()))
+        S_low = max(1, int(flat_u.float().kthvalue(n_all - n_all // 10).values.item()))
+        cap = int((flat_u >= S).sum().item())               # (every target of data set (a) has a letter)
+        out[f"{P}_min_score"], out[f"{P}_passing"], out[f"{P}_passing_share"] = S, cap, round(cap / n_all, 5)
+        tbits = max(1, int(nt - 1).bit_length())
+
+        def masked_top(thr):
+            """The top rows of the full table among the pairs with U >= thr, by torch: (hits, nhits) as the library lays them out."""
+            score = torch.where(u >= thr, table[:, :, 1], torch.full_like(table[:, :, 1], -1))
+            key = torch.where(score >= 0, (score << tbits) | (nt - 1 - torch.arange(nt, device=dev)), torch.full_like(score, -1))
+            best, target = key.topk(top, dim=1)
+            ok = best >= 0
+            rows = torch.gather(table, 1, target[:, :, None].expand(nq, top, 3))
+            hits = torch.stack([torch.where(ok, target, torch.full_like(target, -1)), torch.where(ok, rows[:, :, 0], torch.zeros_like(target)),
+                                torch.where(ok, rows[:, :, 1], torch.zeros_like(target))], dim=2)
+            return hits, ok.sum(dim=1)
+
+        want_hits, want_nhits = masked_top(S)
+        outs = {k: (torch.zeros(nq * top * 3, dtype=torch.int64, device=dev), torch.zeros(nq, dtype=torch.int64, device=dev)) for k in ("i", "ii", "iii", "iv", "v")}
+        # leg i: search and dense selection in one call, the parent's code
+        out[f"{P}_full_ms"], out[f"{P}_full_range_ms"] = spread(lambda: db.search_affine_top_device(d_q, qoffs, scoring, top, 0, out=outs["i"]))
+        # leg ii: the three calls by hand, nothing read in between
+        bufs = (torch.empty((cap, 2), dtype=torch.int64, device=dev), torch.zeros(1, dtype=torch.int64, device=dev), None)
+        res = torch.full((cap * 3,), -1, dtype=torch.int64, device=dev)
+
+        def chain():
+            d_pairs, _, _ = db.prefilter_ungapped_device(d_q, qoffs, sub, S, cap, out=bufs)
+            r = db.search_affine_pairs_device(d_q, qoffs, scoring, d_pairs, out=res)
+            return eng.top_hits_pairs_device(d_pairs, r, cap, nq, nt, top, 0, out=outs["ii"])
+
+        out[f"{P}_chain_ms"], out[f"{P}_chain_range_ms"] = spread(chain)
+        out[f"{P}_chain_count"] = int(bufs[1].item())
+        # the shares of the hand chain, each alone on the same buffers
+        out[f"{P}_filter_ms"], out[f"{P}_filter_range_ms"] = spread(lambda: db.prefilter_ungapped_device(d_q, qoffs, sub, S, cap, out=bufs))
+        out[f"{P}_rescore_ms"], out[f"{P}_rescore_range_ms"] = spread(lambda: db.search_affine_pairs_device(d_q, qoffs, scoring, bufs[0], out=res))
+        # leg iii: the one call
+        npairs = [None]
+
+        def one_call():
+            h, n, npairs[0] = db.search_affine_top_prefiltered_device(d_q, qoffs, scoring, S, cap, top, 0, out=outs["iii"])
+            return h, n
+
+        out[f"{P}_one_call_ms"], out[f"{P}_one_call_range_ms"] = spread(one_call)
+        out[f"{P}_one_call_count"] = int(npairs[0].item())
+        out[f"{P}_count_within_cap"] = bool(out[f"{P}_one_call_count"] <= cap and out[f"{P}_chain_count"] <= cap)
+        # leg iv: the selection alone over the list of leg ii
+        out[f"{P}_select_ms"], out[f"{P}_select_range_ms"] = spread(lambda: eng.top_hits_pairs_device(bufs[0], res.view(cap, 3), cap, nq, nt, top, 0, out=outs["iv"]))
+        out[f"{P}_select_launches"], out[f"{P}_select_kernel"] = eng.get_option("last_top_pairs_launches"), eng.get_option("last_top_pairs_kernel")
+        out[f"{P}_select_longest_segment"] = int(torch.bincount(bufs[0][:, 0], minlength=nq).max().item())
+        # leg v: the dense selection over the full table, for scale
+        out[f"{P}_dense_select_ms"], out[f"{P}_dense_select_range_ms"] = spread(lambda: eng.top_hits_device(table, nq, nt, top, 0, out=outs["v"]))
+        views = {k: eng._top_views(h, n, nq, top) for k, (h, n) in outs.items()}
+        torch.cuda.synchronize()
+        out[f"{P}_chain_equals_one_call"] = bool(torch.equal(views["ii"][0], views["iii"][0]) and torch.equal(views["ii"][1], views["iii"][1]))
+        for k, tag in (("ii", "chain"), ("iii", "one_call"), ("iv", "select")):
+            out[f"{P}_{tag}_equals_masked_table"] = bool(torch.equal(views[k][0], want_hits) and torch.equal(views[k][1], want_nhits))
+        found = (views["i"][0][:, :, None, 0] == views["iii"][0][:, None, :, 0]).any(dim=2) & (views["i"][0][:, :, 0] >= 0)
+        out[f"{P}_recall"] = round(float(found.sum().item()) / max(1, int((views["i"][0][:, :, 0] >= 0).sum().item())), 4)
+        out[f"{P}_one_call_faster_than_full"] = bool(out[f"{P}_one_call_ms"] < out[f"{P}_full_ms"])
+        out[f"{P}_full_over_one_call"] = round(out[f"{P}_full_ms"] / out[f"{P}_one_call_ms"], 2)
+        out[f"{P}_select_over_rescore"] = round(out[f"{P}_select_ms"] / out[f"{P}_rescore_ms"], 4)
+        out[f"{P}_select_over_dense_select"] = round(out[f"{P}_select_ms"] / out[f"{P}_dense_select_ms"], 4)
+        # leg vi: legs i and iii, each followed by the alignment of its table
+        ops_cap = args.qlen + int(np.diff(offs).max())
+        abufs = (torch.zeros((nq * top, 7), dtype=torch.int64, device=dev), torch.zeros((nq * top, ops_cap), dtype=torch.uint8, device=dev))
+
+        def full_aligned():
+            h, n = db.search_affine_top_device(d_q, qoffs, scoring, top, 0, out=outs["i"])
+            db.align_affine_hits_device(d_q, qoffs, scoring, h, n, ops_cap=ops_cap, out=abufs)
+
+        def one_call_aligned():
+            h, n = one_call()
+            db.align_affine_hits_device(d_q, qoffs, scoring, h, n, ops_cap=ops_cap, out=abufs)
+
+        out[f"{P}_full_aligned_ms"], out[f"{P}_full_aligned_range_ms"] = spread(full_aligned)
+        out[f"{P}_one_call_aligned_ms"], out[f"{P}_one_call_aligned_range_ms"] = spread(one_call_aligned)
+        # the streaming sort: the selection alone over the list of a threshold that about 10 % of the pairs reach
+        cap_low = int((flat_u >= S_low).sum().item())
+        low = (torch.empty((cap_low, 2), dtype=torch.int64, device=dev), torch.zeros(1, dtype=torch.int64, device=dev), None)
+        db.prefilter_ungapped_device(d_q, qoffs, sub, S_low, cap_low, out=low)
+        res_low = db.search_affine_pairs_device(d_q, qoffs, scoring, low[0])
+        out[f"{P}_low_min_score"], out[f"{P}_low_passing"] = S_low, cap_low
+        for t2 in (top, 4096):
+            o = (torch.zeros(nq * t2 * 3, dtype=torch.int64, device=dev), torch.zeros(nq, dtype=torch.int64, device=dev))
+            out[f"{P}_low_select_top{t2}_ms"], out[f"{P}_low_select_top{t2}_range_ms"] = spread(
+                lambda: eng.top_hits_pairs_device(low[0], res_low, cap_low, nq, nt, t2, 0, out=o))
+            if t2 == top:
+                low_hits, low_nhits = masked_top(S_low)
+                got = eng._top_views(o[0], o[1], nq, top)
+                out[f"{P}_low_select_equals_masked_table"] = bool(torch.equal(got[0], low_hits) and torch.equal(got[1], low_nhits))
+        out[f"{P}_low_select_kernel"] = eng.get_option("last_top_pairs_kernel")
+        out[f"{P}_low_longest_segment"] = int(torch.bincount(low[0][:, 0], minlength=nq).max().item())
+        db.close()
+
     def align_ckpt_leg(q, packed, offs, nq=64):
         d_db = torch.from_numpy(packed.copy()).to(dev)
         db = eng.prepare_db(d_db, offs)
@@ -494,11 +612,13 @@ def main():
     out["a_letters"] = int(offs[-1])
     out["a_len_median"] = int(np.median(lens))
     out["a_len_max"] = int(lens.max())
-    if args.multi or args.top or args.align_hits or args.pairs or args.prefilter:
+    if args.multi or args.top or args.align_hits or args.pairs or args.prefilter or args.prefiltered_top:
         if args.pairs:
             pairs_leg(packed, offs)
         if args.prefilter:
             prefilter_leg(packed, offs)
+        if args.prefiltered_top:
+            prefiltered_top_leg(packed, offs)
         if args.multi:
             multi_legs(packed, offs)
         if args.align_hits and args.checkpoint:
@@ -518,6 +638,12 @@ def main():
                                   "prefilter_packed_count_ok", "prefilter_lanes32_faster_than_full", "prefilter_packed_faster_than_full") if not out[k]]
             if missed:
                 sys.exit("bench_search.py --prefilter: " + ", ".join(missed) + " is false")
+        if args.prefiltered_top:   # the required conditions of the selection from the list: a line that misses one is printed, and the run fails
+            missed = [k for k in ("prefiltered_top_chain_equals_one_call", "prefiltered_top_chain_equals_masked_table", "prefiltered_top_one_call_equals_masked_table",
+                                  "prefiltered_top_select_equals_masked_table", "prefiltered_top_low_select_equals_masked_table", "prefiltered_top_count_within_cap",
+                                  "prefiltered_top_one_call_faster_than_full") if not out[k]]
+            if missed:
+                sys.exit("bench_search.py --prefiltered-top: " + ", ".join(missed) + " is false")
         return
     search_gcups(q, packed, offs, "a")
     align_legs(q, packed, offs, affine_gcups(q, packed, offs, "a"), "a")

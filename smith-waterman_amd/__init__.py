@@ -77,6 +77,9 @@ ABI = {
     "sw_top_hits_device": (_i32, [_vp, _vp, _i64, _i64, _i64, _i64, _vp, _vp, _vp]),
     "sw_db_search_affine_top": (_i32, [_vp, _vp, _vp, _vp, _i64, ctypes.POINTER(_Affine), _i64, _i64, _vp, _vp, _vp]),
     "sw_search_affine_multi_top_host": (_i32, [_vp, _vp, _i64, _vp, _vp, _i64, ctypes.POINTER(_Affine), _i64, _i64, _vp, _vp]),
+    "sw_top_hits_pairs_device": (_i32, [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _vp]),
+    "sw_top_hits_pairs_host": (_i32, [_vp, _vp, _i64, _i64, _i64, _i64, _i64, _vp, _vp]),
+    "sw_db_search_affine_top_prefiltered": (_i32, [_vp, _vp, _vp, _vp, _i64, ctypes.POINTER(_Affine), _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp]),
     "sw_db_align_affine_hits": (_i32, [_vp, _vp, _vp, _vp, _i64, ctypes.POINTER(_Affine), _vp, _vp, _i64, _vp, _vp, _i64, _vp]),
     "sw_align_affine_hits_host": (_i32, [_vp, _vp, _i64, _vp, _vp, _i64, ctypes.POINTER(_Affine), _vp, _vp, _i64, _vp, _vp, _i64]),
     "sw_align_affine_device": (_i32, [_vp, _vp, _i64, _vp, _vp, _i64, _vp, _i64, ctypes.POINTER(_Affine), _vp, _vp, _i64, _vp]),
@@ -328,6 +331,24 @@ def search_affine_multi_top_host(queries, targets, scoring, top: int, min_score:
     sub, sc = _affine(*scoring)
     _check(lib().sw_search_affine_multi_top_host(qs.ctypes.data, qoffs.ctypes.data, nq, db.ctypes.data, offs.ctypes.data, ntargets, ctypes.byref(sc),
                                                  int(top), int(min_score), hits.ctypes.data, nhits.ctypes.data))
+    return hits[:nq * k].reshape(nq, k, 3), nhits[:nq]
+
+
+def top_hits_pairs_host(pairs, results, nqueries: int, ntargets: int, top: int, min_score: int = 0):
+    """sw_top_hits_pairs_host: the best `top` entries of every query of a scored pair list in plain C++ on the host (no GPU).  pairs an
+    (npairs, 2) int64 array of (query, target), results the (npairs, 3) int64 array of (max_pos, max_score, path_len) that belongs to
+    it entry for entry.  An entry qualifies when its query and target lie inside nqueries and ntargets and max_score >= min_score; a
+    row is ordered by score descending, then target ascending, then list position.  Returns (hits (nqueries, top, 3) int64 of
+    (target, max_pos, max_score), unused entries (-1, 0, 0); nhits (nqueries,) int64)."""
+    pr = _pair_list(pairs)
+    res = np.ascontiguousarray(results, np.int64).reshape(-1, 3)
+    if len(res) != len(pr):
+        raise ValueError("results must hold one (max_pos, max_score, path_len) row per pair")
+    nq, k = max(0, int(nqueries)), max(0, int(top))
+    hits = np.zeros((max(1, nq * k), 3), np.int64)
+    nhits = np.zeros(max(1, nq), np.int64)
+    _check(lib().sw_top_hits_pairs_host(pr.ctypes.data if len(pr) else None, res.ctypes.data if len(pr) else None, len(pr), int(nqueries), int(ntargets),
+                                        int(top), int(min_score), hits.ctypes.data, nhits.ctypes.data))
     return hits[:nq * k].reshape(nq, k, 3), nhits[:nq]
 
 
@@ -688,6 +709,42 @@ class Database:
                                              hits.data_ptr(), nhits.data_ptr(), eng._stream()))
         return eng._top_views(hits, nhits, nq, top)
 
+    def search_affine_top_prefiltered(self, queries, scoring, prefilter_min_score: int, top: int, min_score: int = 0, cap=None):
+        """Filter, rescoring and selection in one call on host queries (sw_db_search_affine_top_prefiltered): the table of
+        search_affine_top restricted to the pairs whose ungapped score reaches prefilter_min_score.  cap, the length of the pair list,
+        defaults to nqueries x ntargets; SwError if more pairs pass than it holds.  Returns numpy (hits, nhits, npairs)."""
+        eng = self.engine
+        t = eng.torch
+        qpacked, qoffs = _pack_targets(queries)
+        nq = len(qoffs) - 1
+        cap = nq * self.ntargets if cap is None else int(cap)
+        d_q = t.from_numpy(qpacked.copy() if len(qpacked) else np.zeros(1, np.uint8)).to(f"cuda:{eng.device}")
+        hits, nhits, npairs = self.search_affine_top_prefiltered_device(d_q, qoffs, scoring, prefilter_min_score, cap, top, min_score)
+        eng.synchronize()
+        n = int(npairs.item())
+        if n > cap:
+            raise SwError(-22, f"search_affine_top_prefiltered: {n} pairs pass the pre-filter, the list holds {cap}: raise cap or prefilter_min_score")
+        return hits.cpu().numpy(), nhits.cpu().numpy(), n
+
+    def search_affine_top_prefiltered_device(self, d_queries, qoffsets, scoring, prefilter_min_score: int, cap: int, top: int, min_score: int = 0,
+                                             out=None):
+        """sw_db_search_affine_top_prefiltered on device-resident queries; asynchronous on torch's current stream, nothing comes to the
+        host.  Returns torch (hits (nqueries, top, 3), nhits (nqueries,), npairs (1,)): the table and the pre-filter's TRUE count --
+        where it exceeds cap the table is neither complete nor reproducible, the caller checks.  `out` = (hits, nhits) as for
+        search_affine_top_device."""
+        eng = self.engine
+        t = eng.torch
+        qoffs = np.ascontiguousarray(qoffsets, np.int64).reshape(-1)
+        if len(qoffs) == 0:
+            qoffs = np.zeros(1, np.int64)
+        nq = len(qoffs) - 1
+        hits, nhits = eng._top_out(nq, top, out)
+        npairs = t.zeros(1, dtype=t.int64, device=f"cuda:{eng.device}")
+        sub, sc = _affine(*scoring)
+        _check(lib().sw_db_search_affine_top_prefiltered(eng._h, self._h, d_queries.data_ptr(), qoffs.ctypes.data, nq, ctypes.byref(sc),
+                                                         int(prefilter_min_score), int(cap), int(top), int(min_score), hits.data_ptr(),
+                                                         nhits.data_ptr(), npairs.data_ptr(), eng._stream()))
+        return eng._top_views(hits, nhits, nq, top) + (npairs,)
 
     def align_affine_hits(self, queries, scoring, hits, nhits=None, checkpoint=None):
         """The alignments of a hit table (sw_db_align_affine_hits): queries and scoring as for search_affine; hits a (nqueries, top, 3)
@@ -1038,6 +1095,16 @@ class Engine:
         hits, nhits = self._top_out(int(nqueries), top, out)
         _check(lib().sw_top_hits_device(self._h, d_results.data_ptr(), int(nqueries), int(ntargets), int(top), int(min_score), hits.data_ptr(),
                                         nhits.data_ptr(), self._stream()))
+        return self._top_views(hits, nhits, int(nqueries), top)
+
+    def top_hits_pairs_device(self, d_pairs, d_results, npairs: int, nqueries: int, ntargets: int, top: int, min_score: int = 0, out=None):
+        """sw_top_hits_pairs_device: the best `top` entries of every query of a scored pair list on the device -- d_pairs (npairs, 2) and
+        d_results (npairs, 3) int64 tensors as Database.prefilter_ungapped_device and search_affine_pairs_device leave them, all cap
+        rows: the (-1, -1) rows drop out.  Asynchronous on torch's current stream.  Returns torch (hits (nqueries, top, 3) of (target,
+        max_pos, max_score), nhits (nqueries,)); `out` as for Database.search_affine_top_device."""
+        hits, nhits = self._top_out(int(nqueries), top, out)
+        _check(lib().sw_top_hits_pairs_device(self._h, d_pairs.data_ptr() if npairs else None, d_results.data_ptr() if npairs else None, int(npairs),
+                                              int(nqueries), int(ntargets), int(top), int(min_score), hits.data_ptr(), nhits.data_ptr(), self._stream()))
         return self._top_views(hits, nhits, int(nqueries), top)
 
     def prepare_db(self, db, offsets=None) -> Database:

@@ -12,6 +12,10 @@
 //                              --gap-open, --gap-extend and --align (one sw_db_align_affine_hits call on the device hit table) as for one query.  The K best hits per
 //                              query are selected on the device (sw_db_search_affine_top): only they are copied back
 //     ... --min-score S       with --all-queries: only hits with a score of at least S are printed (fewer than K where fewer qualify)
+//     ... --prefilter-hits S  with --all-queries: the blocks of --all-queries (--top, --min-score, --align as there), the hits selected among the pairs whose
+//                              ungapped score is at least S: pre-filter, rescoring of the passing pairs and selection from that list in one call
+//                              (sw_db_search_affine_top_prefiltered), a fraction of the full search's time; the elapsed line says how many pairs passed.
+//                              More passing pairs than the list holds ("search_results_mib") is an error: raise S.  Not with --prefilter or --pairs.
 //     ... --prefilter S       with --all-queries: the ungapped pre-filter (sw_db_prefilter_ungapped) and then the affine search of the pairs whose ungapped
 //                              score reaches S (sw_db_search_affine_pairs on the filter's device list): one handle, one read-back; the passing pairs in
 //                              ascending (query, target) order in the line format of --pairs with " ungapped=<U>" appended; S >= 1; not with --top,
@@ -221,8 +225,10 @@ static int search_main(const char* qpath, long long rec, const char* dbpath, lon
 // best hits of every query are selected on the device and only they come back; more than SW_TOP_MAX hits per query go the long way:
 // the whole table to the host and a sort of every row.  A linear search goes through the match / mismatch table of --scores with
 // gap_open 0, which sw_search_device equals bit for bit.
+// --prefilter-hits S (prefilter_hits > 0): sw_db_search_affine_top_prefiltered takes the place of sw_db_search_affine_top -- the hits are
+// selected among the pairs whose ungapped score reaches S, on the device from the rescored pair list; everything else is the same.
 static int search_all_main(const char* qpath, const char* dbpath, long long top, long long min_score, const sw_scores& sc, const AffineArgs& af, bool align,
-                           bool align_ckpt) {
+                           bool align_ckpt, long long prefilter_hits = 0) {
     int64_t nq = 0, qtotal = 0, nrec = 0, total = 0;
     CHECK(sw_read_fasta_db(qpath, nullptr, 0, nullptr, 0, &nq, &qtotal));
     std::vector<char> qs((size_t)qtotal + 1);
@@ -234,11 +240,19 @@ static int search_all_main(const char* qpath, const char* dbpath, long long top,
     CHECK(sw_read_fasta_db(dbpath, db.data(), total, offs.data(), nrec + 1, &nrec, &total));
     const long long K = std::max(0ll, std::min(top, (long long)nrec));
     const bool on_device = K <= SW_TOP_MAX;
+    if (prefilter_hits > 0 && !on_device) {
+        fprintf(stderr, "smithW: --prefilter-hits selects on the device: min(--top, records) = %lld is above %d\n", K, SW_TOP_MAX);
+        return 2;
+    }
     sw_ctx* ctx = nullptr;
     CHECK(sw_create(0, &ctx));
     // --align-checkpoint: a table the one call would refuse for its worst pair goes through it checkpointed instead of query by query
     if (align_ckpt) CHECK(sw_set_option(ctx, "align_checkpoint", 2));
-    void *d_q = nullptr, *d_db = nullptr, *d_res = nullptr, *d_hits = nullptr, *d_nhits = nullptr;
+    void *d_q = nullptr, *d_db = nullptr, *d_res = nullptr, *d_hits = nullptr, *d_nhits = nullptr, *d_npairs = nullptr;
+    // the pair list of --prefilter-hits: every pair, or as many as "search_results_mib" lets the call hold (56 bytes each)
+    const int64_t pairs_cap = std::min<int64_t>(nq * nrec, (sw_get_option(ctx, "search_results_mib") << 20) / 56);
+    int64_t npassed = 0;
+    CHECK(sw_device_malloc(ctx, sizeof(int64_t), &d_npairs));
     const size_t nres = on_device ? 1 : (size_t)std::max<int64_t>(1, nq * nrec), nhit = (size_t)std::max<int64_t>(1, nq * K);
     CHECK(sw_device_malloc(ctx, (size_t)qtotal + 16, &d_q));
     CHECK(sw_device_malloc(ctx, (size_t)total + 16, &d_db));
@@ -256,9 +270,20 @@ static int search_all_main(const char* qpath, const char* dbpath, long long top,
     CHECK(sw_db_create(ctx, (const char*)d_db, offs.data(), nrec, &handle));
     const double t1 = now_s();
     if (!on_device) CHECK(sw_db_search_affine(ctx, handle, (const char*)d_q, qoffs.data(), nq, &aff, (sw_result*)d_res, nullptr));
+    else if (K > 0 && prefilter_hits > 0)
+        CHECK(sw_db_search_affine_top_prefiltered(ctx, handle, (const char*)d_q, qoffs.data(), nq, &aff, prefilter_hits, pairs_cap, K, min_score, (sw_hit*)d_hits,
+                                                  (int64_t*)d_nhits, (int64_t*)d_npairs, nullptr));
     else if (K > 0) CHECK(sw_db_search_affine_top(ctx, handle, (const char*)d_q, qoffs.data(), nq, &aff, K, min_score, (sw_hit*)d_hits, (int64_t*)d_nhits, nullptr));
     CHECK(sw_synchronize(ctx, nullptr));
     const double t2 = now_s();
+    if (K > 0 && prefilter_hits > 0) {
+        CHECK(sw_memcpy_d2h(ctx, &npassed, d_npairs, sizeof npassed));
+        if (npassed > pairs_cap) {   // the table was built from the pairs the list happened to keep: not a result
+            fprintf(stderr, "smithW: --prefilter-hits %lld: %lld pairs pass the pre-filter, the list holds %lld: raise S\n", prefilter_hits, (long long)npassed,
+                    (long long)pairs_cap);
+            return 1;
+        }
+    }
     std::vector<sw_hit> hits(nhit);
     std::vector<int64_t> nhits((size_t)nq + 1, 0);
     if (on_device && K > 0 && nq > 0) {
@@ -307,9 +332,14 @@ static int search_all_main(const char* qpath, const char* dbpath, long long top,
                                 ops_cap)) return rc;
     }
     const double cells = (double)qtotal * (double)total;
-    printf("\nElapsed time for database search: %f (%.1f GCUPS; %lld queries in one call, handle prepared in %f)\n\n", t2 - t1,
-           t2 > t1 ? cells / (t2 - t1) / 1e9 : 0.0, (long long)nq, t1 - t0);
+    if (prefilter_hits > 0)
+        printf("\nElapsed time for database search: %f (%.1f GCUPS; %lld queries in one call, %lld of %lld pairs passed the pre-filter U >= %lld, handle prepared in %f)\n\n",
+               t2 - t1, t2 > t1 ? cells / (t2 - t1) / 1e9 : 0.0, (long long)nq, (long long)npassed, (long long)(nq * nrec), prefilter_hits, t1 - t0);
+    else
+        printf("\nElapsed time for database search: %f (%.1f GCUPS; %lld queries in one call, handle prepared in %f)\n\n", t2 - t1,
+               t2 > t1 ? cells / (t2 - t1) / 1e9 : 0.0, (long long)nq, t1 - t0);
     sw_db_free(handle);
+    (void)sw_device_free(ctx, d_npairs);
     (void)sw_device_free(ctx, d_q); (void)sw_device_free(ctx, d_db); (void)sw_device_free(ctx, d_res);
     (void)sw_device_free(ctx, d_hits); (void)sw_device_free(ctx, d_nhits);
     sw_destroy(ctx);
@@ -504,8 +534,8 @@ int main(int argc, char** argv) {
     const char *fasta_a = nullptr, *fasta_b = nullptr;
     long long rec_a = 0, rec_b = 0;
     const char *search_q = nullptr, *search_db = nullptr;
-    long long top = 10, min_score = 0, prefilter = 0;
-    bool has_min_score = false, has_top = false, has_prefilter = false;
+    long long top = 10, min_score = 0, prefilter = 0, prefilter_hits = 0;
+    bool has_min_score = false, has_top = false, has_prefilter = false, has_prefilter_hits = false;
     const char* pairs_path = nullptr;
     AffineArgs af;
     bool align = false, all_queries = false, align_ckpt = false;
@@ -531,6 +561,7 @@ int main(int argc, char** argv) {
         else if (f == "--pairs" && ai + 1 < argc) pairs_path = argv[++ai];
         else if (f == "--min-score" && ai + 1 < argc) { int v = 0; if (!parse_int("--min-score", argv[++ai], &v)) return 2; min_score = v; has_min_score = true; }
         else if (f == "--prefilter" && ai + 1 < argc) { int v = 0; if (!parse_int("--prefilter", argv[++ai], &v)) return 2; prefilter = v; has_prefilter = true; }
+        else if (f == "--prefilter-hits" && ai + 1 < argc) { int v = 0; if (!parse_int("--prefilter-hits", argv[++ai], &v)) return 2; prefilter_hits = v; has_prefilter_hits = true; }
         else if (f == "--matrix" && ai + 1 < argc) { af.matrix = argv[++ai]; af.on = true; }
         else if (f == "--gap-open" && ai + 1 < argc) { if (!parse_int("--gap-open", argv[++ai], &af.open)) return 2; af.has_open = af.on = true; }
         else if (f == "--gap-extend" && ai + 1 < argc) { if (!parse_int("--gap-extend", argv[++ai], &af.extend)) return 2; af.has_extend = true; }
@@ -541,7 +572,7 @@ int main(int argc, char** argv) {
         else if (f == "--record-b" && ai + 1 < argc) rec_b = strtoll(argv[++ai], nullptr, 10);
         else if (f == "--seed" && ai + 1 < argc) seed = (unsigned)strtoul(argv[++ai], nullptr, 10);
         else if (f == "--scores" && ai + 3 < argc) { sc.match = atoi(argv[++ai]); sc.mismatch = atoi(argv[++ai]); sc.gap = atoi(argv[++ai]); }
-        else { fprintf(stderr, "usage: smithW [<cols> <rows> | --fasta A.fa B.fa [--record-a I] [--record-b J] | --search QUERY.fa DB.fa [--record-a I] [--top K] [--all-queries [--min-score S | --prefilter S]] [--pairs FILE] [--matrix FILE] [--gap-open O] [--gap-extend E] [--align [--align-checkpoint]]] [--seed N] [--dump | --dump-labels] [--h64] [--no-backtrack] [--scores M X G] [--gpus N | --devices 0,1,..] [--p8]\n"); return 2; }
+        else { fprintf(stderr, "usage: smithW [<cols> <rows> | --fasta A.fa B.fa [--record-a I] [--record-b J] | --search QUERY.fa DB.fa [--record-a I] [--top K] [--all-queries [--min-score S] [--prefilter S | --prefilter-hits S]] [--pairs FILE] [--matrix FILE] [--gap-open O] [--gap-extend E] [--align [--align-checkpoint]]] [--seed N] [--dump | --dump-labels] [--h64] [--no-backtrack] [--scores M X G] [--gpus N | --devices 0,1,..] [--p8]\n"); return 2; }
     }
     if (npos == 1) { fprintf(stderr, "smithW: <cols> needs <rows>\n"); return 2; }
     if (align_ckpt && !(search_q && align)) { fprintf(stderr, "smithW: --align-checkpoint goes with --search --align\n"); return 2; }
@@ -554,6 +585,12 @@ int main(int argc, char** argv) {
         if (align && !af.on && (sc.match < -128 || sc.match > 127 || sc.mismatch < -128 || sc.mismatch > 127)) {
             fprintf(stderr, "smithW: --align on a linear search needs --scores M X within -128..127 (a table of signed bytes), got %d %d\n", sc.match, sc.mismatch);
             return 2;
+        }
+        if (has_prefilter_hits) {
+            if (!all_queries) { fprintf(stderr, "smithW: --prefilter-hits goes with --search --all-queries\n"); return 2; }
+            if (has_prefilter) { fprintf(stderr, "smithW: --prefilter-hits does not go with --prefilter\n"); return 2; }
+            if (pairs_path) { fprintf(stderr, "smithW: --prefilter-hits does not go with --pairs\n"); return 2; }
+            if (prefilter_hits < 1) { fprintf(stderr, "smithW: --prefilter-hits S needs S >= 1, got %lld\n", prefilter_hits); return 2; }
         }
         if (has_prefilter) {
             if (!all_queries) { fprintf(stderr, "smithW: --prefilter goes with --search --all-queries\n"); return 2; }
@@ -584,11 +621,12 @@ int main(int argc, char** argv) {
                 fprintf(stderr, "smithW: --all-queries without --matrix needs --scores M X within -128..127 (a table of signed bytes), got %d %d\n", sc.match, sc.mismatch);
                 return 2;
             }
-            return search_all_main(search_q, search_db, top, min_score, sc, af, align, align_ckpt);
+            return search_all_main(search_q, search_db, top, min_score, sc, af, align, align_ckpt, prefilter_hits);
         }
         if (has_min_score) { fprintf(stderr, "smithW: --min-score goes with --search --all-queries\n"); return 2; }
         return search_main(search_q, rec_a, search_db, top, sc, af, align, align_ckpt);
     }
+    if (has_prefilter_hits) { fprintf(stderr, "smithW: --prefilter-hits goes with --search --all-queries\n"); return 2; }
     if (has_prefilter) { fprintf(stderr, "smithW: --prefilter goes with --search --all-queries\n"); return 2; }
     if (pairs_path) { fprintf(stderr, "smithW: --pairs goes with --search\n"); return 2; }
     if (all_queries) { fprintf(stderr, "smithW: --all-queries goes with --search\n"); return 2; }

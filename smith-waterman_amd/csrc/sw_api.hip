@@ -75,6 +75,10 @@ void sw_destroy(sw_ctx* c) {
     if (c->d_tres) (void)hipFree(c->d_tres);
     if (c->d_thist) (void)hipFree(c->d_thist);
     if (c->d_tstate) (void)hipFree(c->d_tstate);
+    if (c->d_tpkeys) (void)hipFree(c->d_tpkeys);
+    if (c->d_tppos) (void)hipFree(c->d_tppos);
+    if (c->d_tpseg) (void)hipFree(c->d_tpseg);
+    if (c->d_tplist) (void)hipFree(c->d_tplist);
     delete c;
 }
 
@@ -212,6 +216,8 @@ int64_t sw_get_option(sw_ctx* c, const char* name) {
     if (!strcmp(name, "search_results_mib")) return c->opt_search_results_mib;
     if (!strcmp(name, "last_search_top_chunks")) return c->last_search_top_chunks;
     if (!strcmp(name, "last_search_top_kernel")) return c->last_search_top_kernel;
+    if (!strcmp(name, "last_top_pairs_launches")) return c->last_top_pairs_launches;
+    if (!strcmp(name, "last_top_pairs_kernel")) return c->last_top_pairs_kernel;
     if (!strcmp(name, "search_pairs_chunk")) return c->opt_search_pairs_chunk;
     if (!strcmp(name, "last_search_pairs_groups")) return c->last_search_pairs_groups;
     if (!strcmp(name, "last_search_pairs_chunks")) return c->last_search_pairs_chunks;

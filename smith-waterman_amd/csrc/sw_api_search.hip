@@ -85,6 +85,15 @@ static constexpr Indexed<PrefilterKernel> kPrefilter[] = {
 };
 static_assert(std::size(kPrefilter) == swp::kPrefilterKernels && at_their_indices(kPrefilter));
 
+// the instantiations of the pair-list selection's sort (sw_top_pairs.hip), picked by swp::plan_top_pairs
+using TopPairsSortKernel = void (*)(swk::TopPairsParams);
+static constexpr Indexed<TopPairsSortKernel> kTopPairsSort[] = {
+    {swp::top_pairs_kernel_index(swp::kTopMax, false), swk::sw_top_pairs_sort<(int)swp::kTopMax, false>},
+    {swp::top_pairs_kernel_index(swp::kTopMax, true), swk::sw_top_pairs_sort<(int)swp::kTopMax, true>},
+    {swp::top_pairs_kernel_index(2 * swp::kTopMax, true), swk::sw_top_pairs_sort<2 * (int)swp::kTopMax, true>},
+};
+static_assert(std::size(kTopPairsSort) == swp::kTopPairsKernels && at_their_indices(kTopPairsSort));
+
 // occupancy of every instantiation of a table at 256 threads, asked once per context: the plans' columns per lane and grids depend on it
 template <typename K, size_t N>
 static int occupancy_once(const Indexed<K> (&tab)[N], int (&per_cu)[N], bool& known) {
@@ -304,6 +313,31 @@ static int grow_top_workspaces(sw_ctx* c, const swp::SearchTopPlan& plan, bool r
     if (int rc = grow_workspace((void**)&c->d_tstate, c->tstate_cap, plan.state_need, sizeof(swk::TopState), 0, stream, fresh)) return rc;
     if (rows)
         if (int rc = grow_workspace((void**)&c->d_tres, c->tres_cap, plan.results_need, sizeof(sw_result), 0, stream, fresh)) return rc;
+    return SW_OK;
+}
+
+// What sw_top_hits_pairs_device and sw_db_search_affine_top_prefiltered check alike, and the plan of the selection.
+static int plan_top_pairs_call(sw_ctx* c, const char* who, int64_t npairs, int64_t nqueries, int64_t ntargets, int64_t top, const void* d_hits,
+                               const void* d_nhits, swp::TopPairsPlan& plan) {
+    static_assert(SW_TOP_MAX == swp::kTopMax);
+    if (!d_hits || !d_nhits) { set_err("%s: NULL d_hits or d_nhits", who); return SW_EINVAL; }
+    swp::TopPairsJob tj;
+    tj.npairs = npairs; tj.nqueries = nqueries; tj.ntargets = ntargets; tj.top = top; tj.num_cus = c->num_cus;
+    plan = swp::plan_top_pairs(tj);
+    if (plan.refused) {
+        set_err("%s: %s (npairs = %lld, nqueries = %lld, ntargets = %lld, top = %lld, SW_TOP_MAX = %d)", who, plan.refused, (long long)npairs,
+                (long long)nqueries, (long long)ntargets, (long long)top, SW_TOP_MAX);
+        return SW_EINVAL;
+    }
+    return SW_OK;
+}
+
+// ... grown under the device's launch order
+static int grow_top_pairs_workspaces(sw_ctx* c, const swp::TopPairsPlan& plan, hipStream_t stream) {
+    bool fresh = false;
+    if (int rc = grow_workspace((void**)&c->d_tpkeys, c->tpkeys_cap, plan.keys_need, sizeof(unsigned long long), 0, stream, fresh)) return rc;
+    if (int rc = grow_workspace((void**)&c->d_tppos, c->tppos_cap, plan.pos_need, sizeof(unsigned int), 0, stream, fresh)) return rc;
+    if (int rc = grow_workspace((void**)&c->d_tpseg, c->tpseg_cap, plan.seg_need, sizeof(unsigned int), 0, stream, fresh)) return rc;
     return SW_OK;
 }
 
@@ -854,6 +888,85 @@ int sw_db_prefilter_ungapped(sw_ctx* c, const sw_db* db, const char* d_queries, 
     c->last_prefilter_groups = (int64_t)plan.group.size(); c->last_prefilter_launches = (int64_t)plan.launch.size();
     c->last_prefilter_packed_launches = plan.packed_launches;
     return SW_OK;
+}
+
+// The selection over a scored pair list (csrc/sw_top_pairs.hip).  The host checks the counts and plans from them alone; it reads
+// neither the list nor the results.  One memset zeroes the counts, then count, scan, scatter and sort follow each other in the stream;
+// an empty list takes the sort alone, which writes the empty rows.
+int sw_top_hits_pairs_device(sw_ctx* c, const sw_pair* d_pairs, const sw_result* d_results, int64_t npairs, int64_t nqueries, int64_t ntargets,
+                             int64_t top, int64_t min_score, sw_hit* d_hits, int64_t* d_nhits, void* stream_) {
+    const char* who = "sw_top_hits_pairs_device";
+    if (!c) { set_err("%s: NULL context", who); return SW_EINVAL; }
+    swp::TopPairsPlan plan;
+    if (int rc = plan_top_pairs_call(c, who, npairs, nqueries, ntargets, top, d_hits, d_nhits, plan)) return rc;
+    if (npairs > 0 && (!d_pairs || !d_results)) { set_err("%s: NULL d_pairs or d_results with %lld pairs", who, (long long)npairs); return SW_EINVAL; }
+    c->last_top_pairs_launches = 0; c->last_top_pairs_kernel = plan.kernel;
+    if (nqueries == 0) return SW_OK;
+    hipStream_t stream = (hipStream_t)stream_;
+    HIP_TRY(hipSetDevice(c->device));
+    DevOrder order(c, stream, false);
+    if (order.rc) return order.rc;
+    if (int rc = grow_top_pairs_workspaces(c, plan, stream)) return rc;
+    swk::TopPairsParams tp;
+    memset(&tp, 0, sizeof tp);
+    tp.pairs = d_pairs; tp.results = d_results; tp.npairs = npairs; tp.nqueries = nqueries; tp.ntargets = ntargets;
+    tp.slice = plan.slice; tp.tbits = plan.tbits; tp.top = top; tp.min_score = min_score; tp.T = (unsigned)plan.T;
+    tp.cnt = c->d_tpseg; tp.offs = c->d_tpseg + (nqueries + 1);
+    tp.keys = c->d_tpkeys; tp.pos = c->d_tppos;
+    tp.hits = d_hits; tp.nhits = d_nhits;
+    if (npairs > 0) {
+        HIP_TRY(hipMemsetAsync(tp.cnt, 0, (size_t)nqueries * sizeof(unsigned int), stream));
+        const dim3 grid((unsigned)plan.grid);
+        if (plan.lds) hipLaunchKernelGGL(swk::sw_top_pairs_count<true>, grid, dim3(256), 0, stream, tp);
+        else hipLaunchKernelGGL(swk::sw_top_pairs_count<false>, grid, dim3(256), 0, stream, tp);
+        HIP_TRY(hipGetLastError());
+        hipLaunchKernelGGL(swk::sw_top_pairs_scan, dim3(1), dim3(256), 0, stream, tp);
+        HIP_TRY(hipGetLastError());
+        if (plan.lds) hipLaunchKernelGGL(swk::sw_top_pairs_scatter<true>, grid, dim3(256), 0, stream, tp);
+        else hipLaunchKernelGGL(swk::sw_top_pairs_scatter<false>, grid, dim3(256), 0, stream, tp);
+        HIP_TRY(hipGetLastError());
+    }
+    hipLaunchKernelGGL(kTopPairsSort[plan.sort_kernel].k, dim3((unsigned)plan.sort_grid), dim3(1024), 0, stream, tp);
+    HIP_TRY(hipGetLastError());
+    c->last_top_pairs_launches = plan.launches;
+    return SW_OK;
+}
+
+// Filter, rescoring and selection in one call.  Everything is checked and every workspace has its size before the first launch; the
+// three stages then follow each other in the stream through their own entry points, the list and its results in the context's workspace.
+int sw_db_search_affine_top_prefiltered(sw_ctx* c, const sw_db* db, const char* d_queries, const int64_t* qoffsets, int64_t nqueries, const sw_affine* scoring,
+                                        int64_t prefilter_min_score, int64_t pairs_cap, int64_t top, int64_t min_score, sw_hit* d_hits, int64_t* d_nhits,
+                                        int64_t* d_npairs, void* stream_) {
+    const char* who = "sw_db_search_affine_top_prefiltered";
+    if (!c || !db || !d_queries || !qoffsets || !scoring) { set_err("%s: NULL pointer", who); return SW_EINVAL; }
+    if (db->device != c->device) { set_err("%s: the handle was created on device %d, the context runs on device %d", who, db->device, c->device); return SW_EINVAL; }
+    int64_t maxq = 0;
+    if (int rc = swh::check_search_multi(who, qoffsets, nqueries, db->longest, scoring, &maxq)) return rc;
+    if (prefilter_min_score < 1) { set_err("%s: prefilter_min_score = %lld, a pair passes from 1 on", who, (long long)prefilter_min_score); return SW_EINVAL; }
+    if (pairs_cap < 0) { set_err("%s: negative pairs_cap", who); return SW_EINVAL; }
+    if (!d_npairs) { set_err("%s: NULL d_npairs", who); return SW_EINVAL; }
+    swp::TopPairsPlan plan;
+    if (int rc = plan_top_pairs_call(c, who, pairs_cap, nqueries, db->ntargets, top, d_hits, d_nhits, plan)) return rc;
+    if (pairs_cap > swp::top_prefiltered_cap(c->opt_search_results_mib << 20)) {
+        set_err("%s: pairs_cap = %lld entries of %lld bytes do not fit search_results_mib = %lld (at most %lld entries)", who, (long long)pairs_cap,
+                (long long)swp::kTopPrefilteredEntryBytes, (long long)c->opt_search_results_mib, (long long)swp::top_prefiltered_cap(c->opt_search_results_mib << 20));
+        return SW_EINVAL;
+    }
+    hipStream_t stream = (hipStream_t)stream_;
+    HIP_TRY(hipSetDevice(c->device));
+    {
+        DevOrder order(c, stream, false);
+        if (order.rc) return order.rc;
+        bool fresh = false;
+        if (int rc = grow_workspace((void**)&c->d_tplist, c->tplist_cap, (size_t)pairs_cap, sizeof(sw_pair) + sizeof(sw_result), 0, stream, fresh)) return rc;
+        if (nqueries > 0)
+            if (int rc = grow_top_pairs_workspaces(c, plan, stream)) return rc;
+    }
+    sw_pair* d_pairs = pairs_cap > 0 ? (sw_pair*)c->d_tplist : nullptr;
+    sw_result* d_results = pairs_cap > 0 ? (sw_result*)(c->d_tplist + (size_t)pairs_cap * sizeof(sw_pair)) : nullptr;
+    if (int rc = sw_db_prefilter_ungapped(c, db, d_queries, qoffsets, nqueries, scoring->sub, prefilter_min_score, d_pairs, pairs_cap, d_npairs, nullptr, stream_)) return rc;
+    if (int rc = sw_db_search_affine_pairs(c, db, d_queries, qoffsets, nqueries, scoring, d_pairs, pairs_cap, d_results, stream_)) return rc;
+    return sw_top_hits_pairs_device(c, d_pairs, d_results, pairs_cap, nqueries, db->ntargets, top, min_score, d_hits, d_nhits, stream_);
 }
 
 }  // extern "C"

@@ -158,6 +158,13 @@ struct SW_HIDDEN sw_ctx {
     int64_t opt_search_results_mib = 1024;
     int64_t last_search_top_chunks = 0, last_search_top_kernel = 0;
     int top_hist_per_cu = 0;                                    // occupancy of sw_top_hist at 256 threads, queried at the first call
+    // the best entries per query of a pair list (sw_top_hits_pairs_device): the segments' keys and positions, the per-query counts and
+    // offsets; sw_db_search_affine_top_prefiltered keeps its list and the list's results (16 + 24 bytes per entry) in d_tplist
+    unsigned long long* d_tpkeys = nullptr; size_t tpkeys_cap = 0;
+    unsigned int* d_tppos = nullptr; size_t tppos_cap = 0;
+    unsigned int* d_tpseg = nullptr; size_t tpseg_cap = 0;
+    unsigned char* d_tplist = nullptr; size_t tplist_cap = 0;   // (entries)
+    int64_t last_top_pairs_launches = 0, last_top_pairs_kernel = 0;
     // ---- placement of the output matrices (sw_place.hip)
     int64_t opt_place_hold_gib = 0;     // sw_alloc_outputs: GiB a pair of small matrices may hold beside itself where no plain candidate is good (0: none)
     int64_t opt_place_budget_ms = 1500; // sw_alloc_outputs: time the search for a P in another class of the HBM may take

@@ -558,6 +558,38 @@ int sw_search_affine_multi_top_host(const char* queries, const int64_t* qoffsets
     return SW_OK;
 }
 
+// The CPU leg of sw_top_hits_pairs_device: the qualifying entries in a stable sort by (query, max_score modulo 2^24 descending, target) --
+// stable, so entries equal in all three stay in list order --, then per query the first `top` of them and the {-1, 0, 0} tail.
+int sw_top_hits_pairs_host(const sw_pair* pairs, const sw_result* results, int64_t npairs, int64_t nqueries, int64_t ntargets, int64_t top, int64_t min_score,
+                           sw_hit* hits, int64_t* nhits) {
+    const char* who = "sw_top_hits_pairs_host";
+    if (!hits || !nhits) { swh::set_err("%s: NULL hits or nhits", who); return SW_EINVAL; }
+    if (npairs < 0 || npairs >= (1ll << 31)) { swh::set_err("%s: npairs = %lld is negative or not below 2^31", who, (long long)npairs); return SW_EINVAL; }
+    if (npairs > 0 && (!pairs || !results)) { swh::set_err("%s: NULL pairs or results with %lld pairs", who, (long long)npairs); return SW_EINVAL; }
+    if (nqueries < 0) { swh::set_err("%s: negative query count", who); return SW_EINVAL; }
+    if (ntargets < 0 || ntargets >= (1ll << 31)) { swh::set_err("%s: ntargets = %lld is negative or not below 2^31", who, (long long)ntargets); return SW_EINVAL; }
+    if (top < 1 || top > SW_TOP_MAX) { swh::set_err("%s: top = %lld is out of range 1..%d", who, (long long)top, SW_TOP_MAX); return SW_EINVAL; }
+    std::vector<int64_t> order;
+    for (int64_t p = 0; p < npairs; ++p)
+        if ((uint64_t)pairs[p].query < (uint64_t)nqueries && (uint64_t)pairs[p].target < (uint64_t)ntargets && results[p].max_score >= min_score) order.push_back(p);
+    std::stable_sort(order.begin(), order.end(), [&](int64_t x, int64_t y) {
+        if (pairs[x].query != pairs[y].query) return pairs[x].query < pairs[y].query;
+        const int64_t sx = results[x].max_score & 0xFFFFFF, sy = results[y].max_score & 0xFFFFFF;
+        if (sx != sy) return sx > sy;
+        return pairs[x].target < pairs[y].target;
+    });
+    size_t at = 0;
+    for (int64_t q = 0; q < nqueries; ++q) {
+        int64_t n = 0;
+        for (; at < order.size() && pairs[order[at]].query == q; ++at, ++n)
+            if (n < top) hits[q * top + n] = sw_hit{pairs[order[at]].target, results[order[at]].max_pos, results[order[at]].max_score};
+        n = std::min(n, top);
+        for (int64_t i = n; i < top; ++i) hits[q * top + i] = sw_hit{-1, 0, 0};
+        nhits[q] = n;
+    }
+    return SW_OK;
+}
+
 // The CPU leg of sw_align_affine_device: the same recurrence with one direction byte per cell (bits 0-1: where H came from, 0 nothing
 // positive / 1 diagonal / 2 E / 3 F, compared in that order; bit 2: E[i][j] opened from H[i-1][j]; bit 3: F[i][j] opened from
 // H[i][j-1]; opening wins a tie), then the walk of the canonical alignment (include/swhip.h) from the arg-max.

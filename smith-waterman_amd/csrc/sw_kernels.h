@@ -251,6 +251,27 @@ __global__ void sw_top_scan(TopParams p);
 __global__ void sw_top_compact(TopParams p);
 __global__ void sw_top_sort(TopParams p);
 
+// sw_top_pairs.hip: the best `top` entries of every query of a scored pair list (swp::plan_top_pairs has the geometry)
+struct TopPairsParams {
+    const sw_pair* pairs; const sw_result* results;   // the list and its results, entry for entry; only read
+    int64_t npairs, nqueries, ntargets;
+    int64_t slice;                       // count, scatter: workgroup w reads the entries [w * slice, min(npairs, (w + 1) * slice))
+    int tbits;                           // key = score << tbits | (2^tbits - 1 - target)
+    int64_t top, min_score;
+    unsigned int T;                      // streaming sort: items kept between rounds, pow2ceil(top)
+    unsigned int* cnt;                   // per query: qualifying entries (count), then the next free slot of its segment (scan, scatter)
+    unsigned int* offs;                  // nqueries + 1: where the segment of a query starts
+    unsigned long long* keys; unsigned int* pos;   // the segments: key and list position of every qualifying entry
+    sw_hit* hits; int64_t* nhits;        // nqueries x top, nqueries
+};
+template <bool LDS>
+__global__ void sw_top_pairs_count(TopPairsParams p);
+__global__ void sw_top_pairs_scan(TopPairsParams p);
+template <bool LDS>
+__global__ void sw_top_pairs_scatter(TopPairsParams p);
+template <int ITEMS, bool STREAM>
+__global__ void sw_top_pairs_sort(TopPairsParams p);
+
 // sw_align_affine.hip: the alignment of chosen hits under affine scoring (direction fill + walk, one wave per hit)
 struct AlignAffineParams {
     const unsigned char* db;             // the targets back to back

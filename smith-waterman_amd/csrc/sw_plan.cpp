@@ -586,6 +586,32 @@ SearchTopPlan plan_search_top(const SearchTopJob& j) {
     return t;
 }
 
+TopPairsPlan plan_top_pairs(const TopPairsJob& j) {
+    TopPairsPlan t;
+    if (j.npairs < 0 || j.npairs >= (1ll << 31)) { t.refused = "npairs is negative or not below 2^31"; return t; }
+    if (j.nqueries < 0) { t.refused = "nqueries is negative"; return t; }
+    if (j.ntargets < 0 || j.ntargets >= (1ll << 31)) { t.refused = "ntargets is negative or not below 2^31"; return t; }
+    if (j.top < 1 || j.top > kTopMax) { t.refused = "top is out of range 1..SW_TOP_MAX"; return t; }
+    while ((1ll << t.tbits) < j.ntargets) ++t.tbits;
+    t.lds = j.nqueries <= kTopPairsLdsQueries;
+    // enough workgroups to fill the device four times over, none with less than kTopPairsMinSlice entries; slices in whole 256s
+    if (j.npairs > 0) {
+        const int64_t wgs = std::clamp<int64_t>((j.npairs + kTopPairsMinSlice - 1) / kTopPairsMinSlice, 1, 4ll * std::max(1, j.num_cus));
+        t.slice = ((j.npairs + wgs - 1) / wgs + 255) / 256 * 256;
+        t.grid = (j.npairs + t.slice - 1) / t.slice;
+    }
+    while (t.T < j.top) t.T <<= 1;
+    t.kernel = j.npairs > kTopMax ? 1 : 0;
+    t.items = t.kernel ? std::max<int64_t>(kTopMax, 2 * t.T) : kTopMax;
+    t.sort_kernel = top_pairs_kernel_index(t.items, t.kernel == 1);
+    t.sort_grid = std::min(j.nqueries, kTopPairsSortGrid);
+    t.launches = j.nqueries == 0 ? 0 : (j.npairs > 0 ? 4 : 1);   // an empty list: the sort alone writes the empty rows
+    t.keys_need = t.pos_need = (size_t)j.npairs;
+    t.seg_need = 2 * ((size_t)j.nqueries + 1);
+    t.segment_bytes = 12 * j.npairs;
+    return t;
+}
+
 // The direction fill carries the search kernel's state plus the packed bytes of a row; the thresholds of the search hold for the same
 // reasons (plan_search_affine).  A slot is a whole direction matrix of the longest hit, so that any hit runs in any slot; the waves
 // take hits from a counter, longest first, and a call with more hits than slots simply keeps its waves busy longer.

@@ -373,6 +373,50 @@ struct SearchTopPlan {
 
 SearchTopPlan plan_search_top(const SearchTopJob& job);
 
+// ---- the best `top` entries of every query of a scored PAIR LIST (sw_top_hits_pairs_device; sw_top_pairs.hip).  The list is neither
+// sorted nor grouped, so the selection first groups it: a count launch (qualifying entries per query), a one-workgroup scan (segment
+// offsets), a scatter launch (every qualifying entry's sort item -- the key above, 8 bytes, beside its list position, 4 bytes -- into
+// its query's segment), then one workgroup per query orders its segment by (key descending, position ascending) and writes the row.
+// Count and scatter: `grid` workgroups of 256 threads, workgroup w over the entries [w * slice, min(npairs, (w + 1) * slice)).  Up to
+// kTopPairsLdsQueries queries (`lds`) a workgroup counts its slice in an LDS histogram and touches global memory with one vector atomic
+// per (workgroup, query) that occurs in it -- a list has far more entries than queries, and one global atomic per entry on a few
+// addresses serialises; beyond that many queries the addresses are many and every entry takes its own atomic.
+// Sort: `items` sort items of LDS per workgroup.  Kernel 0 (npairs <= kTopMax: every segment fits) sorts a segment whole.  Kernel 1
+// streams a longer segment: the best T = pow2ceil(top) items so far stay in front, the next items - T entries of the segment are
+// loaded behind them, the whole is sorted and the first T kept.  items = max(kTopMax, 2 T): 4096 (48 KiB) up to top = 2048, 8192
+// (96 KiB) above, so a round takes in at least as many new entries as it keeps.
+constexpr int64_t kTopPairsLdsQueries = 8192;   // 32 KiB of LDS counters
+constexpr int64_t kTopPairsMinSlice = 4096;     // a workgroup of 256 threads takes at least 16 entries per thread
+constexpr int64_t kTopPairsSortGrid = 1 << 16;  // the sort's workgroups walk the queries in strides of at most this many
+constexpr int kTopPairsKernels = 3;
+constexpr int top_pairs_kernel_index(int64_t items, bool stream) { return stream ? (items > kTopMax ? 2 : 1) : 0; }
+
+struct TopPairsJob {
+    int64_t npairs = 0, nqueries = 0, ntargets = 0, top = 1;
+    int num_cus = 256;
+};
+
+struct TopPairsPlan {
+    const char* refused = nullptr;           // not NULL: the call is SW_EINVAL for this reason, nothing else of the plan is set
+    int tbits = 0;                           // bits of a key's target field: ceil(log2 ntargets)
+    bool lds = false;                        // count and scatter aggregate per workgroup in LDS
+    int64_t grid = 0, slice = 0;             // count and scatter: workgroups and the entries each one reads (0 workgroups: an empty list)
+    int kernel = 0;                          // 0: every segment is sorted whole, 1: the streaming form ("last_top_pairs_kernel")
+    int64_t T = 1, items = kTopMax;          // the sort: items kept between rounds, sort items of LDS
+    int sort_kernel = 0;                     // index of sw_top_pairs_sort<items, stream> (kTopPairsKernels)
+    int64_t sort_grid = 0;
+    int launches = 0;                        // kernel launches of the call ("last_top_pairs_launches")
+    size_t keys_need = 0, pos_need = 0;      // workspaces: keys (uint64) and positions (uint32) of the segments, npairs each ...
+    size_t seg_need = 0;                     // ... and per query a count / cursor and an offset (uint32): 2 * (nqueries + 1)
+    int64_t segment_bytes = 0;               // 12 * npairs: what the segments take (at most 16 bytes per entry)
+};
+
+TopPairsPlan plan_top_pairs(const TopPairsJob& job);
+
+// The workspace of sw_db_search_affine_top_prefiltered: list and results (16 + 24 bytes per entry) beside the segments above.
+constexpr int64_t kTopPrefilteredEntryBytes = 56;
+constexpr int64_t top_prefiltered_cap(int64_t budget_bytes) { return budget_bytes / kTopPrefilteredEntryBytes; }
+
 // ---- alignment of chosen hits under affine scoring (sw_align_affine_device): sw_align_affine_wave<C> for C = 4, 8, 16, its index in
 // kAlignAffine (sw_api_search.hip, which checks its order against it at compile time)
 constexpr int kAlignAffineKernels = 3;

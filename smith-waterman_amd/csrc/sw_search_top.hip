@@ -17,15 +17,12 @@
 // table once the ranks are known.  Scores are taken modulo 2^24 (the bound every search call enforces) so that no input can carry a key
 // out of its fields; a slot is checked against `top` before it is written.
 #include "sw_kernels.h"
+#include "sw_top_key.h"
 
 namespace swk {
 
 constexpr int kTopBins = 1 << swp::kTopDigitBits;
 static_assert(kTopBins % 256 == 0);
-
-__device__ __forceinline__ unsigned long long top_key(long long score, long long target, int tbits) {
-    return ((unsigned long long)(score & 0xFFFFFF) << tbits) | (((1ull << tbits) - 1) - (unsigned long long)target);
-}
 
 __global__ void __launch_bounds__(256) sw_top_hist(TopParams p) {
     __shared__ unsigned int h[kTopBins];
