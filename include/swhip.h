@@ -509,6 +509,71 @@ int  sw_db_search_affine_top_prefiltered(sw_ctx* ctx, const sw_db* db, const cha
                                          const sw_affine* scoring, int64_t prefilter_min_score, int64_t pairs_cap, int64_t top,
                                          int64_t min_score, sw_hit* d_hits, int64_t* d_nhits, int64_t* d_npairs, void* stream);
 
+/* Queries that are position-specific scoring matrices (PSSMs; csrc/sw_pssm.hip): one row of scores per query COLUMN in place of a letter
+ * scored through a table -- the query of a PSI-BLAST iteration, of a profile or domain library.  The three calls below are the twins of
+ * sw_db_search_affine, sw_db_search_affine_top and sw_db_align_affine_hits: the same handle, outputs, layouts, options, chunks, tiers and
+ * refusals, and the same kernels behind the query profiles; only the profiles are built from another source.
+ *   sw_pssm_scoring  letters    : HOST, the nletters target bytes a column has an entry for (1..256, no byte twice)
+ *                    other      : the score of a target byte that is not in `letters`, at every column; -128..smax
+ *                    smax       : 0..127; every entry above smax is TAKEN AS smax
+ *                    gap_open, gap_extend : as in sw_affine
+ *   d_pssm    : device, int8.  Column g is the nletters bytes at d_pssm + g * nletters; byte k of a column scores the target byte
+ *               letters[k].  No alignment is asked of d_pssm.
+ *   qoffsets  : HOST, as everywhere in the family, counted in COLUMNS: query q is the columns [qoffsets[q], qoffsets[q+1]);
+ *               qoffsets[0] >= 0 and may be positive.  A call reads no byte outside
+ *               [d_pssm + qoffsets[0] * nletters, d_pssm + qoffsets[nqueries] * nletters).
+ * The score of query column j (1-based inside its query, column g of d_pssm) against target byte x is
+ *   s(j, x) = min(entry, smax)  where x = letters[k], entry = d_pssm[g * nletters + k];   s(j, x) = other  for every other x.
+ * With s(j, t[i-1]) in place of s[q[j-1]][t[i-1]] the recurrence, the arg-max rule, the result layouts and the canonical alignment are the
+ * ones stated above for sw_search_affine_device and sw_align_affine_device.
+ * THE CLAMP.  The host never reads d_pssm, so it cannot bound the entries the way the table calls bound theirs; smax does it by
+ * construction.  The 24-bit bound is smax x min(longest query, longest target) < 2^24, and gap_open + gap_extend >= -2^24 as before.
+ * Compare sw_top_hits_device: there 0 <= max_score < 2^24 is a PRECONDITION the call cannot check on device data; here the same bound
+ * is ENFORCED, whatever bytes d_pssm holds, and a hit table of sw_db_search_pssm_top meets that precondition.  A caller whose entries
+ * all lie at or below smax loses nothing; smax = 127 clamps nothing.
+ * Asynchronous on `stream`, no host round trip; the host work of a call is O(nqueries) + O(nletters).  Every argument is checked before
+ * the first launch.  "last_search_multi_*", "last_search_top_*" and "last_align_hits_*" describe these calls as they describe the twins.
+ * SW_EINVAL: the argument errors of the twin; NULL d_pssm, scoring or letters; nletters outside 1..256; a byte twice in letters; smax
+ * outside 0..127; other outside -128..smax; the two bounds above.
+ *   sw_search_pssm_multi_host, sw_align_pssm_hits_host  the CPU legs: the same results in plain C++ from host memory (pssm: the host
+ *               copy of d_pssm, indexed by the same qoffsets), no GPU needed; every argument is checked before the first query runs.
+ *   sw_pssm_from_queries  the PSSM that reproduces sequence queries under a table, iteration 0 of an iterative search:
+ *               out[(qoffsets[q] - qoffsets[0] + j) * nletters + k] = sub->s[q[j]][letters[k]], q[j] = queries[qoffsets[q] + j].  `out`
+ *               holds (qoffsets[nqueries] - qoffsets[0]) * nletters bytes and starts at the FIRST query's first column: pass
+ *               d_pssm = (device copy of out) - qoffsets[0] * nletters, or offsets rebased to 0.  With every byte the targets use in
+ *               `letters`, other <= smax and smax >= the table's largest entry, the PSSM calls then equal the table calls bit for bit.
+ *   sw_read_pssm  the ASCII PSSM that PSI-BLAST writes (-out_ascii_pssm).  The header is the first line whose tokens are all single
+ *               letters; the letters are its tokens up to the first repeat (PSI-BLAST prints the alphabet twice: scores, then
+ *               percentages), and that repeat has to be of the FIRST letter -- any other is a letter listed twice.  Lines end with
+ *               LF or CRLF.  Every following line that starts with an integer is a column: position, residue letter, then nletters
+ *               integers; the rest of the line is ignored.  The first other line after a column ends the table.  Entries must fit
+ *               int8.  Two-call pattern as in sw_read_fasta_db: with pssm == NULL it reports *nletters, *ncols and the letters only;
+ *               otherwise pssm receives ncols * nletters bytes (cap at least that), column-major as d_pssm wants them.  letters_out
+ *               holds 256 bytes.  SW_EINVAL with a message for an unreadable or malformed file (no header, no column, a short
+ *               column, an entry that is no integer or does not fit int8) and for a cap too small; nothing is read or written out
+ *               of bounds whatever the file holds. */
+typedef struct {
+    const char* letters; int32_t nletters;   /* HOST: the target bytes the PSSM has a row entry for, 1..256, no byte twice */
+    int32_t other;                           /* score of a target byte not in `letters`, at every column; -128..smax */
+    int32_t smax;                            /* 0..127: every entry above smax is TAKEN AS smax (see above) */
+    int32_t gap_open, gap_extend;            /* as in sw_affine */
+} sw_pssm_scoring;
+int  sw_db_search_pssm(sw_ctx* ctx, const sw_db* db, const int8_t* d_pssm, const int64_t* qoffsets, int64_t nqueries,
+                       const sw_pssm_scoring* scoring, sw_result* d_results, void* stream);
+int  sw_db_search_pssm_top(sw_ctx* ctx, const sw_db* db, const int8_t* d_pssm, const int64_t* qoffsets, int64_t nqueries,
+                           const sw_pssm_scoring* scoring, int64_t top, int64_t min_score, sw_hit* d_hits, int64_t* d_nhits, void* stream);
+int  sw_db_align_pssm_hits(sw_ctx* ctx, const sw_db* db, const int8_t* d_pssm, const int64_t* qoffsets, int64_t nqueries,
+                           const sw_pssm_scoring* scoring, const sw_hit* d_hits, const int64_t* d_nhits, int64_t top,
+                           sw_alignment* d_aln, char* d_ops, int64_t ops_cap, void* stream);
+int  sw_search_pssm_multi_host(const int8_t* pssm, const int64_t* qoffsets, int64_t nqueries, const char* db, const int64_t* offsets,
+                               int64_t ntargets, const sw_pssm_scoring* scoring, sw_result* results);
+int  sw_align_pssm_hits_host(const int8_t* pssm, const int64_t* qoffsets, int64_t nqueries, const char* db, const int64_t* offsets,
+                             int64_t ntargets, const sw_pssm_scoring* scoring, const sw_hit* hits, const int64_t* nhits, int64_t top,
+                             sw_alignment* aln, char* ops, int64_t ops_cap);
+int  sw_pssm_from_queries(const char* queries, const int64_t* qoffsets, int64_t nqueries, const sw_submat* sub, const char* letters,
+                          int32_t nletters, int8_t* out);
+int  sw_read_pssm(const char* path, char* letters_out, int32_t* nletters, int8_t* pssm, int64_t cap, int64_t* ncols);
+
 /* Tables.  sw_submat_match: s[x][y] = x == y ? match : mismatch (matchMissmatchScore, serial_smithW.c:251-256; both must fit int8:
  * the builder returns nothing, so it clamps them to -128..127 -- a caller that takes them from a user checks the range first, as
  * smithW and the Python wrapper do, which refuse such scores).  sw_submat_from_letters: `scores` is n x n, row = query letter, over the n bytes of

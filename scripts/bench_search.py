@@ -45,6 +45,11 @@
   about 20 000 entries, the streaming sort.  Checked on the device: the tables of (ii) and (iii) are equal, both equal the top 10 of
   the full table masked by U >= S (torch, from a d_scores run), the count is at most the cap; the run fails if a check fails or if
   (iii) is not faster than (i).  The recall -- the share of (i)'s hits that (iii) found -- is recorded, not gated
+  --pssm: data set (a) only, 64 queries of --qlen through one handle: sw_db_search_pssm on the matrices sw_pssm_from_queries derives from
+  the queries beside sw_db_search_affine on the queries, in one process, ALTERNATING, at least five repeats each, torch events around
+  whole calls, medians and ranges; the results are compared on the device.  The margin is the range of the sw_db_search_affine repeats
+  (pssm_within_margin is recorded, not gated).  *_profile_call_ms: the same two calls against a handle of ONE one-letter target -- the
+  uploads, the profile launch of all 64 queries and a sweep of 64 cells: what the two calls do NOT share, measured without the sweeps
 GCUPS = query letters x target letters / time of the call (torch events, median of --reps after --warmup)."""
 import argparse
 import importlib
@@ -93,6 +98,7 @@ def main():
     ap.add_argument("--pairs", action="store_true", help="data set (a) only: a pair list of 1 %% and of all of the cross product of 64 queries beside the full search")
     ap.add_argument("--prefilter", action="store_true", help="data set (a) only: the ungapped pre-filter of 64 queries, alone and chained into the pair-list search, beside the full search")
     ap.add_argument("--prefiltered-top", action="store_true", help="data set (a) only: the top 10 of 64 queries by the full search and by pre-filter, rescoring and selection from the pair list")
+    ap.add_argument("--pssm", action="store_true", help="data set (a) only: 64 PSSM queries derived from 64 sequence queries beside those, alternating")
     ap.add_argument("--top", action="store_true", help="data set (a) only: the best 100 targets of 64 queries by the full table and by the selection on the device")
     args = ap.parse_args()
     rng = np.random.default_rng(2026)
@@ -541,6 +547,52 @@ def main():
         out[f"{P}_low_longest_segment"] = int(torch.bincount(low[0][:, 0], minlength=nq).max().item())
         db.close()
 
+    def pssm_leg(packed, offs, nq=64):
+        d_db = torch.from_numpy(packed.copy()).to(dev)
+        db = eng.prepare_db(d_db, offs)
+        tiny = eng.prepare_db(d_db, offs[:1] + np.array([0, 1]))             # one target of one letter: a call is its uploads and its profile launch
+        nt = len(offs) - 1
+        qoffs = np.arange(nq + 1, dtype=np.int64) * args.qlen
+        queries = rng.choice(PROTEIN, int(qoffs[-1])).astype(np.uint8)
+        d_q = torch.from_numpy(queries).to(dev)
+        m, moffs = swamd.pssm_from_queries((queries, qoffs), sub, letters)   # iteration 0: the matrices that reproduce the queries
+        d_m = torch.from_numpy(m.reshape(-1).copy()).to(dev)
+        scoring, pscoring = (sub, -11, -1), (letters, -4, 127, -11, -1)
+        res_a = torch.zeros(nq * nt * 3, dtype=torch.int64, device=dev)
+        res_p = torch.zeros(nq * nt * 3, dtype=torch.int64, device=dev)
+        one = torch.zeros(nq * 3, dtype=torch.int64, device=dev)
+        legs = {"affine": lambda: db.search_affine_device(d_q, qoffs, scoring, out=res_a), "pssm": lambda: db.search_pssm_device(d_m, moffs, pscoring, out=res_p),
+                "affine_profile_call": lambda: tiny.search_affine_device(d_q, qoffs, scoring, out=one),
+                "pssm_profile_call": lambda: tiny.search_pssm_device(d_m, moffs, pscoring, out=one)}
+        reps = max(5, args.reps)
+        P = "pssm"
+        out[f"{P}_queries"], out[f"{P}_qlen"], out[f"{P}_targets"], out[f"{P}_letters"], out[f"{P}_reps"] = nq, args.qlen, nt, len(letters), reps
+        for pair in (("affine", "pssm"), ("affine_profile_call", "pssm_profile_call")):
+            ms = {k: [] for k in pair}
+            for _ in range(max(1, args.warmup)):
+                for k in pair:
+                    legs[k]()
+            torch.cuda.synchronize()
+            for _ in range(reps):                                            # alternating: a drift of the device shows in both alike
+                for k in pair:
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    e0.record()
+                    legs[k]()
+                    e1.record()
+                    torch.cuda.synchronize()
+                    ms[k].append(e0.elapsed_time(e1))
+            for k in pair:
+                out[f"{P}_{k}_ms"], out[f"{P}_{k}_range_ms"] = round(float(np.median(ms[k])), 4), [round(min(ms[k]), 4), round(max(ms[k]), 4)]
+        out[f"{P}_identical"] = bool(torch.equal(res_a, res_p))
+        out[f"{P}_launches"] = eng.get_option("last_search_multi_launches")
+        # the expectation: the same sweeps behind a profile that is 257 x 512 bytes per query -- equal within the affine call's own spread
+        margin = out[f"{P}_affine_range_ms"][1] - out[f"{P}_affine_range_ms"][0]
+        out[f"{P}_margin_ms"] = round(margin, 4)
+        out[f"{P}_minus_affine_ms"] = round(out[f"{P}_pssm_ms"] - out[f"{P}_affine_ms"], 4)
+        out[f"{P}_within_margin"] = bool(abs(out[f"{P}_minus_affine_ms"]) <= margin)
+        db.close()
+        tiny.close()
+
     def align_ckpt_leg(q, packed, offs, nq=64):
         d_db = torch.from_numpy(packed.copy()).to(dev)
         db = eng.prepare_db(d_db, offs)
@@ -612,7 +664,9 @@ def main():
     out["a_letters"] = int(offs[-1])
     out["a_len_median"] = int(np.median(lens))
     out["a_len_max"] = int(lens.max())
-    if args.multi or args.top or args.align_hits or args.pairs or args.prefilter or args.prefiltered_top:
+    if args.multi or args.top or args.align_hits or args.pairs or args.prefilter or args.prefiltered_top or args.pssm:
+        if args.pssm:
+            pssm_leg(packed, offs)
         if args.pairs:
             pairs_leg(packed, offs)
         if args.prefilter:
@@ -629,6 +683,8 @@ def main():
             top_leg(packed, offs)
         eng.close()
         print(json.dumps(out))
+        if args.pssm and not out["pssm_identical"]:
+            sys.exit("bench_search.py --pssm: pssm_identical is false")
         if args.pairs:   # the required conditions of the pair-list call: a line that misses one is printed, and the run fails
             missed = [k for k in ("pairs_sparse_identical", "pairs_list_identical", "pairs_sparse_faster_than_full") if not out[k]]
             if missed:

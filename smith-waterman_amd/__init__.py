@@ -46,6 +46,11 @@ class _Affine(ctypes.Structure):   # sw_affine: the table by pointer
     _fields_ = [("sub", ctypes.c_void_p), ("gap_open", ctypes.c_int32), ("gap_extend", ctypes.c_int32)]
 
 
+class _PssmScoring(ctypes.Structure):   # sw_pssm_scoring: the letters by pointer
+    _fields_ = [("letters", ctypes.c_void_p), ("nletters", ctypes.c_int32), ("other", ctypes.c_int32), ("smax", ctypes.c_int32),
+                ("gap_open", ctypes.c_int32), ("gap_extend", ctypes.c_int32)]
+
+
 # every symbol include/swhip.h declares: (restype, argtypes)
 _vp, _i64, _i32, _u32, _sz = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_uint32, ctypes.c_size_t
 ABI = {
@@ -82,6 +87,13 @@ ABI = {
     "sw_db_search_affine_top_prefiltered": (_i32, [_vp, _vp, _vp, _vp, _i64, ctypes.POINTER(_Affine), _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp]),
     "sw_db_align_affine_hits": (_i32, [_vp, _vp, _vp, _vp, _i64, ctypes.POINTER(_Affine), _vp, _vp, _i64, _vp, _vp, _i64, _vp]),
     "sw_align_affine_hits_host": (_i32, [_vp, _vp, _i64, _vp, _vp, _i64, ctypes.POINTER(_Affine), _vp, _vp, _i64, _vp, _vp, _i64]),
+    "sw_db_search_pssm": (_i32, [_vp, _vp, _vp, _vp, _i64, ctypes.POINTER(_PssmScoring), _vp, _vp]),
+    "sw_db_search_pssm_top": (_i32, [_vp, _vp, _vp, _vp, _i64, ctypes.POINTER(_PssmScoring), _i64, _i64, _vp, _vp, _vp]),
+    "sw_db_align_pssm_hits": (_i32, [_vp, _vp, _vp, _vp, _i64, ctypes.POINTER(_PssmScoring), _vp, _vp, _i64, _vp, _vp, _i64, _vp]),
+    "sw_search_pssm_multi_host": (_i32, [_vp, _vp, _i64, _vp, _vp, _i64, ctypes.POINTER(_PssmScoring), _vp]),
+    "sw_align_pssm_hits_host": (_i32, [_vp, _vp, _i64, _vp, _vp, _i64, ctypes.POINTER(_PssmScoring), _vp, _vp, _i64, _vp, _vp, _i64]),
+    "sw_pssm_from_queries": (_i32, [_vp, _vp, _i64, _vp, _vp, _i32, _vp]),
+    "sw_read_pssm": (_i32, [ctypes.c_char_p, _vp, ctypes.POINTER(ctypes.c_int32), _vp, _i64, ctypes.POINTER(_i64)]),
     "sw_align_affine_device": (_i32, [_vp, _vp, _i64, _vp, _vp, _i64, _vp, _i64, ctypes.POINTER(_Affine), _vp, _vp, _i64, _vp]),
     "sw_align_affine_host": (_i32, [_vp, _i64, _vp, _vp, _i64, _vp, _i64, ctypes.POINTER(_Affine), _vp, _vp, _i64]),
     "sw_submat_match": (None, [_i32, _i32, _vp]),
@@ -416,6 +428,86 @@ def align_affine_hits_host(queries, targets, scoring, hits, nhits=None):
     return aln.reshape(nq, top, 7), _ops_rows(aln, ops, cap, nq, top)
 
 
+def _pssm_scoring(scoring):
+    """(the letters kept alive, the sw_pssm_scoring that points at them) from (letters, other, smax, gap_open, gap_extend)."""
+    letters, other, smax, gap_open, gap_extend = scoring
+    lt = np.ascontiguousarray(_as_seq(letters))
+    buf = np.concatenate([lt, np.zeros(1, np.uint8)])   # (never an empty buffer: the library, not a NULL pointer, refuses nletters = 0)
+    return buf, _PssmScoring(buf.ctypes.data, len(lt), int(other), int(smax), int(gap_open), int(gap_extend))
+
+
+def _pack_pssm(pssm, nletters: int):
+    """A list of per-query (columns, nletters) int8 matrices, or a ((total columns, nletters) int8, int64 offsets) pair whose offsets
+    count columns of the array -> (int8 array of total columns x nletters, int64 offsets)."""
+    if isinstance(pssm, tuple) and len(pssm) == 2:
+        m = np.ascontiguousarray(pssm[0], np.int8).reshape(-1, nletters)
+        return m, np.ascontiguousarray(pssm[1], np.int64).reshape(-1)
+    ms = [np.ascontiguousarray(m, np.int8).reshape(-1, nletters) for m in pssm]
+    offs = np.zeros(len(ms) + 1, np.int64)
+    if ms:
+        offs[1:] = np.cumsum([len(m) for m in ms])
+    return (np.concatenate(ms) if ms else np.zeros((0, nletters), np.int8)), offs
+
+
+def pssm_from_queries(queries, submat, letters):
+    """sw_pssm_from_queries: the PSSMs that reproduce sequence queries under a table -- column j of query q is the table's row of
+    letter q[j] at `letters`.  Returns (pssm (total columns, nletters) int8, offsets int64 starting at 0), what the *_pssm calls take."""
+    qpacked, qoffs = _pack_targets(queries)
+    lt = np.ascontiguousarray(_as_seq(letters))
+    sub = _submat(submat)
+    n = int(qoffs[-1] - qoffs[0])
+    out = np.zeros((max(1, n), max(1, len(lt))), np.int8)
+    qs = qpacked if len(qpacked) else np.zeros(1, np.uint8)
+    _check(lib().sw_pssm_from_queries(qs.ctypes.data, qoffs.ctypes.data, len(qoffs) - 1, sub.ctypes.data, lt.ctypes.data if len(lt) else None, len(lt),
+                                      out.ctypes.data))
+    return out[:n], qoffs - qoffs[0]
+
+
+def read_pssm(path: str):
+    """sw_read_pssm: the ASCII PSSM that PSI-BLAST writes.  Returns (letters uint8 (nletters,), pssm int8 (columns, nletters))."""
+    letters = np.zeros(256, np.uint8)
+    nl, ncols = ctypes.c_int32(), _i64()
+    _check(lib().sw_read_pssm(os.fsencode(path), letters.ctypes.data, ctypes.byref(nl), None, 0, ctypes.byref(ncols)))
+    m = np.zeros((ncols.value, nl.value), np.int8)
+    _check(lib().sw_read_pssm(os.fsencode(path), letters.ctypes.data, ctypes.byref(nl), m.ctypes.data, m.size, ctypes.byref(ncols)))
+    return letters[:nl.value].copy(), m
+
+
+def search_pssm_multi_host(pssm, targets, scoring):
+    """sw_search_pssm_multi_host: every PSSM against every target in plain C++ on the host (no GPU).  Arguments and result as
+    Database.search_pssm."""
+    lt, sc = _pssm_scoring(scoring)
+    m, qoffs = _pack_pssm(pssm, max(1, sc.nletters))
+    packed, offs = _pack_targets(targets)
+    nq, ntargets = len(qoffs) - 1, len(offs) - 1
+    mm = m if m.size else np.zeros((1, 1), np.int8)
+    db = packed if len(packed) else np.zeros(1, np.uint8)
+    res = np.zeros((max(1, nq * ntargets), 3), np.int64)
+    _check(lib().sw_search_pssm_multi_host(mm.ctypes.data, qoffs.ctypes.data, nq, db.ctypes.data, offs.ctypes.data, ntargets, ctypes.byref(sc),
+                                           res.ctypes.data))
+    return res[:nq * ntargets].reshape(nq, ntargets, 3)
+
+
+def align_pssm_hits_host(pssm, targets, scoring, hits, nhits=None):
+    """sw_align_pssm_hits_host: the alignments of a hit table under PSSM queries in plain C++ on the host (no GPU).  Arguments and
+    results as Database.align_pssm_hits."""
+    lt, sc = _pssm_scoring(scoring)
+    m, qoffs = _pack_pssm(pssm, max(1, sc.nletters))
+    packed, offs = _pack_targets(targets)
+    nq = len(qoffs) - 1
+    hits, nhits = _hit_table(hits, nhits, nq)
+    top = hits.shape[1]
+    mm = m if m.size else np.zeros((1, 1), np.int8)
+    db = packed if len(packed) else np.zeros(1, np.uint8)
+    cap = max(1, int(np.diff(qoffs).max(initial=0)) + int(np.diff(offs).max(initial=0)))
+    aln = np.zeros((max(1, nq * top), 7), np.int64)
+    ops = np.zeros((max(1, nq * top), cap), np.uint8)
+    _check(lib().sw_align_pssm_hits_host(mm.ctypes.data, qoffs.ctypes.data, nq, db.ctypes.data, offs.ctypes.data, len(offs) - 1, ctypes.byref(sc),
+                                         hits.ctypes.data, nhits.ctypes.data if nhits is not None else None, top, aln.ctypes.data, ops.ctypes.data, cap))
+    aln = aln[:nq * top]
+    return aln.reshape(nq, top, 7), _ops_rows(aln, ops, cap, nq, top)
+
+
 def _ops_rows(aln, ops, cap, nq: int, top: int):
     flat = _ops_list(aln.reshape(-1, 7), ops, cap)
     return [flat[q * top:(q + 1) * top] for q in range(nq)]
@@ -423,7 +515,8 @@ def _ops_rows(aln, ops, cap, nq: int, top: int):
 
 def format_alignment(query, target, aln_row, ops):
     """The three display lines of an alignment (an sw_alignment row and its ops): the query with '-' where the target has letters
-    of its own, a midline ('|' under equal letters, a space otherwise), the target with '-'."""
+    of its own, a midline ('|' under equal letters, a space otherwise), the target with '-'.  For a PSSM query pass its consensus --
+    any string with one letter per column -- as `query`."""
     q, t = _as_seq(query), _as_seq(target)
     j, i = int(aln_row[2]), int(aln_row[3])
     top, mid, bot = [], [], []
@@ -585,6 +678,11 @@ class Database:
         """sw_db_search_affine on device-resident queries (a torch uint8 tensor), host int64 offsets and a host table; asynchronous on
         torch's current stream.  Returns the (nqueries, ntargets, 3) int64 result tensor (a view of `out`, a flat int64 tensor of at
         least nqueries * ntargets * 3 elements, if given)."""
+        sub, sc = _affine(*scoring)
+        return self._search_call(lib().sw_db_search_affine, d_queries, qoffsets, sc, out)
+
+    def _search_call(self, fn, d_source, qoffsets, sc, out):
+        """sw_db_search_affine / sw_db_search_pssm: the queries' letters or their matrices in d_source, the scoring object that goes with them."""
         eng = self.engine
         t = eng.torch
         qoffs = np.ascontiguousarray(qoffsets, np.int64).reshape(-1)
@@ -594,9 +692,31 @@ class Database:
         res = out if out is not None else t.zeros(max(3, n), dtype=t.int64, device=f"cuda:{eng.device}")
         if res.dtype != t.int64 or not res.is_contiguous() or res.numel() < n:
             raise ValueError(f"out must be a contiguous int64 tensor of at least {n} elements ({nq} queries x {self.ntargets} targets x 3)")
-        sub, sc = _affine(*scoring)
-        _check(lib().sw_db_search_affine(eng._h, self._h, d_queries.data_ptr(), qoffs.ctypes.data, nq, ctypes.byref(sc), res.data_ptr(), eng._stream()))
+        _check(fn(eng._h, self._h, d_source.data_ptr(), qoffs.ctypes.data, nq, ctypes.byref(sc), res.data_ptr(), eng._stream()))
         return res[:n].view(nq, self.ntargets, 3)
+
+    def _pssm_to_device(self, pssm, nletters: int):
+        """Host PSSMs (see _pack_pssm) -> (flat int8 device tensor, int64 offsets in columns)."""
+        eng = self.engine
+        t = eng.torch
+        m, qoffs = _pack_pssm(pssm, max(1, nletters))
+        return t.from_numpy(m.reshape(-1).copy() if m.size else np.zeros(1, np.int8)).to(f"cuda:{eng.device}"), qoffs
+
+    def search_pssm(self, pssm, scoring):
+        """Every PSSM query against every target (sw_db_search_pssm).  pssm: a list of per-query (columns, nletters) int8 matrices, or a
+        ((total columns, nletters) int8, int64 column offsets) pair; scoring = (letters, other, smax, gap_open, gap_extend): entry k of a
+        column scores the target byte letters[k], every other byte scores `other`, entries above smax count as smax.  Returns the
+        (nqueries, ntargets, 3) int64 numpy array of (max_pos, max_score, path_len = 0), as search_affine does."""
+        d_m, qoffs = self._pssm_to_device(pssm, len(_as_seq(scoring[0])))
+        res = self.search_pssm_device(d_m, qoffs, scoring)
+        self.engine.synchronize()
+        return res.cpu().numpy()
+
+    def search_pssm_device(self, d_pssm, qoffsets, scoring, out=None):
+        """sw_db_search_pssm on a device-resident matrix (a torch int8 tensor: column g is the nletters bytes at g * nletters) and host
+        int64 column offsets; asynchronous on torch's current stream.  Result and `out` as for search_affine_device."""
+        lt, sc = _pssm_scoring(scoring)
+        return self._search_call(lib().sw_db_search_pssm, d_pssm, qoffsets, sc, out)
 
     def search_affine_pairs(self, queries, scoring, pairs):
         """The scores of a list of (query, target) pairs (sw_db_search_affine_pairs): queries and scoring as for search_affine; pairs an
@@ -698,16 +818,34 @@ class Database:
         """sw_db_search_affine_top on device-resident queries; asynchronous on torch's current stream.  Returns torch (hits (nqueries,
         top, 3), nhits (nqueries,)), views of `out` = (flat int64 tensor of at least nqueries * top * 3 elements, int64 tensor of at
         least nqueries elements) if given."""
+        sub, sc = _affine(*scoring)
+        return self._search_top_call(lib().sw_db_search_affine_top, d_queries, qoffsets, sc, top, min_score, out)
+
+    def _search_top_call(self, fn, d_source, qoffsets, sc, top: int, min_score: int, out):
+        """sw_db_search_affine_top / sw_db_search_pssm_top (see _search_call)."""
         eng = self.engine
         qoffs = np.ascontiguousarray(qoffsets, np.int64).reshape(-1)
         if len(qoffs) == 0:
             qoffs = np.zeros(1, np.int64)
         nq = len(qoffs) - 1
         hits, nhits = eng._top_out(nq, top, out)
-        sub, sc = _affine(*scoring)
-        _check(lib().sw_db_search_affine_top(eng._h, self._h, d_queries.data_ptr(), qoffs.ctypes.data, nq, ctypes.byref(sc), int(top), int(min_score),
-                                             hits.data_ptr(), nhits.data_ptr(), eng._stream()))
+        _check(fn(eng._h, self._h, d_source.data_ptr(), qoffs.ctypes.data, nq, ctypes.byref(sc), int(top), int(min_score), hits.data_ptr(), nhits.data_ptr(),
+                  eng._stream()))
         return eng._top_views(hits, nhits, nq, top)
+
+    def search_pssm_top(self, pssm, scoring, top: int, min_score: int = 0):
+        """The best `top` targets of every PSSM query (sw_db_search_pssm_top): pssm and scoring as for search_pssm, results as for
+        search_affine_top."""
+        d_m, qoffs = self._pssm_to_device(pssm, len(_as_seq(scoring[0])))
+        hits, nhits = self.search_pssm_top_device(d_m, qoffs, scoring, top, min_score)
+        self.engine.synchronize()
+        return hits.cpu().numpy(), nhits.cpu().numpy()
+
+    def search_pssm_top_device(self, d_pssm, qoffsets, scoring, top: int, min_score: int = 0, out=None):
+        """sw_db_search_pssm_top on a device-resident matrix; asynchronous on torch's current stream.  Results and `out` as for
+        search_affine_top_device."""
+        lt, sc = _pssm_scoring(scoring)
+        return self._search_top_call(lib().sw_db_search_pssm_top, d_pssm, qoffsets, sc, top, min_score, out)
 
     def search_affine_top_prefiltered(self, queries, scoring, prefilter_min_score: int, top: int, min_score: int = 0, cap=None):
         """Filter, rescoring and selection in one call on host queries (sw_db_search_affine_top_prefiltered): the table of
@@ -752,22 +890,38 @@ class Database:
         (nqueries,) counts or None for whole rows.  Returns (aln, ops): aln the (nqueries, top, 7) int64 numpy array of (max_pos,
         max_score, q_begin, t_begin, q_end, t_end, nops), all zeros for unused entries and targets outside the database; ops a list per
         query of `top` bytes objects over b"MID".  checkpoint: the option "align_checkpoint" (0, 1, 2) for this call alone."""
+        t = self.engine.torch
+        qpacked, qoffs = _pack_targets(queries)
+        d_q = t.from_numpy(qpacked.copy() if len(qpacked) else np.zeros(1, np.uint8)).to(f"cuda:{self.engine.device}")
+        return self._align_hits_from_host(self.align_affine_hits_device, d_q, qoffs, scoring, hits, nhits, checkpoint)
+
+    def _align_hits_from_host(self, device_call, d_source, qoffs, scoring, hits, nhits, checkpoint):
+        """align_affine_hits / align_pssm_hits behind the upload of their queries: the host hit table to the device, the call, the
+        results back."""
         eng = self.engine
         t = eng.torch
         dev = f"cuda:{eng.device}"
-        qpacked, qoffs = _pack_targets(queries)
         nq = len(qoffs) - 1
         hits, nhits = _hit_table(hits, nhits, nq)
         top = hits.shape[1]
-        d_q = t.from_numpy(qpacked.copy() if len(qpacked) else np.zeros(1, np.uint8)).to(dev)
         d_hits = t.from_numpy(hits.reshape(-1).copy() if hits.size else np.zeros(3, np.int64)).to(dev)
         d_nhits = t.from_numpy(nhits.copy()).to(dev) if nhits is not None and len(nhits) else None
         cap = max(1, int(np.diff(qoffs).max(initial=0)) + self.info()["longest"])
-        aln, ops = self.align_affine_hits_device(d_q, qoffs, scoring, d_hits.view(nq, top, 3) if hits.size else d_hits, d_nhits, ops_cap=cap, top=top,
-                                                 checkpoint=checkpoint)
+        aln, ops = device_call(d_source, qoffs, scoring, d_hits.view(nq, top, 3) if hits.size else d_hits, d_nhits, ops_cap=cap, top=top, checkpoint=checkpoint)
         eng.synchronize()
         aln = aln.cpu().numpy()
         return aln, _ops_rows(aln, ops.cpu().numpy().reshape(-1, cap), cap, nq, top)
+
+    def align_pssm_hits(self, pssm, scoring, hits, nhits=None, checkpoint=None):
+        """The alignments of a hit table under PSSM queries (sw_db_align_pssm_hits): pssm and scoring as for search_pssm, everything
+        else as for align_affine_hits."""
+        d_m, qoffs = self._pssm_to_device(pssm, len(_as_seq(scoring[0])))
+        return self._align_hits_from_host(self.align_pssm_hits_device, d_m, qoffs, scoring, hits, nhits, checkpoint)
+
+    def align_pssm_hits_device(self, d_pssm, qoffsets, scoring, hits, nhits, ops_cap: int = 0, out=None, top=None, checkpoint=None):
+        """sw_db_align_pssm_hits on a device-resident matrix and a device hit table; everything else as for align_affine_hits_device."""
+        lt, sc = _pssm_scoring(scoring)
+        return self._align_hits_call(lib().sw_db_align_pssm_hits, d_pssm, qoffsets, sc, hits, nhits, ops_cap, out, top, checkpoint)
 
     def align_affine_hits_device(self, d_queries, qoffsets, scoring, hits, nhits, ops_cap: int = 0, out=None, top=None, checkpoint=None):
         """sw_db_align_affine_hits on device-resident queries and a device hit table -- the (nqueries, top, 3) int64 tensor and the
@@ -775,6 +929,11 @@ class Database:
         only where the table's shape does not tell it); asynchronous on torch's current stream, nothing comes to the host.  Returns
         (aln, ops): the (nqueries, top, 7) int64 tensor and the (nqueries, top, ops_cap) uint8 tensor (None with ops_cap = 0:
         coordinates only); out = (aln, ops) reuses given tensors.  checkpoint: the option "align_checkpoint" for this call alone."""
+        sub, sc = _affine(*scoring)
+        return self._align_hits_call(lib().sw_db_align_affine_hits, d_queries, qoffsets, sc, hits, nhits, ops_cap, out, top, checkpoint)
+
+    def _align_hits_call(self, fn, d_source, qoffsets, sc, hits, nhits, ops_cap, out, top, checkpoint):
+        """sw_db_align_affine_hits / sw_db_align_pssm_hits (see _search_call)."""
         eng = self.engine
         t = eng.torch
         qoffs = np.ascontiguousarray(qoffsets, np.int64).reshape(-1)
@@ -797,11 +956,9 @@ class Database:
             raise ValueError(f"out: aln must be a contiguous int64 tensor of at least {n * 7} elements")
         if ops is not None and (ops.dtype != t.uint8 or not ops.is_contiguous() or ops.numel() < n * ops_cap):
             raise ValueError(f"out: ops must be a contiguous uint8 tensor of at least {n * ops_cap} elements")
-        sub, sc = _affine(*scoring)
         with eng._checkpoint(checkpoint):
-            _check(lib().sw_db_align_affine_hits(eng._h, self._h, d_queries.data_ptr(), qoffs.ctypes.data, nq, ctypes.byref(sc), hits.data_ptr(),
-                                                 nhits.data_ptr() if nhits is not None else None, top, aln.data_ptr(),
-                                                 ops.data_ptr() if ops is not None else None, ops_cap, eng._stream()))
+            _check(fn(eng._h, self._h, d_source.data_ptr(), qoffs.ctypes.data, nq, ctypes.byref(sc), hits.data_ptr(),
+                      nhits.data_ptr() if nhits is not None else None, top, aln.data_ptr(), ops.data_ptr() if ops is not None else None, ops_cap, eng._stream()))
         return (aln.view(-1)[:n * 7].view(nq, max(0, top), 7),
                 ops.view(-1)[:n * ops_cap].view(nq, max(0, top), ops_cap) if ops is not None else None)
 

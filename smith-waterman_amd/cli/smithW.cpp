@@ -33,6 +33,10 @@
 //                              bytes) with gap_open 0 and the gap of --scores: the reference's backtrack() path
 //     ... --align-checkpoint  with --align: option "align_checkpoint" = 2 -- hits (with --all-queries: tables) whose whole direction matrices do not
 //                              fit the workspace are aligned from checkpoint rows in bounded memory, in the same one call; the output is unchanged
+//   smithW --search --pssm FILE DB.fa --gap-open O --gap-extend E [--top K] [--min-score S] [--align]
+//                              the ONE query is a position-specific scoring matrix, PSI-BLAST's ASCII PSSM (sw_read_pssm), searched through a prepared
+//                              handle (sw_db_search_pssm_top, sw_db_align_pssm_hits); the output is that of --all-queries for one record, the Q line of an
+//                              alignment the matrix's consensus (per column the first letter with the largest entry)
 // Extra flags: --seed N  --dump | --dump-labels (the header-row printers of omp_smithW.c)  --h64  --no-backtrack  --scores M X G  --record-a I  --record-b J
 //   --gpus N | --devices 0,1,..   ONE matrix over several GPUs (row bands, sw_multi_*; an id may repeat)  --p8  int8 P
 // The DP fill runs on the GPU through the C-ABI (include/swhip.h); stdout keeps the two
@@ -346,6 +350,97 @@ static int search_all_main(const char* qpath, const char* dbpath, long long top,
     return 0;
 }
 
+// --search --pssm FILE DB.fa: ONE position-specific scoring matrix (PSI-BLAST's ASCII format, sw_read_pssm) as the one query against the
+// database, through a prepared handle: sw_db_search_pssm_top (or, for more than SW_TOP_MAX hits, sw_db_search_pssm and a sort on the
+// host) and, with --align, one sw_db_align_pssm_hits call on the device hit table.  The output is the output of --all-queries for a file
+// of one record.  Bytes the matrix has no row entry for score the file's smallest entry (the rule of sw_read_submat) and smax is its
+// largest one, so nothing is clamped; the query line of an alignment is the matrix's consensus: per column the first letter with the
+// largest entry, '|' where the target has that letter.
+static int search_pssm_main(const char* ppath, const char* dbpath, long long top, long long min_score, const AffineArgs& af, bool align, bool align_ckpt) {
+    char letters[256];
+    int32_t nletters = 0;
+    int64_t ncols = 0, nrec = 0, total = 0;
+    CHECK(sw_read_pssm(ppath, letters, &nletters, nullptr, 0, &ncols));
+    std::vector<int8_t> pssm((size_t)ncols * (size_t)nletters);
+    CHECK(sw_read_pssm(ppath, letters, &nletters, pssm.data(), (int64_t)pssm.size(), &ncols));
+    CHECK(sw_read_fasta_db(dbpath, nullptr, 0, nullptr, 0, &nrec, &total));
+    std::vector<char> db((size_t)total + 1);
+    std::vector<int64_t> offs((size_t)nrec + 1, 0);
+    CHECK(sw_read_fasta_db(dbpath, db.data(), total, offs.data(), nrec + 1, &nrec, &total));
+    const int lo = *std::min_element(pssm.begin(), pssm.end()), hi = *std::max_element(pssm.begin(), pssm.end());
+    const sw_pssm_scoring scoring = {letters, nletters, std::min(lo, 0), std::max(hi, 0), af.has_open ? af.open : 0, af.has_extend ? af.extend : 0};
+    std::string consensus((size_t)ncols, '?');
+    for (int64_t g = 0; g < ncols; ++g) {
+        const int8_t* col = pssm.data() + g * nletters;
+        consensus[(size_t)g] = letters[std::max_element(col, col + nletters) - col];
+    }
+    const int64_t qoffs[2] = {0, ncols};
+    const long long K = std::max(0ll, std::min(top, (long long)nrec));
+    const bool on_device = K <= SW_TOP_MAX;
+    if (align && !on_device) { fprintf(stderr, "smithW: --pssm --align aligns a device hit table: min(--top, records) = %lld is above %d\n", K, SW_TOP_MAX); return 2; }
+    sw_ctx* ctx = nullptr;
+    CHECK(sw_create(0, &ctx));
+    if (align_ckpt) CHECK(sw_set_option(ctx, "align_checkpoint", 2));
+    void *d_pssm = nullptr, *d_db = nullptr, *d_res = nullptr, *d_hits = nullptr, *d_nhits = nullptr;
+    const size_t nres = on_device ? 1 : (size_t)std::max<int64_t>(1, nrec), nhit = (size_t)std::max<long long>(1, K);
+    CHECK(sw_device_malloc(ctx, pssm.size() + 16, &d_pssm));
+    CHECK(sw_device_malloc(ctx, (size_t)total + 16, &d_db));
+    CHECK(sw_device_malloc(ctx, nres * sizeof(sw_result), &d_res));
+    CHECK(sw_device_malloc(ctx, nhit * sizeof(sw_hit), &d_hits));
+    CHECK(sw_device_malloc(ctx, sizeof(int64_t), &d_nhits));
+    CHECK(sw_memcpy_h2d(ctx, d_pssm, pssm.data(), pssm.size()));
+    if (total) CHECK(sw_memcpy_h2d(ctx, d_db, db.data(), (size_t)total));
+    sw_db* handle = nullptr;
+    const double t0 = now_s();
+    CHECK(sw_db_create(ctx, (const char*)d_db, offs.data(), nrec, &handle));
+    const double t1 = now_s();
+    if (!on_device) CHECK(sw_db_search_pssm(ctx, handle, (const int8_t*)d_pssm, qoffs, 1, &scoring, (sw_result*)d_res, nullptr));
+    else if (K > 0) CHECK(sw_db_search_pssm_top(ctx, handle, (const int8_t*)d_pssm, qoffs, 1, &scoring, K, min_score, (sw_hit*)d_hits, (int64_t*)d_nhits, nullptr));
+    CHECK(sw_synchronize(ctx, nullptr));
+    const double t2 = now_s();
+    std::vector<sw_hit> hits(nhit);
+    int64_t nhits = 0;
+    if (on_device && K > 0) {
+        CHECK(sw_memcpy_d2h(ctx, hits.data(), d_hits, (size_t)K * sizeof(sw_hit)));
+        CHECK(sw_memcpy_d2h(ctx, &nhits, d_nhits, sizeof nhits));
+    } else if (!on_device) {
+        std::vector<sw_result> res(nres);
+        CHECK(sw_memcpy_d2h(ctx, res.data(), d_res, (size_t)nrec * sizeof(sw_result)));
+        hits = rank_hits(res.data(), nrec, K, min_score);
+        nhits = (int64_t)hits.size();
+    }
+    std::vector<sw_alignment> aln;
+    std::vector<char> ops;
+    int64_t ops_cap = 0;
+    if (align && K > 0) {
+        int64_t longest = 0;
+        CHECK(sw_db_info(handle, nullptr, nullptr, &longest, nullptr));
+        ops_cap = ncols + longest;
+        void *d_aln = nullptr, *d_ops = nullptr;
+        CHECK(sw_device_malloc(ctx, (size_t)K * sizeof(sw_alignment), &d_aln));
+        CHECK(sw_device_malloc(ctx, (size_t)K * (size_t)ops_cap, &d_ops));
+        CHECK(sw_db_align_pssm_hits(ctx, handle, (const int8_t*)d_pssm, qoffs, 1, &scoring, (const sw_hit*)d_hits, (const int64_t*)d_nhits, K, (sw_alignment*)d_aln,
+                                    (char*)d_ops, ops_cap, nullptr));
+        CHECK(sw_synchronize(ctx, nullptr));
+        aln.resize((size_t)K); ops.resize((size_t)K * (size_t)ops_cap);
+        CHECK(sw_memcpy_d2h(ctx, aln.data(), d_aln, aln.size() * sizeof(sw_alignment)));
+        CHECK(sw_memcpy_d2h(ctx, ops.data(), d_ops, ops.size()));
+        (void)sw_device_free(ctx, d_aln); (void)sw_device_free(ctx, d_ops);
+    }
+    printf("## query record 0 of %s\n", ppath);
+    const sw_affine unused = {nullptr, 0, 0};   // (print_hits aligns nothing itself when it is given the rows of a call)
+    if (int rc = print_hits(ctx, consensus.data(), ncols, nullptr, db, d_db, offs, nrec, total, hits.data(), (long long)nhits, align && K > 0, unused,
+                            aln.empty() ? nullptr : aln.data(), aln.empty() ? nullptr : ops.data(), ops_cap)) return rc;
+    const double cells = (double)ncols * (double)total;
+    printf("\nElapsed time for database search: %f (%.1f GCUPS; 1 PSSM of %lld columns over %d letters, handle prepared in %f)\n\n", t2 - t1,
+           t2 > t1 ? cells / (t2 - t1) / 1e9 : 0.0, (long long)ncols, nletters, t1 - t0);
+    sw_db_free(handle);
+    (void)sw_device_free(ctx, d_pssm); (void)sw_device_free(ctx, d_db); (void)sw_device_free(ctx, d_res);
+    (void)sw_device_free(ctx, d_hits); (void)sw_device_free(ctx, d_nhits);
+    sw_destroy(ctx);
+    return 0;
+}
+
 // the first word of every record's header line, by the record rule of sw_read_fasta_db (a headerless record is "-")
 static std::vector<std::string> fasta_names(const char* path) {
     std::vector<std::string> names;
@@ -536,7 +631,7 @@ int main(int argc, char** argv) {
     const char *search_q = nullptr, *search_db = nullptr;
     long long top = 10, min_score = 0, prefilter = 0, prefilter_hits = 0;
     bool has_min_score = false, has_top = false, has_prefilter = false, has_prefilter_hits = false;
-    const char* pairs_path = nullptr;
+    const char *pairs_path = nullptr, *pssm_path = nullptr;
     AffineArgs af;
     bool align = false, all_queries = false, align_ckpt = false;
     sw_scores sc = {3, -3, -2};
@@ -556,6 +651,7 @@ int main(int argc, char** argv) {
         else if (f == "--gpus" && ai + 1 < argc) { const int n = atoi(argv[++ai]); for (int g = 0; g < n; ++g) devices.push_back(g); }
         else if (f == "--devices" && ai + 1 < argc) { for (char* t = strtok(argv[++ai], ","); t; t = strtok(nullptr, ",")) devices.push_back(atoi(t)); }
         else if (f == "--fasta" && ai + 2 < argc) { fasta_a = argv[++ai]; fasta_b = argv[++ai]; builtin = false; }
+        else if (f == "--search" && ai + 3 < argc && std::string(argv[ai + 1]) == "--pssm") { ai += 1; search_q = pssm_path = argv[++ai]; search_db = argv[++ai]; builtin = false; }
         else if (f == "--search" && ai + 2 < argc) { search_q = argv[++ai]; search_db = argv[++ai]; builtin = false; }
         else if (f == "--top" && ai + 1 < argc) { top = strtoll(argv[++ai], nullptr, 10); has_top = true; }
         else if (f == "--pairs" && ai + 1 < argc) pairs_path = argv[++ai];
@@ -572,10 +668,18 @@ int main(int argc, char** argv) {
         else if (f == "--record-b" && ai + 1 < argc) rec_b = strtoll(argv[++ai], nullptr, 10);
         else if (f == "--seed" && ai + 1 < argc) seed = (unsigned)strtoul(argv[++ai], nullptr, 10);
         else if (f == "--scores" && ai + 3 < argc) { sc.match = atoi(argv[++ai]); sc.mismatch = atoi(argv[++ai]); sc.gap = atoi(argv[++ai]); }
-        else { fprintf(stderr, "usage: smithW [<cols> <rows> | --fasta A.fa B.fa [--record-a I] [--record-b J] | --search QUERY.fa DB.fa [--record-a I] [--top K] [--all-queries [--min-score S] [--prefilter S | --prefilter-hits S]] [--pairs FILE] [--matrix FILE] [--gap-open O] [--gap-extend E] [--align [--align-checkpoint]]] [--seed N] [--dump | --dump-labels] [--h64] [--no-backtrack] [--scores M X G] [--gpus N | --devices 0,1,..] [--p8]\n"); return 2; }
+        else { fprintf(stderr, "usage: smithW [<cols> <rows> | --fasta A.fa B.fa [--record-a I] [--record-b J] | --search QUERY.fa DB.fa [--record-a I] [--top K] [--all-queries [--min-score S] [--prefilter S | --prefilter-hits S]] [--pairs FILE] [--matrix FILE] [--gap-open O] [--gap-extend E] [--align [--align-checkpoint]] | --search --pssm FILE DB.fa --gap-open O --gap-extend E [--top K] [--min-score S] [--align]] [--seed N] [--dump | --dump-labels] [--h64] [--no-backtrack] [--scores M X G] [--gpus N | --devices 0,1,..] [--p8]\n"); return 2; }
     }
     if (npos == 1) { fprintf(stderr, "smithW: <cols> needs <rows>\n"); return 2; }
     if (align_ckpt && !(search_q && align)) { fprintf(stderr, "smithW: --align-checkpoint goes with --search --align\n"); return 2; }
+    if (pssm_path) {   // the matrix is the query and the scoring at once
+        if (af.matrix) { fprintf(stderr, "smithW: --pssm does not go with --matrix\n"); return 2; }
+        if (all_queries) { fprintf(stderr, "smithW: --pssm does not go with --all-queries (the file is the one query)\n"); return 2; }
+        if (pairs_path) { fprintf(stderr, "smithW: --pssm does not go with --pairs\n"); return 2; }
+        if (has_prefilter || has_prefilter_hits) { fprintf(stderr, "smithW: --pssm does not go with --prefilter / --prefilter-hits\n"); return 2; }
+        if (!af.has_open || !af.has_extend) { fprintf(stderr, "smithW: --pssm needs --gap-open O and --gap-extend E\n"); return 2; }
+        return search_pssm_main(pssm_path, search_db, top, min_score, af, align, align_ckpt);
+    }
     if (search_q) {
         if (af.on && !af.matrix && (sc.match < -128 || sc.match > 127 || sc.mismatch < -128 || sc.mismatch > 127)) {   // (sw_submat_match would clamp them)
             fprintf(stderr, "smithW: --gap-open without --matrix needs --scores M X within -128..127 (a table of signed bytes), got %d %d\n", sc.match, sc.mismatch);

@@ -123,7 +123,7 @@ static int grow_schedule(sw_ctx* c, size_t need, hipStream_t stream) {
 // The schedule and the table are uploaded from pinned copies, which a call overwrites: first the previous call's uploads have to have left
 // them (sitems_ev, recorded by upload_search_call).  Then the workspaces the three kernels share grow to what this call's plan needs; the
 // counter and (for a call with a `table`) the table's two copies are allocated at their first use.  On return c->h_sitems is free to write.
-static int stage_search_call(sw_ctx* c, hipStream_t stream, size_t nitems, size_t prof_need, size_t bnd_need, const sw_submat* table) {
+static int stage_search_call(sw_ctx* c, hipStream_t stream, size_t nitems, size_t prof_need, size_t bnd_need, bool table) {
     if (c->sitems_ev) HIP_TRY(hipEventSynchronize(c->sitems_ev));
     else HIP_TRY(hipEventCreateWithFlags(&c->sitems_ev, hipEventDisableTiming));
     bool fresh = false;
@@ -184,11 +184,36 @@ static std::vector<int64_t> query_lengths(const int64_t* qoffsets, int64_t nquer
     return qlens;
 }
 
+// Where the profiles of a many-query call come from.  Everything behind the profile -- the sweeps, the selection, the alignments --
+// reads 257 x qpad bytes per query and the two gap costs, whichever source built them:
+//   * the queries' letters on the device and a 256 x 256 table on the host (the sw_*_affine_* calls), or
+//   * a position-specific scoring matrix on the device (the sw_*_pssm_* calls): one column of `nletters` bytes per query column, and
+//     the host's 256-byte code table from a target byte to its place in a column (swh::check_search_pssm builds it).
+// A call builds one from its checked arguments; upload_query_table and launch_group_profiles are the only two places that look inside.
+struct QuerySource {
+    const char* d_queries = nullptr; const sw_submat* sub = nullptr;                                          // letters through a table
+    const signed char* d_pssm = nullptr; int nletters = 0, other = 0, smax = 0; unsigned char code[256] = {};   // a PSSM
+    int gap_open = 0, gap_extend = 0;
+    bool pssm() const { return d_pssm != nullptr; }
+    static QuerySource sequences(const char* d_queries, const sw_affine* sc) {
+        QuerySource s;
+        s.d_queries = d_queries; s.sub = sc->sub; s.gap_open = sc->gap_open; s.gap_extend = sc->gap_extend;
+        return s;
+    }
+    static QuerySource matrix(const int8_t* d_pssm, const sw_pssm_scoring* sc, const unsigned char (&code)[256]) {
+        QuerySource s;
+        s.d_pssm = (const signed char*)d_pssm; s.nletters = sc->nletters; s.other = sc->other; s.smax = sc->smax;
+        memcpy(s.code, code, sizeof s.code);
+        s.gap_open = sc->gap_open; s.gap_extend = sc->gap_extend;
+        return s;
+    }
+};
+
 // The start of a many-query call, behind stage_search_call (which has waited for the last uploads from the pinned copies): the plan's
 // table, every entry's qstart taken from the caller's offsets, and behind its entries an optional tail (the pair list's entry_of) go
 // through one pinned copy to c->d_mq in one upload; the scoring table follows through its own.  The event is recorded once, behind BOTH
 // uploads: whoever has waited for it may overwrite either pinned copy.
-static int upload_query_table(sw_ctx* c, hipStream_t stream, const std::vector<swk::MultiQuery>& table, const int64_t* qoffsets, const sw_affine* scoring,
+static int upload_query_table(sw_ctx* c, hipStream_t stream, const std::vector<swk::MultiQuery>& table, const int64_t* qoffsets, const QuerySource& src,
                               const void* tail = nullptr, size_t tail_bytes = 0) {
     const size_t nq = table.size(), slots = nq + (tail_bytes + sizeof(swk::MultiQuery) - 1) / sizeof(swk::MultiQuery);
     if (int rc = grow_query_table(c, slots, stream)) return rc;
@@ -197,29 +222,36 @@ static int upload_query_table(sw_ctx* c, hipStream_t stream, const std::vector<s
         c->h_mq[t].qstart = qoffsets[table[t].row];
     }
     if (tail_bytes) memcpy(c->h_mq + nq, tail, tail_bytes);
-    memcpy(c->h_submat, scoring->sub, sizeof(sw_submat));
+    // a PSSM's code table takes the place of the scoring table in the same two copies: its first 256 bytes
+    const size_t table_bytes = src.pssm() ? sizeof src.code : sizeof(sw_submat);
+    memcpy(c->h_submat, src.pssm() ? (const void*)src.code : (const void*)src.sub, table_bytes);
     HIP_TRY(hipMemcpyAsync(c->d_mq, c->h_mq, slots * sizeof(swk::MultiQuery), hipMemcpyHostToDevice, stream));
-    HIP_TRY(hipMemcpyAsync(c->d_submat, c->h_submat, sizeof(sw_submat), hipMemcpyHostToDevice, stream));
+    HIP_TRY(hipMemcpyAsync(c->d_submat, c->h_submat, table_bytes, hipMemcpyHostToDevice, stream));
     HIP_TRY(hipEventRecord(c->sitems_ev, stream));
     return SW_OK;
 }
 
 // The profiles of a group's queries (the table entries grp.q0 .. grp.q0 + grp.nq - 1) in one launch: every query's profile in shares of
-// about 16 KiB, over at most 4096 workgroups.
+// about 16 KiB, over at most 4096 workgroups; from the letters and the table, or from the PSSM (csrc/sw_pssm.hip: shares of whole tiles).
 template <typename Group>
-static int launch_group_profiles(sw_ctx* c, hipStream_t stream, const char* d_queries, const Group& grp) {
+static int launch_group_profiles(sw_ctx* c, hipStream_t stream, const QuerySource& src, const Group& grp) {
     const int parts = (int)std::clamp<int64_t>(grp.prof_bytes / grp.nq / 16384, 1, 4096);
     const unsigned blocks = (unsigned)std::min<int64_t>(grp.nq * parts, 4096);
-    hipLaunchKernelGGL(swk::sw_search_profile_submat_multi, dim3(blocks), dim3(256), 0, stream, (const unsigned char*)d_queries, c->d_mq + grp.q0, grp.nq,
-                       parts, c->d_sprof, (const signed char*)c->d_submat);
+    if (src.pssm())
+        hipLaunchKernelGGL(swk::sw_search_profile_pssm_multi, dim3(blocks), dim3(256), swk::sw_pssm_profile_lds_bytes(src.nletters), stream, src.d_pssm,
+                           c->d_mq + grp.q0, grp.nq, parts, c->d_sprof, (const unsigned char*)c->d_submat, src.nletters, src.other, src.smax);
+    else
+        hipLaunchKernelGGL(swk::sw_search_profile_submat_multi, dim3(blocks), dim3(256), 0, stream, (const unsigned char*)src.d_queries, c->d_mq + grp.q0,
+                           grp.nq, parts, c->d_sprof, (const signed char*)c->d_submat);
     HIP_TRY(hipGetLastError());
     return SW_OK;
 }
 
 // The many-query search of checked arguments into `d_results` (nqueries x ntargets, nqueries > 0, ntargets > 0): what sw_db_search_affine
-// does for a whole call and sw_db_search_affine_top for every chunk of one.  The caller holds the device's launch order (DevOrder).
-static int run_search_multi(sw_ctx* c, const sw_db* db, const char* d_queries, const int64_t* qoffsets, int64_t nqueries, const sw_affine* scoring,
-                            sw_result* d_results, hipStream_t stream) {
+// and sw_db_search_pssm do for a whole call and their _top forms for every chunk of one.  The caller holds the device's launch order
+// (DevOrder).
+static int run_search_multi(sw_ctx* c, const sw_db* db, const QuerySource& src, const int64_t* qoffsets, int64_t nqueries, sw_result* d_results,
+                            hipStream_t stream) {
     // empty targets keep the zeros: {0, 0, 0}
     HIP_TRY(hipMemsetAsync(d_results, 0, (size_t)nqueries * (size_t)db->ntargets * sizeof(sw_result), stream));
     if (db->nonempty == 0) return SW_OK;
@@ -232,12 +264,12 @@ static int run_search_multi(sw_ctx* c, const sw_db* db, const char* d_queries, c
     const swp::SearchMultiPlan plan = swp::plan_search_multi(mj);
     for (const swp::MultiLaunch& l : plan.launch)
         if (c->search_multi_per_cu[l.kernel] < 1) { set_err("the many-query search kernel does not fit a CU on this device"); return SW_EDEVICE; }
-    if (int rc = stage_search_call(c, stream, 0, plan.prof_need, plan.bnd_need, scoring->sub)) return rc;
-    if (int rc = upload_query_table(c, stream, plan.table, qoffsets, scoring)) return rc;
+    if (int rc = stage_search_call(c, stream, 0, plan.prof_need, plan.bnd_need, true)) return rc;
+    if (int rc = upload_query_table(c, stream, plan.table, qoffsets, src)) return rc;
     size_t li = 0;
     for (size_t g = 0; g < plan.group.size(); ++g) {
         const swp::MultiGroup& grp = plan.group[g];
-        if (int rc = launch_group_profiles(c, stream, d_queries, grp)) return rc;
+        if (int rc = launch_group_profiles(c, stream, src, grp)) return rc;
         for (; li < plan.launch.size() && plan.launch[li].group == (int)g; ++li) {
             const swp::MultiLaunch& l = plan.launch[li];
             swk::SearchMultiParams sp;
@@ -246,7 +278,7 @@ static int run_search_multi(sw_ctx* c, const sw_db* db, const char* d_queries, c
             sp.items = db->d_items; sp.rank0 = l.rank0;
             sp.queries = c->d_mq + l.q0; sp.nq = (unsigned)l.nq; sp.nitems = l.items;
             sp.prof = c->d_sprof; sp.ntargets = db->ntargets;
-            sp.ge = scoring->gap_extend; sp.goe = scoring->gap_open + scoring->gap_extend;
+            sp.ge = src.gap_extend; sp.goe = src.gap_open + src.gap_extend;
             sp.bnd = l.bnd_per ? c->d_sbnd : nullptr; sp.bnd_per = l.bnd_per;
             sp.counter = c->d_sctr;
             sp.results = d_results;
@@ -365,7 +397,7 @@ int sw_search_device(sw_ctx* c, const char* d_query, int64_t qlen, const char* d
     sj.qlen = qlen; sj.maxlen = maxlen; sj.ntargets = nonempty; sj.match = sc->match; sj.mismatch = sc->mismatch; sj.gap = sc->gap;
     const swp::SearchPlan plan = swp::plan_search(sj, device_facts(c));
     if (c->search_per_cu[plan.kernel] < 1) { set_err("the search kernel does not fit a CU on this device"); return SW_EDEVICE; }
-    if (int rc = stage_search_call(c, stream, (size_t)nonempty, plan.prof_need, plan.bnd_need, nullptr)) return rc;
+    if (int rc = stage_search_call(c, stream, (size_t)nonempty, plan.prof_need, plan.bnd_need, false)) return rc;
     swp::search_schedule(offsets, ntargets, c->h_sitems);
     if (int rc = upload_search_call(c, stream, (size_t)nonempty, nullptr)) return rc;
     hipLaunchKernelGGL(swk::sw_search_profile, dim3((unsigned)plan.prof_blocks), dim3(256), 0, stream, (const unsigned char*)d_query, qlen, plan.qpad,
@@ -401,7 +433,7 @@ int sw_search_affine_device(sw_ctx* c, const char* d_query, int64_t qlen, const 
     std::copy(std::begin(c->search_affine_per_cu), std::end(c->search_affine_per_cu), sj.per_cu);
     const swp::SearchAffinePlan plan = swp::plan_search_affine(sj);
     if (c->search_affine_per_cu[plan.kernel] < 1) { set_err("the affine search kernel does not fit a CU on this device"); return SW_EDEVICE; }
-    if (int rc = stage_search_call(c, stream, (size_t)nonempty, plan.prof_need, plan.bnd_need, scoring->sub)) return rc;
+    if (int rc = stage_search_call(c, stream, (size_t)nonempty, plan.prof_need, plan.bnd_need, true)) return rc;
     swp::search_schedule(offsets, ntargets, c->h_sitems);
     if (int rc = upload_search_call(c, stream, (size_t)nonempty, scoring->sub)) return rc;
     hipLaunchKernelGGL(swk::sw_search_profile_submat, dim3((unsigned)plan.prof_blocks), dim3(256), 0, stream, (const unsigned char*)d_query, qlen,
@@ -432,7 +464,7 @@ static int align_affine_ckpt(sw_ctx* c, const char* d_query, int64_t qlen, const
         return SW_EINVAL;
     }
     if (c->align_ckpt_per_cu[plan.kernel] < 1) { set_err("the checkpointed alignment kernel does not fit a CU on this device"); return SW_EDEVICE; }
-    if (int rc = stage_search_call(c, stream, (size_t)nhits, plan.prof_need, plan.bnd_need, scoring->sub)) return rc;
+    if (int rc = stage_search_call(c, stream, (size_t)nhits, plan.prof_need, plan.bnd_need, true)) return rc;
     bool fresh = false;   // (the direction workspace: a band and its checkpoint rows per slot)
     if (int rc = grow_workspace((void**)&c->d_adir, c->adir_cap, plan.dir_need, 1, 0, stream, fresh)) return rc;
     swp::align_schedule(offsets, hits, nhits, c->h_sitems);
@@ -481,7 +513,7 @@ int sw_align_affine_device(sw_ctx* c, const char* d_query, int64_t qlen, const c
         return SW_EINVAL;
     }
     if (c->align_affine_per_cu[plan.kernel] < 1) { set_err("the alignment kernel does not fit a CU on this device"); return SW_EDEVICE; }
-    if (int rc = stage_search_call(c, stream, (size_t)nhits, plan.prof_need, plan.bnd_need, scoring->sub)) return rc;
+    if (int rc = stage_search_call(c, stream, (size_t)nhits, plan.prof_need, plan.bnd_need, true)) return rc;
     bool fresh = false;   // (its own workspace: one direction matrix per slot)
     if (int rc = grow_workspace((void**)&c->d_adir, c->adir_cap, plan.dir_need, 1, 0, stream, fresh)) return rc;
     swp::align_schedule(offsets, hits, nhits, c->h_sitems);
@@ -563,6 +595,16 @@ int sw_db_info(const sw_db* db, int64_t* ntargets, int64_t* nonempty, int64_t* l
     return SW_OK;
 }
 
+// sw_db_search_affine / sw_db_search_pssm behind their checks: the stream's turn on the device and the search.
+static int db_search_call(sw_ctx* c, const sw_db* db, const QuerySource& src, const int64_t* qoffsets, int64_t nqueries, sw_result* d_results, void* stream_) {
+    if (nqueries == 0 || db->ntargets == 0) return SW_OK;
+    hipStream_t stream = (hipStream_t)stream_;
+    HIP_TRY(hipSetDevice(c->device));
+    DevOrder order(c, stream, false);
+    if (order.rc) return order.rc;
+    return run_search_multi(c, db, src, qoffsets, nqueries, d_results, stream);
+}
+
 // Every query against every target of the handle.  Per call the host checks and plans the QUERIES (O(nqueries)), uploads their table
 // and the scoring table from pinned copies, and enqueues per group one profile launch and one launch per class of queries; the targets'
 // offsets are not looked at again and nothing is sorted.
@@ -572,12 +614,18 @@ int sw_db_search_affine(sw_ctx* c, const sw_db* db, const char* d_queries, const
     if (db->device != c->device) { set_err("sw_db_search_affine: the handle was created on device %d, the context runs on device %d", db->device, c->device); return SW_EINVAL; }
     int64_t maxq = 0;
     if (int rc = swh::check_search_multi("sw_db_search_affine", qoffsets, nqueries, db->longest, scoring, &maxq)) return rc;
-    if (nqueries == 0 || db->ntargets == 0) return SW_OK;
-    hipStream_t stream = (hipStream_t)stream_;
-    HIP_TRY(hipSetDevice(c->device));
-    DevOrder order(c, stream, false);
-    if (order.rc) return order.rc;
-    return run_search_multi(c, db, d_queries, qoffsets, nqueries, scoring, d_results, stream);
+    return db_search_call(c, db, QuerySource::sequences(d_queries, scoring), qoffsets, nqueries, d_results, stream_);
+}
+
+// The same search with a position-specific scoring matrix in place of letters and a table: only the source of the profiles differs.
+int sw_db_search_pssm(sw_ctx* c, const sw_db* db, const int8_t* d_pssm, const int64_t* qoffsets, int64_t nqueries, const sw_pssm_scoring* scoring,
+                      sw_result* d_results, void* stream_) {
+    if (!c || !db || !d_pssm || !qoffsets || !scoring || !d_results) { set_err("sw_db_search_pssm: NULL pointer"); return SW_EINVAL; }
+    if (db->device != c->device) { set_err("sw_db_search_pssm: the handle was created on device %d, the context runs on device %d", db->device, c->device); return SW_EINVAL; }
+    int64_t maxq = 0;
+    unsigned char code[256];
+    if (int rc = swh::check_search_pssm("sw_db_search_pssm", qoffsets, nqueries, db->longest, scoring, &maxq, code)) return rc;
+    return db_search_call(c, db, QuerySource::matrix(d_pssm, scoring, code), qoffsets, nqueries, d_results, stream_);
 }
 
 // The selection alone over a table the caller holds: the plan's chunks only bound the histograms here (no budget on the rows).
@@ -598,39 +646,53 @@ int sw_top_hits_device(sw_ctx* c, const sw_result* d_results, int64_t nqueries, 
 }
 
 // Search and selection with bounded result memory: chunk after chunk of queries through run_search_multi into the result workspace,
-// then that chunk's rows of d_hits.  The stream orders the chunks, which share the workspace.
-int sw_db_search_affine_top(sw_ctx* c, const sw_db* db, const char* d_queries, const int64_t* qoffsets, int64_t nqueries, const sw_affine* scoring,
-                            int64_t top, int64_t min_score, sw_hit* d_hits, int64_t* d_nhits, void* stream_) {
-    if (!c || !db || !d_queries || !qoffsets || !scoring) { set_err("sw_db_search_affine_top: NULL pointer"); return SW_EINVAL; }
-    if (db->device != c->device) { set_err("sw_db_search_affine_top: the handle was created on device %d, the context runs on device %d", db->device, c->device); return SW_EINVAL; }
-    int64_t maxq = 0;
-    if (int rc = swh::check_search_multi("sw_db_search_affine_top", qoffsets, nqueries, db->longest, scoring, &maxq)) return rc;
+// then that chunk's rows of d_hits.  The stream orders the chunks, which share the workspace.  (`who`'s search arguments are checked.)
+static int db_search_top_call(const char* who, sw_ctx* c, const sw_db* db, const QuerySource& src, const int64_t* qoffsets, int64_t nqueries, int64_t top,
+                              int64_t min_score, sw_hit* d_hits, int64_t* d_nhits, void* stream_) {
     hipStream_t stream = (hipStream_t)stream_;
     swp::SearchTopPlan plan;
-    if (int rc = plan_top_call(c, "sw_db_search_affine_top", nqueries, db->ntargets, top, d_hits, d_nhits, c->opt_search_results_mib << 20, plan)) return rc;
+    if (int rc = plan_top_call(c, who, nqueries, db->ntargets, top, d_hits, d_nhits, c->opt_search_results_mib << 20, plan)) return rc;
     if (nqueries == 0) return SW_OK;
     DevOrder order(c, stream, false);
     if (order.rc) return order.rc;
     if (int rc = grow_top_workspaces(c, plan, true, stream)) return rc;
     for (const swp::TopChunk& ch : plan.chunk) {
         if (db->ntargets > 0)
-            if (int rc = run_search_multi(c, db, d_queries, qoffsets + ch.q0, ch.nq, scoring, c->d_tres, stream)) return rc;
+            if (int rc = run_search_multi(c, db, src, qoffsets + ch.q0, ch.nq, c->d_tres, stream)) return rc;
         if (int rc = select_top(c, plan, c->d_tres, ch.nq, db->ntargets, top, min_score, d_hits + ch.q0 * top, d_nhits + ch.q0, stream)) return rc;
     }
     c->last_search_top_chunks = (int64_t)plan.chunk.size(); c->last_search_top_kernel = plan.kernel;
     return SW_OK;
 }
 
+int sw_db_search_affine_top(sw_ctx* c, const sw_db* db, const char* d_queries, const int64_t* qoffsets, int64_t nqueries, const sw_affine* scoring,
+                            int64_t top, int64_t min_score, sw_hit* d_hits, int64_t* d_nhits, void* stream_) {
+    if (!c || !db || !d_queries || !qoffsets || !scoring) { set_err("sw_db_search_affine_top: NULL pointer"); return SW_EINVAL; }
+    if (db->device != c->device) { set_err("sw_db_search_affine_top: the handle was created on device %d, the context runs on device %d", db->device, c->device); return SW_EINVAL; }
+    int64_t maxq = 0;
+    if (int rc = swh::check_search_multi("sw_db_search_affine_top", qoffsets, nqueries, db->longest, scoring, &maxq)) return rc;
+    return db_search_top_call("sw_db_search_affine_top", c, db, QuerySource::sequences(d_queries, scoring), qoffsets, nqueries, top, min_score, d_hits, d_nhits,
+                              stream_);
+}
+
+int sw_db_search_pssm_top(sw_ctx* c, const sw_db* db, const int8_t* d_pssm, const int64_t* qoffsets, int64_t nqueries, const sw_pssm_scoring* scoring,
+                          int64_t top, int64_t min_score, sw_hit* d_hits, int64_t* d_nhits, void* stream_) {
+    if (!c || !db || !d_pssm || !qoffsets || !scoring) { set_err("sw_db_search_pssm_top: NULL pointer"); return SW_EINVAL; }
+    if (db->device != c->device) { set_err("sw_db_search_pssm_top: the handle was created on device %d, the context runs on device %d", db->device, c->device); return SW_EINVAL; }
+    int64_t maxq = 0;
+    unsigned char code[256];
+    if (int rc = swh::check_search_pssm("sw_db_search_pssm_top", qoffsets, nqueries, db->longest, scoring, &maxq, code)) return rc;
+    return db_search_top_call("sw_db_search_pssm_top", c, db, QuerySource::matrix(d_pssm, scoring, code), qoffsets, nqueries, top, min_score, d_hits, d_nhits,
+                              stream_);
+}
+
 // The alignments of a device hit table (csrc/sw_align_hits.hip).  Per call the host checks and plans the QUERIES (O(nqueries)) against
 // the handle's longest target; the table, the counts and the targets' offsets are read on the device only.  Per group: one profile
 // launch, two binning launches, one alignment launch per (class, tier) whose grid the plan fixed for the longest list it could get.
-int sw_db_align_affine_hits(sw_ctx* c, const sw_db* db, const char* d_queries, const int64_t* qoffsets, int64_t nqueries, const sw_affine* scoring,
-                            const sw_hit* d_hits, const int64_t* d_nhits, int64_t top, sw_alignment* d_aln, char* d_ops, int64_t ops_cap, void* stream_) {
-    if (!c || !db || !d_queries || !qoffsets || !scoring) { set_err("sw_db_align_affine_hits: NULL pointer"); return SW_EINVAL; }
-    if (db->device != c->device) { set_err("sw_db_align_affine_hits: the handle was created on device %d, the context runs on device %d", db->device, c->device); return SW_EINVAL; }
-    int64_t maxq = 0;
-    if (int rc = swh::check_search_multi("sw_db_align_affine_hits", qoffsets, nqueries, db->longest, scoring, &maxq)) return rc;
-    if (int rc = swh::check_align_hits("sw_db_align_affine_hits", top, d_hits, d_aln, d_ops, ops_cap)) return rc;
+// (`who`'s search arguments are checked)
+static int db_align_hits_call(const char* who, sw_ctx* c, const sw_db* db, const QuerySource& src, const int64_t* qoffsets, int64_t nqueries,
+                              const sw_hit* d_hits, const int64_t* d_nhits, int64_t top, sw_alignment* d_aln, char* d_ops, int64_t ops_cap, void* stream_) {
+    if (int rc = swh::check_align_hits(who, top, d_hits, d_aln, d_ops, ops_cap)) return rc;
     c->last_align_hits_launches = c->last_align_hits_tiers = c->last_align_hits_slots = 0;   // (a call that launches no alignment reports none)
     c->last_align_hits_checkpointed = c->last_align_hits_band_rows = 0;
     if (nqueries == 0) return SW_OK;
@@ -653,14 +715,14 @@ int sw_db_align_affine_hits(sw_ctx* c, const sw_db* db, const char* d_queries, c
         cj.band_rows = c->opt_align_checkpoint_rows;
         plan = swp::plan_align_hits_ckpt(cj);
         if (!plan.fits) {
-            set_err("sw_db_align_affine_hits: the checkpointed slot of the handle's longest target against the longest query (%lld rows against %lld padded "
-                    "columns = %lld bytes) does not fit align_workspace_mib = %lld (or the 2 GiB a slot may take)", (long long)std::max<int64_t>(1, db->longest),
+            set_err("%s: the checkpointed slot of the handle's longest target against the longest query (%lld rows against %lld padded "
+                    "columns = %lld bytes) does not fit align_workspace_mib = %lld (or the 2 GiB a slot may take)", who, (long long)std::max<int64_t>(1, db->longest),
                     (long long)plan.worst_qpad, (long long)plan.worst_bytes, (long long)c->opt_align_workspace_mib);
             return SW_EINVAL;
         }
     } else if (!plan.fits) {   // decided from host data alone, whatever the table names
-        set_err("sw_db_align_affine_hits: the direction matrix of the handle's longest target against the longest query (%lld rows x %lld bytes = %lld bytes) "
-                "does not fit align_workspace_mib = %lld (or the 2 GiB a slot may take)", (long long)std::max<int64_t>(1, db->longest), (long long)plan.worst_qpad,
+        set_err("%s: the direction matrix of the handle's longest target against the longest query (%lld rows x %lld bytes = %lld bytes) "
+                "does not fit align_workspace_mib = %lld (or the 2 GiB a slot may take)", who, (long long)std::max<int64_t>(1, db->longest), (long long)plan.worst_qpad,
                 (long long)plan.worst_bytes, (long long)c->opt_align_workspace_mib);
         return SW_EINVAL;
     }
@@ -672,18 +734,18 @@ int sw_db_align_affine_hits(sw_ctx* c, const sw_db* db, const char* d_queries, c
     }
     for (const swp::AlignHitsLaunch& l : plan.launch)
         if ((ckpt ? c->align_hits_ckpt_per_cu : c->align_hits_per_cu)[l.kernel] < 1) { set_err("the hit-table alignment kernel does not fit a CU on this device"); return SW_EDEVICE; }
-    if (int rc = stage_search_call(c, stream, 0, plan.prof_need, plan.bnd_need, scoring->sub)) return rc;
+    if (int rc = stage_search_call(c, stream, 0, plan.prof_need, plan.bnd_need, true)) return rc;
     bool fresh = false;
     if (int rc = grow_workspace((void**)&c->d_adir, c->adir_cap, plan.dir_need, 1, 0, stream, fresh)) return rc;
     if (int rc = grow_workspace((void**)&c->d_ahitems, c->ahitems_cap, plan.items_need, sizeof(swk::AlignHitItem), 0, stream, fresh)) return rc;
     if (!c->d_ahctl) HIP_TRY(hipMalloc((void**)&c->d_ahctl, sizeof(swk::AlignHitsCtl)));
     if (!c->d_ahfilled) HIP_TRY(hipMalloc((void**)&c->d_ahfilled, 64));
     HIP_TRY(hipMemsetAsync(c->d_ahfilled, 0, 4, stream));
-    if (int rc = upload_query_table(c, stream, plan.table, qoffsets, scoring)) return rc;
+    if (int rc = upload_query_table(c, stream, plan.table, qoffsets, src)) return rc;
     size_t li = 0;
     for (size_t g = 0; g < plan.group.size(); ++g) {
         const swp::AlignHitsGroup& grp = plan.group[g];
-        if (int rc = launch_group_profiles(c, stream, d_queries, grp)) return rc;
+        if (int rc = launch_group_profiles(c, stream, src, grp)) return rc;
         // the lists of the group: counts, cursors and work counters start at zero
         HIP_TRY(hipMemsetAsync(c->d_ahctl, 0, sizeof(swk::AlignHitsCtl), stream));
         swk::AlignHitsBinParams bp;
@@ -713,7 +775,7 @@ int sw_db_align_affine_hits(sw_ctx* c, const sw_db* db, const char* d_queries, c
                 kp.items = c->d_ahitems + grp.cls[l.kernel].item0;
                 kp.counts = c->d_ahctl->count[l.kernel]; kp.tier = l.tier;
                 kp.queries = c->d_mq + grp.q0; kp.prof = c->d_sprof;
-                kp.ge = scoring->gap_extend; kp.goe = scoring->gap_open + scoring->gap_extend;
+                kp.ge = src.gap_extend; kp.goe = src.gap_open + src.gap_extend;
                 kp.bnd = l.bnd_per ? c->d_sbnd : nullptr; kp.bnd_per = l.bnd_per;
                 kp.counter = &c->d_ahctl->work[l.kernel][l.tier];
                 kp.dir = c->d_adir; kp.slot_bytes = l.slot_bytes; kp.nslots = l.slots; kp.log_band = l.log_band;
@@ -729,7 +791,7 @@ int sw_db_align_affine_hits(sw_ctx* c, const sw_db* db, const char* d_queries, c
             ap.items = c->d_ahitems + grp.cls[l.kernel].item0;
             ap.counts = c->d_ahctl->count[l.kernel]; ap.tier = l.tier;
             ap.queries = c->d_mq + grp.q0; ap.prof = c->d_sprof;
-            ap.ge = scoring->gap_extend; ap.goe = scoring->gap_open + scoring->gap_extend;
+            ap.ge = src.gap_extend; ap.goe = src.gap_open + src.gap_extend;
             ap.bnd = l.bnd_per ? c->d_sbnd : nullptr; ap.bnd_per = l.bnd_per;
             ap.counter = &c->d_ahctl->work[l.kernel][l.tier];
             ap.dir = c->d_adir; ap.slot_bytes = l.slot_bytes; ap.nslots = l.slots;
@@ -741,6 +803,27 @@ int sw_db_align_affine_hits(sw_ctx* c, const sw_db* db, const char* d_queries, c
     c->last_align_hits_launches = (int64_t)(3 * plan.group.size() + plan.launch.size()); c->last_align_hits_tiers = plan.tiers; c->last_align_hits_slots = plan.slots;
     c->last_align_hits_checkpointed = ckpt ? 1 : 0;
     return SW_OK;
+}
+
+int sw_db_align_affine_hits(sw_ctx* c, const sw_db* db, const char* d_queries, const int64_t* qoffsets, int64_t nqueries, const sw_affine* scoring,
+                            const sw_hit* d_hits, const int64_t* d_nhits, int64_t top, sw_alignment* d_aln, char* d_ops, int64_t ops_cap, void* stream_) {
+    if (!c || !db || !d_queries || !qoffsets || !scoring) { set_err("sw_db_align_affine_hits: NULL pointer"); return SW_EINVAL; }
+    if (db->device != c->device) { set_err("sw_db_align_affine_hits: the handle was created on device %d, the context runs on device %d", db->device, c->device); return SW_EINVAL; }
+    int64_t maxq = 0;
+    if (int rc = swh::check_search_multi("sw_db_align_affine_hits", qoffsets, nqueries, db->longest, scoring, &maxq)) return rc;
+    return db_align_hits_call("sw_db_align_affine_hits", c, db, QuerySource::sequences(d_queries, scoring), qoffsets, nqueries, d_hits, d_nhits, top, d_aln, d_ops,
+                              ops_cap, stream_);
+}
+
+int sw_db_align_pssm_hits(sw_ctx* c, const sw_db* db, const int8_t* d_pssm, const int64_t* qoffsets, int64_t nqueries, const sw_pssm_scoring* scoring,
+                          const sw_hit* d_hits, const int64_t* d_nhits, int64_t top, sw_alignment* d_aln, char* d_ops, int64_t ops_cap, void* stream_) {
+    if (!c || !db || !d_pssm || !qoffsets || !scoring) { set_err("sw_db_align_pssm_hits: NULL pointer"); return SW_EINVAL; }
+    if (db->device != c->device) { set_err("sw_db_align_pssm_hits: the handle was created on device %d, the context runs on device %d", db->device, c->device); return SW_EINVAL; }
+    int64_t maxq = 0;
+    unsigned char code[256];
+    if (int rc = swh::check_search_pssm("sw_db_align_pssm_hits", qoffsets, nqueries, db->longest, scoring, &maxq, code)) return rc;
+    return db_align_hits_call("sw_db_align_pssm_hits", c, db, QuerySource::matrix(d_pssm, scoring, code), qoffsets, nqueries, d_hits, d_nhits, top, d_aln, d_ops,
+                              ops_cap, stream_);
 }
 
 // The scores of a device pair list (csrc/sw_search_pairs.hip).  Per call the host checks and plans the QUERIES (O(nqueries)) against the
@@ -773,16 +856,17 @@ int sw_db_search_affine_pairs(sw_ctx* c, const sw_db* db, const char* d_queries,
     const swp::SearchPairsPlan plan = swp::plan_search_pairs(pj);
     for (const swp::PairsLaunch& l : plan.launch)
         if (c->search_pairs_per_cu[l.kernel] < 1) { set_err("the pair-list search kernel does not fit a CU on this device"); return SW_EDEVICE; }
-    if (int rc = stage_search_call(c, stream, 0, plan.prof_need, plan.bnd_need, scoring->sub)) return rc;
+    if (int rc = stage_search_call(c, stream, 0, plan.prof_need, plan.bnd_need, true)) return rc;
     bool fresh = false;
     if (int rc = grow_workspace((void**)&c->d_spitems, c->spitems_cap, plan.items_need, 1, 0, stream, fresh)) return rc;
     if (!c->d_spctl) HIP_TRY(hipMalloc((void**)&c->d_spctl, sizeof(swk::SearchPairsCtl)));
     // behind the table's nqueries entries: entry_of (4 bytes per query)
-    if (int rc = upload_query_table(c, stream, plan.table, qoffsets, scoring, plan.entry_of.data(), (size_t)nqueries * sizeof(int32_t))) return rc;
+    const QuerySource src = QuerySource::sequences(d_queries, scoring);
+    if (int rc = upload_query_table(c, stream, plan.table, qoffsets, src, plan.entry_of.data(), (size_t)nqueries * sizeof(int32_t))) return rc;
     size_t l0 = 0;
     for (size_t g = 0; g < plan.group.size(); ++g) {
         const swp::PairsGroup& grp = plan.group[g];
-        if (int rc = launch_group_profiles(c, stream, d_queries, grp)) return rc;
+        if (int rc = launch_group_profiles(c, stream, src, grp)) return rc;
         size_t l1 = l0;
         while (l1 < plan.launch.size() && plan.launch[l1].group == (int)g) ++l1;
         for (int64_t ch = 0; ch < plan.nchunks; ++ch) {
@@ -858,14 +942,15 @@ int sw_db_prefilter_ungapped(sw_ctx* c, const sw_db* db, const char* d_queries, 
     const swp::PrefilterPlan plan = swp::plan_prefilter(pj);
     for (const swp::PrefilterLaunch& l : plan.launch)
         if (c->prefilter_per_cu[l.kernel] < 1) { set_err("the pre-filter kernel does not fit a CU on this device"); return SW_EDEVICE; }
-    if (int rc = stage_search_call(c, stream, 0, plan.prof_need, plan.bnd_need, sub)) return rc;
+    if (int rc = stage_search_call(c, stream, 0, plan.prof_need, plan.bnd_need, true)) return rc;
     if (!c->d_pfctl) HIP_TRY(hipMalloc((void**)&c->d_pfctl, sizeof(swk::PrefilterCtl)));
-    if (int rc = upload_query_table(c, stream, plan.table, qoffsets, &scoring)) return rc;
+    const QuerySource src = QuerySource::sequences(d_queries, &scoring);
+    if (int rc = upload_query_table(c, stream, plan.table, qoffsets, src)) return rc;
     hipLaunchKernelGGL(swk::sw_prefilter_commit, dim3(1), dim3(64), 0, stream, c->d_pfctl, d_npairs, 1);
     HIP_TRY(hipGetLastError());
     size_t li = 0;
     for (size_t g = 0; g < plan.group.size(); ++g) {
-        if (int rc = launch_group_profiles(c, stream, d_queries, plan.group[g])) return rc;
+        if (int rc = launch_group_profiles(c, stream, src, plan.group[g])) return rc;
         for (; li < plan.launch.size() && plan.launch[li].group == (int)g; ++li) {
             const swp::PrefilterLaunch& l = plan.launch[li];
             swk::PrefilterParams pp;

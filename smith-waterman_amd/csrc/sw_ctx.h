@@ -19,6 +19,8 @@ int check_search_affine(const char* who, int64_t qlen, const int64_t* offsets, i
 int check_align_affine(const char* who, const int64_t* offsets, int64_t ntargets, const int64_t* hits, int64_t nhits, const void* aln, const void* ops,
                        int64_t ops_cap, int64_t* maxhit_out);
 int check_search_multi(const char* who, const int64_t* qoffsets, int64_t nqueries, int64_t longest_target, const sw_affine* sc, int64_t* maxq_out);
+SW_HIDDEN int check_search_pssm(const char* who, const int64_t* qoffsets, int64_t nqueries, int64_t longest_target, const sw_pssm_scoring* sc,
+                                int64_t* maxq_out, unsigned char (&code)[256]);
 int check_prefilter(const char* who, int64_t min_score, const void* pairs, int64_t pairs_cap, const void* npairs, const void* scores);
 int check_align_hits(const char* who, int64_t top, const void* hits, const void* aln, const void* ops, int64_t ops_cap);
 SW_HIDDEN int check_targets(const char* who, int64_t qlen, const int64_t* offsets, int64_t ntargets, int64_t* maxlen_out, int64_t* nonempty_out);

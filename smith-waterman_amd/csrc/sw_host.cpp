@@ -67,14 +67,19 @@ int check_targets(const char* who, int64_t qlen, const int64_t* offsets, int64_t
 }
 
 // The scoring rules of the affine calls for a query of `qlen` against a longest target of `maxlen` (include/swhip.h).
-static int check_affine_scoring(const char* who, const sw_affine* sc, int64_t qlen, int64_t maxlen) {
-    constexpr int64_t kScoreLimit = 1ll << 24;
-    if (sc->gap_open > 0) { set_err("%s: gap_open must be <= 0 (got %d)", who, sc->gap_open); return SW_EINVAL; }
-    if (sc->gap_extend > 0) { set_err("%s: gap_extend must be <= 0 (got %d)", who, sc->gap_extend); return SW_EINVAL; }
-    if ((int64_t)sc->gap_open + (int64_t)sc->gap_extend < -kScoreLimit) {
-        set_err("%s: gap_open + gap_extend = %lld is below -2^24", who, (long long)sc->gap_open + (long long)sc->gap_extend);
+constexpr int64_t kScoreLimit = 1ll << 24;
+static int check_gap_costs(const char* who, int32_t gap_open, int32_t gap_extend) {
+    if (gap_open > 0) { set_err("%s: gap_open must be <= 0 (got %d)", who, gap_open); return SW_EINVAL; }
+    if (gap_extend > 0) { set_err("%s: gap_extend must be <= 0 (got %d)", who, gap_extend); return SW_EINVAL; }
+    if ((int64_t)gap_open + (int64_t)gap_extend < -kScoreLimit) {
+        set_err("%s: gap_open + gap_extend = %lld is below -2^24", who, (long long)gap_open + (long long)gap_extend);
         return SW_EINVAL;
     }
+    return SW_OK;
+}
+
+static int check_affine_scoring(const char* who, const sw_affine* sc, int64_t qlen, int64_t maxlen) {
+    if (int rc = check_gap_costs(who, sc->gap_open, sc->gap_extend)) return rc;
     int best = 0, bx = 0, by = 0;
     for (int x = 0; x < 256; ++x)
         for (int y = 0; y < 256; ++y)
@@ -101,9 +106,8 @@ int check_search_affine(const char* who, int64_t qlen, const int64_t* offsets, i
 
 // The argument rules of a many-query search (sw_db_search_affine, sw_search_affine_multi_host): the query offsets, every query's
 // length, and the scoring rules taken over the longest query against the database's longest target.  O(nqueries).
-int check_search_multi(const char* who, const int64_t* qoffsets, int64_t nqueries, int64_t longest_target, const sw_affine* sc, int64_t* maxq_out) {
+static int check_query_offsets(const char* who, const int64_t* qoffsets, int64_t nqueries, int64_t* maxq_out) {
     constexpr int64_t kMaxDim = swk::SW_MAX_DIM;
-    if (!qoffsets || !sc || !sc->sub) { set_err("%s: NULL query offsets, scoring or substitution matrix", who); return SW_EINVAL; }
     if (nqueries < 0) { set_err("%s: negative query count", who); return SW_EINVAL; }
     if (qoffsets[0] < 0) { set_err("%s: qoffsets[0] = %lld is negative", who, (long long)qoffsets[0]); return SW_EINVAL; }
     int64_t maxq = 0;
@@ -113,7 +117,45 @@ int check_search_multi(const char* who, const int64_t* qoffsets, int64_t nquerie
         if (len < 1 || len > kMaxDim) { set_err("%s: query %lld has length %lld, out of range 1..%lld", who, (long long)q, (long long)len, (long long)kMaxDim); return SW_EINVAL; }
         maxq = std::max(maxq, len);
     }
+    *maxq_out = maxq;
+    return SW_OK;
+}
+
+int check_search_multi(const char* who, const int64_t* qoffsets, int64_t nqueries, int64_t longest_target, const sw_affine* sc, int64_t* maxq_out) {
+    if (!qoffsets || !sc || !sc->sub) { set_err("%s: NULL query offsets, scoring or substitution matrix", who); return SW_EINVAL; }
+    int64_t maxq = 0;
+    if (int rc = check_query_offsets(who, qoffsets, nqueries, &maxq)) return rc;
     if (int rc = check_affine_scoring(who, sc, maxq, longest_target)) return rc;
+    *maxq_out = maxq;
+    return SW_OK;
+}
+
+// The argument rules of a many-query PSSM call (sw_db_search_pssm and its twins, sw_search_pssm_multi_host): the offsets as above, the
+// scoring object, and the 24-bit bound that smax makes hold whatever the matrix holds.  O(nqueries) + O(nletters).  Builds the code
+// table: code[x] = the place of target byte x in a column, 255 (>= nletters: `other`) for a byte that is not among the letters --
+// with 256 letters every byte has a place and no code says `other`.
+int check_search_pssm(const char* who, const int64_t* qoffsets, int64_t nqueries, int64_t longest_target, const sw_pssm_scoring* sc, int64_t* maxq_out,
+                      unsigned char (&code)[256]) {
+    if (!qoffsets || !sc || !sc->letters) { set_err("%s: NULL query offsets, scoring or letters", who); return SW_EINVAL; }
+    int64_t maxq = 0;
+    if (int rc = check_query_offsets(who, qoffsets, nqueries, &maxq)) return rc;
+    if (sc->nletters < 1 || sc->nletters > 256) { set_err("%s: nletters = %d is out of range 1..256", who, sc->nletters); return SW_EINVAL; }
+    if (sc->smax < 0 || sc->smax > 127) { set_err("%s: smax = %d is out of range 0..127", who, sc->smax); return SW_EINVAL; }
+    if (sc->other < -128 || sc->other > sc->smax) { set_err("%s: other = %d is out of range -128..smax = %d", who, sc->other, sc->smax); return SW_EINVAL; }
+    bool seen[256] = {};
+    memset(code, 255, sizeof code);
+    for (int k = 0; k < sc->nletters; ++k) {
+        const int b = (unsigned char)sc->letters[k];
+        if (seen[b]) { set_err("%s: letter 0x%02x is listed twice", who, b); return SW_EINVAL; }
+        seen[b] = true;
+        code[b] = (unsigned char)k;
+    }
+    if (int rc = check_gap_costs(who, sc->gap_open, sc->gap_extend)) return rc;
+    if ((int64_t)sc->smax * std::min(maxq, longest_target) >= kScoreLimit) {
+        set_err("%s: smax = %d times min(longest query %lld, longest target %lld) reaches 2^24 (the 24-bit score of the arg-max key)", who, sc->smax,
+                (long long)maxq, (long long)longest_target);
+        return SW_EINVAL;
+    }
     *maxq_out = maxq;
     return SW_OK;
 }
@@ -169,6 +211,136 @@ static int64_t traceback_t(PT* P, int64_t m, int64_t max_pos, int64_t* path, int
         pos -= (pr == SW_DIAGONAL) ? m + 1 : (pr == SW_UP) ? m : 1;
     }
     return len;
+}
+
+// Gotoh's recurrence of one query against targets, row by row with one row of H and E kept (include/swhip.h states it); -inf is a
+// value no sum can reach from below (every E, F inside the matrix is at least gap_open + gap_extend >= -2^24).  s(j, y): the score of
+// query column j (1-based) against target byte y -- a table entry for a sequence query, a PSSM entry for a matrix.
+template <typename Score>
+static void search_targets(Score s, int64_t qlen, const char* db, const int64_t* offsets, int64_t ntargets, int64_t go, int64_t ge, sw_result* results) {
+    const int64_t M = qlen + 1;
+    constexpr int64_t NEG = -(1ll << 40);
+    std::vector<int64_t> Hrow((size_t)M), Erow((size_t)M);
+    for (int64_t k = 0; k < ntargets; ++k) {
+        const unsigned char* t = (const unsigned char*)db + offsets[k];
+        const int64_t len = offsets[k + 1] - offsets[k];
+        std::fill(Hrow.begin(), Hrow.end(), 0);
+        std::fill(Erow.begin(), Erow.end(), NEG);
+        int64_t best = 0, best_pos = 0;
+        for (int64_t i = 1; i <= len; ++i) {
+            const unsigned char y = t[i - 1];
+            int64_t diag = 0, left = 0, F = NEG;       // H[i-1][j-1], H[i][j-1], F[i][j-1]
+            for (int64_t j = 1; j <= qlen; ++j) {
+                const int64_t up = Hrow[(size_t)j];
+                const int64_t E = std::max(Erow[(size_t)j], up + go) + ge;
+                F = std::max(F, left + go) + ge;
+                const int64_t h = std::max<int64_t>({0, diag + s(j, y), E, F});
+                Erow[(size_t)j] = E;
+                Hrow[(size_t)j] = h;
+                diag = up;
+                left = h;
+                if (h > best) { best = h; best_pos = i * M + j; }   // row-major scan, strict: the lowest index among equals
+            }
+        }
+        results[k] = sw_result{best_pos, best, 0};
+    }
+}
+
+// The same recurrence with one direction byte per cell (bits 0-1: where H came from, 0 nothing positive / 1 diagonal / 2 E / 3 F,
+// compared in that order; bit 2: E[i][j] opened from H[i-1][j]; bit 3: F[i][j] opened from H[i][j-1]; opening wins a tie), then the
+// walk of the canonical alignment (include/swhip.h) from the arg-max, for the targets hits[0 .. nhits) (none longer than maxhit).
+template <typename Score>
+static void align_targets(Score s, int64_t qlen, const char* db, const int64_t* offsets, const int64_t* hits, int64_t nhits, int64_t maxhit, int64_t go,
+                          int64_t ge, sw_alignment* aln, char* ops, int64_t ops_cap) {
+    const int64_t M = qlen + 1;
+    constexpr int64_t NEG = -(1ll << 40);
+    std::vector<int64_t> Hrow((size_t)M), Erow((size_t)M);
+    std::vector<unsigned char> dir((size_t)(maxhit + 1) * (size_t)M);
+    std::string rev;
+    for (int64_t hx = 0; hx < nhits; ++hx) {
+        const unsigned char* t = (const unsigned char*)db + offsets[hits[hx]];
+        const int64_t len = offsets[hits[hx] + 1] - offsets[hits[hx]];
+        std::fill(Hrow.begin(), Hrow.end(), 0);
+        std::fill(Erow.begin(), Erow.end(), NEG);
+        int64_t best = 0, best_pos = 0;
+        for (int64_t i = 1; i <= len; ++i) {
+            const unsigned char y = t[i - 1];
+            unsigned char* d = dir.data() + i * M;
+            int64_t diag = 0, left = 0, F = NEG;       // H[i-1][j-1], H[i][j-1], F[i][j-1]
+            for (int64_t j = 1; j <= qlen; ++j) {
+                const int64_t up = Hrow[(size_t)j];
+                const bool eopen = up + go >= Erow[(size_t)j], fopen = left + go >= F;
+                const int64_t E = std::max(Erow[(size_t)j], up + go) + ge;
+                F = std::max(F, left + go) + ge;
+                const int64_t dg = diag + s(j, y);
+                const int64_t h = std::max<int64_t>({0, dg, E, F});
+                d[j] = (unsigned char)((h == 0 ? 0 : h == dg ? 1 : h == E ? 2 : 3) | (eopen ? 4 : 0) | (fopen ? 8 : 0));
+                Erow[(size_t)j] = E;
+                Hrow[(size_t)j] = h;
+                diag = up;
+                left = h;
+                if (h > best) { best = h; best_pos = i * M + j; }
+            }
+        }
+        int64_t i = best_pos / M, j = best_pos % M;
+        const int64_t i1 = i, j1 = j;
+        rev.clear();
+        int state = 0;                                 // 0: H, 2: E, 3: F
+        while (best > 0) {
+            const unsigned char c = dir[(size_t)(i * M + j)];
+            if (state == 0) {
+                if (i == 0 || j == 0 || (c & 3) == 0) break;
+                if ((c & 3) == 1) { rev.push_back('M'); --i; --j; }
+                else state = c & 3;
+            } else if (state == 2) {
+                rev.push_back('D');
+                if (c & 4) state = 0;
+                --i;
+            } else {
+                rev.push_back('I');
+                if (c & 8) state = 0;
+                --j;
+            }
+        }
+        const int64_t nops = (int64_t)rev.size();
+        aln[hx] = best > 0 ? sw_alignment{best_pos, best, j, i, j1, i1, nops} : sw_alignment{0, 0, 0, 0, 0, 0, 0};
+        if (ops && nops <= ops_cap) std::reverse_copy(rev.begin(), rev.end(), ops + hx * ops_cap);
+    }
+}
+
+// The score of a PSSM's column against a target byte (include/swhip.h): the clamped entry where the byte is among the letters.
+struct PssmScore {
+    const int8_t* col0;   // the query's first column
+    const unsigned char* code; int64_t nletters, other, smax;
+    int64_t operator()(int64_t j, unsigned char y) const {
+        const int k = code[y];
+        return k < nletters ? std::min<int64_t>(col0[(j - 1) * nletters + k], smax) : other;
+    }
+};
+
+// One query's used hits through `align` into rows of their own, copied to their places; every other entry of the row is all zeros and
+// its ops row is left alone (the rule of sw_db_align_affine_hits).  align(targets, n, maxhit, aln_rows, ops_rows, ops_cap), maxhit being
+// the longest target the row lists: the direction matrix is sized by the hits, not by the database.
+template <typename Align>
+static void align_hit_row(Align align, int64_t q, const int64_t* offsets, int64_t ntargets, const sw_hit* hits, const int64_t* nhits, int64_t top,
+                          sw_alignment* aln, char* ops, int64_t ops_cap) {
+    std::vector<int64_t> targets, where;
+    const int64_t used = nhits ? std::clamp<int64_t>(nhits[q], 0, top) : top;
+    for (int64_t r = 0; r < top; ++r) {
+        const uint64_t target = (uint64_t)hits[q * top + r].target;
+        if (r < used && target < (uint64_t)ntargets) { targets.push_back((int64_t)target); where.push_back(q * top + r); }
+        else aln[q * top + r] = sw_alignment{0, 0, 0, 0, 0, 0, 0};
+    }
+    if (targets.empty()) return;
+    std::vector<sw_alignment> row(targets.size());
+    std::vector<char> rows(ops ? targets.size() * (size_t)ops_cap : 0);
+    int64_t maxhit = 0;
+    for (int64_t t : targets) maxhit = std::max(maxhit, offsets[t + 1] - offsets[t]);
+    align(targets.data(), (int64_t)targets.size(), maxhit, row.data(), ops ? rows.data() : nullptr, ops ? ops_cap : 0);
+    for (size_t k = 0; k < targets.size(); ++k) {
+        aln[where[k]] = row[k];
+        if (ops && row[k].nops <= ops_cap) std::copy_n(rows.data() + k * (size_t)ops_cap, (size_t)row[k].nops, ops + where[k] * ops_cap);
+    }
 }
 
 extern "C" {
@@ -422,33 +594,10 @@ int sw_search_affine_host(const char* query, int64_t qlen, const char* db, const
     if (!query || !db || !offsets || !results || !scoring || ntargets < 0) { swh::set_err("sw_search_affine_host: NULL pointer or negative target count"); return SW_EINVAL; }
     int64_t maxlen = 0, nonempty = 0;
     if (int rc = swh::check_search_affine("sw_search_affine_host", qlen, offsets, ntargets, scoring, &maxlen, &nonempty)) return rc;
-    const int64_t go = scoring->gap_open, ge = scoring->gap_extend, M = qlen + 1;
-    constexpr int64_t NEG = -(1ll << 40);
-    std::vector<int64_t> Hrow((size_t)M), Erow((size_t)M);
     const unsigned char* q = (const unsigned char*)query;
-    for (int64_t k = 0; k < ntargets; ++k) {
-        const unsigned char* t = (const unsigned char*)db + offsets[k];
-        const int64_t len = offsets[k + 1] - offsets[k];
-        std::fill(Hrow.begin(), Hrow.end(), 0);
-        std::fill(Erow.begin(), Erow.end(), NEG);
-        int64_t best = 0, best_pos = 0;
-        for (int64_t i = 1; i <= len; ++i) {
-            const unsigned char y = t[i - 1];
-            int64_t diag = 0, left = 0, F = NEG;       // H[i-1][j-1], H[i][j-1], F[i][j-1]
-            for (int64_t j = 1; j <= qlen; ++j) {
-                const int64_t up = Hrow[(size_t)j];
-                const int64_t E = std::max(Erow[(size_t)j], up + go) + ge;
-                F = std::max(F, left + go) + ge;
-                const int64_t h = std::max<int64_t>({0, diag + scoring->sub->s[q[j - 1]][y], E, F});
-                Erow[(size_t)j] = E;
-                Hrow[(size_t)j] = h;
-                diag = up;
-                left = h;
-                if (h > best) { best = h; best_pos = i * M + j; }   // row-major scan, strict: the lowest index among equals
-            }
-        }
-        results[k] = sw_result{best_pos, best, 0};
-    }
+    const sw_submat* sub = scoring->sub;
+    search_targets([=](int64_t j, unsigned char y) { return (int64_t)sub->s[q[j - 1]][y]; }, qlen, db, offsets, ntargets, scoring->gap_open, scoring->gap_extend,
+                   results);
     return SW_OK;
 }
 
@@ -590,76 +739,23 @@ int sw_top_hits_pairs_host(const sw_pair* pairs, const sw_result* results, int64
     return SW_OK;
 }
 
-// The CPU leg of sw_align_affine_device: the same recurrence with one direction byte per cell (bits 0-1: where H came from, 0 nothing
-// positive / 1 diagonal / 2 E / 3 F, compared in that order; bit 2: E[i][j] opened from H[i-1][j]; bit 3: F[i][j] opened from
-// H[i][j-1]; opening wins a tie), then the walk of the canonical alignment (include/swhip.h) from the arg-max.
+// The CPU leg of sw_align_affine_device: align_targets (above) with the table's entry as the score of a cell.
 int sw_align_affine_host(const char* query, int64_t qlen, const char* db, const int64_t* offsets, int64_t ntargets, const int64_t* hits, int64_t nhits,
                          const sw_affine* scoring, sw_alignment* aln, char* ops, int64_t ops_cap) {
     if (!query || !db || !offsets || !scoring || ntargets < 0) { swh::set_err("sw_align_affine_host: NULL pointer or negative target count"); return SW_EINVAL; }
     int64_t maxlen = 0, nonempty = 0, maxhit = 0;
     if (int rc = swh::check_search_affine("sw_align_affine_host", qlen, offsets, ntargets, scoring, &maxlen, &nonempty)) return rc;
     if (int rc = swh::check_align_affine("sw_align_affine_host", offsets, ntargets, hits, nhits, aln, ops, ops_cap, &maxhit)) return rc;
-    const int64_t go = scoring->gap_open, ge = scoring->gap_extend, M = qlen + 1;
-    constexpr int64_t NEG = -(1ll << 40);
-    std::vector<int64_t> Hrow((size_t)M), Erow((size_t)M);
-    std::vector<unsigned char> dir((size_t)(maxhit + 1) * (size_t)M);
-    std::string rev;
     const unsigned char* q = (const unsigned char*)query;
-    for (int64_t hx = 0; hx < nhits; ++hx) {
-        const unsigned char* t = (const unsigned char*)db + offsets[hits[hx]];
-        const int64_t len = offsets[hits[hx] + 1] - offsets[hits[hx]];
-        std::fill(Hrow.begin(), Hrow.end(), 0);
-        std::fill(Erow.begin(), Erow.end(), NEG);
-        int64_t best = 0, best_pos = 0;
-        for (int64_t i = 1; i <= len; ++i) {
-            const unsigned char y = t[i - 1];
-            unsigned char* d = dir.data() + i * M;
-            int64_t diag = 0, left = 0, F = NEG;       // H[i-1][j-1], H[i][j-1], F[i][j-1]
-            for (int64_t j = 1; j <= qlen; ++j) {
-                const int64_t up = Hrow[(size_t)j];
-                const bool eopen = up + go >= Erow[(size_t)j], fopen = left + go >= F;
-                const int64_t E = std::max(Erow[(size_t)j], up + go) + ge;
-                F = std::max(F, left + go) + ge;
-                const int64_t dg = diag + scoring->sub->s[q[j - 1]][y];
-                const int64_t h = std::max<int64_t>({0, dg, E, F});
-                d[j] = (unsigned char)((h == 0 ? 0 : h == dg ? 1 : h == E ? 2 : 3) | (eopen ? 4 : 0) | (fopen ? 8 : 0));
-                Erow[(size_t)j] = E;
-                Hrow[(size_t)j] = h;
-                diag = up;
-                left = h;
-                if (h > best) { best = h; best_pos = i * M + j; }
-            }
-        }
-        int64_t i = best_pos / M, j = best_pos % M;
-        const int64_t i1 = i, j1 = j;
-        rev.clear();
-        int state = 0;                                 // 0: H, 2: E, 3: F
-        while (best > 0) {
-            const unsigned char c = dir[(size_t)(i * M + j)];
-            if (state == 0) {
-                if (i == 0 || j == 0 || (c & 3) == 0) break;
-                if ((c & 3) == 1) { rev.push_back('M'); --i; --j; }
-                else state = c & 3;
-            } else if (state == 2) {
-                rev.push_back('D');
-                if (c & 4) state = 0;
-                --i;
-            } else {
-                rev.push_back('I');
-                if (c & 8) state = 0;
-                --j;
-            }
-        }
-        const int64_t nops = (int64_t)rev.size();
-        aln[hx] = best > 0 ? sw_alignment{best_pos, best, j, i, j1, i1, nops} : sw_alignment{0, 0, 0, 0, 0, 0, 0};
-        if (ops && nops <= ops_cap) std::reverse_copy(rev.begin(), rev.end(), ops + hx * ops_cap);
-    }
+    const sw_submat* sub = scoring->sub;
+    align_targets([=](int64_t j, unsigned char y) { return (int64_t)sub->s[q[j - 1]][y]; }, qlen, db, offsets, hits, nhits, maxhit, scoring->gap_open,
+                  scoring->gap_extend, aln, ops, ops_cap);
     return SW_OK;
 }
 
 // The CPU leg of sw_db_align_affine_hits: per query the used entries of its row whose target lies inside the database go through
-// sw_align_affine_host in one call, into rows of their own, and are copied to their places; every other entry is all zeros and its ops
-// row is left alone.  Everything is checked before the first alignment.
+// align_targets in one call, into rows of their own, and are copied to their places (align_hit_row); every other entry is all zeros
+// and its ops row is left alone.  Everything is checked before the first alignment.
 int sw_align_affine_hits_host(const char* queries, const int64_t* qoffsets, int64_t nqueries, const char* db, const int64_t* offsets, int64_t ntargets,
                               const sw_affine* scoring, const sw_hit* hits, const int64_t* nhits, int64_t top, sw_alignment* aln, char* ops, int64_t ops_cap) {
     if (!queries || !qoffsets || !db || !offsets || !scoring || ntargets < 0) {
@@ -670,26 +766,69 @@ int sw_align_affine_hits_host(const char* queries, const int64_t* qoffsets, int6
     if (int rc = swh::check_targets("sw_align_affine_hits_host", 1, offsets, ntargets, &maxlen, &nonempty)) return rc;
     if (int rc = swh::check_search_multi("sw_align_affine_hits_host", qoffsets, nqueries, maxlen, scoring, &maxq)) return rc;
     if (int rc = swh::check_align_hits("sw_align_affine_hits_host", top, hits, aln, ops, ops_cap)) return rc;
-    std::vector<int64_t> targets, where;
-    std::vector<sw_alignment> row;
-    std::vector<char> rows;
+    const sw_submat* sub = scoring->sub;
     for (int64_t q = 0; q < nqueries; ++q) {
-        const int64_t used = nhits ? std::clamp<int64_t>(nhits[q], 0, top) : top;
-        targets.clear(); where.clear();
-        for (int64_t r = 0; r < top; ++r) {
-            const uint64_t target = (uint64_t)hits[q * top + r].target;
-            if (r < used && target < (uint64_t)ntargets) { targets.push_back((int64_t)target); where.push_back(q * top + r); }
-            else aln[q * top + r] = sw_alignment{0, 0, 0, 0, 0, 0, 0};
-        }
-        if (targets.empty()) continue;
-        row.resize(targets.size());
-        rows.resize(ops ? targets.size() * (size_t)ops_cap : 0);
-        if (int rc = sw_align_affine_host(queries + qoffsets[q], qoffsets[q + 1] - qoffsets[q], db, offsets, ntargets, targets.data(), (int64_t)targets.size(),
-                                          scoring, row.data(), ops ? rows.data() : nullptr, ops ? ops_cap : 0)) return rc;
-        for (size_t k = 0; k < targets.size(); ++k) {
-            aln[where[k]] = row[k];
-            if (ops && row[k].nops <= ops_cap) std::copy_n(rows.data() + k * (size_t)ops_cap, (size_t)row[k].nops, ops + where[k] * ops_cap);
-        }
+        const unsigned char* qq = (const unsigned char*)queries + qoffsets[q];
+        const int64_t qlen = qoffsets[q + 1] - qoffsets[q];
+        align_hit_row([&](const int64_t* targets, int64_t n, int64_t maxhit, sw_alignment* row, char* rows, int64_t cap) {
+            align_targets([=](int64_t j, unsigned char y) { return (int64_t)sub->s[qq[j - 1]][y]; }, qlen, db, offsets, targets, n, maxhit, scoring->gap_open,
+                          scoring->gap_extend, row, rows, cap);
+        }, q, offsets, ntargets, hits, nhits, top, aln, ops, ops_cap);
+    }
+    return SW_OK;
+}
+
+// ---- position-specific scoring matrices (include/swhip.h)
+
+// The CPU leg of sw_db_search_pssm: search_targets query after query into the query-major results, the score of a cell taken from the
+// matrix.  Everything is checked before the first query runs, so an error leaves `results` untouched.
+int sw_search_pssm_multi_host(const int8_t* pssm, const int64_t* qoffsets, int64_t nqueries, const char* db, const int64_t* offsets, int64_t ntargets,
+                              const sw_pssm_scoring* scoring, sw_result* results) {
+    const char* who = "sw_search_pssm_multi_host";
+    if (!pssm || !qoffsets || !db || !offsets || !results || !scoring || ntargets < 0) { swh::set_err("%s: NULL pointer or negative target count", who); return SW_EINVAL; }
+    int64_t maxlen = 0, nonempty = 0, maxq = 0;
+    unsigned char code[256];
+    if (int rc = swh::check_targets(who, 1, offsets, ntargets, &maxlen, &nonempty)) return rc;
+    if (int rc = swh::check_search_pssm(who, qoffsets, nqueries, maxlen, scoring, &maxq, code)) return rc;
+    for (int64_t q = 0; q < nqueries; ++q)
+        search_targets(PssmScore{pssm + qoffsets[q] * scoring->nletters, code, scoring->nletters, scoring->other, scoring->smax}, qoffsets[q + 1] - qoffsets[q], db,
+                       offsets, ntargets, scoring->gap_open, scoring->gap_extend, results + q * ntargets);
+    return SW_OK;
+}
+
+// The CPU leg of sw_db_align_pssm_hits: sw_align_affine_hits_host with the score of a cell taken from the matrix.
+int sw_align_pssm_hits_host(const int8_t* pssm, const int64_t* qoffsets, int64_t nqueries, const char* db, const int64_t* offsets, int64_t ntargets,
+                            const sw_pssm_scoring* scoring, const sw_hit* hits, const int64_t* nhits, int64_t top, sw_alignment* aln, char* ops, int64_t ops_cap) {
+    const char* who = "sw_align_pssm_hits_host";
+    if (!pssm || !qoffsets || !db || !offsets || !scoring || ntargets < 0) { swh::set_err("%s: NULL pointer or negative target count", who); return SW_EINVAL; }
+    int64_t maxlen = 0, nonempty = 0, maxq = 0;
+    unsigned char code[256];
+    if (int rc = swh::check_targets(who, 1, offsets, ntargets, &maxlen, &nonempty)) return rc;
+    if (int rc = swh::check_search_pssm(who, qoffsets, nqueries, maxlen, scoring, &maxq, code)) return rc;
+    if (int rc = swh::check_align_hits(who, top, hits, aln, ops, ops_cap)) return rc;
+    for (int64_t q = 0; q < nqueries; ++q) {
+        const PssmScore s{pssm + qoffsets[q] * scoring->nletters, code, scoring->nletters, scoring->other, scoring->smax};
+        const int64_t qlen = qoffsets[q + 1] - qoffsets[q];
+        align_hit_row([&](const int64_t* targets, int64_t n, int64_t maxhit, sw_alignment* row, char* rows, int64_t cap) {
+            align_targets(s, qlen, db, offsets, targets, n, maxhit, scoring->gap_open, scoring->gap_extend, row, rows, cap);
+        }, q, offsets, ntargets, hits, nhits, top, aln, ops, ops_cap);
+    }
+    return SW_OK;
+}
+
+// The PSSM that reproduces sequence queries under a table: column (q, j) holds the table's row of letter q[j] at the given letters.
+int sw_pssm_from_queries(const char* queries, const int64_t* qoffsets, int64_t nqueries, const sw_submat* sub, const char* letters, int32_t nletters,
+                         int8_t* out) {
+    const char* who = "sw_pssm_from_queries";
+    if (!queries || !qoffsets || !sub || !letters || !out || nqueries < 0) { swh::set_err("%s: NULL pointer or negative query count", who); return SW_EINVAL; }
+    if (nletters < 1 || nletters > 256) { swh::set_err("%s: nletters = %d is out of range 1..256", who, nletters); return SW_EINVAL; }
+    if (qoffsets[0] < 0) { swh::set_err("%s: qoffsets[0] = %lld is negative", who, (long long)qoffsets[0]); return SW_EINVAL; }
+    for (int64_t q = 0; q < nqueries; ++q)
+        if (qoffsets[q + 1] < qoffsets[q]) { swh::set_err("%s: qoffsets decrease at query %lld", who, (long long)q); return SW_EINVAL; }
+    for (int64_t g = qoffsets[0]; g < qoffsets[nqueries]; ++g) {
+        const int8_t* row = sub->s[(unsigned char)queries[g]];
+        int8_t* col = out + (g - qoffsets[0]) * nletters;
+        for (int k = 0; k < nletters; ++k) col[k] = row[(unsigned char)letters[k]];
     }
     return SW_OK;
 }

@@ -158,6 +158,12 @@ __global__ void sw_search_profile_submat_multi(const unsigned char* q, const Mul
 template <int C>
 __global__ void sw_search_affine_multi_wave(SearchMultiParams p);
 
+// sw_pssm.hip: the same profiles from a position-specific scoring matrix (sw_db_search_pssm and its twins)
+__global__ void sw_search_profile_pssm_multi(const signed char* pssm, const MultiQuery* tab, int64_t nq, int parts, signed char* prof, const unsigned char* code,
+                                             int nletters, int other, int smax);
+// ... its dynamic LDS: 256 columns of an odd number of dwords each (sw_pssm.hip says why), at most 64 KiB
+constexpr unsigned sw_pssm_profile_lds_bytes(int nletters) { return 1024u * (nletters > 252 ? 64u : (unsigned)(((nletters + 3) >> 2) | 1)); }
+
 // sw_search_pairs.hip: the scores of a device list of (query, target) pairs (sw_db_search_affine_pairs).  Per (chunk of the list, group
 // of queries) two binning launches turn the usable pairs into work items, one list per class, heaviest bucket first
 // (swp::plan_search_pairs); one launch of sw_search_affine_pairs_wave<C> per class scores them.
