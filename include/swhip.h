@@ -300,6 +300,15 @@ int sw_align_affine_host(const char* query, int64_t qlen, const char* db, const 
  *     SW_EINVAL: NULL pointers, nqueries < 0, decreasing qoffsets or qoffsets[0] < 0, a query of length 0 or above 2^20 - 1, the
  *     scoring errors of sw_search_affine_device with the 24-bit bound taken over the LONGEST query, a handle created on another
  *     context's device.  nqueries == 0 returns SW_OK and launches nothing; a handle without a non-empty target only zeroes the results.
+ *     LANES.  The option "search_lanes" (32, the default, or 16) chooses the kernel of this call, of sw_db_search_affine_top and of
+ *     their PSSM twins; every byte they write is the same under both.  Under 32 a wave scores one target on 32-bit lanes.  Under 16 a
+ *     wave scores TWO targets of one query on packed 16-bit lanes, for every query with
+ *         max(max_entry, 0) x min(its length, the handle's longest target) <= 32767
+ *     (max_entry: the table's largest entry; for the PSSM calls smax), provided that, for the whole call,
+ *         gap_open + 2 gap_extend >= -32768;
+ *     a query outside the rule runs on 32-bit lanes inside the same call, and refusals, workspaces, groups and chunks do not depend
+ *     on the option.  "last_search_multi_packed_launches" counts the packed launches among the "last_search_multi_launches" of the
+ *     last such call: 0 after any call under 32 and after a call that launched nothing.
  *   sw_search_affine_multi_host  the CPU leg: sw_search_affine_host query after query, the same result layout, no GPU needed; every
  *     argument is checked before the first query runs. */
 typedef struct sw_db sw_db;
@@ -766,7 +775,9 @@ int sw_synchronize(sw_ctx* ctx, void* stream);   /* waits for `stream`; reports 
  * buffer "debug_buf" names must hold at least three 8-byte words;
  * "search_profile_mib" (settable,
  * default 256) bounds the profiles of a group of sw_db_search_affine, "last_search_multi_groups", "last_search_multi_launches" and
- * "last_search_multi_grid" (workgroups of its last launch) describe the last such call; "search_results_mib" (settable, default 1024,
+ * "last_search_multi_grid" (workgroups of its last launch) describe the last such call; "search_lanes" (settable, 32 or 16, default
+ * 32) sends the queries of the many-query search whose scores fit 16 bits to the kernel that runs two targets per wave on packed lanes
+ * (sw_db_search_affine above has the rule) and "last_search_multi_packed_launches" counts those launches; "search_results_mib" (settable, default 1024,
  * 1..2^20) bounds the result rows a chunk of sw_db_search_affine_top holds, "last_search_top_chunks" and "last_search_top_kernel"
  * describe the last sw_db_search_affine_top / sw_top_hits_device call; "last_align_hits_launches", "last_align_hits_tiers",
  * "last_align_hits_slots" and "last_align_hits_lists" the last sw_db_align_affine_hits call; "search_pairs_chunk" (settable, default

@@ -50,6 +50,10 @@
   whole calls, medians and ranges; the results are compared on the device.  The margin is the range of the sw_db_search_affine repeats
   (pssm_within_margin is recorded, not gated).  *_profile_call_ms: the same two calls against a handle of ONE one-letter target -- the
   uploads, the profile launch of all 64 queries and a sweep of 64 cells: what the two calls do NOT share, measured without the sweeps
+  --lanes: data set (a) only, 64 queries of --qlen through one handle and the same buffers in one process: sw_db_search_affine under
+  "search_lanes" = 32 and = 16, ALTERNATING, and a second pair of legs for sw_db_search_affine_top with top 10, torch events around whole
+  calls, medians and ranges of --reps after --warmup, the ratio 16 / 32 of either pair.  lanes_identical is a byte comparison of the full
+  result tables and of the hit tables of the two modes at the timed size; the run fails if it is false
 GCUPS = query letters x target letters / time of the call (torch events, median of --reps after --warmup)."""
 import argparse
 import importlib
@@ -99,6 +103,7 @@ def main():
     ap.add_argument("--prefilter", action="store_true", help="data set (a) only: the ungapped pre-filter of 64 queries, alone and chained into the pair-list search, beside the full search")
     ap.add_argument("--prefiltered-top", action="store_true", help="data set (a) only: the top 10 of 64 queries by the full search and by pre-filter, rescoring and selection from the pair list")
     ap.add_argument("--pssm", action="store_true", help="data set (a) only: 64 PSSM queries derived from 64 sequence queries beside those, alternating")
+    ap.add_argument("--lanes", action="store_true", help="data set (a) only: 64 queries under search_lanes 32 and 16, alternating, full tables and top 10")
     ap.add_argument("--top", action="store_true", help="data set (a) only: the best 100 targets of 64 queries by the full table and by the selection on the device")
     args = ap.parse_args()
     rng = np.random.default_rng(2026)
@@ -593,6 +598,54 @@ def main():
         db.close()
         tiny.close()
 
+    def lanes_leg(packed, offs, nq=64, top=10):
+        d_db = torch.from_numpy(packed.copy()).to(dev)
+        db = eng.prepare_db(d_db, offs)
+        nt = len(offs) - 1
+        qoffs = np.arange(nq + 1, dtype=np.int64) * args.qlen
+        d_q = torch.from_numpy(rng.choice(PROTEIN, int(qoffs[-1])).astype(np.uint8)).to(dev)
+        scoring = (sub, -11, -1)
+        cells = float(qoffs[-1]) * float(offs[-1] - offs[0])
+        P = "lanes"
+        out[f"{P}_queries"], out[f"{P}_qlen"], out[f"{P}_targets"], out[f"{P}_top"], out[f"{P}_cells"] = nq, args.qlen, nt, top, int(cells)
+        tables = {lanes: torch.zeros(nq * nt * 3, dtype=torch.int64, device=dev) for lanes in (32, 16)}
+        hits = {lanes: (torch.zeros(nq * top * 3, dtype=torch.int64, device=dev), torch.zeros(nq, dtype=torch.int64, device=dev)) for lanes in (32, 16)}
+
+        def call(kind, lanes):
+            eng.set_option("search_lanes", lanes)
+            if kind == "search":
+                db.search_affine_device(d_q, qoffs, scoring, out=tables[lanes])
+            else:
+                db.search_affine_top_device(d_q, qoffs, scoring, top, 0, out=hits[lanes])
+
+        for kind in ("search", "top"):
+            ms = {32: [], 16: []}
+            for _ in range(max(1, args.warmup)):
+                for lanes in (32, 16):
+                    call(kind, lanes)
+            torch.cuda.synchronize()
+            for _ in range(args.reps):                                       # alternating: a drift of the device shows in both alike
+                for lanes in (32, 16):
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    e0.record()
+                    call(kind, lanes)
+                    e1.record()
+                    torch.cuda.synchronize()
+                    ms[lanes].append(e0.elapsed_time(e1))
+                    out[f"{P}_{kind}{lanes}_launches"] = eng.get_option("last_search_multi_launches")
+                    out[f"{P}_{kind}{lanes}_packed_launches"] = eng.get_option("last_search_multi_packed_launches")
+            for lanes in (32, 16):
+                med = float(np.median(ms[lanes]))
+                out[f"{P}_{kind}{lanes}_ms"], out[f"{P}_{kind}{lanes}_range_ms"] = round(med, 3), [round(min(ms[lanes]), 3), round(max(ms[lanes]), 3)]
+                out[f"{P}_{kind}{lanes}_gcups"] = round(cells / med / 1e6, 1)
+            out[f"{P}_{kind}_16_over_32"] = round(out[f"{P}_{kind}16_ms"] / out[f"{P}_{kind}32_ms"], 4)
+            out[f"{P}_{kind}_ranges_overlap"] = bool(out[f"{P}_{kind}16_range_ms"][1] >= out[f"{P}_{kind}32_range_ms"][0])
+        eng.set_option("search_lanes", 32)
+        torch.cuda.synchronize()
+        out[f"{P}_identical"] = bool(torch.equal(tables[32], tables[16]) and torch.equal(hits[32][0], hits[16][0]) and torch.equal(hits[32][1], hits[16][1])
+                                     and out[f"{P}_search16_packed_launches"] > 0 and out[f"{P}_search32_packed_launches"] == 0)
+        db.close()
+
     def align_ckpt_leg(q, packed, offs, nq=64):
         d_db = torch.from_numpy(packed.copy()).to(dev)
         db = eng.prepare_db(d_db, offs)
@@ -664,7 +717,9 @@ def main():
     out["a_letters"] = int(offs[-1])
     out["a_len_median"] = int(np.median(lens))
     out["a_len_max"] = int(lens.max())
-    if args.multi or args.top or args.align_hits or args.pairs or args.prefilter or args.prefiltered_top or args.pssm:
+    if args.multi or args.top or args.align_hits or args.pairs or args.prefilter or args.prefiltered_top or args.pssm or args.lanes:
+        if args.lanes:
+            lanes_leg(packed, offs)
         if args.pssm:
             pssm_leg(packed, offs)
         if args.pairs:
@@ -683,6 +738,8 @@ def main():
             top_leg(packed, offs)
         eng.close()
         print(json.dumps(out))
+        if args.lanes and not out["lanes_identical"]:
+            sys.exit("bench_search.py --lanes: lanes_identical is false")
         if args.pssm and not out["pssm_identical"]:
             sys.exit("bench_search.py --pssm: pssm_identical is false")
         if args.pairs:   # the required conditions of the pair-list call: a line that misses one is printed, and the run fails

@@ -665,7 +665,9 @@ class Database:
     def search_affine(self, queries, scoring):
         """Every query against every target (sw_db_search_affine).  queries: a list of sequences or a (packed uint8, int64 offsets) pair;
         scoring = (submat, gap_open, gap_extend) as for Engine.search_affine.  Returns the (nqueries, ntargets, 3) int64 numpy array of
-        (max_pos, max_score, path_len = 0), both axes in input order."""
+        (max_pos, max_score, path_len = 0), both axes in input order.  Engine.set_option("search_lanes", 16) runs two targets per
+        wave on packed 16-bit lanes for every query whose scores fit them (include/swhip.h has the rule); the result is the same
+        byte for byte."""
         eng = self.engine
         t = eng.torch
         qpacked, qoffs = _pack_targets(queries)
@@ -706,7 +708,8 @@ class Database:
         """Every PSSM query against every target (sw_db_search_pssm).  pssm: a list of per-query (columns, nletters) int8 matrices, or a
         ((total columns, nletters) int8, int64 column offsets) pair; scoring = (letters, other, smax, gap_open, gap_extend): entry k of a
         column scores the target byte letters[k], every other byte scores `other`, entries above smax count as smax.  Returns the
-        (nqueries, ntargets, 3) int64 numpy array of (max_pos, max_score, path_len = 0), as search_affine does."""
+        (nqueries, ntargets, 3) int64 numpy array of (max_pos, max_score, path_len = 0), as search_affine does.  "search_lanes" = 16
+        applies as there, with smax in the place of the table's largest entry."""
         d_m, qoffs = self._pssm_to_device(pssm, len(_as_seq(scoring[0])))
         res = self.search_pssm_device(d_m, qoffs, scoring)
         self.engine.synchronize()
@@ -805,7 +808,8 @@ class Database:
         """The best `top` targets of every query, selected on the device (sw_db_search_affine_top): the full result table never exists
         and only the hits come back.  queries and scoring as for search_affine.  Returns numpy (hits (nqueries, top, 3) int64 of
         (target, max_pos, max_score) in rank order -- score descending, then target ascending; unused entries (-1, 0, 0) --,
-        nhits (nqueries,) int64).  Only targets with max_score >= min_score qualify."""
+        nhits (nqueries,) int64).  Only targets with max_score >= min_score qualify.  The option "search_lanes" applies to the search
+        of every chunk as it does to search_affine; the hits are the same under 16 and 32."""
         eng = self.engine
         t = eng.torch
         qpacked, qoffs = _pack_targets(queries)
@@ -835,7 +839,7 @@ class Database:
 
     def search_pssm_top(self, pssm, scoring, top: int, min_score: int = 0):
         """The best `top` targets of every PSSM query (sw_db_search_pssm_top): pssm and scoring as for search_pssm, results as for
-        search_affine_top."""
+        search_affine_top; "search_lanes" = 16 applies as for search_pssm."""
         d_m, qoffs = self._pssm_to_device(pssm, len(_as_seq(scoring[0])))
         hits, nhits = self.search_pssm_top_device(d_m, qoffs, scoring, top, min_score)
         self.engine.synchronize()

@@ -12,6 +12,9 @@
 //                              --gap-open, --gap-extend and --align (one sw_db_align_affine_hits call on the device hit table) as for one query.  The K best hits per
 //                              query are selected on the device (sw_db_search_affine_top): only they are copied back
 //     ... --min-score S       with --all-queries: only hits with a score of at least S are printed (fewer than K where fewer qualify)
+//     ... --search-lanes 16|32  with --all-queries (and with --pssm): option "search_lanes" -- 16 runs two targets per wave on packed 16-bit lanes for
+//                              every query whose scores fit them (include/swhip.h has the rule), 32 (the default) one target per wave; the output is
+//                              the same byte for byte.  Not with --prefilter, --prefilter-hits or --pairs
 //     ... --prefilter-hits S  with --all-queries: the blocks of --all-queries (--top, --min-score, --align as there), the hits selected among the pairs whose
 //                              ungapped score is at least S: pre-filter, rescoring of the passing pairs and selection from that list in one call
 //                              (sw_db_search_affine_top_prefiltered), a fraction of the full search's time; the elapsed line says how many pairs passed.
@@ -33,7 +36,7 @@
 //                              bytes) with gap_open 0 and the gap of --scores: the reference's backtrack() path
 //     ... --align-checkpoint  with --align: option "align_checkpoint" = 2 -- hits (with --all-queries: tables) whose whole direction matrices do not
 //                              fit the workspace are aligned from checkpoint rows in bounded memory, in the same one call; the output is unchanged
-//   smithW --search --pssm FILE DB.fa --gap-open O --gap-extend E [--top K] [--min-score S] [--align]
+//   smithW --search --pssm FILE DB.fa --gap-open O --gap-extend E [--top K] [--min-score S] [--align] [--search-lanes 16|32]
 //                              the ONE query is a position-specific scoring matrix, PSI-BLAST's ASCII PSSM (sw_read_pssm), searched through a prepared
 //                              handle (sw_db_search_pssm_top, sw_db_align_pssm_hits); the output is that of --all-queries for one record, the Q line of an
 //                              alignment the matrix's consensus (per column the first letter with the largest entry)
@@ -232,7 +235,7 @@ static int search_main(const char* qpath, long long rec, const char* dbpath, lon
 // --prefilter-hits S (prefilter_hits > 0): sw_db_search_affine_top_prefiltered takes the place of sw_db_search_affine_top -- the hits are
 // selected among the pairs whose ungapped score reaches S, on the device from the rescored pair list; everything else is the same.
 static int search_all_main(const char* qpath, const char* dbpath, long long top, long long min_score, const sw_scores& sc, const AffineArgs& af, bool align,
-                           bool align_ckpt, long long prefilter_hits = 0) {
+                           bool align_ckpt, long long prefilter_hits = 0, int search_lanes = 32) {
     int64_t nq = 0, qtotal = 0, nrec = 0, total = 0;
     CHECK(sw_read_fasta_db(qpath, nullptr, 0, nullptr, 0, &nq, &qtotal));
     std::vector<char> qs((size_t)qtotal + 1);
@@ -252,6 +255,7 @@ static int search_all_main(const char* qpath, const char* dbpath, long long top,
     CHECK(sw_create(0, &ctx));
     // --align-checkpoint: a table the one call would refuse for its worst pair goes through it checkpointed instead of query by query
     if (align_ckpt) CHECK(sw_set_option(ctx, "align_checkpoint", 2));
+    CHECK(sw_set_option(ctx, "search_lanes", search_lanes));
     void *d_q = nullptr, *d_db = nullptr, *d_res = nullptr, *d_hits = nullptr, *d_nhits = nullptr, *d_npairs = nullptr;
     // the pair list of --prefilter-hits: every pair, or as many as "search_results_mib" lets the call hold (56 bytes each)
     const int64_t pairs_cap = std::min<int64_t>(nq * nrec, (sw_get_option(ctx, "search_results_mib") << 20) / 56);
@@ -356,7 +360,8 @@ static int search_all_main(const char* qpath, const char* dbpath, long long top,
 // of one record.  Bytes the matrix has no row entry for score the file's smallest entry (the rule of sw_read_submat) and smax is its
 // largest one, so nothing is clamped; the query line of an alignment is the matrix's consensus: per column the first letter with the
 // largest entry, '|' where the target has that letter.
-static int search_pssm_main(const char* ppath, const char* dbpath, long long top, long long min_score, const AffineArgs& af, bool align, bool align_ckpt) {
+static int search_pssm_main(const char* ppath, const char* dbpath, long long top, long long min_score, const AffineArgs& af, bool align, bool align_ckpt,
+                            int search_lanes = 32) {
     char letters[256];
     int32_t nletters = 0;
     int64_t ncols = 0, nrec = 0, total = 0;
@@ -381,6 +386,7 @@ static int search_pssm_main(const char* ppath, const char* dbpath, long long top
     sw_ctx* ctx = nullptr;
     CHECK(sw_create(0, &ctx));
     if (align_ckpt) CHECK(sw_set_option(ctx, "align_checkpoint", 2));
+    CHECK(sw_set_option(ctx, "search_lanes", search_lanes));
     void *d_pssm = nullptr, *d_db = nullptr, *d_res = nullptr, *d_hits = nullptr, *d_nhits = nullptr;
     const size_t nres = on_device ? 1 : (size_t)std::max<int64_t>(1, nrec), nhit = (size_t)std::max<long long>(1, K);
     CHECK(sw_device_malloc(ctx, pssm.size() + 16, &d_pssm));
@@ -634,6 +640,8 @@ int main(int argc, char** argv) {
     const char *pairs_path = nullptr, *pssm_path = nullptr;
     AffineArgs af;
     bool align = false, all_queries = false, align_ckpt = false;
+    int search_lanes = 32;
+    bool has_search_lanes = false;
     sw_scores sc = {3, -3, -2};
     int npos = 0;
     for (int ai = 1; ai < argc; ++ai) {
@@ -658,6 +666,7 @@ int main(int argc, char** argv) {
         else if (f == "--min-score" && ai + 1 < argc) { int v = 0; if (!parse_int("--min-score", argv[++ai], &v)) return 2; min_score = v; has_min_score = true; }
         else if (f == "--prefilter" && ai + 1 < argc) { int v = 0; if (!parse_int("--prefilter", argv[++ai], &v)) return 2; prefilter = v; has_prefilter = true; }
         else if (f == "--prefilter-hits" && ai + 1 < argc) { int v = 0; if (!parse_int("--prefilter-hits", argv[++ai], &v)) return 2; prefilter_hits = v; has_prefilter_hits = true; }
+        else if (f == "--search-lanes" && ai + 1 < argc) { if (!parse_int("--search-lanes", argv[++ai], &search_lanes)) return 2; has_search_lanes = true; }
         else if (f == "--matrix" && ai + 1 < argc) { af.matrix = argv[++ai]; af.on = true; }
         else if (f == "--gap-open" && ai + 1 < argc) { if (!parse_int("--gap-open", argv[++ai], &af.open)) return 2; af.has_open = af.on = true; }
         else if (f == "--gap-extend" && ai + 1 < argc) { if (!parse_int("--gap-extend", argv[++ai], &af.extend)) return 2; af.has_extend = true; }
@@ -668,17 +677,22 @@ int main(int argc, char** argv) {
         else if (f == "--record-b" && ai + 1 < argc) rec_b = strtoll(argv[++ai], nullptr, 10);
         else if (f == "--seed" && ai + 1 < argc) seed = (unsigned)strtoul(argv[++ai], nullptr, 10);
         else if (f == "--scores" && ai + 3 < argc) { sc.match = atoi(argv[++ai]); sc.mismatch = atoi(argv[++ai]); sc.gap = atoi(argv[++ai]); }
-        else { fprintf(stderr, "usage: smithW [<cols> <rows> | --fasta A.fa B.fa [--record-a I] [--record-b J] | --search QUERY.fa DB.fa [--record-a I] [--top K] [--all-queries [--min-score S] [--prefilter S | --prefilter-hits S]] [--pairs FILE] [--matrix FILE] [--gap-open O] [--gap-extend E] [--align [--align-checkpoint]] | --search --pssm FILE DB.fa --gap-open O --gap-extend E [--top K] [--min-score S] [--align]] [--seed N] [--dump | --dump-labels] [--h64] [--no-backtrack] [--scores M X G] [--gpus N | --devices 0,1,..] [--p8]\n"); return 2; }
+        else { fprintf(stderr, "usage: smithW [<cols> <rows> | --fasta A.fa B.fa [--record-a I] [--record-b J] | --search QUERY.fa DB.fa [--record-a I] [--top K] [--all-queries [--min-score S] [--prefilter S | --prefilter-hits S] [--search-lanes 16|32]] [--pairs FILE] [--matrix FILE] [--gap-open O] [--gap-extend E] [--align [--align-checkpoint]] | --search --pssm FILE DB.fa --gap-open O --gap-extend E [--top K] [--min-score S] [--align] [--search-lanes 16|32]] [--seed N] [--dump | --dump-labels] [--h64] [--no-backtrack] [--scores M X G] [--gpus N | --devices 0,1,..] [--p8]\n"); return 2; }
     }
     if (npos == 1) { fprintf(stderr, "smithW: <cols> needs <rows>\n"); return 2; }
     if (align_ckpt && !(search_q && align)) { fprintf(stderr, "smithW: --align-checkpoint goes with --search --align\n"); return 2; }
+    if (has_search_lanes) {   // the many-query search alone has the two kinds of lanes
+        if (search_lanes != 16 && search_lanes != 32) { fprintf(stderr, "smithW: --search-lanes takes 16 or 32, got %d\n", search_lanes); return 2; }
+        if (!pssm_path && !(search_q && all_queries)) { fprintf(stderr, "smithW: --search-lanes goes with --search --all-queries or --search --pssm\n"); return 2; }
+        if (has_prefilter || has_prefilter_hits || pairs_path) { fprintf(stderr, "smithW: --search-lanes does not go with --prefilter / --prefilter-hits / --pairs\n"); return 2; }
+    }
     if (pssm_path) {   // the matrix is the query and the scoring at once
         if (af.matrix) { fprintf(stderr, "smithW: --pssm does not go with --matrix\n"); return 2; }
         if (all_queries) { fprintf(stderr, "smithW: --pssm does not go with --all-queries (the file is the one query)\n"); return 2; }
         if (pairs_path) { fprintf(stderr, "smithW: --pssm does not go with --pairs\n"); return 2; }
         if (has_prefilter || has_prefilter_hits) { fprintf(stderr, "smithW: --pssm does not go with --prefilter / --prefilter-hits\n"); return 2; }
         if (!af.has_open || !af.has_extend) { fprintf(stderr, "smithW: --pssm needs --gap-open O and --gap-extend E\n"); return 2; }
-        return search_pssm_main(pssm_path, search_db, top, min_score, af, align, align_ckpt);
+        return search_pssm_main(pssm_path, search_db, top, min_score, af, align, align_ckpt, search_lanes);
     }
     if (search_q) {
         if (af.on && !af.matrix && (sc.match < -128 || sc.match > 127 || sc.mismatch < -128 || sc.mismatch > 127)) {   // (sw_submat_match would clamp them)
@@ -725,7 +739,7 @@ int main(int argc, char** argv) {
                 fprintf(stderr, "smithW: --all-queries without --matrix needs --scores M X within -128..127 (a table of signed bytes), got %d %d\n", sc.match, sc.mismatch);
                 return 2;
             }
-            return search_all_main(search_q, search_db, top, min_score, sc, af, align, align_ckpt, prefilter_hits);
+            return search_all_main(search_q, search_db, top, min_score, sc, af, align, align_ckpt, prefilter_hits, search_lanes);
         }
         if (has_min_score) { fprintf(stderr, "smithW: --min-score goes with --search --all-queries\n"); return 2; }
         return search_main(search_q, rec_a, search_db, top, sc, af, align, align_ckpt);

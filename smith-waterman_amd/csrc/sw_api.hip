@@ -142,6 +142,11 @@ int sw_set_option(sw_ctx* c, const char* name, int64_t v) {
         c->opt_prefilter_lanes = v;
         return SW_OK;
     }
+    if (!strcmp(name, "search_lanes")) {
+        if (v != 32 && v != 16) { set_err("search_lanes must be 32 (one target per wave) or 16 (two targets per wave on packed lanes where a query is eligible)"); return SW_EINVAL; }
+        c->opt_search_lanes = v;
+        return SW_OK;
+    }
     if (!strcmp(name, "placement_budget_ms")) { c->opt_place_budget_ms = v > 0 ? v : 1500; return SW_OK; }
     if (!strcmp(name, "placement_hold_gib")) { c->opt_place_hold_gib = v < 0 ? 0 : (v > 128 ? 128 : v); return SW_OK; }
     if (!strcmp(name, "probe_foreign_pairs")) { c->opt.probe_foreign_pairs = v ? 1 : 0; return SW_OK; }
@@ -213,6 +218,8 @@ int64_t sw_get_option(sw_ctx* c, const char* name) {
     if (!strcmp(name, "last_search_multi_groups")) return c->last_search_multi_groups;
     if (!strcmp(name, "last_search_multi_launches")) return c->last_search_multi_launches;
     if (!strcmp(name, "last_search_multi_grid")) return c->last_search_multi_grid;
+    if (!strcmp(name, "search_lanes")) return c->opt_search_lanes;
+    if (!strcmp(name, "last_search_multi_packed_launches")) return c->last_search_multi_packed_launches;
     if (!strcmp(name, "search_results_mib")) return c->opt_search_results_mib;
     if (!strcmp(name, "last_search_top_chunks")) return c->last_search_top_chunks;
     if (!strcmp(name, "last_search_top_kernel")) return c->last_search_top_kernel;

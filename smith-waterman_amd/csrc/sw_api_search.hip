@@ -42,6 +42,15 @@ static constexpr Indexed<SearchMultiKernel> kSearchMulti[] = {
 };
 static_assert(std::size(kSearchMulti) == swp::kSearchMultiKernels && at_their_indices(kSearchMulti));
 
+// the instantiations of its packed form (sw_search_multi16.hip: two targets per wave), picked by swp::plan_search_multi_lanes
+using SearchMultiPackedKernel = void (*)(swk::SearchMultiPackedParams);
+static constexpr Indexed<SearchMultiPackedKernel> kSearchMultiPacked[] = {
+    {swp::search_multi_kernel_index(4), swk::sw_search_multi_pk_wave<4>},
+    {swp::search_multi_kernel_index(8), swk::sw_search_multi_pk_wave<8>},
+    {swp::search_multi_kernel_index(16), swk::sw_search_multi_pk_wave<16>},
+};
+static_assert(std::size(kSearchMultiPacked) == swp::kSearchMultiKernels && at_their_indices(kSearchMultiPacked));
+
 // the instantiations of the hit-table alignment kernel (sw_align_hits.hip), picked by swp::plan_align_hits
 using AlignHitsKernel = void (*)(swk::AlignHitsParams);
 static constexpr Indexed<AlignHitsKernel> kAlignHits[] = {
@@ -195,6 +204,14 @@ struct QuerySource {
     const signed char* d_pssm = nullptr; int nletters = 0, other = 0, smax = 0; unsigned char code[256] = {};   // a PSSM
     int gap_open = 0, gap_extend = 0;
     bool pssm() const { return d_pssm != nullptr; }
+    // what bounds a profile byte from above: the table's largest entry; a PSSM's smax (entries are clamped to it, other <= smax)
+    int max_entry() const {
+        if (pssm()) return smax;
+        int m = -128;
+        for (int x = 0; x < 256; ++x)
+            for (int y = 0; y < 256; ++y) m = std::max<int>(m, sub->s[x][y]);
+        return m;
+    }
     static QuerySource sequences(const char* d_queries, const sw_affine* sc) {
         QuerySource s;
         s.d_queries = d_queries; s.sub = sc->sub; s.gap_open = sc->gap_open; s.gap_extend = sc->gap_extend;
@@ -254,16 +271,25 @@ static int run_search_multi(sw_ctx* c, const sw_db* db, const QuerySource& src, 
                             hipStream_t stream) {
     // empty targets keep the zeros: {0, 0, 0}
     HIP_TRY(hipMemsetAsync(d_results, 0, (size_t)nqueries * (size_t)db->ntargets * sizeof(sw_result), stream));
+    c->last_search_multi_packed_launches = 0;   // (a call that launches no kernel reports none)
     if (db->nonempty == 0) return SW_OK;
     if (int rc = occupancy_once(kSearchMulti, c->search_multi_per_cu, c->search_multi_per_cu_known)) return rc;
+    const bool lanes16 = c->opt_search_lanes == 16;
+    if (lanes16)
+        if (int rc = occupancy_once(kSearchMultiPacked, c->search_multi_packed_per_cu, c->search_multi_packed_per_cu_known)) return rc;
     const std::vector<int64_t> qlens = query_lengths(qoffsets, nqueries);
-    swp::SearchMultiJob mj;
+    swp::SearchMultiLanesJob mj;
     mj.qlens = qlens.data(); mj.nqueries = nqueries; mj.longest = db->longest; mj.nonempty = db->nonempty; mj.num_cus = c->num_cus;
     mj.budget_bytes = c->opt_search_profile_mib << 20;
     std::copy(std::begin(c->search_multi_per_cu), std::end(c->search_multi_per_cu), mj.per_cu);
-    const swp::SearchMultiPlan plan = swp::plan_search_multi(mj);
-    for (const swp::MultiLaunch& l : plan.launch)
-        if (c->search_multi_per_cu[l.kernel] < 1) { set_err("the many-query search kernel does not fit a CU on this device"); return SW_EDEVICE; }
+    mj.lanes = (int)c->opt_search_lanes; mj.gap_open = src.gap_open; mj.gap_extend = src.gap_extend;
+    if (lanes16) {   // (the 32-bit plan asks for neither)
+        std::copy(std::begin(c->search_multi_packed_per_cu), std::end(c->search_multi_packed_per_cu), mj.packed_per_cu);
+        mj.max_entry = src.max_entry();
+    }
+    const swp::SearchMultiLanesPlan plan = swp::plan_search_multi_lanes(mj);
+    for (const swp::MultiLanesLaunch& l : plan.launch)
+        if ((l.packed ? c->search_multi_packed_per_cu : c->search_multi_per_cu)[l.kernel] < 1) { set_err("the many-query search kernel does not fit a CU on this device"); return SW_EDEVICE; }
     if (int rc = stage_search_call(c, stream, 0, plan.prof_need, plan.bnd_need, true)) return rc;
     if (int rc = upload_query_table(c, stream, plan.table, qoffsets, src)) return rc;
     size_t li = 0;
@@ -271,7 +297,24 @@ static int run_search_multi(sw_ctx* c, const sw_db* db, const QuerySource& src, 
         const swp::MultiGroup& grp = plan.group[g];
         if (int rc = launch_group_profiles(c, stream, src, grp)) return rc;
         for (; li < plan.launch.size() && plan.launch[li].group == (int)g; ++li) {
-            const swp::MultiLaunch& l = plan.launch[li];
+            const swp::MultiLanesLaunch& l = plan.launch[li];
+            if (l.packed) {   // two targets per wave: the ranks rank0 .. rank0 + nranks - 1 in pairs
+                swk::SearchMultiPackedParams kp;
+                memset(&kp, 0, sizeof kp);
+                kp.db = (const unsigned char*)db->d_db;
+                kp.items = db->d_items; kp.rank0 = l.rank0; kp.nranks = l.nranks;
+                kp.queries = c->d_mq + l.q0; kp.nq = (unsigned)l.nq; kp.nitems = l.items;
+                kp.prof = c->d_sprof; kp.ntargets = db->ntargets;
+                kp.ge = src.gap_extend; kp.goe = src.gap_open + src.gap_extend;
+                kp.bnd = l.bnd_per ? c->d_sbnd : nullptr; kp.bnd_per = l.bnd_per;
+                kp.counter = c->d_sctr;
+                kp.results = d_results;
+                HIP_TRY(hipMemsetAsync(c->d_sctr, 0, 4, stream));
+                hipLaunchKernelGGL(kSearchMultiPacked[l.kernel].k, dim3((unsigned)l.grid), dim3(256), 0, stream, kp);
+                HIP_TRY(hipGetLastError());
+                c->last_search_multi_grid = l.grid;
+                continue;
+            }
             swk::SearchMultiParams sp;
             memset(&sp, 0, sizeof sp);
             sp.db = (const unsigned char*)db->d_db;
@@ -289,6 +332,7 @@ static int run_search_multi(sw_ctx* c, const sw_db* db, const QuerySource& src, 
         }
     }
     c->last_search_multi_groups = (int64_t)plan.group.size(); c->last_search_multi_launches = (int64_t)plan.launch.size();
+    c->last_search_multi_packed_launches = plan.packed_launches;
     return SW_OK;
 }
 
@@ -597,6 +641,7 @@ int sw_db_info(const sw_db* db, int64_t* ntargets, int64_t* nonempty, int64_t* l
 
 // sw_db_search_affine / sw_db_search_pssm behind their checks: the stream's turn on the device and the search.
 static int db_search_call(sw_ctx* c, const sw_db* db, const QuerySource& src, const int64_t* qoffsets, int64_t nqueries, sw_result* d_results, void* stream_) {
+    c->last_search_multi_packed_launches = 0;   // (a call that launches no kernel reports none)
     if (nqueries == 0 || db->ntargets == 0) return SW_OK;
     hipStream_t stream = (hipStream_t)stream_;
     HIP_TRY(hipSetDevice(c->device));
@@ -652,6 +697,7 @@ static int db_search_top_call(const char* who, sw_ctx* c, const sw_db* db, const
     hipStream_t stream = (hipStream_t)stream_;
     swp::SearchTopPlan plan;
     if (int rc = plan_top_call(c, who, nqueries, db->ntargets, top, d_hits, d_nhits, c->opt_search_results_mib << 20, plan)) return rc;
+    c->last_search_multi_packed_launches = 0;   // (a call that launches no kernel reports none)
     if (nqueries == 0) return SW_OK;
     DevOrder order(c, stream, false);
     if (order.rc) return order.rc;

@@ -138,6 +138,11 @@ struct SW_HIDDEN sw_ctx {
     int64_t last_search_multi_groups = 0, last_search_multi_launches = 0, last_search_multi_grid = 0;   // of the last call; the grid of its last launch
     int search_multi_per_cu[swp::kSearchMultiKernels] = {};     // occupancy of every sw_search_affine_multi_wave instantiation at 256 threads ...
     bool search_multi_per_cu_known = false;                     // ... queried at the first call
+    // the same search on packed 16-bit lanes (sw_search_multi16.hip): "search_lanes" (32 / 16), the packed launches of the last call
+    int64_t opt_search_lanes = 32;
+    int64_t last_search_multi_packed_launches = 0;
+    int search_multi_packed_per_cu[swp::kSearchMultiKernels] = {};   // occupancy of every sw_search_multi_pk_wave instantiation at 256 threads ...
+    bool search_multi_packed_per_cu_known = false;              // ... queried at the first call
     // a pair list against a prepared database (sw_db_search_affine_pairs): the items of a chunk and the control words of a (chunk, group);
     // the profiles, the boundary columns and the query table are those of the calls above (the table carries entry_of behind its entries)
     swk::SearchPairItem* d_spitems = nullptr; size_t spitems_cap = 0;   // (bytes)

@@ -158,6 +158,25 @@ __global__ void sw_search_profile_submat_multi(const unsigned char* q, const Mul
 template <int C>
 __global__ void sw_search_affine_multi_wave(SearchMultiParams p);
 
+// sw_search_multi16.hip: the same search with two targets per wave on packed 16-bit lanes ("search_lanes" = 16); the launches and the
+// queries that may run here are swp::plan_search_multi_lanes's
+struct SearchMultiPackedParams {
+    const unsigned char* db;             // the targets back to back
+    const SearchItem* items;             // the handle's schedule: every non-empty target, longest first
+    int64_t rank0, nranks;               // the target ranks of this launch: rank0 is even, an odd nranks leaves the last rank without a partner
+    const MultiQuery* queries;           // the launch's queries (entries of the call's table)
+    unsigned int nq;                     // ... how many: item w = (ranks rank0 + 2 (w / nq) and the next, w % nq)
+    int64_t nitems;                      // nq * ceil(nranks / 2), below 2^31
+    const signed char* prof;             // the group's profiles, query t at its prof_off
+    int64_t ntargets;                    // row stride of the results
+    int ge, goe;                         // gap_extend, gap_open + gap_extend (both <= 0, gap_open + 2 gap_extend >= -32768)
+    int* bnd; int64_t bnd_per;           // per resident wave: boundary pairs (H, F) of both targets between strips (ints), as SearchMultiParams
+    unsigned int* counter;               // next item (zero at launch)
+    sw_result* results;                  // query-major, nqueries x ntargets, the caller's order
+};
+template <int C>
+__global__ void sw_search_multi_pk_wave(SearchMultiPackedParams p);
+
 // sw_pssm.hip: the same profiles from a position-specific scoring matrix (sw_db_search_pssm and its twins)
 __global__ void sw_search_profile_pssm_multi(const signed char* pssm, const MultiQuery* tab, int64_t nq, int parts, signed char* prof, const unsigned char* code,
                                              int nletters, int other, int smax);

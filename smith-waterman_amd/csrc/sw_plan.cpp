@@ -556,6 +556,63 @@ PrefilterPlan plan_prefilter(const PrefilterJob& j) {
     return f;
 }
 
+// The many-query search with a choice of lanes.  The table and the groups come from plan_search_multi itself (asked for a handle without
+// targets, it plans no launch), with the 32-bit kernels' occupancy, so the classes do not depend on the lanes; per (group, class) the
+// packed queries move to the front, every entry keeping its profile's place.  With no packed query every class is one part, and the
+// loops below are plan_search_multi's.
+SearchMultiLanesPlan plan_search_multi_lanes(const SearchMultiLanesJob& j) {
+    SearchMultiLanesPlan f;
+    SearchMultiJob mj = j;
+    mj.nonempty = 0;
+    SearchMultiPlan m = plan_search_multi(mj);
+    f.table = std::move(m.table);
+    f.group = std::move(m.group);
+    f.prof_need = m.prof_need;
+    const int64_t max_items = std::max<int64_t>(1, std::min(j.max_items, kMultiMaxItems));
+    auto klass = [](const swk::MultiQuery& d) { return d.qpad / d.nstrips / 64 / 8; };   // columns per lane 4, 8, 16 -> 0, 1, 2
+    for (size_t g = 0; g < f.group.size(); ++g) {
+        const int64_t g0 = f.group[g].q0, g1 = g0 + f.group[g].nq;
+        for (int64_t a = g0; a < g1;) {
+            const int k = klass(f.table[(size_t)a]), C = k == 0 ? 4 : 8 * k;
+            int64_t b = a;
+            while (b < g1 && klass(f.table[(size_t)b]) == k) ++b;
+            // (the packed kernel of 16 columns per lane is taken where it keeps the workgroups on a CU that the 32-bit one needs)
+            const bool fits = j.packed_per_cu[k] >= (C == 16 ? kAffineC16MinPerCu : 1);
+            auto packed = [&](const swk::MultiQuery& d) { return fits && search_multi_packed(j.max_entry, d.qlen, j.longest, j.gap_open, j.gap_extend, j.lanes); };
+            const int64_t mid = std::stable_partition(f.table.begin() + a, f.table.begin() + b, packed) - f.table.begin();
+            for (int side = 0; side < 2 && j.nonempty > 0; ++side) {
+                const bool pk = side == 0;
+                const int64_t s0 = pk ? a : mid, s1 = pk ? mid : b;
+                const int per_cu = pk ? j.packed_per_cu[k] : j.per_cu[k];
+                for (int64_t qa = s0; qa < s1;) {
+                    const int64_t nq = std::min(s1 - qa, max_items);
+                    // target ranks of a launch: as many as keep its items inside max_items; packed launches take them in pairs
+                    const int64_t ranks_per = pk ? 2 * (max_items / nq) : max_items / nq;
+                    int64_t strips = 1;
+                    for (int64_t t = qa; t < qa + nq; ++t) strips = std::max<int64_t>(strips, f.table[(size_t)t].nstrips);
+                    for (int64_t r0 = 0; r0 < j.nonempty; r0 += ranks_per) {
+                        MultiLanesLaunch l;
+                        l.group = (int)g; l.C = C; l.kernel = k; l.packed = pk;
+                        l.q0 = qa; l.nq = nq;
+                        l.rank0 = r0; l.nranks = std::min(ranks_per, j.nonempty - r0);
+                        l.items = l.nq * (pk ? (l.nranks + 1) / 2 : l.nranks);
+                        l.bnd_per = 2 * boundary_ints(strips, j.longest);
+                        l.grid = std::min<int64_t>((int64_t)per_cu * j.num_cus, (l.items + 3) / 4);
+                        if (l.bnd_per) l.grid = std::min<int64_t>(l.grid, kSearchBndBytes / (l.bnd_per * 4 * 4));
+                        l.grid = std::max<int64_t>(1, l.grid);
+                        f.bnd_need = std::max(f.bnd_need, (size_t)(l.grid * 4 * l.bnd_per));
+                        f.packed_launches += pk;
+                        f.launch.push_back(l);
+                    }
+                    qa += nq;
+                }
+            }
+            a = b;
+        }
+    }
+    return f;
+}
+
 // The best `top` of every row.  Every row has the same length, so the chunks are uniform and the geometry of a row is decided once.
 // The passes take kTopDigitBits bits each from the top of the key down; the last one takes what is left.
 SearchTopPlan plan_search_top(const SearchTopJob& j) {

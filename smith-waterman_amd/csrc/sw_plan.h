@@ -335,6 +335,49 @@ struct PrefilterPlan {
 
 PrefilterPlan plan_prefilter(const PrefilterJob& job);
 
+// ---- the many-query search with a choice of lanes ("search_lanes"; sw_search_multi16.hip): sw_search_multi_pk_wave<C> for C = 4, 8, 16
+// runs two targets of a query per wave on packed 16-bit lanes; its index in kSearchMultiPacked (sw_api_search.hip, which checks its
+// order against it at compile time) is search_multi_kernel_index(C).
+// Queries: the groups, the classes and every table entry are plan_search_multi's for the 32-bit kernels' occupancy, whatever the lanes
+// (the profiles lie where they lie there); inside a (group, class) the entries of the queries that run packed come first, input order
+// within either part.
+// Packed: under lanes = 16 a query runs on 16-bit lanes where
+//     max(max_entry, 0) x min(qlen, longest target) <= kPrefilterPackedMax   and   gap_open + 2 gap_extend >= kSearchPackedGapMin
+// (max_entry: the largest entry of the table, or a PSSM's smax) -- the header of sw_search_multi16.hip proves that no half wraps under
+// them -- and where the packed kernel of its class fits a CU (16 columns per lane: kAffineC16MinPerCu workgroups, as the 32-bit
+// kernel).  Every other query runs on the 32-bit kernel inside the same call; lanes = 32 sends every query there, and then the launches
+// are plan_search_multi's, field for field.
+// Launches: as plan_prefilter's.  Per (group, class) the packed queries and the others get launches of their own, cut by target ranks
+// where the items would pass max_items.  A packed launch has nq x ceil(nranks / 2) items; item w runs the ranks rank0 + 2 (w / nq) and,
+// if it lies inside the launch, the next one, against entry q0 + w % nq -- rank0 is even, and only the last launch of a class can hold
+// an odd last rank.  Its boundary workspace per resident wave is that of the 32-bit launch of the same queries.
+constexpr int64_t kSearchPackedGapMin = -32768;
+constexpr bool search_multi_packed(int64_t max_entry, int64_t qlen, int64_t longest, int64_t gap_open, int64_t gap_extend, int lanes) {
+    return lanes == 16 && gap_open + 2 * gap_extend >= kSearchPackedGapMin &&
+           (max_entry < 0 ? 0 : max_entry) * (qlen < longest ? qlen : longest) <= kPrefilterPackedMax;
+}
+
+struct SearchMultiLanesJob : SearchMultiJob {    // per_cu: of the 32-bit kernels, as there
+    int packed_per_cu[kSearchMultiKernels] = {}; // occupancy of every sw_search_multi_pk_wave instantiation at 256 threads (workgroups per CU)
+    int max_entry = 0;                       // the largest entry of the substitution table; a PSSM's smax
+    int gap_open = 0, gap_extend = 0;
+    int lanes = 32;                          // "search_lanes": 32 never packed, 16 packed where a query is eligible
+};
+
+struct MultiLanesLaunch : MultiLaunch {      // kernel: index in kSearchMulti, packed: in kSearchMultiPacked; items packed: nq * ceil(nranks / 2)
+    bool packed = false;
+};
+
+struct SearchMultiLanesPlan {
+    std::vector<swk::MultiQuery> table;      // as SearchMultiPlan::table, but for the order inside a (group, class)
+    std::vector<MultiGroup> group;
+    std::vector<MultiLanesLaunch> launch;    // in the order they are enqueued: group after group
+    int64_t packed_launches = 0;
+    size_t prof_need = 0, bnd_need = 0;      // workspaces: profiles of the largest group (bytes), boundary columns (ints)
+};
+
+SearchMultiLanesPlan plan_search_multi_lanes(const SearchMultiLanesJob& job);
+
 // ---- the best `top` targets of every row of a query-major result table (sw_top_hits_device, sw_db_search_affine_top; sw_search_top.hip).
 // Key: a target's key is score << tbits | (2^tbits - 1 - target) with tbits = ceil(log2 ntargets): unique per target, and plain integer
 // order of the keys is the rank order (score descending, target ascending).  nbits = 24 + tbits bits of a key can differ.

@@ -2,7 +2,7 @@
 """Post-build audit of the gfx950 ISA of sw_kernels.hip (run by `make check_isa`):
   * v126/v127 (landing registers of the hand-tracked edge prefetch) appear ONLY in the two asm
     statements that own them;
-  * no scratch (spills) in the fill kernels, none at all in the search kernels (sw_search.hip, sw_search_affine.hip, sw_search_multi.hip)
+  * no scratch (spills) in the fill kernels, none at all in the search kernels (sw_search.hip, sw_search_affine.hip, sw_search_multi.hip, sw_search_multi16.hip)
     and the alignment kernels (sw_align_affine.hip, sw_align_hits.hip, sw_align_ckpt.hip), whose work counter is a vector buffer atomic."""
 import re, subprocess, sys, os, tempfile
 here = os.path.dirname(os.path.abspath(__file__))
@@ -120,5 +120,15 @@ bodies9 = re.findall(r"^(\S*sw_align_(?:hits_)?ckpt_wave\S*):[^\n]*\n(.*?)^\.Lfu
 without9 = [name for name, body in bodies9 if not re.search(r"^\s*buffer_atomic_add ", body, flags=re.M)]
 if nckpt != 3 or nckpth != 3 or len(bodies9) != 6 or without9:
     print(f"checkpointed alignment kernels: expected 3 + 3 kernels with a vector buffer atomic work counter ({nckpt} + {nckpth} kernels, {len(bodies9)} bodies found, none in {without9})"); sys.exit(1)
+# sw_search_multi16.hip (the many-query search on packed 16-bit lanes): the same two rules for its three kernels
+s10 = dev_asm("sw_search_multi16.hip")
+for m in re.finditer(r"\.private_segment_fixed_size:\s*(\d+)", s10):
+    if int(m.group(1)) > 0:
+        print("scratch in use (packed many-query search):", m.group(0)); sys.exit(1)
+npacked = len(re.findall(r"^\s*\.name:\s+\S*sw_search_multi_pk_wave", s10, flags=re.M))
+bodies10 = re.findall(r"^(\S*sw_search_multi_pk_wave\S*):[^\n]*\n(.*?)^\.Lfunc_end\d+:", s10, flags=re.M | re.S)
+without10 = [name for name, body in bodies10 if not re.search(r"^\s*buffer_atomic_add ", body, flags=re.M)]
+if npacked != 3 or len(bodies10) != npacked or without10:
+    print(f"packed many-query search kernels: expected a vector buffer atomic work counter in each of 3 kernels ({npacked} kernels, {len(bodies10)} bodies found, none in {without10})"); sys.exit(1)
 n = len(re.findall(r"global_load_dwordx2 v\[126:127\]", s))
-print(f"check_isa ok: {n} prefetch sites, v126/v127 private; {nprod} producer paths keep v100..v120 private; traceback window v62..v127 private; no scratch; {nsearch} search kernels without scratch; {naffine} affine search kernels without scratch; {nmulti} many-query search kernels without scratch; {nalign} affine alignment kernels without scratch; {nhits} + {nbin} hit-table alignment kernels without scratch; {nckpt} + {nckpth} checkpointed alignment kernels without scratch")
+print(f"check_isa ok: {n} prefetch sites, v126/v127 private; {nprod} producer paths keep v100..v120 private; traceback window v62..v127 private; no scratch; {nsearch} search kernels without scratch; {naffine} affine search kernels without scratch; {nmulti} many-query search kernels without scratch; {nalign} affine alignment kernels without scratch; {nhits} + {nbin} hit-table alignment kernels without scratch; {nckpt} + {nckpth} checkpointed alignment kernels without scratch; {npacked} packed many-query search kernels without scratch")
