@@ -13,7 +13,14 @@
  *     H and P are (rows+1) x (cols+1), row-major, row stride cols+1 (serial_smithW.c:192).
  *   - "d_" pointers are DEVICE (HBM) pointers, everything else is host memory.
  *   - `stream` is a hipStream_t passed as void* (NULL = the default stream).  Every launch, memset and copy of a call goes to that
- *     stream (and, for the fills, behind the previous fill of the device, see sw_ctx).
+ *     stream, behind the previous call of the device (see sw_ctx).  That holds for the fills and for every search, selection and
+ *     alignment call alike (every call below that takes a `stream`: the sw_*_device calls and the searches, selections, pre-filter and
+ *     alignments of a sw_db; not sw_db_create, sw_db_free or sw_db_info, which enqueue nothing): a context's calls share its pinned
+ *     staging copies and device workspaces, so a call enqueued on another stream than the device's previous call first waits, on the
+ *     device, for that call.  Calls of one context may therefore follow each other on any streams without a synchronisation in between.
+ *     "Asynchronous, no host round trip" has a bound: before it rewrites the pinned copies a call waits on the host for the previous
+ *     call's uploads to have left them, and those are ordered behind the call before that one, so the host runs about two calls ahead
+ *     of the device, not more; where a workspace has to grow, the call also waits for the stream.
  *   - WRITE extents.  A call writes the outputs it documents and nothing else of the caller's: exactly (rows+1) x (cols+1) elements of
  *     d_H / d_P (a tile: its own rectangle inside the row stride), one sw_result / sw_alignment per problem, the documented number of
  *     granules, flags, path entries and op bytes.  Outputs need no initialisation and no particular alignment beyond that of their
@@ -63,7 +70,8 @@ typedef struct { int64_t max_pos; int64_t max_score; int64_t path_len; } sw_resu
 
 /* One per GPU; one host thread drives a ctx at a time.  Fills of one DEVICE are serialised by the library (a fill's
  * workgroups wait for each other, so two fills must not share the CUs): a fill enqueued on another stream than the
- * previous fill of that device first waits, on the device, for that stream.  Contexts of different devices are
+ * previous fill of that device first waits, on the device, for that stream.  The search, selection and alignment calls take
+ * the same turn (their workspaces are shared between the families of a context).  Contexts of different devices are
  * independent. */
 typedef struct sw_ctx sw_ctx;
 

@@ -1,0 +1,302 @@
+"""GPU: the sessions of tests/session_cases.py -- every search and alignment family of one context enqueued back to back on a fresh
+context.  Every call stages through the same pinned copies (schedule, query table, scoring table) and device workspaces, so what
+keeps one call's state from another's is the library's own ordering alone: the event wait before a pinned copy is rewritten, the drain
+before a workspace is freed, the wait behind the device's previous call on another stream, the memsets in front of every launch.
+
+A test allocates every input, handle and output first (outputs poisoned, the hit tables and alignments carved out of a guarded arena),
+synchronises once, enqueues all steps without synchronising, copying to the host or reading a device value in between -- options are
+host state and so are the "last_*" routes read here: sw_get_option reads fields of the context for all of them but
+"last_align_hits_lists", which is not used --, synchronises once more and compares every output bit for bit with the expectation of
+test_session_host.py.  The growing session runs twice on its context, the second time with a second set of tables on warm workspaces.
+
+Each test prints what it observed of the overlap (whether the first step's event and which others were still pending when the last
+enqueue returned, which steps were still running when the enqueue of the next returned, the time of the enqueue loop and of the
+drain); nothing of that is asserted: DESIGN section 9o records the figures.  The references of all three tests are computed once, by
+the first test that needs them."""
+import time
+
+import numpy as np
+import pytest
+
+import session_cases as sc
+from affine_cases import checker  # noqa: F401
+from buffer_cases import POISON, POISON32, POISON64, Arena, arena_bytes, assert_guards
+
+pytestmark = pytest.mark.gpu
+
+DEV = "cuda:0"
+
+
+@pytest.fixture(scope="module")
+def expect(checker, oracle, swamd):  # noqa: F811
+    return sc.Expect(checker, oracle, swamd)
+
+
+def to_dev(t, data):
+    """The bytes on the device with 16 zeroed spare bytes behind them."""
+    data = np.ascontiguousarray(data).view(np.uint8).reshape(-1)
+    buf = t.zeros(len(data) + 16, dtype=t.uint8, device=DEV)
+    buf[:len(data)] = t.from_numpy(data.copy())
+    return buf[:len(data)]
+
+
+def ops_cap(step):
+    return max(len(q) for q in step.queries) + int(np.diff(sc.databases()[step.db]["offs"]).max())
+
+
+class Run:
+    """One fresh context and everything its steps need, allocated before the first call."""
+
+    def __init__(self, swamd, torch, steps):
+        t = self.t = torch
+        self.steps = steps
+        self.eng = swamd.Engine(0)
+        self.second = t.cuda.Stream()
+        self.d_db = {n: to_dev(t, d["packed"]) for n, d in sc.databases().items()}
+        self.db = {n: self.eng.prepare_db(self.d_db[n], d["offs"]) for n, d in sc.databases().items()}
+        self.d_q = {n: to_dev(t, q["qpacked"]) for n, q in sc.query_sets().items()}
+        self.d_pssm = {id(s.ty): to_dev(t, s.ty.matrix).view(t.int8) for s in steps if s.ty is not None}
+        a, b = sc.fill_pair()
+        self.d_a, self.d_b = self.eng.to_device(a)[0], self.eng.to_device(b)[0]
+        full = lambda n, dtype=t.int64, v=POISON64: t.full((n,), v, dtype=dtype, device=DEV)  # noqa: E731
+        # the arena of the hit tables and the alignments
+        sizes = []
+        for s in steps:
+            nq = len(s.queries) if s.call != "fill" else 0
+            if s.call in sc.SELECTING_CALLS:
+                sizes += [nq * s.top * 24, nq * 8]
+            elif s.call in ("align_affine_hits", "align_pssm_hits"):
+                sizes += [nq * s.top * 56, nq * s.top * ops_cap(s)]
+            elif s.call == "align_affine_one":
+                sizes += [len(s.hits) * 56, len(s.hits) * ops_cap(s)]
+        self.arena = Arena(t, DEV, arena_bytes(*sizes))
+        i64 = lambda n, name: self.arena.view(self.arena.carve(n * 8, align=8, name=name), t.int64, (n,))  # noqa: E731
+        u8 = lambda n, name: self.arena.view(self.arena.carve(n, name=name), t.uint8, (n,))  # noqa: E731
+        self.buf, self.out, self.events = {}, {}, {}
+        for s in steps:
+            nq = len(s.queries) if s.call != "fill" else 0
+            nt = len(sc.databases()[s.db]["targets"]) if s.db else 0
+            tag = f"{s.name}-{s.p}"
+            if s.call in ("search_affine", "search_pssm"):
+                self.buf[s.key] = full(nq * nt * 3)
+            elif s.call in ("search_linear", "search_affine_one"):
+                self.buf[s.key] = full(nt * 3).view(nt, 3)
+            elif s.call in sc.SELECTING_CALLS:
+                self.buf[s.key] = (i64(nq * s.top * 3, tag + " hits"), i64(nq, tag + " nhits"))
+            elif s.call == "prefilter":
+                self.buf[s.key] = (full(s.cap * 2).view(s.cap, 2), full(1), full(nq * nt, t.int32, POISON32).view(nq, nt))
+            elif s.call == "search_pairs":
+                self.buf[s.key] = full(s.cap * 3)
+            elif s.call in ("align_affine_hits", "align_pssm_hits"):
+                self.buf[s.key] = (i64(nq * s.top * 7, tag + " aln"), u8(nq * s.top * ops_cap(s), tag + " ops"))
+                if s.hits is not None:
+                    self.buf[s.key] += (t.from_numpy(s.hits.copy()).to(DEV), t.from_numpy(s.nhits.copy()).to(DEV))
+            elif s.call == "align_affine_one":
+                n = len(s.hits)
+                self.buf[s.key] = (i64(n * 7, tag + " aln").view(n, 7), u8(n * ops_cap(s), tag + " ops").view(n, ops_cap(s)))
+            elif s.call == "fill":
+                f = self.eng.alloc(len(a), len(b))
+                f.H.fill_(POISON32)
+                f.P.fill_(POISON32)
+                f.res.fill_(POISON64)
+                self.buf[s.key] = f
+        t.zeros(1, dtype=t.int64, device=DEV)                       # (the one-call search allocates its count: the allocator is warm)
+        with t.cuda.stream(self.second):
+            t.zeros(1, dtype=t.int64, device=DEV)
+
+    def close(self):
+        for db in self.db.values():
+            db.close()
+        self.eng.close()
+
+    def enqueue(self, s):
+        """The step's call on its stream, the routes it reports read from the host's fields, an event behind it.  Nothing waits."""
+        t, eng = self.t, self.eng
+        if s.stream:
+            with t.cuda.stream(self.second):
+                self._call(s)
+                ev = t.cuda.Event()
+                ev.record()
+        else:
+            self._call(s)
+            ev = t.cuda.Event()
+            ev.record()
+        self.events[s.key] = ev
+        if s.call in sc.MULTI_SEARCH_CALLS:
+            packed = eng.get_option("last_search_multi_packed_launches")
+            assert (packed > 0) if s.packed else (packed == 0), (s.name, packed)
+        elif s.call in ("align_affine_hits", "align_pssm_hits"):
+            assert eng.get_option("last_align_hits_checkpointed") == s.checkpoint, s.name
+        elif s.call == "align_affine_one":
+            assert eng.get_option("last_align_affine_checkpointed") == s.checkpoint, s.name
+
+    def _call(self, s):
+        eng, buf = self.eng, self.buf.get(s.key)
+        eng.set_option("search_lanes", s.lanes)
+        eng.set_option("align_checkpoint", s.checkpoint)
+        c = s.call
+        if c == "fill":
+            self.out[s.key] = eng.fill_into(buf, self.d_a, self.d_b)
+            return
+        db, d = self.db[s.db], sc.databases()[s.db]
+        if s.ty is not None:
+            d_src, qoffs, scoring = self.d_pssm[id(s.ty)], s.ty.qoffs, s.ty.scoring(*s.gaps)
+        else:
+            qs = sc.query_sets()[s.q]
+            d_src, qoffs, scoring = self.d_q[s.q], qs["qoffs"], (s.sub, *s.gaps)
+            if s.one is not None:
+                d_one, qlen = d_src[int(qoffs[s.one]):], len(s.queries[0])
+        if c == "search_affine":
+            self.out[s.key] = db.search_affine_device(d_src, qoffs, scoring, out=buf)
+        elif c == "search_pssm":
+            self.out[s.key] = db.search_pssm_device(d_src, qoffs, scoring, out=buf)
+        elif c == "search_affine_top":
+            self.out[s.key] = db.search_affine_top_device(d_src, qoffs, scoring, s.top, s.min_score, out=buf)
+        elif c == "search_pssm_top":
+            self.out[s.key] = db.search_pssm_top_device(d_src, qoffs, scoring, s.top, s.min_score, out=buf)
+        elif c == "prefilter":
+            self.out[s.key] = db.prefilter_ungapped_device(d_src, qoffs, s.sub, s.min_score, s.cap, want_scores=True, out=buf)
+        elif c == "search_pairs":
+            pairs = self.out[(s.source, s.p)][0]
+            self.out[s.key] = (pairs, db.search_affine_pairs_device(d_src, qoffs, scoring, pairs, out=buf))
+        elif c == "top_pairs":
+            pairs, res = self.out[(s.source, s.p)]
+            self.out[s.key] = eng.top_hits_pairs_device(pairs, res, s.cap, len(s.queries), len(d["targets"]), s.top, s.min_score, out=buf)
+        elif c == "top_prefiltered":
+            self.out[s.key] = db.search_affine_top_prefiltered_device(d_src, qoffs, scoring, sc.PREFILTER_MIN, s.cap, s.top, s.min_score, out=buf)
+        elif c == "align_affine_hits":
+            hits, nhits = self.out[(s.source, s.p)]
+            self.out[s.key] = db.align_affine_hits_device(d_src, qoffs, scoring, hits, nhits, ops_cap=ops_cap(s), out=buf[:2])
+        elif c == "align_pssm_hits":
+            self.out[s.key] = db.align_pssm_hits_device(d_src, qoffs, scoring, buf[2], buf[3], ops_cap=ops_cap(s), out=buf[:2])
+        elif c == "search_linear":
+            self.out[s.key] = eng.search_device(d_one, qlen, self.d_db[s.db], d["offs"], s.linear, out=buf)
+        elif c == "search_affine_one":
+            self.out[s.key] = eng.search_affine_device(d_one, qlen, self.d_db[s.db], d["offs"], s.sub, *s.gaps, out=buf)
+        elif c == "align_affine_one":
+            self.out[s.key] = eng.align_affine_device(d_one, qlen, self.d_db[s.db], d["offs"], s.sub, *s.gaps, s.hits, ops_cap=ops_cap(s), out=buf)
+        else:
+            raise AssertionError(c)
+
+    def pending(self):
+        """The steps whose event has not completed (a query, not a wait)."""
+        return [s.name for s in self.steps if s.key in self.events and not self.events[s.key].query()]
+
+    # ---- after the final synchronisation ----
+
+    def check(self, expect):
+        """Every step against its expectation; all the steps that differ are reported, not the first alone."""
+        wrong = []
+        for s in self.steps:
+            try:
+                self._check(s, expect.of(s), self.out[s.key])
+            except AssertionError as err:
+                wrong.append(str(err).splitlines()[0])
+        assert not wrong, f"{len(wrong)} of {len(self.steps)} steps differ:\n  " + "\n  ".join(wrong)
+        assert_guards(self.arena)
+
+    def _check(self, s, e, out):
+        what = f"{s.name} (pass {s.p}, stream {s.stream})"
+        host = lambda x: x.cpu().numpy()  # noqa: E731
+        c = s.call
+        if c == "fill":
+            assert np.array_equal(host(out.H), e["H"]) and np.array_equal(host(out.P), e["P"]), what
+            assert host(out.res).tolist()[:2] == [e["max_pos"], e["max_score"]], what
+            return
+        empty = np.diff(sc.databases()[s.db]["offs"]) == 0
+        if c in ("search_affine", "search_pssm", "search_linear", "search_affine_one"):
+            got = host(out)
+            bad = np.argwhere((got != e["results"]).any(axis=-1))
+            assert len(bad) == 0, f"{what}: {len(bad)} entries differ, first {tuple(bad[0])}: {got[tuple(bad[0])]} vs {e['results'][tuple(bad[0])]}"
+            assert empty.any() and not got[..., empty, :].any(), what                  # {0, 0, 0} over the poison
+        elif c in sc.SELECTING_CALLS:
+            hits, nhits = host(out[0]), host(out[1])
+            assert np.array_equal(nhits, e["nhits"]), f"{what}: nhits {nhits.tolist()} vs {e['nhits'].tolist()}"
+            bad = np.argwhere((hits != e["hits"]).any(axis=-1))
+            assert len(bad) == 0, f"{what}: {len(bad)} hits differ, first {tuple(bad[0])}: {hits[tuple(bad[0])]} vs {e['hits'][tuple(bad[0])]}"
+            if c == "top_prefiltered":
+                assert int(host(out[2])[0]) == e["npairs"], what
+        elif c == "prefilter":
+            pairs, n, scores = host(out[0]), int(host(out[1])[0]), host(out[2])
+            assert n == e["npairs"], f"{what}: {n} pairs pass, expected {e['npairs']}"
+            pr = pairs[:n]
+            assert np.array_equal(pr[np.lexsort((pr[:, 1], pr[:, 0]))], e["pairs"]) and (pairs[n:] == -1).all(), what
+            assert np.array_equal(scores, e["scores"]) and not scores[:, empty].any(), what
+        elif c == "search_pairs":
+            pairs, got = host(out[0]), host(out[1])
+            want = np.zeros_like(got)
+            valid = pairs[:, 0] >= 0
+            want[valid] = e["full"][pairs[valid, 0], pairs[valid, 1]]
+            bad = np.nonzero((got != want).any(axis=1))[0]
+            assert len(bad) == 0, f"{what}: {len(bad)} entries differ, first {bad[0]} {tuple(pairs[bad[0]])}: {got[bad[0]]} vs {want[bad[0]]}"
+            assert valid.sum() == len(e["pairs"]) and got[valid, 1].max() > 0, what
+        else:                                                                           # the three alignment calls
+            aln, ops = host(out[0]), host(out[1])
+            bad = np.argwhere((aln != e["aln"]).any(axis=-1))
+            assert len(bad) == 0, f"{what}: {len(bad)} alignments differ, first {tuple(bad[0])}: {aln[tuple(bad[0])]} vs {e['aln'][tuple(bad[0])]}"
+            flat_aln, flat_ops = aln.reshape(-1, 7), ops.reshape(len(aln.reshape(-1, 7)), -1)
+            want_ops = e["ops"] if c == "align_affine_one" else [o for row in e["ops"] for o in row]
+            for h, o in enumerate(want_ops):
+                n = int(flat_aln[h, 6])
+                assert flat_ops[h, :n].tobytes() == o and (flat_ops[h, n:] == POISON).all(), f"{what}: ops of entry {h}"
+
+
+def run_sessions(runs, order, label):
+    """Enqueues `order` -- (run, step) pairs -- with nothing in between, drains once, and says what it saw of the overlap."""
+    import torch
+    torch.cuda.synchronize()
+    first, before, overlapped = None, None, []
+    t0 = time.perf_counter()
+    for run, s in order:
+        run.enqueue(s)
+        if before is not None and not before[0].events[before[1].key].query():      # (a query of the event, not a wait)
+            overlapped.append(before[1].name)
+        before = (run, s)
+        if first is None:
+            first = run.events[s.key]
+    first_pending = not first.query()
+    t1 = time.perf_counter()
+    pending = [n for run in runs for n in run.pending()]
+    torch.cuda.synchronize()
+    t2 = time.perf_counter()
+    print(f"\n[{label}] {len(order)} calls enqueued in {1e3 * (t1 - t0):.1f} ms, drained in {1e3 * (t2 - t1):.1f} ms; the first step's event was "
+          f"{'still pending' if first_pending else 'complete'} when the last enqueue returned; pending then: {pending}; "
+          f"{len(overlapped)} steps were still running when the enqueue of the next returned: {overlapped}")
+
+
+@pytest.fixture
+def runs(swamd):
+    made = []
+
+    def make(steps):
+        import torch
+        made.append(Run(swamd, torch, steps))
+        return made[-1]
+
+    yield make
+    for r in made:
+        r.close()
+
+
+def test_growing_session_twice_on_one_fresh_context(runs, expect):
+    steps = sc.growing(0) + sc.growing(1)
+    run = runs(steps)
+    run_sessions([run], [(run, s) for s in steps], "growing, two passes")
+    run.check(expect)
+
+
+def test_shrinking_session_on_two_streams(runs, expect):
+    """The largest search first; the second pass finds every workspace at its final size, so nothing is reallocated in it."""
+    run = runs(sc.shrinking(0) + sc.shrinking(1))
+    assert run.steps[0].name == "top_packed"
+    run_sessions([run], [(run, s) for s in sc.shrinking(0)], "shrinking, cold")
+    run_sessions([run], [(run, s) for s in sc.shrinking(1)], "shrinking, warm")
+    run.check(expect)
+
+
+def test_two_contexts_interleaved_on_one_device(runs, expect):
+    a, b = sc.two_contexts()
+    ra, rb = runs(a), runs(b)
+    run_sessions([ra, rb], [x for sa, sb in zip(a, b) for x in ((ra, sa), (rb, sb))], "two contexts")
+    ra.check(expect)
+    rb.check(expect)

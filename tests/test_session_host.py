@@ -1,0 +1,246 @@
+"""CPU: the sessions of tests/session_cases.py before any GPU sees them.  Every step's expectation comes from the independent
+references alone and the library's host leg of the same call must equal it; then the conditions that keep a step of the GPU test from
+passing on stale state -- what an earlier call of another shape or scoring left in a shared buffer -- are asserted on the references:
+
+  * scores: a step's table, recomputed under the scoring of the step before it in its context (whatever its kind: a table, a PSSM read
+    as the checker's table, the match and mismatch scores of a linear search) and, where that is another step, under the scoring of
+    the last earlier step of its own kind (a 64 KiB table, or a PSSM's letters), differs from its own in at least one entry of every
+    query that has a non-empty target, and holds a non-zero score;
+  * a table call whose table is the first upload behind a PSSM call's code table: with row 0 of its table replaced by that code table
+    the step's expected table changes for every query that holds the byte 0 (every query of more than one letter does), and the
+    table differs from the last table before it inside those 256 bytes and beyond them;
+  * every selecting step selects something and `top` cuts at least one row; the pre-filter passes a strict, non-empty subset;
+  * the packed steps are eligible for 16-bit lanes;
+  * the growing session grows.
+
+Growth is taken of the running maxima of session_cases.Step.measures(), which is what a workspace's size follows: the session ends on
+its small first call and runs the one-query calls behind the forty queries, so the values of the steps themselves are not monotone.
+What is asserted: each of the maxima rises strictly at least once behind the first step, and every step raises at least one of them
+or is the first to use one of session_cases.WORKSPACES -- but for the four steps of session_cases.REUSING, exactly.  No GPU is needed."""
+import ctypes
+
+import numpy as np
+import pytest
+
+import pairs_top_cases as ptc
+import pssm_cases
+import session_cases as sc
+from affine_cases import checker  # noqa: F401
+from align_cases import replay
+
+
+@pytest.fixture(scope="module")
+def expect(checker, oracle, swamd):  # noqa: F811
+    return sc.Expect(checker, oracle, swamd)
+
+
+def contexts():
+    """{name: the steps one context runs, in enqueue order}."""
+    a, b = sc.two_contexts()
+    return {"growing": sc.growing(0) + sc.growing(1), "shrinking": sc.shrinking(0) + sc.shrinking(1), "two_a": a, "two_b": b}
+
+
+ALL_STEPS = sc.growing(0) + sc.growing(1)
+
+
+def sets_of(step):
+    d = sc.databases()[step.db]
+    if step.ty is not None:
+        return (step.ty.matrix, step.ty.qoffs), (d["packed"], d["offs"])
+    qs = sc.query_sets()[step.q]
+    return (qs["qpacked"], qs["qoffs"]), (d["packed"], d["offs"])
+
+
+def check_alignments(step, e, full, table, counts):
+    """Every used entry inside the database: the ops replay over the letters to the alignment's own score, which is the checker's;
+    every other entry is the zero alignment."""
+    d = sc.databases()[step.db]
+    nt, seen = len(d["targets"]), 0
+    for q, query in enumerate(step.queries):
+        used = table.shape[1] if counts is None else int(np.clip(counts[q], 0, table.shape[1]))
+        for r in range(table.shape[1]):
+            k = int(table[q, r, 0])
+            if r < used and 0 <= k < nt:
+                assert tuple(e["aln"][q, r, :2]) == tuple(full[q, k, :2]), (step.name, q, r)
+                replay(query, d["targets"][k], step.checker_table, *step.gaps, e["aln"][q, r], e["ops"][q][r])
+                seen += e["aln"][q, r, 1] > 0
+            else:
+                assert not e["aln"][q, r].any() and e["ops"][q][r] == b"", (step.name, q, r)
+    assert seen > 0, step.name
+
+
+@pytest.mark.parametrize("step", ALL_STEPS, ids=lambda s: f"{s.name}-{s.p}")
+def test_host_leg_equals_the_references(swamd, oracle, expect, step):
+    e = expect.of(step, sc.by_name(sc.growing(step.p)))
+    c = step.call
+    if c == "fill":
+        a, b = sc.fill_pair()
+        H, P = np.zeros_like(e["H"]), np.zeros_like(e["P"])
+        r = swamd._Result()
+        scores = swamd._Scores(*swamd.DEFAULT_SCORES)
+        aa, bb = np.concatenate([a, np.zeros(1, np.uint8)]), np.concatenate([b, np.zeros(1, np.uint8)])
+        assert swamd.lib().sw_fill_cpu(aa.ctypes.data, len(a), bb.ctypes.data, len(b), ctypes.byref(scores), H.ctypes.data, P.ctypes.data, ctypes.byref(r)) == 0
+        assert np.array_equal(H, e["H"]) and np.array_equal(P, e["P"]) and (r.max_pos, r.max_score) == (e["max_pos"], e["max_score"]) and r.max_score > 0
+        return
+    queries, targets = sets_of(step)
+    d = sc.databases()[step.db]
+    nq, nt = len(step.queries), len(d["targets"])
+    empty = np.diff(d["offs"]) == 0
+    if c == "search_affine":
+        got = swamd.search_affine_multi_host(queries, targets, (step.sub, *step.gaps))
+        assert np.array_equal(got, e["results"]) and not got[:, empty].any() and got[:, :, 1].max() > 0
+    elif c == "search_pssm":
+        got = swamd.search_pssm_multi_host(queries, targets, step.ty.scoring(*step.gaps))
+        assert np.array_equal(got, e["results"]) and not got[:, empty].any() and got[:, :, 1].max() > 0
+    elif c == "search_affine_top":
+        hits, nhits = swamd.search_affine_multi_top_host(queries, targets, (step.sub, *step.gaps), step.top, step.min_score)
+        assert np.array_equal(hits, e["hits"]) and np.array_equal(nhits, e["nhits"])
+    elif c == "search_pssm_top":
+        full = swamd.search_pssm_multi_host(queries, targets, step.ty.scoring(*step.gaps))
+        hits, nhits = pssm_cases.rank_order(full, step.top, step.min_score)
+        assert np.array_equal(full, expect.full(step)) and np.array_equal(hits, e["hits"]) and np.array_equal(nhits, e["nhits"])
+    elif c == "prefilter":
+        pairs, n, scores = swamd.prefilter_ungapped_host(queries, targets, step.sub, step.min_score, step.cap)
+        assert n == e["npairs"] and np.array_equal(pairs[:n], e["pairs"]) and (pairs[n:] == -1).all() and np.array_equal(scores, e["scores"])
+        assert 0 < n < int((~empty).sum()) * nq                                         # a strict, non-empty subset
+    elif c == "search_pairs":
+        got = swamd.search_affine_pairs_host(queries, targets, (step.sub, *step.gaps), e["pairs"])
+        assert np.array_equal(got, e["results"]) and got[:, 1].max() > 0
+    elif c == "top_pairs":
+        names = sc.by_name(sc.growing(step.p))
+        src = expect.of(names[step.source], names)
+        hits, nhits = swamd.top_hits_pairs_host(src["pairs"], src["results"], nq, nt, step.top, step.min_score)
+        assert np.array_equal(hits, e["hits"]) and np.array_equal(nhits, e["nhits"])
+    elif c == "top_prefiltered":
+        pairs, n, _ = swamd.prefilter_ungapped_host(queries, targets, step.sub, sc.PREFILTER_MIN, step.cap, want_scores=False)
+        res = swamd.search_affine_pairs_host(queries, targets, (step.sub, *step.gaps), pairs[:n])
+        hits, nhits = swamd.top_hits_pairs_host(pairs[:n], res, nq, nt, step.top, step.min_score)
+        assert n == e["npairs"] and 0 < n < int((~empty).sum()) * nq
+        assert np.array_equal(hits, e["hits"]) and np.array_equal(nhits, e["nhits"])
+    elif c in ("align_affine_hits", "align_pssm_hits"):
+        check_alignments(step, e, expect.full(step), e["table"], e["counts"])
+    elif c == "align_affine_one":
+        full = expect.full(step)
+        assert (e["aln"][:, 6] > 0).any()
+        for h, k in enumerate(step.hits):
+            assert tuple(e["aln"][h, :2]) == tuple(full[0, k, :2]), (step.name, h)
+            replay(step.queries[0], d["targets"][k], step.sub, *step.gaps, e["aln"][h], e["ops"][h])
+    elif c == "search_linear":
+        got = swamd.search_affine_host(step.queries[0], targets, swamd.submat_match(*step.linear[:2]), 0, step.linear[2])
+        assert np.array_equal(got, e["results"]) and got[:, 1].max() > 0
+        for k in (1, 77, 198):                                                          # the fill oracle says the same of the linear recurrence
+            o = oracle.fill_streaming(step.queries[0], d["targets"][k], step.linear)
+            assert (o["max_pos"], o["max_score"]) == tuple(e["results"][k, :2]), k
+    elif c == "search_affine_one":
+        got = swamd.search_affine_host(step.queries[0], targets, step.sub, *step.gaps)
+        assert np.array_equal(got, e["results"]) and got[:, 1].max() > 0
+    else:
+        raise AssertionError(c)
+    if c in sc.SELECTING_CALLS:
+        if c in ("top_pairs", "top_prefiltered"):
+            pr = expect.of(sc.by_name(sc.growing(step.p))["prefilter"])["pairs"] if c == "top_pairs" else expect.ungapped(step)[1]
+            candidates = np.bincount(pr[:, 0], minlength=nq)
+        else:
+            candidates = (expect.full(step)[:, :, 1] >= step.min_score).sum(axis=1)
+        assert e["nhits"].sum() > 0 and (candidates > step.top).any(), f"{step.name}: nothing selected, or top cuts no row"
+        assert (e["nhits"] <= np.minimum(candidates, step.top)).all() and (e["nhits"] == step.top).any()
+
+
+def scored(step):
+    return step.checker_table is not None and step.call not in ("fill", "top_pairs")
+
+
+@pytest.mark.parametrize("name", list(contexts()))
+def test_no_step_passes_on_the_previous_scoring(expect, name):
+    steps = contexts()[name]
+    last = {"table": None, "pssm": None}           # the last step that uploaded a 64 KiB table / a PSSM's code table
+    before = None                                  # the last step with a scoring of any kind: its profiles are what the workspace holds
+    uploaded = None                                # what the scoring table's two copies hold last: "table" or "pssm"
+    same_kind = across = row0 = 0
+    for step in steps:
+        if not scored(step):
+            continue                               # the selection of a list and the fill have no scoring
+        kind = step.kind                           # (None: the linear search uploads no table)
+        filters = step.call in ("prefilter", "top_prefiltered")
+        own = expect.full(step) if step.call != "prefilter" else None
+        offs = sc.databases()[step.db]["offs"]
+        if own is not None:
+            assert own[:, :, 1].max() > 0, step.name
+
+        def differs(tab, gaps, only=None):
+            ok = True
+            if filters:
+                ok = sc.ungapped_differs(step, tab, expect.ungapped(step)[0], only)
+            if own is not None:
+                ok = ok and sc.differs_per_query(own, expect.full_under(step, tab, gaps), offs, only)
+            return ok
+
+        if before is not None:                     # the step before it, whatever its kind
+            gaps = before.checker_gaps if before.call != "prefilter" else step.checker_gaps
+            assert differs(before.checker_table, gaps), (step.name, before.name)
+            across += 1
+        prev = last[kind] if kind else None
+        if prev is not None and prev is not before:
+            if kind == "table":
+                assert not np.array_equal(step.sub, prev.sub), (step.name, prev.name)
+                assert differs(prev.sub, prev.gaps if prev.call != "prefilter" else step.gaps), (step.name, prev.name)
+            else:                                  # the step's matrix read through the previous PSSM's letters, clamp and gaps
+                alt = np.full((256, 256), prev.ty.other, np.int8)
+                alt[:, prev.ty.letters] = np.minimum(step.ty.types, prev.ty.smax)
+                assert not np.array_equal(step.ty.letters, prev.ty.letters)
+                assert differs(alt, prev.gaps), (step.name, prev.name)
+            same_kind += 1
+        if kind == "table" and uploaded == "pssm":  # row 0 of the table's copies holds the PSSM's code table until this call's upload
+            alt = step.sub.copy()
+            alt[0] = sc.code_row(last["pssm"].ty)
+            holds0 = [k for k, q in enumerate(step.queries) if (q == 0).any()]
+            assert holds0 == [k for k, q in enumerate(step.queries) if len(q) > 1], step.name
+            assert differs(alt, step.gaps, holds0), (step.name, last["pssm"].name)
+            if last["table"] is not None:
+                new, old = step.sub.reshape(-1), last["table"].sub.reshape(-1)
+                assert (new[:256] != old[:256]).any() and (new[256:] != old[256:]).any(), step.name
+            row0 += 1
+        if kind:
+            last[kind], uploaded = step, kind
+        before = step
+    nscored = len([s for s in steps if scored(s)])
+    assert across == nscored - 1 and same_kind >= 3
+    assert row0 >= (3 if name == "growing" else 2) * len({s.p for s in steps})   # table calls per pass that take over from a PSSM's code table
+
+
+def test_the_packed_steps_are_eligible():
+    packed = [s for s in ALL_STEPS if s.packed]
+    assert len(packed) == sc.PASSES and all(s.lanes == 16 for s in packed) and all(s.lanes == 32 for s in ALL_STEPS if not s.packed)
+    for s in packed:
+        longest = int(np.diff(sc.databases()[s.db]["offs"]).max())
+        assert all(int(s.sub.max()) * min(len(q), longest) <= 32767 for q in s.queries)
+        assert s.gaps[0] + 2 * s.gaps[1] >= -32768
+
+
+def test_the_growing_session_grows():
+    steps = sc.growing(0)
+    names = [s.name for s in steps]
+    m = np.array([s.measures() for s in steps])
+    running = np.maximum.accumulate(m, axis=0)
+    assert (running[-1] > running[0]).all()                                             # each of the measures rises strictly at least once
+    used, reusing = set(sc.WORKSPACES[steps[0].call]), []
+    for i in range(1, len(steps)):
+        first_use = set(sc.WORKSPACES[steps[i].call]) - used
+        used |= first_use
+        if not (m[i] > running[i - 1]).any() and not first_use:
+            reusing.append(names[i])
+    assert tuple(reusing) == sc.REUSING, f"steps that need no more of anything and use nothing first: {reusing}"
+    assert (m[1:names.index("prefilter") + 1, :4] > running[:names.index("prefilter"), :4]).any(axis=1).all()   # up to the pre-filter by size alone
+    assert tuple(m[-1]) == tuple(m[0]) and (m[-1] <= running[-2]).all()                 # the small call on workspaces far larger than it needs
+    assert [s.stream for s in steps].count(1) == 1 and steps[names.index("align_hits")].stream == 1
+
+
+def test_the_other_sessions_are_the_same_steps():
+    for p in range(sc.PASSES):
+        g, s = sc.growing(p), sc.shrinking(p)
+        assert sorted(x.key for x in g) == sorted(x.key for x in s) and s[0].name == "top_packed"
+        assert [x.stream for x in s] == [i % 2 for i in range(len(s))]
+        order = [x.name for x in s]
+        assert [n for n in order if n in sc.CHAIN] == list(sc.CHAIN)                    # producers stay in front of their consumers
+    a, b = sc.two_contexts()
+    assert {x.stream for x in a} == {0} and {x.stream for x in b} == {1} and len(a) == len(b)
