@@ -426,6 +426,20 @@ int  sw_align_affine_hits_host(const char* queries, const int64_t* qoffsets, int
  * the groups of sw_db_search_affine ("search_profile_mib").  "last_search_pairs_groups", "last_search_pairs_chunks" and
  * "last_search_pairs_launches" (kernel launches, the profile launches included) describe the last call, all 0 for one that launched
  * no kernel.
+ *     LANES.  The option "search_pairs_lanes" (32, the default, or 16) chooses the kernel of this call and of the rescoring inside
+ *     sw_db_search_affine_top_prefiltered; it is an option of its own, "search_lanes" does not reach a pair list.  Under 16 a query
+ *     that is ELIGIBLE has its listed pairs run two per wave on packed 16-bit lanes (csrc/sw_search_pairs16.hip): the device pairs
+ *     the pairs of a query whose weights len x padded query length share a power of two, so partners differ in length by less than a
+ *     factor of two; a pair left over runs alone.  Eligible is the rule of sw_db_search_affine's "search_lanes" = 16, per query:
+ *     max(largest table entry, 0) x min(qlen, longest target OF THE HANDLE) <= 32767 and gap_open + 2 gap_extend >= -32768, and the
+ *     packed kernel of the query's width fits the device.  The handle's longest target is a conservative bound for a list -- the list
+ *     may name shorter targets only, and the host does not read it --, so a query can stay on 32-bit lanes that a shorter database
+ *     would let run packed.  Every other query runs on the 32-bit kernel inside the same call.  The results are the same bytes under
+ *     16 and 32, on every run, whichever pairs the device happens to put together.  Under 16 a chunk's items take up to 48 bytes per
+ *     entry, and per group of queries 12 x 41 bytes per query of counters.  "last_search_pairs_packed_launches" is the number of
+ *     packed score launches of the last call (0 under 32 and for a call that launched none); "last_search_pairs_packed_items" the
+ *     number of two-pair work items the device built in it, pairs without a partner included -- counted on the device: reading it
+ *     waits for the device, like "last_align_hits_lists".
  * Alignments of listed pairs: sw_top_hits_pairs_device (below) selects the best entries of every query from the scored list into an
  * nqueries x top sw_hit table on the device, and sw_db_align_affine_hits aligns that table.
  *   sw_search_affine_pairs_host  the CPU leg: every entry as sw_search_affine_host computes that pair, in plain C++ on host memory, no
@@ -505,7 +519,8 @@ int  sw_prefilter_ungapped_host(const char* queries, const int64_t* qoffsets, in
  *   sw_db_search_affine_top_prefiltered  the whole chain in one call: sw_db_prefilter_ungapped (the table of `scoring`, threshold
  *             prefilter_min_score, no d_scores), sw_db_search_affine_pairs over all pairs_cap entries, then the selection above, all on
  *             `stream` with no host read in between.  d_queries, qoffsets, scoring and the handle as for sw_db_search_affine; top,
- *             min_score, d_hits, d_nhits as above.
+ *             min_score, d_hits, d_nhits as above.  The rescoring follows the option "search_pairs_lanes" as sw_db_search_affine_pairs
+ *             does (the table is the same under 16 and 32); the pre-filter has "prefilter_lanes".
  *             WHAT IT COMPUTES: the table of sw_db_search_affine_top restricted to the pairs with U >= prefilter_min_score (U: the
  *             ungapped score above).  That is a FILTER, not the same hits: a pair whose gapped score is high and whose best gapless
  *             segment is below the threshold is not found.  One case is exact: with prefilter_min_score = 1 and min_score >= 1 the two
@@ -790,13 +805,17 @@ int sw_synchronize(sw_ctx* ctx, void* stream);   /* waits for `stream`; reports 
  * describe the last sw_db_search_affine_top / sw_top_hits_device call; "last_align_hits_launches", "last_align_hits_tiers",
  * "last_align_hits_slots" and "last_align_hits_lists" the last sw_db_align_affine_hits call; "search_pairs_chunk" (settable, default
  * 2^22, 1..2^31 - 1) is the most entries of a pair list that sw_db_search_affine_pairs bins at a time, "last_search_pairs_groups",
- * "last_search_pairs_chunks" and "last_search_pairs_launches" describe the last such call; "prefilter_lanes" (settable, 0 or 32) and
+ * "last_search_pairs_chunks" and "last_search_pairs_launches" describe the last such call, "search_pairs_lanes" (settable, 32 or 16,
+ * default 32) sends the listed pairs of the queries whose scores fit 16 bits to the kernel that runs two pairs per wave on packed lanes
+ * (sw_db_search_affine_pairs above has the rule), "last_search_pairs_packed_launches" counts those launches and
+ * "last_search_pairs_packed_items" the two-pair work items the device built (reading it waits for the device); "prefilter_lanes" (settable, 0 or 32) and
  * "last_prefilter_groups", "last_prefilter_launches", "last_prefilter_packed_launches" belong to sw_db_prefilter_ungapped (above);
  * "last_top_pairs_launches" and "last_top_pairs_kernel" describe the last sw_top_hits_pairs_device call, and "search_results_mib" also
  * bounds the pairs_cap of sw_db_search_affine_top_prefiltered (56 bytes per entry).
  * "debug_search_pairs_items_ptr" (an
  * accessor for tests) is the device address of that call's item workspace, which a call leaves as its last (chunk, group) filled it:
- * 24-byte items {int64 start, int64 out, int32 len, int32 entry}, the classes' lists back to back. */
+ * 24-byte items {int64 start, int64 out, int32 len, int32 entry}, the classes' lists back to back (under "search_pairs_lanes" = 16 the
+ * two-pair items of a group with packed queries come first, 48 bytes each, the 24-byte items behind them). */
 int sw_set_option(sw_ctx* ctx, const char* name, int64_t value);
 int64_t sw_get_option(sw_ctx* ctx, const char* name);
 

@@ -54,6 +54,12 @@
   "search_lanes" = 32 and = 16, ALTERNATING, and a second pair of legs for sw_db_search_affine_top with top 10, torch events around whole
   calls, medians and ranges of --reps after --warmup, the ratio 16 / 32 of either pair.  lanes_identical is a byte comparison of the full
   result tables and of the hit tables of the two modes at the timed size; the run fails if it is false
+  --pairs-lanes: data set (a) only, 64 queries of --qlen through one handle and the same buffers in one process: sw_db_search_affine_pairs
+  under "search_pairs_lanes" = 32 and = 16, ALTERNATING, at three list sizes -- every pair of the cross product in shuffled order (the
+  list of --pairs), a random 10 % and a random 1 % (the list of --pairs) -- and then sw_db_search_affine_top_prefiltered (top 10, threshold
+  60) under both; torch events around whole calls, medians and ranges of 7 calls after a warm-up, the ratio 16 / 32 of every pair of legs.
+  pairs_lanes_identical is a byte comparison of the result arrays (and of the hit tables) of the two modes at the timed size; the run
+  fails if it is false.  pairs_lanes_*_packed_items is "last_search_pairs_packed_items" of the call under 16
 GCUPS = query letters x target letters / time of the call (torch events, median of --reps after --warmup)."""
 import argparse
 import importlib
@@ -104,6 +110,7 @@ def main():
     ap.add_argument("--prefiltered-top", action="store_true", help="data set (a) only: the top 10 of 64 queries by the full search and by pre-filter, rescoring and selection from the pair list")
     ap.add_argument("--pssm", action="store_true", help="data set (a) only: 64 PSSM queries derived from 64 sequence queries beside those, alternating")
     ap.add_argument("--lanes", action="store_true", help="data set (a) only: 64 queries under search_lanes 32 and 16, alternating, full tables and top 10")
+    ap.add_argument("--pairs-lanes", action="store_true", help="data set (a) only: pair lists of all, 10 %% and 1 %% of the cross product under search_pairs_lanes 32 and 16, alternating")
     ap.add_argument("--top", action="store_true", help="data set (a) only: the best 100 targets of 64 queries by the full table and by the selection on the device")
     args = ap.parse_args()
     rng = np.random.default_rng(2026)
@@ -646,6 +653,82 @@ def main():
                                      and out[f"{P}_search16_packed_launches"] > 0 and out[f"{P}_search32_packed_launches"] == 0)
         db.close()
 
+    def pairs_lanes_leg(packed, offs, nq=64, top=10, threshold=60, reps=7):
+        d_db = torch.from_numpy(packed.copy()).to(dev)
+        db = eng.prepare_db(d_db, offs)
+        nt = len(offs) - 1
+        lens = np.diff(offs)
+        qoffs = np.arange(nq + 1, dtype=np.int64) * args.qlen
+        d_q = torch.from_numpy(rng.choice(PROTEIN, int(qoffs[-1])).astype(np.uint8)).to(dev)
+        scoring = (sub, -11, -1)
+        prng = np.random.default_rng(7)                                      # (the generator and the draws of --pairs: its 1 % list and its full list)
+        flat_sparse = prng.choice(nq * nt, nq * nt // 100, replace=False).astype(np.int64)
+        flat_full = prng.permutation(nq * nt).astype(np.int64)
+        flat_tenth = prng.choice(nq * nt, nq * nt // 10, replace=False).astype(np.int64)
+        P = "pairs_lanes"
+        out[f"{P}_queries"], out[f"{P}_qlen"], out[f"{P}_targets"], out[f"{P}_reps"] = nq, args.qlen, nt, reps
+
+        def alternate(tag, call, cells=None):
+            """Medians and ranges of `reps` calls per mode after a warm-up, the modes alternating: a drift of the device shows in both alike."""
+            ms = {32: [], 16: []}
+            for _ in range(max(1, args.warmup)):
+                for lanes in (32, 16):
+                    call(lanes)
+            torch.cuda.synchronize()
+            for _ in range(reps):
+                for lanes in (32, 16):
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    e0.record()
+                    call(lanes)
+                    e1.record()
+                    torch.cuda.synchronize()
+                    ms[lanes].append(e0.elapsed_time(e1))
+                    out[f"{P}_{tag}{lanes}_launches"] = eng.get_option("last_search_pairs_launches")
+                    out[f"{P}_{tag}{lanes}_packed_launches"] = eng.get_option("last_search_pairs_packed_launches")
+                    out[f"{P}_{tag}{lanes}_packed_items"] = eng.get_option("last_search_pairs_packed_items")
+            for lanes in (32, 16):
+                med = float(np.median(ms[lanes]))
+                out[f"{P}_{tag}{lanes}_ms"], out[f"{P}_{tag}{lanes}_range_ms"] = round(med, 3), [round(min(ms[lanes]), 3), round(max(ms[lanes]), 3)]
+                if cells:
+                    out[f"{P}_{tag}{lanes}_gcups"] = round(cells / med / 1e6, 1)
+            out[f"{P}_{tag}_16_over_32"] = round(out[f"{P}_{tag}16_ms"] / out[f"{P}_{tag}32_ms"], 4)
+            out[f"{P}_{tag}_ranges_disjoint_in_favour_of_16"] = bool(out[f"{P}_{tag}16_range_ms"][1] < out[f"{P}_{tag}32_range_ms"][0])
+            return out[f"{P}_{tag}16_packed_launches"] > 0 and out[f"{P}_{tag}32_packed_launches"] == 0
+
+        same = True
+        for tag, flat in (("all", flat_full), ("tenth", flat_tenth), ("sparse", flat_sparse)):
+            pairs = np.stack([flat // nt, flat % nt], axis=1)
+            d_pairs = torch.from_numpy(pairs).to(dev)
+            res = {lanes: torch.full((len(flat) * 3,), -1, dtype=torch.int64, device=dev) for lanes in (32, 16)}
+
+            def call(lanes):
+                eng.set_option("search_pairs_lanes", lanes)
+                db.search_affine_pairs_device(d_q, qoffs, scoring, d_pairs, out=res[lanes])
+
+            cells = float(args.qlen) * float(lens[pairs[:, 1]].sum())
+            out[f"{P}_{tag}_n"], out[f"{P}_{tag}_cells"] = len(flat), int(cells)
+            routed = alternate(tag, call, cells)
+            out[f"{P}_{tag}_identical"] = bool(torch.equal(res[32], res[16]) and routed)
+            same = same and out[f"{P}_{tag}_identical"]
+            del d_pairs, res
+        # the one-call pipeline: pre-filter, rescoring, selection
+        cap = min(nq * nt, (eng.get_option("search_results_mib") << 20) // 56)
+        hits = {lanes: (torch.zeros(nq * top * 3, dtype=torch.int64, device=dev), torch.zeros(nq, dtype=torch.int64, device=dev)) for lanes in (32, 16)}
+        count = {}
+
+        def one_call(lanes):
+            eng.set_option("search_pairs_lanes", lanes)
+            _, _, count[lanes] = db.search_affine_top_prefiltered_device(d_q, qoffs, scoring, threshold, cap, top, 0, out=hits[lanes])
+
+        routed = alternate("one_call", one_call)
+        eng.set_option("search_pairs_lanes", 32)
+        torch.cuda.synchronize()
+        out[f"{P}_one_call_threshold"], out[f"{P}_one_call_cap"], out[f"{P}_one_call_count"] = threshold, cap, int(count[16].item())
+        out[f"{P}_one_call_identical"] = bool(torch.equal(hits[32][0], hits[16][0]) and torch.equal(hits[32][1], hits[16][1]) and int(count[32].item()) == int(count[16].item())
+                                              and int(count[16].item()) <= cap and routed)
+        out[f"{P}_identical"] = bool(same and out[f"{P}_one_call_identical"])
+        db.close()
+
     def align_ckpt_leg(q, packed, offs, nq=64):
         d_db = torch.from_numpy(packed.copy()).to(dev)
         db = eng.prepare_db(d_db, offs)
@@ -717,9 +800,11 @@ def main():
     out["a_letters"] = int(offs[-1])
     out["a_len_median"] = int(np.median(lens))
     out["a_len_max"] = int(lens.max())
-    if args.multi or args.top or args.align_hits or args.pairs or args.prefilter or args.prefiltered_top or args.pssm or args.lanes:
+    if args.multi or args.top or args.align_hits or args.pairs or args.prefilter or args.prefiltered_top or args.pssm or args.lanes or args.pairs_lanes:
         if args.lanes:
             lanes_leg(packed, offs)
+        if args.pairs_lanes:
+            pairs_lanes_leg(packed, offs)
         if args.pssm:
             pssm_leg(packed, offs)
         if args.pairs:
@@ -740,6 +825,8 @@ def main():
         print(json.dumps(out))
         if args.lanes and not out["lanes_identical"]:
             sys.exit("bench_search.py --lanes: lanes_identical is false")
+        if args.pairs_lanes and not out["pairs_lanes_identical"]:
+            sys.exit("bench_search.py --pairs-lanes: pairs_lanes_identical is false")
         if args.pssm and not out["pssm_identical"]:
             sys.exit("bench_search.py --pssm: pssm_identical is false")
         if args.pairs:   # the required conditions of the pair-list call: a line that misses one is printed, and the run fails

@@ -724,7 +724,9 @@ class Database:
     def search_affine_pairs(self, queries, scoring, pairs):
         """The scores of a list of (query, target) pairs (sw_db_search_affine_pairs): queries and scoring as for search_affine; pairs an
         (npairs, 2) int64 array or a list of (query, target) tuples, any order, duplicates allowed.  Returns the (npairs, 3) int64 numpy
-        array of (max_pos, max_score, path_len = 0) in list order; an entry that names no query, no target or an empty target is zero."""
+        array of (max_pos, max_score, path_len = 0) in list order; an entry that names no query, no target or an empty target is zero.
+        Engine.set_option("search_pairs_lanes", 16) runs two listed pairs of a query per wave on packed 16-bit lanes where the query is
+        eligible (include/swhip.h says when); the results are the same bytes under 16 and 32."""
         eng = self.engine
         t = eng.torch
         dev = f"cuda:{eng.device}"
@@ -739,7 +741,9 @@ class Database:
     def search_affine_pairs_device(self, d_queries, qoffsets, scoring, d_pairs, out=None):
         """sw_db_search_affine_pairs on device-resident queries and a device pair list, a contiguous torch int64 tensor of shape
         (npairs, 2); asynchronous on torch's current stream, nothing comes to the host.  Returns the (npairs, 3) int64 result tensor
-        (a view of `out`, a flat int64 tensor of at least npairs * 3 elements, if given)."""
+        (a view of `out`, a flat int64 tensor of at least npairs * 3 elements, if given).  The option "search_pairs_lanes" applies as for
+        search_affine_pairs; after a call under 16 "last_search_pairs_packed_launches" and "last_search_pairs_packed_items" say what ran
+        packed (reading the second waits for the device)."""
         eng = self.engine
         t = eng.torch
         qoffs = np.ascontiguousarray(qoffsets, np.int64).reshape(-1)
@@ -854,7 +858,8 @@ class Database:
     def search_affine_top_prefiltered(self, queries, scoring, prefilter_min_score: int, top: int, min_score: int = 0, cap=None):
         """Filter, rescoring and selection in one call on host queries (sw_db_search_affine_top_prefiltered): the table of
         search_affine_top restricted to the pairs whose ungapped score reaches prefilter_min_score.  cap, the length of the pair list,
-        defaults to nqueries x ntargets; SwError if more pairs pass than it holds.  Returns numpy (hits, nhits, npairs)."""
+        defaults to nqueries x ntargets; SwError if more pairs pass than it holds.  Returns numpy (hits, nhits, npairs).  The rescoring
+        follows the option "search_pairs_lanes" as search_affine_pairs does; the hits are the same under 16 and 32."""
         eng = self.engine
         t = eng.torch
         qpacked, qoffs = _pack_targets(queries)
@@ -873,7 +878,7 @@ class Database:
         """sw_db_search_affine_top_prefiltered on device-resident queries; asynchronous on torch's current stream, nothing comes to the
         host.  Returns torch (hits (nqueries, top, 3), nhits (nqueries,), npairs (1,)): the table and the pre-filter's TRUE count --
         where it exceeds cap the table is neither complete nor reproducible, the caller checks.  `out` = (hits, nhits) as for
-        search_affine_top_device."""
+        search_affine_top_device.  The rescoring follows the option "search_pairs_lanes" (search_affine_pairs_device)."""
         eng = self.engine
         t = eng.torch
         qoffs = np.ascontiguousarray(qoffsets, np.int64).reshape(-1)

@@ -27,6 +27,9 @@
 //                              per line, "<query record> <target record>", 0-based; '#' lines and blank lines are skipped.  One line per pair in input
 //                              order: query record, target record, the target's name, score, target_end, query_end (a pair outside the files: name "-",
 //                              zeros).  --matrix, --gap-open, --gap-extend or --scores as for --all-queries; not with --all-queries, --top, --min-score, --align
+//     ... --pairs-lanes 16|32  with --pairs or --prefilter-hits: option "search_pairs_lanes" -- 16 rescoring runs two listed pairs of a query per wave on
+//                              packed 16-bit lanes for every query whose scores fit them (include/swhip.h has the rule), 32 (the default) one pair per
+//                              wave; the printed lines are the same.  Nowhere else
 //     ... --align             every printed hit is followed by its alignment (sw_align_affine_device; the canonical alignment of swhip.h), four lines:
 //                                "align\t<q_begin>\t<q_end>\t<t_begin>\t<t_end>\t<nops>"   query [q_begin, q_end) against target [t_begin, t_end), 0-based, half open
 //                                "Q <query letters, '-' where the target has letters of its own>"
@@ -235,7 +238,7 @@ static int search_main(const char* qpath, long long rec, const char* dbpath, lon
 // --prefilter-hits S (prefilter_hits > 0): sw_db_search_affine_top_prefiltered takes the place of sw_db_search_affine_top -- the hits are
 // selected among the pairs whose ungapped score reaches S, on the device from the rescored pair list; everything else is the same.
 static int search_all_main(const char* qpath, const char* dbpath, long long top, long long min_score, const sw_scores& sc, const AffineArgs& af, bool align,
-                           bool align_ckpt, long long prefilter_hits = 0, int search_lanes = 32) {
+                           bool align_ckpt, long long prefilter_hits = 0, int search_lanes = 32, int pairs_lanes = 32) {
     int64_t nq = 0, qtotal = 0, nrec = 0, total = 0;
     CHECK(sw_read_fasta_db(qpath, nullptr, 0, nullptr, 0, &nq, &qtotal));
     std::vector<char> qs((size_t)qtotal + 1);
@@ -256,6 +259,7 @@ static int search_all_main(const char* qpath, const char* dbpath, long long top,
     // --align-checkpoint: a table the one call would refuse for its worst pair goes through it checkpointed instead of query by query
     if (align_ckpt) CHECK(sw_set_option(ctx, "align_checkpoint", 2));
     CHECK(sw_set_option(ctx, "search_lanes", search_lanes));
+    CHECK(sw_set_option(ctx, "search_pairs_lanes", pairs_lanes));
     void *d_q = nullptr, *d_db = nullptr, *d_res = nullptr, *d_hits = nullptr, *d_nhits = nullptr, *d_npairs = nullptr;
     // the pair list of --prefilter-hits: every pair, or as many as "search_results_mib" lets the call hold (56 bytes each)
     const int64_t pairs_cap = std::min<int64_t>(nq * nrec, (sw_get_option(ctx, "search_results_mib") << 20) / 56);
@@ -469,7 +473,7 @@ static std::vector<std::string> fasta_names(const char* path) {
 // --search --pairs FILE: the listed (query record, target record) pairs through ONE prepared handle and one call
 // (sw_db_create / sw_db_search_affine_pairs), one output line per pair in input order.  A linear search goes through the match /
 // mismatch table of --scores with gap_open 0, as --all-queries does.
-static int search_pairs_main(const char* qpath, const char* dbpath, const char* ppath, const sw_scores& sc, const AffineArgs& af) {
+static int search_pairs_main(const char* qpath, const char* dbpath, const char* ppath, const sw_scores& sc, const AffineArgs& af, int pairs_lanes = 32) {
     std::vector<sw_pair> pairs;
     {
         FILE* f = fopen(ppath, "r");
@@ -512,6 +516,7 @@ static int search_pairs_main(const char* qpath, const char* dbpath, const char* 
     const int64_t np = (int64_t)pairs.size();
     sw_ctx* ctx = nullptr;
     CHECK(sw_create(0, &ctx));
+    CHECK(sw_set_option(ctx, "search_pairs_lanes", pairs_lanes));
     void *d_q = nullptr, *d_db = nullptr, *d_pairs = nullptr, *d_res = nullptr;
     CHECK(sw_device_malloc(ctx, (size_t)qtotal + 16, &d_q));
     CHECK(sw_device_malloc(ctx, (size_t)total + 16, &d_db));
@@ -640,8 +645,8 @@ int main(int argc, char** argv) {
     const char *pairs_path = nullptr, *pssm_path = nullptr;
     AffineArgs af;
     bool align = false, all_queries = false, align_ckpt = false;
-    int search_lanes = 32;
-    bool has_search_lanes = false;
+    int search_lanes = 32, pairs_lanes = 32;
+    bool has_search_lanes = false, has_pairs_lanes = false;
     sw_scores sc = {3, -3, -2};
     int npos = 0;
     for (int ai = 1; ai < argc; ++ai) {
@@ -667,6 +672,7 @@ int main(int argc, char** argv) {
         else if (f == "--prefilter" && ai + 1 < argc) { int v = 0; if (!parse_int("--prefilter", argv[++ai], &v)) return 2; prefilter = v; has_prefilter = true; }
         else if (f == "--prefilter-hits" && ai + 1 < argc) { int v = 0; if (!parse_int("--prefilter-hits", argv[++ai], &v)) return 2; prefilter_hits = v; has_prefilter_hits = true; }
         else if (f == "--search-lanes" && ai + 1 < argc) { if (!parse_int("--search-lanes", argv[++ai], &search_lanes)) return 2; has_search_lanes = true; }
+        else if (f == "--pairs-lanes" && ai + 1 < argc) { if (!parse_int("--pairs-lanes", argv[++ai], &pairs_lanes)) return 2; has_pairs_lanes = true; }
         else if (f == "--matrix" && ai + 1 < argc) { af.matrix = argv[++ai]; af.on = true; }
         else if (f == "--gap-open" && ai + 1 < argc) { if (!parse_int("--gap-open", argv[++ai], &af.open)) return 2; af.has_open = af.on = true; }
         else if (f == "--gap-extend" && ai + 1 < argc) { if (!parse_int("--gap-extend", argv[++ai], &af.extend)) return 2; af.has_extend = true; }
@@ -677,7 +683,7 @@ int main(int argc, char** argv) {
         else if (f == "--record-b" && ai + 1 < argc) rec_b = strtoll(argv[++ai], nullptr, 10);
         else if (f == "--seed" && ai + 1 < argc) seed = (unsigned)strtoul(argv[++ai], nullptr, 10);
         else if (f == "--scores" && ai + 3 < argc) { sc.match = atoi(argv[++ai]); sc.mismatch = atoi(argv[++ai]); sc.gap = atoi(argv[++ai]); }
-        else { fprintf(stderr, "usage: smithW [<cols> <rows> | --fasta A.fa B.fa [--record-a I] [--record-b J] | --search QUERY.fa DB.fa [--record-a I] [--top K] [--all-queries [--min-score S] [--prefilter S | --prefilter-hits S] [--search-lanes 16|32]] [--pairs FILE] [--matrix FILE] [--gap-open O] [--gap-extend E] [--align [--align-checkpoint]] | --search --pssm FILE DB.fa --gap-open O --gap-extend E [--top K] [--min-score S] [--align] [--search-lanes 16|32]] [--seed N] [--dump | --dump-labels] [--h64] [--no-backtrack] [--scores M X G] [--gpus N | --devices 0,1,..] [--p8]\n"); return 2; }
+        else { fprintf(stderr, "usage: smithW [<cols> <rows> | --fasta A.fa B.fa [--record-a I] [--record-b J] | --search QUERY.fa DB.fa [--record-a I] [--top K] [--all-queries [--min-score S] [--prefilter S | --prefilter-hits S [--pairs-lanes 16|32]] [--search-lanes 16|32]] [--pairs FILE [--pairs-lanes 16|32]] [--matrix FILE] [--gap-open O] [--gap-extend E] [--align [--align-checkpoint]] | --search --pssm FILE DB.fa --gap-open O --gap-extend E [--top K] [--min-score S] [--align] [--search-lanes 16|32]] [--seed N] [--dump | --dump-labels] [--h64] [--no-backtrack] [--scores M X G] [--gpus N | --devices 0,1,..] [--p8]\n"); return 2; }
     }
     if (npos == 1) { fprintf(stderr, "smithW: <cols> needs <rows>\n"); return 2; }
     if (align_ckpt && !(search_q && align)) { fprintf(stderr, "smithW: --align-checkpoint goes with --search --align\n"); return 2; }
@@ -685,6 +691,10 @@ int main(int argc, char** argv) {
         if (search_lanes != 16 && search_lanes != 32) { fprintf(stderr, "smithW: --search-lanes takes 16 or 32, got %d\n", search_lanes); return 2; }
         if (!pssm_path && !(search_q && all_queries)) { fprintf(stderr, "smithW: --search-lanes goes with --search --all-queries or --search --pssm\n"); return 2; }
         if (has_prefilter || has_prefilter_hits || pairs_path) { fprintf(stderr, "smithW: --search-lanes does not go with --prefilter / --prefilter-hits / --pairs\n"); return 2; }
+    }
+    if (has_pairs_lanes) {   // the rescoring of a pair list alone has this choice
+        if (pairs_lanes != 16 && pairs_lanes != 32) { fprintf(stderr, "smithW: --pairs-lanes takes 16 or 32, got %d\n", pairs_lanes); return 2; }
+        if (!search_q || pssm_path || !(pairs_path || has_prefilter_hits)) { fprintf(stderr, "smithW: --pairs-lanes goes with --search --pairs or --search --all-queries --prefilter-hits\n"); return 2; }
     }
     if (pssm_path) {   // the matrix is the query and the scoring at once
         if (af.matrix) { fprintf(stderr, "smithW: --pssm does not go with --matrix\n"); return 2; }
@@ -732,14 +742,14 @@ int main(int argc, char** argv) {
                 fprintf(stderr, "smithW: --pairs without --matrix needs --scores M X within -128..127 (a table of signed bytes), got %d %d\n", sc.match, sc.mismatch);
                 return 2;
             }
-            return search_pairs_main(search_q, search_db, pairs_path, sc, af);
+            return search_pairs_main(search_q, search_db, pairs_path, sc, af, pairs_lanes);
         }
         if (all_queries) {
             if (!af.matrix && (sc.match < -128 || sc.match > 127 || sc.mismatch < -128 || sc.mismatch > 127)) {
                 fprintf(stderr, "smithW: --all-queries without --matrix needs --scores M X within -128..127 (a table of signed bytes), got %d %d\n", sc.match, sc.mismatch);
                 return 2;
             }
-            return search_all_main(search_q, search_db, top, min_score, sc, af, align, align_ckpt, prefilter_hits, search_lanes);
+            return search_all_main(search_q, search_db, top, min_score, sc, af, align, align_ckpt, prefilter_hits, search_lanes, pairs_lanes);
         }
         if (has_min_score) { fprintf(stderr, "smithW: --min-score goes with --search --all-queries\n"); return 2; }
         return search_main(search_q, rec_a, search_db, top, sc, af, align, align_ckpt);

@@ -69,6 +69,8 @@ void sw_destroy(sw_ctx* c) {
     if (c->d_ahfilled) (void)hipFree(c->d_ahfilled);
     if (c->d_spitems) (void)hipFree(c->d_spitems);
     if (c->d_spctl) (void)hipFree(c->d_spctl);
+    if (c->d_spcells) (void)hipFree(c->d_spcells);
+    if (c->d_sptotal) (void)hipFree(c->d_sptotal);
     if (c->d_pfctl) (void)hipFree(c->d_pfctl);
     if (c->d_mq) (void)hipFree(c->d_mq);
     if (c->h_mq) (void)hipHostFree(c->h_mq);
@@ -135,6 +137,11 @@ int sw_set_option(sw_ctx* c, const char* name, int64_t v) {
     if (!strcmp(name, "search_pairs_chunk")) {
         if (v < 1 || v > swp::kSearchPairsChunkMax) { set_err("search_pairs_chunk must be 1..2^31 - 1"); return SW_EINVAL; }
         c->opt_search_pairs_chunk = v;
+        return SW_OK;
+    }
+    if (!strcmp(name, "search_pairs_lanes")) {
+        if (v != 32 && v != 16) { set_err("search_pairs_lanes must be 32 (one pair per wave) or 16 (two pairs of a query per wave on packed lanes where the query is eligible)"); return SW_EINVAL; }
+        c->opt_search_pairs_lanes = v;
         return SW_OK;
     }
     if (!strcmp(name, "prefilter_lanes")) {
@@ -229,6 +236,15 @@ int64_t sw_get_option(sw_ctx* c, const char* name) {
     if (!strcmp(name, "last_search_pairs_groups")) return c->last_search_pairs_groups;
     if (!strcmp(name, "last_search_pairs_chunks")) return c->last_search_pairs_chunks;
     if (!strcmp(name, "last_search_pairs_launches")) return c->last_search_pairs_launches;
+    if (!strcmp(name, "search_pairs_lanes")) return c->opt_search_pairs_lanes;
+    if (!strcmp(name, "last_search_pairs_packed_launches")) return c->last_search_pairs_packed_launches;
+    if (!strcmp(name, "last_search_pairs_packed_items")) {   // counted on the device: waits for it, then reads the one word back
+        unsigned long long n = 0;
+        if (!c->d_sptotal || c->last_search_pairs_packed_launches == 0) return 0;
+        if (hipSetDevice(c->device) != hipSuccess || hipDeviceSynchronize() != hipSuccess ||
+            hipMemcpy(&n, c->d_sptotal, sizeof n, hipMemcpyDeviceToHost) != hipSuccess) return -1;
+        return (int64_t)n;
+    }
     if (!strcmp(name, "prefilter_lanes")) return c->opt_prefilter_lanes;
     if (!strcmp(name, "last_prefilter_groups")) return c->last_prefilter_groups;
     if (!strcmp(name, "last_prefilter_launches")) return c->last_prefilter_launches;

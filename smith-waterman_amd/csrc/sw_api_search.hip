@@ -85,6 +85,15 @@ static constexpr Indexed<SearchPairsKernel> kSearchPairs[] = {
 };
 static_assert(std::size(kSearchPairs) == swp::kSearchPairsKernels && at_their_indices(kSearchPairs));
 
+// the instantiations of its packed form (sw_search_pairs16.hip: two pairs of a query per wave), picked by swp::plan_search_pairs_lanes
+using SearchPairsPackedKernel = void (*)(swk::SearchPairsPackedParams);
+static constexpr Indexed<SearchPairsPackedKernel> kSearchPairsPacked[] = {
+    {swp::search_pairs_kernel_index(4), swk::sw_search_pairs_pk_wave<4>},
+    {swp::search_pairs_kernel_index(8), swk::sw_search_pairs_pk_wave<8>},
+    {swp::search_pairs_kernel_index(16), swk::sw_search_pairs_pk_wave<16>},
+};
+static_assert(std::size(kSearchPairsPacked) == swp::kSearchPairsKernels && at_their_indices(kSearchPairsPacked));
+
 // the instantiations of the pre-filter kernels (sw_prefilter.hip), picked by swp::plan_prefilter
 using PrefilterKernel = void (*)(swk::PrefilterParams);
 static constexpr Indexed<PrefilterKernel> kPrefilter[] = {
@@ -876,6 +885,8 @@ int sw_db_align_pssm_hits(sw_ctx* c, const sw_db* db, const int8_t* d_pssm, cons
 // handle's longest target; the pairs and the targets' offsets are read on the device only.  One memset zeroes the call's results up
 // front -- the pairs that never become an item keep it, the binning writes no result --, then per group one profile launch and per
 // chunk of the list two binning launches and one score launch per class of the group, its grid planned for the most its list could hold.
+// Under "search_pairs_lanes" = 16 a group that holds packed queries gets the three binning launches of csrc/sw_search_pairs16.hip instead,
+// and a class a packed score launch ahead of the 32-bit one; under 32 the plan, and so every launch, is swp::plan_search_pairs's.
 int sw_db_search_affine_pairs(sw_ctx* c, const sw_db* db, const char* d_queries, const int64_t* qoffsets, int64_t nqueries, const sw_affine* scoring,
                               const sw_pair* d_pairs, int64_t npairs, sw_result* d_results, void* stream_) {
     if (!c || !db || !d_queries || !qoffsets || !scoring) { set_err("sw_db_search_affine_pairs: NULL pointer"); return SW_EINVAL; }
@@ -885,6 +896,7 @@ int sw_db_search_affine_pairs(sw_ctx* c, const sw_db* db, const char* d_queries,
     if (npairs < 0) { set_err("sw_db_search_affine_pairs: negative pair count"); return SW_EINVAL; }
     if (npairs > 0 && (!d_pairs || !d_results)) { set_err("sw_db_search_affine_pairs: NULL d_pairs or d_results with %lld pairs", (long long)npairs); return SW_EINVAL; }
     c->last_search_pairs_groups = c->last_search_pairs_chunks = c->last_search_pairs_launches = 0;   // (a call that launches no kernel reports none)
+    c->last_search_pairs_packed_launches = 0;
     if (npairs == 0) return SW_OK;
     hipStream_t stream = (hipStream_t)stream_;
     HIP_TRY(hipSetDevice(c->device));
@@ -894,24 +906,37 @@ int sw_db_search_affine_pairs(sw_ctx* c, const sw_db* db, const char* d_queries,
     HIP_TRY(hipMemsetAsync(d_results, 0, (size_t)npairs * sizeof(sw_result), stream));
     if (nqueries == 0 || db->nonempty == 0) return SW_OK;
     if (int rc = occupancy_once(kSearchPairs, c->search_pairs_per_cu, c->search_pairs_per_cu_known)) return rc;
+    const bool lanes16 = c->opt_search_pairs_lanes == 16;
+    if (lanes16)
+        if (int rc = occupancy_once(kSearchPairsPacked, c->search_pairs_packed_per_cu, c->search_pairs_packed_per_cu_known)) return rc;
+    const QuerySource src = QuerySource::sequences(d_queries, scoring);
     const std::vector<int64_t> qlens = query_lengths(qoffsets, nqueries);
-    swp::SearchPairsJob pj;
+    swp::SearchPairsLanesJob pj;
     pj.qlens = qlens.data(); pj.nqueries = nqueries; pj.npairs = npairs; pj.longest = db->longest; pj.num_cus = c->num_cus;
     pj.budget_bytes = c->opt_search_profile_mib << 20; pj.chunk = c->opt_search_pairs_chunk;
     std::copy(std::begin(c->search_pairs_per_cu), std::end(c->search_pairs_per_cu), pj.per_cu);
-    const swp::SearchPairsPlan plan = swp::plan_search_pairs(pj);
-    for (const swp::PairsLaunch& l : plan.launch)
-        if (c->search_pairs_per_cu[l.kernel] < 1) { set_err("the pair-list search kernel does not fit a CU on this device"); return SW_EDEVICE; }
+    pj.lanes = (int)c->opt_search_pairs_lanes; pj.gap_open = scoring->gap_open; pj.gap_extend = scoring->gap_extend;
+    if (lanes16) {   // (the 32-bit plan asks for neither)
+        std::copy(std::begin(c->search_pairs_packed_per_cu), std::end(c->search_pairs_packed_per_cu), pj.packed_per_cu);
+        pj.max_entry = src.max_entry();
+    }
+    const swp::SearchPairsLanesPlan plan = swp::plan_search_pairs_lanes(pj);
+    for (const swp::PairsLanesLaunch& l : plan.launch)
+        if ((l.packed ? c->search_pairs_packed_per_cu : c->search_pairs_per_cu)[l.kernel] < 1) { set_err("the pair-list search kernel does not fit a CU on this device"); return SW_EDEVICE; }
     if (int rc = stage_search_call(c, stream, 0, plan.prof_need, plan.bnd_need, true)) return rc;
     bool fresh = false;
     if (int rc = grow_workspace((void**)&c->d_spitems, c->spitems_cap, plan.items_need, 1, 0, stream, fresh)) return rc;
     if (!c->d_spctl) HIP_TRY(hipMalloc((void**)&c->d_spctl, sizeof(swk::SearchPairsCtl)));
+    if (plan.cells_need) {   // the cells of the packed queries and the call's count of two-pair items, which starts at zero
+        if (int rc = grow_workspace((void**)&c->d_spcells, c->spcells_cap, plan.cells_need, 1, 0, stream, fresh)) return rc;
+        if (!c->d_sptotal) HIP_TRY(hipMalloc((void**)&c->d_sptotal, sizeof(unsigned long long)));
+        HIP_TRY(hipMemsetAsync(c->d_sptotal, 0, sizeof(unsigned long long), stream));
+    }
     // behind the table's nqueries entries: entry_of (4 bytes per query)
-    const QuerySource src = QuerySource::sequences(d_queries, scoring);
     if (int rc = upload_query_table(c, stream, plan.table, qoffsets, src, plan.entry_of.data(), (size_t)nqueries * sizeof(int32_t))) return rc;
     size_t l0 = 0;
     for (size_t g = 0; g < plan.group.size(); ++g) {
-        const swp::PairsGroup& grp = plan.group[g];
+        const swp::PairsLanesGroup& grp = plan.group[g];
         if (int rc = launch_group_profiles(c, stream, src, grp)) return rc;
         size_t l1 = l0;
         while (l1 < plan.launch.size() && plan.launch[l1].group == (int)g) ++l1;
@@ -927,12 +952,45 @@ int sw_db_search_affine_pairs(sw_ctx* c, const sw_db* db, const char* d_queries,
             std::copy(std::begin(grp.cls_q0), std::end(grp.cls_q0), bp.cls_q0);
             bp.ctl = c->d_spctl; bp.items = c->d_spitems;
             const unsigned bin_blocks = (unsigned)std::clamp<int64_t>((np + 255) / 256, 1, 4096);
-            hipLaunchKernelGGL(swk::sw_search_pairs_bin<false>, dim3(bin_blocks), dim3(256), 0, stream, bp);
-            HIP_TRY(hipGetLastError());
-            hipLaunchKernelGGL(swk::sw_search_pairs_bin<true>, dim3(bin_blocks), dim3(256), 0, stream, bp);
-            HIP_TRY(hipGetLastError());
+            if (grp.cells) {   // a group with packed queries: count, scan, scatter (sw_search_pairs16.hip)
+                swk::SearchPairsPackedCtl* const pk = (swk::SearchPairsPackedCtl*)c->d_spcells;
+                // its control words, counts and cursors start at zero; the scan writes every base
+                HIP_TRY(hipMemsetAsync(c->d_spcells, 0, (size_t)(swp::kSearchPairsCellsHead + 8 * grp.cells), stream));
+                swk::SearchPairsPackedBinParams kp;
+                memset(&kp, 0, sizeof kp);
+                kp.bin = bp;
+                std::copy(std::begin(grp.pk_q1), std::end(grp.pk_q1), kp.pk_q1);
+                kp.cells = grp.cells; kp.pk = pk; kp.total = c->d_sptotal;
+                hipLaunchKernelGGL(swk::sw_search_pairs_pk_bin<false>, dim3(bin_blocks), dim3(256), 0, stream, kp);
+                HIP_TRY(hipGetLastError());
+                hipLaunchKernelGGL(swk::sw_search_pairs_pk_scan, dim3(1), dim3(256), 0, stream, kp);
+                HIP_TRY(hipGetLastError());
+                hipLaunchKernelGGL(swk::sw_search_pairs_pk_bin<true>, dim3(bin_blocks), dim3(256), 0, stream, kp);
+                HIP_TRY(hipGetLastError());
+            } else {
+                hipLaunchKernelGGL(swk::sw_search_pairs_bin<false>, dim3(bin_blocks), dim3(256), 0, stream, bp);
+                HIP_TRY(hipGetLastError());
+                hipLaunchKernelGGL(swk::sw_search_pairs_bin<true>, dim3(bin_blocks), dim3(256), 0, stream, bp);
+                HIP_TRY(hipGetLastError());
+            }
             for (size_t li = l0; li < l1; ++li) {
-                const swp::PairsLaunch& l = plan.launch[li];
+                const swp::PairsLanesLaunch& l = plan.launch[li];
+                const unsigned grid = (unsigned)swp::search_pairs_lanes_grid(l, np, grp.cells);
+                if (l.packed) {   // two pairs of a query per wave: the class's two-pair items at the head of the item buffer
+                    swk::SearchPairsPackedCtl* const pk = (swk::SearchPairsPackedCtl*)c->d_spcells;
+                    swk::SearchPairsPackedParams kp;
+                    memset(&kp, 0, sizeof kp);
+                    kp.db = (const unsigned char*)db->d_db;
+                    kp.items = (const swk::SearchPairItem2*)c->d_spitems; kp.list = &pk->list[l.kernel];
+                    kp.queries = c->d_mq; kp.prof = c->d_sprof;
+                    kp.ge = scoring->gap_extend; kp.goe = scoring->gap_open + scoring->gap_extend;
+                    kp.bnd = l.bnd_per ? c->d_sbnd : nullptr; kp.bnd_per = l.bnd_per;
+                    kp.counter = &pk->work[l.kernel];
+                    kp.results = d_results;
+                    hipLaunchKernelGGL(kSearchPairsPacked[l.kernel].k, dim3(grid), dim3(256), 0, stream, kp);
+                    HIP_TRY(hipGetLastError());
+                    continue;
+                }
                 swk::SearchPairsParams sp;
                 memset(&sp, 0, sizeof sp);
                 sp.db = (const unsigned char*)db->d_db;
@@ -942,13 +1000,14 @@ int sw_db_search_affine_pairs(sw_ctx* c, const sw_db* db, const char* d_queries,
                 sp.bnd = l.bnd_per ? c->d_sbnd : nullptr; sp.bnd_per = l.bnd_per;
                 sp.counter = &c->d_spctl->work[l.kernel];
                 sp.results = d_results;
-                hipLaunchKernelGGL(kSearchPairs[l.kernel].k, dim3((unsigned)swp::search_pairs_grid(l, np)), dim3(256), 0, stream, sp);
+                hipLaunchKernelGGL(kSearchPairs[l.kernel].k, dim3(grid), dim3(256), 0, stream, sp);
                 HIP_TRY(hipGetLastError());
             }
         }
         l0 = l1;
     }
     c->last_search_pairs_groups = (int64_t)plan.group.size(); c->last_search_pairs_chunks = plan.nchunks; c->last_search_pairs_launches = plan.launches;
+    c->last_search_pairs_packed_launches = plan.packed_launches;
     return SW_OK;
 }
 

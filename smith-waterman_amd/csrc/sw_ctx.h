@@ -151,6 +151,14 @@ struct SW_HIDDEN sw_ctx {
     int64_t last_search_pairs_groups = 0, last_search_pairs_chunks = 0, last_search_pairs_launches = 0;
     int search_pairs_per_cu[swp::kSearchPairsKernels] = {};     // occupancy of every sw_search_affine_pairs_wave instantiation at 256 threads ...
     bool search_pairs_per_cu_known = false;                     // ... queried at the first call
+    // the same call on packed 16-bit lanes (sw_search_pairs16.hip): "search_pairs_lanes" (32 / 16), the cell workspace of a (chunk, group)
+    // -- control words, then count, cursor and base of every cell --, the two-pair items the device built in the last call, its packed launches
+    int64_t opt_search_pairs_lanes = 32;
+    unsigned char* d_spcells = nullptr; size_t spcells_cap = 0;     // (bytes)
+    unsigned long long* d_sptotal = nullptr;                    // "last_search_pairs_packed_items"
+    int64_t last_search_pairs_packed_launches = 0;
+    int search_pairs_packed_per_cu[swp::kSearchPairsKernels] = {};   // occupancy of every sw_search_pairs_pk_wave instantiation at 256 threads ...
+    bool search_pairs_packed_per_cu_known = false;              // ... queried at the first call
     // the ungapped pre-filter (sw_db_prefilter_ungapped): its control words, "prefilter_lanes", what the last call did
     swk::PrefilterCtl* d_pfctl = nullptr;
     int64_t opt_prefilter_lanes = 0;

@@ -222,6 +222,43 @@ struct SearchPairsParams {
 template <int C>
 __global__ void sw_search_affine_pairs_wave(SearchPairsParams p);
 
+// sw_search_pairs16.hip: the same call with two pairs of one query per wave on packed 16-bit lanes ("search_pairs_lanes" = 16), for the
+// groups that hold packed queries (swp::plan_search_pairs_lanes).  Per (chunk, group) three binning launches -- count, scan, scatter --
+// pair the listed pairs of a packed query inside a bucket into two-pair items and keep the lists of the other queries as
+// sw_search_pairs_bin makes them; sw_search_pairs_pk_wave<C> scores the two-pair items of a class.
+struct SearchPairItem2 { SearchPairItem half[2]; };   // half 0 is never empty; an empty half 1 has len = 0 (the scan launch writes it)
+// the control words of a (chunk, group) at the head of the cell workspace, zero before its binning; behind them
+// (swp::kSearchPairsCellsHead bytes from the start) the cells' counts, cursors -- zero too -- and bases, `cells` words each
+struct SearchPairsPackedCtl {
+    SearchPairsList list[SW_SP_CLASSES];         // a class's two-pair items: how many, and the first one's index in the item buffer
+    unsigned int work[SW_SP_CLASSES];            // the work counters of the packed launches
+    unsigned int base32[SW_SP_CLASSES][SW_SP_BUCKETS];   // where the 32-bit items of a (class, bucket) start, in SearchPairItem units
+};
+static_assert(sizeof(SearchPairsPackedCtl) <= swp::kSearchPairsCellsHead);
+struct SearchPairsPackedBinParams {
+    SearchPairsBinParams bin;                    // what sw_search_pairs_bin takes; bin.items: the item buffer of the (chunk, group)
+    int64_t pk_q1[SW_SP_CLASSES];                // class k: the entries bin.cls_q0[k] .. pk_q1[k] - 1 run packed
+    int64_t cells;                               // SW_SP_BUCKETS x packed entries of the group
+    SearchPairsPackedCtl* pk;                    // the head of the cell workspace
+    unsigned long long* total;                   // two-pair items of the call so far ("last_search_pairs_packed_items")
+};
+template <bool SCATTER>
+__global__ void sw_search_pairs_pk_bin(SearchPairsPackedBinParams p);
+__global__ void sw_search_pairs_pk_scan(SearchPairsPackedBinParams p);
+struct SearchPairsPackedParams {
+    const unsigned char* db;             // the targets back to back
+    const SearchPairItem2* items;        // the (chunk, group)'s item buffer: the classes' two-pair lists back to back at its start
+    const SearchPairsList* list;         // this class's list (SearchPairsPackedCtl::list[k])
+    const MultiQuery* queries;           // the call's table
+    const signed char* prof;             // the group's profiles, query t at its prof_off
+    int ge, goe;                         // gap_extend, gap_open + gap_extend (both <= 0, gap_open + 2 gap_extend >= -32768)
+    int* bnd; int64_t bnd_per;           // per resident wave: boundary pairs (H, F) of both halves between strips (ints), as SearchPairsParams
+    unsigned int* counter;               // next item (zero at launch)
+    sw_result* results;                  // npairs, the order of the caller's list
+};
+template <int C>
+__global__ void sw_search_pairs_pk_wave(SearchPairsPackedParams p);
+
 // sw_prefilter.hip: the ungapped pre-filter (sw_db_prefilter_ungapped): the best gapless local score U of every (query, target) pair and
 // the list of the pairs with U >= min_score.  The items and the launches are swp::plan_prefilter's.
 struct PrefilterCtl {                    // the control words of a call

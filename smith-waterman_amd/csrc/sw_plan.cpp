@@ -613,6 +613,66 @@ SearchMultiLanesPlan plan_search_multi_lanes(const SearchMultiLanesJob& j) {
     return f;
 }
 
+// The pair list with a choice of lanes.  Everything but the order inside a class and the launches is plan_search_pairs's own answer: per
+// (group, class) the packed queries move to the front, every entry keeping its profile's place, and a class with both kinds gets two
+// score launches.  With no packed query nothing moves and nothing is added.  O(nqueries), as there.
+SearchPairsLanesPlan plan_search_pairs_lanes(const SearchPairsLanesJob& j) {
+    SearchPairsLanesPlan f;
+    SearchPairsPlan s = plan_search_pairs(j);
+    f.table = std::move(s.table);
+    f.chunk = s.chunk; f.nchunks = s.nchunks;
+    f.prof_need = s.prof_need; f.bnd_need = s.bnd_need; f.items_need = s.items_need;
+    const int64_t most = std::min(std::max<int64_t>(0, j.npairs), f.chunk);   // pairs of the largest chunk
+    int64_t binning = 0;                     // binning launches of one chunk
+    size_t li = 0;
+    for (size_t g = 0; g < s.group.size(); ++g) {
+        PairsLanesGroup grp;
+        static_cast<PairsGroup&>(grp) = s.group[g];
+        int64_t npacked = 0;
+        for (int k = 0; k < kSearchPairsKernels; ++k) {
+            const int64_t a = grp.cls_q0[k], b = grp.cls_q0[k + 1];
+            const int C = k == 0 ? 4 : 8 * k;
+            // (the packed kernel of 16 columns per lane is taken where it keeps the workgroups on a CU that the 32-bit one needs)
+            const bool fits = j.packed_per_cu[k] >= (C == 16 ? kAffineC16MinPerCu : 1);
+            auto packed = [&](const swk::MultiQuery& d) { return fits && search_multi_packed(j.max_entry, d.qlen, j.longest, j.gap_open, j.gap_extend, j.lanes); };
+            grp.pk_q1[k] = std::stable_partition(f.table.begin() + a, f.table.begin() + b, packed) - f.table.begin();
+            npacked += grp.pk_q1[k] - a;
+        }
+        grp.cells = kSearchPairsBuckets * npacked;
+        binning += npacked ? 3 : 2;
+        if (npacked) {
+            f.items_need = std::max(f.items_need, (size_t)search_pairs_lanes_item_bytes(most, grp.cells));
+            f.cells_need = std::max(f.cells_need, (size_t)(kSearchPairsCellsHead + 12 * grp.cells));
+        }
+        for (; li < s.launch.size() && s.launch[li].group == (int)g; ++li) {
+            const int k = s.launch[li].kernel;
+            for (int side = 0; side < 2; ++side) {
+                const bool pk = side == 0;
+                PairsLanesLaunch l;
+                static_cast<PairsLaunch&>(l) = s.launch[li];
+                l.packed = pk;
+                l.q0 = pk ? grp.cls_q0[k] : grp.pk_q1[k];
+                l.nq = (pk ? grp.pk_q1[k] : grp.cls_q0[k + 1]) - l.q0;
+                if (l.nq == 0) continue;
+                if (pk) {   // the waves the packed kernel keeps resident, under the class's boundary column
+                    l.max_grid = (int64_t)j.packed_per_cu[k] * j.num_cus;
+                    if (l.bnd_per) l.max_grid = std::min<int64_t>(l.max_grid, kSearchBndBytes / (l.bnd_per * 4 * 4));
+                    l.max_grid = std::max<int64_t>(1, l.max_grid);
+                    f.bnd_need = std::max(f.bnd_need, (size_t)(search_pairs_lanes_grid(l, most, grp.cells) * 4 * l.bnd_per));
+                    ++f.packed_launches;
+                }
+                f.launch.push_back(l);
+            }
+        }
+        f.group.push_back(grp);
+    }
+    f.entry_of.resize((size_t)j.nqueries);
+    for (int64_t t = 0; t < j.nqueries; ++t) f.entry_of[(size_t)f.table[(size_t)t].row] = (int32_t)t;
+    f.packed_launches *= f.nchunks;
+    f.launches = (int64_t)f.group.size() + f.nchunks * (binning + (int64_t)f.launch.size());
+    return f;
+}
+
 // The best `top` of every row.  Every row has the same length, so the chunks are uniform and the geometry of a row is decided once.
 // The passes take kTopDigitBits bits each from the top of the key down; the last one takes what is left.
 SearchTopPlan plan_search_top(const SearchTopJob& j) {

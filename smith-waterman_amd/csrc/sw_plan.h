@@ -378,6 +378,70 @@ struct SearchMultiLanesPlan {
 
 SearchMultiLanesPlan plan_search_multi_lanes(const SearchMultiLanesJob& job);
 
+// ---- the pair list with a choice of lanes ("search_pairs_lanes"; sw_search_pairs16.hip): sw_search_pairs_pk_wave<C> for C = 4, 8, 16
+// runs two listed pairs of one query per wave on packed 16-bit lanes; its index in kSearchPairsPacked (sw_api_search.hip, which checks
+// its order against it at compile time) is search_pairs_kernel_index(C).  The relation to plan_search_pairs is the relation of
+// plan_search_multi_lanes to plan_search_multi.
+// Queries: the groups, the classes, the chunks and every table entry are plan_search_pairs's for the 32-bit kernels' occupancy,
+// whatever the lanes; inside a (group, class) the entries of the queries that run packed come first, input order within either part,
+// and entry_of follows.  Packed: search_multi_packed's rule against the HANDLE's longest target -- a conservative bound for a list,
+// which may name shorter targets only -- and the packed kernel of the class fits a CU (16 columns per lane: kAffineC16MinPerCu).
+// lanes = 32 sends every query to the 32-bit kernel, and then the plan is plan_search_pairs's, field for field.
+// Cells: the device pairs the listed pairs of a packed query inside a bucket.  A group's cells are (packed entry, bucket), laid out
+// class after class, inside a class the heaviest bucket first, inside a bucket entry after entry (search_pairs_cell): a prefix sum in
+// that order gives every cell its place in the list of two-pair items.  A cell of n pairs takes ceil(n / 2) items.
+// Items: np pairs in `cells` cells make at most search_pairs_packed_items_max(np, cells) = min(np, floor((np + cells) / 2)) two-pair
+// items -- every cell holds at most one item with an empty half, and no more items than pairs --, and the bound is met (cells of one
+// pair each, the rest in one cell).  A two-pair item takes twice a pair's item (2 x 24 bytes), and the 32-bit items of the (chunk,
+// group) lie behind the two-pair items: every pair takes 24 bytes wherever it goes and every empty half another 24, one per cell at
+// most and no more than there are pairs, so a chunk of `most` pairs needs 24 x min(2 most, most + cells) bytes where a group has packed
+// queries; items_need is the largest of these and the 24 x most of plan_search_pairs.  cells_need: the counters of the largest
+// group's cells (count, cursor, base: 4 bytes each) behind kSearchPairsCellsHead bytes of control words.
+// Launches: a group WITHOUT packed queries is plan_search_pairs's: two binning launches per chunk and a score launch per class.  A group
+// with packed queries gets three binning launches per chunk (count, scan, scatter) and per class a packed score launch (if the class has
+// packed queries) followed by a 32-bit one (if it has others), both with the boundary workspace of the class.
+constexpr int64_t kSearchPairsCellsHead = 1024;
+constexpr int64_t search_pairs_packed_items_max(int64_t np, int64_t cells) { return np < (np + cells) / 2 ? np : (np + cells) / 2; }
+// bytes of the item workspace for a (chunk, group) of np pairs with `cells` cells: 24 per pair and 24 per empty half
+constexpr int64_t search_pairs_lanes_item_bytes(int64_t np, int64_t cells) { return 24 * (2 * np < np + cells ? 2 * np : np + cells); }
+// the cell of (entry t of class k, bucket b): cell0 = cells of the classes before, npk = packed entries of the class, t0 = its first entry
+constexpr int64_t search_pairs_cell(int64_t cell0, int64_t npk, int64_t t0, int64_t t, int b) { return cell0 + (int64_t)(kSearchPairsBuckets - 1 - b) * npk + (t - t0); }
+
+struct SearchPairsLanesJob : SearchPairsJob {    // per_cu: of the 32-bit kernels, as there
+    int packed_per_cu[kSearchPairsKernels] = {}; // occupancy of every sw_search_pairs_pk_wave instantiation at 256 threads (workgroups per CU)
+    int max_entry = 0;                       // the largest entry of the substitution table
+    int gap_open = 0, gap_extend = 0;
+    int lanes = 32;                          // "search_pairs_lanes": 32 never packed, 16 packed where a query is eligible
+};
+
+struct PairsLanesGroup : PairsGroup {
+    int64_t pk_q1[kSearchPairsKernels] = {}; // class k: its packed entries are cls_q0[k] .. pk_q1[k] - 1, the others pk_q1[k] .. cls_q0[k + 1] - 1
+    int64_t cells = 0;                       // kSearchPairsBuckets x packed entries of the group
+};
+struct PairsLanesLaunch : PairsLaunch {      // kernel: index in kSearchPairs, packed: in kSearchPairsPacked; q0, nq: its part of the class
+    bool packed = false;
+};
+// workgroups of a score launch for a chunk of `chunk_pairs` pairs: a packed launch has at most items_max(chunk_pairs, cells) items
+constexpr int64_t search_pairs_lanes_grid(const PairsLanesLaunch& l, int64_t chunk_pairs, int64_t cells) {
+    return search_pairs_grid(l, l.packed ? search_pairs_packed_items_max(chunk_pairs, cells) : chunk_pairs);
+}
+
+struct SearchPairsLanesPlan {
+    std::vector<swk::MultiQuery> table;      // as SearchPairsPlan::table, but for the order inside a (group, class)
+    std::vector<int32_t> entry_of;           // per query: its entry of the table
+    std::vector<PairsLanesGroup> group;
+    std::vector<PairsLanesLaunch> launch;    // the score launches of ONE chunk in the order they are enqueued: group after group, class after class, packed first
+    int64_t chunk = 0, nchunks = 0;          // as SearchPairsPlan
+    int64_t launches = 0;                    // kernel launches of the call: per group a profile launch, per (chunk, group) its binning and score launches
+    int64_t packed_launches = 0;             // ... the packed score launches among them
+    size_t prof_need = 0, bnd_need = 0, items_need = 0;   // workspaces as SearchPairsPlan
+    size_t cells_need = 0;                   // the cell workspace (bytes), 0 without a packed query
+    int64_t chunk_p0(int64_t i) const { return i * chunk; }
+    int64_t chunk_pairs(int64_t i, int64_t npairs) const { return npairs - i * chunk < chunk ? npairs - i * chunk : chunk; }
+};
+
+SearchPairsLanesPlan plan_search_pairs_lanes(const SearchPairsLanesJob& job);
+
 // ---- the best `top` targets of every row of a query-major result table (sw_top_hits_device, sw_db_search_affine_top; sw_search_top.hip).
 // Key: a target's key is score << tbits | (2^tbits - 1 - target) with tbits = ceil(log2 ntargets): unique per target, and plain integer
 // order of the keys is the rank order (score descending, target ascending).  nbits = 24 + tbits bits of a key can differ.
