@@ -209,7 +209,9 @@ int sw_batch_traceback_device(sw_ctx* ctx, void* d_P, int p_elem_bytes, int64_t 
  *   d_query      : device, qlen >= 1 bytes
  *   d_db         : device, the targets back to back; target k = d_db[offsets[k] .. offsets[k+1]), no alignment asked
  *   offsets      : HOST, ntargets + 1 non-decreasing int64 (offsets[0] may be > 0; empty targets allowed); the library
- *                  copies what it needs before returning, so the array may be reused at once
+ *                  copies what it needs before returning, so the array may be reused at once.  Here and in every call of the
+ *                  search family each offset, count, cap and stride is used as a 64-bit quantity end to end -- on the host, in the
+ *                  kernels' addresses and in the workspaces -- and placement beyond 4 GiB is tested (tests/test_far_gpu.py)
  *   d_results    : device, ntargets sw_result in INPUT order: max_score, max_pos = r*(qlen+1)+c in target k's own
  *                  (len_k+1) x (qlen+1) matrix, lowest index among ties, 0 if no cell is positive; path_len = 0
  * Any byte value is a letter (bytes compared as in matchMissmatchScore, serial_smithW.c:251-256).  Asynchronous on
