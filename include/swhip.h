@@ -608,6 +608,68 @@ int  sw_pssm_from_queries(const char* queries, const int64_t* qoffsets, int64_t 
                           int32_t nletters, int8_t* out);
 int  sw_read_pssm(const char* path, char* letters_out, int32_t* nletters, int8_t* pssm, int64_t cap, int64_t* ncols);
 
+/* The NEXT iteration's PSSM, built on the device from aligned hits (csrc/sw_pssm_hits.hip): the step that closes the loop
+ *   sw_db_search_pssm_top -> sw_db_align_pssm_hits -> sw_db_pssm_from_hits -> sw_db_search_pssm_top -> ...
+ * It takes the hit table, the alignments and the ops exactly as the first two calls leave them on the device and writes a PSSM that
+ * goes straight back into the first.  The arithmetic is integers only -- no log, no floats --, so device and host agree bit for bit;
+ * a caller who wants true log-odds takes the exact count matrix (d_counts) and does the small float step alone.  The score rule is
+ * Gribskov's average profile: a column's new row is the weighted mean of its prior row and of the substitution-table rows of the
+ * residues observed in that column.
+ *   d_prior, d_pssm_out : device, int8, the layout of d_pssm (column g at + g * nletters), indexed by the same qoffsets.  Only the
+ *               columns [qoffsets[0], qoffsets[nqueries]) are written.  d_pssm_out == d_prior (exactly the same buffer) is allowed;
+ *               any other overlap is the caller's error.  d_pssm_out may be NULL where d_counts is not.
+ *   scoring   : letters, nletters and smax are used (other and the gap costs are checked as everywhere, and not used).
+ *   upd       : sub, the table S is taken from; prior_weight 0..65535; include_min_score.
+ *   d_hits, d_nhits, top, d_aln, d_ops, ops_cap : the tables of sw_db_align_pssm_hits / sw_db_align_affine_hits; d_ops is required,
+ *               ops_cap >= 1.  Only read.
+ *   d_weights : device, optional: nqueries x top int32, the weight of entry (q, r); NULL: every weight is 1.
+ *   d_counts  : device, optional: (qoffsets[nqueries] - qoffsets[0]) x nletters int32, rebased to the first query's first column like the
+ *               output of sw_pssm_from_queries; every entry is written.
+ * Notation: query q has qlen columns j (0-based) at column g = qoffsets[q] + j.  P[j][k] = min(prior entry, smax).
+ * S[b][k] = sub->s[(uint8) letters[b]][(uint8) letters[k]]: the observed residue plays the query letter.
+ * USED ENTRIES.  Entry (q, r) is used when ALL of these hold:  r < clamp(d_nhits[q], 0, top) (d_nhits == NULL: all top entries);
+ *   d_hits[q * top + r].target, compared unsigned, < ntargets;  d_aln[q * top + r].max_score >= include_min_score;  0 < nops <= ops_cap;
+ *   q_begin and t_begin, compared unsigned, <= qlen and <= the target's length.  Each index is compared before anything is loaded
+ *   through it (the rule of sw_db_align_affine_hits).
+ * THE WALK of a used entry starts at j = q_begin, i = t_begin and goes through its nops op bytes in order:
+ *   'M': if j < qlen and i < len the entry PAIRS column j with the target byte t[i]; then j++, i++.
+ *   'I': j++ (consumes a query letter).   'D': i++.   Any other byte consumes nothing.
+ *   So the call is defined for ANY bytes in the tables and reads nothing out of bounds; for tables that come from the alignment calls
+ *   none of the guards ever fires.
+ * WEIGHTS.  w(q, r) = d_weights ? clamp(d_weights[q * top + r], 0, 65535) : 1 -- taken as, like smax: the host cannot check device data.
+ * COUNTS.  C[j][k] = the sum of w over the used entries of query q that pair column j with the byte letters[k]; bytes that are not in
+ *   `letters` are not counted.  N[j] = sum over k of C[j][k].  A walk visits a column at most once: N[j] <= 4096 x 65535 < 2^28.
+ * NEW ENTRY.  den = prior_weight + N[j].  den == 0: out[j][k] = P[j][k].  Otherwise, in int64,
+ *   num = prior_weight x P[j][k] + sum over b of C[j][b] x S[b][k],   out[j][k] = clamp(floor((2 num + den) / (2 den)), -128, 127):
+ *   round half up with FLOOR division (C's '/' truncates toward zero, which differs for negative numerators).
+ * Integer sums do not depend on their order: the same bytes come out on every run.
+ * Asynchronous on `stream`, no host round trip: the host reads none of the device tables; its work is O(nqueries) + O(nletters^2) (S).
+ * One small table (S, the code table, the offsets) is uploaded from pinned memory; the context holds TWO such copies and uses them in turn,
+ * so a call waits on the host only for the upload of the call before the last one -- a loop can be enqueued one call ahead of the
+ * device.  (The search and alignment calls of the loop keep one pinned copy each and wait for their own previous upload, as ever.)
+ * nqueries == 0 launches nothing; a handle with ntargets == 0 uses no entry: the clamped prior comes out and the counts are zero.
+ * One launch: one workgroup per (query, tile of columns), a tile's counts in LDS, no global atomics (swp::plan_pssm_hits cuts the
+ * tiles).  "last_pssm_hits_launches" reports the kernel launches of the last call.
+ * SW_EINVAL, checked before the first launch: the argument errors of sw_db_align_pssm_hits (the offsets, the scoring object, the
+ * handle's device, top outside 1..SW_TOP_MAX); NULL d_prior, upd, upd->sub, d_hits, d_aln or d_ops; ops_cap < 1; prior_weight outside
+ * 0..65535; both outputs NULL.
+ *   sw_pssm_from_hits_host  the CPU leg: the same bytes in plain C++ from host memory, db / offsets / ntargets in the handle's place.
+ *   sw_write_pssm  the ASCII layout sw_read_pssm reads (PSI-BLAST's): a title line, the alphabet twice, one line per column with its
+ *               position, its residue (consensus[g], or 'X' with consensus == NULL), the nletters scores and nletters zero percentages.
+ *               sw_read_pssm on the file returns the same letters and bytes.  SW_EINVAL for what that reader could not read back: a
+ *               letter outside A-Z, a-z, '*' (so: at most 53 letters), a letter twice, ncols < 1, a consensus byte that is not a
+ *               printable character, a file that cannot be written. */
+typedef struct { const sw_submat* sub; int32_t prior_weight; int64_t include_min_score; } sw_pssm_update;
+int  sw_db_pssm_from_hits(sw_ctx* ctx, const sw_db* db, const int8_t* d_prior, const int64_t* qoffsets, int64_t nqueries,
+                          const sw_pssm_scoring* scoring, const sw_pssm_update* upd, const sw_hit* d_hits, const int64_t* d_nhits, int64_t top,
+                          const sw_alignment* d_aln, const char* d_ops, int64_t ops_cap, const int32_t* d_weights, int8_t* d_pssm_out,
+                          int32_t* d_counts, void* stream);
+int  sw_pssm_from_hits_host(const int8_t* prior, const int64_t* qoffsets, int64_t nqueries, const char* db, const int64_t* offsets,
+                            int64_t ntargets, const sw_pssm_scoring* scoring, const sw_pssm_update* upd, const sw_hit* hits,
+                            const int64_t* nhits, int64_t top, const sw_alignment* aln, const char* ops, int64_t ops_cap,
+                            const int32_t* weights, int8_t* pssm_out, int32_t* counts);
+int  sw_write_pssm(const char* path, const char* letters, int32_t nletters, const int8_t* pssm, int64_t ncols, const char* consensus);
+
 /* Tables.  sw_submat_match: s[x][y] = x == y ? match : mismatch (matchMissmatchScore, serial_smithW.c:251-256; both must fit int8:
  * the builder returns nothing, so it clamps them to -128..127 -- a caller that takes them from a user checks the range first, as
  * smithW and the Python wrapper do, which refuse such scores).  sw_submat_from_letters: `scores` is n x n, row = query letter, over the n bytes of

@@ -60,6 +60,12 @@
   60) under both; torch events around whole calls, medians and ranges of 7 calls after a warm-up, the ratio 16 / 32 of every pair of legs.
   pairs_lanes_identical is a byte comparison of the result arrays (and of the hit tables) of the two modes at the timed size; the run
   fails if it is false.  pairs_lanes_*_packed_items is "last_search_pairs_packed_items" of the call under 16
+  --pssm-iterate: data set (a) only, 64 PSSM queries of --qlen (sw_pssm_from_queries) through one handle, top 10, 100 and 4096, 7 calls
+  each after a warm-up, torch events (device legs) or wall clock around a synchronised leg (legs with host work), ALTERNATING in one
+  process.  (a) pssm_from_hits_device alone against what a caller had to do without it: D2H of d_aln, d_ops and d_hits (and the counts),
+  pssm_from_hits_host, H2D of the matrix -- the matrices compared byte for byte (the run fails if they differ).  (b) one whole iteration,
+  align_pssm_hits_device + pssm_from_hits_device + search_pssm_top_device, against search_pssm_top_device alone.  ops_cap is 4 x qlen, not
+  qlen + the longest target: an entry whose alignment is longer counts as unused on both sides alike (*_over_cap says how many there are)
 GCUPS = query letters x target letters / time of the call (torch events, median of --reps after --warmup)."""
 import argparse
 import importlib
@@ -109,6 +115,7 @@ def main():
     ap.add_argument("--prefilter", action="store_true", help="data set (a) only: the ungapped pre-filter of 64 queries, alone and chained into the pair-list search, beside the full search")
     ap.add_argument("--prefiltered-top", action="store_true", help="data set (a) only: the top 10 of 64 queries by the full search and by pre-filter, rescoring and selection from the pair list")
     ap.add_argument("--pssm", action="store_true", help="data set (a) only: 64 PSSM queries derived from 64 sequence queries beside those, alternating")
+    ap.add_argument("--pssm-iterate", action="store_true", help="data set (a) only: the PSSM update on the device against the host round trip, and a whole iteration against the search alone")
     ap.add_argument("--lanes", action="store_true", help="data set (a) only: 64 queries under search_lanes 32 and 16, alternating, full tables and top 10")
     ap.add_argument("--pairs-lanes", action="store_true", help="data set (a) only: pair lists of all, 10 %% and 1 %% of the cross product under search_pairs_lanes 32 and 16, alternating")
     ap.add_argument("--top", action="store_true", help="data set (a) only: the best 100 targets of 64 queries by the full table and by the selection on the device")
@@ -605,6 +612,68 @@ def main():
         db.close()
         tiny.close()
 
+    def pssm_iterate_leg(packed, offs, nq=64, reps=7):
+        import time
+        d_db = torch.from_numpy(packed.copy()).to(dev)
+        db = eng.prepare_db(d_db, offs)
+        qoffs = np.arange(nq + 1, dtype=np.int64) * args.qlen
+        queries = rng.choice(PROTEIN, int(qoffs[-1])).astype(np.uint8)
+        m, moffs = swamd.pssm_from_queries((queries, qoffs), sub, letters)
+        d_m = torch.from_numpy(m.reshape(-1).copy()).to(dev)
+        pscoring, update, cap = (letters, -4, 127, -11, -1), (sub, 10, 1), 4 * args.qlen
+        P = "pssm_iterate"
+        out[f"{P}_queries"], out[f"{P}_qlen"], out[f"{P}_targets"], out[f"{P}_reps"], out[f"{P}_ops_cap"] = nq, args.qlen, len(offs) - 1, reps, cap
+        for top in (10, 100, 4096):
+            hits, nhits = db.search_pssm_top_device(d_m, moffs, pscoring, top, 1)
+            aln, ops = db.align_pssm_hits_device(d_m, moffs, pscoring, hits, nhits, ops_cap=cap)
+            d_out = torch.empty_like(d_m)
+            h2 = (torch.zeros_like(hits), torch.zeros_like(nhits))
+            state = {}
+
+            def device_call():
+                db.pssm_from_hits_device(d_m, moffs, pscoring, update, hits, nhits, aln, ops, cap, out=d_out)
+
+            def host_round_trip():
+                h, n, a, o = hits.cpu().numpy(), nhits.cpu().numpy(), aln.cpu().numpy(), ops.cpu().numpy()
+                state["m"] = swamd.pssm_from_hits_host((m, moffs), (packed, offs), pscoring, update, h, n, a, o)
+                state["d"] = torch.from_numpy(state["m"].reshape(-1)).to(dev)
+
+            def search_alone():
+                db.search_pssm_top_device(d_m, moffs, pscoring, top, 1, out=h2)
+
+            def iteration():
+                db.align_pssm_hits_device(d_m, moffs, pscoring, hits, nhits, ops_cap=cap, out=(aln, ops))
+                db.pssm_from_hits_device(d_m, moffs, pscoring, update, hits, nhits, aln, ops, cap, out=d_out)
+                db.search_pssm_top_device(d_out, moffs, pscoring, top, 1, out=h2)
+
+            def wall(fn):                                                    # a leg with host work: wall clock around a synchronised call
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                fn()
+                torch.cuda.synchronize()
+                return (time.perf_counter() - t0) * 1e3
+
+            for pair in (("device_call", "host_round_trip"), ("search_alone", "iteration")):
+                legs = {"device_call": device_call, "host_round_trip": host_round_trip, "search_alone": search_alone, "iteration": iteration}
+                ms = {k: [] for k in pair}
+                for k in pair:
+                    wall(legs[k])                                            # warm-up
+                for _ in range(reps):                                        # alternating: a drift of the device shows in both alike
+                    for k in pair:
+                        ms[k].append(wall(legs[k]))
+                for k in pair:
+                    out[f"{P}_top{top}_{k}_ms"] = round(float(np.median(ms[k])), 4)
+                    out[f"{P}_top{top}_{k}_range_ms"] = [round(min(ms[k]), 4), round(max(ms[k]), 4)]
+            device_call()
+            torch.cuda.synchronize()
+            out[f"{P}_top{top}_identical"] = bool((d_out.cpu().numpy().reshape(m.shape) == state["m"]).all())
+            out[f"{P}_top{top}_over_cap"] = int((aln[:, :, 6] > cap).sum().item())
+            out[f"{P}_top{top}_moved"] = bool((state["m"] != m).any())
+            out[f"{P}_top{top}_host_over_device"] = round(out[f"{P}_top{top}_host_round_trip_ms"] / out[f"{P}_top{top}_device_call_ms"], 2)
+            out[f"{P}_top{top}_iteration_over_search"] = round(out[f"{P}_top{top}_iteration_ms"] / out[f"{P}_top{top}_search_alone_ms"], 3)
+        out[f"{P}_identical"] = all(out[f"{P}_top{t}_identical"] for t in (10, 100, 4096))
+        db.close()
+
     def lanes_leg(packed, offs, nq=64, top=10):
         d_db = torch.from_numpy(packed.copy()).to(dev)
         db = eng.prepare_db(d_db, offs)
@@ -800,13 +869,15 @@ def main():
     out["a_letters"] = int(offs[-1])
     out["a_len_median"] = int(np.median(lens))
     out["a_len_max"] = int(lens.max())
-    if args.multi or args.top or args.align_hits or args.pairs or args.prefilter or args.prefiltered_top or args.pssm or args.lanes or args.pairs_lanes:
+    if args.multi or args.top or args.align_hits or args.pairs or args.prefilter or args.prefiltered_top or args.pssm or args.pssm_iterate or args.lanes or args.pairs_lanes:
         if args.lanes:
             lanes_leg(packed, offs)
         if args.pairs_lanes:
             pairs_lanes_leg(packed, offs)
         if args.pssm:
             pssm_leg(packed, offs)
+        if args.pssm_iterate:
+            pssm_iterate_leg(packed, offs)
         if args.pairs:
             pairs_leg(packed, offs)
         if args.prefilter:
@@ -827,6 +898,8 @@ def main():
             sys.exit("bench_search.py --lanes: lanes_identical is false")
         if args.pairs_lanes and not out["pairs_lanes_identical"]:
             sys.exit("bench_search.py --pairs-lanes: pairs_lanes_identical is false")
+        if args.pssm_iterate and not out["pssm_iterate_identical"]:
+            sys.exit("bench_search.py --pssm-iterate: pssm_iterate_identical is false")
         if args.pssm and not out["pssm_identical"]:
             sys.exit("bench_search.py --pssm: pssm_identical is false")
         if args.pairs:   # the required conditions of the pair-list call: a line that misses one is printed, and the run fails

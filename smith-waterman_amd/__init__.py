@@ -51,6 +51,10 @@ class _PssmScoring(ctypes.Structure):   # sw_pssm_scoring: the letters by pointe
                 ("gap_open", ctypes.c_int32), ("gap_extend", ctypes.c_int32)]
 
 
+class _PssmUpdate(ctypes.Structure):   # sw_pssm_update: the table by pointer
+    _fields_ = [("sub", ctypes.c_void_p), ("prior_weight", ctypes.c_int32), ("include_min_score", ctypes.c_int64)]
+
+
 # every symbol include/swhip.h declares: (restype, argtypes)
 _vp, _i64, _i32, _u32, _sz = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_uint32, ctypes.c_size_t
 ABI = {
@@ -94,6 +98,11 @@ ABI = {
     "sw_align_pssm_hits_host": (_i32, [_vp, _vp, _i64, _vp, _vp, _i64, ctypes.POINTER(_PssmScoring), _vp, _vp, _i64, _vp, _vp, _i64]),
     "sw_pssm_from_queries": (_i32, [_vp, _vp, _i64, _vp, _vp, _i32, _vp]),
     "sw_read_pssm": (_i32, [ctypes.c_char_p, _vp, ctypes.POINTER(ctypes.c_int32), _vp, _i64, ctypes.POINTER(_i64)]),
+    "sw_db_pssm_from_hits": (_i32, [_vp, _vp, _vp, _vp, _i64, ctypes.POINTER(_PssmScoring), ctypes.POINTER(_PssmUpdate), _vp, _vp, _i64, _vp, _vp, _i64, _vp,
+                                    _vp, _vp, _vp]),
+    "sw_pssm_from_hits_host": (_i32, [_vp, _vp, _i64, _vp, _vp, _i64, ctypes.POINTER(_PssmScoring), ctypes.POINTER(_PssmUpdate), _vp, _vp, _i64, _vp, _vp,
+                                      _i64, _vp, _vp, _vp]),
+    "sw_write_pssm": (_i32, [ctypes.c_char_p, _vp, ctypes.c_int32, _vp, _i64, _vp]),
     "sw_align_affine_device": (_i32, [_vp, _vp, _i64, _vp, _vp, _i64, _vp, _i64, ctypes.POINTER(_Affine), _vp, _vp, _i64, _vp]),
     "sw_align_affine_host": (_i32, [_vp, _i64, _vp, _vp, _i64, _vp, _i64, ctypes.POINTER(_Affine), _vp, _vp, _i64]),
     "sw_submat_match": (None, [_i32, _i32, _vp]),
@@ -471,6 +480,76 @@ def read_pssm(path: str):
     m = np.zeros((ncols.value, nl.value), np.int8)
     _check(lib().sw_read_pssm(os.fsencode(path), letters.ctypes.data, ctypes.byref(nl), m.ctypes.data, m.size, ctypes.byref(ncols)))
     return letters[:nl.value].copy(), m
+
+
+def write_pssm(path: str, letters, pssm, consensus=None):
+    """sw_write_pssm: a (columns, nletters) int8 matrix in the ASCII layout read_pssm reads back.  consensus: one printable byte per
+    column (the residue printed beside the position), or None for 'X'."""
+    lt = np.ascontiguousarray(_as_seq(letters))
+    m = np.ascontiguousarray(pssm, np.int8).reshape(-1, max(1, len(lt)))
+    cons = None
+    if consensus is not None:
+        cons = np.ascontiguousarray(_as_seq(consensus))
+        if len(cons) != len(m):
+            raise ValueError(f"consensus must hold one byte per column ({len(m)})")
+    buf = np.concatenate([lt, np.zeros(1, np.uint8)])
+    _check(lib().sw_write_pssm(os.fsencode(path), buf.ctypes.data, len(lt), m.ctypes.data if m.size else None, len(m),
+                               cons.ctypes.data if cons is not None and len(cons) else None))
+
+
+def _pssm_update(update):
+    """(the table kept alive, the sw_pssm_update that points at it) from (submat, prior_weight, include_min_score)."""
+    submat, prior_weight, include_min_score = update
+    sub = _submat(submat)
+    return sub, _PssmUpdate(sub.ctypes.data, int(prior_weight), int(include_min_score))
+
+
+def _ops_table(ops, nq: int, top: int):
+    """The ops of a hit table as the C-ABI takes them: a (nq, top, ops_cap) uint8 array, or the list per query of `top` bytes objects
+    the align calls return -> ((nq * top, ops_cap) uint8, ops_cap)."""
+    if isinstance(ops, np.ndarray):
+        o = np.ascontiguousarray(ops, np.uint8).reshape(max(1, nq * top), -1)
+        return o, o.shape[1]
+    cap = max([1] + [len(b) for row in ops for b in row])
+    o = np.zeros((max(1, nq * top), cap), np.uint8)
+    for q, row in enumerate(ops):
+        for r, b in enumerate(row):
+            o[q * top + r, :len(b)] = np.frombuffer(b, np.uint8)
+    return o, cap
+
+
+def pssm_from_hits_host(prior, targets, scoring, update, hits, nhits, aln, ops, weights=None, want_counts: bool = False):
+    """sw_pssm_from_hits_host: the next iteration's PSSM from aligned hits in plain C++ on the host (no GPU).  Arguments and results as
+    Database.pssm_from_hits."""
+    lt, sc = _pssm_scoring(scoring)
+    sub, up = _pssm_update(update)
+    nl = max(1, sc.nletters)
+    m, qoffs = _pack_pssm(prior, nl)
+    packed, offs = _pack_targets(targets)
+    nq = len(qoffs) - 1
+    hits, nhits = _hit_table(hits, nhits, nq)
+    top = hits.shape[1]
+    a = np.ascontiguousarray(aln, np.int64).reshape(-1, 7)
+    if len(a) != nq * top:
+        raise ValueError(f"aln must be ({nq}, {top}, 7) int64")
+    o, cap = _ops_table(ops, nq, top)
+    w = None
+    if weights is not None:
+        w = np.ascontiguousarray(weights, np.int32).reshape(-1)
+        if len(w) != nq * top:
+            raise ValueError(f"weights must be ({nq}, {top}) int32")
+    mm = m if m.size else np.zeros((1, nl), np.int8)
+    db = packed if len(packed) else np.zeros(1, np.uint8)
+    ncols = int(qoffs[-1] - qoffs[0])
+    out = mm.copy()
+    counts = np.zeros((max(1, ncols), nl), np.int32)
+    aa = a if len(a) else np.zeros((1, 7), np.int64)
+    _check(lib().sw_pssm_from_hits_host(mm.ctypes.data, qoffs.ctypes.data, nq, db.ctypes.data, offs.ctypes.data, len(offs) - 1, ctypes.byref(sc),
+                                        ctypes.byref(up), hits.ctypes.data if hits.size else aa.ctypes.data, nhits.ctypes.data if nhits is not None else None,
+                                        top, aa.ctypes.data, o.ctypes.data, cap, w.ctypes.data if w is not None and len(w) else None, out.ctypes.data,
+                                        counts.ctypes.data))
+    out = out[:len(m)]
+    return (out, counts[:ncols]) if want_counts else out
 
 
 def search_pssm_multi_host(pssm, targets, scoring):
@@ -931,6 +1010,86 @@ class Database:
         """sw_db_align_pssm_hits on a device-resident matrix and a device hit table; everything else as for align_affine_hits_device."""
         lt, sc = _pssm_scoring(scoring)
         return self._align_hits_call(lib().sw_db_align_pssm_hits, d_pssm, qoffsets, sc, hits, nhits, ops_cap, out, top, checkpoint)
+
+    def pssm_from_hits(self, prior, scoring, update, hits, nhits, aln, ops, weights=None, want_counts: bool = False):
+        """The next iteration's PSSM from aligned hits (sw_db_pssm_from_hits).  prior and scoring as for search_pssm; update =
+        (submat, prior_weight, include_min_score); hits, nhits as search_pssm_top returns them, aln and ops as align_pssm_hits returns
+        them (ops: the list per query of bytes objects, or a (nqueries, top, ops_cap) uint8 array); weights a (nqueries, top) int32
+        array or None for 1.  Returns the new (total columns, nletters) int8 matrix -- the columns in front of the first query are the
+        prior's --, with want_counts (matrix, counts): the (columns of the queries, nletters) int32 counts.  include/swhip.h states the
+        rule: a column's new row is the rounded weighted mean of its prior row and the table rows of the residues aligned to it."""
+        eng = self.engine
+        t = eng.torch
+        dev = f"cuda:{eng.device}"
+        nl = max(1, len(_as_seq(scoring[0])))
+        m, qoffs = _pack_pssm(prior, nl)
+        nq = len(qoffs) - 1
+        hits, nhits = _hit_table(hits, nhits, nq)
+        top = hits.shape[1]
+        a = np.ascontiguousarray(aln, np.int64).reshape(-1, 7)
+        if len(a) != nq * top:
+            raise ValueError(f"aln must be ({nq}, {top}, 7) int64")
+        o, cap = _ops_table(ops, nq, top)
+        d_m = t.from_numpy(m.reshape(-1).copy() if m.size else np.zeros(1, np.int8)).to(dev)
+        d_hits = t.from_numpy(hits.reshape(-1).copy() if hits.size else np.zeros(3, np.int64)).to(dev)
+        d_nhits = t.from_numpy(nhits.copy()).to(dev) if nhits is not None and len(nhits) else None
+        d_aln = t.from_numpy(a.reshape(-1).copy() if a.size else np.zeros(7, np.int64)).to(dev)
+        d_ops = t.from_numpy(o.reshape(-1).copy()).to(dev)
+        d_w = t.from_numpy(np.ascontiguousarray(weights, np.int32).reshape(-1).copy()).to(dev) if weights is not None and nq * top else None
+        counts = t.zeros(max(1, int(qoffs[-1] - qoffs[0]) * nl), dtype=t.int32, device=dev) if want_counts else None
+        out = self.pssm_from_hits_device(d_m, qoffs, scoring, update, d_hits, d_nhits, d_aln, d_ops, cap, weights=d_w, top=top, counts=counts)
+        eng.synchronize()
+        res = out.cpu().numpy().reshape(-1, nl)[:len(m)]
+        return (res, counts.cpu().numpy().reshape(-1, nl)[:int(qoffs[-1] - qoffs[0])]) if want_counts else res
+
+    def pssm_from_hits_device(self, d_prior, qoffsets, scoring, update, hits, nhits, aln, ops, ops_cap: int, weights=None, out=None, top=None,
+                              counts=None):
+        """sw_db_pssm_from_hits on device-resident tables: the prior (a torch int8 tensor in the layout of d_pssm), the hit table and
+        counts of search_pssm_top_device, the alignments and ops of align_pssm_hits_device, optional int32 weights; asynchronous on
+        torch's current stream, nothing comes to the host.  out: the int8 tensor that receives the new matrix (the columns of the
+        queries are written, nothing else), None for a fresh copy of the prior, or d_prior itself (in place); False: counts only.
+        counts: an int32 tensor of at least (columns of the queries) x nletters elements, or None.  Returns `out` (counts with
+        out=False)."""
+        eng = self.engine
+        t = eng.torch
+        lt, sc = _pssm_scoring(scoring)
+        sub, up = _pssm_update(update)
+        qoffs = np.ascontiguousarray(qoffsets, np.int64).reshape(-1)
+        if len(qoffs) == 0:
+            qoffs = np.zeros(1, np.int64)
+        nq, nl = len(qoffs) - 1, max(1, sc.nletters)
+        if top is None:
+            if hits.dim() != 3:
+                raise ValueError("hits must be (nqueries, top, 3), or `top` given")
+            top = hits.shape[1]
+        top = int(top)
+        n = nq * max(0, top)
+        if d_prior.dtype != t.int8 or not d_prior.is_contiguous() or d_prior.numel() < int(qoffs[-1]) * nl:
+            raise ValueError(f"d_prior must be a contiguous int8 tensor of at least {int(qoffs[-1]) * nl} elements")
+        if hits.dtype != t.int64 or not hits.is_contiguous() or hits.numel() < n * 3:
+            raise ValueError(f"hits must be a contiguous int64 tensor of at least {nq} x {top} x 3 elements")
+        if nhits is not None and (nhits.dtype != t.int64 or not nhits.is_contiguous() or nhits.numel() < nq):
+            raise ValueError(f"nhits must be a contiguous int64 tensor of at least {nq} elements")
+        if aln.dtype != t.int64 or not aln.is_contiguous() or aln.numel() < n * 7:
+            raise ValueError(f"aln must be a contiguous int64 tensor of at least {n * 7} elements")
+        if ops is not None and (ops.dtype != t.uint8 or not ops.is_contiguous() or ops.numel() < n * max(0, int(ops_cap))):
+            raise ValueError(f"ops must be a contiguous uint8 tensor of at least {n * max(0, int(ops_cap))} elements")
+        if weights is not None and (weights.dtype != t.int32 or not weights.is_contiguous() or weights.numel() < n):
+            raise ValueError(f"weights must be a contiguous int32 tensor of at least {n} elements")
+        if out is None:
+            out = d_prior.clone()
+        elif out is False:
+            out = None
+        if out is not None and (out.dtype != t.int8 or not out.is_contiguous() or out.numel() < int(qoffs[-1]) * nl):
+            raise ValueError(f"out must be a contiguous int8 tensor of at least {int(qoffs[-1]) * nl} elements")
+        ncnt = int(qoffs[-1] - qoffs[0]) * nl
+        if counts is not None and (counts.dtype != t.int32 or not counts.is_contiguous() or counts.numel() < ncnt):
+            raise ValueError(f"counts must be a contiguous int32 tensor of at least {ncnt} elements")
+        _check(lib().sw_db_pssm_from_hits(eng._h, self._h, d_prior.data_ptr(), qoffs.ctypes.data, nq, ctypes.byref(sc), ctypes.byref(up), hits.data_ptr(),
+                                          nhits.data_ptr() if nhits is not None else None, top, aln.data_ptr(), ops.data_ptr() if ops is not None else None,
+                                          int(ops_cap), weights.data_ptr() if weights is not None else None, out.data_ptr() if out is not None else None,
+                                          counts.data_ptr() if counts is not None else None, eng._stream()))
+        return out if out is not None else counts
 
     def align_affine_hits_device(self, d_queries, qoffsets, scoring, hits, nhits, ops_cap: int = 0, out=None, top=None, checkpoint=None):
         """sw_db_align_affine_hits on device-resident queries and a device hit table -- the (nqueries, top, 3) int64 tensor and the

@@ -39,6 +39,9 @@
 //                              bytes) with gap_open 0 and the gap of --scores: the reference's backtrack() path
 //     ... --align-checkpoint  with --align: option "align_checkpoint" = 2 -- hits (with --all-queries: tables) whose whole direction matrices do not
 //                              fit the workspace are aligned from checkpoint rows in bounded memory, in the same one call; the output is unchanged
+//     ... --iterations N      with --all-queries or --pssm: N >= 1 rounds of search, alignment of the top hits and a new PSSM built from them on the device
+//                              (sw_db_pssm_from_hits; --include-score S, default 1; --prior-weight W, default 10; --out-pssm PREFIX writes PREFIX.<query>.pssm);
+//                              the hits and --align output are those of the last round; N = 1 is the search of today
 //   smithW --search --pssm FILE DB.fa --gap-open O --gap-extend E [--top K] [--min-score S] [--align] [--search-lanes 16|32]
 //                              the ONE query is a position-specific scoring matrix, PSI-BLAST's ASCII PSSM (sw_read_pssm), searched through a prepared
 //                              handle (sw_db_search_pssm_top, sw_db_align_pssm_hits); the output is that of --all-queries for one record, the Q line of an
@@ -451,6 +454,153 @@ static int search_pssm_main(const char* ppath, const char* dbpath, long long top
     return 0;
 }
 
+// --iterations N (with --search Q.fa DB.fa --all-queries, or --search --pssm FILE DB.fa): an iterative search that stays on the device.
+// Iteration 0 is the search of today: the sequence queries go through sw_pssm_from_queries (letters: the distinct bytes of the database
+// and the queries, ascending; other / smax: the smallest / largest entry of the table over those letters, so nothing is clamped and the
+// hits are those of --all-queries), a PSSM file is taken as it is (its letters, other and smax as for --pssm).  Every further iteration
+// aligns the top hits (sw_db_align_pssm_hits), builds the next matrix from them with the iteration-0 matrix as prior
+// (sw_db_pssm_from_hits: --prior-weight W, --include-score S; S: the table of --matrix, or of --scores where there is none, which is
+// always the case with --pssm) and searches again (sw_db_search_pssm_top); the host reads nothing in between.  The hits printed, and
+// with --align their alignments, are those of the LAST iteration, in the format of --all-queries; the query line of an alignment is the
+// query's letters, for a PSSM file the consensus of the last matrix.  --out-pssm PREFIX writes the matrix the last search ran with, per
+// query, to PREFIX.<query index>.pssm (sw_write_pssm).
+static int search_iter_main(const char* qpath, const char* ppath, const char* dbpath, long long top, long long min_score, const sw_scores& sc, const AffineArgs& af,
+                            bool align, bool align_ckpt, int search_lanes, long long iterations, long long include_score, long long prior_weight,
+                            const char* out_pssm) {
+    int64_t nq = 0, qtotal = 0, nrec = 0, total = 0;
+    CHECK(sw_read_fasta_db(dbpath, nullptr, 0, nullptr, 0, &nrec, &total));
+    std::vector<char> db((size_t)total + 1);
+    std::vector<int64_t> offs((size_t)nrec + 1, 0);
+    CHECK(sw_read_fasta_db(dbpath, db.data(), total, offs.data(), nrec + 1, &nrec, &total));
+    std::vector<sw_submat> sub(1);
+    if (af.matrix) CHECK(sw_read_submat(af.matrix, sub.data()));
+    else sw_submat_match(sc.match, sc.mismatch, sub.data());
+    char letters[256];
+    int32_t nletters = 0;
+    std::vector<char> qs;                 // the query line of every query's alignments, back to back
+    std::vector<int64_t> qoffs;
+    std::vector<int8_t> pssm;             // iteration 0
+    sw_pssm_scoring scoring = {letters, 0, 0, 0, af.has_open ? af.open : 0, af.has_extend ? af.extend : (ppath ? 0 : sc.gap)};
+    if (ppath) {
+        int64_t ncols = 0;
+        CHECK(sw_read_pssm(ppath, letters, &nletters, nullptr, 0, &ncols));
+        pssm.resize((size_t)ncols * (size_t)nletters);
+        CHECK(sw_read_pssm(ppath, letters, &nletters, pssm.data(), (int64_t)pssm.size(), &ncols));
+        nq = 1; qtotal = ncols;
+        qoffs = {0, ncols};
+        qs.assign((size_t)ncols, '?');
+        scoring.other = std::min<int>(*std::min_element(pssm.begin(), pssm.end()), 0);
+        scoring.smax = std::max<int>(*std::max_element(pssm.begin(), pssm.end()), 0);
+    } else {
+        CHECK(sw_read_fasta_db(qpath, nullptr, 0, nullptr, 0, &nq, &qtotal));
+        qs.resize((size_t)qtotal + 1);
+        qoffs.assign((size_t)nq + 1, 0);
+        CHECK(sw_read_fasta_db(qpath, qs.data(), qtotal, qoffs.data(), nq + 1, &nq, &qtotal));
+        bool seen[256] = {};
+        for (int64_t i = 0; i < total; ++i) seen[(unsigned char)db[(size_t)i]] = true;
+        for (int64_t i = 0; i < qtotal; ++i) seen[(unsigned char)qs[(size_t)i]] = true;
+        for (int b = 0; b < 256; ++b)
+            if (seen[b]) letters[nletters++] = (char)b;
+        if (nletters == 0 || qtotal == 0) { fprintf(stderr, "smithW: --iterations needs queries and a database with letters\n"); return 2; }
+        int lo = 0, hi = 0;
+        for (int x = 0; x < nletters; ++x)
+            for (int y = 0; y < nletters; ++y) {
+                const int v = sub[0].s[(unsigned char)letters[x]][(unsigned char)letters[y]];
+                lo = std::min(lo, v); hi = std::max(hi, v);
+            }
+        scoring.other = lo; scoring.smax = hi;
+        pssm.resize((size_t)qtotal * (size_t)nletters);
+        CHECK(sw_pssm_from_queries(qs.data(), qoffs.data(), nq, sub.data(), letters, nletters, pssm.data()));
+        if (qoffs[0] != 0) { fprintf(stderr, "smithW: query offsets do not start at 0\n"); return 1; }
+    }
+    scoring.nletters = nletters;
+    const long long K = std::max(0ll, std::min(top, (long long)nrec));
+    if (K < 1 || K > SW_TOP_MAX) { fprintf(stderr, "smithW: --iterations / --out-pssm work on a device hit table: min(--top, records) = %lld is outside 1..%d\n", K, SW_TOP_MAX); return 2; }
+    sw_ctx* ctx = nullptr;
+    CHECK(sw_create(0, &ctx));
+    if (align_ckpt) CHECK(sw_set_option(ctx, "align_checkpoint", 2));
+    CHECK(sw_set_option(ctx, "search_lanes", search_lanes));
+    void *d_prior = nullptr, *d_work = nullptr, *d_db = nullptr, *d_hits = nullptr, *d_nhits = nullptr, *d_aln = nullptr, *d_ops = nullptr;
+    const size_t n = (size_t)(nq * K);
+    CHECK(sw_device_malloc(ctx, pssm.size() + 16, &d_prior));
+    CHECK(sw_device_malloc(ctx, pssm.size() + 16, &d_work));
+    CHECK(sw_device_malloc(ctx, (size_t)total + 16, &d_db));
+    CHECK(sw_device_malloc(ctx, n * sizeof(sw_hit), &d_hits));
+    CHECK(sw_device_malloc(ctx, (size_t)nq * sizeof(int64_t), &d_nhits));
+    CHECK(sw_memcpy_h2d(ctx, d_prior, pssm.data(), pssm.size()));
+    if (total) CHECK(sw_memcpy_h2d(ctx, d_db, db.data(), (size_t)total));
+    sw_db* handle = nullptr;
+    const double t0 = now_s();
+    CHECK(sw_db_create(ctx, (const char*)d_db, offs.data(), nrec, &handle));
+    int64_t maxq = 0, longest = 0;
+    for (int64_t i = 0; i < nq; ++i) maxq = std::max(maxq, qoffs[(size_t)i + 1] - qoffs[(size_t)i]);
+    CHECK(sw_db_info(handle, nullptr, nullptr, &longest, nullptr));
+    const int64_t ops_cap = std::max<int64_t>(1, maxq + longest);
+    if (iterations > 1 || align) {
+        if ((double)n * (double)ops_cap > (double)(1ll << 32)) { fprintf(stderr, "smithW: the ops of %zu hits x %lld bytes pass 4 GiB: lower --top\n", n, (long long)ops_cap); return 2; }
+        CHECK(sw_device_malloc(ctx, n * sizeof(sw_alignment), &d_aln));
+        CHECK(sw_device_malloc(ctx, n * (size_t)ops_cap, &d_ops));
+    }
+    const sw_pssm_update upd = {sub.data(), (int32_t)prior_weight, include_score};
+    const double t1 = now_s();
+    const int8_t* d_cur = (const int8_t*)d_prior;
+    for (long long it = 0; it < iterations; ++it) {   // nothing below waits for the device or reads from it
+        if (it > 0) {
+            CHECK(sw_db_align_pssm_hits(ctx, handle, d_cur, qoffs.data(), nq, &scoring, (const sw_hit*)d_hits, (const int64_t*)d_nhits, K, (sw_alignment*)d_aln,
+                                        (char*)d_ops, ops_cap, nullptr));
+            CHECK(sw_db_pssm_from_hits(ctx, handle, (const int8_t*)d_prior, qoffs.data(), nq, &scoring, &upd, (const sw_hit*)d_hits, (const int64_t*)d_nhits, K,
+                                       (const sw_alignment*)d_aln, (const char*)d_ops, ops_cap, nullptr, (int8_t*)d_work, nullptr, nullptr));
+            d_cur = (const int8_t*)d_work;
+        }
+        CHECK(sw_db_search_pssm_top(ctx, handle, d_cur, qoffs.data(), nq, &scoring, K, min_score, (sw_hit*)d_hits, (int64_t*)d_nhits, nullptr));
+    }
+    if (align)
+        CHECK(sw_db_align_pssm_hits(ctx, handle, d_cur, qoffs.data(), nq, &scoring, (const sw_hit*)d_hits, (const int64_t*)d_nhits, K, (sw_alignment*)d_aln,
+                                    (char*)d_ops, ops_cap, nullptr));
+    CHECK(sw_synchronize(ctx, nullptr));
+    const double t2 = now_s();
+    std::vector<sw_hit> hits(n);
+    std::vector<int64_t> nhits((size_t)nq);
+    std::vector<int8_t> last(pssm.size());
+    CHECK(sw_memcpy_d2h(ctx, hits.data(), d_hits, n * sizeof(sw_hit)));
+    CHECK(sw_memcpy_d2h(ctx, nhits.data(), d_nhits, (size_t)nq * sizeof(int64_t)));
+    CHECK(sw_memcpy_d2h(ctx, last.data(), d_cur, last.size()));
+    std::vector<sw_alignment> aln;
+    std::vector<char> ops;
+    if (align) {
+        aln.resize(n); ops.resize(n * (size_t)ops_cap);
+        CHECK(sw_memcpy_d2h(ctx, aln.data(), d_aln, n * sizeof(sw_alignment)));
+        CHECK(sw_memcpy_d2h(ctx, ops.data(), d_ops, ops.size()));
+    }
+    if (ppath)   // the consensus of the last matrix: per column the first letter with the largest entry
+        for (int64_t g = 0; g < qtotal; ++g) {
+            const int8_t* col = last.data() + g * nletters;
+            qs[(size_t)g] = letters[std::max_element(col, col + nletters) - col];
+        }
+    const sw_affine unused = {nullptr, 0, 0};   // (print_hits aligns nothing itself when it is given the rows of a call)
+    for (int64_t i = 0; i < nq; ++i) {
+        printf("## query record %lld of %s\n", (long long)i, ppath ? ppath : qpath);
+        if (int rc = print_hits(ctx, qs.data() + qoffs[(size_t)i], qoffs[(size_t)i + 1] - qoffs[(size_t)i], nullptr, db, d_db, offs, nrec, total, hits.data() + i * K,
+                                (long long)nhits[(size_t)i], align, unused, align ? aln.data() + i * K : nullptr, align ? ops.data() + (size_t)(i * K) * (size_t)ops_cap : nullptr,
+                                ops_cap)) return rc;
+        if (out_pssm) {
+            const std::string path = std::string(out_pssm) + "." + std::to_string((long long)i) + ".pssm";
+            CHECK(sw_write_pssm(path.c_str(), letters, nletters, last.data() + qoffs[(size_t)i] * nletters, qoffs[(size_t)i + 1] - qoffs[(size_t)i],
+                                qs.data() + qoffs[(size_t)i]));
+        }
+    }
+    const double cells = (double)qtotal * (double)total * (double)iterations;
+    printf("\nElapsed time for database search: %f (%.1f GCUPS; %lld queries, %lld iterations on the device, handle prepared in %f)\n\n", t2 - t1,
+           t2 > t1 ? cells / (t2 - t1) / 1e9 : 0.0, (long long)nq, iterations, t1 - t0);
+    sw_db_free(handle);
+    (void)sw_device_free(ctx, d_prior); (void)sw_device_free(ctx, d_work); (void)sw_device_free(ctx, d_db); (void)sw_device_free(ctx, d_hits);
+    (void)sw_device_free(ctx, d_nhits);
+    if (d_aln) (void)sw_device_free(ctx, d_aln);
+    if (d_ops) (void)sw_device_free(ctx, d_ops);
+    sw_destroy(ctx);
+    return 0;
+}
+
 // the first word of every record's header line, by the record rule of sw_read_fasta_db (a headerless record is "-")
 static std::vector<std::string> fasta_names(const char* path) {
     std::vector<std::string> names;
@@ -647,6 +797,9 @@ int main(int argc, char** argv) {
     bool align = false, all_queries = false, align_ckpt = false;
     int search_lanes = 32, pairs_lanes = 32;
     bool has_search_lanes = false, has_pairs_lanes = false;
+    int iterations = 1, include_score = 1, prior_weight = 10;
+    bool has_iter_flag = false;
+    const char* out_pssm = nullptr;
     sw_scores sc = {3, -3, -2};
     int npos = 0;
     for (int ai = 1; ai < argc; ++ai) {
@@ -673,6 +826,10 @@ int main(int argc, char** argv) {
         else if (f == "--prefilter-hits" && ai + 1 < argc) { int v = 0; if (!parse_int("--prefilter-hits", argv[++ai], &v)) return 2; prefilter_hits = v; has_prefilter_hits = true; }
         else if (f == "--search-lanes" && ai + 1 < argc) { if (!parse_int("--search-lanes", argv[++ai], &search_lanes)) return 2; has_search_lanes = true; }
         else if (f == "--pairs-lanes" && ai + 1 < argc) { if (!parse_int("--pairs-lanes", argv[++ai], &pairs_lanes)) return 2; has_pairs_lanes = true; }
+        else if (f == "--iterations" && ai + 1 < argc) { if (!parse_int("--iterations", argv[++ai], &iterations)) return 2; has_iter_flag = true; }
+        else if (f == "--include-score" && ai + 1 < argc) { if (!parse_int("--include-score", argv[++ai], &include_score)) return 2; has_iter_flag = true; }
+        else if (f == "--prior-weight" && ai + 1 < argc) { if (!parse_int("--prior-weight", argv[++ai], &prior_weight)) return 2; has_iter_flag = true; }
+        else if (f == "--out-pssm" && ai + 1 < argc) { out_pssm = argv[++ai]; has_iter_flag = true; }
         else if (f == "--matrix" && ai + 1 < argc) { af.matrix = argv[++ai]; af.on = true; }
         else if (f == "--gap-open" && ai + 1 < argc) { if (!parse_int("--gap-open", argv[++ai], &af.open)) return 2; af.has_open = af.on = true; }
         else if (f == "--gap-extend" && ai + 1 < argc) { if (!parse_int("--gap-extend", argv[++ai], &af.extend)) return 2; af.has_extend = true; }
@@ -683,7 +840,7 @@ int main(int argc, char** argv) {
         else if (f == "--record-b" && ai + 1 < argc) rec_b = strtoll(argv[++ai], nullptr, 10);
         else if (f == "--seed" && ai + 1 < argc) seed = (unsigned)strtoul(argv[++ai], nullptr, 10);
         else if (f == "--scores" && ai + 3 < argc) { sc.match = atoi(argv[++ai]); sc.mismatch = atoi(argv[++ai]); sc.gap = atoi(argv[++ai]); }
-        else { fprintf(stderr, "usage: smithW [<cols> <rows> | --fasta A.fa B.fa [--record-a I] [--record-b J] | --search QUERY.fa DB.fa [--record-a I] [--top K] [--all-queries [--min-score S] [--prefilter S | --prefilter-hits S [--pairs-lanes 16|32]] [--search-lanes 16|32]] [--pairs FILE [--pairs-lanes 16|32]] [--matrix FILE] [--gap-open O] [--gap-extend E] [--align [--align-checkpoint]] | --search --pssm FILE DB.fa --gap-open O --gap-extend E [--top K] [--min-score S] [--align] [--search-lanes 16|32]] [--seed N] [--dump | --dump-labels] [--h64] [--no-backtrack] [--scores M X G] [--gpus N | --devices 0,1,..] [--p8]\n"); return 2; }
+        else { fprintf(stderr, "usage: smithW [<cols> <rows> | --fasta A.fa B.fa [--record-a I] [--record-b J] | --search QUERY.fa DB.fa [--record-a I] [--top K] [--all-queries [--min-score S] [--prefilter S | --prefilter-hits S [--pairs-lanes 16|32]] [--search-lanes 16|32]] [--pairs FILE [--pairs-lanes 16|32]] [--matrix FILE] [--gap-open O] [--gap-extend E] [--align [--align-checkpoint]] | --search --pssm FILE DB.fa --gap-open O --gap-extend E [--top K] [--min-score S] [--align] [--search-lanes 16|32] | with --all-queries or --pssm: [--iterations N] [--include-score S] [--prior-weight W] [--out-pssm PREFIX]] [--seed N] [--dump | --dump-labels] [--h64] [--no-backtrack] [--scores M X G] [--gpus N | --devices 0,1,..] [--p8]\n"); return 2; }
     }
     if (npos == 1) { fprintf(stderr, "smithW: <cols> needs <rows>\n"); return 2; }
     if (align_ckpt && !(search_q && align)) { fprintf(stderr, "smithW: --align-checkpoint goes with --search --align\n"); return 2; }
@@ -696,12 +853,23 @@ int main(int argc, char** argv) {
         if (pairs_lanes != 16 && pairs_lanes != 32) { fprintf(stderr, "smithW: --pairs-lanes takes 16 or 32, got %d\n", pairs_lanes); return 2; }
         if (!search_q || pssm_path || !(pairs_path || has_prefilter_hits)) { fprintf(stderr, "smithW: --pairs-lanes goes with --search --pairs or --search --all-queries --prefilter-hits\n"); return 2; }
     }
+    if (has_iter_flag) {   // the iterative search: many sequence queries, or one matrix
+        if (!(search_q && (all_queries || pssm_path))) { fprintf(stderr, "smithW: --iterations / --include-score / --prior-weight / --out-pssm go with --search --all-queries or --search --pssm\n"); return 2; }
+        if (iterations < 1) { fprintf(stderr, "smithW: --iterations N needs N >= 1, got %d\n", iterations); return 2; }
+        if (prior_weight < 0 || prior_weight > 65535) { fprintf(stderr, "smithW: --prior-weight W needs W within 0..65535, got %d\n", prior_weight); return 2; }
+        if (has_prefilter || has_prefilter_hits || pairs_path) { fprintf(stderr, "smithW: --iterations does not go with --prefilter / --prefilter-hits / --pairs\n"); return 2; }
+    }
+    const bool iterate = iterations > 1 || out_pssm;   // (--iterations 1 alone is the search of today, through today's path)
     if (pssm_path) {   // the matrix is the query and the scoring at once
         if (af.matrix) { fprintf(stderr, "smithW: --pssm does not go with --matrix\n"); return 2; }
         if (all_queries) { fprintf(stderr, "smithW: --pssm does not go with --all-queries (the file is the one query)\n"); return 2; }
         if (pairs_path) { fprintf(stderr, "smithW: --pssm does not go with --pairs\n"); return 2; }
         if (has_prefilter || has_prefilter_hits) { fprintf(stderr, "smithW: --pssm does not go with --prefilter / --prefilter-hits\n"); return 2; }
         if (!af.has_open || !af.has_extend) { fprintf(stderr, "smithW: --pssm needs --gap-open O and --gap-extend E\n"); return 2; }
+        if (iterate) {
+            if (sc.match < -128 || sc.match > 127 || sc.mismatch < -128 || sc.mismatch > 127) { fprintf(stderr, "smithW: --pssm --iterations takes its table from --scores M X within -128..127, got %d %d\n", sc.match, sc.mismatch); return 2; }
+            return search_iter_main(nullptr, pssm_path, search_db, top, min_score, sc, af, align, align_ckpt, search_lanes, iterations, include_score, prior_weight, out_pssm);
+        }
         return search_pssm_main(pssm_path, search_db, top, min_score, af, align, align_ckpt, search_lanes);
     }
     if (search_q) {
@@ -749,6 +917,7 @@ int main(int argc, char** argv) {
                 fprintf(stderr, "smithW: --all-queries without --matrix needs --scores M X within -128..127 (a table of signed bytes), got %d %d\n", sc.match, sc.mismatch);
                 return 2;
             }
+            if (iterate) return search_iter_main(search_q, nullptr, search_db, top, min_score, sc, af, align, align_ckpt, search_lanes, iterations, include_score, prior_weight, out_pssm);
             return search_all_main(search_q, search_db, top, min_score, sc, af, align, align_ckpt, prefilter_hits, search_lanes, pairs_lanes);
         }
         if (has_min_score) { fprintf(stderr, "smithW: --min-score goes with --search --all-queries\n"); return 2; }

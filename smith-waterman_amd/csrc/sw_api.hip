@@ -81,6 +81,11 @@ void sw_destroy(sw_ctx* c) {
     if (c->d_tppos) (void)hipFree(c->d_tppos);
     if (c->d_tpseg) (void)hipFree(c->d_tpseg);
     if (c->d_tplist) (void)hipFree(c->d_tplist);
+    for (int i = 0; i < 2; ++i) {
+        if (c->phtab_ev[i]) { (void)hipEventSynchronize(c->phtab_ev[i]); (void)hipEventDestroy(c->phtab_ev[i]); }
+        if (c->h_phtab[i]) (void)hipHostFree(c->h_phtab[i]);
+    }
+    if (c->d_phtab) (void)hipFree(c->d_phtab);
     delete c;
 }
 
@@ -232,6 +237,7 @@ int64_t sw_get_option(sw_ctx* c, const char* name) {
     if (!strcmp(name, "last_search_top_kernel")) return c->last_search_top_kernel;
     if (!strcmp(name, "last_top_pairs_launches")) return c->last_top_pairs_launches;
     if (!strcmp(name, "last_top_pairs_kernel")) return c->last_top_pairs_kernel;
+    if (!strcmp(name, "last_pssm_hits_launches")) return c->last_pssm_hits_launches;
     if (!strcmp(name, "search_pairs_chunk")) return c->opt_search_pairs_chunk;
     if (!strcmp(name, "last_search_pairs_groups")) return c->last_search_pairs_groups;
     if (!strcmp(name, "last_search_pairs_chunks")) return c->last_search_pairs_chunks;

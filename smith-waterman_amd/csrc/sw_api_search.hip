@@ -881,6 +881,76 @@ int sw_db_align_pssm_hits(sw_ctx* c, const sw_db* db, const int8_t* d_pssm, cons
                               ops_cap, stream_);
 }
 
+// The next iteration's PSSM from a device hit table, its alignments and their ops (csrc/sw_pssm_hits.hip).  The host checks the
+// arguments, cuts the tiles (swp::plan_pssm_hits) and uploads one small table through two pinned copies of its own, used in turn -- S
+// (nletters x nletters), the 256-byte code table, the nqueries + 1 offsets --; the hit table, the alignments, the ops, the weights and the targets'
+// offsets are read on the device only.  One launch; a handle without targets takes the same launch (no entry is used).
+int sw_db_pssm_from_hits(sw_ctx* c, const sw_db* db, const int8_t* d_prior, const int64_t* qoffsets, int64_t nqueries, const sw_pssm_scoring* scoring,
+                         const sw_pssm_update* upd, const sw_hit* d_hits, const int64_t* d_nhits, int64_t top, const sw_alignment* d_aln, const char* d_ops,
+                         int64_t ops_cap, const int32_t* d_weights, int8_t* d_pssm_out, int32_t* d_counts, void* stream_) {
+    const char* who = "sw_db_pssm_from_hits";
+    if (!c || !db || !d_prior || !qoffsets || !scoring) { set_err("%s: NULL pointer", who); return SW_EINVAL; }
+    if (db->device != c->device) { set_err("%s: the handle was created on device %d, the context runs on device %d", who, db->device, c->device); return SW_EINVAL; }
+    int64_t maxq = 0;
+    unsigned char code[256];
+    if (int rc = swh::check_search_pssm(who, qoffsets, nqueries, db->longest, scoring, &maxq, code)) return rc;
+    if (int rc = swh::check_pssm_update(who, upd, top, d_hits, d_aln, d_ops, ops_cap, d_pssm_out, d_counts)) return rc;
+    c->last_pssm_hits_launches = 0;   // (a call that launches no kernel reports none)
+    if (nqueries == 0) return SW_OK;
+    hipStream_t stream = (hipStream_t)stream_;
+    HIP_TRY(hipSetDevice(c->device));
+    const std::vector<int64_t> qlens = query_lengths(qoffsets, nqueries);
+    swp::PssmHitsJob pj;
+    pj.qlens = qlens.data(); pj.nqueries = nqueries; pj.nletters = scoring->nletters; pj.num_cus = c->num_cus;
+    const swp::PssmHitsPlan plan = swp::plan_pssm_hits(pj);
+    DevOrder order(c, stream, false);
+    if (order.rc) return order.rc;
+    // the call's table: S, padded to 256 bytes, the code table, the offsets
+    const int n = scoring->nletters;
+    const size_t s_bytes = ((size_t)n * n + 255) & ~(size_t)255, off_bytes = (size_t)(nqueries + 1) * sizeof(int64_t), need = s_bytes + 256 + off_bytes;
+    // two pinned copies in turn: this call overwrites the copy of the call before the last one, and waits (on the host) for THAT upload only
+    const int turn = c->phtab_turn;
+    c->phtab_turn ^= 1;
+    if (c->phtab_ev[turn]) HIP_TRY(hipEventSynchronize(c->phtab_ev[turn]));
+    else HIP_TRY(hipEventCreateWithFlags(&c->phtab_ev[turn], hipEventDisableTiming));
+    if (need > c->phtab_cap) {
+        HIP_TRY(hipStreamSynchronize(stream));                   // launches in flight may still read the old table
+        if (c->phtab_ev[turn ^ 1]) HIP_TRY(hipEventSynchronize(c->phtab_ev[turn ^ 1]));   // ... and an upload the other copy
+        if (c->d_phtab) HIP_TRY(hipFree(c->d_phtab));
+        c->d_phtab = nullptr; c->phtab_cap = 0;
+        for (int i = 0; i < 2; ++i) {
+            if (c->h_phtab[i]) HIP_TRY(hipHostFree(c->h_phtab[i]));
+            c->h_phtab[i] = nullptr;
+        }
+        if (hipMalloc((void**)&c->d_phtab, need) != hipSuccess || hipHostMalloc((void**)&c->h_phtab[0], need, 0) != hipSuccess ||
+            hipHostMalloc((void**)&c->h_phtab[1], need, 0) != hipSuccess) {
+            set_err("%s: workspace allocation of %zu bytes failed", who, need);
+            return SW_ENOMEM;
+        }
+        c->phtab_cap = need;
+    }
+    unsigned char* h_tab = c->h_phtab[turn];
+    swh::pssm_update_table(upd->sub, scoring->letters, n, (int8_t*)h_tab);
+    memcpy(h_tab + s_bytes, code, 256);
+    memcpy(h_tab + s_bytes + 256, qoffsets, off_bytes);
+    HIP_TRY(hipMemcpyAsync(c->d_phtab, h_tab, need, hipMemcpyHostToDevice, stream));
+    HIP_TRY(hipEventRecord(c->phtab_ev[turn], stream));
+    swk::PssmHitsParams kp;
+    memset(&kp, 0, sizeof kp);
+    kp.prior = (const signed char*)d_prior; kp.out = (signed char*)d_pssm_out; kp.counts = d_counts;
+    kp.S = (const signed char*)c->d_phtab; kp.code = c->d_phtab + s_bytes; kp.qoffs = (const int64_t*)(c->d_phtab + s_bytes + 256);
+    kp.db = (const unsigned char*)db->d_db; kp.offsets = db->d_offsets; kp.ntargets = db->ntargets;
+    kp.hits = d_hits; kp.nhits = d_nhits; kp.top = top;
+    kp.aln = d_aln; kp.ops = d_ops; kp.ops_cap = ops_cap; kp.weights = d_weights;
+    kp.nqueries = nqueries; kp.tiles_per_query = plan.tiles_per_query; kp.col0 = qoffsets[0];
+    kp.include_min = upd->include_min_score;
+    kp.nletters = n; kp.stride = plan.stride; kp.tile_cols = plan.tile_cols; kp.smax = scoring->smax; kp.prior_weight = upd->prior_weight;
+    hipLaunchKernelGGL(swk::sw_pssm_from_hits, dim3((unsigned)plan.grid), dim3(256), plan.lds_bytes, stream, kp);
+    HIP_TRY(hipGetLastError());
+    c->last_pssm_hits_launches = plan.launches;
+    return SW_OK;
+}
+
 // The scores of a device pair list (csrc/sw_search_pairs.hip).  Per call the host checks and plans the QUERIES (O(nqueries)) against the
 // handle's longest target; the pairs and the targets' offsets are read on the device only.  One memset zeroes the call's results up
 // front -- the pairs that never become an item keep it, the binning writes no result --, then per group one profile launch and per

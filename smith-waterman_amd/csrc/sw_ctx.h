@@ -23,6 +23,9 @@ SW_HIDDEN int check_search_pssm(const char* who, const int64_t* qoffsets, int64_
                                 int64_t* maxq_out, unsigned char (&code)[256]);
 int check_prefilter(const char* who, int64_t min_score, const void* pairs, int64_t pairs_cap, const void* npairs, const void* scores);
 int check_align_hits(const char* who, int64_t top, const void* hits, const void* aln, const void* ops, int64_t ops_cap);
+SW_HIDDEN int check_pssm_update(const char* who, const sw_pssm_update* upd, int64_t top, const void* hits, const void* aln, const void* ops, int64_t ops_cap,
+                                const void* out, const void* counts);                                 // sw_pssm_read.cpp
+SW_HIDDEN void pssm_update_table(const sw_submat* sub, const char* letters, int n, int8_t* S);        // sw_pssm_read.cpp
 SW_HIDDEN int check_targets(const char* who, int64_t qlen, const int64_t* offsets, int64_t ntargets, int64_t* maxlen_out, int64_t* nonempty_out);
 }
 using swh::set_err;
@@ -180,6 +183,13 @@ struct SW_HIDDEN sw_ctx {
     unsigned int* d_tpseg = nullptr; size_t tpseg_cap = 0;
     unsigned char* d_tplist = nullptr; size_t tplist_cap = 0;   // (entries)
     int64_t last_top_pairs_launches = 0, last_top_pairs_kernel = 0;
+    // the next PSSM from aligned hits (sw_db_pssm_from_hits): the call's table -- S, the code table, the query offsets -- on the device +
+    // TWO pinned copies it is uploaded from in turn: phtab_ev[i] is recorded behind the upload from copy i, and a call waits for the event
+    // of the copy it is about to overwrite -- the upload of the call before the last one --, so a loop can be enqueued one call ahead
+    unsigned char* d_phtab = nullptr; unsigned char* h_phtab[2] = {nullptr, nullptr}; size_t phtab_cap = 0;   // (bytes)
+    hipEvent_t phtab_ev[2] = {nullptr, nullptr};
+    int phtab_turn = 0;
+    int64_t last_pssm_hits_launches = 0;
     // ---- placement of the output matrices (sw_place.hip)
     int64_t opt_place_hold_gib = 0;     // sw_alloc_outputs: GiB a pair of small matrices may hold beside itself where no plain candidate is good (0: none)
     int64_t opt_place_budget_ms = 1500; // sw_alloc_outputs: time the search for a P in another class of the HBM may take

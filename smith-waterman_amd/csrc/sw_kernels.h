@@ -183,6 +183,24 @@ __global__ void sw_search_profile_pssm_multi(const signed char* pssm, const Mult
 // ... its dynamic LDS: 256 columns of an odd number of dwords each (sw_pssm.hip says why), at most 64 KiB
 constexpr unsigned sw_pssm_profile_lds_bytes(int nletters) { return 1024u * (nletters > 252 ? 64u : (unsigned)(((nletters + 3) >> 2) | 1)); }
 
+// sw_pssm_hits.hip: the next iteration's PSSM from a hit table, its alignments and their ops (sw_db_pssm_from_hits).  One workgroup per
+// (query, tile of columns) as swp::plan_pssm_hits cuts them; dynamic LDS: the plan's lds_bytes.
+struct PssmHitsParams {
+    const signed char* prior; signed char* out;  // the layout of d_pssm; out may be NULL, or prior itself
+    int* counts;                                 // (qoffsets[nqueries] - qoffsets[0]) x nletters, or NULL
+    const int64_t* qoffs;                        // device copy of the caller's nqueries + 1 offsets
+    const signed char* S;                        // nletters x nletters: S[b * nletters + k] = sub[letters[b]][letters[k]]
+    const unsigned char* code;                   // 256 bytes: target byte -> its place in a column, 255 where it has none (swh::check_search_pssm)
+    const unsigned char* db; const int64_t* offsets; int64_t ntargets;   // the handle's bytes and its ntargets + 1 offsets on the device
+    const sw_hit* hits; const int64_t* nhits; int64_t top;               // the caller's tables, as sw_db_align_pssm_hits takes and leaves them
+    const sw_alignment* aln; const char* ops; int64_t ops_cap;
+    const int* weights;                          // nqueries x top, or NULL: every weight 1
+    int64_t nqueries, tiles_per_query, col0;     // col0 = qoffsets[0]: counts start at the first query's first column
+    int64_t include_min;
+    int nletters, stride, tile_cols, smax, prior_weight;
+};
+__global__ void sw_pssm_from_hits(PssmHitsParams p);
+
 // sw_search_pairs.hip: the scores of a device list of (query, target) pairs (sw_db_search_affine_pairs).  Per (chunk of the list, group
 // of queries) two binning launches turn the usable pairs into work items, one list per class, heaviest bucket first
 // (swp::plan_search_pairs); one launch of sw_search_affine_pairs_wave<C> per class scores them.

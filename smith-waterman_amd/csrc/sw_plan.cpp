@@ -884,6 +884,29 @@ static AlignHitsPlan plan_align_hits_sized(const AlignHitsJob& j, bool ckpt, int
 AlignHitsPlan plan_align_hits(const AlignHitsJob& j) { return plan_align_hits_sized(j, false, 0); }
 AlignHitsPlan plan_align_hits_ckpt(const AlignHitsCkptJob& j) { return plan_align_hits_sized(j, true, j.band_rows); }
 
+PssmHitsPlan plan_pssm_hits(const PssmHitsJob& j) {
+    PssmHitsPlan p;
+    const int nl = std::clamp(j.nletters, 1, 256);
+    p.stride = (nl + 1) | 1;
+    p.max_cols = (kPssmHitsLdsBytes - kPssmHitsCodeBytes) / (4 * (int64_t)p.stride);
+    int64_t total = 0, maxq = 0;
+    for (int64_t q = 0; q < j.nqueries; ++q) {
+        total += j.qlens[q];
+        maxq = std::max(maxq, j.qlens[q]);
+    }
+    const int64_t share = (total + 2 * std::max(1, j.num_cus) - 1) / (2 * std::max(1, j.num_cus));   // columns per workgroup at two per CU
+    int64_t tile = std::max<int64_t>(64, (share + 63) / 64 * 64);
+    tile = std::min(tile, std::max<int64_t>(1, maxq));
+    p.tile_cols = (int)std::min(tile, p.max_cols);
+    p.lds_bytes = (unsigned)(kPssmHitsCodeBytes + 4 * (int64_t)p.tile_cols * p.stride);
+    if (j.nqueries < 1) return p;
+    p.tiles_per_query = (maxq + p.tile_cols - 1) / p.tile_cols;
+    // (nqueries x tiles stays far inside 63 bits: query lengths are at most 2^20 - 1)
+    p.grid = std::min(j.nqueries * p.tiles_per_query, kPssmHitsGridMax);
+    p.launches = 1;
+    return p;
+}
+
 void align_schedule(const int64_t* offsets, const int64_t* hits, int64_t nhits, swk::SearchItem* items) {
     std::vector<int64_t> order((size_t)nhits);
     for (int64_t h = 0; h < nhits; ++h) order[(size_t)h] = h;

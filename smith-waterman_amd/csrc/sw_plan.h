@@ -524,6 +524,41 @@ TopPairsPlan plan_top_pairs(const TopPairsJob& job);
 constexpr int64_t kTopPrefilteredEntryBytes = 56;
 constexpr int64_t top_prefiltered_cap(int64_t budget_bytes) { return budget_bytes / kTopPrefilteredEntryBytes; }
 
+// ---- the next iteration's PSSM from aligned hits (sw_db_pssm_from_hits; sw_pssm_hits.hip).  One workgroup of 256 threads per (query,
+// tile of tile_cols columns); a tile's int32 counts lie in LDS, `stride` dwords per column behind the 256-byte table from a target byte
+// to its place in a column.
+// Stride: (nletters + 1) | 1 -- one spare dword per column for its sum N[j], and odd, so that the same letter of adjacent columns (what
+// the lanes of a run of 'M' touch) falls into different banks.
+// LDS: kPssmHitsLdsBytes, the 64 KiB every workgroup may take without opting in; two workgroups per CU keep their waves apart.  That
+// holds 604 columns of 25 letters and 63 columns of 256 letters.
+// Tile: every workgroup of a query walks the ops of all the query's hits up to the end of its tile, so tiles are as wide as spreading
+// the call over the device allows -- the columns of the call over two workgroups per CU, in whole chunks of 64 columns (a chunk of ops
+// advances at most 64 columns), at least 64 -- and at most what the LDS holds or the longest query needs.
+// Grid: queries x tiles of the LONGEST query (a shorter query's surplus workgroups return at once), walked in strides of at most
+// kPssmHitsGridMax workgroups.
+constexpr int64_t kPssmHitsLdsBytes = 64 << 10;
+constexpr int64_t kPssmHitsCodeBytes = 256;
+constexpr int64_t kPssmHitsGridMax = 1 << 20;
+
+struct PssmHitsJob {
+    const int64_t* qlens = nullptr;          // length of every query, input order
+    int64_t nqueries = 0;
+    int nletters = 1;                        // 1..256
+    int num_cus = 256;
+};
+
+struct PssmHitsPlan {
+    int stride = 0;                          // dwords per column in LDS
+    int tile_cols = 0;                       // columns per workgroup
+    int64_t max_cols = 0;                    // ... and the most the LDS holds
+    int64_t tiles_per_query = 0;             // tiles of the longest query
+    int64_t grid = 0;                        // workgroups (0: no query)
+    unsigned lds_bytes = 0;                  // dynamic LDS of a workgroup
+    int launches = 0;                        // kernel launches of the call ("last_pssm_hits_launches")
+};
+
+PssmHitsPlan plan_pssm_hits(const PssmHitsJob& job);
+
 // ---- alignment of chosen hits under affine scoring (sw_align_affine_device): sw_align_affine_wave<C> for C = 4, 8, 16, its index in
 // kAlignAffine (sw_api_search.hip, which checks its order against it at compile time)
 constexpr int kAlignAffineKernels = 3;

@@ -93,4 +93,187 @@ int sw_read_pssm(const char* path, char* letters_out, int32_t* nletters, int8_t*
     return SW_OK;
 }
 
+// The writer of the same layout: a title line, the alphabet twice, per column its position, its residue, the scores and as many zero
+// percentages, a blank line.  The contract is the reader's: only letters its header test accepts can be written.
+int sw_write_pssm(const char* path, const char* letters, int32_t nletters, const int8_t* pssm, int64_t ncols, const char* consensus) {
+    if (!path || !letters || !pssm) { swh::set_err("sw_write_pssm: NULL pointer"); return SW_EINVAL; }
+    if (nletters < 1 || nletters > 256) { swh::set_err("sw_write_pssm: nletters = %d is out of range 1..256", nletters); return SW_EINVAL; }
+    if (ncols < 1) { swh::set_err("sw_write_pssm: ncols = %lld: a file needs a column", (long long)ncols); return SW_EINVAL; }
+    bool seen[256] = {};
+    for (int k = 0; k < nletters; ++k) {
+        const unsigned char b = (unsigned char)letters[k];
+        if (!((b >= 'A' && b <= 'Z') || (b >= 'a' && b <= 'z') || b == '*')) {
+            swh::set_err("sw_write_pssm: letter 0x%02x cannot stand in the header of an ASCII PSSM (A-Z, a-z and '*' can)", b);
+            return SW_EINVAL;
+        }
+        if (seen[b]) { swh::set_err("sw_write_pssm: letter '%c' is listed twice", b); return SW_EINVAL; }
+        seen[b] = true;
+    }
+    if (consensus)
+        for (int64_t g = 0; g < ncols; ++g)
+            if ((unsigned char)consensus[g] <= ' ' || (unsigned char)consensus[g] > '~') {
+                swh::set_err("sw_write_pssm: consensus byte 0x%02x of column %lld is not a printable character", (unsigned char)consensus[g], (long long)g);
+                return SW_EINVAL;
+            }
+    std::string text = "\nLast position-specific scoring matrix computed, weighted observed percentages rounded down\n         ";
+    for (int rep = 0; rep < 2; ++rep)
+        for (int k = 0; k < nletters; ++k) { text += "   "; text += letters[k]; }
+    text += '\n';
+    char num[32];
+    for (int64_t g = 0; g < ncols; ++g) {
+        snprintf(num, sizeof num, "%5lld %c  ", (long long)(g + 1), consensus ? consensus[g] : 'X');
+        text += num;
+        for (int k = 0; k < nletters; ++k) { snprintf(num, sizeof num, " %3d", (int)pssm[g * nletters + k]); text += num; }
+        for (int k = 0; k < nletters; ++k) text += "   0";
+        text += '\n';
+    }
+    text += '\n';
+    FILE* f = fopen(path, "wb");
+    if (!f) { swh::set_err("sw_write_pssm: cannot open %s for writing", path); return SW_EINVAL; }
+    const bool ok = fwrite(text.data(), 1, text.size(), f) == text.size();
+    if (fclose(f) != 0 || !ok) { swh::set_err("sw_write_pssm: write error on %s", path); return SW_EINVAL; }
+    return SW_OK;
+}
+
+}  // extern "C"
+
+// ---- the next iteration's PSSM from aligned hits (sw_pssm_from_hits_host; include/swhip.h states the rule).  It lives here, beside the
+// reader and the writer, because like them it needs nothing of the library: a stand-alone program can compile this file alone.
+namespace swh {
+// (shared with sw_api_search.hip through sw_ctx.h, not exported by the library)
+__attribute__((visibility("hidden"))) int check_pssm_update(const char* who, const sw_pssm_update* upd, int64_t top, const void* hits, const void* aln,
+                                                            const void* ops, int64_t ops_cap, const void* out, const void* counts);
+__attribute__((visibility("hidden"))) void pssm_update_table(const sw_submat* sub, const char* letters, int n, int8_t* S);
+
+// What sw_db_pssm_from_hits and sw_pssm_from_hits_host check beyond the search arguments.
+int check_pssm_update(const char* who, const sw_pssm_update* upd, int64_t top, const void* hits, const void* aln, const void* ops, int64_t ops_cap,
+                      const void* out, const void* counts) {
+    if (!upd || !upd->sub) { set_err("%s: NULL update rule or substitution matrix", who); return SW_EINVAL; }
+    if (top < 1 || top > SW_TOP_MAX) { set_err("%s: top = %lld is out of range 1..%d", who, (long long)top, SW_TOP_MAX); return SW_EINVAL; }
+    if (!hits || !aln || !ops) { set_err("%s: NULL hit table, alignment array or ops buffer", who); return SW_EINVAL; }
+    if (ops_cap < 1) { set_err("%s: ops_cap = %lld is below 1", who, (long long)ops_cap); return SW_EINVAL; }
+    if (upd->prior_weight < 0 || upd->prior_weight > 65535) { set_err("%s: prior_weight = %d is out of range 0..65535", who, upd->prior_weight); return SW_EINVAL; }
+    if (!out && !counts) { set_err("%s: both outputs are NULL", who); return SW_EINVAL; }
+    return SW_OK;
+}
+
+// S[b * n + k] = sub[letters[b]][letters[k]]: the observed residue letters[b] plays the query letter.
+void pssm_update_table(const sw_submat* sub, const char* letters, int n, int8_t* S) {
+    for (int b = 0; b < n; ++b)
+        for (int k = 0; k < n; ++k) S[b * n + k] = sub->s[(unsigned char)letters[b]][(unsigned char)letters[k]];
+}
+
+}  // namespace swh
+
+namespace {
+
+constexpr int64_t kMaxDim = (1 << 20) - 1;   // swk::SW_MAX_DIM (this file does not see the kernels' header)
+
+// The argument errors of sw_align_pssm_hits_host, restated: the checks of sw_host.cpp need the whole library behind them.
+int check_host_args(const char* who, const int64_t* qoffsets, int64_t nqueries, const int64_t* offsets, int64_t ntargets, const sw_pssm_scoring* sc) {
+    using swh::set_err;
+    if (nqueries < 0 || ntargets < 0) { set_err("%s: negative query or target count", who); return SW_EINVAL; }
+    if (offsets[0] < 0 || qoffsets[0] < 0) { set_err("%s: offsets[0] or qoffsets[0] is negative", who); return SW_EINVAL; }
+    int64_t maxlen = 0, maxq = 0;
+    for (int64_t k = 0; k < ntargets; ++k) {
+        const int64_t len = offsets[k + 1] - offsets[k];
+        if (len < 0 || len > kMaxDim) { set_err("%s: target %lld has length %lld, out of range 0..%lld", who, (long long)k, (long long)len, (long long)kMaxDim); return SW_EINVAL; }
+        maxlen = std::max(maxlen, len);
+    }
+    for (int64_t q = 0; q < nqueries; ++q) {
+        const int64_t len = qoffsets[q + 1] - qoffsets[q];
+        if (len < 1 || len > kMaxDim) { set_err("%s: query %lld has length %lld, out of range 1..%lld", who, (long long)q, (long long)len, (long long)kMaxDim); return SW_EINVAL; }
+        maxq = std::max(maxq, len);
+    }
+    if (!sc->letters) { set_err("%s: NULL letters", who); return SW_EINVAL; }
+    if (sc->nletters < 1 || sc->nletters > 256) { set_err("%s: nletters = %d is out of range 1..256", who, sc->nletters); return SW_EINVAL; }
+    if (sc->smax < 0 || sc->smax > 127) { set_err("%s: smax = %d is out of range 0..127", who, sc->smax); return SW_EINVAL; }
+    if (sc->other < -128 || sc->other > sc->smax) { set_err("%s: other = %d is out of range -128..smax = %d", who, sc->other, sc->smax); return SW_EINVAL; }
+    bool seen[256] = {};
+    for (int k = 0; k < sc->nletters; ++k) {
+        const int b = (unsigned char)sc->letters[k];
+        if (seen[b]) { set_err("%s: letter 0x%02x is listed twice", who, b); return SW_EINVAL; }
+        seen[b] = true;
+    }
+    if (sc->gap_open > 0 || sc->gap_extend > 0 || (int64_t)sc->gap_open + sc->gap_extend < -(1ll << 24)) {
+        set_err("%s: gap_open and gap_extend must be <= 0 and their sum at least -2^24", who);
+        return SW_EINVAL;
+    }
+    if ((int64_t)sc->smax * std::min(maxq, maxlen) >= (1ll << 24)) { set_err("%s: smax times min(longest query, longest target) reaches 2^24", who); return SW_EINVAL; }
+    return SW_OK;
+}
+
+int64_t floor_div(int64_t a, int64_t b) {   // b > 0; C++ '/' truncates toward zero
+    int64_t q = a / b;
+    if (a % b != 0 && a < 0) --q;
+    return q;
+}
+
+}  // namespace
+
+extern "C" {
+
+// The CPU leg of sw_db_pssm_from_hits: per query the counts of its used entries, walked op by op, then the rounded weighted mean.
+// Everything is checked before the first byte is written.
+int sw_pssm_from_hits_host(const int8_t* prior, const int64_t* qoffsets, int64_t nqueries, const char* db, const int64_t* offsets, int64_t ntargets,
+                           const sw_pssm_scoring* scoring, const sw_pssm_update* upd, const sw_hit* hits, const int64_t* nhits, int64_t top,
+                           const sw_alignment* aln, const char* ops, int64_t ops_cap, const int32_t* weights, int8_t* pssm_out, int32_t* counts) {
+    const char* who = "sw_pssm_from_hits_host";
+    if (!prior || !qoffsets || !db || !offsets || !scoring) { swh::set_err("%s: NULL pointer", who); return SW_EINVAL; }
+    if (int rc = check_host_args(who, qoffsets, nqueries, offsets, ntargets, scoring)) return rc;
+    if (int rc = swh::check_pssm_update(who, upd, top, hits, aln, ops, ops_cap, pssm_out, counts)) return rc;
+    const int n = scoring->nletters;
+    int code[256];
+    std::fill(code, code + 256, -1);
+    for (int k = 0; k < n; ++k) code[(unsigned char)scoring->letters[k]] = k;
+    std::vector<int8_t> S((size_t)n * n);
+    swh::pssm_update_table(upd->sub, scoring->letters, n, S.data());
+    std::vector<int32_t> C;
+    for (int64_t q = 0; q < nqueries; ++q) {
+        const int64_t g0 = qoffsets[q], qlen = qoffsets[q + 1] - g0;
+        C.assign((size_t)(qlen * n), 0);
+        const int64_t nh = nhits ? std::clamp<int64_t>(nhits[q], 0, top) : top;
+        for (int64_t r = 0; r < nh; ++r) {
+            const int64_t e = q * top + r;
+            const uint64_t t = (uint64_t)hits[e].target;
+            if (t >= (uint64_t)ntargets) continue;
+            const sw_alignment& a = aln[e];
+            if (a.max_score < upd->include_min_score || a.nops <= 0 || a.nops > ops_cap) continue;
+            const int64_t len = offsets[t + 1] - offsets[t];
+            if ((uint64_t)a.q_begin > (uint64_t)qlen || (uint64_t)a.t_begin > (uint64_t)len) continue;
+            const int32_t w = weights ? std::clamp<int32_t>(weights[e], 0, 65535) : 1;
+            const unsigned char* tb = (const unsigned char*)db + offsets[t];
+            const char* row = ops + e * ops_cap;
+            int64_t j = a.q_begin, i = a.t_begin;
+            for (int64_t o = 0; o < a.nops; ++o) {
+                const char op = row[o];
+                if (op == 'M') {
+                    if (j < qlen && i < len && code[tb[i]] >= 0) C[(size_t)(j * n + code[tb[i]])] += w;
+                    ++j; ++i;
+                } else if (op == 'I') ++j;
+                else if (op == 'D') ++i;
+            }
+        }
+        if (counts) std::copy(C.begin(), C.end(), counts + (g0 - qoffsets[0]) * n);
+        if (!pssm_out) continue;
+        for (int64_t j = 0; j < qlen; ++j) {
+            const int32_t* cj = C.data() + j * n;
+            int64_t N = 0;
+            for (int k = 0; k < n; ++k) N += cj[k];
+            const int64_t den = (int64_t)upd->prior_weight + N;
+            for (int k = 0; k < n; ++k) {
+                const int64_t P = std::min<int>(prior[(g0 + j) * n + k], scoring->smax);
+                int64_t v = P;
+                if (den != 0) {
+                    int64_t num = (int64_t)upd->prior_weight * P;
+                    for (int b = 0; b < n; ++b) num += (int64_t)cj[b] * S[(size_t)b * n + k];
+                    v = std::clamp<int64_t>(floor_div(2 * num + den, 2 * den), -128, 127);
+                }
+                pssm_out[(g0 + j) * n + k] = (int8_t)v;
+            }
+        }
+    }
+    return SW_OK;
+}
+
 }  // extern "C"

@@ -1,0 +1,265 @@
+"""Shared by the tests of the PSSM update (test_pssm_hits_host.py, test_pssm_hits_gpu.py, test_pssm_hits_cli_gpu.py): a numpy
+restatement of the rule in include/swhip.h (sw_db_pssm_from_hits) -- used entries, the walk, weights, counts, round half up with floor
+division -- that shares no code with the library, and the builders of the cases: synthetic tables that put ops on every side of a
+64-op chunk, garbage tables, and real tables from the host legs of the search and the alignment over a database with planted
+homologues.  The builders assert that what they build is not vacuous."""
+import types
+
+import numpy as np
+
+from affine_cases import PROTEIN, random_submat
+
+QLENS = [1, 63, 64, 65, 257, 513]
+QFRONT = 3                                     # qoffsets[0]: unused columns in front of the first query
+NOPS = [1, 63, 64, 65, 128, 129, 300]
+OPS_CAP = 300
+M, I, D = ord("M"), ord("I"), ord("D")
+
+
+def letters_of(rng, n):
+    """n distinct target bytes, the protein letters (what the databases are drawn from) first."""
+    if n <= len(PROTEIN):
+        return PROTEIN[:n].copy()
+    rest = np.setdiff1d(np.arange(256, dtype=np.uint8), PROTEIN)
+    return np.concatenate([PROTEIN, rng.permutation(rest)[:n - len(PROTEIN)]]).astype(np.uint8)
+
+
+def reference(c, prior_weight, include_min, weights=None):
+    """(new matrix int8 in the layout of c.prior, counts int32 rebased to the first query, used (nq, top) bool) by the rule of the header."""
+    nl, nq, top = len(c.letters), len(c.qoffs) - 1, c.hits.shape[1]
+    ntargets = len(c.offs) - 1
+    code = np.full(256, -1, np.int64)
+    code[c.letters] = np.arange(nl)
+    S = c.sub[np.ix_(c.letters, c.letters)].astype(np.int64)             # S[b][k]: the observed residue plays the query letter
+    P = np.minimum(c.prior.astype(np.int64), c.smax)
+    out = c.prior.astype(np.int64).copy()
+    counts = np.zeros((int(c.qoffs[-1] - c.qoffs[0]), nl), np.int64)
+    used = np.zeros((nq, top), bool)
+    for q in range(nq):
+        g0, qlen = int(c.qoffs[q]), int(c.qoffs[q + 1] - c.qoffs[q])
+        nh = top if c.nhits is None else int(np.clip(c.nhits[q], 0, top))
+        C = np.zeros((qlen, nl), np.int64)
+        for r in range(nh):
+            t = int(c.hits[q, r, 0])
+            if not 0 <= t < ntargets:
+                continue
+            ms, qb, tb, nops = (int(c.aln[q, r, f]) for f in (1, 2, 3, 6))
+            if ms < include_min or not 0 < nops <= c.cap:
+                continue
+            ln = int(c.offs[t + 1] - c.offs[t])
+            if not (0 <= qb <= qlen and 0 <= tb <= ln):
+                continue
+            used[q, r] = True
+            w = 1 if weights is None else int(np.clip(weights[q, r], 0, 65535))
+            o = c.ops[q * top + r, :nops]
+            is_m = o == M
+            cq, ct = is_m | (o == I), is_m | (o == D)
+            j, i = qb + np.cumsum(cq) - cq, tb + np.cumsum(ct) - ct        # where every op stands before it consumes anything
+            pair = is_m & (j < qlen) & (i < ln)
+            k = code[c.packed[c.offs[t] + i[pair]]]
+            np.add.at(C, (j[pair][k >= 0], k[k >= 0]), w)
+        counts[g0 - int(c.qoffs[0]):g0 - int(c.qoffs[0]) + qlen] = C
+        N = C.sum(axis=1)
+        den = (prior_weight + N)[:, None]
+        num = prior_weight * P[g0:g0 + qlen] + C @ S
+        new = np.clip((2 * num + den) // np.maximum(2 * den, 1), -128, 127)    # numpy's // floors
+        out[g0:g0 + qlen] = np.where(den == 0, P[g0:g0 + qlen], new)
+    assert counts.max(initial=0) < 2**28
+    return out.astype(np.int8), counts.astype(np.int32), used
+
+
+def _case(rng, letters, smax, qlens, packed, offs, top, lo=-8, hi=12, sub=None):
+    c = types.SimpleNamespace()
+    c.letters, c.smax, c.other = np.asarray(letters, np.uint8), int(smax), -4
+    c.qoffs = np.concatenate([[QFRONT], QFRONT + np.cumsum(qlens)]).astype(np.int64)
+    c.prior = rng.integers(lo, hi + 1, (int(c.qoffs[-1]), len(c.letters))).astype(np.int8)   # the unused front columns too
+    c.packed, c.offs = packed, offs
+    c.sub = random_submat(rng) if sub is None else sub
+    nq = len(qlens)
+    c.hits = np.zeros((nq, top, 3), np.int64)
+    c.nhits = None
+    c.aln = np.zeros((nq, top, 7), np.int64)
+    c.cap = OPS_CAP
+    c.ops = np.full((nq * top, OPS_CAP), 0x5A, np.uint8)
+    return c
+
+
+def scoring(c):
+    return (c.letters, c.other, c.smax, -10, -1)
+
+
+def _pattern(rng, kind, nops):
+    """nops op bytes of one of the shapes the chunked walk can get wrong."""
+    if kind == 0:
+        o = np.full(nops, M)
+    elif kind == 1:                          # a run of I longer than a chunk: a whole chunk consumes the query only
+        o = np.concatenate([np.full(3, M), np.full(70, I), np.full(max(0, nops - 73), M)])
+    elif kind == 2:                          # ... and of D: the target only
+        o = np.concatenate([np.full(3, M), np.full(70, D), np.full(max(0, nops - 73), M)])
+    elif kind == 3:                          # an M directly on each side of every chunk edge, nothing else pairs
+        o = np.where(np.arange(nops) % 2 == 0, I, D)
+        edge = np.arange(64, nops, 64)
+        o[edge] = M
+        o[edge - 1] = M
+    else:
+        o = rng.choice([M, M, M, I, D], nops)
+    return o[:nops].astype(np.uint8)
+
+
+def synthetic(rng, nletters, top, qlens=QLENS, smax=11, dup_targets=None):
+    """Tables written by hand over a small database: every nops of NOPS, every pattern, q_begin at 0 and at qlen - 1, alignments that end
+    exactly at qlen and at len, in turn over the entries."""
+    letters = letters_of(rng, nletters)
+    tlens = [0, 1, 5, 64, 65, 130, 400, 700] if dup_targets is None else dup_targets
+    offs = np.concatenate([[7], 7 + np.cumsum(tlens)]).astype(np.int64)
+    packed = rng.choice(PROTEIN, int(offs[-1])).astype(np.uint8)
+    c = _case(rng, letters, smax, qlens, packed, offs, top)
+    nq, n = len(qlens), 0
+    kinds = set()
+    for q in range(nq):
+        qlen = qlens[q]
+        for r in range(top):
+            nops, kind, place = NOPS[n % len(NOPS)], (n // len(NOPS)) % 5, (n // (5 * len(NOPS))) % 4
+            n += 1
+            t = int(rng.integers(0, len(tlens)))
+            ln = tlens[t]
+            o = _pattern(rng, kind, nops)
+            nq_used, nt_used = int(((o == M) | (o == I)).sum()), int(((o == M) | (o == D)).sum())
+            if place == 0:
+                qb, tb = 0, 0
+            elif place == 1:
+                qb, tb = qlen - 1, int(rng.integers(0, ln + 1))
+            elif place == 2:                 # ends exactly at qlen and at len where it fits (a walk past either end is defined too)
+                qb, tb = max(0, qlen - nq_used), max(0, ln - nt_used)
+            else:
+                qb, tb = int(rng.integers(0, qlen + 1)), int(rng.integers(0, ln + 1))
+            c.hits[q, r] = (t, 0, 0)
+            c.aln[q, r] = (0, int(rng.integers(0, 100)), qb, tb, 0, 0, nops)
+            c.ops[q * top + r, :nops] = o
+            kinds.add((nops, kind, place))
+    if nq * top >= 5 * len(NOPS):
+        assert len({(a, b) for a, b, _ in kinds}) == 5 * len(NOPS)         # every nops with every pattern
+    return c
+
+
+def garbage(rng, c):
+    """The same case with entries no alignment call would write: the call has to stay defined and inside its buffers."""
+    nq, top, _ = c.hits.shape
+    ntargets = len(c.offs) - 1
+    flat = [(q, r) for q in range(nq) for r in range(top)]
+    for n, (q, r) in enumerate(flat):
+        what = n % 9
+        if what == 0:
+            c.hits[q, r, 0] = -1
+        elif what == 1:
+            c.hits[q, r, 0] = ntargets
+        elif what == 2:
+            c.aln[q, r, 6] = 0
+        elif what == 3:
+            c.aln[q, r, 6] = c.cap + 1
+        elif what == 4:
+            c.aln[q, r, 2] = int(c.qoffs[q + 1] - c.qoffs[q]) + 1
+        elif what == 5:
+            c.ops[q * top + r, ::3] = 0x00
+            c.ops[q * top + r, 1::3] = 0xFF
+        elif what == 6:                      # a walk that runs past qlen and len
+            c.aln[q, r, 6] = c.cap
+            c.ops[q * top + r] = M
+        elif what == 7:
+            c.aln[q, r, 3] = -1
+        # 8: left as it is
+    c.nhits = np.array([(-5, top + 7, top, max(0, top - 1))[q % 4] for q in range(nq)], np.int64)
+    return c
+
+
+def mutate(rng, seq, alpha):
+    """A homologue: substitutions, insertions and deletions."""
+    out = []
+    for x in seq:
+        u = rng.random()
+        if u < 0.03:
+            continue
+        out.append(int(rng.choice(alpha)) if u < 0.15 else int(x))
+        if rng.random() < 0.03:
+            out.extend(int(y) for y in rng.choice(alpha, int(rng.integers(1, 4))))
+    return np.array(out, np.uint8)
+
+
+def homologue_database(rng, queries, nrandom, copies=3):
+    """Random protein targets of 0..600 letters with `copies` mutated copies of every query planted inside flanks."""
+    targets = [rng.choice(PROTEIN[:20], int(n)).astype(np.uint8) for n in [0, 1, 63, 64, 65, 0] + list(rng.integers(2, 601, nrandom))]
+    for qs in queries:
+        for _ in range(copies):
+            targets.append(np.concatenate([rng.choice(PROTEIN[:20], int(rng.integers(0, 40))).astype(np.uint8), mutate(rng, qs, PROTEIN[:20]),
+                                           rng.choice(PROTEIN[:20], int(rng.integers(0, 40))).astype(np.uint8)]))
+    order = rng.permutation(len(targets))
+    targets = [targets[k] for k in order]
+    offs = np.concatenate([[7], 7 + np.cumsum([len(t) for t in targets])]).astype(np.int64)
+    packed = np.concatenate([rng.integers(0, 256, 7).astype(np.uint8)] + targets)
+    return packed, offs
+
+
+def real(swamd, rng, top, qlens=QLENS, nrandom=40, nletters=24):
+    """Iteration 0 of a search on the host: sequence queries through sw_pssm_from_queries, the search, the rank order, the alignment."""
+    from pssm_cases import rank_order
+    letters = letters_of(rng, nletters)
+    queries = [rng.choice(PROTEIN[:20], n).astype(np.uint8) for n in qlens]
+    packed, offs = homologue_database(rng, queries, nrandom)
+    sub = random_submat(rng, lo=-6, hi=8)
+    sub = np.minimum(sub, sub.T)                                            # (symmetric, as real tables are; nothing depends on it)
+    c = _case(rng, letters, 127, qlens, packed, offs, top, sub=sub)
+    m, moffs = swamd.pssm_from_queries(queries, sub, letters)
+    c.prior[QFRONT:] = m
+    c.queries = queries
+    sc = scoring(c)
+    res = swamd.search_pssm_multi_host((c.prior, c.qoffs), (packed, offs), sc)
+    c.hits, c.nhits = rank_order(res, top, 1)
+    aln, ops = swamd.align_pssm_hits_host((c.prior, c.qoffs), (packed, offs), sc, c.hits, c.nhits)
+    c.aln = aln
+    c.cap = max(1, max(qlens) + int(np.diff(offs).max()))
+    c.ops = np.full((len(qlens) * top, c.cap), 0x5A, np.uint8)
+    for q, row in enumerate(ops):
+        for r, b in enumerate(row):
+            c.ops[q * top + r, :len(b)] = np.frombuffer(b, np.uint8)
+    # not vacuous: conditions on the inputs
+    _, counts, used = reference(c, 1, 1)
+    live = c.ops[np.arange(c.cap)[None, :] < c.aln.reshape(-1, 7)[:, 6:7]]       # the op bytes inside every row's nops
+    assert used.sum() * 2 >= used.size, "fewer than half of the entries are used"
+    assert (live == I).any() and (live == D).any(), "the alignments hold no I or no D"
+    assert c.aln[:, :, 6].max() > 64, "no alignment exceeds 64 ops"
+    assert counts.sum(axis=1).max() >= 2, "no column was observed twice"
+    return c
+
+
+GUARD, POISON = 64, 0x55
+
+
+def host_leg(swamd, c, prior_weight, include_min, weights=None, want_out=True, want_counts=True, in_place=False):
+    """sw_pssm_from_hits_host through ctypes on buffers with guard bytes around them and poison in the unused front columns: asserts
+    SW_OK and that nothing outside the queries' columns changed.  Returns (matrix of the queries' columns or None, counts or None)."""
+    import ctypes
+    L = swamd.lib()
+    lt, sc = swamd._pssm_scoring(scoring(c))
+    sub, up = swamd._pssm_update((c.sub, prior_weight, include_min))
+    nl, nq, top = len(c.letters), len(c.qoffs) - 1, c.hits.shape[1]
+    front, total = int(c.qoffs[0]) * nl, int(c.qoffs[-1]) * nl
+    prior = np.full(GUARD + total + GUARD, POISON, np.int8)
+    prior[GUARD + front:GUARD + total] = c.prior.reshape(-1)[front:]
+    out = prior if in_place else np.full(GUARD + total + GUARD, POISON, np.int8)
+    ncnt = total - front
+    counts = np.full(GUARD + ncnt + GUARD, 0x55555555, np.int32)
+    hits, aln, ops = np.ascontiguousarray(c.hits), np.ascontiguousarray(c.aln), np.ascontiguousarray(c.ops)
+    w = None if weights is None else np.ascontiguousarray(weights, np.int32)
+    rc = L.sw_pssm_from_hits_host(prior[GUARD:].ctypes.data, c.qoffs.ctypes.data, nq, c.packed.ctypes.data, c.offs.ctypes.data, len(c.offs) - 1,
+                                  ctypes.byref(sc), ctypes.byref(up), hits.ctypes.data, c.nhits.ctypes.data if c.nhits is not None else None, top,
+                                  aln.ctypes.data, ops.ctypes.data, c.cap, w.ctypes.data if w is not None else None,
+                                  out[GUARD:].ctypes.data if want_out else None, counts[GUARD:].ctypes.data if want_counts else None)
+    assert rc == 0, L.sw_last_error().decode()
+    assert (out[:GUARD + front] == POISON).all() and (out[GUARD + total:] == POISON).all(), "the matrix was written outside the queries' columns"
+    assert (counts[:GUARD] == 0x55555555).all() and (counts[GUARD + ncnt:] == 0x55555555).all(), "the counts were written outside their buffer"
+    if not want_out and not in_place:
+        assert (out == POISON).all()
+    if not want_counts:
+        assert (counts == 0x55555555).all()
+    return (out[GUARD + front:GUARD + total].reshape(-1, nl).copy() if want_out else None,
+            counts[GUARD:GUARD + ncnt].reshape(-1, nl).copy() if want_counts else None)
