@@ -18,12 +18,12 @@ int sw_create(int device, sw_ctx** out) {
     hipDeviceProp_t prop;
     HIP_TRY(hipGetDeviceProperties(&prop, device));
     c->num_cus = prop.multiProcessorCount;
-    HIP_TRY(hipMalloc((void**)&c->d_key, 64));
+    if (int rc = c->d_key.once(64)) return rc;
     HIP_TRY(hipMemset(c->d_key, 0, 64));
-    HIP_TRY(hipMalloc((void**)&c->d_alpha, 2048));
+    if (int rc = c->d_alpha.once(2048)) return rc;
     HIP_TRY(hipMemset(c->d_alpha, 0, 2048));
-    HIP_TRY(hipMalloc((void**)&c->d_part, 2048 * 32));
-    HIP_TRY(hipMalloc((void**)&c->d_sync, 256));
+    if (int rc = c->d_part.once(2048 * 32)) return rc;
+    if (int rc = c->d_sync.once(256)) return rc;
     HIP_TRY(hipMemset(c->d_sync, 0, 256));
     // Are the workgroups of a launch dealt round-robin to 8 XCDs of 32 CUs (workgroup i on XCD i % 8)?  The two-column kernel then
     // places every scout on the XCD of the workgroups that read its edge column (sw_systolic2.inc).
@@ -44,48 +44,12 @@ int sw_create(int device, sw_ctx** out) {
 void sw_destroy(sw_ctx* c) {
     if (!c) return;
     (void)hipSetDevice(c->device);
-    if (c->d_edge) (void)hipFree(c->d_edge);
-    if (c->d_key) (void)hipFree(c->d_key);
-    if (c->d_cb) (void)hipFree(c->d_cb);
-    if (c->d_edge4) (void)hipFree(c->d_edge4);
-    if (c->d_alpha) (void)hipFree(c->d_alpha);
-    if (c->d_part) (void)hipFree(c->d_part);
-    if (c->d_sync) (void)hipFree(c->d_sync);
-    if (c->d_priv) (void)hipFree(c->d_priv);
-    if (c->d_keys) (void)hipFree(c->d_keys);
-    if (c->d_bcodes) (void)hipFree(c->d_bcodes);
-    if (c->d_bnd) (void)hipFree(c->d_bnd);
+    // the uploads from the pinned copies have to have left them; every Workspace and Staged member is released with the context
     if (c->sitems_ev) { (void)hipEventSynchronize(c->sitems_ev); (void)hipEventDestroy(c->sitems_ev); }
-    if (c->d_sprof) (void)hipFree(c->d_sprof);
-    if (c->d_sbnd) (void)hipFree(c->d_sbnd);
-    if (c->d_sitems) (void)hipFree(c->d_sitems);
-    if (c->h_sitems) (void)hipHostFree(c->h_sitems);
-    if (c->d_sctr) (void)hipFree(c->d_sctr);
-    if (c->d_submat) (void)hipFree(c->d_submat);
-    if (c->h_submat) (void)hipHostFree(c->h_submat);
-    if (c->d_adir) (void)hipFree(c->d_adir);
-    if (c->d_ahitems) (void)hipFree(c->d_ahitems);
-    if (c->d_ahctl) (void)hipFree(c->d_ahctl);
-    if (c->d_ahfilled) (void)hipFree(c->d_ahfilled);
-    if (c->d_spitems) (void)hipFree(c->d_spitems);
-    if (c->d_spctl) (void)hipFree(c->d_spctl);
-    if (c->d_spcells) (void)hipFree(c->d_spcells);
-    if (c->d_sptotal) (void)hipFree(c->d_sptotal);
-    if (c->d_pfctl) (void)hipFree(c->d_pfctl);
-    if (c->d_mq) (void)hipFree(c->d_mq);
-    if (c->h_mq) (void)hipHostFree(c->h_mq);
-    if (c->d_tres) (void)hipFree(c->d_tres);
-    if (c->d_thist) (void)hipFree(c->d_thist);
-    if (c->d_tstate) (void)hipFree(c->d_tstate);
-    if (c->d_tpkeys) (void)hipFree(c->d_tpkeys);
-    if (c->d_tppos) (void)hipFree(c->d_tppos);
-    if (c->d_tpseg) (void)hipFree(c->d_tpseg);
-    if (c->d_tplist) (void)hipFree(c->d_tplist);
     for (int i = 0; i < 2; ++i) {
         if (c->phtab_ev[i]) { (void)hipEventSynchronize(c->phtab_ev[i]); (void)hipEventDestroy(c->phtab_ev[i]); }
         if (c->h_phtab[i]) (void)hipHostFree(c->h_phtab[i]);
     }
-    if (c->d_phtab) (void)hipFree(c->d_phtab);
     delete c;
 }
 
@@ -188,8 +152,8 @@ int64_t sw_get_option(sw_ctx* c, const char* name) {
     if (!strcmp(name, "pace_ps")) return c->opt_pace_ps;
     if (!strcmp(name, "band_wait_ms")) return c->opt_band_wait_ms;
     if (!strcmp(name, "num_cus")) return c->num_cus;
-    if (!strcmp(name, "debug_edge4_ptr")) return (int64_t)(uintptr_t)c->d_edge4;
-    if (!strcmp(name, "debug_edge4_cap")) return (int64_t)c->edge4_cap;
+    if (!strcmp(name, "debug_edge4_ptr")) return (int64_t)(uintptr_t)c->d_edge4.p;
+    if (!strcmp(name, "debug_edge4_cap")) return (int64_t)c->d_edge4.cap;
     if (!strcmp(name, "last_grid")) return c->last_grid;
     const swp::TilePlan& last_tile = c->last_plan.tile[c->last_plan.ntile - 1];   // (all zero where the two-column kernel did not run)
     if (!strcmp(name, "last_strips")) return c->last_plan.S;
@@ -255,7 +219,7 @@ int64_t sw_get_option(sw_ctx* c, const char* name) {
     if (!strcmp(name, "last_prefilter_groups")) return c->last_prefilter_groups;
     if (!strcmp(name, "last_prefilter_launches")) return c->last_prefilter_launches;
     if (!strcmp(name, "last_prefilter_packed_launches")) return c->last_prefilter_packed_launches;
-    if (!strcmp(name, "debug_search_pairs_items_ptr")) return (int64_t)(uintptr_t)c->d_spitems;
+    if (!strcmp(name, "debug_search_pairs_items_ptr")) return (int64_t)(uintptr_t)c->d_spitems.p;
     if (!strcmp(name, "placement_budget_ms")) return c->opt_place_budget_ms;
     if (!strcmp(name, "placement_hold_gib")) return c->opt_place_hold_gib;
     if (!strcmp(name, "probe_foreign_pairs")) return c->opt.probe_foreign_pairs;

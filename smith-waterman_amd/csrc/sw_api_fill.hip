@@ -28,21 +28,20 @@ struct FillJob {
 };
 
 static int ensure_workspaces(sw_ctx* c, const swp::FillPlan& f, hipStream_t stream) {
-    bool fresh = false;
-    if (int rc = grow_workspace((void**)&c->d_edge, c->edge_cap, f.edge_need, 8, 0, stream, fresh)) return rc;
-    if (fresh) { HIP_TRY(hipMemsetAsync(c->d_edge, 0, c->edge_cap * 8, stream)); c->epoch = 0; }
-    if (int rc = grow_workspace((void**)&c->d_cb, c->cb_cap, f.cb_need, 4, 64, stream, fresh)) return rc;
-    if (int rc = grow_workspace((void**)&c->d_edge4, c->edge4_cap, f.edge4_need, 4, 0, stream, fresh)) return rc;
-    if (fresh) c->epoch8 = 255;   // fresh memory: the next tag wraps and wipes it
-    return grow_workspace((void**)&c->d_priv, c->priv_cap, f.priv_need, 1, 0, stream, fresh);
+    if (int rc = c->d_edge.grow(f.edge_need, stream)) return rc;
+    if (c->d_edge.fresh) { HIP_TRY(hipMemsetAsync(c->d_edge, 0, c->d_edge.cap * 8, stream)); c->epoch = 0; }
+    if (int rc = c->d_cb.grow(f.cb_need, stream, 64)) return rc;
+    if (int rc = c->d_edge4.grow(f.edge4_need, stream)) return rc;
+    if (c->d_edge4.fresh) c->epoch8 = 255;   // fresh memory: the next tag wraps and wipes it
+    return c->d_priv.grow(f.priv_need, stream);
 }
 
 // Advances the 8-bit launch tag of the perm producer's self-tagged edge values and returns the G bias that carries it.  A wrapped tag
 // could match stale values: they are wiped.
 static unsigned next_gbias(sw_ctx* c, hipStream_t stream) {
     if (++c->epoch8 >= (unsigned)((c->opt.debug_flags & swk::DBG_EPOCH8_WRAP_EARLY) ? 4 : 256)) {
-        const unsigned nb = (unsigned)std::max<size_t>(1, std::min<size_t>((c->edge4_cap + 255) / 256, 2048));
-        hipLaunchKernelGGL(swk::sw_wipe_u32, dim3(nb), dim3(256), 0, stream, c->d_edge4, c->edge4_cap);
+        const unsigned nb = (unsigned)std::max<size_t>(1, std::min<size_t>((c->d_edge4.cap + 255) / 256, 2048));
+        hipLaunchKernelGGL(swk::sw_wipe_u32, dim3(nb), dim3(256), 0, stream, c->d_edge4, c->d_edge4.cap);
         c->epoch8 = 1;
     }
     return (c->epoch8 << 24) | 0x10000u;
@@ -111,7 +110,7 @@ static int launch_fill(sw_ctx* c, const sw_scores* sc, const FillJob& j, hipStre
     if (systolic && one_col == std::end(kSystolic)) { set_err("unsupported strips_per_group/consumers combination %d/%d", plan.NS, plan.NC); return SW_EINVAL; }
     if (int rc = ensure_workspaces(c, plan, stream)) return rc;
     if (++c->epoch >= 4096) {  // 12-bit tag wrapped: stale tags could match again, wipe them
-        HIP_TRY(hipMemsetAsync(c->d_edge, 0, c->edge_cap * 8, stream));
+        HIP_TRY(hipMemsetAsync(c->d_edge, 0, c->d_edge.cap * 8, stream));
         c->epoch = 1;
     }
     c->last_plan = plan;
@@ -148,9 +147,9 @@ static int launch_fill(sw_ctx* c, const sw_scores* sc, const FillJob& j, hipStre
         HIP_TRY(hipGetLastError());
         return SW_OK;
     }
-    const size_t cb16 = ((c->cb_cap + 15) / 16) * 16;
+    const size_t cb16 = ((c->d_cb.cap + 15) / 16) * 16;
     unsigned short* d_cb16 = (unsigned short*)(c->d_cb + cb16);
-    unsigned char* d_cbc = c->d_cb + cb16 + ((2 * c->cb_cap + 15) / 16) * 16;
+    unsigned char* d_cbc = c->d_cb + cb16 + ((2 * c->d_cb.cap + 15) / 16) * 16;
     if (plan.perm) {
         p.edge4 = c->d_edge4; p.e4stride = plan.e4stride; p.edge4_pstride = S * plan.e4stride;
         p.gbias = next_gbias(c, stream);
@@ -356,9 +355,8 @@ static_assert(std::size(kBatch) == swp::kBatchKernels && at_their_indices(kBatch
 static int batch_one_pair_per_wave(sw_ctx* c, const swp::BatchPlan& plan, const char* d_a, int64_t a_stride, int64_t cols, const char* d_b,
                                    int64_t b_stride, int64_t rows, int64_t npairs, const sw_scores* sc, int32_t* d_H, void* d_P, int p_elem_bytes,
                                    sw_result* d_results, hipStream_t stream) {
-    bool fresh = false;
-    if (int rc = grow_workspace((void**)&c->d_bcodes, c->bcodes_cap, plan.bcodes_need, 1, 64, stream, fresh)) return rc;
-    if (int rc = grow_workspace((void**)&c->d_bnd, c->bnd_cap, plan.bnd_need, 4, 0, stream, fresh)) return rc;
+    if (int rc = c->d_bcodes.grow(plan.bcodes_need, stream, 64)) return rc;
+    if (int rc = c->d_bnd.grow(plan.bnd_need, stream)) return rc;
     const unsigned char* ua = (const unsigned char*)d_a;
     const unsigned char* ub = (const unsigned char*)d_b;
     // alphabet of the whole batch -> letter codes; the count decides whether the profile look-up applies
@@ -432,8 +430,7 @@ int sw_batch_device_ex(sw_ctx* c, const char* d_a, int64_t a_stride, int64_t col
         if (rc != 1) return rc;      // 1: not eligible after all (an alphabet of more than 8 letters)
     }
     // the fall-back: the single-pair machinery, plan.single_chunk pairs per launch
-    bool fresh = false;
-    if (int rc = grow_workspace((void**)&c->d_keys, c->keys_cap, (size_t)plan.single_chunk, 8, 0, stream, fresh)) return rc;
+    if (int rc = c->d_keys.grow((size_t)plan.single_chunk, stream)) return rc;
     HIP_TRY(hipMemsetAsync(c->d_key, 0, 16, stream));
     c->key_dirty = true;
     const int64_t cells = (cols + 1) * (rows + 1);

@@ -112,54 +112,25 @@ static constexpr Indexed<TopPairsSortKernel> kTopPairsSort[] = {
 };
 static_assert(std::size(kTopPairsSort) == swp::kTopPairsKernels && at_their_indices(kTopPairsSort));
 
-// occupancy of every instantiation of a table at 256 threads, asked once per context: the plans' columns per lane and grids depend on it
-template <typename K, size_t N>
-static int occupancy_once(const Indexed<K> (&tab)[N], int (&per_cu)[N], bool& known) {
-    if (known) return SW_OK;
-    for (size_t k = 0; k < N; ++k) HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu[k], tab[k].k, 256, 0));
-    known = true;
-    return SW_OK;
-}
-
-// The search schedule's device buffer and the pinned copy it is uploaded from, grown together to `need` items (the caller has waited
-// for the last upload from the pinned copy).
-static int grow_schedule(sw_ctx* c, size_t need, hipStream_t stream) {
-    if (need <= c->sitems_cap) return SW_OK;
-    HIP_TRY(hipStreamSynchronize(stream));
-    if (c->d_sitems) HIP_TRY(hipFree(c->d_sitems));
-    if (c->h_sitems) HIP_TRY(hipHostFree(c->h_sitems));
-    c->d_sitems = nullptr; c->h_sitems = nullptr; c->sitems_cap = 0;
-    if (hipMalloc((void**)&c->d_sitems, need * sizeof(swk::SearchItem)) != hipSuccess ||
-        hipHostMalloc((void**)&c->h_sitems, need * sizeof(swk::SearchItem), 0) != hipSuccess) {
-        set_err("sw_search_device: workspace allocation failed");
-        return SW_ENOMEM;
-    }
-    c->sitems_cap = need;
-    return SW_OK;
-}
-
 // The schedule and the table are uploaded from pinned copies, which a call overwrites: first the previous call's uploads have to have left
 // them (sitems_ev, recorded by upload_search_call).  Then the workspaces the three kernels share grow to what this call's plan needs; the
-// counter and (for a call with a `table`) the table's two copies are allocated at their first use.  On return c->h_sitems is free to write.
+// counter and (for a call with a `table`) the table's two copies are allocated at their first use.  On return c->sitems.h is free to write.
 static int stage_search_call(sw_ctx* c, hipStream_t stream, size_t nitems, size_t prof_need, size_t bnd_need, bool table) {
     if (c->sitems_ev) HIP_TRY(hipEventSynchronize(c->sitems_ev));
     else HIP_TRY(hipEventCreateWithFlags(&c->sitems_ev, hipEventDisableTiming));
-    bool fresh = false;
-    if (int rc = grow_schedule(c, nitems, stream)) return rc;
-    if (int rc = grow_workspace((void**)&c->d_sprof, c->sprof_cap, prof_need, 1, 0, stream, fresh)) return rc;
-    if (int rc = grow_workspace((void**)&c->d_sbnd, c->sbnd_cap, bnd_need, 4, 0, stream, fresh)) return rc;
-    if (!c->d_sctr) HIP_TRY(hipMalloc((void**)&c->d_sctr, 64));
-    if (table && !c->d_submat) HIP_TRY(hipMalloc((void**)&c->d_submat, sizeof(sw_submat)));
-    if (table && !c->h_submat) HIP_TRY(hipHostMalloc((void**)&c->h_submat, sizeof(sw_submat), 0));
-    return SW_OK;
+    if (int rc = c->sitems.grow(nitems, stream, "sw_search_device")) return rc;
+    if (int rc = c->d_sprof.grow(prof_need, stream)) return rc;
+    if (int rc = c->d_sbnd.grow(bnd_need, stream)) return rc;
+    if (int rc = c->d_sctr.once(64)) return rc;
+    return table ? c->submat.once() : SW_OK;
 }
 
-// Uploads the schedule the caller has written to c->h_sitems, and the table through its pinned copy.  The event is recorded once, behind
+// Uploads the schedule the caller has written to c->sitems.h, and the table through its pinned copy.  The event is recorded once, behind
 // BOTH uploads: whoever has waited for it may overwrite either pinned copy.  The work counter starts every launch at zero.
 static int upload_search_call(sw_ctx* c, hipStream_t stream, size_t nitems, const sw_submat* table) {
-    if (table) memcpy(c->h_submat, table, sizeof(sw_submat));
-    HIP_TRY(hipMemcpyAsync(c->d_sitems, c->h_sitems, nitems * sizeof(swk::SearchItem), hipMemcpyHostToDevice, stream));
-    if (table) HIP_TRY(hipMemcpyAsync(c->d_submat, c->h_submat, sizeof(sw_submat), hipMemcpyHostToDevice, stream));
+    if (table) memcpy(c->submat.h, table, sizeof(sw_submat));
+    HIP_TRY(hipMemcpyAsync(c->sitems.d, c->sitems.h, nitems * sizeof(swk::SearchItem), hipMemcpyHostToDevice, stream));
+    if (table) HIP_TRY(hipMemcpyAsync(c->submat.d, c->submat.h, sizeof(sw_submat), hipMemcpyHostToDevice, stream));
     HIP_TRY(hipEventRecord(c->sitems_ev, stream));
     HIP_TRY(hipMemsetAsync(c->d_sctr, 0, 4, stream));
     return SW_OK;
@@ -171,29 +142,21 @@ static Params search_params(const sw_ctx* c, const char* d_db, int64_t nitems, i
     Params p;
     memset(&p, 0, sizeof p);
     p.db = (const unsigned char*)d_db;
-    p.items = c->d_sitems; p.nitems = nitems;
+    p.items = c->sitems.d; p.nitems = nitems;
     p.prof = c->d_sprof; p.qpad = plan.qpad; p.qlen = qlen;
     p.bnd = plan.bnd_per ? c->d_sbnd : nullptr; p.bnd_per = plan.bnd_per;
     p.counter = c->d_sctr;
     return p;
 }
 
-// The query table of a many-query call: the device buffer and the pinned copy it is uploaded from, grown together (the caller has waited
-// for the last upload from the pinned copy: stage_search_call).
-static int grow_query_table(sw_ctx* c, size_t need, hipStream_t stream) {
-    if (need <= c->mq_cap) return SW_OK;
-    HIP_TRY(hipStreamSynchronize(stream));
-    if (c->d_mq) HIP_TRY(hipFree(c->d_mq));
-    if (c->h_mq) HIP_TRY(hipHostFree(c->h_mq));
-    c->d_mq = nullptr; c->h_mq = nullptr; c->mq_cap = 0;
-    if (hipMalloc((void**)&c->d_mq, need * sizeof(swk::MultiQuery)) != hipSuccess ||
-        hipHostMalloc((void**)&c->h_mq, need * sizeof(swk::MultiQuery), 0) != hipSuccess) {
-        set_err("sw_db_search_affine: workspace allocation failed");
-        return SW_ENOMEM;
-    }
-    c->mq_cap = need;
+// What every call on a prepared database checks first: the two handles and the pointers it cannot do without (`pointers`: all of them
+// are there), and that both handles live on one device.
+static int check_db_call(const char* who, const sw_ctx* c, const sw_db* db, bool pointers) {
+    if (!c || !db || !pointers) { set_err("%s: NULL pointer", who); return SW_EINVAL; }
+    if (db->device != c->device) { set_err("%s: the handle was created on device %d, the context runs on device %d", who, db->device, c->device); return SW_EINVAL; }
     return SW_OK;
 }
+
 
 // The lengths of a call's queries, as the planners of the many-query calls take them.
 static std::vector<int64_t> query_lengths(const int64_t* qoffsets, int64_t nqueries) {
@@ -237,22 +200,22 @@ struct QuerySource {
 
 // The start of a many-query call, behind stage_search_call (which has waited for the last uploads from the pinned copies): the plan's
 // table, every entry's qstart taken from the caller's offsets, and behind its entries an optional tail (the pair list's entry_of) go
-// through one pinned copy to c->d_mq in one upload; the scoring table follows through its own.  The event is recorded once, behind BOTH
+// through one pinned copy to c->mq.d in one upload; the scoring table follows through its own.  The event is recorded once, behind BOTH
 // uploads: whoever has waited for it may overwrite either pinned copy.
 static int upload_query_table(sw_ctx* c, hipStream_t stream, const std::vector<swk::MultiQuery>& table, const int64_t* qoffsets, const QuerySource& src,
                               const void* tail = nullptr, size_t tail_bytes = 0) {
     const size_t nq = table.size(), slots = nq + (tail_bytes + sizeof(swk::MultiQuery) - 1) / sizeof(swk::MultiQuery);
-    if (int rc = grow_query_table(c, slots, stream)) return rc;
+    if (int rc = c->mq.grow(slots, stream, "sw_db_search_affine")) return rc;
     for (size_t t = 0; t < nq; ++t) {
-        c->h_mq[t] = table[t];
-        c->h_mq[t].qstart = qoffsets[table[t].row];
+        c->mq.h[t] = table[t];
+        c->mq.h[t].qstart = qoffsets[table[t].row];
     }
-    if (tail_bytes) memcpy(c->h_mq + nq, tail, tail_bytes);
+    if (tail_bytes) memcpy(c->mq.h + nq, tail, tail_bytes);
     // a PSSM's code table takes the place of the scoring table in the same two copies: its first 256 bytes
     const size_t table_bytes = src.pssm() ? sizeof src.code : sizeof(sw_submat);
-    memcpy(c->h_submat, src.pssm() ? (const void*)src.code : (const void*)src.sub, table_bytes);
-    HIP_TRY(hipMemcpyAsync(c->d_mq, c->h_mq, slots * sizeof(swk::MultiQuery), hipMemcpyHostToDevice, stream));
-    HIP_TRY(hipMemcpyAsync(c->d_submat, c->h_submat, table_bytes, hipMemcpyHostToDevice, stream));
+    memcpy(c->submat.h, src.pssm() ? (const void*)src.code : (const void*)src.sub, table_bytes);
+    HIP_TRY(hipMemcpyAsync(c->mq.d, c->mq.h, slots * sizeof(swk::MultiQuery), hipMemcpyHostToDevice, stream));
+    HIP_TRY(hipMemcpyAsync(c->submat.d, c->submat.h, table_bytes, hipMemcpyHostToDevice, stream));
     HIP_TRY(hipEventRecord(c->sitems_ev, stream));
     return SW_OK;
 }
@@ -265,12 +228,77 @@ static int launch_group_profiles(sw_ctx* c, hipStream_t stream, const QuerySourc
     const unsigned blocks = (unsigned)std::min<int64_t>(grp.nq * parts, 4096);
     if (src.pssm())
         hipLaunchKernelGGL(swk::sw_search_profile_pssm_multi, dim3(blocks), dim3(256), swk::sw_pssm_profile_lds_bytes(src.nletters), stream, src.d_pssm,
-                           c->d_mq + grp.q0, grp.nq, parts, c->d_sprof, (const unsigned char*)c->d_submat, src.nletters, src.other, src.smax);
+                           c->mq.d + grp.q0, grp.nq, parts, c->d_sprof, (const unsigned char*)c->submat.d, src.nletters, src.other, src.smax);
     else
-        hipLaunchKernelGGL(swk::sw_search_profile_submat_multi, dim3(blocks), dim3(256), 0, stream, (const unsigned char*)src.d_queries, c->d_mq + grp.q0,
-                           grp.nq, parts, c->d_sprof, (const signed char*)c->d_submat);
+        hipLaunchKernelGGL(swk::sw_search_profile_submat_multi, dim3(blocks), dim3(256), 0, stream, (const unsigned char*)src.d_queries, c->mq.d + grp.q0,
+                           grp.nq, parts, c->d_sprof, (const signed char*)c->submat.d);
     HIP_TRY(hipGetLastError());
     return SW_OK;
+}
+
+// The twins of a launch -- the 32-bit kernel's parameters and those of its packed or checkpointed form (sw_kernels.h) -- are filled by
+// one template each: the fields the twins share; the rest is zero, and what only one of them has is set where it is launched.
+//
+// A launch cut by target ranks (SearchMultiParams, SearchMultiPackedParams, the head of PrefilterParams): its part of the handle's
+// schedule and of the query table.
+template <typename Params, typename Launch>
+static Params rank_launch_params(const sw_ctx* c, const sw_db* db, const Launch& l) {
+    Params p;
+    memset(&p, 0, sizeof p);
+    p.db = (const unsigned char*)db->d_db;
+    p.items = db->d_items; p.rank0 = l.rank0;
+    p.queries = c->mq.d + l.q0; p.nq = (unsigned)l.nq; p.nitems = l.items;
+    p.prof = c->d_sprof; p.ntargets = db->ntargets;
+    p.bnd = l.bnd_per ? c->d_sbnd : nullptr; p.bnd_per = l.bnd_per;
+    return p;
+}
+template <typename Params>
+static Params search_multi_params(const sw_ctx* c, const sw_db* db, const QuerySource& src, const swp::MultiLanesLaunch& l, sw_result* d_results) {
+    Params p = rank_launch_params<Params>(c, db, l);
+    p.ge = src.gap_extend; p.goe = src.gap_open + src.gap_extend;
+    p.counter = c->d_sctr;
+    p.results = d_results;
+    return p;
+}
+// The score launch of a class of a pair list (SearchPairsParams, SearchPairsPackedParams); items, list and counter are the caller's.
+template <typename Params>
+static Params search_pairs_params(const sw_ctx* c, const sw_db* db, const sw_affine* scoring, const swp::PairsLanesLaunch& l, sw_result* d_results) {
+    Params p;
+    memset(&p, 0, sizeof p);
+    p.db = (const unsigned char*)db->d_db;
+    p.queries = c->mq.d; p.prof = c->d_sprof;
+    p.ge = scoring->gap_extend; p.goe = scoring->gap_open + scoring->gap_extend;
+    p.bnd = l.bnd_per ? c->d_sbnd : nullptr; p.bnd_per = l.bnd_per;
+    p.results = d_results;
+    return p;
+}
+// A tier's launch of the hit-table alignment (AlignHitsParams, AlignHitsCkptParams); log_band is the caller's.
+template <typename Params>
+static Params align_hits_params(sw_ctx* c, const sw_db* db, const QuerySource& src, const swp::AlignHitsGroup& grp, const swp::AlignHitsLaunch& l,
+                                sw_alignment* d_aln, char* d_ops, int64_t ops_cap) {
+    Params p;
+    memset(&p, 0, sizeof p);
+    p.db = (const unsigned char*)db->d_db;
+    p.items = c->d_ahitems + grp.cls[l.kernel].item0;
+    p.counts = c->d_ahctl->count[l.kernel]; p.tier = l.tier;
+    p.queries = c->mq.d + grp.q0; p.prof = c->d_sprof;
+    p.ge = src.gap_extend; p.goe = src.gap_open + src.gap_extend;
+    p.bnd = l.bnd_per ? c->d_sbnd : nullptr; p.bnd_per = l.bnd_per;
+    p.counter = &c->d_ahctl->work[l.kernel][l.tier];
+    p.dir = c->d_adir; p.slot_bytes = l.slot_bytes; p.nslots = l.slots;
+    p.aln = d_aln; p.ops = d_ops; p.ops_cap = ops_cap;
+    return p;
+}
+// The alignment of one query's hits (AlignAffineParams, AlignCkptParams), on search_params; log_band is the caller's.
+template <typename Params>
+static Params align_affine_params(const sw_ctx* c, const char* d_db, int64_t nhits, int64_t qlen, const swp::AlignAffinePlan& plan, const sw_affine* scoring,
+                                  sw_alignment* d_aln, char* d_ops, int64_t ops_cap) {
+    Params p = search_params<Params>(c, d_db, nhits, qlen, plan);
+    p.ge = scoring->gap_extend; p.goe = scoring->gap_open + scoring->gap_extend;
+    p.dir = c->d_adir; p.slot_bytes = plan.slot_bytes; p.nslots = plan.slots;
+    p.aln = d_aln; p.ops = d_ops; p.ops_cap = ops_cap;
+    p.stamps = (unsigned long long*)(uintptr_t)c->opt_dbg_ptr;
+    return p;
 }
 
 // The many-query search of checked arguments into `d_results` (nqueries x ntargets, nqueries > 0, ntargets > 0): what sw_db_search_affine
@@ -282,10 +310,10 @@ static int run_search_multi(sw_ctx* c, const sw_db* db, const QuerySource& src, 
     HIP_TRY(hipMemsetAsync(d_results, 0, (size_t)nqueries * (size_t)db->ntargets * sizeof(sw_result), stream));
     c->last_search_multi_packed_launches = 0;   // (a call that launches no kernel reports none)
     if (db->nonempty == 0) return SW_OK;
-    if (int rc = occupancy_once(kSearchMulti, c->search_multi_per_cu, c->search_multi_per_cu_known)) return rc;
+    if (int rc = c->search_multi_per_cu.once(kSearchMulti)) return rc;
     const bool lanes16 = c->opt_search_lanes == 16;
     if (lanes16)
-        if (int rc = occupancy_once(kSearchMultiPacked, c->search_multi_packed_per_cu, c->search_multi_packed_per_cu_known)) return rc;
+        if (int rc = c->search_multi_packed_per_cu.once(kSearchMultiPacked)) return rc;
     const std::vector<int64_t> qlens = query_lengths(qoffsets, nqueries);
     swp::SearchMultiLanesJob mj;
     mj.qlens = qlens.data(); mj.nqueries = nqueries; mj.longest = db->longest; mj.nonempty = db->nonempty; mj.num_cus = c->num_cus;
@@ -307,35 +335,15 @@ static int run_search_multi(sw_ctx* c, const sw_db* db, const QuerySource& src, 
         if (int rc = launch_group_profiles(c, stream, src, grp)) return rc;
         for (; li < plan.launch.size() && plan.launch[li].group == (int)g; ++li) {
             const swp::MultiLanesLaunch& l = plan.launch[li];
-            if (l.packed) {   // two targets per wave: the ranks rank0 .. rank0 + nranks - 1 in pairs
-                swk::SearchMultiPackedParams kp;
-                memset(&kp, 0, sizeof kp);
-                kp.db = (const unsigned char*)db->d_db;
-                kp.items = db->d_items; kp.rank0 = l.rank0; kp.nranks = l.nranks;
-                kp.queries = c->d_mq + l.q0; kp.nq = (unsigned)l.nq; kp.nitems = l.items;
-                kp.prof = c->d_sprof; kp.ntargets = db->ntargets;
-                kp.ge = src.gap_extend; kp.goe = src.gap_open + src.gap_extend;
-                kp.bnd = l.bnd_per ? c->d_sbnd : nullptr; kp.bnd_per = l.bnd_per;
-                kp.counter = c->d_sctr;
-                kp.results = d_results;
-                HIP_TRY(hipMemsetAsync(c->d_sctr, 0, 4, stream));
-                hipLaunchKernelGGL(kSearchMultiPacked[l.kernel].k, dim3((unsigned)l.grid), dim3(256), 0, stream, kp);
-                HIP_TRY(hipGetLastError());
-                c->last_search_multi_grid = l.grid;
-                continue;
-            }
-            swk::SearchMultiParams sp;
-            memset(&sp, 0, sizeof sp);
-            sp.db = (const unsigned char*)db->d_db;
-            sp.items = db->d_items; sp.rank0 = l.rank0;
-            sp.queries = c->d_mq + l.q0; sp.nq = (unsigned)l.nq; sp.nitems = l.items;
-            sp.prof = c->d_sprof; sp.ntargets = db->ntargets;
-            sp.ge = src.gap_extend; sp.goe = src.gap_open + src.gap_extend;
-            sp.bnd = l.bnd_per ? c->d_sbnd : nullptr; sp.bnd_per = l.bnd_per;
-            sp.counter = c->d_sctr;
-            sp.results = d_results;
             HIP_TRY(hipMemsetAsync(c->d_sctr, 0, 4, stream));   // the work counter starts every launch at zero
-            hipLaunchKernelGGL(kSearchMulti[l.kernel].k, dim3((unsigned)l.grid), dim3(256), 0, stream, sp);
+            if (l.packed) {   // two targets per wave: the ranks rank0 .. rank0 + nranks - 1 in pairs
+                swk::SearchMultiPackedParams kp = search_multi_params<swk::SearchMultiPackedParams>(c, db, src, l, d_results);
+                kp.nranks = l.nranks;
+                hipLaunchKernelGGL(kSearchMultiPacked[l.kernel].k, dim3((unsigned)l.grid), dim3(256), 0, stream, kp);
+            } else {
+                const swk::SearchMultiParams sp = search_multi_params<swk::SearchMultiParams>(c, db, src, l, d_results);
+                hipLaunchKernelGGL(kSearchMulti[l.kernel].k, dim3((unsigned)l.grid), dim3(256), 0, stream, sp);
+            }
             HIP_TRY(hipGetLastError());
             c->last_search_multi_grid = l.grid;
         }
@@ -393,11 +401,10 @@ static int plan_top_call(sw_ctx* c, const char* who, int64_t nqueries, int64_t n
 
 // ... grown under the device's launch order; `rows`: the call keeps the result rows of a chunk in the context's workspace
 static int grow_top_workspaces(sw_ctx* c, const swp::SearchTopPlan& plan, bool rows, hipStream_t stream) {
-    bool fresh = false;
-    if (int rc = grow_workspace((void**)&c->d_thist, c->thist_cap, plan.hist_need, sizeof(unsigned int), 0, stream, fresh)) return rc;
-    if (int rc = grow_workspace((void**)&c->d_tstate, c->tstate_cap, plan.state_need, sizeof(swk::TopState), 0, stream, fresh)) return rc;
+    if (int rc = c->d_thist.grow(plan.hist_need, stream)) return rc;
+    if (int rc = c->d_tstate.grow(plan.state_need, stream)) return rc;
     if (rows)
-        if (int rc = grow_workspace((void**)&c->d_tres, c->tres_cap, plan.results_need, sizeof(sw_result), 0, stream, fresh)) return rc;
+        if (int rc = c->d_tres.grow(plan.results_need, stream)) return rc;
     return SW_OK;
 }
 
@@ -419,10 +426,9 @@ static int plan_top_pairs_call(sw_ctx* c, const char* who, int64_t npairs, int64
 
 // ... grown under the device's launch order
 static int grow_top_pairs_workspaces(sw_ctx* c, const swp::TopPairsPlan& plan, hipStream_t stream) {
-    bool fresh = false;
-    if (int rc = grow_workspace((void**)&c->d_tpkeys, c->tpkeys_cap, plan.keys_need, sizeof(unsigned long long), 0, stream, fresh)) return rc;
-    if (int rc = grow_workspace((void**)&c->d_tppos, c->tppos_cap, plan.pos_need, sizeof(unsigned int), 0, stream, fresh)) return rc;
-    if (int rc = grow_workspace((void**)&c->d_tpseg, c->tpseg_cap, plan.seg_need, sizeof(unsigned int), 0, stream, fresh)) return rc;
+    if (int rc = c->d_tpkeys.grow(plan.keys_need, stream)) return rc;
+    if (int rc = c->d_tppos.grow(plan.pos_need, stream)) return rc;
+    if (int rc = c->d_tpseg.grow(plan.seg_need, stream)) return rc;
     return SW_OK;
 }
 
@@ -445,13 +451,13 @@ int sw_search_device(sw_ctx* c, const char* d_query, int64_t qlen, const char* d
     // empty targets keep the zeros: {0, 0, 0}
     HIP_TRY(hipMemsetAsync(d_results, 0, (size_t)ntargets * sizeof(sw_result), stream));
     if (nonempty == 0) return SW_OK;
-    if (int rc = occupancy_once(kSearch, c->search_per_cu, c->search_per_cu_known)) return rc;
+    if (int rc = c->search_per_cu.once(kSearch)) return rc;
     swp::SearchJob sj;
     sj.qlen = qlen; sj.maxlen = maxlen; sj.ntargets = nonempty; sj.match = sc->match; sj.mismatch = sc->mismatch; sj.gap = sc->gap;
     const swp::SearchPlan plan = swp::plan_search(sj, device_facts(c));
     if (c->search_per_cu[plan.kernel] < 1) { set_err("the search kernel does not fit a CU on this device"); return SW_EDEVICE; }
     if (int rc = stage_search_call(c, stream, (size_t)nonempty, plan.prof_need, plan.bnd_need, false)) return rc;
-    swp::search_schedule(offsets, ntargets, c->h_sitems);
+    swp::search_schedule(offsets, ntargets, c->sitems.h);
     if (int rc = upload_search_call(c, stream, (size_t)nonempty, nullptr)) return rc;
     hipLaunchKernelGGL(swk::sw_search_profile, dim3((unsigned)plan.prof_blocks), dim3(256), 0, stream, (const unsigned char*)d_query, qlen, plan.qpad,
                        c->d_sprof, sc->match, sc->mismatch, plan.wide ? 1 : 0);
@@ -480,17 +486,17 @@ int sw_search_affine_device(sw_ctx* c, const char* d_query, int64_t qlen, const 
     // empty targets keep the zeros: {0, 0, 0}
     HIP_TRY(hipMemsetAsync(d_results, 0, (size_t)ntargets * sizeof(sw_result), stream));
     if (nonempty == 0) return SW_OK;
-    if (int rc = occupancy_once(kSearchAffine, c->search_affine_per_cu, c->search_affine_per_cu_known)) return rc;
+    if (int rc = c->search_affine_per_cu.once(kSearchAffine)) return rc;
     swp::SearchAffineJob sj;
     sj.qlen = qlen; sj.maxlen = maxlen; sj.ntargets = nonempty; sj.num_cus = c->num_cus;
     std::copy(std::begin(c->search_affine_per_cu), std::end(c->search_affine_per_cu), sj.per_cu);
     const swp::SearchAffinePlan plan = swp::plan_search_affine(sj);
     if (c->search_affine_per_cu[plan.kernel] < 1) { set_err("the affine search kernel does not fit a CU on this device"); return SW_EDEVICE; }
     if (int rc = stage_search_call(c, stream, (size_t)nonempty, plan.prof_need, plan.bnd_need, true)) return rc;
-    swp::search_schedule(offsets, ntargets, c->h_sitems);
+    swp::search_schedule(offsets, ntargets, c->sitems.h);
     if (int rc = upload_search_call(c, stream, (size_t)nonempty, scoring->sub)) return rc;
     hipLaunchKernelGGL(swk::sw_search_profile_submat, dim3((unsigned)plan.prof_blocks), dim3(256), 0, stream, (const unsigned char*)d_query, qlen,
-                       plan.qpad, c->d_sprof, (const signed char*)c->d_submat);
+                       plan.qpad, c->d_sprof, (const signed char*)c->submat.d);
     HIP_TRY(hipGetLastError());
     swk::SearchAffineParams sp = search_params<swk::SearchAffineParams>(c, d_db, nonempty, qlen, plan);
     sp.ge = scoring->gap_extend; sp.goe = scoring->gap_open + scoring->gap_extend;
@@ -501,45 +507,10 @@ int sw_search_affine_device(sw_ctx* c, const char* d_query, int64_t qlen, const 
     return SW_OK;
 }
 
-// sw_align_affine_device under "align_checkpoint" (csrc/sw_align_ckpt.hip): the caller has checked the arguments and taken the stream.
-static int align_affine_ckpt(sw_ctx* c, const char* d_query, int64_t qlen, const char* d_db, const int64_t* offsets, const int64_t* hits, int64_t nhits,
-                             int64_t maxhit, const sw_affine* scoring, sw_alignment* d_aln, char* d_ops, int64_t ops_cap, hipStream_t stream) {
-    if (int rc = occupancy_once(kAlignCkpt, c->align_ckpt_per_cu, c->align_ckpt_per_cu_known)) return rc;
-    swp::AlignCkptJob aj;
-    aj.qlen = qlen; aj.maxhit = maxhit; aj.nhits = nhits; aj.num_cus = c->num_cus; aj.budget_bytes = c->opt_align_workspace_mib << 20;
-    aj.band_rows = c->opt_align_checkpoint_rows;
-    std::copy(std::begin(c->align_ckpt_per_cu), std::end(c->align_ckpt_per_cu), aj.per_cu);
-    const swp::AlignCkptPlan plan = swp::plan_align_ckpt(aj);
-    if (!plan.fits) {
-        set_err("sw_align_affine_device: the checkpointed slot of the longest hit (%lld rows against %lld padded columns in bands of %lld rows = %lld bytes) "
-                "does not fit align_workspace_mib = %lld (or the 2 GiB a slot may take)", (long long)maxhit, (long long)plan.qpad, (long long)plan.band_rows,
-                (long long)plan.slot_bytes, (long long)c->opt_align_workspace_mib);
-        return SW_EINVAL;
-    }
-    if (c->align_ckpt_per_cu[plan.kernel] < 1) { set_err("the checkpointed alignment kernel does not fit a CU on this device"); return SW_EDEVICE; }
-    if (int rc = stage_search_call(c, stream, (size_t)nhits, plan.prof_need, plan.bnd_need, true)) return rc;
-    bool fresh = false;   // (the direction workspace: a band and its checkpoint rows per slot)
-    if (int rc = grow_workspace((void**)&c->d_adir, c->adir_cap, plan.dir_need, 1, 0, stream, fresh)) return rc;
-    swp::align_schedule(offsets, hits, nhits, c->h_sitems);
-    if (int rc = upload_search_call(c, stream, (size_t)nhits, scoring->sub)) return rc;
-    hipLaunchKernelGGL(swk::sw_search_profile_submat, dim3((unsigned)plan.prof_blocks), dim3(256), 0, stream, (const unsigned char*)d_query, qlen,
-                       plan.qpad, c->d_sprof, (const signed char*)c->d_submat);
-    HIP_TRY(hipGetLastError());
-    swk::AlignCkptParams ap = search_params<swk::AlignCkptParams>(c, d_db, nhits, qlen, plan);
-    ap.ge = scoring->gap_extend; ap.goe = scoring->gap_open + scoring->gap_extend;
-    ap.dir = c->d_adir; ap.slot_bytes = plan.slot_bytes; ap.nslots = plan.slots; ap.log_band = plan.log_band;
-    ap.aln = d_aln; ap.ops = d_ops; ap.ops_cap = ops_cap;
-    ap.stamps = (unsigned long long*)(uintptr_t)c->opt_dbg_ptr;
-    hipLaunchKernelGGL(kAlignCkpt[plan.kernel].k, dim3((unsigned)plan.grid), dim3(256), 0, stream, ap);
-    HIP_TRY(hipGetLastError());
-    c->last_align_affine_kernel = plan.kernel; c->last_align_affine_slots = plan.slots;
-    c->last_align_affine_checkpointed = 1; c->last_align_affine_band_rows = plan.band_rows; c->last_align_affine_slot_bytes = plan.slot_bytes;
-    return SW_OK;
-}
-
-// The alignment of chosen hits under affine scoring (csrc/sw_align_affine.hip).  The shape of sw_search_affine_device: no host round
-// trip, the order of the hits and the table are uploaded from pinned copies, the profile is built on the device; the plan decides.
-// "align_checkpoint" decides once, here, before any launch, whether the call runs on whole direction matrices or checkpointed.
+// The alignment of chosen hits under affine scoring (csrc/sw_align_affine.hip; checkpointed: csrc/sw_align_ckpt.hip).  The shape of
+// sw_search_affine_device: no host round trip, the order of the hits and the table are uploaded from pinned copies, the profile is built
+// on the device; the plan decides.  "align_checkpoint" decides once, here, before any launch, whether the call runs on whole direction
+// matrices or checkpointed.
 int sw_align_affine_device(sw_ctx* c, const char* d_query, int64_t qlen, const char* d_db, const int64_t* offsets, int64_t ntargets,
                            const int64_t* hits, int64_t nhits, const sw_affine* scoring, sw_alignment* d_aln, char* d_ops, int64_t ops_cap,
                            void* stream_) {
@@ -552,36 +523,54 @@ int sw_align_affine_device(sw_ctx* c, const char* d_query, int64_t qlen, const c
     HIP_TRY(hipSetDevice(c->device));
     DevOrder order(c, stream, false);
     if (order.rc) return order.rc;
-    if (int rc = occupancy_once(kAlignAffine, c->align_affine_per_cu, c->align_affine_per_cu_known)) return rc;
-    swp::AlignAffineJob aj;
+    if (int rc = c->align_affine_per_cu.once(kAlignAffine)) return rc;
+    swp::AlignCkptJob aj;
     aj.qlen = qlen; aj.maxhit = maxhit; aj.nhits = nhits; aj.num_cus = c->num_cus; aj.budget_bytes = c->opt_align_workspace_mib << 20;
+    aj.band_rows = c->opt_align_checkpoint_rows;
     std::copy(std::begin(c->align_affine_per_cu), std::end(c->align_affine_per_cu), aj.per_cu);
-    const swp::AlignAffinePlan plan = swp::plan_align_affine(aj);
+    swp::AlignCkptPlan plan;   // (band_rows and log_band stay 0 on whole matrices)
+    static_cast<swp::AlignAffinePlan&>(plan) = swp::plan_align_affine(aj);
     c->last_align_affine_checkpointed = c->last_align_affine_band_rows = 0;
-    if (swp::align_use_ckpt(c->opt_align_checkpoint, plan.fits))
-        return align_affine_ckpt(c, d_query, qlen, d_db, offsets, hits, nhits, maxhit, scoring, d_aln, d_ops, ops_cap, stream);
+    const bool ckpt = swp::align_use_ckpt(c->opt_align_checkpoint, plan.fits);
+    if (ckpt) {
+        if (int rc = c->align_ckpt_per_cu.once(kAlignCkpt)) return rc;
+        std::copy(std::begin(c->align_ckpt_per_cu), std::end(c->align_ckpt_per_cu), aj.per_cu);
+        plan = swp::plan_align_ckpt(aj);
+    }
+    if (!plan.fits && ckpt) {
+        set_err("sw_align_affine_device: the checkpointed slot of the longest hit (%lld rows against %lld padded columns in bands of %lld rows = %lld bytes) "
+                "does not fit align_workspace_mib = %lld (or the 2 GiB a slot may take)", (long long)maxhit, (long long)plan.qpad, (long long)plan.band_rows,
+                (long long)plan.slot_bytes, (long long)c->opt_align_workspace_mib);
+        return SW_EINVAL;
+    }
     if (!plan.fits) {
         set_err("sw_align_affine_device: the direction matrix of the longest hit (%lld rows x %lld bytes = %lld bytes) does not fit align_workspace_mib = %lld "
                 "(or the 2 GiB a slot may take)", (long long)maxhit, (long long)plan.qpad, (long long)plan.slot_bytes, (long long)c->opt_align_workspace_mib);
         return SW_EINVAL;
     }
-    if (c->align_affine_per_cu[plan.kernel] < 1) { set_err("the alignment kernel does not fit a CU on this device"); return SW_EDEVICE; }
+    if ((ckpt ? c->align_ckpt_per_cu : c->align_affine_per_cu)[plan.kernel] < 1) {
+        set_err("%s", ckpt ? "the checkpointed alignment kernel does not fit a CU on this device" : "the alignment kernel does not fit a CU on this device");
+        return SW_EDEVICE;
+    }
     if (int rc = stage_search_call(c, stream, (size_t)nhits, plan.prof_need, plan.bnd_need, true)) return rc;
-    bool fresh = false;   // (its own workspace: one direction matrix per slot)
-    if (int rc = grow_workspace((void**)&c->d_adir, c->adir_cap, plan.dir_need, 1, 0, stream, fresh)) return rc;
-    swp::align_schedule(offsets, hits, nhits, c->h_sitems);
+    // the direction workspace: per slot one direction matrix, or a band and its checkpoint rows
+    if (int rc = c->d_adir.grow(plan.dir_need, stream)) return rc;
+    swp::align_schedule(offsets, hits, nhits, c->sitems.h);
     if (int rc = upload_search_call(c, stream, (size_t)nhits, scoring->sub)) return rc;
     hipLaunchKernelGGL(swk::sw_search_profile_submat, dim3((unsigned)plan.prof_blocks), dim3(256), 0, stream, (const unsigned char*)d_query, qlen,
-                       plan.qpad, c->d_sprof, (const signed char*)c->d_submat);
+                       plan.qpad, c->d_sprof, (const signed char*)c->submat.d);
     HIP_TRY(hipGetLastError());
-    swk::AlignAffineParams ap = search_params<swk::AlignAffineParams>(c, d_db, nhits, qlen, plan);
-    ap.ge = scoring->gap_extend; ap.goe = scoring->gap_open + scoring->gap_extend;
-    ap.dir = c->d_adir; ap.slot_bytes = plan.slot_bytes; ap.nslots = plan.slots;
-    ap.aln = d_aln; ap.ops = d_ops; ap.ops_cap = ops_cap;
-    ap.stamps = (unsigned long long*)(uintptr_t)c->opt_dbg_ptr;
-    hipLaunchKernelGGL(kAlignAffine[plan.kernel].k, dim3((unsigned)plan.grid), dim3(256), 0, stream, ap);
+    if (ckpt) {
+        swk::AlignCkptParams ap = align_affine_params<swk::AlignCkptParams>(c, d_db, nhits, qlen, plan, scoring, d_aln, d_ops, ops_cap);
+        ap.log_band = plan.log_band;
+        hipLaunchKernelGGL(kAlignCkpt[plan.kernel].k, dim3((unsigned)plan.grid), dim3(256), 0, stream, ap);
+    } else {
+        const swk::AlignAffineParams ap = align_affine_params<swk::AlignAffineParams>(c, d_db, nhits, qlen, plan, scoring, d_aln, d_ops, ops_cap);
+        hipLaunchKernelGGL(kAlignAffine[plan.kernel].k, dim3((unsigned)plan.grid), dim3(256), 0, stream, ap);
+    }
     HIP_TRY(hipGetLastError());
     c->last_align_affine_kernel = plan.kernel; c->last_align_affine_slots = plan.slots; c->last_align_affine_slot_bytes = plan.slot_bytes;
+    c->last_align_affine_checkpointed = ckpt ? 1 : 0; c->last_align_affine_band_rows = plan.band_rows;
     return SW_OK;
 }
 
@@ -664,8 +653,7 @@ static int db_search_call(sw_ctx* c, const sw_db* db, const QuerySource& src, co
 // offsets are not looked at again and nothing is sorted.
 int sw_db_search_affine(sw_ctx* c, const sw_db* db, const char* d_queries, const int64_t* qoffsets, int64_t nqueries, const sw_affine* scoring,
                         sw_result* d_results, void* stream_) {
-    if (!c || !db || !d_queries || !qoffsets || !scoring || !d_results) { set_err("sw_db_search_affine: NULL pointer"); return SW_EINVAL; }
-    if (db->device != c->device) { set_err("sw_db_search_affine: the handle was created on device %d, the context runs on device %d", db->device, c->device); return SW_EINVAL; }
+    if (int rc = check_db_call("sw_db_search_affine", c, db, d_queries && qoffsets && scoring && d_results)) return rc;
     int64_t maxq = 0;
     if (int rc = swh::check_search_multi("sw_db_search_affine", qoffsets, nqueries, db->longest, scoring, &maxq)) return rc;
     return db_search_call(c, db, QuerySource::sequences(d_queries, scoring), qoffsets, nqueries, d_results, stream_);
@@ -674,8 +662,7 @@ int sw_db_search_affine(sw_ctx* c, const sw_db* db, const char* d_queries, const
 // The same search with a position-specific scoring matrix in place of letters and a table: only the source of the profiles differs.
 int sw_db_search_pssm(sw_ctx* c, const sw_db* db, const int8_t* d_pssm, const int64_t* qoffsets, int64_t nqueries, const sw_pssm_scoring* scoring,
                       sw_result* d_results, void* stream_) {
-    if (!c || !db || !d_pssm || !qoffsets || !scoring || !d_results) { set_err("sw_db_search_pssm: NULL pointer"); return SW_EINVAL; }
-    if (db->device != c->device) { set_err("sw_db_search_pssm: the handle was created on device %d, the context runs on device %d", db->device, c->device); return SW_EINVAL; }
+    if (int rc = check_db_call("sw_db_search_pssm", c, db, d_pssm && qoffsets && scoring && d_results)) return rc;
     int64_t maxq = 0;
     unsigned char code[256];
     if (int rc = swh::check_search_pssm("sw_db_search_pssm", qoffsets, nqueries, db->longest, scoring, &maxq, code)) return rc;
@@ -722,8 +709,7 @@ static int db_search_top_call(const char* who, sw_ctx* c, const sw_db* db, const
 
 int sw_db_search_affine_top(sw_ctx* c, const sw_db* db, const char* d_queries, const int64_t* qoffsets, int64_t nqueries, const sw_affine* scoring,
                             int64_t top, int64_t min_score, sw_hit* d_hits, int64_t* d_nhits, void* stream_) {
-    if (!c || !db || !d_queries || !qoffsets || !scoring) { set_err("sw_db_search_affine_top: NULL pointer"); return SW_EINVAL; }
-    if (db->device != c->device) { set_err("sw_db_search_affine_top: the handle was created on device %d, the context runs on device %d", db->device, c->device); return SW_EINVAL; }
+    if (int rc = check_db_call("sw_db_search_affine_top", c, db, d_queries && qoffsets && scoring)) return rc;
     int64_t maxq = 0;
     if (int rc = swh::check_search_multi("sw_db_search_affine_top", qoffsets, nqueries, db->longest, scoring, &maxq)) return rc;
     return db_search_top_call("sw_db_search_affine_top", c, db, QuerySource::sequences(d_queries, scoring), qoffsets, nqueries, top, min_score, d_hits, d_nhits,
@@ -732,8 +718,7 @@ int sw_db_search_affine_top(sw_ctx* c, const sw_db* db, const char* d_queries, c
 
 int sw_db_search_pssm_top(sw_ctx* c, const sw_db* db, const int8_t* d_pssm, const int64_t* qoffsets, int64_t nqueries, const sw_pssm_scoring* scoring,
                           int64_t top, int64_t min_score, sw_hit* d_hits, int64_t* d_nhits, void* stream_) {
-    if (!c || !db || !d_pssm || !qoffsets || !scoring) { set_err("sw_db_search_pssm_top: NULL pointer"); return SW_EINVAL; }
-    if (db->device != c->device) { set_err("sw_db_search_pssm_top: the handle was created on device %d, the context runs on device %d", db->device, c->device); return SW_EINVAL; }
+    if (int rc = check_db_call("sw_db_search_pssm_top", c, db, d_pssm && qoffsets && scoring)) return rc;
     int64_t maxq = 0;
     unsigned char code[256];
     if (int rc = swh::check_search_pssm("sw_db_search_pssm_top", qoffsets, nqueries, db->longest, scoring, &maxq, code)) return rc;
@@ -753,7 +738,7 @@ static int db_align_hits_call(const char* who, sw_ctx* c, const sw_db* db, const
     if (nqueries == 0) return SW_OK;
     hipStream_t stream = (hipStream_t)stream_;
     HIP_TRY(hipSetDevice(c->device));
-    if (int rc = occupancy_once(kAlignHits, c->align_hits_per_cu, c->align_hits_per_cu_known)) return rc;
+    if (int rc = c->align_hits_per_cu.once(kAlignHits)) return rc;
     const std::vector<int64_t> qlens = query_lengths(qoffsets, nqueries);
     swp::AlignHitsJob aj;
     aj.qlens = qlens.data(); aj.nqueries = nqueries; aj.top = top; aj.longest = db->longest; aj.num_cus = c->num_cus;
@@ -763,7 +748,7 @@ static int db_align_hits_call(const char* who, sw_ctx* c, const sw_db* db, const
     // "align_checkpoint": decided once, from host data alone, before any launch
     const bool ckpt = swp::align_use_ckpt(c->opt_align_checkpoint, plan.fits);
     if (ckpt) {
-        if (int rc = occupancy_once(kAlignHitsCkpt, c->align_hits_ckpt_per_cu, c->align_hits_ckpt_per_cu_known)) return rc;
+        if (int rc = c->align_hits_ckpt_per_cu.once(kAlignHitsCkpt)) return rc;
         swp::AlignHitsCkptJob cj;
         static_cast<swp::AlignHitsJob&>(cj) = aj;
         std::copy(std::begin(c->align_hits_ckpt_per_cu), std::end(c->align_hits_ckpt_per_cu), cj.per_cu);
@@ -790,11 +775,10 @@ static int db_align_hits_call(const char* who, sw_ctx* c, const sw_db* db, const
     for (const swp::AlignHitsLaunch& l : plan.launch)
         if ((ckpt ? c->align_hits_ckpt_per_cu : c->align_hits_per_cu)[l.kernel] < 1) { set_err("the hit-table alignment kernel does not fit a CU on this device"); return SW_EDEVICE; }
     if (int rc = stage_search_call(c, stream, 0, plan.prof_need, plan.bnd_need, true)) return rc;
-    bool fresh = false;
-    if (int rc = grow_workspace((void**)&c->d_adir, c->adir_cap, plan.dir_need, 1, 0, stream, fresh)) return rc;
-    if (int rc = grow_workspace((void**)&c->d_ahitems, c->ahitems_cap, plan.items_need, sizeof(swk::AlignHitItem), 0, stream, fresh)) return rc;
-    if (!c->d_ahctl) HIP_TRY(hipMalloc((void**)&c->d_ahctl, sizeof(swk::AlignHitsCtl)));
-    if (!c->d_ahfilled) HIP_TRY(hipMalloc((void**)&c->d_ahfilled, 64));
+    if (int rc = c->d_adir.grow(plan.dir_need, stream)) return rc;
+    if (int rc = c->d_ahitems.grow(plan.items_need, stream)) return rc;
+    if (int rc = c->d_ahctl.once(sizeof(swk::AlignHitsCtl))) return rc;
+    if (int rc = c->d_ahfilled.once(64)) return rc;
     HIP_TRY(hipMemsetAsync(c->d_ahfilled, 0, 4, stream));
     if (int rc = upload_query_table(c, stream, plan.table, qoffsets, src)) return rc;
     size_t li = 0;
@@ -807,7 +791,7 @@ static int db_align_hits_call(const char* who, sw_ctx* c, const sw_db* db, const
         memset(&bp, 0, sizeof bp);
         bp.hits = d_hits; bp.nhits = d_nhits; bp.top = top;
         bp.offsets = db->d_offsets; bp.ntargets = db->ntargets;
-        bp.queries = c->d_mq + grp.q0; bp.nq = grp.nq;
+        bp.queries = c->mq.d + grp.q0; bp.nq = grp.nq;
         for (int k = 0; k < swp::kAlignHitsKernels; ++k) {
             bp.cls_q0[k] = grp.cls[k].q0 - grp.q0;
             bp.ntiers[k] = grp.cls[k].ntiers;
@@ -824,35 +808,15 @@ static int db_align_hits_call(const char* who, sw_ctx* c, const sw_db* db, const
         for (; li < plan.launch.size() && plan.launch[li].group == (int)g; ++li) {
             const swp::AlignHitsLaunch& l = plan.launch[li];
             if (ckpt) {
-                swk::AlignHitsCkptParams kp;
-                memset(&kp, 0, sizeof kp);
-                kp.db = (const unsigned char*)db->d_db;
-                kp.items = c->d_ahitems + grp.cls[l.kernel].item0;
-                kp.counts = c->d_ahctl->count[l.kernel]; kp.tier = l.tier;
-                kp.queries = c->d_mq + grp.q0; kp.prof = c->d_sprof;
-                kp.ge = src.gap_extend; kp.goe = src.gap_open + src.gap_extend;
-                kp.bnd = l.bnd_per ? c->d_sbnd : nullptr; kp.bnd_per = l.bnd_per;
-                kp.counter = &c->d_ahctl->work[l.kernel][l.tier];
-                kp.dir = c->d_adir; kp.slot_bytes = l.slot_bytes; kp.nslots = l.slots; kp.log_band = l.log_band;
-                kp.aln = d_aln; kp.ops = d_ops; kp.ops_cap = ops_cap;
+                swk::AlignHitsCkptParams kp = align_hits_params<swk::AlignHitsCkptParams>(c, db, src, grp, l, d_aln, d_ops, ops_cap);
+                kp.log_band = l.log_band;
                 hipLaunchKernelGGL(kAlignHitsCkpt[l.kernel].k, dim3((unsigned)l.grid), dim3(256), 0, stream, kp);
-                HIP_TRY(hipGetLastError());
-                c->last_align_hits_band_rows = std::max<int64_t>(c->last_align_hits_band_rows, 1ll << l.log_band);
-                continue;
+            } else {
+                const swk::AlignHitsParams ap = align_hits_params<swk::AlignHitsParams>(c, db, src, grp, l, d_aln, d_ops, ops_cap);
+                hipLaunchKernelGGL(kAlignHits[l.kernel].k, dim3((unsigned)l.grid), dim3(256), 0, stream, ap);
             }
-            swk::AlignHitsParams ap;
-            memset(&ap, 0, sizeof ap);
-            ap.db = (const unsigned char*)db->d_db;
-            ap.items = c->d_ahitems + grp.cls[l.kernel].item0;
-            ap.counts = c->d_ahctl->count[l.kernel]; ap.tier = l.tier;
-            ap.queries = c->d_mq + grp.q0; ap.prof = c->d_sprof;
-            ap.ge = src.gap_extend; ap.goe = src.gap_open + src.gap_extend;
-            ap.bnd = l.bnd_per ? c->d_sbnd : nullptr; ap.bnd_per = l.bnd_per;
-            ap.counter = &c->d_ahctl->work[l.kernel][l.tier];
-            ap.dir = c->d_adir; ap.slot_bytes = l.slot_bytes; ap.nslots = l.slots;
-            ap.aln = d_aln; ap.ops = d_ops; ap.ops_cap = ops_cap;
-            hipLaunchKernelGGL(kAlignHits[l.kernel].k, dim3((unsigned)l.grid), dim3(256), 0, stream, ap);
             HIP_TRY(hipGetLastError());
+            if (ckpt) c->last_align_hits_band_rows = std::max<int64_t>(c->last_align_hits_band_rows, 1ll << l.log_band);
         }
     }
     c->last_align_hits_launches = (int64_t)(3 * plan.group.size() + plan.launch.size()); c->last_align_hits_tiers = plan.tiers; c->last_align_hits_slots = plan.slots;
@@ -862,8 +826,7 @@ static int db_align_hits_call(const char* who, sw_ctx* c, const sw_db* db, const
 
 int sw_db_align_affine_hits(sw_ctx* c, const sw_db* db, const char* d_queries, const int64_t* qoffsets, int64_t nqueries, const sw_affine* scoring,
                             const sw_hit* d_hits, const int64_t* d_nhits, int64_t top, sw_alignment* d_aln, char* d_ops, int64_t ops_cap, void* stream_) {
-    if (!c || !db || !d_queries || !qoffsets || !scoring) { set_err("sw_db_align_affine_hits: NULL pointer"); return SW_EINVAL; }
-    if (db->device != c->device) { set_err("sw_db_align_affine_hits: the handle was created on device %d, the context runs on device %d", db->device, c->device); return SW_EINVAL; }
+    if (int rc = check_db_call("sw_db_align_affine_hits", c, db, d_queries && qoffsets && scoring)) return rc;
     int64_t maxq = 0;
     if (int rc = swh::check_search_multi("sw_db_align_affine_hits", qoffsets, nqueries, db->longest, scoring, &maxq)) return rc;
     return db_align_hits_call("sw_db_align_affine_hits", c, db, QuerySource::sequences(d_queries, scoring), qoffsets, nqueries, d_hits, d_nhits, top, d_aln, d_ops,
@@ -872,8 +835,7 @@ int sw_db_align_affine_hits(sw_ctx* c, const sw_db* db, const char* d_queries, c
 
 int sw_db_align_pssm_hits(sw_ctx* c, const sw_db* db, const int8_t* d_pssm, const int64_t* qoffsets, int64_t nqueries, const sw_pssm_scoring* scoring,
                           const sw_hit* d_hits, const int64_t* d_nhits, int64_t top, sw_alignment* d_aln, char* d_ops, int64_t ops_cap, void* stream_) {
-    if (!c || !db || !d_pssm || !qoffsets || !scoring) { set_err("sw_db_align_pssm_hits: NULL pointer"); return SW_EINVAL; }
-    if (db->device != c->device) { set_err("sw_db_align_pssm_hits: the handle was created on device %d, the context runs on device %d", db->device, c->device); return SW_EINVAL; }
+    if (int rc = check_db_call("sw_db_align_pssm_hits", c, db, d_pssm && qoffsets && scoring)) return rc;
     int64_t maxq = 0;
     unsigned char code[256];
     if (int rc = swh::check_search_pssm("sw_db_align_pssm_hits", qoffsets, nqueries, db->longest, scoring, &maxq, code)) return rc;
@@ -889,8 +851,7 @@ int sw_db_pssm_from_hits(sw_ctx* c, const sw_db* db, const int8_t* d_prior, cons
                          const sw_pssm_update* upd, const sw_hit* d_hits, const int64_t* d_nhits, int64_t top, const sw_alignment* d_aln, const char* d_ops,
                          int64_t ops_cap, const int32_t* d_weights, int8_t* d_pssm_out, int32_t* d_counts, void* stream_) {
     const char* who = "sw_db_pssm_from_hits";
-    if (!c || !db || !d_prior || !qoffsets || !scoring) { set_err("%s: NULL pointer", who); return SW_EINVAL; }
-    if (db->device != c->device) { set_err("%s: the handle was created on device %d, the context runs on device %d", who, db->device, c->device); return SW_EINVAL; }
+    if (int rc = check_db_call(who, c, db, d_prior && qoffsets && scoring)) return rc;
     int64_t maxq = 0;
     unsigned char code[256];
     if (int rc = swh::check_search_pssm(who, qoffsets, nqueries, db->longest, scoring, &maxq, code)) return rc;
@@ -913,21 +874,21 @@ int sw_db_pssm_from_hits(sw_ctx* c, const sw_db* db, const int8_t* d_prior, cons
     c->phtab_turn ^= 1;
     if (c->phtab_ev[turn]) HIP_TRY(hipEventSynchronize(c->phtab_ev[turn]));
     else HIP_TRY(hipEventCreateWithFlags(&c->phtab_ev[turn], hipEventDisableTiming));
-    if (need > c->phtab_cap) {
+    if (need > c->d_phtab.cap) {
         HIP_TRY(hipStreamSynchronize(stream));                   // launches in flight may still read the old table
         if (c->phtab_ev[turn ^ 1]) HIP_TRY(hipEventSynchronize(c->phtab_ev[turn ^ 1]));   // ... and an upload the other copy
         if (c->d_phtab) HIP_TRY(hipFree(c->d_phtab));
-        c->d_phtab = nullptr; c->phtab_cap = 0;
+        c->d_phtab.p = nullptr; c->d_phtab.cap = 0;
         for (int i = 0; i < 2; ++i) {
             if (c->h_phtab[i]) HIP_TRY(hipHostFree(c->h_phtab[i]));
             c->h_phtab[i] = nullptr;
         }
-        if (hipMalloc((void**)&c->d_phtab, need) != hipSuccess || hipHostMalloc((void**)&c->h_phtab[0], need, 0) != hipSuccess ||
+        if (hipMalloc((void**)&c->d_phtab.p, need) != hipSuccess || hipHostMalloc((void**)&c->h_phtab[0], need, 0) != hipSuccess ||
             hipHostMalloc((void**)&c->h_phtab[1], need, 0) != hipSuccess) {
             set_err("%s: workspace allocation of %zu bytes failed", who, need);
             return SW_ENOMEM;
         }
-        c->phtab_cap = need;
+        c->d_phtab.cap = need;
     }
     unsigned char* h_tab = c->h_phtab[turn];
     swh::pssm_update_table(upd->sub, scoring->letters, n, (int8_t*)h_tab);
@@ -938,7 +899,7 @@ int sw_db_pssm_from_hits(sw_ctx* c, const sw_db* db, const int8_t* d_prior, cons
     swk::PssmHitsParams kp;
     memset(&kp, 0, sizeof kp);
     kp.prior = (const signed char*)d_prior; kp.out = (signed char*)d_pssm_out; kp.counts = d_counts;
-    kp.S = (const signed char*)c->d_phtab; kp.code = c->d_phtab + s_bytes; kp.qoffs = (const int64_t*)(c->d_phtab + s_bytes + 256);
+    kp.S = (const signed char*)c->d_phtab.p; kp.code = c->d_phtab + s_bytes; kp.qoffs = (const int64_t*)(c->d_phtab + s_bytes + 256);
     kp.db = (const unsigned char*)db->d_db; kp.offsets = db->d_offsets; kp.ntargets = db->ntargets;
     kp.hits = d_hits; kp.nhits = d_nhits; kp.top = top;
     kp.aln = d_aln; kp.ops = d_ops; kp.ops_cap = ops_cap; kp.weights = d_weights;
@@ -959,8 +920,7 @@ int sw_db_pssm_from_hits(sw_ctx* c, const sw_db* db, const int8_t* d_prior, cons
 // and a class a packed score launch ahead of the 32-bit one; under 32 the plan, and so every launch, is swp::plan_search_pairs's.
 int sw_db_search_affine_pairs(sw_ctx* c, const sw_db* db, const char* d_queries, const int64_t* qoffsets, int64_t nqueries, const sw_affine* scoring,
                               const sw_pair* d_pairs, int64_t npairs, sw_result* d_results, void* stream_) {
-    if (!c || !db || !d_queries || !qoffsets || !scoring) { set_err("sw_db_search_affine_pairs: NULL pointer"); return SW_EINVAL; }
-    if (db->device != c->device) { set_err("sw_db_search_affine_pairs: the handle was created on device %d, the context runs on device %d", db->device, c->device); return SW_EINVAL; }
+    if (int rc = check_db_call("sw_db_search_affine_pairs", c, db, d_queries && qoffsets && scoring)) return rc;
     int64_t maxq = 0;
     if (int rc = swh::check_search_multi("sw_db_search_affine_pairs", qoffsets, nqueries, db->longest, scoring, &maxq)) return rc;
     if (npairs < 0) { set_err("sw_db_search_affine_pairs: negative pair count"); return SW_EINVAL; }
@@ -975,10 +935,10 @@ int sw_db_search_affine_pairs(sw_ctx* c, const sw_db* db, const char* d_queries,
     // every entry that names no query, no target or an empty target keeps these zeros: {0, 0, 0}
     HIP_TRY(hipMemsetAsync(d_results, 0, (size_t)npairs * sizeof(sw_result), stream));
     if (nqueries == 0 || db->nonempty == 0) return SW_OK;
-    if (int rc = occupancy_once(kSearchPairs, c->search_pairs_per_cu, c->search_pairs_per_cu_known)) return rc;
+    if (int rc = c->search_pairs_per_cu.once(kSearchPairs)) return rc;
     const bool lanes16 = c->opt_search_pairs_lanes == 16;
     if (lanes16)
-        if (int rc = occupancy_once(kSearchPairsPacked, c->search_pairs_packed_per_cu, c->search_pairs_packed_per_cu_known)) return rc;
+        if (int rc = c->search_pairs_packed_per_cu.once(kSearchPairsPacked)) return rc;
     const QuerySource src = QuerySource::sequences(d_queries, scoring);
     const std::vector<int64_t> qlens = query_lengths(qoffsets, nqueries);
     swp::SearchPairsLanesJob pj;
@@ -994,12 +954,11 @@ int sw_db_search_affine_pairs(sw_ctx* c, const sw_db* db, const char* d_queries,
     for (const swp::PairsLanesLaunch& l : plan.launch)
         if ((l.packed ? c->search_pairs_packed_per_cu : c->search_pairs_per_cu)[l.kernel] < 1) { set_err("the pair-list search kernel does not fit a CU on this device"); return SW_EDEVICE; }
     if (int rc = stage_search_call(c, stream, 0, plan.prof_need, plan.bnd_need, true)) return rc;
-    bool fresh = false;
-    if (int rc = grow_workspace((void**)&c->d_spitems, c->spitems_cap, plan.items_need, 1, 0, stream, fresh)) return rc;
-    if (!c->d_spctl) HIP_TRY(hipMalloc((void**)&c->d_spctl, sizeof(swk::SearchPairsCtl)));
+    if (int rc = c->d_spitems.grow(plan.items_need, stream)) return rc;
+    if (int rc = c->d_spctl.once(sizeof(swk::SearchPairsCtl))) return rc;
     if (plan.cells_need) {   // the cells of the packed queries and the call's count of two-pair items, which starts at zero
-        if (int rc = grow_workspace((void**)&c->d_spcells, c->spcells_cap, plan.cells_need, 1, 0, stream, fresh)) return rc;
-        if (!c->d_sptotal) HIP_TRY(hipMalloc((void**)&c->d_sptotal, sizeof(unsigned long long)));
+        if (int rc = c->d_spcells.grow(plan.cells_need, stream)) return rc;
+        if (int rc = c->d_sptotal.once(sizeof(unsigned long long))) return rc;
         HIP_TRY(hipMemsetAsync(c->d_sptotal, 0, sizeof(unsigned long long), stream));
     }
     // behind the table's nqueries entries: entry_of (4 bytes per query)
@@ -1018,12 +977,12 @@ int sw_db_search_affine_pairs(sw_ctx* c, const sw_db* db, const char* d_queries,
             memset(&bp, 0, sizeof bp);
             bp.pairs = d_pairs; bp.p0 = plan.chunk_p0(ch); bp.np = np;
             bp.offsets = db->d_offsets; bp.ntargets = db->ntargets;
-            bp.queries = c->d_mq; bp.entry_of = (const int32_t*)(c->d_mq + nqueries); bp.nqueries = nqueries;
+            bp.queries = c->mq.d; bp.entry_of = (const int32_t*)(c->mq.d + nqueries); bp.nqueries = nqueries;
             std::copy(std::begin(grp.cls_q0), std::end(grp.cls_q0), bp.cls_q0);
             bp.ctl = c->d_spctl; bp.items = c->d_spitems;
             const unsigned bin_blocks = (unsigned)std::clamp<int64_t>((np + 255) / 256, 1, 4096);
             if (grp.cells) {   // a group with packed queries: count, scan, scatter (sw_search_pairs16.hip)
-                swk::SearchPairsPackedCtl* const pk = (swk::SearchPairsPackedCtl*)c->d_spcells;
+                swk::SearchPairsPackedCtl* const pk = (swk::SearchPairsPackedCtl*)c->d_spcells.p;
                 // its control words, counts and cursors start at zero; the scan writes every base
                 HIP_TRY(hipMemsetAsync(c->d_spcells, 0, (size_t)(swp::kSearchPairsCellsHead + 8 * grp.cells), stream));
                 swk::SearchPairsPackedBinParams kp;
@@ -1047,30 +1006,17 @@ int sw_db_search_affine_pairs(sw_ctx* c, const sw_db* db, const char* d_queries,
                 const swp::PairsLanesLaunch& l = plan.launch[li];
                 const unsigned grid = (unsigned)swp::search_pairs_lanes_grid(l, np, grp.cells);
                 if (l.packed) {   // two pairs of a query per wave: the class's two-pair items at the head of the item buffer
-                    swk::SearchPairsPackedCtl* const pk = (swk::SearchPairsPackedCtl*)c->d_spcells;
-                    swk::SearchPairsPackedParams kp;
-                    memset(&kp, 0, sizeof kp);
-                    kp.db = (const unsigned char*)db->d_db;
-                    kp.items = (const swk::SearchPairItem2*)c->d_spitems; kp.list = &pk->list[l.kernel];
-                    kp.queries = c->d_mq; kp.prof = c->d_sprof;
-                    kp.ge = scoring->gap_extend; kp.goe = scoring->gap_open + scoring->gap_extend;
-                    kp.bnd = l.bnd_per ? c->d_sbnd : nullptr; kp.bnd_per = l.bnd_per;
+                    swk::SearchPairsPackedCtl* const pk = (swk::SearchPairsPackedCtl*)c->d_spcells.p;
+                    swk::SearchPairsPackedParams kp = search_pairs_params<swk::SearchPairsPackedParams>(c, db, scoring, l, d_results);
+                    kp.items = (const swk::SearchPairItem2*)c->d_spitems.p; kp.list = &pk->list[l.kernel];
                     kp.counter = &pk->work[l.kernel];
-                    kp.results = d_results;
                     hipLaunchKernelGGL(kSearchPairsPacked[l.kernel].k, dim3(grid), dim3(256), 0, stream, kp);
-                    HIP_TRY(hipGetLastError());
-                    continue;
+                } else {
+                    swk::SearchPairsParams sp = search_pairs_params<swk::SearchPairsParams>(c, db, scoring, l, d_results);
+                    sp.items = c->d_spitems; sp.list = &c->d_spctl->list[l.kernel];
+                    sp.counter = &c->d_spctl->work[l.kernel];
+                    hipLaunchKernelGGL(kSearchPairs[l.kernel].k, dim3(grid), dim3(256), 0, stream, sp);
                 }
-                swk::SearchPairsParams sp;
-                memset(&sp, 0, sizeof sp);
-                sp.db = (const unsigned char*)db->d_db;
-                sp.items = c->d_spitems; sp.list = &c->d_spctl->list[l.kernel];
-                sp.queries = c->d_mq; sp.prof = c->d_sprof;
-                sp.ge = scoring->gap_extend; sp.goe = scoring->gap_open + scoring->gap_extend;
-                sp.bnd = l.bnd_per ? c->d_sbnd : nullptr; sp.bnd_per = l.bnd_per;
-                sp.counter = &c->d_spctl->work[l.kernel];
-                sp.results = d_results;
-                hipLaunchKernelGGL(kSearchPairs[l.kernel].k, dim3(grid), dim3(256), 0, stream, sp);
                 HIP_TRY(hipGetLastError());
             }
         }
@@ -1088,8 +1034,7 @@ int sw_db_search_affine_pairs(sw_ctx* c, const sw_db* db, const char* d_queries,
 int sw_db_prefilter_ungapped(sw_ctx* c, const sw_db* db, const char* d_queries, const int64_t* qoffsets, int64_t nqueries, const sw_submat* sub,
                              int64_t min_score, sw_pair* d_pairs, int64_t pairs_cap, int64_t* d_npairs, int32_t* d_scores, void* stream_) {
     const char* who = "sw_db_prefilter_ungapped";
-    if (!c || !db || !d_queries || !qoffsets || !sub) { set_err("%s: NULL pointer", who); return SW_EINVAL; }
-    if (db->device != c->device) { set_err("%s: the handle was created on device %d, the context runs on device %d", who, db->device, c->device); return SW_EINVAL; }
+    if (int rc = check_db_call(who, c, db, d_queries && qoffsets && sub)) return rc;
     int64_t maxq = 0;
     const sw_affine scoring = {sub, 0, 0};
     if (int rc = swh::check_search_multi(who, qoffsets, nqueries, db->longest, &scoring, &maxq)) return rc;
@@ -1106,20 +1051,21 @@ int sw_db_prefilter_ungapped(sw_ctx* c, const sw_db* db, const char* d_queries, 
         if (d_npairs) HIP_TRY(hipMemsetAsync(d_npairs, 0, sizeof(int64_t), stream));
         return SW_OK;
     }
-    if (int rc = occupancy_once(kPrefilter, c->prefilter_per_cu, c->prefilter_per_cu_known)) return rc;
+    if (int rc = c->prefilter_per_cu.once(kPrefilter)) return rc;
     const std::vector<int64_t> qlens = query_lengths(qoffsets, nqueries);
     swp::PrefilterJob pj;
     pj.qlens = qlens.data(); pj.nqueries = nqueries; pj.longest = db->longest; pj.nonempty = db->nonempty; pj.num_cus = c->num_cus;
     pj.budget_bytes = c->opt_search_profile_mib << 20; pj.lanes = (int)c->opt_prefilter_lanes;
-    for (int x = 0; x < 256; ++x)
-        for (int y = 0; y < 256; ++y) pj.max_entry = std::max<int>(pj.max_entry, sub->s[x][y]);
+    // (of a table without a positive entry max_entry() is that entry where this call used to plan with 0: swp::prefilter_packed clamps a
+    // negative value to 0, so the plan is the same)
+    const QuerySource src = QuerySource::sequences(d_queries, &scoring);
+    pj.max_entry = src.max_entry();
     std::copy(std::begin(c->prefilter_per_cu), std::end(c->prefilter_per_cu), pj.per_cu);
     const swp::PrefilterPlan plan = swp::plan_prefilter(pj);
     for (const swp::PrefilterLaunch& l : plan.launch)
         if (c->prefilter_per_cu[l.kernel] < 1) { set_err("the pre-filter kernel does not fit a CU on this device"); return SW_EDEVICE; }
     if (int rc = stage_search_call(c, stream, 0, plan.prof_need, plan.bnd_need, true)) return rc;
-    if (!c->d_pfctl) HIP_TRY(hipMalloc((void**)&c->d_pfctl, sizeof(swk::PrefilterCtl)));
-    const QuerySource src = QuerySource::sequences(d_queries, &scoring);
+    if (int rc = c->d_pfctl.once(sizeof(swk::PrefilterCtl))) return rc;
     if (int rc = upload_query_table(c, stream, plan.table, qoffsets, src)) return rc;
     hipLaunchKernelGGL(swk::sw_prefilter_commit, dim3(1), dim3(64), 0, stream, c->d_pfctl, d_npairs, 1);
     HIP_TRY(hipGetLastError());
@@ -1128,13 +1074,8 @@ int sw_db_prefilter_ungapped(sw_ctx* c, const sw_db* db, const char* d_queries, 
         if (int rc = launch_group_profiles(c, stream, src, plan.group[g])) return rc;
         for (; li < plan.launch.size() && plan.launch[li].group == (int)g; ++li) {
             const swp::PrefilterLaunch& l = plan.launch[li];
-            swk::PrefilterParams pp;
-            memset(&pp, 0, sizeof pp);
-            pp.db = (const unsigned char*)db->d_db;
-            pp.items = db->d_items; pp.rank0 = l.rank0; pp.nranks = l.nranks;
-            pp.queries = c->d_mq + l.q0; pp.nq = (unsigned)l.nq; pp.nitems = l.items;
-            pp.prof = c->d_sprof; pp.ntargets = db->ntargets;
-            pp.bnd = l.bnd_per ? c->d_sbnd : nullptr; pp.bnd_per = l.bnd_per;
+            swk::PrefilterParams pp = rank_launch_params<swk::PrefilterParams>(c, db, l);
+            pp.nranks = l.nranks;
             pp.ctl = c->d_pfctl;
             pp.min_score = (int)std::min<int64_t>(min_score, INT32_MAX);
             pp.pairs = d_pairs; pp.pairs_cap = pairs_cap;
@@ -1198,8 +1139,7 @@ int sw_db_search_affine_top_prefiltered(sw_ctx* c, const sw_db* db, const char* 
                                         int64_t prefilter_min_score, int64_t pairs_cap, int64_t top, int64_t min_score, sw_hit* d_hits, int64_t* d_nhits,
                                         int64_t* d_npairs, void* stream_) {
     const char* who = "sw_db_search_affine_top_prefiltered";
-    if (!c || !db || !d_queries || !qoffsets || !scoring) { set_err("%s: NULL pointer", who); return SW_EINVAL; }
-    if (db->device != c->device) { set_err("%s: the handle was created on device %d, the context runs on device %d", who, db->device, c->device); return SW_EINVAL; }
+    if (int rc = check_db_call(who, c, db, d_queries && qoffsets && scoring)) return rc;
     int64_t maxq = 0;
     if (int rc = swh::check_search_multi(who, qoffsets, nqueries, db->longest, scoring, &maxq)) return rc;
     if (prefilter_min_score < 1) { set_err("%s: prefilter_min_score = %lld, a pair passes from 1 on", who, (long long)prefilter_min_score); return SW_EINVAL; }
@@ -1217,12 +1157,11 @@ int sw_db_search_affine_top_prefiltered(sw_ctx* c, const sw_db* db, const char* 
     {
         DevOrder order(c, stream, false);
         if (order.rc) return order.rc;
-        bool fresh = false;
-        if (int rc = grow_workspace((void**)&c->d_tplist, c->tplist_cap, (size_t)pairs_cap, sizeof(sw_pair) + sizeof(sw_result), 0, stream, fresh)) return rc;
+        if (int rc = c->d_tplist.grow((size_t)pairs_cap, stream)) return rc;
         if (nqueries > 0)
             if (int rc = grow_top_pairs_workspaces(c, plan, stream)) return rc;
     }
-    sw_pair* d_pairs = pairs_cap > 0 ? (sw_pair*)c->d_tplist : nullptr;
+    sw_pair* d_pairs = pairs_cap > 0 ? (sw_pair*)c->d_tplist.p : nullptr;
     sw_result* d_results = pairs_cap > 0 ? (sw_result*)(c->d_tplist + (size_t)pairs_cap * sizeof(sw_pair)) : nullptr;
     if (int rc = sw_db_prefilter_ungapped(c, db, d_queries, qoffsets, nqueries, scoring->sub, prefilter_min_score, d_pairs, pairs_cap, d_npairs, nullptr, stream_)) return rc;
     if (int rc = sw_db_search_affine_pairs(c, db, d_queries, qoffsets, nqueries, scoring, d_pairs, pairs_cap, d_results, stream_)) return rc;

@@ -60,26 +60,105 @@ struct DevState {
 };
 extern SW_HIDDEN DevState g_dev[64];   // sw_api.hip
 
+// A launch table: every instantiation beside the index the planner gives it, checked at compile time to sit at that index.
+template <typename K> struct Indexed { int index; K k; };
+template <typename K, size_t N> constexpr bool at_their_indices(const Indexed<K> (&t)[N]) {
+    for (size_t i = 0; i < N; ++i)
+        if (t[i].index != (int)i) return false;
+    return true;
+}
+
+// The occupancy of every instantiation of a launch table at 256 threads (workgroups per CU), asked once per context: the plans' columns
+// per lane and grids depend on it.  once() is the one way in; the jobs and device_facts read it like the plain array it stands for.
+template <size_t N> class Occupancy {
+    int per_cu[N] = {};
+    bool known = false;
+public:
+    template <typename K> int once(const Indexed<K> (&tab)[N]) {
+        if (known) return SW_OK;
+        for (size_t k = 0; k < N; ++k) HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu[k], tab[k].k, 256, 0));
+        known = true;
+        return SW_OK;
+    }
+    int operator[](size_t k) const { return per_cu[k]; }
+    const int* begin() const { return per_cu; }
+    const int* end() const { return per_cu + N; }
+};
+
+// A device buffer of the context, freed with it; reads like the pointer it holds.  grow: to `need` elements of Elem bytes (+ `slack`
+// bytes) -- waits for the stream (launches in flight may still read the old one), frees it and allocates afresh; `fresh` says whether
+// the last grow did: the caller wipes what must start zeroed.  once: a buffer of fixed size, allocated at its first use.
+template <typename T, size_t Elem = sizeof(T)> struct Workspace {
+    T* p = nullptr;
+    size_t cap = 0;      // elements
+    bool fresh = false;
+    Workspace() = default;
+    Workspace(const Workspace&) = delete;
+    Workspace& operator=(const Workspace&) = delete;
+    ~Workspace() { if (p) (void)hipFree(p); }
+    operator T*() const { return p; }
+    T* operator->() const { return p; }
+    int grow(size_t need, hipStream_t stream, size_t slack = 0) {
+        fresh = false;
+        if (need <= cap) return SW_OK;
+        HIP_TRY(hipStreamSynchronize(stream));
+        if (p) HIP_TRY(hipFree(p));
+        p = nullptr; cap = 0;
+        const size_t bytes = need * Elem + slack;
+        if (hipMalloc((void**)&p, bytes) != hipSuccess) { set_err("workspace allocation of %zu bytes failed", bytes); return SW_ENOMEM; }
+        cap = need; fresh = true;
+        return SW_OK;
+    }
+    int once(size_t bytes) { if (!p) HIP_TRY(hipMalloc((void**)&p, bytes)); return SW_OK; }
+};
+
+// A device buffer and the pinned host copy it is uploaded from, grown together to `need` elements (the caller has waited for the last
+// upload from the pinned copy); `who` names the call in the text of a failed allocation.  once: the pair at a fixed size.
+template <typename T> struct Staged {
+    T* d = nullptr;
+    T* h = nullptr;
+    size_t cap = 0;
+    Staged() = default;
+    Staged(const Staged&) = delete;
+    Staged& operator=(const Staged&) = delete;
+    ~Staged() { if (d) (void)hipFree(d); if (h) (void)hipHostFree(h); }
+    int grow(size_t need, hipStream_t stream, const char* who) {
+        if (need <= cap) return SW_OK;
+        HIP_TRY(hipStreamSynchronize(stream));
+        if (d) HIP_TRY(hipFree(d));
+        if (h) HIP_TRY(hipHostFree(h));
+        d = nullptr; h = nullptr; cap = 0;
+        if (hipMalloc((void**)&d, need * sizeof(T)) != hipSuccess || hipHostMalloc((void**)&h, need * sizeof(T), 0) != hipSuccess) {
+            set_err("%s: workspace allocation failed", who);
+            return SW_ENOMEM;
+        }
+        cap = need;
+        return SW_OK;
+    }
+    int once() {
+        if (!d) HIP_TRY(hipMalloc((void**)&d, sizeof(T)));
+        if (!h) HIP_TRY(hipHostMalloc((void**)&h, sizeof(T), 0));
+        return SW_OK;
+    }
+};
+
 struct SW_HIDDEN sw_ctx {
     int device = 0;
     int num_cus = 256;
     bool xcd_round_robin = false;       // sw_xcc_probe saw workgroup i on XCD i % 8 (8 XCDs of 32 CUs)
-    unsigned char* d_alpha = nullptr;   // [64..323] letter code table + letter count; [512..1535] XCD of every workgroup of the running launch (sw_systolic2, xcd_mode)
-    unsigned int* d_part = nullptr;     // sw_prep_scan: one 256-bit presence map of byte values per block (up to 2048 blocks)
+    Workspace<unsigned char> d_alpha;     // [64..323] letter code table + letter count; [512..1535] XCD of every workgroup of the running launch (sw_systolic2, xcd_mode)
+    Workspace<unsigned int> d_part;       // sw_prep_scan: one 256-bit presence map of byte values per block (up to 2048 blocks)
     int64_t opt_dbg_ptr = 0;
     swp::PlanOptions opt;               // the options the planners read (sw_set_option; include/swhip.h)
     // ---- fills (sw_api_fill.hip)
     unsigned epoch = 0;                 // 12-bit launch tag, see FillParams::tag_base
-    unsigned long long* d_edge = nullptr;
-    size_t edge_cap = 0;                // granules
-    unsigned long long* d_key = nullptr; // [0] = arg-max key, [1] low word = abort flag
-    unsigned char* d_cb = nullptr;      // systolic engine: padded copies of b (bytes, 16-bit, letter codes; sw_pad_b)
-    size_t cb_cap = 0;
-    unsigned int* d_edge4 = nullptr;    // perm producer: lane-63 columns as self-tagged 4-byte values
-    size_t edge4_cap = 0;               // elements
+    Workspace<unsigned long long> d_edge;   // (granules)
+    Workspace<unsigned long long> d_key; // [0] = arg-max key, [1] low word = abort flag
+    Workspace<unsigned char, 4> d_cb;   // systolic engine: padded copies of b (bytes, 16-bit, letter codes; sw_pad_b): 4 bytes per element
+    Workspace<unsigned int> d_edge4;    // perm producer: lane-63 columns as self-tagged 4-byte values
     unsigned epoch8 = 0;                // 8-bit launch tag of those values
-    unsigned int* d_sync = nullptr;     // one-launch fills (sw_systolic2's prologue / epilogue): barrier and exit counters, presence map; zero between launches
-    unsigned char* d_priv = nullptr; size_t priv_cap = 0;   // ... and every workgroup's own padded copy of b + letter codes
+    Workspace<unsigned int> d_sync;       // one-launch fills (sw_systolic2's prologue / epilogue): barrier and exit counters, presence map; zero between launches
+    Workspace<unsigned char> d_priv;      // ... and every workgroup's own padded copy of b + letter codes
     bool key_dirty = false;             // d_key was left non-zero by a launch that does not re-arm it (everything but the one-launch fill)
     bool last_fused = false;            // the last launch_fill reports by itself (no sw_finalize behind it)
     swp::FillPlan last_plan;            // the plan of the last fill (sw_get_option "last_*")
@@ -90,103 +169,92 @@ struct SW_HIDDEN sw_ctx {
     int64_t opt_pace_ps = 0;            // systolic: pacing of strip 0 (ps per row; 0 = off)
     int64_t opt_band_wait_ms = 20000;   // band-resident launch: patience of the top-halo poll
     // ---- batches (sw_api_fill.hip)
-    unsigned long long* d_keys = nullptr; size_t keys_cap = 0;  // the fall-back: one key per pair
-    unsigned char* d_bcodes = nullptr; size_t bcodes_cap = 0;   // batch kernel: padded letter codes of every pair's b
-    int* d_bnd = nullptr; size_t bnd_cap = 0;                   // batch kernel: boundary columns between strips (ints)
+    Workspace<unsigned long long> d_keys;      // the fall-back: one key per pair
+    Workspace<unsigned char> d_bcodes;         // batch kernel: padded letter codes of every pair's b
+    Workspace<int> d_bnd;                      // batch kernel: boundary columns between strips (ints)
     int64_t opt_batch_lds = 0;          // batch kernel: dynamic LDS bytes per workgroup (caps the waves per CU; experiments)
     int64_t last_batch_kernel = 0;      // 1: the last sw_batch_device call ran on sw_batch_wave (one pair per wave)
     // ---- the search family (sw_api_search.hip).  Shared by its three calls: profile of the query, per-wave boundary columns, the schedule
     // and the substitution matrix (each on the device + a pinned host copy it is uploaded from), the work counter.  sitems_ev is recorded
     // behind the uploads of a call; the next call waits for it before it overwrites the pinned copies (stage_search_call).
-    signed char* d_sprof = nullptr; size_t sprof_cap = 0;
-    int* d_sbnd = nullptr; size_t sbnd_cap = 0;
-    swk::SearchItem* d_sitems = nullptr; swk::SearchItem* h_sitems = nullptr; size_t sitems_cap = 0;
-    signed char* d_submat = nullptr; signed char* h_submat = nullptr;
+    Workspace<signed char> d_sprof;
+    Workspace<int> d_sbnd;
+    Staged<swk::SearchItem> sitems;
+    Staged<sw_submat> submat;
     hipEvent_t sitems_ev = nullptr;
-    unsigned int* d_sctr = nullptr;
+    Workspace<unsigned int> d_sctr;
     int64_t last_search_grid = 0;       // workgroups of the last search launch
     int64_t last_search_kernel = 0;     // its kernel: index in kSearch (swp::search_kernel_index)
-    int search_per_cu[swp::kSearchKernels] = {};   // occupancy of every sw_search_wave instantiation at 256 threads ...
-    bool search_per_cu_known = false;              // ... queried at the first search
+    Occupancy<swp::kSearchKernels> search_per_cu;  // of every sw_search_wave instantiation, queried at the first search
     int64_t last_search_affine_grid = 0;    // workgroups of the last affine search launch
     int64_t last_search_affine_kernel = 0;  // its kernel: index in kSearchAffine (swp::search_affine_kernel_index)
-    int search_affine_per_cu[swp::kSearchAffineKernels] = {};   // occupancy of every sw_search_affine_wave instantiation at 256 threads ...
-    bool search_affine_per_cu_known = false;                    // ... queried at the first affine search
+    Occupancy<swp::kSearchAffineKernels> search_affine_per_cu;  // of every sw_search_affine_wave instantiation, queried at the first affine search
     // alignment of hits (sw_align_affine_device): one direction matrix per wave at work
-    unsigned char* d_adir = nullptr; size_t adir_cap = 0;
+    Workspace<unsigned char> d_adir;
     int64_t opt_align_workspace_mib = 1024;
     int64_t last_align_affine_kernel = 0, last_align_affine_slots = 0;
-    int align_affine_per_cu[swp::kAlignAffineKernels] = {};     // occupancy of every sw_align_affine_wave instantiation at 256 threads ...
-    bool align_affine_per_cu_known = false;                     // ... queried at the first call
+    Occupancy<swp::kAlignAffineKernels> align_affine_per_cu;    // of every sw_align_affine_wave instantiation, queried at the first call
     // checkpointed alignment (sw_align_ckpt.hip) of both alignment calls: 0 whole matrices, 1 always, 2 where 0 would refuse for size
     int64_t opt_align_checkpoint = 0, opt_align_checkpoint_rows = 0;
     int64_t last_align_affine_checkpointed = 0, last_align_affine_band_rows = 0, last_align_affine_slot_bytes = 0;
     int64_t last_align_hits_checkpointed = 0, last_align_hits_band_rows = 0;
-    int align_ckpt_per_cu[swp::kAlignAffineKernels] = {};       // occupancy of every sw_align_ckpt_wave instantiation at 256 threads ...
-    bool align_ckpt_per_cu_known = false;                       // ... queried at the first checkpointed call
-    int align_hits_ckpt_per_cu[swp::kAlignHitsKernels] = {};    // likewise sw_align_hits_ckpt_wave
-    bool align_hits_ckpt_per_cu_known = false;
+    Occupancy<swp::kAlignAffineKernels> align_ckpt_per_cu;      // of every sw_align_ckpt_wave instantiation, queried at the first checkpointed call
+    Occupancy<swp::kAlignHitsKernels> align_hits_ckpt_per_cu;   // likewise sw_align_hits_ckpt_wave
     // alignment of the hits of many queries (sw_db_align_affine_hits): the item list of a group and the control words of its lists; the
     // profiles, the boundary columns, the query table and the direction workspace are those of the calls above
-    swk::AlignHitItem* d_ahitems = nullptr; size_t ahitems_cap = 0;
-    swk::AlignHitsCtl* d_ahctl = nullptr;
-    unsigned int* d_ahfilled = nullptr;  // lists of the last call that received items, counted by the binning ("last_align_hits_lists")
+    Workspace<swk::AlignHitItem> d_ahitems;
+    Workspace<swk::AlignHitsCtl> d_ahctl;
+    Workspace<unsigned int> d_ahfilled;  // lists of the last call that received items, counted by the binning ("last_align_hits_lists")
     int64_t last_align_hits_launches = 0, last_align_hits_tiers = 0, last_align_hits_slots = 0;
-    int align_hits_per_cu[swp::kAlignHitsKernels] = {};         // occupancy of every sw_align_hits_wave instantiation at 256 threads ...
-    bool align_hits_per_cu_known = false;                       // ... queried at the first call
+    Occupancy<swp::kAlignHitsKernels> align_hits_per_cu;        // of every sw_align_hits_wave instantiation, queried at the first call
     // many queries against a prepared database (sw_db_search_affine): the call's query table on the device + the pinned copy it is uploaded
     // from (the protocol of sitems_ev covers it), the budget of a group's profiles
-    swk::MultiQuery* d_mq = nullptr; swk::MultiQuery* h_mq = nullptr; size_t mq_cap = 0;
+    Staged<swk::MultiQuery> mq;
     int64_t opt_search_profile_mib = 256;
     int64_t last_search_multi_groups = 0, last_search_multi_launches = 0, last_search_multi_grid = 0;   // of the last call; the grid of its last launch
-    int search_multi_per_cu[swp::kSearchMultiKernels] = {};     // occupancy of every sw_search_affine_multi_wave instantiation at 256 threads ...
-    bool search_multi_per_cu_known = false;                     // ... queried at the first call
+    Occupancy<swp::kSearchMultiKernels> search_multi_per_cu;    // of every sw_search_affine_multi_wave instantiation, queried at the first call
     // the same search on packed 16-bit lanes (sw_search_multi16.hip): "search_lanes" (32 / 16), the packed launches of the last call
     int64_t opt_search_lanes = 32;
     int64_t last_search_multi_packed_launches = 0;
-    int search_multi_packed_per_cu[swp::kSearchMultiKernels] = {};   // occupancy of every sw_search_multi_pk_wave instantiation at 256 threads ...
-    bool search_multi_packed_per_cu_known = false;              // ... queried at the first call
+    Occupancy<swp::kSearchMultiKernels> search_multi_packed_per_cu;   // of every sw_search_multi_pk_wave instantiation, queried at the first call
     // a pair list against a prepared database (sw_db_search_affine_pairs): the items of a chunk and the control words of a (chunk, group);
     // the profiles, the boundary columns and the query table are those of the calls above (the table carries entry_of behind its entries)
-    swk::SearchPairItem* d_spitems = nullptr; size_t spitems_cap = 0;   // (bytes)
-    swk::SearchPairsCtl* d_spctl = nullptr;
+    Workspace<swk::SearchPairItem, 1> d_spitems;                // (grown in bytes)
+    Workspace<swk::SearchPairsCtl> d_spctl;
     int64_t opt_search_pairs_chunk = swp::kSearchPairsChunk;
     int64_t last_search_pairs_groups = 0, last_search_pairs_chunks = 0, last_search_pairs_launches = 0;
-    int search_pairs_per_cu[swp::kSearchPairsKernels] = {};     // occupancy of every sw_search_affine_pairs_wave instantiation at 256 threads ...
-    bool search_pairs_per_cu_known = false;                     // ... queried at the first call
+    Occupancy<swp::kSearchPairsKernels> search_pairs_per_cu;    // of every sw_search_affine_pairs_wave instantiation, queried at the first call
     // the same call on packed 16-bit lanes (sw_search_pairs16.hip): "search_pairs_lanes" (32 / 16), the cell workspace of a (chunk, group)
     // -- control words, then count, cursor and base of every cell --, the two-pair items the device built in the last call, its packed launches
     int64_t opt_search_pairs_lanes = 32;
-    unsigned char* d_spcells = nullptr; size_t spcells_cap = 0;     // (bytes)
-    unsigned long long* d_sptotal = nullptr;                    // "last_search_pairs_packed_items"
+    Workspace<unsigned char> d_spcells;
+    Workspace<unsigned long long> d_sptotal;                    // "last_search_pairs_packed_items"
     int64_t last_search_pairs_packed_launches = 0;
-    int search_pairs_packed_per_cu[swp::kSearchPairsKernels] = {};   // occupancy of every sw_search_pairs_pk_wave instantiation at 256 threads ...
-    bool search_pairs_packed_per_cu_known = false;              // ... queried at the first call
+    Occupancy<swp::kSearchPairsKernels> search_pairs_packed_per_cu;   // of every sw_search_pairs_pk_wave instantiation, queried at the first call
     // the ungapped pre-filter (sw_db_prefilter_ungapped): its control words, "prefilter_lanes", what the last call did
-    swk::PrefilterCtl* d_pfctl = nullptr;
+    Workspace<swk::PrefilterCtl> d_pfctl;
     int64_t opt_prefilter_lanes = 0;
     int64_t last_prefilter_groups = 0, last_prefilter_launches = 0, last_prefilter_packed_launches = 0;
-    int prefilter_per_cu[swp::kPrefilterKernels] = {};          // occupancy of every sw_prefilter_wave / _wave16 instantiation at 256 threads ...
-    bool prefilter_per_cu_known = false;                        // ... queried at the first call
+    Occupancy<swp::kPrefilterKernels> prefilter_per_cu;         // of every sw_prefilter_wave / _wave16 instantiation, queried at the first call
     // the best targets per query (sw_top_hits_device, sw_db_search_affine_top): the result rows of a chunk, the histograms and the
     // per-row states of the radix select
-    sw_result* d_tres = nullptr; size_t tres_cap = 0;
-    unsigned int* d_thist = nullptr; size_t thist_cap = 0;
-    swk::TopState* d_tstate = nullptr; size_t tstate_cap = 0;
+    Workspace<sw_result> d_tres;
+    Workspace<unsigned int> d_thist;
+    Workspace<swk::TopState> d_tstate;
     int64_t opt_search_results_mib = 1024;
     int64_t last_search_top_chunks = 0, last_search_top_kernel = 0;
     int top_hist_per_cu = 0;                                    // occupancy of sw_top_hist at 256 threads, queried at the first call
     // the best entries per query of a pair list (sw_top_hits_pairs_device): the segments' keys and positions, the per-query counts and
     // offsets; sw_db_search_affine_top_prefiltered keeps its list and the list's results (16 + 24 bytes per entry) in d_tplist
-    unsigned long long* d_tpkeys = nullptr; size_t tpkeys_cap = 0;
-    unsigned int* d_tppos = nullptr; size_t tppos_cap = 0;
-    unsigned int* d_tpseg = nullptr; size_t tpseg_cap = 0;
-    unsigned char* d_tplist = nullptr; size_t tplist_cap = 0;   // (entries)
+    Workspace<unsigned long long> d_tpkeys;
+    Workspace<unsigned int> d_tppos;
+    Workspace<unsigned int> d_tpseg;
+    Workspace<unsigned char, sizeof(sw_pair) + sizeof(sw_result)> d_tplist;   // (grown in entries)
     int64_t last_top_pairs_launches = 0, last_top_pairs_kernel = 0;
     // the next PSSM from aligned hits (sw_db_pssm_from_hits): the call's table -- S, the code table, the query offsets -- on the device +
     // TWO pinned copies it is uploaded from in turn: phtab_ev[i] is recorded behind the upload from copy i, and a call waits for the event
     // of the copy it is about to overwrite -- the upload of the call before the last one --, so a loop can be enqueued one call ahead
-    unsigned char* d_phtab = nullptr; unsigned char* h_phtab[2] = {nullptr, nullptr}; size_t phtab_cap = 0;   // (bytes)
+    Workspace<unsigned char> d_phtab; unsigned char* h_phtab[2] = {nullptr, nullptr};   // (released by sw_destroy beside their events)
     hipEvent_t phtab_ev[2] = {nullptr, nullptr};
     int phtab_turn = 0;
     int64_t last_pssm_hits_launches = 0;
@@ -210,14 +278,6 @@ struct SW_HIDDEN sw_db {
     swk::SearchItem* d_items = nullptr;  // the nonempty targets, longest first (swp::search_schedule)
     int64_t* d_offsets = nullptr;        // the ntargets + 1 offsets, the caller's order
 };
-
-// A launch table: every instantiation beside the index the planner gives it, checked at compile time to sit at that index.
-template <typename K> struct Indexed { int index; K k; };
-template <typename K, size_t N> constexpr bool at_their_indices(const Indexed<K> (&t)[N]) {
-    for (size_t i = 0; i < N; ++i)
-        if (t[i].index != (int)i) return false;
-    return true;
-}
 
 constexpr sw_scores kDefaultScores = {3, -3, -2};  // serial_smithW.c:59-61
 
@@ -274,17 +334,3 @@ struct DevOrder {   // RAII: device lock + stream ordering for one fill call
         else { (void)hipGetLastError(); d.any = false; }
     }
 };
-
-// Grows a workspace of the context to `need` elements of `elem` bytes (+ `slack` bytes): waits for the stream (launches in flight may
-// still read the old one), frees it and allocates afresh.  `fresh` says whether it did: the caller wipes what must start zeroed.
-static inline int grow_workspace(void** buf, size_t& cap, size_t need, size_t elem, size_t slack, hipStream_t stream, bool& fresh) {
-    fresh = false;
-    if (need <= cap) return SW_OK;
-    HIP_TRY(hipStreamSynchronize(stream));
-    if (*buf) HIP_TRY(hipFree(*buf));
-    *buf = nullptr; cap = 0;
-    const size_t bytes = need * elem + slack;
-    if (hipMalloc(buf, bytes) != hipSuccess) { set_err("workspace allocation of %zu bytes failed", bytes); return SW_ENOMEM; }
-    cap = need; fresh = true;
-    return SW_OK;
-}

@@ -1,5 +1,5 @@
 // sw_plan.cpp -- the fill, batch and search planners (sw_plan.h).  No side effects, no allocation, no runtime calls -- except search_schedule,
-// which writes the schedule to the caller's buffer and sorts through a vector of its own, and plan_search_multi, whose plan grows with the queries.
+// which writes the schedule to the caller's buffer and sorts through a vector of its own, and the many-query plans, which grow with the queries.
 #include "sw_plan.h"
 #include <algorithm>
 #include <vector>
@@ -370,125 +370,200 @@ SearchPlan plan_search(const SearchJob& j, const DeviceFacts& dev) {
 // Measured: 3371 GCUPS on the kernel at 16 columns per lane and a query of 2048, 3017 at 8 columns and a query of 512.
 constexpr int kAffineC16MinPerCu = 2;
 
+namespace {
+
+// Columns per lane of a query under affine gaps: lane_columns, but 16 only where the 16-column kernel (occupancy per_cu16) keeps
+// kAffineC16MinPerCu workgroups on a CU.
+int query_columns(int64_t qlen, int per_cu16) {
+    const int C = lane_columns(qlen);
+    return C == 16 && per_cu16 < kAffineC16MinPerCu ? 8 : C;
+}
+int64_t query_padded(int64_t qlen, int per_cu16) {
+    const int64_t w = 64 * query_columns(qlen, per_cu16);
+    return (qlen + w - 1) / w * w;
+}
+
+// Workgroups of four waves a launch may run: the resident ones, a quarter of its items (items < 0: not known here, the answer is the
+// most any list can use), what the boundary columns leave of kSearchBndBytes; at least 1.
+int64_t grid_cap(int per_cu, int num_cus, int64_t bnd_per, int64_t items = -1) {
+    int64_t grid = (int64_t)per_cu * num_cus;
+    if (items >= 0) grid = std::min(grid, (items + 3) / 4);
+    if (bnd_per) grid = std::min(grid, kSearchBndBytes / (bnd_per * 4 * 4));
+    return std::max<int64_t>(1, grid);
+}
+
+// Slots of an alignment launch, one per wave at work: the entries, the resident waves, the budget, the boundary columns; at least 1.
+int64_t slot_cap(int64_t entries, int per_cu, int num_cus, int64_t budget_bytes, int64_t slot_bytes, int64_t bnd_per) {
+    int64_t slots = std::min<int64_t>({entries, (int64_t)per_cu * num_cus * 4, budget_bytes / slot_bytes});
+    if (bnd_per) slots = std::min(slots, kSearchBndBytes / (bnd_per * 4));
+    return std::max<int64_t>(1, slots);
+}
+
+}  // namespace
+
 SearchAffinePlan plan_search_affine(const SearchAffineJob& j) {
     using swk::SW_SEARCH_ROWS;
     SearchAffinePlan s;
-    s.C = lane_columns(j.qlen);
-    if (s.C == 16 && j.per_cu[search_affine_kernel_index(16)] < kAffineC16MinPerCu) s.C = 8;
+    s.C = query_columns(j.qlen, j.per_cu[search_affine_kernel_index(16)]);
     s.kernel = search_affine_kernel_index(s.C);
     s.nstrips = (j.qlen + 64 * s.C - 1) / (64 * s.C);
     s.qpad = s.nstrips * 64 * s.C;
     s.bnd_row_ints = 2;
     s.bnd_per = s.bnd_row_ints * boundary_ints(s.nstrips, j.maxlen);
-    s.grid = std::min<int64_t>((int64_t)j.per_cu[s.kernel] * j.num_cus, (j.ntargets + 3) / 4);
-    if (s.bnd_per) s.grid = std::min<int64_t>(s.grid, kSearchBndBytes / (s.bnd_per * 4 * 4));
-    s.grid = std::max<int64_t>(1, s.grid);
+    s.grid = grid_cap(j.per_cu[s.kernel], j.num_cus, s.bnd_per, j.ntargets);
     s.prof_need = (size_t)(SW_SEARCH_ROWS * s.qpad);
     s.prof_blocks = (int)std::min<int64_t>((SW_SEARCH_ROWS * s.qpad + 255) / 256, kProfileBlocks);
     s.bnd_need = s.bnd_per ? (size_t)(s.grid * 4 * s.bnd_per) : 0;
     return s;
 }
 
-// Many queries against a prepared database.  Host work is O(nqueries): one pass cuts the groups, one pass per group counts its classes
-// and lays the table out; nothing here looks at a target.
-SearchMultiPlan plan_search_multi(const SearchMultiJob& j) {
+// ---- the shared parts of the many-query plans.  Every many-query kernel table has one instantiation per width, at index C / 8.
+namespace {
+
+constexpr int kQueryClasses = 3;
+static_assert(kSearchMultiKernels == kQueryClasses && kSearchPairsKernels == kQueryClasses && kAlignHitsKernels == kQueryClasses &&
+              kPrefilterKernels == 2 * kQueryClasses && search_multi_kernel_index(16) == kQueryClasses - 1);
+constexpr int class_columns(int k) { return k == 0 ? 4 : 8 * k; }
+
+// The layout of a call's queries.  Groups: consecutive queries while their profiles fit the budget and, where the caller bounds them,
+// at most group_queries of them; at least one, so one query alone may exceed the budget.  The table of a group: by class, input order
+// within a class; the profiles lie in table order.  Host work is O(nqueries); nothing here looks at a target.
+struct QueryClass { int64_t q0 = 0, nq = 0, qpad = 0, nstrips = 0; };   // entries q0 .. q0 + nq - 1; the largest qpad and nstrips among them
+struct QueryGroup {
+    int64_t q0 = 0, nq = 0, prof_bytes = 0;
+    QueryClass cls[kQueryClasses];
+};
+struct QueryLayout {
+    std::vector<swk::MultiQuery> table;
+    std::vector<QueryGroup> group;
+    size_t prof_need = 0;
+};
+
+QueryLayout layout_queries(const int64_t* qlens, int64_t n, int per_cu16, int64_t budget_bytes, int64_t group_queries = INT64_MAX) {
     using swk::SW_SEARCH_ROWS;
-    SearchMultiPlan m;
-    const int64_t n = j.nqueries;
-    m.table.resize((size_t)n);
-    auto columns = [&](int64_t qlen) {
-        int C = lane_columns(qlen);
-        if (C == 16 && j.per_cu[search_multi_kernel_index(16)] < kAffineC16MinPerCu) C = 8;
-        return C;
-    };
-    auto padded = [&](int64_t qlen) { const int64_t w = 64 * columns(qlen); return (qlen + w - 1) / w * w; };
-    const int64_t max_items = std::max<int64_t>(1, std::min(j.max_items, kMultiMaxItems));
+    QueryLayout y;
+    y.table.resize((size_t)n);
     for (int64_t g0 = 0; g0 < n;) {
-        // the group: consecutive queries while their profiles fit the budget, at least one
+        QueryGroup grp;
         int64_t g1 = g0, bytes = 0;
-        while (g1 < n && (g1 == g0 || bytes + SW_SEARCH_ROWS * padded(j.qlens[g1]) <= j.budget_bytes)) bytes += SW_SEARCH_ROWS * padded(j.qlens[g1++]);
-        m.group.push_back(MultiGroup{g0, g1 - g0, bytes});
-        m.prof_need = std::max(m.prof_need, (size_t)bytes);
-        // the table of the group: by class, input order within a class; the profiles lie in table order
-        int64_t at[kSearchMultiKernels + 1] = {};
-        for (int64_t q = g0; q < g1; ++q) ++at[search_multi_kernel_index(columns(j.qlens[q])) + 1];
-        for (int k = 0; k < kSearchMultiKernels; ++k) at[k + 1] += at[k];
-        int64_t first[kSearchMultiKernels + 1];
-        std::copy(at, at + kSearchMultiKernels + 1, first);
+        while (g1 < n && (g1 == g0 || (g1 - g0 < group_queries && bytes + SW_SEARCH_ROWS * query_padded(qlens[g1], per_cu16) <= budget_bytes)))
+            bytes += SW_SEARCH_ROWS * query_padded(qlens[g1++], per_cu16);
+        grp.q0 = g0; grp.nq = g1 - g0; grp.prof_bytes = bytes;
+        y.prof_need = std::max(y.prof_need, (size_t)bytes);
+        int64_t at[kQueryClasses + 1] = {};
+        for (int64_t q = g0; q < g1; ++q) ++at[query_columns(qlens[q], per_cu16) / 8 + 1];
+        for (int k = 0; k < kQueryClasses; ++k) {
+            at[k + 1] += at[k];
+            grp.cls[k].q0 = g0 + at[k]; grp.cls[k].nq = at[k + 1] - at[k];
+        }
         for (int64_t q = g0; q < g1; ++q) {
-            const int C = columns(j.qlens[q]);
-            const int64_t qpad = padded(j.qlens[q]);
-            m.table[(size_t)(g0 + at[search_multi_kernel_index(C)]++)] = swk::MultiQuery{0, 0, q, (int32_t)j.qlens[q], (int32_t)qpad, (int32_t)(qpad / (64 * C)), 0};
+            const int C = query_columns(qlens[q], per_cu16);
+            const int64_t qpad = query_padded(qlens[q], per_cu16);
+            QueryClass& c = grp.cls[C / 8];
+            y.table[(size_t)(g0 + at[C / 8]++)] = swk::MultiQuery{0, 0, q, (int32_t)qlens[q], (int32_t)qpad, (int32_t)(qpad / (64 * C)), 0};
+            c.qpad = std::max(c.qpad, qpad);
+            c.nstrips = std::max(c.nstrips, qpad / (64 * C));
         }
         int64_t off = 0;
-        for (int64_t t = g0; t < g1; ++t) { m.table[(size_t)t].prof_off = off; off += SW_SEARCH_ROWS * m.table[(size_t)t].qpad; }
-        // the launches of the group: per class, cut by target ranks (and by queries, should a class alone pass the limit)
-        for (int k = 0; k < kSearchMultiKernels && j.nonempty > 0; ++k) {
-            for (int64_t qa = first[k]; qa < first[k + 1];) {
-                const int64_t nq = std::min(first[k + 1] - qa, max_items), ranks_per = max_items / nq;
-                int64_t strips = 1;
-                for (int64_t t = qa; t < qa + nq; ++t) strips = std::max<int64_t>(strips, m.table[(size_t)(g0 + t)].nstrips);
-                for (int64_t r0 = 0; r0 < j.nonempty; r0 += ranks_per) {
-                    MultiLaunch l;
-                    l.group = (int)m.group.size() - 1; l.C = k == 0 ? 4 : 8 * k; l.kernel = k;
-                    l.q0 = g0 + qa; l.nq = nq;
-                    l.rank0 = r0; l.nranks = std::min(ranks_per, j.nonempty - r0);
-                    l.items = l.nq * l.nranks;
-                    l.bnd_per = 2 * boundary_ints(strips, j.longest);
-                    l.grid = std::min<int64_t>((int64_t)j.per_cu[k] * j.num_cus, (l.items + 3) / 4);
-                    if (l.bnd_per) l.grid = std::min<int64_t>(l.grid, kSearchBndBytes / (l.bnd_per * 4 * 4));
-                    l.grid = std::max<int64_t>(1, l.grid);
-                    m.bnd_need = std::max(m.bnd_need, (size_t)(l.grid * 4 * l.bnd_per));
-                    m.launch.push_back(l);
-                }
-                qa += nq;
-            }
-        }
+        for (int64_t t = g0; t < g1; ++t) { y.table[(size_t)t].prof_off = off; off += SW_SEARCH_ROWS * y.table[(size_t)t].qpad; }
+        y.group.push_back(grp);
         g0 = g1;
     }
+    return y;
+}
+
+// The entries [a, b) of a class with those that run packed moved to the front, input order within either part (every entry keeps its
+// profile's place); returns where the others begin.
+template <typename Packed>
+int64_t packed_first(std::vector<swk::MultiQuery>& table, int64_t a, int64_t b, Packed packed) {
+    return std::stable_partition(table.begin() + a, table.begin() + b, packed) - table.begin();
+}
+// (the packed kernel of 16 columns per lane is taken where it keeps the workgroups on a CU that the 32-bit one needs)
+bool packed_kernel_fits(const int* packed_per_cu, int k) { return packed_per_cu[k] >= (class_columns(k) == 16 ? kAffineC16MinPerCu : 1); }
+
+// The launches of the entries [s0, s1) of a class, all packed or all not, against every target rank: cut by target ranks (and by queries,
+// should the part alone pass the limit) so that no launch has more than max_items items.  A packed launch takes the ranks in pairs and
+// counts rank pairs.  The boundary columns are sized by the strips of the launch's own queries.  Returns the launches it added.
+struct Ranks { int num_cus; int64_t nonempty, longest, max_items; };
+template <typename Job>
+Ranks ranks_of(const Job& j) { return Ranks{j.num_cus, j.nonempty, j.longest, std::max<int64_t>(1, std::min(j.max_items, kMultiMaxItems))}; }
+
+template <typename Launch>
+int64_t cut_rank_launches(std::vector<Launch>& out, size_t& bnd_need, const std::vector<swk::MultiQuery>& table, const Ranks& r, int group, int C, int kernel,
+                          int per_cu, bool packed, int64_t s0, int64_t s1) {
+    const size_t before = out.size();
+    for (int64_t qa = s0; qa < s1 && r.nonempty > 0;) {
+        const int64_t nq = std::min(s1 - qa, r.max_items), ranks_per = (packed ? 2 : 1) * (r.max_items / nq);
+        int64_t strips = 1;
+        for (int64_t t = qa; t < qa + nq; ++t) strips = std::max<int64_t>(strips, table[(size_t)t].nstrips);
+        for (int64_t r0 = 0; r0 < r.nonempty; r0 += ranks_per) {
+            Launch l;
+            l.group = group; l.C = C; l.kernel = kernel;
+            if constexpr (requires { l.packed; }) l.packed = packed;
+            l.q0 = qa; l.nq = nq;
+            l.rank0 = r0; l.nranks = std::min(ranks_per, r.nonempty - r0);
+            l.items = l.nq * (packed ? (l.nranks + 1) / 2 : l.nranks);
+            l.bnd_per = 2 * boundary_ints(strips, r.longest);
+            l.grid = grid_cap(per_cu, r.num_cus, l.bnd_per, l.items);
+            bnd_need = std::max(bnd_need, (size_t)(l.grid * 4 * l.bnd_per));
+            out.push_back(l);
+        }
+        qa += nq;
+    }
+    return (int64_t)(out.size() - before);
+}
+
+// What the three plans of rank launches hand over of a layout.
+template <typename Plan>
+void take_layout(Plan& p, QueryLayout& y) {
+    p.table = std::move(y.table);
+    p.prof_need = y.prof_need;
+    for (const QueryGroup& g : y.group) p.group.push_back(MultiGroup{g.q0, g.nq, g.prof_bytes});
+}
+
+}  // namespace
+
+// Many queries against a prepared database: per (group, class) the launches of cut_rank_launches.
+SearchMultiPlan plan_search_multi(const SearchMultiJob& j) {
+    SearchMultiPlan m;
+    QueryLayout y = layout_queries(j.qlens, j.nqueries, j.per_cu[search_multi_kernel_index(16)], j.budget_bytes);
+    const Ranks r = ranks_of(j);
+    for (size_t g = 0; g < y.group.size(); ++g)
+        for (int k = 0; k < kQueryClasses; ++k) {
+            const QueryClass& c = y.group[g].cls[k];
+            cut_rank_launches(m.launch, m.bnd_need, y.table, r, (int)g, class_columns(k), k, j.per_cu[k], false, c.q0, c.q0 + c.nq);
+        }
+    take_layout(m, y);
     return m;
 }
 
-// A pair list against a prepared database.  The table and the groups come from plan_search_multi itself (asked for a handle without
-// targets, it plans no launch); the rest is O(nqueries) too: nothing here looks at a pair or a target, and the chunks are arithmetic.
+// A pair list against a prepared database.  O(nqueries): nothing here looks at a pair or a target, and the chunks are arithmetic.  One
+// score launch per class present in a group; its boundary columns are sized by the whole class.
 SearchPairsPlan plan_search_pairs(const SearchPairsJob& j) {
     SearchPairsPlan s;
-    SearchMultiJob mj;
-    mj.qlens = j.qlens; mj.nqueries = j.nqueries; mj.longest = j.longest; mj.nonempty = 0; mj.num_cus = j.num_cus; mj.budget_bytes = j.budget_bytes;
-    std::copy(std::begin(j.per_cu), std::end(j.per_cu), mj.per_cu);   // (decides whether 16 columns per lane are taken, as there)
-    SearchMultiPlan m = plan_search_multi(mj);
-    s.table = std::move(m.table);
-    s.prof_need = m.prof_need;
+    QueryLayout y = layout_queries(j.qlens, j.nqueries, j.per_cu[search_pairs_kernel_index(16)], j.budget_bytes);
+    s.table = std::move(y.table);
+    s.prof_need = y.prof_need;
     s.entry_of.resize((size_t)j.nqueries);
     for (int64_t t = 0; t < j.nqueries; ++t) s.entry_of[(size_t)s.table[(size_t)t].row] = (int32_t)t;
     s.chunk = std::clamp<int64_t>(j.chunk, 1, kSearchPairsChunkMax);
     const int64_t npairs = std::max<int64_t>(0, j.npairs), most = std::min(npairs, s.chunk);   // pairs of the largest chunk
     s.nchunks = (npairs + s.chunk - 1) / s.chunk;
     s.items_need = (size_t)(24 * most);
-    for (size_t g = 0; g < m.group.size(); ++g) {
+    for (size_t g = 0; g < y.group.size(); ++g) {
         PairsGroup grp;
-        grp.q0 = m.group[g].q0; grp.nq = m.group[g].nq; grp.prof_bytes = m.group[g].prof_bytes;
-        // the classes of the group: its entries are sorted by columns per lane, qpad = nstrips * 64 * C
-        int64_t strips[kSearchPairsKernels] = {}, t = grp.q0;
-        for (int k = 0; k < kSearchPairsKernels; ++k) {
-            grp.cls_q0[k] = t;
-            for (; t < grp.q0 + grp.nq; ++t) {
-                const swk::MultiQuery& d = s.table[(size_t)t];
-                if (search_pairs_kernel_index(d.qpad / d.nstrips / 64) != k) break;
-                strips[k] = std::max<int64_t>(strips[k], d.nstrips);
-            }
-        }
-        grp.cls_q0[kSearchPairsKernels] = t;
+        grp.q0 = y.group[g].q0; grp.nq = y.group[g].nq; grp.prof_bytes = y.group[g].prof_bytes;
+        for (int k = 0; k < kQueryClasses; ++k) grp.cls_q0[k] = y.group[g].cls[k].q0;
+        grp.cls_q0[kQueryClasses] = grp.q0 + grp.nq;
         s.group.push_back(grp);
-        for (int k = 0; k < kSearchPairsKernels; ++k) {
-            if (grp.cls_q0[k + 1] == grp.cls_q0[k]) continue;
+        for (int k = 0; k < kQueryClasses; ++k) {
+            const QueryClass& c = y.group[g].cls[k];
+            if (c.nq == 0) continue;
             PairsLaunch l;
-            l.group = (int)g; l.C = k == 0 ? 4 : 8 * k; l.kernel = k;
-            l.q0 = grp.cls_q0[k]; l.nq = grp.cls_q0[k + 1] - grp.cls_q0[k];
-            l.bnd_per = 2 * boundary_ints(strips[k], j.longest);
-            l.max_grid = (int64_t)j.per_cu[k] * j.num_cus;
-            if (l.bnd_per) l.max_grid = std::min<int64_t>(l.max_grid, kSearchBndBytes / (l.bnd_per * 4 * 4));
-            l.max_grid = std::max<int64_t>(1, l.max_grid);
+            l.group = (int)g; l.C = class_columns(k); l.kernel = k;
+            l.q0 = c.q0; l.nq = c.nq;
+            l.bnd_per = 2 * boundary_ints(c.nstrips, j.longest);
+            l.max_grid = grid_cap(j.per_cu[k], j.num_cus, l.bnd_per);
             s.bnd_need = std::max(s.bnd_need, (size_t)(search_pairs_grid(l, most) * 4 * l.bnd_per));
             s.launch.push_back(l);
         }
@@ -497,119 +572,43 @@ SearchPairsPlan plan_search_pairs(const SearchPairsJob& j) {
     return s;
 }
 
-// The ungapped pre-filter.  The table and the groups come from plan_search_multi itself (asked for a handle without targets, it plans
-// no launch); per (group, class) the packed queries move to the front, every entry keeping its profile's place.  O(nqueries): nothing
-// here looks at a target, and the launches of a class are cut by arithmetic on the ranks.
+// The ungapped pre-filter: per (group, class) the packed queries move to the front and either part gets its rank launches.  The classes
+// take 16 columns per lane where both kernels of that width keep two workgroups on a CU.
 PrefilterPlan plan_prefilter(const PrefilterJob& j) {
     PrefilterPlan f;
-    SearchMultiJob mj;
-    mj.qlens = j.qlens; mj.nqueries = j.nqueries; mj.longest = j.longest; mj.nonempty = 0; mj.num_cus = j.num_cus; mj.budget_bytes = j.budget_bytes;
-    // (16 columns per lane are taken as there: where both kernels of that width keep two workgroups on a CU)
-    for (int k = 0; k < kSearchMultiKernels; ++k) {
-        const int C = k == 0 ? 4 : 8 * k;
-        mj.per_cu[k] = std::min(j.per_cu[prefilter_kernel_index(C, false)], j.per_cu[prefilter_kernel_index(C, true)]);
-    }
-    SearchMultiPlan m = plan_search_multi(mj);
-    f.table = std::move(m.table);
-    f.group = std::move(m.group);
-    f.prof_need = m.prof_need;
-    const int64_t max_items = std::max<int64_t>(1, std::min(j.max_items, kMultiMaxItems));
+    QueryLayout y = layout_queries(j.qlens, j.nqueries, std::min(j.per_cu[prefilter_kernel_index(16, false)], j.per_cu[prefilter_kernel_index(16, true)]),
+                                   j.budget_bytes);
+    const Ranks r = ranks_of(j);
     auto packed = [&](const swk::MultiQuery& d) { return prefilter_packed(j.max_entry, d.qlen, j.longest, j.lanes); };
-    auto klass = [](const swk::MultiQuery& d) { return d.qpad / d.nstrips / 64 / 8; };   // columns per lane 4, 8, 16 -> 0, 1, 2
-    for (size_t g = 0; g < f.group.size(); ++g) {
-        const int64_t g0 = f.group[g].q0, g1 = g0 + f.group[g].nq;
-        for (int64_t a = g0; a < g1;) {
-            const int k = klass(f.table[(size_t)a]), C = k == 0 ? 4 : 8 * k;
-            int64_t b = a;
-            while (b < g1 && klass(f.table[(size_t)b]) == k) ++b;
-            const int64_t mid = std::stable_partition(f.table.begin() + a, f.table.begin() + b, packed) - f.table.begin();
-            for (int side = 0; side < 2 && j.nonempty > 0; ++side) {
-                const bool pk = side == 0;
-                const int64_t s0 = pk ? a : mid, s1 = pk ? mid : b;
-                const int kernel = prefilter_kernel_index(C, pk);
-                for (int64_t qa = s0; qa < s1;) {
-                    const int64_t nq = std::min(s1 - qa, max_items);
-                    // target ranks of a launch: as many as keep its items inside max_items; packed launches take them in pairs
-                    const int64_t ranks_per = pk ? 2 * (max_items / nq) : max_items / nq;
-                    int64_t strips = 1;
-                    for (int64_t t = qa; t < qa + nq; ++t) strips = std::max<int64_t>(strips, f.table[(size_t)t].nstrips);
-                    for (int64_t r0 = 0; r0 < j.nonempty; r0 += ranks_per) {
-                        PrefilterLaunch l;
-                        l.group = (int)g; l.C = C; l.kernel = kernel; l.packed = pk;
-                        l.q0 = qa; l.nq = nq;
-                        l.rank0 = r0; l.nranks = std::min(ranks_per, j.nonempty - r0);
-                        l.items = l.nq * (pk ? (l.nranks + 1) / 2 : l.nranks);
-                        l.bnd_per = 2 * boundary_ints(strips, j.longest);
-                        l.grid = std::min<int64_t>((int64_t)j.per_cu[kernel] * j.num_cus, (l.items + 3) / 4);
-                        if (l.bnd_per) l.grid = std::min<int64_t>(l.grid, kSearchBndBytes / (l.bnd_per * 4 * 4));
-                        l.grid = std::max<int64_t>(1, l.grid);
-                        f.bnd_need = std::max(f.bnd_need, (size_t)(l.grid * 4 * l.bnd_per));
-                        f.packed_launches += pk;
-                        f.launch.push_back(l);
-                    }
-                    qa += nq;
-                }
-            }
-            a = b;
+    for (size_t g = 0; g < y.group.size(); ++g)
+        for (int k = 0; k < kQueryClasses; ++k) {
+            const QueryClass& c = y.group[g].cls[k];
+            const int C = class_columns(k), pk = prefilter_kernel_index(C, true), w32 = prefilter_kernel_index(C, false);
+            const int64_t mid = packed_first(y.table, c.q0, c.q0 + c.nq, packed);
+            f.packed_launches += cut_rank_launches(f.launch, f.bnd_need, y.table, r, (int)g, C, pk, j.per_cu[pk], true, c.q0, mid);
+            cut_rank_launches(f.launch, f.bnd_need, y.table, r, (int)g, C, w32, j.per_cu[w32], false, mid, c.q0 + c.nq);
         }
-    }
+    take_layout(f, y);
     return f;
 }
 
-// The many-query search with a choice of lanes.  The table and the groups come from plan_search_multi itself (asked for a handle without
-// targets, it plans no launch), with the 32-bit kernels' occupancy, so the classes do not depend on the lanes; per (group, class) the
-// packed queries move to the front, every entry keeping its profile's place.  With no packed query every class is one part, and the
-// loops below are plan_search_multi's.
+// The many-query search with a choice of lanes: plan_prefilter's shape with search_multi_packed's rule.  The classes come from the
+// 32-bit kernels' occupancy, so they do not depend on the lanes; with no packed query every class is one part and the launches are
+// plan_search_multi's.
 SearchMultiLanesPlan plan_search_multi_lanes(const SearchMultiLanesJob& j) {
     SearchMultiLanesPlan f;
-    SearchMultiJob mj = j;
-    mj.nonempty = 0;
-    SearchMultiPlan m = plan_search_multi(mj);
-    f.table = std::move(m.table);
-    f.group = std::move(m.group);
-    f.prof_need = m.prof_need;
-    const int64_t max_items = std::max<int64_t>(1, std::min(j.max_items, kMultiMaxItems));
-    auto klass = [](const swk::MultiQuery& d) { return d.qpad / d.nstrips / 64 / 8; };   // columns per lane 4, 8, 16 -> 0, 1, 2
-    for (size_t g = 0; g < f.group.size(); ++g) {
-        const int64_t g0 = f.group[g].q0, g1 = g0 + f.group[g].nq;
-        for (int64_t a = g0; a < g1;) {
-            const int k = klass(f.table[(size_t)a]), C = k == 0 ? 4 : 8 * k;
-            int64_t b = a;
-            while (b < g1 && klass(f.table[(size_t)b]) == k) ++b;
-            // (the packed kernel of 16 columns per lane is taken where it keeps the workgroups on a CU that the 32-bit one needs)
-            const bool fits = j.packed_per_cu[k] >= (C == 16 ? kAffineC16MinPerCu : 1);
+    QueryLayout y = layout_queries(j.qlens, j.nqueries, j.per_cu[search_multi_kernel_index(16)], j.budget_bytes);
+    const Ranks r = ranks_of(j);
+    for (size_t g = 0; g < y.group.size(); ++g)
+        for (int k = 0; k < kQueryClasses; ++k) {
+            const QueryClass& c = y.group[g].cls[k];
+            const bool fits = packed_kernel_fits(j.packed_per_cu, k);
             auto packed = [&](const swk::MultiQuery& d) { return fits && search_multi_packed(j.max_entry, d.qlen, j.longest, j.gap_open, j.gap_extend, j.lanes); };
-            const int64_t mid = std::stable_partition(f.table.begin() + a, f.table.begin() + b, packed) - f.table.begin();
-            for (int side = 0; side < 2 && j.nonempty > 0; ++side) {
-                const bool pk = side == 0;
-                const int64_t s0 = pk ? a : mid, s1 = pk ? mid : b;
-                const int per_cu = pk ? j.packed_per_cu[k] : j.per_cu[k];
-                for (int64_t qa = s0; qa < s1;) {
-                    const int64_t nq = std::min(s1 - qa, max_items);
-                    // target ranks of a launch: as many as keep its items inside max_items; packed launches take them in pairs
-                    const int64_t ranks_per = pk ? 2 * (max_items / nq) : max_items / nq;
-                    int64_t strips = 1;
-                    for (int64_t t = qa; t < qa + nq; ++t) strips = std::max<int64_t>(strips, f.table[(size_t)t].nstrips);
-                    for (int64_t r0 = 0; r0 < j.nonempty; r0 += ranks_per) {
-                        MultiLanesLaunch l;
-                        l.group = (int)g; l.C = C; l.kernel = k; l.packed = pk;
-                        l.q0 = qa; l.nq = nq;
-                        l.rank0 = r0; l.nranks = std::min(ranks_per, j.nonempty - r0);
-                        l.items = l.nq * (pk ? (l.nranks + 1) / 2 : l.nranks);
-                        l.bnd_per = 2 * boundary_ints(strips, j.longest);
-                        l.grid = std::min<int64_t>((int64_t)per_cu * j.num_cus, (l.items + 3) / 4);
-                        if (l.bnd_per) l.grid = std::min<int64_t>(l.grid, kSearchBndBytes / (l.bnd_per * 4 * 4));
-                        l.grid = std::max<int64_t>(1, l.grid);
-                        f.bnd_need = std::max(f.bnd_need, (size_t)(l.grid * 4 * l.bnd_per));
-                        f.packed_launches += pk;
-                        f.launch.push_back(l);
-                    }
-                    qa += nq;
-                }
-            }
-            a = b;
+            const int64_t mid = packed_first(y.table, c.q0, c.q0 + c.nq, packed);
+            f.packed_launches += cut_rank_launches(f.launch, f.bnd_need, y.table, r, (int)g, class_columns(k), k, j.packed_per_cu[k], true, c.q0, mid);
+            cut_rank_launches(f.launch, f.bnd_need, y.table, r, (int)g, class_columns(k), k, j.per_cu[k], false, mid, c.q0 + c.nq);
         }
-    }
+    take_layout(f, y);
     return f;
 }
 
@@ -630,13 +629,10 @@ SearchPairsLanesPlan plan_search_pairs_lanes(const SearchPairsLanesJob& j) {
         static_cast<PairsGroup&>(grp) = s.group[g];
         int64_t npacked = 0;
         for (int k = 0; k < kSearchPairsKernels; ++k) {
-            const int64_t a = grp.cls_q0[k], b = grp.cls_q0[k + 1];
-            const int C = k == 0 ? 4 : 8 * k;
-            // (the packed kernel of 16 columns per lane is taken where it keeps the workgroups on a CU that the 32-bit one needs)
-            const bool fits = j.packed_per_cu[k] >= (C == 16 ? kAffineC16MinPerCu : 1);
+            const bool fits = packed_kernel_fits(j.packed_per_cu, k);
             auto packed = [&](const swk::MultiQuery& d) { return fits && search_multi_packed(j.max_entry, d.qlen, j.longest, j.gap_open, j.gap_extend, j.lanes); };
-            grp.pk_q1[k] = std::stable_partition(f.table.begin() + a, f.table.begin() + b, packed) - f.table.begin();
-            npacked += grp.pk_q1[k] - a;
+            grp.pk_q1[k] = packed_first(f.table, grp.cls_q0[k], grp.cls_q0[k + 1], packed);
+            npacked += grp.pk_q1[k] - grp.cls_q0[k];
         }
         grp.cells = kSearchPairsBuckets * npacked;
         binning += npacked ? 3 : 2;
@@ -655,9 +651,7 @@ SearchPairsLanesPlan plan_search_pairs_lanes(const SearchPairsLanesJob& j) {
                 l.nq = (pk ? grp.pk_q1[k] : grp.cls_q0[k + 1]) - l.q0;
                 if (l.nq == 0) continue;
                 if (pk) {   // the waves the packed kernel keeps resident, under the class's boundary column
-                    l.max_grid = (int64_t)j.packed_per_cu[k] * j.num_cus;
-                    if (l.bnd_per) l.max_grid = std::min<int64_t>(l.max_grid, kSearchBndBytes / (l.bnd_per * 4 * 4));
-                    l.max_grid = std::max<int64_t>(1, l.max_grid);
+                    l.max_grid = grid_cap(j.packed_per_cu[k], j.num_cus, l.bnd_per);
                     f.bnd_need = std::max(f.bnd_need, (size_t)(search_pairs_lanes_grid(l, most, grp.cells) * 4 * l.bnd_per));
                     ++f.packed_launches;
                 }
@@ -733,29 +727,6 @@ TopPairsPlan plan_top_pairs(const TopPairsJob& j) {
 // reasons (plan_search_affine).  A slot is a whole direction matrix of the longest hit, so that any hit runs in any slot; the waves
 // take hits from a counter, longest first, and a call with more hits than slots simply keeps its waves busy longer.
 
-AlignAffinePlan plan_align_affine(const AlignAffineJob& j) {
-    using swk::SW_SEARCH_ROWS;
-    AlignAffinePlan a;
-    a.C = lane_columns(j.qlen);
-    if (a.C == 16 && j.per_cu[align_affine_kernel_index(16)] < kAffineC16MinPerCu) a.C = 8;
-    a.kernel = align_affine_kernel_index(a.C);
-    a.nstrips = (j.qlen + 64 * a.C - 1) / (64 * a.C);
-    a.qpad = a.nstrips * 64 * a.C;
-    a.bnd_per = 2 * boundary_ints(a.nstrips, j.maxhit);
-    a.slot_bytes = std::max<int64_t>(1, j.maxhit) * a.qpad;
-    a.fits = a.slot_bytes <= j.budget_bytes && a.slot_bytes <= kAlignSlotLimit;
-    a.prof_need = (size_t)(SW_SEARCH_ROWS * a.qpad);
-    a.prof_blocks = (int)std::min<int64_t>((SW_SEARCH_ROWS * a.qpad + 255) / 256, kProfileBlocks);
-    if (!a.fits) return a;
-    a.slots = std::min<int64_t>({j.nhits, (int64_t)j.per_cu[a.kernel] * j.num_cus * 4, j.budget_bytes / a.slot_bytes});
-    if (a.bnd_per) a.slots = std::min<int64_t>(a.slots, kSearchBndBytes / (a.bnd_per * 4));
-    a.slots = std::max<int64_t>(1, a.slots);
-    a.grid = (a.slots + 3) / 4;
-    a.bnd_need = (size_t)(a.slots * a.bnd_per);
-    a.dir_need = (size_t)(a.slots * a.slot_bytes);
-    return a;
-}
-
 AlignCkptBand align_ckpt_band(int64_t len, int64_t qpad, int64_t forced_rows, int64_t budget_bytes) {
     AlignCkptBand best;
     for (int64_t B = forced_rows ? forced_rows : kAlignCkptFloorRows; B <= (forced_rows ? forced_rows : kAlignCkptMaxRows); B *= 2) {
@@ -767,47 +738,48 @@ AlignCkptBand align_ckpt_band(int64_t len, int64_t qpad, int64_t forced_rows, in
     return best;
 }
 
-// plan_align_affine with the slot of align_ckpt_band and a boundary column of one band's rows.
-AlignCkptPlan plan_align_ckpt(const AlignCkptJob& j) {
+// One query's hits.  ckpt: the slot is align_ckpt_band's and a boundary column is one band's (plan_align_ckpt).
+static AlignCkptPlan plan_align_one(const AlignAffineJob& j, bool ckpt, int64_t band_rows) {
     using swk::SW_SEARCH_ROWS;
     AlignCkptPlan a;
-    a.C = lane_columns(j.qlen);
-    if (a.C == 16 && j.per_cu[align_affine_kernel_index(16)] < kAffineC16MinPerCu) a.C = 8;
+    a.C = query_columns(j.qlen, j.per_cu[align_affine_kernel_index(16)]);
     a.kernel = align_affine_kernel_index(a.C);
     a.nstrips = (j.qlen + 64 * a.C - 1) / (64 * a.C);
     a.qpad = a.nstrips * 64 * a.C;
-    const AlignCkptBand band = align_ckpt_band(j.maxhit, a.qpad, j.band_rows, j.budget_bytes);
-    a.band_rows = band.rows; a.log_band = band.log_rows;
-    a.bnd_per = 2 * boundary_ints(a.nstrips, std::min(band.rows, std::max<int64_t>(1, j.maxhit)));
-    a.slot_bytes = band.slot_bytes;
-    a.fits = band.fits;
+    const int64_t rows = std::max<int64_t>(1, j.maxhit);
+    if (ckpt) {
+        const AlignCkptBand band = align_ckpt_band(j.maxhit, a.qpad, band_rows, j.budget_bytes);
+        a.band_rows = band.rows; a.log_band = band.log_rows;
+        a.bnd_per = 2 * boundary_ints(a.nstrips, std::min(band.rows, rows));
+        a.slot_bytes = band.slot_bytes;
+        a.fits = band.fits;
+    } else {
+        a.bnd_per = 2 * boundary_ints(a.nstrips, j.maxhit);
+        a.slot_bytes = rows * a.qpad;
+        a.fits = a.slot_bytes <= j.budget_bytes && a.slot_bytes <= kAlignSlotLimit;
+    }
     a.prof_need = (size_t)(SW_SEARCH_ROWS * a.qpad);
     a.prof_blocks = (int)std::min<int64_t>((SW_SEARCH_ROWS * a.qpad + 255) / 256, kProfileBlocks);
     if (!a.fits) return a;
-    a.slots = std::min<int64_t>({j.nhits, (int64_t)j.per_cu[a.kernel] * j.num_cus * 4, j.budget_bytes / a.slot_bytes});
-    if (a.bnd_per) a.slots = std::min<int64_t>(a.slots, kSearchBndBytes / (a.bnd_per * 4));
-    a.slots = std::max<int64_t>(1, a.slots);
+    a.slots = slot_cap(j.nhits, j.per_cu[a.kernel], j.num_cus, j.budget_bytes, a.slot_bytes, a.bnd_per);
     a.grid = (a.slots + 3) / 4;
     a.bnd_need = (size_t)(a.slots * a.bnd_per);
     a.dir_need = (size_t)(a.slots * a.slot_bytes);
     return a;
 }
 
-// The hits of many queries from a device table.  Host work is O(nqueries): the loop of plan_search_multi over the queries, with the
-// entry bound as a second reason to close a group, and per group a constant number of tiers and launches.  Nothing here depends on
-// which targets the table names; the counts of items are products of int64 counts, never sums over items.
+AlignAffinePlan plan_align_affine(const AlignAffineJob& j) { return plan_align_one(j, false, 0); }
+AlignCkptPlan plan_align_ckpt(const AlignCkptJob& j) { return plan_align_one(j, true, j.band_rows); }
+
+// The hits of many queries from a device table.  Host work is O(nqueries): layout_queries with the entry bound as a second reason to
+// close a group, and per group a constant number of tiers and launches.  Nothing here depends on which targets the table names; the
+// counts of items are products of int64 counts, never sums over items.
 // ckpt: the sizes are align_ckpt_slot_bytes at the class's band height instead of len x qpad (plan_align_hits_ckpt).
 static AlignHitsPlan plan_align_hits_sized(const AlignHitsJob& j, bool ckpt, int64_t band_rows) {
-    using swk::SW_SEARCH_ROWS;
     AlignHitsPlan a;
     const int64_t n = j.nqueries, top = std::max<int64_t>(1, j.top), rows = std::max<int64_t>(1, j.longest);
-    auto columns = [&](int64_t qlen) {
-        int C = lane_columns(qlen);
-        if (C == 16 && j.per_cu[align_hits_kernel_index(16)] < kAffineC16MinPerCu) C = 8;
-        return C;
-    };
-    auto padded = [&](int64_t qlen) { const int64_t w = 64 * columns(qlen); return (qlen + w - 1) / w * w; };
-    for (int64_t q = 0; q < n; ++q) a.worst_qpad = std::max(a.worst_qpad, padded(j.qlens[q]));
+    const int per_cu16 = j.per_cu[align_hits_kernel_index(16)];
+    for (int64_t q = 0; q < n; ++q) a.worst_qpad = std::max(a.worst_qpad, query_padded(j.qlens[q], per_cu16));
     if (ckpt) {   // (a slot grows with qpad at every band height: the widest query's smallest slot is the call's worst)
         const AlignCkptBand worst = align_ckpt_band(rows, a.worst_qpad, band_rows, j.budget_bytes);
         a.worst_bytes = worst.slot_bytes;
@@ -817,38 +789,20 @@ static AlignHitsPlan plan_align_hits_sized(const AlignHitsJob& j, bool ckpt, int
         a.fits = a.worst_bytes <= j.budget_bytes && a.worst_bytes <= kAlignSlotLimit;
     }
     if (!a.fits) return a;
-    a.table.resize((size_t)n);
-    const int64_t group_queries = std::max<int64_t>(1, std::max<int64_t>(1, j.max_items) / top);
-    for (int64_t g0 = 0; g0 < n;) {
-        int64_t g1 = g0, bytes = 0;
-        while (g1 < n && (g1 == g0 || (g1 - g0 < group_queries && bytes + SW_SEARCH_ROWS * padded(j.qlens[g1]) <= j.profile_budget_bytes)))
-            bytes += SW_SEARCH_ROWS * padded(j.qlens[g1++]);
+    QueryLayout y = layout_queries(j.qlens, n, per_cu16, j.profile_budget_bytes, std::max<int64_t>(1, std::max<int64_t>(1, j.max_items) / top));
+    a.table = std::move(y.table);
+    a.prof_need = y.prof_need;
+    for (const QueryGroup& yg : y.group) {
         AlignHitsGroup grp;
-        grp.q0 = g0; grp.nq = g1 - g0; grp.prof_bytes = bytes;
-        a.prof_need = std::max(a.prof_need, (size_t)bytes);
+        grp.q0 = yg.q0; grp.nq = yg.nq; grp.prof_bytes = yg.prof_bytes;
         a.items_need = std::max(a.items_need, (size_t)(grp.nq * top));
-        // the table of the group: by class, input order within a class; the profiles lie in table order
-        int64_t at[kAlignHitsKernels + 1] = {};
-        for (int64_t q = g0; q < g1; ++q) ++at[align_hits_kernel_index(columns(j.qlens[q])) + 1];
-        for (int k = 0; k < kAlignHitsKernels; ++k) at[k + 1] += at[k];
-        for (int k = 0; k < kAlignHitsKernels; ++k) {
-            grp.cls[k].q0 = g0 + at[k]; grp.cls[k].nq = at[k + 1] - at[k];
-            grp.cls[k].item0 = at[k] * top; grp.cls[k].entries = grp.cls[k].nq * top;
-        }
-        for (int64_t q = g0; q < g1; ++q) {
-            const int C = columns(j.qlens[q]), k = align_hits_kernel_index(C);
-            const int64_t qpad = padded(j.qlens[q]);
-            a.table[(size_t)(g0 + at[k]++)] = swk::MultiQuery{0, 0, q, (int32_t)j.qlens[q], (int32_t)qpad, (int32_t)(qpad / (64 * C)), 0};
-            grp.cls[k].qpad = std::max(grp.cls[k].qpad, qpad);
-            grp.cls[k].nstrips = std::max(grp.cls[k].nstrips, qpad / (64 * C));
-        }
-        int64_t off = 0;
-        for (int64_t t = g0; t < g1; ++t) { a.table[(size_t)t].prof_off = off; off += SW_SEARCH_ROWS * a.table[(size_t)t].qpad; }
         // the tiers of every class and their launches, largest first
         for (int k = 0; k < kAlignHitsKernels; ++k) {
             AlignHitsClass& c = grp.cls[k];
+            c.q0 = yg.cls[k].q0; c.nq = yg.cls[k].nq; c.qpad = yg.cls[k].qpad; c.nstrips = yg.cls[k].nstrips;
+            c.item0 = (c.q0 - grp.q0) * top; c.entries = c.nq * top;
             if (c.nq == 0) continue;
-            const int C = k == 0 ? 4 : 8 * k;
+            const int C = class_columns(k);
             int64_t down[kAlignHitsTiers];
             const AlignCkptBand band = ckpt ? align_ckpt_band(rows, c.qpad, band_rows, j.budget_bytes) : AlignCkptBand{};
             c.log_band = band.log_rows;
@@ -864,9 +818,7 @@ static AlignHitsPlan plan_align_hits_sized(const AlignHitsJob& j, bool ckpt, int
                 // a query of several strips is at least two strips wide: that bounds the rows of a tier's items that cross a boundary
                 // (ckpt: a boundary column is one band's)
                 l.bnd_per = 2 * boundary_ints(c.nstrips, ckpt ? std::min(rows, band.rows) : std::min(rows, c.bound[t] / (2 * 64 * C)));
-                l.slots = std::min<int64_t>({c.entries, (int64_t)j.per_cu[k] * j.num_cus * 4, j.budget_bytes / l.slot_bytes});
-                if (l.bnd_per) l.slots = std::min<int64_t>(l.slots, kSearchBndBytes / (l.bnd_per * 4));
-                l.slots = std::max<int64_t>(1, l.slots);
+                l.slots = slot_cap(c.entries, j.per_cu[k], j.num_cus, j.budget_bytes, l.slot_bytes, l.bnd_per);
                 l.grid = (l.slots + 3) / 4;
                 a.bnd_need = std::max(a.bnd_need, (size_t)(l.slots * l.bnd_per));
                 a.dir_need = std::max(a.dir_need, (size_t)(l.slots * l.slot_bytes));
@@ -875,7 +827,6 @@ static AlignHitsPlan plan_align_hits_sized(const AlignHitsJob& j, bool ckpt, int
             }
         }
         a.group.push_back(grp);
-        g0 = g1;
     }
     a.tiers = (int64_t)a.launch.size();
     return a;
