@@ -564,7 +564,10 @@ int  sw_db_search_affine_top_prefiltered(sw_ctx* ctx, const sw_db* db, const cha
  * construction.  The 24-bit bound is smax x min(longest query, longest target) < 2^24, and gap_open + gap_extend >= -2^24 as before.
  * Compare sw_top_hits_device: there 0 <= max_score < 2^24 is a PRECONDITION the call cannot check on device data; here the same bound
  * is ENFORCED, whatever bytes d_pssm holds, and a hit table of sw_db_search_pssm_top meets that precondition.  A caller whose entries
- * all lie at or below smax loses nothing; smax = 127 clamps nothing.
+ * all lie at or below smax loses nothing; smax = 127 clamps nothing.  The three calls are tested at the edges of this rule as the
+ * table calls are at theirs -- entries of -128 and 127, other = -128 and other = smax, smax = 0, 1..256 letters with the bytes 0x00,
+ * 0x7F, 0x80 and 0xFF among them and among the bytes that score `other`, on 32-bit and packed 16-bit lanes
+ * (tests/test_pssm_range_gpu.py).
  * Asynchronous on `stream`, no host round trip; the host work of a call is O(nqueries) + O(nletters).  Every argument is checked before
  * the first launch.  "last_search_multi_*", "last_search_top_*" and "last_align_hits_*" describe these calls as they describe the twins.
  * SW_EINVAL: the argument errors of the twin; NULL d_pssm, scoring or letters; nletters outside 1..256; a byte twice in letters; smax
@@ -641,12 +644,14 @@ int  sw_read_pssm(const char* path, char* letters_out, int32_t* nletters, int8_t
  *   `letters` are not counted.  N[j] = sum over k of C[j][k].  A walk visits a column at most once: N[j] <= 4096 x 65535 < 2^28.
  * NEW ENTRY.  den = prior_weight + N[j].  den == 0: out[j][k] = P[j][k].  Otherwise, in int64,
  *   num = prior_weight x P[j][k] + sum over b of C[j][b] x S[b][k],   out[j][k] = clamp(floor((2 num + den) / (2 den)), -128, 127):
- *   round half up with FLOOR division (C's '/' truncates toward zero, which differs for negative numerators).
+ *   round half up with FLOOR division (C's '/' truncates toward zero, which differs for negative numerators).  num reaches
+ *   4096 x 65535 x 127 = 3.4e10; tests/test_pssm_hits_gpu.py runs sums beyond 2^32, exact halves of both signs there and both clamps.
  * Integer sums do not depend on their order: the same bytes come out on every run.
  * Asynchronous on `stream`, no host round trip: the host reads none of the device tables; its work is O(nqueries) + O(nletters^2) (S).
  * One small table (S, the code table, the offsets) is uploaded from pinned memory; the context holds TWO such copies and uses them in turn,
  * so a call waits on the host only for the upload of the call before the last one -- a loop can be enqueued one call ahead of the
  * device.  (The search and alignment calls of the loop keep one pinned copy each and wait for their own previous upload, as ever.)
+ * tests/test_session_gpu.py enqueues five such calls of different shapes in a row on two streams, unsynchronised.
  * nqueries == 0 launches nothing; a handle with ntargets == 0 uses no entry: the clamped prior comes out and the counts are zero.
  * One launch: one workgroup per (query, tile of columns), a tile's counts in LDS, no global atomics (swp::plan_pssm_hits cuts the
  * tiles).  "last_pssm_hits_launches" reports the kernel launches of the last call.

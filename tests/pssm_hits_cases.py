@@ -24,12 +24,17 @@ def letters_of(rng, n):
     return np.concatenate([PROTEIN, rng.permutation(rest)[:n - len(PROTEIN)]]).astype(np.uint8)
 
 
-def reference(c, prior_weight, include_min, weights=None):
-    """(new matrix int8 in the layout of c.prior, counts int32 rebased to the first query, used (nq, top) bool) by the rule of the header."""
+def reference(c, prior_weight, include_min, weights=None, code=None):
+    """(new matrix int8 in the layout of c.prior, counts int32 rebased to the first query, used (nq, top) bool) by the rule of the header.
+    code: 256 places to take in the place of the letters' own -- what a call would count had it read another call's code table (a
+    place outside the letters counts nothing); the session tests ask that."""
     nl, nq, top = len(c.letters), len(c.qoffs) - 1, c.hits.shape[1]
     ntargets = len(c.offs) - 1
-    code = np.full(256, -1, np.int64)
-    code[c.letters] = np.arange(nl)
+    if code is None:
+        code = np.full(256, -1, np.int64)
+        code[c.letters] = np.arange(nl)
+    else:
+        code = np.where((np.asarray(code, np.int64) >= 0) & (np.asarray(code, np.int64) < nl), np.asarray(code, np.int64), -1)
     S = c.sub[np.ix_(c.letters, c.letters)].astype(np.int64)             # S[b][k]: the observed residue plays the query letter
     P = np.minimum(c.prior.astype(np.int64), c.smax)
     out = c.prior.astype(np.int64).copy()
@@ -185,13 +190,13 @@ def mutate(rng, seq, alpha):
     return np.array(out, np.uint8)
 
 
-def homologue_database(rng, queries, nrandom, copies=3):
+def homologue_database(rng, queries, nrandom, copies=3, alpha=PROTEIN[:20]):
     """Random protein targets of 0..600 letters with `copies` mutated copies of every query planted inside flanks."""
-    targets = [rng.choice(PROTEIN[:20], int(n)).astype(np.uint8) for n in [0, 1, 63, 64, 65, 0] + list(rng.integers(2, 601, nrandom))]
+    targets = [rng.choice(alpha, int(n)).astype(np.uint8) for n in [0, 1, 63, 64, 65, 0] + list(rng.integers(2, 601, nrandom))]
     for qs in queries:
         for _ in range(copies):
-            targets.append(np.concatenate([rng.choice(PROTEIN[:20], int(rng.integers(0, 40))).astype(np.uint8), mutate(rng, qs, PROTEIN[:20]),
-                                           rng.choice(PROTEIN[:20], int(rng.integers(0, 40))).astype(np.uint8)]))
+            targets.append(np.concatenate([rng.choice(alpha, int(rng.integers(0, 40))).astype(np.uint8), mutate(rng, qs, alpha),
+                                           rng.choice(alpha, int(rng.integers(0, 40))).astype(np.uint8)]))
     order = rng.permutation(len(targets))
     targets = [targets[k] for k in order]
     offs = np.concatenate([[7], 7 + np.cumsum([len(t) for t in targets])]).astype(np.int64)
@@ -199,14 +204,16 @@ def homologue_database(rng, queries, nrandom, copies=3):
     return packed, offs
 
 
-def real(swamd, rng, top, qlens=QLENS, nrandom=40, nletters=24):
-    """Iteration 0 of a search on the host: sequence queries through sw_pssm_from_queries, the search, the rank order, the alignment."""
+def real(swamd, rng, top, qlens=QLENS, nrandom=40, nletters=24, alpha=PROTEIN[:20], sub=None):
+    """Iteration 0 of a search on the host: sequence queries through sw_pssm_from_queries, the search, the rank order, the alignment.
+    alpha: the letters the sequences are drawn from; sub: the table (default: a random symmetric one)."""
     from pssm_cases import rank_order
     letters = letters_of(rng, nletters)
-    queries = [rng.choice(PROTEIN[:20], n).astype(np.uint8) for n in qlens]
-    packed, offs = homologue_database(rng, queries, nrandom)
-    sub = random_submat(rng, lo=-6, hi=8)
-    sub = np.minimum(sub, sub.T)                                            # (symmetric, as real tables are; nothing depends on it)
+    queries = [rng.choice(alpha, n).astype(np.uint8) for n in qlens]
+    packed, offs = homologue_database(rng, queries, nrandom, alpha=alpha)
+    if sub is None:
+        sub = random_submat(rng, lo=-6, hi=8)
+        sub = np.minimum(sub, sub.T)                                        # (symmetric, as real tables are; nothing depends on it)
     c = _case(rng, letters, 127, qlens, packed, offs, top, sub=sub)
     m, moffs = swamd.pssm_from_queries(queries, sub, letters)
     c.prior[QFRONT:] = m
@@ -263,3 +270,119 @@ def host_leg(swamd, c, prior_weight, include_min, weights=None, want_out=True, w
         assert (counts == 0x55555555).all()
     return (out[GUARD + front:GUARD + total].reshape(-1, nl).copy() if want_out else None,
             counts[GUARD:GUARD + ncnt].reshape(-1, nl).copy() if want_counts else None)
+
+
+# ---- the update at its arithmetic edges ----
+
+def all_m_case(svals, parts, prior, smax=127, ncols=65):
+    """One query of ncols columns over len(svals) letters, top = sum(parts): `parts[b]` entries name target b, ncols x letter b, and pair
+    every column with it from (0, 0) through ncols 'M'; row b of S is svals[b] at every k.  So every column has C[j][b] = parts[b] x w
+    and the same new row, whose entries are all equal.  prior: one value for every entry."""
+    rng = np.random.default_rng(len(svals) + sum(parts))
+    nl, top = len(svals), int(sum(parts))
+    letters = PROTEIN[:nl].copy()
+    offs = np.concatenate([[7], 7 + ncols * np.arange(1, nl + 1)]).astype(np.int64)
+    packed = np.concatenate([rng.choice(PROTEIN, 7).astype(np.uint8)] + [np.full(ncols, x, np.uint8) for x in letters])
+    c = _case(rng, letters, smax, [ncols], packed, offs, top)
+    c.prior[:] = prior
+    c.sub = rng.integers(-128, 128, (256, 256)).astype(np.int8)
+    for b, s in enumerate(svals):
+        c.sub[letters[b], :] = s
+    c.hits[0, :, 0] = np.repeat(np.arange(nl), parts)
+    c.aln[0, :] = (0, 5, 0, 0, 0, 0, ncols)
+    c.cap = ncols
+    c.ops = np.full((top, ncols), M, np.uint8)
+    return c
+
+
+def overflow_case(first=2048):
+    """65 columns, 3 letters, top = 4096 at weight 65535: `first` entries pair every column with the letter whose row of S is 127, the
+    others with the one whose row is -128.  (case, weights).  C x S passes 2^31 and N[j] is the largest the header allows; with equal
+    halves num is an exact -1/2 of den, with unequal ones num itself passes 2^32 and a sum kept in 32 bits has another sign."""
+    c = all_m_case([127, -128, 5], [first, 4096 - first, 0], prior=3)
+    c.prior[:, 0], c.prior[:, 2] = -3, -77                # rows [-3, 3, -77]: both signs beside the half
+    w = np.full((1, 4096), 65535, np.int32)
+    front = int(c.qoffs[0])
+    S = c.sub[np.ix_(c.letters, c.letters)].astype(np.int64)
+    for pw in (0, 1, 65535):
+        out, counts, used = reference(c, pw, 0, w)
+        C = counts.astype(np.int64)
+        assert used.all() and (C.sum(axis=1) == 4096 * 65535).all() and 4096 * 65535 < 2**28
+        assert (np.abs(C[:, :, None] * S[None, :, :]) > 2**31).any()
+        assert out[front:].min() > -128 and out[front:].max() < 127                     # at no clamp
+        total = (C @ S)[0, 0]
+        if first == 2048:
+            assert 2 * total == -4096 * 65535 and (pw > 0 or not out[front:].any())     # the exact half -1/2 rounds up to 0
+        else:
+            wrapped = (int(total) + 2**31) % 2**32 - 2**31
+            assert abs(total) > 2**32 and (wrapped < 0) != (total < 0) and abs(int(out[front, 0])) > 30
+    return c, w
+
+
+def clamp_case(s, smax):
+    """Five letters, S == s everywhere and a prior of -128 everywhere: an observed column gives s under prior_weight 0 (127 and -128 are
+    the two clamps), an unobserved one min(-128, smax) = -128."""
+    rng = np.random.default_rng(1000 + s + smax)
+    c = synthetic(rng, 5, 3, smax=smax)
+    c.prior[:] = -128
+    c.sub = np.full((256, 256), s, np.int8)
+    front = int(c.qoffs[0])
+    out, counts, _ = reference(c, 0, 0)
+    seen = counts.sum(axis=1) > 0
+    assert seen.any() and not seen.all() and (out[front:][seen] == s).all() and (out[front:][~seen] == -128).all()
+    return c
+
+
+ROUNDING = [                 # (prior_weight, prior, S per letter, entries per letter, weight, expected entry)
+    (0, 0, (127, 126), (2048, 2048), 65535, 127),          # 126.5: an exact half, num = 3.4e10
+    (0, 0, (-127, -128), (2048, 2048), 65535, -127),       # -127.5 -> -127, num = -3.4e10
+    (0, 0, (-127, -128), (1024, 3072), 65535, -128),       # -127.75 -> -128; truncating (2 num + den) / (2 den) = -127.25 would give -127
+    (0, 0, (127, 126), (1024, 3072), 65535, 126),          # 126.25
+    (65535, -128, (-127, -128), (2048, 2047), 65535, -127),   # -127.5 exactly, the prior's share (65535 x -128) included
+    (1, 127, (100, -100), (2048, 2048), 65535, 0),         # 127 / den: just above 0
+    (1, -127, (100, -100), (2048, 2048), 65535, 0),        # -127 / den: just below 0 and far above -1/2
+    (1, -128, (1, -2), (2048, 2048), 65535, -1),           # (-128 - 2048 x 65535) / (1 + 4096 x 65535): a hair BELOW -1/2 -> -1
+    (1, 127, (1, -2), (2048, 2048), 65535, 0),             # ... and a hair above it -> 0
+    (0, 0, (1, -2), (2048, 2048), 65535, 0),               # -1/2 exactly -> 0
+    (0, 0, (-1, -2), (2048, 2048), 65535, -1),             # -3/2 exactly -> -1
+]
+
+
+def rounding_case(pw, prior, svals, parts, weight, exp):
+    """One column; (case, weights).  The expected entry is checked here against the header's formula in Python integers."""
+    c = all_m_case(list(svals), list(parts), prior=prior, ncols=1)
+    num = pw * prior + sum(n * weight * s for n, s in zip(parts, svals))
+    den = pw + sum(parts) * weight
+    assert exp == max(-128, min(127, (2 * num + den) // (2 * den))), (num, den)
+    return c, np.full((1, sum(parts)), weight, np.int32)
+
+
+def alphabet_case(rng, nletters, top):
+    """synthetic() at another alphabet.  At 255 letters the one byte that is no letter stands at every third place of the targets (code
+    255: "none"), at 256 letters the letter at place 255 does (code 255: a letter): (case, the counts of that byte's pairs)."""
+    c = synthetic(rng, nletters, top)
+    if nletters < 255:
+        return c, None
+    byte = np.setdiff1d(np.arange(256, dtype=np.uint8), c.letters)[0] if nletters == 255 else c.letters[255]
+    c.packed[::3] = byte
+    if nletters == 256:
+        at = reference(c, 1, 0)[1][:, 255]
+        assert at.sum() > 0                                    # the letter at place 255 is paired and counted
+        return c, at
+    wide = types.SimpleNamespace(**vars(c))
+    wide.letters = np.concatenate([c.letters, [byte]]).astype(np.uint8)
+    wide.prior = np.concatenate([c.prior, c.prior[:, :1]], axis=1)
+    counts, wcounts = reference(c, 1, 0)[1], reference(wide, 1, 0)[1]
+    assert wcounts[:, 255].sum() > 0                           # some 'M' pairs the missing byte ...
+    assert (counts == wcounts[:, :255]).all()                  # ... and nothing is counted for it
+    return c, wcounts[:, 255]
+
+
+def full_range_case(rng, nletters, top, smax):
+    """synthetic() with S from the full-range table of tests/affine_range_cases.py and a prior uniform over -128 .. 127."""
+    import affine_range_cases as arc
+    c = synthetic(rng, nletters, top, smax=smax)
+    c.sub = arc.table("full8").copy()
+    c.prior = rng.integers(-128, 128, c.prior.shape).astype(np.int8)
+    assert c.prior.min() == -128 and c.prior.max() == 127
+    return c

@@ -7,7 +7,10 @@ read-only afterwards.
 A step names its call, its database, its query set (or its matrices), a scoring of its own, the stream (0 or 1) and the options to set
 just before it.  Every table call brings a table no other step of its pass uses and the second pass brings a second set, so a step
 that scored with what an earlier call left in a shared buffer gives a different table: test_session_host.py asserts that on the
-references alone."""
+references alone.
+
+ITERATING, at the end of this file, is a fourth session of steps of other kinds -- sw_db_pssm_from_hits five times in a row, and the
+packed routes of the pair list and the pre-filter -- as data of its own; the three sessions above keep their step lists."""
 import functools
 
 import numpy as np
@@ -371,3 +374,113 @@ def ungapped_differs(step, prev_table, u, only=None):
         if not any(len(t) and ungapped_score(q, t, prev_table) != u[a, b] for b, t in enumerate(d["targets"])):
             return False
     return True
+
+
+# ---- the fourth session: updates back to back ----
+#
+# sw_db_pssm_from_hits stages S, the code table and the offsets through two pinned copies used in turn and one device table that grows,
+# so update N + 2 rewrites the copy of update N.  ITERATING is the order of the calls of one fresh context; the five updates stand in a
+# row on alternating streams, their worlds hold 4, 24, 256, 4 and 24 letters (the device table grows before the second and before the
+# third), and every one has an S, an order of the letters, offsets, a number of queries, a top and a prior weight of its own.
+
+UPDATE_NLETTERS = [4, 24, 256, 4, 24]
+UPDATE_QLENS = [[30, 90, 50, 60, 33, 47], [63, 64, 65, 129, 257], [1, 300, 513, 64], [257, 65, 600], [200, 256]]
+UPDATE_TOPS = [5, 7, 9, 12, 20]
+UPDATE_PW = [2, 1, 3, 0, 5]
+ITERATING = (("pssm_top", 0), ("pairs16", 1), ("align", 0), ("prefilter16", 1), ("update0", 0), ("update1", 1), ("update2", 0), ("update3", 1),
+             ("update4", 0), ("pssm_top_again", 1))                          # (step, stream)
+ITER_MIN_SCORE, ITER_TOP_AGAIN = 1, 3
+
+_iterating = {}
+
+
+def iterating(swamd):
+    """The data of the session: {"worlds": the five cases of tests/pssm_hits_cases.py (worlds[0] holds the host legs' iteration 0 over a
+    four-letter database with planted homologues -- test_session_host.py checks those tables against the checker --, the others
+    synthetic tables), "pairs": the pair list of the packed pair step over db200 / "seven" / lanes_cases.table24(), "prefilter_min"}."""
+    if not _iterating:
+        import pssm_hits_cases as phc
+        worlds = []
+        for k, (nl, qlens, top) in enumerate(zip(UPDATE_NLETTERS, UPDATE_QLENS, UPDATE_TOPS)):
+            rng = np.random.default_rng(5600 + k)
+            if k == 0:
+                alpha = PROTEIN[:4]
+                sub = np.full((256, 256), -4, np.int8)
+                sub[np.ix_(alpha, alpha)] = rng.integers(-4, 0, (4, 4))
+                sub[alpha, alpha] = rng.integers(5, 10, 4)
+                sub = np.minimum(sub, sub.T)
+                c = phc.real(swamd, rng, top, qlens=qlens, nrandom=30, nletters=4, alpha=alpha, sub=sub)
+                order = np.arange(4)                               # (the prior's columns follow the letters: the order stays)
+            else:
+                c = phc.synthetic(rng, nl, top, qlens=qlens)
+                order = rng.permutation(nl)
+            c.letters = c.letters[order]
+            c.pw, c.inc = UPDATE_PW[k], 0
+            worlds.append(c)
+        rng = np.random.default_rng(5650)
+        pairs = np.stack([rng.integers(0, len(lc.QLENS), 150), rng.integers(0, 200, 150)], axis=1).astype(np.int64)
+        pairs[140:] = -1
+        pairs[100:110] = pairs[:10]
+        _frozen(pairs)
+        _iterating.update(worlds=worlds, pairs=pairs)
+    return _iterating
+
+
+def code_of(letters):
+    """The place of every byte among the letters, -1 for a byte that is not among them."""
+    code = np.full(256, -1, np.int64)
+    code[letters] = np.arange(len(letters))
+    return code
+
+
+def update_expected(c, sub=None, code=None, qoffs=None):
+    """The matrix the rule gives for update world c (tests/pssm_hits_cases.reference), or what it would give had the call taken another
+    call's S, code table or offsets."""
+    import types
+
+    import pssm_hits_cases as phc
+    v = types.SimpleNamespace(**vars(c))
+    if sub is not None:
+        v.sub = sub
+    if qoffs is not None:
+        v.qoffs = np.ascontiguousarray(qoffs[:len(c.qoffs)], np.int64)
+    return phc.reference(v, c.pw, c.inc, code=code)[0]
+
+
+def typed_of_matrix(m, letters, other, smax):
+    """A query of at most 256 columns as the checker takes it: every column a type of its own.  (type string, (256, 256) table)."""
+    assert len(m) <= 256
+    tab = np.full((256, 256), other, np.int8)
+    tab[:len(m), letters] = np.minimum(m, smax)
+    return np.arange(len(m), dtype=np.uint8), tab
+
+
+def iterating_search_again(checker, c, m):
+    """The checker's (nqueries, ntargets, 3) table of matrix m over the queries of world c (each of at most 256 columns)."""
+    import pssm_hits_cases as phc
+    _, other, smax, go, ge = phc.scoring(c)
+    out = []
+    for q in range(len(c.qoffs) - 1):
+        names, tab = typed_of_matrix(m[c.qoffs[q]:c.qoffs[q + 1]], c.letters, other, smax)
+        out.append(checker.search(names, c.packed, c.offs, tab, go, ge))
+    return np.stack(out)
+
+
+ITER_PREFILTER_MIN = 40
+
+
+@functools.lru_cache(maxsize=None)
+def iterating_prefilter():
+    """(U (40, 40), the sorted pairs that pass) of the packed pre-filter step: "forty" against db40 under lanes_cases.table24()."""
+    d, qs = databases()["db40"], query_sets()["forty"]
+    u = ungapped_table(qs["qpacked"], qs["qoffs"], d["packed"], d["offs"], packed_table(0))
+    pr = passing(u, d["offs"], ITER_PREFILTER_MIN)
+    _frozen(u, pr)
+    return u, pr
+
+
+def sequence_table(sub, letters, other, smax):
+    """The checker's table of a PSSM that sw_pssm_from_queries made of sequence queries under `sub`."""
+    tab = np.full((256, 256), other, np.int8)
+    tab[:, letters] = np.minimum(sub[:, letters], smax)
+    return tab

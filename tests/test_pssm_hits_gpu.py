@@ -1,7 +1,10 @@
 """GPU: the next iteration's PSSM built on the device (sw_db_pssm_from_hits) against its host leg, byte for byte on counts and matrix:
 the synthetic, garbage and real tables of tests/pssm_hits_cases.py, top = 4096 over a five-target database, a query longer than one
 tile, in place, counts only, matrix only, the same bytes on two runs, guard bytes and poisoned unused columns around every output --
-and the closed loop search -> align -> update -> search on one stream with no synchronisation in between against the host legs chained."""
+and the closed loop search -> align -> update -> search on one stream with no synchronisation in between against the host legs chained.
+The arithmetic edges (equal_to_reference: the device against the numpy rule directly, then against the host leg): products C x S of
+1.7e10 and sums beyond 2^32 at N[j] = 4096 x 65535, the rounding table at that magnitude, both clamps, unobserved columns, alphabets
+of 3, 5, 255 and 256 letters, S and prior over all of -128 .. 127 under smax 0, 1 and 127."""
 import numpy as np
 import pytest
 
@@ -127,6 +130,90 @@ def test_top_4096_over_five_targets(swamd, engine):
     _, cnt = equal_to_host(swamd, engine, c, 1, 0, weights_of(rng, 2, 4096))
     assert cnt.sum(axis=1).max() > 1000 * 65535 // 100   # a column that thousands of entries, many at weight 65535, added to
     assert cnt.sum(axis=1).max() < 2**28
+
+
+def equal_to_reference(swamd, engine, c, pw, inc, weights=None):
+    """The device against the numpy rule of tests/pssm_hits_cases.py directly, then equal_to_host (the host leg, in place, counts only,
+    matrix only, twice the same)."""
+    exp_out, exp_cnt, _ = cases.reference(c, pw, inc, weights)
+    exp_out = exp_out[int(c.qoffs[0]):]
+    with engine.prepare_db((c.packed, c.offs)) as db:
+        out, cnt = Device(engine, c, weights).run(db, pw, inc)
+    assert (cnt == exp_cnt).all(), f"{(cnt != exp_cnt).sum()} counts differ from the rule"
+    assert (out == exp_out).all(), f"{(out != exp_out).sum()} entries differ from the rule, first {np.argwhere(out != exp_out)[0].tolist()}: " \
+                                   f"{out[out != exp_out][0]} vs {exp_out[out != exp_out][0]}"
+    host_out, host_cnt = equal_to_host(swamd, engine, c, pw, inc, weights)
+    assert (host_out == exp_out).all() and (host_cnt == exp_cnt).all()
+    return exp_out, exp_cnt
+
+
+@pytest.mark.parametrize("first", [2048, 3072])
+def test_products_beyond_32_bits(swamd, engine, first):
+    """N[j] = 4096 x 65535 and C x S = 1.7e10 (the builder asserts both): equal halves give the exact half -1/2, the twin of 3072 and
+    1024 a sum beyond 2^32 whose low 32 bits have the other sign."""
+    c, w = cases.overflow_case(first)
+    for pw in (0, 1, 65535):
+        out, cnt = equal_to_reference(swamd, engine, c, pw, 0, w)
+        want = [63, 63, 63] if first == 3072 else [0, 0, 0] if pw == 0 else [-1, 0, -1]
+        assert (out == want).all() and (cnt.sum(axis=1) == 4096 * 65535).all(), (pw, out[0])
+
+
+@pytest.mark.parametrize("row", cases.ROUNDING, ids=lambda r: f"pw{r[0]}_p{r[1]}_s{r[2][0]}_{r[2][1]}_n{r[3][0]}")
+def test_rounding_at_numerators_of_1e10(swamd, engine, row):
+    c, w = cases.rounding_case(*row)
+    out, _ = equal_to_reference(swamd, engine, c, row[0], 0, w)
+    assert (out == row[5]).all()
+
+
+@pytest.mark.parametrize("pw,prior,s,w,exp", [(1, -3, 0, 1, -1), (1, -5, 0, 1, -2), (1, -5, 0, 2, -2), (2, -1, 0, 1, -1), (1, 5, 0, 1, 3), (1, 4, -7, 2, -3),
+                                              (0, 9, -128, 1, -128), (1, 100, 127, 65535, 127)])
+def test_round_half_up_with_floor_division(swamd, engine, pw, prior, s, w, exp):
+    """The table of tests/test_pssm_hits_host.py on the device: one column, one letter, one 'M'."""
+    c = cases.all_m_case([s], [1], prior=prior, ncols=1)
+    out, cnt = equal_to_reference(swamd, engine, c, pw, 0, np.array([[w]], np.int32))
+    assert cnt[0, 0] == w and out[0, 0] == exp
+
+
+@pytest.mark.parametrize("smax", [0, 127])
+@pytest.mark.parametrize("s", [127, -128])
+def test_both_clamps(swamd, engine, s, smax):
+    c = cases.clamp_case(s, smax)
+    for pw in (0, 1, 65535):
+        out, cnt = equal_to_reference(swamd, engine, c, pw, 0)
+        assert (out[cnt.sum(axis=1) == 0] == -128).all()
+    out, cnt = equal_to_reference(swamd, engine, c, 0, 0)
+    assert (out[cnt.sum(axis=1) > 0] == s).all()
+
+
+@pytest.mark.parametrize("smax", [0, 1, 127])
+def test_an_unobserved_column_keeps_its_clamped_prior_exactly(swamd, engine, smax):
+    """den == 0 (prior_weight 0) and the shortcut at N[j] == 0: P itself, negative and odd P among them."""
+    rng = np.random.default_rng(40 + smax)
+    c = cases.full_range_case(rng, 5, 3, smax)
+    want = np.minimum(c.prior[int(c.qoffs[0]):], smax)
+    for pw in (0, 1, 2, 65535):
+        out, cnt = equal_to_reference(swamd, engine, c, pw, int(c.aln[:, :, 1].max()) + 1)
+        assert not cnt.any() and (out == want).all()
+
+
+@pytest.mark.parametrize("nletters", [3, 5, 255, 256])
+def test_alphabets_of_3_5_255_and_256_letters(swamd, engine, nletters):
+    """(the write loop steps k by 256 % nletters with a carry; code 255 is "none" at 255 letters and a letter at 256)"""
+    rng = np.random.default_rng(7000 + nletters)
+    c, at = cases.alphabet_case(rng, nletters, 9)
+    for pw, kind in [(0, None), (2, "wild")]:
+        _, cnt = equal_to_reference(swamd, engine, c, pw, 0, weights_of(rng, len(cases.QLENS), 9) if kind else None)
+    if nletters == 256:
+        assert cnt[:, 255].sum() > 0
+
+
+@pytest.mark.parametrize("smax", [0, 1, 127])
+@pytest.mark.parametrize("nletters", [5, 256])
+def test_full_range_inputs(swamd, engine, nletters, smax):
+    rng = np.random.default_rng(8000 + nletters + smax)
+    c = cases.full_range_case(rng, nletters, 9, smax)
+    for pw, w in [(0, None), (1, None), (3, weights_of(rng, len(cases.QLENS), 9)), (65535, weights_of(rng, len(cases.QLENS), 9))]:
+        equal_to_reference(swamd, engine, c, pw, 0, w)
 
 
 def test_refusals_and_empty_calls(swamd, engine):

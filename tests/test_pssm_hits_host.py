@@ -1,6 +1,7 @@
 """CPU: the host leg of the PSSM update (sw_pssm_from_hits_host) against the numpy restatement of its rule (tests/pssm_hits_cases.py),
 byte for byte on counts and matrix -- synthetic tables around every 64-op chunk edge, real tables from the host legs of the search and
-the alignment, garbage tables between guard bytes --, its refusals, the writer sw_write_pssm read back by sw_read_pssm, and both in a
+the alignment, garbage tables between guard bytes, and the arithmetic edges the GPU test shares (sums beyond 2^32, the rounding table
+at numerators of 1e10, both clamps, unobserved columns, 3 to 256 letters, full-range S and prior) --, its refusals, the writer sw_write_pssm read back by sw_read_pssm, and both in a
 stand-alone program under the address and undefined-behaviour sanitizers."""
 import ctypes
 import os
@@ -89,6 +90,71 @@ def test_round_half_up_with_floor_division(swamd, pw, prior, s, w, exp):
     c.ops[0, 0] = cases.M
     out, counts, _ = check(swamd, c, pw, 0, np.array([[w]], np.int32))
     assert counts[0, 0] == w and out[0, 0] == exp
+
+
+@pytest.mark.parametrize("row", cases.ROUNDING, ids=lambda r: f"pw{r[0]}_p{r[1]}_s{r[2][0]}_{r[2][1]}_n{r[3][0]}")
+def test_rounding_at_numerators_of_1e10(swamd, row):
+    """The rounding table at N[j] = 4096 x 65535: exact halves of both signs, a hair on either side of one, floor against truncation."""
+    c, w = cases.rounding_case(*row)
+    out, counts, _ = check(swamd, c, row[0], 0, w)
+    assert counts.sum() >= 4095 * 65535 and (out == row[5]).all()
+
+
+@pytest.mark.parametrize("first", [2048, 3072])
+def test_products_beyond_32_bits(swamd, first):
+    """C x S = 1.7e10 (the builder asserts it): equal halves, and the twin whose sum itself passes 2^32."""
+    c, w = cases.overflow_case(first)
+    for pw in (0, 1, 65535):
+        out, _, _ = check(swamd, c, pw, 0, w)
+        want = [63, 63, 63] if first == 3072 else [0, 0, 0] if pw == 0 else [-1, 0, -1]
+        assert (out == want).all(), (pw, out[0])
+
+
+@pytest.mark.parametrize("smax", [0, 127])
+@pytest.mark.parametrize("s", [127, -128])
+def test_both_clamps(swamd, s, smax):
+    c = cases.clamp_case(s, smax)
+    for pw in (0, 1, 65535):
+        out, counts, _ = check(swamd, c, pw, 0, None)
+        seen = counts.sum(axis=1) > 0
+        assert (out[~seen] == -128).all()                # min(-128, smax), observed or not
+    out, counts, _ = check(swamd, c, 0, 0, None)
+    assert (out[counts.sum(axis=1) > 0] == s).all()
+
+
+@pytest.mark.parametrize("smax", [0, 1, 127])
+def test_an_unobserved_column_keeps_its_clamped_prior_exactly(swamd, smax):
+    """den == 0 (prior_weight 0) and den == prior_weight (the kernel's shortcut): P itself, negative and odd P among them."""
+    rng = np.random.default_rng(40 + smax)
+    c = cases.full_range_case(rng, 5, 3, smax)
+    front, nothing = int(c.qoffs[0]), int(c.aln[:, :, 1].max()) + 1
+    want = np.minimum(c.prior[front:], smax)
+    assert (want % 2 == 1).any() and (want < 0).any()
+    for pw in (0, 1, 2, 65535):
+        out, counts, _ = check(swamd, c, pw, nothing, None)
+        assert not counts.any() and (out == want).all()
+        out, counts, _ = check(swamd, c, pw, 0, None)    # ... and with entries used: the columns no entry reaches
+        assert (out[counts.sum(axis=1) == 0] == want[counts.sum(axis=1) == 0]).all() and (counts.sum(axis=1) == 0).any()
+
+
+@pytest.mark.parametrize("nletters", [3, 5, 255, 256])
+def test_alphabets_of_3_5_255_and_256_letters(swamd, nletters):
+    rng = np.random.default_rng(7000 + nletters)
+    c, _ = cases.alphabet_case(rng, nletters, 9)
+    for pw, kind in [(0, "none"), (2, "wild")]:
+        check(swamd, c, pw, 0, weights_of(rng, kind, len(cases.QLENS), 9))
+
+
+@pytest.mark.parametrize("smax", [0, 1, 127])
+@pytest.mark.parametrize("nletters", [5, 256])
+def test_full_range_inputs(swamd, nletters, smax):
+    rng = np.random.default_rng(8000 + nletters + smax)
+    c = cases.full_range_case(rng, nletters, 9, smax)
+    clamps = set()
+    for pw, kind in [(0, "none"), (1, "zeros"), (3, "wild"), (65535, "wild")]:
+        out, _, _ = check(swamd, c, pw, 0, weights_of(rng, kind, len(cases.QLENS), 9))
+        clamps |= {int(out.min()), int(out.max())}
+    assert {-128, 127} <= clamps or smax < 127
 
 
 def test_real_tables(swamd):

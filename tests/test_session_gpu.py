@@ -12,7 +12,11 @@ test_session_host.py.  The growing session runs twice on its context, the second
 Each test prints what it observed of the overlap (whether the first step's event and which others were still pending when the last
 enqueue returned, which steps were still running when the enqueue of the next returned, the time of the enqueue loop and of the
 drain); nothing of that is asserted: DESIGN section 9o records the figures.  The references of all three tests are computed once, by
-the first test that needs them."""
+the first test that needs them.
+
+The fourth session (session_cases.ITERATING) puts sw_db_pssm_from_hits into such a row: five updates back to
+back on alternating streams behind the search and the alignment that feed the first, with the packed pair-list and pre-filter
+routes in between."""
 import time
 
 import numpy as np
@@ -292,6 +296,129 @@ def test_shrinking_session_on_two_streams(runs, expect):
     run_sessions([run], [(run, s) for s in sc.shrinking(0)], "shrinking, cold")
     run_sessions([run], [(run, s) for s in sc.shrinking(1)], "shrinking, warm")
     run.check(expect)
+
+
+def test_iterating_session_updates_back_to_back(swamd, expect, checker):  # noqa: F811
+    """session_cases.ITERATING on one fresh context: search_pssm_top and align_pssm_hits, five sw_db_pssm_from_hits in a row on
+    alternating streams -- worlds of 4, 24, 256, 4 and 24 letters, so the device table grows twice and the fourth and fifth calls
+    rewrite the pinned copies of the second and third --, a search on the fifth matrix, and the packed pair-list and pre-filter
+    steps in between.  Every input is uploaded first; nothing is synchronised, copied or read between the calls; the updates are
+    compared with the numpy rule, the searches and alignments with the checker's tables (tests/test_session_host.py)."""
+    import torch as t
+
+    import pssm_cases
+    import pssm_hits_cases as phc
+    it = sc.iterating(swamd)
+    worlds, pairs = it["worlds"], it["pairs"]
+    eng = swamd.Engine(0)
+    second = t.cuda.Stream()
+    dbs = []
+    try:
+        i8 = lambda a: t.from_numpy(np.ascontiguousarray(a).reshape(-1).copy()).to(DEV)  # noqa: E731
+        w_db = [eng.prepare_db(to_dev(t, c.packed), c.offs) for c in worlds]
+        dbs += w_db
+        d_prior = [i8(c.prior) for c in worlds]
+        c0, c4 = worlds[0], worlds[4]
+        nq0, top0, cap0 = len(c0.qoffs) - 1, sc.UPDATE_TOPS[0], c0.cap
+        nq4 = len(c4.qoffs) - 1
+        sizes = [nq0 * top0 * 24, nq0 * 8, nq0 * top0 * 56, nq0 * top0 * cap0, nq4 * sc.ITER_TOP_AGAIN * 24, nq4 * 8] + [c.prior.size for c in worlds]
+        arena = Arena(t, DEV, arena_bytes(*sizes))
+        i64 = lambda n, name: arena.view(arena.carve(n * 8, align=8, name=name), t.int64, (n,))  # noqa: E731
+        hits0, nhits0, aln0 = i64(nq0 * top0 * 3, "hits"), i64(nq0, "nhits"), i64(nq0 * top0 * 7, "aln")
+        ops0 = arena.view(arena.carve(nq0 * top0 * cap0, name="ops"), t.uint8, (nq0 * top0 * cap0,))
+        hits4, nhits4 = i64(nq4 * sc.ITER_TOP_AGAIN * 3, "hits again"), i64(nq4, "nhits again")
+        d_new = [arena.view(arena.carve(c.prior.size, name=f"matrix {k}"), t.int8, (c.prior.size,)) for k, c in enumerate(worlds)]
+        tables = [None] + [(t.from_numpy(c.hits.copy()).to(DEV), t.from_numpy(c.aln.copy()).to(DEV), t.from_numpy(c.ops.copy()).to(DEV)) for c in worlds[1:]]
+        # the packed steps
+        db200, db40 = (eng.prepare_db(to_dev(t, sc.databases()[n]["packed"]), sc.databases()[n]["offs"]) for n in ("db200", "db40"))
+        dbs += [db200, db40]
+        seven, forty = sc.query_sets()["seven"], sc.query_sets()["forty"]
+        d_seven, d_forty, d_pairs = to_dev(t, seven["qpacked"]), to_dev(t, forty["qpacked"]), t.from_numpy(pairs.copy()).to(DEV)
+        res_pairs = t.full((len(pairs) * 3,), POISON64, dtype=t.int64, device=DEV)
+        cap = 40 * 40
+        pre = (t.full((cap, 2), POISON64, dtype=t.int64, device=DEV), t.full((1,), POISON64, dtype=t.int64, device=DEV),
+               t.full((40, 40), POISON32, dtype=t.int32, device=DEV))
+        with t.cuda.stream(second):
+            t.zeros(1, dtype=t.int64, device=DEV)
+        out, said = {}, {}
+
+        def call(name):
+            if name == "pssm_top":
+                out[name] = w_db[0].search_pssm_top_device(d_prior[0], c0.qoffs, phc.scoring(c0), top0, sc.ITER_MIN_SCORE, out=(hits0, nhits0))
+            elif name == "align":
+                out[name] = w_db[0].align_pssm_hits_device(d_prior[0], c0.qoffs, phc.scoring(c0), hits0, nhits0, ops_cap=cap0, out=(aln0, ops0), top=top0)
+            elif name.startswith("update"):
+                k = int(name[6:])
+                c = worlds[k]
+                h, n, a, o = (hits0, nhits0, aln0, ops0) if k == 0 else (tables[k][0], None, tables[k][1], tables[k][2])
+                out[name] = w_db[k].pssm_from_hits_device(d_prior[k], c.qoffs, phc.scoring(c), (c.sub, c.pw, c.inc), h, n, a, o, c.cap, out=d_new[k],
+                                                          top=c.hits.shape[1])
+                said[name] = eng.get_option("last_pssm_hits_launches")
+            elif name == "pssm_top_again":
+                out[name] = w_db[4].search_pssm_top_device(d_new[4], c4.qoffs, phc.scoring(c4), sc.ITER_TOP_AGAIN, sc.ITER_MIN_SCORE, out=(hits4, nhits4))
+            elif name == "pairs16":
+                eng.set_option("search_pairs_lanes", 16)
+                try:
+                    out[name] = db200.search_affine_pairs_device(d_seven, seven["qoffs"], (sc.packed_table(0), *sc.lc.GAPS[0]), d_pairs, out=res_pairs)
+                    said[name] = eng.get_option("last_search_pairs_packed_launches")
+                finally:
+                    eng.set_option("search_pairs_lanes", 32)
+            else:
+                assert name == "prefilter16"
+                out[name] = db40.prefilter_ungapped_device(d_forty, forty["qoffs"], sc.packed_table(0), sc.ITER_PREFILTER_MIN, cap, want_scores=True, out=pre)
+                said[name] = eng.get_option("last_prefilter_packed_launches")
+
+        t.cuda.synchronize()
+        t0 = time.perf_counter()
+        for name, stream in sc.ITERATING:
+            if stream:
+                with t.cuda.stream(second):
+                    call(name)
+            else:
+                call(name)
+        t1 = time.perf_counter()
+        t.cuda.synchronize()
+        print(f"\n[iterating] {len(sc.ITERATING)} calls enqueued in {1e3 * (t1 - t0):.1f} ms, drained in {1e3 * (time.perf_counter() - t1):.1f} ms")
+        host = lambda x: x.cpu().numpy()  # noqa: E731
+        # the routes
+        assert said["pairs16"] > 0 and said["prefilter16"] > 0 and all(said[f"update{k}"] == 1 for k in range(5)), said
+        # steps 1 and 2
+        assert np.array_equal(host(hits0).reshape(nq0, top0, 3), c0.hits) and np.array_equal(host(nhits0), c0.nhits)
+        assert np.array_equal(host(aln0).reshape(nq0, top0, 7), c0.aln)
+        ops = host(ops0).reshape(nq0 * top0, cap0)
+        live = np.arange(cap0)[None, :] < c0.aln.reshape(-1, 7)[:, 6:7]
+        assert np.array_equal(ops[live], c0.ops[live]) and (ops[~live] == POISON).all()
+        # the five updates against the rule
+        wrong = []
+        for k, c in enumerate(worlds):
+            got, want = host(d_new[k]).reshape(c.prior.shape), sc.update_expected(c)
+            front = int(c.qoffs[0])
+            if not (got[:front].view(np.uint8) == POISON).all():
+                wrong.append(f"update{k}: the unused front columns were written")
+            if not np.array_equal(got[front:], want[front:]):
+                bad = np.argwhere(got[front:] != want[front:])
+                wrong.append(f"update{k}: {len(bad)} entries differ, first (column, letter) {bad[0].tolist()}: {got[front:][tuple(bad[0])]} vs {want[front:][tuple(bad[0])]}")
+        assert not wrong, "\n  ".join(wrong)
+        # the search on the fifth matrix
+        full = sc.iterating_search_again(checker, c4, sc.update_expected(c4))
+        want_hits, want_n = pssm_cases.rank_order(full, sc.ITER_TOP_AGAIN, sc.ITER_MIN_SCORE)
+        assert np.array_equal(host(hits4).reshape(want_hits.shape), want_hits) and np.array_equal(host(nhits4), want_n)
+        # the packed steps
+        step = sc.Step("iter_pairs", "search_pairs", 0, db="db200", q="seven", sub=sc.packed_table(0), gaps=sc.lc.GAPS[0])
+        table = expect.full_under(step, step.sub, step.gaps)
+        want = np.zeros((len(pairs), 3), np.int64)
+        want[:140] = table[pairs[:140, 0], pairs[:140, 1]]
+        assert np.array_equal(host(res_pairs).reshape(-1, 3), want) and want[:, 1].max() > 0
+        u, pr = sc.iterating_prefilter()
+        got_pairs, n, scores = host(pre[0]), int(host(pre[1])[0]), host(pre[2])
+        assert n == len(pr) and np.array_equal(scores, u.astype(np.int32))
+        p = got_pairs[:n]
+        assert np.array_equal(p[np.lexsort((p[:, 1], p[:, 0]))], pr) and (got_pairs[n:] == -1).all()
+        assert_guards(arena)
+    finally:
+        for db in dbs:
+            db.close()
+        eng.close()
 
 
 def test_two_contexts_interleaved_on_one_device(runs, expect):

@@ -16,7 +16,11 @@ passing on stale state -- what an earlier call of another shape or scoring left 
 Growth is taken of the running maxima of session_cases.Step.measures(), which is what a workspace's size follows: the session ends on
 its small first call and runs the one-query calls behind the forty queries, so the values of the steps themselves are not monotone.
 What is asserted: each of the maxima rises strictly at least once behind the first step, and every step raises at least one of them
-or is the first to use one of session_cases.WORKSPACES -- but for the four steps of session_cases.REUSING, exactly.  No GPU is needed."""
+or is the first to use one of session_cases.WORKSPACES -- but for the four steps of session_cases.REUSING, exactly.  No GPU is needed.
+
+The fourth session (session_cases.ITERATING: five sw_db_pssm_from_hits calls back to back) has tests of its own at the end: the tables
+its first two steps leave are the checker's, every update's host leg equals the numpy rule, and no update could pass on the S, the
+code table or the offsets of the update before it or of the one two before it, whose pinned copy it rewrites."""
 import ctypes
 
 import numpy as np
@@ -206,6 +210,95 @@ def test_no_step_passes_on_the_previous_scoring(expect, name):
     nscored = len([s for s in steps if scored(s)])
     assert across == nscored - 1 and same_kind >= 3
     assert row0 >= (3 if name == "growing" else 2) * len({s.p for s in steps})   # table calls per pass that take over from a PSSM's code table
+
+
+# ---- the fourth session: updates back to back ----
+
+def test_iterating_first_world_holds_the_checkers_tables(swamd, checker):  # noqa: F811
+    """Steps 1 and 2 of the session (search_pssm_top, align_pssm_hits) leave the tables of worlds[0]: they are the rank order of the
+    checker's scores and the rule's alignments over the checker's matrices."""
+    from align_cases import expected
+    import pssm_hits_cases as phc
+    c = sc.iterating(swamd)["worlds"][0]
+    tab = sc.sequence_table(c.sub, c.letters, c.other, c.smax)
+    full = np.stack([checker.search(q, c.packed, c.offs, tab, -10, -1) for q in c.queries])
+    hits, nhits = pssm_cases.rank_order(full, sc.UPDATE_TOPS[0], sc.ITER_MIN_SCORE)
+    assert np.array_equal(hits, c.hits) and np.array_equal(nhits, c.nhits) and nhits.min() >= 1 and (nhits == sc.UPDATE_TOPS[0]).any()
+    top = sc.UPDATE_TOPS[0]
+    for q, query in enumerate(c.queries):
+        for r in range(top):
+            if r < nhits[q]:
+                k = int(hits[q, r, 0])
+                row, ops, _ = expected(checker, query, c.packed[c.offs[k]:c.offs[k + 1]], tab, -10, -1)
+                assert tuple(c.aln[q, r]) == row and c.ops[q * top + r, :row[6]].tobytes() == ops, (q, r)
+            else:
+                assert not c.aln[q, r].any()
+    assert phc.scoring(c)[3:] == (-10, -1)
+
+
+def test_iterating_updates_equal_the_rule_and_their_shapes_differ(swamd):
+    import pssm_hits_cases as phc
+    worlds = sc.iterating(swamd)["worlds"]
+    assert [len(c.letters) for c in worlds] == sc.UPDATE_NLETTERS == [4, 24, 256, 4, 24]
+    assert [n for n, _ in sc.ITERATING[4:9]] == [f"update{k}" for k in range(5)] and [s for _, s in sc.ITERATING[4:9]] == [0, 1, 0, 1, 0]
+    assert len({len(c.qoffs) for c in worlds}) == 5 and len({c.pw for c in worlds}) == 5 and len({c.hits.shape[1] for c in worlds}) == 5
+    for c in worlds:
+        out, _ = phc.host_leg(swamd, c, c.pw, c.inc)
+        want = sc.update_expected(c)
+        front = int(c.qoffs[0])
+        assert np.array_equal(out, want[front:]) and (want[front:] != np.minimum(c.prior[front:], c.smax)).any()
+
+
+def rows_differ_in_every_query(c, a, b):
+    return all((a[c.qoffs[q]:c.qoffs[q + 1]] != b[c.qoffs[q]:c.qoffs[q + 1]]).any() for q in range(len(c.qoffs) - 1))
+
+
+def test_iterating_no_update_could_pass_on_stale_state(swamd):
+    """For every update and the updates one and two before it (two before: the one whose pinned copy it rewrites): its expected matrix
+    differs in every query under the other's S and under the other's code table, and differs under the other's offsets wherever
+    the other has as many queries and its columns fit."""
+    worlds = sc.iterating(swamd)["worlds"]
+    fits = 0
+    for k, c in enumerate(worlds):
+        own = sc.update_expected(c)
+        for back in (1, 2):
+            if k - back < 0:
+                continue
+            o = worlds[k - back]
+            assert rows_differ_in_every_query(c, own, sc.update_expected(c, sub=o.sub)), (k, back, "S")
+            assert rows_differ_in_every_query(c, own, sc.update_expected(c, code=sc.code_of(o.letters))), (k, back, "letters")
+            assert not np.array_equal(c.qoffs, o.qoffs[:len(c.qoffs)])
+        if k >= 1:
+            o = worlds[k - 1]
+            if len(o.qoffs) >= len(c.qoffs) and o.qoffs[len(c.qoffs) - 1] <= c.qoffs[-1]:
+                fits += 1
+                assert not np.array_equal(own, sc.update_expected(c, qoffs=o.qoffs)), (k, "offsets")
+    assert fits >= 3
+
+
+def test_iterating_search_on_the_fifth_matrix(swamd, checker):  # noqa: F811
+    import pssm_hits_cases as phc
+    c = sc.iterating(swamd)["worlds"][4]
+    m = sc.update_expected(c)
+    want = sc.iterating_search_again(checker, c, m)
+    got = swamd.search_pssm_multi_host((m, c.qoffs), (c.packed, c.offs), phc.scoring(c))
+    assert np.array_equal(got, want) and want[:, :, 1].max() > 0
+    hits, nhits = pssm_cases.rank_order(want, sc.ITER_TOP_AGAIN, sc.ITER_MIN_SCORE)
+    assert nhits.min() >= 1
+    # the search reads the NEW matrix: under the prior the table is another
+    assert not np.array_equal(want, sc.iterating_search_again(checker, c, c.prior))
+
+
+def test_iterating_packed_steps_are_eligible_and_select(swamd, expect):
+    it = sc.iterating(swamd)
+    d, qs = sc.databases()["db200"], sc.query_sets()["seven"]
+    longest = int(np.diff(d["offs"]).max())
+    sub = sc.packed_table(0)
+    assert all(max(int(sub.max()), 0) * min(len(q), longest) <= 32767 for q in qs["queries"]) and sc.lc.GAPS[0][0] + 2 * sc.lc.GAPS[0][1] >= -32768
+    pairs = it["pairs"]
+    assert (pairs[140:] == -1).all() and (pairs[:140] >= 0).all() and np.array_equal(pairs[100:110], pairs[:10])
+    u, pr = sc.iterating_prefilter()
+    assert 0 < len(pr) < (np.diff(sc.databases()["db40"]["offs"]) > 0).sum() * 40
 
 
 def test_the_packed_steps_are_eligible():
