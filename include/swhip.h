@@ -675,6 +675,57 @@ int  sw_pssm_from_hits_host(const int8_t* prior, const int64_t* qoffsets, int64_
                             const int32_t* weights, int8_t* pssm_out, int32_t* counts);
 int  sw_write_pssm(const char* path, const char* letters, int32_t nletters, const int8_t* pssm, int64_t ncols, const char* consensus);
 
+/* The WEIGHTS of aligned hits, on the device (csrc/sw_pssm_weights.hip): the d_weights table of sw_db_pssm_from_hits, written from the
+ * same device tables, so that the loop
+ *   sw_db_search_pssm_top -> sw_db_align_pssm_hits -> sw_db_pssm_hit_weights -> sw_db_pssm_from_hits -> sw_db_search_pssm_top -> ...
+ * stays on one stream with no host round trip.  With every weight 1 a family that appears 200 times among the hits outvotes a distant
+ * homologue 200 to 1 and the profile collapses onto that family; position-based sequence weights (Henikoff & Henikoff 1994, J. Mol.
+ * Biol. 243:574) share a column's vote among the residues seen in it and a residue's share among the sequences that show it.  The
+ * rule below is that one in integers only -- no floats --, so device, host leg and a restatement in any language agree bit for bit,
+ * and every run writes the same bytes.
+ *   scoring   : letters and nletters are used (the rest is checked as everywhere, and not used).
+ *   weighting : per_hit 1..65535, the mean weight of an informative hit; include_min_score.
+ *   d_hits, d_nhits, top, d_aln, d_ops, ops_cap : as for sw_db_pssm_from_hits.  Only read.
+ *   d_weights : device, nqueries x top int32.  EVERY entry is written.
+ * For query q of qlen columns j:
+ * USED ENTRIES and THE WALK are exactly those of sw_db_pssm_from_hits, with weighting->include_min_score in the place of
+ *   upd->include_min_score: the same guards, every index compared, unsigned, before anything is loaded through it; an 'M' PAIRS column
+ *   j with the byte t[i] only if j < qlen and i < len.  Only pairs whose byte is in `letters` count below.
+ * n[j][k] = the number of used entries that pair column j with letters[k], 0..4096 (the same target twice in the table: two sequences).
+ * k_j     = the number of k with n[j][k] > 0, 0..256.
+ * F = 2^20, so k_j x n[j][k] <= F and every term below is >= 1.
+ * For a used entry r:  m_r = the number of counted pairs it makes;  T_r = the sum over those pairs (j, k) of floor(F / (k_j x n[j][k])),
+ *   below 2^40, in int64;  A_r = m_r > 0 ? floor(T_r / m_r) : 0, within 1..2^20: the fixed-point mean, over the columns the hit
+ *   covers, of Henikoff's 1 / (k n).  An entry that is not used has A_r = 0.
+ * U = the number of entries with A_r > 0;  SUM = the sum of A_r over the query's entries, <= 2^32.
+ * THE WEIGHT.  w(q, r) = SUM > 0 ? min(65535, floor((2 x per_hit x U x A_r + SUM) / (2 x SUM))) : 0 -- rounded half up; the numerator stays
+ *   below 2^50.  The weights of a query sum to about per_hit x U: the mean weight of an informative hit is per_hit.
+ * Entries that are not used, and r at or beyond clamp(d_nhits[q], 0, top), get 0.  The call is defined for ANY bytes in the device
+ * tables and reads nothing out of bounds.
+ * What follows from the rule (tests/test_pssm_weights_host.py holds it): U identical entries get exactly per_hit each; permuting a
+ * query's entries permutes its weights; two copies of one sequence beside one sequence that differs from it in every column get
+ * 0.75, 0.75 and 1.5 x per_hit; a query's weights depend on no other query.
+ * Downstream, N[j] of sw_db_pssm_from_hits counts in units of per_hit: scale prior_weight with it.
+ * Asynchronous on `stream`, no host round trip: the host reads none of the device tables; its work is O(nqueries) + O(nletters).  The
+ * output feeds sw_db_pssm_from_hits(..., d_weights, ...) on the same stream with nothing in between.  The small table (the code table,
+ * the offsets) is uploaded through the two pinned copies of sw_db_pssm_from_hits, in the same turns: a loop can still be enqueued
+ * one call ahead of the device.  Two launches behind one memset of the context's nqueries x top x 8 bytes of accumulators: one workgroup
+ * per (query, tile of columns) -- counts, then terms, in LDS; one 64-bit integer atomic add per (entry, tile) --, then one workgroup per
+ * query (swp::plan_pssm_weights).  "last_pssm_weights_launches" reports the kernel launches of the last call, "last_pssm_weights_tiles"
+ * the tiles its longest query was cut into.
+ * nqueries == 0 launches nothing; with a handle of ntargets == 0 every weight is 0.
+ * SW_EINVAL, checked before the first launch: the argument errors sw_db_pssm_from_hits reports for the same arguments (the offsets, the
+ * scoring object, the handle's device, top outside 1..SW_TOP_MAX, NULL d_hits, d_aln or d_ops, ops_cap < 1); NULL weighting or
+ * d_weights; per_hit outside 1..65535.
+ *   sw_pssm_hit_weights_host  the CPU leg: the same bytes in plain C++ from host memory, db / offsets / ntargets in the handle's place. */
+typedef struct { int32_t per_hit; int64_t include_min_score; } sw_pssm_weighting;   /* per_hit 1..65535 */
+int  sw_db_pssm_hit_weights(sw_ctx* ctx, const sw_db* db, const int64_t* qoffsets, int64_t nqueries, const sw_pssm_scoring* scoring,
+                            const sw_pssm_weighting* weighting, const sw_hit* d_hits, const int64_t* d_nhits, int64_t top,
+                            const sw_alignment* d_aln, const char* d_ops, int64_t ops_cap, int32_t* d_weights, void* stream);
+int  sw_pssm_hit_weights_host(const int64_t* qoffsets, int64_t nqueries, const char* db, const int64_t* offsets, int64_t ntargets,
+                              const sw_pssm_scoring* scoring, const sw_pssm_weighting* weighting, const sw_hit* hits, const int64_t* nhits,
+                              int64_t top, const sw_alignment* aln, const char* ops, int64_t ops_cap, int32_t* weights);
+
 /* Tables.  sw_submat_match: s[x][y] = x == y ? match : mismatch (matchMissmatchScore, serial_smithW.c:251-256; both must fit int8:
  * the builder returns nothing, so it clamps them to -128..127 -- a caller that takes them from a user checks the range first, as
  * smithW and the Python wrapper do, which refuse such scores).  sw_submat_from_letters: `scores` is n x n, row = query letter, over the n bytes of

@@ -66,6 +66,12 @@
   pssm_from_hits_host, H2D of the matrix -- the matrices compared byte for byte (the run fails if they differ).  (b) one whole iteration,
   align_pssm_hits_device + pssm_from_hits_device + search_pssm_top_device, against search_pssm_top_device alone.  ops_cap is 4 x qlen, not
   qlen + the longest target: an entry whose alignment is longer counts as unused on both sides alike (*_over_cap says how many there are)
+  --pssm-weights: data set (a) only, the queries, tables and ops_cap of --pssm-iterate, top 10, 100 and 4096, 7 calls each after a warm-up,
+  wall clock around a synchronised leg, ALTERNATING in one process.  (a) pssm_hit_weights_device alone against what a caller had to do
+  without it: D2H of d_hits, d_nhits, d_aln and d_ops, pssm_hit_weights_host, H2D of the weights -- the weights compared byte for byte (the
+  run fails if they differ).  (b) one weighted iteration, align_pssm_hits_device + pssm_hit_weights_device + pssm_from_hits_device (with the
+  weights; prior_weight x per_hit) + search_pssm_top_device, against the unweighted one of --pssm-iterate; *_update_alone_ms is
+  pssm_from_hits_device without weights, the kernel the expectation "about twice" refers to
 GCUPS = query letters x target letters / time of the call (torch events, median of --reps after --warmup)."""
 import argparse
 import importlib
@@ -116,6 +122,7 @@ def main():
     ap.add_argument("--prefiltered-top", action="store_true", help="data set (a) only: the top 10 of 64 queries by the full search and by pre-filter, rescoring and selection from the pair list")
     ap.add_argument("--pssm", action="store_true", help="data set (a) only: 64 PSSM queries derived from 64 sequence queries beside those, alternating")
     ap.add_argument("--pssm-iterate", action="store_true", help="data set (a) only: the PSSM update on the device against the host round trip, and a whole iteration against the search alone")
+    ap.add_argument("--pssm-weights", action="store_true", help="data set (a) only: the hit weights on the device against the host round trip, and a weighted iteration against the unweighted one")
     ap.add_argument("--lanes", action="store_true", help="data set (a) only: 64 queries under search_lanes 32 and 16, alternating, full tables and top 10")
     ap.add_argument("--pairs-lanes", action="store_true", help="data set (a) only: pair lists of all, 10 %% and 1 %% of the cross product under search_pairs_lanes 32 and 16, alternating")
     ap.add_argument("--top", action="store_true", help="data set (a) only: the best 100 targets of 64 queries by the full table and by the selection on the device")
@@ -674,6 +681,82 @@ def main():
         out[f"{P}_identical"] = all(out[f"{P}_top{t}_identical"] for t in (10, 100, 4096))
         db.close()
 
+    def pssm_weights_leg(packed, offs, nq=64, reps=7, per_hit=16):
+        import time
+        d_db = torch.from_numpy(packed.copy()).to(dev)
+        db = eng.prepare_db(d_db, offs)
+        qoffs = np.arange(nq + 1, dtype=np.int64) * args.qlen
+        queries = rng.choice(PROTEIN, int(qoffs[-1])).astype(np.uint8)
+        m, moffs = swamd.pssm_from_queries((queries, qoffs), sub, letters)
+        d_m = torch.from_numpy(m.reshape(-1).copy()).to(dev)
+        pscoring, update, weighting, cap = (letters, -4, 127, -11, -1), (sub, 10, 1), (per_hit, 1), 4 * args.qlen
+        wupdate = (sub, 10 * per_hit, 1)                                     # N[j] counts in units of per_hit
+        P = "pssm_weights"
+        out[f"{P}_queries"], out[f"{P}_qlen"], out[f"{P}_targets"], out[f"{P}_reps"], out[f"{P}_ops_cap"], out[f"{P}_per_hit"] = nq, args.qlen, len(offs) - 1, reps, cap, per_hit
+        for top in (10, 100, 4096):
+            hits, nhits = db.search_pssm_top_device(d_m, moffs, pscoring, top, 1)
+            aln, ops = db.align_pssm_hits_device(d_m, moffs, pscoring, hits, nhits, ops_cap=cap)
+            d_out = torch.empty_like(d_m)
+            d_w = torch.empty((nq, top), dtype=torch.int32, device=dev)
+            h2 = (torch.zeros_like(hits), torch.zeros_like(nhits))
+            state = {}
+
+            def device_call():
+                db.pssm_hit_weights_device(moffs, pscoring, weighting, hits, nhits, aln, ops, cap, out=d_w)
+
+            def host_round_trip():
+                h, n, a, o = hits.cpu().numpy(), nhits.cpu().numpy(), aln.cpu().numpy(), ops.cpu().numpy()
+                state["w"] = swamd.pssm_hit_weights_host(moffs, (packed, offs), pscoring, weighting, h, n, a, o)
+                state["d"] = torch.from_numpy(state["w"].reshape(-1)).to(dev)
+
+            def update_alone():
+                db.pssm_from_hits_device(d_m, moffs, pscoring, update, hits, nhits, aln, ops, cap, out=d_out)
+
+            def iteration():
+                db.align_pssm_hits_device(d_m, moffs, pscoring, hits, nhits, ops_cap=cap, out=(aln, ops))
+                db.pssm_from_hits_device(d_m, moffs, pscoring, update, hits, nhits, aln, ops, cap, out=d_out)
+                db.search_pssm_top_device(d_out, moffs, pscoring, top, 1, out=h2)
+
+            def weighted_iteration():
+                db.align_pssm_hits_device(d_m, moffs, pscoring, hits, nhits, ops_cap=cap, out=(aln, ops))
+                db.pssm_hit_weights_device(moffs, pscoring, weighting, hits, nhits, aln, ops, cap, out=d_w)
+                db.pssm_from_hits_device(d_m, moffs, pscoring, wupdate, hits, nhits, aln, ops, cap, weights=d_w, out=d_out)
+                db.search_pssm_top_device(d_out, moffs, pscoring, top, 1, out=h2)
+
+            def wall(fn):                                                    # wall clock around a synchronised call
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                fn()
+                torch.cuda.synchronize()
+                return (time.perf_counter() - t0) * 1e3
+
+            legs = {"device_call": device_call, "host_round_trip": host_round_trip, "update_alone": update_alone, "iteration": iteration,
+                    "weighted_iteration": weighted_iteration}
+            for group in (("device_call", "update_alone", "host_round_trip"), ("iteration", "weighted_iteration")):
+                ms = {k: [] for k in group}
+                for k in group:
+                    wall(legs[k])                                            # warm-up
+                for _ in range(reps):                                        # alternating: a drift of the device shows in all alike
+                    for k in group:
+                        ms[k].append(wall(legs[k]))
+                for k in group:
+                    out[f"{P}_top{top}_{k}_ms"] = round(float(np.median(ms[k])), 4)
+                    out[f"{P}_top{top}_{k}_range_ms"] = [round(min(ms[k]), 4), round(max(ms[k]), 4)]
+            d_w.fill_(0x55555555)
+            device_call()
+            torch.cuda.synchronize()
+            w = d_w.cpu().numpy()
+            out[f"{P}_top{top}_identical"] = bool(w.tobytes() == state["w"].tobytes())
+            out[f"{P}_top{top}_launches"] = eng.get_option("last_pssm_weights_launches")
+            out[f"{P}_top{top}_tiles_per_query"] = eng.get_option("last_pssm_weights_tiles")
+            out[f"{P}_top{top}_informative"] = int((w > 0).sum())
+            out[f"{P}_top{top}_weight_min_max"] = [int(w[w > 0].min()), int(w.max())] if (w > 0).any() else [0, 0]
+            out[f"{P}_top{top}_host_over_device"] = round(out[f"{P}_top{top}_host_round_trip_ms"] / out[f"{P}_top{top}_device_call_ms"], 2)
+            out[f"{P}_top{top}_device_over_update"] = round(out[f"{P}_top{top}_device_call_ms"] / out[f"{P}_top{top}_update_alone_ms"], 2)
+            out[f"{P}_top{top}_weighted_over_unweighted"] = round(out[f"{P}_top{top}_weighted_iteration_ms"] / out[f"{P}_top{top}_iteration_ms"], 4)
+        out[f"{P}_identical"] = all(out[f"{P}_top{t}_identical"] for t in (10, 100, 4096))
+        db.close()
+
     def lanes_leg(packed, offs, nq=64, top=10):
         d_db = torch.from_numpy(packed.copy()).to(dev)
         db = eng.prepare_db(d_db, offs)
@@ -869,7 +952,7 @@ def main():
     out["a_letters"] = int(offs[-1])
     out["a_len_median"] = int(np.median(lens))
     out["a_len_max"] = int(lens.max())
-    if args.multi or args.top or args.align_hits or args.pairs or args.prefilter or args.prefiltered_top or args.pssm or args.pssm_iterate or args.lanes or args.pairs_lanes:
+    if args.multi or args.top or args.align_hits or args.pairs or args.prefilter or args.prefiltered_top or args.pssm or args.pssm_iterate or args.pssm_weights or args.lanes or args.pairs_lanes:
         if args.lanes:
             lanes_leg(packed, offs)
         if args.pairs_lanes:
@@ -878,6 +961,8 @@ def main():
             pssm_leg(packed, offs)
         if args.pssm_iterate:
             pssm_iterate_leg(packed, offs)
+        if args.pssm_weights:
+            pssm_weights_leg(packed, offs)
         if args.pairs:
             pairs_leg(packed, offs)
         if args.prefilter:
@@ -900,6 +985,8 @@ def main():
             sys.exit("bench_search.py --pairs-lanes: pairs_lanes_identical is false")
         if args.pssm_iterate and not out["pssm_iterate_identical"]:
             sys.exit("bench_search.py --pssm-iterate: pssm_iterate_identical is false")
+        if args.pssm_weights and not out["pssm_weights_identical"]:
+            sys.exit("bench_search.py --pssm-weights: pssm_weights_identical is false")
         if args.pssm and not out["pssm_identical"]:
             sys.exit("bench_search.py --pssm: pssm_identical is false")
         if args.pairs:   # the required conditions of the pair-list call: a line that misses one is printed, and the run fails

@@ -55,6 +55,10 @@ class _PssmUpdate(ctypes.Structure):   # sw_pssm_update: the table by pointer
     _fields_ = [("sub", ctypes.c_void_p), ("prior_weight", ctypes.c_int32), ("include_min_score", ctypes.c_int64)]
 
 
+class _PssmWeighting(ctypes.Structure):   # sw_pssm_weighting
+    _fields_ = [("per_hit", ctypes.c_int32), ("include_min_score", ctypes.c_int64)]
+
+
 # every symbol include/swhip.h declares: (restype, argtypes)
 _vp, _i64, _i32, _u32, _sz = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_uint32, ctypes.c_size_t
 ABI = {
@@ -102,6 +106,10 @@ ABI = {
                                     _vp, _vp, _vp]),
     "sw_pssm_from_hits_host": (_i32, [_vp, _vp, _i64, _vp, _vp, _i64, ctypes.POINTER(_PssmScoring), ctypes.POINTER(_PssmUpdate), _vp, _vp, _i64, _vp, _vp,
                                       _i64, _vp, _vp, _vp]),
+    "sw_db_pssm_hit_weights": (_i32, [_vp, _vp, _vp, _i64, ctypes.POINTER(_PssmScoring), ctypes.POINTER(_PssmWeighting), _vp, _vp, _i64, _vp, _vp, _i64, _vp,
+                                      _vp]),
+    "sw_pssm_hit_weights_host": (_i32, [_vp, _i64, _vp, _vp, _i64, ctypes.POINTER(_PssmScoring), ctypes.POINTER(_PssmWeighting), _vp, _vp, _i64, _vp, _vp,
+                                        _i64, _vp]),
     "sw_write_pssm": (_i32, [ctypes.c_char_p, _vp, ctypes.c_int32, _vp, _i64, _vp]),
     "sw_align_affine_device": (_i32, [_vp, _vp, _i64, _vp, _vp, _i64, _vp, _i64, ctypes.POINTER(_Affine), _vp, _vp, _i64, _vp]),
     "sw_align_affine_host": (_i32, [_vp, _i64, _vp, _vp, _i64, _vp, _i64, ctypes.POINTER(_Affine), _vp, _vp, _i64]),
@@ -550,6 +558,42 @@ def pssm_from_hits_host(prior, targets, scoring, update, hits, nhits, aln, ops, 
                                         counts.ctypes.data))
     out = out[:len(m)]
     return (out, counts[:ncols]) if want_counts else out
+
+
+def _pssm_weighting(weighting):
+    """The sw_pssm_weighting from (per_hit, include_min_score)."""
+    per_hit, include_min_score = weighting
+    return _PssmWeighting(int(per_hit), int(include_min_score))
+
+
+def _query_offsets(qoffsets_or_pssm, nletters: int):
+    """The int64 column offsets of the queries: an offsets array, or a PSSM as search_pssm takes it (only its offsets are used)."""
+    if isinstance(qoffsets_or_pssm, np.ndarray) and qoffsets_or_pssm.ndim == 1:
+        return np.ascontiguousarray(qoffsets_or_pssm, np.int64)
+    return _pack_pssm(qoffsets_or_pssm, nletters)[1]
+
+
+def pssm_hit_weights_host(qoffsets_or_pssm, targets, scoring, weighting, hits, nhits, aln, ops):
+    """sw_pssm_hit_weights_host: the position-based weights of aligned hits in plain C++ on the host (no GPU).  Arguments and result as
+    Database.pssm_hit_weights."""
+    lt, sc = _pssm_scoring(scoring)
+    wt = _pssm_weighting(weighting)
+    qoffs = _query_offsets(qoffsets_or_pssm, max(1, sc.nletters))
+    packed, offs = _pack_targets(targets)
+    nq = len(qoffs) - 1
+    hits, nhits = _hit_table(hits, nhits, nq)
+    top = hits.shape[1]
+    a = np.ascontiguousarray(aln, np.int64).reshape(-1, 7)
+    if len(a) != nq * top:
+        raise ValueError(f"aln must be ({nq}, {top}, 7) int64")
+    o, cap = _ops_table(ops, nq, top)
+    db = packed if len(packed) else np.zeros(1, np.uint8)
+    aa = a if len(a) else np.zeros((1, 7), np.int64)
+    w = np.zeros(max(1, nq * top), np.int32)
+    _check(lib().sw_pssm_hit_weights_host(qoffs.ctypes.data, nq, db.ctypes.data, offs.ctypes.data, len(offs) - 1, ctypes.byref(sc), ctypes.byref(wt),
+                                          hits.ctypes.data if hits.size else aa.ctypes.data, nhits.ctypes.data if nhits is not None else None, top,
+                                          aa.ctypes.data, o.ctypes.data, cap, w.ctypes.data))
+    return w[:nq * top].reshape(nq, top)
 
 
 def search_pssm_multi_host(pssm, targets, scoring):
@@ -1090,6 +1134,66 @@ class Database:
                                           int(ops_cap), weights.data_ptr() if weights is not None else None, out.data_ptr() if out is not None else None,
                                           counts.data_ptr() if counts is not None else None, eng._stream()))
         return out if out is not None else counts
+
+    def pssm_hit_weights(self, scoring, weighting, qoffsets_or_pssm, hits, nhits, aln, ops):
+        """The position-based (Henikoff) weights of aligned hits (sw_db_pssm_hit_weights): the `weights` of pssm_from_hits.  scoring as
+        for search_pssm; weighting = (per_hit, include_min_score); qoffsets_or_pssm: the int64 column offsets of the queries, or the
+        PSSM as search_pssm takes it (only its offsets are used); hits, nhits, aln, ops as for pssm_from_hits.  Returns the (nqueries,
+        top) int32 weights.  include/swhip.h states the rule."""
+        eng = self.engine
+        t = eng.torch
+        dev = f"cuda:{eng.device}"
+        qoffs = _query_offsets(qoffsets_or_pssm, max(1, len(_as_seq(scoring[0]))))
+        nq = len(qoffs) - 1
+        hits, nhits = _hit_table(hits, nhits, nq)
+        top = hits.shape[1]
+        a = np.ascontiguousarray(aln, np.int64).reshape(-1, 7)
+        if len(a) != nq * top:
+            raise ValueError(f"aln must be ({nq}, {top}, 7) int64")
+        o, cap = _ops_table(ops, nq, top)
+        d_hits = t.from_numpy(hits.reshape(-1).copy() if hits.size else np.zeros(3, np.int64)).to(dev)
+        d_nhits = t.from_numpy(nhits.copy()).to(dev) if nhits is not None and len(nhits) else None
+        d_aln = t.from_numpy(a.reshape(-1).copy() if a.size else np.zeros(7, np.int64)).to(dev)
+        d_ops = t.from_numpy(o.reshape(-1).copy()).to(dev)
+        out = self.pssm_hit_weights_device(qoffs, scoring, weighting, d_hits, d_nhits, d_aln, d_ops, cap, top=top)
+        eng.synchronize()
+        return out.cpu().numpy()[:nq * top].reshape(nq, top)
+
+    def pssm_hit_weights_device(self, qoffsets, scoring, weighting, hits, nhits, aln, ops, ops_cap: int, out=None, top=None):
+        """sw_db_pssm_hit_weights on device-resident tables: the hit table and counts of search_pssm_top_device, the alignments and ops
+        of align_pssm_hits_device; asynchronous on torch's current stream, nothing comes to the host.  out: the int32 tensor of at
+        least nqueries x top elements that receives the weights (every entry is written), None for a fresh (nqueries, top) one.
+        Returns `out`: the `weights` of pssm_from_hits_device."""
+        eng = self.engine
+        t = eng.torch
+        lt, sc = _pssm_scoring(scoring)
+        wt = _pssm_weighting(weighting)
+        qoffs = np.ascontiguousarray(qoffsets, np.int64).reshape(-1)
+        if len(qoffs) == 0:
+            qoffs = np.zeros(1, np.int64)
+        nq = len(qoffs) - 1
+        if top is None:
+            if hits.dim() != 3:
+                raise ValueError("hits must be (nqueries, top, 3), or `top` given")
+            top = hits.shape[1]
+        top = int(top)
+        n = nq * max(0, top)
+        if hits.dtype != t.int64 or not hits.is_contiguous() or hits.numel() < n * 3:
+            raise ValueError(f"hits must be a contiguous int64 tensor of at least {nq} x {top} x 3 elements")
+        if nhits is not None and (nhits.dtype != t.int64 or not nhits.is_contiguous() or nhits.numel() < nq):
+            raise ValueError(f"nhits must be a contiguous int64 tensor of at least {nq} elements")
+        if aln.dtype != t.int64 or not aln.is_contiguous() or aln.numel() < n * 7:
+            raise ValueError(f"aln must be a contiguous int64 tensor of at least {n * 7} elements")
+        if ops is not None and (ops.dtype != t.uint8 or not ops.is_contiguous() or ops.numel() < n * max(0, int(ops_cap))):
+            raise ValueError(f"ops must be a contiguous uint8 tensor of at least {n * max(0, int(ops_cap))} elements")
+        if out is None:
+            out = t.empty((nq, max(0, top)) if n else (1,), dtype=t.int32, device=f"cuda:{eng.device}")
+        if out.dtype != t.int32 or not out.is_contiguous() or out.numel() < n:
+            raise ValueError(f"out must be a contiguous int32 tensor of at least {n} elements")
+        _check(lib().sw_db_pssm_hit_weights(eng._h, self._h, qoffs.ctypes.data, nq, ctypes.byref(sc), ctypes.byref(wt), hits.data_ptr(),
+                                            nhits.data_ptr() if nhits is not None else None, top, aln.data_ptr(), ops.data_ptr() if ops is not None else None,
+                                            int(ops_cap), out.data_ptr(), eng._stream()))
+        return out
 
     def align_affine_hits_device(self, d_queries, qoffsets, scoring, hits, nhits, ops_cap: int = 0, out=None, top=None, checkpoint=None):
         """sw_db_align_affine_hits on device-resident queries and a device hit table -- the (nqueries, top, 3) int64 tensor and the

@@ -42,6 +42,10 @@
 //     ... --iterations N      with --all-queries or --pssm: N >= 1 rounds of search, alignment of the top hits and a new PSSM built from them on the device
 //                              (sw_db_pssm_from_hits; --include-score S, default 1; --prior-weight W, default 10; --out-pssm PREFIX writes PREFIX.<query>.pssm);
 //                              the hits and --align output are those of the last round; N = 1 is the search of today
+//     ... --weight-hits P     with --iterations / --out-pssm: every round weights its aligned hits on the device before it builds the matrix
+//                              (sw_db_pssm_hit_weights, Henikoff's position-based weights; per_hit = P within 1..65535, the round's --include-score):
+//                              a family that fills the hit list no longer outvotes a distant homologue.  N[j] of the update then counts in units
+//                              of P, so --prior-weight scales with it: --weight-hits 16 --prior-weight 160 is the balance of --prior-weight 10
 //   smithW --search --pssm FILE DB.fa --gap-open O --gap-extend E [--top K] [--min-score S] [--align] [--search-lanes 16|32]
 //                              the ONE query is a position-specific scoring matrix, PSI-BLAST's ASCII PSSM (sw_read_pssm), searched through a prepared
 //                              handle (sw_db_search_pssm_top, sw_db_align_pssm_hits); the output is that of --all-queries for one record, the Q line of an
@@ -463,10 +467,11 @@ static int search_pssm_main(const char* ppath, const char* dbpath, long long top
 // always the case with --pssm) and searches again (sw_db_search_pssm_top); the host reads nothing in between.  The hits printed, and
 // with --align their alignments, are those of the LAST iteration, in the format of --all-queries; the query line of an alignment is the
 // query's letters, for a PSSM file the consensus of the last matrix.  --out-pssm PREFIX writes the matrix the last search ran with, per
-// query, to PREFIX.<query index>.pssm (sw_write_pssm).
+// query, to PREFIX.<query index>.pssm (sw_write_pssm).  --weight-hits P puts sw_db_pssm_hit_weights (per_hit = P, the same
+// --include-score) between the alignment and the update of every round and hands its table to the update; 0: no weights, every hit counts 1.
 static int search_iter_main(const char* qpath, const char* ppath, const char* dbpath, long long top, long long min_score, const sw_scores& sc, const AffineArgs& af,
                             bool align, bool align_ckpt, int search_lanes, long long iterations, long long include_score, long long prior_weight,
-                            const char* out_pssm) {
+                            const char* out_pssm, long long weight_hits) {
     int64_t nq = 0, qtotal = 0, nrec = 0, total = 0;
     CHECK(sw_read_fasta_db(dbpath, nullptr, 0, nullptr, 0, &nrec, &total));
     std::vector<char> db((size_t)total + 1);
@@ -520,7 +525,7 @@ static int search_iter_main(const char* qpath, const char* ppath, const char* db
     CHECK(sw_create(0, &ctx));
     if (align_ckpt) CHECK(sw_set_option(ctx, "align_checkpoint", 2));
     CHECK(sw_set_option(ctx, "search_lanes", search_lanes));
-    void *d_prior = nullptr, *d_work = nullptr, *d_db = nullptr, *d_hits = nullptr, *d_nhits = nullptr, *d_aln = nullptr, *d_ops = nullptr;
+    void *d_prior = nullptr, *d_work = nullptr, *d_db = nullptr, *d_hits = nullptr, *d_nhits = nullptr, *d_aln = nullptr, *d_ops = nullptr, *d_weights = nullptr;
     const size_t n = (size_t)(nq * K);
     CHECK(sw_device_malloc(ctx, pssm.size() + 16, &d_prior));
     CHECK(sw_device_malloc(ctx, pssm.size() + 16, &d_work));
@@ -541,15 +546,20 @@ static int search_iter_main(const char* qpath, const char* ppath, const char* db
         CHECK(sw_device_malloc(ctx, n * sizeof(sw_alignment), &d_aln));
         CHECK(sw_device_malloc(ctx, n * (size_t)ops_cap, &d_ops));
     }
+    if (weight_hits > 0 && iterations > 1) CHECK(sw_device_malloc(ctx, n * sizeof(int32_t), &d_weights));
     const sw_pssm_update upd = {sub.data(), (int32_t)prior_weight, include_score};
+    const sw_pssm_weighting weighting = {(int32_t)weight_hits, include_score};
     const double t1 = now_s();
     const int8_t* d_cur = (const int8_t*)d_prior;
     for (long long it = 0; it < iterations; ++it) {   // nothing below waits for the device or reads from it
         if (it > 0) {
             CHECK(sw_db_align_pssm_hits(ctx, handle, d_cur, qoffs.data(), nq, &scoring, (const sw_hit*)d_hits, (const int64_t*)d_nhits, K, (sw_alignment*)d_aln,
                                         (char*)d_ops, ops_cap, nullptr));
+            if (d_weights)
+                CHECK(sw_db_pssm_hit_weights(ctx, handle, qoffs.data(), nq, &scoring, &weighting, (const sw_hit*)d_hits, (const int64_t*)d_nhits, K,
+                                             (const sw_alignment*)d_aln, (const char*)d_ops, ops_cap, (int32_t*)d_weights, nullptr));
             CHECK(sw_db_pssm_from_hits(ctx, handle, (const int8_t*)d_prior, qoffs.data(), nq, &scoring, &upd, (const sw_hit*)d_hits, (const int64_t*)d_nhits, K,
-                                       (const sw_alignment*)d_aln, (const char*)d_ops, ops_cap, nullptr, (int8_t*)d_work, nullptr, nullptr));
+                                       (const sw_alignment*)d_aln, (const char*)d_ops, ops_cap, (const int32_t*)d_weights, (int8_t*)d_work, nullptr, nullptr));
             d_cur = (const int8_t*)d_work;
         }
         CHECK(sw_db_search_pssm_top(ctx, handle, d_cur, qoffs.data(), nq, &scoring, K, min_score, (sw_hit*)d_hits, (int64_t*)d_nhits, nullptr));
@@ -597,6 +607,7 @@ static int search_iter_main(const char* qpath, const char* ppath, const char* db
     (void)sw_device_free(ctx, d_nhits);
     if (d_aln) (void)sw_device_free(ctx, d_aln);
     if (d_ops) (void)sw_device_free(ctx, d_ops);
+    if (d_weights) (void)sw_device_free(ctx, d_weights);
     sw_destroy(ctx);
     return 0;
 }
@@ -797,7 +808,8 @@ int main(int argc, char** argv) {
     bool align = false, all_queries = false, align_ckpt = false;
     int search_lanes = 32, pairs_lanes = 32;
     bool has_search_lanes = false, has_pairs_lanes = false;
-    int iterations = 1, include_score = 1, prior_weight = 10;
+    int iterations = 1, include_score = 1, prior_weight = 10, weight_hits = 0;
+    bool has_weight_hits = false;
     bool has_iter_flag = false;
     const char* out_pssm = nullptr;
     sw_scores sc = {3, -3, -2};
@@ -830,6 +842,7 @@ int main(int argc, char** argv) {
         else if (f == "--include-score" && ai + 1 < argc) { if (!parse_int("--include-score", argv[++ai], &include_score)) return 2; has_iter_flag = true; }
         else if (f == "--prior-weight" && ai + 1 < argc) { if (!parse_int("--prior-weight", argv[++ai], &prior_weight)) return 2; has_iter_flag = true; }
         else if (f == "--out-pssm" && ai + 1 < argc) { out_pssm = argv[++ai]; has_iter_flag = true; }
+        else if (f == "--weight-hits" && ai + 1 < argc) { if (!parse_int("--weight-hits", argv[++ai], &weight_hits)) return 2; has_weight_hits = true; }
         else if (f == "--matrix" && ai + 1 < argc) { af.matrix = argv[++ai]; af.on = true; }
         else if (f == "--gap-open" && ai + 1 < argc) { if (!parse_int("--gap-open", argv[++ai], &af.open)) return 2; af.has_open = af.on = true; }
         else if (f == "--gap-extend" && ai + 1 < argc) { if (!parse_int("--gap-extend", argv[++ai], &af.extend)) return 2; af.has_extend = true; }
@@ -840,7 +853,7 @@ int main(int argc, char** argv) {
         else if (f == "--record-b" && ai + 1 < argc) rec_b = strtoll(argv[++ai], nullptr, 10);
         else if (f == "--seed" && ai + 1 < argc) seed = (unsigned)strtoul(argv[++ai], nullptr, 10);
         else if (f == "--scores" && ai + 3 < argc) { sc.match = atoi(argv[++ai]); sc.mismatch = atoi(argv[++ai]); sc.gap = atoi(argv[++ai]); }
-        else { fprintf(stderr, "usage: smithW [<cols> <rows> | --fasta A.fa B.fa [--record-a I] [--record-b J] | --search QUERY.fa DB.fa [--record-a I] [--top K] [--all-queries [--min-score S] [--prefilter S | --prefilter-hits S [--pairs-lanes 16|32]] [--search-lanes 16|32]] [--pairs FILE [--pairs-lanes 16|32]] [--matrix FILE] [--gap-open O] [--gap-extend E] [--align [--align-checkpoint]] | --search --pssm FILE DB.fa --gap-open O --gap-extend E [--top K] [--min-score S] [--align] [--search-lanes 16|32] | with --all-queries or --pssm: [--iterations N] [--include-score S] [--prior-weight W] [--out-pssm PREFIX]] [--seed N] [--dump | --dump-labels] [--h64] [--no-backtrack] [--scores M X G] [--gpus N | --devices 0,1,..] [--p8]\n"); return 2; }
+        else { fprintf(stderr, "usage: smithW [<cols> <rows> | --fasta A.fa B.fa [--record-a I] [--record-b J] | --search QUERY.fa DB.fa [--record-a I] [--top K] [--all-queries [--min-score S] [--prefilter S | --prefilter-hits S [--pairs-lanes 16|32]] [--search-lanes 16|32]] [--pairs FILE [--pairs-lanes 16|32]] [--matrix FILE] [--gap-open O] [--gap-extend E] [--align [--align-checkpoint]] | --search --pssm FILE DB.fa --gap-open O --gap-extend E [--top K] [--min-score S] [--align] [--search-lanes 16|32] | with --all-queries or --pssm: [--iterations N] [--include-score S] [--prior-weight W] [--out-pssm PREFIX] [--weight-hits P: Henikoff weights on the device, N[j] then counts in units of P, so scale --prior-weight with it]] [--seed N] [--dump | --dump-labels] [--h64] [--no-backtrack] [--scores M X G] [--gpus N | --devices 0,1,..] [--p8]\n"); return 2; }
     }
     if (npos == 1) { fprintf(stderr, "smithW: <cols> needs <rows>\n"); return 2; }
     if (align_ckpt && !(search_q && align)) { fprintf(stderr, "smithW: --align-checkpoint goes with --search --align\n"); return 2; }
@@ -860,6 +873,10 @@ int main(int argc, char** argv) {
         if (has_prefilter || has_prefilter_hits || pairs_path) { fprintf(stderr, "smithW: --iterations does not go with --prefilter / --prefilter-hits / --pairs\n"); return 2; }
     }
     const bool iterate = iterations > 1 || out_pssm;   // (--iterations 1 alone is the search of today, through today's path)
+    if (has_weight_hits) {   // the weights feed the update of an iterative search and nothing else
+        if (!(has_iter_flag && iterate)) { fprintf(stderr, "smithW: --weight-hits goes with --iterations N (N > 1) or --out-pssm\n"); return 2; }
+        if (weight_hits < 1 || weight_hits > 65535) { fprintf(stderr, "smithW: --weight-hits P needs P within 1..65535, got %d\n", weight_hits); return 2; }
+    }
     if (pssm_path) {   // the matrix is the query and the scoring at once
         if (af.matrix) { fprintf(stderr, "smithW: --pssm does not go with --matrix\n"); return 2; }
         if (all_queries) { fprintf(stderr, "smithW: --pssm does not go with --all-queries (the file is the one query)\n"); return 2; }
@@ -868,7 +885,7 @@ int main(int argc, char** argv) {
         if (!af.has_open || !af.has_extend) { fprintf(stderr, "smithW: --pssm needs --gap-open O and --gap-extend E\n"); return 2; }
         if (iterate) {
             if (sc.match < -128 || sc.match > 127 || sc.mismatch < -128 || sc.mismatch > 127) { fprintf(stderr, "smithW: --pssm --iterations takes its table from --scores M X within -128..127, got %d %d\n", sc.match, sc.mismatch); return 2; }
-            return search_iter_main(nullptr, pssm_path, search_db, top, min_score, sc, af, align, align_ckpt, search_lanes, iterations, include_score, prior_weight, out_pssm);
+            return search_iter_main(nullptr, pssm_path, search_db, top, min_score, sc, af, align, align_ckpt, search_lanes, iterations, include_score, prior_weight, out_pssm, weight_hits);
         }
         return search_pssm_main(pssm_path, search_db, top, min_score, af, align, align_ckpt, search_lanes);
     }
@@ -917,7 +934,7 @@ int main(int argc, char** argv) {
                 fprintf(stderr, "smithW: --all-queries without --matrix needs --scores M X within -128..127 (a table of signed bytes), got %d %d\n", sc.match, sc.mismatch);
                 return 2;
             }
-            if (iterate) return search_iter_main(search_q, nullptr, search_db, top, min_score, sc, af, align, align_ckpt, search_lanes, iterations, include_score, prior_weight, out_pssm);
+            if (iterate) return search_iter_main(search_q, nullptr, search_db, top, min_score, sc, af, align, align_ckpt, search_lanes, iterations, include_score, prior_weight, out_pssm, weight_hits);
             return search_all_main(search_q, search_db, top, min_score, sc, af, align, align_ckpt, prefilter_hits, search_lanes, pairs_lanes);
         }
         if (has_min_score) { fprintf(stderr, "smithW: --min-score goes with --search --all-queries\n"); return 2; }

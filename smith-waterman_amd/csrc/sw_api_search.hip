@@ -843,6 +843,34 @@ int sw_db_align_pssm_hits(sw_ctx* c, const sw_db* db, const int8_t* d_pssm, cons
                               ops_cap, stream_);
 }
 
+// The small table of sw_db_pssm_from_hits and sw_db_pssm_hit_weights: one device copy (d_phtab), at least `need` bytes after this, and
+// the pinned copy h_phtab[*turn_out] the caller fills and uploads, recording phtab_ev[*turn_out] behind the upload.
+static int pssm_table_turn(const char* who, sw_ctx* c, hipStream_t stream, size_t need, int* turn_out) {
+    // two pinned copies in turn: this call overwrites the copy of the call before the last one, and waits (on the host) for THAT upload only
+    const int turn = c->phtab_turn;
+    *turn_out = turn;
+    c->phtab_turn ^= 1;
+    if (c->phtab_ev[turn]) HIP_TRY(hipEventSynchronize(c->phtab_ev[turn]));
+    else HIP_TRY(hipEventCreateWithFlags(&c->phtab_ev[turn], hipEventDisableTiming));
+    if (need > c->d_phtab.cap) {
+        HIP_TRY(hipStreamSynchronize(stream));                   // launches in flight may still read the old table
+        if (c->phtab_ev[turn ^ 1]) HIP_TRY(hipEventSynchronize(c->phtab_ev[turn ^ 1]));   // ... and an upload the other copy
+        if (c->d_phtab) HIP_TRY(hipFree(c->d_phtab));
+        c->d_phtab.p = nullptr; c->d_phtab.cap = 0;
+        for (int i = 0; i < 2; ++i) {
+            if (c->h_phtab[i]) HIP_TRY(hipHostFree(c->h_phtab[i]));
+            c->h_phtab[i] = nullptr;
+        }
+        if (hipMalloc((void**)&c->d_phtab.p, need) != hipSuccess || hipHostMalloc((void**)&c->h_phtab[0], need, 0) != hipSuccess ||
+            hipHostMalloc((void**)&c->h_phtab[1], need, 0) != hipSuccess) {
+            set_err("%s: workspace allocation of %zu bytes failed", who, need);
+            return SW_ENOMEM;
+        }
+        c->d_phtab.cap = need;
+    }
+    return SW_OK;
+}
+
 // The next iteration's PSSM from a device hit table, its alignments and their ops (csrc/sw_pssm_hits.hip).  The host checks the
 // arguments, cuts the tiles (swp::plan_pssm_hits) and uploads one small table through two pinned copies of its own, used in turn -- S
 // (nletters x nletters), the 256-byte code table, the nqueries + 1 offsets --; the hit table, the alignments, the ops, the weights and the targets'
@@ -869,27 +897,8 @@ int sw_db_pssm_from_hits(sw_ctx* c, const sw_db* db, const int8_t* d_prior, cons
     // the call's table: S, padded to 256 bytes, the code table, the offsets
     const int n = scoring->nletters;
     const size_t s_bytes = ((size_t)n * n + 255) & ~(size_t)255, off_bytes = (size_t)(nqueries + 1) * sizeof(int64_t), need = s_bytes + 256 + off_bytes;
-    // two pinned copies in turn: this call overwrites the copy of the call before the last one, and waits (on the host) for THAT upload only
-    const int turn = c->phtab_turn;
-    c->phtab_turn ^= 1;
-    if (c->phtab_ev[turn]) HIP_TRY(hipEventSynchronize(c->phtab_ev[turn]));
-    else HIP_TRY(hipEventCreateWithFlags(&c->phtab_ev[turn], hipEventDisableTiming));
-    if (need > c->d_phtab.cap) {
-        HIP_TRY(hipStreamSynchronize(stream));                   // launches in flight may still read the old table
-        if (c->phtab_ev[turn ^ 1]) HIP_TRY(hipEventSynchronize(c->phtab_ev[turn ^ 1]));   // ... and an upload the other copy
-        if (c->d_phtab) HIP_TRY(hipFree(c->d_phtab));
-        c->d_phtab.p = nullptr; c->d_phtab.cap = 0;
-        for (int i = 0; i < 2; ++i) {
-            if (c->h_phtab[i]) HIP_TRY(hipHostFree(c->h_phtab[i]));
-            c->h_phtab[i] = nullptr;
-        }
-        if (hipMalloc((void**)&c->d_phtab.p, need) != hipSuccess || hipHostMalloc((void**)&c->h_phtab[0], need, 0) != hipSuccess ||
-            hipHostMalloc((void**)&c->h_phtab[1], need, 0) != hipSuccess) {
-            set_err("%s: workspace allocation of %zu bytes failed", who, need);
-            return SW_ENOMEM;
-        }
-        c->d_phtab.cap = need;
-    }
+    int turn = 0;
+    if (int rc = pssm_table_turn(who, c, stream, need, &turn)) return rc;
     unsigned char* h_tab = c->h_phtab[turn];
     swh::pssm_update_table(upd->sub, scoring->letters, n, (int8_t*)h_tab);
     memcpy(h_tab + s_bytes, code, 256);
@@ -909,6 +918,59 @@ int sw_db_pssm_from_hits(sw_ctx* c, const sw_db* db, const int8_t* d_prior, cons
     hipLaunchKernelGGL(swk::sw_pssm_from_hits, dim3((unsigned)plan.grid), dim3(256), plan.lds_bytes, stream, kp);
     HIP_TRY(hipGetLastError());
     c->last_pssm_hits_launches = plan.launches;
+    return SW_OK;
+}
+
+// The weights of a device hit table's entries (csrc/sw_pssm_weights.hip): the d_weights of the call above.  The host checks the
+// arguments, plans (swp::plan_pssm_weights) and uploads the code table and the offsets through the small table of the call above; one
+// memset zeroes the entries' accumulators, then the tile launch and the finish launch.  A handle without targets takes the same
+// launches (no entry is used: every weight is 0).
+int sw_db_pssm_hit_weights(sw_ctx* c, const sw_db* db, const int64_t* qoffsets, int64_t nqueries, const sw_pssm_scoring* scoring,
+                           const sw_pssm_weighting* weighting, const sw_hit* d_hits, const int64_t* d_nhits, int64_t top, const sw_alignment* d_aln,
+                           const char* d_ops, int64_t ops_cap, int32_t* d_weights, void* stream_) {
+    const char* who = "sw_db_pssm_hit_weights";
+    if (int rc = check_db_call(who, c, db, qoffsets && scoring)) return rc;
+    int64_t maxq = 0;
+    unsigned char code[256];
+    if (int rc = swh::check_search_pssm(who, qoffsets, nqueries, db->longest, scoring, &maxq, code)) return rc;
+    if (int rc = swh::check_pssm_weighting(who, weighting, top, d_hits, d_aln, d_ops, ops_cap, d_weights)) return rc;
+    c->last_pssm_weights_launches = c->last_pssm_weights_tiles = 0;   // (a call that launches no kernel reports none)
+    if (nqueries == 0) return SW_OK;
+    hipStream_t stream = (hipStream_t)stream_;
+    HIP_TRY(hipSetDevice(c->device));
+    const std::vector<int64_t> qlens = query_lengths(qoffsets, nqueries);
+    swp::PssmWeightsJob pj;
+    pj.queries.qlens = qlens.data(); pj.queries.nqueries = nqueries; pj.queries.nletters = scoring->nletters; pj.queries.num_cus = c->num_cus;
+    pj.top = top;
+    const swp::PssmWeightsPlan plan = swp::plan_pssm_weights(pj);
+    DevOrder order(c, stream, false);
+    if (order.rc) return order.rc;
+    if (int rc = c->d_pwacc.grow((size_t)plan.acc_entries, stream)) return rc;
+    // the call's table: the code table, the offsets
+    const size_t off_bytes = (size_t)(nqueries + 1) * sizeof(int64_t), need = 256 + off_bytes;
+    int turn = 0;
+    if (int rc = pssm_table_turn(who, c, stream, need, &turn)) return rc;
+    unsigned char* h_tab = c->h_phtab[turn];
+    memcpy(h_tab, code, 256);
+    memcpy(h_tab + 256, qoffsets, off_bytes);
+    HIP_TRY(hipMemcpyAsync(c->d_phtab, h_tab, need, hipMemcpyHostToDevice, stream));
+    HIP_TRY(hipEventRecord(c->phtab_ev[turn], stream));
+    HIP_TRY(hipMemsetAsync(c->d_pwacc, 0, (size_t)plan.acc_bytes, stream));
+    swk::PssmWeightsParams kp;
+    memset(&kp, 0, sizeof kp);
+    kp.code = c->d_phtab.p; kp.qoffs = (const int64_t*)(c->d_phtab + 256);
+    kp.db = (const unsigned char*)db->d_db; kp.offsets = db->d_offsets; kp.ntargets = db->ntargets;
+    kp.hits = d_hits; kp.nhits = d_nhits; kp.top = top;
+    kp.aln = d_aln; kp.ops = d_ops; kp.ops_cap = ops_cap;
+    kp.acc = c->d_pwacc; kp.weights = d_weights;
+    kp.nqueries = nqueries; kp.tiles_per_query = plan.tiles.tiles_per_query;
+    kp.include_min = weighting->include_min_score;
+    kp.nletters = scoring->nletters; kp.stride = plan.tiles.stride; kp.tile_cols = plan.tiles.tile_cols; kp.per_hit = weighting->per_hit;
+    hipLaunchKernelGGL(swk::sw_pssm_weights_tile, dim3((unsigned)plan.tiles.grid), dim3(256), plan.tiles.lds_bytes, stream, kp);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(swk::sw_pssm_weights_finish, dim3((unsigned)plan.finish_grid), dim3(256), 0, stream, kp);
+    HIP_TRY(hipGetLastError());
+    c->last_pssm_weights_launches = plan.launches; c->last_pssm_weights_tiles = plan.tiles.tiles_per_query;
     return SW_OK;
 }
 

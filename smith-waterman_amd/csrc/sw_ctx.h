@@ -25,6 +25,8 @@ int check_prefilter(const char* who, int64_t min_score, const void* pairs, int64
 int check_align_hits(const char* who, int64_t top, const void* hits, const void* aln, const void* ops, int64_t ops_cap);
 SW_HIDDEN int check_pssm_update(const char* who, const sw_pssm_update* upd, int64_t top, const void* hits, const void* aln, const void* ops, int64_t ops_cap,
                                 const void* out, const void* counts);                                 // sw_pssm_read.cpp
+SW_HIDDEN int check_pssm_weighting(const char* who, const sw_pssm_weighting* wt, int64_t top, const void* hits, const void* aln, const void* ops,
+                                   int64_t ops_cap, const void* weights);                             // sw_pssm_read.cpp
 SW_HIDDEN void pssm_update_table(const sw_submat* sub, const char* letters, int n, int8_t* S);        // sw_pssm_read.cpp
 SW_HIDDEN int check_targets(const char* who, int64_t qlen, const int64_t* offsets, int64_t ntargets, int64_t* maxlen_out, int64_t* nonempty_out);
 }
@@ -258,6 +260,10 @@ struct SW_HIDDEN sw_ctx {
     hipEvent_t phtab_ev[2] = {nullptr, nullptr};
     int phtab_turn = 0;
     int64_t last_pssm_hits_launches = 0;
+    // the weights of aligned hits (sw_db_pssm_hit_weights): the entries' accumulators; its small table -- the code table, the query
+    // offsets -- goes through d_phtab and the two pinned copies above, in the same turns
+    Workspace<unsigned long long> d_pwacc;
+    int64_t last_pssm_weights_launches = 0, last_pssm_weights_tiles = 0;   // ... and the tiles of its longest query
     // ---- placement of the output matrices (sw_place.hip)
     int64_t opt_place_hold_gib = 0;     // sw_alloc_outputs: GiB a pair of small matrices may hold beside itself where no plain candidate is good (0: none)
     int64_t opt_place_budget_ms = 1500; // sw_alloc_outputs: time the search for a P in another class of the HBM may take

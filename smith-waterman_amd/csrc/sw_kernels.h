@@ -201,6 +201,24 @@ struct PssmHitsParams {
 };
 __global__ void sw_pssm_from_hits(PssmHitsParams p);
 
+// sw_pssm_weights.hip: the position-based weights of a hit table's entries (sw_db_pssm_hit_weights).  sw_pssm_weights_tile: one workgroup
+// per (query, tile of columns) with the tiles and the dynamic LDS of swp::plan_pssm_weights (those of plan_pssm_hits);
+// sw_pssm_weights_finish: one workgroup of 256 threads per query, static LDS.
+struct PssmWeightsParams {
+    const int64_t* qoffs;                        // device copy of the caller's nqueries + 1 offsets
+    const unsigned char* code;                   // 256 bytes: target byte -> its place in a column, 255 where it has none
+    const unsigned char* db; const int64_t* offsets; int64_t ntargets;   // the handle's bytes and its ntargets + 1 offsets on the device
+    const sw_hit* hits; const int64_t* nhits; int64_t top;               // the caller's tables, as sw_db_align_pssm_hits takes and leaves them
+    const sw_alignment* aln; const char* ops; int64_t ops_cap;
+    unsigned long long* acc;                     // nqueries x top, zero before the tile launch: T_r + (m_r << 40)
+    int* weights;                                // nqueries x top: every entry is written
+    int64_t nqueries, tiles_per_query;
+    int64_t include_min;
+    int nletters, stride, tile_cols, per_hit;
+};
+__global__ void sw_pssm_weights_tile(PssmWeightsParams p);
+__global__ void sw_pssm_weights_finish(PssmWeightsParams p);
+
 // sw_search_pairs.hip: the scores of a device list of (query, target) pairs (sw_db_search_affine_pairs).  Per (chunk of the list, group
 // of queries) two binning launches turn the usable pairs into work items, one list per class, heaviest bucket first
 // (swp::plan_search_pairs); one launch of sw_search_affine_pairs_wave<C> per class scores them.

@@ -858,6 +858,18 @@ PssmHitsPlan plan_pssm_hits(const PssmHitsJob& j) {
     return p;
 }
 
+PssmWeightsPlan plan_pssm_weights(const PssmWeightsJob& j) {
+    PssmWeightsPlan p;
+    p.tiles = plan_pssm_hits(j.queries);
+    if (j.queries.nqueries < 1) return p;
+    p.finish_grid = std::min(j.queries.nqueries, kPssmHitsGridMax);
+    // (nqueries x top x 8 stays inside 63 bits for every nqueries a caller's memory could hold offsets for)
+    p.acc_entries = j.queries.nqueries * std::clamp<int64_t>(j.top, 1, 4096);
+    p.acc_bytes = p.acc_entries * kPssmWeightsAccBytes;
+    p.launches = p.tiles.launches + 1;
+    return p;
+}
+
 void align_schedule(const int64_t* offsets, const int64_t* hits, int64_t nhits, swk::SearchItem* items) {
     std::vector<int64_t> order((size_t)nhits);
     for (int64_t h = 0; h < nhits; ++h) order[(size_t)h] = h;

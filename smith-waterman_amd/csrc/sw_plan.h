@@ -559,6 +559,28 @@ struct PssmHitsPlan {
 
 PssmHitsPlan plan_pssm_hits(const PssmHitsJob& job);
 
+// ---- the position-based weights of aligned hits (sw_db_pssm_hit_weights; sw_pssm_weights.hip).  Two launches.  The first keeps a
+// tile's int32 counts, then its terms, in the LDS layout of the update above -- the spare dword of a column holds k_j in the place of
+// N[j] --, so its tiles, stride, grid and LDS are plan_pssm_hits' for the same queries and letters: `tiles`.  The tiles of an entry add
+// their share to the entry's 64-bit accumulator in the workspace (kPssmWeightsAccBytes per entry, nqueries x top of them, zeroed by a
+// memset before the launch).  The second launch runs one workgroup of 256 threads per query, walked in strides of at most
+// kPssmHitsGridMax workgroups, with the query's top <= SW_TOP_MAX values A_r in static LDS.
+constexpr int64_t kPssmWeightsAccBytes = 8;
+
+struct PssmWeightsJob {
+    PssmHitsJob queries;                     // the queries, the letters and the device, as for the update
+    int64_t top = 1;                         // 1..SW_TOP_MAX
+};
+
+struct PssmWeightsPlan {
+    PssmHitsPlan tiles;                      // the first launch (tiles.launches counts that launch alone)
+    int64_t finish_grid = 0;                 // workgroups of the second launch (0: no query)
+    int64_t acc_entries = 0, acc_bytes = 0;  // the accumulators
+    int launches = 0;                        // kernel launches of the call ("last_pssm_weights_launches")
+};
+
+PssmWeightsPlan plan_pssm_weights(const PssmWeightsJob& job);
+
 // ---- alignment of chosen hits under affine scoring (sw_align_affine_device): sw_align_affine_wave<C> for C = 4, 8, 16, its index in
 // kAlignAffine (sw_api_search.hip, which checks its order against it at compile time)
 constexpr int kAlignAffineKernels = 3;

@@ -157,6 +157,19 @@ int check_pssm_update(const char* who, const sw_pssm_update* upd, int64_t top, c
     return SW_OK;
 }
 
+// What sw_db_pssm_hit_weights and sw_pssm_hit_weights_host check beyond the search arguments: the table arguments as above.
+__attribute__((visibility("hidden"))) int check_pssm_weighting(const char* who, const sw_pssm_weighting* wt, int64_t top, const void* hits, const void* aln,
+                                                               const void* ops, int64_t ops_cap, const void* weights);
+int check_pssm_weighting(const char* who, const sw_pssm_weighting* wt, int64_t top, const void* hits, const void* aln, const void* ops, int64_t ops_cap,
+                         const void* weights) {
+    if (!wt || !weights) { set_err("%s: NULL weighting rule or weight table", who); return SW_EINVAL; }
+    if (top < 1 || top > SW_TOP_MAX) { set_err("%s: top = %lld is out of range 1..%d", who, (long long)top, SW_TOP_MAX); return SW_EINVAL; }
+    if (!hits || !aln || !ops) { set_err("%s: NULL hit table, alignment array or ops buffer", who); return SW_EINVAL; }
+    if (ops_cap < 1) { set_err("%s: ops_cap = %lld is below 1", who, (long long)ops_cap); return SW_EINVAL; }
+    if (wt->per_hit < 1 || wt->per_hit > 65535) { set_err("%s: per_hit = %d is out of range 1..65535", who, wt->per_hit); return SW_EINVAL; }
+    return SW_OK;
+}
+
 // S[b * n + k] = sub[letters[b]][letters[k]]: the observed residue letters[b] plays the query letter.
 void pssm_update_table(const sw_submat* sub, const char* letters, int n, int8_t* S) {
     for (int b = 0; b < n; ++b)
@@ -272,6 +285,87 @@ int sw_pssm_from_hits_host(const int8_t* prior, const int64_t* qoffsets, int64_t
                 pssm_out[(g0 + j) * n + k] = (int8_t)v;
             }
         }
+    }
+    return SW_OK;
+}
+
+}  // extern "C"
+
+namespace {
+
+// at(j, k) for every pair of column j with letters[k] that the used entries of query q make, entry by entry; begin(r) ahead of the
+// pairs of the used entry r.  The guards and the walk are those of sw_pssm_from_hits_host, stated once for the two passes below.
+template <typename Begin, typename At>
+void for_each_counted_pair(int64_t q, int64_t qlen, const char* db, const int64_t* offsets, int64_t ntargets, const int* code, int64_t include_min,
+                           const sw_hit* hits, const int64_t* nhits, int64_t top, const sw_alignment* aln, const char* ops, int64_t ops_cap, Begin begin, At at) {
+    const int64_t nh = nhits ? std::clamp<int64_t>(nhits[q], 0, top) : top;
+    for (int64_t r = 0; r < nh; ++r) {
+        const int64_t e = q * top + r;
+        const uint64_t t = (uint64_t)hits[e].target;
+        if (t >= (uint64_t)ntargets) continue;
+        const sw_alignment& a = aln[e];
+        if (a.max_score < include_min || a.nops <= 0 || a.nops > ops_cap) continue;
+        const int64_t len = offsets[t + 1] - offsets[t];
+        if ((uint64_t)a.q_begin > (uint64_t)qlen || (uint64_t)a.t_begin > (uint64_t)len) continue;
+        begin(r);
+        const unsigned char* tb = (const unsigned char*)db + offsets[t];
+        const char* row = ops + e * ops_cap;
+        int64_t j = a.q_begin, i = a.t_begin;
+        for (int64_t o = 0; o < a.nops; ++o) {
+            const char op = row[o];
+            if (op == 'M') {
+                if (j < qlen && i < len && code[tb[i]] >= 0) at(j, code[tb[i]]);
+                ++j; ++i;
+            } else if (op == 'I') ++j;
+            else if (op == 'D') ++i;
+        }
+    }
+}
+
+}  // namespace
+
+extern "C" {
+
+// The CPU leg of sw_db_pssm_hit_weights: per query n[j][k] and k_j from one walk of its used entries, T_r and m_r from a second, then
+// A_r, their sum and the rounded shares.  Everything is checked before the first weight is written.
+int sw_pssm_hit_weights_host(const int64_t* qoffsets, int64_t nqueries, const char* db, const int64_t* offsets, int64_t ntargets,
+                             const sw_pssm_scoring* scoring, const sw_pssm_weighting* weighting, const sw_hit* hits, const int64_t* nhits, int64_t top,
+                             const sw_alignment* aln, const char* ops, int64_t ops_cap, int32_t* weights) {
+    const char* who = "sw_pssm_hit_weights_host";
+    if (!qoffsets || !db || !offsets || !scoring) { swh::set_err("%s: NULL pointer", who); return SW_EINVAL; }
+    if (int rc = check_host_args(who, qoffsets, nqueries, offsets, ntargets, scoring)) return rc;
+    if (int rc = swh::check_pssm_weighting(who, weighting, top, hits, aln, ops, ops_cap, weights)) return rc;
+    const int n = scoring->nletters;
+    constexpr int64_t F = 1ll << 20;
+    int code[256];
+    std::fill(code, code + 256, -1);
+    for (int k = 0; k < n; ++k) code[(unsigned char)scoring->letters[k]] = k;
+    std::vector<int32_t> N, K;
+    std::vector<int64_t> T((size_t)top), m((size_t)top), A((size_t)top);
+    for (int64_t q = 0; q < nqueries; ++q) {
+        const int64_t qlen = qoffsets[q + 1] - qoffsets[q];
+        N.assign((size_t)(qlen * n), 0);
+        K.assign((size_t)qlen, 0);
+        std::fill(T.begin(), T.end(), 0);
+        std::fill(m.begin(), m.end(), 0);
+        for_each_counted_pair(q, qlen, db, offsets, ntargets, code, weighting->include_min_score, hits, nhits, top, aln, ops, ops_cap, [](int64_t) {},
+                              [&](int64_t j, int k) { ++N[(size_t)(j * n + k)]; });
+        for (int64_t j = 0; j < qlen; ++j)
+            for (int k = 0; k < n; ++k) K[(size_t)j] += N[(size_t)(j * n + k)] > 0;
+        int64_t cur = 0;
+        for_each_counted_pair(q, qlen, db, offsets, ntargets, code, weighting->include_min_score, hits, nhits, top, aln, ops, ops_cap, [&](int64_t r) { cur = r; },
+                              [&](int64_t j, int k) {
+                                  T[(size_t)cur] += F / ((int64_t)K[(size_t)j] * N[(size_t)(j * n + k)]);
+                                  ++m[(size_t)cur];
+                              });
+        int64_t U = 0, sum = 0;
+        for (int64_t r = 0; r < top; ++r) {
+            A[(size_t)r] = m[(size_t)r] > 0 ? T[(size_t)r] / m[(size_t)r] : 0;
+            U += A[(size_t)r] > 0;
+            sum += A[(size_t)r];
+        }
+        for (int64_t r = 0; r < top; ++r)
+            weights[q * top + r] = sum > 0 ? (int32_t)std::min<int64_t>(65535, (2 * (int64_t)weighting->per_hit * U * A[(size_t)r] + sum) / (2 * sum)) : 0;
     }
     return SW_OK;
 }

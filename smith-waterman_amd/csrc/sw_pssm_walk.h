@@ -1,0 +1,52 @@
+// sw_pssm_walk.h -- what kernels that read a hit table's alignments share (gfx950): the guards that make entry (q, r) a USED ENTRY and
+// THE WALK of its ops, as include/swhip.h states them for sw_db_pssm_from_hits.  One wave per entry; everything is __forceinline__ inside
+// an unnamed namespace, as in sw_wave.h.  Both passes of sw_pssm_weights.hip go through it.  sw_pssm_from_hits (sw_pssm_hits.hip) keeps
+// its own text of the same guards and walk: moved onto this header its assembly differs from what it was, and that kernel
+// was to stay byte for byte.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include "../../include/swhip.h"
+
+namespace swk {
+
+namespace {
+
+// Entry e = q * top + r (r below the query's clamped count) of a query of qlen columns: is it used?  Entry and alignment are loaded at
+// wave-uniform addresses, and every index is compared, unsigned, before anything is loaded through it.  A used entry leaves its
+// alignment, its target's first byte in the database and its target's length.
+__device__ __forceinline__ bool sw_pssm_entry_used(const sw_hit* hits, const sw_alignment* aln, const int64_t* offsets, int64_t ntargets, int64_t e, int64_t qlen,
+                                                   int64_t include_min, int64_t ops_cap, sw_alignment& a, int64_t& toff, int64_t& len) {
+    const uint64_t t = (uint64_t)hits[e].target;
+    if (t >= (uint64_t)ntargets) return false;
+    a = aln[e];
+    if (a.max_score < include_min || a.nops <= 0 || a.nops > ops_cap) return false;
+    toff = offsets[t];
+    len = offsets[t + 1] - toff;
+    return (uint64_t)a.q_begin <= (uint64_t)qlen && (uint64_t)a.t_begin <= (uint64_t)len;
+}
+
+// Can the columns [q_begin, q_begin + nops) of a used entry reach the tile [c0, c1)?  (no sum of two table values: none can overflow)
+__device__ __forceinline__ bool sw_pssm_reaches_tile(const sw_alignment& a, int64_t c0, int64_t c1) { return a.q_begin < c1 && a.nops > c0 - a.q_begin; }
+
+// The walk of a used entry through the tile of columns [c0, c1), c1 <= qlen, by one wave: the ops 64 at a time, one op per lane: one
+// ballot of "consumes a query column", one of "consumes a target byte"; the number of set bits below a lane (mbcnt) gives the lane its
+// (j, i), the popcounts advance the wave-uniform bases.  No serial walk, no scan.  at_pair(j, i) runs in every 'M' lane whose column
+// lies in the tile and whose target byte inside the target.  The walk ends with the tile: j only grows.
+template <typename F>
+__device__ __forceinline__ void sw_pssm_walk(const unsigned char* ops, const sw_alignment& a, int64_t len, int64_t c0, int64_t c1, int lane, F&& at_pair) {
+    int64_t jb = a.q_begin, ib = a.t_begin;                          // wave-uniform bases of the chunk
+    for (int64_t o = 0; o < a.nops && jb < c1 && ib < len; o += 64) {
+        const int op = o + lane < a.nops ? (int)ops[o + lane] : 0;
+        const bool m = op == 'M';
+        const uint64_t bq = __ballot(m || op == 'I'), bt = __ballot(m || op == 'D');
+        const int64_t j = jb + (int64_t)__builtin_amdgcn_mbcnt_hi((unsigned)(bq >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)bq, 0u));
+        const int64_t i = ib + (int64_t)__builtin_amdgcn_mbcnt_hi((unsigned)(bt >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)bt, 0u));
+        if (m && j >= c0 && j < c1 && i < len) at_pair(j, i);
+        jb += __popcll(bq); ib += __popcll(bt);
+    }
+}
+
+}  // namespace
+
+}  // namespace swk
