@@ -11,7 +11,7 @@
 //   boundary column and packed arg-max key hold here word for word).  A lane that has just finished row (b + 1) B of a band that is not
 //   the hit's last stores its C values of h and of e (already advanced to the next row) into checkpoint b.  The boundary column between
 //   two strips is a band's, not the hit's.
-//   Pass 2, the bands the walk enters: the direction fill of sw_align_affine_wave into the slot's band, resumed from checkpoint b - 1
+//   Pass 2, the bands the walk enters: the direction fill (sw_align_dirfill.inc defines the byte) into the slot's band, resumed from checkpoint b - 1
 //   (h, e of the lane's columns; diag0 = H[bB][c0 - 1], the column left of the lane's first, from the same checkpoint row), for the
 //   strips at or left of the walk's column only.
 //   A hit of one band (len <= B) has no checkpoint and no sweep: its only band is filled at once, arg-max included, as today.
@@ -21,14 +21,13 @@
 // h, e and diag0 of the lanes whose band row is still <= 0 under a select (and keeps them out of the arg-max); the steady loop is the
 // whole-matrix kernels' own.
 //
-// The walk is sw_align_affine_wave's three-state walk over 64 x 64 LDS windows with two changes: a window is clipped at the first row
-// of the band in the slot, and a look-back into a row above that band is "not known" rather than an answer.  When the cell the lanes
-// look back from leaves the band, the wave re-fills the band above it and goes on.  The walk stays two-pass (count, then write the ops
-// in alignment order, left-justified, only where all of them fit); the second pass re-fills the bands it needs again -- none when the
-// alignment stayed inside one band.  Nothing is written outside the hit's ops_cap bytes.
+// The walk is the text of sw_align_walk.inc, which the whole-matrix kernels run too: it clips a window to the rows the slot holds and
+// takes a look-back into a row above them as "not known".  What this file adds is the walk's hook: when the cell the lanes look back
+// from leaves the band in the slot, the wave re-fills the band above it and goes on.  The second pass of the walk re-fills the bands it
+// needs again -- none when the alignment stayed inside one band.
 //
 // Visibility: only the wave that wrote a slot reads it; it drains vmcnt before the first read of a checkpoint row or of a band, and
-// every such read is an sc1 buffer load (served from the L2: sw_align_affine.hip has the argument).  Offsets: every 32-bit offset lies
+// every such read is an sc1 buffer load (served from the L2: sw_align_walk.inc has the argument).  Offsets: every 32-bit offset lies
 // within a band, a checkpoint area or a boundary column of one band; the target is addressed through a descriptor per band whose base
 // is a 64-bit pointer.  All global writes are vector stores.
 #include <hip/hip_runtime.h>
@@ -39,8 +38,6 @@
 namespace swk {
 
 namespace {
-
-constexpr int AK_SC1 = 16;              // aux bit of the buffer builtins: sc1
 
 // C ints of a lane in a checkpoint row: C / 4 vector stores / sc1 loads of 16 bytes (16 / 32 / 64 bytes per lane)
 template <int C>
@@ -53,12 +50,10 @@ template <int C>
 __device__ __forceinline__ void ak_load_ints(__amdgpu_buffer_rsrc_t r, u32 off, int (&v)[C]) {
 #pragma unroll
     for (int q = 0; q < C / 4; ++q) {
-        const sw_v4i x = __builtin_amdgcn_raw_buffer_load_b128(r, (int)off, 16 * q, AK_SC1);
+        const sw_v4i x = __builtin_amdgcn_raw_buffer_load_b128(r, (int)off, 16 * q, SW_SC1);
         v[4 * q] = x.x; v[4 * q + 1] = x.y; v[4 * q + 2] = x.z; v[4 * q + 3] = x.w;
     }
 }
-
-constexpr int AK_WIN = 64;              // the walk's window: AK_WIN rows of AK_WIN direction bytes per wave
 
 // What a wave keeps over all its hits: its slot (band, checkpoints, boundary column), its LDS window and the scoring.
 struct AkWave {
@@ -90,6 +85,11 @@ __device__ __forceinline__ void ak_align_hit(const AkWave& w, const AkHit& hit) 
     const int64_t band_want = (int64_t)(len < B ? len : B) * (int64_t)qpad;
     const int64_t band_bytes = band_want < w.slot_bytes ? band_want : w.slot_bytes;   // (the planner sized the slot for more: never beyond it)
     const __amdgpu_buffer_rsrc_t rB = w.rB, rQ = hit.rQ;
+    // the walk's names for the hit's ops (sw_align_walk.inc).  References: copies made here move the instructions of all six kernels
+    const __amdgpu_buffer_rsrc_t& rO = hit.rO;
+    const int64_t& ops_cap = hit.ops_cap;
+    const bool& has_ops = hit.has_ops;
+    using walk_round_t = u64;
     const __amdgpu_buffer_rsrc_t rD = __builtin_amdgcn_make_buffer_rsrc((void*)w.slot, 0, (int)band_bytes, 0x00020000);
     const __amdgpu_buffer_rsrc_t rK = __builtin_amdgcn_make_buffer_rsrc((void*)(w.slot + band_bytes), 0, (int)(w.slot_bytes - band_bytes), 0x00020000);
     const int nbands = len > 0 ? (int)(((int64_t)len + B - 1) >> w.logB) : 1;
@@ -117,7 +117,7 @@ __device__ __forceinline__ void ak_align_hit(const AkWave& w, const AkHit& hit) 
             const u32 kin = (u32)(b - 1) * 8u * qpad + colb * 4u;
             ak_load_ints<C>(rK, kin, h);
             ak_load_ints<C>(rK, kin + 4u * qpad, e);
-            diag0 = __builtin_amdgcn_raw_buffer_load_b32(rK, colb ? (int)(kin - 4u) : (int)SW_OOB, 0, AK_SC1);   // H[b B][c0 - 1]; column 0: 0
+            diag0 = __builtin_amdgcn_raw_buffer_load_b32(rK, colb ? (int)(kin - 4u) : (int)SW_OOB, 0, SW_SC1);   // H[b B][c0 - 1]; column 0: 0
         } else {
 #pragma unroll
             for (int k = 0; k < C; ++k) { h[k] = 0; e[k] = goe; }
@@ -125,8 +125,8 @@ __device__ __forceinline__ void ak_align_hit(const AkWave& w, const AkHit& hit) 
         sw_v4i bq0 = {0, 0, 0, 0}, bq1 = {0, 0, 0, 0};
         const u32 voffB = lane == 0 ? 64u * 8u : SW_OOB;
         if (br) {
-            bq0 = __builtin_amdgcn_raw_buffer_load_b128(rB, (int)voffB, 0, AK_SC1);
-            bq1 = __builtin_amdgcn_raw_buffer_load_b128(rB, (int)voffB, 16, AK_SC1);
+            bq0 = __builtin_amdgcn_raw_buffer_load_b128(rB, (int)voffB, 0, SW_SC1);
+            bq1 = __builtin_amdgcn_raw_buffer_load_b128(rB, (int)voffB, 16, SW_SC1);
         }
         auto raw_of = [&](int g, int j) -> u32 {
             const u32 pos = (u32)(4 * g + j - lane - 1);
@@ -153,8 +153,8 @@ __device__ __forceinline__ void ak_align_hit(const AkWave& w, const AkHit& hit) 
             for (int j = 0; j < 4; ++j) raw[j] = raw_of(g + 2, j);
             const int bh[4] = {bq0.x, bq0.z, bq1.x, bq1.z}, bf[4] = {bq0.y, bq0.w, bq1.y, bq1.w};
             if (br) {
-                bq0 = __builtin_amdgcn_raw_buffer_load_b128(rB, (int)voffB, 32 * (g + 1), AK_SC1);
-                bq1 = __builtin_amdgcn_raw_buffer_load_b128(rB, (int)voffB, 32 * (g + 1) + 16, AK_SC1);
+                bq0 = __builtin_amdgcn_raw_buffer_load_b128(rB, (int)voffB, 32 * (g + 1), SW_SC1);
+                bq1 = __builtin_amdgcn_raw_buffer_load_b128(rB, (int)voffB, 32 * (g + 1) + 16, SW_SC1);
             }
             sw_for<0, 4>([&](auto J) {
                 constexpr int j = decltype(J)::value;
@@ -261,93 +261,27 @@ __device__ __forceinline__ void ak_align_hit(const AkWave& w, const AkHit& hit) 
     sw_v4i* const win = w.win;
     const unsigned char* const winb = (const unsigned char*)win;
     int cur = nbands == 1 ? 0 : -1;            // the band whose direction bytes the slot holds
-    int i0 = 0, j0 = 0, nops = 0;
-    for (int pass = 0; pass < 2; ++pass) {
-        if (pass == 1 && (nops == 0 || !hit.has_ops || (int64_t)nops > hit.ops_cap)) break;
-        int i = i1, j = j1, state = 0, n = 0;
-        int wr0 = 1 << 30, wcb = 1 << 30;      // first row and first byte column of the window in LDS (none yet)
-        bool done = score == 0;
-        // `cnt` ops `ch` behind the n already taken: the walk goes backwards, op k from the end lies at nops - 1 - k
-        auto emit = [&](int cnt, int ch) {
-            if (pass == 1) __builtin_amdgcn_raw_buffer_store_b8((unsigned char)ch, hit.rO, lane < cnt ? nops - 1 - n - lane : (int)SW_OOB, 0, 0);
-            n += cnt;
-        };
-        // (every round takes at least one op or changes the state once per op: the bound is never reached, it only keeps a damaged
-        //  band from holding the wave)
-        const u64 rounds = 2ull * ((u64)len + (u64)qlen) + 8;
-        for (u64 round = 0; !done && round < rounds; ++round) {
-            if (i < 1 || j < 1) break;          // H at the edge of the matrix: 0 (E and F leave for H before they get here)
-            // the cell the lanes look back from: (i, j) in H, one up in E, one left in F
-            const int ai = state == 2 ? i - 1 : i, aj = state == 3 ? j - 1 : j;
-            if (ai >= 1 && aj >= 1) {
-                const int need = (ai - 1) >> w.logB;
-                if (need != cur) {              // the anchor has left the band in the slot: fill its band, the strips up to its column
-                    const u64 t0 = w.stamps ? wall_clock64() : 0;
-                    const int last = (aj - 1) / (64 * C);
-                    for (int st = 0; st <= last; ++st) unit(std::true_type{}, need, st, false);
-                    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                    cur = need;
-                    wr0 = wcb = 1 << 30;
-                    if (w.stamps) refill_ticks += wall_clock64() - t0;
-                }
-            }
-            const int bf = (cur << w.logB) + 1;                       // first row of the band in the slot (cur >= 0 whenever a cell is inside)
-            if (ai >= 1 && aj >= 1 && (ai < wr0 || aj - 1 < wcb)) {
-                const int bl = (int)((int64_t)bf + B - 1 < (int64_t)len ? (int64_t)bf + B - 1 : (int64_t)len);
-                wr0 = ai - (AK_WIN - 1);
-                wcb = ((aj - 1) & ~15) - (AK_WIN - 16);
-                __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-                sw_v4i v[4];
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    const int row = wr0 + 16 * q + (lane >> 2), cb = wcb + 16 * (lane & 3);
-                    const bool in = row >= bf && row <= bl && cb >= 0;
-                    v[q] = __builtin_amdgcn_raw_buffer_load_b128(rD, in ? (int)((u32)(row - bf) * qpad + (u32)cb) : (int)SW_OOB, 0, AK_SC1);
-                }
-#pragma unroll
-                for (int q = 0; q < 4; ++q) win[(16 * q + (lane >> 2)) * (AK_WIN / 16) + (lane & 3)] = v[q];
-                __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-                __builtin_amdgcn_wave_barrier();
-            }
-            // lane l: the cell l steps back along the state's direction; `known`: outside the matrix (a fixed answer) or in the window
-            // AND in the band -- a row above the band is not known until its band has been filled
-            const int r = state == 3 ? ai : ai - lane, c = state == 2 ? aj : aj - lane;
-            const bool inside = r >= 1 && c >= 1, inwin = inside && r >= wr0 && r >= bf && c - 1 >= wcb;
-            const bool known = !inside || inwin;
-            const int bb = inwin ? (int)winb[(r - wr0) * AK_WIN + (c - 1 - wcb)] : 0;
-            if (state == 0) {
-                const u64 notdiag = ~__builtin_amdgcn_ballot_w64(known && (bb & 3) == 1);
-                const int run = notdiag ? (int)__builtin_ctzll(notdiag) : 64;
-                emit(run, 'M');
-                i -= run; j -= run;
-                if (run < 64 && __builtin_amdgcn_readlane((int)known, run)) {
-                    const int src = __builtin_amdgcn_readlane(bb, run) & 3;
-                    if (src == 0) done = true; else state = src;
-                }
-            } else {
-                const bool open = !inside || (bb & (state == 2 ? 4 : 8)) != 0;
-                const u64 stop = __builtin_amdgcn_ballot_w64(!known || open);
-                const int first = stop ? (int)__builtin_ctzll(stop) : 64;
-                // lanes 0 .. first - 1 extend; lane `first` opens (one more op, back to H) or lies beyond what is known
-                const bool opens = first < 64 && __builtin_amdgcn_readlane((int)known, first);
-                const int cnt = first + (opens ? 1 : 0);
-                emit(cnt, state == 2 ? 'D' : 'I');
-                if (state == 2) i -= cnt; else j -= cnt;
-                if (opens) state = 0;
-            }
-        }
-        if (pass == 0) { nops = n; i0 = i; j0 = j; }
-    }
-    {
-        const bool any = score != 0;
-        const sw_v4i v0 = {(int)(u32)pos, (int)(u32)(pos >> 32), (int)(u32)score, 0};
-        const sw_v4i v1 = {any ? j0 : 0, 0, any ? i0 : 0, 0};
-        const sw_v4i v2 = {any ? j1 : 0, 0, any ? i1 : 0, 0};
-        __builtin_amdgcn_raw_buffer_store_b128(v0, hit.rA, (int)voffL0, 0, 0);                    // max_pos, max_score
-        __builtin_amdgcn_raw_buffer_store_b128(v1, hit.rA, (int)voffL0, 16, 0);                   // q_begin, t_begin
-        __builtin_amdgcn_raw_buffer_store_b128(v2, hit.rA, (int)voffL0, 32, 0);                   // q_end, t_end
-        __builtin_amdgcn_raw_buffer_store_b64(sw_v2i{nops, 0}, hit.rA, (int)voffL0, 48, 0);       // nops
-    }
+    // The hook of the walk: when the cell the lanes look back from has left the band in the slot, fill its band, the strips up to its
+    // column, and forget the window; then the first and the last row of the band in the slot (cur >= 0 whenever a cell is inside).
+#define SW_WALK_BAND \
+    if (ai >= 1 && aj >= 1) { \
+        const int need = (ai - 1) >> w.logB; \
+        if (need != cur) { \
+            const u64 t0 = w.stamps ? wall_clock64() : 0; \
+            const int last = (aj - 1) / (64 * C); \
+            for (int st = 0; st <= last; ++st) unit(std::true_type{}, need, st, false); \
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); \
+            cur = need; \
+            wr0 = wcb = 1 << 30; \
+            if (w.stamps) refill_ticks += wall_clock64() - t0; \
+        } \
+    } \
+    const int bf = (cur << w.logB) + 1; \
+    const int bl = (int)((int64_t)bf + B - 1 < (int64_t)len ? (int64_t)bf + B - 1 : (int64_t)len);
+#define SW_WALK_ALN hit.rA
+#include "sw_align_walk.inc"
+#undef SW_WALK_BAND
+#undef SW_WALK_ALN
     if (w.stamps) {   // timing aid ("debug_buf", three words here): ticks of the 100 MHz clock in the sweep, the walk and its re-fills
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         const u64 tick2 = wall_clock64();
@@ -365,7 +299,7 @@ __device__ __forceinline__ void ak_align_hit(const AkWave& w, const AkHit& hit) 
 template <int C>
 __global__ void __launch_bounds__(256) sw_align_ckpt_wave(AlignCkptParams p) {
     static_assert(C % 4 == 0 && C <= 16, "C is a multiple of 4");
-    __shared__ sw_v4i win_all[4][AK_WIN * AK_WIN / 16];
+    __shared__ sw_v4i win_all[4][SW_WIN * SW_WIN / 16];
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const int64_t slot = (int64_t)blockIdx.x * (blockDim.x >> 6) + wave;     // resident wave: its own boundary column, band and checkpoints
@@ -400,7 +334,7 @@ __global__ void __launch_bounds__(256) sw_align_ckpt_wave(AlignCkptParams p) {
 template <int C>
 __global__ void __launch_bounds__(256) sw_align_hits_ckpt_wave(AlignHitsCkptParams p) {
     static_assert(C % 4 == 0 && C <= 16, "C is a multiple of 4");
-    __shared__ sw_v4i win_all[4][AK_WIN * AK_WIN / 16];
+    __shared__ sw_v4i win_all[4][SW_WIN * SW_WIN / 16];
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const int64_t slot = (int64_t)blockIdx.x * (blockDim.x >> 6) + wave;

@@ -1,6 +1,7 @@
 // sw_wave.h -- what the one-wave-per-item kernels (batch, search, affine search, alignment) share below their recurrences (gfx950):
-// the dropped buffer offset, the DPP moves, the profile row load / direction row store and the compile-time loop.  Everything is
-// __forceinline__ inside an unnamed namespace: linkage stays internal to the translation unit and nothing leaves a symbol.
+// the dropped buffer offset, the sc1 bit and the window size of the alignment kernels, the DPP moves, the profile row load / direction
+// row store and the compile-time loop.  Everything is __forceinline__ inside an unnamed namespace: linkage stays internal to the
+// translation unit and nothing leaves a symbol.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -16,6 +17,8 @@ typedef int sw_v4i __attribute__((ext_vector_type(4)));
 typedef int sw_v2i __attribute__((ext_vector_type(2)));
 
 constexpr u32 SW_OOB = 0xFFFFFF00u;     // buffer offset beyond every descriptor: the access is dropped (loads return 0)
+constexpr int SW_SC1 = 16;              // aux bit of the buffer builtins: sc1 (the alignment kernels read their own slot past the L1)
+constexpr int SW_WIN = 64;              // the alignment walk's window: SW_WIN rows of SW_WIN direction bytes per wave (sw_align_walk.inc)
 
 __device__ __forceinline__ int sw_dpp_shr1(int old, int src) {   // lane l <- lane l-1; lane 0 keeps `old`
     return __builtin_amdgcn_update_dpp(old, src, 0x138, 0xF, 0xF, false);
