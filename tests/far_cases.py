@@ -8,7 +8,10 @@ arrays, once per process, read-only.  No result depends on placement: max_pos is
 THE FAR RANGE.  Every far offset lies in [2^32, 2^32 + 2^31).  Its low 32 bits are then a small positive number whether a wrong kernel
 takes them as u32 or as int32, so a truncated address lands inside the same allocation at offset - 2^32.  There lies a DECOY: a second
 world of the same lengths from another seed whose result differs from the true one for every (query, non-empty target) pair -- a
-kernel (or a ctypes argtypes entry) that drops the high half shows as wrong values and never as a fault."""
+kernel (or a ctypes argtypes entry) that drops the high half shows as wrong values and never as a fault.
+
+The PSSM update and the hit weights read the same world through the reference's hit table and the rule's alignments (hits_case); their
+decoy condition (hits_decoy_failures) is part of decoy_failures(), and count_case() is the one case whose OUTPUT passes 4 GiB."""
 import functools
 
 import numpy as np
@@ -42,6 +45,16 @@ NATURAL_ORDER = list(range(NT))
 TAIL = 16                                          # spare bytes behind a payload
 WORLD_SEED, DECOY_SEED = 3315, 4635      # searched: the decoy condition of decoy_failures() holds for this pair
 TOP, MIN_SCORE, PREFILTER_MIN = 4, 1, 12           # the selecting calls of the small world
+NHITS_CUT = [4, 0, 3, 4, 2]                        # the counts of the alignment calls: unused entries in the table, one empty row
+# the update and the hit weights over the small world: hits_decoy_failures() is empty for these.  per_hit 16 rounds the shares of the
+# three-hit query to the same weights in the world and in the decoy; a prior weight of 2 beside weights of some 256 leaves the prior no
+# say (a decoy PRIOR would not show), so the weighted update takes 2 x per_hit; and two hits alone weigh the same whatever their
+# residues (every term is 1/2 or 1 by the columns they share, not by the letters), so the last query gets three.
+PRIOR_WEIGHT, PER_HIT, INCLUDE_MIN = 2, 256, 1
+PRIOR_WEIGHT_WEIGHTED = 2 * PER_HIT
+HITS_NHITS_CUT = [4, 0, 3, 4, 4]
+OPS_CAP = max(QLENS) + max(TLENS)
+OPS_POISON = 0xA5
 
 
 def table24():
@@ -230,6 +243,42 @@ def pair_results(exp, gaps, pairs, order=NATURAL_ORDER):
     return out
 
 
+# ---- the PSSM update and the hit weights over the small world ----
+
+def hits_case(exp, gaps, order=NATURAL_ORDER, nletters=24, targets=None, queries=None, nhits_cut=HITS_NHITS_CUT, hits=None):
+    """The small world as a case of tests/pssm_hits_cases.py, compact: the prior is the PSSM of the queries (pssm_of), the tables are
+    the reference's hit table in target order `order` (or `hits` = (hits, nhits)), cut to nhits_cut, with the rule's alignments and ops
+    (poison behind every row's ops), S is table24.  targets / queries: other sequences of the same lengths in the place of the world's
+    -- what a call would read had it dropped the high half of an address: the tables stay those of the true world."""
+    import types
+    w = world()
+    c = types.SimpleNamespace()
+    c.letters, c.smax, c.other = pssm_letters(nletters), SMAX, OTHER
+    c.qoffs = np.concatenate([[0], np.cumsum(QLENS)]).astype(np.int64)
+    c.prior = pssm_of(queries if queries is not None else w["queries"], nletters)
+    c.packed, c.offs = packed(targets if targets is not None else w["targets"], 0, order)
+    c.sub = table24()
+    h, n = hits if hits is not None else hit_table(exp, gaps, order)
+    c.hits, c.nhits = np.ascontiguousarray(h), np.minimum(n, nhits_cut).astype(np.int64)
+    c.aln, ops = alignments(exp, gaps, c.hits, c.nhits, order)
+    c.cap = OPS_CAP
+    c.ops = np.full((c.hits.shape[0] * c.hits.shape[1], OPS_CAP), OPS_POISON, np.uint8)
+    for q, row in enumerate(ops):
+        for r, o in enumerate(row):
+            c.ops[q * c.hits.shape[1] + r, :len(o)] = np.frombuffer(o, np.uint8)
+    return c
+
+
+def hits_want(c, weighted):
+    """(weights, new matrix, counts) of a case by the numpy rules (tests/pssm_weights_cases.py, tests/pssm_hits_cases.py): the weights
+    under PER_HIT, the update under PRIOR_WEIGHT_WEIGHTED with those weights or under PRIOR_WEIGHT with none."""
+    import pssm_hits_cases as hc
+    import pssm_weights_cases as wc
+    w = wc.reference(c, PER_HIT, INCLUDE_MIN)[0]
+    out, counts, _ = hc.reference(c, PRIOR_WEIGHT_WEIGHTED if weighted else PRIOR_WEIGHT, INCLUDE_MIN, w if weighted else None)
+    return w, out, counts
+
+
 # ---- the decoy condition ----
 
 def decoy_failures(checker):
@@ -255,7 +304,48 @@ def decoy_failures(checker):
         got = _table(checker, w["queries"], [hybrid], table24(), g)
         if all(tuple(got[q, 0]) == tuple(exp["R"][g][q, 7]) for q in range(NQ)):
             bad.append((f"affine {g}", "straddle hybrid", -1, 7))
-    return bad
+    return bad + hits_decoy_failures(checker)
+
+
+HITS_EXCUSED = [("pssm_hit_weights", 0)]
+# query 0 has ONE column: its four hits pair that column with one residue each, and the weights only tell which of those residues
+# coincide -- four different letters in the world and in the decoy alike give four equal weights.  The update of the same query does
+# change (its counts name the letters), and so does every other query of both calls.
+
+
+def hits_decoy_failures(checker):
+    """The (family, mixture, nletters, target order, query) for which a decoy does NOT change a byte of the result of
+    sw_db_pssm_hit_weights or sw_db_pssm_from_hits (with and without weights) under either of GAPS, over the queries with a used entry
+    and but for HITS_EXCUSED: must be empty.  A far database gives decoy targets under truncation (both calls, the natural and the
+    straddle order), far PSSM columns a decoy prior (the update only); the tables are the true world's.  The tests run every family
+    under both GAPS, so a query shows a truncation when it differs under one of them: under GAPS[0] no column of the longest query is
+    paired by more than two of its hits, and then no term of the weights depends on a residue (1/2 where two hits share the column,
+    whatever their letters, 1 where one stands alone); under GAPS[1] its four hits run over the whole query."""
+    w, d, exp = world(), decoy(), expected(checker)
+    same = {}
+    for g in GAPS:
+        for nl in (24, 256):
+            for order in (NATURAL_ORDER, STRADDLE_ORDER):
+                true = hits_case(exp, g, order, nl)
+                has = [q for q in range(NQ) if true.nhits[q] > 0 and (true.aln[q, :true.nhits[q], 6] > 0).any()]
+                assert len(has) == 4
+                mixes = {"decoy targets": hits_case(exp, g, order, nl, targets=d["targets"])}
+                if order is NATURAL_ORDER:
+                    mixes["decoy prior"] = hits_case(exp, g, order, nl, queries=d["queries"])
+                    mixes["both decoys"] = hits_case(exp, g, order, nl, targets=d["targets"], queries=d["queries"])
+                for weighted in (True, False):
+                    tw, tout, _ = hits_want(true, weighted)
+                    for name, c in mixes.items():
+                        gw, gout, _ = hits_want(c, weighted)
+                        for q in has:
+                            rows = slice(int(true.qoffs[q]), int(true.qoffs[q + 1]))
+                            key = ("pssm_from_hits" + (" weighted" if weighted else ""), name, nl, tuple(order), q)
+                            same[key] = same.get(key, True) and np.array_equal(gout[rows], tout[rows])
+                            if weighted and name != "decoy prior" and ("pssm_hit_weights", q) not in HITS_EXCUSED:
+                                key = ("pssm_hit_weights", name, nl, tuple(order), q)
+                                same[key] = same.get(key, True) and np.array_equal(gw[q], tw[q])
+    assert len(same) == 2 * 4 * 2 * 4 + 3 * 2 * 3          # the update: 4 mixtures x 2 alphabets x 4 queries, twice; the weights: 3 x 2 x 3
+    return [k for k, v in same.items() if v]
 
 
 # ---- placements ----
@@ -436,3 +526,78 @@ def slots_expected(checker):
         c = slots_case()
         _SLOTS_EXPECTED["aln"] = [rule_alignment(checker, c["query"], t, table24(), *GAPS[0])[:2] for t in c["targets"]]
     return _SLOTS_EXPECTED["aln"]
+
+
+# ---- a count matrix beyond 4 GiB ----
+
+COUNT_NQ, COUNT_QLEN, COUNT_NL, COUNT_TOP = 5, 2**20 - 1, 256, 4
+COUNT_PRIOR, COUNT_PW, COUNT_INC = 13, 3, 20                    # a constant prior above SMAX: an unobserved entry comes out as SMAX
+assert COUNT_NQ * COUNT_QLEN > 2**22 and COUNT_NQ * COUNT_QLEN * COUNT_NL * 4 > WRAP          # the int32 counts pass 4 GiB
+assert (COUNT_NQ - 1) * COUNT_QLEN * COUNT_NL * 4 == WRAP - 4096                              # the last query's counts begin 4 columns below byte 2^32
+assert SMAX * min(COUNT_QLEN, max(TLENS)) < 2**24 and max(TLENS) == 301                       # what the call checks of smax and the sizes
+
+
+@functools.lru_cache(maxsize=None)
+def count_case():
+    """Five queries of 2^20 - 1 columns over 256 letters against the small world, top = 4.  Used entries in the first and the last query
+    only -- the entries of the queries 1 and 3 fail one guard of the rule each, query 2 has a count of 0 --, every one `nops` 'M' from
+    (q_begin, t_begin); one runs past its target's end, the last one past the query's.  Every used entry of the last query pairs
+    columns >= 4, so its counts lie wholly beyond byte 2^32, and the count 2^32 bytes below each (the first query's column j - 4, same
+    letter) is an expected zero (asserted).  {"qoffs", "hits", "nhits", "aln", "ops", "cap", "weights", "windows": [(query, first
+    column, columns, entry)], "compact": the windows as a case of tests/pssm_hits_cases.py -- one query per window, top 1 --, which the
+    numpy rule can walk: the prior is constant and no two used entries of a query share a column}."""
+    import types
+    w = world()
+    L, top = COUNT_QLEN, COUNT_TOP
+    packed_, offs = packed(w["targets"], 0)
+    targets = [7, 8, 6, 4]                                       # 300, 301, 127 and 65 letters
+    begins = {0: [0, 2000, 70000, 500000], COUNT_NQ - 1: [10000, 600000, 900000, L - 62]}
+    cap = max(TLENS) + 3
+    hits = np.zeros((COUNT_NQ, top, 3), np.int64)
+    aln = np.zeros((COUNT_NQ, top, 7), np.int64)
+    ops = np.full((COUNT_NQ * top, cap), OPS_POISON, np.uint8)
+    weights = np.array([[3, 1, 2, 5]] * COUNT_NQ, np.int32)
+    windows = []
+    for q in range(COUNT_NQ):
+        for r, t in enumerate(targets):
+            hits[q, r] = (t, 0, 50)
+            tb = 10 if r == 1 else 0                             # entry 1 runs past its target's end
+            aln[q, r] = (0, 50, begins.get(q, begins[0])[r], tb, 0, 0, TLENS[t])
+            ops[q * top + r, :TLENS[t]] = ord("M")
+            if q in begins:
+                windows.append((q, begins[q][r], min(TLENS[t], L - begins[q][r]), r))
+    hits[1, :, 0] = (-1, NT, 2**40, -2**40)                      # query 1: no target in range
+    aln[3, :, 1] = COUNT_INC - 1                                 # query 3: below include_min_score
+    aln[3, 2, 6], aln[3, 3, 6] = 0, cap + 1
+    nhits = np.array([top, top, 0, top + 3, top], np.int64)
+    assert windows[-1][2] == 62 < TLENS[4]                       # the last entry runs past the end of the last query
+    cols = {q: set() for q in begins}
+    for q, c0, n, _ in windows:
+        assert not cols[q] & set(range(c0, c0 + n))              # no two entries of a query share a column
+        cols[q] |= set(range(c0, c0 + n))
+    assert min(cols[COUNT_NQ - 1]) >= 4 and not {j - 4 for j in cols[COUNT_NQ - 1]} & cols[0]
+    c = types.SimpleNamespace()
+    c.letters, c.smax, c.other = pssm_letters(COUNT_NL), SMAX, OTHER
+    c.qoffs = np.concatenate([[0], np.cumsum([n for _, _, n, _ in windows])]).astype(np.int64)
+    c.prior = np.full((int(c.qoffs[-1]), COUNT_NL), COUNT_PRIOR, np.int8)
+    c.packed, c.offs, c.sub = packed_, offs, table24()
+    c.hits = np.stack([hits[q, r] for q, _, _, r in windows])[:, None, :]
+    c.aln = np.stack([aln[q, r] for q, _, _, r in windows])[:, None, :].copy()
+    c.aln[:, 0, 2] = 0
+    c.nhits, c.cap = None, cap
+    c.ops = np.stack([ops[q * top + r] for q, _, _, r in windows])
+    c.weights = np.array([[weights[q, r]] for q, _, _, r in windows], np.int32)
+    out = {"qoffs": COUNT_QLEN * np.arange(COUNT_NQ + 1, dtype=np.int64), "hits": hits, "nhits": nhits, "aln": aln, "ops": ops, "cap": cap,
+           "weights": weights, "windows": windows, "compact": c}
+    for a in (out["qoffs"], hits, nhits, aln, ops, weights, c.prior, c.hits, c.aln, c.ops, c.weights):
+        a.setflags(write=False)
+    return out
+
+
+def count_want():
+    """(new matrix, counts) of count_case()["compact"] by the numpy rule, each (columns of all windows, 256)."""
+    import pssm_hits_cases as hc
+    c = count_case()["compact"]
+    m, counts, used = hc.reference(c, COUNT_PW, COUNT_INC, c.weights)
+    assert used.all() and (counts.sum(axis=1) > 0).sum() > 1000 and (m != SMAX).any()
+    return m, counts

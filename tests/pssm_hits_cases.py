@@ -3,6 +3,7 @@ restatement of the rule in include/swhip.h (sw_db_pssm_from_hits) -- used entrie
 division -- that shares no code with the library, and the builders of the cases: synthetic tables that put ops on every side of a
 64-op chunk, garbage tables, and real tables from the host legs of the search and the alignment over a database with planted
 homologues.  The builders assert that what they build is not vacuous."""
+import functools
 import types
 
 import numpy as np
@@ -386,3 +387,120 @@ def full_range_case(rng, nletters, top, smax):
     c.prior = rng.integers(-128, 128, c.prior.shape).astype(np.int8)
     assert c.prior.min() == -128 and c.prior.max() == 127
     return c
+
+
+# ---- the second turn of the grid-stride loops (test_pssm_full_size_host.py, test_pssm_full_size_gpu.py) ----
+
+GRID_MAX = 1 << 20                         # swp::kPssmHitsGridMax
+TURN_INCLUDE_MIN = 20                      # include_min_score of the calls on second_turn_case()
+TURN_LONG, TURN_TILE = 567, 63             # three queries of 9 tiles of 63 columns (256 letters) among one-column queries
+
+
+def subcase(c, qs):
+    """The queries qs of a case as a case of their own (a query depends on no other query): what the numpy rule can walk when the whole
+    case has a million queries."""
+    top = c.hits.shape[1]
+    s = types.SimpleNamespace(**vars(c))
+    qlens = [int(c.qoffs[q + 1] - c.qoffs[q]) for q in qs]
+    s.qoffs = np.concatenate([[QFRONT], QFRONT + np.cumsum(qlens)]).astype(np.int64)
+    rows = np.concatenate([np.arange(c.qoffs[q], c.qoffs[q + 1]) for q in qs])
+    s.prior = np.concatenate([c.prior[:QFRONT], c.prior[rows]])
+    s.hits, s.aln = c.hits[qs], c.aln[qs]
+    s.nhits = None if c.nhits is None else c.nhits[qs]
+    s.ops = c.ops.reshape(len(c.qoffs) - 1, top, -1)[qs].reshape(len(qs) * top, -1)
+    return s
+
+
+def live_jobs(c, tiles_per_query, tile_cols, group):
+    """The jobs workgroup `group` of a grid of GRID_MAX takes in its grid-stride loop and does not skip, in order: (query, tile)."""
+    nq = len(c.qoffs) - 1
+    out = []
+    for job in range(group, nq * tiles_per_query, GRID_MAX):
+        q, tile = divmod(job, tiles_per_query)
+        if tile * tile_cols < int(c.qoffs[q + 1] - c.qoffs[q]):
+            out.append((q, tile))
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def second_turn_case():
+    """GRID_MAX + 3 queries over 256 letters, top = 1: one column each, except TURN_LONG columns (9 tiles) at the indices 0, 2^19 and
+    last.  9 x (GRID_MAX + 3) jobs over GRID_MAX workgroups: workgroup g takes the jobs g, g + GRID_MAX, ...; those it does not skip are the
+    tiles of the long queries and tile 0 of the others.  Used entries: the three long queries (each across a tile edge), some 2000 one-
+    column queries drawn at random, and the one-column queries that follow or precede a long query's tile in the same workgroup, set
+    so that a tile WITH counts is followed by another query's tile WITHOUT and the reverse (asserted below from job % GRID_MAX).  Entries
+    that are not used are so in turn for each reason the rule names.  (case, the queries with a used entry, sorted, subcase(case,
+    those queries)): built once and shared -- the tests leave it unchanged."""
+    rng = np.random.default_rng(20)
+    nq, nl, cap, tpq = GRID_MAX + 3, 256, 16, TURN_LONG // TURN_TILE
+    assert tpq * TURN_TILE == TURN_LONG and tpq == 9
+    longq = [0, GRID_MAX // 2, nq - 1]
+    qlens = np.ones(nq, np.int64)
+    qlens[longq] = TURN_LONG
+    c = types.SimpleNamespace()
+    c.letters, c.smax, c.other = letters_of(rng, nl), 11, -4
+    c.qoffs = np.concatenate([[QFRONT], QFRONT + np.cumsum(qlens)]).astype(np.int64)
+    c.prior = rng.integers(-128, 128, (int(c.qoffs[-1]), nl), dtype=np.int8)
+    tlens = [0, 1, 5, 64, 65, 130, 400, 700]
+    c.offs = np.concatenate([[7], 7 + np.cumsum(tlens)]).astype(np.int64)
+    c.packed = rng.integers(0, 256, int(c.offs[-1]), dtype=np.uint8)
+    c.sub = random_submat(rng)
+    c.cap, c.nhits = cap, None
+    c.ops = np.full((nq, cap), 0x5A, np.uint8)
+    # nothing is used until it is made so below: a target out of range, a score below include_min = 20, nops 0 or beyond ops_cap, in turn
+    c.hits = np.zeros((nq, 1, 3), np.int64)
+    c.hits[:, 0, 0] = np.where(np.arange(nq) % 4 == 0, len(tlens), rng.integers(3, len(tlens), nq))
+    c.aln = np.zeros((nq, 1, 7), np.int64)
+    c.aln[:, 0, 1] = np.where(np.arange(nq) % 4 == 1, 19, 50)
+    c.aln[:, 0, 6] = np.select([np.arange(nq) % 4 == 2, np.arange(nq) % 4 == 3], [0, cap + 1], 7)
+    c.ops[:, :7] = M                                              # (ops that WOULD count, were the entry used)
+
+    def use(q, qb, nops, lead_d=0):
+        t = int(rng.integers(5, len(tlens)))                      # a target of 130 letters or more
+        c.hits[q, 0] = (t, 0, 0)
+        c.aln[q, 0] = (0, 20 + int(rng.integers(0, 50)), qb, int(rng.integers(0, 100)), 0, 0, nops)
+        c.ops[q] = 0x5A
+        c.ops[q, :lead_d] = D
+        c.ops[q, lead_d:nops] = M
+
+    # the long queries: 16 'M' across the edges of the tiles 0|1, 3|4 and 7|8
+    for q, qb in zip(longq, (55, 4 * TURN_TILE - 8, 8 * TURN_TILE - 8)):
+        use(q, qb, cap)
+    counted = {(longq[0], 0), (longq[0], 1), (longq[1], 3), (longq[1], 4), (longq[2], 7), (longq[2], 8)}
+    ones = np.setdiff1d(rng.choice(nq, 2000, replace=False), longq)
+    # the workgroups of the long queries' tiles: which one-column query each takes, and whether it gets a used entry
+    groups = sorted({(q * tpq + tile) % GRID_MAX for q in longq for tile in range(tpq)})
+    forced = {}
+    for g in groups:
+        for q, tile in live_jobs(types.SimpleNamespace(qoffs=c.qoffs), tpq, TURN_TILE, g):
+            if q not in longq:
+                forced[q] = g % 2 == 1                           # with a used entry in the odd workgroups, without in the even ones
+    forced[1], forced[GRID_MAX + 1] = True, False                # (the finish kernel's workgroup 1, below)
+    ones = np.setdiff1d(ones, [q for q, u in forced.items() if not u])
+    ones = np.union1d(ones, [q for q, u in forced.items() if u]).astype(np.int64)
+    for n, q in enumerate(ones):
+        use(int(q), 0, 1 + n % cap, lead_d=n % 3 if n % cap >= 3 else 0)
+    used_q = np.union1d(ones, longq).astype(np.int64)
+    counted |= {(int(q), 0) for q in ones}
+    # the pairing, from job % GRID_MAX: in some workgroup counts -> none and in some none -> counts, between different queries
+    seen = set()
+    for g in groups:
+        jobs = live_jobs(c, tpq, TURN_TILE, g)
+        for (q0, t0), (q1, t1) in zip(jobs, jobs[1:]):
+            if q0 != q1:
+                seen.add(((q0, t0) in counted, (q1, t1) in counted))
+    assert {(True, False), (False, True), (True, True)} <= seen, seen
+    # the finish kernel's second turn: the workgroups 0, 1, 2 take the queries GRID_MAX, GRID_MAX + 1, GRID_MAX + 2 after 0, 1, 2
+    first, second = np.isin([0, 1, 2], used_q), np.isin([GRID_MAX, GRID_MAX + 1, GRID_MAX + 2], used_q)
+    assert first.tolist() == [True, True, False] and second.tolist() == [False, False, True]      # used -> not used twice, and the reverse
+    return c, used_q, subcase(c, used_q)
+
+
+def second_turn_expected(c, used_q, sub_out, sub_counts):
+    """The whole call's matrix (the queries' columns) and the nonzero counts as (rows, counts of those rows), from the results of
+    subcase(c, used_q): min(prior, smax) and zero counts in every query without a used entry."""
+    front = int(c.qoffs[0])
+    out = np.minimum(c.prior[front:], c.smax).astype(np.int8)
+    rows = np.concatenate([np.arange(c.qoffs[q], c.qoffs[q + 1]) for q in used_q]) - front
+    out[rows] = sub_out
+    return out, rows, sub_counts

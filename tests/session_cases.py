@@ -484,3 +484,103 @@ def sequence_table(sub, letters, other, smax):
     tab = np.full((256, 256), other, np.int8)
     tab[:, letters] = np.minimum(sub[:, letters], smax)
     return tab
+
+
+# ---- the fifth session: weights and updates in turn ----
+#
+# sw_db_pssm_hit_weights stages its code table and offsets through the device table and the two pinned copies of sw_db_pssm_from_hits,
+# in the same turns, but lays the table out differently: its code table stands at byte 0, where the update keeps S.  It owns a second
+# workspace, one 64-bit accumulator per entry, which grows with nqueries x top.  WEIGHTED is the order of the calls of one fresh
+# context: weightsK on stream 0, updateK -- which takes weightsK's device output as d_weights -- on stream 1, nothing synchronised.  The
+# worlds hold 4, 24 and 256 letters and 6, 7 and 8 queries, so the table's need alternates between the two layouts and grows before
+# update0 (weights0 allocated it), update1 and update2; the accumulators grow before weights1 and weights2 (asserted in
+# test_session_host.py from the sizes the driver computes).
+
+WEIGHT_NLETTERS = [4, 24, 256]
+WEIGHT_QLENS = [[30, 90, 50, 60, 33, 47], [40, 63, 33, 64, 30, 65, 257], [1, 63, 64, 65, 129, 100, 30, 513]]   # (the first queries of a world fit the world before)
+WEIGHT_TOPS = [5, 7, 9]
+WEIGHT_PER_HIT = [16, 7, 100]
+WEIGHT_PW = [32, 1, 3]
+WEIGHT_INC = [1, 0, 20]
+WEIGHTED = (("pssm_top", 0), ("align", 1), ("weights0", 0), ("update0", 1), ("weights1", 0), ("update1", 1), ("weights2", 0), ("update2", 1),
+            ("pssm_top_again", 0))                                           # (step, stream)
+WEIGHTED_TOP_AGAIN = 3
+
+_weighted = {}
+
+
+def weighted(swamd):
+    """The worlds of the session (cases of tests/pssm_hits_cases.py): worlds[0] holds the host legs' iteration 0 over a four-letter
+    database with planted homologues, the others synthetic tables; each with per_hit, pw and inc of its own and the letters in an order
+    of its own."""
+    if not _weighted:
+        import pssm_hits_cases as phc
+        worlds = []
+        for k, (nl, qlens, top) in enumerate(zip(WEIGHT_NLETTERS, WEIGHT_QLENS, WEIGHT_TOPS)):
+            rng = np.random.default_rng(5700 + k)
+            if k == 0:
+                alpha = PROTEIN[:4]
+                sub = np.full((256, 256), -4, np.int8)
+                sub[np.ix_(alpha, alpha)] = rng.integers(-4, 0, (4, 4))
+                sub[alpha, alpha] = rng.integers(5, 10, 4)
+                sub = np.minimum(sub, sub.T)
+                c = phc.real(swamd, rng, top, qlens=qlens, nrandom=30, nletters=4, alpha=alpha, sub=sub)
+                order = np.arange(4)                               # (the prior's columns follow the letters: the order stays)
+            else:
+                c = phc.synthetic(rng, nl, top, qlens=qlens)
+                order = rng.permutation(nl)
+            c.letters = c.letters[order]
+            c.per_hit, c.pw, c.inc = WEIGHT_PER_HIT[k], WEIGHT_PW[k], WEIGHT_INC[k]
+            worlds.append(c)
+        _weighted.update(worlds=worlds)
+    return _weighted
+
+
+def weighted_expected(swamd):
+    """The host legs chained: per world (weights, new matrix in the layout of the prior), then the hit table of the search on the last
+    matrix.  Computed once."""
+    if "expected" not in _weighted:
+        import pssm_hits_cases as phc
+        import pssm_weights_cases as pwc
+        steps = []
+        for c in weighted(swamd)["worlds"]:
+            w = pwc.host_leg(swamd, c, c.per_hit, c.inc)
+            out, _ = phc.host_leg(swamd, c, c.pw, c.inc, w)
+            m = c.prior.copy()
+            m[int(c.qoffs[0]):] = out
+            _frozen(w, m)
+            steps.append((w, m))
+        c = weighted(swamd)["worlds"][-1]
+        full = swamd.search_pssm_multi_host((steps[-1][1], c.qoffs), (c.packed, c.offs), phc.scoring(c))
+        _weighted["expected"] = (steps, pssm_cases.rank_order(full, WEIGHTED_TOP_AGAIN, ITER_MIN_SCORE), full)
+    return _weighted["expected"]
+
+
+def table_needs(c):
+    """(bytes of the weights call's table, bytes of the update's, accumulators of the weights call) as the driver sizes them
+    (smith-waterman_amd/csrc/sw_api_search.hip): 256 + offsets; S padded to 256 bytes + 256 + offsets; nqueries x top."""
+    n, nq = len(c.letters), len(c.qoffs) - 1
+    off = 8 * (nq + 1)
+    return 256 + off, ((n * n + 255) & ~255) + 256 + off, nq * c.hits.shape[1]
+
+
+def weights_under(c, code=None, qoffs=None, acc=None):
+    """The weights the rule gives for world c (tests/pssm_weights_cases.py), or what it would give had the call taken another call's code
+    table or offsets, or had it added to another call's accumulators (acc: that call's (T, m), taken entry by entry in table order)
+    where it should have started from zero."""
+    import types
+
+    import pssm_weights_cases as pwc
+    v = types.SimpleNamespace(**vars(c))
+    if qoffs is not None:
+        v.qoffs = np.ascontiguousarray(qoffs[:len(c.qoffs)], np.int64)
+    T, m, _ = pwc.accumulators(v, c.inc, code)
+    if acc is not None:
+        for mine, theirs in zip((T, m), acc):
+            flat, old = mine.reshape(-1), theirs.reshape(-1)
+            n = min(len(flat), len(old))
+            flat[:n] = flat[:n] + old[:n]
+    try:
+        return pwc.weights_of(T, m, c.per_hit)[0]
+    except AssertionError:
+        return None                                                # (outside the rule's ranges: no table a correct call could give)

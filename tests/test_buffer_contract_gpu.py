@@ -10,6 +10,8 @@ import pytest
 
 from affine_cases import DNA, PROTEIN, checker, random_submat  # noqa: F401
 from align_cases import expected, pack
+import pssm_hits_cases as hc
+import pssm_weights_cases as wc
 from buffer_cases import POISON, POISON8, POISON32, POISON64, Arena, arena_bytes, assert_guards, live_head, live_tail
 
 pytestmark = pytest.mark.gpu
@@ -636,3 +638,89 @@ def test_side_stream_align_affine(engine, checker):  # noqa: F811
         assert tuple(int(x) for x in aln[h]) == row and ops[h, :row[6]].tobytes() == eops, f"hit {h} (target {k})"
     assert_guards(out)
     assert POISON64 < 0
+
+
+# ---- the PSSM update and the hit weights ----------------------------------------------------------------------------------------------
+def _table(ar, arr, skew, name):
+    """An int32 / int64 input table at its natural alignment plus an odd multiple of it, must-stay, between poison."""
+    arr = np.ascontiguousarray(arr)
+    t, c = ar.place(arr.reshape(-1).view(np.uint8), 256, skew, name=name)
+    assert skew % arr.itemsize == 0 and (skew // arr.itemsize) % 2 == 1
+    return ar.view(c, {4: ar.torch.int32, 8: ar.torch.int64}[arr.itemsize], (arr.size,))
+
+
+@pytest.mark.parametrize("skew", [0, 1, 3])
+@pytest.mark.parametrize("kind", ["synthetic", "garbage"])
+def test_pssm_hit_weights_and_update(engine, swamd, kind, skew):
+    """sw_db_pssm_hit_weights, then sw_db_pssm_from_hits out of place with counts and in place without, every buffer carved out of one
+    poisoned arena per direction: the database, the ops, the prior and the matrix at base % 64 = skew, the int64 tables (hits, nhits,
+    alignments) at 8 x 3 and the int32 ones (weights, counts) at 4 x 3 past a 256-byte line.  After each call the inputs hold their bytes,
+    every guard is whole and only the outputs of THAT call changed.  24 letters, top 9; the garbage table trips every guard of the rule
+    (tests/pssm_hits_cases.py: garbage).  Expected: the host legs (held to the numpy rules in tests/test_pssm_*_host.py)."""
+    torch = engine.torch
+    rng = np.random.default_rng(1200 + skew)
+    c = hc.synthetic(rng, 24, 9)
+    if kind == "garbage":
+        c = hc.garbage(rng, c)
+    else:
+        c.nhits = np.array([9, 0, 4, 9, 8, 9], np.int64)
+    per_hit, pw, inc = 16, 3, 20
+    nl, nq, top = len(c.letters), len(c.qoffs) - 1, 9
+    front, total = int(c.qoffs[0]) * nl, int(c.qoffs[-1]) * nl
+    exp_w = wc.host_leg(swamd, c, per_hit, inc)
+    exp_out, exp_cnt = hc.host_leg(swamd, c, pw, inc, exp_w)
+    assert exp_w.any() and exp_cnt.any() and (exp_out != np.minimum(c.prior[int(c.qoffs[0]):], c.smax)).any()
+    prior_bytes = np.ascontiguousarray(c.prior).reshape(-1).view(np.uint8)
+
+    inp = Arena(torch, _dev(engine), arena_bytes(len(c.packed) + 128, c.ops.size + 128, total + 128, c.hits.size * 8, nq * 8, c.aln.size * 8))
+    d_db = _inp(inp, c.packed, 64, skew, "db")
+    d_ops = _inp(inp, c.ops, 64, skew, "ops")
+    d_prior = _inp(inp, prior_bytes, 64, skew, "prior").view(torch.int8)
+    d_hits = _table(inp, c.hits, 24, "hits")
+    d_nhits = _table(inp, c.nhits, 24, "nhits")
+    d_aln = _table(inp, c.aln, 24, "aln")
+    out = Arena(torch, _dev(engine), arena_bytes(nq * top * 4, (total - front) * 4, total, total))
+    d_w, c_w = _out(out, (nq * top,), torch.int32, 12, "weights")
+    d_cnt, c_cnt = _out(out, (total - front,), torch.int32, 12, "counts")
+    d_m, c_m = _out(out, (total,), torch.int8, skew, "matrix", align=64)
+    c_in = out.carve(total, 64, skew, name="in place")
+    d_in = out.view(c_in, torch.int8, (total,))
+    d_in.copy_(d_prior)
+    for cv in (c_cnt, c_m):
+        out.must_stay(cv)
+    out.must_stay(c_in, prior_bytes)
+
+    def unchanged(case):
+        assert_guards(out)
+        assert_guards(inp)
+
+    with engine.prepare_db(d_db, c.offs) as db:
+        # the weights: only their carve changes
+        got = db.pssm_hit_weights_device(c.qoffs, hc.scoring(c), (per_hit, inc), d_hits, d_nhits, d_aln, d_ops, c.cap, out=d_w, top=top)
+        assert got.data_ptr() == d_w.data_ptr() and engine.get_option("last_pssm_weights_launches") == 2
+        engine.synchronize()
+        assert np.array_equal(d_w.cpu().numpy().reshape(nq, top), exp_w), "weights"
+        unchanged("weights")
+        # the update out of place, with counts, reading the weights: the weights are an input now
+        out.must_stay(c_w, exp_w.reshape(-1).view(np.uint8))
+        c_cnt.expect = c_m.expect = None
+        db.pssm_from_hits_device(d_prior, c.qoffs, hc.scoring(c), (c.sub, pw, inc), d_hits, d_nhits, d_aln, d_ops, c.cap, weights=d_w, out=d_m, top=top,
+                                 counts=d_cnt)
+        assert engine.get_option("last_pssm_hits_launches") == 1
+        engine.synchronize()
+        m = d_m.cpu().numpy()
+        assert (m[:front] == POISON8).all(), "the columns in front of the first query were written"
+        assert np.array_equal(m[front:].reshape(-1, nl), exp_out), "matrix"
+        assert np.array_equal(d_cnt.cpu().numpy().reshape(-1, nl), exp_cnt), "counts"
+        unchanged("update")
+        # in place, matrix only: the counts and the matrix of the call before are must-stay now
+        out.must_stay(c_cnt, exp_cnt.reshape(-1).view(np.uint8))
+        out.must_stay(c_m, m.view(np.uint8))
+        c_in.expect = None
+        db.pssm_from_hits_device(d_in, c.qoffs, hc.scoring(c), (c.sub, pw, inc), d_hits, d_nhits, d_aln, d_ops, c.cap, weights=d_w, out=d_in, top=top)
+        assert engine.get_option("last_pssm_hits_launches") == 1
+        engine.synchronize()
+        m2 = d_in.cpu().numpy()
+        assert np.array_equal(m2[:front].view(np.uint8), prior_bytes[:front]), "the columns in front of the first query changed"
+        assert np.array_equal(m2[front:].reshape(-1, nl), exp_out), "matrix in place"
+        unchanged("update in place")

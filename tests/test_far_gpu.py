@@ -5,6 +5,10 @@ checker (tests/affine_oracle.cpp), the rule's walk (tests/align_cases.py) and th
 call at near placement is an extra bytewise comparison.  A kernel that drops the high half of an offset reads or writes the decoy 2^32
 bytes below and shows as wrong values, not as a fault.
 
+The PSSM update and the hit weights (sw_db_pssm_from_hits, sw_db_pssm_hit_weights) are two families of their own: far databases, far
+PSSM columns (prior and matrix), ops rows beyond byte 2^32 and a count matrix of 5.4 GB; their expected values are the numpy rules of
+tests/pssm_hits_cases.py and tests/pssm_weights_cases.py over the small world (tests/far_cases.py: hits_case, count_case).
+
 Every test frees its tensors and empties torch's cache before the next one starts; none holds more than about 12 GiB."""
 import ctypes
 import json
@@ -23,8 +27,8 @@ pytestmark = pytest.mark.gpu
 
 POISON64, POISON32, POISON8 = -0x5A5A5A5A5A5A5A5B, -0x5A5A5A5B, 0xA5
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-OPS_CAP = max(fc.QLENS) + max(fc.TLENS)
-NHITS_CUT = [4, 0, 3, 4, 2]                       # the counts of the alignment calls: unused entries in the table, one empty row
+OPS_CAP = fc.OPS_CAP
+NHITS_CUT = fc.NHITS_CUT                          # the counts of the alignment calls: unused entries in the table, one empty row
 
 
 @pytest.fixture(autouse=True)
@@ -279,8 +283,105 @@ def want_align_hits(exp, order):
     return out
 
 
+HITS_GUARD = 4096
+
+
+def poisoned_window(engine, size, lo, hi, far):
+    """A uint8 device buffer of `size` bytes, not initialised but for poison on [lo - guard, hi + guard) and, with far, on the same
+    range 2^32 bytes below: (buffer, the poisoned (first, last) ranges)."""
+    t = engine.torch
+    buf = t.empty(size, dtype=t.uint8, device=dev_of(engine))
+    spans = [(max(0, lo - HITS_GUARD), min(size, hi + HITS_GUARD))]
+    if far:
+        assert lo - fc.WRAP - HITS_GUARD >= 0 and hi - fc.WRAP + HITS_GUARD < lo - HITS_GUARD
+        spans.append((lo - fc.WRAP - HITS_GUARD, hi - fc.WRAP + HITS_GUARD))
+    for a, b in spans:
+        buf[a:b] = POISON8
+    return buf, spans
+
+
+def still_poison(buf, spans, lo, hi, what):
+    """Every poisoned byte outside the live window [lo, hi) is still poison."""
+    for a, b in spans:
+        if a <= lo and hi <= b:
+            assert bool((buf[a:lo] == POISON8).all()) and bool((buf[hi:b] == POISON8).all()), f"{what}: written outside the queries' columns"
+        else:
+            assert bool((buf[a:b] == POISON8).all()), f"{what}: the bytes 2^32 below the output were written"
+
+
+def run_pssm_hits(engine, P, exp, family):
+    """sw_db_pssm_hit_weights, or sw_db_pssm_from_hits with and without d_weights, with d_counts, and once with d_pssm_out == d_prior,
+    over the reference's hit table and the rule's alignments and ops; every call twice.  The prior is the placement's PSSM; the new
+    matrix goes to a buffer of its own at the same columns, with poison around the queries' columns and (far columns) 2^32 bytes
+    below them; the in-place call runs last, on the prior itself, whose live window is then put back."""
+    out, t, nl = {}, engine.torch, P.nletters
+    lo, hi = int(P.moffs[0]) * nl, int(P.moffs[-1]) * nl
+    far = lo >= fc.WRAP
+    ncnt = (hi - lo)
+    for g in fc.GAPS:
+        c = fc.hits_case(exp, g, P.order, nl)
+        sc = fc.pssm_scoring(nl, g)
+        tabs = (upload(engine, c.hits), upload(engine, c.nhits), upload(engine, c.aln), upload(engine, c.ops))
+        n = fc.NQ * fc.TOP
+        twice = []
+        for _ in range(2):
+            wbuf = poison(engine, n + 2 * HITS_GUARD, t.int32)
+            d_w = P.db.pssm_hit_weights_device(P.moffs, sc, (fc.PER_HIT, fc.INCLUDE_MIN), *tabs, fc.OPS_CAP, out=wbuf[HITS_GUARD:HITS_GUARD + n], top=fc.TOP)
+            assert engine.get_option("last_pssm_weights_launches") == 2 and engine.get_option("last_pssm_weights_tiles") >= 1
+            engine.synchronize()
+            assert bool((wbuf[:HITS_GUARD] == POISON32).all()) and bool((wbuf[HITS_GUARD + n:] == POISON32).all()), "the weights were written outside their buffer"
+            twice.append(host(d_w).reshape(fc.NQ, fc.TOP))
+        assert twice[0].tobytes() == twice[1].tobytes()
+        if family == "pssm_hit_weights":
+            out[f"weights {g}"] = twice[0]
+            continue
+        for how, pw, weights in (("plain", fc.PRIOR_WEIGHT, None), ("weighted", fc.PRIOR_WEIGHT_WEIGHTED, d_w)):
+            twice = []
+            for _ in range(2):
+                mbuf, spans = poisoned_window(engine, P.d_m.numel(), lo, hi, far)
+                cbuf = poison(engine, ncnt + 2 * HITS_GUARD, t.int32)
+                P.db.pssm_from_hits_device(P.d_m, P.moffs, sc, (fc.table24(), pw, fc.INCLUDE_MIN), *tabs, fc.OPS_CAP, weights=weights, out=mbuf.view(t.int8),
+                                           top=fc.TOP, counts=cbuf[HITS_GUARD:HITS_GUARD + ncnt])
+                assert engine.get_option("last_pssm_hits_launches") == 1
+                engine.synchronize()
+                still_poison(mbuf, spans, lo, hi, f"{how} {g}")
+                assert bool((cbuf[:HITS_GUARD] == POISON32).all()) and bool((cbuf[HITS_GUARD + ncnt:] == POISON32).all()), "the counts were written outside their buffer"
+                twice.append((host(mbuf[lo:hi].view(t.int8)).reshape(-1, nl), host(cbuf[HITS_GUARD:HITS_GUARD + ncnt]).reshape(-1, nl)))
+                del mbuf, cbuf
+            assert twice[0][0].tobytes() == twice[1][0].tobytes() and twice[0][1].tobytes() == twice[1][1].tobytes()
+            out[f"update {g} {how}: matrix"], out[f"update {g} {how}: counts"] = twice[0]
+        # in place, on the prior itself: the decoy 2^32 bytes below it stays what it was
+        keep = P.d_m[lo:hi].clone()
+        below = P.d_m[lo - fc.WRAP:hi - fc.WRAP].clone() if far else None
+        P.db.pssm_from_hits_device(P.d_m, P.moffs, sc, (fc.table24(), fc.PRIOR_WEIGHT_WEIGHTED, fc.INCLUDE_MIN), *tabs, fc.OPS_CAP, weights=d_w, out=P.d_m, top=fc.TOP)
+        engine.synchronize()
+        out[f"update {g} in place: matrix"] = host(P.d_m[lo:hi]).reshape(-1, nl)
+        if far:
+            assert t.equal(P.d_m[lo - fc.WRAP:hi - fc.WRAP], below), "the decoy PSSM below the prior changed"
+        P.d_m[lo:hi] = keep
+    return out
+
+
+def want_pssm_hits(exp, order, nletters, family):
+    out = {}
+    for g in fc.GAPS:
+        c = fc.hits_case(exp, g, order, nletters)
+        w, m, _ = fc.hits_want(c, True)
+        if family == "pssm_hit_weights":
+            out[f"weights {g}"] = w
+            continue
+        _, plain, counts = fc.hits_want(c, False)
+        _, _, wcounts = fc.hits_want(c, True)
+        out[f"update {g} plain: matrix"], out[f"update {g} plain: counts"] = plain, counts
+        out[f"update {g} weighted: matrix"], out[f"update {g} weighted: counts"] = m, wcounts
+        out[f"update {g} in place: matrix"] = m
+    return out
+
+
 def run_family(engine, exp, P, family):
     """(what the device gave, what the references give) of one family at one placement."""
+    if family in ("pssm_from_hits", "pssm_hit_weights"):
+        return run_pssm_hits(engine, P, exp, family), want_pssm_hits(exp, P.order, P.nletters, family)
     if family == "single":
         return run_single(engine, P), want_single(exp, P.order)
     if family in ("multi", "pssm"):
@@ -319,7 +420,7 @@ def check_family(engine, exp, P, family):
 
 # ---- A. far inputs ----
 
-FAR_INPUTS = [(kind, family) for kind in ("db_far", "db_straddle") for family in ("single", "multi", "pairs", "prefilter", "align_hits", "pssm", "align_pssm_hits")] + \
+FAR_INPUTS = [(kind, family) for kind in ("db_far", "db_straddle") for family in ("single", "multi", "pairs", "prefilter", "align_hits", "pssm", "align_pssm_hits", "pssm_from_hits", "pssm_hit_weights")] + \
              [(kind, family) for kind in ("q_far", "both_far") for family in ("multi", "pairs", "prefilter", "align_hits")]
 
 
@@ -337,7 +438,7 @@ def test_far_inputs(engine, checker, kind, family):  # noqa: F811
 
 @pytest.mark.parametrize("kind", ["near", "db_far"])
 @pytest.mark.parametrize("nletters", [256, 24])
-@pytest.mark.parametrize("family", ["pssm", "align_pssm_hits"])
+@pytest.mark.parametrize("family", ["pssm", "align_pssm_hits", "pssm_from_hits", "pssm_hit_weights"])
 def test_far_pssm_columns(engine, checker, family, nletters, kind):  # noqa: F811
     """The crossing comes from the product: the column index stays below 2^32, times nletters it does not."""
     exp = fc.expected(checker)
@@ -419,8 +520,14 @@ def test_public_methods_take_far_offsets(engine, checker):  # noqa: F811
         same(host(aln), want, "Database.align_affine_hits_device")
         same(host(P.db.search_pssm_device(P.d_m, P.moffs, psc)), exp["R"][g], "Database.search_pssm_device")
         same(host(P.db.search_pssm_top_device(P.d_m, P.moffs, psc, fc.TOP, fc.MIN_SCORE)[0]), wh, "Database.search_pssm_top_device")
-        aln, _ = P.db.align_pssm_hits_device(P.d_m, P.moffs, psc, hits, nhits, ops_cap=OPS_CAP, checkpoint=1)
+        aln, ops = P.db.align_pssm_hits_device(P.d_m, P.moffs, psc, hits, nhits, ops_cap=OPS_CAP, checkpoint=1)
         same(host(aln), want, "Database.align_pssm_hits_device")
+        c = fc.hits_case(exp, g, nhits_cut=[fc.TOP] * fc.NQ)
+        ww, wm, _ = fc.hits_want(c, True)
+        w = P.db.pssm_hit_weights_device(P.moffs, psc, (fc.PER_HIT, fc.INCLUDE_MIN), hits, nhits, aln, ops, OPS_CAP, top=fc.TOP)
+        same(host(w).reshape(fc.NQ, fc.TOP), ww, "Database.pssm_hit_weights_device")
+        m = P.db.pssm_from_hits_device(P.d_m, P.moffs, psc, (t24, fc.PRIOR_WEIGHT_WEIGHTED, fc.INCLUDE_MIN), hits, nhits, aln, ops, OPS_CAP, weights=w, out=P.d_m, top=fc.TOP)
+        same(host(m[int(P.moffs[0]) * 24:int(P.moffs[-1]) * 24]).reshape(-1, 24), wm, "Database.pssm_from_hits_device")     # (in place: the last use of the PSSM)
     finally:
         P.close()
 
@@ -575,9 +682,82 @@ def test_ops_rows_beyond_4gib(engine, checker, pssm, checkpoint):  # noqa: F811
         heads = host(ops[used, :OPS_CAP])
         same(heads, ops_rows([wops[q][r] for q in range(fc.NQ) for r in range(int(nhits[q]))]), "the used ops rows")
         assert all(len(wops[q][r]) > 0 for q in range(fc.NQ) for r in range(int(nhits[q])))
+        if pssm:
+            # the tables the alignment left on the device, rows of 2^20 ops and all, go on to the weights and the update: entry 4 x top
+            # starts at byte 2^32 of the ops.  Expected: the numpy rules on the same entries in a table of TOP columns and OPS_CAP ops.
+            c = fc.hits_case(exp, g, nhits_cut=nhits, hits=(ranked, np.full(fc.NQ, fc.TOP, np.int64)))
+            ww, wm, wc_ = fc.hits_want(c, True)
+            d_hits, d_nhits = upload(engine, hits), upload(engine, nhits)
+            lo, hi = int(P.moffs[0]) * 24, int(P.moffs[-1]) * 24
+            for _ in range(2):
+                wbuf = poison(engine, fc.NQ * top + 2 * HITS_GUARD, t.int32)
+                d_w = P.db.pssm_hit_weights_device(P.moffs, scoring, (fc.PER_HIT, fc.INCLUDE_MIN), d_hits, d_nhits, got, ops, cap,
+                                                   out=wbuf[HITS_GUARD:HITS_GUARD + fc.NQ * top], top=top)
+                assert engine.get_option("last_pssm_weights_launches") == 2
+                mbuf, spans = poisoned_window(engine, P.d_m.numel(), lo, hi, False)
+                cbuf = poison(engine, hi - lo + 2 * HITS_GUARD, t.int32)
+                P.db.pssm_from_hits_device(P.d_m, P.moffs, scoring, (fc.table24(), fc.PRIOR_WEIGHT_WEIGHTED, fc.INCLUDE_MIN), d_hits, d_nhits, got, ops, cap,
+                                           weights=d_w, out=mbuf.view(t.int8), top=top, counts=cbuf[HITS_GUARD:HITS_GUARD + hi - lo])
+                assert engine.get_option("last_pssm_hits_launches") == 1
+                engine.synchronize()
+                assert bool((wbuf[:HITS_GUARD] == POISON32).all()) and bool((wbuf[HITS_GUARD + fc.NQ * top:] == POISON32).all())
+                assert bool((cbuf[:HITS_GUARD] == POISON32).all()) and bool((cbuf[HITS_GUARD + hi - lo:] == POISON32).all())
+                still_poison(mbuf, spans, lo, hi, "the update behind far ops rows")
+                w = host(d_w).reshape(fc.NQ, top)
+                same(w[:, :fc.TOP], ww, "weights from far ops rows")
+                assert not w[:, fc.TOP:].any()
+                same(host(mbuf[lo:hi].view(t.int8)).reshape(-1, 24), wm, "update from far ops rows: matrix")
+                same(host(cbuf[HITS_GUARD:HITS_GUARD + hi - lo]).reshape(-1, 24), wc_, "update from far ops rows: counts")
+            assert ww[4].any() and wc_[int(c.qoffs[4]):].any()                           # the entries beyond byte 2^32 weigh and count
+            same(host(ops[used, :OPS_CAP]), heads, "the used ops rows after the weights and the update: only read")
         ops[used, :OPS_CAP] = POISON8                                                   # what was compared; everything else must still be poison
         assert count_unequal(ops.view(-1).view(t.int64), POISON64) == 0, "an unused ops row or the tail of a used one was written"
         del aln, ops, got
+    finally:
+        P.close()
+
+
+def test_count_matrix_beyond_4gib(engine):
+    """sw_db_pssm_from_hits with d_counts over five queries of 2^20 - 1 columns and 256 letters: 5.4 GB of int32 counts (and 1.3 GB each of
+    prior and matrix; about 8 GiB in all).  Used entries in the first and the last query only; the last query's counts lie beyond byte
+    2^32 and the count 2^32 bytes below each is an expected zero (tests/far_cases.py: count_case), so a count stored through 32 bits
+    shows twice: missing above, present below.  The live windows are compared with the numpy rule; everything else is counted on the
+    device: no other count is nonzero, no other entry of the matrix differs from min(prior, smax).  Twice, the same buffers poisoned
+    again.  A far weights table, hit table or accumulator is NOT built: nqueries x top would have to pass 2^30, and the sw_hit and
+    sw_alignment tables alone would then take more than 80 GiB."""
+    t, cc = engine.torch, fc.count_case()
+    wm, wcnt = fc.count_want()
+    nl, L, nq, top = fc.COUNT_NL, fc.COUNT_QLEN, fc.COUNT_NQ, fc.COUNT_TOP
+    total = nq * L * nl
+    assert total * 4 > 2**32 and total + total + total * 4 < 9 * 2**30
+    P = Placed(engine, "near")
+    try:
+        prior = t.full((total,), fc.COUNT_PRIOR, dtype=t.int8, device=dev_of(engine))
+        mbuf = t.empty(total + 2 * HITS_GUARD, dtype=t.uint8, device=dev_of(engine))
+        cbuf = t.empty(total + 2 * HITS_GUARD, dtype=t.int32, device=dev_of(engine))
+        tabs = (upload(engine, cc["hits"]), upload(engine, cc["nhits"]), upload(engine, cc["aln"]), upload(engine, cc["ops"]))
+        d_w = upload(engine, cc["weights"])
+        sc = fc.pssm_scoring(nl, fc.GAPS[0])
+        for run in range(2):
+            mbuf.fill_(POISON8)
+            cbuf.fill_(POISON32)
+            m, counts = mbuf[HITS_GUARD:HITS_GUARD + total].view(t.int8), cbuf[HITS_GUARD:HITS_GUARD + total]
+            P.db.pssm_from_hits_device(prior, cc["qoffs"], sc, (fc.table24(), fc.COUNT_PW, fc.COUNT_INC), *tabs, cc["cap"], weights=d_w, out=m, top=top, counts=counts)
+            assert engine.get_option("last_pssm_hits_launches") == 1
+            engine.synchronize()
+            assert bool((mbuf[:HITS_GUARD] == POISON8).all()) and bool((mbuf[HITS_GUARD + total:] == POISON8).all()), "the matrix was written outside its buffer"
+            assert bool((cbuf[:HITS_GUARD] == POISON32).all()) and bool((cbuf[HITS_GUARD + total:] == POISON32).all()), "the counts were written outside their buffer"
+            at = 0
+            for q, c0, n, r in cc["windows"]:
+                lo, hi = (q * L + c0) * nl, (q * L + c0 + n) * nl
+                assert (q == nq - 1) == (lo * 4 > 2**32)
+                same(host(counts[lo:hi]).reshape(n, nl), wcnt[at:at + n], f"run {run}: counts of query {q}, entry {r}")
+                same(host(m[lo:hi]).reshape(n, nl), wm[at:at + n], f"run {run}: matrix of query {q}, entry {r}")
+                at += n
+            assert count_unequal(counts, 0) == np.count_nonzero(wcnt), "a count outside the live windows is not zero"
+            assert count_unequal(m, min(fc.COUNT_PRIOR, fc.SMAX)) == int((wm != min(fc.COUNT_PRIOR, fc.SMAX)).sum()), "an entry outside the live windows changed"
+        assert bool((prior == fc.COUNT_PRIOR).all()), "the prior changed"
+        del prior, mbuf, cbuf
     finally:
         P.close()
 

@@ -95,6 +95,46 @@ def test_pssm_layouts_cross_by_the_product(checker):  # noqa: F811
         assert m.shape == (sum(fc.QLENS), nl) and m.max() <= fc.SMAX
 
 
+def test_the_decoy_condition_excuses_one_query_of_the_weights_only():
+    """sw_db_pssm_hit_weights and sw_db_pssm_from_hits are part of fc.decoy_failures() (empty, above).  One query is excused, by name:
+    query 0 of the weights has one column, and four residues on one column weigh the same whenever they are four different letters
+    -- in the world and in the decoy alike.  Its update is NOT excused, nor is any other query of either call."""
+    assert fc.HITS_EXCUSED == [("pssm_hit_weights", 0)] and fc.QLENS[0] == 1
+    assert (fc.PRIOR_WEIGHT, fc.PRIOR_WEIGHT_WEIGHTED, fc.PER_HIT, fc.INCLUDE_MIN) == (2, 512, 256, 1)
+
+
+def test_hits_case_host_legs_equal_the_rules(swamd, checker):  # noqa: F811
+    """The small world's update and weights: the host legs equal the numpy rules that the GPU tests take as expected."""
+    import pssm_hits_cases as hc
+    import pssm_weights_cases as wc
+    exp = fc.expected(checker)
+    for g in fc.GAPS:
+        for nl in (24, 256):
+            for order in (fc.NATURAL_ORDER, fc.STRADDLE_ORDER):
+                c = fc.hits_case(exp, g, order, nl)
+                w, m, counts = fc.hits_want(c, True)
+                assert w.any() and counts.any()
+                same(wc.host_leg(swamd, c, fc.PER_HIT, fc.INCLUDE_MIN), w, "weights")
+                out, cnt = hc.host_leg(swamd, c, fc.PRIOR_WEIGHT_WEIGHTED, fc.INCLUDE_MIN, w)
+                same(out, m, "matrix")
+                same(cnt, counts, "counts")
+
+
+def test_count_case_crosses_4gib_and_its_windows_equal_the_rule(swamd):
+    import pssm_hits_cases as hc
+    cc = fc.count_case()
+    m, counts = fc.count_want()
+    c = cc["compact"]
+    out, cnt = hc.host_leg(swamd, c, fc.COUNT_PW, fc.COUNT_INC, c.weights)
+    same(out, m, "matrix")
+    same(cnt, counts, "counts")
+    L, nl = fc.COUNT_QLEN, fc.COUNT_NL
+    assert int(cc["qoffs"][-1]) * nl * 4 > 2**32 > int(cc["qoffs"][-2]) * nl * 4
+    last = [(q * L + c0) * nl * 4 for q, c0, n, r in cc["windows"] if q == fc.COUNT_NQ - 1]
+    assert len(last) == 4 and min(last) > 2**32                                        # every live count of the last query lies beyond the line
+    assert counts[-62:].sum() > 0 and cc["windows"][-1][1] + 62 == L                   # ... up to its last column
+
+
 # ---- the host legs ----
 
 KINDS = ["db_far", "db_straddle", "q_far", "both_far"]

@@ -16,7 +16,11 @@ the first test that needs them.
 
 The fourth session (session_cases.ITERATING) puts sw_db_pssm_from_hits into such a row: five updates back to
 back on alternating streams behind the search and the alignment that feed the first, with the packed pair-list and pre-filter
-routes in between."""
+routes in between.
+
+The fifth (session_cases.WEIGHTED) alternates sw_db_pssm_hit_weights on stream 0 with the sw_db_pssm_from_hits on stream 1 that takes
+its output as d_weights: the two calls share one device table and two pinned copies but lay the table out differently, and only the
+library's ordering keeps the weights call of the next world from overwriting the table the update of this world is still reading."""
 import time
 
 import numpy as np
@@ -414,6 +418,109 @@ def test_iterating_session_updates_back_to_back(swamd, expect, checker):  # noqa
         assert n == len(pr) and np.array_equal(scores, u.astype(np.int32))
         p = got_pairs[:n]
         assert np.array_equal(p[np.lexsort((p[:, 1], p[:, 0]))], pr) and (got_pairs[n:] == -1).all()
+        assert_guards(arena)
+    finally:
+        for db in dbs:
+            db.close()
+        eng.close()
+
+
+def test_weighted_session_weights_and_updates_in_turn(swamd):
+    """session_cases.WEIGHTED on one fresh context: search_pssm_top and align_pssm_hits, then for worlds of 4, 24 and 256 letters the
+    weights on stream 0 and the update that reads them on stream 1, then a search on the last matrix.  The table the two calls share
+    takes the weights layout and the update layout in turn and grows before update0, update1 and update2, the accumulators before
+    weights1 and weights2 (tests/test_session_host.py).  Every input is uploaded first; nothing is synchronised, copied or read between
+    the calls; every output lies in one guarded arena; expected: the host legs chained (held to the numpy rules in
+    tests/test_session_host.py)."""
+    import torch as t
+
+    import pssm_hits_cases as phc
+    worlds = sc.weighted(swamd)["worlds"]
+    steps, (want_hits, want_n), _ = sc.weighted_expected(swamd)
+    eng = swamd.Engine(0)
+    second = t.cuda.Stream()
+    dbs = []
+    try:
+        i8 = lambda a: t.from_numpy(np.ascontiguousarray(a).reshape(-1).copy()).to(DEV)  # noqa: E731
+        w_db = [eng.prepare_db(to_dev(t, c.packed), c.offs) for c in worlds]
+        dbs += w_db
+        d_prior = [i8(c.prior) for c in worlds]
+        c0, c2 = worlds[0], worlds[2]
+        nq0, top0, cap0 = len(c0.qoffs) - 1, sc.WEIGHT_TOPS[0], c0.cap
+        nq2 = len(c2.qoffs) - 1
+        nent = [(len(c.qoffs) - 1) * c.hits.shape[1] for c in worlds]
+        sizes = ([nq0 * top0 * 24, nq0 * 8, nq0 * top0 * 56, nq0 * top0 * cap0, nq2 * sc.WEIGHTED_TOP_AGAIN * 24, nq2 * 8] + [c.prior.size for c in worlds]
+                 + [4 * n for n in nent])
+        arena = Arena(t, DEV, arena_bytes(*sizes))
+        i64 = lambda n, name: arena.view(arena.carve(n * 8, align=8, name=name), t.int64, (n,))  # noqa: E731
+        hits0, nhits0, aln0 = i64(nq0 * top0 * 3, "hits"), i64(nq0, "nhits"), i64(nq0 * top0 * 7, "aln")
+        ops0 = arena.view(arena.carve(nq0 * top0 * cap0, name="ops"), t.uint8, (nq0 * top0 * cap0,))
+        hits2, nhits2 = i64(nq2 * sc.WEIGHTED_TOP_AGAIN * 3, "hits again"), i64(nq2, "nhits again")
+        d_new = [arena.view(arena.carve(c.prior.size, name=f"matrix {k}"), t.int8, (c.prior.size,)) for k, c in enumerate(worlds)]
+        d_w = [arena.view(arena.carve(4 * n, align=4, name=f"weights {k}"), t.int32, (n,)) for k, n in enumerate(nent)]
+        tables = [None] + [(t.from_numpy(c.hits.copy()).to(DEV), t.from_numpy(c.aln.copy()).to(DEV), t.from_numpy(c.ops.copy()).to(DEV)) for c in worlds[1:]]
+        with t.cuda.stream(second):
+            t.zeros(1, dtype=t.int64, device=DEV)
+        said = {}
+
+        def call(name):
+            if name == "pssm_top":
+                w_db[0].search_pssm_top_device(d_prior[0], c0.qoffs, phc.scoring(c0), top0, sc.ITER_MIN_SCORE, out=(hits0, nhits0))
+            elif name == "align":
+                w_db[0].align_pssm_hits_device(d_prior[0], c0.qoffs, phc.scoring(c0), hits0, nhits0, ops_cap=cap0, out=(aln0, ops0), top=top0)
+            elif name == "pssm_top_again":
+                w_db[2].search_pssm_top_device(d_new[2], c2.qoffs, phc.scoring(c2), sc.WEIGHTED_TOP_AGAIN, sc.ITER_MIN_SCORE, out=(hits2, nhits2))
+            else:
+                k = int(name[-1])
+                c = worlds[k]
+                h, n, a, o = (hits0, nhits0, aln0, ops0) if k == 0 else (tables[k][0], None, tables[k][1], tables[k][2])
+                if name.startswith("weights"):
+                    w_db[k].pssm_hit_weights_device(c.qoffs, phc.scoring(c), (c.per_hit, c.inc), h, n, a, o, c.cap, out=d_w[k], top=c.hits.shape[1])
+                    said[name] = (eng.get_option("last_pssm_weights_launches"), eng.get_option("last_pssm_weights_tiles"))
+                else:
+                    assert name.startswith("update")
+                    w_db[k].pssm_from_hits_device(d_prior[k], c.qoffs, phc.scoring(c), (c.sub, c.pw, c.inc), h, n, a, o, c.cap, weights=d_w[k], out=d_new[k],
+                                                  top=c.hits.shape[1])
+                    said[name] = eng.get_option("last_pssm_hits_launches")
+
+        t.cuda.synchronize()
+        t0 = time.perf_counter()
+        for name, stream in sc.WEIGHTED:
+            if stream:
+                with t.cuda.stream(second):
+                    call(name)
+            else:
+                call(name)
+        t1 = time.perf_counter()
+        t.cuda.synchronize()
+        print(f"\n[weighted] {len(sc.WEIGHTED)} calls enqueued in {1e3 * (t1 - t0):.1f} ms, drained in {1e3 * (time.perf_counter() - t1):.1f} ms")
+        host = lambda x: x.cpu().numpy()  # noqa: E731
+        # the routes: two launches per weights call, one per update; the 513 columns of the last world at 256 letters take 9 tiles
+        assert all(said[f"weights{k}"][0] == 2 and said[f"update{k}"] == 1 for k in range(3)), said
+        assert said["weights2"][1] == 9 and said["weights0"][1] >= 1
+        # steps 1 and 2
+        assert np.array_equal(host(hits0).reshape(nq0, top0, 3), c0.hits) and np.array_equal(host(nhits0), c0.nhits)
+        assert np.array_equal(host(aln0).reshape(nq0, top0, 7), c0.aln)
+        ops = host(ops0).reshape(nq0 * top0, cap0)
+        live = np.arange(cap0)[None, :] < c0.aln.reshape(-1, 7)[:, 6:7]
+        assert np.array_equal(ops[live], c0.ops[live]) and (ops[~live] == POISON).all()
+        # the weights and the updates against the host legs chained
+        wrong = []
+        for k, (c, (w, m)) in enumerate(zip(worlds, steps)):
+            got_w = host(d_w[k]).reshape(w.shape)
+            if not np.array_equal(got_w, w):
+                bad = np.argwhere(got_w != w)
+                wrong.append(f"weights{k}: {len(bad)} weights differ, first (query, entry) {bad[0].tolist()}: {got_w[tuple(bad[0])]} vs {w[tuple(bad[0])]}")
+            got = host(d_new[k]).reshape(c.prior.shape)
+            front = int(c.qoffs[0])
+            if not (got[:front].view(np.uint8) == POISON).all():
+                wrong.append(f"update{k}: the unused front columns were written")
+            if not np.array_equal(got[front:], m[front:]):
+                bad = np.argwhere(got[front:] != m[front:])
+                wrong.append(f"update{k}: {len(bad)} entries differ, first (column, letter) {bad[0].tolist()}: {got[front:][tuple(bad[0])]} vs {m[front:][tuple(bad[0])]}")
+        assert not wrong, "\n  ".join(wrong)
+        # the search on the last matrix
+        assert np.array_equal(host(hits2).reshape(want_hits.shape), want_hits) and np.array_equal(host(nhits2), want_n)
         assert_guards(arena)
     finally:
         for db in dbs:

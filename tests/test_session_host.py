@@ -20,7 +20,11 @@ or is the first to use one of session_cases.WORKSPACES -- but for the four steps
 
 The fourth session (session_cases.ITERATING: five sw_db_pssm_from_hits calls back to back) has tests of its own at the end: the tables
 its first two steps leave are the checker's, every update's host leg equals the numpy rule, and no update could pass on the S, the
-code table or the offsets of the update before it or of the one two before it, whose pinned copy it rewrites."""
+code table or the offsets of the update before it or of the one two before it, whose pinned copy it rewrites.
+
+The fifth session (session_cases.WEIGHTED: sw_db_pssm_hit_weights and sw_db_pssm_from_hits in turn on two streams) likewise: the host
+legs chained equal the numpy rules, the shared table and the accumulators grow where the session says they do, and no weights call or
+update could pass on the code table, the offsets, the S or the accumulators of any other step of the session."""
 import ctypes
 
 import numpy as np
@@ -337,3 +341,95 @@ def test_the_other_sessions_are_the_same_steps():
         assert [n for n in order if n in sc.CHAIN] == list(sc.CHAIN)                    # producers stay in front of their consumers
     a, b = sc.two_contexts()
     assert {x.stream for x in a} == {0} and {x.stream for x in b} == {1} and len(a) == len(b)
+
+
+# ---- the fifth session ----
+
+def test_weighted_host_legs_equal_the_rules_and_the_workspaces_grow(swamd):
+    import pssm_hits_cases as phc
+    import pssm_weights_cases as pwc
+    worlds = sc.weighted(swamd)["worlds"]
+    steps, (hits, nhits), full = sc.weighted_expected(swamd)
+    assert [len(c.letters) for c in worlds] == sc.WEIGHT_NLETTERS == [4, 24, 256]
+    assert [n for n, _ in sc.WEIGHTED] == ["pssm_top", "align", "weights0", "update0", "weights1", "update1", "weights2", "update2", "pssm_top_again"]
+    assert [st for _, st in sc.WEIGHTED] == [0, 1, 0, 1, 0, 1, 0, 1, 0]
+    nqs = [len(c.qoffs) - 1 for c in worlds]
+    assert nqs == sorted(set(nqs)) and len({c.hits.shape[1] for c in worlds}) == 3 and len({c.per_hit for c in worlds}) == 3
+    for c, (w, m) in zip(worlds, steps):
+        front = int(c.qoffs[0])
+        rw, _, used = pwc.reference(c, c.per_hit, c.inc)
+        assert np.array_equal(w, rw)
+        assert sum(len(set(w[q][used[q]].tolist())) > 1 for q in range(len(w))) >= 3          # the rule is at work: the hits of a query weigh differently
+        rm, _, _ = phc.reference(c, c.pw, c.inc, w)
+        assert np.array_equal(m[front:], rm[front:]) and (m[front:] != np.minimum(c.prior[front:], c.smax)).any()
+        assert not np.array_equal(rm, phc.reference(c, c.pw, c.inc)[0])                 # the weights matter to the matrix
+    # the table's need in call order: the two layouts in turn, a larger table before update0, update1 and update2; the accumulators grow twice
+    needs, cap, grew = [], 0, []
+    for k, c in enumerate(worlds):
+        wn, un, acc = sc.table_needs(c)
+        needs += [(f"weights{k}", wn), (f"update{k}", un)]
+    for name, n in needs:
+        if n > cap:
+            grew.append(name)
+            cap = n
+    assert grew == ["weights0", "update0", "update1", "update2"]
+    accs = [sc.table_needs(c)[2] for c in worlds]
+    assert accs[0] < accs[1] < accs[2]
+    # the search on the last matrix reads the NEW matrix
+    c = worlds[-1]
+    assert nhits.min() >= 0 and nhits.max() >= 1 and full[:, :, 1].max() > 0
+    assert not np.array_equal(full, swamd.search_pssm_multi_host((c.prior, c.qoffs), (c.packed, c.offs), phc.scoring(c)))
+
+
+def test_weighted_no_step_could_pass_on_another_steps_state(swamd):
+    """For every world and every OTHER world of the session (the table a call reads may be the one an earlier call left or the one a
+    later call on the other stream has already written): the weights differ in every query with more than two used entries under the
+    other's code table (but where that table merely relabels the residues, once: the 256 letters under the 24), and differ under the
+    other's offsets and on top of the other's accumulators; the matrix differs in every query
+    under the other's S and code table and differs under its offsets where they fit."""
+    import pssm_hits_cases as phc
+    import pssm_weights_cases as pwc
+    worlds = sc.weighted(swamd)["worlds"]
+    steps, _, _ = sc.weighted_expected(swamd)
+    checked = [0, 0]
+    for k, c in enumerate(worlds):
+        w, m = steps[k]
+        used = pwc.reference(c, c.per_hit, c.inc)[2]
+        varied = [q for q in range(len(w)) if used[q].sum() > 2]
+        assert len(varied) >= 3
+        upd = lambda **kw: phc.reference(_with(c, **kw), c.pw, c.inc, w, code=kw.get("code"))[0]  # noqa: E731
+        for j, o in enumerate(worlds):
+            if j == k:
+                continue
+            code = sc.code_of(o.letters)
+            wc_ = sc.weights_under(c, code=code)
+            places = code[np.unique(c.packed[int(c.offs[0]):])]
+            if (places >= 0).all() and places.max() < len(c.letters) and len(set(places.tolist())) == len(places):
+                # the other table only relabels the bytes of this world's targets: the weights cannot tell (the rule counts which residues
+                # coincide, not which they are); the update of the same step, which reads the same table, can -- below
+                assert np.array_equal(wc_, w) and (k, j) == (2, 1)
+            else:
+                assert wc_ is None or all((wc_[q] != w[q]).any() for q in varied), (k, j, "weights: code table")
+            assert not np.array_equal(c.qoffs, o.qoffs[:len(c.qoffs)])
+            if len(o.qoffs) >= len(c.qoffs):
+                wo = sc.weights_under(c, qoffs=o.qoffs)
+                assert wo is None or not np.array_equal(wo, w), (k, j, "weights: offsets")
+                checked[0] += 1
+            wa = sc.weights_under(c, acc=pwc.accumulators(o, o.inc)[:2])
+            assert wa is None or not np.array_equal(wa, w), (k, j, "weights: accumulators")
+            assert rows_differ_in_every_query(c, m, upd(sub=o.sub)), (k, j, "update: S")
+            assert rows_differ_in_every_query(c, m, upd(code=code)), (k, j, "update: code table")
+            if len(o.qoffs) >= len(c.qoffs) and o.qoffs[len(c.qoffs) - 1] <= c.qoffs[-1]:
+                assert not np.array_equal(m, upd(qoffs=np.ascontiguousarray(o.qoffs[:len(c.qoffs)]))), (k, j, "update: offsets")
+                checked[1] += 1
+    assert checked == [3, 2]                                  # every world under each later one; the matrix where the later one's columns fit
+
+
+def _with(c, sub=None, code=None, qoffs=None):
+    import types
+    v = types.SimpleNamespace(**vars(c))
+    if sub is not None:
+        v.sub = sub
+    if qoffs is not None:
+        v.qoffs = qoffs
+    return v
