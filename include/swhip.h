@@ -726,6 +726,60 @@ int  sw_pssm_hit_weights_host(const int64_t* qoffsets, int64_t nqueries, const c
                               const sw_pssm_scoring* scoring, const sw_pssm_weighting* weighting, const sw_hit* hits, const int64_t* nhits,
                               int64_t top, const sw_alignment* aln, const char* ops, int64_t ops_cap, int32_t* weights);
 
+/* The QUERY-ANCHORED ALIGNMENT of aligned hits, on the device (csrc/sw_msa_hits.hip): what an iterative search is usually run for --
+ * the multiple alignment of the hits with one column per query position, as jackhmmer and HHblits write it (A3M) -- from the tables
+ * sw_db_align_affine_hits / sw_db_align_pssm_hits leave on the device, without bringing the nqueries x top x ops_cap op rows to the host.
+ *   d_queries : device, the query letters as the sequence calls take them (query q at d_queries + qoffsets[q]); NULL for PSSM
+ *               queries, which have no letters: nident is then 0.  Used for nident only.
+ *   include_min_score, d_hits, d_nhits, top, d_aln, d_ops, ops_cap : as for sw_db_pssm_from_hits.  Only read.
+ * USED ENTRIES and THE WALK are exactly those of sw_db_pssm_from_hits, with include_min_score in the place of upd->include_min_score:
+ *   the same guards, every index compared, unsigned, before anything is loaded through it; an 'M' PAIRS column j with the byte t[i]
+ *   only if j < qlen and i < len.  A VALID INSERT is a 'D' op met with i < len and j <= qlen: the target byte t[i] stands between
+ *   columns j - 1 and j.  The call is defined for ANY bytes in the device tables and reads and writes nothing out of bounds.
+ * COLUMN ROWS, d_cols (optional): device, (qoffsets[nqueries] - qoffsets[0]) x top bytes; EVERY byte is written.  Row (q, r) has qlen
+ *   bytes at d_cols + (qoffsets[q] - qoffsets[0]) x top + r x qlen: byte j is t[i], verbatim, where the walk pairs column j, and '-'
+ *   everywhere else; the row of an entry that is not used is all '-'.  A query's rows are a top x qlen matrix a kernel reads by column.
+ * A3M ROWS, d_a3m with d_rows (optional together): the row of a used entry is its column row with the byte of every valid insert
+ *   placed before column j, in op order (inserts behind the last column at the end); insert bytes 'A'..'Z' become + 32 (lower case),
+ *   every other byte stays.  So column j sits at j + the valid inserts seen before the walk reaches column j (all of them for the
+ *   columns behind the walk's end), and len = qlen + ninsert; an entry that is not used has len = 0.
+ *   d_rows    : device, nqueries x top sw_msa_row; EVERY one is written.  off: the exclusive prefix sum of len over the entries in (q, r)
+ *               order, computed on the device; nmatch: the paired columns; nident: the paired columns with t[i] == the query's letter j
+ *               (0 with d_queries == NULL); ninsert: the valid inserts.  An entry that is not used gets {off, 0, 0, 0, 0}.
+ *   d_a3m, a3m_cap : device, a3m_cap bytes (d_a3m may be NULL: the rows alone, a sizing call).  The row of entry (q, r) lies at
+ *               d_a3m + off; a row with off + len > a3m_cap is not written, and nothing is written at or beyond d_a3m + a3m_cap.
+ *   d_a3m_bytes : device, one int64 (optional with d_rows alone): the TRUE total of len, also beyond a3m_cap -- the caller compares and calls again.
+ * Bytes only: the same bytes on every run.  Asynchronous on `stream`, no host round trip: the host reads none of the device tables;
+ * its work is O(nqueries).  The offsets are uploaded through the two pinned copies of sw_db_pssm_from_hits, in the same turns.
+ * Launches (swp::plan_msa_hits): A, one workgroup per (query, slice of entries), writes the column rows and the rows' counts; with
+ * d_rows, B scans len in two levels (256 entries per workgroup in LDS, then one workgroup over the sums; no atomics) and C writes off
+ * and the A3M rows, one wave per entry.  "last_msa_hits_launches" reports the kernel launches of the last call.
+ * nqueries == 0 launches nothing; with a handle of ntargets == 0 no entry is used: '-' everywhere, every len 0.
+ * SW_EINVAL, checked before the first launch: the offset and handle errors of sw_db_align_affine_hits; top outside 1..SW_TOP_MAX; NULL
+ * d_hits, d_aln or d_ops; ops_cap < 1; every output NULL (d_cols and d_rows both NULL); d_a3m or d_a3m_bytes without d_rows; d_a3m
+ * without d_a3m_bytes; a negative a3m_cap.
+ *   sw_msa_from_hits_host  the CPU leg: the same bytes in plain C++ from host memory, db / offsets / ntargets in the handle's place
+ *               (queries: the letters at queries + qoffsets[q], or NULL).
+ *   sw_write_a3m  one query's A3M file from host copies of the tables: with `query` (qlen letters) the file opens with the record
+ *               ">qname" and the query's letters, with query == NULL (a PSSM) there is no query record.  Then, for r = 0 .. top - 1 in
+ *               order, every entry with rows[r].len > 0 whose row lies inside a3m_cap gets
+ *                   >NAME score=S q=B-E t=B-E ident=N/M
+ *               (NAME = tnames[target], or the target's index with tnames == NULL; S = max_score; the begins and ends of sw_alignment;
+ *               N = nident, M = nmatch) and its row a3m[rows[r].off .. + len).  hits, aln, rows: the query's top entries;
+ *               a3m, a3m_cap: the call's whole buffer.  SW_EINVAL: NULL path, qname, hits, aln, rows or a3m, top < 1, qlen < 1, a row
+ *               of a target index outside 0..ntargets - 1, a file that cannot be written. */
+typedef struct { int64_t off; int32_t len; int32_t nmatch; int32_t nident; int32_t ninsert; } sw_msa_row;
+int  sw_db_msa_from_hits(sw_ctx* ctx, const sw_db* db, const char* d_queries, const int64_t* qoffsets, int64_t nqueries,
+                         int64_t include_min_score, const sw_hit* d_hits, const int64_t* d_nhits, int64_t top, const sw_alignment* d_aln,
+                         const char* d_ops, int64_t ops_cap, char* d_cols, sw_msa_row* d_rows, char* d_a3m, int64_t a3m_cap,
+                         int64_t* d_a3m_bytes, void* stream);
+int  sw_msa_from_hits_host(const char* queries, const int64_t* qoffsets, int64_t nqueries, const char* db, const int64_t* offsets,
+                           int64_t ntargets, int64_t include_min_score, const sw_hit* hits, const int64_t* nhits, int64_t top,
+                           const sw_alignment* aln, const char* ops, int64_t ops_cap, char* cols, sw_msa_row* rows, char* a3m,
+                           int64_t a3m_cap, int64_t* a3m_bytes);
+int  sw_write_a3m(const char* path, const char* qname, const char* query, int64_t qlen, const char* const* tnames, int64_t ntargets,
+                  const sw_hit* hits, const sw_alignment* aln, const sw_msa_row* rows, int64_t top, const char* a3m, int64_t a3m_cap);
+
 /* Tables.  sw_submat_match: s[x][y] = x == y ? match : mismatch (matchMissmatchScore, serial_smithW.c:251-256; both must fit int8:
  * the builder returns nothing, so it clamps them to -128..127 -- a caller that takes them from a user checks the range first, as
  * smithW and the Python wrapper do, which refuse such scores).  sw_submat_from_letters: `scores` is n x n, row = query letter, over the n bytes of

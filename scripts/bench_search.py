@@ -72,6 +72,12 @@
   run fails if they differ).  (b) one weighted iteration, align_pssm_hits_device + pssm_hit_weights_device + pssm_from_hits_device (with the
   weights; prior_weight x per_hit) + search_pssm_top_device, against the unweighted one of --pssm-iterate; *_update_alone_ms is
   pssm_from_hits_device without weights, the kernel the expectation "about twice" refers to
+  --msa: data set (a) only, 64 sequence queries of --qlen through one handle, top 10, 100 and 4096: search_affine_top_device and
+  align_affine_hits_device fill the device tables once (ops_cap 4 x qlen, as for --pssm-iterate); then msa_from_hits_device alone -- the
+  column rows, the row table and the A3M rows into buffers sized by one sizing call beforehand -- against what a caller had to do
+  without it: D2H of d_hits, d_nhits, d_aln and d_ops, then msa_from_hits_host.  7 calls each after a warm-up, wall clock around a
+  synchronised leg, ALTERNATING in one process; the three outputs compared byte for byte (the run fails if they differ).  *_bytes_written
+  is what the device call stores (column rows + 24 bytes per entry + A3M rows), *_write_gbs that over the device call's time
 GCUPS = query letters x target letters / time of the call (torch events, median of --reps after --warmup)."""
 import argparse
 import importlib
@@ -123,6 +129,7 @@ def main():
     ap.add_argument("--pssm", action="store_true", help="data set (a) only: 64 PSSM queries derived from 64 sequence queries beside those, alternating")
     ap.add_argument("--pssm-iterate", action="store_true", help="data set (a) only: the PSSM update on the device against the host round trip, and a whole iteration against the search alone")
     ap.add_argument("--pssm-weights", action="store_true", help="data set (a) only: the hit weights on the device against the host round trip, and a weighted iteration against the unweighted one")
+    ap.add_argument("--msa", action="store_true", help="data set (a) only: the query-anchored alignment of the top 10 / 100 / 4096 hits of 64 queries on the device against the host round trip")
     ap.add_argument("--lanes", action="store_true", help="data set (a) only: 64 queries under search_lanes 32 and 16, alternating, full tables and top 10")
     ap.add_argument("--pairs-lanes", action="store_true", help="data set (a) only: pair lists of all, 10 %% and 1 %% of the cross product under search_pairs_lanes 32 and 16, alternating")
     ap.add_argument("--top", action="store_true", help="data set (a) only: the best 100 targets of 64 queries by the full table and by the selection on the device")
@@ -681,6 +688,69 @@ def main():
         out[f"{P}_identical"] = all(out[f"{P}_top{t}_identical"] for t in (10, 100, 4096))
         db.close()
 
+    def msa_leg(packed, offs, nq=64, reps=7):
+        import time
+        d_db = torch.from_numpy(packed.copy()).to(dev)
+        db = eng.prepare_db(d_db, offs)
+        qoffs = np.arange(nq + 1, dtype=np.int64) * args.qlen
+        queries = rng.choice(PROTEIN, int(qoffs[-1])).astype(np.uint8)
+        d_q = torch.from_numpy(queries.copy()).to(dev)
+        scoring, cap, inc = (sub, -11, -1), 4 * args.qlen, 1
+        P = "msa"
+        out[f"{P}_queries"], out[f"{P}_qlen"], out[f"{P}_targets"], out[f"{P}_reps"], out[f"{P}_ops_cap"] = nq, args.qlen, len(offs) - 1, reps, cap
+        for top in (10, 100, 4096):
+            hits, nhits = db.search_affine_top_device(d_q, qoffs, scoring, top, 1)
+            aln, ops = db.align_affine_hits_device(d_q, qoffs, scoring, hits, nhits, ops_cap=cap)
+            _, rows, _, total = db.msa_from_hits_device(d_q, qoffs, inc, hits, nhits, aln, ops, cap, cols=False)      # the sizing call
+            torch.cuda.synchronize()
+            a3m_bytes = int(total.item())
+            cols = torch.empty(int(qoffs[-1]) * top, dtype=torch.uint8, device=dev)
+            a3m = torch.empty(max(1, a3m_bytes), dtype=torch.uint8, device=dev)
+            state = {}
+
+            def device_call():
+                db.msa_from_hits_device(d_q, qoffs, inc, hits, nhits, aln, ops, cap, cols=cols, rows=rows, a3m=a3m, a3m_cap=a3m_bytes, a3m_bytes=total)
+
+            def host_round_trip():
+                h, n, a, o = hits.cpu().numpy(), nhits.cpu().numpy(), aln.cpu().numpy(), ops.cpu().numpy()
+                state["host"] = swamd.msa_from_hits_host((queries, qoffs), (packed, offs), inc, h, n, a, o, a3m_cap=a3m_bytes)
+
+            def wall(fn):                                                    # wall clock around a synchronised call
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                fn()
+                torch.cuda.synchronize()
+                return (time.perf_counter() - t0) * 1e3
+
+            legs = {"device_call": device_call, "host_round_trip": host_round_trip}
+            ms = {k: [] for k in legs}
+            for k in legs:
+                wall(legs[k])                                                # warm-up
+            for _ in range(reps):                                            # alternating: a drift of the device shows in both alike
+                for k in legs:
+                    ms[k].append(wall(legs[k]))
+            for k in legs:
+                out[f"{P}_top{top}_{k}_ms"] = round(float(np.median(ms[k])), 4)
+                out[f"{P}_top{top}_{k}_range_ms"] = [round(min(ms[k]), 4), round(max(ms[k]), 4)]
+            cols.fill_(0x55); rows.fill_(0x5555555555555555); a3m.fill_(0x55); total.fill_(-1)
+            device_call()
+            torch.cuda.synchronize()
+            hc, hr, ha = state["host"]
+            n = nq * top
+            out[f"{P}_top{top}_identical"] = bool(cols.cpu().numpy().tobytes() == hc.tobytes() and rows.cpu().numpy()[:3 * n].tobytes() == hr.tobytes()
+                                                  and a3m.cpu().numpy()[:a3m_bytes].tobytes() == ha.tobytes() and int(total.item()) == a3m_bytes)
+            out[f"{P}_top{top}_launches"] = eng.get_option("last_msa_hits_launches")
+            out[f"{P}_top{top}_used_entries"] = int((hr["len"] > 0).sum())
+            out[f"{P}_top{top}_inserts"] = int(hr["ninsert"].sum())
+            out[f"{P}_top{top}_over_cap"] = int((aln[:, :, 6] > cap).sum().item())
+            written = cols.numel() + 24 * n + a3m_bytes
+            out[f"{P}_top{top}_bytes_written"] = int(written)
+            out[f"{P}_top{top}_d2h_bytes"] = int(hits.numel() * 8 + nhits.numel() * 8 + aln.numel() * 8 + ops.numel())
+            out[f"{P}_top{top}_write_gbs"] = round(written / out[f"{P}_top{top}_device_call_ms"] / 1e6, 2)
+            out[f"{P}_top{top}_host_over_device"] = round(out[f"{P}_top{top}_host_round_trip_ms"] / out[f"{P}_top{top}_device_call_ms"], 2)
+        out[f"{P}_identical"] = all(out[f"{P}_top{t}_identical"] for t in (10, 100, 4096))
+        db.close()
+
     def pssm_weights_leg(packed, offs, nq=64, reps=7, per_hit=16):
         import time
         d_db = torch.from_numpy(packed.copy()).to(dev)
@@ -952,7 +1022,7 @@ def main():
     out["a_letters"] = int(offs[-1])
     out["a_len_median"] = int(np.median(lens))
     out["a_len_max"] = int(lens.max())
-    if args.multi or args.top or args.align_hits or args.pairs or args.prefilter or args.prefiltered_top or args.pssm or args.pssm_iterate or args.pssm_weights or args.lanes or args.pairs_lanes:
+    if args.multi or args.top or args.align_hits or args.pairs or args.prefilter or args.prefiltered_top or args.pssm or args.pssm_iterate or args.pssm_weights or args.msa or args.lanes or args.pairs_lanes:
         if args.lanes:
             lanes_leg(packed, offs)
         if args.pairs_lanes:
@@ -963,6 +1033,8 @@ def main():
             pssm_iterate_leg(packed, offs)
         if args.pssm_weights:
             pssm_weights_leg(packed, offs)
+        if args.msa:
+            msa_leg(packed, offs)
         if args.pairs:
             pairs_leg(packed, offs)
         if args.prefilter:
@@ -987,6 +1059,8 @@ def main():
             sys.exit("bench_search.py --pssm-iterate: pssm_iterate_identical is false")
         if args.pssm_weights and not out["pssm_weights_identical"]:
             sys.exit("bench_search.py --pssm-weights: pssm_weights_identical is false")
+        if args.msa and not out["msa_identical"]:
+            sys.exit("bench_search.py --msa: msa_identical is false")
         if args.pssm and not out["pssm_identical"]:
             sys.exit("bench_search.py --pssm: pssm_identical is false")
         if args.pairs:   # the required conditions of the pair-list call: a line that misses one is printed, and the run fails

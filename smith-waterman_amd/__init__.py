@@ -110,6 +110,9 @@ ABI = {
                                       _vp]),
     "sw_pssm_hit_weights_host": (_i32, [_vp, _i64, _vp, _vp, _i64, ctypes.POINTER(_PssmScoring), ctypes.POINTER(_PssmWeighting), _vp, _vp, _i64, _vp, _vp,
                                         _i64, _vp]),
+    "sw_db_msa_from_hits": (_i32, [_vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp]),
+    "sw_msa_from_hits_host": (_i32, [_vp, _vp, _i64, _vp, _vp, _i64, _i64, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _vp]),
+    "sw_write_a3m": (_i32, [ctypes.c_char_p, ctypes.c_char_p, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _i64]),
     "sw_write_pssm": (_i32, [ctypes.c_char_p, _vp, ctypes.c_int32, _vp, _i64, _vp]),
     "sw_align_affine_device": (_i32, [_vp, _vp, _i64, _vp, _vp, _i64, _vp, _i64, ctypes.POINTER(_Affine), _vp, _vp, _i64, _vp]),
     "sw_align_affine_host": (_i32, [_vp, _i64, _vp, _vp, _i64, _vp, _i64, ctypes.POINTER(_Affine), _vp, _vp, _i64]),
@@ -155,6 +158,8 @@ ABI = {
 }
 
 SW_TOP_MAX = 4096   # include/swhip.h: the most hits per query a selecting call takes
+# sw_msa_row (include/swhip.h), 24 bytes: an entry's A3M row is a3m[off : off + len]
+MSA_ROW = np.dtype([("off", np.int64), ("len", np.int32), ("nmatch", np.int32), ("nident", np.int32), ("ninsert", np.int32)])
 
 _lib = None
 
@@ -594,6 +599,68 @@ def pssm_hit_weights_host(qoffsets_or_pssm, targets, scoring, weighting, hits, n
                                           hits.ctypes.data if hits.size else aa.ctypes.data, nhits.ctypes.data if nhits is not None else None, top,
                                           aa.ctypes.data, o.ctypes.data, cap, w.ctypes.data))
     return w[:nq * top].reshape(nq, top)
+
+
+def _msa_queries(queries):
+    """The queries of an msa_from_hits call -> (packed letters or None, int64 offsets): a list of sequences or a (packed, offsets) pair;
+    a 1-D int64 array is the column offsets of PSSM queries, which have no letters."""
+    if isinstance(queries, np.ndarray) and queries.ndim == 1 and queries.dtype == np.int64:
+        return None, np.ascontiguousarray(queries)
+    return _pack_targets(queries)
+
+
+def msa_from_hits_host(queries, targets, include_min_score, hits, nhits, aln, ops, a3m_cap=None):
+    """sw_msa_from_hits_host: the query-anchored alignment of aligned hits in plain C++ on the host (no GPU).  Arguments and results as
+    Database.msa_from_hits."""
+    qpacked, qoffs = _msa_queries(queries)
+    packed, offs = _pack_targets(targets)
+    nq = len(qoffs) - 1
+    hits, nhits = _hit_table(hits, nhits, nq)
+    top = hits.shape[1]
+    a = np.ascontiguousarray(aln, np.int64).reshape(-1, 7)
+    if len(a) != nq * top:
+        raise ValueError(f"aln must be ({nq}, {top}, 7) int64")
+    o, cap = _ops_table(ops, nq, top)
+    db = packed if len(packed) else np.zeros(1, np.uint8)
+    aa = a if len(a) else np.zeros((1, 7), np.int64)
+    ncols = int(qoffs[-1] - qoffs[0])
+    cols = np.zeros(max(1, ncols * top), np.uint8)
+    rows = np.zeros(max(1, nq * top), MSA_ROW)
+    total = _i64(0)
+
+    def call(c, a3m, a3m_cap):
+        _check(lib().sw_msa_from_hits_host(qpacked.ctypes.data if qpacked is not None and len(qpacked) else None, qoffs.ctypes.data, nq, db.ctypes.data,
+                                           offs.ctypes.data, len(offs) - 1, int(include_min_score), hits.ctypes.data if hits.size else aa.ctypes.data,
+                                           nhits.ctypes.data if nhits is not None else None, top, aa.ctypes.data, o.ctypes.data, cap, c, rows.ctypes.data,
+                                           a3m, a3m_cap, ctypes.addressof(total)))
+    if a3m_cap is None:
+        call(None, None, 0)   # the sizing call: the rows and the total
+        a3m_cap = total.value
+    a3m = np.zeros(max(1, int(a3m_cap)), np.uint8)
+    call(cols.ctypes.data, a3m.ctypes.data, int(a3m_cap))
+    return cols[:ncols * top], rows[:nq * top].reshape(nq, top), a3m[:int(a3m_cap)]
+
+
+def write_a3m(path: str, qname: str, query, tnames, hits, aln, rows, a3m):
+    """sw_write_a3m: one query's A3M file.  query: its letters, or an int (the number of columns of a PSSM query: no query record);
+    tnames: the names of ALL targets, or None for their indices; hits, aln, rows: the query's (top, 3), (top, 7) and (top,) MSA_ROW
+    entries; a3m: the whole byte buffer the rows' off count from."""
+    q = None if isinstance(query, (int, np.integer)) else np.ascontiguousarray(_as_seq(query))
+    qlen = int(query) if q is None else len(q)
+    h = np.ascontiguousarray(hits, np.int64).reshape(-1, 3)
+    al = np.ascontiguousarray(aln, np.int64).reshape(-1, 7)
+    rw = np.ascontiguousarray(rows, MSA_ROW).reshape(-1)
+    buf = np.ascontiguousarray(a3m, np.uint8).reshape(-1)
+    if not (len(h) == len(al) == len(rw)):
+        raise ValueError("hits, aln and rows must hold the same number of entries")
+    names, nt = None, int(h[:, 0].max(initial=-1)) + 1
+    if tnames is not None:
+        nt = len(tnames)
+        names = (ctypes.c_char_p * max(1, nt))(*[os.fsencode(n) if isinstance(n, str) else bytes(n) for n in tnames])
+    one = np.zeros(1, np.uint8)
+    _check(lib().sw_write_a3m(os.fsencode(path), qname.encode(), q.ctypes.data if q is not None and len(q) else None, qlen,
+                              ctypes.cast(names, _vp) if names is not None else None, nt, h.ctypes.data if len(h) else None, al.ctypes.data if len(al) else None,
+                              rw.ctypes.data if len(rw) else None, len(h), (buf if len(buf) else one).ctypes.data, len(buf)))
 
 
 def search_pssm_multi_host(pssm, targets, scoring):
@@ -1194,6 +1261,101 @@ class Database:
                                             nhits.data_ptr() if nhits is not None else None, top, aln.data_ptr(), ops.data_ptr() if ops is not None else None,
                                             int(ops_cap), out.data_ptr(), eng._stream()))
         return out
+
+    def msa_from_hits(self, queries, include_min_score, hits, nhits, aln, ops):
+        """The query-anchored alignment of aligned hits (sw_db_msa_from_hits).  queries: the sequences as for search_affine, or the 1-D
+        int64 column offsets of PSSM queries (no letters: nident is 0); hits, nhits, aln, ops as for pssm_from_hits.  Returns (cols,
+        rows, a3m) as numpy arrays: cols, uint8, query q's (top, qlen) matrix of column rows at (qoffsets[q] - qoffsets[0]) * top;
+        rows, (nqueries, top) of MSA_ROW; a3m, uint8, entry (q, r)'s A3M row at rows[q, r]["off"], rows[q, r]["len"] bytes.
+        include/swhip.h states the rule.  Two calls: one for the rows and the size, one for the bytes."""
+        eng = self.engine
+        t = eng.torch
+        dev = f"cuda:{eng.device}"
+        qpacked, qoffs = _msa_queries(queries)
+        nq = len(qoffs) - 1
+        hits, nhits = _hit_table(hits, nhits, nq)
+        top = hits.shape[1]
+        a = np.ascontiguousarray(aln, np.int64).reshape(-1, 7)
+        if len(a) != nq * top:
+            raise ValueError(f"aln must be ({nq}, {top}, 7) int64")
+        o, cap = _ops_table(ops, nq, top)
+        d_q = t.from_numpy(qpacked.copy()).to(dev) if qpacked is not None and len(qpacked) else None
+        d_hits = t.from_numpy(hits.reshape(-1).copy() if hits.size else np.zeros(3, np.int64)).to(dev)
+        d_nhits = t.from_numpy(nhits.copy()).to(dev) if nhits is not None and len(nhits) else None
+        d_aln = t.from_numpy(a.reshape(-1).copy() if a.size else np.zeros(7, np.int64)).to(dev)
+        d_ops = t.from_numpy(o.reshape(-1).copy()).to(dev)
+        tables = (d_q, qoffs, include_min_score, d_hits, d_nhits, d_aln, d_ops, cap)
+        _, rows, _, total = self.msa_from_hits_device(*tables, top=top, cols=False)
+        eng.synchronize()
+        a3m = t.zeros(max(1, int(total.item())), dtype=t.uint8, device=dev)
+        cols, rows, a3m, total = self.msa_from_hits_device(*tables, top=top, rows=rows, a3m=a3m, a3m_cap=int(total.item()), a3m_bytes=total)
+        eng.synchronize()
+        ncols = int(qoffs[-1] - qoffs[0])
+        return (cols.cpu().numpy()[:ncols * top], rows.cpu().numpy().view(MSA_ROW).reshape(-1)[:nq * top].reshape(nq, top),
+                a3m.cpu().numpy()[:int(total.item())])
+
+    def msa_from_hits_device(self, d_queries, qoffsets, include_min_score, hits, nhits, aln, ops, ops_cap: int, top=None, cols=None, rows=None,
+                             a3m=None, a3m_cap=None, a3m_bytes=None):
+        """sw_db_msa_from_hits on device-resident tables: the query letters (a uint8 tensor, query q at qoffsets[q]; None for PSSM
+        queries), the hit table and counts of search_*_top_device, the alignments and ops of align_*_hits_device; asynchronous on
+        torch's current stream, nothing comes to the host.  cols: the uint8 tensor of at least (columns of the queries) x top elements
+        that receives the column rows, None for a fresh one, False for none.  rows: the int64 tensor of at least nqueries x top x 3
+        elements that receives the sw_msa_row table (24 bytes per entry: view its numpy copy as MSA_ROW), None for a fresh one, False
+        for none (the column rows alone).  a3m: the uint8 tensor that receives the A3M rows, None for none (the rows and the total
+        alone: a sizing call); a3m_cap: the bytes of it the call may write (default: all).  a3m_bytes: the int64 tensor that receives
+        the true total, None for a fresh one.  Returns (cols, rows, a3m, a3m_bytes), None where there is none."""
+        eng = self.engine
+        t = eng.torch
+        dev = f"cuda:{eng.device}"
+        qoffs = np.ascontiguousarray(qoffsets, np.int64).reshape(-1)
+        if len(qoffs) == 0:
+            qoffs = np.zeros(1, np.int64)
+        nq = len(qoffs) - 1
+        if top is None:
+            if hits.dim() != 3:
+                raise ValueError("hits must be (nqueries, top, 3), or `top` given")
+            top = hits.shape[1]
+        top = int(top)
+        n = nq * max(0, top)
+        if d_queries is not None and (d_queries.dtype != t.uint8 or not d_queries.is_contiguous() or d_queries.numel() < int(qoffs[-1])):
+            raise ValueError(f"d_queries must be a contiguous uint8 tensor of at least {int(qoffs[-1])} elements")
+        if hits.dtype != t.int64 or not hits.is_contiguous() or hits.numel() < n * 3:
+            raise ValueError(f"hits must be a contiguous int64 tensor of at least {nq} x {top} x 3 elements")
+        if nhits is not None and (nhits.dtype != t.int64 or not nhits.is_contiguous() or nhits.numel() < nq):
+            raise ValueError(f"nhits must be a contiguous int64 tensor of at least {nq} elements")
+        if aln.dtype != t.int64 or not aln.is_contiguous() or aln.numel() < n * 7:
+            raise ValueError(f"aln must be a contiguous int64 tensor of at least {n * 7} elements")
+        if ops is not None and (ops.dtype != t.uint8 or not ops.is_contiguous() or ops.numel() < n * max(0, int(ops_cap))):
+            raise ValueError(f"ops must be a contiguous uint8 tensor of at least {n * max(0, int(ops_cap))} elements")
+        ncols = int(qoffs[-1] - qoffs[0]) * max(0, top)
+        if cols is None:
+            cols = t.empty(max(1, ncols), dtype=t.uint8, device=dev)
+        elif cols is False:
+            cols = None
+        if cols is not None and (cols.dtype != t.uint8 or not cols.is_contiguous() or cols.numel() < ncols):
+            raise ValueError(f"cols must be a contiguous uint8 tensor of at least {ncols} elements")
+        if rows is None:
+            rows = t.empty(max(1, n) * 3, dtype=t.int64, device=dev)
+        elif rows is False:
+            rows = None
+        if rows is not None and (rows.dtype != t.int64 or not rows.is_contiguous() or rows.numel() < n * 3):
+            raise ValueError(f"rows must be a contiguous int64 tensor of at least {n * 3} elements")
+        if a3m is not None and (a3m.dtype != t.uint8 or not a3m.is_contiguous()):
+            raise ValueError("a3m must be a contiguous uint8 tensor")
+        if a3m_cap is None:
+            a3m_cap = a3m.numel() if a3m is not None else 0
+        if a3m is not None and a3m.numel() < int(a3m_cap):
+            raise ValueError(f"a3m must hold at least a3m_cap = {int(a3m_cap)} elements")
+        if a3m_bytes is None and rows is not None:
+            a3m_bytes = t.zeros(1, dtype=t.int64, device=dev)
+        if a3m_bytes is not None and (a3m_bytes.dtype != t.int64 or a3m_bytes.numel() < 1):
+            raise ValueError("a3m_bytes must be an int64 tensor of at least one element")
+        _check(lib().sw_db_msa_from_hits(eng._h, self._h, d_queries.data_ptr() if d_queries is not None else None, qoffs.ctypes.data, nq,
+                                         int(include_min_score), hits.data_ptr(), nhits.data_ptr() if nhits is not None else None, top, aln.data_ptr(),
+                                         ops.data_ptr() if ops is not None else None, int(ops_cap), cols.data_ptr() if cols is not None else None,
+                                         rows.data_ptr() if rows is not None else None, a3m.data_ptr() if a3m is not None else None, int(a3m_cap),
+                                         a3m_bytes.data_ptr() if a3m_bytes is not None else None, eng._stream()))
+        return cols, rows, a3m, a3m_bytes
 
     def align_affine_hits_device(self, d_queries, qoffsets, scoring, hits, nhits, ops_cap: int = 0, out=None, top=None, checkpoint=None):
         """sw_db_align_affine_hits on device-resident queries and a device hit table -- the (nqueries, top, 3) int64 tensor and the

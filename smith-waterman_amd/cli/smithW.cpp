@@ -42,6 +42,11 @@
 //     ... --iterations N      with --all-queries or --pssm: N >= 1 rounds of search, alignment of the top hits and a new PSSM built from them on the device
 //                              (sw_db_pssm_from_hits; --include-score S, default 1; --prior-weight W, default 10; --out-pssm PREFIX writes PREFIX.<query>.pssm);
 //                              the hits and --align output are those of the last round; N = 1 is the search of today
+//     ... --out-a3m PREFIX    with --all-queries or --pssm, --align, with or without --iterations: the query-anchored multiple alignment of the LAST round's
+//                              aligned hits, built on the device (sw_db_msa_from_hits) and written per query to PREFIX.<query>.a3m (sw_write_a3m): for a
+//                              sequence query its own record first (with --pssm there is NO query record: a matrix has no letters), then per hit whose
+//                              score reaches --include-score ">name score=S q=b-e t=b-e ident=n/nmatch" and its A3M row -- one byte per query column,
+//                              '-' where the hit has none, the target's inserted letters in lower case between them
 //     ... --weight-hits P     with --iterations / --out-pssm: every round weights its aligned hits on the device before it builds the matrix
 //                              (sw_db_pssm_hit_weights, Henikoff's position-based weights; per_hit = P within 1..65535, the round's --include-score):
 //                              a family that fills the hit list no longer outvotes a distant homologue.  N[j] of the update then counts in units
@@ -469,9 +474,11 @@ static int search_pssm_main(const char* ppath, const char* dbpath, long long top
 // query's letters, for a PSSM file the consensus of the last matrix.  --out-pssm PREFIX writes the matrix the last search ran with, per
 // query, to PREFIX.<query index>.pssm (sw_write_pssm).  --weight-hits P puts sw_db_pssm_hit_weights (per_hit = P, the same
 // --include-score) between the alignment and the update of every round and hands its table to the update; 0: no weights, every hit counts 1.
+static std::vector<std::string> fasta_names(const char* path);
+
 static int search_iter_main(const char* qpath, const char* ppath, const char* dbpath, long long top, long long min_score, const sw_scores& sc, const AffineArgs& af,
                             bool align, bool align_ckpt, int search_lanes, long long iterations, long long include_score, long long prior_weight,
-                            const char* out_pssm, long long weight_hits) {
+                            const char* out_pssm, long long weight_hits, const char* out_a3m) {
     int64_t nq = 0, qtotal = 0, nrec = 0, total = 0;
     CHECK(sw_read_fasta_db(dbpath, nullptr, 0, nullptr, 0, &nrec, &total));
     std::vector<char> db((size_t)total + 1);
@@ -567,6 +574,25 @@ static int search_iter_main(const char* qpath, const char* ppath, const char* db
     if (align)
         CHECK(sw_db_align_pssm_hits(ctx, handle, d_cur, qoffs.data(), nq, &scoring, (const sw_hit*)d_hits, (const int64_t*)d_nhits, K, (sw_alignment*)d_aln,
                                     (char*)d_ops, ops_cap, nullptr));
+    // --out-a3m: the rows of the last round's tables, still on the device: one call for the row table and the size, one for the bytes
+    void *d_qs = nullptr, *d_rows = nullptr, *d_a3m = nullptr, *d_a3m_bytes = nullptr;
+    int64_t a3m_bytes = 0;
+    if (out_a3m) {
+        if (!ppath) {
+            CHECK(sw_device_malloc(ctx, (size_t)qtotal + 16, &d_qs));
+            CHECK(sw_memcpy_h2d(ctx, d_qs, qs.data(), (size_t)qtotal));
+        }
+        CHECK(sw_device_malloc(ctx, n * sizeof(sw_msa_row), &d_rows));
+        CHECK(sw_device_malloc(ctx, sizeof(int64_t), &d_a3m_bytes));
+        CHECK(sw_db_msa_from_hits(ctx, handle, (const char*)d_qs, qoffs.data(), nq, include_score, (const sw_hit*)d_hits, (const int64_t*)d_nhits, K,
+                                  (const sw_alignment*)d_aln, (const char*)d_ops, ops_cap, nullptr, (sw_msa_row*)d_rows, nullptr, 0, (int64_t*)d_a3m_bytes, nullptr));
+        CHECK(sw_synchronize(ctx, nullptr));
+        CHECK(sw_memcpy_d2h(ctx, &a3m_bytes, d_a3m_bytes, sizeof a3m_bytes));
+        CHECK(sw_device_malloc(ctx, (size_t)a3m_bytes + 16, &d_a3m));
+        CHECK(sw_db_msa_from_hits(ctx, handle, (const char*)d_qs, qoffs.data(), nq, include_score, (const sw_hit*)d_hits, (const int64_t*)d_nhits, K,
+                                  (const sw_alignment*)d_aln, (const char*)d_ops, ops_cap, nullptr, (sw_msa_row*)d_rows, (char*)d_a3m, a3m_bytes,
+                                  (int64_t*)d_a3m_bytes, nullptr));
+    }
     CHECK(sw_synchronize(ctx, nullptr));
     const double t2 = now_s();
     std::vector<sw_hit> hits(n);
@@ -587,6 +613,20 @@ static int search_iter_main(const char* qpath, const char* ppath, const char* db
             const int8_t* col = last.data() + g * nletters;
             qs[(size_t)g] = letters[std::max_element(col, col + nletters) - col];
         }
+    std::vector<sw_msa_row> msa_rows;
+    std::vector<char> a3m;
+    std::vector<std::string> tnames, qnames;
+    std::vector<const char*> tname_ptrs;
+    if (out_a3m) {
+        msa_rows.resize(n); a3m.resize((size_t)a3m_bytes + 1);
+        CHECK(sw_memcpy_d2h(ctx, msa_rows.data(), d_rows, n * sizeof(sw_msa_row)));
+        if (a3m_bytes) CHECK(sw_memcpy_d2h(ctx, a3m.data(), d_a3m, (size_t)a3m_bytes));
+        tnames = fasta_names(dbpath);
+        tnames.resize((size_t)nrec, "-");
+        for (const std::string& s : tnames) tname_ptrs.push_back(s.c_str());
+        if (!ppath) qnames = fasta_names(qpath);
+        qnames.resize((size_t)nq, "-");
+    }
     const sw_affine unused = {nullptr, 0, 0};   // (print_hits aligns nothing itself when it is given the rows of a call)
     for (int64_t i = 0; i < nq; ++i) {
         printf("## query record %lld of %s\n", (long long)i, ppath ? ppath : qpath);
@@ -598,6 +638,11 @@ static int search_iter_main(const char* qpath, const char* ppath, const char* db
             CHECK(sw_write_pssm(path.c_str(), letters, nletters, last.data() + qoffs[(size_t)i] * nletters, qoffs[(size_t)i + 1] - qoffs[(size_t)i],
                                 qs.data() + qoffs[(size_t)i]));
         }
+        if (out_a3m) {
+            const std::string path = std::string(out_a3m) + "." + std::to_string((long long)i) + ".a3m";
+            CHECK(sw_write_a3m(path.c_str(), qnames[(size_t)i].c_str(), ppath ? nullptr : qs.data() + qoffs[(size_t)i], qoffs[(size_t)i + 1] - qoffs[(size_t)i],
+                               tname_ptrs.data(), nrec, hits.data() + i * K, aln.data() + i * K, msa_rows.data() + i * K, K, a3m.data(), a3m_bytes));
+        }
     }
     const double cells = (double)qtotal * (double)total * (double)iterations;
     printf("\nElapsed time for database search: %f (%.1f GCUPS; %lld queries, %lld iterations on the device, handle prepared in %f)\n\n", t2 - t1,
@@ -608,6 +653,8 @@ static int search_iter_main(const char* qpath, const char* ppath, const char* db
     if (d_aln) (void)sw_device_free(ctx, d_aln);
     if (d_ops) (void)sw_device_free(ctx, d_ops);
     if (d_weights) (void)sw_device_free(ctx, d_weights);
+    for (void* d : {d_qs, d_rows, d_a3m, d_a3m_bytes})
+        if (d) (void)sw_device_free(ctx, d);
     sw_destroy(ctx);
     return 0;
 }
@@ -811,7 +858,7 @@ int main(int argc, char** argv) {
     int iterations = 1, include_score = 1, prior_weight = 10, weight_hits = 0;
     bool has_weight_hits = false;
     bool has_iter_flag = false;
-    const char* out_pssm = nullptr;
+    const char *out_pssm = nullptr, *out_a3m = nullptr;
     sw_scores sc = {3, -3, -2};
     int npos = 0;
     for (int ai = 1; ai < argc; ++ai) {
@@ -842,6 +889,7 @@ int main(int argc, char** argv) {
         else if (f == "--include-score" && ai + 1 < argc) { if (!parse_int("--include-score", argv[++ai], &include_score)) return 2; has_iter_flag = true; }
         else if (f == "--prior-weight" && ai + 1 < argc) { if (!parse_int("--prior-weight", argv[++ai], &prior_weight)) return 2; has_iter_flag = true; }
         else if (f == "--out-pssm" && ai + 1 < argc) { out_pssm = argv[++ai]; has_iter_flag = true; }
+        else if (f == "--out-a3m" && ai + 1 < argc) { out_a3m = argv[++ai]; has_iter_flag = true; }
         else if (f == "--weight-hits" && ai + 1 < argc) { if (!parse_int("--weight-hits", argv[++ai], &weight_hits)) return 2; has_weight_hits = true; }
         else if (f == "--matrix" && ai + 1 < argc) { af.matrix = argv[++ai]; af.on = true; }
         else if (f == "--gap-open" && ai + 1 < argc) { if (!parse_int("--gap-open", argv[++ai], &af.open)) return 2; af.has_open = af.on = true; }
@@ -853,7 +901,7 @@ int main(int argc, char** argv) {
         else if (f == "--record-b" && ai + 1 < argc) rec_b = strtoll(argv[++ai], nullptr, 10);
         else if (f == "--seed" && ai + 1 < argc) seed = (unsigned)strtoul(argv[++ai], nullptr, 10);
         else if (f == "--scores" && ai + 3 < argc) { sc.match = atoi(argv[++ai]); sc.mismatch = atoi(argv[++ai]); sc.gap = atoi(argv[++ai]); }
-        else { fprintf(stderr, "usage: smithW [<cols> <rows> | --fasta A.fa B.fa [--record-a I] [--record-b J] | --search QUERY.fa DB.fa [--record-a I] [--top K] [--all-queries [--min-score S] [--prefilter S | --prefilter-hits S [--pairs-lanes 16|32]] [--search-lanes 16|32]] [--pairs FILE [--pairs-lanes 16|32]] [--matrix FILE] [--gap-open O] [--gap-extend E] [--align [--align-checkpoint]] | --search --pssm FILE DB.fa --gap-open O --gap-extend E [--top K] [--min-score S] [--align] [--search-lanes 16|32] | with --all-queries or --pssm: [--iterations N] [--include-score S] [--prior-weight W] [--out-pssm PREFIX] [--weight-hits P: Henikoff weights on the device, N[j] then counts in units of P, so scale --prior-weight with it]] [--seed N] [--dump | --dump-labels] [--h64] [--no-backtrack] [--scores M X G] [--gpus N | --devices 0,1,..] [--p8]\n"); return 2; }
+        else { fprintf(stderr, "usage: smithW [<cols> <rows> | --fasta A.fa B.fa [--record-a I] [--record-b J] | --search QUERY.fa DB.fa [--record-a I] [--top K] [--all-queries [--min-score S] [--prefilter S | --prefilter-hits S [--pairs-lanes 16|32]] [--search-lanes 16|32]] [--pairs FILE [--pairs-lanes 16|32]] [--matrix FILE] [--gap-open O] [--gap-extend E] [--align [--align-checkpoint]] | --search --pssm FILE DB.fa --gap-open O --gap-extend E [--top K] [--min-score S] [--align] [--search-lanes 16|32] | with --all-queries or --pssm: [--iterations N] [--include-score S] [--prior-weight W] [--out-pssm PREFIX] [--align --out-a3m PREFIX: the A3M of the last round's hits per query, PREFIX.<query>.a3m; with --pssm it holds no query record] [--weight-hits P: Henikoff weights on the device, N[j] then counts in units of P, so scale --prior-weight with it]] [--seed N] [--dump | --dump-labels] [--h64] [--no-backtrack] [--scores M X G] [--gpus N | --devices 0,1,..] [--p8]\n"); return 2; }
     }
     if (npos == 1) { fprintf(stderr, "smithW: <cols> needs <rows>\n"); return 2; }
     if (align_ckpt && !(search_q && align)) { fprintf(stderr, "smithW: --align-checkpoint goes with --search --align\n"); return 2; }
@@ -867,12 +915,13 @@ int main(int argc, char** argv) {
         if (!search_q || pssm_path || !(pairs_path || has_prefilter_hits)) { fprintf(stderr, "smithW: --pairs-lanes goes with --search --pairs or --search --all-queries --prefilter-hits\n"); return 2; }
     }
     if (has_iter_flag) {   // the iterative search: many sequence queries, or one matrix
-        if (!(search_q && (all_queries || pssm_path))) { fprintf(stderr, "smithW: --iterations / --include-score / --prior-weight / --out-pssm go with --search --all-queries or --search --pssm\n"); return 2; }
+        if (!(search_q && (all_queries || pssm_path))) { fprintf(stderr, "smithW: --iterations / --include-score / --prior-weight / --out-pssm / --out-a3m go with --search --all-queries or --search --pssm\n"); return 2; }
         if (iterations < 1) { fprintf(stderr, "smithW: --iterations N needs N >= 1, got %d\n", iterations); return 2; }
         if (prior_weight < 0 || prior_weight > 65535) { fprintf(stderr, "smithW: --prior-weight W needs W within 0..65535, got %d\n", prior_weight); return 2; }
         if (has_prefilter || has_prefilter_hits || pairs_path) { fprintf(stderr, "smithW: --iterations does not go with --prefilter / --prefilter-hits / --pairs\n"); return 2; }
     }
-    const bool iterate = iterations > 1 || out_pssm;   // (--iterations 1 alone is the search of today, through today's path)
+    const bool iterate = iterations > 1 || out_pssm || out_a3m;   // (--iterations 1 alone is the search of today, through today's path)
+    if (out_a3m && !align) { fprintf(stderr, "smithW: --out-a3m writes the alignment of the aligned hits: it goes with --align\n"); return 2; }
     if (has_weight_hits) {   // the weights feed the update of an iterative search and nothing else
         if (!(has_iter_flag && iterate)) { fprintf(stderr, "smithW: --weight-hits goes with --iterations N (N > 1) or --out-pssm\n"); return 2; }
         if (weight_hits < 1 || weight_hits > 65535) { fprintf(stderr, "smithW: --weight-hits P needs P within 1..65535, got %d\n", weight_hits); return 2; }
@@ -885,7 +934,7 @@ int main(int argc, char** argv) {
         if (!af.has_open || !af.has_extend) { fprintf(stderr, "smithW: --pssm needs --gap-open O and --gap-extend E\n"); return 2; }
         if (iterate) {
             if (sc.match < -128 || sc.match > 127 || sc.mismatch < -128 || sc.mismatch > 127) { fprintf(stderr, "smithW: --pssm --iterations takes its table from --scores M X within -128..127, got %d %d\n", sc.match, sc.mismatch); return 2; }
-            return search_iter_main(nullptr, pssm_path, search_db, top, min_score, sc, af, align, align_ckpt, search_lanes, iterations, include_score, prior_weight, out_pssm, weight_hits);
+            return search_iter_main(nullptr, pssm_path, search_db, top, min_score, sc, af, align, align_ckpt, search_lanes, iterations, include_score, prior_weight, out_pssm, weight_hits, out_a3m);
         }
         return search_pssm_main(pssm_path, search_db, top, min_score, af, align, align_ckpt, search_lanes);
     }
@@ -934,7 +983,7 @@ int main(int argc, char** argv) {
                 fprintf(stderr, "smithW: --all-queries without --matrix needs --scores M X within -128..127 (a table of signed bytes), got %d %d\n", sc.match, sc.mismatch);
                 return 2;
             }
-            if (iterate) return search_iter_main(search_q, nullptr, search_db, top, min_score, sc, af, align, align_ckpt, search_lanes, iterations, include_score, prior_weight, out_pssm, weight_hits);
+            if (iterate) return search_iter_main(search_q, nullptr, search_db, top, min_score, sc, af, align, align_ckpt, search_lanes, iterations, include_score, prior_weight, out_pssm, weight_hits, out_a3m);
             return search_all_main(search_q, search_db, top, min_score, sc, af, align, align_ckpt, prefilter_hits, search_lanes, pairs_lanes);
         }
         if (has_min_score) { fprintf(stderr, "smithW: --min-score goes with --search --all-queries\n"); return 2; }

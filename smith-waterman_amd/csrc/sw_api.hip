@@ -202,6 +202,7 @@ int64_t sw_get_option(sw_ctx* c, const char* name) {
     if (!strcmp(name, "last_top_pairs_launches")) return c->last_top_pairs_launches;
     if (!strcmp(name, "last_top_pairs_kernel")) return c->last_top_pairs_kernel;
     if (!strcmp(name, "last_pssm_hits_launches")) return c->last_pssm_hits_launches;
+    if (!strcmp(name, "last_msa_hits_launches")) return c->last_msa_hits_launches;
     if (!strcmp(name, "last_pssm_weights_launches")) return c->last_pssm_weights_launches;
     if (!strcmp(name, "last_pssm_weights_tiles")) return c->last_pssm_weights_tiles;
     if (!strcmp(name, "search_pairs_chunk")) return c->opt_search_pairs_chunk;

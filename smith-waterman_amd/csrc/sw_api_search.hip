@@ -974,6 +974,58 @@ int sw_db_pssm_hit_weights(sw_ctx* c, const sw_db* db, const int64_t* qoffsets, 
     return SW_OK;
 }
 
+// The query-anchored alignment of a device hit table's entries (csrc/sw_msa_hits.hip).  The host checks the arguments, plans
+// (swp::plan_msa_hits) and uploads the offsets through the small table of the calls above; the hit table, the alignments, the ops and
+// the targets' offsets are read on the device only.  Launch A always; with d_rows the two scan launches and the row launch.  A handle
+// without targets takes the same launches (no entry is used).
+int sw_db_msa_from_hits(sw_ctx* c, const sw_db* db, const char* d_queries, const int64_t* qoffsets, int64_t nqueries, int64_t include_min_score,
+                        const sw_hit* d_hits, const int64_t* d_nhits, int64_t top, const sw_alignment* d_aln, const char* d_ops, int64_t ops_cap, char* d_cols,
+                        sw_msa_row* d_rows, char* d_a3m, int64_t a3m_cap, int64_t* d_a3m_bytes, void* stream_) {
+    const char* who = "sw_db_msa_from_hits";
+    if (int rc = check_db_call(who, c, db, qoffsets != nullptr)) return rc;
+    if (int rc = swh::check_msa(who, qoffsets, nqueries, top, d_hits, d_aln, d_ops, ops_cap, d_cols, d_rows, d_a3m, a3m_cap, d_a3m_bytes)) return rc;
+    c->last_msa_hits_launches = 0;   // (a call that launches no kernel reports none)
+    if (nqueries == 0) return SW_OK;
+    hipStream_t stream = (hipStream_t)stream_;
+    HIP_TRY(hipSetDevice(c->device));
+    swp::MsaHitsJob mj;
+    mj.nqueries = nqueries; mj.top = top; mj.num_cus = c->num_cus; mj.rows = d_rows != nullptr;
+    const swp::MsaHitsPlan plan = swp::plan_msa_hits(mj);
+    DevOrder order(c, stream, false);
+    if (order.rc) return order.rc;
+    if (int rc = c->d_msasum.grow((size_t)plan.scan_chunks, stream)) return rc;
+    // the call's table: the offsets
+    const size_t need = (size_t)(nqueries + 1) * sizeof(int64_t);
+    int turn = 0;
+    if (int rc = pssm_table_turn(who, c, stream, need, &turn)) return rc;
+    memcpy(c->h_phtab[turn], qoffsets, need);
+    HIP_TRY(hipMemcpyAsync(c->d_phtab, c->h_phtab[turn], need, hipMemcpyHostToDevice, stream));
+    HIP_TRY(hipEventRecord(c->phtab_ev[turn], stream));
+    swk::MsaHitsParams kp;
+    memset(&kp, 0, sizeof kp);
+    kp.queries = (const unsigned char*)d_queries; kp.qoffs = (const int64_t*)c->d_phtab.p;
+    kp.db = (const unsigned char*)db->d_db; kp.offsets = db->d_offsets; kp.ntargets = db->ntargets;
+    kp.hits = d_hits; kp.nhits = d_nhits; kp.top = top;
+    kp.aln = d_aln; kp.ops = d_ops; kp.ops_cap = ops_cap;
+    kp.cols = (unsigned char*)d_cols; kp.rows = d_rows; kp.a3m = (unsigned char*)d_a3m; kp.a3m_cap = a3m_cap; kp.a3m_bytes = d_a3m_bytes;
+    kp.chunk_off = (int64_t*)c->d_msasum.p;
+    kp.nqueries = nqueries; kp.entries = plan.entries; kp.chunks = plan.scan_chunks;
+    kp.slices_per_query = plan.slices_per_query; kp.slice_entries = plan.slice_entries; kp.col0 = qoffsets[0];
+    kp.include_min = include_min_score;
+    hipLaunchKernelGGL(swk::sw_msa_cols, dim3((unsigned)plan.cols_grid), dim3(256), 0, stream, kp);
+    HIP_TRY(hipGetLastError());
+    if (d_rows) {
+        hipLaunchKernelGGL(swk::sw_msa_scan_chunks, dim3((unsigned)plan.scan_grid), dim3(256), 0, stream, kp);
+        HIP_TRY(hipGetLastError());
+        hipLaunchKernelGGL(swk::sw_msa_scan_top, dim3(1), dim3(256), 0, stream, kp);
+        HIP_TRY(hipGetLastError());
+        hipLaunchKernelGGL(swk::sw_msa_rows, dim3((unsigned)plan.rows_grid), dim3(256), 0, stream, kp);
+        HIP_TRY(hipGetLastError());
+    }
+    c->last_msa_hits_launches = plan.launches;
+    return SW_OK;
+}
+
 // The scores of a device pair list (csrc/sw_search_pairs.hip).  Per call the host checks and plans the QUERIES (O(nqueries)) against the
 // handle's longest target; the pairs and the targets' offsets are read on the device only.  One memset zeroes the call's results up
 // front -- the pairs that never become an item keep it, the binning writes no result --, then per group one profile launch and per

@@ -219,6 +219,30 @@ struct PssmWeightsParams {
 __global__ void sw_pssm_weights_tile(PssmWeightsParams p);
 __global__ void sw_pssm_weights_finish(PssmWeightsParams p);
 
+// sw_msa_hits.hip: the query-anchored alignment of a hit table's entries (sw_db_msa_from_hits), as swp::plan_msa_hits cuts it.
+// sw_msa_cols: one workgroup per (query, slice of entries), the column rows and every field of a sw_msa_row but `off`;
+// sw_msa_scan_chunks / sw_msa_scan_top: the exclusive scan of `len` in chunks of swp::kMsaScanChunk entries and over the chunks' sums;
+// sw_msa_rows: one wave per entry, its final `off` and its A3M row.
+struct MsaHitsParams {
+    const unsigned char* queries;                // the query letters at qoffs[q] + j, or NULL (PSSM queries): nident = 0
+    const int64_t* qoffs;                        // device copy of the caller's nqueries + 1 offsets
+    const unsigned char* db; const int64_t* offsets; int64_t ntargets;   // the handle's bytes and its ntargets + 1 offsets on the device
+    const sw_hit* hits; const int64_t* nhits; int64_t top;               // the caller's tables, as the alignment calls take and leave them
+    const sw_alignment* aln; const char* ops; int64_t ops_cap;
+    unsigned char* cols;                         // (qoffsets[nqueries] - qoffsets[0]) x top bytes, or NULL
+    sw_msa_row* rows;                            // nqueries x top, or NULL
+    unsigned char* a3m; int64_t a3m_cap;         // a3m_cap bytes, or NULL
+    int64_t* a3m_bytes;                          // the true total (with rows)
+    int64_t* chunk_off;                          // workspace: per scan chunk its sum, then its exclusive offset
+    int64_t nqueries, entries, chunks;           // entries = nqueries x top; chunks of swp::kMsaScanChunk entries
+    int64_t slices_per_query, slice_entries, col0;   // col0 = qoffsets[0]: cols start at the first query's first column
+    int64_t include_min;
+};
+__global__ void sw_msa_cols(MsaHitsParams p);
+__global__ void sw_msa_scan_chunks(MsaHitsParams p);
+__global__ void sw_msa_scan_top(MsaHitsParams p);
+__global__ void sw_msa_rows(MsaHitsParams p);
+
 // sw_search_pairs.hip: the scores of a device list of (query, target) pairs (sw_db_search_affine_pairs).  Per (chunk of the list, group
 // of queries) two binning launches turn the usable pairs into work items, one list per class, heaviest bucket first
 // (swp::plan_search_pairs); one launch of sw_search_affine_pairs_wave<C> per class scores them.

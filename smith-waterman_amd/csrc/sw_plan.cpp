@@ -870,6 +870,29 @@ PssmWeightsPlan plan_pssm_weights(const PssmWeightsJob& j) {
     return p;
 }
 
+MsaHitsPlan plan_msa_hits(const MsaHitsJob& j) {
+    MsaHitsPlan p;
+    if (j.nqueries < 1) return p;
+    const int64_t top = std::clamp<int64_t>(j.top, 1, 4096);
+    // (nqueries x top stays inside 63 bits for every nqueries a caller's memory could hold offsets for)
+    p.entries = j.nqueries * top;
+    const int64_t wgs = kMsaHitsWgsPerCu * std::max(1, j.num_cus);
+    const int64_t share = (p.entries + wgs - 1) / wgs;               // entries per workgroup at kMsaHitsWgsPerCu per CU
+    p.slice_entries = std::min((share + 3) / 4 * 4, (top + 3) / 4 * 4);
+    p.slices_per_query = (top + p.slice_entries - 1) / p.slice_entries;
+    p.cols_grid = std::min(j.nqueries * p.slices_per_query, kPssmHitsGridMax);
+    p.launches = 1;
+    if (!j.rows) return p;
+    p.scan_chunks = (p.entries + kMsaScanChunk - 1) / kMsaScanChunk;
+    p.scan_grid = std::min(p.scan_chunks, kPssmHitsGridMax);
+    p.top_rounds = (p.scan_chunks + kMsaScanChunk - 1) / kMsaScanChunk;
+    p.scan_levels = p.scan_chunks > 1 ? 2 : 1;
+    p.rows_grid = std::min((p.entries + 3) / 4, kPssmHitsGridMax);
+    p.sums_bytes = 8 * p.scan_chunks;
+    p.launches = 4;
+    return p;
+}
+
 void align_schedule(const int64_t* offsets, const int64_t* hits, int64_t nhits, swk::SearchItem* items) {
     std::vector<int64_t> order((size_t)nhits);
     for (int64_t h = 0; h < nhits; ++h) order[(size_t)h] = h;

@@ -581,6 +581,38 @@ struct PssmWeightsPlan {
 
 PssmWeightsPlan plan_pssm_weights(const PssmWeightsJob& job);
 
+// ---- the query-anchored alignment of aligned hits (sw_db_msa_from_hits; sw_msa_hits.hip).  Up to four launches of 256 threads.
+// Launch A (column rows and the rows' counts): one workgroup per (query, slice of slice_entries entries r), its four waves taking the
+// slice's entries round robin.  A slice is the call's nqueries x top entries over kMsaHitsWgsPerCu workgroups per CU, in whole rounds of
+// the four waves, at least one round and at most the rounds `top` takes; the slices of a query cover 0 .. top - 1 exactly once.
+// Grid: queries x slices, walked in strides of at most kPssmHitsGridMax workgroups.
+// Launch B (with rows only; the exclusive scan of the rows' lengths), two levels: scan_chunks chunks of kMsaScanChunk entries, one
+// workgroup each (walked in strides of at most kPssmHitsGridMax), leave their sums in the workspace (8 bytes per chunk); ONE workgroup
+// scans those sums kMsaScanChunk at a time in top_rounds rounds.  scan_levels: 1 where one chunk holds every entry (the second level
+// then only carries the total out), else 2.
+// Launch C (with rows only): one wave per entry, four to a workgroup, walked in strides of at most kPssmHitsGridMax workgroups.
+constexpr int64_t kMsaScanChunk = 256;
+constexpr int64_t kMsaHitsWgsPerCu = 8;
+
+struct MsaHitsJob {
+    int64_t nqueries = 0, top = 1;           // top: 1..SW_TOP_MAX
+    int num_cus = 256;
+    bool rows = true;                        // the A3M side is asked for (d_rows): launches B and C
+};
+
+struct MsaHitsPlan {
+    int64_t entries = 0;                     // nqueries x top
+    int64_t slice_entries = 0, slices_per_query = 0, cols_grid = 0;   // launch A (grid 0: no query)
+    int64_t scan_chunks = 0, scan_grid = 0;  // launch B, first level (0: no rows)
+    int64_t top_rounds = 0;                  // ... second level: rounds of its one workgroup
+    int scan_levels = 0;
+    int64_t rows_grid = 0;                   // launch C
+    int64_t sums_bytes = 0;                  // the workspace: one int64 per chunk
+    int launches = 0;                        // kernel launches of the call ("last_msa_hits_launches")
+};
+
+MsaHitsPlan plan_msa_hits(const MsaHitsJob& job);
+
 // ---- alignment of chosen hits under affine scoring (sw_align_affine_device): sw_align_affine_wave<C> for C = 4, 8, 16, its index in
 // kAlignAffine (sw_api_search.hip, which checks its order against it at compile time)
 constexpr int kAlignAffineKernels = 3;

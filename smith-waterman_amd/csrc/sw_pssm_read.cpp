@@ -371,3 +371,137 @@ int sw_pssm_hit_weights_host(const int64_t* qoffsets, int64_t nqueries, const ch
 }
 
 }  // extern "C"
+
+// ---- the query-anchored alignment of aligned hits (sw_msa_from_hits_host, sw_write_a3m; include/swhip.h states the rule)
+namespace swh {
+__attribute__((visibility("hidden"))) int check_msa(const char* who, const int64_t* qoffsets, int64_t nqueries, int64_t top, const void* hits, const void* aln,
+                                                    const void* ops, int64_t ops_cap, const void* cols, const void* rows, const void* a3m, int64_t a3m_cap,
+                                                    const void* a3m_bytes);
+
+// What sw_db_msa_from_hits and sw_msa_from_hits_host check beyond their pointers and the targets: the query offsets (the rule of every
+// many-query call), the tables and the outputs.
+int check_msa(const char* who, const int64_t* qoffsets, int64_t nqueries, int64_t top, const void* hits, const void* aln, const void* ops, int64_t ops_cap,
+              const void* cols, const void* rows, const void* a3m, int64_t a3m_cap, const void* a3m_bytes) {
+    if (!qoffsets) { set_err("%s: NULL query offsets", who); return SW_EINVAL; }
+    if (nqueries < 0) { set_err("%s: negative query count", who); return SW_EINVAL; }
+    if (qoffsets[0] < 0) { set_err("%s: qoffsets[0] = %lld is negative", who, (long long)qoffsets[0]); return SW_EINVAL; }
+    for (int64_t q = 0; q < nqueries; ++q) {
+        const int64_t len = qoffsets[q + 1] - qoffsets[q];
+        if (len < 1 || len > kMaxDim) { set_err("%s: query %lld has length %lld, out of range 1..%lld", who, (long long)q, (long long)len, (long long)kMaxDim); return SW_EINVAL; }
+    }
+    if (top < 1 || top > SW_TOP_MAX) { set_err("%s: top = %lld is out of range 1..%d", who, (long long)top, SW_TOP_MAX); return SW_EINVAL; }
+    if (!hits || !aln || !ops) { set_err("%s: NULL hit table, alignment array or ops buffer", who); return SW_EINVAL; }
+    if (ops_cap < 1) { set_err("%s: ops_cap = %lld is below 1", who, (long long)ops_cap); return SW_EINVAL; }
+    if (!cols && !rows) { set_err("%s: no output: the column rows and the row table are both NULL", who); return SW_EINVAL; }
+    if (!rows && (a3m || a3m_bytes)) { set_err("%s: A3M bytes or their total without the row table", who); return SW_EINVAL; }
+    if (a3m && !a3m_bytes) { set_err("%s: A3M bytes without a place for their total", who); return SW_EINVAL; }
+    if (a3m_cap < 0) { set_err("%s: a3m_cap = %lld is negative", who, (long long)a3m_cap); return SW_EINVAL; }
+    return SW_OK;
+}
+}  // namespace swh
+
+extern "C" {
+
+// The CPU leg of sw_db_msa_from_hits: entry by entry in (q, r) order, its ops walked one by one.  Everything is checked before the
+// first byte is written.
+int sw_msa_from_hits_host(const char* queries, const int64_t* qoffsets, int64_t nqueries, const char* db, const int64_t* offsets, int64_t ntargets,
+                          int64_t include_min_score, const sw_hit* hits, const int64_t* nhits, int64_t top, const sw_alignment* aln, const char* ops,
+                          int64_t ops_cap, char* cols, sw_msa_row* rows, char* a3m, int64_t a3m_cap, int64_t* a3m_bytes) {
+    const char* who = "sw_msa_from_hits_host";
+    if (!db || !offsets) { swh::set_err("%s: NULL pointer", who); return SW_EINVAL; }
+    if (ntargets < 0 || offsets[0] < 0) { swh::set_err("%s: negative target count or offsets[0]", who); return SW_EINVAL; }
+    for (int64_t k = 0; k < ntargets; ++k) {
+        const int64_t len = offsets[k + 1] - offsets[k];
+        if (len < 0 || len > kMaxDim) { swh::set_err("%s: target %lld has length %lld, out of range 0..%lld", who, (long long)k, (long long)len, (long long)kMaxDim); return SW_EINVAL; }
+    }
+    if (int rc = swh::check_msa(who, qoffsets, nqueries, top, hits, aln, ops, ops_cap, cols, rows, a3m, a3m_cap, a3m_bytes)) return rc;
+    std::string row;   // the A3M row of the entry at hand
+    int64_t off = 0;
+    for (int64_t q = 0; q < nqueries; ++q) {
+        const int64_t g0 = qoffsets[q], qlen = qoffsets[q + 1] - g0;
+        const int64_t nh = nhits ? std::clamp<int64_t>(nhits[q], 0, top) : top;
+        for (int64_t r = 0; r < top; ++r) {
+            const int64_t e = q * top + r;
+            char* crow = cols ? cols + (g0 - qoffsets[0]) * top + r * qlen : nullptr;
+            if (crow) std::fill(crow, crow + qlen, '-');
+            sw_msa_row out{off, 0, 0, 0, 0};
+            const uint64_t t = (uint64_t)hits[e].target;
+            bool used = r < nh && t < (uint64_t)ntargets;
+            if (used) {
+                const sw_alignment& a = aln[e];
+                used = a.max_score >= include_min_score && a.nops > 0 && a.nops <= ops_cap;
+                const int64_t len = used ? offsets[t + 1] - offsets[t] : 0;
+                used = used && (uint64_t)a.q_begin <= (uint64_t)qlen && (uint64_t)a.t_begin <= (uint64_t)len;
+                if (used) {
+                    const unsigned char* tb = (const unsigned char*)db + offsets[t];
+                    const char* op = ops + e * ops_cap;
+                    row.assign((size_t)a.q_begin, '-');
+                    int64_t j = a.q_begin, i = a.t_begin;
+                    for (int64_t o = 0; o < a.nops; ++o) {
+                        if (op[o] == 'M') {
+                            const bool pair = j < qlen && i < len;
+                            if (pair) {
+                                if (crow) crow[j] = (char)tb[i];
+                                ++out.nmatch;
+                                out.nident += queries && (unsigned char)queries[g0 + j] == tb[i];
+                            }
+                            if (j < qlen) row += pair ? (char)tb[i] : '-';
+                            ++j; ++i;
+                        } else if (op[o] == 'I') {
+                            if (j < qlen) row += '-';
+                            ++j;
+                        } else if (op[o] == 'D') {
+                            if (i < len && j <= qlen) {
+                                const unsigned char c = tb[i];
+                                row += (char)(c >= 'A' && c <= 'Z' ? c + 32 : c);
+                                ++out.ninsert;
+                            }
+                            ++i;
+                        }
+                    }
+                    row.append((size_t)(qlen + out.ninsert) - row.size(), '-');   // the columns behind the walk's end
+                    out.len = (int32_t)(qlen + out.ninsert);
+                    if (a3m && off + out.len <= a3m_cap) std::copy(row.begin(), row.end(), a3m + off);
+                }
+            }
+            if (rows) rows[e] = out;
+            off += out.len;
+        }
+    }
+    if (a3m_bytes) *a3m_bytes = off;
+    return SW_OK;
+}
+
+// One query's A3M file (include/swhip.h states the layout); the text is built whole and written once.
+int sw_write_a3m(const char* path, const char* qname, const char* query, int64_t qlen, const char* const* tnames, int64_t ntargets, const sw_hit* hits,
+                 const sw_alignment* aln, const sw_msa_row* rows, int64_t top, const char* a3m, int64_t a3m_cap) {
+    if (!path || !qname || !hits || !aln || !rows || !a3m || top < 1 || qlen < 1) { swh::set_err("sw_write_a3m: bad argument"); return SW_EINVAL; }
+    std::string text;
+    if (query) {
+        text += '>'; text += qname; text += '\n';
+        text.append(query, (size_t)qlen);
+        text += '\n';
+    }
+    for (int64_t r = 0; r < top; ++r) {
+        const sw_msa_row& w = rows[r];
+        if (w.len <= 0 || w.off < 0 || w.off + w.len > a3m_cap) continue;
+        const int64_t t = hits[r].target;
+        if (t < 0 || t >= ntargets) { swh::set_err("sw_write_a3m: entry %lld names target %lld of %lld", (long long)r, (long long)t, (long long)ntargets); return SW_EINVAL; }
+        const sw_alignment& a = aln[r];
+        text += '>';
+        text += tnames ? std::string(tnames[t]) : std::to_string(t);
+        char buf[200];
+        snprintf(buf, sizeof buf, " score=%lld q=%lld-%lld t=%lld-%lld ident=%d/%d\n", (long long)a.max_score, (long long)a.q_begin, (long long)a.q_end,
+                 (long long)a.t_begin, (long long)a.t_end, w.nident, w.nmatch);
+        text += buf;
+        text.append(a3m + w.off, (size_t)w.len);
+        text += '\n';
+    }
+    FILE* f = fopen(path, "wb");
+    if (!f) { swh::set_err("sw_write_a3m: cannot open %s for writing", path); return SW_EINVAL; }
+    const bool ok = fwrite(text.data(), 1, text.size(), f) == text.size();
+    if (fclose(f) != 0 || !ok) { swh::set_err("sw_write_a3m: write error on %s", path); return SW_EINVAL; }
+    return SW_OK;
+}
+
+}  // extern "C"

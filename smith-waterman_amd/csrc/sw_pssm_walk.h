@@ -1,6 +1,7 @@
 // sw_pssm_walk.h -- what kernels that read a hit table's alignments share (gfx950): the guards that make entry (q, r) a USED ENTRY and
 // THE WALK of its ops, as include/swhip.h states them for sw_db_pssm_from_hits.  One wave per entry; everything is __forceinline__ inside
-// an unnamed namespace, as in sw_wave.h.  Both passes of sw_pssm_weights.hip go through it.  sw_pssm_from_hits (sw_pssm_hits.hip) keeps
+// an unnamed namespace, as in sw_wave.h.  Both passes of sw_pssm_weights.hip go through it, and the two walking launches of
+// sw_msa_hits.hip through the guards and sw_msa_walk, the walk over all columns with the inserts counted.  sw_pssm_from_hits (sw_pssm_hits.hip) keeps
 // its own text of the same guards and walk: moved onto this header its assembly differs from what it was, and that kernel
 // was to stay byte for byte.
 #pragma once
@@ -45,6 +46,32 @@ __device__ __forceinline__ void sw_pssm_walk(const unsigned char* ops, const sw_
         if (m && j >= c0 && j < c1 && i < len) at_pair(j, i);
         jb += __popcll(bq); ib += __popcll(bt);
     }
+}
+
+// The same walk over ALL columns of the query, with the running count of VALID INSERTS -- a 'D' op met with i < len and j <= qlen --
+// that the rows of sw_db_msa_from_hits need (sw_msa_hits.hip): a third ballot, whose set bits below a lane are the inserts the walk has
+// seen before the lane's op.  at_op(pair, col, ins, j, i, k) runs in EVERY lane of every chunk (it may ballot): pair: an 'M' that pairs
+// column j with target byte i; col: an 'M' or 'I' that consumes column j < qlen (pair implies col); ins: a valid insert of target
+// byte i before column j; k: the valid inserts before this op.  (j, i, k stay below 2^21 + 64: q_begin <= qlen, t_begin <= len, both at
+// most 2^20 - 1, and the walk ends with the first chunk that starts behind the query or the target -- no later op pairs, inserts, or
+// sees another insert.)  Leaves j_end, the first column the chunks walked did not reach (<= qlen), and the number of valid inserts.
+template <typename F>
+__device__ __forceinline__ void sw_msa_walk(const unsigned char* ops, const sw_alignment& a, int qlen, int len, int lane, int& j_end, int& inserts, F&& at_op) {
+    int jb = (int)a.q_begin, ib = (int)a.t_begin, kb = 0;            // wave-uniform bases of the chunk
+    for (int64_t o = 0; o < a.nops && jb <= qlen && ib < len; o += 64) {
+        const int op = o + lane < a.nops ? (int)ops[o + lane] : 0;
+        const bool m = op == 'M';
+        const uint64_t bq = __ballot(m || op == 'I'), bt = __ballot(m || op == 'D');
+        const int j = jb + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(bq >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)bq, 0u));
+        const int i = ib + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(bt >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)bt, 0u));
+        const bool ins = op == 'D' && i < len && j <= qlen;
+        const uint64_t bd = __ballot(ins);
+        const int k = kb + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(bd >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)bd, 0u));
+        const bool col = (m || op == 'I') && j < qlen;
+        at_op(m && col && i < len, col, ins, j, i, k);
+        jb += __popcll(bq); ib += __popcll(bt); kb += __popcll(bd);
+    }
+    j_end = min(jb, qlen); inserts = kb;
 }
 
 }  // namespace
