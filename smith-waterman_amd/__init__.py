@@ -531,6 +531,19 @@ def _ops_table(ops, nq: int, top: int):
     return o, cap
 
 
+def _pack_hit_tables(hits, nhits, aln, ops, nq: int):
+    """The host tables of a call that reads a hit table's alignments, as the C-ABI takes them -> (hits, nhits, top, aln, ops, ops_cap):
+    hits and nhits of _hit_table, aln (nq * top, 7) int64 -- one row of zeros where there is no entry: never an empty buffer --, ops and
+    ops_cap of _ops_table."""
+    hits, nhits = _hit_table(hits, nhits, nq)
+    top = hits.shape[1]
+    a = np.ascontiguousarray(aln, np.int64).reshape(-1, 7)
+    if len(a) != nq * top:
+        raise ValueError(f"aln must be ({nq}, {top}, 7) int64")
+    o, cap = _ops_table(ops, nq, top)
+    return hits, nhits, top, a if len(a) else np.zeros((1, 7), np.int64), o, cap
+
+
 def pssm_from_hits_host(prior, targets, scoring, update, hits, nhits, aln, ops, weights=None, want_counts: bool = False):
     """sw_pssm_from_hits_host: the next iteration's PSSM from aligned hits in plain C++ on the host (no GPU).  Arguments and results as
     Database.pssm_from_hits."""
@@ -540,12 +553,7 @@ def pssm_from_hits_host(prior, targets, scoring, update, hits, nhits, aln, ops, 
     m, qoffs = _pack_pssm(prior, nl)
     packed, offs = _pack_targets(targets)
     nq = len(qoffs) - 1
-    hits, nhits = _hit_table(hits, nhits, nq)
-    top = hits.shape[1]
-    a = np.ascontiguousarray(aln, np.int64).reshape(-1, 7)
-    if len(a) != nq * top:
-        raise ValueError(f"aln must be ({nq}, {top}, 7) int64")
-    o, cap = _ops_table(ops, nq, top)
+    hits, nhits, top, aa, o, cap = _pack_hit_tables(hits, nhits, aln, ops, nq)
     w = None
     if weights is not None:
         w = np.ascontiguousarray(weights, np.int32).reshape(-1)
@@ -556,7 +564,6 @@ def pssm_from_hits_host(prior, targets, scoring, update, hits, nhits, aln, ops, 
     ncols = int(qoffs[-1] - qoffs[0])
     out = mm.copy()
     counts = np.zeros((max(1, ncols), nl), np.int32)
-    aa = a if len(a) else np.zeros((1, 7), np.int64)
     _check(lib().sw_pssm_from_hits_host(mm.ctypes.data, qoffs.ctypes.data, nq, db.ctypes.data, offs.ctypes.data, len(offs) - 1, ctypes.byref(sc),
                                         ctypes.byref(up), hits.ctypes.data if hits.size else aa.ctypes.data, nhits.ctypes.data if nhits is not None else None,
                                         top, aa.ctypes.data, o.ctypes.data, cap, w.ctypes.data if w is not None and len(w) else None, out.ctypes.data,
@@ -586,14 +593,8 @@ def pssm_hit_weights_host(qoffsets_or_pssm, targets, scoring, weighting, hits, n
     qoffs = _query_offsets(qoffsets_or_pssm, max(1, sc.nletters))
     packed, offs = _pack_targets(targets)
     nq = len(qoffs) - 1
-    hits, nhits = _hit_table(hits, nhits, nq)
-    top = hits.shape[1]
-    a = np.ascontiguousarray(aln, np.int64).reshape(-1, 7)
-    if len(a) != nq * top:
-        raise ValueError(f"aln must be ({nq}, {top}, 7) int64")
-    o, cap = _ops_table(ops, nq, top)
+    hits, nhits, top, aa, o, cap = _pack_hit_tables(hits, nhits, aln, ops, nq)
     db = packed if len(packed) else np.zeros(1, np.uint8)
-    aa = a if len(a) else np.zeros((1, 7), np.int64)
     w = np.zeros(max(1, nq * top), np.int32)
     _check(lib().sw_pssm_hit_weights_host(qoffs.ctypes.data, nq, db.ctypes.data, offs.ctypes.data, len(offs) - 1, ctypes.byref(sc), ctypes.byref(wt),
                                           hits.ctypes.data if hits.size else aa.ctypes.data, nhits.ctypes.data if nhits is not None else None, top,
@@ -615,14 +616,8 @@ def msa_from_hits_host(queries, targets, include_min_score, hits, nhits, aln, op
     qpacked, qoffs = _msa_queries(queries)
     packed, offs = _pack_targets(targets)
     nq = len(qoffs) - 1
-    hits, nhits = _hit_table(hits, nhits, nq)
-    top = hits.shape[1]
-    a = np.ascontiguousarray(aln, np.int64).reshape(-1, 7)
-    if len(a) != nq * top:
-        raise ValueError(f"aln must be ({nq}, {top}, 7) int64")
-    o, cap = _ops_table(ops, nq, top)
+    hits, nhits, top, aa, o, cap = _pack_hit_tables(hits, nhits, aln, ops, nq)
     db = packed if len(packed) else np.zeros(1, np.uint8)
-    aa = a if len(a) else np.zeros((1, 7), np.int64)
     ncols = int(qoffs[-1] - qoffs[0])
     cols = np.zeros(max(1, ncols * top), np.uint8)
     rows = np.zeros(max(1, nq * top), MSA_ROW)
@@ -1122,6 +1117,41 @@ class Database:
         lt, sc = _pssm_scoring(scoring)
         return self._align_hits_call(lib().sw_db_align_pssm_hits, d_pssm, qoffsets, sc, hits, nhits, ops_cap, out, top, checkpoint)
 
+    def _upload_hit_tables(self, hits, nhits, aln, ops, nq: int):
+        """The host tables of pssm_from_hits, pssm_hit_weights and msa_from_hits (_pack_hit_tables) as device tensors -> (top, ops_cap,
+        d_hits, d_nhits, d_aln, d_ops)."""
+        t, dev = self.engine.torch, f"cuda:{self.engine.device}"
+        hits, nhits, top, a, o, cap = _pack_hit_tables(hits, nhits, aln, ops, nq)
+        d_hits = t.from_numpy(hits.reshape(-1).copy() if hits.size else np.zeros(3, np.int64)).to(dev)
+        d_nhits = t.from_numpy(nhits.copy()).to(dev) if nhits is not None and len(nhits) else None
+        return top, cap, d_hits, d_nhits, t.from_numpy(a.reshape(-1).copy()).to(dev), t.from_numpy(o.reshape(-1).copy()).to(dev)
+
+    def _hit_table_args(self, qoffsets, hits, nhits, top, aln=None, ops=None, ops_cap=0):
+        """What every call on a device hit table checks first -> (qoffs, nq, top, n = nq * top): the int64 offsets; `top`, from the
+        table's shape where it is not given; hits and nhits; with `aln`, the alignments and ops of a call that READS them (the
+        alignment calls, which write them, check their `out` themselves)."""
+        t = self.engine.torch
+        qoffs = np.ascontiguousarray(qoffsets, np.int64).reshape(-1)
+        if len(qoffs) == 0:
+            qoffs = np.zeros(1, np.int64)
+        nq = len(qoffs) - 1
+        if top is None:
+            if hits.dim() != 3:
+                raise ValueError("hits must be (nqueries, top, 3), or `top` given")
+            top = hits.shape[1]
+        top = int(top)
+        n = nq * max(0, top)
+        if hits.dtype != t.int64 or not hits.is_contiguous() or hits.numel() < n * 3:
+            raise ValueError(f"hits must be a contiguous int64 tensor of at least {nq} x {top} x 3 elements")
+        if nhits is not None and (nhits.dtype != t.int64 or not nhits.is_contiguous() or nhits.numel() < nq):
+            raise ValueError(f"nhits must be a contiguous int64 tensor of at least {nq} elements")
+        if aln is not None:
+            if aln.dtype != t.int64 or not aln.is_contiguous() or aln.numel() < n * 7:
+                raise ValueError(f"aln must be a contiguous int64 tensor of at least {n * 7} elements")
+            if ops is not None and (ops.dtype != t.uint8 or not ops.is_contiguous() or ops.numel() < n * max(0, int(ops_cap))):
+                raise ValueError(f"ops must be a contiguous uint8 tensor of at least {n * max(0, int(ops_cap))} elements")
+        return qoffs, nq, top, n
+
     def pssm_from_hits(self, prior, scoring, update, hits, nhits, aln, ops, weights=None, want_counts: bool = False):
         """The next iteration's PSSM from aligned hits (sw_db_pssm_from_hits).  prior and scoring as for search_pssm; update =
         (submat, prior_weight, include_min_score); hits, nhits as search_pssm_top returns them, aln and ops as align_pssm_hits returns
@@ -1135,17 +1165,8 @@ class Database:
         nl = max(1, len(_as_seq(scoring[0])))
         m, qoffs = _pack_pssm(prior, nl)
         nq = len(qoffs) - 1
-        hits, nhits = _hit_table(hits, nhits, nq)
-        top = hits.shape[1]
-        a = np.ascontiguousarray(aln, np.int64).reshape(-1, 7)
-        if len(a) != nq * top:
-            raise ValueError(f"aln must be ({nq}, {top}, 7) int64")
-        o, cap = _ops_table(ops, nq, top)
         d_m = t.from_numpy(m.reshape(-1).copy() if m.size else np.zeros(1, np.int8)).to(dev)
-        d_hits = t.from_numpy(hits.reshape(-1).copy() if hits.size else np.zeros(3, np.int64)).to(dev)
-        d_nhits = t.from_numpy(nhits.copy()).to(dev) if nhits is not None and len(nhits) else None
-        d_aln = t.from_numpy(a.reshape(-1).copy() if a.size else np.zeros(7, np.int64)).to(dev)
-        d_ops = t.from_numpy(o.reshape(-1).copy()).to(dev)
+        top, cap, d_hits, d_nhits, d_aln, d_ops = self._upload_hit_tables(hits, nhits, aln, ops, nq)
         d_w = t.from_numpy(np.ascontiguousarray(weights, np.int32).reshape(-1).copy()).to(dev) if weights is not None and nq * top else None
         counts = t.zeros(max(1, int(qoffs[-1] - qoffs[0]) * nl), dtype=t.int32, device=dev) if want_counts else None
         out = self.pssm_from_hits_device(d_m, qoffs, scoring, update, d_hits, d_nhits, d_aln, d_ops, cap, weights=d_w, top=top, counts=counts)
@@ -1165,26 +1186,10 @@ class Database:
         t = eng.torch
         lt, sc = _pssm_scoring(scoring)
         sub, up = _pssm_update(update)
-        qoffs = np.ascontiguousarray(qoffsets, np.int64).reshape(-1)
-        if len(qoffs) == 0:
-            qoffs = np.zeros(1, np.int64)
-        nq, nl = len(qoffs) - 1, max(1, sc.nletters)
-        if top is None:
-            if hits.dim() != 3:
-                raise ValueError("hits must be (nqueries, top, 3), or `top` given")
-            top = hits.shape[1]
-        top = int(top)
-        n = nq * max(0, top)
+        qoffs, nq, top, n = self._hit_table_args(qoffsets, hits, nhits, top, aln, ops, ops_cap)
+        nl = max(1, sc.nletters)
         if d_prior.dtype != t.int8 or not d_prior.is_contiguous() or d_prior.numel() < int(qoffs[-1]) * nl:
             raise ValueError(f"d_prior must be a contiguous int8 tensor of at least {int(qoffs[-1]) * nl} elements")
-        if hits.dtype != t.int64 or not hits.is_contiguous() or hits.numel() < n * 3:
-            raise ValueError(f"hits must be a contiguous int64 tensor of at least {nq} x {top} x 3 elements")
-        if nhits is not None and (nhits.dtype != t.int64 or not nhits.is_contiguous() or nhits.numel() < nq):
-            raise ValueError(f"nhits must be a contiguous int64 tensor of at least {nq} elements")
-        if aln.dtype != t.int64 or not aln.is_contiguous() or aln.numel() < n * 7:
-            raise ValueError(f"aln must be a contiguous int64 tensor of at least {n * 7} elements")
-        if ops is not None and (ops.dtype != t.uint8 or not ops.is_contiguous() or ops.numel() < n * max(0, int(ops_cap))):
-            raise ValueError(f"ops must be a contiguous uint8 tensor of at least {n * max(0, int(ops_cap))} elements")
         if weights is not None and (weights.dtype != t.int32 or not weights.is_contiguous() or weights.numel() < n):
             raise ValueError(f"weights must be a contiguous int32 tensor of at least {n} elements")
         if out is None:
@@ -1208,20 +1213,9 @@ class Database:
         PSSM as search_pssm takes it (only its offsets are used); hits, nhits, aln, ops as for pssm_from_hits.  Returns the (nqueries,
         top) int32 weights.  include/swhip.h states the rule."""
         eng = self.engine
-        t = eng.torch
-        dev = f"cuda:{eng.device}"
         qoffs = _query_offsets(qoffsets_or_pssm, max(1, len(_as_seq(scoring[0]))))
         nq = len(qoffs) - 1
-        hits, nhits = _hit_table(hits, nhits, nq)
-        top = hits.shape[1]
-        a = np.ascontiguousarray(aln, np.int64).reshape(-1, 7)
-        if len(a) != nq * top:
-            raise ValueError(f"aln must be ({nq}, {top}, 7) int64")
-        o, cap = _ops_table(ops, nq, top)
-        d_hits = t.from_numpy(hits.reshape(-1).copy() if hits.size else np.zeros(3, np.int64)).to(dev)
-        d_nhits = t.from_numpy(nhits.copy()).to(dev) if nhits is not None and len(nhits) else None
-        d_aln = t.from_numpy(a.reshape(-1).copy() if a.size else np.zeros(7, np.int64)).to(dev)
-        d_ops = t.from_numpy(o.reshape(-1).copy()).to(dev)
+        top, cap, d_hits, d_nhits, d_aln, d_ops = self._upload_hit_tables(hits, nhits, aln, ops, nq)
         out = self.pssm_hit_weights_device(qoffs, scoring, weighting, d_hits, d_nhits, d_aln, d_ops, cap, top=top)
         eng.synchronize()
         return out.cpu().numpy()[:nq * top].reshape(nq, top)
@@ -1235,24 +1229,7 @@ class Database:
         t = eng.torch
         lt, sc = _pssm_scoring(scoring)
         wt = _pssm_weighting(weighting)
-        qoffs = np.ascontiguousarray(qoffsets, np.int64).reshape(-1)
-        if len(qoffs) == 0:
-            qoffs = np.zeros(1, np.int64)
-        nq = len(qoffs) - 1
-        if top is None:
-            if hits.dim() != 3:
-                raise ValueError("hits must be (nqueries, top, 3), or `top` given")
-            top = hits.shape[1]
-        top = int(top)
-        n = nq * max(0, top)
-        if hits.dtype != t.int64 or not hits.is_contiguous() or hits.numel() < n * 3:
-            raise ValueError(f"hits must be a contiguous int64 tensor of at least {nq} x {top} x 3 elements")
-        if nhits is not None and (nhits.dtype != t.int64 or not nhits.is_contiguous() or nhits.numel() < nq):
-            raise ValueError(f"nhits must be a contiguous int64 tensor of at least {nq} elements")
-        if aln.dtype != t.int64 or not aln.is_contiguous() or aln.numel() < n * 7:
-            raise ValueError(f"aln must be a contiguous int64 tensor of at least {n * 7} elements")
-        if ops is not None and (ops.dtype != t.uint8 or not ops.is_contiguous() or ops.numel() < n * max(0, int(ops_cap))):
-            raise ValueError(f"ops must be a contiguous uint8 tensor of at least {n * max(0, int(ops_cap))} elements")
+        qoffs, nq, top, n = self._hit_table_args(qoffsets, hits, nhits, top, aln, ops, ops_cap)
         if out is None:
             out = t.empty((nq, max(0, top)) if n else (1,), dtype=t.int32, device=f"cuda:{eng.device}")
         if out.dtype != t.int32 or not out.is_contiguous() or out.numel() < n:
@@ -1273,17 +1250,8 @@ class Database:
         dev = f"cuda:{eng.device}"
         qpacked, qoffs = _msa_queries(queries)
         nq = len(qoffs) - 1
-        hits, nhits = _hit_table(hits, nhits, nq)
-        top = hits.shape[1]
-        a = np.ascontiguousarray(aln, np.int64).reshape(-1, 7)
-        if len(a) != nq * top:
-            raise ValueError(f"aln must be ({nq}, {top}, 7) int64")
-        o, cap = _ops_table(ops, nq, top)
         d_q = t.from_numpy(qpacked.copy()).to(dev) if qpacked is not None and len(qpacked) else None
-        d_hits = t.from_numpy(hits.reshape(-1).copy() if hits.size else np.zeros(3, np.int64)).to(dev)
-        d_nhits = t.from_numpy(nhits.copy()).to(dev) if nhits is not None and len(nhits) else None
-        d_aln = t.from_numpy(a.reshape(-1).copy() if a.size else np.zeros(7, np.int64)).to(dev)
-        d_ops = t.from_numpy(o.reshape(-1).copy()).to(dev)
+        top, cap, d_hits, d_nhits, d_aln, d_ops = self._upload_hit_tables(hits, nhits, aln, ops, nq)
         tables = (d_q, qoffs, include_min_score, d_hits, d_nhits, d_aln, d_ops, cap)
         _, rows, _, total = self.msa_from_hits_device(*tables, top=top, cols=False)
         eng.synchronize()
@@ -1307,26 +1275,9 @@ class Database:
         eng = self.engine
         t = eng.torch
         dev = f"cuda:{eng.device}"
-        qoffs = np.ascontiguousarray(qoffsets, np.int64).reshape(-1)
-        if len(qoffs) == 0:
-            qoffs = np.zeros(1, np.int64)
-        nq = len(qoffs) - 1
-        if top is None:
-            if hits.dim() != 3:
-                raise ValueError("hits must be (nqueries, top, 3), or `top` given")
-            top = hits.shape[1]
-        top = int(top)
-        n = nq * max(0, top)
+        qoffs, nq, top, n = self._hit_table_args(qoffsets, hits, nhits, top, aln, ops, ops_cap)
         if d_queries is not None and (d_queries.dtype != t.uint8 or not d_queries.is_contiguous() or d_queries.numel() < int(qoffs[-1])):
             raise ValueError(f"d_queries must be a contiguous uint8 tensor of at least {int(qoffs[-1])} elements")
-        if hits.dtype != t.int64 or not hits.is_contiguous() or hits.numel() < n * 3:
-            raise ValueError(f"hits must be a contiguous int64 tensor of at least {nq} x {top} x 3 elements")
-        if nhits is not None and (nhits.dtype != t.int64 or not nhits.is_contiguous() or nhits.numel() < nq):
-            raise ValueError(f"nhits must be a contiguous int64 tensor of at least {nq} elements")
-        if aln.dtype != t.int64 or not aln.is_contiguous() or aln.numel() < n * 7:
-            raise ValueError(f"aln must be a contiguous int64 tensor of at least {n * 7} elements")
-        if ops is not None and (ops.dtype != t.uint8 or not ops.is_contiguous() or ops.numel() < n * max(0, int(ops_cap))):
-            raise ValueError(f"ops must be a contiguous uint8 tensor of at least {n * max(0, int(ops_cap))} elements")
         ncols = int(qoffs[-1] - qoffs[0]) * max(0, top)
         if cols is None:
             cols = t.empty(max(1, ncols), dtype=t.uint8, device=dev)
@@ -1370,20 +1321,8 @@ class Database:
         """sw_db_align_affine_hits / sw_db_align_pssm_hits (see _search_call)."""
         eng = self.engine
         t = eng.torch
-        qoffs = np.ascontiguousarray(qoffsets, np.int64).reshape(-1)
-        if len(qoffs) == 0:
-            qoffs = np.zeros(1, np.int64)
-        nq = len(qoffs) - 1
-        if top is None:
-            if hits.dim() != 3:
-                raise ValueError("hits must be (nqueries, top, 3), or `top` given")
-            top = hits.shape[1]
-        top = int(top)
-        if hits.dtype != t.int64 or not hits.is_contiguous() or hits.numel() < nq * max(0, top) * 3:
-            raise ValueError(f"hits must be a contiguous int64 tensor of at least {nq} x {top} x 3 elements")
-        if nhits is not None and (nhits.dtype != t.int64 or not nhits.is_contiguous() or nhits.numel() < nq):
-            raise ValueError(f"nhits must be a contiguous int64 tensor of at least {nq} elements")
-        n, dev = nq * max(0, top), f"cuda:{eng.device}"
+        qoffs, nq, top, n = self._hit_table_args(qoffsets, hits, nhits, top)
+        dev = f"cuda:{eng.device}"
         aln, ops = out if out is not None else (t.zeros((max(1, n), 7), dtype=t.int64, device=dev),
                                                 t.zeros((max(1, n), ops_cap), dtype=t.uint8, device=dev) if ops_cap > 0 else None)
         if aln.dtype != t.int64 or not aln.is_contiguous() or aln.numel() < n * 7:

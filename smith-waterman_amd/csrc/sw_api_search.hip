@@ -871,6 +871,38 @@ static int pssm_table_turn(const char* who, sw_ctx* c, hipStream_t stream, size_
     return SW_OK;
 }
 
+// The small table of a call that reads a hit table's alignments, on the device: S (with `sub`; nletters x nletters, padded to 256
+// bytes), the 256-byte code table (with `code`), the nqueries + 1 offsets -- in this order, so every device address keeps its alignment.
+// Filled into the pinned copy of the call's turn, one upload, phtab_ev[turn] recorded behind it.
+struct HitsCallTable { const signed char* S; const unsigned char* code; const int64_t* qoffs; };
+static int upload_hits_call_table(const char* who, sw_ctx* c, hipStream_t stream, const sw_submat* sub, const char* letters, int nletters,
+                                  const unsigned char* code, const int64_t* qoffsets, int64_t nqueries, HitsCallTable* tab) {
+    const size_t s_bytes = sub ? ((size_t)nletters * nletters + 255) & ~(size_t)255 : 0, code_bytes = code ? 256 : 0;
+    const size_t off_bytes = (size_t)(nqueries + 1) * sizeof(int64_t), need = s_bytes + code_bytes + off_bytes;
+    int turn = 0;
+    if (int rc = pssm_table_turn(who, c, stream, need, &turn)) return rc;
+    unsigned char* h_tab = c->h_phtab[turn];
+    if (sub) swh::pssm_update_table(sub, letters, nletters, (int8_t*)h_tab);
+    if (code) memcpy(h_tab + s_bytes, code, 256);
+    memcpy(h_tab + s_bytes + code_bytes, qoffsets, off_bytes);
+    HIP_TRY(hipMemcpyAsync(c->d_phtab, h_tab, need, hipMemcpyHostToDevice, stream));
+    HIP_TRY(hipEventRecord(c->phtab_ev[turn], stream));
+    tab->S = (const signed char*)c->d_phtab.p; tab->code = c->d_phtab + s_bytes; tab->qoffs = (const int64_t*)(c->d_phtab + s_bytes + code_bytes);
+    return SW_OK;
+}
+
+// The tables those calls' kernels read: the handle's targets, the uploaded offsets and the caller's device tables.
+static swk::HitTables hit_tables(const sw_db* db, const int64_t* d_qoffs, int64_t nqueries, const sw_hit* d_hits, const int64_t* d_nhits, int64_t top,
+                                 const sw_alignment* d_aln, const char* d_ops, int64_t ops_cap, int64_t include_min) {
+    swk::HitTables t;
+    t.qoffs = d_qoffs; t.nqueries = nqueries;
+    t.db = (const unsigned char*)db->d_db; t.offsets = db->d_offsets; t.ntargets = db->ntargets;
+    t.hits = d_hits; t.nhits = d_nhits; t.top = top;
+    t.aln = d_aln; t.ops = d_ops; t.ops_cap = ops_cap;
+    t.include_min = include_min;
+    return t;
+}
+
 // The next iteration's PSSM from a device hit table, its alignments and their ops (csrc/sw_pssm_hits.hip).  The host checks the
 // arguments, cuts the tiles (swp::plan_pssm_hits) and uploads one small table through two pinned copies of its own, used in turn -- S
 // (nletters x nletters), the 256-byte code table, the nqueries + 1 offsets --; the hit table, the alignments, the ops, the weights and the targets'
@@ -894,26 +926,15 @@ int sw_db_pssm_from_hits(sw_ctx* c, const sw_db* db, const int8_t* d_prior, cons
     const swp::PssmHitsPlan plan = swp::plan_pssm_hits(pj);
     DevOrder order(c, stream, false);
     if (order.rc) return order.rc;
-    // the call's table: S, padded to 256 bytes, the code table, the offsets
     const int n = scoring->nletters;
-    const size_t s_bytes = ((size_t)n * n + 255) & ~(size_t)255, off_bytes = (size_t)(nqueries + 1) * sizeof(int64_t), need = s_bytes + 256 + off_bytes;
-    int turn = 0;
-    if (int rc = pssm_table_turn(who, c, stream, need, &turn)) return rc;
-    unsigned char* h_tab = c->h_phtab[turn];
-    swh::pssm_update_table(upd->sub, scoring->letters, n, (int8_t*)h_tab);
-    memcpy(h_tab + s_bytes, code, 256);
-    memcpy(h_tab + s_bytes + 256, qoffsets, off_bytes);
-    HIP_TRY(hipMemcpyAsync(c->d_phtab, h_tab, need, hipMemcpyHostToDevice, stream));
-    HIP_TRY(hipEventRecord(c->phtab_ev[turn], stream));
+    HitsCallTable tab;
+    if (int rc = upload_hits_call_table(who, c, stream, upd->sub, scoring->letters, n, code, qoffsets, nqueries, &tab)) return rc;
     swk::PssmHitsParams kp;
     memset(&kp, 0, sizeof kp);
+    kp.t = hit_tables(db, tab.qoffs, nqueries, d_hits, d_nhits, top, d_aln, d_ops, ops_cap, upd->include_min_score);
     kp.prior = (const signed char*)d_prior; kp.out = (signed char*)d_pssm_out; kp.counts = d_counts;
-    kp.S = (const signed char*)c->d_phtab.p; kp.code = c->d_phtab + s_bytes; kp.qoffs = (const int64_t*)(c->d_phtab + s_bytes + 256);
-    kp.db = (const unsigned char*)db->d_db; kp.offsets = db->d_offsets; kp.ntargets = db->ntargets;
-    kp.hits = d_hits; kp.nhits = d_nhits; kp.top = top;
-    kp.aln = d_aln; kp.ops = d_ops; kp.ops_cap = ops_cap; kp.weights = d_weights;
-    kp.nqueries = nqueries; kp.tiles_per_query = plan.tiles_per_query; kp.col0 = qoffsets[0];
-    kp.include_min = upd->include_min_score;
+    kp.S = tab.S; kp.code = tab.code; kp.weights = d_weights;
+    kp.tiles_per_query = plan.tiles_per_query; kp.col0 = qoffsets[0];
     kp.nletters = n; kp.stride = plan.stride; kp.tile_cols = plan.tile_cols; kp.smax = scoring->smax; kp.prior_weight = upd->prior_weight;
     hipLaunchKernelGGL(swk::sw_pssm_from_hits, dim3((unsigned)plan.grid), dim3(256), plan.lds_bytes, stream, kp);
     HIP_TRY(hipGetLastError());
@@ -946,25 +967,14 @@ int sw_db_pssm_hit_weights(sw_ctx* c, const sw_db* db, const int64_t* qoffsets, 
     DevOrder order(c, stream, false);
     if (order.rc) return order.rc;
     if (int rc = c->d_pwacc.grow((size_t)plan.acc_entries, stream)) return rc;
-    // the call's table: the code table, the offsets
-    const size_t off_bytes = (size_t)(nqueries + 1) * sizeof(int64_t), need = 256 + off_bytes;
-    int turn = 0;
-    if (int rc = pssm_table_turn(who, c, stream, need, &turn)) return rc;
-    unsigned char* h_tab = c->h_phtab[turn];
-    memcpy(h_tab, code, 256);
-    memcpy(h_tab + 256, qoffsets, off_bytes);
-    HIP_TRY(hipMemcpyAsync(c->d_phtab, h_tab, need, hipMemcpyHostToDevice, stream));
-    HIP_TRY(hipEventRecord(c->phtab_ev[turn], stream));
+    HitsCallTable tab;
+    if (int rc = upload_hits_call_table(who, c, stream, nullptr, nullptr, 0, code, qoffsets, nqueries, &tab)) return rc;
     HIP_TRY(hipMemsetAsync(c->d_pwacc, 0, (size_t)plan.acc_bytes, stream));
     swk::PssmWeightsParams kp;
     memset(&kp, 0, sizeof kp);
-    kp.code = c->d_phtab.p; kp.qoffs = (const int64_t*)(c->d_phtab + 256);
-    kp.db = (const unsigned char*)db->d_db; kp.offsets = db->d_offsets; kp.ntargets = db->ntargets;
-    kp.hits = d_hits; kp.nhits = d_nhits; kp.top = top;
-    kp.aln = d_aln; kp.ops = d_ops; kp.ops_cap = ops_cap;
-    kp.acc = c->d_pwacc; kp.weights = d_weights;
-    kp.nqueries = nqueries; kp.tiles_per_query = plan.tiles.tiles_per_query;
-    kp.include_min = weighting->include_min_score;
+    kp.t = hit_tables(db, tab.qoffs, nqueries, d_hits, d_nhits, top, d_aln, d_ops, ops_cap, weighting->include_min_score);
+    kp.code = tab.code; kp.acc = c->d_pwacc; kp.weights = d_weights;
+    kp.tiles_per_query = plan.tiles.tiles_per_query;
     kp.nletters = scoring->nletters; kp.stride = plan.tiles.stride; kp.tile_cols = plan.tiles.tile_cols; kp.per_hit = weighting->per_hit;
     hipLaunchKernelGGL(swk::sw_pssm_weights_tile, dim3((unsigned)plan.tiles.grid), dim3(256), plan.tiles.lds_bytes, stream, kp);
     HIP_TRY(hipGetLastError());
@@ -994,24 +1004,16 @@ int sw_db_msa_from_hits(sw_ctx* c, const sw_db* db, const char* d_queries, const
     DevOrder order(c, stream, false);
     if (order.rc) return order.rc;
     if (int rc = c->d_msasum.grow((size_t)plan.scan_chunks, stream)) return rc;
-    // the call's table: the offsets
-    const size_t need = (size_t)(nqueries + 1) * sizeof(int64_t);
-    int turn = 0;
-    if (int rc = pssm_table_turn(who, c, stream, need, &turn)) return rc;
-    memcpy(c->h_phtab[turn], qoffsets, need);
-    HIP_TRY(hipMemcpyAsync(c->d_phtab, c->h_phtab[turn], need, hipMemcpyHostToDevice, stream));
-    HIP_TRY(hipEventRecord(c->phtab_ev[turn], stream));
+    HitsCallTable tab;
+    if (int rc = upload_hits_call_table(who, c, stream, nullptr, nullptr, 0, nullptr, qoffsets, nqueries, &tab)) return rc;
     swk::MsaHitsParams kp;
     memset(&kp, 0, sizeof kp);
-    kp.queries = (const unsigned char*)d_queries; kp.qoffs = (const int64_t*)c->d_phtab.p;
-    kp.db = (const unsigned char*)db->d_db; kp.offsets = db->d_offsets; kp.ntargets = db->ntargets;
-    kp.hits = d_hits; kp.nhits = d_nhits; kp.top = top;
-    kp.aln = d_aln; kp.ops = d_ops; kp.ops_cap = ops_cap;
+    kp.t = hit_tables(db, tab.qoffs, nqueries, d_hits, d_nhits, top, d_aln, d_ops, ops_cap, include_min_score);
+    kp.queries = (const unsigned char*)d_queries;
     kp.cols = (unsigned char*)d_cols; kp.rows = d_rows; kp.a3m = (unsigned char*)d_a3m; kp.a3m_cap = a3m_cap; kp.a3m_bytes = d_a3m_bytes;
     kp.chunk_off = (int64_t*)c->d_msasum.p;
-    kp.nqueries = nqueries; kp.entries = plan.entries; kp.chunks = plan.scan_chunks;
+    kp.entries = plan.entries; kp.chunks = plan.scan_chunks;
     kp.slices_per_query = plan.slices_per_query; kp.slice_entries = plan.slice_entries; kp.col0 = qoffsets[0];
-    kp.include_min = include_min_score;
     hipLaunchKernelGGL(swk::sw_msa_cols, dim3((unsigned)plan.cols_grid), dim3(256), 0, stream, kp);
     HIP_TRY(hipGetLastError());
     if (d_rows) {

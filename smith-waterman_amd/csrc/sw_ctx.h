@@ -24,12 +24,12 @@ SW_HIDDEN int check_search_pssm(const char* who, const int64_t* qoffsets, int64_
 int check_prefilter(const char* who, int64_t min_score, const void* pairs, int64_t pairs_cap, const void* npairs, const void* scores);
 int check_align_hits(const char* who, int64_t top, const void* hits, const void* aln, const void* ops, int64_t ops_cap);
 SW_HIDDEN int check_pssm_update(const char* who, const sw_pssm_update* upd, int64_t top, const void* hits, const void* aln, const void* ops, int64_t ops_cap,
-                                const void* out, const void* counts);                                 // sw_pssm_read.cpp
+                                const void* out, const void* counts);                                 // sw_hits_host.cpp
 SW_HIDDEN int check_pssm_weighting(const char* who, const sw_pssm_weighting* wt, int64_t top, const void* hits, const void* aln, const void* ops,
-                                   int64_t ops_cap, const void* weights);                             // sw_pssm_read.cpp
+                                   int64_t ops_cap, const void* weights);                             // sw_hits_host.cpp
 SW_HIDDEN int check_msa(const char* who, const int64_t* qoffsets, int64_t nqueries, int64_t top, const void* hits, const void* aln, const void* ops,
-                        int64_t ops_cap, const void* cols, const void* rows, const void* a3m, int64_t a3m_cap, const void* a3m_bytes);   // sw_pssm_read.cpp
-SW_HIDDEN void pssm_update_table(const sw_submat* sub, const char* letters, int n, int8_t* S);        // sw_pssm_read.cpp
+                        int64_t ops_cap, const void* cols, const void* rows, const void* a3m, int64_t a3m_cap, const void* a3m_bytes);   // sw_hits_host.cpp
+SW_HIDDEN void pssm_update_table(const sw_submat* sub, const char* letters, int n, int8_t* S);        // sw_hits_host.cpp
 SW_HIDDEN int check_targets(const char* who, int64_t qlen, const int64_t* offsets, int64_t ntargets, int64_t* maxlen_out, int64_t* nonempty_out);
 }
 using swh::set_err;

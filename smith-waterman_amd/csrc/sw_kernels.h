@@ -183,20 +183,25 @@ __global__ void sw_search_profile_pssm_multi(const signed char* pssm, const Mult
 // ... its dynamic LDS: 256 columns of an odd number of dwords each (sw_pssm.hip says why), at most 64 KiB
 constexpr unsigned sw_pssm_profile_lds_bytes(int nletters) { return 1024u * (nletters > 252 ? 64u : (unsigned)(((nletters + 3) >> 2) | 1)); }
 
+// What every kernel that reads a hit table's alignments takes (sw_pssm_walk.h holds the used-entry rule and the walks over it).
+struct HitTables {
+    const int64_t* qoffs; int64_t nqueries;      // device copy of the caller's nqueries + 1 offsets
+    const unsigned char* db; const int64_t* offsets; int64_t ntargets;   // the handle's bytes and its ntargets + 1 offsets on the device
+    const sw_hit* hits; const int64_t* nhits; int64_t top;               // the caller's tables, as the alignment calls take and leave them
+    const sw_alignment* aln; const char* ops; int64_t ops_cap;
+    int64_t include_min;                         // entries that score less are not used
+};
+
 // sw_pssm_hits.hip: the next iteration's PSSM from a hit table, its alignments and their ops (sw_db_pssm_from_hits).  One workgroup per
 // (query, tile of columns) as swp::plan_pssm_hits cuts them; dynamic LDS: the plan's lds_bytes.
 struct PssmHitsParams {
+    HitTables t;
     const signed char* prior; signed char* out;  // the layout of d_pssm; out may be NULL, or prior itself
     int* counts;                                 // (qoffsets[nqueries] - qoffsets[0]) x nletters, or NULL
-    const int64_t* qoffs;                        // device copy of the caller's nqueries + 1 offsets
     const signed char* S;                        // nletters x nletters: S[b * nletters + k] = sub[letters[b]][letters[k]]
     const unsigned char* code;                   // 256 bytes: target byte -> its place in a column, 255 where it has none (swh::check_search_pssm)
-    const unsigned char* db; const int64_t* offsets; int64_t ntargets;   // the handle's bytes and its ntargets + 1 offsets on the device
-    const sw_hit* hits; const int64_t* nhits; int64_t top;               // the caller's tables, as sw_db_align_pssm_hits takes and leaves them
-    const sw_alignment* aln; const char* ops; int64_t ops_cap;
     const int* weights;                          // nqueries x top, or NULL: every weight 1
-    int64_t nqueries, tiles_per_query, col0;     // col0 = qoffsets[0]: counts start at the first query's first column
-    int64_t include_min;
+    int64_t tiles_per_query, col0;               // col0 = qoffsets[0]: counts start at the first query's first column
     int nletters, stride, tile_cols, smax, prior_weight;
 };
 __global__ void sw_pssm_from_hits(PssmHitsParams p);
@@ -205,15 +210,11 @@ __global__ void sw_pssm_from_hits(PssmHitsParams p);
 // per (query, tile of columns) with the tiles and the dynamic LDS of swp::plan_pssm_weights (those of plan_pssm_hits);
 // sw_pssm_weights_finish: one workgroup of 256 threads per query, static LDS.
 struct PssmWeightsParams {
-    const int64_t* qoffs;                        // device copy of the caller's nqueries + 1 offsets
+    HitTables t;
     const unsigned char* code;                   // 256 bytes: target byte -> its place in a column, 255 where it has none
-    const unsigned char* db; const int64_t* offsets; int64_t ntargets;   // the handle's bytes and its ntargets + 1 offsets on the device
-    const sw_hit* hits; const int64_t* nhits; int64_t top;               // the caller's tables, as sw_db_align_pssm_hits takes and leaves them
-    const sw_alignment* aln; const char* ops; int64_t ops_cap;
     unsigned long long* acc;                     // nqueries x top, zero before the tile launch: T_r + (m_r << 40)
     int* weights;                                // nqueries x top: every entry is written
-    int64_t nqueries, tiles_per_query;
-    int64_t include_min;
+    int64_t tiles_per_query;
     int nletters, stride, tile_cols, per_hit;
 };
 __global__ void sw_pssm_weights_tile(PssmWeightsParams p);
@@ -224,19 +225,15 @@ __global__ void sw_pssm_weights_finish(PssmWeightsParams p);
 // sw_msa_scan_chunks / sw_msa_scan_top: the exclusive scan of `len` in chunks of swp::kMsaScanChunk entries and over the chunks' sums;
 // sw_msa_rows: one wave per entry, its final `off` and its A3M row.
 struct MsaHitsParams {
+    HitTables t;
     const unsigned char* queries;                // the query letters at qoffs[q] + j, or NULL (PSSM queries): nident = 0
-    const int64_t* qoffs;                        // device copy of the caller's nqueries + 1 offsets
-    const unsigned char* db; const int64_t* offsets; int64_t ntargets;   // the handle's bytes and its ntargets + 1 offsets on the device
-    const sw_hit* hits; const int64_t* nhits; int64_t top;               // the caller's tables, as the alignment calls take and leave them
-    const sw_alignment* aln; const char* ops; int64_t ops_cap;
-    unsigned char* cols;                         // (qoffsets[nqueries] - qoffsets[0]) x top bytes, or NULL
+    unsigned char* cols;                        // (qoffsets[nqueries] - qoffsets[0]) x top bytes, or NULL
     sw_msa_row* rows;                            // nqueries x top, or NULL
     unsigned char* a3m; int64_t a3m_cap;         // a3m_cap bytes, or NULL
     int64_t* a3m_bytes;                          // the true total (with rows)
     int64_t* chunk_off;                          // workspace: per scan chunk its sum, then its exclusive offset
-    int64_t nqueries, entries, chunks;           // entries = nqueries x top; chunks of swp::kMsaScanChunk entries
+    int64_t entries, chunks;                     // entries = nqueries x top; chunks of swp::kMsaScanChunk entries
     int64_t slices_per_query, slice_entries, col0;   // col0 = qoffsets[0]: cols start at the first query's first column
-    int64_t include_min;
 };
 __global__ void sw_msa_cols(MsaHitsParams p);
 __global__ void sw_msa_scan_chunks(MsaHitsParams p);

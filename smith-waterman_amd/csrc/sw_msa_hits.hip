@@ -1,6 +1,6 @@
 // sw_msa_hits.hip -- the query-anchored multiple alignment of aligned hits (sw_db_msa_from_hits, gfx950): the column rows and the A3M
 // rows of the entries of a hit table, from the tables sw_db_align_affine_hits / sw_db_align_pssm_hits leave on the device.
-// include/swhip.h states the rule (used entries, the walk, valid inserts, the two layouts); sw_msa_from_hits_host (sw_pssm_read.cpp) is
+// include/swhip.h states the rule (used entries, the walk, valid inserts, the two layouts); sw_msa_from_hits_host (sw_hits_host.cpp) is
 // the same rule in plain C++.  Used entries and the walk come from sw_pssm_walk.h: the ops 64 at a time, one op per lane, the lane's
 // (j, i) and the inserts before it from three ballots and mbcnt.  No floats, no atomics; every byte has one writer per launch.
 //
@@ -64,27 +64,27 @@ __device__ __forceinline__ T sw_msa_scan256(T v, T* s, int tid, T& total) {
 
 __global__ void __launch_bounds__(256) sw_msa_cols(MsaHitsParams p) {
     const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    for (int64_t job = blockIdx.x; job < p.nqueries * p.slices_per_query; job += gridDim.x) {
+    const HitTables& t = p.t;
+    for (int64_t job = blockIdx.x; job < t.nqueries * p.slices_per_query; job += gridDim.x) {
         const int64_t q = job / p.slices_per_query, r0 = (job % p.slices_per_query) * p.slice_entries;
-        const int64_t g0 = p.qoffs[q];
-        const int qlen = (int)(p.qoffs[q + 1] - g0);
-        int64_t nh = p.top;
-        if (p.nhits) nh = min(max(p.nhits[q], (int64_t)0), p.top);
+        const int64_t g0 = t.qoffs[q];
+        const int qlen = (int)(t.qoffs[q + 1] - g0);
+        const int64_t nh = sw_pssm_query_hits(t, q);
         const unsigned char* qs = p.queries ? p.queries + g0 : nullptr;
-        const int64_t r1 = min(p.top, r0 + p.slice_entries);
+        const int64_t r1 = min(t.top, r0 + p.slice_entries);
         for (int64_t r = r0 + wave; r < r1; r += 4) {
-            const int64_t e = q * p.top + r;
-            unsigned char* row = p.cols ? p.cols + (g0 - p.col0) * p.top + r * qlen : nullptr;
+            const int64_t e = q * t.top + r;
+            unsigned char* row = p.cols ? p.cols + (g0 - p.col0) * t.top + r * qlen : nullptr;
             if (row) sw_msa_dashes(row, qlen, lane);
             sw_alignment a;
             int64_t toff = 0, len64 = 0;
             int nmatch = 0, nident = 0, nins = 0;
-            const bool used = r < nh && sw_pssm_entry_used(p.hits, p.aln, p.offsets, p.ntargets, e, qlen, p.include_min, p.ops_cap, a, toff, len64);
+            const bool used = r < nh && sw_pssm_entry_used(t, e, qlen, a, toff, len64);
             if (used) {
                 if (row) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // the dashes have reached the L2 before a pair overwrites one
-                const unsigned char* tb = p.db + toff;
+                const unsigned char* tb = t.db + toff;
                 int j_end;
-                sw_msa_walk((const unsigned char*)p.ops + e * p.ops_cap, a, qlen, (int)len64, lane, j_end, nins, [&](bool pair, bool, bool, int j, int i, int) {
+                sw_msa_walk(sw_pssm_entry_ops(t, e), a, qlen, (int)len64, lane, j_end, nins, [&](bool pair, bool, bool, int j, int i, int) {
                     bool same = false;
                     if (pair) {
                         const unsigned char c = tb[i];
@@ -135,20 +135,18 @@ __global__ void __launch_bounds__(256) sw_msa_rows(MsaHitsParams p) {
         const int64_t off = mine.off + p.chunk_off[e / kChunk];
         if (lane == 0) p.rows[e].off = off;
         if (!p.a3m || mine.len <= 0 || off + mine.len > p.a3m_cap) continue;
-        const int64_t q = e / p.top, r = e - q * p.top;
-        const int64_t g0 = p.qoffs[q];
-        const int qlen = (int)(p.qoffs[q + 1] - g0);
-        int64_t nh = p.top;
-        if (p.nhits) nh = min(max(p.nhits[q], (int64_t)0), p.top);
+        const HitTables& t = p.t;
+        const int64_t q = e / t.top, r = e - q * t.top;
+        const int qlen = (int)(t.qoffs[q + 1] - t.qoffs[q]);
         sw_alignment a;
         int64_t toff = 0, len64 = 0;
-        if (r >= nh || !sw_pssm_entry_used(p.hits, p.aln, p.offsets, p.ntargets, e, qlen, p.include_min, p.ops_cap, a, toff, len64)) continue;
+        if (r >= sw_pssm_query_hits(t, q) || !sw_pssm_entry_used(t, e, qlen, a, toff, len64)) continue;
         if (mine.len != qlen + mine.ninsert) continue;               // (launch A's row of these same tables: never)
         unsigned char* out = p.a3m + off;
-        const unsigned char* tb = p.db + toff;
+        const unsigned char* tb = t.db + toff;
         sw_msa_dashes(out, (int)a.q_begin, lane);
         int j_end, nins;
-        sw_msa_walk((const unsigned char*)p.ops + e * p.ops_cap, a, qlen, (int)len64, lane, j_end, nins, [&](bool pair, bool col, bool ins, int j, int i, int k) {
+        sw_msa_walk(sw_pssm_entry_ops(t, e), a, qlen, (int)len64, lane, j_end, nins, [&](bool pair, bool col, bool ins, int j, int i, int k) {
             // (j + k < qlen + the inserts of the whole walk = mine.len: the same tables give the same walk; compared all the same)
             if (j + k >= mine.len) return;
             if (col) out[j + k] = pair ? tb[i] : (unsigned char)'-';

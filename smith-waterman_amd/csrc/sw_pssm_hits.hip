@@ -1,16 +1,14 @@
 // sw_pssm_hits.hip -- the next iteration's PSSM from aligned hits (sw_db_pssm_from_hits, gfx950): the step that closes the loop
 // sw_db_search_pssm_top -> sw_db_align_pssm_hits -> here -> sw_db_search_pssm_top.  include/swhip.h states the rule (used entries, the
-// walk, weights, counts, the rounded weighted mean); sw_pssm_from_hits_host (sw_pssm_read.cpp) is the same rule in plain C++.
+// walk, weights, counts, the rounded weighted mean); sw_pssm_from_hits_host (sw_hits_host.cpp) is the same rule in plain C++.
 //
 // One workgroup (4 waves) per (query, tile of `tile_cols` columns); the plan (swp::plan_pssm_hits) fixes the tile so that its counts --
 // `stride` int32 per column, stride odd and > nletters -- and the 256-byte table from a target byte to its place in a column fit the LDS.
-//   * COUNT.  The waves take the query's entries round robin.  Entry, alignment and weight are loaded at wave-uniform addresses and
-//     every index is compared, unsigned, before anything is loaded through it.  An entry whose columns [q_begin, q_begin + nops) cannot
-//     reach the tile is skipped.  The ops are walked 64 at a time, one op per lane: one ballot of "consumes a query column", one of
-//     "consumes a target byte"; the number of set bits below a lane (mbcnt) gives the lane its (j, i), the popcounts advance the bases.
-//     No serial walk, no scan.  An 'M' lane whose column lies in the tile (and inside qlen / the target) loads its target byte, maps
-//     it through the table and adds the entry's weight to its count in LDS (ds_add_u32; integer adds commute, so the bytes that come
-//     out do not depend on the order).  The walk of an entry ends with the tile: j only grows.
+//   * COUNT.  The waves take the query's entries round robin; the used-entry guards, the skip of an entry whose columns cannot reach
+//     the tile and the walk of its ops, 64 at a time, are those of sw_pssm_walk.h.  The entry's weight is loaded at a wave-uniform
+//     address.  An 'M' lane whose column lies in the tile (and inside qlen / the target) loads its target byte, maps it through the
+//     table and adds the entry's weight to its count in LDS (ds_add_u32; integer adds commute, so the bytes that come out do not
+//     depend on the order).
 //   * WRITE.  After a barrier one thread per column sums its counts into the column's spare dword (N[j]).  After another, thread e of
 //     the tile's cols x nletters entries stores count e if the counts were asked for, then computes entry e: the prior's byte, the
 //     column's counts from LDS (the same address across the lanes of a column: a broadcast) against S[b][k] from global memory (adjacent
@@ -27,6 +25,7 @@
 #include <stdint.h>
 #include "sw_kernels.h"
 #include "sw_wave.h"
+#include "sw_pssm_walk.h"
 
 namespace swk {
 
@@ -45,9 +44,9 @@ __global__ void __launch_bounds__(256) sw_pssm_from_hits(PssmHitsParams p) {
     int* cnt = (int*)(lds_dw + 64);                                  // tile_cols x stride
     const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int nl = p.nletters, stride = p.stride;
-    for (int64_t job = blockIdx.x; job < p.nqueries * p.tiles_per_query; job += gridDim.x) {
+    for (int64_t job = blockIdx.x; job < p.t.nqueries * p.tiles_per_query; job += gridDim.x) {
         const int64_t q = job / p.tiles_per_query, c0 = (job % p.tiles_per_query) * p.tile_cols;
-        const int64_t g0 = p.qoffs[q], qlen = p.qoffs[q + 1] - g0;
+        const int64_t g0 = p.t.qoffs[q], qlen = p.t.qoffs[q + 1] - g0;
         if (c0 >= qlen) continue;                                    // (uniform in the workgroup: a shorter query has fewer tiles)
         const int cols = (int)min((int64_t)p.tile_cols, qlen - c0);
         const int64_t c1 = c0 + cols;
@@ -57,35 +56,21 @@ __global__ void __launch_bounds__(256) sw_pssm_from_hits(PssmHitsParams p) {
         __syncthreads();
 
         // ---- COUNT
-        int64_t nh = p.top;
-        if (p.nhits) nh = min(max(p.nhits[q], (int64_t)0), p.top);
+        const int64_t nh = sw_pssm_query_hits(p.t, q);
         for (int64_t r = wave; r < nh; r += 4) {
-            const int64_t e = q * p.top + r;
-            const uint64_t t = (uint64_t)p.hits[e].target;
-            if (t >= (uint64_t)p.ntargets) continue;
-            const sw_alignment a = p.aln[e];
-            if (a.max_score < p.include_min || a.nops <= 0 || a.nops > p.ops_cap) continue;
-            const int64_t toff = p.offsets[t], len = p.offsets[t + 1] - toff;
-            if ((uint64_t)a.q_begin > (uint64_t)qlen || (uint64_t)a.t_begin > (uint64_t)len) continue;
+            const int64_t e = q * p.t.top + r;
+            sw_alignment a;
+            int64_t toff, len;
+            if (!sw_pssm_entry_used(p.t, e, qlen, a, toff, len)) continue;
             int w = 1;
             if (p.weights) w = min(max(p.weights[e], 0), 65535);
             if (w == 0) continue;
-            if (a.q_begin >= c1 || a.nops <= c0 - a.q_begin) continue;   // its columns cannot reach the tile (no sum of two table values: none can overflow)
-            const unsigned char* ops = (const unsigned char*)p.ops + e * p.ops_cap;
-            const unsigned char* tb = p.db + toff;
-            int64_t jb = a.q_begin, ib = a.t_begin;                  // wave-uniform bases of the chunk
-            for (int64_t o = 0; o < a.nops && jb < c1 && ib < len; o += 64) {
-                const int op = o + lane < a.nops ? (int)ops[o + lane] : 0;
-                const bool m = op == 'M';
-                const uint64_t bq = __ballot(m || op == 'I'), bt = __ballot(m || op == 'D');
-                const int64_t j = jb + (int64_t)__builtin_amdgcn_mbcnt_hi((unsigned)(bq >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)bq, 0u));
-                const int64_t i = ib + (int64_t)__builtin_amdgcn_mbcnt_hi((unsigned)(bt >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)bt, 0u));
-                if (m && j >= c0 && j < c1 && i < len) {             // (c1 <= qlen)
-                    const int k = code[tb[i]];
-                    if (k < nl) atomicAdd(&cnt[(int)(j - c0) * stride + k], w);
-                }
-                jb += __popcll(bq); ib += __popcll(bt);
-            }
+            if (!sw_pssm_reaches_tile(a, c0, c1)) continue;
+            const unsigned char* tb = p.t.db + toff;
+            sw_pssm_walk(sw_pssm_entry_ops(p.t, e), a, len, c0, c1, lane, [&](int64_t j, int64_t i) {
+                const int k = code[tb[i]];
+                if (k < nl) atomicAdd(&cnt[(int)(j - c0) * stride + k], w);
+            });
         }
         __syncthreads();
 

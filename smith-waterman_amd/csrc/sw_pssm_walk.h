@@ -1,29 +1,34 @@
-// sw_pssm_walk.h -- what kernels that read a hit table's alignments share (gfx950): the guards that make entry (q, r) a USED ENTRY and
-// THE WALK of its ops, as include/swhip.h states them for sw_db_pssm_from_hits.  One wave per entry; everything is __forceinline__ inside
-// an unnamed namespace, as in sw_wave.h.  Both passes of sw_pssm_weights.hip go through it, and the two walking launches of
-// sw_msa_hits.hip through the guards and sw_msa_walk, the walk over all columns with the inserts counted.  sw_pssm_from_hits (sw_pssm_hits.hip) keeps
-// its own text of the same guards and walk: moved onto this header its assembly differs from what it was, and that kernel
-// was to stay byte for byte.
+// sw_pssm_walk.h -- what kernels that read a hit table's alignments share (gfx950): the clamped count of a query, the guards that make
+// entry (q, r) a USED ENTRY and THE WALK of its ops, as include/swhip.h states them for sw_db_pssm_from_hits.  One wave per entry;
+// everything is __forceinline__ inside an unnamed namespace, as in sw_wave.h.  sw_pssm_from_hits (sw_pssm_hits.hip) and both passes of
+// sw_pssm_weights.hip go through the guards, the reach test and sw_pssm_walk, the two walking launches of sw_msa_hits.hip through the
+// guards and sw_msa_walk, the walk over all columns with the inserts counted.  The loop over a query's entries stays written out in the
+// tile kernels: behind one helper sw_pssm_weights_tile measured 1 % slower at top = 4096.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include "../../include/swhip.h"
+#include "sw_kernels.h"
 
 namespace swk {
 
 namespace {
 
+// The entries of query q that count: nhits[q] clamped to 0..top, top without the counts.
+__device__ __forceinline__ int64_t sw_pssm_query_hits(const HitTables& t, int64_t q) { return t.nhits ? min(max(t.nhits[q], (int64_t)0), t.top) : t.top; }
+
+// The ops of entry e
+__device__ __forceinline__ const unsigned char* sw_pssm_entry_ops(const HitTables& t, int64_t e) { return (const unsigned char*)t.ops + e * t.ops_cap; }
+
 // Entry e = q * top + r (r below the query's clamped count) of a query of qlen columns: is it used?  Entry and alignment are loaded at
 // wave-uniform addresses, and every index is compared, unsigned, before anything is loaded through it.  A used entry leaves its
 // alignment, its target's first byte in the database and its target's length.
-__device__ __forceinline__ bool sw_pssm_entry_used(const sw_hit* hits, const sw_alignment* aln, const int64_t* offsets, int64_t ntargets, int64_t e, int64_t qlen,
-                                                   int64_t include_min, int64_t ops_cap, sw_alignment& a, int64_t& toff, int64_t& len) {
-    const uint64_t t = (uint64_t)hits[e].target;
-    if (t >= (uint64_t)ntargets) return false;
-    a = aln[e];
-    if (a.max_score < include_min || a.nops <= 0 || a.nops > ops_cap) return false;
-    toff = offsets[t];
-    len = offsets[t + 1] - toff;
+__device__ __forceinline__ bool sw_pssm_entry_used(const HitTables& t, int64_t e, int64_t qlen, sw_alignment& a, int64_t& toff, int64_t& len) {
+    const uint64_t tg = (uint64_t)t.hits[e].target;
+    if (tg >= (uint64_t)t.ntargets) return false;
+    a = t.aln[e];
+    if (a.max_score < t.include_min || a.nops <= 0 || a.nops > t.ops_cap) return false;
+    toff = t.offsets[tg];
+    len = t.offsets[tg + 1] - toff;
     return (uint64_t)a.q_begin <= (uint64_t)qlen && (uint64_t)a.t_begin <= (uint64_t)len;
 }
 

@@ -1,7 +1,7 @@
 // sw_pssm_weights.hip -- position-based sequence weights of aligned hits (sw_db_pssm_hit_weights, gfx950): the table that
 // sw_db_pssm_from_hits takes as d_weights, written on the device between sw_db_align_pssm_hits and that call.  include/swhip.h states
 // the rule (Henikoff & Henikoff 1994 in integers: n[j][k], k_j, the terms floor(F / (k_j n)), A_r, the rounded share of per_hit x U);
-// sw_pssm_hit_weights_host (sw_pssm_read.cpp) is the same rule in plain C++.  Used entries and the walk are those of sw_pssm_hits.hip,
+// sw_pssm_hit_weights_host (sw_hits_host.cpp) is the same rule in plain C++.  Used entries and the walk are those of sw_pssm_hits.hip,
 // through sw_pssm_walk.h.
 //
 // sw_pssm_weights_tile: one workgroup (4 waves) per (query, tile of columns), the tiles and the LDS layout of swp::plan_pssm_hits: the
@@ -50,9 +50,9 @@ __global__ void __launch_bounds__(256) sw_pssm_weights_tile(PssmWeightsParams p)
     int* cnt = (int*)(lds_dw + 64);                                  // tile_cols x stride: counts, then terms; k_j in the spare dword
     const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int nl = p.nletters, stride = p.stride;
-    for (int64_t job = blockIdx.x; job < p.nqueries * p.tiles_per_query; job += gridDim.x) {
+    for (int64_t job = blockIdx.x; job < p.t.nqueries * p.tiles_per_query; job += gridDim.x) {
         const int64_t q = job / p.tiles_per_query, c0 = (job % p.tiles_per_query) * p.tile_cols;
-        const int64_t qlen = p.qoffs[q + 1] - p.qoffs[q];
+        const int64_t qlen = p.t.qoffs[q + 1] - p.t.qoffs[q];
         if (c0 >= qlen) continue;                                    // (uniform in the workgroup: a shorter query has fewer tiles)
         const int cols = (int)min((int64_t)p.tile_cols, qlen - c0);
         const int64_t c1 = c0 + cols;
@@ -60,18 +60,17 @@ __global__ void __launch_bounds__(256) sw_pssm_weights_tile(PssmWeightsParams p)
         code[tid] = p.code[tid];
         for (int e = tid; e < cols * stride; e += 256) cnt[e] = 0;
         __syncthreads();
-        int64_t nh = p.top;
-        if (p.nhits) nh = min(max(p.nhits[q], (int64_t)0), p.top);
+        const int64_t nh = sw_pssm_query_hits(p.t, q);
 
         // ---- COUNT
         for (int64_t r = wave; r < nh; r += 4) {
-            const int64_t e = q * p.top + r;
+            const int64_t e = q * p.t.top + r;
             sw_alignment a;
             int64_t toff, len;
-            if (!sw_pssm_entry_used(p.hits, p.aln, p.offsets, p.ntargets, e, qlen, p.include_min, p.ops_cap, a, toff, len)) continue;
+            if (!sw_pssm_entry_used(p.t, e, qlen, a, toff, len)) continue;
             if (!sw_pssm_reaches_tile(a, c0, c1)) continue;
-            const unsigned char* tb = p.db + toff;
-            sw_pssm_walk((const unsigned char*)p.ops + e * p.ops_cap, a, len, c0, c1, lane, [&](int64_t j, int64_t i) {
+            const unsigned char* tb = p.t.db + toff;
+            sw_pssm_walk(sw_pssm_entry_ops(p.t, e), a, len, c0, c1, lane, [&](int64_t j, int64_t i) {
                 const int k = code[tb[i]];
                 if (k < nl) atomicAdd(&cnt[(int)(j - c0) * stride + k], 1);
             });
@@ -96,14 +95,14 @@ __global__ void __launch_bounds__(256) sw_pssm_weights_tile(PssmWeightsParams p)
 
         // ---- SUM
         for (int64_t r = wave; r < nh; r += 4) {
-            const int64_t e = q * p.top + r;
+            const int64_t e = q * p.t.top + r;
             sw_alignment a;
             int64_t toff, len;
-            if (!sw_pssm_entry_used(p.hits, p.aln, p.offsets, p.ntargets, e, qlen, p.include_min, p.ops_cap, a, toff, len)) continue;
+            if (!sw_pssm_entry_used(p.t, e, qlen, a, toff, len)) continue;
             if (!sw_pssm_reaches_tile(a, c0, c1)) continue;
-            const unsigned char* tb = p.db + toff;
+            const unsigned char* tb = p.t.db + toff;
             u64 mine = 0;
-            sw_pssm_walk((const unsigned char*)p.ops + e * p.ops_cap, a, len, c0, c1, lane, [&](int64_t j, int64_t i) {
+            sw_pssm_walk(sw_pssm_entry_ops(p.t, e), a, len, c0, c1, lane, [&](int64_t j, int64_t i) {
                 const int k = code[tb[i]];
                 if (k < nl) mine += (u64)(u32)cnt[(int)(j - c0) * stride + k] + (1ull << kPairShift);
             });
@@ -118,11 +117,12 @@ __global__ void __launch_bounds__(256) sw_pssm_weights_finish(PssmWeightsParams 
     __shared__ u64 part_sum[4];
     __shared__ int part_used[4];
     const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    for (int64_t q = blockIdx.x; q < p.nqueries; q += gridDim.x) {
+    const int64_t top = p.t.top;
+    for (int64_t q = blockIdx.x; q < p.t.nqueries; q += gridDim.x) {
         __syncthreads();                                             // the last query's sums have been read
         u64 s = 0, u = 0;
-        for (int64_t r = tid; r < p.top; r += 256) {
-            const u64 v = p.acc[q * p.top + r];
+        for (int64_t r = tid; r < top; r += 256) {
+            const u64 v = p.acc[q * top + r];
             const u64 T = v & ((1ull << kPairShift) - 1), m = v >> kPairShift;
             const int a = m ? (int)(T / m) : 0;
             A[r] = a;
@@ -134,10 +134,10 @@ __global__ void __launch_bounds__(256) sw_pssm_weights_finish(PssmWeightsParams 
         const u64 S = part_sum[0] + part_sum[1] + part_sum[2] + part_sum[3];
         const u64 U = (u64)(part_used[0] + part_used[1] + part_used[2] + part_used[3]);
         const u64 scale = 2 * (u64)p.per_hit * U;                    // (< 2^30; times A_r <= 2^20, plus S <= 2^32: below 2^51)
-        for (int64_t r = tid; r < p.top; r += 256) {
+        for (int64_t r = tid; r < top; r += 256) {
             int w = 0;
             if (S > 0) w = (int)min((scale * (u64)A[r] + S) / (2 * S), (u64)65535);
-            p.weights[q * p.top + r] = w;
+            p.weights[q * top + r] = w;
         }
     }
 }

@@ -1,4 +1,4 @@
-// Drives sw_pssm_from_hits_host and sw_write_pssm (smith-waterman_amd/csrc/sw_pssm_read.cpp) for tests/test_pssm_hits_host.py over tables
+// Drives sw_pssm_from_hits_host (smith-waterman_amd/csrc/sw_hits_host.cpp) and sw_write_pssm (.../sw_pssm_read.cpp) for tests/test_pssm_hits_host.py over tables
 // NO alignment call would write -- targets -1 and ntargets, counts below 0 and above top, nops 0 and ops_cap + 1, q_begin / t_begin out
 // of range, op bytes 0x00 / 0xFF, walks that run past qlen and len, weights out of range -- with every buffer a heap block of EXACTLY
 // its size, so that a read or write past one is a sanitizer error.  Built with -fsanitize=address,undefined.  argv[1]: a file to write.

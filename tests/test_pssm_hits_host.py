@@ -262,12 +262,13 @@ def test_write_pssm_round_trip(swamd, tmp_path):
 
 
 def test_host_leg_and_writer_are_clean_under_the_sanitizers(tmp_path):
-    """tests/pssm_hits_driver.cpp, a program of its own, with the source that holds the host leg and the writer, both under
+    """tests/pssm_hits_driver.cpp, a program of its own, with the sources that hold the host leg and the writer, all under
     -fsanitize=address,undefined: garbage tables in heap blocks of exactly their sizes.  A clean exit is the test."""
     if shutil.which("g++") is None:
         pytest.fail("g++ is needed to build the driver")
     exe = str(tmp_path / "pssm_hits_driver")
     subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-Wall", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-o", exe,
-                    os.path.join(ROOT, "tests", "pssm_hits_driver.cpp"), os.path.join(ROOT, "smith-waterman_amd", "csrc", "sw_pssm_read.cpp")], check=True)
+                    os.path.join(ROOT, "tests", "pssm_hits_driver.cpp"), os.path.join(ROOT, "smith-waterman_amd", "csrc", "sw_hits_host.cpp"),
+                    os.path.join(ROOT, "smith-waterman_amd", "csrc", "sw_pssm_read.cpp")], check=True)
     r = subprocess.run([exe, str(tmp_path / "driver.pssm")], capture_output=True, text=True)
     assert r.returncode == 0 and r.stderr == "" and r.stdout.startswith("ok "), (r.returncode, r.stdout, r.stderr)
