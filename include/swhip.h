@@ -780,6 +780,49 @@ int  sw_msa_from_hits_host(const char* queries, const int64_t* qoffsets, int64_t
 int  sw_write_a3m(const char* path, const char* qname, const char* query, int64_t qlen, const char* const* tnames, int64_t ntargets,
                   const sw_hit* hits, const sw_alignment* aln, const sw_msa_row* rows, int64_t top, const char* a3m, int64_t a3m_cap);
 
+/* The FILTER of a hit alignment, on the device (csrc/sw_msa_filter.hip): the stage between "align" and "weights / update" that drops
+ * the rows that are too short and the rows that are nearly identical to the query or to a better-ranked row (PSI-BLAST's purge,
+ * hhfilter -id -cov).  It reads the COLUMN ROWS of sw_db_msa_from_hits exactly as that call writes them into d_cols -- per query q of
+ * qlen = qoffsets[q + 1] - qoffsets[q] columns, row r = 0 .. top - 1 has qlen bytes at d_cols + (qoffsets[q] - qoffsets[0]) x top +
+ * r x qlen -- and needs no database handle.  Bytes are taken verbatim; '-' (0x2D) means NO LETTER, so a target byte that happens to be
+ * 0x2D counts as no letter.
+ * THE RULE, per query, integers only:
+ *   n_r          : the bytes of row r that are not '-'.
+ *   same(r, r')  : the columns j where row r has a letter and row r' holds the same byte.
+ *   sameq(r)     : the same count against the query's letters d_queries[qoffsets[q] + j]; only with d_queries != NULL.  For tables that
+ *                  come from the alignment calls it equals nident of sw_msa_row.
+ *   covered(r)   : n_r >= 1 and 100 x n_r >= min_cover_pct x qlen.
+ *   redundant(r | r') : 100 x same(r, r') >= max_ident_pct x n_r -- at least max_ident_pct percent of what row r shows is already
+ *                  shown, letter for letter, by r'.  Asymmetric on purpose: the lower-ranked row is measured against its own length.
+ *   keep(r), for r = 0 .. top - 1 in rank order, holds when covered(r); and d_queries == NULL or 100 x sameq(r) < max_ident_pct x n_r;
+ *                  and redundant(r | r') is false for every r' < r with keep(r').  GREEDY: a row that was dropped suppresses nothing.
+ *   sw_msa_filter : max_ident_pct 1..101 (101 drops nothing for identity: same <= n_r), min_cover_pct 0..100.  Every product fits
+ *                  int32 (100 x 2^20).  No floats: device, host leg and any restatement agree bit for bit, every run writes the same bytes.
+ * Outputs (at least one of d_keep and d_hits_out):
+ *   d_keep     : device, nqueries x top int32, 1 or 0, EVERY entry written; the layout of d_weights, so it goes into
+ *                sw_db_pssm_from_hits as unit weights.  Optional.
+ *   d_hits_out : device, nqueries x top sw_hit, with d_hits (optional together): entry (q, r) is d_hits[q x top + r] with target = -1
+ *                where keep is 0, unchanged otherwise.  d_hits_out == d_hits (in place) is allowed.  A dropped entry is not a USED
+ *                ENTRY of sw_db_pssm_hit_weights, sw_db_pssm_from_hits and sw_db_msa_from_hits: they see the kept entries only.
+ *   d_nkept    : device, nqueries int64: the rows kept.  Optional.
+ * Asynchronous on `stream`, no host round trip: the host reads no device table, its work is O(nqueries).  The offsets are uploaded
+ * through the two pinned copies of sw_db_pssm_from_hits, in the same turns: a loop can be enqueued one call ahead.  Defined for ANY
+ * bytes in d_cols and d_queries; nothing is read or written out of bounds; rows need no alignment (qlen and the bases may be odd).
+ * Launches (swp::plan_msa_filter), per chunk of queries whose bit matrices fit the option "msa_filter_workspace_mib" (default 256, at
+ * least what one query of top 4096 needs): the PAIR launch, one workgroup per (query, 64 x 64 tile of the triangle r' <= r), leaves
+ * bit r' of word (r' / 64, r) set where redundant(r | r'), and the row's own test (cover, query) beside it -- the tiles on the diagonal
+ * compare with the query; the GREEDY launch, one workgroup per query, resolves keep in rank order 64 rows at a time and writes the
+ * outputs.  "last_msa_filter_launches" and "last_msa_filter_chunks" report the last call.  nqueries == 0 launches nothing.
+ * SW_EINVAL, checked before the first launch: the offset errors of sw_db_msa_from_hits (so every query has at least one column); top
+ * outside 1..SW_TOP_MAX; NULL d_cols or filter; a percentage out of range; both outputs NULL; d_hits_out without d_hits.
+ *   sw_msa_filter_host  the CPU leg: the same bytes in plain C++ from host memory. */
+typedef struct { int32_t max_ident_pct; int32_t min_cover_pct; } sw_msa_filter;
+int  sw_msa_filter_device(sw_ctx* ctx, const char* d_cols, const char* d_queries, const int64_t* qoffsets, int64_t nqueries, int64_t top,
+                          const sw_msa_filter* filter, const sw_hit* d_hits, sw_hit* d_hits_out, int32_t* d_keep, int64_t* d_nkept,
+                          void* stream);
+int  sw_msa_filter_host(const char* cols, const char* queries, const int64_t* qoffsets, int64_t nqueries, int64_t top,
+                        const sw_msa_filter* filter, const sw_hit* hits, sw_hit* hits_out, int32_t* keep, int64_t* nkept);
+
 /* Tables.  sw_submat_match: s[x][y] = x == y ? match : mismatch (matchMissmatchScore, serial_smithW.c:251-256; both must fit int8:
  * the builder returns nothing, so it clamps them to -128..127 -- a caller that takes them from a user checks the range first, as
  * smithW and the Python wrapper do, which refuse such scores).  sw_submat_from_letters: `scores` is n x n, row = query letter, over the n bytes of

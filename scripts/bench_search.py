@@ -78,6 +78,13 @@
   without it: D2H of d_hits, d_nhits, d_aln and d_ops, then msa_from_hits_host.  7 calls each after a warm-up, wall clock around a
   synchronised leg, ALTERNATING in one process; the three outputs compared byte for byte (the run fails if they differ).  *_bytes_written
   is what the device call stores (column rows + 24 bytes per entry + A3M rows), *_write_gbs that over the device call's time
+  --msa-filter: data set (a) only, the 64 queries, tables and top 10 / 100 / 4096 of --pssm-weights plus the column rows of
+  msa_from_hits_device; the filter is (max_ident_pct 90, min_cover_pct 0), hhfilter's defaults.  (a) msa_filter_device alone -- keep,
+  the counts and the filtered hit table -- against what a caller has to do without it: D2H of the column rows and the hit table,
+  msa_filter_host, H2D of the filtered table; the three outputs compared byte for byte (the run fails if they differ).  7 calls each
+  after a warm-up, ALTERNATING; a leg whose warm-up call takes more than 20 s is timed by that call alone (*_calls says how many calls
+  stand behind a median).  (b) a weighted iteration (--pssm-weights (b)) beside one with msa_from_hits_device (column rows) and
+  msa_filter_device in front of the weights, which with the update then read the filtered table
 GCUPS = query letters x target letters / time of the call (torch events, median of --reps after --warmup)."""
 import argparse
 import importlib
@@ -130,6 +137,7 @@ def main():
     ap.add_argument("--pssm-iterate", action="store_true", help="data set (a) only: the PSSM update on the device against the host round trip, and a whole iteration against the search alone")
     ap.add_argument("--pssm-weights", action="store_true", help="data set (a) only: the hit weights on the device against the host round trip, and a weighted iteration against the unweighted one")
     ap.add_argument("--msa", action="store_true", help="data set (a) only: the query-anchored alignment of the top 10 / 100 / 4096 hits of 64 queries on the device against the host round trip")
+    ap.add_argument("--msa-filter", action="store_true", help="data set (a) only: the filter of the column rows of the top 10 / 100 / 4096 hits of 64 queries on the device against the host round trip, and a weighted iteration with and without it")
     ap.add_argument("--lanes", action="store_true", help="data set (a) only: 64 queries under search_lanes 32 and 16, alternating, full tables and top 10")
     ap.add_argument("--pairs-lanes", action="store_true", help="data set (a) only: pair lists of all, 10 %% and 1 %% of the cross product under search_pairs_lanes 32 and 16, alternating")
     ap.add_argument("--top", action="store_true", help="data set (a) only: the best 100 targets of 64 queries by the full table and by the selection on the device")
@@ -751,6 +759,94 @@ def main():
         out[f"{P}_identical"] = all(out[f"{P}_top{t}_identical"] for t in (10, 100, 4096))
         db.close()
 
+    def msa_filter_leg(packed, offs, nq=64, reps=7, per_hit=16, filt=(90, 0)):
+        import time
+        d_db = torch.from_numpy(packed.copy()).to(dev)
+        db = eng.prepare_db(d_db, offs)
+        qoffs = np.arange(nq + 1, dtype=np.int64) * args.qlen
+        queries = rng.choice(PROTEIN, int(qoffs[-1])).astype(np.uint8)
+        d_q = torch.from_numpy(queries.copy()).to(dev)
+        m, moffs = swamd.pssm_from_queries((queries, qoffs), sub, letters)
+        d_m = torch.from_numpy(m.reshape(-1).copy()).to(dev)
+        pscoring, weighting, cap, inc = (letters, -4, 127, -11, -1), (per_hit, 1), 4 * args.qlen, 1
+        wupdate = (sub, 10 * per_hit, 1)
+        P = "msa_filter"
+        out[f"{P}_queries"], out[f"{P}_qlen"], out[f"{P}_targets"], out[f"{P}_reps"], out[f"{P}_ops_cap"] = nq, args.qlen, len(offs) - 1, reps, cap
+        out[f"{P}_max_ident_pct"], out[f"{P}_min_cover_pct"] = filt
+        for top in (10, 100, 4096):
+            hits, nhits = db.search_pssm_top_device(d_m, moffs, pscoring, top, 1)
+            aln, ops = db.align_pssm_hits_device(d_m, moffs, pscoring, hits, nhits, ops_cap=cap)
+            cols = db.msa_from_hits_device(d_q, moffs, inc, hits, nhits, aln, ops, cap, rows=False)[0]
+            d_keep = torch.empty(nq * top, dtype=torch.int32, device=dev)
+            d_nkept = torch.empty(nq, dtype=torch.int64, device=dev)
+            hf = torch.empty_like(hits)
+            d_out = torch.empty_like(d_m)
+            d_w = torch.empty((nq, top), dtype=torch.int32, device=dev)
+            h2 = (torch.zeros_like(hits), torch.zeros_like(nhits))
+            state = {}
+
+            def device_call():
+                eng.msa_filter_device(cols, d_q, moffs, top, filt, hits=hits.view(-1), hits_out=hf.view(-1), keep=d_keep, nkept=d_nkept)
+
+            def host_round_trip():                                           # what a caller has today: D2H, the host leg, H2D of the table
+                c, h = cols.cpu().numpy(), hits.cpu().numpy()
+                state["host"] = swamd.msa_filter_host(c, (queries, qoffs), top, filt[0], filt[1], hits=h)
+                state["d"] = torch.from_numpy(state["host"][2].reshape(-1)).to(dev)
+
+            def weighted_iteration():
+                db.align_pssm_hits_device(d_m, moffs, pscoring, hits, nhits, ops_cap=cap, out=(aln, ops))
+                db.pssm_hit_weights_device(moffs, pscoring, weighting, hits, nhits, aln, ops, cap, out=d_w)
+                db.pssm_from_hits_device(d_m, moffs, pscoring, wupdate, hits, nhits, aln, ops, cap, weights=d_w, out=d_out)
+                db.search_pssm_top_device(d_out, moffs, pscoring, top, 1, out=h2)
+
+            def filtered_iteration():
+                db.align_pssm_hits_device(d_m, moffs, pscoring, hits, nhits, ops_cap=cap, out=(aln, ops))
+                db.msa_from_hits_device(d_q, moffs, inc, hits, nhits, aln, ops, cap, cols=cols, rows=False)
+                eng.msa_filter_device(cols, d_q, moffs, top, filt, hits=hits.view(-1), hits_out=hf.view(-1), keep=False, nkept=False)
+                db.pssm_hit_weights_device(moffs, pscoring, weighting, hf, nhits, aln, ops, cap, out=d_w)
+                db.pssm_from_hits_device(d_m, moffs, pscoring, wupdate, hf, nhits, aln, ops, cap, weights=d_w, out=d_out)
+                db.search_pssm_top_device(d_out, moffs, pscoring, top, 1, out=h2)
+
+            def wall(fn):                                                    # wall clock around a synchronised call
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                fn()
+                torch.cuda.synchronize()
+                return (time.perf_counter() - t0) * 1e3
+
+            legs = {"device_call": device_call, "host_round_trip": host_round_trip, "weighted_iteration": weighted_iteration,
+                    "filtered_iteration": filtered_iteration}
+            for group in (("device_call", "host_round_trip"), ("weighted_iteration", "filtered_iteration")):
+                ms = {k: [] for k in group}
+                first = {k: wall(legs[k]) for k in group}                    # warm-up
+                # a host leg of more than 20 s is timed by that one call: seven more would take the better part of an hour
+                once = {k for k in group if first[k] > 20e3}
+                for _ in range(reps):                                        # alternating: a drift of the device shows in all alike
+                    for k in group:
+                        if k not in once:
+                            ms[k].append(wall(legs[k]))
+                for k in group:
+                    if k in once:
+                        ms[k] = [first[k]]
+                    out[f"{P}_top{top}_{k}_ms"] = round(float(np.median(ms[k])), 4)
+                    out[f"{P}_top{top}_{k}_range_ms"] = [round(min(ms[k]), 4), round(max(ms[k]), 4)]
+                    out[f"{P}_top{top}_{k}_calls"] = len(ms[k])
+            d_keep.fill_(0x55555555); d_nkept.fill_(-1); hf.fill_(0x5555555555555555)
+            device_call()
+            torch.cuda.synchronize()
+            hk, hn, hh = state["host"]
+            out[f"{P}_top{top}_identical"] = bool(d_keep.cpu().numpy().tobytes() == hk.tobytes() and d_nkept.cpu().numpy().tobytes() == hn.tobytes()
+                                                  and hf.cpu().numpy().tobytes() == hh.tobytes())
+            out[f"{P}_top{top}_launches"] = eng.get_option("last_msa_filter_launches")
+            out[f"{P}_top{top}_chunks"] = eng.get_option("last_msa_filter_chunks")
+            out[f"{P}_top{top}_kept"] = int(hn.sum())
+            out[f"{P}_top{top}_rows_with_letters"] = int((cols.cpu().numpy().reshape(-1, args.qlen) != 0x2D).any(axis=1).sum())
+            out[f"{P}_top{top}_d2h_bytes"] = int(cols.numel() + hits.numel() * 8)
+            out[f"{P}_top{top}_host_over_device"] = round(out[f"{P}_top{top}_host_round_trip_ms"] / out[f"{P}_top{top}_device_call_ms"], 2)
+            out[f"{P}_top{top}_filtered_over_weighted"] = round(out[f"{P}_top{top}_filtered_iteration_ms"] / out[f"{P}_top{top}_weighted_iteration_ms"], 4)
+        out[f"{P}_identical"] = all(out[f"{P}_top{t}_identical"] for t in (10, 100, 4096))
+        db.close()
+
     def pssm_weights_leg(packed, offs, nq=64, reps=7, per_hit=16):
         import time
         d_db = torch.from_numpy(packed.copy()).to(dev)
@@ -1022,7 +1118,7 @@ def main():
     out["a_letters"] = int(offs[-1])
     out["a_len_median"] = int(np.median(lens))
     out["a_len_max"] = int(lens.max())
-    if args.multi or args.top or args.align_hits or args.pairs or args.prefilter or args.prefiltered_top or args.pssm or args.pssm_iterate or args.pssm_weights or args.msa or args.lanes or args.pairs_lanes:
+    if args.multi or args.top or args.align_hits or args.pairs or args.prefilter or args.prefiltered_top or args.pssm or args.pssm_iterate or args.pssm_weights or args.msa or args.msa_filter or args.lanes or args.pairs_lanes:
         if args.lanes:
             lanes_leg(packed, offs)
         if args.pairs_lanes:
@@ -1035,6 +1131,8 @@ def main():
             pssm_weights_leg(packed, offs)
         if args.msa:
             msa_leg(packed, offs)
+        if args.msa_filter:
+            msa_filter_leg(packed, offs)
         if args.pairs:
             pairs_leg(packed, offs)
         if args.prefilter:
@@ -1061,6 +1159,8 @@ def main():
             sys.exit("bench_search.py --pssm-weights: pssm_weights_identical is false")
         if args.msa and not out["msa_identical"]:
             sys.exit("bench_search.py --msa: msa_identical is false")
+        if args.msa_filter and not out["msa_filter_identical"]:
+            sys.exit("bench_search.py --msa-filter: msa_filter_identical is false")
         if args.pssm and not out["pssm_identical"]:
             sys.exit("bench_search.py --pssm: pssm_identical is false")
         if args.pairs:   # the required conditions of the pair-list call: a line that misses one is printed, and the run fails

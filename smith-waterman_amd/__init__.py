@@ -59,6 +59,10 @@ class _PssmWeighting(ctypes.Structure):   # sw_pssm_weighting
     _fields_ = [("per_hit", ctypes.c_int32), ("include_min_score", ctypes.c_int64)]
 
 
+class _MsaFilter(ctypes.Structure):   # sw_msa_filter
+    _fields_ = [("max_ident_pct", ctypes.c_int32), ("min_cover_pct", ctypes.c_int32)]
+
+
 # every symbol include/swhip.h declares: (restype, argtypes)
 _vp, _i64, _i32, _u32, _sz = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_uint32, ctypes.c_size_t
 ABI = {
@@ -112,6 +116,8 @@ ABI = {
                                         _i64, _vp]),
     "sw_db_msa_from_hits": (_i32, [_vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp]),
     "sw_msa_from_hits_host": (_i32, [_vp, _vp, _i64, _vp, _vp, _i64, _i64, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _vp]),
+    "sw_msa_filter_device": (_i32, [_vp, _vp, _vp, _vp, _i64, _i64, ctypes.POINTER(_MsaFilter), _vp, _vp, _vp, _vp, _vp]),
+    "sw_msa_filter_host": (_i32, [_vp, _vp, _vp, _i64, _i64, ctypes.POINTER(_MsaFilter), _vp, _vp, _vp, _vp]),
     "sw_write_a3m": (_i32, [ctypes.c_char_p, ctypes.c_char_p, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _i64]),
     "sw_write_pssm": (_i32, [ctypes.c_char_p, _vp, ctypes.c_int32, _vp, _i64, _vp]),
     "sw_align_affine_device": (_i32, [_vp, _vp, _i64, _vp, _vp, _i64, _vp, _i64, ctypes.POINTER(_Affine), _vp, _vp, _i64, _vp]),
@@ -634,6 +640,43 @@ def msa_from_hits_host(queries, targets, include_min_score, hits, nhits, aln, op
     a3m = np.zeros(max(1, int(a3m_cap)), np.uint8)
     call(cols.ctypes.data, a3m.ctypes.data, int(a3m_cap))
     return cols[:ncols * top], rows[:nq * top].reshape(nq, top), a3m[:int(a3m_cap)]
+
+
+def _msa_filter(filter):
+    """The sw_msa_filter from (max_ident_pct, min_cover_pct)."""
+    max_ident_pct, min_cover_pct = filter
+    return _MsaFilter(int(max_ident_pct), int(min_cover_pct))
+
+
+def _msa_filter_args(cols, queries_or_qoffsets, top: int, hits):
+    """The host arguments of a filter call, checked: (cols uint8, query letters or None, int64 offsets, nq, top, (nq, top, 3) hits or None)."""
+    qpacked, qoffs = _msa_queries(queries_or_qoffsets)
+    nq, top = len(qoffs) - 1, int(top)
+    c = np.ascontiguousarray(cols, np.uint8).reshape(-1)
+    need = int(qoffs[-1] - qoffs[0]) * max(0, top)
+    if len(c) < need:
+        raise ValueError(f"cols must hold at least {need} bytes")
+    if qpacked is not None and len(qpacked) < int(qoffs[-1]):
+        raise ValueError(f"the query letters must hold at least {int(qoffs[-1])} bytes")
+    if hits is not None:
+        hits, _ = _hit_table(hits, None, nq)
+        if hits.shape[1] != top:
+            raise ValueError(f"hits must be ({nq}, {top}, 3) int64")
+    return c, qpacked, qoffs, nq, top, hits
+
+
+def msa_filter_host(cols, queries_or_qoffsets, top: int, max_ident_pct: int, min_cover_pct: int, hits=None):
+    """sw_msa_filter_host: the filter of the column rows in plain C++ on the host (no GPU).  Arguments and results as Engine.msa_filter."""
+    c, qpacked, qoffs, nq, top, hits = _msa_filter_args(cols, queries_or_qoffsets, top, hits)
+    f = _msa_filter((max_ident_pct, min_cover_pct))
+    one = np.zeros(1, np.uint8)
+    keep = np.zeros(max(1, nq * max(0, top)), np.int32)
+    nkept = np.zeros(max(1, nq), np.int64)
+    out = np.zeros_like(hits) if hits is not None else None
+    _check(lib().sw_msa_filter_host((c if len(c) else one).ctypes.data, qpacked.ctypes.data if qpacked is not None and len(qpacked) else None,
+                                    qoffs.ctypes.data, nq, top, ctypes.byref(f), hits.ctypes.data if hits is not None and hits.size else None,
+                                    out.ctypes.data if out is not None and out.size else None, keep.ctypes.data, nkept.ctypes.data))
+    return keep[:nq * top].reshape(nq, top), nkept[:nq], out
 
 
 def write_a3m(path: str, qname: str, query, tnames, hits, aln, rows, a3m):
@@ -1636,6 +1679,67 @@ class Engine:
         _check(lib().sw_top_hits_pairs_device(self._h, d_pairs.data_ptr() if npairs else None, d_results.data_ptr() if npairs else None, int(npairs),
                                               int(nqueries), int(ntargets), int(top), int(min_score), hits.data_ptr(), nhits.data_ptr(), self._stream()))
         return self._top_views(hits, nhits, int(nqueries), top)
+
+    def msa_filter(self, cols, queries_or_qoffsets, top: int, max_ident_pct: int, min_cover_pct: int, hits=None):
+        """The filter of a hit alignment (sw_msa_filter_device): which rows of the column rows of Database.msa_from_hits are kept --
+        covered to min_cover_pct percent, less than max_ident_pct percent identical to the query and to every kept row of better rank
+        (include/swhip.h states the rule).  cols: the uint8 column rows; queries_or_qoffsets: the sequences as for search_affine, or
+        the 1-D int64 column offsets (no letters: no row is compared with the query); hits: the (nqueries, top, 3) hit table, or
+        None.  Returns numpy (keep (nqueries, top) int32, nkept (nqueries,) int64, the hit table with target = -1 in the dropped
+        entries or None)."""
+        t = self.torch
+        dev = f"cuda:{self.device}"
+        c, qpacked, qoffs, nq, top, hits = _msa_filter_args(cols, queries_or_qoffsets, top, hits)
+        d_cols = t.from_numpy(c.copy() if len(c) else np.zeros(1, np.uint8)).to(dev)
+        d_q = t.from_numpy(qpacked.copy()).to(dev) if qpacked is not None and len(qpacked) else None
+        d_hits = t.from_numpy(hits.reshape(-1).copy()).to(dev) if hits is not None and hits.size else None
+        keep, nkept, out = self.msa_filter_device(d_cols, d_q, qoffs, top, (max_ident_pct, min_cover_pct), hits=d_hits, hits_out=d_hits)
+        self.synchronize()
+        return (keep.cpu().numpy()[:nq * top].reshape(nq, top), nkept.cpu().numpy()[:nq],
+                out.cpu().numpy()[:nq * top * 3].reshape(nq, top, 3) if out is not None else None)
+
+    def msa_filter_device(self, d_cols, d_queries, qoffsets, top: int, filter, hits=None, hits_out=None, keep=None, nkept=None):
+        """sw_msa_filter_device on device-resident column rows (the uint8 tensor Database.msa_from_hits_device fills) and query letters
+        (a uint8 tensor, query q at qoffsets[q]; None: no row is compared with the query); asynchronous on torch's current stream,
+        nothing comes to the host.  filter: (max_ident_pct, min_cover_pct).  hits: the int64 hit table of nqueries x top x 3 elements,
+        hits_out: the tensor that receives it with target = -1 in the dropped entries -- `hits` itself for in place, None for none.
+        keep: the int32 tensor of at least nqueries x top elements that receives 1 / 0 per entry, None for a fresh one, False for none;
+        nkept: the int64 tensor of at least nqueries elements that receives the rows kept, None for a fresh one, False for none.
+        Returns (keep, nkept, hits_out), None where there is none."""
+        t = self.torch
+        dev = f"cuda:{self.device}"
+        qoffs = np.ascontiguousarray(qoffsets, np.int64).reshape(-1)
+        if len(qoffs) == 0:
+            qoffs = np.zeros(1, np.int64)
+        nq, top = len(qoffs) - 1, int(top)
+        n = nq * max(0, top)
+        ncols = int(qoffs[-1] - qoffs[0]) * max(0, top)
+        if d_cols is not None and (d_cols.dtype != t.uint8 or not d_cols.is_contiguous() or d_cols.numel() < ncols):
+            raise ValueError(f"d_cols must be a contiguous uint8 tensor of at least {ncols} elements")
+        if d_queries is not None and (d_queries.dtype != t.uint8 or not d_queries.is_contiguous() or d_queries.numel() < int(qoffs[-1])):
+            raise ValueError(f"d_queries must be a contiguous uint8 tensor of at least {int(qoffs[-1])} elements")
+        for x, what in ((hits, "hits"), (hits_out, "hits_out")):
+            if x is not None and (x.dtype != t.int64 or not x.is_contiguous() or x.numel() < n * 3):
+                raise ValueError(f"{what} must be a contiguous int64 tensor of at least {nq} x {top} x 3 elements")
+        if keep is None:
+            keep = t.empty(max(1, n), dtype=t.int32, device=dev)
+        elif keep is False:
+            keep = None
+        if keep is not None and (keep.dtype != t.int32 or not keep.is_contiguous() or keep.numel() < n):
+            raise ValueError(f"keep must be a contiguous int32 tensor of at least {n} elements")
+        if nkept is None:
+            nkept = t.empty(max(1, nq), dtype=t.int64, device=dev)
+        elif nkept is False:
+            nkept = None
+        if nkept is not None and (nkept.dtype != t.int64 or not nkept.is_contiguous() or nkept.numel() < nq):
+            raise ValueError(f"nkept must be a contiguous int64 tensor of at least {nq} elements")
+        f = _msa_filter(filter)
+        _check(lib().sw_msa_filter_device(self._h, d_cols.data_ptr() if d_cols is not None else None,
+                                          d_queries.data_ptr() if d_queries is not None else None, qoffs.ctypes.data, nq, top, ctypes.byref(f),
+                                          hits.data_ptr() if hits is not None else None, hits_out.data_ptr() if hits_out is not None else None,
+                                          keep.data_ptr() if keep is not None else None, nkept.data_ptr() if nkept is not None else None,
+                                          self._stream()))
+        return keep, nkept, hits_out
 
     def prepare_db(self, db, offsets=None) -> Database:
         """A prepared database (sw_db_create) for Database.search_affine.  db: a list of sequences, a (packed, offsets) pair, or --

@@ -103,6 +103,11 @@ int sw_set_option(sw_ctx* c, const char* name, int64_t v) {
         c->opt_search_results_mib = v;
         return SW_OK;
     }
+    if (!strcmp(name, "msa_filter_workspace_mib")) {
+        if (v < swp::kMsaFilterMinMib || v > (1ll << 20)) { set_err("msa_filter_workspace_mib must be %lld (one query of top 4096) .. 2^20", (long long)swp::kMsaFilterMinMib); return SW_EINVAL; }
+        c->opt_msa_filter_workspace_mib = v;
+        return SW_OK;
+    }
     if (!strcmp(name, "search_pairs_chunk")) {
         if (v < 1 || v > swp::kSearchPairsChunkMax) { set_err("search_pairs_chunk must be 1..2^31 - 1"); return SW_EINVAL; }
         c->opt_search_pairs_chunk = v;
@@ -203,6 +208,9 @@ int64_t sw_get_option(sw_ctx* c, const char* name) {
     if (!strcmp(name, "last_top_pairs_kernel")) return c->last_top_pairs_kernel;
     if (!strcmp(name, "last_pssm_hits_launches")) return c->last_pssm_hits_launches;
     if (!strcmp(name, "last_msa_hits_launches")) return c->last_msa_hits_launches;
+    if (!strcmp(name, "msa_filter_workspace_mib")) return c->opt_msa_filter_workspace_mib;
+    if (!strcmp(name, "last_msa_filter_launches")) return c->last_msa_filter_launches;
+    if (!strcmp(name, "last_msa_filter_chunks")) return c->last_msa_filter_chunks;
     if (!strcmp(name, "last_pssm_weights_launches")) return c->last_pssm_weights_launches;
     if (!strcmp(name, "last_pssm_weights_tiles")) return c->last_pssm_weights_tiles;
     if (!strcmp(name, "search_pairs_chunk")) return c->opt_search_pairs_chunk;

@@ -1028,6 +1028,45 @@ int sw_db_msa_from_hits(sw_ctx* c, const sw_db* db, const char* d_queries, const
     return SW_OK;
 }
 
+// The filter of the column rows of the call above (csrc/sw_msa_filter.hip).  The host checks the arguments, plans (swp::plan_msa_filter)
+// and uploads the offsets through the small table of the calls above; per chunk of queries the pair launch fills the bit planes of the
+// workspace and the greedy launch turns them into the outputs.  Needs no handle: the column rows hold the targets' letters.
+int sw_msa_filter_device(sw_ctx* c, const char* d_cols, const char* d_queries, const int64_t* qoffsets, int64_t nqueries, int64_t top,
+                         const sw_msa_filter* filter, const sw_hit* d_hits, sw_hit* d_hits_out, int32_t* d_keep, int64_t* d_nkept, void* stream_) {
+    const char* who = "sw_msa_filter_device";
+    if (!c) { set_err("%s: NULL pointer", who); return SW_EINVAL; }
+    if (int rc = swh::check_msa_filter(who, qoffsets, nqueries, top, d_cols, filter, d_hits, d_hits_out, d_keep)) return rc;
+    c->last_msa_filter_launches = c->last_msa_filter_chunks = 0;   // (a call that launches no kernel reports none)
+    if (nqueries == 0) return SW_OK;
+    hipStream_t stream = (hipStream_t)stream_;
+    HIP_TRY(hipSetDevice(c->device));
+    swp::MsaFilterJob fj;
+    fj.nqueries = nqueries; fj.top = top; fj.budget_bytes = c->opt_msa_filter_workspace_mib << 20;
+    const swp::MsaFilterPlan plan = swp::plan_msa_filter(fj);
+    DevOrder order(c, stream, false);
+    if (order.rc) return order.rc;
+    if (int rc = c->d_msafilt.grow((size_t)(plan.queries_per_chunk * plan.query_words), stream)) return rc;
+    HitsCallTable tab;
+    if (int rc = upload_hits_call_table(who, c, stream, nullptr, nullptr, 0, nullptr, qoffsets, nqueries, &tab)) return rc;
+    swk::MsaFilterParams kp;
+    memset(&kp, 0, sizeof kp);
+    kp.cols = (const unsigned char*)d_cols; kp.queries = (const unsigned char*)d_queries; kp.qoffs = tab.qoffs; kp.col0 = qoffsets[0];
+    kp.top = top; kp.blocks = plan.blocks; kp.tiles_per_query = plan.tiles_per_query; kp.query_words = plan.query_words;
+    kp.ws = c->d_msafilt;
+    kp.max_ident_pct = filter->max_ident_pct; kp.min_cover_pct = filter->min_cover_pct;
+    kp.hits = d_hits; kp.hits_out = d_hits_out; kp.keep = d_keep; kp.nkept = d_nkept;
+    for (int64_t ch = 0; ch < plan.chunks; ++ch) {
+        const bool last = ch == plan.chunks - 1;
+        kp.q0 = ch * plan.queries_per_chunk; kp.nq = last ? plan.last_queries : plan.queries_per_chunk;
+        hipLaunchKernelGGL(swk::sw_msa_filter_pairs, dim3((unsigned)(last ? plan.last_pair_grid : plan.pair_grid)), dim3(256), 0, stream, kp);
+        HIP_TRY(hipGetLastError());
+        hipLaunchKernelGGL(swk::sw_msa_filter_greedy, dim3((unsigned)(last ? plan.last_greedy_grid : plan.greedy_grid)), dim3(256), 0, stream, kp);
+        HIP_TRY(hipGetLastError());
+    }
+    c->last_msa_filter_launches = plan.launches; c->last_msa_filter_chunks = plan.chunks;
+    return SW_OK;
+}
+
 // The scores of a device pair list (csrc/sw_search_pairs.hip).  Per call the host checks and plans the QUERIES (O(nqueries)) against the
 // handle's longest target; the pairs and the targets' offsets are read on the device only.  One memset zeroes the call's results up
 // front -- the pairs that never become an item keep it, the binning writes no result --, then per group one profile launch and per

@@ -29,6 +29,8 @@ SW_HIDDEN int check_pssm_weighting(const char* who, const sw_pssm_weighting* wt,
                                    int64_t ops_cap, const void* weights);                             // sw_hits_host.cpp
 SW_HIDDEN int check_msa(const char* who, const int64_t* qoffsets, int64_t nqueries, int64_t top, const void* hits, const void* aln, const void* ops,
                         int64_t ops_cap, const void* cols, const void* rows, const void* a3m, int64_t a3m_cap, const void* a3m_bytes);   // sw_hits_host.cpp
+SW_HIDDEN int check_msa_filter(const char* who, const int64_t* qoffsets, int64_t nqueries, int64_t top, const void* cols, const sw_msa_filter* filter,
+                               const void* hits, const void* hits_out, const void* keep);            // sw_hits_host.cpp
 SW_HIDDEN void pssm_update_table(const sw_submat* sub, const char* letters, int n, int8_t* S);        // sw_hits_host.cpp
 SW_HIDDEN int check_targets(const char* who, int64_t qlen, const int64_t* offsets, int64_t ntargets, int64_t* maxlen_out, int64_t* nonempty_out);
 }
@@ -270,6 +272,11 @@ struct SW_HIDDEN sw_ctx {
     // d_phtab and the two pinned copies above, in the same turns
     Workspace<long long> d_msasum;
     int64_t last_msa_hits_launches = 0;
+    // the filter of the column rows (sw_msa_filter_device): the bit planes of a chunk of queries, at most "msa_filter_workspace_mib"; the
+    // query offsets go through d_phtab and the two pinned copies above, in the same turns
+    Workspace<unsigned long long> d_msafilt;
+    int64_t opt_msa_filter_workspace_mib = 256;
+    int64_t last_msa_filter_launches = 0, last_msa_filter_chunks = 0;
     // ---- placement of the output matrices (sw_place.hip)
     int64_t opt_place_hold_gib = 0;     // sw_alloc_outputs: GiB a pair of small matrices may hold beside itself where no plain candidate is good (0: none)
     int64_t opt_place_budget_ms = 1500; // sw_alloc_outputs: time the search for a P in another class of the HBM may take

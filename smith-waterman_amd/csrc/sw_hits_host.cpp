@@ -1,5 +1,6 @@
 // sw_hits_host.cpp -- the CPU legs of the calls that read a hit table's alignments (sw_pssm_from_hits_host, sw_pssm_hit_weights_host,
-// sw_msa_from_hits_host; include/swhip.h states their rules), the argument checks they share with the device calls, and sw_write_a3m.
+// sw_msa_from_hits_host; include/swhip.h states their rules) and of the filter of the column rows (sw_msa_filter_host), the argument
+// checks they share with the device calls, and sw_write_a3m.
 // What a USED ENTRY is and how its ops are WALKED stands here once, for all three legs.  Plain C++ that needs nothing of the library but
 // the header and the error text: a stand-alone program can compile this file alone (tests/pssm_hits_driver.cpp does, under the address
 // and undefined-behaviour sanitizers).
@@ -19,6 +20,8 @@ __attribute__((visibility("hidden"))) int check_pssm_weighting(const char* who, 
 __attribute__((visibility("hidden"))) int check_msa(const char* who, const int64_t* qoffsets, int64_t nqueries, int64_t top, const void* hits, const void* aln,
                                                     const void* ops, int64_t ops_cap, const void* cols, const void* rows, const void* a3m, int64_t a3m_cap,
                                                     const void* a3m_bytes);
+__attribute__((visibility("hidden"))) int check_msa_filter(const char* who, const int64_t* qoffsets, int64_t nqueries, int64_t top, const void* cols,
+                                                           const sw_msa_filter* filter, const void* hits, const void* hits_out, const void* keep);
 __attribute__((visibility("hidden"))) void pssm_update_table(const sw_submat* sub, const char* letters, int n, int8_t* S);
 }  // namespace swh
 
@@ -85,6 +88,25 @@ int check_msa(const char* who, const int64_t* qoffsets, int64_t nqueries, int64_
     if (!rows && (a3m || a3m_bytes)) { set_err("%s: A3M bytes or their total without the row table", who); return SW_EINVAL; }
     if (a3m && !a3m_bytes) { set_err("%s: A3M bytes without a place for their total", who); return SW_EINVAL; }
     if (a3m_cap < 0) { set_err("%s: a3m_cap = %lld is negative", who, (long long)a3m_cap); return SW_EINVAL; }
+    return SW_OK;
+}
+
+// What sw_msa_filter_device and sw_msa_filter_host check: the query offsets (the rule of check_msa), top, the rule and the outputs.
+int check_msa_filter(const char* who, const int64_t* qoffsets, int64_t nqueries, int64_t top, const void* cols, const sw_msa_filter* filter,
+                     const void* hits, const void* hits_out, const void* keep) {
+    if (!qoffsets) { set_err("%s: NULL query offsets", who); return SW_EINVAL; }
+    if (nqueries < 0) { set_err("%s: negative query count", who); return SW_EINVAL; }
+    if (qoffsets[0] < 0) { set_err("%s: qoffsets[0] = %lld is negative", who, (long long)qoffsets[0]); return SW_EINVAL; }
+    for (int64_t q = 0; q < nqueries; ++q) {
+        const int64_t len = qoffsets[q + 1] - qoffsets[q];
+        if (len < 1 || len > kMaxDim) { set_err("%s: query %lld has length %lld, out of range 1..%lld", who, (long long)q, (long long)len, (long long)kMaxDim); return SW_EINVAL; }
+    }
+    if (top < 1 || top > SW_TOP_MAX) { set_err("%s: top = %lld is out of range 1..%d", who, (long long)top, SW_TOP_MAX); return SW_EINVAL; }
+    if (!cols || !filter) { set_err("%s: NULL column rows or filter rule", who); return SW_EINVAL; }
+    if (filter->max_ident_pct < 1 || filter->max_ident_pct > 101) { set_err("%s: max_ident_pct = %d is out of range 1..101", who, filter->max_ident_pct); return SW_EINVAL; }
+    if (filter->min_cover_pct < 0 || filter->min_cover_pct > 100) { set_err("%s: min_cover_pct = %d is out of range 0..100", who, filter->min_cover_pct); return SW_EINVAL; }
+    if (!keep && !hits_out) { set_err("%s: no output: the keep table and the filtered hit table are both NULL", who); return SW_EINVAL; }
+    if (hits_out && !hits) { set_err("%s: a filtered hit table without the hit table it is made from", who); return SW_EINVAL; }
     return SW_OK;
 }
 
@@ -340,6 +362,46 @@ int sw_msa_from_hits_host(const char* queries, const int64_t* qoffsets, int64_t 
         }
     }
     if (a3m_bytes) *a3m_bytes = off;
+    return SW_OK;
+}
+
+// The CPU leg of sw_msa_filter_device: the rule of include/swhip.h restated, row by row in rank order; a row is compared with the rows
+// kept before it only.  Everything is checked before the first byte is written; hits_out may be hits.
+int sw_msa_filter_host(const char* cols, const char* queries, const int64_t* qoffsets, int64_t nqueries, int64_t top, const sw_msa_filter* filter,
+                       const sw_hit* hits, sw_hit* hits_out, int32_t* keep, int64_t* nkept) {
+    const char* who = "sw_msa_filter_host";
+    if (int rc = swh::check_msa_filter(who, qoffsets, nqueries, top, cols, filter, hits, hits_out, keep)) return rc;
+    const int32_t ident = filter->max_ident_pct, cover = filter->min_cover_pct;
+    std::vector<int64_t> kept;   // the rows of the query at hand that are kept so far
+    for (int64_t q = 0; q < nqueries; ++q) {
+        const int64_t g0 = qoffsets[q], qlen = qoffsets[q + 1] - g0;
+        const char* rows = cols + (g0 - qoffsets[0]) * top;
+        kept.clear();
+        for (int64_t r = 0; r < top; ++r) {
+            const char* row = rows + r * qlen;
+            int32_t n = 0, sameq = 0;
+            int64_t lo = qlen, hi = 0;   // the row's letters lie in [lo, hi): nothing outside counts in same or sameq
+            for (int64_t j = 0; j < qlen; ++j)
+                if (row[j] != '-') { ++n; lo = std::min(lo, j); hi = j + 1; }
+            if (queries)
+                for (int64_t j = lo; j < hi; ++j) sameq += (row[j] != '-') & (row[j] == queries[g0 + j]);
+            bool k = n >= 1 && (int64_t)100 * n >= (int64_t)cover * qlen && (!queries || 100 * sameq < ident * n);
+            for (size_t i = 0; k && i < kept.size(); ++i) {
+                const char* other = rows + kept[i] * qlen;
+                int32_t same = 0;
+                for (int64_t j = lo; j < hi; ++j) same += (row[j] != '-') & (row[j] == other[j]);
+                k = 100 * same < ident * n;
+            }
+            if (k) kept.push_back(r);
+            const int64_t e = q * top + r;
+            if (keep) keep[e] = k;
+            if (hits_out) {
+                const sw_hit h = hits[e];
+                hits_out[e] = sw_hit{k ? h.target : -1, h.max_pos, h.max_score};
+            }
+        }
+        if (nkept) nkept[q] = (int64_t)kept.size();
+    }
     return SW_OK;
 }
 

@@ -240,6 +240,24 @@ __global__ void sw_msa_scan_chunks(MsaHitsParams p);
 __global__ void sw_msa_scan_top(MsaHitsParams p);
 __global__ void sw_msa_rows(MsaHitsParams p);
 
+// sw_msa_filter.hip: the filter of the column rows (sw_msa_filter_device), as swp::plan_msa_filter cuts it, for the queries
+// q0 .. q0 + nq - 1 of one chunk.  sw_msa_filter_pairs: one workgroup per (query, tile), the bit planes of the workspace;
+// sw_msa_filter_greedy: one workgroup per query, keep in rank order and the outputs.
+struct MsaFilterParams {
+    const unsigned char* cols;                   // the column rows of sw_db_msa_from_hits
+    const unsigned char* queries;                // the query letters at qoffs[q] + j, or NULL: no row is compared with the query
+    const int64_t* qoffs; int64_t col0;          // device copy of the offsets; col0 = qoffsets[0]: cols start at the first query's first column
+    int64_t q0, nq;                              // the chunk's queries
+    int64_t top, blocks, tiles_per_query, query_words;
+    unsigned long long* ws;                      // nq x query_words: query q's planes at (q - q0) x query_words
+    int max_ident_pct, min_cover_pct;
+    const sw_hit* hits; sw_hit* hits_out;        // nqueries x top, or NULL together / hits_out alone NULL
+    int* keep;                                   // nqueries x top, or NULL
+    int64_t* nkept;                              // nqueries, or NULL
+};
+__global__ void sw_msa_filter_pairs(MsaFilterParams p);
+__global__ void sw_msa_filter_greedy(MsaFilterParams p);
+
 // sw_search_pairs.hip: the scores of a device list of (query, target) pairs (sw_db_search_affine_pairs).  Per (chunk of the list, group
 // of queries) two binning launches turn the usable pairs into work items, one list per class, heaviest bucket first
 // (swp::plan_search_pairs); one launch of sw_search_affine_pairs_wave<C> per class scores them.

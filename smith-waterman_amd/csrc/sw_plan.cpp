@@ -893,6 +893,28 @@ MsaHitsPlan plan_msa_hits(const MsaHitsJob& j) {
     return p;
 }
 
+MsaFilterPlan plan_msa_filter(const MsaFilterJob& j) {
+    MsaFilterPlan p;
+    const int64_t top = std::clamp<int64_t>(j.top, 1, 4096);
+    p.blocks = (top + kMsaFilterTile - 1) / kMsaFilterTile;
+    p.tiles_per_query = p.blocks * (p.blocks + 1) / 2;
+    p.chunk_cols = (int)kMsaFilterChunkCols;
+    p.query_words = msa_filter_query_words(top);
+    p.query_bytes = 8 * p.query_words;
+    if (j.nqueries < 1) return p;
+    p.queries_per_chunk = std::clamp<int64_t>(j.budget_bytes / p.query_bytes, 1, j.nqueries);
+    p.chunks = (j.nqueries + p.queries_per_chunk - 1) / p.queries_per_chunk;
+    p.workspace_bytes = p.queries_per_chunk * p.query_bytes;
+    // (queries x tiles stays inside 63 bits: at most 2080 tiles)
+    p.pair_grid = std::min(p.queries_per_chunk * p.tiles_per_query, kPssmHitsGridMax);
+    p.greedy_grid = std::min(p.queries_per_chunk, kPssmHitsGridMax);
+    p.last_queries = j.nqueries - (p.chunks - 1) * p.queries_per_chunk;
+    p.last_pair_grid = std::min(p.last_queries * p.tiles_per_query, kPssmHitsGridMax);
+    p.last_greedy_grid = std::min(p.last_queries, kPssmHitsGridMax);
+    p.launches = (int)std::min<int64_t>(2 * p.chunks, INT32_MAX);
+    return p;
+}
+
 void align_schedule(const int64_t* offsets, const int64_t* hits, int64_t nhits, swk::SearchItem* items) {
     std::vector<int64_t> order((size_t)nhits);
     for (int64_t h = 0; h < nhits; ++h) order[(size_t)h] = h;

@@ -613,6 +613,52 @@ struct MsaHitsPlan {
 
 MsaHitsPlan plan_msa_hits(const MsaHitsJob& job);
 
+// ---- the filter of a hit alignment (sw_msa_filter_device; sw_msa_filter.hip).  Two launches of 256 threads per chunk of queries.
+// Rows go in blocks of kMsaFilterTile = 64: `blocks` per query.  Per query the workspace holds blocks + 1 planes of blocks x 64 64-bit
+// words: word r of plane c has bit i set where row r is redundant to row 64 c + i (planes c <= r / 64 only; bit i of a word on the
+// diagonal only for 64 c + i < r), word r of the last plane is the row's own test (cover, query).  A plane is indexed by the row, so
+// the 64 lanes of a wave store and load neighbouring words.
+// Pair launch: one workgroup per (query, tile); tile t of the tiles_per_query = blocks (blocks + 1) / 2 is (row block rb, compared
+// block cb <= rb) in row-major order of the triangle (msa_filter_tile); every pair r' < r lies in exactly one tile, (r / 64, r' / 64).
+// The tiles on the diagonal also compare their rows with the query.  A tile takes its rows kMsaFilterChunkCols columns at a time.
+// Greedy launch: one workgroup per query.
+// Chunks: queries_per_chunk queries, as many as fit budget_bytes ("msa_filter_workspace_mib"), at least one -- one query is never
+// refused --, so the workspace holds at most max(budget_bytes, one query's bytes).  Grids: walked in strides of at most
+// kPssmHitsGridMax workgroups.
+constexpr int64_t kMsaFilterTile = 64;
+constexpr int64_t kMsaFilterChunkCols = 64;
+constexpr int64_t msa_filter_query_words(int64_t top) {
+    const int64_t blocks = (top + kMsaFilterTile - 1) / kMsaFilterTile;
+    return (blocks + 1) * blocks * kMsaFilterTile;
+}
+constexpr int64_t kMsaFilterMinMib = (8 * msa_filter_query_words(4096) + (1 << 20) - 1) >> 20;   // one query of top 4096: 3
+// tile t -> (rb, cb), cb <= rb: t = rb (rb + 1) / 2 + cb
+constexpr void msa_filter_tile(int64_t t, int& rb, int& cb) {
+    int r = 0;
+    while ((int64_t)(r + 1) * (r + 2) / 2 <= t) ++r;
+    rb = r;
+    cb = (int)(t - (int64_t)r * (r + 1) / 2);
+}
+
+struct MsaFilterJob {
+    int64_t nqueries = 0, top = 1;           // top: 1..SW_TOP_MAX
+    int64_t budget_bytes = 256ll << 20;      // "msa_filter_workspace_mib"
+};
+
+struct MsaFilterPlan {
+    int64_t blocks = 0;                      // row blocks of a query
+    int64_t tiles_per_query = 0;             // the triangle with its diagonal; the diagonal tiles take the query column
+    int chunk_cols = 0;                      // columns a tile stages at a time
+    int64_t query_words = 0, query_bytes = 0;   // a query's share of the workspace
+    int64_t queries_per_chunk = 0, chunks = 0;
+    int64_t workspace_bytes = 0;             // queries_per_chunk queries
+    int64_t pair_grid = 0, greedy_grid = 0;  // of a whole chunk (0: no query)
+    int64_t last_queries = 0, last_pair_grid = 0, last_greedy_grid = 0;   // of the last chunk
+    int launches = 0;                        // kernel launches of the call ("last_msa_filter_launches")
+};
+
+MsaFilterPlan plan_msa_filter(const MsaFilterJob& job);
+
 // ---- alignment of chosen hits under affine scoring (sw_align_affine_device): sw_align_affine_wave<C> for C = 4, 8, 16, its index in
 // kAlignAffine (sw_api_search.hip, which checks its order against it at compile time)
 constexpr int kAlignAffineKernels = 3;
