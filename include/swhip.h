@@ -823,6 +823,76 @@ int  sw_msa_filter_device(sw_ctx* ctx, const char* d_cols, const char* d_queries
 int  sw_msa_filter_host(const char* cols, const char* queries, const int64_t* qoffsets, int64_t nqueries, int64_t top,
                         const sw_msa_filter* filter, const sw_hit* hits, sw_hit* hits_out, int32_t* keep, int64_t* nkept);
 
+/* The STATISTICS of a many-query search (csrc/sw_score_hist.hip, csrc/sw_score_stats.cpp): E-values from the scores of the search
+ * itself, per query, as SSEARCH estimates them -- this library takes any alphabet, table, gap costs and its own PSSMs, so no tabulated
+ * Karlin-Altschul constants exist for it.  Nearly every target is unrelated to the query; the unrelated targets' score grows linearly
+ * with the log of the target's length and follows an extreme-value law around that line.  Four steps:
+ * 1. THE HISTOGRAM (device and host leg, integers, the same bytes on both and on every run).  Per query SW_HIST_CLASSES x SW_HIST_BINS
+ *    uint32 counters, 40 KiB: d_hist[(q x 40 + c) x 256 + s] is the number of NON-EMPTY targets k with class(len_k) == c and
+ *    bin(max_score) == s.  class(1) = 0; for L >= 2 with e = floor(log2 L): class(L) = 2 e + ((L >> (e - 1)) & 1) -- half octaves of
+ *    the length, L < 2^20 gives c <= 39 (class 1 holds no length).  bin(v) = min(max(v, 0) >> shift, 255), shift 0..SW_HIST_SHIFT_MAX:
+ *    bin 255 collects everything at or above it, a negative entry goes to bin 0.  Empty targets are counted nowhere.
+ *   sw_score_hist_device  over any query-major nqueries x ntargets table of sw_result on the device; the lengths come from the handle's
+ *             device copy of the offsets.  EVERY counter of d_hist is written (the call zeroes the buffer on the stream); nothing
+ *             outside d_hist is written.  Asynchronous, no host round trip, host work O(1).  One launch (swp::plan_score_hist): one
+ *             workgroup per (query, slice of targets) with a private histogram in LDS, LDS integer adds, then one global uint32 atomic
+ *             add per non-zero counter.  The option "score_hist_copies" (0, the default: the planner's choice; 1 / 2 / 4) sets the LDS
+ *             histograms per workgroup; "last_score_hist_launches" and "last_score_hist_slices" report the last call.
+ *             SW_EINVAL before any launch: NULL pointers, nqueries < 0, shift out of range, a handle of another context's device,
+ *             ntargets >= 2^31.  nqueries == 0 launches nothing; ntargets == 0 only zeroes.
+ *   sw_score_hist_host    the CPU leg from host memory; also refuses a target length outside 0..2^20 - 1.
+ * 2. INSIDE THE BOUNDED-MEMORY SEARCHES.  sw_db_search_affine_top_stats / sw_db_search_pssm_top_stats are sw_db_search_affine_top /
+ *    sw_db_search_pssm_top with `shift` and `d_hist` (device, nqueries x 40 x 256 uint32): after the search of each chunk of queries, one
+ *    histogram launch runs over the chunk's rows while they are in the workspace, then the selection as before.  d_hits and d_nhits are
+ *    byte for byte those of the plain call; d_hist is what sw_score_hist_device gives on the full table, which never exists.
+ *    SW_EINVAL in addition: NULL d_hist, shift out of range.  OUT OF SCOPE: the prefiltered search (sw_db_search_affine_top_prefiltered)
+ *    scores only the pairs above a cut-off, a censored sample this fit is not made for.
+ * 3. THE FIT AND THE E-VALUE (host only, double, ONE implementation for every path; floating point, so deliberately not duplicated on
+ *    the device: the bit-for-bit rule covers steps 1, 2 and 4).  A caller brings the histograms to the host: 40 KiB per query and one
+ *    synchronisation per round.  Per query: a cell (c, s) with s < 255 has x = c, y = s x 2^shift + (2^shift - 1) / 2 and its count as
+ *    weight w; bin 255 never enters a fit (n_censored); n_db is the sum of ALL counters.  One round: W = SUM w, the weighted means mx,
+ *    my, b = SUM w (x - mx)(y - my) / SUM w (x - mx)^2 (0 where the denominator is 0), a = my - b mx, r = y - a - b x, sigma^2 =
+ *    SUM w r^2 / (W - 2) (sigma = 0 where W <= 2).  The first round takes every cell; three more rounds each give every cell its full
+ *    count again, then zero the cells whose z = r / sigma under the PREVIOUS round's fit is > 5 or < -4 (not cumulative; a previous
+ *    round without sigma > 0 drops nothing), and refit.  valid = 1 iff the last W >= 30 and sigma > 0; n_fit is the last W.
+ *   sw_score_evalue  with z = (score - a - b class(len)) / sigma and gamma Euler's constant:
+ *             E = n_db (1 - exp(-exp(-(pi / sqrt 6) z - gamma))), computed as -n_db expm1(-exp(...)); NaN for an invalid fit, a NULL
+ *             fit or target_len < 1.
+ *   sw_score_thresholds  T[q x 40 + c] = the smallest integer score with E <= evalue in class c: ceil(a + b c + sigma z0) with
+ *             z0 = -(sqrt 6 / pi)(ln(-ln(1 - evalue / n_db)) + gamma), then held against sw_score_evalue itself so that
+ *             E(T) <= evalue < E(T - 1) as computed.  T = 0 where evalue >= n_db or the fit is invalid: a tiny database drops
+ *             nothing.  SW_EINVAL: NULL pointers, nqueries < 0, evalue not above 0.
+ * 4. THE THRESHOLDS ON A HIT TABLE (device and host leg, integers, the same bytes).  The shape and the output rules of
+ *    sw_msa_filter_device: keep(q, r) = 1 iff r < clamp(d_nhits[q], 0, top) (NULL d_nhits: all top entries); target, compared unsigned,
+ *    < ntargets, before any load through it; the target is non-empty; max_score >= d_thresholds[q x 40 + class(len)].
+ *    d_hits_out (optional): entry = input entry with target = -1 where keep is 0; d_hits_out == d_hits (in place) is allowed.  d_keep
+ *    (optional): nqueries x top int32 1 / 0, EVERY entry written, usable as unit d_weights.  d_nkept (optional): nqueries int64.  At
+ *    least one of d_keep and d_hits_out.  A dropped entry is not a USED ENTRY of sw_db_pssm_hit_weights, sw_db_pssm_from_hits,
+ *    sw_db_msa_from_hits and the aligners, so per-query, per-length inclusion enters the loop with no signature changed: threshold a
+ *    COPY of the table for the column rows, the filter, the weights and the update, with include_min_score at its minimum.
+ *    Asynchronous, no host round trip, one launch, one workgroup per query.  SW_EINVAL: NULL ctx, db, d_thresholds or d_hits; a handle
+ *    of another context's device; nqueries < 0; top outside 1..SW_TOP_MAX; both outputs NULL; (host leg) NULL offsets, ntargets < 0 or
+ *    >= 2^31, a target length out of range.  nqueries == 0 launches nothing. */
+#define SW_HIST_CLASSES 40
+#define SW_HIST_BINS 256
+#define SW_HIST_SHIFT_MAX 16
+typedef struct { double a, b, sigma; int64_t n_db, n_fit, n_censored; int32_t valid, shift; } sw_score_fit;
+int  sw_score_hist_device(sw_ctx* ctx, const sw_db* db, const sw_result* d_results, int64_t nqueries, int shift, uint32_t* d_hist, void* stream);
+int  sw_score_hist_host(const sw_result* results, int64_t nqueries, const int64_t* offsets, int64_t ntargets, int shift, uint32_t* hist);
+int  sw_db_search_affine_top_stats(sw_ctx* ctx, const sw_db* db, const char* d_queries, const int64_t* qoffsets, int64_t nqueries,
+                                   const sw_affine* scoring, int64_t top, int64_t min_score, sw_hit* d_hits, int64_t* d_nhits, int shift,
+                                   uint32_t* d_hist, void* stream);
+int  sw_db_search_pssm_top_stats(sw_ctx* ctx, const sw_db* db, const int8_t* d_pssm, const int64_t* qoffsets, int64_t nqueries,
+                                 const sw_pssm_scoring* scoring, int64_t top, int64_t min_score, sw_hit* d_hits, int64_t* d_nhits, int shift,
+                                 uint32_t* d_hist, void* stream);
+int  sw_score_fit_hist(const uint32_t* hist, int64_t nqueries, int shift, sw_score_fit* fit);
+double sw_score_evalue(const sw_score_fit* fit, int64_t target_len, int64_t score);
+int  sw_score_thresholds(const sw_score_fit* fit, int64_t nqueries, double evalue, int64_t* thresholds /* nqueries x 40 */);
+int  sw_hits_threshold_device(sw_ctx* ctx, const sw_db* db, const int64_t* d_thresholds, int64_t nqueries, int64_t top, const sw_hit* d_hits,
+                              const int64_t* d_nhits, sw_hit* d_hits_out, int32_t* d_keep, int64_t* d_nkept, void* stream);
+int  sw_hits_threshold_host(const int64_t* offsets, int64_t ntargets, const int64_t* thresholds, int64_t nqueries, int64_t top,
+                            const sw_hit* hits, const int64_t* nhits, sw_hit* hits_out, int32_t* keep, int64_t* nkept);
+
 /* Tables.  sw_submat_match: s[x][y] = x == y ? match : mismatch (matchMissmatchScore, serial_smithW.c:251-256; both must fit int8:
  * the builder returns nothing, so it clamps them to -128..127 -- a caller that takes them from a user checks the range first, as
  * smithW and the Python wrapper do, which refuse such scores).  sw_submat_from_letters: `scores` is n x n, row = query letter, over the n bytes of
@@ -1028,7 +1098,9 @@ int sw_synchronize(sw_ctx* ctx, void* stream);   /* waits for `stream`; reports 
  * "last_search_pairs_packed_items" the two-pair work items the device built (reading it waits for the device); "prefilter_lanes" (settable, 0 or 32) and
  * "last_prefilter_groups", "last_prefilter_launches", "last_prefilter_packed_launches" belong to sw_db_prefilter_ungapped (above);
  * "last_top_pairs_launches" and "last_top_pairs_kernel" describe the last sw_top_hits_pairs_device call, and "search_results_mib" also
- * bounds the pairs_cap of sw_db_search_affine_top_prefiltered (56 bytes per entry).
+ * bounds the pairs_cap of sw_db_search_affine_top_prefiltered (56 bytes per entry); "score_hist_copies" (settable: 0, the default, the
+ * planner's choice, or 1 / 2 / 4) sets the LDS histograms a workgroup of the score histogram keeps, "last_score_hist_launches" and
+ * "last_score_hist_slices" (slices of targets per query) describe the last sw_score_hist_device / _top_stats call.
  * "debug_search_pairs_items_ptr" (an
  * accessor for tests) is the device address of that call's item workspace, which a call leaves as its last (chunk, group) filled it:
  * 24-byte items {int64 start, int64 out, int32 len, int32 entry}, the classes' lists back to back (under "search_pairs_lanes" = 16 the

@@ -85,6 +85,15 @@
   after a warm-up, ALTERNATING; a leg whose warm-up call takes more than 20 s is timed by that call alone (*_calls says how many calls
   stand behind a median).  (b) a weighted iteration (--pssm-weights (b)) beside one with msa_from_hits_device (column rows) and
   msa_filter_device in front of the weights, which with the update then read the filtered table
+  --score-stats: data set (a) only, 64 queries, top 100.  (1) search_affine_top_stats_device beside search_affine_top_device, 7 calls
+  each after a warm-up, wall clock around a synchronised call, ALTERNATING; hits, counts and -- against score_hist_device over the full
+  table -- histograms compared byte for byte (the run fails if they differ).  (2) score_hist_device alone over the full 64 x 200 000
+  table (torch events, median of 20) in GB/s of the table's 24 bytes per entry, beside torch.sum over the same tensor, for the
+  search's own scores and for a table with every score in ONE cell, under "score_hist_copies" 1, 2 and 4.  (3) what a round of
+  --include-evalue adds: D2H of the histograms, score_fit, score_thresholds, H2D of the thresholds, hits_threshold_device.  (4) an
+  iteration (align, update, search) with the inclusion by E-value beside one by raw score, at an E-value no hit misses, so that both
+  build the same matrix and the searches that follow cost the same.  (5) the path a caller had before: D2H of
+  the full table and score_hist_host
 GCUPS = query letters x target letters / time of the call (torch events, median of --reps after --warmup)."""
 import argparse
 import importlib
@@ -138,6 +147,7 @@ def main():
     ap.add_argument("--pssm-weights", action="store_true", help="data set (a) only: the hit weights on the device against the host round trip, and a weighted iteration against the unweighted one")
     ap.add_argument("--msa", action="store_true", help="data set (a) only: the query-anchored alignment of the top 10 / 100 / 4096 hits of 64 queries on the device against the host round trip")
     ap.add_argument("--msa-filter", action="store_true", help="data set (a) only: the filter of the column rows of the top 10 / 100 / 4096 hits of 64 queries on the device against the host round trip, and a weighted iteration with and without it")
+    ap.add_argument("--score-stats", action="store_true", help="data set (a) only: the score histogram inside the top search and alone, the fit's round trip, an iteration by E-value beside one by raw score")
     ap.add_argument("--lanes", action="store_true", help="data set (a) only: 64 queries under search_lanes 32 and 16, alternating, full tables and top 10")
     ap.add_argument("--pairs-lanes", action="store_true", help="data set (a) only: pair lists of all, 10 %% and 1 %% of the cross product under search_pairs_lanes 32 and 16, alternating")
     ap.add_argument("--top", action="store_true", help="data set (a) only: the best 100 targets of 64 queries by the full table and by the selection on the device")
@@ -847,6 +857,120 @@ def main():
         out[f"{P}_identical"] = all(out[f"{P}_top{t}_identical"] for t in (10, 100, 4096))
         db.close()
 
+    def score_stats_leg(packed, offs, nq=64, reps=7, top=100, evalue=1e-3):
+        import time
+        d_db = torch.from_numpy(packed.copy()).to(dev)
+        db = eng.prepare_db(d_db, offs)
+        nt = len(offs) - 1
+        qoffs = np.arange(nq + 1, dtype=np.int64) * args.qlen
+        queries = rng.choice(PROTEIN, int(qoffs[-1])).astype(np.uint8)
+        d_q = torch.from_numpy(queries.copy()).to(dev)
+        scoring = (sub, -11, -1)
+        m, moffs = swamd.pssm_from_queries((queries, qoffs), sub, letters)
+        d_m = torch.from_numpy(m.reshape(-1).copy()).to(dev)
+        pscoring, cap = (letters, -4, 127, -11, -1), 4 * args.qlen
+        P = "score_stats"
+        out[f"{P}_queries"], out[f"{P}_qlen"], out[f"{P}_targets"], out[f"{P}_reps"], out[f"{P}_top"], out[f"{P}_evalue"] = nq, args.qlen, nt, reps, top, evalue
+        cells = nq * swamd.HIST_CLASSES * swamd.HIST_BINS
+        h_plain = (torch.zeros(nq * top * 3, dtype=torch.int64, device=dev), torch.zeros(nq, dtype=torch.int64, device=dev))
+        h_stats = (torch.zeros(nq * top * 3, dtype=torch.int64, device=dev), torch.zeros(nq, dtype=torch.int64, device=dev))
+        d_hist = torch.empty(cells, dtype=torch.int32, device=dev)
+        d_hist2 = torch.empty(cells, dtype=torch.int32, device=dev)
+        d_thr = torch.empty(nq * swamd.HIST_CLASSES, dtype=torch.int64, device=dev)
+        d_inc = torch.empty(nq * top * 3, dtype=torch.int64, device=dev)
+        state = {}
+
+        def wall(fn):                                                        # wall clock around a synchronised call
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            fn()
+            torch.cuda.synchronize()
+            return (time.perf_counter() - t0) * 1e3
+
+        def alternate(legs):
+            ms = {k: [] for k in legs}
+            for k in legs:
+                wall(legs[k])                                                # warm-up
+            for _ in range(reps):                                            # alternating: a drift of the device shows in all alike
+                for k in legs:
+                    ms[k].append(wall(legs[k]))
+            for k in legs:
+                out[f"{P}_{k}_ms"] = round(float(np.median(ms[k])), 4)
+                out[f"{P}_{k}_range_ms"] = [round(min(ms[k]), 4), round(max(ms[k]), 4)]
+
+        # (1) the histogram inside the bounded-memory search
+        alternate({"top": lambda: db.search_affine_top_device(d_q, qoffs, scoring, top, 1, out=h_plain),
+                   "top_stats": lambda: db.search_affine_top_stats_device(d_q, qoffs, scoring, top, 1, 0, out=h_stats, hist=d_hist)})
+        out[f"{P}_top_stats_over_top"] = round(out[f"{P}_top_stats_ms"] / out[f"{P}_top_ms"], 4)
+        out[f"{P}_top_chunks"] = eng.get_option("last_search_top_chunks")
+        out[f"{P}_hist_slices"] = eng.get_option("last_score_hist_slices")
+        # (2) the histogram alone over the full table, beside a plain read of it
+        table = db.search_affine_device(d_q, qoffs, scoring)
+        one_cell = table.clone()
+        one_cell[:, :, 1] = 41
+        d_db1 = torch.zeros(1, dtype=torch.uint8, device=dev)
+        db1 = eng.prepare_db(d_db1, np.arange(nt + 1, dtype=np.int64) * 150)   # ... every target in one length class
+        table_bytes = table.numel() * 8
+        out[f"{P}_table_bytes"] = table_bytes
+        for name, t_, h_ in (("search", table, db), ("one_cell", one_cell, db1)):
+            for copies in (1, 2, 4):
+                eng.set_option("score_hist_copies", copies)
+                ms = timed(lambda: eng.score_hist_device(h_, t_.view(-1), nq, 0, hist=d_hist2), 2, 20)
+                out[f"{P}_hist_{name}_copies{copies}_ms"] = round(ms, 4)
+                out[f"{P}_hist_{name}_copies{copies}_gbs"] = round(table_bytes / ms / 1e6, 1)
+            eng.set_option("score_hist_copies", 0)
+            ms = timed(lambda: eng.score_hist_device(h_, t_.view(-1), nq, 0, hist=d_hist2), 2, 20)
+            out[f"{P}_hist_{name}_ms"], out[f"{P}_hist_{name}_gbs"] = round(ms, 4), round(table_bytes / ms / 1e6, 1)
+        ms = timed(lambda: torch.sum(table), 2, 20)
+        out[f"{P}_torch_sum_ms"], out[f"{P}_torch_sum_gbs"] = round(ms, 4), round(table_bytes / ms / 1e6, 1)
+        eng.score_hist_device(db, table.view(-1), nq, 0, hist=d_hist2)
+        torch.cuda.synchronize()
+        out[f"{P}_identical"] = bool(torch.equal(d_hist.view(-1), d_hist2.view(-1)) and torch.equal(h_plain[0], h_stats[0]) and torch.equal(h_plain[1], h_stats[1]))
+        one = eng.score_hist_device(db1, one_cell.view(-1), nq, 0).cpu().numpy().view(np.uint32)
+        out[f"{P}_one_cell_count"] = int(one[:, swamd.length_class(150), 41].min())
+        out[f"{P}_identical"] = bool(out[f"{P}_identical"] and (one.sum(axis=(1, 2)) == nt).all() and out[f"{P}_one_cell_count"] == nt)
+
+        # (3) what a round of the inclusion by E-value adds, and (5) the path a caller had before
+        def fit_round_trip(evalue=evalue):
+            h = d_hist.cpu().numpy().view(np.uint32).reshape(nq, swamd.HIST_CLASSES, swamd.HIST_BINS)
+            state["fit"] = swamd.score_fit(h, 0)
+            state["thr"] = swamd.score_thresholds(state["fit"], evalue)
+            d_thr.copy_(torch.from_numpy(state["thr"].reshape(-1)))
+            db.hits_threshold_device(d_thr, nq, top, h_stats[0], h_stats[1], hits_out=d_inc, keep=False, nkept=False)
+
+        def host_histogram():
+            state["host_hist"] = swamd.score_hist_host(table.cpu().numpy(), offs, 0)
+
+        alternate({"fit_round_trip": fit_round_trip, "host_histogram": host_histogram})
+        out[f"{P}_identical"] = bool(out[f"{P}_identical"] and (state["host_hist"] == d_hist.cpu().numpy().view(np.uint32).reshape(state["host_hist"].shape)).all())
+        out[f"{P}_fit_valid"] = int(state["fit"]["valid"].sum())
+        out[f"{P}_fit_b_median"], out[f"{P}_fit_sigma_median"] = round(float(np.median(state["fit"]["b"])), 3), round(float(np.median(state["fit"]["sigma"])), 3)
+        out[f"{P}_kept_at_evalue"] = int((d_inc.view(nq, top, 3)[:, :, 0] >= 0).sum().item())
+        # (4) an iteration by E-value beside one by raw score
+        hits, nhits = db.search_pssm_top_device(d_m, moffs, pscoring, top, 1)
+        aln, ops = db.align_pssm_hits_device(d_m, moffs, pscoring, hits, nhits, ops_cap=cap)
+        d_out = torch.empty_like(d_m)
+        h2 = (torch.zeros_like(hits), torch.zeros_like(nhits))
+        least = -(1 << 63)
+
+        def score_iteration():
+            db.align_pssm_hits_device(d_m, moffs, pscoring, hits, nhits, ops_cap=cap, out=(aln, ops))
+            db.pssm_from_hits_device(d_m, moffs, pscoring, (sub, 10, 1), hits, nhits, aln, ops, cap, out=d_out)
+            db.search_pssm_top_device(d_out, moffs, pscoring, top, 1, out=h2)
+
+        def evalue_iteration():                                              # the round's histogram is that of the search before it;
+            fit_round_trip(1e12)                                             # an E-value no hit misses: both iterations build the same matrix
+            db.align_pssm_hits_device(d_m, moffs, pscoring, hits, nhits, ops_cap=cap, out=(aln, ops))
+            db.pssm_from_hits_device(d_m, moffs, pscoring, (sub, 10, least), d_inc.view(nq, top, 3), nhits, aln, ops, cap, out=d_out)
+            db.search_pssm_top_stats_device(d_out, moffs, pscoring, top, 1, 0, out=h2, hist=d_hist2)
+
+        db.search_pssm_top_stats_device(d_m, moffs, pscoring, top, 1, 0, out=(hits.view(-1), nhits), hist=d_hist)
+        h_stats = (hits.view(-1), nhits)
+        alternate({"score_iteration": score_iteration, "evalue_iteration": evalue_iteration})
+        out[f"{P}_evalue_over_score_iteration"] = round(out[f"{P}_evalue_iteration_ms"] / out[f"{P}_score_iteration_ms"], 4)
+        db1.close()
+        db.close()
+
     def pssm_weights_leg(packed, offs, nq=64, reps=7, per_hit=16):
         import time
         d_db = torch.from_numpy(packed.copy()).to(dev)
@@ -1118,7 +1242,9 @@ def main():
     out["a_letters"] = int(offs[-1])
     out["a_len_median"] = int(np.median(lens))
     out["a_len_max"] = int(lens.max())
-    if args.multi or args.top or args.align_hits or args.pairs or args.prefilter or args.prefiltered_top or args.pssm or args.pssm_iterate or args.pssm_weights or args.msa or args.msa_filter or args.lanes or args.pairs_lanes:
+    if args.multi or args.top or args.align_hits or args.pairs or args.prefilter or args.prefiltered_top or args.pssm or args.pssm_iterate or args.pssm_weights or args.msa or args.msa_filter or args.score_stats or args.lanes or args.pairs_lanes:
+        if args.score_stats:
+            score_stats_leg(packed, offs)
         if args.lanes:
             lanes_leg(packed, offs)
         if args.pairs_lanes:
@@ -1159,6 +1285,8 @@ def main():
             sys.exit("bench_search.py --pssm-weights: pssm_weights_identical is false")
         if args.msa and not out["msa_identical"]:
             sys.exit("bench_search.py --msa: msa_identical is false")
+        if args.score_stats and not out["score_stats_identical"]:
+            sys.exit("bench_search.py --score-stats: score_stats_identical is false")
         if args.msa_filter and not out["msa_filter_identical"]:
             sys.exit("bench_search.py --msa-filter: msa_filter_identical is false")
         if args.pssm and not out["pssm_identical"]:

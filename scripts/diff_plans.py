@@ -230,13 +230,18 @@ def gen_msa_filter(r):
               budget_bytes=r.choice([0, 1 << 20, 3 << 20, (3 << 20) + 1, 256 << 20, 1 << 40]), tiles=r.choice([0, 0, 1]))
 
 
+def gen_score_hist(r):
+    return kv(nqueries=r.choice([0, 1, 3, 64, 70, 4096, 1 << 20, (1 << 20) + 5]), ntargets=r.choice([0, 1, 63, 64, 65, 257, 4095, 4096, 4097, 5000, 25000, 200000, (1 << 31) - 1]),
+              num_cus=r.choice([1, 256, 304]), copies=r.choice([0, 0, 1, 2, 4]))
+
+
 GENERATORS = {"search_multi_plan_driver": gen_search_multi, "search_multi_lanes_plan_driver": gen_search_multi_lanes, "prefilter_plan_driver": gen_prefilter,
               "search_pairs_plan_driver": gen_search_pairs, "search_pairs_lanes_plan_driver": gen_search_pairs_lanes, "align_hits_plan_driver": gen_align_hits,
               "align_ckpt_plan_driver": gen_align_ckpt, "align_affine_plan_driver": gen_align_affine, "search_affine_plan_driver": gen_search_affine,
               "fill_plan_driver": gen_fill, "prologue_plan_driver": gen_prologue, "search_top_plan_driver": gen_search_top,
               "top_pairs_plan_driver": gen_top_pairs, "pssm_hits_plan_driver": gen_pssm_hits,
               "pssm_weights_plan_driver": gen_pssm_weights, "msa_hits_plan_driver": gen_msa_hits,
-              "msa_filter_plan_driver": gen_msa_filter}
+              "msa_filter_plan_driver": gen_msa_filter, "score_hist_plan_driver": gen_score_hist}
 
 
 def random_cases(n, seed):

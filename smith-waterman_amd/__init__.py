@@ -118,6 +118,15 @@ ABI = {
     "sw_msa_from_hits_host": (_i32, [_vp, _vp, _i64, _vp, _vp, _i64, _i64, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _vp]),
     "sw_msa_filter_device": (_i32, [_vp, _vp, _vp, _vp, _i64, _i64, ctypes.POINTER(_MsaFilter), _vp, _vp, _vp, _vp, _vp]),
     "sw_msa_filter_host": (_i32, [_vp, _vp, _vp, _i64, _i64, ctypes.POINTER(_MsaFilter), _vp, _vp, _vp, _vp]),
+    "sw_score_hist_device": (_i32, [_vp, _vp, _vp, _i64, _i32, _vp, _vp]),
+    "sw_score_hist_host": (_i32, [_vp, _i64, _vp, _i64, _i32, _vp]),
+    "sw_db_search_affine_top_stats": (_i32, [_vp, _vp, _vp, _vp, _i64, ctypes.POINTER(_Affine), _i64, _i64, _vp, _vp, _i32, _vp, _vp]),
+    "sw_db_search_pssm_top_stats": (_i32, [_vp, _vp, _vp, _vp, _i64, ctypes.POINTER(_PssmScoring), _i64, _i64, _vp, _vp, _i32, _vp, _vp]),
+    "sw_score_fit_hist": (_i32, [_vp, _i64, _i32, _vp]),
+    "sw_score_evalue": (ctypes.c_double, [_vp, _i64, _i64]),
+    "sw_score_thresholds": (_i32, [_vp, _i64, ctypes.c_double, _vp]),
+    "sw_hits_threshold_device": (_i32, [_vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "sw_hits_threshold_host": (_i32, [_vp, _i64, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp]),
     "sw_write_a3m": (_i32, [ctypes.c_char_p, ctypes.c_char_p, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _i64]),
     "sw_write_pssm": (_i32, [ctypes.c_char_p, _vp, ctypes.c_int32, _vp, _i64, _vp]),
     "sw_align_affine_device": (_i32, [_vp, _vp, _i64, _vp, _vp, _i64, _vp, _i64, ctypes.POINTER(_Affine), _vp, _vp, _i64, _vp]),
@@ -166,6 +175,10 @@ ABI = {
 SW_TOP_MAX = 4096   # include/swhip.h: the most hits per query a selecting call takes
 # sw_msa_row (include/swhip.h), 24 bytes: an entry's A3M row is a3m[off : off + len]
 MSA_ROW = np.dtype([("off", np.int64), ("len", np.int32), ("nmatch", np.int32), ("nident", np.int32), ("ninsert", np.int32)])
+# the score histogram of a query (include/swhip.h): SW_HIST_CLASSES x SW_HIST_BINS uint32 counters; sw_score_fit, 56 bytes
+HIST_CLASSES, HIST_BINS, HIST_SHIFT_MAX = 40, 256, 16
+SCORE_FIT = np.dtype([("a", np.float64), ("b", np.float64), ("sigma", np.float64), ("n_db", np.int64), ("n_fit", np.int64),
+                      ("n_censored", np.int64), ("valid", np.int32), ("shift", np.int32)])
 
 _lib = None
 
@@ -679,6 +692,106 @@ def msa_filter_host(cols, queries_or_qoffsets, top: int, max_ident_pct: int, min
     return keep[:nq * top].reshape(nq, top), nkept[:nq], out
 
 
+def _target_offsets(targets_or_offsets):
+    """The int64 offsets of the targets: from a 1-D integer array of offsets as it is, else as _pack_targets gives them."""
+    if isinstance(targets_or_offsets, np.ndarray) and targets_or_offsets.ndim == 1 and targets_or_offsets.dtype.kind in "iu" \
+            and targets_or_offsets.dtype != np.uint8:
+        return np.ascontiguousarray(targets_or_offsets, np.int64)
+    return _pack_targets(targets_or_offsets)[1]
+
+
+def score_hist_host(results, targets_or_offsets, shift: int = 0):
+    """sw_score_hist_host: the score histogram of a result table in plain C++ on the host (no GPU).  results: the (nqueries, ntargets,
+    3) int64 table of (max_pos, max_score, path_len) a search returns; targets_or_offsets: the targets as for search_affine, or their
+    1-D int64 offsets (only the lengths count).  Returns (nqueries, 40, 256) uint32: [q, c, s] counts the non-empty targets of
+    half-octave length class c whose score lies in bin s = min(max(score, 0) >> shift, 255) (include/swhip.h states the rule)."""
+    offs = _target_offsets(targets_or_offsets)
+    ntargets = len(offs) - 1
+    res = np.ascontiguousarray(results, np.int64)
+    if res.ndim != 3 or res.shape[1] != ntargets or res.shape[2] != 3:
+        raise ValueError(f"results must be (nqueries, {ntargets}, 3) int64")
+    nq = res.shape[0]
+    hist = np.zeros((max(1, nq), HIST_CLASSES, HIST_BINS), np.uint32)
+    one = np.zeros(3, np.int64)
+    _check(lib().sw_score_hist_host((res if res.size else one).ctypes.data, nq, offs.ctypes.data, ntargets, int(shift), hist.ctypes.data))
+    return hist[:nq]
+
+
+def _hists(hist):
+    hist = np.ascontiguousarray(hist, np.uint32)
+    if hist.ndim == 2:
+        hist = hist[None]
+    if hist.ndim != 3 or hist.shape[1:] != (HIST_CLASSES, HIST_BINS):
+        raise ValueError(f"hist must be (nqueries, {HIST_CLASSES}, {HIST_BINS}) uint32")
+    return hist
+
+
+def score_fit(hist, shift: int = 0):
+    """sw_score_fit_hist: per query the line score = a + b x class(length) through the unrelated targets' scores and its spread sigma,
+    from the histograms of score_hist / search_affine_top_stats ((nqueries, 40, 256) uint32; `shift` as they were taken with).  Host
+    only, double.  Returns a numpy record array of SCORE_FIT: a, b, sigma, n_db, n_fit, n_censored, valid, shift."""
+    hist = _hists(hist)
+    nq = hist.shape[0]
+    fit = np.zeros(max(1, nq), SCORE_FIT)
+    one = np.zeros(1, np.uint32)
+    _check(lib().sw_score_fit_hist((hist if hist.size else one).ctypes.data, nq, int(shift), fit.ctypes.data))
+    return fit[:nq]
+
+
+def _fits(fit):
+    fit = np.ascontiguousarray(np.atleast_1d(fit))
+    if fit.dtype != SCORE_FIT:
+        raise ValueError("fit must be the SCORE_FIT records score_fit returns")
+    return fit
+
+
+def score_thresholds(fit, evalue: float):
+    """sw_score_thresholds: (nqueries, 40) int64, [q, c] the smallest integer score of a target of length class c whose E-value for query
+    q is <= evalue; 0 where evalue >= n_db or the fit is invalid."""
+    fit = _fits(fit)
+    thr = np.zeros((max(1, len(fit)), HIST_CLASSES), np.int64)
+    _check(lib().sw_score_thresholds((fit if len(fit) else np.zeros(1, SCORE_FIT)).ctypes.data, len(fit), float(evalue), thr.ctypes.data))
+    return thr[:len(fit)]
+
+
+def score_evalue(fit, target_len: int, score: int) -> float:
+    """sw_score_evalue: the E-value of `score` against a target of target_len letters under ONE query's fit (a SCORE_FIT record); NaN
+    for an invalid fit."""
+    fit = _fits(fit)
+    if len(fit) != 1:
+        raise ValueError("fit must be one SCORE_FIT record")
+    return float(lib().sw_score_evalue(fit.ctypes.data, int(target_len), int(score)))
+
+
+def length_class(length: int) -> int:
+    """The half-octave class of a target's length (include/swhip.h): 0 for 1, else 2 e + the bit below the leading one, e = floor(log2)."""
+    length = int(length)
+    if length < 2:
+        return 0
+    e = length.bit_length() - 1
+    return 2 * e + ((length >> (e - 1)) & 1)
+
+
+def hits_threshold_host(targets_or_offsets, thresholds, hits, nhits=None):
+    """sw_hits_threshold_host: the thresholds of score_thresholds applied to a hit table in plain C++ on the host (no GPU).  Arguments
+    and results as Database.hits_threshold, the targets as for score_hist_host."""
+    offs = _target_offsets(targets_or_offsets)
+    thr = np.ascontiguousarray(thresholds, np.int64)
+    if thr.ndim != 2 or thr.shape[1] != HIST_CLASSES:
+        raise ValueError(f"thresholds must be (nqueries, {HIST_CLASSES}) int64")
+    nq = thr.shape[0]
+    hits, nhits = _hit_table(hits, nhits, nq)
+    top = hits.shape[1]
+    keep = np.zeros((max(1, nq), max(1, top)), np.int32)
+    nkept = np.zeros(max(1, nq), np.int64)
+    out = np.zeros((max(1, nq), max(1, top), 3), np.int64)
+    one = np.zeros(HIST_CLASSES, np.int64)
+    _check(lib().sw_hits_threshold_host(offs.ctypes.data, len(offs) - 1, (thr if thr.size else one).ctypes.data, nq, top,
+                                        (hits if hits.size else one).ctypes.data, nhits.ctypes.data if nhits is not None else None,
+                                        out.ctypes.data, keep.ctypes.data, nkept.ctypes.data))
+    return keep[:nq, :top], nkept[:nq], out[:nq, :top]
+
+
 def write_a3m(path: str, qname: str, query, tnames, hits, aln, rows, a3m):
     """sw_write_a3m: one query's A3M file.  query: its letters, or an int (the number of columns of a PSSM query: no query record);
     tnames: the names of ALL targets, or None for their indices; hits, aln, rows: the query's (top, 3), (top, 7) and (top,) MSA_ROW
@@ -1082,6 +1195,103 @@ class Database:
         search_affine_top_device."""
         lt, sc = _pssm_scoring(scoring)
         return self._search_top_call(lib().sw_db_search_pssm_top, d_pssm, qoffsets, sc, top, min_score, out)
+
+    def search_affine_top_stats(self, queries, scoring, top: int, min_score: int = 0, shift: int = 0):
+        """search_affine_top with the score histogram of every query, collected on the device inside the call, chunk by chunk, while
+        the chunk's rows are in the workspace (sw_db_search_affine_top_stats).  Returns numpy (hits, nhits, hist (nqueries, 40, 256)
+        uint32): hits and nhits are those of search_affine_top, hist is score_hist_host of the full table, which never exists.
+        score_fit, score_thresholds and score_evalue turn hist into E-values."""
+        eng = self.engine
+        t = eng.torch
+        qpacked, qoffs = _pack_targets(queries)
+        d_q = t.from_numpy(qpacked.copy() if len(qpacked) else np.zeros(1, np.uint8)).to(f"cuda:{eng.device}")
+        hits, nhits, hist = self.search_affine_top_stats_device(d_q, qoffs, scoring, top, min_score, shift)
+        eng.synchronize()
+        return hits.cpu().numpy(), nhits.cpu().numpy(), hist.cpu().numpy().view(np.uint32)
+
+    def search_affine_top_stats_device(self, d_queries, qoffsets, scoring, top: int, min_score: int = 0, shift: int = 0, out=None, hist=None):
+        """sw_db_search_affine_top_stats on device-resident queries; asynchronous on torch's current stream.  Returns torch (hits, nhits,
+        hist (nqueries, 40, 256) int32 -- the uint32 counters' bits); `out` as for search_affine_top_device, `hist` a contiguous int32
+        tensor of at least nqueries x 10240 elements, or None for a fresh one."""
+        sub, sc = _affine(*scoring)
+        return self._search_top_stats_call(lib().sw_db_search_affine_top_stats, d_queries, qoffsets, sc, top, min_score, shift, out, hist)
+
+    def _search_top_stats_call(self, fn, d_source, qoffsets, sc, top: int, min_score: int, shift: int, out, hist):
+        """sw_db_search_affine_top_stats / sw_db_search_pssm_top_stats (see _search_top_call)."""
+        eng = self.engine
+        qoffs = np.ascontiguousarray(qoffsets, np.int64).reshape(-1)
+        if len(qoffs) == 0:
+            qoffs = np.zeros(1, np.int64)
+        nq = len(qoffs) - 1
+        hits, nhits = eng._top_out(nq, top, out)
+        hist = eng._hist_out(nq, hist)
+        _check(fn(eng._h, self._h, d_source.data_ptr(), qoffs.ctypes.data, nq, ctypes.byref(sc), int(top), int(min_score), hits.data_ptr(), nhits.data_ptr(),
+                  int(shift), hist.data_ptr(), eng._stream()))
+        return eng._top_views(hits, nhits, nq, top) + (hist.view(-1)[:nq * HIST_CLASSES * HIST_BINS].view(nq, HIST_CLASSES, HIST_BINS),)
+
+    def search_pssm_top_stats(self, pssm, scoring, top: int, min_score: int = 0, shift: int = 0):
+        """search_pssm_top with the score histogram of every query (sw_db_search_pssm_top_stats); results as for
+        search_affine_top_stats."""
+        d_m, qoffs = self._pssm_to_device(pssm, len(_as_seq(scoring[0])))
+        hits, nhits, hist = self.search_pssm_top_stats_device(d_m, qoffs, scoring, top, min_score, shift)
+        self.engine.synchronize()
+        return hits.cpu().numpy(), nhits.cpu().numpy(), hist.cpu().numpy().view(np.uint32)
+
+    def search_pssm_top_stats_device(self, d_pssm, qoffsets, scoring, top: int, min_score: int = 0, shift: int = 0, out=None, hist=None):
+        """sw_db_search_pssm_top_stats on a device-resident matrix; results, `out` and `hist` as for search_affine_top_stats_device."""
+        lt, sc = _pssm_scoring(scoring)
+        return self._search_top_stats_call(lib().sw_db_search_pssm_top_stats, d_pssm, qoffsets, sc, top, min_score, shift, out, hist)
+
+    def hits_threshold(self, thresholds, hits, nhits=None):
+        """The thresholds of score_thresholds applied to a hit table (sw_hits_threshold_device): an entry is kept when it is a used entry
+        -- below the query's count, target inside the handle and not empty -- and its score reaches thresholds[q, class(length of its
+        target)].  thresholds: (nqueries, 40) int64; hits: the (nqueries, top, 3) table; nhits: the counts or None (all top entries).
+        Returns numpy (keep (nqueries, top) int32, nkept (nqueries,) int64, the hit table with target = -1 in the dropped entries)."""
+        eng = self.engine
+        t = eng.torch
+        dev = f"cuda:{eng.device}"
+        thr = np.ascontiguousarray(thresholds, np.int64)
+        if thr.ndim != 2 or thr.shape[1] != HIST_CLASSES:
+            raise ValueError(f"thresholds must be (nqueries, {HIST_CLASSES}) int64")
+        nq = thr.shape[0]
+        hits, nhits = _hit_table(hits, nhits, nq)
+        top = hits.shape[1]
+        d_thr = t.from_numpy(thr.reshape(-1).copy() if thr.size else np.zeros(1, np.int64)).to(dev)
+        d_hits = t.from_numpy(hits.reshape(-1).copy() if hits.size else np.zeros(3, np.int64)).to(dev)
+        d_n = t.from_numpy(nhits.copy() if len(nhits) else np.zeros(1, np.int64)).to(dev) if nhits is not None else None
+        keep, nkept, out = self.hits_threshold_device(d_thr, nq, top, d_hits, d_n, hits_out=d_hits)
+        eng.synchronize()
+        return (keep.cpu().numpy()[:nq * top].reshape(nq, top), nkept.cpu().numpy()[:nq], out.cpu().numpy()[:nq * top * 3].reshape(nq, top, 3))
+
+    def hits_threshold_device(self, d_thresholds, nqueries: int, top: int, hits, nhits=None, hits_out=None, keep=None, nkept=None):
+        """sw_hits_threshold_device on device tensors; asynchronous on torch's current stream, nothing comes to the host.  d_thresholds:
+        int64, nqueries x 40; hits: int64, nqueries x top x 3; nhits: int64 counts or None; hits_out: the tensor that receives the table
+        with target = -1 in the dropped entries -- `hits` itself for in place, None for none; keep / nkept: as for
+        Engine.msa_filter_device.  Returns (keep, nkept, hits_out), None where there is none."""
+        eng = self.engine
+        t = eng.torch
+        dev = f"cuda:{eng.device}"
+        nq, top = int(nqueries), int(top)
+        n = max(0, nq) * max(0, top)
+        for x, need, what in ((d_thresholds, nq * HIST_CLASSES, "d_thresholds"), (hits, n * 3, "hits"), (hits_out, n * 3, "hits_out"), (nhits, nq, "nhits")):
+            if x is not None and (x.dtype != t.int64 or not x.is_contiguous() or x.numel() < need):
+                raise ValueError(f"{what} must be a contiguous int64 tensor of at least {need} elements")
+        if keep is None:
+            keep = t.empty(max(1, n), dtype=t.int32, device=dev)
+        elif keep is False:
+            keep = None
+        if keep is not None and (keep.dtype != t.int32 or not keep.is_contiguous() or keep.numel() < n):
+            raise ValueError(f"keep must be a contiguous int32 tensor of at least {n} elements")
+        if nkept is None:
+            nkept = t.empty(max(1, nq), dtype=t.int64, device=dev)
+        elif nkept is False:
+            nkept = None
+        if nkept is not None and (nkept.dtype != t.int64 or not nkept.is_contiguous() or nkept.numel() < nq):
+            raise ValueError(f"nkept must be a contiguous int64 tensor of at least {nq} elements")
+        ptr = lambda x: x.data_ptr() if x is not None else None
+        _check(lib().sw_hits_threshold_device(eng._h, self._h, ptr(d_thresholds), nq, top, ptr(hits), ptr(nhits), ptr(hits_out), ptr(keep), ptr(nkept),
+                                              eng._stream()))
+        return keep, nkept, hits_out
 
     def search_affine_top_prefiltered(self, queries, scoring, prefilter_min_score: int, top: int, min_score: int = 0, cap=None):
         """Filter, rescoring and selection in one call on host queries (sw_db_search_affine_top_prefiltered): the table of
@@ -1679,6 +1889,43 @@ class Engine:
         _check(lib().sw_top_hits_pairs_device(self._h, d_pairs.data_ptr() if npairs else None, d_results.data_ptr() if npairs else None, int(npairs),
                                               int(nqueries), int(ntargets), int(top), int(min_score), hits.data_ptr(), nhits.data_ptr(), self._stream()))
         return self._top_views(hits, nhits, int(nqueries), top)
+
+    def _hist_out(self, nq: int, hist):
+        """The histogram buffer of a statistics call: `hist` checked, or a fresh one (int32: the uint32 counters' bits)."""
+        t = self.torch
+        n = nq * HIST_CLASSES * HIST_BINS
+        if hist is None:
+            return t.empty(max(1, n), dtype=t.int32, device=f"cuda:{self.device}")
+        if hist.dtype != t.int32 or not hist.is_contiguous() or hist.numel() < n:
+            raise ValueError(f"hist must be a contiguous int32 tensor of at least {n} elements")
+        return hist
+
+    def score_hist(self, database, results, shift: int = 0):
+        """The score histogram of a host result table on the device (sw_score_hist_device): results the (nqueries, ntargets, 3) int64
+        table of a search of `database` (a Database; its offsets give the lengths).  Returns (nqueries, 40, 256) uint32, the bytes of
+        score_hist_host."""
+        t = self.torch
+        res = np.ascontiguousarray(results, np.int64)
+        if res.ndim != 3 or res.shape[1] != database.ntargets or res.shape[2] != 3:
+            raise ValueError(f"results must be (nqueries, {database.ntargets}, 3) int64")
+        d_res = t.from_numpy(res.reshape(-1).copy() if res.size else np.zeros(3, np.int64)).to(f"cuda:{self.device}")
+        hist = self.score_hist_device(database, d_res, res.shape[0], shift)
+        self.synchronize()
+        return hist.cpu().numpy().view(np.uint32)
+
+    def score_hist_device(self, database, d_results, nqueries: int, shift: int = 0, hist=None):
+        """sw_score_hist_device on a device-resident query-major result table (int64, nqueries x ntargets x 3, what
+        Database.search_affine_device returns); asynchronous on torch's current stream.  Every counter is written.  Returns the
+        (nqueries, 40, 256) int32 tensor of the uint32 counters' bits, a view of `hist` if given (see _hist_out)."""
+        t = self.torch
+        nq = int(nqueries)
+        need = max(0, nq) * database.ntargets * 3
+        if d_results is not None and (d_results.dtype != t.int64 or not d_results.is_contiguous() or d_results.numel() < need):
+            raise ValueError(f"d_results must be a contiguous int64 tensor of at least {need} elements")
+        hist = self._hist_out(max(0, nq), hist)
+        _check(lib().sw_score_hist_device(self._h, database._h, d_results.data_ptr() if d_results is not None else None, nq, int(shift),
+                                          hist.data_ptr(), self._stream()))
+        return hist.view(-1)[:max(0, nq) * HIST_CLASSES * HIST_BINS].view(max(0, nq), HIST_CLASSES, HIST_BINS)
 
     def msa_filter(self, cols, queries_or_qoffsets, top: int, max_ident_pct: int, min_cover_pct: int, hits=None):
         """The filter of a hit alignment (sw_msa_filter_device): which rows of the column rows of Database.msa_from_hits are kept --

@@ -175,6 +175,36 @@ static AlignedHits download_aligned(const DeviceBuffer& d_aln, const DeviceBuffe
     return a;
 }
 
+// ---- the statistics of a many-query search (--evalue, --include-evalue): the score histograms the _top_stats calls fill on the
+// device, and what the host makes of them once per round -- 40 KiB per query come back, the fit and the thresholds are O(queries)
+struct ScoreStats : NoCopy {
+    int64_t nq = 0;
+    int shift = 0;
+    DeviceBuffer d_hist, d_thr;
+    std::vector<uint32_t> hist;
+    std::vector<sw_score_fit> fit;
+    std::vector<int64_t> thr;
+    void alloc(sw_ctx* ctx, int64_t queries, int score_shift) {
+        nq = queries; shift = score_shift;
+        const size_t cells = (size_t)std::max<int64_t>(1, nq) * SW_HIST_CLASSES * SW_HIST_BINS;
+        d_hist.alloc(ctx, cells * sizeof(uint32_t));
+        d_thr.alloc(ctx, (size_t)std::max<int64_t>(1, nq) * SW_HIST_CLASSES * sizeof(int64_t));
+        hist.resize(cells); fit.resize((size_t)std::max<int64_t>(1, nq)); thr.resize((size_t)std::max<int64_t>(1, nq) * SW_HIST_CLASSES);
+    }
+    explicit operator bool() const { return (bool)d_hist; }
+    // the stream has been synchronised: the histograms of the last search come to the host and are fitted
+    void fit_last_search() {
+        d_hist.download(hist.data(), (size_t)nq * SW_HIST_CLASSES * SW_HIST_BINS * sizeof(uint32_t));
+        CHECK(sw_score_fit_hist(hist.data(), nq, shift, fit.data()));
+    }
+    // ... and the thresholds of `evalue` under that fit, on the host and in d_thr
+    const int64_t* thresholds(double evalue) {
+        CHECK(sw_score_thresholds(fit.data(), nq, evalue, thr.data()));
+        d_thr.upload(thr.data(), (size_t)nq * SW_HIST_CLASSES * sizeof(int64_t));
+        return thr.data();
+    }
+};
+
 // ---- printers
 // the line the run scripts grep for: seconds, GCUPS of `cells`, then the mode's own detail inside the parentheses ("; ...", or none)
 __attribute__((format(printf, 3, 4))) static void print_elapsed(double seconds, double cells, const char* detail, ...) {
@@ -209,8 +239,30 @@ struct Options {
     int search_lanes = 32, pairs_lanes = 32;
     bool has_search_lanes = false, has_pairs_lanes = false;
     int iterations = 1, include_score = 1, prior_weight = 10, weight_hits = 0;
-    bool has_weight_hits = false, has_iter_flag = false;
+    bool has_weight_hits = false, has_iter_flag = false, has_include_score = false;
+    double evalue = 0, include_evalue = 0;   // --evalue E: report by E-value; --include-evalue E: include in the next round by E-value
+    bool has_evalue = false, has_include_evalue = false, has_score_shift = false;
+    int score_shift = 0;
     const char *out_pssm = nullptr, *out_a3m = nullptr;
     sw_scores sc = {3, -3, -2};
     bool iterate() const { return iterations > 1 || out_pssm || out_a3m; }   // (--iterations 1 alone is the search of today, through today's path)
+    bool stats() const { return has_evalue || has_include_evalue; }
 };
+
+// Which command lines the statistics flags go with: the message of the first rule broken, or none.  (tests/test_cli_score_stats_host.py
+// holds every one; main() prints it as it prints its own.)
+static std::string score_stats_rule(const Options& o) {
+    char msg[256] = "";
+    const auto say = [&](const char* fmt, auto... v) { snprintf(msg, sizeof msg, fmt, v...); return std::string(msg); };
+    if (!o.stats() && !o.has_score_shift) return "";
+    if (o.has_evalue && !(o.evalue > 0)) return say("--evalue E needs E > 0, got %g", o.evalue);
+    if (o.has_include_evalue && !(o.include_evalue > 0)) return say("--include-evalue E needs E > 0, got %g", o.include_evalue);
+    if (o.score_shift < 0 || o.score_shift > SW_HIST_SHIFT_MAX) return say("--score-shift N needs N within 0..%d, got %d", SW_HIST_SHIFT_MAX, o.score_shift);
+    if (!o.stats()) return "--score-shift goes with --evalue or --include-evalue";
+    if (o.has_prefilter || o.has_prefilter_hits || o.pairs_path)
+        return "--evalue / --include-evalue do not go with --prefilter / --prefilter-hits / --pairs (the fit needs every score, not a censored sample)";
+    if (!(o.search_q && (o.all_queries || o.pssm_path))) return "--evalue / --include-evalue go with --search --all-queries or --search --pssm";
+    if (o.has_include_evalue && o.has_include_score) return "--include-evalue does not go with --include-score";
+    if (o.has_include_evalue && o.iterations < 2) return "--include-evalue goes with --iterations N (N > 1)";
+    return "";
+}

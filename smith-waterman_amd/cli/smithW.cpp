@@ -51,6 +51,16 @@
 //                              (sw_db_pssm_hit_weights, Henikoff's position-based weights; per_hit = P within 1..65535, the round's --include-score):
 //                              a family that fills the hit list no longer outvotes a distant homologue.  N[j] of the update then counts in units
 //                              of P, so --prior-weight scales with it: --weight-hits 16 --prior-weight 160 is the balance of --prior-weight 10
+//     ... --evalue E          with --all-queries or --pssm (also with --iterations): only hits whose E-value is at most E > 0 are printed, and every hit line
+//                              ends in " E=<E-value>".  The E-values come from the scores of the search itself, per query: the search collects a histogram
+//                              of every target's score by length class on the device (sw_db_search_affine_top_stats / sw_db_search_pssm_top_stats), the host
+//                              fits the unrelated targets' line and spread to it (sw_score_fit_hist) and derives a score threshold per length class
+//                              (sw_score_thresholds); a database too small for a fit (fewer than 30 targets) drops nothing and prints E=nan.  The histograms
+//                              come to the host: 40 KiB per query and one synchronisation per round.  Not with --prefilter, --prefilter-hits or --pairs
+//     ... --include-evalue E  with --iterations N (N > 1), in the place of --include-score: every round thresholds a COPY of its hit table by E-value on the
+//                              device (sw_hits_threshold_device); the copy goes to the weights, the update and --out-a3m, the untouched table to the aligner
+//                              and the printer
+//     ... --score-shift N     with --evalue / --include-evalue: the histogram's bins are 2^N scores wide (0..16, default 0; 256 bins, the last one open)
 //   smithW --search --pssm FILE DB.fa --gap-open O --gap-extend E [--top K] [--min-score S] [--align] [--search-lanes 16|32]
 //                              the ONE query is a position-specific scoring matrix, PSI-BLAST's ASCII PSSM (sw_read_pssm), searched through a prepared
 //                              handle (sw_db_search_pssm_top, sw_db_align_pssm_hits); the output is that of --all-queries for one record, the Q line of an
@@ -120,6 +130,14 @@ static bool parse_int(const char* flag, const char* text, int* out) {
     *out = (int)v;
     return true;
 }
+// ... and a whole decimal number
+static bool parse_real(const char* flag, const char* text, double* out) {
+    char* end = nullptr;
+    const double v = strtod(text, &end);
+    if (end == text || *end) { fprintf(stderr, "smithW: %s needs a number, got \"%s\"\n", flag, text); return false; }
+    *out = v;
+    return true;
+}
 // The best K targets of one row of results in rank order -- by score, ties: lower record first --, those below min_score left out.
 static std::vector<sw_hit> rank_hits(const sw_result* res, int64_t nrec, long long K, long long min_score) {
     std::vector<int64_t> order;
@@ -134,8 +152,9 @@ static std::vector<sw_hit> rank_hits(const sw_result* res, int64_t nrec, long lo
 
 // The hit block of one query: the header line, its K hits in rank order and, with `align`, every hit's alignment: the row `done` of a
 // call that aligned every query's hits or -- `done` empty -- the K hits re-filled with directions and walked on the device here.
+// --evalue: `keep` says which of the K hits are printed (the ranks count those), `fit` gives every printed line its " E=" field.
 static void print_hits(sw_ctx* ctx, const char* q, int64_t qlen, const char* d_q, const Db& db, const DeviceBuffer& d_db, const sw_hit* hits, long long K, bool align,
-                       const sw_affine& aff, const AlignedHits& done = AlignedHits()) {
+                       const sw_affine& aff, const AlignedHits& done = AlignedHits(), const int32_t* keep = nullptr, const sw_score_fit* fit = nullptr) {
     std::vector<int64_t> order((size_t)K);
     for (long long i = 0; i < K; ++i) order[(size_t)i] = hits[i].target;
     AlignedHits here;   // --align without `done`: ops of at most query + longest hit letters each
@@ -150,10 +169,14 @@ static void print_hits(sw_ctx* ctx, const char* q, int64_t qlen, const char* d_q
     }
     const AlignedHits& got = done.empty() ? here : done;
     printf("# query %lld letters, %lld targets, %lld letters; rank\trecord\tscore\ttarget_end\tquery_end\n", (long long)qlen, (long long)db.nrec, (long long)db.total);
+    long long rank = 0;
     for (long long i = 0; i < K; ++i) {
+        if (keep && !keep[i]) continue;
         const sw_hit& r = hits[i];
         const long long te = r.max_pos / (qlen + 1), qe = r.max_pos % (qlen + 1);
-        printf("%lld\t%lld\t%lld\t%lld\t%lld\n", i + 1, (long long)order[(size_t)i], (long long)r.max_score, te, qe);
+        printf("%lld\t%lld\t%lld\t%lld\t%lld", ++rank, (long long)order[(size_t)i], (long long)r.max_score, te, qe);
+        if (fit) printf(" E=%.2e", sw_score_evalue(fit, db.len(order[(size_t)i]), r.max_score));
+        printf("\n");
         if (!align) continue;
         const sw_alignment& a = got.aln[(size_t)i];
         printf("align\t%lld\t%lld\t%lld\t%lld\t%lld\n", (long long)a.q_begin, (long long)a.q_end, (long long)a.t_begin, (long long)a.t_end, (long long)a.nops);
@@ -212,6 +235,10 @@ static int search_all_main(const Options& o) {
         fprintf(stderr, "smithW: --prefilter-hits selects on the device: min(--top, records) = %lld is above %d\n", K, SW_TOP_MAX);
         return 2;
     }
+    if (o.has_evalue && !on_device) {
+        fprintf(stderr, "smithW: --evalue takes its histogram inside the search that selects on the device: min(--top, records) = %lld is above %d\n", K, SW_TOP_MAX);
+        return 2;
+    }
     Context ctx(0);
     // --align-checkpoint: a table the one call would refuse for its worst pair goes through it checkpointed instead of query by query
     if (o.align_ckpt) CHECK(sw_set_option(ctx, "align_checkpoint", 2));
@@ -224,11 +251,16 @@ static int search_all_main(const Options& o) {
     DeviceBuffer d_npairs(ctx, sizeof(int64_t)), d_q(ctx, qs.letters.data(), (size_t)qs.total), d_db(ctx, db.letters.data(), (size_t)db.total),
         d_res(ctx, nres * sizeof(sw_result)), d_hits(ctx, nhit * sizeof(sw_hit)), d_nhits(ctx, (size_t)std::max<int64_t>(1, nq) * sizeof(int64_t));
     const Scoring s(o.af, o.sc);
+    ScoreStats stats;   // --evalue: the histograms of the search
+    if (o.has_evalue && K > 0) stats.alloc(ctx, nq, o.score_shift);
     DbHandle handle;
     const double t0 = now_s();
     handle.create(ctx, d_db, db.offsets, nrec);
     const double t1 = now_s();
     if (!on_device) CHECK(sw_db_search_affine(ctx, handle, d_q.as<const char>(), qs.offsets.data(), nq, &s.aff, d_res.as<sw_result>(), nullptr));
+    else if (stats)
+        CHECK(sw_db_search_affine_top_stats(ctx, handle, d_q.as<const char>(), qs.offsets.data(), nq, &s.aff, K, o.min_score, d_hits.as<sw_hit>(), d_nhits.as<int64_t>(),
+                                            o.score_shift, stats.d_hist.as<uint32_t>(), nullptr));
     else if (prefiltered)
         CHECK(sw_db_search_affine_top_prefiltered(ctx, handle, d_q.as<const char>(), qs.offsets.data(), nq, &s.aff, o.prefilter_hits, pairs_cap, K, o.min_score,
                                                   d_hits.as<sw_hit>(), d_nhits.as<int64_t>(), d_npairs.as<int64_t>(), nullptr));
@@ -252,6 +284,12 @@ static int search_all_main(const Options& o) {
     }
     std::vector<sw_result> res(nres);
     if (!on_device) d_res.download(res.data(), (size_t)(nq * nrec) * sizeof(sw_result));
+    std::vector<int32_t> keep;   // --evalue: the hits at or above the threshold of their length class
+    if (stats) {
+        stats.fit_last_search();
+        keep.resize(nhit);
+        CHECK(sw_hits_threshold_host(db.offsets.data(), nrec, stats.thresholds(o.evalue), nq, K, hits.data(), nhits.data(), nullptr, keep.data(), nullptr));
+    }
     // --align: the hits of every query in ONE call on the device table as the selection left it (sw_db_align_affine_hits), ops of at most
     // longest query + longest target letters each; a table of ops beyond 1 GiB, or one the call refuses, goes query by query instead (print_hits)
     AlignedHits aligned;
@@ -277,7 +315,8 @@ static int search_all_main(const Options& o) {
         const std::vector<sw_hit> ranked = on_device ? std::vector<sw_hit>() : rank_hits(res.data() + i * nrec, nrec, K, o.min_score);
         const sw_hit* row = on_device ? hits.data() + i * K : ranked.data();
         const long long n = on_device ? (long long)nhits[(size_t)i] : (long long)ranked.size();
-        print_hits(ctx, qs.record(i), qs.len(i), d_q.as<const char>() + qs.offsets[(size_t)i], db, d_db, row, n, o.align, s.aff, aligned.only_row(i, K));
+        print_hits(ctx, qs.record(i), qs.len(i), d_q.as<const char>() + qs.offsets[(size_t)i], db, d_db, row, n, o.align, s.aff, aligned.only_row(i, K),
+                   stats ? keep.data() + i * K : nullptr, stats ? &stats.fit[(size_t)i] : nullptr);
     }
     const double cells = (double)qs.total * (double)db.total;
     if (o.prefilter_hits > 0)
@@ -302,17 +341,26 @@ static int search_pssm_main(const Options& o) {
     const long long K = std::max(0ll, std::min(o.top, (long long)nrec));
     const bool on_device = K <= SW_TOP_MAX, align = o.align && K > 0;
     if (o.align && !on_device) { fprintf(stderr, "smithW: --pssm --align aligns a device hit table: min(--top, records) = %lld is above %d\n", K, SW_TOP_MAX); return 2; }
+    if (o.has_evalue && !on_device) {
+        fprintf(stderr, "smithW: --evalue takes its histogram inside the search that selects on the device: min(--top, records) = %lld is above %d\n", K, SW_TOP_MAX);
+        return 2;
+    }
     Context ctx(0);
     if (o.align_ckpt) CHECK(sw_set_option(ctx, "align_checkpoint", 2));
     CHECK(sw_set_option(ctx, "search_lanes", o.search_lanes));
     const size_t nres = on_device ? 1 : (size_t)std::max<int64_t>(1, nrec), nhit = (size_t)std::max<long long>(1, K);
     DeviceBuffer d_pssm(ctx, m.matrix.data(), m.matrix.size()), d_db(ctx, db.letters.data(), (size_t)db.total), d_res(ctx, nres * sizeof(sw_result)),
         d_hits(ctx, nhit * sizeof(sw_hit)), d_nhits(ctx, sizeof(int64_t));
+    ScoreStats stats;   // --evalue: the histogram of the search
+    if (o.has_evalue && K > 0) stats.alloc(ctx, 1, o.score_shift);
     DbHandle handle;
     const double t0 = now_s();
     handle.create(ctx, d_db, db.offsets, nrec);
     const double t1 = now_s();
     if (!on_device) CHECK(sw_db_search_pssm(ctx, handle, d_pssm.as<const int8_t>(), qoffs, 1, &scoring, d_res.as<sw_result>(), nullptr));
+    else if (stats)
+        CHECK(sw_db_search_pssm_top_stats(ctx, handle, d_pssm.as<const int8_t>(), qoffs, 1, &scoring, K, o.min_score, d_hits.as<sw_hit>(), d_nhits.as<int64_t>(), o.score_shift,
+                                          stats.d_hist.as<uint32_t>(), nullptr));
     else if (K > 0) CHECK(sw_db_search_pssm_top(ctx, handle, d_pssm.as<const int8_t>(), qoffs, 1, &scoring, K, o.min_score, d_hits.as<sw_hit>(), d_nhits.as<int64_t>(), nullptr));
     CHECK(sw_synchronize(ctx, nullptr));
     const double t2 = now_s();
@@ -336,9 +384,16 @@ static int search_pssm_main(const Options& o) {
         CHECK(sw_synchronize(ctx, nullptr));
         aligned = download_aligned(d_aln, d_ops, (size_t)K, ops_cap);
     }
+    std::vector<int32_t> keep;   // --evalue: the hits at or above the threshold of their length class
+    if (stats) {
+        stats.fit_last_search();
+        keep.resize(nhit);
+        CHECK(sw_hits_threshold_host(db.offsets.data(), nrec, stats.thresholds(o.evalue), 1, K, hits.data(), &nhits, nullptr, keep.data(), nullptr));
+    }
     printf("## query record 0 of %s\n", o.pssm_path);
     const sw_affine unused = {nullptr, 0, 0};   // (print_hits aligns nothing itself when it is given the rows of a call)
-    print_hits(ctx, query.data(), ncols, nullptr, db, d_db, hits.data(), (long long)nhits, align, unused, aligned);
+    print_hits(ctx, query.data(), ncols, nullptr, db, d_db, hits.data(), (long long)nhits, align, unused, aligned, stats ? keep.data() : nullptr,
+               stats ? stats.fit.data() : nullptr);
     print_elapsed(t2 - t1, (double)ncols * (double)db.total, "; 1 PSSM of %lld columns over %d letters, handle prepared in %f", (long long)ncols, m.nletters, t1 - t0);
     return 0;
 }
@@ -354,6 +409,10 @@ static int search_pssm_main(const Options& o) {
 // query's letters, for a PSSM file the consensus of the last matrix.  --out-pssm PREFIX writes the matrix the last search ran with, per
 // query, to PREFIX.<query index>.pssm (sw_write_pssm).  --weight-hits P puts sw_db_pssm_hit_weights (per_hit = P, the same
 // --include-score) between the alignment and the update of every round and hands its table to the update; 0: no weights, every hit counts 1.
+// --evalue / --include-evalue: every search is the _top_stats call.  With --include-evalue a round that feeds an update or the A3M waits
+// for its search, fits the histograms on the host and thresholds a COPY of the hit table on the device (sw_hits_threshold_device): the
+// copy goes to the weights, the update and --out-a3m with include_min_score at its minimum, the untouched table to the aligner and the
+// printer.  That is the one synchronisation per round this path adds.
 static int search_iter_main(const Options& o) {
     const char *ppath = o.pssm_path, *qpath = o.search_q;   // (with --pssm the two are the one file)
     const Db db = read_db(o.search_db);
@@ -402,8 +461,14 @@ static int search_iter_main(const Options& o) {
         d_ops.alloc(ctx, n * (size_t)ops_cap);
     }
     if (o.weight_hits > 0 && o.iterations > 1) d_weights.alloc(ctx, n * sizeof(int32_t));
-    const sw_pssm_update upd = {&s.sub, (int32_t)o.prior_weight, o.include_score};
-    const sw_pssm_weighting weighting = {(int32_t)o.weight_hits, o.include_score};
+    ScoreStats stats;
+    DeviceBuffer d_included;   // --include-evalue: the thresholded copy of the hit table
+    if (o.stats()) stats.alloc(ctx, nq, o.score_shift);
+    if (o.has_include_evalue) d_included.alloc(ctx, n * sizeof(sw_hit));
+    const sw_hit* d_use = o.has_include_evalue ? d_included.as<const sw_hit>() : d_hits.as<const sw_hit>();   // what the weights, the update and the A3M read
+    const int64_t include_min = o.has_include_evalue ? INT64_MIN : (int64_t)o.include_score;
+    const sw_pssm_update upd = {&s.sub, (int32_t)o.prior_weight, include_min};
+    const sw_pssm_weighting weighting = {(int32_t)o.weight_hits, include_min};
     const double t1 = now_s();
     const DeviceBuffer* cur = &d_prior;   // the matrix the search runs with
     for (long long it = 0; it < o.iterations; ++it) {   // nothing below waits for the device or reads from it
@@ -411,13 +476,23 @@ static int search_iter_main(const Options& o) {
             CHECK(sw_db_align_pssm_hits(ctx, handle, cur->as<const int8_t>(), qoffs, nq, &scoring, d_hits.as<const sw_hit>(), d_nhits.as<const int64_t>(), K,
                                         d_aln.as<sw_alignment>(), d_ops.as<char>(), ops_cap, nullptr));
             if (d_weights)
-                CHECK(sw_db_pssm_hit_weights(ctx, handle, qoffs, nq, &scoring, &weighting, d_hits.as<const sw_hit>(), d_nhits.as<const int64_t>(), K,
+                CHECK(sw_db_pssm_hit_weights(ctx, handle, qoffs, nq, &scoring, &weighting, d_use, d_nhits.as<const int64_t>(), K,
                                              d_aln.as<const sw_alignment>(), d_ops.as<const char>(), ops_cap, d_weights.as<int32_t>(), nullptr));
-            CHECK(sw_db_pssm_from_hits(ctx, handle, d_prior.as<const int8_t>(), qoffs, nq, &scoring, &upd, d_hits.as<const sw_hit>(), d_nhits.as<const int64_t>(), K,
+            CHECK(sw_db_pssm_from_hits(ctx, handle, d_prior.as<const int8_t>(), qoffs, nq, &scoring, &upd, d_use, d_nhits.as<const int64_t>(), K,
                                        d_aln.as<const sw_alignment>(), d_ops.as<const char>(), ops_cap, d_weights.as<const int32_t>(), d_work.as<int8_t>(), nullptr, nullptr));
             cur = &d_work;
         }
-        CHECK(sw_db_search_pssm_top(ctx, handle, cur->as<const int8_t>(), qoffs, nq, &scoring, K, o.min_score, d_hits.as<sw_hit>(), d_nhits.as<int64_t>(), nullptr));
+        if (stats)
+            CHECK(sw_db_search_pssm_top_stats(ctx, handle, cur->as<const int8_t>(), qoffs, nq, &scoring, K, o.min_score, d_hits.as<sw_hit>(), d_nhits.as<int64_t>(),
+                                              o.score_shift, stats.d_hist.as<uint32_t>(), nullptr));
+        else CHECK(sw_db_search_pssm_top(ctx, handle, cur->as<const int8_t>(), qoffs, nq, &scoring, K, o.min_score, d_hits.as<sw_hit>(), d_nhits.as<int64_t>(), nullptr));
+        if (o.has_include_evalue && (it + 1 < o.iterations || o.out_a3m)) {   // this round's table feeds an update or the A3M
+            CHECK(sw_synchronize(ctx, nullptr));
+            stats.fit_last_search();
+            stats.thresholds(o.include_evalue);
+            CHECK(sw_hits_threshold_device(ctx, handle, stats.d_thr.as<const int64_t>(), nq, K, d_hits.as<const sw_hit>(), d_nhits.as<const int64_t>(),
+                                           d_included.as<sw_hit>(), nullptr, nullptr, nullptr));
+        }
     }
     if (o.align)
         CHECK(sw_db_align_pssm_hits(ctx, handle, cur->as<const int8_t>(), qoffs, nq, &scoring, d_hits.as<const sw_hit>(), d_nhits.as<const int64_t>(), K,
@@ -429,13 +504,13 @@ static int search_iter_main(const Options& o) {
         if (!ppath) d_qs.alloc(ctx, qs.letters.data(), (size_t)qs.total);
         d_rows.alloc(ctx, n * sizeof(sw_msa_row));
         d_a3m_bytes.alloc(ctx, sizeof(int64_t));
-        CHECK(sw_db_msa_from_hits(ctx, handle, d_qs.as<const char>(), qoffs, nq, o.include_score, d_hits.as<const sw_hit>(), d_nhits.as<const int64_t>(), K,
+        CHECK(sw_db_msa_from_hits(ctx, handle, d_qs.as<const char>(), qoffs, nq, include_min, d_use, d_nhits.as<const int64_t>(), K,
                                   d_aln.as<const sw_alignment>(), d_ops.as<const char>(), ops_cap, nullptr, d_rows.as<sw_msa_row>(), nullptr, 0, d_a3m_bytes.as<int64_t>(),
                                   nullptr));
         CHECK(sw_synchronize(ctx, nullptr));
         d_a3m_bytes.download(&a3m_bytes, sizeof a3m_bytes);
         d_a3m.alloc(ctx, (size_t)a3m_bytes + 16);
-        CHECK(sw_db_msa_from_hits(ctx, handle, d_qs.as<const char>(), qoffs, nq, o.include_score, d_hits.as<const sw_hit>(), d_nhits.as<const int64_t>(), K,
+        CHECK(sw_db_msa_from_hits(ctx, handle, d_qs.as<const char>(), qoffs, nq, include_min, d_use, d_nhits.as<const int64_t>(), K,
                                   d_aln.as<const sw_alignment>(), d_ops.as<const char>(), ops_cap, nullptr, d_rows.as<sw_msa_row>(), d_a3m.as<char>(), a3m_bytes,
                                   d_a3m_bytes.as<int64_t>(), nullptr));
     }
@@ -448,6 +523,14 @@ static int search_iter_main(const Options& o) {
     d_nhits.download(nhits.data(), (size_t)nq * sizeof(int64_t));
     cur->download(last.data(), last.size());
     const AlignedHits aligned = o.align ? download_aligned(d_aln, d_ops, n, ops_cap) : AlignedHits();
+    std::vector<sw_hit> used;    // --include-evalue with --out-a3m: the table the A3M rows were made from
+    std::vector<int32_t> keep;   // --evalue: the hits at or above the threshold of their length class
+    if (o.has_include_evalue && o.out_a3m) { used.resize(n); d_included.download(used.data(), n * sizeof(sw_hit)); }
+    if (o.has_evalue) {
+        stats.fit_last_search();
+        keep.resize(n);
+        CHECK(sw_hits_threshold_host(db.offsets.data(), nrec, stats.thresholds(o.evalue), nq, K, hits.data(), nhits.data(), nullptr, keep.data(), nullptr));
+    }
     if (ppath) {   // the consensus of the last matrix
         const std::string c = consensus(m, last.data(), qs.total);
         std::copy(c.begin(), c.end(), qs.letters.begin());
@@ -469,14 +552,16 @@ static int search_iter_main(const Options& o) {
     const sw_affine unused = {nullptr, 0, 0};   // (print_hits aligns nothing itself when it is given the rows of a call)
     for (int64_t i = 0; i < nq; ++i) {
         printf("## query record %lld of %s\n", (long long)i, qpath);
-        print_hits(ctx, qs.record(i), qs.len(i), nullptr, db, d_db, hits.data() + i * K, (long long)nhits[(size_t)i], o.align, unused, aligned.only_row(i, K));
+        print_hits(ctx, qs.record(i), qs.len(i), nullptr, db, d_db, hits.data() + i * K, (long long)nhits[(size_t)i], o.align, unused, aligned.only_row(i, K),
+                   o.has_evalue ? keep.data() + i * K : nullptr, o.has_evalue ? &stats.fit[(size_t)i] : nullptr);
         if (o.out_pssm) {
             const std::string path = std::string(o.out_pssm) + "." + std::to_string((long long)i) + ".pssm";
             CHECK(sw_write_pssm(path.c_str(), m.letters, m.nletters, last.data() + qoffs[i] * m.nletters, qs.len(i), qs.record(i)));
         }
         if (o.out_a3m) {
             const std::string path = std::string(o.out_a3m) + "." + std::to_string((long long)i) + ".a3m";
-            CHECK(sw_write_a3m(path.c_str(), qnames[(size_t)i].c_str(), ppath ? nullptr : qs.record(i), qs.len(i), tname_ptrs.data(), nrec, hits.data() + i * K,
+            CHECK(sw_write_a3m(path.c_str(), qnames[(size_t)i].c_str(), ppath ? nullptr : qs.record(i), qs.len(i), tname_ptrs.data(), nrec,
+                               (used.empty() ? hits : used).data() + i * K,
                                aligned.row(i, K), msa_rows.data() + i * K, K, a3m.data(), a3m_bytes));
         }
     }
@@ -605,6 +690,7 @@ static int parse_options(int argc, char** argv, Options& o) {
         const std::string f = argv[ai];
         const auto flag = [&](const char* name, int values) { return f == name && ai + values < argc; };   // the flag, and its values follow
         const auto integer = [&](int* out) { const char* name = argv[ai]; return parse_int(name, argv[++ai], out); };
+        const auto real = [&](double* out) { const char* name = argv[ai]; return parse_real(name, argv[++ai], out); };
         int v = 0;
         if (f[0] != '-' && o.npos < 2 && ai + (1 - o.npos) < argc) {   // <cols> <rows>, anywhere on the line
             (o.npos == 0 ? o.cols : o.rows) = strtoll(argv[ai], nullptr, 10);
@@ -629,7 +715,10 @@ static int parse_options(int argc, char** argv, Options& o) {
         else if (flag("--search-lanes", 1)) { if (!integer(&o.search_lanes)) return 2; o.has_search_lanes = true; }
         else if (flag("--pairs-lanes", 1)) { if (!integer(&o.pairs_lanes)) return 2; o.has_pairs_lanes = true; }
         else if (flag("--iterations", 1)) { if (!integer(&o.iterations)) return 2; o.has_iter_flag = true; }
-        else if (flag("--include-score", 1)) { if (!integer(&o.include_score)) return 2; o.has_iter_flag = true; }
+        else if (flag("--include-score", 1)) { if (!integer(&o.include_score)) return 2; o.has_iter_flag = o.has_include_score = true; }
+        else if (flag("--evalue", 1)) { if (!real(&o.evalue)) return 2; o.has_evalue = true; }
+        else if (flag("--include-evalue", 1)) { if (!real(&o.include_evalue)) return 2; o.has_include_evalue = true; }
+        else if (flag("--score-shift", 1)) { if (!integer(&o.score_shift)) return 2; o.has_score_shift = true; }
         else if (flag("--prior-weight", 1)) { if (!integer(&o.prior_weight)) return 2; o.has_iter_flag = true; }
         else if (flag("--out-pssm", 1)) { o.out_pssm = argv[++ai]; o.has_iter_flag = true; }
         else if (flag("--out-a3m", 1)) { o.out_a3m = argv[++ai]; o.has_iter_flag = true; }
@@ -791,6 +880,7 @@ static Mode check_options(const Options& o) {
         if (o.pairs_lanes != 16 && o.pairs_lanes != 32) return refuse("--pairs-lanes takes 16 or 32, got %d", o.pairs_lanes);
         if (!o.search_q || o.pssm_path || !(o.pairs_path || o.has_prefilter_hits)) return refuse("--pairs-lanes goes with --search --pairs or --search --all-queries --prefilter-hits");
     }
+    if (const std::string why = score_stats_rule(o); !why.empty()) return refuse("%s", why.c_str());   // (the rules stand in cli_parts.h)
     if (o.has_iter_flag) {   // the iterative search: many sequence queries, or one matrix
         if (!(o.search_q && (o.all_queries || o.pssm_path))) return refuse("--iterations / --include-score / --prior-weight / --out-pssm / --out-a3m go with --search --all-queries or --search --pssm");
         if (o.iterations < 1) return refuse("--iterations N needs N >= 1, got %d", o.iterations);

@@ -108,6 +108,11 @@ int sw_set_option(sw_ctx* c, const char* name, int64_t v) {
         c->opt_msa_filter_workspace_mib = v;
         return SW_OK;
     }
+    if (!strcmp(name, "score_hist_copies")) {
+        if (v != 0 && v != 1 && v != 2 && v != 4) { set_err("score_hist_copies must be 0 (the planner's choice), 1, 2 or 4"); return SW_EINVAL; }
+        c->opt_score_hist_copies = v;
+        return SW_OK;
+    }
     if (!strcmp(name, "search_pairs_chunk")) {
         if (v < 1 || v > swp::kSearchPairsChunkMax) { set_err("search_pairs_chunk must be 1..2^31 - 1"); return SW_EINVAL; }
         c->opt_search_pairs_chunk = v;
@@ -211,6 +216,9 @@ int64_t sw_get_option(sw_ctx* c, const char* name) {
     if (!strcmp(name, "msa_filter_workspace_mib")) return c->opt_msa_filter_workspace_mib;
     if (!strcmp(name, "last_msa_filter_launches")) return c->last_msa_filter_launches;
     if (!strcmp(name, "last_msa_filter_chunks")) return c->last_msa_filter_chunks;
+    if (!strcmp(name, "score_hist_copies")) return c->opt_score_hist_copies;
+    if (!strcmp(name, "last_score_hist_launches")) return c->last_score_hist_launches;
+    if (!strcmp(name, "last_score_hist_slices")) return c->last_score_hist_slices;
     if (!strcmp(name, "last_pssm_weights_launches")) return c->last_pssm_weights_launches;
     if (!strcmp(name, "last_pssm_weights_tiles")) return c->last_pssm_weights_tiles;
     if (!strcmp(name, "search_pairs_chunk")) return c->opt_search_pairs_chunk;

@@ -383,6 +383,29 @@ static int select_top(sw_ctx* c, const swp::SearchTopPlan& plan, const sw_result
     return SW_OK;
 }
 
+// The score histogram of rows [0, nq) of `d_table` (sw_score_hist.hip) into d_hist, nq x 40 x 256 counters: zeroed on the stream, then
+// one launch as swp::plan_score_hist cuts it.  The caller has checked the arguments and holds the device's launch order.
+static int launch_score_hist(sw_ctx* c, const sw_db* db, const sw_result* d_table, int64_t nq, int shift, uint32_t* d_hist, hipStream_t stream) {
+    HIP_TRY(hipMemsetAsync(d_hist, 0, (size_t)nq * swp::kScoreHistCells * sizeof(uint32_t), stream));
+    swp::ScoreHistJob hj;
+    hj.nqueries = nq; hj.ntargets = db->ntargets; hj.num_cus = c->num_cus; hj.copies = (int)c->opt_score_hist_copies;
+    const swp::ScoreHistPlan plan = swp::plan_score_hist(hj);
+    if (plan.grid == 0) return SW_OK;
+    if (plan.lds_bytes > c->score_hist_lds_set) {   // (beyond 64 KiB a kernel asks for its dynamic LDS)
+        HIP_TRY(hipFuncSetAttribute((const void*)swk::sw_score_hist, hipFuncAttributeMaxDynamicSharedMemorySize, (int)plan.lds_bytes));
+        c->score_hist_lds_set = (int)plan.lds_bytes;
+    }
+    swk::ScoreHistParams kp;
+    memset(&kp, 0, sizeof kp);
+    kp.results = d_table; kp.offsets = db->d_offsets; kp.ntargets = db->ntargets; kp.nq = nq;
+    kp.slices_per_query = plan.slices_per_query; kp.slice = plan.slice; kp.items = plan.items;
+    kp.shift = shift; kp.copies = plan.copies; kp.hist = d_hist;
+    hipLaunchKernelGGL(swk::sw_score_hist, dim3((unsigned)plan.grid), dim3(256), (size_t)plan.lds_bytes, stream, kp);
+    HIP_TRY(hipGetLastError());
+    c->last_score_hist_launches += plan.launches; c->last_score_hist_slices = plan.slices_per_query;
+    return SW_OK;
+}
+
 // What the two selecting calls check alike, the plan of the call and the workspaces of the radix select.
 static int plan_top_call(sw_ctx* c, const char* who, int64_t nqueries, int64_t ntargets, int64_t top, const void* d_hits, const void* d_nhits,
                          int64_t budget_bytes, swp::SearchTopPlan& plan) {
@@ -688,12 +711,14 @@ int sw_top_hits_device(sw_ctx* c, const sw_result* d_results, int64_t nqueries, 
 
 // Search and selection with bounded result memory: chunk after chunk of queries through run_search_multi into the result workspace,
 // then that chunk's rows of d_hits.  The stream orders the chunks, which share the workspace.  (`who`'s search arguments are checked.)
+// With d_hist (the _top_stats calls) the score histogram of a chunk is taken between the two, while its rows are in the workspace.
 static int db_search_top_call(const char* who, sw_ctx* c, const sw_db* db, const QuerySource& src, const int64_t* qoffsets, int64_t nqueries, int64_t top,
-                              int64_t min_score, sw_hit* d_hits, int64_t* d_nhits, void* stream_) {
+                              int64_t min_score, sw_hit* d_hits, int64_t* d_nhits, int shift, uint32_t* d_hist, void* stream_) {
     hipStream_t stream = (hipStream_t)stream_;
     swp::SearchTopPlan plan;
     if (int rc = plan_top_call(c, who, nqueries, db->ntargets, top, d_hits, d_nhits, c->opt_search_results_mib << 20, plan)) return rc;
     c->last_search_multi_packed_launches = 0;   // (a call that launches no kernel reports none)
+    if (d_hist) c->last_score_hist_launches = c->last_score_hist_slices = 0;
     if (nqueries == 0) return SW_OK;
     DevOrder order(c, stream, false);
     if (order.rc) return order.rc;
@@ -701,29 +726,93 @@ static int db_search_top_call(const char* who, sw_ctx* c, const sw_db* db, const
     for (const swp::TopChunk& ch : plan.chunk) {
         if (db->ntargets > 0)
             if (int rc = run_search_multi(c, db, src, qoffsets + ch.q0, ch.nq, c->d_tres, stream)) return rc;
+        if (d_hist)
+            if (int rc = launch_score_hist(c, db, c->d_tres, ch.nq, shift, d_hist + ch.q0 * swp::kScoreHistCells, stream)) return rc;
         if (int rc = select_top(c, plan, c->d_tres, ch.nq, db->ntargets, top, min_score, d_hits + ch.q0 * top, d_nhits + ch.q0, stream)) return rc;
     }
     c->last_search_top_chunks = (int64_t)plan.chunk.size(); c->last_search_top_kernel = plan.kernel;
     return SW_OK;
 }
 
+// The sequence form behind its checks: d_hist == NULL is the plain call, `stats` says which of the two was asked for.
+static int db_search_affine_top(const char* who, bool stats, sw_ctx* c, const sw_db* db, const char* d_queries, const int64_t* qoffsets, int64_t nqueries,
+                                const sw_affine* scoring, int64_t top, int64_t min_score, sw_hit* d_hits, int64_t* d_nhits, int shift, uint32_t* d_hist,
+                                void* stream_) {
+    if (int rc = check_db_call(who, c, db, d_queries && qoffsets && scoring && (d_hist || !stats))) return rc;
+    if (stats && (shift < 0 || shift > SW_HIST_SHIFT_MAX)) { set_err("%s: shift = %d is out of range 0..%d", who, shift, SW_HIST_SHIFT_MAX); return SW_EINVAL; }
+    int64_t maxq = 0;
+    if (int rc = swh::check_search_multi(who, qoffsets, nqueries, db->longest, scoring, &maxq)) return rc;
+    return db_search_top_call(who, c, db, QuerySource::sequences(d_queries, scoring), qoffsets, nqueries, top, min_score, d_hits, d_nhits, shift, d_hist, stream_);
+}
+
+// ... and the matrix form.
+static int db_search_pssm_top(const char* who, bool stats, sw_ctx* c, const sw_db* db, const int8_t* d_pssm, const int64_t* qoffsets, int64_t nqueries,
+                              const sw_pssm_scoring* scoring, int64_t top, int64_t min_score, sw_hit* d_hits, int64_t* d_nhits, int shift, uint32_t* d_hist,
+                              void* stream_) {
+    if (int rc = check_db_call(who, c, db, d_pssm && qoffsets && scoring && (d_hist || !stats))) return rc;
+    if (stats && (shift < 0 || shift > SW_HIST_SHIFT_MAX)) { set_err("%s: shift = %d is out of range 0..%d", who, shift, SW_HIST_SHIFT_MAX); return SW_EINVAL; }
+    int64_t maxq = 0;
+    unsigned char code[256];
+    if (int rc = swh::check_search_pssm(who, qoffsets, nqueries, db->longest, scoring, &maxq, code)) return rc;
+    return db_search_top_call(who, c, db, QuerySource::matrix(d_pssm, scoring, code), qoffsets, nqueries, top, min_score, d_hits, d_nhits, shift, d_hist, stream_);
+}
+
 int sw_db_search_affine_top(sw_ctx* c, const sw_db* db, const char* d_queries, const int64_t* qoffsets, int64_t nqueries, const sw_affine* scoring,
                             int64_t top, int64_t min_score, sw_hit* d_hits, int64_t* d_nhits, void* stream_) {
-    if (int rc = check_db_call("sw_db_search_affine_top", c, db, d_queries && qoffsets && scoring)) return rc;
-    int64_t maxq = 0;
-    if (int rc = swh::check_search_multi("sw_db_search_affine_top", qoffsets, nqueries, db->longest, scoring, &maxq)) return rc;
-    return db_search_top_call("sw_db_search_affine_top", c, db, QuerySource::sequences(d_queries, scoring), qoffsets, nqueries, top, min_score, d_hits, d_nhits,
-                              stream_);
+    return db_search_affine_top("sw_db_search_affine_top", false, c, db, d_queries, qoffsets, nqueries, scoring, top, min_score, d_hits, d_nhits, 0, nullptr, stream_);
 }
 
 int sw_db_search_pssm_top(sw_ctx* c, const sw_db* db, const int8_t* d_pssm, const int64_t* qoffsets, int64_t nqueries, const sw_pssm_scoring* scoring,
                           int64_t top, int64_t min_score, sw_hit* d_hits, int64_t* d_nhits, void* stream_) {
-    if (int rc = check_db_call("sw_db_search_pssm_top", c, db, d_pssm && qoffsets && scoring)) return rc;
-    int64_t maxq = 0;
-    unsigned char code[256];
-    if (int rc = swh::check_search_pssm("sw_db_search_pssm_top", qoffsets, nqueries, db->longest, scoring, &maxq, code)) return rc;
-    return db_search_top_call("sw_db_search_pssm_top", c, db, QuerySource::matrix(d_pssm, scoring, code), qoffsets, nqueries, top, min_score, d_hits, d_nhits,
+    return db_search_pssm_top("sw_db_search_pssm_top", false, c, db, d_pssm, qoffsets, nqueries, scoring, top, min_score, d_hits, d_nhits, 0, nullptr, stream_);
+}
+
+// The same searches with the score histogram of every query (include/swhip.h: the statistics of a many-query search).
+int sw_db_search_affine_top_stats(sw_ctx* c, const sw_db* db, const char* d_queries, const int64_t* qoffsets, int64_t nqueries, const sw_affine* scoring,
+                                  int64_t top, int64_t min_score, sw_hit* d_hits, int64_t* d_nhits, int shift, uint32_t* d_hist, void* stream_) {
+    return db_search_affine_top("sw_db_search_affine_top_stats", true, c, db, d_queries, qoffsets, nqueries, scoring, top, min_score, d_hits, d_nhits, shift, d_hist,
+                                stream_);
+}
+
+int sw_db_search_pssm_top_stats(sw_ctx* c, const sw_db* db, const int8_t* d_pssm, const int64_t* qoffsets, int64_t nqueries, const sw_pssm_scoring* scoring,
+                                int64_t top, int64_t min_score, sw_hit* d_hits, int64_t* d_nhits, int shift, uint32_t* d_hist, void* stream_) {
+    return db_search_pssm_top("sw_db_search_pssm_top_stats", true, c, db, d_pssm, qoffsets, nqueries, scoring, top, min_score, d_hits, d_nhits, shift, d_hist,
                               stream_);
+}
+
+// The score histogram of a table the caller holds.
+int sw_score_hist_device(sw_ctx* c, const sw_db* db, const sw_result* d_results, int64_t nqueries, int shift, uint32_t* d_hist, void* stream_) {
+    const char* who = "sw_score_hist_device";
+    if (int rc = check_db_call(who, c, db, true)) return rc;
+    if (int rc = swh::check_score_hist(who, d_results, nqueries, db->ntargets, shift, d_hist)) return rc;
+    c->last_score_hist_launches = c->last_score_hist_slices = 0;   // (a call that launches no kernel reports none)
+    if (nqueries == 0) return SW_OK;
+    hipStream_t stream = (hipStream_t)stream_;
+    HIP_TRY(hipSetDevice(c->device));
+    DevOrder order(c, stream, false);
+    if (order.rc) return order.rc;
+    return launch_score_hist(c, db, d_results, nqueries, shift, d_hist, stream);
+}
+
+// The thresholds of sw_score_thresholds on a hit table (sw_score_hist.hip): one launch, one workgroup per query.
+int sw_hits_threshold_device(sw_ctx* c, const sw_db* db, const int64_t* d_thresholds, int64_t nqueries, int64_t top, const sw_hit* d_hits, const int64_t* d_nhits,
+                             sw_hit* d_hits_out, int32_t* d_keep, int64_t* d_nkept, void* stream_) {
+    const char* who = "sw_hits_threshold_device";
+    if (int rc = check_db_call(who, c, db, true)) return rc;
+    if (int rc = swh::check_hits_threshold(who, d_thresholds, nqueries, db->ntargets, top, d_hits, d_hits_out, d_keep)) return rc;
+    const swp::HitsThresholdPlan plan = swp::plan_hits_threshold(nqueries);
+    if (plan.grid == 0) return SW_OK;
+    hipStream_t stream = (hipStream_t)stream_;
+    HIP_TRY(hipSetDevice(c->device));
+    DevOrder order(c, stream, false);
+    if (order.rc) return order.rc;
+    swk::HitsThresholdParams kp;
+    memset(&kp, 0, sizeof kp);
+    kp.offsets = db->d_offsets; kp.ntargets = db->ntargets; kp.thresholds = d_thresholds; kp.nq = nqueries; kp.top = top;
+    kp.hits = d_hits; kp.nhits = d_nhits; kp.hits_out = d_hits_out; kp.keep = d_keep; kp.nkept = d_nkept;
+    hipLaunchKernelGGL(swk::sw_hits_threshold, dim3((unsigned)plan.grid), dim3(256), 0, stream, kp);
+    HIP_TRY(hipGetLastError());
+    return SW_OK;
 }
 
 // The alignments of a device hit table (csrc/sw_align_hits.hip).  Per call the host checks and plans the QUERIES (O(nqueries)) against

@@ -31,6 +31,9 @@ SW_HIDDEN int check_msa(const char* who, const int64_t* qoffsets, int64_t nqueri
                         int64_t ops_cap, const void* cols, const void* rows, const void* a3m, int64_t a3m_cap, const void* a3m_bytes);   // sw_hits_host.cpp
 SW_HIDDEN int check_msa_filter(const char* who, const int64_t* qoffsets, int64_t nqueries, int64_t top, const void* cols, const sw_msa_filter* filter,
                                const void* hits, const void* hits_out, const void* keep);            // sw_hits_host.cpp
+SW_HIDDEN int check_score_hist(const char* who, const void* results, int64_t nqueries, int64_t ntargets, int shift, const void* hist);   // sw_score_stats.cpp
+SW_HIDDEN int check_hits_threshold(const char* who, const void* thresholds, int64_t nqueries, int64_t ntargets, int64_t top, const void* hits,
+                                   const void* hits_out, const void* keep);                          // sw_score_stats.cpp
 SW_HIDDEN void pssm_update_table(const sw_submat* sub, const char* letters, int n, int8_t* S);        // sw_hits_host.cpp
 SW_HIDDEN int check_targets(const char* who, int64_t qlen, const int64_t* offsets, int64_t ntargets, int64_t* maxlen_out, int64_t* nonempty_out);
 }
@@ -277,6 +280,11 @@ struct SW_HIDDEN sw_ctx {
     Workspace<unsigned long long> d_msafilt;
     int64_t opt_msa_filter_workspace_mib = 256;
     int64_t last_msa_filter_launches = 0, last_msa_filter_chunks = 0;
+    // the score histogram (sw_score_hist_device, the _top_stats searches) and the thresholds of a hit table: no workspace; the LDS
+    // copies per workgroup ("score_hist_copies": 0 = the planner's choice) and what the last call did
+    int64_t opt_score_hist_copies = 0;
+    int64_t last_score_hist_launches = 0, last_score_hist_slices = 0;
+    int score_hist_lds_set = 0;         // the dynamic-LDS limit the kernel has been given (bytes)
     // ---- placement of the output matrices (sw_place.hip)
     int64_t opt_place_hold_gib = 0;     // sw_alloc_outputs: GiB a pair of small matrices may hold beside itself where no plain candidate is good (0: none)
     int64_t opt_place_budget_ms = 1500; // sw_alloc_outputs: time the search for a P in another class of the HBM may take

@@ -258,6 +258,36 @@ struct MsaFilterParams {
 __global__ void sw_msa_filter_pairs(MsaFilterParams p);
 __global__ void sw_msa_filter_greedy(MsaFilterParams p);
 
+// sw_score_hist.hip: the score histogram of a query-major result table (sw_score_hist_device and the _top_stats searches), as
+// swp::plan_score_hist cuts it, and the thresholds of a hit table (sw_hits_threshold_device), one workgroup per query.
+// score_class / score_bin are the rule of include/swhip.h, shared by both kernels.
+__host__ __device__ inline int score_class(int64_t len) {   // len >= 1
+    if (len < 2) return 0;
+    const int e = 63 - __builtin_clzll((unsigned long long)len);
+    return 2 * e + (int)((len >> (e - 1)) & 1);
+}
+__host__ __device__ inline int score_bin(int64_t v, int shift) {
+    const int64_t b = (v > 0 ? v : 0) >> shift;
+    return b < 255 ? (int)b : 255;
+}
+struct ScoreHistParams {
+    const sw_result* results;                    // nq x ntargets, query-major
+    const int64_t* offsets;                      // the handle's ntargets + 1 offsets
+    int64_t ntargets, nq;
+    int64_t slices_per_query, slice, items;
+    int shift, copies;
+    unsigned int* hist;                          // nq x 40 x 256, zeroed on the stream before the launch
+};
+__global__ void sw_score_hist(ScoreHistParams p);
+struct HitsThresholdParams {
+    const int64_t* offsets; int64_t ntargets;    // the handle's offsets
+    const int64_t* thresholds;                   // nq x 40
+    int64_t nq, top;
+    const sw_hit* hits; const int64_t* nhits;    // nq x top; nq or NULL
+    sw_hit* hits_out; int* keep; int64_t* nkept; // each may be NULL
+};
+__global__ void sw_hits_threshold(HitsThresholdParams p);
+
 // sw_search_pairs.hip: the scores of a device list of (query, target) pairs (sw_db_search_affine_pairs).  Per (chunk of the list, group
 // of queries) two binning launches turn the usable pairs into work items, one list per class, heaviest bucket first
 // (swp::plan_search_pairs); one launch of sw_search_affine_pairs_wave<C> per class scores them.

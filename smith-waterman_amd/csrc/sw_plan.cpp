@@ -915,6 +915,32 @@ MsaFilterPlan plan_msa_filter(const MsaFilterJob& j) {
     return p;
 }
 
+ScoreHistPlan plan_score_hist(const ScoreHistJob& j) {
+    ScoreHistPlan p;
+    // one copy by default: the adds of a wave into one address are serialised inside its own instruction whichever copy they go to, and
+    // one copy leaves room for four workgroups per CU (DESIGN 9y has the measurement)
+    p.copies = j.copies == 2 || j.copies == 4 ? j.copies : 1;
+    p.lds_bytes = p.copies * kScoreHistCells * 4;
+    if (j.nqueries < 1 || j.ntargets < 1) return p;
+    const int64_t want = std::max<int64_t>(1, (int64_t)std::max(j.num_cus, 1) * kScoreHistWgsPerCu / j.nqueries);
+    const int64_t most = std::max<int64_t>(1, j.ntargets / kScoreHistMinSlice);
+    p.slices_per_query = std::min({want, most, kScoreHistMaxSlices});
+    p.slice = (j.ntargets + p.slices_per_query - 1) / p.slices_per_query;
+    p.slices_per_query = (j.ntargets + p.slice - 1) / p.slice;   // (no empty slice)
+    p.items = j.nqueries * p.slices_per_query;
+    p.grid = std::min(p.items, kPssmHitsGridMax);
+    p.launches = 1;
+    return p;
+}
+
+HitsThresholdPlan plan_hits_threshold(int64_t nqueries) {
+    HitsThresholdPlan p;
+    if (nqueries < 1) return p;
+    p.grid = std::min(nqueries, kPssmHitsGridMax);
+    p.launches = 1;
+    return p;
+}
+
 void align_schedule(const int64_t* offsets, const int64_t* hits, int64_t nhits, swk::SearchItem* items) {
     std::vector<int64_t> order((size_t)nhits);
     for (int64_t h = 0; h < nhits; ++h) order[(size_t)h] = h;

@@ -659,6 +659,41 @@ struct MsaFilterPlan {
 
 MsaFilterPlan plan_msa_filter(const MsaFilterJob& job);
 
+// ---- the score histogram of a result table (sw_score_hist_device, the _top_stats searches; sw_score_hist.hip).  One launch of 256
+// threads per call or chunk.  A query's histogram is kScoreHistClasses x kScoreHistBins uint32 counters, 40 KiB; a workgroup keeps
+// `copies` private ones in LDS (wave w adds into copy w % copies), so copies x 40 KiB <= the CU's 160 KiB.  Work item w of the
+// nqueries x slices_per_query is (query w / slices_per_query, targets [s x slice, min(ntargets, (s + 1) x slice)) with s = w %
+// slices_per_query): every target of every query lies in exactly one item.  Slices: as many as give every CU kScoreHistWgsPerCu
+// workgroups, but no slice below kScoreHistMinSlice targets -- zeroing and flushing 10 240 counters costs a workgroup as much as 40
+// targets per thread -- and at most kScoreHistMaxSlices, which bounds the adds into one global counter.  The grid is walked in strides
+// of at most kPssmHitsGridMax workgroups.
+constexpr int kScoreHistClasses = 40;        // SW_HIST_CLASSES: half octaves of the target's length, lengths below 2^20
+constexpr int kScoreHistBins = 256;          // SW_HIST_BINS
+constexpr int64_t kScoreHistCells = (int64_t)kScoreHistClasses * kScoreHistBins;
+constexpr int64_t kScoreHistLdsMax = 160 << 10;
+constexpr int64_t kScoreHistMinSlice = 4096;
+constexpr int64_t kScoreHistMaxSlices = 1024;
+constexpr int kScoreHistWgsPerCu = 4;
+
+struct ScoreHistJob {
+    int64_t nqueries = 0, ntargets = 0;
+    int num_cus = 256;
+    int copies = 0;                          // "score_hist_copies": 0 = the planner's choice, or 1 / 2 / 4 LDS copies per workgroup
+};
+
+struct ScoreHistPlan {
+    int64_t slices_per_query = 0, slice = 0; // (0: nothing to count)
+    int64_t items = 0, grid = 0;             // nqueries x slices_per_query work items; workgroups launched
+    int copies = 0; int64_t lds_bytes = 0;   // LDS histograms of a workgroup and their bytes (dynamic LDS of the launch)
+    int launches = 0;
+};
+
+ScoreHistPlan plan_score_hist(const ScoreHistJob& job);
+
+// ---- the thresholds of a hit table (sw_hits_threshold_device; sw_score_hist.hip): one workgroup of 256 threads per query.
+struct HitsThresholdPlan { int64_t grid = 0; int launches = 0; };
+HitsThresholdPlan plan_hits_threshold(int64_t nqueries);
+
 // ---- alignment of chosen hits under affine scoring (sw_align_affine_device): sw_align_affine_wave<C> for C = 4, 8, 16, its index in
 // kAlignAffine (sw_api_search.hip, which checks its order against it at compile time)
 constexpr int kAlignAffineKernels = 3;
