@@ -893,6 +893,63 @@ int  sw_hits_threshold_device(sw_ctx* ctx, const sw_db* db, const int64_t* d_thr
 int  sw_hits_threshold_host(const int64_t* offsets, int64_t ntargets, const int64_t* thresholds, int64_t nqueries, int64_t top,
                             const sw_hit* hits, const int64_t* nhits, sw_hit* hits_out, int32_t* keep, int64_t* nkept);
 
+/* LOW-COMPLEXITY MASKING of a database, on the device (csrc/sw_mask.hip): the stage in front of the search loop.  Compositionally
+ * biased stretches (poly-Q, SGSGSG..., collagen-like repeats) score high against each other without being related, and the E-values
+ * above make it worse: such targets are the outliers the trimmed fit removes from the null line.  The call writes a MASKED COPY of a
+ * handle's bytes with the same offsets; the caller makes a second handle over it (sw_db_create(ctx, d_out, offsets, ntargets, &masked))
+ * and searches, selects, aligns and updates on that one, while hit tables and ops carry indices, not letters, so sw_db_msa_from_hits
+ * can still be given the UNMASKED handle: the A3M keeps the original letters (what BLAST calls soft masking).
+ * THE RULE is the first stage of SEG (Wootton & Federhen 1993) -- trigger windows, extended through overlapping windows of slightly
+ * higher complexity -- restated in integers.  SEG's second stage, which trims each raw segment by a log-probability optimisation, is
+ * floating point and deliberately left out: this masker is somewhat GREEDIER AT THE SEGMENT ENDS than `seg`.  Per target t[0 .. len):
+ *   sw_mask_params : window W, 2..64 (SEG: 12); trigger_mbits K1 and extend_mbits K2, 0 <= K1 <= K2, entropy in thousandths of a bit
+ *                (SEG: 2200, 2500); letters / nletters, the alphabet, 1..32 distinct bytes -- every other byte is NO LETTER;
+ *                mask_byte, what a masked position becomes.
+ *   G          : G[c] = floor(c x log2(c) x 65536 + 0.5), c = 0..64, G[0] = G[1] = 0: 65 integer literals in csrc/sw_mask_table.h,
+ *                which the kernel and the host leg both include; never computed at run time.
+ *   valid(i)   : i + W <= len and none of t[i .. i + W) is a no-letter.  Windows never cross a target's end.
+ *   D(i)       : for a valid start, G[W] - SUM_k G[c_k], c_k the count of letters[k] in the window: W x 65536 x the window's Shannon
+ *                entropy in bits, an integer >= 0.
+ *   low1(i)    : valid(i) and 1000 x D(i) <= K1 x W x 65536, that is D(i) <= floor(K1 x W x 65536 / 1000); low2(i) the same with K2.
+ *                The host computes the two right-hand sides once in 64-bit integers; the kernel compares int32.
+ *   run        : a maximal sequence of consecutive starts s .. e with low2; TRIGGERED when low1 holds for at least one of them.
+ *   masked(p)  : p lies in [s, e + W) of a triggered run.
+ *   out[p]     : mask_byte where masked(p), t[p] verbatim otherwise, for any byte 0..255.
+ *   So: a target shorter than W is never masked, an empty target contributes nothing.  No floats: device, host leg and any
+ *   restatement agree bit for bit, every run writes the same bytes.
+ * sw_db_mask_low_complexity:
+ *   db         : a handle over the UNMASKED bytes.
+ *   d_out      : device memory laid out like the handle's d_db: byte p of d_out answers byte p of d_db.  Exactly
+ *                [offsets[0], offsets[ntargets]) is written, nothing outside.  d_out == d_db (in place) is REFUSED; buffers that
+ *                overlap in part are the caller's error and are not detected.
+ *   d_nmasked  : device, ntargets int64, optional: the masked positions per target, EVERY entry written, 0 for an empty target.
+ *   Asynchronous on `stream`, no host round trip, host work O(1): the lengths come from the handle's device copy of the offsets.
+ *   (As with every workspace of the context: the first call that needs a larger one than any call before waits for the stream once
+ *   and allocates.)
+ *   Flat over the concatenated bytes in tiles of swp::kMaskTile positions (swp::plan_mask), whatever the targets' lengths; per
+ *   position two bits (low1, low2) and the mask bit in a workspace of the context.  Launches: WINDOWS (one workgroup per tile: letter
+ *   classes and target ends staged in LDS, a lane slides over consecutive starts with its counts in LDS, a summary per tile), CARRIES
+ *   (one workgroup: for every tile border, whether the run that crosses it is triggered anywhere, however far away), APPLY (triggers
+ *   spread through runs a 64-position word at a time by add-with-carry, dilated by W, the bytes written) and, with d_nmasked, COUNT
+ *   (population counts of the mask bits between a target's offsets; no atomics).  "last_mask_launches" and "last_mask_tiles" report
+ *   the last call, "mask_tile" (read-only) the positions of a tile.  A handle without letters launches nothing but the zeroes of d_nmasked.
+ *   QUERIES need no call of their own: a handle over the query bytes (sw_db_create on d_queries and the query offsets) costs next to
+ *   nothing; on the host sw_mask_low_complexity_host serves them as it serves targets.
+ *   SW_EINVAL before any launch: NULL pointers; a handle of another context's device; d_out == d_db; window outside 2..64;
+ *   trigger_mbits < 0, extend_mbits < trigger_mbits, or a value for which K x W x 65536 leaves int64; nletters outside 1..32 or a
+ *   letter named twice.
+ * sw_mask_low_complexity_host: the CPU leg, the rule restated window by window in plain C++ from host memory.  seq and out are indexed
+ *   by the offsets themselves (seq + offsets[t]); out == seq is refused likewise; SW_EINVAL besides for negative or decreasing offsets. */
+typedef struct {
+    int64_t trigger_mbits, extend_mbits;
+    int32_t window, nletters;
+    unsigned char letters[32];
+    unsigned char mask_byte;
+} sw_mask_params;
+int  sw_db_mask_low_complexity(sw_ctx* ctx, const sw_db* db, const sw_mask_params* params, char* d_out, int64_t* d_nmasked, void* stream);
+int  sw_mask_low_complexity_host(const char* seq, const int64_t* offsets, int64_t ntargets, const sw_mask_params* params, char* out,
+                                 int64_t* nmasked);
+
 /* Tables.  sw_submat_match: s[x][y] = x == y ? match : mismatch (matchMissmatchScore, serial_smithW.c:251-256; both must fit int8:
  * the builder returns nothing, so it clamps them to -128..127 -- a caller that takes them from a user checks the range first, as
  * smithW and the Python wrapper do, which refuse such scores).  sw_submat_from_letters: `scores` is n x n, row = query letter, over the n bytes of

@@ -85,6 +85,10 @@
   after a warm-up, ALTERNATING; a leg whose warm-up call takes more than 20 s is timed by that call alone (*_calls says how many calls
   stand behind a median).  (b) a weighted iteration (--pssm-weights (b)) beside one with msa_from_hits_device (column rows) and
   msa_filter_device in front of the weights, which with the update then read the filtered table
+  --mask: data set (a) only.  (1) mask_low_complexity_device (SEG's window and bounds over the 20 letters) with and without the counts,
+  beside torch.clone and copy_ of the same bytes and beside the path a caller had before -- D2H, mask_low_complexity_host, H2D (3 calls);
+  7 calls each, alternating, medians; the outputs compared byte for byte (the run fails if they differ).  (2) the iteration by E-value
+  of --score-stats on the plain handle and on a handle over the masked copy
   --score-stats: data set (a) only, 64 queries, top 100.  (1) search_affine_top_stats_device beside search_affine_top_device, 7 calls
   each after a warm-up, wall clock around a synchronised call, ALTERNATING; hits, counts and -- against score_hist_device over the full
   table -- histograms compared byte for byte (the run fails if they differ).  (2) score_hist_device alone over the full 64 x 200 000
@@ -148,6 +152,7 @@ def main():
     ap.add_argument("--msa", action="store_true", help="data set (a) only: the query-anchored alignment of the top 10 / 100 / 4096 hits of 64 queries on the device against the host round trip")
     ap.add_argument("--msa-filter", action="store_true", help="data set (a) only: the filter of the column rows of the top 10 / 100 / 4096 hits of 64 queries on the device against the host round trip, and a weighted iteration with and without it")
     ap.add_argument("--score-stats", action="store_true", help="data set (a) only: the score histogram inside the top search and alone, the fit's round trip, an iteration by E-value beside one by raw score")
+    ap.add_argument("--mask", action="store_true", help="data set (a) only: the low-complexity mask on the device beside a plain device copy and the host round trip, and an iteration by E-value on the plain and on the masked handle")
     ap.add_argument("--lanes", action="store_true", help="data set (a) only: 64 queries under search_lanes 32 and 16, alternating, full tables and top 10")
     ap.add_argument("--pairs-lanes", action="store_true", help="data set (a) only: pair lists of all, 10 %% and 1 %% of the cross product under search_pairs_lanes 32 and 16, alternating")
     ap.add_argument("--top", action="store_true", help="data set (a) only: the best 100 targets of 64 queries by the full table and by the selection on the device")
@@ -971,6 +976,86 @@ def main():
         db1.close()
         db.close()
 
+    def mask_leg(packed, offs, nq=64, reps=7, top=100, evalue=1e-3):
+        import time
+        d_db = torch.from_numpy(packed.copy()).to(dev)
+        db = eng.prepare_db(d_db, offs)
+        nt, nbytes = len(offs) - 1, int(offs[-1])
+        P = "mask"
+        out[f"{P}_targets"], out[f"{P}_letters"], out[f"{P}_reps"] = nt, nbytes, reps
+        d_out, d_out2, d_host, d_copy = (torch.zeros_like(d_db) for _ in range(4))
+        d_n = torch.zeros(nt, dtype=torch.int64, device=dev)
+        state = {}
+
+        def wall(fn):                                                        # wall clock around a synchronised call
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            fn()
+            torch.cuda.synchronize()
+            return (time.perf_counter() - t0) * 1e3
+
+        def alternate(legs, reps=reps):
+            ms = {k: [] for k in legs}
+            for k in legs:
+                wall(legs[k])                                                # warm-up
+            for _ in range(reps):                                            # alternating: a drift of the device shows in all alike
+                for k in legs:
+                    ms[k].append(wall(legs[k]))
+            for k in legs:
+                out[f"{P}_{k}_ms"] = round(float(np.median(ms[k])), 4)
+                out[f"{P}_{k}_range_ms"] = [round(min(ms[k]), 4), round(max(ms[k]), 4)]
+
+        # (1) the device call, with and without the counts, beside a plain device copy of the same bytes
+        def host_path():                                                     # what a caller had before: D2H, the host leg, H2D
+            h = d_db.cpu().numpy()
+            state["host"] = swamd.mask_low_complexity_host((h, offs))
+            d_host.copy_(torch.from_numpy(state["host"][0]))
+
+        alternate({"device": lambda: db.mask_low_complexity_device(out=d_out, nmasked=d_n),
+                   "device_no_counts": lambda: db.mask_low_complexity_device(out=d_out2, nmasked=False),
+                   "clone": lambda: state.__setitem__("clone", torch.clone(d_db)),
+                   "copy": lambda: d_copy.copy_(d_db)})
+        alternate({"host_path": host_path}, reps=3)
+        db.mask_low_complexity_device(out=d_out, nmasked=d_n)
+        out[f"{P}_launches"], out[f"{P}_tiles"] = eng.get_option("last_mask_launches"), eng.get_option("last_mask_tiles")
+        torch.cuda.synchronize()
+        out[f"{P}_identical"] = bool(torch.equal(d_out, d_host) and torch.equal(d_out, d_out2) and (d_n.cpu().numpy() == state["host"][1]).all())
+        out[f"{P}_letters_masked"], out[f"{P}_targets_masked"] = int(d_n.sum().item()), int((d_n > 0).sum().item())
+        out[f"{P}_device_gbs"] = round(2 * nbytes / out[f"{P}_device_ms"] / 1e6, 1)
+        out[f"{P}_clone_gbs"] = round(2 * nbytes / out[f"{P}_clone_ms"] / 1e6, 1)
+        out[f"{P}_host_over_device"] = round(out[f"{P}_host_path_ms"] / out[f"{P}_device_ms"], 1)
+        out[f"{P}_device_over_clone"] = round(out[f"{P}_device_ms"] / out[f"{P}_clone_ms"], 2)
+        # (2) an iteration by E-value (the one of --score-stats) on the plain handle and on the masked one
+        dbm = eng.prepare_db(d_out, offs)
+        qoffs = np.arange(nq + 1, dtype=np.int64) * args.qlen
+        queries = rng.choice(PROTEIN, int(qoffs[-1])).astype(np.uint8)
+        m, moffs = swamd.pssm_from_queries((queries, qoffs), sub, letters)
+        d_m = torch.from_numpy(m.reshape(-1).copy()).to(dev)
+        pscoring, cap, least = (letters, -4, 127, -11, -1), 4 * args.qlen, -(1 << 63)
+        cells = nq * swamd.HIST_CLASSES * swamd.HIST_BINS
+        d_thr = torch.empty(nq * swamd.HIST_CLASSES, dtype=torch.int64, device=dev)
+        d_inc = torch.empty(nq * top * 3, dtype=torch.int64, device=dev)
+        d_next = torch.empty_like(d_m)
+        legs = {}
+        for name, h_ in (("plain", db), ("masked", dbm)):
+            hist, hist2 = (torch.empty(cells, dtype=torch.int32, device=dev) for _ in range(2))
+            hits, nhits, _ = h_.search_pssm_top_stats_device(d_m, moffs, pscoring, top, 1, 0, hist=hist)
+            aln, ops = h_.align_pssm_hits_device(d_m, moffs, pscoring, hits, nhits, ops_cap=cap)
+            h2 = (torch.zeros_like(hits).view(-1), torch.zeros_like(nhits))
+
+            def iteration(h_=h_, hist=hist, hist2=hist2, hits=hits, nhits=nhits, aln=aln, ops=ops, h2=h2):
+                fit = swamd.score_fit(hist.cpu().numpy().view(np.uint32).reshape(nq, swamd.HIST_CLASSES, swamd.HIST_BINS), 0)
+                d_thr.copy_(torch.from_numpy(swamd.score_thresholds(fit, evalue).reshape(-1)))
+                h_.hits_threshold_device(d_thr, nq, top, hits.view(-1), nhits, hits_out=d_inc, keep=False, nkept=False)
+                h_.align_pssm_hits_device(d_m, moffs, pscoring, hits, nhits, ops_cap=cap, out=(aln, ops))
+                h_.pssm_from_hits_device(d_m, moffs, pscoring, (sub, 10, least), d_inc.view(nq, top, 3), nhits, aln, ops, cap, out=d_next)
+                h_.search_pssm_top_stats_device(d_next, moffs, pscoring, top, 1, 0, out=h2, hist=hist2)
+            legs[f"{name}_iteration"] = iteration
+        alternate(legs)
+        out[f"{P}_masked_over_plain_iteration"] = round(out[f"{P}_masked_iteration_ms"] / out[f"{P}_plain_iteration_ms"], 4)
+        dbm.close()
+        db.close()
+
     def pssm_weights_leg(packed, offs, nq=64, reps=7, per_hit=16):
         import time
         d_db = torch.from_numpy(packed.copy()).to(dev)
@@ -1242,7 +1327,9 @@ def main():
     out["a_letters"] = int(offs[-1])
     out["a_len_median"] = int(np.median(lens))
     out["a_len_max"] = int(lens.max())
-    if args.multi or args.top or args.align_hits or args.pairs or args.prefilter or args.prefiltered_top or args.pssm or args.pssm_iterate or args.pssm_weights or args.msa or args.msa_filter or args.score_stats or args.lanes or args.pairs_lanes:
+    if args.multi or args.top or args.align_hits or args.pairs or args.prefilter or args.prefiltered_top or args.pssm or args.pssm_iterate or args.pssm_weights or args.msa or args.msa_filter or args.score_stats or args.mask or args.lanes or args.pairs_lanes:
+        if args.mask:
+            mask_leg(packed, offs)
         if args.score_stats:
             score_stats_leg(packed, offs)
         if args.lanes:
@@ -1287,6 +1374,8 @@ def main():
             sys.exit("bench_search.py --msa: msa_identical is false")
         if args.score_stats and not out["score_stats_identical"]:
             sys.exit("bench_search.py --score-stats: score_stats_identical is false")
+        if args.mask and not out["mask_identical"]:
+            sys.exit("bench_search.py --mask: mask_identical is false")
         if args.msa_filter and not out["msa_filter_identical"]:
             sys.exit("bench_search.py --msa-filter: msa_filter_identical is false")
         if args.pssm and not out["pssm_identical"]:

@@ -235,13 +235,18 @@ def gen_score_hist(r):
               num_cus=r.choice([1, 256, 304]), copies=r.choice([0, 0, 1, 2, 4]))
 
 
+def gen_mask(r):
+    return kv(letters=r.choice([0, 1, 63, 64, 4095, 4096, 4097, 70_000_000, (1 << 31) - 1, 1 << 33]), ntargets=r.choice([0, 1, 255, 256, 257, 200_000, 1 << 30]),
+              window=r.choice([2, 12, 63, 64]), count=r.choice([0, 1]))
+
+
 GENERATORS = {"search_multi_plan_driver": gen_search_multi, "search_multi_lanes_plan_driver": gen_search_multi_lanes, "prefilter_plan_driver": gen_prefilter,
               "search_pairs_plan_driver": gen_search_pairs, "search_pairs_lanes_plan_driver": gen_search_pairs_lanes, "align_hits_plan_driver": gen_align_hits,
               "align_ckpt_plan_driver": gen_align_ckpt, "align_affine_plan_driver": gen_align_affine, "search_affine_plan_driver": gen_search_affine,
               "fill_plan_driver": gen_fill, "prologue_plan_driver": gen_prologue, "search_top_plan_driver": gen_search_top,
               "top_pairs_plan_driver": gen_top_pairs, "pssm_hits_plan_driver": gen_pssm_hits,
               "pssm_weights_plan_driver": gen_pssm_weights, "msa_hits_plan_driver": gen_msa_hits,
-              "msa_filter_plan_driver": gen_msa_filter, "score_hist_plan_driver": gen_score_hist}
+              "msa_filter_plan_driver": gen_msa_filter, "mask_plan_driver": gen_mask, "score_hist_plan_driver": gen_score_hist}
 
 
 def random_cases(n, seed):

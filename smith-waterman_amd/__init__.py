@@ -63,6 +63,11 @@ class _MsaFilter(ctypes.Structure):   # sw_msa_filter
     _fields_ = [("max_ident_pct", ctypes.c_int32), ("min_cover_pct", ctypes.c_int32)]
 
 
+class _MaskParams(ctypes.Structure):   # sw_mask_params
+    _fields_ = [("trigger_mbits", ctypes.c_int64), ("extend_mbits", ctypes.c_int64), ("window", ctypes.c_int32), ("nletters", ctypes.c_int32),
+                ("letters", ctypes.c_ubyte * 32), ("mask_byte", ctypes.c_ubyte)]
+
+
 # every symbol include/swhip.h declares: (restype, argtypes)
 _vp, _i64, _i32, _u32, _sz = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_uint32, ctypes.c_size_t
 ABI = {
@@ -118,6 +123,8 @@ ABI = {
     "sw_msa_from_hits_host": (_i32, [_vp, _vp, _i64, _vp, _vp, _i64, _i64, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _vp]),
     "sw_msa_filter_device": (_i32, [_vp, _vp, _vp, _vp, _i64, _i64, ctypes.POINTER(_MsaFilter), _vp, _vp, _vp, _vp, _vp]),
     "sw_msa_filter_host": (_i32, [_vp, _vp, _vp, _i64, _i64, ctypes.POINTER(_MsaFilter), _vp, _vp, _vp, _vp]),
+    "sw_db_mask_low_complexity": (_i32, [_vp, _vp, ctypes.POINTER(_MaskParams), _vp, _vp, _vp]),
+    "sw_mask_low_complexity_host": (_i32, [_vp, _vp, _i64, ctypes.POINTER(_MaskParams), _vp, _vp]),
     "sw_score_hist_device": (_i32, [_vp, _vp, _vp, _i64, _i32, _vp, _vp]),
     "sw_score_hist_host": (_i32, [_vp, _i64, _vp, _i64, _i32, _vp]),
     "sw_db_search_affine_top_stats": (_i32, [_vp, _vp, _vp, _vp, _i64, ctypes.POINTER(_Affine), _i64, _i64, _vp, _vp, _i32, _vp, _vp]),
@@ -717,6 +724,58 @@ def score_hist_host(results, targets_or_offsets, shift: int = 0):
     return hist[:nq]
 
 
+MASK_LETTERS = b"ACDEFGHIKLMNPQRSTVWY"
+
+
+def _mask_params(window=12, trigger_mbits=2200, extend_mbits=2500, letters=MASK_LETTERS, mask_byte=ord("X")):
+    """The sw_mask_params of the masking calls; the defaults are SEG's window and bounds over the 20 amino acids.  The C side checks the
+    ranges; here only what the struct cannot hold is refused."""
+    if isinstance(letters, str):
+        letters = letters.encode("latin-1")
+    letters = bytes(bytearray(letters))
+    if len(letters) > 32:
+        raise ValueError("letters: at most 32 letters")
+    if isinstance(mask_byte, (str, bytes, bytearray)):
+        if len(mask_byte) != 1:
+            raise ValueError("mask_byte must be one byte")
+        mask_byte = ord(mask_byte) if isinstance(mask_byte, str) else mask_byte[0]
+    if not 0 <= int(mask_byte) <= 255:
+        raise ValueError("mask_byte must be 0..255")
+    for name, v in (("window", window), ("trigger_mbits", trigger_mbits), ("extend_mbits", extend_mbits)):
+        bits = 31 if name == "window" else 63
+        if not -(1 << bits) <= int(v) < (1 << bits):
+            raise ValueError(f"{name} = {v} does not fit its field")
+    mp = _MaskParams(int(trigger_mbits), int(extend_mbits), int(window), len(letters))
+    for k, b in enumerate(letters):
+        mp.letters[k] = b
+    mp.mask_byte = int(mask_byte)
+    return mp
+
+
+def mask_low_complexity_host(targets, window=12, trigger_mbits=2200, extend_mbits=2500, letters=MASK_LETTERS, mask_byte=ord("X"), out=None):
+    """sw_mask_low_complexity_host: the low-complexity mask in plain C++ on the host (no GPU); it serves queries as it serves targets.
+    targets: a list of sequences or a (packed uint8, int64 offsets) pair; the rule and its parameters are stated in include/swhip.h.
+    Returns (masked, nmasked): the packed bytes with mask_byte at the masked positions -- a copy of the input outside
+    [offsets[0], offsets[-1]), or `out` (uint8, as long as the packed input), of which only that range is written -- and the (ntargets,)
+    int64 masked positions per target."""
+    packed, offs = _pack_targets(targets)
+    if len(offs) == 0:
+        offs = np.zeros(1, np.int64)
+    if len(packed) < int(offs[-1]):
+        raise ValueError(f"the packed bytes must hold at least {int(offs[-1])} bytes")
+    nt = len(offs) - 1
+    mp = _mask_params(window, trigger_mbits, extend_mbits, letters, mask_byte)
+    if out is None:
+        out = packed.copy()
+    if not isinstance(out, np.ndarray) or out.dtype != np.uint8 or not out.flags.c_contiguous or out.size < len(packed):
+        raise ValueError(f"out must be a contiguous uint8 array of at least {len(packed)} bytes")
+    one, one_out = np.zeros(1, np.uint8), np.zeros(1, np.uint8)
+    nmasked = np.zeros(max(1, nt), np.int64)
+    _check(lib().sw_mask_low_complexity_host((packed if len(packed) else one).ctypes.data, offs.ctypes.data, nt, ctypes.byref(mp),
+                                             (out if out.size else one_out).ctypes.data, nmasked.ctypes.data))
+    return out, nmasked[:nt]
+
+
 def _hists(hist):
     hist = np.ascontiguousarray(hist, np.uint32)
     if hist.ndim == 2:
@@ -1002,6 +1061,37 @@ class Database:
         v = [_i64() for _ in range(4)]
         _check(lib().sw_db_info(self._h, *[ctypes.byref(x) for x in v]))
         return dict(zip(("ntargets", "nonempty", "longest", "letters"), (x.value for x in v)))
+
+    def mask_low_complexity(self, window=12, trigger_mbits=2200, extend_mbits=2500, letters=MASK_LETTERS, mask_byte=ord("X")):
+        """The low-complexity mask of the handle's bytes on the device (sw_db_mask_low_complexity; include/swhip.h states the rule).
+        Returns (masked, nmasked): a fresh uint8 device tensor laid out like the handle's bytes -- mask_byte at the masked positions,
+        zero outside [offsets[0], offsets[-1]) -- and the (ntargets,) int64 device tensor of the masked positions per target.
+        Engine.prepare_db(masked, offsets) makes the handle to search; keep this one for msa_from_hits (the original letters)."""
+        masked, nmasked = self.mask_low_complexity_device(None, None, window, trigger_mbits, extend_mbits, letters, mask_byte)
+        return masked, nmasked[:self.ntargets]
+
+    def mask_low_complexity_device(self, out=None, nmasked=None, window=12, trigger_mbits=2200, extend_mbits=2500, letters=MASK_LETTERS,
+                                   mask_byte=ord("X")):
+        """sw_db_mask_low_complexity into caller tensors; asynchronous on torch's current stream, nothing comes to the host.  out: a
+        contiguous uint8 tensor at least as long as the handle's bytes and not those bytes themselves (None: a zeroed one); nmasked: a
+        contiguous int64 tensor of at least ntargets elements, None for a fresh one, False for none.  Returns (out, nmasked)."""
+        eng = self.engine
+        t = eng.torch
+        dev = f"cuda:{eng.device}"
+        if out is None:
+            out = t.zeros_like(self.d_db)
+        if out.dtype != t.uint8 or not out.is_contiguous() or out.numel() < self.d_db.numel():
+            raise ValueError(f"out must be a contiguous uint8 tensor of at least {self.d_db.numel()} elements")
+        if nmasked is None:
+            nmasked = t.empty(max(1, self.ntargets), dtype=t.int64, device=dev)
+        elif nmasked is False:
+            nmasked = None
+        if nmasked is not None and (nmasked.dtype != t.int64 or not nmasked.is_contiguous() or nmasked.numel() < self.ntargets):
+            raise ValueError(f"nmasked must be a contiguous int64 tensor of at least {self.ntargets} elements")
+        mp = _mask_params(window, trigger_mbits, extend_mbits, letters, mask_byte)
+        _check(lib().sw_db_mask_low_complexity(eng._h, self._h, ctypes.byref(mp), out.data_ptr(), nmasked.data_ptr() if nmasked is not None else None,
+                                               eng._stream()))
+        return out, nmasked
 
     def search_affine(self, queries, scoring):
         """Every query against every target (sw_db_search_affine).  queries: a list of sequences or a (packed uint8, int64 offsets) pair;

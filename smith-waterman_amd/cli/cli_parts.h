@@ -149,6 +149,53 @@ static std::vector<std::string> target_names(const char* flag, const char* path,
     return names;
 }
 
+// ---- --mask: the low-complexity mask of the database (sw_db_mask_low_complexity) and what the command line says about its rule
+struct MaskArgs {
+    bool on = false, has_sub = false;        // --mask; any of the sub-flags
+    int window = 12, trigger = 2200, extend = 2500;
+    const char *byte = "X", *letters = "ACDEFGHIKLMNPQRSTVWY";
+    sw_mask_params params() const {
+        sw_mask_params mp;
+        memset(&mp, 0, sizeof mp);
+        mp.window = window; mp.trigger_mbits = trigger; mp.extend_mbits = extend;
+        mp.nletters = (int32_t)std::min<size_t>(strlen(letters), 32);
+        memcpy(mp.letters, letters, (size_t)mp.nletters);
+        mp.mask_byte = (unsigned char)byte[0];
+        return mp;
+    }
+};
+// After the upload: the masked copy of the database in a second buffer, its letters on the host (what --align prints is what was
+// scored) and the handle over the UNMASKED bytes, through which --out-a3m writes the original letters.  Without --mask it is the
+// database as it was read and uploaded.  One line on stderr says what was masked.
+struct MaskedDb : NoCopy {
+    const Db& plain;
+    const DeviceBuffer& d_plain;
+    bool on;
+    Db host;
+    DeviceBuffer d_masked;
+    DbHandle unmasked;
+    MaskedDb(sw_ctx* ctx, const MaskArgs& m, const Db& db, const DeviceBuffer& d_db) : plain(db), d_plain(d_db), on(m.on) {
+        if (!on) return;
+        const sw_mask_params mp = m.params();
+        const size_t nrec = (size_t)std::max<int64_t>(1, db.nrec);
+        unmasked.create(ctx, d_db, db.offsets, db.nrec);
+        d_masked.alloc(ctx, (size_t)db.total + 16);
+        DeviceBuffer d_n(ctx, nrec * sizeof(int64_t));
+        CHECK(sw_db_mask_low_complexity(ctx, unmasked, &mp, d_masked.as<char>(), d_n.as<int64_t>(), nullptr));
+        CHECK(sw_synchronize(ctx, nullptr));
+        host = db;
+        d_masked.download(host.letters.data(), (size_t)db.total);
+        std::vector<int64_t> n(nrec, 0);
+        d_n.download(n.data(), (size_t)db.nrec * sizeof(int64_t));
+        long long letters = 0, targets = 0;
+        for (int64_t i = 0; i < db.nrec; ++i) { letters += n[(size_t)i]; targets += n[(size_t)i] > 0; }
+        fprintf(stderr, "smithW: --mask: %lld letters of %lld targets masked (of %lld letters, %lld targets)\n", letters, targets, (long long)db.total, (long long)db.nrec);
+    }
+    const Db& db() const { return on ? host : plain; }
+    const DeviceBuffer& buffer() const { return on ? d_masked : d_plain; }
+    sw_db* original(sw_db* searched) const { return on ? unmasked.p : searched; }   // the handle that holds the letters as they were read
+};
+
 // ---- the alignments of a table of hits on the host: K entries per row, ops_cap bytes of ops per entry
 struct AlignedHits {
     std::vector<sw_alignment> aln;
@@ -244,6 +291,7 @@ struct Options {
     bool has_evalue = false, has_include_evalue = false, has_score_shift = false;
     int score_shift = 0;
     const char *out_pssm = nullptr, *out_a3m = nullptr;
+    MaskArgs mask;
     sw_scores sc = {3, -3, -2};
     bool iterate() const { return iterations > 1 || out_pssm || out_a3m; }   // (--iterations 1 alone is the search of today, through today's path)
     bool stats() const { return has_evalue || has_include_evalue; }
@@ -264,5 +312,25 @@ static std::string score_stats_rule(const Options& o) {
     if (!(o.search_q && (o.all_queries || o.pssm_path))) return "--evalue / --include-evalue go with --search --all-queries or --search --pssm";
     if (o.has_include_evalue && o.has_include_score) return "--include-evalue does not go with --include-score";
     if (o.has_include_evalue && o.iterations < 2) return "--include-evalue goes with --iterations N (N > 1)";
+    return "";
+}
+
+// Which command lines --mask and its sub-flags go with, and the values they take: the message of the first rule broken, or none.
+// (tests/test_cli_mask_host.py holds every one; main() prints it as it prints its own.)
+static std::string mask_rule(const Options& o) {
+    char msg[256] = "";
+    const auto say = [&](const char* fmt, auto... v) { snprintf(msg, sizeof msg, fmt, v...); return std::string(msg); };
+    const MaskArgs& m = o.mask;
+    if (!m.on && !m.has_sub) return "";
+    if (!m.on) return "--mask-window / --mask-trigger / --mask-extend / --mask-byte / --mask-letters go with --mask";
+    if (!o.search_q) return "--mask goes with --search";
+    if (m.window < 2 || m.window > 64) return say("--mask-window W needs W within 2..64, got %d", m.window);
+    if (m.trigger < 0) return say("--mask-trigger MB needs MB >= 0 (thousandths of a bit), got %d", m.trigger);
+    if (m.extend < m.trigger) return say("--mask-extend MB needs MB >= the trigger's %d, got %d", m.trigger, m.extend);
+    if (strlen(m.byte) != 1) return say("--mask-byte C takes one character, got \"%s\"", m.byte);
+    const size_t n = strlen(m.letters);
+    if (n < 1 || n > 32) return say("--mask-letters STR takes 1..32 letters, got %d", (int)n);
+    for (size_t i = 0; i < n; ++i)
+        if (memchr(m.letters, m.letters[i], i)) return say("--mask-letters names '%c' twice", m.letters[i]);
     return "";
 }

@@ -61,6 +61,13 @@
 //                              device (sw_hits_threshold_device); the copy goes to the weights, the update and --out-a3m, the untouched table to the aligner
 //                              and the printer
 //     ... --score-shift N     with --evalue / --include-evalue: the histogram's bins are 2^N scores wide (0..16, default 0; 256 bins, the last one open)
+//     ... --mask              with every --search mode: after the upload the database's low-complexity regions are masked on the device
+//                              (sw_db_mask_low_complexity: SEG's first stage in integers) into a second buffer; the search, the selection, the statistics,
+//                              the alignment and the PSSM update run on the MASKED copy, so printed alignments show the mask byte -- what was scored --,
+//                              while --out-a3m writes its rows through the unmasked handle: the file carries the original letters.  One line on
+//                              stderr says how many letters of how many targets were masked.  --mask-window W (2..64, default 12), --mask-trigger MB
+//                              and --mask-extend MB (thousandths of a bit, defaults 2200 and 2500), --mask-byte C (default X), --mask-letters STR
+//                              (the alphabet, default the 20 amino acids; every other byte is no letter)
 //   smithW --search --pssm FILE DB.fa --gap-open O --gap-extend E [--top K] [--min-score S] [--align] [--search-lanes 16|32]
 //                              the ONE query is a position-specific scoring matrix, PSI-BLAST's ASCII PSSM (sw_read_pssm), searched through a prepared
 //                              handle (sw_db_search_pssm_top, sw_db_align_pssm_hits); the output is that of --all-queries for one record, the Q line of an
@@ -205,16 +212,17 @@ static int search_main(const Options& o) {
     Context ctx(0);
     if (o.align_ckpt) CHECK(sw_set_option(ctx, "align_checkpoint", 2));   // hits too large for whole direction matrices are aligned checkpointed
     DeviceBuffer d_q(ctx, q.data(), (size_t)qlen), d_db(ctx, db.letters.data(), (size_t)db.total), d_res(ctx, (size_t)(db.nrec > 0 ? db.nrec : 1) * sizeof(sw_result));
+    const MaskedDb masked(ctx, o.mask, db, d_db);   // --mask: the search, the alignment and the printer see the masked copy from here on
     const Scoring s(o.af, sc);   // (a linear search without --align does not look at it)
     const double t0 = now_s();
-    if (o.af.on) CHECK(sw_search_affine_device(ctx, d_q.as<const char>(), qlen, d_db.as<const char>(), db.offsets.data(), db.nrec, &s.aff, d_res.as<sw_result>(), nullptr));
-    else CHECK(sw_search_device(ctx, d_q.as<const char>(), qlen, d_db.as<const char>(), db.offsets.data(), db.nrec, &sc, d_res.as<sw_result>(), nullptr));
+    if (o.af.on) CHECK(sw_search_affine_device(ctx, d_q.as<const char>(), qlen, masked.buffer().as<const char>(), db.offsets.data(), db.nrec, &s.aff, d_res.as<sw_result>(), nullptr));
+    else CHECK(sw_search_device(ctx, d_q.as<const char>(), qlen, masked.buffer().as<const char>(), db.offsets.data(), db.nrec, &sc, d_res.as<sw_result>(), nullptr));
     CHECK(sw_synchronize(ctx, nullptr));
     const double t1 = now_s();
     std::vector<sw_result> res((size_t)db.nrec);
     d_res.download(res.data(), (size_t)db.nrec * sizeof(sw_result));
     const std::vector<sw_hit> hits = rank_hits(res.data(), db.nrec, o.top, 0);
-    print_hits(ctx, q.data(), qlen, d_q.as<const char>(), db, d_db, hits.data(), (long long)hits.size(), o.align, s.aff);
+    print_hits(ctx, q.data(), qlen, d_q.as<const char>(), masked.db(), masked.buffer(), hits.data(), (long long)hits.size(), o.align, s.aff);
     print_elapsed(t1 - t0, (double)qlen * (double)db.total, nullptr);
     return 0;
 }
@@ -250,12 +258,13 @@ static int search_all_main(const Options& o) {
     const size_t nres = on_device ? 1 : (size_t)std::max<int64_t>(1, nq * nrec), nhit = (size_t)std::max<int64_t>(1, nq * K);
     DeviceBuffer d_npairs(ctx, sizeof(int64_t)), d_q(ctx, qs.letters.data(), (size_t)qs.total), d_db(ctx, db.letters.data(), (size_t)db.total),
         d_res(ctx, nres * sizeof(sw_result)), d_hits(ctx, nhit * sizeof(sw_hit)), d_nhits(ctx, (size_t)std::max<int64_t>(1, nq) * sizeof(int64_t));
+    const MaskedDb masked(ctx, o.mask, db, d_db);   // --mask: the search, the alignment and the printer see the masked copy from here on
     const Scoring s(o.af, o.sc);
     ScoreStats stats;   // --evalue: the histograms of the search
     if (o.has_evalue && K > 0) stats.alloc(ctx, nq, o.score_shift);
     DbHandle handle;
     const double t0 = now_s();
-    handle.create(ctx, d_db, db.offsets, nrec);
+    handle.create(ctx, masked.buffer(), db.offsets, nrec);
     const double t1 = now_s();
     if (!on_device) CHECK(sw_db_search_affine(ctx, handle, d_q.as<const char>(), qs.offsets.data(), nq, &s.aff, d_res.as<sw_result>(), nullptr));
     else if (stats)
@@ -315,7 +324,7 @@ static int search_all_main(const Options& o) {
         const std::vector<sw_hit> ranked = on_device ? std::vector<sw_hit>() : rank_hits(res.data() + i * nrec, nrec, K, o.min_score);
         const sw_hit* row = on_device ? hits.data() + i * K : ranked.data();
         const long long n = on_device ? (long long)nhits[(size_t)i] : (long long)ranked.size();
-        print_hits(ctx, qs.record(i), qs.len(i), d_q.as<const char>() + qs.offsets[(size_t)i], db, d_db, row, n, o.align, s.aff, aligned.only_row(i, K),
+        print_hits(ctx, qs.record(i), qs.len(i), d_q.as<const char>() + qs.offsets[(size_t)i], masked.db(), masked.buffer(), row, n, o.align, s.aff, aligned.only_row(i, K),
                    stats ? keep.data() + i * K : nullptr, stats ? &stats.fit[(size_t)i] : nullptr);
     }
     const double cells = (double)qs.total * (double)db.total;
@@ -351,11 +360,12 @@ static int search_pssm_main(const Options& o) {
     const size_t nres = on_device ? 1 : (size_t)std::max<int64_t>(1, nrec), nhit = (size_t)std::max<long long>(1, K);
     DeviceBuffer d_pssm(ctx, m.matrix.data(), m.matrix.size()), d_db(ctx, db.letters.data(), (size_t)db.total), d_res(ctx, nres * sizeof(sw_result)),
         d_hits(ctx, nhit * sizeof(sw_hit)), d_nhits(ctx, sizeof(int64_t));
+    const MaskedDb masked(ctx, o.mask, db, d_db);   // --mask: the search, the alignment and the printer see the masked copy from here on
     ScoreStats stats;   // --evalue: the histogram of the search
     if (o.has_evalue && K > 0) stats.alloc(ctx, 1, o.score_shift);
     DbHandle handle;
     const double t0 = now_s();
-    handle.create(ctx, d_db, db.offsets, nrec);
+    handle.create(ctx, masked.buffer(), db.offsets, nrec);
     const double t1 = now_s();
     if (!on_device) CHECK(sw_db_search_pssm(ctx, handle, d_pssm.as<const int8_t>(), qoffs, 1, &scoring, d_res.as<sw_result>(), nullptr));
     else if (stats)
@@ -392,7 +402,7 @@ static int search_pssm_main(const Options& o) {
     }
     printf("## query record 0 of %s\n", o.pssm_path);
     const sw_affine unused = {nullptr, 0, 0};   // (print_hits aligns nothing itself when it is given the rows of a call)
-    print_hits(ctx, query.data(), ncols, nullptr, db, d_db, hits.data(), (long long)nhits, align, unused, aligned, stats ? keep.data() : nullptr,
+    print_hits(ctx, query.data(), ncols, nullptr, masked.db(), masked.buffer(), hits.data(), (long long)nhits, align, unused, aligned, stats ? keep.data() : nullptr,
                stats ? stats.fit.data() : nullptr);
     print_elapsed(t2 - t1, (double)ncols * (double)db.total, "; 1 PSSM of %lld columns over %d letters, handle prepared in %f", (long long)ncols, m.nletters, t1 - t0);
     return 0;
@@ -451,9 +461,10 @@ static int search_iter_main(const Options& o) {
     const size_t n = (size_t)(nq * K);
     DeviceBuffer d_prior(ctx, m.matrix.data(), m.matrix.size()), d_work(ctx, m.matrix.size() + 16), d_db(ctx, db.letters.data(), (size_t)db.total),
         d_hits(ctx, n * sizeof(sw_hit)), d_nhits(ctx, (size_t)nq * sizeof(int64_t)), d_aln, d_ops, d_weights;
+    const MaskedDb masked(ctx, o.mask, db, d_db);   // --mask: the search, the alignment and the printer see the masked copy from here on
     DbHandle handle;
     const double t0 = now_s();
-    handle.create(ctx, d_db, db.offsets, nrec);
+    handle.create(ctx, masked.buffer(), db.offsets, nrec);
     const int64_t ops_cap = std::max<int64_t>(1, qs.longest() + handle.longest());
     if (o.iterations > 1 || o.align) {
         if ((double)n * (double)ops_cap > (double)(1ll << 32)) { fprintf(stderr, "smithW: the ops of %zu hits x %lld bytes pass 4 GiB: lower --top\n", n, (long long)ops_cap); return 2; }
@@ -498,19 +509,20 @@ static int search_iter_main(const Options& o) {
         CHECK(sw_db_align_pssm_hits(ctx, handle, cur->as<const int8_t>(), qoffs, nq, &scoring, d_hits.as<const sw_hit>(), d_nhits.as<const int64_t>(), K,
                                     d_aln.as<sw_alignment>(), d_ops.as<char>(), ops_cap, nullptr));
     // --out-a3m: the rows of the last round's tables, still on the device: one call for the row table and the size, one for the bytes
+    // (through the handle over the letters as they were read: ops and offsets do not depend on letters, so with --mask the file keeps the original ones)
     DeviceBuffer d_qs, d_rows, d_a3m, d_a3m_bytes;
     int64_t a3m_bytes = 0;
     if (o.out_a3m) {
         if (!ppath) d_qs.alloc(ctx, qs.letters.data(), (size_t)qs.total);
         d_rows.alloc(ctx, n * sizeof(sw_msa_row));
         d_a3m_bytes.alloc(ctx, sizeof(int64_t));
-        CHECK(sw_db_msa_from_hits(ctx, handle, d_qs.as<const char>(), qoffs, nq, include_min, d_use, d_nhits.as<const int64_t>(), K,
+        CHECK(sw_db_msa_from_hits(ctx, masked.original(handle), d_qs.as<const char>(), qoffs, nq, include_min, d_use, d_nhits.as<const int64_t>(), K,
                                   d_aln.as<const sw_alignment>(), d_ops.as<const char>(), ops_cap, nullptr, d_rows.as<sw_msa_row>(), nullptr, 0, d_a3m_bytes.as<int64_t>(),
                                   nullptr));
         CHECK(sw_synchronize(ctx, nullptr));
         d_a3m_bytes.download(&a3m_bytes, sizeof a3m_bytes);
         d_a3m.alloc(ctx, (size_t)a3m_bytes + 16);
-        CHECK(sw_db_msa_from_hits(ctx, handle, d_qs.as<const char>(), qoffs, nq, include_min, d_use, d_nhits.as<const int64_t>(), K,
+        CHECK(sw_db_msa_from_hits(ctx, masked.original(handle), d_qs.as<const char>(), qoffs, nq, include_min, d_use, d_nhits.as<const int64_t>(), K,
                                   d_aln.as<const sw_alignment>(), d_ops.as<const char>(), ops_cap, nullptr, d_rows.as<sw_msa_row>(), d_a3m.as<char>(), a3m_bytes,
                                   d_a3m_bytes.as<int64_t>(), nullptr));
     }
@@ -552,7 +564,7 @@ static int search_iter_main(const Options& o) {
     const sw_affine unused = {nullptr, 0, 0};   // (print_hits aligns nothing itself when it is given the rows of a call)
     for (int64_t i = 0; i < nq; ++i) {
         printf("## query record %lld of %s\n", (long long)i, qpath);
-        print_hits(ctx, qs.record(i), qs.len(i), nullptr, db, d_db, hits.data() + i * K, (long long)nhits[(size_t)i], o.align, unused, aligned.only_row(i, K),
+        print_hits(ctx, qs.record(i), qs.len(i), nullptr, masked.db(), masked.buffer(), hits.data() + i * K, (long long)nhits[(size_t)i], o.align, unused, aligned.only_row(i, K),
                    o.has_evalue ? keep.data() + i * K : nullptr, o.has_evalue ? &stats.fit[(size_t)i] : nullptr);
         if (o.out_pssm) {
             const std::string path = std::string(o.out_pssm) + "." + std::to_string((long long)i) + ".pssm";
@@ -611,11 +623,12 @@ static int search_pairs_main(const Options& o) {
     CHECK(sw_set_option(ctx, "search_pairs_lanes", o.pairs_lanes));
     DeviceBuffer d_q(ctx, qs.letters.data(), (size_t)qs.total), d_db(ctx, db.letters.data(), (size_t)db.total),
         d_pairs(ctx, (size_t)std::max<int64_t>(1, np) * sizeof(sw_pair)), d_res(ctx, (size_t)std::max<int64_t>(1, np) * sizeof(sw_result));
+    const MaskedDb masked(ctx, o.mask, db, d_db);   // --mask: the search, the alignment and the printer see the masked copy from here on
     d_pairs.upload(pairs.data(), (size_t)np * sizeof(sw_pair));
     const Scoring s(o.af, o.sc);
     DbHandle handle;
     const double t0 = now_s();
-    handle.create(ctx, d_db, db.offsets, nrec);
+    handle.create(ctx, masked.buffer(), db.offsets, nrec);
     const double t1 = now_s();
     CHECK(sw_db_search_affine_pairs(ctx, handle, d_q.as<const char>(), qs.offsets.data(), nq, &s.aff, d_pairs.as<const sw_pair>(), np, d_res.as<sw_result>(), nullptr));
     CHECK(sw_synchronize(ctx, nullptr));
@@ -649,13 +662,14 @@ static int search_prefilter_main(const Options& o) {
                  out_bytes = o_u + (size_t)cap * sizeof(int32_t);
     Context ctx(0);
     DeviceBuffer d_q(ctx, qs.letters.data(), (size_t)qs.total), d_db(ctx, db.letters.data(), (size_t)db.total), d_out(ctx, out_bytes);
+    const MaskedDb masked(ctx, o.mask, db, d_db);   // --mask: the search, the alignment and the printer see the masked copy from here on
     const Scoring s(o.af, o.sc);
     sw_pair* d_pairs = cap ? (sw_pair*)(d_out.as<char>() + o_pairs) : nullptr;
     sw_result* d_res = cap ? (sw_result*)(d_out.as<char>() + o_res) : nullptr;
     int32_t* d_u = cap ? (int32_t*)(d_out.as<char>() + o_u) : nullptr;
     DbHandle handle;
     const double t0 = now_s();
-    handle.create(ctx, d_db, db.offsets, nrec);
+    handle.create(ctx, masked.buffer(), db.offsets, nrec);
     const double t1 = now_s();
     CHECK(sw_db_prefilter_ungapped(ctx, handle, d_q.as<const char>(), qs.offsets.data(), nq, &s.sub, o.prefilter, d_pairs, cap, d_out.as<int64_t>(), d_u, nullptr));
     CHECK(sw_db_search_affine_pairs(ctx, handle, d_q.as<const char>(), qs.offsets.data(), nq, &s.aff, d_pairs, cap, d_res, nullptr));
@@ -719,6 +733,12 @@ static int parse_options(int argc, char** argv, Options& o) {
         else if (flag("--evalue", 1)) { if (!real(&o.evalue)) return 2; o.has_evalue = true; }
         else if (flag("--include-evalue", 1)) { if (!real(&o.include_evalue)) return 2; o.has_include_evalue = true; }
         else if (flag("--score-shift", 1)) { if (!integer(&o.score_shift)) return 2; o.has_score_shift = true; }
+        else if (f == "--mask") o.mask.on = true;
+        else if (flag("--mask-window", 1)) { if (!integer(&o.mask.window)) return 2; o.mask.has_sub = true; }
+        else if (flag("--mask-trigger", 1)) { if (!integer(&o.mask.trigger)) return 2; o.mask.has_sub = true; }
+        else if (flag("--mask-extend", 1)) { if (!integer(&o.mask.extend)) return 2; o.mask.has_sub = true; }
+        else if (flag("--mask-byte", 1)) { o.mask.byte = argv[++ai]; o.mask.has_sub = true; }
+        else if (flag("--mask-letters", 1)) { o.mask.letters = argv[++ai]; o.mask.has_sub = true; }
         else if (flag("--prior-weight", 1)) { if (!integer(&o.prior_weight)) return 2; o.has_iter_flag = true; }
         else if (flag("--out-pssm", 1)) { o.out_pssm = argv[++ai]; o.has_iter_flag = true; }
         else if (flag("--out-a3m", 1)) { o.out_a3m = argv[++ai]; o.has_iter_flag = true; }
@@ -881,6 +901,7 @@ static Mode check_options(const Options& o) {
         if (!o.search_q || o.pssm_path || !(o.pairs_path || o.has_prefilter_hits)) return refuse("--pairs-lanes goes with --search --pairs or --search --all-queries --prefilter-hits");
     }
     if (const std::string why = score_stats_rule(o); !why.empty()) return refuse("%s", why.c_str());   // (the rules stand in cli_parts.h)
+    if (const std::string why = mask_rule(o); !why.empty()) return refuse("%s", why.c_str());          // (likewise)
     if (o.has_iter_flag) {   // the iterative search: many sequence queries, or one matrix
         if (!(o.search_q && (o.all_queries || o.pssm_path))) return refuse("--iterations / --include-score / --prior-weight / --out-pssm / --out-a3m go with --search --all-queries or --search --pssm");
         if (o.iterations < 1) return refuse("--iterations N needs N >= 1, got %d", o.iterations);

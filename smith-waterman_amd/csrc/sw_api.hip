@@ -219,6 +219,9 @@ int64_t sw_get_option(sw_ctx* c, const char* name) {
     if (!strcmp(name, "score_hist_copies")) return c->opt_score_hist_copies;
     if (!strcmp(name, "last_score_hist_launches")) return c->last_score_hist_launches;
     if (!strcmp(name, "last_score_hist_slices")) return c->last_score_hist_slices;
+    if (!strcmp(name, "last_mask_launches")) return c->last_mask_launches;
+    if (!strcmp(name, "last_mask_tiles")) return c->last_mask_tiles;
+    if (!strcmp(name, "mask_tile")) return swp::kMaskTile;
     if (!strcmp(name, "last_pssm_weights_launches")) return c->last_pssm_weights_launches;
     if (!strcmp(name, "last_pssm_weights_tiles")) return c->last_pssm_weights_tiles;
     if (!strcmp(name, "search_pairs_chunk")) return c->opt_search_pairs_chunk;

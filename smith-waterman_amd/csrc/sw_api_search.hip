@@ -609,7 +609,7 @@ int sw_db_create(sw_ctx* c, const char* d_db, const int64_t* offsets, int64_t nt
     HIP_TRY(hipSetDevice(c->device));
     sw_db* db = new sw_db;
     db->device = c->device; db->d_db = d_db;
-    db->ntargets = ntargets; db->nonempty = nonempty; db->longest = maxlen; db->letters = offsets[ntargets] - offsets[0];
+    db->ntargets = ntargets; db->nonempty = nonempty; db->longest = maxlen; db->letters = offsets[ntargets] - offsets[0]; db->first = offsets[0];
     {   // the offsets, for the calls that get from a target index to its bytes on the device (8 bytes per target)
         const size_t bytes = (size_t)(ntargets + 1) * sizeof(int64_t);
         hipError_t e = hipMalloc((void**)&db->d_offsets, bytes);
@@ -1153,6 +1153,53 @@ int sw_msa_filter_device(sw_ctx* c, const char* d_cols, const char* d_queries, c
         HIP_TRY(hipGetLastError());
     }
     c->last_msa_filter_launches = plan.launches; c->last_msa_filter_chunks = plan.chunks;
+    return SW_OK;
+}
+
+// The low-complexity mask of a handle's bytes (csrc/sw_mask.hip).  The host checks the rule, turns the two bounds into integers
+// (swh::check_mask_params), plans from the handle's counts (swp::plan_mask) and launches; the lengths are read on the device only.
+int sw_db_mask_low_complexity(sw_ctx* c, const sw_db* db, const sw_mask_params* params, char* d_out, int64_t* d_nmasked, void* stream_) {
+    const char* who = "sw_db_mask_low_complexity";
+    if (int rc = check_db_call(who, c, db, params && d_out)) return rc;
+    if (d_out == db->d_db) { set_err("%s: in place (d_out == the handle's bytes) is refused", who); return SW_EINVAL; }
+    int32_t bound1, bound2;
+    unsigned char cls[256];
+    if (int rc = swh::check_mask_params(who, params, &bound1, &bound2, cls)) return rc;
+    c->last_mask_launches = c->last_mask_tiles = 0;   // (a call that launches no kernel reports none)
+    swp::MaskJob mj;
+    mj.letters = db->letters; mj.ntargets = db->ntargets; mj.window = params->window; mj.count = d_nmasked != nullptr;
+    const swp::MaskPlan plan = swp::plan_mask(mj);
+    if (plan.launches == 0) return SW_OK;
+    hipStream_t stream = (hipStream_t)stream_;
+    HIP_TRY(hipSetDevice(c->device));
+    DevOrder order(c, stream, false);
+    if (order.rc) return order.rc;
+    if (int rc = c->d_mask.grow((size_t)plan.workspace_bytes, stream)) return rc;
+    swk::MaskParams kp;
+    memset(&kp, 0, sizeof kp);
+    kp.in = (const unsigned char*)db->d_db; kp.out = (unsigned char*)d_out; kp.offs = db->d_offsets; kp.ntargets = db->ntargets;
+    kp.base = db->first; kp.letters = db->letters; kp.tiles = plan.tiles;
+    if (plan.tiles) {
+        kp.low1 = (unsigned long long*)(c->d_mask + plan.low1_off); kp.low2 = (unsigned long long*)(c->d_mask + plan.low2_off);
+        kp.mask = (unsigned long long*)(c->d_mask + plan.mask_off);
+        kp.summary = (unsigned int*)(c->d_mask + plan.summary_off); kp.carry = (unsigned int*)(c->d_mask + plan.carry_off);
+    }
+    kp.window = params->window; kp.bound1 = bound1; kp.bound2 = bound2; kp.gw = swp::kMaskG[params->window];
+    kp.nletters = params->nletters; memcpy(kp.letters_, params->letters, sizeof kp.letters_);
+    kp.mask_byte = params->mask_byte; kp.nmasked = d_nmasked;
+    if (plan.tiles) {
+        hipLaunchKernelGGL(swk::sw_mask_windows, dim3((unsigned)plan.window_grid), dim3(256), 0, stream, kp);
+        HIP_TRY(hipGetLastError());
+        hipLaunchKernelGGL(swk::sw_mask_carries, dim3((unsigned)plan.carry_grid), dim3(swp::kMaskCarryThreads), 0, stream, kp);
+        HIP_TRY(hipGetLastError());
+        hipLaunchKernelGGL(swk::sw_mask_apply, dim3((unsigned)plan.apply_grid), dim3(256), 0, stream, kp);
+        HIP_TRY(hipGetLastError());
+    }
+    if (plan.count_grid) {
+        hipLaunchKernelGGL(swk::sw_mask_count, dim3((unsigned)plan.count_grid), dim3(256), 0, stream, kp);
+        HIP_TRY(hipGetLastError());
+    }
+    c->last_mask_launches = plan.launches; c->last_mask_tiles = plan.tiles;
     return SW_OK;
 }
 

@@ -34,6 +34,7 @@ SW_HIDDEN int check_msa_filter(const char* who, const int64_t* qoffsets, int64_t
 SW_HIDDEN int check_score_hist(const char* who, const void* results, int64_t nqueries, int64_t ntargets, int shift, const void* hist);   // sw_score_stats.cpp
 SW_HIDDEN int check_hits_threshold(const char* who, const void* thresholds, int64_t nqueries, int64_t ntargets, int64_t top, const void* hits,
                                    const void* hits_out, const void* keep);                          // sw_score_stats.cpp
+SW_HIDDEN int check_mask_params(const char* who, const sw_mask_params* mp, int32_t* bound1, int32_t* bound2, unsigned char (&cls)[256]);   // sw_mask_host.cpp
 SW_HIDDEN void pssm_update_table(const sw_submat* sub, const char* letters, int n, int8_t* S);        // sw_hits_host.cpp
 SW_HIDDEN int check_targets(const char* who, int64_t qlen, const int64_t* offsets, int64_t ntargets, int64_t* maxlen_out, int64_t* nonempty_out);
 }
@@ -285,6 +286,9 @@ struct SW_HIDDEN sw_ctx {
     int64_t opt_score_hist_copies = 0;
     int64_t last_score_hist_launches = 0, last_score_hist_slices = 0;
     int score_hist_lds_set = 0;         // the dynamic-LDS limit the kernel has been given (bytes)
+    // the low-complexity mask (sw_db_mask_low_complexity): the three bit arrays, the summaries and the carries of swp::plan_mask
+    Workspace<unsigned char> d_mask;
+    int64_t last_mask_launches = 0, last_mask_tiles = 0;
     // ---- placement of the output matrices (sw_place.hip)
     int64_t opt_place_hold_gib = 0;     // sw_alloc_outputs: GiB a pair of small matrices may hold beside itself where no plain candidate is good (0: none)
     int64_t opt_place_budget_ms = 1500; // sw_alloc_outputs: time the search for a P in another class of the HBM may take
@@ -301,7 +305,7 @@ struct SW_HIDDEN sw_ctx {
 struct SW_HIDDEN sw_db {
     int device = 0;
     const char* d_db = nullptr;
-    int64_t ntargets = 0, nonempty = 0, longest = 0, letters = 0;
+    int64_t ntargets = 0, nonempty = 0, longest = 0, letters = 0, first = 0;   // first: offsets[0]
     swk::SearchItem* d_items = nullptr;  // the nonempty targets, longest first (swp::search_schedule)
     int64_t* d_offsets = nullptr;        // the ntargets + 1 offsets, the caller's order
 };

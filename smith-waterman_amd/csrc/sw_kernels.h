@@ -288,6 +288,26 @@ struct HitsThresholdParams {
 };
 __global__ void sw_hits_threshold(HitsThresholdParams p);
 
+// sw_mask.hip: the low-complexity mask of a handle's bytes (sw_db_mask_low_complexity), flat over the positions 0 .. letters - 1 of the
+// concatenated targets (position p is byte offs[0] + p) in the tiles of swp::plan_mask.  sw_mask_windows: low1 / low2 bits and a
+// summary per tile; sw_mask_carries: one workgroup, the carry word of every tile; sw_mask_apply: the mask bits and the bytes;
+// sw_mask_count: the masked positions per target.
+struct MaskParams {
+    const unsigned char* in; unsigned char* out; // the handle's bytes and the masked copy, both indexed like d_db
+    const int64_t* offs; int64_t ntargets;       // the handle's ntargets + 1 offsets on the device
+    int64_t base, letters, tiles;                // offs[0]; offs[ntargets] - offs[0]; tiles of swp::kMaskTile positions
+    unsigned long long *low1, *low2, *mask;      // tiles x 64 words each: bit p % 64 of word p / 64 is position p
+    unsigned int *summary, *carry;               // per tile
+    int window, bound1, bound2, gw;              // W; D <= bound1 is low1, D <= bound2 is low2; gw = G[W]
+    int nletters; unsigned char letters_[32];    // the alphabet: class k is letters_[k]
+    unsigned int mask_byte;
+    int64_t* nmasked;                            // ntargets, or NULL
+};
+__global__ void sw_mask_windows(MaskParams p);
+__global__ void sw_mask_carries(MaskParams p);
+__global__ void sw_mask_apply(MaskParams p);
+__global__ void sw_mask_count(MaskParams p);
+
 // sw_search_pairs.hip: the scores of a device list of (query, target) pairs (sw_db_search_affine_pairs).  Per (chunk of the list, group
 // of queries) two binning launches turn the usable pairs into work items, one list per class, heaviest bucket first
 // (swp::plan_search_pairs); one launch of sw_search_affine_pairs_wave<C> per class scores them.

@@ -941,6 +941,25 @@ HitsThresholdPlan plan_hits_threshold(int64_t nqueries) {
     return p;
 }
 
+MaskPlan plan_mask(const MaskJob& j) {
+    MaskPlan p;
+    p.halo = std::clamp(j.window, 2, 64) - 1;
+    if (j.count && j.ntargets >= 1) {        // (without letters the count launch still writes its zeroes)
+        p.count_grid = std::min((j.ntargets + kMaskCountTargets - 1) / kMaskCountTargets, kPssmHitsGridMax);
+        p.launches = 1;
+    }
+    if (j.letters < 1) return p;
+    p.tiles = (j.letters + kMaskTile - 1) / kMaskTile;
+    p.words = p.tiles * kMaskTileWords;
+    p.low1_off = 0; p.low2_off = 8 * p.words; p.mask_off = 16 * p.words;
+    p.summary_off = 24 * p.words; p.carry_off = p.summary_off + 4 * p.tiles;
+    p.workspace_bytes = p.carry_off + 4 * p.tiles;
+    p.window_grid = p.apply_grid = std::min(p.tiles, kPssmHitsGridMax);
+    p.carry_grid = 1;
+    p.launches += 3;
+    return p;
+}
+
 void align_schedule(const int64_t* offsets, const int64_t* hits, int64_t nhits, swk::SearchItem* items) {
     std::vector<int64_t> order((size_t)nhits);
     for (int64_t h = 0; h < nhits; ++h) order[(size_t)h] = h;

@@ -10,6 +10,7 @@
 #include <cstdint>
 #include <vector>
 #include "sw_debug.h"
+#include "sw_mask_table.h"
 
 namespace swk {   // shared with the search kernels (sw_kernels.h)
 
@@ -693,6 +694,42 @@ ScoreHistPlan plan_score_hist(const ScoreHistJob& job);
 // ---- the thresholds of a hit table (sw_hits_threshold_device; sw_score_hist.hip): one workgroup of 256 threads per query.
 struct HitsThresholdPlan { int64_t grid = 0; int launches = 0; };
 HitsThresholdPlan plan_hits_threshold(int64_t nqueries);
+
+// ---- the low-complexity mask of a database (sw_db_mask_low_complexity; sw_mask.hip).  The work is FLAT over the `letters` concatenated
+// bytes of the handle, whatever the targets' lengths: the last W - 1 starts of every target are invalid, so a run of low windows never
+// crosses a target's end and a position needs no target index, only to know where targets end.  Tile i of the `tiles` holds the
+// positions [i x kMaskTile, min(letters, (i + 1) x kMaskTile)): every position lies in exactly one tile.  A workgroup of 256 threads
+// takes a tile (the grids are walked in strides of at most kPssmHitsGridMax workgroups); a lane of the window launch owns
+// kMaskStartsPerLane consecutive starts, so its 16 bits of an array are one half-word and need no ballot.  A tile stages its bytes and
+// a halo of W - 1 behind them.  The workspace holds per tile kMaskTileWords 64-bit words of each of three bit arrays -- low1, low2,
+// masked; bit p % 64 of word p / 64 is position p -- then one 32-bit summary and one 32-bit carry word per tile: every word of the
+// tiles at hand is written by the call before it is read, so nothing of an earlier call is seen.  Launches: windows, carries (one
+// workgroup, every thread a contiguous share of the tiles), apply, and -- only with d_nmasked -- count, 256 targets per workgroup.
+constexpr int64_t kMaskTile = 4096;
+constexpr int kMaskStartsPerLane = 16;
+constexpr int64_t kMaskTileWords = kMaskTile / 64;
+constexpr int kMaskCarryThreads = 1024;          // the one workgroup of the carry launch
+constexpr int kMaskCountTargets = 256;           // targets of a workgroup of the count launch: one per thread
+constexpr int kMaskCountLaneWords = 8;           // ... which counts a target of up to this many words alone; a longer one takes the whole wave
+constexpr int kMaskG[SW_MASK_WINDOW_MAX + 1] = {SW_MASK_G_LITERALS};   // (sw_mask_table.h; the driver hands G[W] to the kernel)
+static_assert(kMaskTile == 256 * kMaskStartsPerLane, "a workgroup of 256 lanes covers a tile");
+
+struct MaskJob {
+    int64_t letters = 0, ntargets = 0;       // of the handle
+    int window = 12;                         // 2..64
+    bool count = true;                       // d_nmasked is given
+};
+
+struct MaskPlan {
+    int64_t tile = kMaskTile; int starts_per_lane = kMaskStartsPerLane; int halo = 0;   // halo: W - 1 bytes staged behind a tile
+    int64_t tiles = 0, words = 0;            // words of ONE bit array: tiles x kMaskTileWords
+    int64_t low1_off = 0, low2_off = 0, mask_off = 0, summary_off = 0, carry_off = 0;   // byte offsets into the workspace
+    int64_t workspace_bytes = 0;
+    int64_t window_grid = 0, carry_grid = 0, apply_grid = 0, count_grid = 0;   // (0: not launched)
+    int launches = 0;                        // kernel launches of the call ("last_mask_launches")
+};
+
+MaskPlan plan_mask(const MaskJob& job);
 
 // ---- alignment of chosen hits under affine scoring (sw_align_affine_device): sw_align_affine_wave<C> for C = 4, 8, 16, its index in
 // kAlignAffine (sw_api_search.hip, which checks its order against it at compile time)
